@@ -38,6 +38,49 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy ceiling
 
+# --dump-outputs: what the timed path hands its caller after the last timed step, bounded to DUMP_BYTES_MAX in all.  Per-instance
+# vectors cover the whole batch up to DUMP_VECTOR_INSTANCES (beyond it: a seeded sample of that many), full states (x, P, landmark
+# ids) a seeded sample of at most DUMP_STATE_INSTANCES instances, fewer when one state is large.
+DUMP_BYTES_MAX = 64 << 20
+DUMP_VECTOR_INSTANCES = 131072
+DUMP_STATE_INSTANCES = 64
+
+
+def _dump_sample(n, k, seed):
+    """k of range(n) (all of it if n <= k), drawn by a fixed seed, ascending."""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def ekf_outputs(f, first):
+    """The arrays a caller of the EKF handle receives after the timed run_sim: estimated and true poses, landmark counts, status
+    flags, the average position error, and for a sample of instances the full state.  Keyed by file name, float64; instance ids
+    are global (shard offset `first` added)."""
+    B, L, n_max = f.batch, f.L_max, f.n_max
+    vec = _dump_sample(B, DUMP_VECTOR_INSTANCES, 1)
+    per_state = 8 * (n_max * n_max + n_max + L)
+    picks = _dump_sample(B, max(1, min(DUMP_STATE_INSTANCES, (DUMP_BYTES_MAX // 2) // per_state)), 2)
+    xs = np.full((picks.size, n_max), np.nan)
+    Ps = np.full((picks.size, n_max, n_max), np.nan)
+    ids = np.full((picks.size, L), -1.0)
+    for i, b in enumerate(picks):
+        s = f.get_state(int(b))
+        n = s["x"].size
+        xs[i, :n], Ps[i, :n, :n], ids[i, :s["M"]] = s["x"], s["P"], s["ids"]
+    out = {"instances": first + vec, "pose": f.poses()[vec], "truth": f.truth()[vec], "landmark_count": f.landmark_counts()[vec],
+           "status": f.status()[vec], "avg_position_error": f.error_stats()[vec],
+           "state_instances": first + picks, "state_x": xs, "state_P": Ps, "state_landmark_ids": ids}
+    return {k: np.asarray(v, dtype=np.float64) for k, v in out.items()}
+
+
+def write_outputs(outdir, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES_MAX, f"output dump of {total} bytes exceeds {DUMP_BYTES_MAX}"
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
 
 def cpu_baseline(lm, cmds, vis, L, seconds_budget=20.0):
     """The oracle timed on this box's host cores on a bounded sample of the same workload (rank 0, N=1 only).
@@ -461,7 +504,13 @@ def main():
     ap.add_argument("--no-batch-256", action="store_true", help="pgs: skip the batch-256 figure measured beside a larger batch (profiling runs)")
     ap.add_argument("--iterative", action="store_true",
                     help="pgs: the reference's default mode solve_graph_every_iteration (params.yaml:64): one run of poses - 1 ticks, each solved and adopted")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="ekf: after the timed steps write what they computed (DIR/<name>.npy, float64, <= 64 MB; rank 0's shard)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.filter != "ekf":
+        ap.error("--dump-outputs is implemented for --filter ekf only")
     if args.filter == "pgs":   # configs[4] defaults unless given explicitly
         argv = " ".join(sys.argv[1:])
         if "--landmarks" not in argv: args.landmarks = 200
@@ -695,6 +744,8 @@ def bench_ekf(args, torch, dist, rank, local_rank, world, dev, compact=False):
 
         # ---- after the timed region: parity of the timed trajectory, once-per-step leg, per-k table, long runs ----
         flags = f.status()
+        if getattr(args, "dump_outputs", None) and rank == 0 and not compact:
+            write_outputs(args.dump_outputs, ekf_outputs(f, first))   # the state after the K timed steps, before anything runs further
         picks = sorted(set([0, 1, B // 2, B - 1]))
         states = {b: f.get_state(b) for b in picks} if not args.no_parity_check else {}
         once = None

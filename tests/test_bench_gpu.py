@@ -6,6 +6,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -127,3 +128,30 @@ def test_two_ranks_over_rccl_on_one_gpu_or_the_reason_why_not():
     assert ("Duplicate GPU" in txt) or ("duplicate" in txt.lower()) or ("invalid usage" in txt.lower()), txt[-3000:]
     pytest.skip("RCCL refuses two ranks on one device (duplicate-GPU check): the nccl branch needs a multi-GPU node; "
                 "the gloo path (test_two_ranks_strong_scaling_on_one_gpu) covers the control flow")
+
+
+def test_dump_outputs_hold_the_state_after_exactly_k_timed_steps(tmp_path, oracle):
+    """--dump-outputs writes what the timed path computed in its last step: the dumped state of a sampled instance and its true pose
+    equal the oracle's after window_start + K timesteps, so --steps sets the timed steps and the dump is taken right behind them."""
+    from live_ekf_slam_amd.scenario import make_scenario
+    K, B, L, out_dir = 3, 4096, 50, tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", "2", "--batch", str(B),
+                          "--no-long-runs", "--no-cpu-baseline", "--no-once-per-step", "--no-parity-check", "--dump-outputs", str(out_dir)],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = _last_json(out.stdout)
+    a = {p.stem: np.load(p) for p in out_dir.glob("*.npy")}
+    assert {"instances", "pose", "truth", "landmark_count", "status", "avg_position_error", "state_instances", "state_x", "state_P"} <= set(a)
+    assert all(v.dtype == np.float64 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert np.array_equal(a["instances"], np.arange(B)) and np.all(a["status"] == 0)
+    T = d["config"]["window_start"] + K
+    lm, cmds = make_scenario(1234, L, T)
+    vis = np.tile([3.0, -1.57, 1.57], (T, 1)); vis[0] = [1e9, -4.0, 4.0]
+    for i in (0, a["state_instances"].size - 1):
+        b = int(a["state_instances"][i])
+        r = oracle.run_ekf_batch(lm, cmds, 1, L, seed=2025, inst0=b, mode=oracle.MODE_FAST, vision=vis)
+        n = 3 + 2 * int(r["M"][0])
+        assert np.array_equal(a["state_x"][i, :n], r["x"][0, :n]), f"instance {b}"
+        assert np.array_equal(a["state_P"][i, :n, :n].ravel(), r["P"][0, :n * n]), f"instance {b}"
+        assert np.array_equal(a["truth"][b], r["truth"][0]) and np.array_equal(a["pose"][b], r["x"][0, :3])
+        assert a["avg_position_error"][b] == r["avg_err"][0] and a["landmark_count"][b] == r["M"][0]
