@@ -255,6 +255,27 @@ int slam_k_histogram(slam_handle* h, uint64_t out[8], int reset);
  * by the square-root kernel since slam_create or the last reset: out[0] / out[1] is the mean number of sweeps the
  * `nearestSPD` + `.sqrt()` of ukf.cpp:106-123,208 took, which sets the arithmetic of a UKF step.  Synchronises. */
 int slam_ukf_sweep_stats(slam_handle* h, uint64_t out[2], int reset);
+/* UKF matrix square root of every step (UKF_SLAM and UKF_LOC handles).
+ * SLAM_UKF_SQRT_EIGEN (default): nearestSPD + `.sqrt()` of ukf.cpp:106-123,208, a symmetric eigen-decomposition, bit-identical to the
+ *   reference.
+ * SLAM_UKF_SQRT_CHOLESKY: an opt-in mode that is NOT bit-identical to the reference and pays off only where P is positive
+ *   definite, which the reference's signed process noise (ukf.cpp:183-186) rarely leaves: on the reference configuration most steps
+ *   fall back and the mode is SLOWER than the default.  Each step forms
+ *   Y = 0.5 (P + P^T) * float((2M+4)/(1-W_0)) exactly as nearestSPD does, factors Y = L L^T with a lower-triangular L and takes the
+ *   columns of L as the sigma-point offsets, X_i = x +- L(:, i-1).  L L^T = Y gives sigma points with the same first two moments as the
+ *   symmetric root.  sqtP (slam_get_sigma_points) then holds L^T row-major, zeros below its diagonal.  If a pivot
+ *   d_k = Y_kk - sum_j L_kj^2 is <= 1e-8 (the floor of nearestSPD's cwiseMax) or not finite, that instance takes the eigen path for
+ *   that step, starting Jacobi cold: every Cholesky step discards the warm-start eigenvectors.  Such a fallback is counted, not
+ *   flagged (the step succeeded).  Everything after the square root is unchanged.  The mode persists until set again and is not
+ *   part of a state file.  A handle that has taken Cholesky steps is no longer bit-identical to the reference after switching back
+ *   (its warm start was reset).
+ * Returns SLAM_ERR_ARG for EKF handles or an unknown mode, SLAM_ERR_UNSUPPORTED for the Cholesky mode on the HBM-streamed size class
+ * (UKF_SLAM with L_max > 50), which has no Cholesky kernel. */
+enum slam_ukf_sqrt_mode { SLAM_UKF_SQRT_EIGEN = 0, SLAM_UKF_SQRT_CHOLESKY = 1 };
+int slam_ukf_set_sqrt_mode(slam_handle* h, int mode);
+/* UKF handles: out[0] = Cholesky factorisations that succeeded, out[1] = instance-steps that fell back to the eigen path, since
+ * slam_create or the last reset (also zeroed by slam_reset_counters_async).  SLAM_ERR_ARG for EKF handles.  Synchronises. */
+int slam_ukf_sqrt_stats(slam_handle* h, uint64_t out[2], int reset);
 /* EKF handles: what the step kernels moved through global memory, counted ON THE DEVICE (one accumulation per pass and
  * workgroup, summed per launch like the k histogram) since slam_create or the last reset: out[0] = bytes the passes of the
  * P stream read + wrote (`P -= K (H P)`, ekf.cpp:140, applied for a group of deferred updates at once), out[1] = every other

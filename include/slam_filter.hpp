@@ -9,6 +9,7 @@
 // they are replaced by base_pkg::Command / std_msgs::Float32MultiArray via the two typedefs below
 // (INTEGRATION.md §2).
 #pragma once
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <memory>
@@ -238,6 +239,12 @@ public:
         return s;
     }
     std::vector<double> errorStats() { need(); std::vector<double> e(batch_); check(slam_error_stats(h_, e.data())); return e; }
+    // SLAM_UKF_SQRT_EIGEN (default, bit-identical to the reference) or SLAM_UKF_SQRT_CHOLESKY (not bit-identical; L_max <= 50;
+    // faster only where P stays positive definite, slower on the reference configuration):
+    // include/slam_batch.h.  readParams() creates a new handle, which starts in SLAM_UKF_SQRT_EIGEN.
+    void setSqrtMode(int mode) { need(); check(slam_ukf_set_sqrt_mode(h_, mode)); }
+    // {Cholesky factorisations that succeeded, instance-steps that fell back to the eigen path}
+    std::array<uint64_t, 2> sqrtStats(bool reset = false) { need(); std::array<uint64_t, 2> s{}; check(slam_ukf_sqrt_stats(h_, s.data(), reset ? 1 : 0)); return s; }
     slam_handle* handle() { return h_; }
     UKFState last_state;
 

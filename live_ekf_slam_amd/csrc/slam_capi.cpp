@@ -141,6 +141,7 @@ struct slam_handle {
     double* dvt = nullptr; int32_t* dvage = nullptr;  // UKF: V^T of the last eigen-decomposition + warm-start age
     double* dbigws = nullptr;                         // UKF beyond the LDS size classes: [B][2 * pstride] scratch (ukf_big_kernel.hip)
     uint4* drot = nullptr;                            // UKF (n <= 44): pass table of the fast sqrt kernel (launch_ukf_quad_table)
+    uint8_t* dchol = nullptr; bool chol = false;      // UKF: SLAM_UKF_SQRT_CHOLESKY is on; [B] "the Cholesky factor succeeded" (ukf_chol_kernel)
     hipStream_t aux_stream[3] = {nullptr, nullptr, nullptr}; hipEvent_t aux_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // UKF run_sim: the other parts of the batch
     int ukf_parts = 2;                                                               // streams the UKF batch is split over (SLAM_UKF_PARTS, 1..4)
     int ukf_split_min = 1024;                                                        // batch size from which it is used
@@ -202,6 +203,7 @@ void fill_ukf_params(slam_handle* h, slam::UkfStepParams& p, const float cmd[2])
     p.khist = h->dkhist;
     p.big_ws = h->dbigws;
     p.prof = (h->dbg & 4) ? h->dprof : nullptr;
+    p.chol_ok = h->chol ? h->dchol : nullptr;
 }
 
 // ekf.cpp:65,73 and ukf.cpp:249-287 walk a message of any length.  The LDS size classes hold as many detections of one message as the class
@@ -456,7 +458,7 @@ int slam_destroy(slam_handle* h) {
         if (s.copied) hipEventDestroy(s.copied);
         if (s.used) hipEventDestroy(s.used);
     }
-    void* bufs[] = {h->dP, h->dP2, h->dx, h->dM, h->dids, h->dflags, h->dts, h->dtruth, h->derr, h->dmap, h->dmeas, h->dcount, h->dscalar, h->dprof, h->dsq, h->dnsq, h->dscratch, h->dmapf, h->dcmds, h->dxprev, h->dvt, h->dvage, h->dkhist, h->drot, h->dbigws};
+    void* bufs[] = {h->dP, h->dP2, h->dx, h->dM, h->dids, h->dflags, h->dts, h->dtruth, h->derr, h->dmap, h->dmeas, h->dcount, h->dscalar, h->dprof, h->dsq, h->dnsq, h->dscratch, h->dmapf, h->dcmds, h->dxprev, h->dvt, h->dvage, h->dkhist, h->drot, h->dbigws, h->dchol};
     for (void* q : bufs)
         if (q) hipFree(q);
     if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
@@ -941,7 +943,7 @@ int slam_update_dev(slam_handle* h, const float* d_meas, const int32_t* d_count,
 }
 
 // UKFState.X (ukf.cpp:92-101): the sigma points of the last predictionStage, column-major n x (2n+1):
-// X = [x, x + sqtP(:,i), x - sqtP(:,i)] (ukf.cpp:214-219) around the x_t that step started from.
+// X = [x, x + offset i, x - offset i] with offset i = row i of sqtP (ukf.cpp:214-219) around the x_t that step started from.
 int slam_get_sigma_points(slam_handle* h, int inst, double* X, int32_t* rows, int32_t* cols) {
     if (!h || inst < 0 || inst >= h->B) return fail(SLAM_ERR_ARG, "bad instance");
     FLUSH(h);
@@ -958,11 +960,13 @@ int slam_get_sigma_points(slam_handle* h, int inst, double* X, int32_t* rows, in
     std::vector<double> x(n), S((size_t)n * n);
     HIP_TRY(hipMemcpy(x.data(), h->dxprev + (size_t)inst * h->xstride, sizeof(double) * n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(S.data(), h->dsq + (size_t)inst * h->pstride, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost));
+    // offset i = row i of sqtP, as ukf_step_kernel reads it: the symmetric eigen root (both halves written from one value) or, in
+    // SLAM_UKF_SQRT_CHOLESKY mode, L^T row-major, whose row i is column i of L
     for (int r = 0; r < n; ++r) X[r] = x[r];
     for (int i = 0; i < n; ++i)
         for (int r = 0; r < n; ++r) {
-            X[(size_t)(1 + i) * n + r] = x[r] + S[(size_t)r * n + i];
-            X[(size_t)(1 + n + i) * n + r] = x[r] - S[(size_t)r * n + i];
+            X[(size_t)(1 + i) * n + r] = x[r] + S[(size_t)i * n + r];
+            X[(size_t)(1 + n + i) * n + r] = x[r] - S[(size_t)i * n + r];
         }
     return SLAM_OK;
 }
@@ -1321,6 +1325,31 @@ int slam_ukf_sweep_stats(slam_handle* h, uint64_t out[2], int reset) {
     HIP_TRY(hipDeviceSynchronize());   // the UKF splits large batches over two streams
     HIP_TRY(hipMemcpy(out, h->dkhist + 8, sizeof(uint64_t) * 2, hipMemcpyDeviceToHost));
     if (reset) HIP_TRY(hipMemset(h->dkhist + 8, 0, sizeof(uint64_t) * 2));
+    return SLAM_OK;
+}
+
+int slam_ukf_set_sqrt_mode(slam_handle* h, int mode) {
+    if (!h) return fail(SLAM_ERR_ARG, "bad argument");
+    if (h->kind == SLAM_EKF_SLAM) return fail(SLAM_ERR_ARG, "the square-root mode is a UKF setting");
+    if (mode != SLAM_UKF_SQRT_EIGEN && mode != SLAM_UKF_SQRT_CHOLESKY) return fail(SLAM_ERR_ARG, "unknown square-root mode %d", mode);
+    if (mode == SLAM_UKF_SQRT_CHOLESKY && h->L_max > slam::kUkfLdsMaxLandmarks)
+        return fail(SLAM_ERR_UNSUPPORTED, "the Cholesky square root exists for the LDS size classes only (L_max <= %d), this handle has L_max %d",
+                    slam::kUkfLdsMaxLandmarks, h->L_max);
+    FLUSH(h);
+    HIP_TRY(hipSetDevice(h->device));
+    if (mode == SLAM_UKF_SQRT_CHOLESKY && !h->dchol) HIP_TRY(hipMalloc(&h->dchol, (size_t)h->B));
+    h->chol = mode == SLAM_UKF_SQRT_CHOLESKY;
+    return SLAM_OK;
+}
+
+int slam_ukf_sqrt_stats(slam_handle* h, uint64_t out[2], int reset) {
+    if (!h || !out) return fail(SLAM_ERR_ARG, "bad argument");
+    if (h->kind == SLAM_EKF_SLAM) return fail(SLAM_ERR_ARG, "UKF handles only");
+    FLUSH(h);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());   // the UKF splits large batches over two streams
+    HIP_TRY(hipMemcpy(out, h->dkhist + slam::kUkfCholSlot, sizeof(uint64_t) * 2, hipMemcpyDeviceToHost));
+    if (reset) HIP_TRY(hipMemset(h->dkhist + slam::kUkfCholSlot, 0, sizeof(uint64_t) * 2));
     return SLAM_OK;
 }
 

@@ -274,8 +274,8 @@ __global__ __launch_bounds__(kTpb) void ukf_big_step_kernel(const UkfStepParams 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             if (i == 0) v[r] = s_xt[r];
-            else if (i <= n) v[r] = s_xt[r] + Sq[(size_t)r * n + (i - 1)];
-            else v[r] = s_xt[r] - Sq[(size_t)r * n + (i - 1 - n)];
+            else if (i <= n) v[r] = s_xt[r] + Sq[(size_t)(i - 1) * n + r];
+            else v[r] = s_xt[r] - Sq[(size_t)(i - 1 - n) * n + r];
         }
         const float yaw = yawf(v[2], v[3]);
         double sy, cy;
@@ -296,11 +296,13 @@ __global__ __launch_bounds__(kTpb) void ukf_big_step_kernel(const UkfStepParams 
     __syncthreads();
     const double w0 = (double)kW0b;
     const double wi = (double)((1 - kW0b) / (2 * n));   // float arithmetic (ukf.cpp:174-175)
+    // sigma-point offset i - 1 = ROW i - 1 of sqtP, as ukf_step_kernel reads it: the symmetric eigen root (both halves written from one
+    // value, so rows and columns are the same bits) or, in SLAM_UKF_SQRT_CHOLESKY mode on a long-message launch of an LDS class, L^T
     auto xel = [&](int r, int i) -> double {   // X_pred(r, i): rows 0..3 from the motion model, rows >= 4 = the sigma point itself
         if (r < 4) return s_X4[r * ns + i];
         if (i == 0) return s_xt[r];
-        if (i <= n) return s_xt[r] + Sq[(size_t)r * n + (i - 1)];
-        return s_xt[r] - Sq[(size_t)r * n + (i - 1 - n)];
+        if (i <= n) return s_xt[r] + Sq[(size_t)(i - 1) * n + r];
+        return s_xt[r] - Sq[(size_t)(i - 1 - n) * n + r];
     };
     // ---- weighted mean (ukf.cpp:228-232), sequential in i ----
     for (int r = tid; r < n; r += kTpb) {

@@ -63,6 +63,10 @@ struct UkfStepParams {
     // message exceeds long_cap untouched, with ukf_big_step_kernel for exactly those (long_mode = 2 inside that launch); in SIM mode, where the
     // count is not known before the generator has run, the streamed kernel takes the whole launch.  The sqrt kernel is the class's own either way.
     int32_t long_mode, long_cap;
+    // SLAM_UKF_SQRT_CHOLESKY (slam_ukf_set_sqrt_mode): [B] per-instance byte, 1 = ukf_chol_kernel factored Y = L L^T this step and
+    // wrote sqtP = L^T, 0 = a pivot <= 1e-8 or non-finite, the eigen kernel that follows computes sqtP cold.  NULL = the eigen path
+    // (the default, reference-exact): launch_ukf_sqrt then launches exactly what it launched before the mode existed.
+    uint8_t* chol_ok;
 };
 // detections ONE message may hold in the LDS size class of the step kernel (launch_ukf_step picks the class the same way)
 inline int ukf_class_message_capacity(int L_max, bool loc, int L_map) { return ((loc && L_map > 20) ? 104 : 4 + 2 * L_max) <= 44 ? 20 : 50; }
@@ -78,6 +82,10 @@ static constexpr int kUkfMaxLandmarks = 200;     // beyond: ukf_big_kernel.hip, 
 hipError_t launch_ukf_big_sqrt(const UkfStepParams& p, hipStream_t stream);
 hipError_t launch_ukf_big_step(const UkfStepParams& p, hipStream_t stream);
 
+// SLAM_UKF_SQRT_CHOLESKY: khist[kUkfCholSlot] = Cholesky factors that succeeded, khist[kUkfCholSlot + 1] = eigen fallbacks
+static constexpr int kUkfCholSlot = 14;
+// Eigen mode: ukf_sqrt_kernel.  Cholesky mode (p.chol_ok != NULL, LDS classes only): ukf_chol_kernel, then ukf_sqrt_kernel for the
+// instances whose factorisation failed (the others leave at once), in stream order without a host synchronisation.
 hipError_t launch_ukf_sqrt(const UkfStepParams& p, hipStream_t stream);
 hipError_t launch_ukf_step(const UkfStepParams& p, hipStream_t stream);
 

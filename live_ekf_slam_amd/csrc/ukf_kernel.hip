@@ -209,6 +209,7 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 256 && !PROF) ? SLAM_UKF
     __shared__ int s_pass_flag;                                    // passes without the table: wavefront 1 -> wavefront 0, "critical blocks of pass # written"
 
     const int b = blockIdx.x + p.b_off, tid = threadIdx.x;
+    if (p.chol_ok != nullptr && p.chol_ok[b]) return;   // Cholesky mode: ukf_chol_kernel already wrote this instance's sqtP
     const int M = p.M[b];
     const int n = 4 + 2 * M, m = n / 2;
     const double* __restrict__ Pb = p.P + (size_t)b * p.pstride;
@@ -876,6 +877,72 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 256 && !PROF) ? SLAM_UKF
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Cholesky square root (SLAM_UKF_SQRT_CHOLESKY: opt-in, NOT bit-identical to the reference)
+// ------------------------------------------------------------------------------------------------------------------
+// Y = 0.5 (P + P^T) * scale, formed exactly as ukf_sqrt_kernel forms it, is factored Y = L L^T right-looking in a packed lower
+// triangle in LDS: per column k the pivot d_k = Y_kk - sum_j L_kj^2 (accumulated by the earlier trailing updates), the column
+// divided by sqrt(d_k), then the rank-1 update of the trailing triangle, one work item per element through a table of the
+// (row, column) pairs of a packed triangle.  Two barriers per column; with one wavefront per workgroup (n <= 44) they are cheap.
+// n^3 / 6 fma against the Jacobi sweeps plus the n^3 reconstruction of the eigen path.
+// sqtP = L^T row-major with explicit zeros below the diagonal: row i of sqtP is column i of L, which is what ukf_step_kernel and
+// slam_get_sigma_points take as sigma-point offset i (both read rows of sqtP, valid for the symmetric eigen root and for L^T).
+// A pivot <= 1e-8 (the floor of nearestSPD's cwiseMax) or a non-finite one leaves sqtP alone and marks the instance for the
+// eigen kernel launched next.  Either way the warm-start V^T is declared stale (v_age = -1), so a fallback starts Jacobi cold.
+template <int NMAX, int TPB>
+__global__ __launch_bounds__(TPB) void ukf_chol_kernel(const UkfStepParams p) {
+    static_assert(NMAX < 256, "the (row, column) table packs both into one byte each");
+    constexpr int NT = NMAX * (NMAX + 1) / 2;
+    __shared__ double sA[NT];          // A(r, c), r >= c, at r (r + 1) / 2 + c; column k becomes L(:, k) below the diagonal
+    __shared__ uint16_t s_rc[NT];      // packed index e -> (r << 8) | c
+    __shared__ double s_ld[NMAX];      // L(k, k)
+    const int b = blockIdx.x + p.b_off, tid = threadIdx.x;
+    const int M = p.M[b];
+    const int n = 4 + 2 * M, nt = n * (n + 1) / 2;
+    const double* __restrict__ Pb = p.P + (size_t)b * p.pstride;
+    const double scale = (double)((float)(2 * M + 4) / (1 - kW0));   // ukf.cpp:114, evaluated in float, as ukf_sqrt_kernel
+#pragma unroll 4
+    for (int e = tid; e < nt; e += TPB) {
+        int r = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);   // row of packed index e, corrected for rounding
+        r -= r * (r + 1) / 2 > e;
+        r += (r + 1) * (r + 2) / 2 <= e;
+        const int c = e - r * (r + 1) / 2;
+        sA[e] = (0.5 * (Pb[(size_t)r * n + c] + Pb[(size_t)c * n + r])) * scale;
+        s_rc[e] = (uint16_t)((r << 8) | c);
+    }
+    __syncthreads();
+    bool ok = true;
+#pragma unroll 1
+    for (int k = 0; k < n; ++k) {
+        const double d = sA[k * (k + 1) / 2 + k];   // every thread reads the same pivot: the branch is uniform
+        if (!(d > 0.00000001 && d < HUGE_VAL)) { ok = false; break; }
+        const double lkk = sqrt(d);
+        if (tid == 0) s_ld[k] = lkk;
+        for (int i = k + 1 + tid; i < n; i += TPB) sA[i * (i + 1) / 2 + k] /= lkk;
+        __syncthreads();
+        const int m = n - 1 - k, mt = m * (m + 1) / 2;   // trailing triangle: element (k + 1 + ii, k + 1 + jj) for packed (ii, jj)
+        for (int e = tid; e < mt; e += TPB) {
+            const int rc = s_rc[e], i = k + 1 + (rc >> 8), j = k + 1 + (rc & 255);
+            const int ri = i * (i + 1) / 2;
+            sA[ri + j] = fma(-sA[ri + k], sA[j * (j + 1) / 2 + k], sA[ri + j]);
+        }
+        __syncthreads();
+    }
+    if (ok) {
+        double* __restrict__ Sq = p.sqtP + (size_t)b * p.pstride;
+        for (int e = tid; e < n * n; e += TPB) {
+            const int r = e / n, c = e - r * n;   // sqtP(r, c) = L(c, r)
+            Sq[e] = c > r ? sA[c * (c + 1) / 2 + r] : (c == r ? s_ld[r] : 0.0);
+        }
+    }
+    if (tid == 0) {
+        p.v_age[b] = -1;
+        p.chol_ok[b] = ok ? 1 : 0;
+        if (ok) p.n_sq[b] = n;
+        if (p.khist) atomicAdd(&p.khist[kUkfCholSlot + (ok ? 0 : 1)], 1ull);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // prediction + update
 // ------------------------------------------------------------------------------------------------------------------
 // PROF: phase timers compiled in (own instantiation, launched only with the debug buffer attached; as a run-time option
@@ -1367,6 +1434,13 @@ static int env_tpb(int which, int dflt) {
 
 hipError_t launch_ukf_sqrt(const UkfStepParams& p, hipStream_t stream) {
     const int nmax = 4 + 2 * p.L_max;
+    if (p.chol_ok != nullptr) {   // Cholesky mode: the factor first; the eigen kernel below then only runs the instances it refused
+        if (nmax <= 44) hipLaunchKernelGGL((ukf_chol_kernel<44, 64>), dim3(p.b_cnt), dim3(64), 0, stream, p);
+        else if (nmax <= 104) hipLaunchKernelGGL((ukf_chol_kernel<104, 256>), dim3(p.b_cnt), dim3(256), 0, stream, p);
+        else return hipErrorInvalidValue;   // the HBM-streamed class has no Cholesky kernel (slam_ukf_set_sqrt_mode refuses it)
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
     if (nmax <= 44) {
         switch (env_tpb(0, 256)) {
             case 128: hipLaunchKernelGGL((ukf_sqrt_kernel<44, 128>), dim3(p.b_cnt), dim3(128), 0, stream, p); break;

@@ -317,6 +317,25 @@ class BatchedUKF(BatchedFilter):
         _lib.check(_lib.lib().slam_update_dev(self.h, C.c_void_p(d_meas_ptr), C.c_void_p(d_count_ptr), int(k_stride)))
         self.timestep += 1
 
+    SQRT_MODES = {"eigen": 0, "cholesky": 1}   # SLAM_UKF_SQRT_EIGEN / SLAM_UKF_SQRT_CHOLESKY (include/slam_batch.h)
+
+    def set_sqrt_mode(self, mode):
+        """Matrix square root of every following step: "eigen" (default; nearestSPD + sqrt of ukf.cpp:106-123,208, bit-identical to
+        the reference) or "cholesky" (opt-in, NOT bit-identical: Y = L L^T, the columns of L as sigma-point offsets,
+        eigen fallback for a pivot <= 1e-8).  It pays off only where P stays positive definite, which the reference's signed process
+        noise rarely leaves: on the reference configuration it is slower than "eigen" (DESIGN.md 4.2a).  L_max <= 50 only; readParams()
+        creates a new handle, which starts in "eigen"."""
+        self._need()
+        if mode not in self.SQRT_MODES:
+            raise ValueError(f"unknown square-root mode {mode!r}: one of {sorted(self.SQRT_MODES)}")
+        _lib.check(_lib.lib().slam_ukf_set_sqrt_mode(self.h, self.SQRT_MODES[mode]))
+
+    def sqrt_stats(self, reset=False):
+        """(Cholesky factorisations that succeeded, instance-steps that fell back to the eigen path) since creation / the last reset."""
+        self._need(); out = np.zeros(2, dtype=np.uint64)
+        _lib.check(_lib.lib().slam_ukf_sqrt_stats(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)), int(bool(reset))))
+        return out
+
     def sigma_points(self, instance=0):
         """X of the last prediction stage, shape (n, 2n+1) (ukf.cpp:214-219)."""
         self._need()
