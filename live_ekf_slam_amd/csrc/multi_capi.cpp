@@ -20,7 +20,7 @@ struct slam_multi {
     void* rccl = nullptr;
     std::vector<void*> comms;
     std::vector<hipStream_t> cstream;
-    std::vector<double*> dsend, drecv;
+    std::vector<DevBuf<double>> dsend, drecv;   // on device dev[s]
     int64_t pad = 0;
 };
 
@@ -83,8 +83,7 @@ int slam_multi_destroy(slam_multi* m) {
     if (!m) return SLAM_OK;
     for (size_t s = 0; s < m->dsend.size(); ++s) {
         hipSetDevice(m->dev[s]);
-        if (m->dsend[s]) hipFree(m->dsend[s]);
-        if (m->drecv[s]) hipFree(m->drecv[s]);
+        m->dsend[s].reset(); m->drecv[s].reset();
         if (m->cstream[s]) hipStreamDestroy(m->cstream[s]);
     }
     if (m->rccl) {
@@ -156,16 +155,13 @@ int slam_multi_error_stats(slam_multi* m, double* out, int mode) {
         int64_t pad = 0;
         for (int s = 0; s < n; ++s) pad = m->count[s] > pad ? m->count[s] : pad;   // equal-sized contributions (ragged shards are padded)
         std::vector<hipStream_t> cstream(n, nullptr);
-        std::vector<double*> dsend(n, nullptr), drecv(n, nullptr);
+        std::vector<DevBuf<double>> dsend(n), drecv(n);   // (released by their destructors if a step fails)
         bool ok = true;
         for (int s = 0; s < n && ok; ++s)
             ok = hipSetDevice(m->dev[s]) == hipSuccess && hipStreamCreateWithFlags(&cstream[s], hipStreamNonBlocking) == hipSuccess &&
-                 hipMalloc(&dsend[s], sizeof(double) * pad) == hipSuccess && hipMalloc(&drecv[s], sizeof(double) * pad * n) == hipSuccess;
+                 dsend[s].reserve((size_t)pad) == hipSuccess && drecv[s].reserve((size_t)pad * n) == hipSuccess;
         if (!ok) {
             for (int s = 0; s < n; ++s) {
-                hipSetDevice(m->dev[s]);
-                if (dsend[s]) hipFree(dsend[s]);
-                if (drecv[s]) hipFree(drecv[s]);
                 if (cstream[s]) hipStreamDestroy(cstream[s]);
                 if (comm_destroy && comms[s]) comm_destroy(comms[s]);
             }

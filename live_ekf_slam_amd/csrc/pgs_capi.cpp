@@ -16,15 +16,6 @@
 #include "pgs_kernel.h"
 
 #define fail slam_internal_fail
-// (The runtime's "last error" is sticky and per thread: a launcher that ends in hipGetLastError() would report an error some OTHER library
-// of the process left behind - PyTorch creating a stream right before slam_init did exactly that in a test.  It is cleared before every
-// call; our own calls are all checked through their return values.)
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        (void)hipGetLastError();                                                                   \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(SLAM_ERR_HIP, "%s -> %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 struct pgs_handle {
     slam_config cfg;
@@ -36,29 +27,32 @@ struct pgs_handle {
     uint64_t seed = 2025;
     int64_t inst0 = 0;
     slam::PgsParams p;
-    std::vector<void*> allocs;
-    float* dcmds = nullptr;
-    float* dmeas = nullptr; int32_t* dcount = nullptr; double* dsec = nullptr; int k_stride = 0;
-    double* dout = nullptr;
+    // The device arrays behind p's pointer fields, each with the address of the field it backs (bind_arrays writes it).  slot_bytes > 0:
+    // a per-slot array the clones (lambda lanes) get a copy of when a solve begins (clone_instances / clone_listed), bytes per slot.
+    struct Array { DevBuf<char> buf; void** field; size_t slot_bytes; };
+    std::vector<Array> arrays;                 // sized by pgs_create
+    std::vector<Array> seg_arrays;             // sized for segments of seg_alloc poses (segT joins on first use): replaced as a whole by resize_segments
+    DevBuf<double> map;                        // p.map
+    DevBuf<float> dcmds;                       // p.cmds
+    DevBuf<float> dmeas; DevBuf<int32_t> dcount; DevBuf<double> dsec;   // pgs_update's staging
+    DevBuf<double> dout;
     int max_trials = 400;
     int lanes = 4;                             // slots per instance for speculative lambda lanes (SLAM_PGS_LANES, 1 = off)
     int lanes_switch_all = 16;                 // ... from which down ALL lanes are used (SLAM_PGS_LANES_SWITCH_ALL)
     int lanes_switch = 64;                     // active instances (of the whole batch) from which down the lanes are used (SLAM_PGS_LANES_SWITCH)
-    struct Slab { void* ptr; size_t bytes; };  // per-slot arrays the clones need a copy of when a solve begins (bytes per slot)
-    std::vector<Slab> clone_slabs;
     // solve groups: the batch is split into `groups` contiguous ranges whose LM loops run on their own streams, so
     // the latency-bound phases of one group overlap the bandwidth-bound phases of another (0 = choose from the batch)
     int groups = 0;
     std::vector<hipStream_t> gstreams;
     std::vector<hipEvent_t> gevents;
-    int32_t* h_active = nullptr;               // pinned host: per-group active counts
+    PinnedDefaultBuf<int32_t> h_active;        // pinned host: per-group active counts
     // streaming (round 6, pgs_kernel.h "streaming"): at most `slots` graphs of the batch are in flight (0 = lockstep: all of them), split over
     // the solve groups; trials are enqueued `stream_depth` ahead of the host's reading of their counters
     int slots = 0, stream_depth = 3;
     static constexpr int kRing = 8, kMaxGroups = 16;
-    int32_t* d_cnt = nullptr;                  // device [kMaxGroups][2][8]: the counter blocks, ping-pong by trial parity
-    int32_t* d_wait = nullptr;                 // device [kMaxGroups]: the groups' wait cursors
-    int32_t* h_ring = nullptr;                 // pinned host [kMaxGroups][kRing][8]
+    DevBuf<int32_t> d_cnt;                     // device [kMaxGroups][2][8]: the counter blocks, ping-pong by trial parity
+    DevBuf<int32_t> d_wait;                    // device [kMaxGroups]: the groups' wait cursors
+    PinnedDefaultBuf<int32_t> h_ring;          // pinned host [kMaxGroups][kRing][8]
     std::vector<hipEvent_t> ring_events;       // [kMaxGroups][kRing]
     std::vector<std::vector<int32_t>> timeline;   // per group: slots that ran in every trial of the last solve
     // asynchronous ticks (pgs_run_sim_every_iteration; pgs_kernel.h "asynchronous ticks")
@@ -66,13 +60,13 @@ struct pgs_handle {
     // against 15.0 k graph-ticks/s) - a run lasts as long as its HARDEST graph's dependent chain of lambda trials (42 per tick for the slowest of
     // 256 graphs, median 3: profiles/r06_pgs/iterative_mode.txt), which the lockstep loop shortens with its speculative lambda lanes
     int iter_async = 0;
-    int32_t* d_Nv = nullptr;                   // [slots + 1] poses per graph
-    int32_t* d_mono = nullptr;                 // [2]
+    DevBuf<int32_t> d_Nv;                      // [slots + 1] poses per graph
+    DevBuf<int32_t> d_mono;                    // [2]
     hipStream_t tick_stream = nullptr;
     std::vector<hipEvent_t> async_events;      // [2 * kRing + 1]: decide done, tick step done (rings), start
     long long async_trials = 0;
-    double* d_tick_flop = nullptr;             // [B][2] algorithmic FLOP (SYRK | Cholesky) of the same
-    int32_t* d_tick = nullptr;                 // [B][2] LM iterations / trials summed over the ticks of pgs_run_sim_every_iteration
+    DevBuf<double> d_tick_flop;                // [B][2] algorithmic FLOP (SYRK | Cholesky) of the same
+    DevBuf<int32_t> d_tick;                    // [B][2] LM iterations / trials summed over the ticks of pgs_run_sim_every_iteration
     double iter_ms[4] = {0, 0, 0, 0};
     bool host_prof = false;                    // SLAM_PGS_HOST_PROF: host clock spent enqueuing trials / waiting for their counters (stderr, every-iteration runs)
     double host_launch_ms = 0.0, host_wait_ms = 0.0;
@@ -108,26 +102,43 @@ struct pgs_handle {
 
 namespace {
 
+// a device array of `count` T (at least one) for the field *field into `set`; per_slot > 0: a per-slot array of per_slot T the clones copy
 template <class T>
-int dalloc(pgs_handle* h, T** out, size_t count) {
-    void* ptr = nullptr;
-    HIP_TRY(hipMalloc(&ptr, sizeof(T) * (count ? count : 1)));
-    h->allocs.push_back(ptr);
-    *out = (T*)ptr;
+int add_array(std::vector<pgs_handle::Array>& set, T** field, size_t count, size_t per_slot = 0) {
+    pgs_handle::Array a{{}, (void**)field, per_slot * sizeof(T)};
+    HIP_TRY(a.buf.reserve(sizeof(T) * (count ? count : 1)));
+    set.push_back(std::move(a));
     return SLAM_OK;
 }
 
-#define TRY(expr)                   \
-    do {                            \
-        const int rc_ = (expr);     \
-        if (rc_ != SLAM_OK) return rc_; \
-    } while (0)
-
-int round_up(int v, int m) { return (v + m - 1) / m * m; }
+void bind_arrays(std::vector<pgs_handle::Array>& set) { for (pgs_handle::Array& a : set) *a.field = a.buf.get(); }
 
 int check(pgs_handle* h) {
     if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
     HIP_TRY(hipSetDevice(h->device));
+    return SLAM_OK;
+}
+
+// the layout of Y for segments of SL poses (0: the sequential chain): the separators' rows live behind the pose rows (pgs_kernel.h: yr_rc, yr_sep)
+void seg_geometry(const pgs_handle* h, slam::PgsParams& g, int SL) {
+    g.nseg_max = SL > 0 ? (h->N_max - 2) / SL + 1 : 1;
+    g.yr_sep = g.yr_rc + 6 * (int64_t)g.nseg_max;
+    g.y_stride = (int64_t)(g.yr_sep + round_up(3 * g.nseg_max, 4)) * h->LD;
+}
+
+// The arrays whose size follows the number of segments of geometry g, into `set` (for h->p's fields, not yet bound): the plan (the lambda
+// lanes get copies of it), the segments' outputs and Gram matrices (segT: if with_segT), and Y.  Nothing in them outlives a solve.
+int alloc_seg_arrays(pgs_handle* h, const slam::PgsParams& g, bool with_segT, std::vector<pgs_handle::Array>& set) {
+    slam::PgsParams& p = h->p;
+    const size_t S = (size_t)h->B * h->lanes, L = (size_t)h->L_max, G = (size_t)g.nseg_max;
+    if (h->seg_len > 0) {
+        const size_t NB = (size_t)slam::seg_nb1(h->L_max);
+        TRY(add_array(set, &p.seg_ncol, S * G, G)); TRY(add_array(set, &p.seg_lm, S * G * L, G * L)); TRY(add_array(set, &p.seg_inv, S * G * L, G * L));
+        TRY(add_array(set, &p.seg_evt, S * G * L, G * L)); TRY(add_array(set, &p.seg_blk, S * G * NB, G * NB)); TRY(add_array(set, &p.sep_evt, S * G * L, G * L));
+        TRY(add_array(set, &p.segout, S * G * 32)); TRY(add_array(set, &p.sepfac, S * G * 16));
+        if (with_segT) TRY(add_array(set, &p.segT, S * G * (size_t)p.seg_tld * p.seg_tld));
+    }
+    TRY(add_array(set, &p.Y, S * (size_t)g.y_stride));
     return SLAM_OK;
 }
 
@@ -136,53 +147,26 @@ int check(pgs_handle* h) {
 int ensure_segT(pgs_handle* h) {
     if (h->p.segT || h->seg_len <= 0) return SLAM_OK;
     const size_t S = (size_t)h->B * h->lanes;
-    return dalloc(h, &h->p.segT, S * (size_t)h->p.nseg_max * (size_t)h->p.seg_tld * h->p.seg_tld);
+    TRY(add_array(h->seg_arrays, &h->p.segT, S * (size_t)h->p.nseg_max * (size_t)h->p.seg_tld * h->p.seg_tld));
+    bind_arrays(h->seg_arrays);
+    return SLAM_OK;
 }
 
-template <class T>
-void dfree(pgs_handle* h, T*& ptr) {
-    if (!ptr) return;
-    for (size_t i = 0; i < h->allocs.size(); ++i)
-        if (h->allocs[i] == (void*)ptr) { h->allocs.erase(h->allocs.begin() + (long)i); break; }
-    hipFree((void*)ptr);
-    ptr = nullptr;
-}
-
-// The arrays whose size follows the number of segments (the plan, the segments' outputs, their Gram matrices, and Y - whose separator rows
-// live behind the pose rows) re-made for segments of SL poses, if they were sized for longer ones.  Nothing in them outlives a solve.
-int resize_segments(pgs_handle* h, int SL) {
+// The segment-count-dependent arrays re-made for segments of SL poses, if they were sized for longer ones: the whole new set is allocated
+// before the old one is released and the geometry and seg_alloc are committed.  Out of memory: the old set and geometry stay, *resized = false
+// and the solve takes the sequential chain.  (Both sets at once: at most twice per handle, at 32 -> 16 and 16 -> 8 poses per segment.)
+int resize_segments(pgs_handle* h, int SL, bool* resized) {
+    *resized = true;
     if (SL >= h->seg_alloc) return SLAM_OK;
     HIP_TRY(hipDeviceSynchronize());
-    slam::PgsParams& p = h->p;
-    const size_t S = (size_t)h->B * h->lanes, L = (size_t)h->L_max;
-    void* old[6] = {p.seg_ncol, p.seg_lm, p.seg_inv, p.seg_evt, p.seg_blk, p.sep_evt};
-    dfree(h, p.seg_ncol); dfree(h, p.seg_lm); dfree(h, p.seg_inv); dfree(h, p.seg_evt); dfree(h, p.seg_blk); dfree(h, p.sep_evt);
-    dfree(h, p.segout); dfree(h, p.sepfac); dfree(h, p.segT); dfree(h, p.Y);
-    p.nseg_max = (h->N_max - 2) / SL + 1;
-    p.yr_sep = p.yr_rc + 6 * (int64_t)p.nseg_max;
-    p.y_stride = (int64_t)(p.yr_sep + round_up(3 * p.nseg_max, 4)) * h->LD;
-    const size_t G = (size_t)p.nseg_max;
-    const size_t per[6] = {G, G * L, G * L, G * L, G * (size_t)slam::seg_nb1(h->L_max), G * L};
-    TRY(dalloc(h, &p.seg_ncol, S * per[0])); TRY(dalloc(h, &p.seg_lm, S * per[1])); TRY(dalloc(h, &p.seg_inv, S * per[2]));
-    TRY(dalloc(h, &p.seg_evt, S * per[3])); TRY(dalloc(h, &p.seg_blk, S * per[4])); TRY(dalloc(h, &p.sep_evt, S * per[5]));
-    void* now[6] = {p.seg_ncol, p.seg_lm, p.seg_inv, p.seg_evt, p.seg_blk, p.sep_evt};
-    for (pgs_handle::Slab& sl : h->clone_slabs)     // the lambda lanes get copies of the plan (clone_instances)
-        for (int k = 0; k < 6; ++k)
-            if (sl.ptr == old[k]) {   // (once per slab: the allocator may hand a new array the address another old one had)
-                sl.ptr = now[k]; sl.bytes = per[k] * sizeof(int32_t);
-                break;
-            }
-    TRY(dalloc(h, &p.segout, S * G * 32)); TRY(dalloc(h, &p.sepfac, S * G * 16));
-    TRY(dalloc(h, &p.Y, S * (size_t)p.y_stride));
+    slam::PgsParams g = h->p;
+    seg_geometry(h, g, SL);
+    std::vector<pgs_handle::Array> set;
+    if (alloc_seg_arrays(h, g, h->p.segT != nullptr, set) != SLAM_OK) { *resized = false; return SLAM_OK; }   // (`set` is released)
+    h->seg_arrays.swap(set);   // the old set is released with `set`
+    bind_arrays(h->seg_arrays);
+    h->p.nseg_max = g.nseg_max; h->p.yr_sep = g.yr_sep; h->p.y_stride = g.y_stride;
     h->seg_alloc = SL;
-    return SLAM_OK;   // (segT: ensure_segT, by the solve that runs the order)
-}
-
-int ensure_staging(pgs_handle* h, int k_stride) {
-    if (h->dmeas && h->k_stride >= k_stride) return SLAM_OK;
-    if (h->dmeas) { hipFree(h->dmeas); h->dmeas = nullptr; }
-    HIP_TRY(hipMalloc((void**)&h->dmeas, sizeof(float) * 3 * (size_t)k_stride * h->B));
-    h->k_stride = k_stride;
     return SLAM_OK;
 }
 
@@ -245,17 +229,15 @@ int pgs_create(const slam_config* cfg, int batch, int N_max, int L_max, int k_pe
     const size_t S = B * (size_t)h->lanes;
     p.lanes_max = h->lanes; p.lanes = 1;
     int rc = SLAM_OK;
-    auto A = [&](auto** ptr, size_t count) { if (rc == SLAM_OK) rc = dalloc(h, ptr, count); };
+    auto A = [&](auto** ptr, size_t count) { if (rc == SLAM_OK) rc = add_array(h->arrays, ptr, count); };
     // AC: S slots, and the clones get the instance's content when a solve begins (per-slot element count given)
-    auto AC = [&](auto** ptr, size_t per_slot) {
-        if (rc == SLAM_OK) rc = dalloc(h, ptr, S * per_slot);
-        if (rc == SLAM_OK) h->clone_slabs.push_back({(void*)*ptr, per_slot * sizeof(**ptr)});
-    };
+    auto AC = [&](auto** ptr, size_t per_slot) { if (rc == SLAM_OK) rc = add_array(h->arrays, ptr, S * per_slot, per_slot); };
+    auto D = [&](auto& buf, size_t count) { if (rc == SLAM_OK && buf.reserve(count) != hipSuccess) rc = fail(SLAM_ERR_HIP, "out of device memory"); };
     A(&p.pose0, B * N * 3); A(&p.lm0, B * L * 2); A(&p.pose1, B * N * 3); A(&p.lm1, B * L * 2);
     A(&p.ids, B * L); AC(&p.M, 1); A(&p.flags, S);
     AC(&p.cnt, N); AC(&p.mlm, K); AC(&p.mnext, K); AC(&p.lm_head, L); AC(&p.lm_last, L); AC(&p.lm_first, L);
     AC(&p.mb, K); AC(&p.mr, K);
-    A(&h->dcmds, N * 2); p.cmds = h->dcmds;
+    D(h->dcmds, N * 2); p.cmds = h->dcmds;
     A(&p.cur, B * 3); A(&p.truth, B * 3); A(&p.truth_hist, B * N * 2);
     AC(&p.pw, N * 3); AC(&p.lw, L * 2); A(&p.pn, S * N * 3); A(&p.ln, S * L * 2);
     A(&p.A, S * N * 9); A(&p.C, S * N * 9); A(&p.gp, S * N * 3); A(&p.E, S * K * 6); A(&p.Wl, S * K * 5);
@@ -266,27 +248,24 @@ int pgs_create(const slam_config* cfg, int batch, int N_max, int L_max, int k_pe
     // behind the pose rows of Y (pgs_kernel.h: yr_rc, yr_sep)
     p.seg_len = h->seg_len; p.seg_on = 0; p.syrk_rows = -1; p.syrk_row0 = 0; p.syrk_first = nullptr;
     p.seg_back_global = getenv("SLAM_PGS_SEG_BACK_GLOBAL") ? atoi(getenv("SLAM_PGS_SEG_BACK_GLOBAL")) : 0;
-    p.nseg_max = h->seg_len > 0 ? (N_max - 2) / h->seg_len + 1 : 1;
     p.yr_rc = round_up(3 * N_max, 4);
-    p.yr_sep = p.yr_rc + 6 * (int64_t)p.nseg_max;
-    p.y_stride = (int64_t)(p.yr_sep + round_up(3 * p.nseg_max, 4)) * h->LD;
+    seg_geometry(h, p, h->seg_len);
     if (h->seg_len > 0) {
-        const size_t G = (size_t)p.nseg_max;
-        AC(&p.seg_ncol, G); AC(&p.seg_lm, G * L); AC(&p.seg_inv, G * L); AC(&p.seg_evt, G * L); AC(&p.sep_first, L);
-        AC(&p.seg_blk, G * (size_t)slam::seg_nb1(L_max)); AC(&p.sep_evt, G * L);
-        A(&p.Gs, S * N * 9); A(&p.segout, S * G * 32); A(&p.sepfac, S * G * 16);
+        AC(&p.sep_first, L); A(&p.Gs, S * N * 9);
         // (segT, the segments' Gram matrices - the largest of these arrays - is allocated by the first solve that runs the segmented order: ensure_segT)
         p.seg_tld = round_up(2 * (L_max < slam::kPgsSegMaxLm ? L_max : slam::kPgsSegMaxLm) + 1, 16);
     }
-    A(&p.Y, S * (size_t)p.y_stride); A(&p.S, S * (size_t)h->LD * h->LD);
+    if (rc == SLAM_OK) rc = alloc_seg_arrays(h, p, false, h->seg_arrays);   // the plan, the segments' outputs, Y
+    A(&p.S, S * (size_t)h->LD * h->LD);
     A(&p.dl, S * L * 2); A(&p.dp, S * N * 3);
     A(&p.lambda, S); A(&p.error, B); A(&p.cur_error, B); A(&p.err_init, B);
     A(&p.iters, B); A(&p.trials, B); A(&p.state, S + 1); AC(&p.solve_ok, 1); A(&p.n_active, 64); A(&p.alist, S); A(&p.inst_flop, B); A(&p.work, 3);
     A(&p.nl, B); A(&p.nlin, S); A(&p.nerr, S); A(&p.nok, S);
-    A(&h->dcount, B); A(&h->dsec, B * 3); A(&h->dout, B);
-    A(&h->d_cnt, (size_t)pgs_handle::kMaxGroups * 16); A(&h->d_wait, (size_t)pgs_handle::kMaxGroups);
+    D(h->dcount, B); D(h->dsec, B * 3); D(h->dout, B);
+    D(h->d_cnt, (size_t)pgs_handle::kMaxGroups * 16); D(h->d_wait, (size_t)pgs_handle::kMaxGroups);
     if (getenv("SLAM_PGS_PROF")) { A(&p.prof, S * 24); }   // [S][8] chol phase timers, then [S][2][8] per-workgroup stamps of the fused chain
     if (rc != SLAM_OK) { pgs_destroy(h); return rc; }
+    bind_arrays(h->arrays); bind_arrays(h->seg_arrays);
     hipMemsetAsync(p.truth_hist, 0, sizeof(double) * B * N * 2, h->stream);
     p.dead_slot = (int32_t)S; p.slots_cap = 0; p.n_list_dev = nullptr; p.wait_next = h->d_wait;
     hipMemsetD32Async((hipDeviceptr_t)(p.state + S), 1, 1, h->stream);   // the slot every kernel returns for at entry (pgs_slot)
@@ -311,19 +290,14 @@ int pgs_destroy(pgs_handle* h) {
     if (!h) return SLAM_OK;
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    for (void* ptr : h->allocs) hipFree(ptr);
     for (hipEvent_t e : h->events) hipEventDestroy(e);
     for (hipEvent_t e : h->gevents) hipEventDestroy(e);
     for (hipEvent_t e : h->ring_events) hipEventDestroy(e);
     for (hipEvent_t e : h->async_events) hipEventDestroy(e);
     if (h->tick_stream) hipStreamDestroy(h->tick_stream);
-    if (h->h_ring) hipHostFree(h->h_ring);
     for (hipStream_t st : h->gstreams) hipStreamDestroy(st);
-    if (h->h_active) hipHostFree(h->h_active);
-    if (h->dmeas) hipFree(h->dmeas);
-    if (h->p.map) hipFree((void*)h->p.map);
     if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
-    delete h;
+    delete h;   // the device and pinned buffers
     return SLAM_OK;
 }
 
@@ -339,12 +313,11 @@ int pgs_set_seed(pgs_handle* h, uint64_t seed) { TRY(check(h)); h->seed = seed; 
 int pgs_set_map(pgs_handle* h, const double* map_xy, int L) {
     TRY(check(h));
     if (!map_xy || L <= 0) return fail(SLAM_ERR_ARG, "bad map");
-    if (h->p.map) { hipStreamSynchronize(h->stream); hipFree((void*)h->p.map); h->p.map = nullptr; }
-    double* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, sizeof(double) * 2 * (size_t)L));
-    HIP_TRY(hipMemcpyAsync(d, map_xy, sizeof(double) * 2 * (size_t)L, hipMemcpyHostToDevice, h->stream));
+    if (h->map) hipStreamSynchronize(h->stream);
+    HIP_TRY(h->map.reserve(2 * (size_t)L));
+    HIP_TRY(hipMemcpyAsync(h->map, map_xy, sizeof(double) * 2 * (size_t)L, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    h->p.map = d; h->p.L = L;
+    h->p.map = h->map; h->p.L = L;
     return SLAM_OK;
 }
 
@@ -375,7 +348,7 @@ int pgs_update(pgs_handle* h, const float cmd[2], const float* meas, const int32
     TRY(check(h));
     if (k_stride < 0 || (k_stride > 0 && (!meas || !count))) return fail(SLAM_ERR_ARG, "bad measurement arguments");
     const int ks = k_stride > 0 ? k_stride : 1;
-    TRY(ensure_staging(h, ks));
+    HIP_TRY(h->dmeas.reserve((size_t)3 * ks * h->B));
     if (k_stride > 0) {
         HIP_TRY(hipMemcpyAsync(h->dmeas, meas, sizeof(float) * 3 * (size_t)k_stride * h->B, hipMemcpyHostToDevice, h->stream));
         HIP_TRY(hipMemcpyAsync(h->dcount, count, sizeof(int32_t) * (size_t)h->B, hipMemcpyHostToDevice, h->stream));
@@ -412,9 +385,10 @@ int clone_instances(pgs_handle* h, const slam::PgsParams& p, hipStream_t stream,
     const size_t B = (size_t)h->B, off = (size_t)p.b_off, cnt = (size_t)p.b_cnt;
     for (int j = 1; j < h->lanes; ++j) {
         if (slabs)
-            for (const pgs_handle::Slab& sl : h->clone_slabs)
-                HIP_TRY(hipMemcpyAsync((char*)sl.ptr + ((size_t)j * B + off) * sl.bytes, (const char*)sl.ptr + off * sl.bytes, cnt * sl.bytes,
-                                       hipMemcpyDeviceToDevice, stream));
+            for (const auto* set : {&h->arrays, &h->seg_arrays})
+                for (const pgs_handle::Array& a : *set)
+                    if (const size_t sb = a.slot_bytes)
+                        HIP_TRY(hipMemcpyAsync((char*)*a.field + ((size_t)j * B + off) * sb, (const char*)*a.field + off * sb, cnt * sb, hipMemcpyDeviceToDevice, stream));
         HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(p.state + (size_t)j * B + off), 1, cnt, stream));
     }
     return SLAM_OK;
@@ -424,10 +398,12 @@ int clone_instances(pgs_handle* h, const slam::PgsParams& p, hipStream_t stream,
 int clone_listed(pgs_handle* h, const slam::PgsParams& p, int n_list, hipStream_t stream) {
     slam::PgsCloneTable t;
     t.n = 0;
-    for (const pgs_handle::Slab& sl : h->clone_slabs) {
-        if (t.n >= 28 || (sl.bytes & 3)) return fail(SLAM_ERR_STATE, "clone table: %d arrays, %zu bytes per slot", (int)h->clone_slabs.size(), sl.bytes);
-        t.ptr[t.n] = sl.ptr; t.words[t.n] = (uint32_t)(sl.bytes / 4); t.n += 1;
-    }
+    for (const auto* set : {&h->arrays, &h->seg_arrays})
+        for (const pgs_handle::Array& a : *set) {
+            if (!a.slot_bytes) continue;
+            if (t.n >= 28 || (a.slot_bytes & 3)) return fail(SLAM_ERR_STATE, "clone table: more than %d arrays, or %zu bytes per slot", t.n, a.slot_bytes);
+            t.ptr[t.n] = *a.field; t.words[t.n] = (uint32_t)(a.slot_bytes / 4); t.n += 1;
+        }
     slam::PgsParams q = p;
     q.n_list = n_list;
     HIP_TRY(slam::pgs_launch_clone(q, t, h->lanes, stream));
@@ -526,7 +502,9 @@ int pgs_solve(pgs_handle* h) {
             const int next = SL / 2;
             // (0x7fffffff: more separators than pgs_sep_kernel stages - shorter segments only add separators)
             if (mx == 0x7fffffff || next < 8 || (h->p.N - 2) / next > slam::kPgsSegMaxSep) break;
-            TRY(resize_segments(h, next));
+            bool resized = false;
+            TRY(resize_segments(h, next, &resized));
+            if (!resized) break;   // (no memory for the shorter segments' arrays: the sequential chain, on the arrays that exist)
             SL = next;
         }
         if (h->seg_ok) { h->seg_cur = SL; h->seg_used = SL; TRY(ensure_segT(h)); }
@@ -577,12 +555,12 @@ int pgs_solve(pgs_handle* h) {
         h->gstreams.push_back(st);
     }
     while ((int)h->gevents.size() < G + 1) { hipEvent_t e; HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->gevents.push_back(e); }
-    if (!h->h_active) HIP_TRY(hipHostMalloc((void**)&h->h_active, sizeof(int32_t) * 64, hipHostMallocDefault));
+    HIP_TRY(h->h_active.reserve(64));
     // streaming: `slots` graphs in flight over all groups; a group whose share of the slots covers its graphs runs lockstep as before
     const int per = (h->B + G - 1) / G;
     const int cap_g = (h->slots > 0 && !profile) ? (h->slots + G - 1) / G : 0;
     if (cap_g > 0) {
-        if (!h->h_ring) HIP_TRY(hipHostMalloc((void**)&h->h_ring, sizeof(int32_t) * 8 * pgs_handle::kRing * pgs_handle::kMaxGroups, hipHostMallocDefault));
+        HIP_TRY(h->h_ring.reserve(8 * pgs_handle::kRing * pgs_handle::kMaxGroups));
         while ((int)h->ring_events.size() < pgs_handle::kRing * pgs_handle::kMaxGroups) {
             hipEvent_t e; HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->ring_events.push_back(e);
         }
@@ -766,9 +744,9 @@ int run_every_iteration_async(pgs_handle* h, int T) {
     constexpr int R = pgs_handle::kRing;
     const int D = h->stream_depth, B = h->B;
     const size_t S = (size_t)B * h->lanes;
-    if (!h->d_Nv) TRY(dalloc(h, &h->d_Nv, S + 1));
-    if (!h->d_mono) TRY(dalloc(h, &h->d_mono, 2));
-    if (!h->h_ring) HIP_TRY(hipHostMalloc((void**)&h->h_ring, sizeof(int32_t) * 8 * pgs_handle::kRing * pgs_handle::kMaxGroups, hipHostMallocDefault));
+    HIP_TRY(h->d_Nv.reserve(S + 1));
+    HIP_TRY(h->d_mono.reserve(2));
+    HIP_TRY(h->h_ring.reserve(8 * pgs_handle::kRing * pgs_handle::kMaxGroups));
     while ((int)h->ring_events.size() < pgs_handle::kRing * pgs_handle::kMaxGroups) {
         hipEvent_t e; HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->ring_events.push_back(e);
     }
@@ -853,8 +831,8 @@ int pgs_run_sim_every_iteration(pgs_handle* h, const float* cmds, int T, int32_t
     if (h->timestep + T >= h->N_max) return fail(SLAM_ERR_STATE, "timestep %d + %d commands exceed the pose capacity N_max = %d", h->timestep, T, h->N_max);
     HIP_TRY(hipMemcpyAsync(h->dcmds + 2 * (size_t)h->timestep, cmds, sizeof(float) * 2 * (size_t)T, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));   // cmds is a pageable host array
-    if (!h->d_tick) TRY(dalloc(h, &h->d_tick, (size_t)h->B * 2));
-    if (!h->d_tick_flop) TRY(dalloc(h, &h->d_tick_flop, (size_t)h->B * 2));
+    HIP_TRY(h->d_tick.reserve((size_t)h->B * 2));
+    HIP_TRY(h->d_tick_flop.reserve((size_t)h->B * 2));
     HIP_TRY(hipMemsetAsync(h->d_tick, 0, sizeof(int32_t) * 2 * (size_t)h->B, h->stream));
     HIP_TRY(hipMemsetAsync(h->d_tick_flop, 0, sizeof(double) * 2 * (size_t)h->B, h->stream));
     const bool prof = getenv("SLAM_PGS_ITER_PROF") != nullptr;
@@ -863,7 +841,7 @@ int pgs_run_sim_every_iteration(pgs_handle* h, const float* cmds, int T, int32_t
     h->iter_trials = 0;
     // asynchronous ticks need the segmented elimination (its plan is checked on the device) and its separators within the staging of
     // pgs_sep_kernel for the whole run; per-kernel profiling and the phase table want the lockstep loop
-    if (h->iter_async && !prof && !h->profiling && h->seg_len > 0 && (h->timestep + T - 1) / h->seg_len <= slam::kPgsSegMaxSep && h->use_list) {
+    if (h->iter_async && !prof && !h->profiling && h->seg_cur > 0 && (h->timestep + T - 1) / h->seg_cur <= slam::kPgsSegMaxSep && h->use_list) {
         TRY(run_every_iteration_async(h, T));
         h->iter_trials = h->async_trials;
         h->timestep += T;

@@ -34,18 +34,6 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-// (The runtime's "last error" is sticky and per thread: a launcher that ends in hipGetLastError() would report an error some OTHER library
-// of the process left behind - PyTorch creating a stream right before slam_init did exactly that in a test.  It is cleared before every
-// call; our own calls are all checked through their return values.)
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        (void)hipGetLastError();                                                                   \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(SLAM_ERR_HIP, "%s -> %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
 // fn(begin, end) over [0, n) on a few host threads (packing 65 536 per-instance messages is ~1 ms on one core)
 template <class F>
 void host_parallel(size_t n, F fn) {
@@ -75,26 +63,25 @@ struct slam_handle {
     uint32_t step = 0;
     double range_max, fov_min, fov_max;
     // device buffers
-    void* dP = nullptr; void* dP2 = nullptr;   // dP = current P_t; dP2 = second buffer (EKF: layout changes, UKF: ping-pong)
-    void* dx = nullptr; int esz = 8;           // x_t; element size of P / x storage
-    double* dscratch = nullptr;                // fp32 storage: fp64 slab for P between detection groups
-    int32_t* dM = nullptr; int32_t* dids = nullptr;
-    int32_t* dflags = nullptr; int32_t* dts = nullptr; double* dtruth = nullptr; double* derr = nullptr;
-    double* dmap = nullptr; int L = 0;
-    float* dmeas = nullptr; int32_t* dcount = nullptr; int k_stride = 0;   // last-measurement dump (slam_get_last_meas)
+    // device buffers (released with the handle)
+    DevBuf<char> dP, dP2;                      // dP = current P_t; dP2 = second buffer (EKF: layout changes, UKF: ping-pong)
+    DevBuf<char> dx; int esz = 8;              // x_t; element size of P / x storage
+    DevBuf<double> dscratch;                   // fp32 storage: fp64 slab for P between detection groups
+    DevBuf<int32_t> dM, dids, dflags, dts; DevBuf<double> dtruth, derr;
+    DevBuf<double> dmap; int L = 0;
+    DevBuf<float> dmeas; DevBuf<int32_t> dcount; int k_stride = 0;   // last-measurement dump (slam_get_last_meas); k_stride: what both hold
     // slam_step (host measurements): two pinned staging buffers + two device buffers, filled on a copy stream while the
     // previous step's kernel runs; no stream synchronisation per step
     struct Stage {
-        float* hmeas = nullptr; int32_t* hcount = nullptr;     // pinned host
-        float* dmeas = nullptr; int32_t* dcount = nullptr;     // device
-        size_t cap = 0;                                        // floats in hmeas / dmeas
+        PinnedBuf<float> hmeas; PinnedBuf<int32_t> hcount;     // pinned host
+        DevBuf<float> dmeas; DevBuf<int32_t> dcount;           // device
         hipEvent_t copied = nullptr, used = nullptr;
         bool in_use = false;
     } stage[2];
     hipStream_t copy_stream = nullptr;
     hipEvent_t shadow_ev = nullptr;
     uint32_t stage_next = 0;
-    unsigned long long* dkhist = nullptr;                      // [8] instance-steps by detection count
+    DevBuf<unsigned long long> dkhist;                         // [8] instance-steps by detection count
     // slam_step_sim (EKF): the commands of consecutive calls are queued on the host and run as ONE multi-step launch when the
     // queue is full or anything else touches the handle (every other entry point flushes first).  The kernels are asynchronous
     // anyway, and a multi-step launch gives the same bits as single steps, so only the speed changes (one launch per call
@@ -110,11 +97,10 @@ struct slam_handle {
     // lazy_max timesteps; a flush copies the queue on the copy stream and runs ONE multi-step launch that takes the message of
     // timestep t from the device-side queue instead of the generator.
     struct ExtQueue {
-        float* hmeas = nullptr; int32_t* hcount = nullptr; float* hcmds = nullptr;   // pinned: [cap][B][kExtQ][3], [cap][B], [cap][2]
-        float* dmeas = nullptr; int32_t* dcount = nullptr;                           // device
-        int cap = 0, n = 0;
+        PinnedBuf<float> hmeas; PinnedBuf<int32_t> hcount; PinnedBuf<float> hcmds;   // pinned: [cap][B][kExtQ][3], [cap][B], [cap][2]
+        DevBuf<float> dmeas; DevBuf<int32_t> dcount;                                 // device
+        int cap = 0, n = 0;                                                          // cap: timesteps every buffer of the queue holds
         int ks = 0;                                                                  // detections per instance of this fill (<= kExtQ)
-        size_t meas_cap = 0;                                                         // floats in hmeas / dmeas
         hipEvent_t copied = nullptr, used = nullptr;
         bool in_use = false;
     } extq[2];
@@ -124,9 +110,9 @@ struct slam_handle {
     // the compute stream at the call (so the caller may overwrite its buffers in stream order, as with an immediate launch)
     // and up to lazy_max of them run as one multi-step launch.  One buffer suffices: copies and launches share the stream.
     struct DevQueue {
-        float* dmeas = nullptr; int32_t* dcount = nullptr;   // [cap][B][ks][3], [cap][B]
+        DevBuf<float> dmeas; DevBuf<int32_t> dcount;   // [lazy_max][B][ks][3], [lazy_max][B]
         std::vector<float> cmds;
-        int cap = 0, ks = 0, n = 0;
+        int ks = 0, n = 0;
     } devq;
     // slam_track_instance: instance `tracked` also runs in a one-instance SHADOW filter (same config, seed, map and GLOBAL
     // instance id, hence the same bits: results do not depend on how a batch is partitioned), stepped at once at every step
@@ -134,20 +120,20 @@ struct slam_handle {
     // does not have to run the batch's queued timesteps first.
     slam_handle* shadow = nullptr; int tracked = -1;
     std::vector<double> hmap;                  // host copy of the map (the shadow needs it)
-    double* dscalar = nullptr;
-    unsigned long long* dprof = nullptr;
-    double* dsq = nullptr; int32_t* dnsq = nullptr;   // UKF: matrix square root scratch + its dimension
-    double* dxprev = nullptr;                         // UKF: x_t the last sigma points were drawn around
-    double* dvt = nullptr; int32_t* dvage = nullptr;  // UKF: V^T of the last eigen-decomposition + warm-start age
-    double* dbigws = nullptr;                         // UKF beyond the LDS size classes: [B][2 * pstride] scratch (ukf_big_kernel.hip)
-    uint4* drot = nullptr;                            // UKF (n <= 44): pass table of the fast sqrt kernel (launch_ukf_quad_table)
-    uint8_t* dchol = nullptr; bool chol = false;      // UKF: SLAM_UKF_SQRT_CHOLESKY is on; [B] "the Cholesky factor succeeded" (ukf_chol_kernel)
+    DevBuf<double> dscalar;
+    DevBuf<unsigned long long> dprof;
+    DevBuf<double> dsq; DevBuf<int32_t> dnsq;         // UKF: matrix square root scratch + its dimension
+    DevBuf<double> dxprev;                            // UKF: x_t the last sigma points were drawn around
+    DevBuf<double> dvt; DevBuf<int32_t> dvage;        // UKF: V^T of the last eigen-decomposition + warm-start age
+    DevBuf<double> dbigws;                            // UKF beyond the LDS size classes: [B][2 * pstride] scratch (ukf_big_kernel.hip)
+    DevBuf<uint4> drot;                               // UKF (n <= 44): pass table of the fast sqrt kernel (launch_ukf_quad_table)
+    DevBuf<uint8_t> dchol; bool chol = false;         // UKF: SLAM_UKF_SQRT_CHOLESKY is on; [B] "the Cholesky factor succeeded" (ukf_chol_kernel)
     hipStream_t aux_stream[3] = {nullptr, nullptr, nullptr}; hipEvent_t aux_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // UKF run_sim: the other parts of the batch
     int ukf_parts = 2;                                                               // streams the UKF batch is split over (SLAM_UKF_PARTS, 1..4)
     int ukf_split_min = 1024;                                                        // batch size from which it is used
     bool predicted = false; float pred_cmd[2] = {0.f, 0.f};   // UKF: slam_predict done, slam_update_dev pending
-    float* dmapf = nullptr;                           // UKF_LOC: the known map as float32 [id, x, y] triplets
-    float* dcmds = nullptr; int cmds_cap = 0;         // command sequence of a multi-step launch (slam_run_sim)
+    DevBuf<float> dmapf;                              // UKF_LOC: the known map as float32 [id, x, y] triplets
+    DevBuf<float> dcmds;                              // command sequence of a multi-step launch (slam_run_sim)
     int run_chunk = 0;                                // timesteps per launch in slam_run_sim (0 = all of them)
     int base = 3;                                     // state offset of the first landmark: 3 (EKF) or 4 (UKF)
     bool dump_meas = false;
@@ -182,7 +168,7 @@ void fill_params(slam_handle* h, slam::EkfStepParams& p, const float cmd[2]) {
 
 void fill_ukf_params(slam_handle* h, slam::UkfStepParams& p, const float cmd[2]) {
     memset(&p, 0, sizeof(p));
-    p.P = (const double*)h->dP; p.P_out = (double*)h->dP2; p.x = (double*)h->dx; p.sqtP = h->dsq; p.n_sq = h->dnsq; p.x_prev = h->dxprev; p.Vt_store = h->dvt; p.v_age = h->dvage;
+    p.P = (const double*)h->dP.get(); p.P_out = (double*)h->dP2.get(); p.x = (double*)h->dx.get(); p.sqtP = h->dsq; p.n_sq = h->dnsq; p.x_prev = h->dxprev; p.Vt_store = h->dvt; p.v_age = h->dvage;
     p.M = h->dM; p.ids = h->dids; p.flags = h->dflags; p.timestep = h->dts;
     p.truth = h->dtruth; p.err_sum = h->derr; p.map = h->dmap; p.L = h->L;
     p.fwd = cmd[0]; p.ang = cmd[1];
@@ -224,8 +210,8 @@ int long_message_cap(slam_handle* h, int sim, int k_stride, int* cap_out) {
         cap = slam::ukf_class_message_capacity(h->L_max, h->kind == SLAM_UKF_LOC, h->L);
     }
     if (!(sim ? h->L > cap : k_stride > cap)) return SLAM_OK;
-    if (h->kind != SLAM_EKF_SLAM && !h->dbigws)   // scratch of the streamed step kernel (P_pred), on first use
-        HIP_TRY(hipMalloc(&h->dbigws, sizeof(double) * (size_t)h->B * 2 * h->pstride));
+    if (h->kind != SLAM_EKF_SLAM)   // scratch of the streamed step kernel (P_pred), on first use
+        HIP_TRY(h->dbigws.reserve((size_t)h->B * 2 * h->pstride));
     *cap_out = cap;
     return SLAM_OK;
 }
@@ -258,13 +244,20 @@ int launch_step(slam_handle* h, const float cmd[2], int sim, const float* d_meas
     return SLAM_OK;
 }
 
+// h->k_stride is set only once both buffers hold that stride
 int ensure_meas_buffers(slam_handle* h, int k_stride) {
-    if (h->dmeas && h->k_stride >= k_stride) return SLAM_OK;
-    if (h->dmeas) { hipFree(h->dmeas); hipFree(h->dcount); h->dmeas = nullptr; h->dcount = nullptr; }
-    HIP_TRY(hipMalloc(&h->dmeas, sizeof(float) * 3 * (size_t)k_stride * h->B));
-    HIP_TRY(hipMalloc(&h->dcount, sizeof(int32_t) * (size_t)h->B));
-    HIP_TRY(hipMemsetAsync(h->dcount, 0, sizeof(int32_t) * (size_t)h->B, h->stream));
+    if (h->k_stride >= k_stride) return SLAM_OK;
+    HIP_TRY(h->dmeas.reserve((size_t)3 * k_stride * h->B)); HIP_TRY(h->dcount.reserve((size_t)h->B));
+    HIP_TRY(hipMemsetAsync(h->dcount, 0, sizeof(int32_t) * (size_t)h->B, h->stream));   // no detections recorded at the new stride yet
     h->k_stride = k_stride;
+    return SLAM_OK;
+}
+
+// the device command buffer of a multi-step launch: room for T timesteps (the launches that read the old one are done first)
+int reserve_cmds(slam_handle* h, int T) {
+    if (h->dcmds.cap() >= 2 * (size_t)T) return SLAM_OK;
+    if (h->dcmds) HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(h->dcmds.reserve(2 * (size_t)T));
     return SLAM_OK;
 }
 
@@ -291,11 +284,6 @@ static bool eager_flush(slam_handle* h, int queued) {
     return true;
 }
 static constexpr int kExtQ = 4;   // detections per instance a queued slam_step message can hold
-#define FLUSH(h)                        \
-    do {                                \
-        const int frc_ = flush_lazy(h); \
-        if (frc_) return frc_;          \
-    } while (0)
 
 extern "C" {
 
@@ -384,31 +372,31 @@ int slam_create(const slam_config* cfg, int kind, int batch, int L_max, int dtyp
     h->own_stream = true;
     const size_t B = (size_t)batch;
     hipError_t errs[] = {
-        hipMalloc(&h->dP, (size_t)h->esz * B * h->pstride),
-        hipMalloc(&h->dP2, (size_t)h->esz * B * h->pstride),
-        hipMalloc(&h->dx, (size_t)h->esz * B * h->xstride),
-        hipMalloc(&h->dM, sizeof(int32_t) * B),
-        hipMalloc(&h->dids, sizeof(int32_t) * B * L_max),
-        hipMalloc(&h->dflags, sizeof(int32_t) * B),
-        hipMalloc(&h->dts, sizeof(int32_t) * B),
-        hipMalloc(&h->dtruth, sizeof(double) * B * 3),
-        hipMalloc(&h->derr, sizeof(double) * B),
-        hipMalloc(&h->dscalar, sizeof(double) * 4),
-        (h->dbg & (4 | 32)) ? hipMalloc(&h->dprof, sizeof(unsigned long long) * slam::kEkfProfSlots * B) : hipSuccess,
-        hipMalloc(&h->dkhist, sizeof(unsigned long long) * 16),
-        kind != SLAM_EKF_SLAM ? hipMalloc(&h->dsq, sizeof(double) * B * h->pstride) : hipSuccess,
-        h->esz == 4 ? hipMalloc(&h->dscratch, sizeof(double) * B * h->pstride) : hipSuccess,
-        kind != SLAM_EKF_SLAM ? hipMalloc(&h->dnsq, sizeof(int32_t) * B) : hipSuccess,
-        kind != SLAM_EKF_SLAM ? hipMalloc(&h->dxprev, sizeof(double) * B * h->xstride) : hipSuccess,
-        kind != SLAM_EKF_SLAM ? hipMalloc(&h->dvt, sizeof(double) * B * h->pstride) : hipSuccess,
-        (kind == SLAM_UKF_SLAM && L_max > slam::kUkfLdsMaxLandmarks) ? hipMalloc(&h->dbigws, sizeof(double) * B * 2 * h->pstride) : hipSuccess,
-        kind != SLAM_EKF_SLAM ? hipMalloc(&h->dvage, sizeof(int32_t) * B) : hipSuccess,
-        (kind != SLAM_EKF_SLAM && h->n_max <= 44) ? hipMalloc(&h->drot, sizeof(uint4) * slam::kUkfQuadTabEntries) : hipSuccess,
+        h->dP.reserve((size_t)h->esz * B * h->pstride),
+        h->dP2.reserve((size_t)h->esz * B * h->pstride),
+        h->dx.reserve((size_t)h->esz * B * h->xstride),
+        h->dM.reserve(B),
+        h->dids.reserve(B * L_max),
+        h->dflags.reserve(B),
+        h->dts.reserve(B),
+        h->dtruth.reserve(B * 3),
+        h->derr.reserve(B),
+        h->dscalar.reserve(4),
+        (h->dbg & (4 | 32)) ? h->dprof.reserve(slam::kEkfProfSlots * B) : hipSuccess,
+        h->dkhist.reserve(16),
+        kind != SLAM_EKF_SLAM ? h->dsq.reserve(B * h->pstride) : hipSuccess,
+        h->esz == 4 ? h->dscratch.reserve(B * h->pstride) : hipSuccess,
+        kind != SLAM_EKF_SLAM ? h->dnsq.reserve(B) : hipSuccess,
+        kind != SLAM_EKF_SLAM ? h->dxprev.reserve(B * h->xstride) : hipSuccess,
+        kind != SLAM_EKF_SLAM ? h->dvt.reserve(B * h->pstride) : hipSuccess,
+        (kind == SLAM_UKF_SLAM && L_max > slam::kUkfLdsMaxLandmarks) ? h->dbigws.reserve(B * 2 * h->pstride) : hipSuccess,
+        kind != SLAM_EKF_SLAM ? h->dvage.reserve(B) : hipSuccess,
+        (kind != SLAM_EKF_SLAM && h->n_max <= 44) ? h->drot.reserve(slam::kUkfQuadTabEntries) : hipSuccess,
     };
     for (hipError_t ee : errs)
         if (ee != hipSuccess) {
             slam_destroy(h);
-            return fail(SLAM_ERR_HIP, "hipMalloc -> %s", hipGetErrorString(ee));
+            return fail(SLAM_ERR_HIP, "allocating device memory -> %s", hipGetErrorString(ee));
         }
     // every buffer a getter can read before slam_init is zeroed (M = 0, flags = 0, timestep = 0, ...)
     hipError_t zs[] = {
@@ -445,30 +433,18 @@ int slam_destroy(slam_handle* h) {
     for (auto& ev : h->aux_ev) if (ev) hipEventDestroy(ev);
     if (h->copy_stream) { hipStreamSynchronize(h->copy_stream); hipStreamDestroy(h->copy_stream); }
     if (h->shadow_ev) hipEventDestroy(h->shadow_ev);
-    if (h->devq.dmeas) { hipFree(h->devq.dmeas); hipFree(h->devq.dcount); }
-    for (auto& q : h->extq) {
-        if (q.hmeas) { hipHostFree(q.hmeas); hipHostFree(q.hcount); hipHostFree(q.hcmds); hipFree(q.dmeas); hipFree(q.dcount); }
+    for (auto& q : h->extq)
         if (q.copied) { hipEventDestroy(q.copied); hipEventDestroy(q.used); }
-    }
-    for (auto& s : h->stage) {
-        if (s.hmeas) hipHostFree(s.hmeas);
-        if (s.hcount) hipHostFree(s.hcount);
-        if (s.dmeas) hipFree(s.dmeas);
-        if (s.dcount) hipFree(s.dcount);
-        if (s.copied) hipEventDestroy(s.copied);
-        if (s.used) hipEventDestroy(s.used);
-    }
-    void* bufs[] = {h->dP, h->dP2, h->dx, h->dM, h->dids, h->dflags, h->dts, h->dtruth, h->derr, h->dmap, h->dmeas, h->dcount, h->dscalar, h->dprof, h->dsq, h->dnsq, h->dscratch, h->dmapf, h->dcmds, h->dxprev, h->dvt, h->dvage, h->dkhist, h->drot, h->dbigws, h->dchol};
-    for (void* q : bufs)
-        if (q) hipFree(q);
+    for (auto& s : h->stage)
+        if (s.copied) { hipEventDestroy(s.copied); hipEventDestroy(s.used); }
     if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
-    delete h;
+    delete h;   // the device and pinned buffers
     return SLAM_OK;
 }
 
 int slam_set_stream(slam_handle* h, void* s) {
     if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     if (h->stream) hipStreamSynchronize(h->stream);
     if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
     h->stream = (hipStream_t)s;
@@ -477,26 +453,26 @@ int slam_set_stream(slam_handle* h, void* s) {
 }
 int slam_set_instance_offset(slam_handle* h, int64_t v) {
     if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     h->inst0 = v;
     return h->shadow ? slam_set_instance_offset(h->shadow, v + h->tracked) : SLAM_OK;
 }
 int slam_set_seed(slam_handle* h, uint64_t s) {
     if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     h->seed = s;
     return h->shadow ? slam_set_seed(h->shadow, s) : SLAM_OK;
 }
 int slam_set_vision(slam_handle* h, double range_max, double fov_min, double fov_max) {
     if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     h->range_max = range_max; h->fov_min = fov_min; h->fov_max = fov_max;
     return h->shadow ? slam_set_vision(h->shadow, range_max, fov_min, fov_max) : SLAM_OK;
 }
 
 int slam_init(slam_handle* h, float x0, float y0, float yaw0) {
     if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
     if (h->kind == SLAM_EKF_SLAM) {
         slam::EkfInitParams p;
@@ -508,7 +484,7 @@ int slam_init(slam_handle* h, float x0, float y0, float yaw0) {
         HIP_TRY(slam::launch_ekf_init(p, h->stream));
     } else {
         slam::UkfInitParams p;
-        p.P = (double*)h->dP; p.x = (double*)h->dx; p.n_sq = h->dnsq; p.v_age = h->dvage; p.M = h->dM; p.flags = h->dflags; p.timestep = h->dts; p.truth = h->dtruth; p.err_sum = h->derr;
+        p.P = (double*)h->dP.get(); p.x = (double*)h->dx.get(); p.n_sq = h->dnsq; p.v_age = h->dvage; p.M = h->dM; p.flags = h->dflags; p.timestep = h->dts; p.truth = h->dtruth; p.err_sum = h->derr;
         p.B = h->B; p.pstride = h->pstride; p.xstride = h->xstride;
         double s, c;   // x_t << x_0, y_0, cos(yaw_0), sin(yaw_0) with a float argument (ukf.cpp:33)
         slam::det_sincos((double)yaw0, &s, &c);
@@ -526,17 +502,16 @@ int slam_init(slam_handle* h, float x0, float y0, float yaw0) {
 
 int slam_set_map(slam_handle* h, const double* map_xy, int L) {
     if (!h || !map_xy || L <= 0) return fail(SLAM_ERR_ARG, "bad map");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
-    if (h->dmap) { HIP_TRY(hipStreamSynchronize(h->stream)); hipFree(h->dmap); h->dmap = nullptr; }
-    HIP_TRY(hipMalloc(&h->dmap, sizeof(double) * 2 * (size_t)L));
+    if (h->dmap) HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(h->dmap.reserve(2 * (size_t)L));
     HIP_TRY(hipMemcpyAsync(h->dmap, map_xy, sizeof(double) * 2 * (size_t)L, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (h->kind == SLAM_UKF_LOC) {   // trueMapCallback: filter->map = [id, x, y] float32 (localization_node.cpp:152-156)
         std::vector<float> trip((size_t)3 * L);
         for (int i = 0; i < L; ++i) { trip[3 * i] = (float)i; trip[3 * i + 1] = (float)map_xy[2 * i]; trip[3 * i + 2] = (float)map_xy[2 * i + 1]; }
-        if (h->dmapf) { hipFree(h->dmapf); h->dmapf = nullptr; }
-        HIP_TRY(hipMalloc(&h->dmapf, sizeof(float) * trip.size()));
+        HIP_TRY(h->dmapf.reserve(trip.size()));
         HIP_TRY(hipMemcpy(h->dmapf, trip.data(), sizeof(float) * trip.size(), hipMemcpyHostToDevice));
     }
     h->L = L;
@@ -565,21 +540,21 @@ int slam_step_dev(slam_handle* h, const float cmd[2], const float* d_meas, const
     if (h->kind == SLAM_EKF_SLAM && h->lazy_explicit && h->lazy_max > 1 && h->run_chunk != 1 && !h->dump_meas &&
         k_stride <= slam::ekf_class_message_capacity(h->L_max)) {   // (messages that may be longer: one launch pair per step, launch_step)
         slam_handle::DevQueue& q = h->devq;
-        if (!h->lazy_cmds.empty() || h->extq[h->extq_cur].n > 0 || (q.n > 0 && q.ks != k_stride)) FLUSH(h);   // earlier steps first
+        if (!h->lazy_cmds.empty() || h->extq[h->extq_cur].n > 0 || (q.n > 0 && q.ks != k_stride)) TRY(flush_lazy(h));   // earlier steps first
         const size_t B = (size_t)h->B;
-        if (q.cap < h->lazy_max || q.ks != k_stride) {
-            if (q.dmeas) { HIP_TRY(hipStreamSynchronize(h->stream)); hipFree(q.dmeas); hipFree(q.dcount); q.dmeas = nullptr; q.dcount = nullptr; }
-            q.cap = h->lazy_max; q.ks = k_stride;
-            HIP_TRY(hipMalloc(&q.dmeas, sizeof(float) * 3 * (size_t)k_stride * B * q.cap));
-            HIP_TRY(hipMalloc(&q.dcount, sizeof(int32_t) * B * q.cap));
+        const size_t steps = (size_t)h->lazy_max;
+        if (q.dmeas.cap() < 3 * (size_t)k_stride * B * steps || q.dcount.cap() < B * steps) {
+            if (q.dmeas) HIP_TRY(hipStreamSynchronize(h->stream));
+            HIP_TRY(q.dmeas.reserve(3 * (size_t)k_stride * B * steps)); HIP_TRY(q.dcount.reserve(B * steps));
         }
+        q.ks = k_stride;   // (q.n == 0 or the same stride: a queue of another stride was flushed above)
         HIP_TRY(hipMemcpyAsync(q.dmeas + (size_t)q.n * B * k_stride * 3, d_meas, sizeof(float) * 3 * (size_t)k_stride * B, hipMemcpyDeviceToDevice, h->stream));
         HIP_TRY(hipMemcpyAsync(q.dcount + (size_t)q.n * B, d_count, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, h->stream));
         q.cmds.push_back(cmd[0]); q.cmds.push_back(cmd[1]);
         q.n += 1;
         return q.n >= h->lazy_max ? flush_dev(h) : SLAM_OK;
     }
-    FLUSH(h);
+    TRY(flush_lazy(h));
     if (h->kind == SLAM_UKF_LOC && !h->dmapf) return fail(SLAM_ERR_STATE, "UKF_LOC needs the known map: call slam_set_map first (localization_node.cpp:113-116)");
     return launch_step(h, cmd, 0, d_meas, d_count, k_stride);
 }
@@ -598,12 +573,12 @@ int slam_step(slam_handle* h, const float cmd[2], const float* meas, const int32
         for (size_t b = 0; b < B; ++b) kmax = count[b] > kmax ? count[b] : kmax;   // 65 536 ints: ~20 us
         kmax = kmax < k_stride ? kmax : k_stride;
         if (kmax <= kExtQ) {
-            if (!h->lazy_cmds.empty() || h->devq.n > 0) FLUSH(h);   // steps queued through the other entry points run first
+            if (!h->lazy_cmds.empty() || h->devq.n > 0) TRY(flush_lazy(h));   // steps queued through the other entry points run first
             // a fill of the queue has ONE stride (detections per instance): the largest message this handle has seen so far, at
             // least 2 (a high-water mark: a stride per fill taken from its first message ended fills early whenever a larger
             // message followed, 46 instead of 65 M steps/s); a message above the mark ends the fill and raises it
             if (kmax > h->extq_ks) {
-                if (h->extq[h->extq_cur].n > 0) FLUSH(h);
+                if (h->extq[h->extq_cur].n > 0) TRY(flush_lazy(h));
                 h->extq_ks = kmax;
             }
             slam_handle::ExtQueue& q = h->extq[h->extq_cur];
@@ -611,19 +586,13 @@ int slam_step(slam_handle* h, const float cmd[2], const float* meas, const int32
             // capacity: the full stride kExtQ at once while that stays below 128 MB per queue (re-pinning 100 MB of host memory
             // costs ~40 ms each time the stride grows: 0.5 ms per step over a 300-step run); above that, the stride actually seen
             const size_t full = (size_t)3 * kExtQ * B * h->lazy_max;
-            const size_t need = sizeof(float) * full <= ((size_t)128 << 20) ? full : (size_t)3 * q.ks * B * h->lazy_max;
-            if (q.cap < h->lazy_max || q.meas_cap < need) {
-                if (q.n > 0) FLUSH(h);
+            const size_t need = sizeof(float) * full <= ((size_t)128 << 20) ? full : (size_t)3 * q.ks * B * h->lazy_max;   // floats
+            if (q.cap < h->lazy_max || q.hmeas.cap() < need || q.dmeas.cap() < need) {
+                if (q.n > 0) TRY(flush_lazy(h));
                 if (q.in_use) { HIP_TRY(hipEventSynchronize(q.used)); q.in_use = false; }
-                if (q.hmeas) { hipHostFree(q.hmeas); hipHostFree(q.hcount); hipHostFree(q.hcmds); hipFree(q.dmeas); hipFree(q.dcount); }
-                q.hmeas = nullptr; q.hcount = nullptr; q.hcmds = nullptr; q.dmeas = nullptr; q.dcount = nullptr;
-                q.cap = 0; q.meas_cap = 0;
-                HIP_TRY(hipHostMalloc((void**)&q.hmeas, sizeof(float) * need, hipHostMallocNonCoherent));
-                HIP_TRY(hipHostMalloc((void**)&q.hcount, sizeof(int32_t) * B * h->lazy_max, hipHostMallocNonCoherent));
-                HIP_TRY(hipHostMalloc((void**)&q.hcmds, sizeof(float) * 2 * h->lazy_max, hipHostMallocNonCoherent));
-                HIP_TRY(hipMalloc(&q.dmeas, sizeof(float) * need));
-                HIP_TRY(hipMalloc(&q.dcount, sizeof(int32_t) * B * h->lazy_max));
-                q.cap = h->lazy_max; q.meas_cap = need;
+                HIP_TRY(q.hmeas.reserve(need)); HIP_TRY(q.hcount.reserve(B * h->lazy_max)); HIP_TRY(q.hcmds.reserve(2 * (size_t)h->lazy_max));
+                HIP_TRY(q.dmeas.reserve(need)); HIP_TRY(q.dcount.reserve(B * h->lazy_max));
+                q.cap = h->lazy_max;
                 if (!q.copied) {
                     HIP_TRY(hipEventCreateWithFlags(&q.copied, hipEventDisableTiming));
                     HIP_TRY(hipEventCreateWithFlags(&q.used, hipEventDisableTiming));
@@ -658,7 +627,7 @@ int slam_step(slam_handle* h, const float cmd[2], const float* meas, const int32
             return (q.n >= h->lazy_max || eager_flush(h, q.n)) ? flush_ext(h) : SLAM_OK;
         }
     }
-    FLUSH(h);
+    TRY(flush_lazy(h));
     if (h->kind == SLAM_UKF_LOC && !h->dmapf) return fail(SLAM_ERR_STATE, "UKF_LOC needs the known map: call slam_set_map first (localization_node.cpp:113-116)");
     // The caller's buffers may be reused right after return (ekf.cpp:64 copies the message), so the message is packed
     // into one of two PINNED staging buffers (only max_b count[b] detections per instance travel), copied on a separate
@@ -674,20 +643,13 @@ int slam_step(slam_handle* h, const float cmd[2], const float* meas, const int32
     if (!s.copied) {
         HIP_TRY(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&s.used, hipEventDisableTiming));
-        HIP_TRY(hipHostMalloc((void**)&s.hcount, sizeof(int32_t) * B, hipHostMallocNonCoherent));   // CPU-cached pinned memory: fast to fill
-        HIP_TRY(hipMalloc(&s.dcount, sizeof(int32_t) * B));
     }
+    HIP_TRY(s.hcount.reserve(B)); HIP_TRY(s.dcount.reserve(B));
     if (s.in_use) HIP_TRY(hipEventSynchronize(s.used));   // the kernel of two steps ago has consumed this buffer
     const size_t need = (size_t)3 * kmax * B;
-    if (s.cap < need) {
-        if (s.hmeas) hipHostFree(s.hmeas);
-        if (s.dmeas) hipFree(s.dmeas);
-        s.hmeas = nullptr; s.dmeas = nullptr; s.cap = 0;
-        const size_t cap = (size_t)3 * (kmax < 8 && k_stride >= 8 ? 8 : kmax) * B;
-        HIP_TRY(hipHostMalloc((void**)&s.hmeas, sizeof(float) * cap, hipHostMallocNonCoherent));
-        HIP_TRY(hipMalloc(&s.dmeas, sizeof(float) * cap));
-        s.cap = cap;
-    }
+    const size_t cap = (size_t)3 * (kmax < 8 && k_stride >= 8 ? 8 : kmax) * B;   // (grown to at least 8 detections at once)
+    if (s.hmeas.cap() < need) HIP_TRY(s.hmeas.reserve(cap));
+    if (s.dmeas.cap() < need) HIP_TRY(s.dmeas.reserve(cap));
     memcpy(s.hcount, count, sizeof(int32_t) * B);
     if (kmax == k_stride) {
         memcpy(s.hmeas, meas, sizeof(float) * need);
@@ -713,11 +675,11 @@ int slam_step_sim(slam_handle* h, const float cmd[2]) {
     if (!h->dmap) return fail(SLAM_ERR_STATE, "slam_set_map has not been called");
     if (h->shadow) { const int rs = slam_step_sim(h->shadow, cmd); if (rs) return rs; }
     if (h->kind == SLAM_EKF_SLAM && h->lazy_max > 1 && !h->dump_meas && h->run_chunk != 1) {
-        if (h->extq[h->extq_cur].n > 0 || h->devq.n > 0) FLUSH(h);   // measurement-driven steps queued before this one run first
+        if (h->extq[h->extq_cur].n > 0 || h->devq.n > 0) TRY(flush_lazy(h));   // measurement-driven steps queued before this one run first
         h->lazy_cmds.push_back(cmd[0]); h->lazy_cmds.push_back(cmd[1]);
         return (int)(h->lazy_cmds.size() / 2) >= h->lazy_max ? flush_lazy(h) : SLAM_OK;
     }
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
     return launch_step(h, cmd, 1, nullptr, nullptr, 0);
 }
@@ -729,7 +691,7 @@ int slam_queued_steps(const slam_handle* h) {
 
 int slam_set_lazy_steps(slam_handle* h, int n) {
     if (!h || n < 0) return fail(SLAM_ERR_ARG, "bad argument");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     h->lazy_max = n;
     h->lazy_explicit = true;
     return SLAM_OK;
@@ -740,7 +702,7 @@ int slam_run_sim(slam_handle* h, const float* cmds, int T) {
     if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
     if (!h->dmap) return fail(SLAM_ERR_STATE, "slam_set_map has not been called");
     if (h->shadow) { const int rs = slam_run_sim(h->shadow, cmds, T); if (rs) return rs; }
-    FLUSH(h);
+    TRY(flush_lazy(h));
     return run_sim_now(h, cmds, T);
 }
 
@@ -799,11 +761,7 @@ static int run_sim_now(slam_handle* h, const float* cmds, int T) {
     // EKF: every workgroup carries its instance through a whole chunk of timesteps, keeping x_t, the landmark ids,
     // the true pose and the thin rows/cols of P on chip; only the P stream touches HBM each step.
     HIP_TRY(hipSetDevice(h->device));
-    if (h->cmds_cap < T) {
-        if (h->dcmds) { HIP_TRY(hipStreamSynchronize(h->stream)); hipFree(h->dcmds); h->dcmds = nullptr; }
-        HIP_TRY(hipMalloc(&h->dcmds, sizeof(float) * 2 * (size_t)T));
-        h->cmds_cap = T;
-    }
+    TRY(reserve_cmds(h, T));
     HIP_TRY(hipMemcpyAsync(h->dcmds, cmds, sizeof(float) * 2 * (size_t)T, hipMemcpyHostToDevice, h->stream));
     const int chunk = h->run_chunk > 0 ? h->run_chunk : T;
     int long_cap = 0;   // a map with more landmarks than a message of this size class holds: the streamed kernel, a launch per timestep
@@ -834,11 +792,7 @@ static int flush_ext(slam_handle* h) {
     HIP_TRY(hipMemcpyAsync(q.dcount, q.hcount, sizeof(int32_t) * B * T, hipMemcpyHostToDevice, h->copy_stream));
     HIP_TRY(hipMemcpyAsync(q.dmeas, q.hmeas, sizeof(float) * 3 * q.ks * B * T, hipMemcpyHostToDevice, h->copy_stream));
     HIP_TRY(hipEventRecord(q.copied, h->copy_stream));
-    if (h->cmds_cap < T) {
-        if (h->dcmds) { HIP_TRY(hipStreamSynchronize(h->stream)); hipFree(h->dcmds); h->dcmds = nullptr; }
-        HIP_TRY(hipMalloc(&h->dcmds, sizeof(float) * 2 * (size_t)T));
-        h->cmds_cap = T;
-    }
+    TRY(reserve_cmds(h, T));
     HIP_TRY(hipMemcpyAsync(h->dcmds, q.hcmds, sizeof(float) * 2 * (size_t)T, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamWaitEvent(h->stream, q.copied, 0));
     slam::EkfStepParams p;
@@ -861,11 +815,7 @@ static int flush_dev(slam_handle* h) {
     if (q.n == 0) return SLAM_OK;
     const int T = q.n;
     HIP_TRY(hipSetDevice(h->device));
-    if (h->cmds_cap < T) {
-        if (h->dcmds) { HIP_TRY(hipStreamSynchronize(h->stream)); hipFree(h->dcmds); h->dcmds = nullptr; }
-        HIP_TRY(hipMalloc(&h->dcmds, sizeof(float) * 2 * (size_t)T));
-        h->cmds_cap = T;
-    }
+    TRY(reserve_cmds(h, T));
     // pageable source: the copy is staged by the runtime before the call returns, so q.cmds may be reused at once
     HIP_TRY(hipMemcpyAsync(h->dcmds, q.cmds.data(), sizeof(float) * 2 * (size_t)T, hipMemcpyHostToDevice, h->stream));
     slam::EkfStepParams p;
@@ -904,7 +854,7 @@ extern "C" {
 // bit-identical to slam_step_dev.
 int slam_predict(slam_handle* h, const float cmd[2]) {
     if (!h || !cmd) return fail(SLAM_ERR_ARG, "bad argument");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     if (h->kind == SLAM_EKF_SLAM) return fail(SLAM_ERR_UNSUPPORTED, "EKF has no separate prediction stage: EKF::update does both (ekf.cpp:37-179); use slam_step");
     if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
     if (h->predicted) return fail(SLAM_ERR_STATE, "slam_predict called twice without slam_update_dev");
@@ -918,7 +868,7 @@ int slam_predict(slam_handle* h, const float cmd[2]) {
 }
 int slam_update_dev(slam_handle* h, const float* d_meas, const int32_t* d_count, int k_stride) {
     if (!h || k_stride < 0 || (k_stride > 0 && (!d_meas || !d_count))) return fail(SLAM_ERR_ARG, "bad argument");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     if (h->kind == SLAM_EKF_SLAM) return fail(SLAM_ERR_UNSUPPORTED, "EKF has no separate update stage (ekf.cpp:37-179); use slam_step");
     if (!h->predicted) return fail(SLAM_ERR_STATE, "slam_update_dev needs a preceding slam_predict");
     HIP_TRY(hipSetDevice(h->device));
@@ -946,7 +896,7 @@ int slam_update_dev(slam_handle* h, const float* d_meas, const int32_t* d_count,
 // X = [x, x + offset i, x - offset i] with offset i = row i of sqtP (ukf.cpp:214-219) around the x_t that step started from.
 int slam_get_sigma_points(slam_handle* h, int inst, double* X, int32_t* rows, int32_t* cols) {
     if (!h || inst < 0 || inst >= h->B) return fail(SLAM_ERR_ARG, "bad instance");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     if (h->kind == SLAM_EKF_SLAM) return fail(SLAM_ERR_UNSUPPORTED, "sigma points exist for the UKF kinds only");
     if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
     HIP_TRY(hipSetDevice(h->device));
@@ -986,7 +936,7 @@ static int fetch_elems(slam_handle* h, double* dst, const void* dbase, size_t el
 int slam_get_state(slam_handle* h, int inst, double* x, double* P, int32_t* M, int32_t* ids, int32_t* ts) {
     if (!h || inst < 0 || inst >= h->B) return fail(SLAM_ERR_ARG, "bad instance");
     if (h->shadow && inst == h->tracked) return slam_get_state(h->shadow, 0, x, P, M, ids, ts);   // the batch's queue stays queued
-    FLUSH(h);
+    TRY(flush_lazy(h));
     if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1010,7 +960,7 @@ int slam_get_state(slam_handle* h, int inst, double* x, double* P, int32_t* M, i
 
 int slam_get_poses(slam_handle* h, double* poses) {
     if (!h || !poses) return fail(SLAM_ERR_ARG, "bad argument");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (h->esz == 8) {
@@ -1025,7 +975,7 @@ int slam_get_poses(slam_handle* h, double* poses) {
 
 static int copy_out(slam_handle* h, void* dst, const void* src, size_t bytes) {
     if (!h || !dst) return fail(SLAM_ERR_ARG, "bad argument");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
@@ -1037,7 +987,7 @@ int slam_status(slam_handle* h, int32_t* f) { return copy_out(h, f, h ? h->dflag
 
 int slam_get_last_meas(slam_handle* h, float* meas, int32_t* count, int k_stride) {
     if (!h || !meas || !count || k_stride <= 0) return fail(SLAM_ERR_ARG, "bad argument");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
     if (!h->dump_meas || h->k_stride < k_stride) {
         // enable the dump for subsequent slam_step_sim calls; nothing recorded yet for past steps
@@ -1071,7 +1021,7 @@ int slam_error_stats(slam_handle* h, double* avg) {
 extern "C" int slam_internal_error_stats_dev(slam_handle* h, double* d_out, long long pad) {
     if (!h || !d_out || pad < h->B) return fail(SLAM_ERR_ARG, "bad argument");
     if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(slam::launch_avg_error(h->derr, h->dts, h->B, (int)pad, d_out, h->stream));
     HIP_TRY(h->kind == SLAM_EKF_SLAM ? hipStreamSynchronize(h->stream) : hipDeviceSynchronize());
@@ -1107,7 +1057,7 @@ std::vector<CkptItem> ckpt_items(slam_handle* h) {
 
 int slam_save_state(slam_handle* h, const char* path) {
     if (!h || !path) return fail(SLAM_ERR_ARG, "bad argument");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     if (h->predicted) return fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev first");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(h->kind == SLAM_EKF_SLAM ? hipStreamSynchronize(h->stream) : hipDeviceSynchronize());
@@ -1132,7 +1082,7 @@ int slam_save_state(slam_handle* h, const char* path) {
 
 int slam_load_state(slam_handle* h, const char* path) {
     if (!h || !path) return fail(SLAM_ERR_ARG, "bad argument");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(h->kind == SLAM_EKF_SLAM ? hipStreamSynchronize(h->stream) : hipDeviceSynchronize());
     FILE* f = fopen(path, "rb");
@@ -1188,7 +1138,7 @@ int slam_load_state(slam_handle* h, const char* path) {
 
 int slam_track_instance(slam_handle* h, int inst) {
     if (!h || inst >= h->B) return fail(SLAM_ERR_ARG, "bad instance");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     if (h->predicted) return fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev first");
     if (h->shadow) { slam_destroy(h->shadow); h->shadow = nullptr; h->tracked = -1; }
     if (inst < 0) return SLAM_OK;
@@ -1232,7 +1182,7 @@ int slam_track_instance(slam_handle* h, int inst) {
 
 int slam_sync(slam_handle* h) {
     if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->eager_target = h->eager_init;   // the pipeline is drained: the next burst of calls fills it from small launches again
@@ -1243,7 +1193,7 @@ int slam_state_dim_max(const slam_handle* h) { return h ? h->n_max : 0; }
 
 int slam_set_run_chunk(slam_handle* h, int steps_per_launch) {
     if (!h || steps_per_launch < 0) return fail(SLAM_ERR_ARG, "bad argument");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     h->run_chunk = steps_per_launch;
     return SLAM_OK;
 }
@@ -1252,16 +1202,15 @@ int slam_set_run_chunk(slam_handle* h, int steps_per_launch) {
 // The ablation bits are honoured by -DSLAM_ABLATE builds only.
 int slam_set_debug_flags(slam_handle* h, int flags) {
     if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
 #ifndef SLAM_ABLATE
     flags &= (4 | 32 | 128);   // 128: tests only, provokes the watchdog of the EKF step kernel
 #endif
     if ((flags & (4 | 32)) && !h->dprof) {
-        const size_t bytes = sizeof(unsigned long long) * slam::kEkfProfSlots * (size_t)h->B;
-        HIP_TRY(hipMalloc(&h->dprof, bytes));
-        HIP_TRY(hipMemset(h->dprof, 0, bytes));
+        HIP_TRY(h->dprof.reserve(slam::kEkfProfSlots * (size_t)h->B));
+        HIP_TRY(hipMemset(h->dprof, 0, sizeof(unsigned long long) * h->dprof.cap()));
     }
     h->dbg = flags;
     return SLAM_OK;
@@ -1271,7 +1220,7 @@ int slam_variant_available(int L_max, int dtype, int variant) { return slam::ekf
 
 int slam_k_histogram(slam_handle* h, uint64_t out[8], int reset) {
     if (!h || !out) return fail(SLAM_ERR_ARG, "bad argument");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(h->kind == SLAM_EKF_SLAM ? hipStreamSynchronize(h->stream) : hipDeviceSynchronize());
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "histogram element size");
@@ -1283,7 +1232,7 @@ int slam_k_histogram(slam_handle* h, uint64_t out[8], int reset) {
 int slam_traffic_counters(slam_handle* h, uint64_t out[4], int reset) {
     if (!h || !out) return fail(SLAM_ERR_ARG, "bad argument");
     if (h->kind != SLAM_EKF_SLAM) return fail(SLAM_ERR_UNSUPPORTED, "the traffic counters are kept by the EKF step kernels");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(out, h->dkhist + slam::kEkfTrafficSlot, sizeof(uint64_t) * 4, hipMemcpyDeviceToHost));
@@ -1296,7 +1245,7 @@ int slam_traffic_counters(slam_handle* h, uint64_t out[4], int reset) {
 // device before a 20-step launch costs it 9 % (clocks).
 int slam_reset_counters_async(slam_handle* h) {
     if (!h) return fail(SLAM_ERR_ARG, "bad argument");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipMemsetAsync(h->dkhist, 0, sizeof(unsigned long long) * 16, h->stream));
     return SLAM_OK;
@@ -1320,7 +1269,7 @@ int slam_kernel_info(slam_handle* h, int multi_step, char* name, int name_cap, i
 int slam_ukf_sweep_stats(slam_handle* h, uint64_t out[2], int reset) {
     if (!h || !out) return fail(SLAM_ERR_ARG, "bad argument");
     if (h->kind == SLAM_EKF_SLAM) return fail(SLAM_ERR_STATE, "UKF handles only");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipDeviceSynchronize());   // the UKF splits large batches over two streams
     HIP_TRY(hipMemcpy(out, h->dkhist + 8, sizeof(uint64_t) * 2, hipMemcpyDeviceToHost));
@@ -1335,9 +1284,9 @@ int slam_ukf_set_sqrt_mode(slam_handle* h, int mode) {
     if (mode == SLAM_UKF_SQRT_CHOLESKY && h->L_max > slam::kUkfLdsMaxLandmarks)
         return fail(SLAM_ERR_UNSUPPORTED, "the Cholesky square root exists for the LDS size classes only (L_max <= %d), this handle has L_max %d",
                     slam::kUkfLdsMaxLandmarks, h->L_max);
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
-    if (mode == SLAM_UKF_SQRT_CHOLESKY && !h->dchol) HIP_TRY(hipMalloc(&h->dchol, (size_t)h->B));
+    if (mode == SLAM_UKF_SQRT_CHOLESKY) HIP_TRY(h->dchol.reserve((size_t)h->B));
     h->chol = mode == SLAM_UKF_SQRT_CHOLESKY;
     return SLAM_OK;
 }
@@ -1345,7 +1294,7 @@ int slam_ukf_set_sqrt_mode(slam_handle* h, int mode) {
 int slam_ukf_sqrt_stats(slam_handle* h, uint64_t out[2], int reset) {
     if (!h || !out) return fail(SLAM_ERR_ARG, "bad argument");
     if (h->kind == SLAM_EKF_SLAM) return fail(SLAM_ERR_ARG, "UKF handles only");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipDeviceSynchronize());   // the UKF splits large batches over two streams
     HIP_TRY(hipMemcpy(out, h->dkhist + slam::kUkfCholSlot, sizeof(uint64_t) * 2, hipMemcpyDeviceToHost));
@@ -1356,7 +1305,7 @@ int slam_ukf_sqrt_stats(slam_handle* h, uint64_t out[2], int reset) {
 int slam_algorithmic_bytes(slam_handle* h, double* bytes) {
     if (!h || !bytes) return fail(SLAM_ERR_ARG, "bad argument");
     if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipMemsetAsync(h->dscalar, 0, sizeof(double), h->stream));
     HIP_TRY(slam::launch_algorithmic_bytes(h->dM, h->B, h->base, h->esz, h->dscalar, h->stream));
@@ -1369,7 +1318,7 @@ int slam_algorithmic_bytes(slam_handle* h, double* bytes) {
 // (SLAM_DEBUG_FLAGS & 4)
 int slam_debug_read_prof(slam_handle* h, unsigned long long* out) {
     if (!h || !out) return fail(SLAM_ERR_ARG, "bad argument");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (!h->dprof) return fail(SLAM_ERR_STATE, "SLAM_DEBUG_FLAGS has no timer bit (4 / 32) set");
@@ -1386,7 +1335,7 @@ int slam_debug_read_prof(slam_handle* h, unsigned long long* out) {
 // debug only: the raw [B][16] buffer
 int slam_debug_read_prof_raw(slam_handle* h, unsigned long long* out) {
     if (!h || !out) return fail(SLAM_ERR_ARG, "bad argument");
-    FLUSH(h);
+    TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (!h->dprof) return fail(SLAM_ERR_STATE, "SLAM_DEBUG_FLAGS has no timer bit (4 / 32) set");
@@ -1399,16 +1348,13 @@ int slam_debug_read_prof_raw(slam_handle* h, unsigned long long* out) {
 int slam_math_probe(const double* a, const double* b, double* out, int n, int device) {
     if (!a || !b || !out || n <= 0) return fail(SLAM_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(device));
-    double *da, *db, *dout;
-    HIP_TRY(hipMalloc(&da, sizeof(double) * n));
-    HIP_TRY(hipMalloc(&db, sizeof(double) * n));
-    HIP_TRY(hipMalloc(&dout, sizeof(double) * 8 * (size_t)n));
+    DevBuf<double> da, db, dout;   // (released on every return)
+    HIP_TRY(da.reserve(n)); HIP_TRY(db.reserve(n)); HIP_TRY(dout.reserve(8 * (size_t)n));
     HIP_TRY(hipMemcpy(da, a, sizeof(double) * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(db, b, sizeof(double) * n, hipMemcpyHostToDevice));
     HIP_TRY(slam::launch_math_probe(da, db, dout, n, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, dout, sizeof(double) * 8 * (size_t)n, hipMemcpyDeviceToHost));
-    hipFree(da); hipFree(db); hipFree(dout);
     return SLAM_OK;
 }
 
