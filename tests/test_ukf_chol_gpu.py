@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from batch_state import ckpt_layout
 from conftest import load_golden
 from test_ukf_chol_reference import NumpyUKF, cholesky_lower
 
@@ -110,15 +111,10 @@ def test_default_and_explicit_eigen_stay_bit_identical_to_the_oracle(S, oracle):
 
 
 def _ckpt_layout(f, path):
-    """Byte offsets of the P slab and of the warm-start age column in a UKF checkpoint (slam_save_state: header, then
-    P, x, M, ids, flags, timestep, truth, err, sqtP, n_sq, x_prev, V^T, age)."""
-    raw = open(path, "rb").read()
-    hdr = np.frombuffer(raw[8:40], dtype=np.int32)   # kind, B, L_max, dtype, n_max, pstride, xstride, esz
-    B, L_max, ps, xs = int(hdr[1]), int(hdr[2]), int(hdr[5]), int(hdr[6])
-    items = 8 * B * ps + 8 * B * xs + 4 * B + 4 * B * L_max + 4 * B + 4 * B + 24 * B + 8 * B + 8 * B * ps + 4 * B + 8 * B * xs + 8 * B * ps + 4 * B
-    head = len(raw) - items
-    assert 0 < head <= 128, head
-    return bytearray(raw), head, ps, len(raw) - 4 * B
+    """The checkpoint's bytes, the byte offset of the P slab, the P stride and the byte offset of the warm-start age column
+    (tests/batch_state.py: ckpt_layout)."""
+    head, off, hd = ckpt_layout(path)
+    return bytearray(open(path, "rb").read()), head, hd["pstride"], off["age"][0]
 
 
 def test_fallback_on_an_indefinite_P_is_the_cold_eigen_step(S, tmp_path):
