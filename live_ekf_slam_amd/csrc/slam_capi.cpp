@@ -47,6 +47,31 @@ void host_parallel(size_t n, F fn) {
     for (auto& t : th) t.join();
 }
 
+// EKF: consecutive calls of the per-tick entry points (slam_step_sim, slam_step, slam_step_dev) are queued on the host and run as
+// ONE multi-step launch when the queue is full or anything else touches the handle (every other entry point runs it first).  The
+// kernels are asynchronous anyway, and a multi-step launch gives the same bits as single steps, so only the speed changes (one
+// launch per call re-reads x, ids and the thin rows / columns of P and cannot keep update groups open across timesteps).  Steps
+// run in call order, so the queue holds the steps of one source at a time (queue_takes) and one function runs it (flush_lazy).
+struct StepQueue {
+    enum Source { kNone, kSim, kHost, kDev } src = kNone;
+    std::vector<float> cmds;                      // [steps][2]
+    int ks = 0;                                   // detections per instance of this fill (host and device messages)
+    int steps() const { return (int)(cmds.size() / 2); }
+    // host messages (slam_step): each call packs its message into one of two pinned fills; the flush copies the fill on the copy
+    // stream, so packing the next fill overlaps the launch of the last one
+    struct HostFill {
+        PinnedBuf<float> hmeas; PinnedBuf<int32_t> hcount; PinnedBuf<float> hcmds;   // pinned: [lazy_max][B][ks][3], [lazy_max][B], [lazy_max][2]
+        DevBuf<float> dmeas; DevBuf<int32_t> dcount;                                 // device
+        hipEvent_t copied = nullptr, used = nullptr;
+        bool in_use = false;
+    } host[2];
+    int host_cur = 0;
+    int host_ks = 2;                              // stride of the next host fill: the largest message seen so far
+    // device messages (slam_step_dev): copied device-to-device at the call on the compute stream (so the caller may overwrite its
+    // buffers in stream order, as with an immediate launch); one buffer suffices, since copies and launches share the stream
+    DevBuf<float> dmeas; DevBuf<int32_t> dcount;  // [lazy_max][B][ks][3], [lazy_max][B]
+};
+
 }  // namespace
 
 struct slam_handle {
@@ -82,38 +107,12 @@ struct slam_handle {
     hipEvent_t shadow_ev = nullptr;
     uint32_t stage_next = 0;
     DevBuf<unsigned long long> dkhist;                         // [8] instance-steps by detection count
-    // slam_step_sim (EKF): the commands of consecutive calls are queued on the host and run as ONE multi-step launch when the
-    // queue is full or anything else touches the handle (every other entry point flushes first).  The kernels are asynchronous
-    // anyway, and a multi-step launch gives the same bits as single steps, so only the speed changes (one launch per call
-    // re-reads x, ids and the thin rows / columns of P and cannot keep update groups open across timesteps).
-    std::vector<float> lazy_cmds;
+    StepQueue q;                                               // EKF: the queued steps of slam_step_sim, slam_step and slam_step_dev
     int eager_init = 2;                                        // first idle-GPU launch size (SLAM_EAGER_FLUSH, 0 = off)
     int eager_target = 2;                                      // queued steps an idle GPU is given at once (doubles per such launch)
     bool lazy_explicit = false;                                // slam_set_lazy_steps / SLAM_LAZY_STEPS asked for queueing: slam_step_dev queues only then
     int lazy_max = 32;                                         // 0 / 1 = off (SLAM_LAZY_STEPS, slam_set_lazy_steps); per launch a workgroup pays
                                                                // ~25 us of start / drain: 16 -> 61 M, 32 -> 66 M, 64 -> 70 M steps/s (one launch: 73 M)
-    // slam_step (EKF, HOST measurements): the same queueing.  Each call packs its message (stride kExtQ detections per
-    // instance; a message with more goes through the immediate path) and its command into one of two pinned queues of up to
-    // lazy_max timesteps; a flush copies the queue on the copy stream and runs ONE multi-step launch that takes the message of
-    // timestep t from the device-side queue instead of the generator.
-    struct ExtQueue {
-        PinnedBuf<float> hmeas; PinnedBuf<int32_t> hcount; PinnedBuf<float> hcmds;   // pinned: [cap][B][kExtQ][3], [cap][B], [cap][2]
-        DevBuf<float> dmeas; DevBuf<int32_t> dcount;                                 // device
-        int cap = 0, n = 0;                                                          // cap: timesteps every buffer of the queue holds
-        int ks = 0;                                                                  // detections per instance of this fill (<= kExtQ)
-        hipEvent_t copied = nullptr, used = nullptr;
-        bool in_use = false;
-    } extq[2];
-    int extq_cur = 0;
-    int extq_ks = 2;                                                                 // stride of the next fill: largest message seen so far
-    // slam_step_dev (EKF, DEVICE measurements): the same queueing.  The message is copied device-to-device into the queue on
-    // the compute stream at the call (so the caller may overwrite its buffers in stream order, as with an immediate launch)
-    // and up to lazy_max of them run as one multi-step launch.  One buffer suffices: copies and launches share the stream.
-    struct DevQueue {
-        DevBuf<float> dmeas; DevBuf<int32_t> dcount;   // [lazy_max][B][ks][3], [lazy_max][B]
-        std::vector<float> cmds;
-        int ks = 0, n = 0;
-    } devq;
     // slam_track_instance: instance `tracked` also runs in a one-instance SHADOW filter (same config, seed, map and GLOBAL
     // instance id, hence the same bits: results do not depend on how a batch is partitioned), stepped at once at every step
     // call on its own stream, so that slam_get_state(h, tracked) - the publishState of every tick, localization_node.cpp:139 -
@@ -141,7 +140,21 @@ struct slam_handle {
 
 namespace {
 
-void fill_params(slam_handle* h, slam::EkfStepParams& p, const float cmd[2]) {
+// The fields of a step launch that say where its input comes from, either filter kind: `sim` = the device-side generator, else messages of
+// stride k_stride at meas / count; long_cap > 0: messages may exceed the size class (long_message_cap).  The generator's measurements are
+// dumped while slam_get_last_meas asked for them.
+template <class Params>
+void set_step_input(const slam_handle* h, Params& p, int sim, int long_cap, const float* meas, const int32_t* count, int k_stride) {
+    p.sim = sim;
+    p.long_mode = long_cap > 0 ? 1 : 0; p.long_cap = long_cap;
+    p.meas_in = meas; p.meas_count_in = count; p.k_stride_in = k_stride;
+    if (sim && h->dump_meas) { p.meas_out = h->dmeas; p.meas_count_out = h->dcount; p.k_stride_out = h->k_stride; }
+}
+
+// Every EKF step launch: T = 0 is one timestep with `cmd`; T > 0 is a multi-step launch over the device commands d_cmds, whose first
+// command is `cmd`, with the messages of timestep t at meas + t * B * k_stride * 3 / count + t * B.
+void fill_ekf_params(slam_handle* h, slam::EkfStepParams& p, const float cmd[2], int sim, int long_cap, const float* meas, const int32_t* count,
+                     int k_stride, const float* d_cmds, int T) {
     memset(&p, 0, sizeof(p));
     p.P = h->dP; p.P_out = h->dP2; p.x = h->dx; p.scratch = h->dscratch; p.M = h->dM; p.ids = h->dids; p.flags = h->dflags; p.timestep = h->dts;
     p.truth = h->dtruth; p.err_sum = h->derr; p.map = h->dmap; p.L = h->L;
@@ -164,6 +177,8 @@ void fill_params(slam_handle* h, slam::EkfStepParams& p, const float cmd[2]) {
     p.dbg = h->dbg;
     p.prof = (h->dbg & (4 | 32)) ? h->dprof : nullptr;
     p.khist = h->dkhist;
+    set_step_input(h, p, sim, long_cap, meas, count, k_stride);
+    p.cmds = d_cmds; p.T = T;
 }
 
 void fill_ukf_params(slam_handle* h, slam::UkfStepParams& p, const float cmd[2]) {
@@ -216,6 +231,18 @@ int long_message_cap(slam_handle* h, int sim, int k_stride, int* cap_out) {
     return SLAM_OK;
 }
 
+// one UKF timestep of instances [b_off, b_off + b_cnt) on `stream`
+int launch_ukf_pair(slam_handle* h, const float cmd[2], int sim, int long_cap, const float* meas, const int32_t* count, int k_stride,
+                    int b_off, int b_cnt, hipStream_t stream) {
+    slam::UkfStepParams p;
+    fill_ukf_params(h, p, cmd);
+    set_step_input(h, p, sim, long_cap, meas, count, k_stride);
+    p.b_off = b_off; p.b_cnt = b_cnt;
+    HIP_TRY(slam::launch_ukf_sqrt(p, stream));   // nearestSPD + sqrt (ukf.cpp:106-123,208)
+    HIP_TRY(slam::launch_ukf_step(p, stream));   // predictionStage + updateStage (ukf.cpp:197-372)
+    return SLAM_OK;
+}
+
 // one timestep, either filter kind; `sim` = device-side measurement generator
 int launch_step(slam_handle* h, const float cmd[2], int sim, const float* d_meas, const int32_t* d_count, int k_stride) {
     if (h->predicted) return fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev before the next step");
@@ -223,24 +250,13 @@ int launch_step(slam_handle* h, const float cmd[2], int sim, const float* d_meas
     if (const int rc = long_message_cap(h, sim, k_stride, &long_cap)) return rc;
     if (h->kind == SLAM_EKF_SLAM) {
         slam::EkfStepParams p;
-        fill_params(h, p, cmd);
-        p.sim = sim;
-        p.long_mode = long_cap > 0 ? 1 : 0; p.long_cap = long_cap;
-        p.meas_in = d_meas; p.meas_count_in = d_count; p.k_stride_in = k_stride;
-        if (sim && h->dump_meas) { p.meas_out = h->dmeas; p.meas_count_out = h->dcount; p.k_stride_out = h->k_stride; }
+        fill_ekf_params(h, p, cmd, sim, long_cap, d_meas, d_count, k_stride, nullptr, 0);
         HIP_TRY(slam::launch_ekf_step(p, h->waves_per_filter, h->esz == 4, h->stream));
     } else {
-        slam::UkfStepParams p;
-        fill_ukf_params(h, p, cmd);
-        p.sim = sim;
-        p.long_mode = long_cap > 0 ? 1 : 0; p.long_cap = long_cap;
-        p.meas_in = d_meas; p.meas_count_in = d_count; p.k_stride_in = k_stride;
-        if (sim && h->dump_meas) { p.meas_out = h->dmeas; p.meas_count_out = h->dcount; p.k_stride_out = h->k_stride; }
-        HIP_TRY(slam::launch_ukf_sqrt(p, h->stream));   // nearestSPD + sqrt (ukf.cpp:106-123,208)
-        HIP_TRY(slam::launch_ukf_step(p, h->stream));   // predictionStage + updateStage (ukf.cpp:197-372)
+        TRY(launch_ukf_pair(h, cmd, sim, long_cap, d_meas, d_count, k_stride, 0, h->B, h->stream));
+        std::swap(h->dP, h->dP2);   // UKF: the kernel wrote the next P_t into the other buffer (the EKF kernel updates dP in place)
     }
-    if (h->kind != SLAM_EKF_SLAM) std::swap(h->dP, h->dP2);   // UKF: the kernel wrote the next P_t into the other buffer
-    h->step += 1;                                              // (the EKF kernel updates dP in place)
+    h->step += 1;
     return SLAM_OK;
 }
 
@@ -265,9 +281,16 @@ int reserve_cmds(slam_handle* h, int T) {
 
 static int run_sim_now(slam_handle* h, const float* cmds, int T);
 static int flush_lazy(slam_handle* h);
-static int flush_ext(slam_handle* h);
-static int flush_dev(slam_handle* h);
-// The queues exist to give the GPU long multi-step launches while the caller keeps calling once per tick; when the GPU has
+// Whether the EKF step queue can take one more step from `src` as it stands: it is empty, or it holds steps of the same source with a
+// compatible stride (host messages: at most the stride of the fill, device messages: the same stride) and has room.  If it cannot, the
+// caller runs the queue first, so that steps run in call order.
+static bool queue_takes(const slam_handle* h, StepQueue::Source src, int ks) {
+    const StepQueue& q = h->q;
+    if (q.steps() == 0) return true;
+    const bool stride_ok = src == StepQueue::kHost ? ks <= q.ks : ks == q.ks;
+    return q.src == src && stride_ok && q.steps() < h->lazy_max;
+}
+// The queue exists to give the GPU long multi-step launches while the caller keeps calling once per tick; when the GPU has
 // nothing to do, waiting for the queue to fill only delays the work (a run of K calls paid one whole queue of packing with
 // the GPU idle before the first launch).  So a queued step is launched at once if the compute stream is idle.
 // Launching every single queued step would waste the multi-step kernel (2.4 vs 1.5 ms per step), so the idle-GPU launch
@@ -433,8 +456,8 @@ int slam_destroy(slam_handle* h) {
     for (auto& ev : h->aux_ev) if (ev) hipEventDestroy(ev);
     if (h->copy_stream) { hipStreamSynchronize(h->copy_stream); hipStreamDestroy(h->copy_stream); }
     if (h->shadow_ev) hipEventDestroy(h->shadow_ev);
-    for (auto& q : h->extq)
-        if (q.copied) { hipEventDestroy(q.copied); hipEventDestroy(q.used); }
+    for (auto& f : h->q.host)
+        if (f.copied) { hipEventDestroy(f.copied); hipEventDestroy(f.used); }
     for (auto& s : h->stage)
         if (s.copied) { hipEventDestroy(s.copied); hipEventDestroy(s.used); }
     if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
@@ -539,20 +562,20 @@ int slam_step_dev(slam_handle* h, const float cmd[2], const float* d_meas, const
     // call enqueues only its device-to-device copy on the stream, not the step itself
     if (h->kind == SLAM_EKF_SLAM && h->lazy_explicit && h->lazy_max > 1 && h->run_chunk != 1 && !h->dump_meas &&
         k_stride <= slam::ekf_class_message_capacity(h->L_max)) {   // (messages that may be longer: one launch pair per step, launch_step)
-        slam_handle::DevQueue& q = h->devq;
-        if (!h->lazy_cmds.empty() || h->extq[h->extq_cur].n > 0 || (q.n > 0 && q.ks != k_stride)) TRY(flush_lazy(h));   // earlier steps first
+        StepQueue& q = h->q;
+        if (!queue_takes(h, StepQueue::kDev, k_stride)) TRY(flush_lazy(h));   // earlier steps first
         const size_t B = (size_t)h->B;
         const size_t steps = (size_t)h->lazy_max;
         if (q.dmeas.cap() < 3 * (size_t)k_stride * B * steps || q.dcount.cap() < B * steps) {
             if (q.dmeas) HIP_TRY(hipStreamSynchronize(h->stream));
             HIP_TRY(q.dmeas.reserve(3 * (size_t)k_stride * B * steps)); HIP_TRY(q.dcount.reserve(B * steps));
         }
-        q.ks = k_stride;   // (q.n == 0 or the same stride: a queue of another stride was flushed above)
-        HIP_TRY(hipMemcpyAsync(q.dmeas + (size_t)q.n * B * k_stride * 3, d_meas, sizeof(float) * 3 * (size_t)k_stride * B, hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(q.dcount + (size_t)q.n * B, d_count, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, h->stream));
+        const size_t n = (size_t)q.steps();
+        HIP_TRY(hipMemcpyAsync(q.dmeas + n * B * k_stride * 3, d_meas, sizeof(float) * 3 * (size_t)k_stride * B, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(q.dcount + n * B, d_count, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, h->stream));
+        q.src = StepQueue::kDev; q.ks = k_stride;
         q.cmds.push_back(cmd[0]); q.cmds.push_back(cmd[1]);
-        q.n += 1;
-        return q.n >= h->lazy_max ? flush_dev(h) : SLAM_OK;
+        return q.steps() >= h->lazy_max ? flush_lazy(h) : SLAM_OK;
     }
     TRY(flush_lazy(h));
     if (h->kind == SLAM_UKF_LOC && !h->dmapf) return fail(SLAM_ERR_STATE, "UKF_LOC needs the known map: call slam_set_map first (localization_node.cpp:113-116)");
@@ -567,65 +590,58 @@ int slam_step(slam_handle* h, const float cmd[2], const float* meas, const int32
         const int rs = slam_step(h->shadow, cmd, meas + (size_t)h->tracked * k_stride * 3, count + h->tracked, k_stride);
         if (rs) return rs;
     }
-    if (h->kind == SLAM_EKF_SLAM && h->lazy_max > 1 && h->run_chunk != 1) {
-        const size_t B = (size_t)h->B;
-        int kmax = 0;
-        for (size_t b = 0; b < B; ++b) kmax = count[b] > kmax ? count[b] : kmax;   // 65 536 ints: ~20 us
-        kmax = kmax < k_stride ? kmax : k_stride;
-        if (kmax <= kExtQ) {
-            if (!h->lazy_cmds.empty() || h->devq.n > 0) TRY(flush_lazy(h));   // steps queued through the other entry points run first
-            // a fill of the queue has ONE stride (detections per instance): the largest message this handle has seen so far, at
-            // least 2 (a high-water mark: a stride per fill taken from its first message ended fills early whenever a larger
-            // message followed, 46 instead of 65 M steps/s); a message above the mark ends the fill and raises it
-            if (kmax > h->extq_ks) {
-                if (h->extq[h->extq_cur].n > 0) TRY(flush_lazy(h));
-                h->extq_ks = kmax;
-            }
-            slam_handle::ExtQueue& q = h->extq[h->extq_cur];
-            if (q.n == 0) q.ks = h->extq_ks;
-            // capacity: the full stride kExtQ at once while that stays below 128 MB per queue (re-pinning 100 MB of host memory
+    const size_t B = (size_t)h->B;
+    int kmax = 0;   // the longest message, clamped to k_stride
+    for (size_t b = 0; b < B; ++b) kmax = count[b] > kmax ? count[b] : kmax;   // 65 536 ints: ~20 us
+    kmax = kmax < k_stride ? kmax : k_stride;
+    if (h->kind == SLAM_EKF_SLAM && h->lazy_max > 1 && h->run_chunk != 1 && kmax <= kExtQ) {
+        StepQueue& q = h->q;
+        // a fill of the queue has ONE stride (detections per instance): the largest message this handle has seen so far, at
+        // least 2 (a high-water mark: a stride per fill taken from its first message ended fills early whenever a larger
+        // message followed, 46 instead of 65 M steps/s); a message above the mark ends the fill and raises it
+        if (!queue_takes(h, StepQueue::kHost, kmax)) TRY(flush_lazy(h));
+        if (kmax > q.host_ks) q.host_ks = kmax;
+        StepQueue::HostFill& f = q.host[q.host_cur];
+        if (q.steps() == 0) {
+            if (f.in_use) { HIP_TRY(hipEventSynchronize(f.used)); f.in_use = false; }   // the launch that read this fill is done
+            // capacity: the full stride kExtQ at once while that stays below 128 MB per fill (re-pinning 100 MB of host memory
             // costs ~40 ms each time the stride grows: 0.5 ms per step over a 300-step run); above that, the stride actually seen
             const size_t full = (size_t)3 * kExtQ * B * h->lazy_max;
-            const size_t need = sizeof(float) * full <= ((size_t)128 << 20) ? full : (size_t)3 * q.ks * B * h->lazy_max;   // floats
-            if (q.cap < h->lazy_max || q.hmeas.cap() < need || q.dmeas.cap() < need) {
-                if (q.n > 0) TRY(flush_lazy(h));
-                if (q.in_use) { HIP_TRY(hipEventSynchronize(q.used)); q.in_use = false; }
-                HIP_TRY(q.hmeas.reserve(need)); HIP_TRY(q.hcount.reserve(B * h->lazy_max)); HIP_TRY(q.hcmds.reserve(2 * (size_t)h->lazy_max));
-                HIP_TRY(q.dmeas.reserve(need)); HIP_TRY(q.dcount.reserve(B * h->lazy_max));
-                q.cap = h->lazy_max;
-                if (!q.copied) {
-                    HIP_TRY(hipEventCreateWithFlags(&q.copied, hipEventDisableTiming));
-                    HIP_TRY(hipEventCreateWithFlags(&q.used, hipEventDisableTiming));
-                }
+            const size_t need = sizeof(float) * full <= ((size_t)128 << 20) ? full : (size_t)3 * q.host_ks * B * h->lazy_max;   // floats
+            HIP_TRY(f.hmeas.reserve(need)); HIP_TRY(f.hcount.reserve(B * h->lazy_max)); HIP_TRY(f.hcmds.reserve(2 * (size_t)h->lazy_max));
+            HIP_TRY(f.dmeas.reserve(need)); HIP_TRY(f.dcount.reserve(B * h->lazy_max));
+            if (!f.copied) {
+                HIP_TRY(hipEventCreateWithFlags(&f.copied, hipEventDisableTiming));
+                HIP_TRY(hipEventCreateWithFlags(&f.used, hipEventDisableTiming));
             }
-            if (q.n == 0 && q.in_use) { HIP_TRY(hipEventSynchronize(q.used)); q.in_use = false; }   // the launch that read this queue is done
-            const int ks = q.ks;
-            float* dst = q.hmeas + (size_t)q.n * B * ks * 3;
-            int32_t* dcnt = q.hcount + (size_t)q.n * B;
-            const int kc = k_stride < ks ? k_stride : ks;   // detections per instance that are packed
-            // The count is clamped to what is packed, like the immediate path clamps to k_stride, so the kernel never
-            // reads a slot this call did not fill.  The copy itself has a compile-time size (kc detections, all within the caller's
-            // k_stride): a per-instance variable-length memcpy made the call six times slower (1.28 vs 0.2 ms at batch 65 536).
-            auto pack = [&](auto kc_tag) {
-                constexpr int KC = decltype(kc_tag)::value;
-                host_parallel(B, [&](size_t b0, size_t b1) {
-                    for (size_t b = b0; b < b1; ++b) {
-                        const int cb = count[b];
-                        dcnt[b] = cb < 0 ? 0 : (cb < KC ? cb : KC);
-                        memcpy(dst + b * ks * 3, meas + b * (size_t)k_stride * 3, sizeof(float) * 3 * KC);
-                    }
-                });
-            };
-            switch (kc) {
-                case 1: pack(std::integral_constant<int, 1>{}); break;
-                case 2: pack(std::integral_constant<int, 2>{}); break;
-                case 3: pack(std::integral_constant<int, 3>{}); break;
-                default: pack(std::integral_constant<int, 4>{}); break;   // kc <= ks <= kExtQ = 4
-            }
-            q.hcmds[2 * q.n] = cmd[0]; q.hcmds[2 * q.n + 1] = cmd[1];
-            q.n += 1;
-            return (q.n >= h->lazy_max || eager_flush(h, q.n)) ? flush_ext(h) : SLAM_OK;
+            q.src = StepQueue::kHost; q.ks = q.host_ks;
         }
+        const int ks = q.ks;
+        const size_t n = (size_t)q.steps();
+        float* dst = f.hmeas + n * B * ks * 3;
+        int32_t* dcnt = f.hcount + n * B;
+        const int kc = k_stride < ks ? k_stride : ks;   // detections per instance that are packed
+        // The count is clamped to what is packed, like the immediate path clamps to k_stride, so the kernel never
+        // reads a slot this call did not fill.  The copy itself has a compile-time size (kc detections, all within the caller's
+        // k_stride): a per-instance variable-length memcpy made the call six times slower (1.28 vs 0.2 ms at batch 65 536).
+        auto pack = [&](auto kc_tag) {
+            constexpr int KC = decltype(kc_tag)::value;
+            host_parallel(B, [&](size_t b0, size_t b1) {
+                for (size_t b = b0; b < b1; ++b) {
+                    const int cb = count[b];
+                    dcnt[b] = cb < 0 ? 0 : (cb < KC ? cb : KC);
+                    memcpy(dst + b * ks * 3, meas + b * (size_t)k_stride * 3, sizeof(float) * 3 * KC);
+                }
+            });
+        };
+        switch (kc) {
+            case 1: pack(std::integral_constant<int, 1>{}); break;
+            case 2: pack(std::integral_constant<int, 2>{}); break;
+            case 3: pack(std::integral_constant<int, 3>{}); break;
+            default: pack(std::integral_constant<int, 4>{}); break;   // kc <= ks <= kExtQ = 4
+        }
+        q.cmds.push_back(cmd[0]); q.cmds.push_back(cmd[1]);
+        return (q.steps() >= h->lazy_max || eager_flush(h, q.steps())) ? flush_lazy(h) : SLAM_OK;
     }
     TRY(flush_lazy(h));
     if (h->kind == SLAM_UKF_LOC && !h->dmapf) return fail(SLAM_ERR_STATE, "UKF_LOC needs the known map: call slam_set_map first (localization_node.cpp:113-116)");
@@ -635,10 +651,7 @@ int slam_step(slam_handle* h, const float cmd[2], const float* meas, const int32
     // blocks only when it gets two steps ahead of the GPU.
     slam_handle::Stage& s = h->stage[h->stage_next & 1];
     h->stage_next += 1;
-    const size_t B = (size_t)h->B;
-    int kmax = 1;
-    for (size_t b = 0; b < B; ++b) kmax = count[b] > kmax ? count[b] : kmax;
-    kmax = kmax < k_stride ? kmax : k_stride;
+    if (kmax < 1) kmax = 1;
     if (!h->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
     if (!s.copied) {
         HIP_TRY(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
@@ -675,9 +688,11 @@ int slam_step_sim(slam_handle* h, const float cmd[2]) {
     if (!h->dmap) return fail(SLAM_ERR_STATE, "slam_set_map has not been called");
     if (h->shadow) { const int rs = slam_step_sim(h->shadow, cmd); if (rs) return rs; }
     if (h->kind == SLAM_EKF_SLAM && h->lazy_max > 1 && !h->dump_meas && h->run_chunk != 1) {
-        if (h->extq[h->extq_cur].n > 0 || h->devq.n > 0) TRY(flush_lazy(h));   // measurement-driven steps queued before this one run first
-        h->lazy_cmds.push_back(cmd[0]); h->lazy_cmds.push_back(cmd[1]);
-        return (int)(h->lazy_cmds.size() / 2) >= h->lazy_max ? flush_lazy(h) : SLAM_OK;
+        StepQueue& q = h->q;
+        if (!queue_takes(h, StepQueue::kSim, 0)) TRY(flush_lazy(h));   // measurement-driven steps queued before this one run first
+        q.src = StepQueue::kSim; q.ks = 0;
+        q.cmds.push_back(cmd[0]); q.cmds.push_back(cmd[1]);
+        return q.steps() >= h->lazy_max ? flush_lazy(h) : SLAM_OK;
     }
     TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
@@ -686,7 +701,7 @@ int slam_step_sim(slam_handle* h, const float cmd[2]) {
 
 int slam_queued_steps(const slam_handle* h) {
     if (!h) return 0;
-    return (int)(h->lazy_cmds.size() / 2) + h->extq[h->extq_cur].n + h->devq.n;
+    return h->q.steps();
 }
 
 int slam_set_lazy_steps(slam_handle* h, int n) {
@@ -728,17 +743,11 @@ static int run_sim_now(slam_handle* h, const float* cmds, int T) {
         int long_cap = 0;
         if (const int rc = long_message_cap(h, 1, 0, &long_cap)) return rc;
         for (int t = 0; t < T; ++t) {
-            slam::UkfStepParams p;
-            fill_ukf_params(h, p, cmds + 2 * (size_t)t);
-            p.sim = 1;
-            p.long_mode = long_cap > 0 ? 1 : 0; p.long_cap = long_cap;
             for (int part = 0; part < NP; ++part) {
-                p.b_off = part * per;
-                p.b_cnt = h->B - p.b_off < per ? h->B - p.b_off : per;
-                if (p.b_cnt <= 0) continue;
-                hipStream_t st = part ? h->aux_stream[part - 1] : h->stream;
-                HIP_TRY(slam::launch_ukf_sqrt(p, st));
-                HIP_TRY(slam::launch_ukf_step(p, st));
+                const int b_off = part * per;
+                const int b_cnt = h->B - b_off < per ? h->B - b_off : per;
+                if (b_cnt <= 0) continue;
+                TRY(launch_ukf_pair(h, cmds + 2 * (size_t)t, 1, long_cap, nullptr, nullptr, 0, b_off, b_cnt, part ? h->aux_stream[part - 1] : h->stream));
             }
             std::swap(h->dP, h->dP2);
             h->step += 1;
@@ -769,80 +778,54 @@ static int run_sim_now(slam_handle* h, const float* cmds, int T) {
     for (int t0 = 0; t0 < T; t0 += chunk) {
         const int tc = T - t0 < chunk ? T - t0 : chunk;
         slam::EkfStepParams p;
-        fill_params(h, p, cmds + 2 * (size_t)t0);
-        p.sim = 1;
-        p.long_mode = long_cap > 0 ? 1 : 0; p.long_cap = long_cap;
-        p.cmds = h->dcmds + 2 * (size_t)t0;
-        p.T = tc;
+        fill_ekf_params(h, p, cmds + 2 * (size_t)t0, 1, long_cap, nullptr, nullptr, 0, h->dcmds + 2 * (size_t)t0, tc);
         HIP_TRY(slam::launch_ekf_step(p, h->waves_per_filter, h->esz == 4, h->stream));
         h->step += (uint32_t)tc;
     }
     return SLAM_OK;
 }
 
-static int flush_ext(slam_handle* h) {
-    slam_handle::ExtQueue& q = h->extq[h->extq_cur];
-    if (q.n == 0) return SLAM_OK;
-    const int T = q.n;
-    const size_t B = (size_t)h->B;
-    // q.n is reset only after the launch has been enqueued: a failing flush keeps the queued timesteps (and fails again on the
-    // next call) instead of dropping them silently
-    HIP_TRY(hipSetDevice(h->device));
-    if (!h->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    HIP_TRY(hipMemcpyAsync(q.dcount, q.hcount, sizeof(int32_t) * B * T, hipMemcpyHostToDevice, h->copy_stream));
-    HIP_TRY(hipMemcpyAsync(q.dmeas, q.hmeas, sizeof(float) * 3 * q.ks * B * T, hipMemcpyHostToDevice, h->copy_stream));
-    HIP_TRY(hipEventRecord(q.copied, h->copy_stream));
-    TRY(reserve_cmds(h, T));
-    HIP_TRY(hipMemcpyAsync(h->dcmds, q.hcmds, sizeof(float) * 2 * (size_t)T, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamWaitEvent(h->stream, q.copied, 0));
-    slam::EkfStepParams p;
-    fill_params(h, p, q.hcmds);
-    p.sim = 0;
-    p.meas_in = q.dmeas; p.meas_count_in = q.dcount; p.k_stride_in = q.ks;
-    p.cmds = h->dcmds;
-    p.T = T;
-    HIP_TRY(slam::launch_ekf_step(p, h->waves_per_filter, h->esz == 4, h->stream));
-    q.n = 0;
-    h->step += (uint32_t)T;
-    HIP_TRY(hipEventRecord(q.used, h->stream));
-    q.in_use = true;
-    h->extq_cur ^= 1;
-    return SLAM_OK;
-}
-
-static int flush_dev(slam_handle* h) {
-    slam_handle::DevQueue& q = h->devq;
-    if (q.n == 0) return SLAM_OK;
-    const int T = q.n;
-    HIP_TRY(hipSetDevice(h->device));
-    TRY(reserve_cmds(h, T));
-    // pageable source: the copy is staged by the runtime before the call returns, so q.cmds may be reused at once
-    HIP_TRY(hipMemcpyAsync(h->dcmds, q.cmds.data(), sizeof(float) * 2 * (size_t)T, hipMemcpyHostToDevice, h->stream));
-    slam::EkfStepParams p;
-    fill_params(h, p, q.cmds.data());
-    p.sim = 0;
-    p.meas_in = q.dmeas; p.meas_count_in = q.dcount; p.k_stride_in = q.ks;
-    p.cmds = h->dcmds;
-    p.T = T;
-    HIP_TRY(slam::launch_ekf_step(p, h->waves_per_filter, h->esz == 4, h->stream));
-    q.n = 0;               // only now: a failed flush keeps its timesteps
-    q.cmds.clear();
-    h->step += (uint32_t)T;
-    return SLAM_OK;
-}
-
+// Runs what the step queue holds: messages as one multi-step launch, generator steps through run_sim_now.  The queue is emptied only
+// once the launch is enqueued: a failed flush keeps the queued timesteps (and fails again on the next call) instead of dropping them
+// silently.
 static int flush_lazy(slam_handle* h) {
-    {
-        const int rc = flush_dev(h);
-        if (rc) return rc;
+    StepQueue& q = h->q;
+    const int T = q.steps();
+    if (T == 0) return SLAM_OK;
+    StepQueue::HostFill& f = q.host[q.host_cur];
+    if (q.src == StepQueue::kSim) {
+        TRY(run_sim_now(h, q.cmds.data(), T));   // chunking (run_chunk) and messages longer than the size class apply here too
+    } else {
+        const size_t B = (size_t)h->B;
+        HIP_TRY(hipSetDevice(h->device));
+        const float* cmds = q.cmds.data();
+        const float* meas = q.dmeas; const int32_t* count = q.dcount;
+        if (q.src == StepQueue::kHost) {
+            if (!h->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+            HIP_TRY(hipMemcpyAsync(f.dcount, f.hcount, sizeof(int32_t) * B * T, hipMemcpyHostToDevice, h->copy_stream));
+            HIP_TRY(hipMemcpyAsync(f.dmeas, f.hmeas, sizeof(float) * 3 * q.ks * B * T, hipMemcpyHostToDevice, h->copy_stream));
+            HIP_TRY(hipEventRecord(f.copied, h->copy_stream));
+            memcpy(f.hcmds, cmds, sizeof(float) * 2 * (size_t)T);
+            cmds = f.hcmds; meas = f.dmeas; count = f.dcount;
+        }
+        TRY(reserve_cmds(h, T));
+        // device messages: a pageable source, so the copy is staged by the runtime before the call returns and q.cmds may be reused at once
+        HIP_TRY(hipMemcpyAsync(h->dcmds, cmds, sizeof(float) * 2 * (size_t)T, hipMemcpyHostToDevice, h->stream));
+        if (q.src == StepQueue::kHost) HIP_TRY(hipStreamWaitEvent(h->stream, f.copied, 0));
+        slam::EkfStepParams p;
+        fill_ekf_params(h, p, cmds, 0, 0, meas, count, q.ks, h->dcmds, T);
+        HIP_TRY(slam::launch_ekf_step(p, h->waves_per_filter, h->esz == 4, h->stream));
+        h->step += (uint32_t)T;
     }
-    if (!h->lazy_cmds.empty()) {
-        std::vector<float> c;
-        c.swap(h->lazy_cmds);
-        const int rc = run_sim_now(h, c.data(), (int)(c.size() / 2));
-        if (rc) { if (h->lazy_cmds.empty()) h->lazy_cmds.swap(c); return rc; }   // a failed launch keeps the queued commands
+    const StepQueue::Source src = q.src;
+    q.src = StepQueue::kNone;
+    q.cmds.clear();
+    if (src == StepQueue::kHost) {   // the next fill packs into the other buffers while this one is copied and read
+        HIP_TRY(hipEventRecord(f.used, h->stream));
+        f.in_use = true;
+        q.host_cur ^= 1;
     }
-    return flush_ext(h);
+    return SLAM_OK;
 }
 
 extern "C" {
