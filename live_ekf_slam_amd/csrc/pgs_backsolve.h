@@ -83,7 +83,7 @@ constexpr int BTPB = 256;
 __global__ __launch_bounds__(BTPB) void pgs_backsolve_kernel(const PgsParams p) {
     const int b = pgs_slot(p, blockIdx.x), tid = threadIdx.x;
     if (p.state[b] || !p.solve_ok[b]) return;
-    const int N = pgs_N(p, b), KP = p.KP;
+    const int N = p.N, KP = p.KP;
     const Inst g = inst_view(p, b);
     const double* gpb = p.gp + (size_t)b * p.N_max * 3;
     const double* Eb = p.E + (size_t)b * p.N_max * KP * 6;

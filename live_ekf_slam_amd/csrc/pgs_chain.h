@@ -26,7 +26,7 @@ __global__ __launch_bounds__(1024) void pgs_chain_kernel(const PgsParams p) {
     __shared__ int s_fail;
     const int b = pgs_slot(p, blockIdx.x), tid = threadIdx.x;
     if (p.state[b]) return;
-    const int N = pgs_N(p, b), LD = p.LD, m2 = 2 * p.M[b];
+    const int N = p.N, LD = p.LD, m2 = 2 * p.M[b];
     const double lambda = p.lambda[b];
     const double* Ab = p.A + (size_t)b * p.N_max * 9;
     const double* Cb = p.C + (size_t)b * p.N_max * 9;

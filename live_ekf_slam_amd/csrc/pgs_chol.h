@@ -4,8 +4,8 @@
 
 // Dense blocked Cholesky of S (2M x 2M, lower, in place; the right-hand-side row 2M rides along as one more panel row,
 // which IS the forward substitution) followed by the blocked backward substitution; dl = S^-1 rhs.
-// CTPB threads per instance: 1024 when few instances are active (the factorisation is a chain of short latency-bound
-// phases: more wavefronts shorten each), 256 when many are (more instances resident per CU).
+// Right-looking, CTPB = 1024 threads per instance (the factorisation is a chain of short latency-bound phases: more wavefronts shorten
+// each).  It runs where the left-looking kernel below does not: LD > 448, whose staging registers that kernel is not sized for.
 template <int CTPB>
 __global__ __launch_bounds__(CTPB) void pgs_chol_kernel(const PgsParams p) {
     constexpr int NB = 16, NBL = 4;   // panel width: fewer, fatter panel steps (each costs several HBM/L2 round trips)
@@ -171,13 +171,13 @@ __global__ __launch_bounds__(CTPB) void pgs_chol_kernel(const PgsParams p) {
 // LDS once per panel for all tiles), stays on chip through the factorisation of its diagonal block and its panel solve, and is written to
 // memory once, as L.  Per element the arithmetic is the SAME chain of fused multiply-adds in ascending k as before (the right-looking
 // kernel rounds to fp64 between panels exactly where this chain does), the diagonal block and the panel solve are the same code: the
-// factor is bit-identical to the right-looking kernel's (SLAM_PGS_CHOL_LL=0 keeps the old one for the comparison).
+// factor is bit-identical to the right-looking kernel's.
 #ifndef SLAM_PGS_LL_KU
 #define SLAM_PGS_LL_KU 4
 #endif
-// CTPB_ threads: 768 by default since the end of round 5 - three wavefronts per SIMD have 168 registers per lane and the kernel no longer spills (at 1024 threads =
+// CTPB_ threads: 768 since the end of round 5 - three wavefronts per SIMD have 168 registers per lane and the kernel no longer spills (at 1024 threads =
 // 128 registers it kept 56 bytes per lane in scratch, most of it around the completion step): 13.4 -> 11.5 ms per solve on one box (docs/dev/sessions/gpu_r5aq.sh), the
-// same factor bit for bit.  SLAM_PGS_CHOL_LL=1 keeps the 1024-thread instantiation.
+// same factor bit for bit.
 template <int CTPB_>
 __global__ __launch_bounds__(CTPB_) void pgs_chol_ll_kernel(const PgsParams p) {
     constexpr int CTPB = CTPB_, NB = 16, NBL = 4, NW = CTPB / 64;

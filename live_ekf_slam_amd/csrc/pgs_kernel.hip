@@ -70,10 +70,6 @@ hipError_t pgs_launch_lm_begin(const PgsParams& p, hipStream_t s) {
 
 hipError_t pgs_launch_trial_kernel(const PgsParams& p, int which, hipStream_t s) {
     const int nslot = pgs_nslot(p);   // slots covered: the instances of the group and their active lambda lanes, or the compacted list
-    if (which == 6) {   // the decide kernel alone (split_decide): one workgroup per graph of the group, whatever the list holds
-        hipLaunchKernelGGL(pgs_decide_kernel, dim3(p.b_cnt), dim3(TPB), 0, s, p);
-        return hipGetLastError();
-    }
     if (nslot <= 0) return hipSuccess;
     switch (which) {
     case 0:
@@ -118,30 +114,20 @@ hipError_t pgs_launch_trial_kernel(const PgsParams& p, int which, hipStream_t s)
             hipLaunchKernelGGL(pgs_syrk_inst_kernel, dim3(8 * SI_NB * ((nslot + 7) / 8)), dim3(SI_TPB), lds, s, p);
             break;
         }
-        if (p.syrk_wave_tile == 64) {
-            const int nt = (p.LD + 127) / 128;
-            hipLaunchKernelGGL(pgs_syrk_kernel<64>, dim3(8 * (nt * (nt + 1) / 2) * ((nslot + 7) / 8)), dim3(256), 0, s, p);
-        } else {
-            const int nt = (p.LD + 63) / 64;
-            hipLaunchKernelGGL(pgs_syrk_kernel<32>, dim3(8 * (nt * (nt + 1) / 2) * ((nslot + 7) / 8)), dim3(256), 0, s, p);
-        }
+        const int nt = (p.LD + 63) / 64;
+        hipLaunchKernelGGL(pgs_syrk_kernel<32>, dim3(8 * (nt * (nt + 1) / 2) * ((nslot + 7) / 8)), dim3(256), 0, s, p);
         break;
     }
     case 3: {
-        const size_t lds = sizeof(double) * (size_t)(p.LD + 16) * 17;   // panel rows x (NB + 1)
         // panels of L_max > 235 need more than the default 64 KiB of dynamic LDS (gfx950: 160 KiB); solve groups launch from several
         // host threads and a single-process host may hold several devices: per (kernel, device), checked (lds_attr.h)
-        const void* ck = p.chol_threads == 256 ? (const void*)pgs_chol_kernel<256> : (p.chol_ll == 1 && p.LD <= 448) ? (const void*)pgs_chol_ll_kernel<1024>
-                       : (p.chol_ll && p.LD <= 448) ? (const void*)pgs_chol_ll_kernel<768> : (const void*)pgs_chol_kernel<1024>;
-        if (const hipError_t e = slam_allow_full_lds(ck); e != hipSuccess) return e;
-        if (p.chol_threads == 256) { hipLaunchKernelGGL(pgs_chol_kernel<256>, dim3(nslot), dim3(256), lds, s, p); break; }
-        if (p.chol_ll && p.LD <= 448) {   // left-looking: two consecutive panels [<= LD + 1][17] each, the staged block rows over the older one (its staging registers are sized for LD <= 448)
-            const size_t lds_ll = sizeof(double) * 2 * (size_t)(p.LD + 1) * 17;
-            if (p.chol_ll == 1) hipLaunchKernelGGL(pgs_chol_ll_kernel<1024>, dim3(nslot), dim3(1024), lds_ll, s, p);
-            else hipLaunchKernelGGL(pgs_chol_ll_kernel<768>, dim3(nslot), dim3(768), lds_ll, s, p);
-            break;
+        if (p.LD <= 448) {   // left-looking: two consecutive panels [<= LD + 1][17] each, the staged block rows over the older one (its staging registers are sized for LD <= 448)
+            if (const hipError_t e = slam_allow_full_lds((const void*)pgs_chol_ll_kernel<768>); e != hipSuccess) return e;
+            hipLaunchKernelGGL(pgs_chol_ll_kernel<768>, dim3(nslot), dim3(768), sizeof(double) * 2 * (size_t)(p.LD + 1) * 17, s, p);
+        } else {             // right-looking: panel rows x (NB + 1)
+            if (const hipError_t e = slam_allow_full_lds((const void*)pgs_chol_kernel<1024>); e != hipSuccess) return e;
+            hipLaunchKernelGGL(pgs_chol_kernel<1024>, dim3(nslot), dim3(1024), sizeof(double) * (size_t)(p.LD + 16) * 17, s, p);
         }
-        hipLaunchKernelGGL(pgs_chol_kernel<1024>, dim3(nslot), dim3(1024), lds, s, p);
         break;
     }
     case 4:
@@ -154,16 +140,9 @@ hipError_t pgs_launch_trial_kernel(const PgsParams& p, int which, hipStream_t s)
     default:   // the candidates of every slot, then GTSAM's accept / lambda / convergence logic per instance
         if (p.nfact_max > 0) hipLaunchKernelGGL(pgs_eval_factor_kernel, dim3(nslot * ((p.nfact_max + LF_TPB - 1) / LF_TPB)), dim3(LF_TPB), 0, s, p);
         hipLaunchKernelGGL(pgs_evaluate_kernel, dim3(nslot), dim3(TPB), 0, s, p);
-        if (!p.split_decide) hipLaunchKernelGGL(pgs_decide_kernel, dim3(p.b_cnt), dim3(TPB), 0, s, p);
+        hipLaunchKernelGGL(pgs_decide_kernel, dim3(p.b_cnt), dim3(TPB), 0, s, p);
         break;
     }
-    return hipGetLastError();
-}
-
-hipError_t pgs_launch_tick(const PgsParams& p, hipStream_t s) {
-    hipLaunchKernelGGL(pgs_tick_kernel, dim3(p.B), dim3(256), 0, s, p);
-    hipLaunchKernelGGL(pgs_seg_plan_kernel, dim3(p.B), dim3(256), 0, s, p);
-    hipLaunchKernelGGL(pgs_lm_begin_kernel, dim3(p.B), dim3(TPB), 0, s, p);
     return hipGetLastError();
 }
 

@@ -16,16 +16,13 @@ __device__ __forceinline__ int pgs_slot(const PgsParams& p, int bl) {
     const int lane = bl / p.b_cnt;
     return lane * p.B + p.b_off + (bl - lane * p.b_cnt);
 }
-// poses of the graph behind slot b: the handle's (lockstep) or the graph's own (asynchronous ticks: lanes are off, slot == instance)
-__device__ __forceinline__ int pgs_N(const PgsParams& p, int b) { return p.Nv ? p.Nv[b] : p.N; }
 // slots a trial-kernel launch covers
 __host__ __device__ __forceinline__ int pgs_nslot(const PgsParams& p) { return p.use_list ? p.n_list : p.b_cnt * (p.lanes > 0 ? p.lanes : 1); }
 
 __global__ __launch_bounds__(TPB) void pgs_lm_begin_kernel(const PgsParams p) {
     __shared__ double s_buf[TPB];
     const int b = blockIdx.x + p.b_off, tid = threadIdx.x;
-    if (p.async_ticks && p.state[b] != 6) return;   // asynchronous ticks: only the graphs whose next tick was just appended
-    const int N = pgs_N(p, b), M = p.M[b];
+    const int N = p.N, M = p.M[b];
     double* pw = p.pw + (size_t)b * p.N_max * 3;
     double* lw = p.lw + (size_t)b * p.L_max * 2;
     const double* p0 = p.pose0 + (size_t)b * p.N_max * 3;
@@ -125,11 +122,8 @@ __global__ __launch_bounds__(TPB) void pgs_lm_begin_kernel(const PgsParams p) {
         p.iters[b] = 0; p.trials[b] = 0; p.solve_ok[b] = 1; p.nl[b] = 1;
         // first trial: every instance of the group, one lane - or, streaming, the first slots_cap of them; the others wait
         const bool runs = p.slots_cap <= 0 || (int)blockIdx.x < p.slots_cap;
-        if (p.async_ticks) p.state[b] = 4;         // the next decide kernel lists it
-        else {
-            p.state[b] = runs ? 0 : 2;
-            if (runs) p.alist[blockIdx.x] = b;
-        }
+        p.state[b] = runs ? 0 : 2;
+        if (runs) p.alist[blockIdx.x] = b;
         for (int j = 0; j < p.lanes_max; ++j) p.lin_ok[(size_t)j * p.B + b] = 0;   // (the clones copy nothing of this: plain per-slot state)
         p.flags[b] &= ~(PGS_FLAG_NOT_CONVERGED | PGS_FLAG_NONFINITE);
     }
@@ -202,7 +196,7 @@ __global__ __launch_bounds__(LF_TPB) void pgs_lin_factor_kernel(const PgsParams 
 __global__ __launch_bounds__(TPB) void pgs_linearize_kernel(const PgsParams p) {
     const int b = pgs_slot(p, blockIdx.x), tid = threadIdx.x;
     if (p.state[b]) return;
-    const int N = pgs_N(p, b), KP = p.KP, M = p.M[b];
+    const int N = p.N, KP = p.KP, M = p.M[b];
     if (p.seg_on && tid == 0) p.solve_ok[b] = 1;   // segmented elimination: a failing segment / separator clears it (the sequential chain kernel sets it itself)
     if (p.lin_ok[b]) return;                       // the previous trial of this slot failed: same values, same linearisation
     const Inst g = inst_view(p, b);

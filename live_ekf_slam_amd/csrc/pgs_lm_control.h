@@ -1,4 +1,4 @@
-// pgs_lm_control.h — evaluation of a candidate, GTSAM's accept / lambda / convergence logic (pgs_decide_kernel, incl. the streaming refill and the asynchronous ticks), end / adopt / tick / average error.
+// pgs_lm_control.h — evaluation of a candidate, GTSAM's accept / lambda / convergence logic (pgs_decide_kernel, incl. the streaming refill), end / adopt / average error.
 // Part of pgs_kernel.hip (round 6: split by phase, pure moves); included there inside namespace slam { namespace {.  DESIGN.md 4.4.
 #pragma once
 
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(TPB) void pgs_evaluate_kernel(const PgsParams p) {
     __shared__ double s_buf[TPB];
     const int b = pgs_slot(p, blockIdx.x), tid = threadIdx.x;
     if (p.state[b]) return;
-    const int N = pgs_N(p, b), KP = p.KP, M = p.M[b];
+    const int N = p.N, KP = p.KP, M = p.M[b];
     const Inst g = inst_view(p, b);
     double* pose = p.pw + (size_t)b * p.N_max * 3;
     double* lm = p.lw + (size_t)b * p.L_max * 2;
@@ -143,22 +143,8 @@ __global__ __launch_bounds__(TPB) void pgs_decide_kernel(const PgsParams p) {
     __shared__ int s_win, s_next;
     const int b = blockIdx.x + p.b_off, tid = threadIdx.x;
     const bool running = p.state[b] == 0;
-    if (p.async_ticks) {
-        // asynchronous ticks: a graph whose next solve is prepared (state 4: pgs_lm_begin_kernel on the tick stream, complete before this
-        // launch) joins the next trial's list; the counters the host sizes the coming grids from ride along
-        if (tid == 0) {
-            if (blockIdx.x == 0) { p.n_active[5] = p.mono[0]; p.n_active[6] = p.mono[1]; }
-            const int stt = p.state[b];
-            if (stt == 4) {
-                p.state[b] = 0;
-                atomicAdd(p.n_active, 1); atomicMax(p.n_active + 1, 1);
-                p.alist[atomicAdd(p.n_active + 2, 1)] = b;
-            } else if (stt == 3 || stt == 5 || stt == 6) atomicAdd(p.n_active, 1);   // between two solves: still counts as unfinished
-        }
-        if (!running) return;
-    }
     if (!running && p.slots_cap <= 0) return;
-    const int N = pgs_N(p, b), M = p.M[b], B = p.B;
+    const int N = p.N, M = p.M[b], B = p.B;
     if (running) {
     if (tid == 0) {
         const double lambdaFactor = 10.0, lambdaUpper = 1e5, minFidelity = 1e-3, relTol = 1e-5, absTol = 1e-5;
@@ -200,9 +186,9 @@ __global__ __launch_bounds__(TPB) void pgs_decide_kernel(const PgsParams p) {
             else if (error <= 0.0 || relDec <= relTol || absDec <= absTol) done = 1;
             else p.cur_error[b] = error;
         }
-        // the trial cap is per GRAPH: where the host's count of launches is not a graph's count of trials (asynchronous ticks, streaming) the decide
-        // step applies it (lockstep: the host stops launching + pgs_lm_end_kernel)
-        if ((p.async_ticks || p.slots_cap > 0) && !done && trials >= p.max_trials) { done = 1; fl = PGS_FLAG_NOT_CONVERGED; }
+        // the trial cap is per GRAPH: where the host's count of launches is not a graph's count of trials (streaming) the decide step
+        // applies it (lockstep: the host stops launching + pgs_lm_end_kernel)
+        if (p.slots_cap > 0 && !done && trials >= p.max_trials) { done = 1; fl = PGS_FLAG_NOT_CONVERGED; }
         atomicAdd(p.work + (p.seg_on ? 2 : (p.fused ? 1 : 0)), (double)(trials - p.trials[b]) * p.inst_flop[b]);   // reporting only
         p.lambda[b] = lambda; p.error[b] = error; p.iters[b] = iters; p.trials[b] = trials;
         // the next trial runs the next `lanes_next` lambdas of the sequence GTSAM would walk if every one of them failed:
@@ -220,11 +206,7 @@ __global__ __launch_bounds__(TPB) void pgs_decide_kernel(const PgsParams p) {
         }
         for (int j = 1; j < p.lanes_max; ++j) p.state[j * B + b] = (!done && j < nnext) ? 0 : 1;
         p.nl[b] = nnext;
-        if (done) {
-            p.flags[b] |= fl;
-            if (p.async_ticks) { p.state[b] = 3; atomicAdd(p.n_active, 1); }   // parked until pgs_tick_kernel has advanced it (or finished it)
-            else p.state[b] = 1;
-        }
+        if (done) { p.flags[b] |= fl; p.state[b] = 1; }
         else {
             atomicAdd(p.n_active, 1); atomicMax(p.n_active + 1, nnext);
             const int at = atomicAdd(p.n_active + 2, nnext);
@@ -295,7 +277,7 @@ __global__ __launch_bounds__(256) void pgs_clone_kernel(const PgsParams p, const
 // result <- current values (also for instances cut off by the trial cap)
 __global__ __launch_bounds__(TPB) void pgs_lm_end_kernel(const PgsParams p) {
     const int b = blockIdx.x + p.b_off, tid = threadIdx.x;
-    const int N = pgs_N(p, b), M = p.M[b];
+    const int N = p.N, M = p.M[b];
     const double* pw = p.pw + (size_t)b * p.N_max * 3;
     const double* lw = p.lw + (size_t)b * p.L_max * 2;
     double* p1 = p.pose1 + (size_t)b * p.N_max * 3;
@@ -307,7 +289,7 @@ __global__ __launch_bounds__(TPB) void pgs_lm_end_kernel(const PgsParams p) {
 
 __global__ __launch_bounds__(TPB) void pgs_adopt_kernel(const PgsParams p) {
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int N = pgs_N(p, b), M = p.M[b];
+    const int N = p.N, M = p.M[b];
     double* p0 = p.pose0 + (size_t)b * p.N_max * 3;
     double* l0 = p.lm0 + (size_t)b * p.L_max * 2;
     const double* p1 = p.pose1 + (size_t)b * p.N_max * 3;
@@ -322,69 +304,12 @@ __global__ __launch_bounds__(TPB) void pgs_adopt_kernel(const PgsParams p) {
     }
 }
 
-// Asynchronous ticks: the step between two solves of ONE graph (pose_graph.cpp:258-264, then the next timer tick's :216-256).  result <-
-// current values (pgs_lm_end_kernel), initial_estimate <- result (pgs_adopt_kernel), the sums over the ticks; then - unless the graph has
-// reached T_end - the graph's next simulator tick, NaiveFilter::update and the append (pgs_run_sim_kernel's body for one timestep, with the
-// graph's own timestep as the noise stream's step index).  State 3 (solve converged) / 5 (first tick: nothing to adopt) -> 6, or 1 = finished.
-__global__ __launch_bounds__(256) void pgs_tick_kernel(const PgsParams p) {
-    constexpr int KCAP = 256;   // (every detection reaches append_step: pgs_run_sim_kernel)
-    __shared__ float s_meas[3 * KCAP];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int st = p.state[b];
-    if (st != 3 && st != 5) return;
-    const int N = p.Nv[b], M = p.M[b];
-    if (st == 3) {
-        const double* pw = p.pw + (size_t)b * p.N_max * 3;
-        const double* lw = p.lw + (size_t)b * p.L_max * 2;
-        double* p0 = p.pose0 + (size_t)b * p.N_max * 3;
-        double* l0 = p.lm0 + (size_t)b * p.L_max * 2;
-        double* p1 = p.pose1 + (size_t)b * p.N_max * 3;
-        double* l1 = p.lm1 + (size_t)b * p.L_max * 2;
-        for (int i = tid; i < 3 * N; i += 256) { const double v = pw[i]; p1[i] = v; p0[i] = v; }
-        for (int i = tid; i < 2 * M; i += 256) { const double v = lw[i]; l1[i] = v; l0[i] = v; }
-        if (tid == 0 && p.tick_acc) { p.tick_acc[2 * b] += p.iters[b]; p.tick_acc[2 * b + 1] += p.trials[b]; }
-        if (tid == 0 && p.tick_flop) {
-            const double n = 2.0 * M, tr = (double)p.trials[b];
-            p.tick_flop[2 * b] += tr * p.inst_flop[b];
-            p.tick_flop[2 * b + 1] += tr * (n * n * n / 3.0 + 2.0 * n * n);
-        }
-    }
-    const int i = N - 1, t1 = N;   // the graph's timestep, the pose the tick adds
-    if (i >= p.T_end || t1 >= p.N_max) {
-        if (tid == 0) { p.state[b] = 1; if (i < p.T_end) p.flags[b] |= PGS_FLAG_POSE_CAP; }
-        return;
-    }
-    if (tid >= 64) return;
-    const int lane = tid;
-    double tx = p.truth[3 * b], ty = p.truth[3 * b + 1], tth = p.truth[3 * b + 2];
-    double lmx = 0.0, lmy = 0.0;
-    if (lane < p.L) { lmx = p.map[2 * lane]; lmy = p.map[2 * lane + 1]; }
-    const float fwd = p.cmds[2 * i], ang = p.cmds[2 * i + 1];
-    int k = sim_wave<KCAP>(p, b, lane, fwd, ang, (uint32_t)i, tx, ty, tth, lmx, lmy, s_meas);
-    if (k > KCAP) { k = KCAP; if (lane == 0) p.flags[b] |= PGS_FLAG_MEAS_CAP; }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    if (lane == 0) {
-        double s, c;
-        const double th = p.cur[3 * b + 2];
-        det_sincos(th, &s, &c);
-        p.cur[3 * b] = p.cur[3 * b] + (double)fwd * c;
-        p.cur[3 * b + 1] = p.cur[3 * b + 1] + (double)fwd * s;
-        p.cur[3 * b + 2] = remainder(th + (double)ang, kTwoPi);
-        double* th_hist = p.truth_hist + ((size_t)b * p.N_max + (t1 - 1)) * 2;
-        th_hist[0] = tx; th_hist[1] = ty;
-        append_step(p, b, t1, s_meas, k);
-        p.Nv[b] = N + 1;
-        atomicMax(p.mono + 1, N + 1);
-        p.state[b] = 6;
-    }
-}
-
 // compute_average_error as the pose-graph plot calls it (plotting_node.py:203-213,432-434): pose i of the message
 // (i < timestep, float32 on the wire) against true_poses[i] = the true pose after step i+1.
 __global__ __launch_bounds__(TPB) void pgs_avg_error_kernel(const PgsParams p, int which, double* out) {
     __shared__ double s_buf[TPB];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int ts = pgs_N(p, b) - 1;
+    const int ts = p.N - 1;
     const double* pose = (which ? p.pose1 : p.pose0) + (size_t)b * p.N_max * 3;
     const double* th = p.truth_hist + (size_t)b * p.N_max * 2;
     double acc = 0.0;

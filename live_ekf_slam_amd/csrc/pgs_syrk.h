@@ -2,12 +2,9 @@
 // Part of pgs_kernel.hip (round 6: split by phase, pure moves); included there inside namespace slam { namespace {.  DESIGN.md 4.4.
 #pragma once
 
-// S_ext = [D + lambda I, .; gl^T, .] - Y^T Y on 128x128 tiles of the lower triangle; 4 wavefronts x (64x64) each = 4x4
-// accumulators of v_mfma_f64_16x16x4_f64 per wavefront (8 operand loads feed 16 MFMAs: the kernel is bound by the
-// L2 -> L1 operand stream, not by HBM, so the wave tile is as large as the register file allows).  Row 2M of S_ext is
-// the right-hand side gl - Y^T z.
-// WT = wavefront tile (64: bulk trials, most instances active; 32: straggler trials, where the few active instances need
-// more wavefronts each).  Workgroup tile SY_T = 2 * WT.
+// S_ext = [D + lambda I, .; gl^T, .] - Y^T Y on 64x64 tiles of the lower triangle; 4 wavefronts x (32x32) each = 2x2
+// accumulators of v_mfma_f64_16x16x4_f64 per wavefront.  Row 2M of S_ext is the right-hand side gl - Y^T z.
+// WT = wavefront tile: 32, the one build (a 64-wide wavefront tile was measured slower at every batch size).  Workgroup tile SY_T = 2 * WT.
 template <int WT>
 __global__ __launch_bounds__(256, 2) void pgs_syrk_kernel(const PgsParams p) {
     constexpr int SY_T = 2 * WT, NI = WT / 16;
@@ -33,12 +30,12 @@ __global__ __launch_bounds__(256, 2) void pgs_syrk_kernel(const PgsParams p) {
     const int rowbase = ti * SY_T + wr * WT, colbase = tj * SY_T + wc * WT;
     if (rowbase > m2 || colbase > m2) return;
     // (segmented elimination: the block of Y rows is the separators' - syrk_row0 / syrk_rows / syrk_first, pgs_kernel.h)
-    const int K3 = p.syrk_rows >= 0 ? (p.Nv ? 3 * seg_ns(pgs_N(p, b), p.seg_len) : p.syrk_rows) : 3 * pgs_N(p, b);
+    const int K3 = p.syrk_rows >= 0 ? p.syrk_rows : 3 * p.N;
     int k0 = 0;
     // Y[k][c] == 0 before the first detection of column c's landmark, and landmarks are numbered in order of first
-    // detection: this wavefront's 64 rows are all zero before pose lm_first[rowbase / 2] (unless it holds the z row)
+    // detection: this wavefront's WT rows are all zero before pose lm_first[rowbase / 2] (unless it holds the z row)
     const int32_t* firstrow = p.syrk_first ? p.syrk_first : p.lm_first;
-    if (rowbase + WT - 1 < m2 && !p.syrk_notrim) k0 = (3 * firstrow[(size_t)b * p.L_max + (rowbase >> 1)]) & ~3;
+    if (rowbase + WT - 1 < m2) k0 = (3 * firstrow[(size_t)b * p.L_max + (rowbase >> 1)]) & ~3;
     if (k0 > K3) k0 = K3 & ~3;
     const double* Yb = p.Y + (size_t)b * p.y_stride + (size_t)p.syrk_row0 * p.LD;
     dbl4_t acc[NI][NI];
@@ -54,7 +51,7 @@ __global__ __launch_bounds__(256, 2) void pgs_syrk_kernel(const PgsParams p) {
         ca[h] = rowbase + 16 * h + cl; if (ca[h] >= LD) ca[h] = LD - 1;
         cb[h] = colbase + 16 * h + cl; if (cb[h] >= LD) cb[h] = LD - 1;
     }
-    constexpr int KU = WT == 64 ? 2 : 4;   // k-steps (of 4 rows) in flight
+    constexpr int KU = 4;   // k-steps (of 4 rows) in flight
     const int Kfull = k0 + ((K3 - k0) / (4 * KU)) * (4 * KU);
     const double* row = Yb + (size_t)(k0 + kq) * LD;
 #pragma unroll 1
@@ -106,133 +103,131 @@ __global__ __launch_bounds__(256, 2) void pgs_syrk_kernel(const PgsParams p) {
                 }
                 acc[i][j][r4] = v;
             }
-    if constexpr (WT == 32) {
-        if (p.seg_on) {
-            // Segmented elimination: this launch covered the separators' rows of Y; the interior rows' products arrive as the segments'
-            // Gram matrices T_p (pgs_seg_gram_kernel) and are subtracted here, segment after segment - a fixed order per element.  A
-            // segment touches this wavefront's 32 x 32 tile only if it sees a landmark of the tile's row block AND one of its column block
-            // (seg_blk: the local ranges of the 16-landmark blocks): a handful of the segments for a tile near the diagonal, none far from
-            // it; the right-hand-side row (the gradient column of every segment) meets them all.
-            const int nb1 = seg_nb1(p.L_max), nseg = seg_ns(pgs_N(p, b), p.seg_len) + 1;
-            const int32_t* blk = p.seg_blk + (size_t)b * p.nseg_max * nb1;
-            const int32_t* sinv = p.seg_inv + (size_t)b * p.nseg_max * p.L_max;
-            const int32_t* ncolb = p.seg_ncol + (size_t)b * p.nseg_max;
-            const int TLD = p.seg_tld;
-            const size_t TSZ = (size_t)TLD * TLD;
-            const double* Tb = p.segT + (size_t)b * p.nseg_max * TSZ;
-            const int rb = rowbase >> 5, cb = colbase >> 5;
-            const bool has_rhs = m2 >= rowbase && m2 < rowbase + WT;
-            if (has_rhs) {   // wave-uniform
-                // The right-hand-side row meets EVERY segment (its gradient column); one segment at a time that was 32 dependent
-                // round trips for the tiles of the last row block.  Lane l takes column colbase + l of the row: the index loads of eight
-                // segments go out together, then the eight T entries, then the subtractions in segment order.
-                __shared__ double s_rhs[4][WT];
-                double* rh = s_rhs[w];
+    if (p.seg_on) {
+        // Segmented elimination: this launch covered the separators' rows of Y; the interior rows' products arrive as the segments'
+        // Gram matrices T_p (pgs_seg_gram_kernel) and are subtracted here, segment after segment - a fixed order per element.  A
+        // segment touches this wavefront's 32 x 32 tile only if it sees a landmark of the tile's row block AND one of its column block
+        // (seg_blk: the local ranges of the 16-landmark blocks): a handful of the segments for a tile near the diagonal, none far from
+        // it; the right-hand-side row (the gradient column of every segment) meets them all.
+        const int nb1 = seg_nb1(p.L_max), nseg = seg_ns(p.N, p.seg_len) + 1;
+        const int32_t* blk = p.seg_blk + (size_t)b * p.nseg_max * nb1;
+        const int32_t* sinv = p.seg_inv + (size_t)b * p.nseg_max * p.L_max;
+        const int32_t* ncolb = p.seg_ncol + (size_t)b * p.nseg_max;
+        const int TLD = p.seg_tld;
+        const size_t TSZ = (size_t)TLD * TLD;
+        const double* Tb = p.segT + (size_t)b * p.nseg_max * TSZ;
+        const int rb = rowbase >> 5, cb = colbase >> 5;
+        const bool has_rhs = m2 >= rowbase && m2 < rowbase + WT;
+        if (has_rhs) {   // wave-uniform
+            // The right-hand-side row meets EVERY segment (its gradient column); one segment at a time that was 32 dependent
+            // round trips for the tiles of the last row block.  Lane l takes column colbase + l of the row: the index loads of eight
+            // segments go out together, then the eight T entries, then the subtractions in segment order.
+            __shared__ double s_rhs[4][WT];
+            double* rh = s_rhs[w];
 #pragma unroll
-                for (int i = 0; i < NI; ++i)
+            for (int i = 0; i < NI; ++i)
 #pragma unroll
-                    for (int j = 0; j < NI; ++j)
+                for (int j = 0; j < NI; ++j)
 #pragma unroll
-                        for (int r4 = 0; r4 < 4; ++r4)
-                            if (rowbase + 16 * i + kq + 4 * r4 == m2) rh[16 * j + cl] = acc[i][j][r4];
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                const int c = colbase + lane;
-                if (lane < WT && c < m2) {
-                    const int jl = c >> 1, d = c & 1;
-                    double v = rh[lane];
-                    constexpr int SB = 8;
+                    for (int r4 = 0; r4 < 4; ++r4)
+                        if (rowbase + 16 * i + kq + 4 * r4 == m2) rh[16 * j + cl] = acc[i][j][r4];
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            const int c = colbase + lane;
+            if (lane < WT && c < m2) {
+                const int jl = c >> 1, d = c & 1;
+                double v = rh[lane];
+                constexpr int SB = 8;
 #pragma unroll 1
-                    for (int ps0 = 0; ps0 < nseg; ps0 += SB) {
-                        int q[SB], nl[SB];
+                for (int ps0 = 0; ps0 < nseg; ps0 += SB) {
+                    int q[SB], nl[SB];
 #pragma unroll
-                        for (int u = 0; u < SB; ++u) {
-                            const int ps = ps0 + u < nseg ? ps0 + u : nseg - 1;
-                            q[u] = ps0 + u < nseg ? sinv[(size_t)ps * p.L_max + jl] : -1;
-                            nl[u] = ncolb[ps];
-                        }
-                        double t[SB];
-#pragma unroll
-                        for (int u = 0; u < SB; ++u) {
-                            const int ps = ps0 + u < nseg ? ps0 + u : nseg - 1;
-                            t[u] = q[u] >= 0 ? Tb[(size_t)ps * TSZ + (size_t)(2 * nl[u]) * TLD + 2 * q[u] + d] : 0.0;
-                        }
-#pragma unroll
-                        for (int u = 0; u < SB; ++u)
-                            if (q[u] >= 0) v = v - t[u];
+                    for (int u = 0; u < SB; ++u) {
+                        const int ps = ps0 + u < nseg ? ps0 + u : nseg - 1;
+                        q[u] = ps0 + u < nseg ? sinv[(size_t)ps * p.L_max + jl] : -1;
+                        nl[u] = ncolb[ps];
                     }
-                    rh[lane] = v;
+                    double t[SB];
+#pragma unroll
+                    for (int u = 0; u < SB; ++u) {
+                        const int ps = ps0 + u < nseg ? ps0 + u : nseg - 1;
+                        t[u] = q[u] >= 0 ? Tb[(size_t)ps * TSZ + (size_t)(2 * nl[u]) * TLD + 2 * q[u] + d] : 0.0;
+                    }
+#pragma unroll
+                    for (int u = 0; u < SB; ++u)
+                        if (q[u] >= 0) v = v - t[u];
                 }
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-#pragma unroll
-                for (int i = 0; i < NI; ++i)
-#pragma unroll
-                    for (int j = 0; j < NI; ++j)
-#pragma unroll
-                        for (int r4 = 0; r4 < 4; ++r4)
-                            if (rowbase + 16 * i + kq + 4 * r4 == m2 && colbase + 16 * j + cl < m2) acc[i][j][r4] = rh[16 * j + cl];
+                rh[lane] = v;
             }
-            // Which segments touch the tile: one LANE per segment tests its seg_blk row, a ballot gives the list - one round trip for all of
-            // them (segment after segment with scalar loads it was one per segment, ~30 of them for the handful that are relevant).  The
-            // relevant ones are then subtracted in ascending order, the index loads of the next one in flight beside the T entries of the
-            // current one: about one dependent round trip per relevant segment instead of two.
-            auto load_idx = [&](const int ps, int (&lr)[NI][4], int (&lc)[NI]) {
-                const int32_t* iv = sinv + (size_t)ps * p.L_max;
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+            for (int i = 0; i < NI; ++i)
+#pragma unroll
+                for (int j = 0; j < NI; ++j)
+#pragma unroll
+                    for (int r4 = 0; r4 < 4; ++r4)
+                        if (rowbase + 16 * i + kq + 4 * r4 == m2 && colbase + 16 * j + cl < m2) acc[i][j][r4] = rh[16 * j + cl];
+        }
+        // Which segments touch the tile: one LANE per segment tests its seg_blk row, a ballot gives the list - one round trip for all of
+        // them (segment after segment with scalar loads it was one per segment, ~30 of them for the handful that are relevant).  The
+        // relevant ones are then subtracted in ascending order, the index loads of the next one in flight beside the T entries of the
+        // current one: about one dependent round trip per relevant segment instead of two.
+        auto load_idx = [&](const int ps, int (&lr)[NI][4], int (&lc)[NI]) {
+            const int32_t* iv = sinv + (size_t)ps * p.L_max;
+#pragma unroll
+            for (int i = 0; i < NI; ++i)
+#pragma unroll
+                for (int r4 = 0; r4 < 4; ++r4) {
+                    const int r = rowbase + 16 * i + kq + 4 * r4;
+                    int l = -1;
+                    if (r < m2) { const int q = iv[r >> 1]; l = q >= 0 ? 2 * q + (r & 1) : -1; }
+                    lr[i][r4] = l;
+                }
+#pragma unroll
+            for (int j = 0; j < NI; ++j) {
+                const int c = colbase + 16 * j + cl;
+                int l = -1;
+                if (c < m2) { const int q = iv[c >> 1]; l = q >= 0 ? 2 * q + (c & 1) : -1; }
+                lc[j] = l;
+            }
+        };
+#pragma unroll 1
+        for (int ps0 = 0; ps0 < nseg; ps0 += 64) {
+            bool rel = false;
+            if (ps0 + lane < nseg) {
+                const int32_t* bk = blk + (size_t)(ps0 + lane) * nb1;
+                rel = bk[rb + 1] > bk[rb] && bk[cb + 1] > bk[cb];
+            }
+            unsigned long long mask = __ballot(rel);   // wave-uniform from here on
+            int lr[NI][4], lc[NI];
+            int ps = mask ? ps0 + (__ffsll((long long)mask) - 1) : -1;
+            if (ps >= 0) load_idx(ps, lr, lc);
+#pragma unroll 1
+            while (ps >= 0) {
+                mask &= mask - 1ull;
+                const int psn = mask ? ps0 + (__ffsll((long long)mask) - 1) : -1;
+                int lrn[NI][4], lcn[NI];
+#pragma unroll
+                for (int i = 0; i < NI; ++i) {
+                    lcn[i] = -1;
+#pragma unroll
+                    for (int r4 = 0; r4 < 4; ++r4) lrn[i][r4] = -1;
+                }
+                if (psn >= 0) load_idx(psn, lrn, lcn);
+                const double* Tp = Tb + (size_t)ps * TSZ;
 #pragma unroll
                 for (int i = 0; i < NI; ++i)
 #pragma unroll
-                    for (int r4 = 0; r4 < 4; ++r4) {
-                        const int r = rowbase + 16 * i + kq + 4 * r4;
-                        int l = -1;
-                        if (r < m2) { const int q = iv[r >> 1]; l = q >= 0 ? 2 * q + (r & 1) : -1; }
-                        lr[i][r4] = l;
-                    }
+                    for (int j = 0; j < NI; ++j)
 #pragma unroll
-                for (int j = 0; j < NI; ++j) {
-                    const int c = colbase + 16 * j + cl;
-                    int l = -1;
-                    if (c < m2) { const int q = iv[c >> 1]; l = q >= 0 ? 2 * q + (c & 1) : -1; }
-                    lc[j] = l;
+                        for (int r4 = 0; r4 < 4; ++r4)
+                            if (lr[i][r4] >= 0 && lc[j] >= 0 && lc[j] <= lr[i][r4]) acc[i][j][r4] = acc[i][j][r4] - Tp[(size_t)lr[i][r4] * TLD + lc[j]];
+#pragma unroll
+                for (int i = 0; i < NI; ++i) {
+                    lc[i] = lcn[i];
+#pragma unroll
+                    for (int r4 = 0; r4 < 4; ++r4) lr[i][r4] = lrn[i][r4];
                 }
-            };
-#pragma unroll 1
-            for (int ps0 = 0; ps0 < nseg; ps0 += 64) {
-                bool rel = false;
-                if (ps0 + lane < nseg) {
-                    const int32_t* bk = blk + (size_t)(ps0 + lane) * nb1;
-                    rel = bk[rb + 1] > bk[rb] && bk[cb + 1] > bk[cb];
-                }
-                unsigned long long mask = __ballot(rel);   // wave-uniform from here on
-                int lr[NI][4], lc[NI];
-                int ps = mask ? ps0 + (__ffsll((long long)mask) - 1) : -1;
-                if (ps >= 0) load_idx(ps, lr, lc);
-#pragma unroll 1
-                while (ps >= 0) {
-                    mask &= mask - 1ull;
-                    const int psn = mask ? ps0 + (__ffsll((long long)mask) - 1) : -1;
-                    int lrn[NI][4], lcn[NI];
-#pragma unroll
-                    for (int i = 0; i < NI; ++i) {
-                        lcn[i] = -1;
-#pragma unroll
-                        for (int r4 = 0; r4 < 4; ++r4) lrn[i][r4] = -1;
-                    }
-                    if (psn >= 0) load_idx(psn, lrn, lcn);
-                    const double* Tp = Tb + (size_t)ps * TSZ;
-#pragma unroll
-                    for (int i = 0; i < NI; ++i)
-#pragma unroll
-                        for (int j = 0; j < NI; ++j)
-#pragma unroll
-                            for (int r4 = 0; r4 < 4; ++r4)
-                                if (lr[i][r4] >= 0 && lc[j] >= 0 && lc[j] <= lr[i][r4]) acc[i][j][r4] = acc[i][j][r4] - Tp[(size_t)lr[i][r4] * TLD + lc[j]];
-#pragma unroll
-                    for (int i = 0; i < NI; ++i) {
-                        lc[i] = lcn[i];
-#pragma unroll
-                        for (int r4 = 0; r4 < 4; ++r4) lr[i][r4] = lrn[i][r4];
-                    }
-                    ps = psn;
-                }
+                ps = psn;
             }
         }
     }
@@ -275,7 +270,7 @@ __global__ __launch_bounds__(SI_TPB) void pgs_syrk_inst_kernel(const PgsParams p
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
     const int kq = lane >> 4, cl = lane & 15;
     const int gw = w * SI_NB + hb;                // wavefront number within the instance
-    const int K3 = 3 * pgs_N(p, b);
+    const int K3 = 3 * p.N;
     const int nchunk = (K3 + SI_ROWS - 1) / SI_ROWS;
     const double* Yb = p.Y + (size_t)b * p.y_stride;
 
@@ -290,7 +285,6 @@ __global__ __launch_bounds__(SI_TPB) void pgs_syrk_inst_kernel(const PgsParams p
     int zcol = -1;                                // column base of this wavefront's tile of the last tile row
     dbl4_t acc[SI_NS][2][2];
     const int32_t* lmf = p.lm_first + (size_t)b * p.L_max;
-    const bool trim = !(p.syrk_notrim & 1);
 #pragma unroll
     for (int s = 0; s < SI_NS; ++s) {
         const int t = gw + 16 * SI_NB * s;
@@ -305,7 +299,7 @@ __global__ __launch_bounds__(SI_TPB) void pgs_syrk_inst_kernel(const PgsParams p
         for (int h = 0; h < 2; ++h) {
             const int rb = rowbase[s] + 16 * h;
             c0[s][h] = 0x7fffffff;
-            if (have[s] && rb < m2) c0[s][h] = trim ? (3 * lmf[rb >> 1]) / SI_ROWS : 0;
+            if (have[s] && rb < m2) c0[s][h] = (3 * lmf[rb >> 1]) / SI_ROWS;
         }
         if (have[s] && rowbase[s] + 31 >= m2) zcol = colbase[s];
 #pragma unroll
@@ -346,12 +340,12 @@ __global__ __launch_bounds__(SI_TPB) void pgs_syrk_inst_kernel(const PgsParams p
     __syncthreads();
 #pragma unroll 1
     for (int c = 0; c < nchunk; ++c) {
-        if (c + 1 < nchunk && !(p.syrk_notrim & 4)) fetch(c + 1);
+        if (c + 1 < nchunk) fetch(c + 1);
         const double* cbuf = s_y + (size_t)(c & 1) * SI_ROWS * ldl;
         const double* src = cbuf + kq * ldl + cl;
 #pragma unroll
         for (int s = 0; s < SI_NS; ++s) {
-            if (c < c0[s][0] || (p.syrk_notrim & 2)) continue;            // wave-uniform
+            if (c < c0[s][0]) continue;                                   // wave-uniform
             const bool both = c >= c0[s][1];                              // rows 16..31 of the tile have begun
             const double* sa = src + rowbase[s];
             const double* sb = src + colbase[s];
@@ -452,14 +446,10 @@ __global__ __launch_bounds__(FC_TPB) void pgs_chain_syrk_kernel(const PgsParams 
         if (p.prof && tid == 0) p.prof[(size_t)p.B * p.lanes_max * 8 + (size_t)b * 16 + 8 * hb + 1] = 0;   // debug: no stamp from this launch
         return;
     }
-    const int N = pgs_N(p, b), LD = p.LD, m2 = 2 * p.M[b];
+    const int N = p.N, LD = p.LD, m2 = 2 * p.M[b];
     const int nch = (N + FC_P - 1) / FC_P;
     const int ncol = (m2 + 1 + 31) & ~31, ldl = ncol + 16;
     if (tid == 0) s_fail = 0;
-    if (p.prof && (p.syrk_notrim & 16)) {            // debug: which SIMD each wavefront of the workgroup runs on (HW_ID bits 5:4)
-        if ((tid & 63) == 0) p.prof[(size_t)p.B * p.lanes_max * 8 + (size_t)b * 16 + 8 * hb + (tid >> 6)] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-        return;
-    }
     for (int k = tid; k < 2 * FC_P * FC_LMAX; k += FC_TPB) (&s_idx[0][0][0])[k] = -1;
     if (tid < 6) s_E[tid / 3][FC_P * FC_KP * 3 + tid % 3] = (dbl2_t){0.0, 0.0};
     __syncthreads();
@@ -596,7 +586,7 @@ __global__ __launch_bounds__(FC_TPB) void pgs_chain_syrk_kernel(const PgsParams 
     const int KP = p.KP, myj = (c >> 1) < FC_LMAX ? (c >> 1) : 0, myd = c & 1;
     const bool is_z = c == m2;                       // the gradient column: its right-hand side is gp, it has no factors (s_idx[.][M] stays -1)
     unsigned long long tc[3] = {0, 0, 0}, tprev = p.prof ? wall_clock64() : 0ull;
-    const int stamp_tid = 64 * (1 + ((p.syrk_notrim >> 8) & 7));   // debug: the consumer wavefront whose phases are timed (SLAM_PGS_NOTRIM bits 8-10; default wavefront 1)
+    constexpr int stamp_tid = 64;                    // debug: the consumer wavefront whose phases are timed (wavefront 1)
 #define FC_STAMP(i) do { if (p.prof && tid == stamp_tid) { const unsigned long long now_ = wall_clock64(); tc[i] += now_ - tprev; tprev = now_; } } while (0)
     auto columns = [&](int it) {
         if (it >= 1 && it <= nch && c <= m2) {       // column recurrence of chunk it - 1 -> s_yb[(it - 1) & 1]
@@ -688,7 +678,6 @@ __global__ __launch_bounds__(FC_TPB) void pgs_chain_syrk_kernel(const PgsParams 
         const int nt = (m2 + 31) >> 5, ntile = nt * (nt + 1) / 2;   // tiles over the landmark rows; row 2M is the VALU's
         const int mw = (w < 4 ? w - 1 : w - 2) * FC_NB + hb;   // MFMA wavefront number within the instance (wavefronts 1-3, 5-7)
         const int32_t* lmf = p.lm_first + (size_t)b * p.L_max;
-        const bool trim = !(p.syrk_notrim & 1);
         // tile descriptors are wavefront-uniform: kept in SGPRs (readfirstlane) so that the phase below branches on scalars and the
         // operand reads of a tile can all be issued ahead of its MFMAs
         int rowbase[NS], colbase[NS], k0[NS][2];
@@ -707,7 +696,7 @@ __global__ __launch_bounds__(FC_TPB) void pgs_chain_syrk_kernel(const PgsParams 
             for (int h = 0; h < 2; ++h) {
                 const int rb = rowbase[s] + 16 * h;
                 int kk = 0x7fffffff;                    // first row of Y where this half of the tile can be non-zero
-                if (have[s] && rb < m2) kk = trim ? 3 * lmf[rb >> 1] : 0;
+                if (have[s] && rb < m2) kk = 3 * lmf[rb >> 1];
                 k0[s][h] = __builtin_amdgcn_readfirstlane(kk);
             }
             rowbase[s] = __builtin_amdgcn_readfirstlane(rowbase[s]); colbase[s] = __builtin_amdgcn_readfirstlane(colbase[s]);

@@ -113,16 +113,13 @@ def test_solve_every_iteration_mode(oracle):
         assert st["flags"][b] == 0
 
 
-@pytest.mark.parametrize("async_ticks", [1, 0])
 @pytest.mark.parametrize("L,T,B,KP", [(10, 60, 6, 6), (20, 300, 5, 8), (60, 200, 3, 16)])
-def test_solve_every_iteration_on_the_device_matches_oracle(monkeypatch, oracle, L, T, B, KP, async_ticks):
+def test_solve_every_iteration_on_the_device_matches_oracle(oracle, L, T, B, KP):
     """pgs_run_sim_every_iteration: the reference's default mode (params.yaml:64; pose_graph.cpp:258-264) with the simulator on the device -
-    per tick one step of the simulator + NaiveFilter + append, the solve, `initial_estimate = result`.  Against the oracle run in the same
-    mode: the LM iteration and lambda-trial counts SUMMED over all ticks are equal, the final result within the one-shot bar.
-    async_ticks = 1 (default): no batch-wide barrier per tick - every graph walks through its ticks at its own pace, one LM trial of all
-    unfinished graphs per round of launches, converged graphs advanced on a second stream; 0: the lockstep tick loop."""
+    per tick one step of the simulator + NaiveFilter + append, the solve of the whole batch in lockstep, `initial_estimate = result`.  Against
+    the oracle run in the same mode: the LM iteration and lambda-trial counts SUMMED over all ticks are equal, the final result within the
+    one-shot bar."""
     import live_ekf_slam_amd as S
-    monkeypatch.setenv("SLAM_PGS_ITER_ASYNC", str(async_ticks))
     lm, cmds = make_scenario(61 + L, L, T)
     cfg = default_config()
     for lin in (oracle.LIN_SCHUR, oracle.LIN_SEG):
@@ -400,27 +397,41 @@ def test_streaming_trial_cap_is_per_graph(monkeypatch, oracle):
 
 @pytest.mark.parametrize("L,T", [(20, 150), (60, 400)])
 def test_syrk_variants_agree_with_the_oracle(monkeypatch, oracle, L, T):
-    """The Schur complement has tile kernels (few active instances) and one with instance-resident accumulators and Y
-    streamed through LDS (many); the Cholesky has a 1024- and a 256-thread build.  Forced in combinations
-    (SLAM_PGS_SYRK_TILE, SLAM_PGS_CHOL_THREADS), all reproduce the oracle's LM path (same iteration and trial counts,
-    _compare) and its result within the usual tolerance."""
+    """The Schur complement has a tile kernel (few running slots) and one with instance-resident accumulators and Y streamed
+    through LDS (many).  Each forced in turn through the slot count it starts at (SLAM_PGS_SYRK_INST_SWITCH), both reproduce the
+    oracle's LM path (same iteration and trial counts, _compare) and its result within the usual tolerance."""
     import live_ekf_slam_amd as S
     KP, B = 8, 12
     lm, cmds = make_scenario(21, L, T)
     cfg = default_config()
     r = oracle.run_pgs_batch(lm, cmds, B, L, KP=KP, seed=6, cfg=cfg, nthreads=8)
-    # SYRK: 32x32 tiles / 64x64 tiles / instance-resident accumulators; Cholesky: 1024 or 256 threads per instance (the
-    # 256-thread one is otherwise chosen only above 256 active instances, i.e. by no other test)
     monkeypatch.setenv("SLAM_PGS_SEG", "0")     # the sequential chain of rounds 1-4 (the default is the segmented elimination, tested below)
     monkeypatch.setenv("SLAM_PGS_FUSED", "0")   # chain and SYRK as two launches (few slots would otherwise run the fused kernel)
-    for tile, chol in (("32", "1024"), ("1", "1024"), ("64", "256"), ("1", "256")):
-        monkeypatch.setenv("SLAM_PGS_SYRK_TILE", tile)
-        monkeypatch.setenv("SLAM_PGS_CHOL_THREADS", chol)
+    for inst_switch in ("1000000000", "0"):      # 32x32 wavefront tiles / instance-resident accumulators
+        monkeypatch.setenv("SLAM_PGS_SYRK_INST_SWITCH", inst_switch)
         pg = S.BatchedPoseGraph(B, num_iterations=T + 1, L_max=L, k_per_pose=KP).readParams(cfg)
         pg.set_map(lm); pg.set_seed(6); pg.init(0.0, 0.0, 0.0)
         pg.run_sim(cmds); pg.solvePoseGraph()
         _compare(pg, r, B)
         pg.close()
+
+
+@pytest.mark.parametrize("seg", ["32", "0"])
+def test_the_right_looking_cholesky_beyond_the_left_looking_staging(monkeypatch, oracle, seg):
+    """L_max = 240: LD = 512, beyond the LD <= 448 the left-looking Cholesky's staging is sized for - the one size at which the
+    right-looking 1024-thread kernel runs, and its panels need more than the default 64 KiB of dynamic LDS.  With the segmented
+    elimination and with the sequential chain, the solve follows the oracle's LM path to the usual tolerance."""
+    import live_ekf_slam_amd as S
+    L, T, KP, B = 240, 300, 32, 4
+    lm, cmds = make_scenario(L + 77, L, T)
+    cfg = default_config()
+    r = oracle.run_pgs_batch(lm, cmds, B, L, KP=KP, seed=5, cfg=cfg, nthreads=8)
+    monkeypatch.setenv("SLAM_PGS_SEG", seg)
+    pg = S.BatchedPoseGraph(B, num_iterations=T + 1, L_max=L, k_per_pose=KP).readParams(cfg)
+    pg.set_map(lm); pg.set_seed(5); pg.init(0.0, 0.0, 0.0)
+    pg.run_sim(cmds); pg.solvePoseGraph()
+    _compare(pg, r, B)
+    pg.close()
 
 
 @pytest.mark.parametrize("L,T,KP,B", [(20, 150, 8, 12), (100, 250, 24, 6), (200, 999, 32, 5)])
