@@ -22,7 +22,13 @@ Launch: `python bench.py --gpus N --steps K --warmup W`; for N>1 under torch.dis
 RCCL).  Scaling is STRONG by default: the global `--batch` (65 536) is sharded contiguously over the ranks (8 192 per GPU at
 N = 8, BASELINE configs[3]) with global instance ids, so the result is the same for every N; `--scaling weak` keeps `--batch`
 instances on every rank.  No data-path collective; the only collective is the end-of-run gather of per-instance error
-statistics.  The headline line also carries `config.secondary_digest` and a few top-level scalars (`roofline.once_per_step_frac`,
+statistics.
+
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs` if asked and prints the line, whose roofline is that of the
+timed launches themselves.  `--full` adds everything else the benchmark measures or checks: the in-run oracle comparison, the CPU
+baselines, the once-per-step leg, the per-k table and the long runs, the pose graph's per-kernel-timed solve and batch-256 figure, and
+the secondary lines (UKF, pose graph, fp32, L=20) of the default configuration.  The `--no-*` options skip parts of a `--full` run.  A
+`--full` line also carries `config.secondary_digest` and a few top-level scalars (`roofline.once_per_step_frac`,
 `config.steady_state_value`, ...) so that a record that keeps only scalars and short strings still shows every BASELINE config.
 """
 import argparse
@@ -242,14 +248,16 @@ def bench_pgs(args, torch, dist, rank, local_rank, world, dev, cpu_budget_s=15.0
         wall = time.perf_counter() - t0
         if getattr(args, "event_value", False):
             wall = ev0.elapsed_time(ev1) * 1e-3
-        # one more solve with per-kernel HIP-event timing (a single group, kernels back to back) for the roofline object
-        pg.set_profiling(True)
-        pg.solvePoseGraph()
-        kms = pg.last_solve_kernel_ms()
-        flop, trials_launched = pg.last_solve_work()
-        paths = pg.last_solve_paths()
-        pg.set_profiling(False)
-        sync_all()
+        profiled = args.full
+        if profiled:
+            # one more solve with per-kernel HIP-event timing (a single group, kernels back to back) for the roofline object
+            pg.set_profiling(True)
+            pg.solvePoseGraph()
+            kms = pg.last_solve_kernel_ms()
+            flop, trials_launched = pg.last_solve_work()
+            paths = pg.last_solve_paths()
+            pg.set_profiling(False)
+            sync_all()
     if world > 1:
         tw = torch.tensor([wall], dtype=torch.float64, device=args.coll_device if args.coll_device is not None else "cpu")
         dist.all_reduce(tw, op=dist.ReduceOp.MAX)
@@ -292,61 +300,64 @@ def bench_pgs(args, torch, dist, rank, local_rank, world, dev, cpu_budget_s=15.0
     line = None
     if rank == 0:
         K1 = K; K = 1   # kms / flop / trials_launched below are per ONE profiled solve
-        # The Schur complement is formed either by a SYRK launch of its own or inside the fused chain + SYRK launch (few running
-        # slots: pgs_kernel.hip).  The roofline object is the launch kind that did most of the solve's algorithmic FLOP; the other
-        # is reported beside it.  A fused launch's time INCLUDES the sequential 3x3 recursion of the chain it overlaps.
-        def rate(f, ms):
-            return f / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
-        sep = {"kernel": "pgs_syrk_inst_kernel / pgs_syrk_kernel (v_mfma_f64_16x16x4_f64)", "algorithmic_flop": paths["flop_separate"],
-               "kernel_ms": round(paths["ms_separate_syrk"], 3), "achieved": round(rate(paths["flop_separate"], paths["ms_separate_syrk"]), 2)}
-        fus = {"kernel": "pgs_chain_syrk_kernel (block-tridiagonal chain + v_mfma_f64_16x16x4_f64 SYRK in one launch, Y in LDS)",
-               "algorithmic_flop": paths["flop_fused"], "kernel_ms": round(paths["ms_fused"], 3),
-               "achieved": round(rate(paths["flop_fused"], paths["ms_fused"]), 2)}
-        for o in (sep, fus):
-            o["frac"] = round(o["achieved"] / 78.6, 4)
-        dom, oth = (fus, sep) if paths["flop_fused"] >= paths["flop_separate"] else (sep, fus)
-        syrk_tf = dom["achieved"]
         M = np.array([pg.get_graph(b, 1)["M"] for b in range(min(B, 8))])
-        seg = None
-        if paths.get("segmented"):
-            # Round 5: the pose chain is eliminated segment by segment (pgs_seg_impl.h), which takes the Schur-complement SYRK from 175
-            # to ~15 MFLOP per instance-trial - the solve's dominant MFMA kernel is now the dense Cholesky of S.  Roofline object: that
-            # kernel, n^3 / 3 + 2 n^2 FLOP per factorisation + solve (n = 2 M, M sampled from the first instances) over its HIP-event time.
-            n2 = 2.0 * float(M.mean())
-            chol_flop = float(st["trials"].sum()) * (n2 ** 3 / 3.0 + 2.0 * n2 * n2)
-            chol_ms = kms["chol"]
-            seg = {"kernel": "pgs_seg_gram_kernel + pgs_syrk_kernel<32> (v_mfma_f64_16x16x4_f64): per-segment Gram matrices + the separators' rows",
-                   "algorithmic_flop": paths["flop_segmented"], "kernel_ms": round(paths["ms_segmented_syrk"], 3),
-                   "achieved": round(rate(paths["flop_segmented"], paths["ms_segmented_syrk"]), 2), "segment_length": paths["segment_length"]}
-            seg["frac"] = round(seg["achieved"] / 78.6, 4)
-            dom = {"kernel": "pgs_chol_ll_kernel (dense left-looking Cholesky of the 2M x 2M Schur complement + substitutions, v_mfma_f64_16x16x4_f64)",
-                   "algorithmic_flop": chol_flop, "kernel_ms": round(chol_ms, 3), "achieved": round(rate(chol_flop, chol_ms), 2)}
-            dom["frac"] = round(dom["achieved"] / 78.6, 4)
-            oth = seg
+        roofline = None
+        if profiled:
+            # The Schur complement is formed either by a SYRK launch of its own or inside the fused chain + SYRK launch (few running
+            # slots: pgs_kernel.hip).  The roofline object is the launch kind that did most of the solve's algorithmic FLOP; the other
+            # is reported beside it.  A fused launch's time INCLUDES the sequential 3x3 recursion of the chain it overlaps.
+            def rate(f, ms):
+                return f / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+            sep = {"kernel": "pgs_syrk_inst_kernel / pgs_syrk_kernel (v_mfma_f64_16x16x4_f64)", "algorithmic_flop": paths["flop_separate"],
+                   "kernel_ms": round(paths["ms_separate_syrk"], 3), "achieved": round(rate(paths["flop_separate"], paths["ms_separate_syrk"]), 2)}
+            fus = {"kernel": "pgs_chain_syrk_kernel (block-tridiagonal chain + v_mfma_f64_16x16x4_f64 SYRK in one launch, Y in LDS)",
+                   "algorithmic_flop": paths["flop_fused"], "kernel_ms": round(paths["ms_fused"], 3),
+                   "achieved": round(rate(paths["flop_fused"], paths["ms_fused"]), 2)}
+            for o in (sep, fus):
+                o["frac"] = round(o["achieved"] / 78.6, 4)
+            dom, oth = (fus, sep) if paths["flop_fused"] >= paths["flop_separate"] else (sep, fus)
             syrk_tf = dom["achieved"]
+            seg = None
+            if paths.get("segmented"):
+                # Round 5: the pose chain is eliminated segment by segment (pgs_seg_impl.h), which takes the Schur-complement SYRK from 175
+                # to ~15 MFLOP per instance-trial - the solve's dominant MFMA kernel is now the dense Cholesky of S.  Roofline object: that
+                # kernel, n^3 / 3 + 2 n^2 FLOP per factorisation + solve (n = 2 M, M sampled from the first instances) over its HIP-event time.
+                n2 = 2.0 * float(M.mean())
+                chol_flop = float(st["trials"].sum()) * (n2 ** 3 / 3.0 + 2.0 * n2 * n2)
+                chol_ms = kms["chol"]
+                seg = {"kernel": "pgs_seg_gram_kernel + pgs_syrk_kernel<32> (v_mfma_f64_16x16x4_f64): per-segment Gram matrices + the separators' rows",
+                       "algorithmic_flop": paths["flop_segmented"], "kernel_ms": round(paths["ms_segmented_syrk"], 3),
+                       "achieved": round(rate(paths["flop_segmented"], paths["ms_segmented_syrk"]), 2), "segment_length": paths["segment_length"]}
+                seg["frac"] = round(seg["achieved"] / 78.6, 4)
+                dom = {"kernel": "pgs_chol_ll_kernel (dense left-looking Cholesky of the 2M x 2M Schur complement + substitutions, v_mfma_f64_16x16x4_f64)",
+                       "algorithmic_flop": chol_flop, "kernel_ms": round(chol_ms, 3), "achieved": round(rate(chol_flop, chol_ms), 2)}
+                dom["frac"] = round(dom["achieved"] / 78.6, 4)
+                oth = seg
+                syrk_tf = dom["achieved"]
+            roofline = {"bound": "mfma", "achieved": round(syrk_tf, 2), "peak": 78.6, "unit": "TFLOP/s", "frac": round(syrk_tf / 78.6, 4),
+                        "traffic": None, "kernel": dom["kernel"], "kernel_ms": dom["kernel_ms"],
+                        "algorithmic_flop_per_solve": flop / K, "algorithmic_flop_in_kernel": dom["algorithmic_flop"],
+                        "other_path": oth,
+                        "limiter": ("latency: a trial is ten short dependent launches per running slot (0.7 ms at the tail of a solve, 0.39 ms of it the "
+                                    "dense Cholesky's 22 panel steps on one workgroup); the lockstep batch takes as many trials as its slowest instance")
+                                   if paths.get("segmented") else
+                                   ("latency of the chain's sequential 3x3 recursion (0.56 ms per trial whatever the batch) and, at a full batch, "
+                                    "the fp64 units: on gfx950 v_mfma_f64 runs at the vector fp64 rate of its SIMD (71.8 TFLOP/s sustained on the chip, tools/calib_mfma64)")}
         line = {"metric": "pose-graph SLAM solves/sec (secondary; BASELINE configs[4] shape)", "value": round(B * world * K1 / wall, 2),
                 "unit": "solves/s", "n_gpus": world, "steps": K1, "warmup": W, "ms_per_step": round(wall / K1 * 1e3, 3),
                 "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
                 "config": {"workload": f"pose-graph SLAM one-time LM solve, {N} poses x {L} landmarks (mapped: {int(M.min())}-{int(M.max())}), "
                                        f"batch={B} graphs per GPU, device-built graphs (simulator + NaiveFilter secondary)",
-                           "batch_per_gpu": B, "batch_256_value": small, "poses": N, "landmarks": L, "lm_trials_launched_per_solve": trials_launched / K,
+                           "batch_per_gpu": B, "batch_256_value": small, "poses": N, "landmarks": L, "lm_trials_launched_per_solve": trials_launched / K if profiled else None,
                            "lm_iterations_mean": float(st["iterations"].mean()), "lm_trials_mean": float(st["trials"].mean()),
                            "instances_flagged": int((st["flags"] != 0).sum()),
                            "avg_position_error_m": {"initial": round(float(e0.mean()), 4), "result": round(float(e1_all.mean()), 4)},
                            "instances_global": int(e1_all.size),
                            "parity_check": parity,
                            "parity": "identical LM iteration / trial counts and max(1e-7 m, 10 x the instance's rounding spread among the oracle's own elimination orders) vs the CPU oracle (tests/test_parity_pgs_gpu.py)",
-                           "elimination": ("segmented: %d poses per segment, interiors side by side, then the separators (pgs_seg_impl.h)" % paths["segment_length"]) if paths.get("segmented") else "sequential chain (rounds 1-4)",
-                           "kernel_ms_per_solve": {k: round(v / K, 3) for k, v in kms.items()}},
-                "roofline": {"bound": "mfma", "achieved": round(syrk_tf, 2), "peak": 78.6, "unit": "TFLOP/s", "frac": round(syrk_tf / 78.6, 4),
-                             "traffic": None, "kernel": dom["kernel"], "kernel_ms": dom["kernel_ms"],
-                             "algorithmic_flop_per_solve": flop / K, "algorithmic_flop_in_kernel": dom["algorithmic_flop"],
-                             "other_path": oth,
-                             "limiter": ("latency: a trial is ten short dependent launches per running slot (0.7 ms at the tail of a solve, 0.39 ms of it the "
-                                         "dense Cholesky's 22 panel steps on one workgroup); the lockstep batch takes as many trials as its slowest instance")
-                                        if paths.get("segmented") else
-                                        ("latency of the chain's sequential 3x3 recursion (0.56 ms per trial whatever the batch) and, at a full batch, "
-                                         "the fp64 units: on gfx950 v_mfma_f64 runs at the vector fp64 rate of its SIMD (71.8 TFLOP/s sustained on the chip, tools/calib_mfma64)")}}
+                           "elimination": (("segmented: %d poses per segment, interiors side by side, then the separators (pgs_seg_impl.h)" % paths["segment_length"]) if paths.get("segmented") else "sequential chain (rounds 1-4)") if profiled else None,
+                           "kernel_ms_per_solve": {k: round(v / K, 3) for k, v in kms.items()} if profiled else None},
+                "roofline": roofline}
         if world == 1 and not args.no_cpu_baseline:
             from oracle import oracle as O
             Bc = max(2, int((48 if L >= 100 else 256) * cpu_budget_s / 15.0))    # about cpu_budget_s of single-thread work
@@ -474,7 +485,10 @@ def finish(line, dist, rank, world):
         dist.destroy_process_group()
 
 
-def main():
+def parse_args(argv=None):
+    """The command line (default: sys.argv[1:]).  Without --full every --no-* option is set: a plain run skips all of it."""
+    if argv is None:
+        argv = sys.argv[1:]
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
@@ -485,13 +499,16 @@ def main():
                     help="strong (default): the global batch is sharded contiguously over the GPUs (BASELINE configs[3]: "
                          "65536 -> 8192 per GPU at 8 GPUs); weak: --batch instances on every GPU")
     ap.add_argument("--window-start", type=int, default=WINDOW_START, help="first timed timestep of the scenario")
-    ap.add_argument("--no-long-runs", action="store_true", help="skip the per-k table, the 1000-step steady-state run and the full run from init")
-    ap.add_argument("--no-parity-check", action="store_true", help="skip the oracle comparison of the timed trajectory")
-    ap.add_argument("--no-once-per-step", action="store_true", help="skip the once-per-step leg (K further timesteps, one launch each)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, run every other measurement and check: oracle comparison, CPU baselines, once-per-step "
+                         "leg, per-k table and long runs, the pose graph's per-kernel-timed solve and batch-256 figure, secondary lines")
+    ap.add_argument("--no-long-runs", action="store_true", help="with --full: skip the per-k table, the 1000-step steady-state run and the full run from init")
+    ap.add_argument("--no-parity-check", action="store_true", help="with --full: skip the oracle comparison of the timed trajectory")
+    ap.add_argument("--no-once-per-step", action="store_true", help="with --full: skip the once-per-step leg (K further timesteps, one launch each)")
     ap.add_argument("--landmarks", type=int, default=50)
     ap.add_argument("--preroll", type=int, default=40, help="ukf: steps before the window")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the compact secondary lines (UKF, pose graph, fp32, L=20) of the default run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the compact secondary lines (UKF, pose graph, fp32, L=20) of the default configuration")
     ap.add_argument("--waves-per-filter", type=int, default=0)
     ap.add_argument("--steps-per-launch", type=int, default=0,
                     help="timesteps one kernel launch carries (0 = all K timed steps in one launch, 1 = launch per step)")
@@ -501,23 +518,30 @@ def main():
                     help="ekf = the headline metric (default); ukf / pgs = BASELINE configs[2] / configs[4]-style secondary lines")
     ap.add_argument("--poses", type=int, default=1000, help="pgs: poses per graph (num_iterations)")
     ap.add_argument("--k-per-pose", type=int, default=32, help="pgs: detections stored per timestep")
-    ap.add_argument("--no-batch-256", action="store_true", help="pgs: skip the batch-256 figure measured beside a larger batch (profiling runs)")
+    ap.add_argument("--no-batch-256", action="store_true", help="pgs, with --full: skip the batch-256 figure measured beside a larger batch (profiling runs)")
     ap.add_argument("--iterative", action="store_true",
                     help="pgs: the reference's default mode solve_graph_every_iteration (params.yaml:64): one run of poses - 1 ticks, each solved and adopted")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="ekf: after the timed steps write what they computed (DIR/<name>.npy, float64, <= 64 MB; rank 0's shard)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.dump_outputs and args.filter != "ekf":
         ap.error("--dump-outputs is implemented for --filter ekf only")
+    if not args.full:   # a plain run: nothing but what its headline figure needs
+        args.no_long_runs = args.no_parity_check = args.no_once_per_step = args.no_cpu_baseline = True
+        args.no_secondary = args.no_batch_256 = True
     if args.filter == "pgs":   # configs[4] defaults unless given explicitly
-        argv = " ".join(sys.argv[1:])
+        argv = " ".join(argv)
         if "--landmarks" not in argv: args.landmarks = 200
         if "--batch" not in argv: args.batch = 256 if args.iterative else 2048   # one-time solve: 10 k solves/s from batch 2048 on (profiles/r06_pgs/stream_table*.txt)
         if "--steps" not in argv: args.steps = 5
         if "--warmup" not in argv: args.warmup = 1
+    return args
 
+
+def main():
+    args = parse_args()
     import torch
     import torch.distributed as dist
 

@@ -27,7 +27,7 @@ def _last_json(out):
 
 def test_single_gpu_line_has_the_contract_fields():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--batch", "4096",
-                          "--no-long-runs", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--full", "--no-long-runs", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json(out.stdout)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
@@ -54,11 +54,28 @@ def test_single_gpu_line_has_the_contract_fields():
     assert "secondary" not in d   # only the default headline configuration carries the secondary lines
 
 
+def test_plain_run_prints_the_headline_only():
+    """Without --full the default configuration times its K steps and prints the line: no oracle comparison, CPU baseline,
+    once-per-step leg, long runs or secondary lines, while the roofline of the timed launch itself stays in the line."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2"],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = _last_json(out.stdout)
+    assert d["metric"].startswith("EKF predict-update steps/sec") and d["unit"] == "steps/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["steps"] == 5 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["value"] > 1e6
+    assert abs(d["value"] - 65536 * 5 / (d["ms_per_step"] * 5e-3)) <= 1e-3 * d["value"]
+    assert "secondary" not in d and "cpu_baseline" not in d
+    c, r = d["config"], d["roofline"]
+    assert c["parity_check"] is None and c["secondary_digest"] is None and "steady_state_long_run" not in c and "per_k_ms" not in c
+    assert c["instances_flagged"] == 0 and c["batch_per_gpu"] == 65536
+    assert r["once_per_step"] is None and 0.0 < r["frac"] <= 1.0 and r["launches"] == 1
+
+
 def test_two_ranks_strong_scaling_on_one_gpu():
     env = dict(os.environ, BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-           "--batch", "8192", "--no-long-runs", "--no-cpu-baseline"]
+           "--batch", "8192", "--full", "--no-long-runs", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-1500:])
     d = _last_json(out.stdout)
@@ -73,7 +90,7 @@ def test_two_ranks_short_window_keeps_the_k_step_definition():
     env = dict(os.environ, BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-           "--batch", "4096", "--no-cpu-baseline", "--no-once-per-step"]
+           "--batch", "4096", "--full", "--no-cpu-baseline", "--no-once-per-step"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-1500:])
     d = _last_json(out.stdout)
@@ -95,7 +112,7 @@ def test_two_ranks_of_the_secondary_filters_on_one_gpu(flt, extra, metric):
     the in-run oracle check of rank 0's first and last instance is part of the line (global ids)."""
     env = dict(os.environ, BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--filter", flt, "--no-cpu-baseline"] + extra
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--filter", flt, "--full", "--no-cpu-baseline"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-1500:])
     d = _last_json(out.stdout)
@@ -110,6 +127,25 @@ def test_two_ranks_of_the_secondary_filters_on_one_gpu(flt, extra, metric):
         assert pc["lm_iteration_and_trial_counts_equal"] and pc["max_abs_diff_m"] < 1e-7
 
 
+@pytest.mark.parametrize("flt,extra,metric", [
+    ("ukf", ["--landmarks", "20", "--batch", "256", "--steps", "6", "--warmup", "2", "--preroll", "10"], "UKF"),
+    ("pgs", ["--landmarks", "20", "--poses", "120", "--batch", "24", "--k-per-pose", "8", "--steps", "1", "--warmup", "1"], "pose-graph SLAM solves"),
+    ("pgs", ["--iterative", "--landmarks", "20", "--poses", "60", "--batch", "12", "--k-per-pose", "8", "--warmup", "3"], "graph-ticks")])
+def test_plain_runs_of_the_secondary_filters(flt, extra, metric):
+    """`--filter ukf | pgs` without --full: the timed figure only - no oracle comparison, no CPU baseline, and for the one-time pose-graph
+    solve no per-kernel-timed solve (its roofline comes with --full)."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--filter", flt] + extra,
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = _last_json(out.stdout)
+    assert metric in d["metric"] and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["config"]["parity_check"] is None and "cpu_baseline" not in d and d["config"]["instances_flagged"] == 0
+    if flt == "pgs" and "--iterative" not in extra:
+        assert d["roofline"] is None and d["config"]["kernel_ms_per_solve"] is None and d["config"]["batch_256_value"] is None
+    else:   # measured on the timed run itself
+        assert d["roofline"]["peak"] == 78.6 and d["roofline"]["achieved"] >= 0.0
+
+
 def test_two_ranks_over_rccl_on_one_gpu_or_the_reason_why_not():
     """the RCCL branch of bench.py (init_process_group("nccl"), the barrier-bracketed timing, the end-of-run
     all-gather / all-reduce of the error statistics) has only ever run with one rank.  Two ranks on GPU 0 over the nccl backend
@@ -118,7 +154,7 @@ def test_two_ranks_over_rccl_on_one_gpu_or_the_reason_why_not():
     env = dict(os.environ, BENCH_SHARE_GPU="nccl", HSA_ENABLE_IPC_MODE_LEGACY="0", NCCL_DEBUG="WARN")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-           "--batch", "8192", "--no-long-runs", "--no-cpu-baseline", "--no-once-per-step"]
+           "--batch", "8192", "--full", "--no-long-runs", "--no-cpu-baseline", "--no-once-per-step"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     if out.returncode == 0:
         d = _last_json(out.stdout)

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 for pass in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_IFETCH SQ_INSTS_VALU SQ_INSTS_LDS" "FETCH_SIZE" "WRITE_SIZE"; do
   tag=$(echo $pass | cut -d' ' -f1)
-  rocprofv3 --output-format csv --pmc $pass -d $R/$out/pmc_$tag -o pmc -- python3 $R/bench.py --no-cpu-baseline --no-long-runs --no-parity-check "$@" > $R/$out/pmc_$tag.log 2>&1
+  rocprofv3 --output-format csv --pmc $pass -d $R/$out/pmc_$tag -o pmc -- python3 $R/bench.py --full --no-cpu-baseline --no-long-runs --no-parity-check "$@" > $R/$out/pmc_$tag.log 2>&1
 done
 cd $R
 python3 - "$out" <<'PY'

@@ -3,7 +3,7 @@
 set -u
 OUT=gpurun_out/prof_syrk_diag; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-ARGS="bench.py --filter pgs --no-cpu-baseline --steps 1 --warmup 1"
+ARGS="bench.py --filter pgs --full --no-cpu-baseline --steps 1 --warmup 1"
 i=0
 for C in "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum" "TCC_HIT_sum TCC_MISS_sum" "SQ_INSTS_VMEM_RD SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "TCP_PENDING_STALL_CYCLES_sum TCP_TCC_READ_REQ_LATENCY_sum" "SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_VMEM SQ_WAIT_ANY"; do
   i=$((i+1))
