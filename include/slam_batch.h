@@ -8,8 +8,9 @@
  * Threading: one caller thread per handle (the reference is single-threaded: localization_node.cpp:197).
  * Kernels are enqueued on one HIP stream per handle (slam_set_stream); slam_get_ and slam_sync synchronise.
  *
- * The batch: B independent filter instances that share the landmark map and the command sequence and differ
- * only in their noise streams (Monte-Carlo seeds).  Instance b of this handle has GLOBAL index
+ * The batch: B independent filter instances.  By default they share the landmark map, the start pose and the command sequence and
+ * differ only in their noise streams (Monte-Carlo seeds); the slam_*_each entry points give every instance its own start pose, map and
+ * commands (several robots or scenarios in one batch, see "heterogeneous batches" below).  Instance b of this handle has GLOBAL index
  * instance_offset + b (slam_set_instance_offset), which keys its counter-based RNG stream, so results do not
  * depend on how a batch is sharded over GPUs.
  */
@@ -186,6 +187,34 @@ int slam_set_run_chunk(slam_handle* h, int steps_per_launch);
  * bit-identical results to slam_step_dev.  d_meas / d_meas_count are DEVICE pointers (k_stride 0 = empty message). */
 int slam_predict(slam_handle* h, const float cmd[2]);
 int slam_update_dev(slam_handle* h, const float* d_meas, const int32_t* d_meas_count, int k_stride);
+
+/* ---- heterogeneous batches: per-instance start poses, maps and commands ------------------------------------------------------------
+ * The entry points above share one command, one start pose and one map over the batch.  These take one per instance (host pointers
+ * unless marked _dev), so that one handle can hold several robots, trajectories or maps.  Every entry point above keeps its behaviour,
+ * and per-instance rows that are all equal give the same bits as the shared call.
+ * Queue: the _each calls run the EKF step queue (slam_set_lazy_steps) first and are not queued themselves, so shared and per-instance
+ *   calls may be mixed and run in call order.
+ * slam_track_instance: the shadow gets the tracked instance's row of every per-instance input.
+ * Checkpoints: maps and commands are inputs, not state; slam_save_state / slam_load_state keep their format, and after a load the caller
+ *   sets the maps (slam_set_maps) again as for slam_set_map.
+ * Not covered: the pose graph (slam_pgs.h: its graphs share one BetweenFactor sequence by construction), slam_multi_*, a per-instance
+ *   known map for UKF_LOC, per-instance noise configs. */
+/* Filter::init with one start pose per instance: pose0 [batch][3] {x, y, yaw} (float, as slam_init's arguments); truth0 [batch][3] =
+ * the simulator's true start pose per instance, NULL = the config's init pose for all.  Resets what slam_init resets. */
+int slam_init_each(slam_handle* h, const float* pose0, const double* truth0);
+/* SIM mode: one true map per instance, maps [batch][L_stride][2], L [batch] landmarks (ids 0 .. L[b]-1; 1 <= L[b] <= L_stride).
+ * Replaces the shared map; a later slam_set_map returns to the shared map.  Where the size class of a launch depends on the map (long
+ * messages, slam_step_sim on a map larger than the class holds), the largest L[b] decides.  EKF and UKF_SLAM; UKF_LOC:
+ * SLAM_ERR_UNSUPPORTED. */
+int slam_set_maps(slam_handle* h, const double* maps, const int32_t* L, int L_stride);
+/* One timestep with one command per instance, cmds [batch][2] {fwd, ang}; otherwise as slam_step / slam_step_dev (slam_step_each_dev:
+ * d_cmds is a device pointer too, read in the order of the handle's stream). */
+int slam_step_each(slam_handle* h, const float* cmds, const float* meas, const int32_t* meas_count, int k_stride);
+int slam_step_each_dev(slam_handle* h, const float* d_cmds, const float* d_meas, const int32_t* d_meas_count, int k_stride);
+/* T SIM timesteps, cmds [T][batch][2]; EKF multi-step launches and slam_set_run_chunk apply as for slam_run_sim. */
+int slam_run_sim_each(slam_handle* h, const float* cmds, int T);
+/* UKF only: predictionStage with cmds [batch][2]; the slam_update_dev that follows uses them.  EKF: SLAM_ERR_UNSUPPORTED. */
+int slam_predict_each(slam_handle* h, const float* cmds);
 
 /* ---- state export: getStateVector / publishState payload (ekf.cpp:181-220, ukf.cpp:47-104) ---------------- */
 /* Sizes: x needs n_max doubles, P needs n_max*n_max doubles, ids needs L_max ints, where

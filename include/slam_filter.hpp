@@ -49,6 +49,39 @@ inline void check(int rc) {
     if (rc != SLAM_OK) throw std::runtime_error(std::string("slam_batch: ") + slam_last_error());
 }
 
+// Heterogeneous batches (slam_*_each): the per-instance inputs, checked for size before they reach the library.
+inline void checkSize(size_t got, size_t want, const char* what) {
+    if (got != want) throw std::invalid_argument(std::string(what) + ": " + std::to_string(got) + " elements, expected " + std::to_string(want));
+}
+inline std::vector<float> packCommands(const std::vector<Command>& cmds, int batch) {   // [B] -> [B][2]
+    checkSize(cmds.size(), (size_t)batch, "commands");
+    std::vector<float> c(2 * cmds.size());
+    for (size_t b = 0; b < cmds.size(); ++b) { c[2 * b] = cmds[b].fwd; c[2 * b + 1] = cmds[b].ang; }
+    return c;
+}
+// One start pose per instance (pose0 [B][3] {x, y, yaw}), optional true start poses (truth0 [B][3], empty = the config's init pose);
+// maps [B][L_stride][2] with L [B] landmarks each; commands [B] of one timestep or [T][B][2] floats of a run.
+#define SLAM_FILTER_EACH_METHODS                                                                                                          \
+    void init(const std::vector<float>& pose0, const std::vector<double>& truth0 = {}) {                                                \
+        need(); checkSize(pose0.size(), 3 * (size_t)batch_, "pose0");                                                                   \
+        if (!truth0.empty()) checkSize(truth0.size(), 3 * (size_t)batch_, "truth0");                                                   \
+        check(slam_init_each(h_, pose0.data(), truth0.empty() ? nullptr : truth0.data()));                                               \
+        isInit = true;                                                                                                                   \
+    }                                                                                                                                    \
+    void setMap(const std::vector<double>& maps, const std::vector<int32_t>& L, int L_stride) {                                          \
+        need(); checkSize(L.size(), (size_t)batch_, "L"); checkSize(maps.size(), 2 * (size_t)L_stride * batch_, "maps");               \
+        check(slam_set_maps(h_, maps.data(), L.data(), L_stride));                                                                       \
+    }                                                                                                                                    \
+    void updateBatch(const std::vector<Command>& cmds, const float* meas, const int32_t* meas_count, int k_stride) {                     \
+        need(); check(slam_step_each(h_, packCommands(cmds, batch_).data(), meas, meas_count, k_stride));                                \
+    }                                                                                                                                    \
+    void updateSim(const std::vector<Command>& cmds) { need(); check(slam_run_sim_each(h_, packCommands(cmds, batch_).data(), 1)); }   \
+    void runSim(const std::vector<float>& cmds) {                                                                                        \
+        need();                                                                                                                          \
+        if (cmds.size() % (2 * (size_t)batch_) != 0) checkSize(cmds.size(), 2 * (size_t)batch_ * (cmds.size() / (2 * (size_t)batch_) + 1), "cmds [T][B][2]"); \
+        check(slam_run_sim_each(h_, cmds.data(), (int)(cmds.size() / (2 * (size_t)batch_))));                                           \
+    }
+
 class Filter {  // filter.h:54-77
 public:
     FilterChoice type = FilterChoice::NOT_SET;
@@ -127,6 +160,7 @@ public:
         const float c[2] = {cmd.fwd, cmd.ang};
         check(slam_step_sim(h_, c));
     }
+    SLAM_FILTER_EACH_METHODS   // per-instance start poses, maps and commands
     std::vector<double> getStateVector() override { return getStateVector(0); }   // ekf.cpp:181-184
     std::vector<double> getStateVector(int instance) {
         need();
@@ -207,6 +241,8 @@ public:
     void updateStage(const float* d_meas, const int32_t* d_meas_count, int k_stride) { need(); check(slam_update_dev(h_, d_meas, d_meas_count, k_stride)); }
     void setMap(const std::vector<double>& map_xy) { need(); check(slam_set_map(h_, map_xy.data(), (int)(map_xy.size() / 2))); }
     void updateSim(const Command& cmd) { need(); const float c[2] = {cmd.fwd, cmd.ang}; check(slam_step_sim(h_, c)); }
+    SLAM_FILTER_EACH_METHODS   // per-instance start poses, maps and commands
+    void predictionStage(const std::vector<Command>& cmds) { need(); check(slam_predict_each(h_, packCommands(cmds, batch_).data())); }
     // ukf.cpp:47-53 (x, y, yaw, landmarks...); the reference's fixed-size Vector3d bug is not replicated
     std::vector<double> getStateVector() override {
         need();
@@ -260,6 +296,8 @@ private:
 
 // NaiveFilter (filter.h:325-369): propagate the commands, ignore the measurements.  The pose graph's default secondary
 // filter (params.yaml:60).
+#undef SLAM_FILTER_EACH_METHODS
+
 class NaiveFilter : public Filter {
 public:
     NaiveFilter() { type = FilterChoice::NAIVE_COMMAND_PROPAGATION; }

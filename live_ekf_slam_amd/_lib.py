@@ -42,6 +42,12 @@ SIGNATURES = {
     "slam_queued_steps": (C.c_int, [_H]),
     "slam_run_sim": (C.c_int, [_H, _fp, C.c_int]),
     "slam_predict": (C.c_int, [_H, _fp]),
+    "slam_init_each": (C.c_int, [_H, _fp, _dp]),
+    "slam_set_maps": (C.c_int, [_H, _dp, _ip, C.c_int]),
+    "slam_step_each": (C.c_int, [_H, _fp, _fp, _ip, C.c_int]),
+    "slam_step_each_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "slam_run_sim_each": (C.c_int, [_H, _fp, C.c_int]),
+    "slam_predict_each": (C.c_int, [_H, _fp]),
     "slam_update_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int]),
     "slam_get_state": (C.c_int, [_H, C.c_int, _dp, _dp, _ip, _ip, _ip]),
     "slam_get_sigma_points": (C.c_int, [_H, C.c_int, _dp, _ip, _ip]),

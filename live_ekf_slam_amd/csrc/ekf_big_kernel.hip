@@ -93,16 +93,21 @@ __global__ __launch_bounds__(kBigTpb) void ekf_big_step_kernel(const EkfStepPara
         s_xt[i] = v; s_xp[i] = v;
     }
     if (tid < 16) s_i[tid] = 0;
-    const float fwd = multi ? p.cmds[2 * t_off] : p.fwd;
-    const float ang = multi ? p.cmds[2 * t_off + 1] : p.ang;
+    // the command array (per-instance, shared multi-step, or none: fwd / ang) is chosen first, then read once (selecting between the
+    // three values instead put this kernel's stack in scratch)
+    const float* const cp = p.cmd_each ? p.cmd_each + ((size_t)t_off * p.B + b) * 2 : (multi ? p.cmds + 2 * t_off : nullptr);
+    const float fwd = cp ? cp[0] : p.fwd;
+    const float ang = cp ? cp[1] : p.ang;
     // ---- the message of this timestep ----
     double tx = 0.0, ty = 0.0, tth = 0.0;
     const float* meas = s_meas;
     if (p.sim) {
         if (tid < 64) {
             tx = p.truth[3 * (size_t)b]; ty = p.truth[3 * (size_t)b + 1]; tth = p.truth[3 * (size_t)b + 2];
-            const double lmx0 = lane < p.L ? p.map[2 * lane] : 0.0, lmy0 = lane < p.L ? p.map[2 * lane + 1] : 0.0;
-            const int kr = sim_wave<(1 << 30), false>(p, b, lane, fwd, ang, p.step + (uint32_t)t_off, tx, ty, tth, lmx0, lmy0, s_meas);
+            const int Lm = sim_map_size(p, b);
+            const double* const map = sim_map(p, b);
+            const double lmx0 = lane < Lm ? map[2 * lane] : 0.0, lmy0 = lane < Lm ? map[2 * lane + 1] : 0.0;
+            const int kr = sim_wave<(1 << 30), false>(p, b, lane, fwd, ang, p.step + (uint32_t)t_off, map, Lm, tx, ty, tth, lmx0, lmy0, s_meas);
             if (lane == 0) { s_i[3] = kr; s_sc[24] = tx; s_sc[25] = ty; s_sc[26] = tth; }
         }
     } else {
@@ -358,7 +363,7 @@ hipError_t launch_ekf_big_step(const EkfStepParams& p, hipStream_t stream, int f
         const hipError_t e = slam_allow_full_lds(fn);
         if (e != hipSuccess) return e;
     }
-    const int multi = (p.cmds != nullptr && p.T > 1) ? 1 : 0;
+    const int multi = (ekf_device_cmds(p) && p.T > 1) ? 1 : 0;
     const int T = multi ? p.T : 1;
     for (int t = 0; t < T; ++t) {   // one launch per timestep: the kernel keeps nothing on chip between steps
         if (f32_storage) hipLaunchKernelGGL(ekf_big_step_kernel<float>, dim3(p.B), dim3(kBigTpb), lds, stream, p, t, multi);

@@ -22,7 +22,12 @@ struct EkfStepParams {
     double* truth;      // [B][3] true pose x_v (sim_node.py:222)
     double* err_sum;    // [B]   running sum of position errors (plotting_node.py:209-212)
     const double* map;  // [L][2]
-    int32_t L;
+    int32_t L;          // landmarks of the map; with map_each: the largest L_each[b] (what the LDS sizing of a launch uses)
+    // per-instance maps (slam_set_maps), NULL = every instance reads `map`: instance b's map is map_each + b * map_stride * 2 with
+    // L_each[b] landmarks
+    const double* map_each;
+    const int32_t* L_each;
+    int32_t map_stride;
     // ---- measurements ----
     const float* meas_in;         // EXT mode: [T][B][k_stride_in][3] (one timestep per launch: T = 1)
     const int32_t* meas_count_in; // EXT mode: [T][B]
@@ -36,6 +41,9 @@ struct EkfStepParams {
     // cmds[2t], cmds[2t+1] and RNG step index step+t; the result is always left in P.  cmds == NULL: T = 1 with (fwd, ang).
     const float* cmds;
     int32_t T;
+    // per-instance commands (the slam_*_each entry points), NULL = the shared command above: timestep tn of the launch (0 .. T-1, one
+    // timestep: 0) of instance b reads cmd_each[(tn * B + b) * 2 + {0, 1}]; T and the choice of kernel are as for a shared-command launch
+    const float* cmd_each;
     // ---- filter config after readCommonParams (filter.h:105-121), effective V / W ----
     float v_d, v_th, w_r, w_b;
     double V00, V11, W00, W11;
@@ -115,6 +123,8 @@ int ekf_variant_available(int L_max, int f32_storage, int variant);
 
 // variant: 0 = the library's default for the size class and batch; otherwise a variant code (or just W).
 hipError_t launch_ekf_step(const EkfStepParams& p, int variant, int f32_storage, hipStream_t stream);
+// a launch over T timesteps of device commands (shared `cmds` or per-instance `cmd_each`), as opposed to one timestep with (fwd, ang)
+inline bool ekf_device_cmds(const EkfStepParams& p) { return p.cmds != nullptr || (p.cmd_each != nullptr && p.T > 0); }
 // the instantiation launch_ekf_step would pick for (L_max, batch, variant, storage); multi = multi-step launch
 hipError_t ekf_kernel_info(int L_max, int B, int variant, int f32_storage, int multi, EkfKernelInfo* out);
 
@@ -133,6 +143,8 @@ struct EkfInitParams {
     int32_t B, pstride, xstride, f32_storage;
     float x0, y0, yaw0;
     double tx, ty, tyaw;
+    const float* pose_each;     // [B][3] {x, y, yaw} per instance (slam_init_each), NULL = (x0, y0, yaw0) for all
+    const double* truth_each;   // [B][3] the simulator's true start pose per instance, NULL = (tx, ty, tyaw) for all
 };
 hipError_t launch_ekf_init(const EkfInitParams& p, hipStream_t stream);
 

@@ -90,7 +90,7 @@ hipError_t launch_ekf_step(const EkfStepParams& p, int variant, int f32_storage,
     const EkfVariant* v = pick_variant(p.L_max, p.B, variant, f32_storage);
     if (!v) return hipErrorInvalidConfiguration;
     if (p.long_mode) {   // a message may exceed what the size class holds (ekf_kernel.h)
-        if (p.sim || p.cmds != nullptr) return launch_ekf_big_step(p, stream, f32_storage);
+        if (p.sim || ekf_device_cmds(p)) return launch_ekf_big_step(p, stream, f32_storage);
         EkfStepParams q = p;
         q.long_mode = 1;                 // the LDS kernel: every instance whose message fits ...
         if (const hipError_t e = v->launch(q, stream); e != hipSuccess) return e;
@@ -145,9 +145,11 @@ __global__ void ekf_init_kernel(const EkfInitParams p) {
     constexpr int ld = ekf_ld(3, (int)sizeof(ST));   // rows start on 16-byte boundaries (ekf_kernel.h)
     for (int i = 0; i < 3 * ld; ++i) P[i] = (ST)0;
     P[0] = (ST)(0.01 * 0.01); P[ld + 1] = (ST)(0.01 * 0.01); P[2 * ld + 2] = (ST)(0.005 * 0.005);   // ekf.cpp:11-14
-    x[0] = (ST)p.x0; x[1] = (ST)p.y0; x[2] = (ST)p.yaw0;                             // ekf.cpp:31 (float arguments)
+    const float* const pe = p.pose_each ? p.pose_each + 3 * (size_t)b : nullptr;
+    x[0] = (ST)(pe ? pe[0] : p.x0); x[1] = (ST)(pe ? pe[1] : p.y0); x[2] = (ST)(pe ? pe[2] : p.yaw0);   // ekf.cpp:31 (float arguments)
     p.M[b] = 0; p.flags[b] = 0; p.timestep[b] = 0;
-    p.truth[3 * (size_t)b] = p.tx; p.truth[3 * (size_t)b + 1] = p.ty; p.truth[3 * (size_t)b + 2] = p.tyaw;
+    const double* const te = p.truth_each ? p.truth_each + 3 * (size_t)b : nullptr;
+    p.truth[3 * (size_t)b] = te ? te[0] : p.tx; p.truth[3 * (size_t)b + 1] = te ? te[1] : p.ty; p.truth[3 * (size_t)b + 2] = te ? te[2] : p.tyaw;
     p.err_sum[b] = 0.0;
 }
 hipError_t launch_ekf_init(const EkfInitParams& p, hipStream_t stream) {

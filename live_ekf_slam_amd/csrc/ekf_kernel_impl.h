@@ -430,7 +430,7 @@ __global__ __launch_bounds__(64 * W, (W >= 2 ? 4 : SLAM_W1_WAVES)) void ekf_step
 
 template <int NMAX, int W, int KG_, int UNR_, class ST, int PIPE, int KP_>
 hipError_t launch_variant(const EkfStepParams& p, hipStream_t stream) {
-    if (p.cmds != nullptr && p.T > 1)
+    if (ekf_device_cmds(p) && p.T > 1)
         hipLaunchKernelGGL((ekf_step_kernel<NMAX, W, KG_, UNR_, ST, PIPE, true, KP_>), dim3(p.B), dim3(64 * W), 0, stream, p);
     else   // a single step takes (fwd, ang); the host sets them to the first command of the chunk
         hipLaunchKernelGGL((ekf_step_kernel<NMAX, W, KG_, UNR_, ST, PIPE, false, KP_>), dim3(p.B), dim3(64 * W), 0, stream, p);

@@ -54,12 +54,17 @@
             if (lane == 0) s_kraw[sq] = kk;
             return;
         }
-        const float fwd_n = MULTI ? p.cmds[2 * tn] : p.fwd;
-        const float ang_n = MULTI ? p.cmds[2 * tn + 1] : p.ang;
+        // the command of timestep tn: the same read as prestep(tn), which may run a whole timestep later (decoupled loop).  The array is
+        // chosen first (per-instance or shared; a one-step launch without either takes fwd / ang), then read once.
+        const float* const cp = p.cmd_each ? p.cmd_each + ((size_t)tn * p.B + b) * 2 : (MULTI ? p.cmds + 2 * tn : nullptr);
+        const float fwd_n = (MULTI || cp) ? cp[0] : p.fwd;
+        const float ang_n = (MULTI || cp) ? cp[1] : p.ang;
         double tx = s_keep[0], ty = s_keep[1], tth = s_keep[2];
         if (lane == 0) { s_tru[sq * 6 + 0] = tx; s_tru[sq * 6 + 1] = ty; s_tru[sq * 6 + 2] = tth; }
-        const double lmx0 = lane < p.L ? p.map[2 * lane] : 0.0, lmy0 = lane < p.L ? p.map[2 * lane + 1] : 0.0;
-        const int kr = sim_wave<KCAP, false>(p, b, lane, fwd_n, ang_n, p.step + (uint32_t)tn, tx, ty, tth, lmx0, lmy0,
+        const int Lm = sim_map_size(p, b);
+        const double* const map = sim_map(p, b);
+        const double lmx0 = lane < Lm ? map[2 * lane] : 0.0, lmy0 = lane < Lm ? map[2 * lane + 1] : 0.0;
+        const int kr = sim_wave<KCAP, false>(p, b, lane, fwd_n, ang_n, p.step + (uint32_t)tn, map, Lm, tx, ty, tth, lmx0, lmy0,
                                              s_meas + sq * 3 * KCAP);   // the true pose goes to HBM in finish()
         if (lane == 0) {
             s_keep[0] = tx; s_keep[1] = ty; s_keep[2] = tth;
@@ -74,8 +79,9 @@
         int* didx = s_didx + qb * KCAP;
         int* nx = s_next + 4 * qb;
         double* ps = s_ps + 10 * qb;
-        const float fwd_n = MULTI ? p.cmds[2 * tn] : p.fwd;
-        const float ang_n = MULTI ? p.cmds[2 * tn + 1] : p.ang;
+        const float* const cp = p.cmd_each ? p.cmd_each + ((size_t)tn * p.B + b) * 2 : (MULTI ? p.cmds + 2 * tn : nullptr);   // as in simgen
+        const float fwd_n = (MULTI || cp) ? cp[0] : p.fwd;
+        const float ang_n = (MULTI || cp) ? cp[1] : p.ang;
         if (s_sim[0] <= tn) {   // not produced ahead of time (the decoupled loop's generator wavefront does that)
             simgen(tn);
             if (lane == 0) s_sim[0] = tn + 1;

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(64) void pgs_run_sim_kernel(const PgsParams p, int 
         const int i = p.N - 1 + t, t1 = i + 1;
         if (t1 >= p.N_max) { if (lane == 0) p.flags[b] |= PGS_FLAG_POSE_CAP; break; }
         const float fwd = p.cmds[2 * i], ang = p.cmds[2 * i + 1];
-        int k = sim_wave<KCAP>(p, b, lane, fwd, ang, step0 + (uint32_t)t, tx, ty, tth, lmx, lmy, s_meas);
+        int k = sim_wave<KCAP>(p, b, lane, fwd, ang, step0 + (uint32_t)t, p.map, p.L, tx, ty, tth, lmx, lmy, s_meas);
         if (k > KCAP) { k = KCAP; if (lane == 0) p.flags[b] |= PGS_FLAG_MEAS_CAP; }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         if (lane == 0) {

@@ -7,15 +7,15 @@
 namespace slam {
 
 // Executed by ONE wavefront (lane = 0..63).  `P` is a step-parameter struct with the simulator fields
-// (seed, inst0, sV00, sV11, sW00, sW11, d_max, th_max, range_max, fov_min, fov_max, map, L, truth).
-// fwd, ang: the commanded motion; step: RNG step index.  tx, ty, tth: the instance's true pose (prefetched),
-// advanced in place; lmx, lmy: prefetched map entry of id = lane.
+// (seed, inst0, sV00, sV11, sW00, sW11, d_max, th_max, range_max, fov_min, fov_max, truth).
+// fwd, ang: the commanded motion; step: RNG step index.  map, L: the instance's true map [L][2] (the shared map or its own,
+// slam_set_maps).  tx, ty, tth: the instance's true pose (prefetched), advanced in place; lmx, lmy: prefetched map entry of id = lane.
 // Writes the [id, range, bearing] float32 triplets of the visible landmarks (ascending id) to s_meas and returns
 // their count (wave-uniform; triplets beyond KCAP are not stored, the caller caps and flags); lane 0 stores the new
 // truth pose unless STORE_TRUTH is false (the EKF kernel writes it when it knows whether the instance froze).
 template <int KCAP, bool STORE_TRUTH = true, class P>
-__device__ __forceinline__ int sim_wave(const P& p, int b, int lane, float fwd, float ang, uint32_t step, double& tx,
-                                        double& ty, double& tth, double lmx, double lmy, float* s_meas) {
+__device__ __forceinline__ int sim_wave(const P& p, int b, int lane, float fwd, float ang, uint32_t step, const double* map, int L,
+                                        double& tx, double& ty, double& tth, double lmx, double lmy, float* s_meas) {
     const uint64_t inst = (uint64_t)(p.inst0 + b);
     double u0, u1;
     noise_pair(p.seed, inst, step, 0u, &u0, &u1);
@@ -32,12 +32,12 @@ __device__ __forceinline__ int sim_wave(const P& p, int b, int lane, float fwd, 
     tth = tth + hdg;
     int count = 0;
 #pragma unroll 1
-    for (int base = 0; base < p.L; base += 64) {
+    for (int base = 0; base < L; base += 64) {
         const int id = base + lane;
         bool vis = false;
         double r = 0.0, beta = 0.0;
-        if (id < p.L) {
-            if (base > 0) { lmx = p.map[2 * id]; lmy = p.map[2 * id + 1]; }   // ids 0..63 were prefetched
+        if (id < L) {
+            if (base > 0) { lmx = map[2 * id]; lmy = map[2 * id + 1]; }   // ids 0..63 were prefetched
             const double dx = lmx - tx, dy = lmy - ty;
             r = sqrt(dx * dx + dy * dy);
             const double gb = det_atan2(dy, dx);
@@ -64,5 +64,12 @@ __device__ __forceinline__ int sim_wave(const P& p, int b, int lane, float fwd, 
     }
     return count;   // the caller caps at KCAP and flags the overflow
 }
+
+// The true map of instance b and its landmark count: its own (slam_set_maps) or the shared one.  The branch is on a pointer of the
+// parameter block, uniform over the launch.
+template <class P>
+__device__ __forceinline__ const double* sim_map(const P& p, int b) { return p.map_each ? p.map_each + (size_t)b * p.map_stride * 2 : p.map; }
+template <class P>
+__device__ __forceinline__ int sim_map_size(const P& p, int b) { return p.map_each ? p.L_each[b] : p.L; }
 
 }  // namespace slam

@@ -136,6 +136,14 @@ struct slam_handle {
     int run_chunk = 0;                                // timesteps per launch in slam_run_sim (0 = all of them)
     int base = 3;                                     // state offset of the first landmark: 3 (EKF) or 4 (UKF)
     bool dump_meas = false;
+    // per-instance inputs (the slam_*_each entry points).  slam_set_maps: one true map per instance, [B][map_stride][2] and [B] landmark
+    // counts; while maps_each is set, L above is the largest count (the size-class and LDS decisions use it) and the kernels read these
+    // instead of dmap.  Host copies for the shadow of slam_track_instance.
+    DevBuf<double> dmaps; DevBuf<int32_t> dLs; int map_stride = 0; bool maps_each = false;
+    std::vector<double> hmaps; std::vector<int32_t> hLs;
+    DevBuf<float> dcmd_each;                          // per-instance commands of the launches of one call: [T][B][2]
+    bool pred_each = false;                           // UKF: slam_predict_each done, the pending update stage reads dcmd_each
+    DevBuf<float> dpose_each; DevBuf<double> dstart_each;   // slam_init_each: EKF [B][3] start poses; [B][4] UKF x_t heads + [B][3] true poses
 };
 
 namespace {
@@ -153,8 +161,15 @@ void set_step_input(const slam_handle* h, Params& p, int sim, int long_cap, cons
 
 // Every EKF step launch: T = 0 is one timestep with `cmd`; T > 0 is a multi-step launch over the device commands d_cmds, whose first
 // command is `cmd`, with the messages of timestep t at meas + t * B * k_stride * 3 / count + t * B.
+// The maps of slam_set_maps, if set, and per-instance commands d_cmd_each (device, [T][B][2]; NULL = the shared ones).
+template <class Params>
+void set_each_inputs(const slam_handle* h, Params& p, const float* d_cmd_each) {
+    if (h->maps_each) { p.map_each = h->dmaps; p.L_each = h->dLs; p.map_stride = h->map_stride; }
+    p.cmd_each = d_cmd_each;
+}
+
 void fill_ekf_params(slam_handle* h, slam::EkfStepParams& p, const float cmd[2], int sim, int long_cap, const float* meas, const int32_t* count,
-                     int k_stride, const float* d_cmds, int T) {
+                     int k_stride, const float* d_cmds, int T, const float* d_cmd_each = nullptr) {
     memset(&p, 0, sizeof(p));
     p.P = h->dP; p.P_out = h->dP2; p.x = h->dx; p.scratch = h->dscratch; p.M = h->dM; p.ids = h->dids; p.flags = h->dflags; p.timestep = h->dts;
     p.truth = h->dtruth; p.err_sum = h->derr; p.map = h->dmap; p.L = h->L;
@@ -179,9 +194,11 @@ void fill_ekf_params(slam_handle* h, slam::EkfStepParams& p, const float cmd[2],
     p.khist = h->dkhist;
     set_step_input(h, p, sim, long_cap, meas, count, k_stride);
     p.cmds = d_cmds; p.T = T;
+    set_each_inputs(h, p, d_cmd_each);
 }
 
-void fill_ukf_params(slam_handle* h, slam::UkfStepParams& p, const float cmd[2]) {
+// d_cmd_each: [B][2] per-instance commands of this timestep (device), NULL = cmd
+void fill_ukf_params(slam_handle* h, slam::UkfStepParams& p, const float cmd[2], const float* d_cmd_each = nullptr) {
     memset(&p, 0, sizeof(p));
     p.P = (const double*)h->dP.get(); p.P_out = (double*)h->dP2.get(); p.x = (double*)h->dx.get(); p.sqtP = h->dsq; p.n_sq = h->dnsq; p.x_prev = h->dxprev; p.Vt_store = h->dvt; p.v_age = h->dvage;
     p.M = h->dM; p.ids = h->dids; p.flags = h->dflags; p.timestep = h->dts;
@@ -205,6 +222,7 @@ void fill_ukf_params(slam_handle* h, slam::UkfStepParams& p, const float cmd[2])
     p.big_ws = h->dbigws;
     p.prof = (h->dbg & 4) ? h->dprof : nullptr;
     p.chol_ok = h->chol ? h->dchol : nullptr;
+    set_each_inputs(h, p, d_cmd_each);
 }
 
 // ekf.cpp:65,73 and ukf.cpp:249-287 walk a message of any length.  The LDS size classes hold as many detections of one message as the class
@@ -233,9 +251,9 @@ int long_message_cap(slam_handle* h, int sim, int k_stride, int* cap_out) {
 
 // one UKF timestep of instances [b_off, b_off + b_cnt) on `stream`
 int launch_ukf_pair(slam_handle* h, const float cmd[2], int sim, int long_cap, const float* meas, const int32_t* count, int k_stride,
-                    int b_off, int b_cnt, hipStream_t stream) {
+                    int b_off, int b_cnt, hipStream_t stream, const float* d_cmd_each = nullptr) {
     slam::UkfStepParams p;
-    fill_ukf_params(h, p, cmd);
+    fill_ukf_params(h, p, cmd, d_cmd_each);
     set_step_input(h, p, sim, long_cap, meas, count, k_stride);
     p.b_off = b_off; p.b_cnt = b_cnt;
     HIP_TRY(slam::launch_ukf_sqrt(p, stream));   // nearestSPD + sqrt (ukf.cpp:106-123,208)
@@ -243,17 +261,18 @@ int launch_ukf_pair(slam_handle* h, const float cmd[2], int sim, int long_cap, c
     return SLAM_OK;
 }
 
-// one timestep, either filter kind; `sim` = device-side measurement generator
-int launch_step(slam_handle* h, const float cmd[2], int sim, const float* d_meas, const int32_t* d_count, int k_stride) {
+// one timestep, either filter kind; `sim` = device-side measurement generator; d_cmd_each: [B][2] per-instance commands (device) or NULL
+int launch_step(slam_handle* h, const float cmd[2], int sim, const float* d_meas, const int32_t* d_count, int k_stride,
+                const float* d_cmd_each = nullptr) {
     if (h->predicted) return fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev before the next step");
     int long_cap = 0;
     if (const int rc = long_message_cap(h, sim, k_stride, &long_cap)) return rc;
     if (h->kind == SLAM_EKF_SLAM) {
         slam::EkfStepParams p;
-        fill_ekf_params(h, p, cmd, sim, long_cap, d_meas, d_count, k_stride, nullptr, 0);
+        fill_ekf_params(h, p, cmd, sim, long_cap, d_meas, d_count, k_stride, nullptr, 0, d_cmd_each);
         HIP_TRY(slam::launch_ekf_step(p, h->waves_per_filter, h->esz == 4, h->stream));
     } else {
-        TRY(launch_ukf_pair(h, cmd, sim, long_cap, d_meas, d_count, k_stride, 0, h->B, h->stream));
+        TRY(launch_ukf_pair(h, cmd, sim, long_cap, d_meas, d_count, k_stride, 0, h->B, h->stream, d_cmd_each));
         std::swap(h->dP, h->dP2);   // UKF: the kernel wrote the next P_t into the other buffer (the EKF kernel updates dP in place)
     }
     h->step += 1;
@@ -277,10 +296,30 @@ int reserve_cmds(slam_handle* h, int T) {
     return SLAM_OK;
 }
 
+// slam_set_map or slam_set_maps has given the simulator a true map
+bool has_map(const slam_handle* h) { return h->dmap || h->maps_each; }
+
+// per-instance commands [T][B][2] of one call from the host into dcmd_each, in stream order (the launches of earlier calls that read the
+// buffer come first; it grows only once they are done).  A pending prediction stage reads the buffer, so nothing may replace it then.
+int upload_cmds_each(slam_handle* h, const float* cmds, int T) {
+    if (h->predicted) return fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev before the next step");
+    const size_t n = 2 * (size_t)T * h->B;
+    if (n == 0) return SLAM_OK;
+    if (h->dcmd_each.cap() < n) {
+        if (h->dcmd_each) HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(h->dcmd_each.reserve(n));
+    }
+    HIP_TRY(hipMemcpyAsync(h->dcmd_each, cmds, sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
+    return SLAM_OK;
+}
+
+constexpr float kNoCmd[2] = {0.f, 0.f};   // the shared command of a launch whose commands are per instance (not read)
+
 }  // namespace
 
-static int run_sim_now(slam_handle* h, const float* cmds, int T);
+static int run_sim_now(slam_handle* h, const float* cmds, int T, const float* d_cmd_each = nullptr);
 static int flush_lazy(slam_handle* h);
+static int step_host_now(slam_handle* h, const float cmd[2], const float* d_cmd_each, const float* meas, const int32_t* count, int k_stride, int kmax);
 // Whether the EKF step queue can take one more step from `src` as it stands: it is empty, or it holds steps of the same source with a
 // compatible stride (host messages: at most the stride of the fill, device messages: the same stride) and has room.  If it cannot, the
 // caller runs the queue first, so that steps run in call order.
@@ -499,6 +538,7 @@ int slam_init(slam_handle* h, float x0, float y0, float yaw0) {
     HIP_TRY(hipSetDevice(h->device));
     if (h->kind == SLAM_EKF_SLAM) {
         slam::EkfInitParams p;
+        memset(&p, 0, sizeof(p));   // (the per-instance pointers stay NULL: the shared start pose)
         p.P = h->dP; p.x = h->dx; p.M = h->dM; p.flags = h->dflags; p.timestep = h->dts; p.truth = h->dtruth; p.err_sum = h->derr;
         p.B = h->B; p.pstride = h->pstride; p.xstride = h->xstride; p.f32_storage = h->esz == 4;
         p.x0 = x0; p.y0 = y0; p.yaw0 = yaw0;
@@ -507,6 +547,7 @@ int slam_init(slam_handle* h, float x0, float y0, float yaw0) {
         HIP_TRY(slam::launch_ekf_init(p, h->stream));
     } else {
         slam::UkfInitParams p;
+        memset(&p, 0, sizeof(p));
         p.P = (double*)h->dP.get(); p.x = (double*)h->dx.get(); p.n_sq = h->dnsq; p.v_age = h->dvage; p.M = h->dM; p.flags = h->dflags; p.timestep = h->dts; p.truth = h->dtruth; p.err_sum = h->derr;
         p.B = h->B; p.pstride = h->pstride; p.xstride = h->xstride;
         double s, c;   // x_t << x_0, y_0, cos(yaw_0), sin(yaw_0) with a float argument (ukf.cpp:33)
@@ -538,6 +579,7 @@ int slam_set_map(slam_handle* h, const double* map_xy, int L) {
         HIP_TRY(hipMemcpy(h->dmapf, trip.data(), sizeof(float) * trip.size(), hipMemcpyHostToDevice));
     }
     h->L = L;
+    h->maps_each = false;   // (after slam_set_maps: back to the shared map)
     h->hmap.assign(map_xy, map_xy + 2 * (size_t)L);
     if (h->shadow) { const int rs = slam_set_map(h->shadow, map_xy, L); if (rs) return rs; }
     return SLAM_OK;
@@ -644,6 +686,15 @@ int slam_step(slam_handle* h, const float cmd[2], const float* meas, const int32
         return (q.steps() >= h->lazy_max || eager_flush(h, q.steps())) ? flush_lazy(h) : SLAM_OK;
     }
     TRY(flush_lazy(h));
+    return step_host_now(h, cmd, nullptr, meas, count, k_stride, kmax);
+}
+
+}  // extern "C"
+
+// One timestep on host messages, launched at the call (after what is queued).  d_cmd_each: [B][2] per-instance commands already on the
+// handle's stream (device), NULL = cmd.  kmax: the longest message of the call, clamped to k_stride.
+static int step_host_now(slam_handle* h, const float cmd[2], const float* d_cmd_each, const float* meas, const int32_t* count, int k_stride, int kmax) {
+    const size_t B = (size_t)h->B;
     if (h->kind == SLAM_UKF_LOC && !h->dmapf) return fail(SLAM_ERR_STATE, "UKF_LOC needs the known map: call slam_set_map first (localization_node.cpp:113-116)");
     // The caller's buffers may be reused right after return (ekf.cpp:64 copies the message), so the message is packed
     // into one of two PINNED staging buffers (only max_b count[b] detections per instance travel), copied on a separate
@@ -675,17 +726,19 @@ int slam_step(slam_handle* h, const float cmd[2], const float* meas, const int32
     HIP_TRY(hipEventRecord(s.copied, h->copy_stream));
     HIP_TRY(hipStreamWaitEvent(h->stream, s.copied, 0));
     // (kmax = the longest message of this call: beyond the size class's capacity the instances concerned take the streamed kernel, launch_step)
-    int rc = launch_step(h, cmd, 0, s.dmeas, s.dcount, kmax);
+    int rc = launch_step(h, cmd, 0, s.dmeas, s.dcount, kmax, d_cmd_each);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(s.used, h->stream));
     s.in_use = true;
     return SLAM_OK;
 }
 
+extern "C" {
+
 int slam_step_sim(slam_handle* h, const float cmd[2]) {
     if (!h || !cmd) return fail(SLAM_ERR_ARG, "bad argument");
     if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
-    if (!h->dmap) return fail(SLAM_ERR_STATE, "slam_set_map has not been called");
+    if (!has_map(h)) return fail(SLAM_ERR_STATE, "slam_set_map has not been called");
     if (h->shadow) { const int rs = slam_step_sim(h->shadow, cmd); if (rs) return rs; }
     if (h->kind == SLAM_EKF_SLAM && h->lazy_max > 1 && !h->dump_meas && h->run_chunk != 1) {
         StepQueue& q = h->q;
@@ -715,7 +768,7 @@ int slam_set_lazy_steps(slam_handle* h, int n) {
 int slam_run_sim(slam_handle* h, const float* cmds, int T) {
     if (!h || !cmds || T < 0) return fail(SLAM_ERR_ARG, "bad argument");
     if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
-    if (!h->dmap) return fail(SLAM_ERR_STATE, "slam_set_map has not been called");
+    if (!has_map(h)) return fail(SLAM_ERR_STATE, "slam_set_map has not been called");
     if (h->shadow) { const int rs = slam_run_sim(h->shadow, cmds, T); if (rs) return rs; }
     TRY(flush_lazy(h));
     return run_sim_now(h, cmds, T);
@@ -723,8 +776,12 @@ int slam_run_sim(slam_handle* h, const float* cmds, int T) {
 
 }  // extern "C"
 
-static int run_sim_now(slam_handle* h, const float* cmds, int T) {
+// d_cmd_each: the commands are per instance, [T][B][2] on the device (cmds is not read)
+static int run_sim_now(slam_handle* h, const float* cmds, int T, const float* d_cmd_each) {
     if (T == 0) return SLAM_OK;
+    const size_t each_step = 2 * (size_t)h->B;   // floats of d_cmd_each per timestep
+    auto cmd_at = [&](size_t t) { return d_cmd_each ? kNoCmd : cmds + 2 * t; };
+    auto each_at = [&](size_t t) { return d_cmd_each ? d_cmd_each + t * each_step : nullptr; };
     if (h->predicted) return fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev before the next step");
     if (h->kind != SLAM_EKF_SLAM && !h->dump_meas && h->B >= h->ukf_split_min) {
         // UKF: two launches per timestep (LDS-bound eigen-sqrt, then the latency-heavier sigma-point kernel).  The two
@@ -747,7 +804,7 @@ static int run_sim_now(slam_handle* h, const float* cmds, int T) {
                 const int b_off = part * per;
                 const int b_cnt = h->B - b_off < per ? h->B - b_off : per;
                 if (b_cnt <= 0) continue;
-                TRY(launch_ukf_pair(h, cmds + 2 * (size_t)t, 1, long_cap, nullptr, nullptr, 0, b_off, b_cnt, part ? h->aux_stream[part - 1] : h->stream));
+                TRY(launch_ukf_pair(h, cmd_at(t), 1, long_cap, nullptr, nullptr, 0, b_off, b_cnt, part ? h->aux_stream[part - 1] : h->stream, each_at(t)));
             }
             std::swap(h->dP, h->dP2);
             h->step += 1;
@@ -762,7 +819,7 @@ static int run_sim_now(slam_handle* h, const float* cmds, int T) {
         // one launch (pair) per timestep
         HIP_TRY(hipSetDevice(h->device));
         for (int t = 0; t < T; ++t) {
-            int rc = launch_step(h, cmds + 2 * (size_t)t, 1, nullptr, nullptr, 0);
+            int rc = launch_step(h, cmd_at(t), 1, nullptr, nullptr, 0, each_at(t));
             if (rc) return rc;
         }
         return SLAM_OK;
@@ -770,15 +827,18 @@ static int run_sim_now(slam_handle* h, const float* cmds, int T) {
     // EKF: every workgroup carries its instance through a whole chunk of timesteps, keeping x_t, the landmark ids,
     // the true pose and the thin rows/cols of P on chip; only the P stream touches HBM each step.
     HIP_TRY(hipSetDevice(h->device));
-    TRY(reserve_cmds(h, T));
-    HIP_TRY(hipMemcpyAsync(h->dcmds, cmds, sizeof(float) * 2 * (size_t)T, hipMemcpyHostToDevice, h->stream));
+    if (!d_cmd_each) {
+        TRY(reserve_cmds(h, T));
+        HIP_TRY(hipMemcpyAsync(h->dcmds, cmds, sizeof(float) * 2 * (size_t)T, hipMemcpyHostToDevice, h->stream));
+    }
     const int chunk = h->run_chunk > 0 ? h->run_chunk : T;
     int long_cap = 0;   // a map with more landmarks than a message of this size class holds: the streamed kernel, a launch per timestep
     if (const int rc = long_message_cap(h, 1, 0, &long_cap)) return rc;
     for (int t0 = 0; t0 < T; t0 += chunk) {
         const int tc = T - t0 < chunk ? T - t0 : chunk;
         slam::EkfStepParams p;
-        fill_ekf_params(h, p, cmds + 2 * (size_t)t0, 1, long_cap, nullptr, nullptr, 0, h->dcmds + 2 * (size_t)t0, tc);
+        if (d_cmd_each) fill_ekf_params(h, p, kNoCmd, 1, long_cap, nullptr, nullptr, 0, nullptr, tc, each_at(t0));
+        else fill_ekf_params(h, p, cmds + 2 * (size_t)t0, 1, long_cap, nullptr, nullptr, 0, h->dcmds + 2 * (size_t)t0, tc);
         HIP_TRY(slam::launch_ekf_step(p, h->waves_per_filter, h->esz == 4, h->stream));
         h->step += (uint32_t)tc;
     }
@@ -846,6 +906,7 @@ int slam_predict(slam_handle* h, const float cmd[2]) {
     fill_ukf_params(h, p, cmd);
     HIP_TRY(slam::launch_ukf_sqrt(p, h->stream));
     h->pred_cmd[0] = cmd[0]; h->pred_cmd[1] = cmd[1];
+    h->pred_each = false;
     h->predicted = true;
     return SLAM_OK;
 }
@@ -864,7 +925,7 @@ int slam_update_dev(slam_handle* h, const float* d_meas, const int32_t* d_count,
     int long_cap = 0;
     if (const int rc = long_message_cap(h, 0, k_stride, &long_cap)) return rc;
     slam::UkfStepParams p;
-    fill_ukf_params(h, p, h->pred_cmd);
+    fill_ukf_params(h, p, h->pred_cmd, h->pred_each ? h->dcmd_each.get() : nullptr);
     p.sim = 0;
     p.long_mode = long_cap > 0 ? 1 : 0; p.long_cap = long_cap;
     p.meas_in = d_meas; p.meas_count_in = d_count; p.k_stride_in = k_stride;
@@ -872,6 +933,7 @@ int slam_update_dev(slam_handle* h, const float* d_meas, const int32_t* d_count,
     std::swap(h->dP, h->dP2);
     h->step += 1;
     h->predicted = false;
+    h->pred_each = false;
     return SLAM_OK;
 }
 
@@ -1135,7 +1197,9 @@ int slam_track_instance(slam_handle* h, int inst) {
     s->seed = h->seed; s->inst0 = h->inst0 + inst;
     s->range_max = h->range_max; s->fov_min = h->fov_min; s->fov_max = h->fov_max;
     s->waves_per_filter = h->waves_per_filter;
-    if (!h->hmap.empty()) rc = slam_set_map(s, h->hmap.data(), h->L);
+    if (!h->hmap.empty()) rc = slam_set_map(s, h->hmap.data(), (int)(h->hmap.size() / 2));
+    if (!rc && h->maps_each)   // the instance's own map (set after the shared one, which it replaces)
+        rc = slam_set_maps(s, h->hmaps.data() + (size_t)inst * h->map_stride * 2, h->hLs.data() + inst, h->map_stride);
     if (!rc && h->inited) {
         // the instance's state as it is now: same slab layout (pstride / xstride depend on L_max and dtype only)
         const size_t b = (size_t)inst, e = (size_t)h->esz;
@@ -1338,6 +1402,158 @@ int slam_math_probe(const double* a, const double* b, double* out, int n, int de
     HIP_TRY(slam::launch_math_probe(da, db, dout, n, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, dout, sizeof(double) * 8 * (size_t)n, hipMemcpyDeviceToHost));
+    return SLAM_OK;
+}
+
+// ---- heterogeneous batches: per-instance start poses, maps and commands ---------------------------------------------------------------
+int slam_init_each(slam_handle* h, const float* pose0, const double* truth0) {
+    if (!h || !pose0) return fail(SLAM_ERR_ARG, "bad argument");
+    TRY(flush_lazy(h));
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t B = (size_t)h->B;
+    if (h->kind == SLAM_EKF_SLAM) {
+        HIP_TRY(h->dpose_each.reserve(3 * B));
+        if (truth0) HIP_TRY(h->dstart_each.reserve(3 * B));
+        HIP_TRY(hipMemcpyAsync(h->dpose_each, pose0, sizeof(float) * 3 * B, hipMemcpyHostToDevice, h->stream));
+        if (truth0) HIP_TRY(hipMemcpyAsync(h->dstart_each, truth0, sizeof(double) * 3 * B, hipMemcpyHostToDevice, h->stream));
+        slam::EkfInitParams p;
+        memset(&p, 0, sizeof(p));
+        p.P = h->dP; p.x = h->dx; p.M = h->dM; p.flags = h->dflags; p.timestep = h->dts; p.truth = h->dtruth; p.err_sum = h->derr;
+        p.B = h->B; p.pstride = h->pstride; p.xstride = h->xstride; p.f32_storage = h->esz == 4;
+        p.tx = h->cfg.init_x; p.ty = h->cfg.init_y; p.tyaw = h->cfg.init_yaw;
+        p.pose_each = h->dpose_each; p.truth_each = truth0 ? h->dstart_each.get() : nullptr;
+        HIP_TRY(slam::launch_ekf_init(p, h->stream));
+    } else {
+        // x_t << x_0, y_0, cos(yaw_0), sin(yaw_0) with a float argument (ukf.cpp:33), per instance as slam_init computes it
+        std::vector<double> st(7 * B);
+        for (size_t b = 0; b < B; ++b) {
+            double sn, cs;
+            slam::det_sincos((double)pose0[3 * b + 2], &sn, &cs);
+            st[4 * b] = pose0[3 * b]; st[4 * b + 1] = pose0[3 * b + 1];
+            st[4 * b + 2] = h->cfg.ukf_float_trig ? (double)(float)cs : cs;
+            st[4 * b + 3] = h->cfg.ukf_float_trig ? (double)(float)sn : sn;
+        }
+        if (truth0) memcpy(st.data() + 4 * B, truth0, sizeof(double) * 3 * B);
+        HIP_TRY(h->dstart_each.reserve(7 * B));
+        HIP_TRY(hipMemcpyAsync(h->dstart_each, st.data(), sizeof(double) * (truth0 ? 7 : 4) * B, hipMemcpyHostToDevice, h->stream));
+        slam::UkfInitParams p;
+        memset(&p, 0, sizeof(p));
+        p.P = (double*)h->dP.get(); p.x = (double*)h->dx.get(); p.n_sq = h->dnsq; p.v_age = h->dvage; p.M = h->dM; p.flags = h->dflags; p.timestep = h->dts; p.truth = h->dtruth; p.err_sum = h->derr;
+        p.B = h->B; p.pstride = h->pstride; p.xstride = h->xstride;
+        p.tx = h->cfg.init_x; p.ty = h->cfg.init_y; p.tyaw = h->cfg.init_yaw;
+        p.x_each = h->dstart_each; p.truth_each = truth0 ? h->dstart_each + 4 * B : nullptr;
+        HIP_TRY(slam::launch_ukf_init(p, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));   // (the host vector of the UKF is staged; the buffers are free for the next call)
+    h->step = 0;
+    h->inited = true;
+    if (h->shadow) return slam_init_each(h->shadow, pose0 + 3 * (size_t)h->tracked, truth0 ? truth0 + 3 * (size_t)h->tracked : nullptr);
+    return SLAM_OK;
+}
+
+int slam_set_maps(slam_handle* h, const double* maps, const int32_t* L, int L_stride) {
+    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
+    if (h->kind == SLAM_UKF_LOC) return fail(SLAM_ERR_UNSUPPORTED, "UKF_LOC localises against one known map: slam_set_map");
+    if (!maps || !L || L_stride <= 0) return fail(SLAM_ERR_ARG, "bad argument");
+    const size_t B = (size_t)h->B;
+    int Lmax = 0;
+    for (size_t b = 0; b < B; ++b) {
+        if (L[b] <= 0 || L[b] > L_stride) return fail(SLAM_ERR_ARG, "instance %zu: %d landmarks, outside [1, L_stride = %d]", b, L[b], L_stride);
+        Lmax = L[b] > Lmax ? L[b] : Lmax;
+    }
+    TRY(flush_lazy(h));
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t nm = 2 * (size_t)L_stride * B;
+    if (h->dmaps.cap() < nm || h->dLs.cap() < B) {   // both new blocks first: a failure leaves the handle with the maps it had
+        DevBuf<double> m; DevBuf<int32_t> l;
+        HIP_TRY(m.reserve(nm)); HIP_TRY(l.reserve(B));
+        HIP_TRY(hipStreamSynchronize(h->stream));     // the launches that read the old ones are done
+        h->dmaps = std::move(m); h->dLs = std::move(l);
+    } else {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(h->dmaps, maps, sizeof(double) * nm, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->dLs, L, sizeof(int32_t) * B, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->maps_each = true; h->map_stride = L_stride; h->L = Lmax;
+    if (h->kind == SLAM_EKF_SLAM) {   // the shadow of slam_track_instance (EKF handles only) takes its slice
+        h->hmaps.assign(maps, maps + nm);
+        h->hLs.assign(L, L + B);
+    }
+    if (h->shadow) return slam_set_maps(h->shadow, maps + (size_t)h->tracked * L_stride * 2, L + h->tracked, L_stride);
+    return SLAM_OK;
+}
+
+int slam_step_each(slam_handle* h, const float* cmds, const float* meas, const int32_t* count, int k_stride) {
+    if (!h || !cmds || !meas || !count || k_stride <= 0) return fail(SLAM_ERR_ARG, "bad argument");
+    if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->shadow) {
+        const int t = h->tracked;
+        const int rs = slam_step_each(h->shadow, cmds + 2 * (size_t)t, meas + (size_t)t * k_stride * 3, count + t, k_stride);
+        if (rs) return rs;
+    }
+    TRY(flush_lazy(h));   // not queued itself: what is queued runs first
+    const size_t B = (size_t)h->B;
+    int kmax = 0;
+    for (size_t b = 0; b < B; ++b) kmax = count[b] > kmax ? count[b] : kmax;
+    kmax = kmax < k_stride ? kmax : k_stride;
+    TRY(upload_cmds_each(h, cmds, 1));
+    return step_host_now(h, kNoCmd, h->dcmd_each, meas, count, k_stride, kmax);
+}
+
+int slam_step_each_dev(slam_handle* h, const float* d_cmds, const float* d_meas, const int32_t* d_count, int k_stride) {
+    if (!h || !d_cmds || !d_meas || !d_count || k_stride <= 0) return fail(SLAM_ERR_ARG, "bad argument");
+    if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->shadow) {   // as slam_step_dev: the shadow's step is ordered after the caller's work on the handle's stream, and the other way round
+        if (!h->shadow_ev) HIP_TRY(hipEventCreateWithFlags(&h->shadow_ev, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(h->shadow_ev, h->stream));
+        HIP_TRY(hipStreamWaitEvent(h->shadow->stream, h->shadow_ev, 0));
+        const int t = h->tracked;
+        const int rs = slam_step_each_dev(h->shadow, d_cmds + 2 * (size_t)t, d_meas + (size_t)t * k_stride * 3, d_count + t, k_stride);
+        if (rs) return rs;
+        HIP_TRY(hipEventRecord(h->shadow_ev, h->shadow->stream));
+        HIP_TRY(hipStreamWaitEvent(h->stream, h->shadow_ev, 0));
+    }
+    TRY(flush_lazy(h));
+    if (h->kind == SLAM_UKF_LOC && !h->dmapf) return fail(SLAM_ERR_STATE, "UKF_LOC needs the known map: call slam_set_map first (localization_node.cpp:113-116)");
+    return launch_step(h, kNoCmd, 0, d_meas, d_count, k_stride, d_cmds);
+}
+
+int slam_run_sim_each(slam_handle* h, const float* cmds, int T) {
+    if (!h || !cmds || T < 0) return fail(SLAM_ERR_ARG, "bad argument");
+    if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
+    if (!has_map(h)) return fail(SLAM_ERR_STATE, "slam_set_map has not been called");
+    if (h->shadow && T > 0) {   // the tracked instance's column of the commands
+        std::vector<float> mine(2 * (size_t)T);
+        for (size_t t = 0; t < (size_t)T; ++t) {
+            mine[2 * t] = cmds[(t * h->B + h->tracked) * 2];
+            mine[2 * t + 1] = cmds[(t * h->B + h->tracked) * 2 + 1];
+        }
+        const int rs = slam_run_sim_each(h->shadow, mine.data(), T);
+        if (rs) return rs;
+    }
+    TRY(flush_lazy(h));
+    if (T == 0) return SLAM_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    TRY(upload_cmds_each(h, cmds, T));
+    return run_sim_now(h, nullptr, T, h->dcmd_each);
+}
+
+int slam_predict_each(slam_handle* h, const float* cmds) {
+    if (!h || !cmds) return fail(SLAM_ERR_ARG, "bad argument");
+    TRY(flush_lazy(h));
+    if (h->kind == SLAM_EKF_SLAM) return fail(SLAM_ERR_UNSUPPORTED, "EKF has no separate prediction stage: EKF::update does both (ekf.cpp:37-179); use slam_step_each");
+    if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
+    if (h->predicted) return fail(SLAM_ERR_STATE, "slam_predict called twice without slam_update_dev");
+    HIP_TRY(hipSetDevice(h->device));
+    TRY(upload_cmds_each(h, cmds, 1));   // read by the update stage; nothing replaces it until then
+    slam::UkfStepParams p;
+    fill_ukf_params(h, p, kNoCmd, h->dcmd_each);
+    HIP_TRY(slam::launch_ukf_sqrt(p, h->stream));
+    h->pred_each = true;
+    h->predicted = true;
     return SLAM_OK;
 }
 

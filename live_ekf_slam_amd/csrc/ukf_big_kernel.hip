@@ -247,8 +247,11 @@ __global__ __launch_bounds__(kTpb) void ukf_big_step_kernel(const UkfStepParams 
         if (tid < 64) {
             double tth = p.truth[3 * (size_t)b + 2];
             tx = p.truth[3 * (size_t)b]; ty = p.truth[3 * (size_t)b + 1];
-            const double lmx = lane < p.L ? p.map[2 * lane] : 0.0, lmy = lane < p.L ? p.map[2 * lane + 1] : 0.0;
-            const int cnt = sim_wave<(1 << 30)>(p, b, lane, p.fwd, p.ang, p.step, tx, ty, tth, lmx, lmy, s_meas);   // stores the new true pose
+            const int Lm = sim_map_size(p, b);
+            const double* const map = sim_map(p, b);
+            const double lmx = lane < Lm ? map[2 * lane] : 0.0, lmy = lane < Lm ? map[2 * lane + 1] : 0.0;
+            const float fwd = p.cmd_each ? p.cmd_each[2 * (size_t)b] : p.fwd, ang = p.cmd_each ? p.cmd_each[2 * (size_t)b + 1] : p.ang;
+            const int cnt = sim_wave<(1 << 30)>(p, b, lane, fwd, ang, p.step, map, Lm, tx, ty, tth, lmx, lmy, s_meas);   // stores the new true pose
             if (lane == 0) { s_i[1] = cnt; s_sc[24] = tx; s_sc[25] = ty; }
         }
     } else {
@@ -267,7 +270,7 @@ __global__ __launch_bounds__(kTpb) void ukf_big_step_kernel(const UkfStepParams 
     }
 
     // ---- sigma points through the motion model (ukf.cpp:214-226,125-135); only rows 0..3 change ----
-    const float u_d = p.fwd, u_th = p.ang;
+    const float u_d = p.cmd_each ? p.cmd_each[2 * (size_t)b] : p.fwd, u_th = p.cmd_each ? p.cmd_each[2 * (size_t)b + 1] : p.ang;
     const float dd = u_d + p.v_d;
     for (int i = tid; i < ns; i += kTpb) {
         double v[4];

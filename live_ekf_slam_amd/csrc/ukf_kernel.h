@@ -27,11 +27,13 @@ struct UkfStepParams {
     double* truth;      // [B][3]
     double* err_sum;    // [B]
     const double* map;  // [L][2]
-    int32_t L;
+    int32_t L;          // landmarks of the map; with map_each: the largest L_each[b] (what the LDS sizing of a launch uses)
+    const double* map_each; const int32_t* L_each; int32_t map_stride;   // per-instance maps (slam_set_maps) as in EkfStepParams, NULL = `map`
     // ---- measurements ----
     const float* meas_in; const int32_t* meas_count_in; int32_t k_stride_in;
     float* meas_out; int32_t* meas_count_out; int32_t k_stride_out;
     float fwd, ang;
+    const float* cmd_each;   // [B][2] per-instance commands of this timestep, indexed by the GLOBAL instance b; NULL = (fwd, ang)
     // ---- filter config (filter.h:105-121) ----
     float v_d, v_th, w_r, w_b;
     double V00, V11, W00, W11;
@@ -94,6 +96,8 @@ struct UkfInitParams {
     int32_t B, pstride, xstride;
     double x0, y0, c0, s0;   // x_t = (x_0, y_0, cos(yaw_0), sin(yaw_0)) as the reference stores them (ukf.cpp:33)
     double tx, ty, tyaw;
+    const double* x_each;       // [B][4] (x_0, y_0, cos, sin) per instance (slam_init_each; the host applies ukf_float_trig), NULL = the above
+    const double* truth_each;   // [B][3] the simulator's true start pose per instance, NULL = (tx, ty, tyaw) for all
 };
 hipError_t launch_ukf_init(const UkfInitParams& p, hipStream_t stream);
 

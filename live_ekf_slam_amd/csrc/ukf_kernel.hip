@@ -994,7 +994,9 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 128 && !PROF) ? SLAM_UKF
     double tx = 0.0, ty = 0.0, tth = 0.0, lmx = 0.0, lmy = 0.0;
     if (p.sim && tid < 64) {
         tx = p.truth[3 * (size_t)b]; ty = p.truth[3 * (size_t)b + 1]; tth = p.truth[3 * (size_t)b + 2];
-        if (tid < p.L) { lmx = p.map[2 * tid]; lmy = p.map[2 * tid + 1]; }
+        const int Lm = sim_map_size(p, b);
+        const double* const map = sim_map(p, b);
+        if (tid < Lm) { lmx = map[2 * tid]; lmy = map[2 * tid + 1]; }
     }
     for (int e = tid; e < n * n; e += TPB) sS[e] = Sq[e];
     __syncthreads();
@@ -1003,7 +1005,10 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 128 && !PROF) ? SLAM_UKF
     // ---- measurements ----
     if (p.sim) {
         if (tid < 64) {
-            const int cnt = sim_wave<KCAP>(p, b, lane, p.fwd, p.ang, p.step, tx, ty, tth, lmx, lmy, s_meas);
+            const int Lm = sim_map_size(p, b);
+            const double* const map = sim_map(p, b);
+            const float fwd = p.cmd_each ? p.cmd_each[2 * (size_t)b] : p.fwd, ang = p.cmd_each ? p.cmd_each[2 * (size_t)b + 1] : p.ang;
+            const int cnt = sim_wave<KCAP>(p, b, lane, fwd, ang, p.step, map, Lm, tx, ty, tth, lmx, lmy, s_meas);
             if (lane == 0) s_misc[0] = cnt;
         }
     } else {
@@ -1052,7 +1057,7 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 128 && !PROF) ? SLAM_UKF
     }
 
     // ---- sigma points through the motion model (ukf.cpp:214-226,125-135); only rows 0..3 change ----
-    const float u_d = p.fwd, u_th = p.ang;
+    const float u_d = p.cmd_each ? p.cmd_each[2 * (size_t)b] : p.fwd, u_th = p.cmd_each ? p.cmd_each[2 * (size_t)b + 1] : p.ang;
     const float dd = u_d + p.v_d;
     for (int i = tid; i < ns; i += TPB) {
         double v[4];
@@ -1519,9 +1524,11 @@ __global__ void ukf_init_kernel(const UkfInitParams p) {
     double* x = p.x + (size_t)b * p.xstride;
     for (int i = 0; i < 16; ++i) P[i] = 0.0;
     P[0] = 0.01 * 0.01; P[5] = 0.01 * 0.01; P[10] = 0.005 * 0.005; P[15] = 0.005 * 0.005;   // ukf.cpp:9-13
-    x[0] = p.x0; x[1] = p.y0; x[2] = p.c0; x[3] = p.s0;                                       // ukf.cpp:33
+    const double* const xe = p.x_each ? p.x_each + 4 * (size_t)b : nullptr;
+    x[0] = xe ? xe[0] : p.x0; x[1] = xe ? xe[1] : p.y0; x[2] = xe ? xe[2] : p.c0; x[3] = xe ? xe[3] : p.s0;   // ukf.cpp:33
     p.M[b] = 0; p.flags[b] = 0; p.timestep[b] = 0; p.n_sq[b] = 0; p.v_age[b] = -1;
-    p.truth[3 * (size_t)b] = p.tx; p.truth[3 * (size_t)b + 1] = p.ty; p.truth[3 * (size_t)b + 2] = p.tyaw;
+    const double* const te = p.truth_each ? p.truth_each + 3 * (size_t)b : nullptr;
+    p.truth[3 * (size_t)b] = te ? te[0] : p.tx; p.truth[3 * (size_t)b + 1] = te ? te[1] : p.ty; p.truth[3 * (size_t)b + 2] = te ? te[2] : p.tyaw;
     p.err_sum[b] = 0.0;
 }
 hipError_t launch_ukf_init(const UkfInitParams& p, hipStream_t stream) {

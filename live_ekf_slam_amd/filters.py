@@ -4,7 +4,8 @@ The reference drives ONE filter object through
     readParams(config) -> init(x_0, y_0, yaw_0) -> update(cmdMsg, lmMeasMsg) -> publishState()/getStateVector()
 (ekf_ws/src/localization_pkg/include/localization_pkg/filter.h:54-77; caller: localization_node.cpp:33-47,
 90-106,108-140).  `BatchedEKF` keeps those names, argument meanings and the exception-on-error convention, for a
-batch of B Monte-Carlo instances that share map + commands; everything numeric happens in libslam_hip.so.
+batch of B instances that share map + commands (Monte-Carlo seeds) or get their own start pose, map and commands (several robots or
+scenarios: the per-instance forms of init / set_map / update / run_sim); everything numeric happens in libslam_hip.so.
 The C++ twin of this class (for a C++/ROS host) is include/slam_filter.hpp.
 """
 import ctypes as C
@@ -87,11 +88,25 @@ class BatchedFilter:
             raise _lib.SlamError("readParams() must be called before using the filter")
 
     # -- Filter::init(float x_0, float y_0, float yaw_0) (filter.h:60) --
-    def init(self, x_0=0.0, y_0=0.0, yaw_0=0.0):
+    def init(self, x_0=0.0, y_0=0.0, yaw_0=0.0, truth0=None):
+        """Scalars: one start pose for the batch.  x_0 a (batch, 3) array of (x, y, yaw): one per instance (slam_init_each; y_0 and
+        yaw_0 are then ignored).  truth0: optional (batch, 3) true start poses of the simulator (default: the config's init pose)."""
         self._need()
-        _lib.check(_lib.lib().slam_init(self.h, x_0, y_0, yaw_0))
+        if np.ndim(x_0) == 0 and truth0 is None:
+            _lib.check(_lib.lib().slam_init(self.h, x_0, y_0, yaw_0))
+        else:
+            pose = (np.asarray(x_0, dtype=np.float32) if np.ndim(x_0) else
+                    np.broadcast_to(np.array([x_0, y_0, yaw_0], dtype=np.float32), (self.batch, 3)))
+            pose = np.ascontiguousarray(self._rows(pose, "x_0", 3), dtype=np.float32)
+            tr = None if truth0 is None else np.ascontiguousarray(self._rows(np.asarray(truth0, dtype=np.float64), "truth0", 3))
+            _lib.check(_lib.lib().slam_init_each(self.h, _f(pose), None if tr is None else _d(tr)))
         self.isInit = True
         self.timestep = 0
+
+    def _rows(self, a, what, width):
+        if a.shape != (self.batch, width):
+            raise ValueError(f"{what}: expected shape ({self.batch}, {width}), got {a.shape}")
+        return a
 
     # -- batch plumbing that has no counterpart in the single-instance reference --
     def set_stream(self, hip_stream_ptr):
@@ -106,11 +121,34 @@ class BatchedFilter:
     def set_vision(self, range_max, fov_min, fov_max):
         self._need(); _lib.check(_lib.lib().slam_set_vision(self.h, range_max, fov_min, fov_max))
 
-    def set_map(self, map_xy):
-        """True landmark map [L][2]; `filter->map` of localization_node.cpp:152-156 / sim landmarks."""
+    def set_map(self, map_xy, counts=None):
+        """True landmark map [L][2]; `filter->map` of localization_node.cpp:152-156 / sim landmarks.  One map per instance
+        (slam_set_maps): a (batch, L_stride, 2) array with `counts` [batch] landmarks each (default: all L_stride), or a list of batch
+        (L_b, 2) maps."""
         self._need()
+        if isinstance(map_xy, (list, tuple)):
+            if counts is not None:
+                raise ValueError("counts go with a (batch, L_stride, 2) array; a list of maps carries its own")
+            maps = [np.asarray(m, dtype=np.float64) for m in map_xy]
+            if len(maps) != self.batch or any(m.ndim != 2 or m.shape[1] != 2 or m.shape[0] == 0 for m in maps):
+                raise ValueError(f"expected a list of {self.batch} maps of shape (L_b > 0, 2)")
+            counts = np.array([m.shape[0] for m in maps], dtype=np.int32)
+            arr = np.zeros((self.batch, int(counts.max()), 2))
+            for b, m in enumerate(maps):
+                arr[b, :m.shape[0]] = m
+            map_xy = arr
         m = np.ascontiguousarray(map_xy, dtype=np.float64)
-        _lib.check(_lib.lib().slam_set_map(self.h, _d(m), m.shape[0]))
+        if m.ndim == 2 and counts is None:
+            if m.shape[1] != 2 or m.shape[0] == 0:
+                raise ValueError(f"expected a map of shape (L > 0, 2), got {m.shape}")
+            _lib.check(_lib.lib().slam_set_map(self.h, _d(m), m.shape[0]))
+            return
+        if m.ndim != 3 or m.shape[0] != self.batch or m.shape[2] != 2 or m.shape[1] == 0:
+            raise ValueError(f"expected per-instance maps of shape ({self.batch}, L_stride > 0, 2), got {m.shape}")
+        cnt = np.full(self.batch, m.shape[1], np.int32) if counts is None else np.ascontiguousarray(counts, dtype=np.int32)
+        if cnt.shape != (self.batch,) or np.any(cnt <= 0) or np.any(cnt > m.shape[1]):
+            raise ValueError(f"counts: expected {self.batch} landmark counts in [1, {m.shape[1]}]")
+        _lib.check(_lib.lib().slam_set_maps(self.h, _d(m), _i(cnt), m.shape[1]))
 
     # -- Filter::update(Command, Float32MultiArray) (filter.h:61) for every instance --
     def update(self, cmdMsg, lmMeasMsg, meas_count=None):
@@ -131,33 +169,63 @@ class BatchedFilter:
         if meas.shape[1] == 0:
             meas = np.zeros((self.batch, 1, 3), np.float32)
         cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
-        _lib.check(_lib.lib().slam_step(self.h, _f(cmd), _f(meas), _i(cnt), meas.shape[1]))
+        if cnt.shape != (self.batch,):
+            raise ValueError(f"meas_count: expected shape ({self.batch},), got {cnt.shape}")
+        step = _lib.lib().slam_step_each if cmd.ndim == 2 else _lib.lib().slam_step
+        _lib.check(step(self.h, _f(cmd), _f(meas), _i(cnt), meas.shape[1]))
         self.timestep += 1
 
     def update_dev(self, cmdMsg, d_meas_ptr, d_count_ptr, k_stride):
+        """One timestep on DEVICE messages; cmdMsg is a Command / (fwd, ang) for the batch.  Per-instance commands already on the
+        device: update_dev_each."""
         self._need()
         cmd = self._cmd(cmdMsg)
+        if cmd.ndim != 1:
+            raise ValueError("update_dev takes one command; per-instance commands on the device go to update_dev_each")
         _lib.check(_lib.lib().slam_step_dev(self.h, _f(cmd), C.c_void_p(d_meas_ptr), C.c_void_p(d_count_ptr), k_stride))
         self.timestep += 1
 
+    def update_dev_each(self, d_cmds_ptr, d_meas_ptr, d_count_ptr, k_stride):
+        """One timestep with per-instance commands, all DEVICE pointers: cmds [B][2] float32, meas [B][k_stride][3], count [B]."""
+        self._need()
+        _lib.check(_lib.lib().slam_step_each_dev(self.h, C.c_void_p(d_cmds_ptr), C.c_void_p(d_meas_ptr), C.c_void_p(d_count_ptr), k_stride))
+        self.timestep += 1
+
     def update_sim(self, cmdMsg):
-        """One step with the device-side generator (get_cmd, sim_node.py:209-250) feeding the filter."""
+        """One step with the device-side generator (get_cmd, sim_node.py:209-250) feeding the filter; a (batch, 2) command array
+        gives every instance its own command."""
         self._need()
         cmd = self._cmd(cmdMsg)
-        _lib.check(_lib.lib().slam_step_sim(self.h, _f(cmd)))
+        if cmd.ndim == 2:
+            _lib.check(_lib.lib().slam_run_sim_each(self.h, _f(cmd), 1))
+        else:
+            _lib.check(_lib.lib().slam_step_sim(self.h, _f(cmd)))
         self.timestep += 1
 
     def run_sim(self, cmds):
+        """cmds: (T, 2) for the batch, or (T, batch, 2) per instance."""
         self._need()
-        c = np.ascontiguousarray(cmds, dtype=np.float32).reshape(-1, 2)
-        _lib.check(_lib.lib().slam_run_sim(self.h, _f(c), c.shape[0]))
+        c = np.ascontiguousarray(cmds, dtype=np.float32)
+        if c.ndim == 3:
+            if c.shape[1:] != (self.batch, 2):
+                raise ValueError(f"per-instance commands: expected shape (T, {self.batch}, 2), got {c.shape}")
+            _lib.check(_lib.lib().slam_run_sim_each(self.h, _f(c), c.shape[0]))
+        else:
+            if c.ndim != 2 or c.shape[1] != 2:
+                raise ValueError(f"expected commands of shape (T, 2) or (T, {self.batch}, 2), got {c.shape}")
+            _lib.check(_lib.lib().slam_run_sim(self.h, _f(c), c.shape[0]))
         self.timestep += c.shape[0]
 
-    @staticmethod
-    def _cmd(cmdMsg):
+    def _cmd(self, cmdMsg):
+        """(2,) float32 for one command, (batch, 2) for one per instance."""
         if isinstance(cmdMsg, Command):
             return np.array([cmdMsg.fwd, cmdMsg.ang], dtype=np.float32)
-        return np.ascontiguousarray(cmdMsg, dtype=np.float32).reshape(2)
+        c = np.ascontiguousarray(cmdMsg, dtype=np.float32)
+        if c.shape == (self.batch, 2):
+            return c
+        if c.size == 2:
+            return c.reshape(2)
+        raise ValueError(f"expected a command of shape (2,) or ({self.batch}, 2), got {c.shape}")
 
     # -- Filter::getStateVector() (filter.h:76; ekf.cpp:181-184) --
     def getStateVector(self, instance=0):
@@ -308,8 +376,10 @@ class BatchedUKF(BatchedFilter):
 
     # -- UKF::predictionStage / UKF::updateStage (filter.h:187-188, ukf.cpp:197-291) --
     def predictionStage(self, cmdMsg):
+        """cmdMsg: a Command / (fwd, ang) for the batch, or (batch, 2) per instance."""
         self._need()
-        _lib.check(_lib.lib().slam_predict(self.h, _f(self._cmd(cmdMsg))))
+        cmd = self._cmd(cmdMsg)
+        _lib.check((_lib.lib().slam_predict_each if cmd.ndim == 2 else _lib.lib().slam_predict)(self.h, _f(cmd)))
 
     def updateStage(self, d_meas_ptr=None, d_count_ptr=None, k_stride=0):
         """Measurements as DEVICE pointers ([B][k_stride][3] float32, [B] int32); none = empty message."""
