@@ -69,7 +69,9 @@ int pgs_run_sim(pgs_handle* h, const float* cmds, int T);
  * sequence (lambda, 10 lambda, ...) at once in spare slots and the sequential accept / lambda logic is replayed over them, so
  * the result, pgs_get_stats' iteration and trial counts are those of the sequential loop.  The slots multiply the LM work
  * space: SLAM_PGS_LANES slots per instance (default 4, 1 = off; reduced at pgs_create if they would take more than half of
- * the free device memory).
+ * the free device memory).  Trial cap: with SLAM_PGS_MAX_TRIALS = K (default 400) every graph consumes at most K lambda trials in
+ * every schedule (lockstep with or without lanes, streaming, the lockstep tail after streaming); a graph that reaches K unconverged
+ * ends flagged PGS_INST_NOT_CONVERGED with the values of its last accepted trial, so results and counts do not depend on the schedule.
  * Launch shape (results do not depend on it beyond the tolerance of the SYRK's summation order): the kernels of a trial run over
  * the compacted list of running slots (SLAM_PGS_LIST=0: full-size grids); with at most 128 running slots, or a batch that fills
  * the device twice, the block-tridiagonal chain and the Schur-complement SYRK are ONE launch with Y kept in LDS, replicated on

@@ -71,6 +71,7 @@ struct pgs_handle {
     // length the segment-count-dependent arrays are sized for (re-made on demand, resize_segments); seg_used: the last solve's.
     int seg_cur = 32, seg_alloc = 32, seg_used = 0;
     bool fused_ok = false;                    // this solve's graphs fit the fused kernel (decided in pgs_solve from max M)
+    bool syrk_inst_ok = false;                // ... and the instance-resident SYRK (its kPgsSyrkInstTiles tiles hold every lower triangle)
     int cus = 256;                            // compute units of the device
     bool use_list = true;                     // SLAM_PGS_LIST=0: full-size grids, inactive workgroups return (the round-2 launch shape)
     int fused_mode = -1;                      // SLAM_PGS_FUSED: 0 = chain and SYRK as two launches, -1 (default) = fused when the tiles fit
@@ -423,8 +424,8 @@ int launch_trial(pgs_handle* h, slam::PgsParams& p, int32_t active_hint, int lan
     p.lanes_next = lanes_for(h, active_hint);
     if (force_lanes_next > 0) p.lanes_next = force_lanes_next;
     active_hint *= p.lanes;   // the kernel variants below are chosen by the number of slots that run (an upper bound), not of instances
-    // instance-resident accumulators (code 1) from syrk_inst_switch running slots (its staging registers are sized for LD <= 448), else 32x32 wavefront tiles
-    p.syrk_wave_tile = active_hint >= h->syrk_inst_switch && p.LD <= 448 ? 1 : 32;
+    // instance-resident accumulators (code 1) from syrk_inst_switch running slots while its tiles hold every graph of the solve (syrk_inst_ok), else 32x32 wavefront tiles
+    p.syrk_wave_tile = active_hint >= h->syrk_inst_switch && h->syrk_inst_ok ? 1 : 32;
     if (profile) { if ((int)h->trial_fused.size() <= trial_index) h->trial_fused.resize(trial_index + 1); h->trial_fused[trial_index] = p.fused; }
     if (!prelaunched) HIP_TRY(hipMemsetAsync(p.n_active, 0, 4 * sizeof(int32_t), stream));
     for (int k = prelaunched ? 1 : 0; k < slam::kPgsTrialKernels; ++k) {
@@ -482,15 +483,18 @@ int pgs_solve(pgs_handle* h) {
     }
     {   // chain + SYRK in one launch (Y stays in LDS) is possible while the lower triangle of every instance fits the 72 wavefront
         // tiles of pgs_chain_syrk_kernel, a column of Y per lane (2M + 1 <= 448) and its event staging (32 factor slots per pose)
-        h->fused_ok = false; h->p.fused = 0;
-        if (!h->seg_ok && h->fused_mode != 0 && h->p.LD <= 448 && h->p.KP <= 32) {
+        // The instance-resident SYRK of the two-launch path holds kPgsSyrkInstTiles 32x32 tiles of S_ext (the z column included): 2M + 1
+        // <= 416, M <= 207.  Beyond that its last tile row was never formed (L_max 208 - 223, LD 448); the tile kernel takes those solves.
+        h->fused_ok = false; h->p.fused = 0; h->syrk_inst_ok = false;
+        if (!h->seg_ok && h->p.LD <= 448) {
             std::vector<int32_t> M((size_t)h->B);
             HIP_TRY(hipMemcpyAsync(M.data(), h->p.M, sizeof(int32_t) * (size_t)h->B, hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(hipStreamSynchronize(h->stream));
             int mx = 0;
             for (int32_t m : M) mx = m > mx ? m : mx;
-            const int nt = (2 * mx + 31) / 32;
-            h->fused_ok = nt * (nt + 1) / 2 <= 72;
+            const int nt = (2 * mx + 31) / 32, nti = (2 * mx + 1 + 31) / 32;
+            h->fused_ok = h->fused_mode != 0 && h->p.KP <= 32 && nt * (nt + 1) / 2 <= 72;
+            h->syrk_inst_ok = nti * (nti + 1) / 2 <= slam::kPgsSyrkInstTiles;
         }
     }
     HIP_TRY(hipMemsetAsync(h->p.work, 0, 3 * sizeof(double), h->stream));
@@ -534,6 +538,7 @@ int pgs_solve(pgs_handle* h) {
     }
     h->timeline.assign(G, {});
     if (G > 1) HIP_TRY(hipEventRecord(h->gevents[G], h->stream));   // everything queued on the handle's stream so far comes first
+    h->p.max_trials = h->max_trials;   // the per-graph trial cap, applied by pgs_decide_kernel in every schedule
     std::vector<slam::PgsParams> gp(G, h->p);
     std::vector<int> gtrials(G, 0), grc(G, SLAM_OK);
     std::vector<char> gdone(G, 0);
@@ -589,8 +594,7 @@ int pgs_solve(pgs_handle* h) {
                 if (last[0] == 0 || (last[4] >= wend && last[0] * G <= h->lanes_switch)) leave = true;
                 return SLAM_OK;
             };
-            // (the trial cap is per graph - pgs_decide_kernel applies it while graphs stream; the launches only need a bound that cannot bind first)
-            q.max_trials = h->max_trials;
+            // (the trial cap is per graph - pgs_decide_kernel applies it; the launches only need a bound that cannot bind first)
             const long long launch_cap = ((long long)q.b_cnt / cap + 2) * h->max_trials;
             while (!leave && t < launch_cap) {
                 q.n_list_dev = dcnt + 8 * (t & 1) + 2;
@@ -610,7 +614,9 @@ int pgs_solve(pgs_handle* h) {
         }
         const bool pipe = !profile;   // per-kernel timing wants every kernel of a trial between its own events
         int32_t* hact = h->h_active + 4 * g;
-        const int trials_end = trials + h->max_trials;   // (after a streaming phase: that many more launches for the graphs still running)
+        // a bound that cannot bind first: every launch consumes at least one trial of every graph still running, and pgs_decide_kernel ends
+        // a graph at its own max_trials-th trial
+        const int trials_end = trials + h->max_trials;
         if (act[0] > 0 && trials < trials_end) {
             bool pre = false;   // the phase's first trial runs over the list it was handed; later ones have their first kernels enqueued ahead
             bool cloned = !h->use_list || profile || h->lanes <= 1;

@@ -123,7 +123,7 @@ struct PgsParams {
                                        // sides ([nseg][6]: left 3, right 3, local columns) and the separators' rows of Y ([NS][3], global columns) live
     // the tile SYRK over an arbitrary block of Y rows: row offset, rows (-1: 3 N), per-landmark first non-zero row / 3 (NULL: lm_first)
     int64_t syrk_row0; int32_t syrk_rows; const int32_t* syrk_first;
-    int32_t max_trials;                // streaming: lambda trials after which a graph's solve is cut off (NOT_CONVERGED; lockstep: the host's cap)
+    int32_t max_trials;                // lambda trials after which a graph's solve is cut off (NOT_CONVERGED), in every schedule (SLAM_PGS_MAX_TRIALS)
     int32_t* tick_acc;                 // optional [B][2]: pgs_adopt_kernel adds the solve's LM iterations / lambda trials (solve_graph_every_iteration: sums over the ticks)
     double* tick_flop;                 // optional [B][2]: ... and the algorithmic FLOP of its trials: Schur-complement SYRK (inst_flop) | dense Cholesky + substitutions (n^3/3 + 2 n^2, n = 2 M)
     unsigned long long* prof;          // optional [B][8] phase timers of the chol kernel (100 MHz wall clock), debug only
@@ -151,6 +151,7 @@ hipError_t pgs_launch_seg_plan(const PgsParams& p, hipStream_t s);
 static constexpr int kPgsSegMaxLen = 32;      // poses a segment holds at most (seg_len <= this)
 static constexpr int kPgsSegMaxLm = 63;       // landmarks a segment's column set may hold for the segmented path (2 * 63 + 1 = 127 columns)
 static constexpr int kPgsSegMaxSep = 128;     // separators the separator kernel stages in LDS
+static constexpr int kPgsSyrkInstTiles = 96;  // 32x32 tiles of S_ext pgs_syrk_inst_kernel holds per instance (16 wavefronts x SI_NB x SI_NS)
 // one tryLambda for every active instance = kernels 0..5 in order: linearize, chain, syrk, chol, backsolve, evaluate (+ decide)
 static constexpr int kPgsTrialKernels = 6;
 hipError_t pgs_launch_trial_kernel(const PgsParams& p, int which, hipStream_t s);

@@ -154,7 +154,7 @@ __global__ __launch_bounds__(TPB) void pgs_decide_kernel(const PgsParams p) {
         const int nl = p.nl[b] > 0 ? p.nl[b] : 1;
         int win = -1, done = 0, fl = 0;
         bool end_inner = false;
-        for (int j = 0; j < nl && !end_inner; ++j) {
+        for (int j = 0; j < nl && !end_inner && trials < p.max_trials; ++j) {   // (the lanes' trials beyond the cap are not consumed)
             const int sl = j * B + b;
             const bool ok = p.nok[sl] != 0;
             const double newLin = p.nlin[sl], newError = p.nerr[sl];
@@ -186,9 +186,9 @@ __global__ __launch_bounds__(TPB) void pgs_decide_kernel(const PgsParams p) {
             else if (error <= 0.0 || relDec <= relTol || absDec <= absTol) done = 1;
             else p.cur_error[b] = error;
         }
-        // the trial cap is per GRAPH: where the host's count of launches is not a graph's count of trials (streaming) the decide step
-        // applies it (lockstep: the host stops launching + pgs_lm_end_kernel)
-        if (p.slots_cap > 0 && !done && trials >= p.max_trials) { done = 1; fl = PGS_FLAG_NOT_CONVERGED; }
+        // the trial cap is per GRAPH and applied here in every schedule (lockstep with or without lanes, streaming, the lockstep tail
+        // after streaming): the host's launch counts are bounds that cannot bind first
+        if (!done && trials >= p.max_trials) { done = 1; fl = PGS_FLAG_NOT_CONVERGED; }
         atomicAdd(p.work + (p.seg_on ? 2 : (p.fused ? 1 : 0)), (double)(trials - p.trials[b]) * p.inst_flop[b]);   // reporting only
         p.lambda[b] = lambda; p.error[b] = error; p.iters[b] = iters; p.trials[b] = trials;
         // the next trial runs the next `lanes_next` lambdas of the sequence GTSAM would walk if every one of them failed:
@@ -196,7 +196,8 @@ __global__ __launch_bounds__(TPB) void pgs_decide_kernel(const PgsParams p) {
         int nnext = 1;
         if (!done) {
             double lj = lambda;
-            const int want = p.lanes_next < p.lanes_max ? p.lanes_next : p.lanes_max;
+            int want = p.lanes_next < p.lanes_max ? p.lanes_next : p.lanes_max;
+            if (want > p.max_trials - trials) want = p.max_trials - trials;   // no lanes for trials beyond the cap (>= 1: not done)
             while (nnext < want) {
                 lj = lj * lambdaFactor;
                 if (lj >= lambdaUpper) break;

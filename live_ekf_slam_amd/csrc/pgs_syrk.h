@@ -254,6 +254,7 @@ __global__ __launch_bounds__(256, 2) void pgs_syrk_kernel(const PgsParams p) {
 // in bank space, so the 8-byte fragment reads are conflict-free.  The workgroups of one instance get ids on the same
 // XCD and march through Y in step, so all but the first read L2.
 constexpr int SI_ROWS = 16, SI_NB = 3, SI_NS = 2, SI_TPB = 1024;
+static_assert(16 * SI_NB * SI_NS == kPgsSyrkInstTiles, "the host chooses this kernel by its tile capacity (pgs_solve)");
 __global__ __launch_bounds__(SI_TPB) void pgs_syrk_inst_kernel(const PgsParams p) {
     extern __shared__ double s_y[];   // [2][SI_ROWS][ldl]
     const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;

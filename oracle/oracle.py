@@ -78,6 +78,8 @@ def lib():
         L.orc_pgs_residuals.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int]
         L.orc_pgs_gradient.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp]
         L.orc_pgs_retract.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp, _dp]
+        L.orc_pgs_jacobian.argtypes = [C.c_void_p, _dp, _dp, _ip, _ip, _dp, C.c_int, _dp, C.c_int, _ip]
+        L.orc_pgs_step.argtypes = [C.c_void_p, _dp, _dp, C.c_double, C.c_int, _dp, _dp]
         L.orc_run_pgs_batch.restype = C.c_double
         L.orc_run_pgs_batch.argtypes = [C.POINTER(SlamConfig), C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _fp, C.c_int,
                                         C.c_uint64, C.c_int64, C.c_int, C.c_int, _dp, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp,
@@ -329,6 +331,30 @@ class OraclePoseGraph:
         pn = np.zeros_like(a[0]); ln = np.zeros_like(a[1])
         lib().orc_pgs_retract(self.h, _d(a[0]), _d(a[1]), _d(a[2]), _d(a[3]), _d(pn), _d(ln))
         return pn, ln
+
+    def jacobian(self, poses, lms):
+        """Whitened sparse Jacobian of the factors at (poses [N][3], lms [M][2]) and the residual: (rows, cols, vals, e).  Rows in the
+        order of residuals(), columns 3 i + a for pose i and 3 N + 2 j + b for landmark j; 0.5 |e|^2 = cost, J^T e = gradient(), and
+        J^T J is the matrix linearize() forms (GTSAM's Between / Prior Jacobians).  Entries are listed per factor block, zeros included."""
+        poses = np.ascontiguousarray(poses, dtype=np.float64); lms = np.ascontiguousarray(lms, dtype=np.float64).reshape(-1)
+        lms = lms if lms.size else np.zeros(2)
+        N = poses.shape[0]
+        cap_rows = 3 * N + 2 * N * self.KP
+        cap_nnz = 3 + 12 * N + 10 * N * self.KP
+        rows = np.zeros(cap_nnz, dtype=np.int32); cols = np.zeros(cap_nnz, dtype=np.int32); vals = np.zeros(cap_nnz)
+        e = np.zeros(cap_rows); nnz = C.c_int(0)
+        m = lib().orc_pgs_jacobian(self.h, _d(poses), _d(lms), _i(rows), _i(cols), _d(vals), cap_nnz, _d(e), cap_rows, C.byref(nnz))
+        assert m <= cap_rows and nnz.value <= cap_nnz
+        k = nnz.value
+        return rows[:k].copy(), cols[:k].copy(), vals[:k].copy(), e[:m].copy()
+
+    def step(self, poses, lms, lam, lin_mode=LIN_SCHUR):
+        """The damped step (J^T J + lam I) delta = -J^T e at (poses, lms) with the elimination of lin_mode: (ok, dp [N][3], dl [M][2])."""
+        poses = np.ascontiguousarray(poses, dtype=np.float64); lms = np.ascontiguousarray(lms, dtype=np.float64).reshape(-1, 2)
+        M = lms.shape[0]
+        dp = np.zeros_like(poses); dl = np.zeros((max(M, 1), 2))
+        ok = lib().orc_pgs_step(self.h, _d(poses), _d(lms if M else np.zeros(2)), float(lam), int(lin_mode), _d(dp), _d(dl))
+        return bool(ok), dp, dl[:M].copy()
 
 
 def run_pgs_batch(map_xy, cmds, B, L_max, KP=8, seed=2025, inst0=0, cfg=None, math=MATH_DET, lin_mode=LIN_SCHUR, nthreads=1,

@@ -930,6 +930,66 @@ void orc_pgs_gradient(void* h, const double* poses, const double* lms, double* g
 void orc_pgs_retract(void* h, const double* poses, const double* lms, const double* dp, const double* dl, double* poses_n, double* lms_n) {
     ((Pgs*)h)->retract(poses, lms, dp, dl, poses_n, lms_n);
 }
+// The whitened sparse Jacobian J of the factors at given values, the one linearize() forms its normal equations from (Between / Prior
+// Jacobians without the rotation of the residual pose, as GTSAM's), and the residual e.  Rows in the order of orc_pgs_residuals; columns
+// 3 i + a for pose i, 3 N + 2 j + b for landmark j.  Every entry of every factor block is listed (structural zeros included); entries
+// past cap_nnz / rows past cap_rows are counted, not written.  Returns the number of rows, *nnz the number of entries.
+int orc_pgs_jacobian(void* h, const double* poses, const double* lms, int* rows, int* cols, double* vals, int cap_nnz, double* e_out,
+                     int cap_rows, int* nnz) {
+    Pgs* p = (Pgs*)h;
+    const int n = p->N();
+    int r0 = 0, k = 0;
+    auto put = [&](int r, int c, double v) {
+        if (k < cap_nnz) { rows[k] = r; cols[k] = c; vals[k] = v; }
+        k += 1;
+    };
+    auto put_e = [&](const double* e, int m) {
+        for (int q = 0; q < m; ++q) if (r0 + q < cap_rows) e_out[r0 + q] = e[q];
+        r0 += m;
+    };
+    double e[3], J1[9];
+    p->prior_factor(poses, e);
+    for (int a = 0; a < 3; ++a) put(r0 + a, a, p->w_prior[a]);
+    put_e(e, 3);
+    for (int i = 0; i < n; ++i) {
+        if (i + 1 < n) {
+            p->between_factor(poses + 3 * i, poses + 3 * (i + 1), p->cmds[2 * i], p->cmds[2 * i + 1], e, J1);
+            for (int a = 0; a < 3; ++a) {
+                for (int b = 0; b < 3; ++b) put(r0 + a, 3 * i + b, J1[3 * a + b]);
+                put(r0 + a, 3 * (i + 1) + a, p->w_btw[a]);
+            }
+            put_e(e, 3);
+        }
+        for (int s = 0; s < p->cnt[i]; ++s) {
+            const size_t kk = (size_t)i * p->KP + s;
+            const int j = p->mlm[kk];
+            double Jp[6], Jl[4];
+            p->bearing_range_factor(poses + 3 * i, lms + 2 * j, p->mb[kk], p->mr[kk], e, Jp, Jl);
+            for (int a = 0; a < 2; ++a) {
+                for (int b = 0; b < 3; ++b) put(r0 + a, 3 * i + b, Jp[3 * a + b]);
+                for (int b = 0; b < 2; ++b) put(r0 + a, 3 * n + 2 * j + b, Jl[2 * a + b]);
+            }
+            put_e(e, 2);
+        }
+    }
+    if (nnz) *nnz = k;
+    return r0;
+}
+// One damped step at given values: linearize there, solve (J^T J + lam I) delta = -J^T e with the elimination of lin_mode (LIN_SCHUR,
+// LIN_DENSE, LIN_SEG | SL << 8).  dp [N][3], dl [max(M, 1)][2].  Returns 1 if the factorisation succeeded.
+int orc_pgs_step(void* h, const double* poses, const double* lms, double lam, int lin_mode, double* dp_out, double* dl_out) {
+    Pgs* p = (Pgs*)h;
+    Pgs::Lin L;
+    p->linearize(poses, lms, L);
+    std::vector<double> dp, dl;
+    const int lmode = lin_mode & 0xff, seg_len = (lin_mode >> 8) > 0 ? (lin_mode >> 8) : 32;
+    const bool ok = lmode == LIN_DENSE ? p->solve_dense(L, lam, dp, dl)
+                    : (lmode == LIN_SEG ? p->solve_seg(L, lam, seg_len, dp, dl) : p->solve_schur(L, lam, dp, dl));
+    if (!ok) return 0;
+    memcpy(dp_out, dp.data(), sizeof(double) * 3 * p->N());
+    memcpy(dl_out, dl.data(), sizeof(double) * 2 * p->M);
+    return 1;
+}
 
 // ---- batch runner: simulator (get_cmd) + NaiveFilter secondary (filter.h:342-348) + graph building + ONE solve at the
 // end (solve_graph_every_iteration = false) for instances inst0..inst0+B-1; T commands => T+1 poses.

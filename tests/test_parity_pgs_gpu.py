@@ -577,3 +577,57 @@ def test_segmented_elimination_on_graphs_that_drop_detections(monkeypatch, oracl
     assert pg.last_solve_paths()["segmented"]
     _compare(pg, r, B)
     pg.close()
+
+
+def test_the_trial_cap_is_the_same_in_every_schedule(monkeypatch):
+    """SLAM_PGS_MAX_TRIALS = K: every graph consumes at most K lambda trials in every schedule - lockstep with and without lambda lanes,
+    streaming, the lockstep tail after streaming - and one that reaches K unconverged ends NOT_CONVERGED with the values of its last
+    accepted trial (lockstep capped the host's launches, each of which may consume up to 4 trials through the lanes; the
+    tail after streaming got K more launches).  For K = 1, 2, 3 and a K that binds for part of the batch: stats and results bit-identical
+    across slots {0, 2, 7} x SLAM_PGS_LANES {1, 4} x groups {1, 2}; trials <= K; graphs that finish within K trials equal the uncapped solve."""
+    import live_ekf_slam_amd as S
+    # the batch of the round-4 soak (test_the_ill_conditioned_instance_of_the_round_4_soak): 4 - 46 trials, most graphs with rejected ones
+    L, T, KP, B, seed, sc = 40, 846, 32, 11, 1058182634, 1043562854
+    lm, cmds = make_scenario(sc, L, T)
+    cfg = default_config()
+
+    def run(slots, lanes, groups):
+        monkeypatch.setenv("SLAM_PGS_LANES", str(lanes))
+        pg = S.BatchedPoseGraph(B, num_iterations=T + 1, L_max=L, k_per_pose=KP).readParams(cfg)
+        pg.set_groups(groups); pg.set_slots(slots)
+        pg.set_map(lm); pg.set_seed(seed); pg.init(0.0, 0.0, 0.0)
+        pg.run_sim(cmds); pg.solvePoseGraph()
+        out = [pg.get_graph(b, 1) for b in range(B)], pg.stats()
+        pg.close()
+        return out
+
+    monkeypatch.delenv("SLAM_PGS_MAX_TRIALS", raising=False)
+    free_g, free_st = run(0, 4, 1)
+    tr = free_st["trials"]
+    assert np.all((free_st["flags"] & 8) == 0) and np.any(tr > free_st["iterations"]), tr      # the premise: rejected trials, different counts
+    k_part = int(np.median(tr))
+    assert np.any(tr > k_part) and np.any(tr <= k_part), tr
+    for K in sorted({1, 2, 3, k_part}):
+        monkeypatch.setenv("SLAM_PGS_MAX_TRIALS", str(K))
+        ref = None
+        for slots in (0, 2, 7):
+            for lanes in (1, 4):
+                for groups in (1, 2):
+                    graphs, st = run(slots, lanes, groups)
+                    tag = (K, slots, lanes, groups)
+                    assert np.all(st["trials"] <= K), (tag, st["trials"])
+                    if ref is None:
+                        ref = graphs, st
+                        under = tr <= K
+                        assert np.all(st["trials"][~under] == K) and np.all(st["flags"][~under] & 8), (tag, st["trials"], st["flags"])
+                        for b in np.flatnonzero(under):   # finished within the cap: the uncapped solve, bit for bit
+                            assert np.array_equal(graphs[b]["poses"], free_g[b]["poses"]), (tag, b)
+                            assert np.array_equal(graphs[b]["landmarks"], free_g[b]["landmarks"]), (tag, b)
+                            for key in ("iterations", "trials", "flags", "err_final", "lam"):
+                                assert st[key][b] == free_st[key][b], (tag, b, key)
+                        continue
+                    for key in ("iterations", "trials", "flags", "err_final", "lam"):
+                        assert np.array_equal(st[key], ref[1][key]), (tag, key, st[key], ref[1][key])
+                    for b in range(B):
+                        assert np.array_equal(graphs[b]["poses"], ref[0][b]["poses"]), (tag, b)
+                        assert np.array_equal(graphs[b]["landmarks"], ref[0][b]["landmarks"]), (tag, b)
