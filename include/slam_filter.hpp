@@ -392,6 +392,34 @@ public:
         if (instance == 0) lm_IDs.assign(ids.begin(), ids.begin() + s.M);
         return s;
     }
+    // gtsam::Marginals marginals(graph, values) (pose_graph.cpp:289): which = 0 initial_estimate, 1 result.  Any update / solve invalidates it.
+    void marginals(int which = 1) { need(); check(pgs_marginals(h_, which)); }
+    // marginals.marginalCovariance(key(pose)) (pose_graph.cpp:292): 3x3 row-major, tangent coordinates of the pose (slam_pgs.h).
+    // Throws for a singular graph (GTSAM: IndeterminantLinearSystemException) and before marginals().
+    std::array<double, 9> marginalCovariance(int instance, int pose) {
+        need();
+        if (pose < 0 || pose > timestep) throw std::out_of_range("marginalCovariance: pose out of range");
+        std::vector<double> pc((size_t)9 * (timestep + 1));
+        int32_t st = 0;
+        check(pgs_get_marginals(h_, instance, pc.data(), nullptr, &st));
+        if (st != 0) throw std::runtime_error("marginalCovariance: the graph of this instance is singular (indeterminate linear system)");
+        std::array<double, 9> out;
+        for (int k = 0; k < 9; ++k) out[k] = pc[(size_t)9 * pose + k];
+        return out;
+    }
+    // ... of landmark j (index in lm_IDs order): 2x2 row-major, world coordinates
+    std::array<double, 4> landmarkCovariance(int instance, int j) {
+        need();
+        int32_t M = 0, ts = 0, st = 0;
+        check(pgs_get_graph(h_, instance, 0, nullptr, nullptr, &ts, &M, nullptr));
+        if (j < 0 || j >= M) throw std::out_of_range("landmarkCovariance: landmark out of range");
+        std::vector<double> lc((size_t)4 * L_max_);
+        check(pgs_get_marginals(h_, instance, nullptr, lc.data(), &st));
+        if (st != 0) throw std::runtime_error("landmarkCovariance: the graph of this instance is singular (indeterminate linear system)");
+        std::array<double, 4> out;
+        for (int k = 0; k < 4; ++k) out[k] = lc[(size_t)4 * j + k];
+        return out;
+    }
     pgs_handle* handle() { return h_; }
     PoseGraphState last_state;
 

@@ -7,6 +7,9 @@
  * measurements and in the secondary filter's estimates.  Same conventions as slam_batch.h: plain pointers and sizes,
  * int status codes (slam_status_code), text in slam_last_error(), one caller thread per handle, kernels on one stream.
  *
+ * Covered beyond the solve: `gtsam::Marginals marginals(graph, result); marginals.marginalCovariance(i)` (pose_graph.cpp:289-294) as
+ * pgs_marginals / pgs_get_marginals, for every pose and landmark (the reference's printout of them is not reproduced).
+ *
  * Not covered: `implementation: sesync | custom` (the reference itself throws for both, pose_graph.cpp:34-38),
  * unknown landmark ids (the reference throws, pose_graph.cpp:137), `update_landmarks_after_adding` (false in
  * params.yaml:63 and forced false when solving every iteration, pose_graph.cpp:45-48).
@@ -136,6 +139,30 @@ int pgs_last_solve_kernel_ms(pgs_handle* h, double ms[6]);
 int pgs_last_solve_paths_v2(pgs_handle* h, double* out, int n /* entries of out, <= 8 */);
 /* The first four entries only (the ABI of rounds 1-4; ADVICE r05: a caller with `double out[4]` must stay valid). */
 int pgs_last_solve_paths(pgs_handle* h, double out[4]);
+
+/* gtsam::Marginals(graph, values).marginalCovariance(key) for every pose and landmark of every instance (pose_graph.cpp:289-294), at the
+ * values `which` (0 = initial_estimate, 1 = result; 1 needs a pgs_solve since pgs_init): with J the whitened Jacobian of all factors at
+ * those values (no damping) and H = J^T J, the 3x3 diagonal block of H^-1 of every pose and the 2x2 block of every landmark.
+ * Pose blocks are in the tangent coordinates of the Pose2 chart the solver uses (GTSAM's Pose2 retract: translation in the pose's OWN
+ * frame, then yaw).  With R = [cos yaw, -sin yaw; sin yaw, cos yaw] of that pose, the world-frame x / y covariance is
+ * R * pose_cov[0:2, 0:2] * R^T.  Landmark blocks are in world coordinates.  Every block is exactly symmetric.
+ * Singular graphs: an instance whose H is not positive definite - a landmark that was created but has no stored factor (its detections
+ * fell to PGS_INST_MEAS_CAP; GTSAM throws IndeterminantLinearSystemException there), or a non-positive / non-finite pivot anywhere -
+ * gets status 1 and NaN in all of its blocks; no other instance is affected and pgs_get_stats' flags are not touched.
+ * The call is synchronous.  Its results belong to the values they were computed at: pgs_init, pgs_update*, pgs_run_sim*, pgs_solve and
+ * pgs_adopt_result invalidate them.  The outputs are allocated by the first call; the factorisation runs in the LM work space the
+ * handle already has (results, pgs_get_graph and pgs_get_stats of earlier and later solves are bit for bit what they are without the
+ * call).  SLAM_PGS_MARG_CHUNK = n runs the batch in launches of n instances (results do not depend on it). */
+int pgs_marginals(pgs_handle* h, int which);
+/* One instance's blocks: pose_cov [timestep+1][9], lm_cov [M][4] row-major, *status 0 ok / 1 singular; any pointer may be NULL.
+ * SLAM_ERR_STATE before a valid pgs_marginals. */
+int pgs_get_marginals(pgs_handle* h, int instance, double* pose_cov, double* lm_cov, int32_t* status);
+/* The device buffers ([batch][N_max][9], [batch][L_max][4], [batch]) for a consumer on the GPU; valid until the next pgs_marginals. */
+int pgs_marginals_dev(pgs_handle* h, const double** d_pose_cov, const double** d_lm_cov, const int32_t** d_status);
+/* Algorithmic FLOP of the last pgs_marginals summed over instances and its HIP-event milliseconds.  Model per instance, N poses,
+ * n = 2 M: 3N n^2 (triangular product, counted dense) + 12 * 3N n (chain recurrence + Gram) + 2 n^3 / 3 (R^-1 and its Gram)
+ * + 3N n^2 + n^3 / 3 (the lambda = 0 factorisation: Schur complement and Cholesky). */
+int pgs_last_marginals_work(pgs_handle* h, double* flop, double* ms);
 int pgs_sync(pgs_handle* h);
 int pgs_timestep(const pgs_handle* h);
 

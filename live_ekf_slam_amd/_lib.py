@@ -103,6 +103,10 @@ SIGNATURES = {
     "pgs_run_sim_every_iteration": (C.c_int, [_H, _fp, C.c_int, _ip]),
     "pgs_last_iter_phases": (C.c_int, [_H, _dp]),
     "pgs_last_solve_timeline": (C.c_int, [_H, C.c_int, _ip, C.c_int, _ip, _ip]),
+    "pgs_marginals": (C.c_int, [_H, C.c_int]),
+    "pgs_get_marginals": (C.c_int, [_H, C.c_int, _dp, _dp, _ip]),
+    "pgs_marginals_dev": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "pgs_last_marginals_work": (C.c_int, [_H, _dp, _dp]),
     "pgs_sync": (C.c_int, [_H]),
     "pgs_timestep": (C.c_int, [_H]),
     # include/slam_multi.h

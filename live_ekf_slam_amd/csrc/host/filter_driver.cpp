@@ -163,7 +163,9 @@ static int run_multi(const std::string& kind, int64_t B, int L, int T, int gpus,
 
 // `filter: "pose_graph"` (params.yaml:11): the node runs a secondary filter first and hands its estimate to the pose
 // graph every tick (localization_node.cpp:124-131); the pose graph solves when timestep+1 >= num_iterations.
-static int run_pose_graph(int B, int L, int T) {
+// With a dump path: marginals(1) after the solve, then the file gets, for the first and the last instance, int64 {poses, M} and the
+// doubles of the result (poses x 3, M x 2), of every marginalCovariance (9 each) and of every landmarkCovariance (4 each).
+static int run_pose_graph(int B, int L, int T, const char* marg_dump = nullptr) {
     LocalizationNode node;
     node.filter = std::make_unique<BatchedPoseGraph>(B, /*num_iterations=*/T, L);       // localization_node.cpp:45-46
     node.filter_secondary = std::make_unique<NaiveFilter>();                              // :68-69
@@ -183,6 +185,24 @@ static int run_pose_graph(int B, int L, int T) {
     std::printf("driver ok: pose_graph batch=%d poses=%d solved=%d M0=%d result_topic=%d x_len=%zu conns=%zu\n", B, pg->timestep + 1,
                 (int)pg->solved_pose_graph, pg->last_state.M, (int)pg->last_state.is_result, pg->last_state.x_v.size(),
                 pg->last_state.meas_connections.size() / 2);
+    if (marg_dump) {
+        pg->marginals(1);
+        FILE* f = std::fopen(marg_dump, "wb");
+        if (!f) throw std::runtime_error(std::string("cannot write ") + marg_dump);
+        for (int inst : {0, B - 1}) {
+            const PoseGraphState s = pg->stateMsg(inst);
+            const int64_t hd[2] = {pg->timestep + 1, s.M};
+            std::fwrite(hd, sizeof(int64_t), 2, f);
+            std::vector<double> poses((size_t)3 * (pg->timestep + 1)), lms((size_t)2 * L);
+            check(pgs_get_graph(pg->handle(), inst, 1, poses.data(), lms.data(), nullptr, nullptr, nullptr));
+            std::fwrite(poses.data(), sizeof(double), poses.size(), f);
+            std::fwrite(lms.data(), sizeof(double), (size_t)2 * s.M, f);
+            for (int i = 0; i <= pg->timestep; ++i) { const auto c = pg->marginalCovariance(inst, i); std::fwrite(c.data(), sizeof(double), 9, f); }
+            for (int j = 0; j < s.M; ++j) { const auto c = pg->landmarkCovariance(inst, j); std::fwrite(c.data(), sizeof(double), 4, f); }
+        }
+        std::fclose(f);
+        std::printf("driver ok: pose_graph marginals dumped\n");
+    }
     return 0;
 }
 
@@ -197,11 +217,11 @@ int main(int argc, char** argv) {
                              argc > 8 ? atoi(argv[8]) : 0);
         if (mode == "stream" && argc >= 7) return run_stream(argv[2], atoi(argv[3]), atoi(argv[4]), argv[5], argv[6]);
         if (mode == "run" && argc >= 6) return run_scenario(argv[2], atoi(argv[3]), atoi(argv[4]), atoi(argv[5]), argc > 6 ? strtoull(argv[6], nullptr, 10) : 1234ull);
-        if (mode == "pose_graph" && argc >= 5) return run_pose_graph(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]));
+        if (mode == "pose_graph" && argc >= 5) return run_pose_graph(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), argc > 5 ? argv[5] : nullptr);
         std::fprintf(stderr, "usage: filter_driver stream <ekf|ukf|ukf_loc> <batch> <L_max> <stream.txt> <dump.bin>\n"
                              "       filter_driver run <ekf|ukf> <batch> <L> <steps> [seed]\n"
                              "       filter_driver run_multi <ekf|ukf> <global batch> <L> <steps> <gpus> [seed] [gather 0|1]\n"
-                             "       filter_driver pose_graph <batch> <L> <steps>\n");
+                             "       filter_driver pose_graph <batch> <L> <steps> [marginals dump.bin]\n");
         return 2;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "driver failed: %s\n", e.what());

@@ -22,6 +22,7 @@ struct pgs_handle {
     int B, N_max, L_max, KP, LD, device;
     int timestep = 0;
     bool inited = false;
+    bool solved = false;                       // a pgs_solve has run since pgs_init: `result` exists
     hipStream_t stream = nullptr;
     bool own_stream = false;
     uint64_t seed = 2025;
@@ -81,6 +82,13 @@ struct pgs_handle {
     std::vector<hipEvent_t> events;
     std::vector<int> trial_fused;             // profiled solve: the fused choice (0 | 2 | 3 | 4) of every trial
     double kernel_ms[slam::kPgsTrialKernels] = {0, 0, 0, 0, 0, 0};
+    // marginal covariances (pgs_marginals): the outputs, and the per-instance flags / lambda = 0 the trial kernels read in place of the
+    // solve's own (nothing pgs_get_stats returns is touched).  Allocated by the first call.  mg_valid: they belong to the current values.
+    DevBuf<double> mg_pose, mg_lm, mg_flop, mg_lambda;   // [B][N_max][9], [B][L_max][4], [B], [B]
+    DevBuf<int32_t> mg_status, mg_state;                 // [B], [3][B]: state | lin_ok | solve_ok
+    hipEvent_t mg_ev[2] = {nullptr, nullptr};
+    bool mg_valid = false;
+    double mg_ms = 0.0;
 };
 
 namespace {
@@ -269,6 +277,7 @@ int pgs_destroy(pgs_handle* h) {
     for (hipEvent_t e : h->events) hipEventDestroy(e);
     for (hipEvent_t e : h->gevents) hipEventDestroy(e);
     for (hipEvent_t e : h->ring_events) hipEventDestroy(e);
+    for (hipEvent_t e : h->mg_ev) if (e) hipEventDestroy(e);
     for (hipStream_t st : h->gstreams) hipStreamDestroy(st);
     if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
     delete h;   // the device and pinned buffers
@@ -297,11 +306,12 @@ int pgs_set_map(pgs_handle* h, const double* map_xy, int L) {
 
 int pgs_init(pgs_handle* h, float x0, float y0, float yaw0) {
     TRY(check(h));
+    h->mg_valid = false;
     h->timestep = 0; h->p.N = 1;
     h->seg_cur = h->seg_len;
     h->p.prior[0] = x0; h->p.prior[1] = y0; h->p.prior[2] = yaw0;
     HIP_TRY(slam::pgs_launch_init(h->p, x0, y0, yaw0, h->stream));
-    h->inited = true;
+    h->inited = true; h->solved = false;
     return SLAM_OK;
 }
 
@@ -310,6 +320,7 @@ int pgs_update_dev(pgs_handle* h, const float cmd[2], const float* d_meas, const
     if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_update");
     if (!cmd) return fail(SLAM_ERR_ARG, "cmd is NULL");
     if (h->timestep + 1 >= h->N_max) return fail(SLAM_ERR_STATE, "pose capacity N_max = %d reached", h->N_max);
+    h->mg_valid = false;
     HIP_TRY(hipMemcpyAsync(h->dcmds + 2 * (size_t)h->timestep, cmd, sizeof(float) * 2, hipMemcpyHostToDevice, h->stream));
     h->p.N = h->timestep + 1;
     HIP_TRY(slam::pgs_launch_append(h->p, d_meas, d_count, k_stride, d_sec, h->stream));
@@ -342,6 +353,7 @@ int pgs_run_sim(pgs_handle* h, const float* cmds, int T) {
     if (!h->p.map) return fail(SLAM_ERR_STATE, "pgs_set_map must be called before pgs_run_sim");
     if (!cmds || T <= 0) return fail(SLAM_ERR_ARG, "bad command sequence");
     if (h->timestep + T >= h->N_max) return fail(SLAM_ERR_STATE, "timestep %d + %d commands exceed the pose capacity N_max = %d", h->timestep, T, h->N_max);
+    h->mg_valid = false;
     HIP_TRY(hipMemcpyAsync(h->dcmds + 2 * (size_t)h->timestep, cmds, sizeof(float) * 2 * (size_t)T, hipMemcpyHostToDevice, h->stream));
     h->p.N = h->timestep + 1;
     HIP_TRY(slam::pgs_launch_run_sim(h->p, T, (uint32_t)h->timestep, h->stream));
@@ -445,6 +457,7 @@ int launch_trial(pgs_handle* h, slam::PgsParams& p, int32_t active_hint, int lan
 int pgs_solve(pgs_handle* h) {
     TRY(check(h));
     if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_solve");
+    h->mg_valid = false; h->solved = true;
     h->p.N = h->timestep + 1;
     h->p.b_off = 0; h->p.b_cnt = h->B;
     {   // Segmented elimination of the pose chain (pgs_seg_impl.h): the plan kernel lists the landmarks every segment's interior poses
@@ -702,6 +715,7 @@ int pgs_set_groups(pgs_handle* h, int groups) { TRY(check(h)); h->groups = group
 
 int pgs_adopt_result(pgs_handle* h) {
     TRY(check(h));
+    h->mg_valid = false;
     HIP_TRY(slam::pgs_launch_adopt(h->p, h->stream));
     return SLAM_OK;
 }
@@ -714,6 +728,7 @@ int pgs_run_sim_every_iteration(pgs_handle* h, const float* cmds, int T, int32_t
     if (!h->p.map) return fail(SLAM_ERR_STATE, "pgs_set_map must be called before pgs_run_sim_every_iteration");
     if (!cmds || T <= 0) return fail(SLAM_ERR_ARG, "bad command sequence");
     if (h->timestep + T >= h->N_max) return fail(SLAM_ERR_STATE, "timestep %d + %d commands exceed the pose capacity N_max = %d", h->timestep, T, h->N_max);
+    h->mg_valid = false;
     HIP_TRY(hipMemcpyAsync(h->dcmds + 2 * (size_t)h->timestep, cmds, sizeof(float) * 2 * (size_t)T, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));   // cmds is a pageable host array
     HIP_TRY(h->d_tick.reserve((size_t)h->B * 2));
@@ -881,6 +896,95 @@ int pgs_debug_prof2(pgs_handle* h, unsigned long long* out) {
     HIP_TRY(hipMemcpy(out, h->p.prof + (size_t)h->B * h->lanes * 8, sizeof(unsigned long long) * 16 * (size_t)h->B, hipMemcpyDeviceToHost));
     return SLAM_OK;
 }
+
+// Marginal covariances of every pose and landmark of every instance at initial_estimate (which = 0) / result (1): the diagonal blocks of
+// (J^T J)^-1 (pgs_marginals.h).  The factorisation runs in the instances' own LM work space (slot b of instance b; a later solve starts
+// from pgs_lm_begin_kernel and reads none of it); the outputs and the flags the trial kernels see are this call's own arrays.
+// SLAM_PGS_MARG_CHUNK = n: the batch in launches of n instances (results do not depend on it).
+int pgs_marginals(pgs_handle* h, int which) {
+    TRY(check(h));
+    if (which != 0 && which != 1) return fail(SLAM_ERR_ARG, "which = %d (0: initial_estimate, 1: result)", which);
+    if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_marginals");
+    if (which == 1 && !h->solved) return fail(SLAM_ERR_STATE, "pgs_marginals(which = 1): no result yet (pgs_solve has not run since pgs_init)");
+    h->mg_valid = false;
+    const size_t B = (size_t)h->B;
+    if (!h->mg_pose) {   // first call: everything or nothing (each owner is filled only once all allocations succeeded)
+        DevBuf<double> a, b, c, d;
+        DevBuf<int32_t> e, f;
+        const size_t need = sizeof(double) * B * ((size_t)h->N_max * 9 + (size_t)h->L_max * 4 + 2) + sizeof(int32_t) * B * 4;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b)
+            return fail(SLAM_ERR_HIP, "pgs_marginals: %zu bytes of output buffers exceed the %zu bytes of free device memory", need, free_b);
+        if (a.reserve(B * (size_t)h->N_max * 9) != hipSuccess || b.reserve(B * (size_t)h->L_max * 4) != hipSuccess || c.reserve(B) != hipSuccess ||
+            d.reserve(B) != hipSuccess || e.reserve(B) != hipSuccess || f.reserve(3 * B) != hipSuccess)
+            return fail(SLAM_ERR_HIP, "pgs_marginals: out of device memory for the output buffers (%zu bytes)", need);
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+            if (e0) hipEventDestroy(e0);
+            (void)hipGetLastError();
+            return fail(SLAM_ERR_HIP, "pgs_marginals: hipEventCreate failed");
+        }
+        h->mg_pose = std::move(a); h->mg_lm = std::move(b); h->mg_flop = std::move(c); h->mg_lambda = std::move(d);
+        h->mg_status = std::move(e); h->mg_state = std::move(f);
+        h->mg_ev[0] = e0; h->mg_ev[1] = e1;
+    }
+    int chunk = h->B;
+    if (const char* e = getenv("SLAM_PGS_MARG_CHUNK")) { const int v = atoi(e); if (v > 0 && v < chunk) chunk = v; }
+    slam::PgsParams q = h->p;
+    q.N = h->timestep + 1;
+    q.state = h->mg_state; q.lin_ok = h->mg_state + B; q.solve_ok = h->mg_state + 2 * B; q.lambda = h->mg_lambda;
+    q.nfact_max = q.N * h->KP;   // an upper bound: the per-factor kernel returns beyond the instance's own count
+    HIP_TRY(hipEventRecord(h->mg_ev[0], h->stream));
+    for (int b0 = 0; b0 < h->B; b0 += chunk) {
+        q.b_off = b0; q.b_cnt = h->B - b0 < chunk ? h->B - b0 : chunk;
+        HIP_TRY(slam::pgs_launch_marginals(q, which, h->mg_pose, h->mg_lm, h->mg_status, h->mg_flop, h->stream));
+    }
+    HIP_TRY(hipEventRecord(h->mg_ev[1], h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, h->mg_ev[0], h->mg_ev[1]));
+    h->mg_ms = ms;
+    h->mg_valid = true;
+    return SLAM_OK;
+}
+
+int pgs_get_marginals(pgs_handle* h, int inst, double* pose_cov, double* lm_cov, int32_t* status) {
+    TRY(check(h));
+    if (inst < 0 || inst >= h->B) return fail(SLAM_ERR_ARG, "instance %d out of range", inst);
+    if (!h->mg_valid) return fail(SLAM_ERR_STATE, "no marginals for the current values: call pgs_marginals after the last update / solve");
+    int32_t m = 0;
+    HIP_TRY(hipMemcpy(&m, h->p.M + inst, sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (pose_cov) HIP_TRY(hipMemcpy(pose_cov, h->mg_pose + (size_t)inst * h->N_max * 9, sizeof(double) * 9 * (size_t)(h->timestep + 1), hipMemcpyDeviceToHost));
+    if (lm_cov && m > 0) HIP_TRY(hipMemcpy(lm_cov, h->mg_lm + (size_t)inst * h->L_max * 4, sizeof(double) * 4 * (size_t)m, hipMemcpyDeviceToHost));
+    if (status) HIP_TRY(hipMemcpy(status, h->mg_status + inst, sizeof(int32_t), hipMemcpyDeviceToHost));
+    return SLAM_OK;
+}
+
+int pgs_marginals_dev(pgs_handle* h, const double** d_pose_cov, const double** d_lm_cov, const int32_t** d_status) {
+    TRY(check(h));
+    if (!h->mg_valid) return fail(SLAM_ERR_STATE, "no marginals for the current values: call pgs_marginals after the last update / solve");
+    if (d_pose_cov) *d_pose_cov = h->mg_pose;
+    if (d_lm_cov) *d_lm_cov = h->mg_lm;
+    if (d_status) *d_status = h->mg_status;
+    return SLAM_OK;
+}
+
+// FLOP model per instance (pgs_marg_begin_kernel), N = poses, n = 2 M: 3N n^2 (Z = V X, counted dense) + 3N n 12 (recurrence + Gram)
+// + 2 n^3 / 3 (R^-1 and its Gram) + 3N n^2 + n^3 / 3 (the lambda = 0 factorisation: Schur complement and Cholesky).
+int pgs_last_marginals_work(pgs_handle* h, double* flop, double* ms) {
+    TRY(check(h));
+    if (!h->mg_valid) return fail(SLAM_ERR_STATE, "no marginals for the current values: call pgs_marginals after the last update / solve");
+    if (flop) {
+        std::vector<double> f((size_t)h->B);
+        HIP_TRY(hipMemcpy(f.data(), h->mg_flop, sizeof(double) * f.size(), hipMemcpyDeviceToHost));
+        double tot = 0.0;
+        for (double v : f) tot += v;
+        *flop = tot;
+    }
+    if (ms) *ms = h->mg_ms;
+    return SLAM_OK;
+}
+
 int pgs_sync(pgs_handle* h) { TRY(check(h)); HIP_TRY(hipStreamSynchronize(h->stream)); return SLAM_OK; }
 int pgs_timestep(const pgs_handle* h) { return h ? h->timestep : -1; }
 

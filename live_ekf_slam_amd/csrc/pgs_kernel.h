@@ -163,5 +163,11 @@ hipError_t pgs_launch_lm_end(const PgsParams& p, hipStream_t s);     // result =
 hipError_t pgs_launch_adopt(const PgsParams& p, hipStream_t s);      // initial_estimate = result
 // avg position error (plotting_node.py:203-213 alignment) of initial (which = 0) / result (1) vs truth_hist: out [B]
 hipError_t pgs_launch_avg_error(const PgsParams& p, int which, double* out, hipStream_t s);
+// Marginal covariances (pgs_marginals.h) of the instances [p.b_off, p.b_off + p.b_cnt) at initial_estimate (which = 0) / result (1):
+// one linearisation at lambda = 0, the sequential chain, the tile SYRK and the dense Cholesky through the trial kernels into the
+// instances' own LM work space, then X = R^-T, V = L_p^-T Y and the blocks.  p.state / lin_ok / solve_ok / lambda must point at
+// arrays of the CALLER ([B] each; the solve's own are not touched), p.nfact_max at an upper bound of the factors of an instance.
+// pose_cov [B][N_max][9], lm_cov [B][L_max][4], status [B] (0 ok, 1 singular: its blocks are NaN), flop [B] (the model, pgs_marginals.h).
+hipError_t pgs_launch_marginals(const PgsParams& p, int which, double* pose_cov, double* lm_cov, int32_t* status, double* flop, hipStream_t s);
 
 }  // namespace slam

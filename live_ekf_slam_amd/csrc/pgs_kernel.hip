@@ -40,6 +40,7 @@ namespace {
 #include "pgs_backsolve.h"
 #include "pgs_lm_control.h"
 #include "pgs_seg_impl.h"
+#include "pgs_marginals.h"
 
 }  // namespace
 
@@ -164,6 +165,21 @@ hipError_t pgs_launch_adopt(const PgsParams& p, hipStream_t s) {
 
 hipError_t pgs_launch_avg_error(const PgsParams& p, int which, double* out, hipStream_t s) {
     hipLaunchKernelGGL(pgs_avg_error_kernel, dim3(p.B), dim3(TPB), 0, s, p, which, out);
+    return hipGetLastError();
+}
+
+hipError_t pgs_launch_marginals(const PgsParams& p, int which, double* pose_cov, double* lm_cov, int32_t* status, double* flop, hipStream_t s) {
+    if (p.b_cnt <= 0) return hipSuccess;
+    PgsParams q = p;   // the sequential elimination order, two-launch path, every instance of the range in grid order
+    q.seg_on = 0; q.fused = 0; q.syrk_wave_tile = 32; q.use_list = 0; q.lanes = 1; q.n_list_dev = nullptr; q.slots_cap = 0;
+    q.syrk_row0 = 0; q.syrk_rows = -1; q.syrk_first = nullptr; q.prof = nullptr;
+    hipLaunchKernelGGL(pgs_marg_begin_kernel, dim3(q.b_cnt), dim3(TPB), 0, s, q, which, flop);
+    for (int k = 0; k < 4; ++k)
+        if (const hipError_t e = pgs_launch_trial_kernel(q, k, s); e != hipSuccess) return e;
+    hipLaunchKernelGGL(pgs_marg_inv_kernel, dim3(q.b_cnt), dim3(MI_TPB), 0, s, q, lm_cov, status);
+    hipLaunchKernelGGL(pgs_marg_back_kernel, dim3(q.b_cnt), dim3(64 + q.LD), 0, s, q, pose_cov);
+    const int ntile = (q.N + 15) / 16;
+    hipLaunchKernelGGL(pgs_marg_gram_kernel, dim3(q.b_cnt * ntile), dim3(MG_TPB), 0, s, q, pose_cov, ntile);
     return hipGetLastError();
 }
 

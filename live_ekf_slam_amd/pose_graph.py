@@ -250,6 +250,41 @@ class BatchedPoseGraph:
         _lib.check(_lib.lib().pgs_get_stats(self.h, _i(it), _i(tr), _i(fl), _d(e0), _d(e1), _d(lam)))
         return dict(iterations=it, trials=tr, flags=fl, err_init=e0, err_final=e1, lam=lam)
 
+    # -- gtsam::Marginals(graph, values).marginalCovariance(key) (pose_graph.cpp:289-294) --
+    def marginals(self, which=None):
+        """Marginal covariances of every pose and landmark of every instance at initial_estimate (which = 0) / result (1; default as
+        get_graph).  Read them with get_marginals / marginalCovariance; any update / solve / adopt_result invalidates them."""
+        self._need()
+        which = int(self.solved_pose_graph) if which is None else int(which)
+        _lib.check(_lib.lib().pgs_marginals(self.h, which))
+
+    def get_marginals(self, instance=0):
+        """dict(pose_cov [N][3][3], lm_cov [M][2][2], status): pose blocks in the tangent coordinates of the pose (translation in its
+        own frame, yaw), status 1 = singular graph (all blocks NaN)."""
+        self._need()
+        N = self.timestep + 1
+        pc = np.zeros((N, 3, 3)); lc = np.zeros((self.L_max, 2, 2)); st = C.c_int32(0)
+        _lib.check(_lib.lib().pgs_get_marginals(self.h, int(instance), _d(pc), _d(lc), C.byref(st)))
+        ts = C.c_int32(0); M = C.c_int32(0)
+        _lib.check(_lib.lib().pgs_get_graph(self.h, int(instance), 0, None, None, C.byref(ts), C.byref(M), None))
+        return dict(pose_cov=pc, lm_cov=lc[:M.value].copy(), status=st.value)
+
+    def marginalCovariance(self, instance, pose=None, landmark=None):
+        """marginals.marginalCovariance(key) of one pose (3x3) or one landmark (2x2, by index) of `instance`."""
+        if (pose is None) == (landmark is None):
+            raise ValueError("give exactly one of pose= and landmark=")
+        m = self.get_marginals(instance)
+        blocks, k = (m["pose_cov"], pose) if pose is not None else (m["lm_cov"], landmark)
+        if not 0 <= int(k) < blocks.shape[0]:
+            raise IndexError(f"{'pose' if pose is not None else 'landmark'} {k} out of range ({blocks.shape[0]})")
+        return blocks[int(k)].copy()
+
+    def last_marginals_work(self):
+        """(algorithmic FLOP of the last marginals() summed over the batch, its HIP-event milliseconds)."""
+        self._need(); f = C.c_double(0); ms = C.c_double(0)
+        _lib.check(_lib.lib().pgs_last_marginals_work(self.h, C.byref(f), C.byref(ms)))
+        return f.value, ms.value
+
     def error_stats(self, which=1):
         self._need(); out = np.zeros(self.batch); _lib.check(_lib.lib().pgs_error_stats(self.h, int(which), _d(out))); return out
 
