@@ -248,6 +248,48 @@ int slam_get_last_meas(slam_handle* h, float* meas, int32_t* meas_count, int k_s
 int slam_error_stats(slam_handle* h, double* per_instance_avg_err);
 int slam_status(slam_handle* h, int32_t* per_instance_flags);       /* [batch] slam_instance_flags */
 
+/* ---- consistency: is the covariance believable? (Bar-Shalom's NEES test over a Monte-Carlo batch) -------------------------------------
+ * The reference has no counterpart (its plotter reports the position error only).  For every instance of an SLAM_EKF_SLAM handle, at
+ * the handle's current state and computed on the GPU (fp64 arithmetic, whatever the storage type), with n = 3 + 2 M,
+ * S = (P_t + P_t^T) / 2 and e = (x - x_true, y - y_true, remainder(yaw - yaw_true, 2 pi), and for landmark slot j:
+ * (x_t[3+2j], x_t[4+2j]) - map[ids[j]]):
+ *   nees_full [batch]  e^T S^-1 e (normalised estimation error squared; chi-square with n degrees of freedom for a consistent filter)
+ *   nees_pose [batch]  the same with the leading 3 x 3 block of S and the first three components of e (marginal of the vehicle pose)
+ *   map_rms   [batch]  sqrt(mean over the M landmark slots of the squared Euclidean landmark error); 0 when M = 0
+ *   dof       [batch]  n
+ *   flags     [batch]  slam_consistency_flags
+ * Any output pointer may be NULL.  Truth: the vehicle pose is the simulator's (slam_get_truth; its yaw is not wrapped), the landmark
+ * truth is row ids[j] of the true map (slam_set_map, or the instance's own map of slam_set_maps), ids[j] being the id stored with slot j
+ * at insertion.  That is the true landmark's index only with landmark_id_is_known = 1: with unknown ids the reference numbers its
+ * landmarks in order of insertion (ekf.cpp:84), so such a handle reports nees_pose and dof only (NO_TRUTH for every instance with M > 0).
+ * Meaningful only while the handle is stepped by the simulator (slam_step_sim, slam_run_sim and their _each forms): with host-fed
+ * measurements the handle's truth does not move, and the call does not try to detect that.
+ * The call runs the queued timesteps first, computes on the handle's stream, returns when the results are on the host, and CHANGES
+ * NOTHING: state, truth, error sums, counters and every later timestep are bit-identical to a run without it.  The value of an
+ * instance does not depend on the batch it sits in, on a second call or on the chunking below.
+ * L_max <= 50: the packed triangle of S is factored in LDS.  Beyond (up to 1000 landmarks): in a device workspace the handle owns,
+ * (n + 1)(n + 2) / 2 doubles per instance, at most SLAM_CONSISTENCY_WS_BYTES (environment variable read at the call, default 256 MiB;
+ * one instance at least) - the batch is then processed in chunks of as many instances as the workspace holds; slow by design.
+ * Errors: SLAM_ERR_STATE before slam_init or without a true map, SLAM_ERR_UNSUPPORTED for the UKF kinds.
+ * Not covered: the UKF kinds (their state carries (cos yaw, sin yaw), so P is rank-deficient along the unit circle by construction and
+ *   indefinite in most steps of the benchmark scenario: a NEES there needs a definition first), slam_multi_* gathers, the pose graph
+ *   (slam_pgs.h has pgs_marginals), accumulation of the NEES inside the step kernels, log-determinants or other information measures,
+ *   guessing a landmark association for unknown ids. */
+enum slam_consistency_flags {
+    SLAM_CONSISTENCY_OK = 0,
+    SLAM_CONSISTENCY_FULL_NOT_PD = 1,      /* a Cholesky pivot of S is <= 0 or not finite (exactly that test, no floor): nees_full = NaN, the rest
+                                              is still reported.  Without a landmark truth (NO_TRUTH) only the 3 x 3 block is factored */
+    SLAM_CONSISTENCY_POSE_NOT_PD = 2,      /* the same for one of the first three pivots: nees_pose = NaN as well */
+    SLAM_CONSISTENCY_NO_TRUTH = 4,         /* an ids[j] outside the instance's map, or unknown-id mode with M > 0: nees_full = map_rms = NaN */
+    SLAM_CONSISTENCY_INSTANCE_FAILED = 8   /* slam_status carries SLAM_INST_NONFINITE or SLAM_INST_WATCHDOG (the state is undefined), or e holds
+                                              a non-finite value: everything NaN but dof, no other bit.  The other status bits leave a valid
+                                              frozen or truncated state, whose numbers are reported like any other */
+};
+int slam_consistency(slam_handle* h, double* nees_full, double* nees_pose, double* map_rms, int32_t* dof, int32_t* flags);
+/* bytes the model says the last slam_consistency had to read (sum over instances of the factored rows of P, n x ld x element size,
+ * plus x, ids, the truth and the map rows) and its device time in ms (HIP events around its launches). */
+int slam_last_consistency_work(slam_handle* h, double* bytes, double* ms);
+
 /* ---- scenario generators (host side; sim_node.py:63-206) ------------------------------------------------------ */
 /* generate_landmarks + generate_full_trajectory of the reference simulator for one scenario seed (the reference seeds
  * CPython's Mersenne Twister; the same generator is implemented in include/slam_scenario.hpp, so a seed gives the reference's

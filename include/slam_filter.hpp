@@ -189,6 +189,16 @@ public:
         return s;
     }
     std::vector<double> errorStats() { need(); std::vector<double> e(batch_); check(slam_error_stats(h_, e.data())); return e; }
+    // NEES consistency statistics of every instance at the current state against the simulator's truth, computed on the GPU
+    // (slam_consistency, include/slam_batch.h: definitions, slam_consistency_flags, what it does not cover).  Changes nothing.
+    struct Consistency { std::vector<double> nees_full, nees_pose, map_rms; std::vector<int32_t> dof, flags; };
+    Consistency consistency() {
+        need();
+        Consistency c;
+        c.nees_full.resize(batch_); c.nees_pose.resize(batch_); c.map_rms.resize(batch_); c.dof.resize(batch_); c.flags.resize(batch_);
+        check(slam_consistency(h_, c.nees_full.data(), c.nees_pose.data(), c.map_rms.data(), c.dof.data(), c.flags.data()));
+        return c;
+    }
     slam_handle* handle() { return h_; }
     EKFState last_state;
 

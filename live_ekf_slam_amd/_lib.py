@@ -60,6 +60,8 @@ SIGNATURES = {
     "slam_get_last_meas": (C.c_int, [_H, _fp, _ip, C.c_int]),
     "slam_error_stats": (C.c_int, [_H, _dp]),
     "slam_status": (C.c_int, [_H, _ip]),
+    "slam_consistency": (C.c_int, [_H, _dp, _dp, _dp, _ip, _ip]),
+    "slam_last_consistency_work": (C.c_int, [_H, _dp, _dp]),
     "slam_sync": (C.c_int, [_H]),
     "slam_batch": (C.c_int, [_H]),
     "slam_state_dim_max": (C.c_int, [_H]),

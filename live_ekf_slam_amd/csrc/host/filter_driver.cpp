@@ -14,6 +14,9 @@
 //       contiguous shards, noise keyed by global instance id, no collective until the gather of the error statistics.
 //   filter_driver pose_graph <batch> <L> <steps>
 //       `filter: pose_graph` with the NaiveFilter secondary (localization_node.cpp:62-69,124-131) over the same harness.
+//   filter_driver consistency <batch> <L> <steps> <dump.bin> [seed]
+//       The EKF run of `run`, then BatchedEKF::consistency(): the file gets int64 batch, then nees_full, nees_pose, map_rms (doubles) and
+//       dof, flags (int32), batch values each.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -133,6 +136,33 @@ static int run_scenario(const std::string& kind, int B, int L, int T, uint64_t s
     return 0;
 }
 
+static int run_consistency(int B, int L, int T, const char* dump_path, uint64_t seed) {
+    const Scenario sc = make_scenario(seed, L, T);
+    BatchedEKF ekf(B, L);
+    slam_config cfg;
+    check(slam_config_default(&cfg));
+    ekf.readParams(cfg);
+    ekf.init(0.f, 0.f, 0.f);
+    ekf.setMap(sc.map_xy);
+    check(slam_run_sim(ekf.handle(), sc.cmds.data(), T));
+    const BatchedEKF::Consistency c = ekf.consistency();
+    FILE* f = std::fopen(dump_path, "wb");
+    if (!f) throw std::runtime_error(std::string("cannot write ") + dump_path);
+    const int64_t hd = B;
+    std::fwrite(&hd, sizeof(int64_t), 1, f);
+    std::fwrite(c.nees_full.data(), sizeof(double), (size_t)B, f);
+    std::fwrite(c.nees_pose.data(), sizeof(double), (size_t)B, f);
+    std::fwrite(c.map_rms.data(), sizeof(double), (size_t)B, f);
+    std::fwrite(c.dof.data(), sizeof(int32_t), (size_t)B, f);
+    std::fwrite(c.flags.data(), sizeof(int32_t), (size_t)B, f);
+    std::fclose(f);
+    int flagged = 0;
+    double sum = 0, dof = 0;
+    for (int b = 0; b < B; ++b) { flagged += c.flags[b] != 0; if (!c.flags[b]) { sum += c.nees_full[b]; dof += c.dof[b]; } }
+    std::printf("driver ok: consistency batch=%d L=%d steps=%d flagged=%d nees_per_dof=%.9g\n", B, L, T, flagged, dof > 0 ? sum / dof : 0.0);
+    return 0;
+}
+
 // the global batch over several GPUs of the node from this one process (SURVEY.md section 8(e) "Host")
 static int run_multi(const std::string& kind, int64_t B, int L, int T, int gpus, uint64_t seed, int gather_mode) {
     const Scenario sc = make_scenario(seed, L, T);
@@ -217,11 +247,14 @@ int main(int argc, char** argv) {
                              argc > 8 ? atoi(argv[8]) : 0);
         if (mode == "stream" && argc >= 7) return run_stream(argv[2], atoi(argv[3]), atoi(argv[4]), argv[5], argv[6]);
         if (mode == "run" && argc >= 6) return run_scenario(argv[2], atoi(argv[3]), atoi(argv[4]), atoi(argv[5]), argc > 6 ? strtoull(argv[6], nullptr, 10) : 1234ull);
+        if (mode == "consistency" && argc >= 6)
+            return run_consistency(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), argv[5], argc > 6 ? strtoull(argv[6], nullptr, 10) : 1234ull);
         if (mode == "pose_graph" && argc >= 5) return run_pose_graph(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), argc > 5 ? argv[5] : nullptr);
         std::fprintf(stderr, "usage: filter_driver stream <ekf|ukf|ukf_loc> <batch> <L_max> <stream.txt> <dump.bin>\n"
                              "       filter_driver run <ekf|ukf> <batch> <L> <steps> [seed]\n"
                              "       filter_driver run_multi <ekf|ukf> <global batch> <L> <steps> <gpus> [seed] [gather 0|1]\n"
-                             "       filter_driver pose_graph <batch> <L> <steps> [marginals dump.bin]\n");
+                             "       filter_driver pose_graph <batch> <L> <steps> [marginals dump.bin]\n"
+                             "       filter_driver consistency <batch> <L> <steps> <dump.bin> [seed]\n");
         return 2;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "driver failed: %s\n", e.what());

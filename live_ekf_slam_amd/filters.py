@@ -325,6 +325,27 @@ class BatchedFilter:
         return dict(name=name.value.decode(), lds_bytes=int(out[0]), vgprs=int(out[1]), threads=int(out[2]),
                     workgroups_per_cu=int(out[3]), cus=int(out[4]))
 
+    # -- no counterpart in the reference: is P believable?  (slam_consistency, include/slam_batch.h) --
+    FULL_NOT_PD, POSE_NOT_PD, NO_TRUTH, INSTANCE_FAILED = 1, 2, 4, 8   # slam_consistency_flags
+
+    def consistency(self):
+        """NEES of every instance at the current state against the simulator's truth, computed on the GPU: dict of [batch] arrays
+        nees_full (e^T S^-1 e, S = (P + P^T) / 2), nees_pose (vehicle marginal), map_rms, dof (3 + 2 M) and flags
+        (FULL_NOT_PD, POSE_NOT_PD, NO_TRUTH, INSTANCE_FAILED).  Changes nothing in the handle.  Meaningful while the handle is stepped
+        by the simulator (update_sim / run_sim) with a map set; consistency_summary() turns a batch into Bar-Shalom's test."""
+        self._need()
+        out = dict(nees_full=np.zeros(self.batch), nees_pose=np.zeros(self.batch), map_rms=np.zeros(self.batch),
+                   dof=np.zeros(self.batch, dtype=np.int32), flags=np.zeros(self.batch, dtype=np.int32))
+        _lib.check(_lib.lib().slam_consistency(self.h, _d(out["nees_full"]), _d(out["nees_pose"]), _d(out["map_rms"]), _i(out["dof"]),
+                                               _i(out["flags"])))
+        return out
+
+    def last_consistency_work(self):
+        """(bytes the model says the last consistency() had to read, its device time in ms)."""
+        self._need(); b = C.c_double(0); ms = C.c_double(0)
+        _lib.check(_lib.lib().slam_last_consistency_work(self.h, C.byref(b), C.byref(ms)))
+        return b.value, ms.value
+
     def set_lazy_steps(self, n):
         self._need(); _lib.check(_lib.lib().slam_set_lazy_steps(self.h, int(n)))
 
@@ -359,6 +380,53 @@ class BatchedEKF(BatchedFilter):
         lm[0::3] = s["ids"]; lm[1::3] = x[3::2]; lm[2::3] = x[4::2]
         return dict(timestep=s["timestep"], x_v=np.float32(x[0]), y_v=np.float32(x[1]), yaw_v=np.float32(x[2]),
                     M=M, landmarks=lm, P=s["P"].astype(np.float32).ravel())  # P row-major (ekf.cpp:211-217)
+
+
+def _normal_quantile(p):
+    """Inverse of the standard normal distribution function (Acklam's rational approximation, relative error < 1.2e-9)."""
+    import math
+    a = (-3.969683028665376e+01, 2.209460984245205e+02, -2.759285104469687e+02, 1.383577518672690e+02, -3.066479806614716e+01,
+         2.506628277459239e+00)
+    b = (-5.447609879822406e+01, 1.615858368580409e+02, -1.556989798598866e+02, 6.680131188771972e+01, -1.328068155288572e+01)
+    c = (-7.784894002430293e-03, -3.223964580411365e-01, -2.400758277161838e+00, -2.549732539343734e+00, 4.374664141464968e+00,
+         2.938163982698783e+00)
+    d = (7.784695709041462e-03, 3.224671290700398e-01, 2.445134137142996e+00, 3.754408661907416e+00)
+    if not 0.0 < p < 1.0:
+        raise ValueError("p must lie in (0, 1)")
+    if p < 0.02425:
+        q = math.sqrt(-2 * math.log(p))
+        return (((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) / ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1)
+    if p > 1 - 0.02425:
+        return -_normal_quantile(1 - p)
+    q = p - 0.5
+    r = q * q
+    return ((((((a[0] * r + a[1]) * r + a[2]) * r + a[3]) * r + a[4]) * r + a[5]) * q /
+            (((((b[0] * r + b[1]) * r + b[2]) * r + b[3]) * r + b[4]) * r + 1))
+
+
+def chi2_quantile(p, dof):
+    """Quantile of the chi-square distribution by the Wilson-Hilferty cube approximation: within 0.31 % of the exact value for
+    dof >= 30 and p in [0.005, 0.995] (0.036 % for dof >= 100; 6.5 % at dof 7, hence the refusal below 30).  scipy is not a
+    dependency of this package."""
+    if dof < 30:
+        raise ValueError(f"the Wilson-Hilferty approximation is refused below 30 degrees of freedom (got {dof})")
+    v = 2.0 / (9.0 * dof)
+    return dof * (1.0 - v + _normal_quantile(p) * v ** 0.5) ** 3
+
+
+def consistency_summary(nees, dof, flags, alpha=0.05):
+    """Bar-Shalom's consistency test over the instances without a flag: {count, left_out, normalised = sum nees / sum dof, lower,
+    upper}, the interval being the chi-square quantiles of sum dof at alpha / 2 and 1 - alpha / 2 divided by sum dof.  A consistent
+    filter has `normalised` inside [lower, upper] with probability 1 - alpha; far below means an over-cautious covariance, above an
+    over-confident one.  Pure numpy (no GPU); raises ValueError when sum dof < 30."""
+    nees, dof, flags = np.asarray(nees, dtype=np.float64), np.asarray(dof, dtype=np.int64), np.asarray(flags)
+    if not (nees.shape == dof.shape == flags.shape) or nees.ndim != 1:
+        raise ValueError("nees, dof and flags must be one-dimensional arrays of one length")
+    ok = flags == 0
+    total = int(dof[ok].sum())
+    lo, hi = chi2_quantile(alpha / 2, total), chi2_quantile(1 - alpha / 2, total)
+    return dict(count=int(ok.sum()), left_out=int((~ok).sum()), normalised=float(nees[ok].sum() / total), lower=lo / total,
+                upper=hi / total)
 
 
 class BatchedUKF(BatchedFilter):
