@@ -290,6 +290,69 @@ int slam_consistency(slam_handle* h, double* nees_full, double* nees_pose, doubl
  * plus x, ids, the truth and the map rows) and its device time in ms (HIP events around its launches). */
 int slam_last_consistency_work(slam_handle* h, double* bytes, double* ms);
 
+/* ---- closed loop: commands from each instance's own estimate (goal_pursuit_node.py:23-50, pure_pursuit.py:17-161) ---------------------
+ * The entry points above run open loop: every command is fixed before the run.  The reference's default launch (sim_base.launch,
+ * precompute_trajectory false) closes the loop instead: goal_pursuit_node computes each Command from the state the filter has just published.
+ * slam_nav_run does that on the device for every instance: one tick = {controller kernel, one SIM timestep with per-instance commands},
+ * both on the handle's stream, no host round trip.
+ * The controller is a restatement of PurePursuit.get_next_cmd / pare_path / choose_lookahead_pt / cmd_loose / cmd_tight (method SLAM_NAV_PP)
+ * and direct_nav (SLAM_NAV_DIRECT), defined once in csrc/nav_kernel.h and mirrored in live_ekf_slam_amd/navigation.py:
+ *   estimate in   the wire values of the state message, x_v, y_v, yaw_v rounded to float32 (EKFState.msg:5-7; UKF: yaw_v =
+ *                 remainder(atan2(x_t(3), x_t(2)), 2 pi), ukf.cpp:71) - slam_nav_estimates returns exactly these
+ *   command out   float32 (Command.msg) after the clamps to [0, d_max] and [-th_max, th_max] of the handle's slam_config
+ *   state         per instance: head (index of the first waypoint still queued: the queue is always a suffix of the path, since pare_path
+ *                 deletes up to the FIRST queued waypoint within 0.15 m, which need not be the head - a path that passes near itself is
+ *                 cut short as in the reference), integ, err_prev, finish_tick (the first tick whose command was issued with an empty
+ *                 queue, counted from the last reset; -1 until then)
+ *   arithmetic    fp64; powers are multiplication chains (x^4 = (x x)(x x), x^12 = x^8 x^4, the cube x x x), distances sqrt, atan2 the
+ *                 library's deterministic one, the heading error IEEE remainder(., 2 pi); no fused multiply-add
+ * Guards the reference lacks: consecutive equal waypoints are refused with SLAM_ERR_ARG when a path is set (the reference divides by zero
+ * there); an instance whose estimate is not finite, or which is frozen (SLAM_INST_INDEX_OOR), gets the command (0, 0) and keeps its
+ * controller state.
+ * Setting a path resets the controller state; slam_init and slam_init_each reset it too and keep the path.
+ * Kinds: EKF_SLAM in both storage types, UKF_SLAM, UKF_LOC; works with slam_set_maps.
+ * Errors: SLAM_ERR_STATE before slam_init, before a path is set, without a map, or while slam_track_instance is on; SLAM_ERR_ARG for a bad
+ * config (dt <= 0, a lookahead distance that is not positive and finite, more than 64 lookahead radii, unknown method or control), a bad
+ * path (no points, more than 1024, a non-finite coordinate, consecutive equal waypoints) or T < 0.
+ * Not covered: planning the path (A*, the occupancy map, the local planner, click goals) - the caller brings the waypoints; the zero
+ *   "kick-off" command the reference's simulator publishes first (issue slam_step_sim with (0, 0) before slam_nav_run for it); controller
+ *   state in slam_save_state files; slam_multi_*; the pose graph. */
+enum slam_nav_method { SLAM_NAV_PP = 0, SLAM_NAV_DIRECT = 1 };     /* path_planning.nav_method "pp" | "direct" ("simple" = direct) */
+enum slam_nav_control { SLAM_NAV_LOOSE = 0, SLAM_NAV_TIGHT = 1 };  /* the launch file's tight_control (goal_pursuit_node.py:158-161) */
+typedef struct slam_nav_config {
+    double dt, lookahead_dist_init, lookahead_dist_max;            /* params.yaml:14,83-84 */
+    int method, control;
+} slam_nav_config;
+/* dt 0.05, lookahead 0.2 .. 2 m, "pp" (params.yaml:14,81-84), loose control (sim_base.launch) */
+int slam_nav_config_default(slam_nav_config* cfg);
+/* Reads dt, nav_method, lookahead_dist_init, lookahead_dist_max from a params.yaml-shaped file, as slam_config_load: missing keys keep
+ * what *cfg holds (control is an argument of the launch file, not a key).  SLAM_ERR_IO: unreadable file, unknown nav_method. */
+int slam_nav_config_load(slam_nav_config* cfg, const char* yaml_path);
+/* One path for every instance: pts [P][2] (x, y), host pointer, 1 <= P <= 1024. */
+int slam_nav_set_path(slam_handle* h, const slam_nav_config* cfg, const double* pts, int P);
+/* One path per instance: pts [batch][P_stride][2], P [batch] waypoints each (1 <= P[b] <= P_stride <= 1024). */
+int slam_nav_set_paths(slam_handle* h, const slam_nav_config* cfg, const double* pts, const int32_t* P, int P_stride);
+/* T ticks of {controller, one SIM timestep}.  Runs the EKF step queue first and is not queued itself; advances truth, error sums,
+ * timestep and RNG exactly as T calls of slam_run_sim_each(h, cmds, 1) with the same commands would.  cmds_out: host [T][batch][2], the
+ * commands issued (NULL: not wanted).  SLAM_ERR_STATE also while a slam_predict is pending.  Returns when the ticks are done (long runs
+ * and command logs are processed in chunks of ticks, each ending synchronised). */
+int slam_nav_run(slam_handle* h, int T, float* cmds_out);
+/* Controller state, [batch] each, any pointer may be NULL: remaining = waypoints still queued. */
+int slam_nav_state(slam_handle* h, int32_t* remaining, int32_t* finish_tick, double* integ, double* err_prev);
+/* The estimates the next controller tick would read: est [batch][3] float32 (x_v, y_v, yaw_v), the state message's wire values. */
+int slam_nav_estimates(slam_handle* h, float* est);
+/* Device time of the last slam_nav_run in ms, by HIP events on the handle's stream: everything (one event pair per chunk of ticks, always),
+ * and the controller kernels alone.  The latter needs an event pair around every controller launch, which is off by default:
+ * slam_nav_set_timing(h, 1) switches it on for the following runs (0: off again); without it *controller_ms = -1. */
+int slam_nav_set_timing(slam_handle* h, int per_tick);
+int slam_last_nav_work(slam_handle* h, double* controller_ms, double* total_ms);
+/* TEST HOOK, not part of the filter interface: the controller's tick function compiled for the HOST (the same source as the kernel, no
+ * device needed), so that the restatement and the argument checks can be tested where there is no GPU.  One instance, one tick.
+ * d_max / th_max: the clamps; est: wire values; frozen != 0: the instance is frozen; tick: ticks since the reset.  head, finish_tick,
+ * integ, err_prev are read and updated in place; cmd receives (fwd, ang).  SLAM_ERR_ARG as for slam_nav_set_path. */
+int slam_nav_tick_host(const slam_nav_config* cfg, double d_max, double th_max, const double* pts, int P, const float est[3], int frozen,
+                       int tick, int32_t* head, int32_t* finish_tick, double* integ, double* err_prev, float cmd[2]);
+
 /* ---- scenario generators (host side; sim_node.py:63-206) ------------------------------------------------------ */
 /* generate_landmarks + generate_full_trajectory of the reference simulator for one scenario seed (the reference seeds
  * CPython's Mersenne Twister; the same generator is implemented in include/slam_scenario.hpp, so a seed gives the reference's

@@ -80,6 +80,28 @@ inline std::vector<float> packCommands(const std::vector<Command>& cmds, int bat
         need();                                                                                                                          \
         if (cmds.size() % (2 * (size_t)batch_) != 0) checkSize(cmds.size(), 2 * (size_t)batch_ * (cmds.size() / (2 * (size_t)batch_) + 1), "cmds [T][B][2]"); \
         check(slam_run_sim_each(h_, cmds.data(), (int)(cmds.size() / (2 * (size_t)batch_))));                                           \
+    }                                                                                                                                    \
+    /* closed loop (slam_nav_*, include/slam_batch.h): one path [P][2] for the batch, or paths [B][P_stride][2] with P [B] waypoints;  */ \
+    /* runNav = T ticks of {controller on each instance's estimate, one simulator timestep}; returns [T][B][2] commands if asked      */ \
+    void setPath(const std::vector<double>& pts, const slam_nav_config& nav) {                                                           \
+        need(); check(slam_nav_set_path(h_, &nav, pts.data(), (int)(pts.size() / 2)));                                                   \
+    }                                                                                                                                    \
+    void setPaths(const std::vector<double>& pts, const std::vector<int32_t>& P, int P_stride, const slam_nav_config& nav) {             \
+        need(); checkSize(P.size(), (size_t)batch_, "P"); checkSize(pts.size(), 2 * (size_t)P_stride * batch_, "paths");               \
+        check(slam_nav_set_paths(h_, &nav, pts.data(), P.data(), P_stride));                                                             \
+    }                                                                                                                                    \
+    std::vector<float> runNav(int T, bool return_cmds = false) {                                                                         \
+        need();                                                                                                                          \
+        std::vector<float> cmds(return_cmds && T > 0 ? 2 * (size_t)T * batch_ : 0);                                                      \
+        check(slam_nav_run(h_, T, cmds.empty() ? nullptr : cmds.data()));                                                                \
+        return cmds;                                                                                                                     \
+    }                                                                                                                                    \
+    struct NavState { std::vector<int32_t> remaining, finish_tick; std::vector<double> integ, err_prev; };                               \
+    NavState navState() {                                                                                                                \
+        need();                                                                                                                          \
+        NavState s; s.remaining.resize(batch_); s.finish_tick.resize(batch_); s.integ.resize(batch_); s.err_prev.resize(batch_);         \
+        check(slam_nav_state(h_, s.remaining.data(), s.finish_tick.data(), s.integ.data(), s.err_prev.data()));                         \
+        return s;                                                                                                                        \
     }
 
 class Filter {  // filter.h:54-77

@@ -5,7 +5,7 @@ There is no CPU fallback: if the library is missing or a HIP call fails, an exce
 import ctypes as C
 import os
 
-from .config import SlamConfig
+from .config import SlamConfig, NavConfig
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # SLAM_HIP_LIB: another build of the same library, for A/B tuning sessions (tools/gpu_ab.sh); the product path is the
@@ -62,6 +62,16 @@ SIGNATURES = {
     "slam_status": (C.c_int, [_H, _ip]),
     "slam_consistency": (C.c_int, [_H, _dp, _dp, _dp, _ip, _ip]),
     "slam_last_consistency_work": (C.c_int, [_H, _dp, _dp]),
+    "slam_nav_config_default": (C.c_int, [C.POINTER(NavConfig)]),
+    "slam_nav_config_load": (C.c_int, [C.POINTER(NavConfig), C.c_char_p]),
+    "slam_nav_set_path": (C.c_int, [_H, C.POINTER(NavConfig), _dp, C.c_int]),
+    "slam_nav_set_paths": (C.c_int, [_H, C.POINTER(NavConfig), _dp, _ip, C.c_int]),
+    "slam_nav_run": (C.c_int, [_H, C.c_int, _fp]),
+    "slam_nav_state": (C.c_int, [_H, _ip, _ip, _dp, _dp]),
+    "slam_nav_estimates": (C.c_int, [_H, _fp]),
+    "slam_nav_set_timing": (C.c_int, [_H, C.c_int]),
+    "slam_last_nav_work": (C.c_int, [_H, _dp, _dp]),
+    "slam_nav_tick_host": (C.c_int, [C.POINTER(NavConfig), C.c_double, C.c_double, _dp, C.c_int, _fp, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _fp]),
     "slam_sync": (C.c_int, [_H]),
     "slam_batch": (C.c_int, [_H]),
     "slam_state_dim_max": (C.c_int, [_H]),

@@ -42,6 +42,21 @@ def default_config() -> SlamConfig:
     return c
 
 
+class NavConfig(C.Structure):
+    """ctypes mirror of `slam_nav_config` (include/slam_batch.h): params.yaml:14,81-84 plus the launch file's tight_control."""
+    _fields_ = [("dt", C.c_double), ("lookahead_dist_init", C.c_double), ("lookahead_dist_max", C.c_double),
+                ("method", C.c_int), ("control", C.c_int)]
+
+
+NAV_PP, NAV_DIRECT = 0, 1
+NAV_LOOSE, NAV_TIGHT = 0, 1
+
+
+def default_nav_config() -> NavConfig:
+    """dt 0.05, lookahead 0.2 .. 2 m, "pp" (params.yaml:14,81-84), loose control (sim_base.launch)."""
+    return NavConfig(0.05, 0.2, 2.0, NAV_PP, NAV_LOOSE)
+
+
 EKF_SLAM, UKF_LOC, UKF_SLAM = 1, 2, 3
 F64, F32 = 0, 1
 INST_NONFINITE, INST_S_SINGULAR, INST_INDEX_OOR, INST_CAPACITY, INST_SQRT_FAILED = 1, 2, 4, 8, 16

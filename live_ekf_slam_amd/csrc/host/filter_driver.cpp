@@ -17,6 +17,10 @@
 //   filter_driver consistency <batch> <L> <steps> <dump.bin> [seed]
 //       The EKF run of `run`, then BatchedEKF::consistency(): the file gets int64 batch, then nees_full, nees_pose, map_rms (doubles) and
 //       dof, flags (int32), batch values each.
+//   filter_driver nav <batch> <L> <ticks> <dump.bin> [seed]
+//       Closed loop through the C++ mirror: setPath (the map's first three landmarks, the reference's controller defaults), runNav with the
+//       commands returned, navState.  The file gets int64 batch, the [ticks][batch][2] float commands, then remaining, finish_tick (int32)
+//       and integ, err_prev (doubles), batch values each.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -163,6 +167,33 @@ static int run_consistency(int B, int L, int T, const char* dump_path, uint64_t 
     return 0;
 }
 
+static int run_nav(int B, int L, int T, const char* dump_path, uint64_t seed) {
+    const Scenario sc = make_scenario(seed, L, T);
+    BatchedEKF ekf(B, L);
+    slam_config cfg;
+    check(slam_config_default(&cfg));
+    ekf.readParams(cfg);
+    ekf.init(0.f, 0.f, 0.f);
+    ekf.setMap(sc.map_xy);
+    slam_nav_config nav;
+    check(slam_nav_config_default(&nav));
+    ekf.setPath(std::vector<double>(sc.map_xy.begin(), sc.map_xy.begin() + 6), nav);
+    const std::vector<float> cmds = ekf.runNav(T, true);
+    const auto st = ekf.navState();
+    FILE* f = std::fopen(dump_path, "wb");
+    if (!f) throw std::runtime_error(std::string("cannot write ") + dump_path);
+    const int64_t hd = B;
+    std::fwrite(&hd, sizeof(int64_t), 1, f);
+    std::fwrite(cmds.data(), sizeof(float), cmds.size(), f);
+    std::fwrite(st.remaining.data(), sizeof(int32_t), (size_t)B, f);
+    std::fwrite(st.finish_tick.data(), sizeof(int32_t), (size_t)B, f);
+    std::fwrite(st.integ.data(), sizeof(double), (size_t)B, f);
+    std::fwrite(st.err_prev.data(), sizeof(double), (size_t)B, f);
+    std::fclose(f);
+    std::printf("driver ok: nav batch=%d L=%d ticks=%d\n", B, L, T);
+    return 0;
+}
+
 // the global batch over several GPUs of the node from this one process (SURVEY.md section 8(e) "Host")
 static int run_multi(const std::string& kind, int64_t B, int L, int T, int gpus, uint64_t seed, int gather_mode) {
     const Scenario sc = make_scenario(seed, L, T);
@@ -249,12 +280,14 @@ int main(int argc, char** argv) {
         if (mode == "run" && argc >= 6) return run_scenario(argv[2], atoi(argv[3]), atoi(argv[4]), atoi(argv[5]), argc > 6 ? strtoull(argv[6], nullptr, 10) : 1234ull);
         if (mode == "consistency" && argc >= 6)
             return run_consistency(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), argv[5], argc > 6 ? strtoull(argv[6], nullptr, 10) : 1234ull);
+        if (mode == "nav" && argc >= 6) return run_nav(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), argv[5], argc > 6 ? strtoull(argv[6], nullptr, 10) : 1234ull);
         if (mode == "pose_graph" && argc >= 5) return run_pose_graph(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), argc > 5 ? argv[5] : nullptr);
         std::fprintf(stderr, "usage: filter_driver stream <ekf|ukf|ukf_loc> <batch> <L_max> <stream.txt> <dump.bin>\n"
                              "       filter_driver run <ekf|ukf> <batch> <L> <steps> [seed]\n"
                              "       filter_driver run_multi <ekf|ukf> <global batch> <L> <steps> <gpus> [seed] [gather 0|1]\n"
                              "       filter_driver pose_graph <batch> <L> <steps> [marginals dump.bin]\n"
-                             "       filter_driver consistency <batch> <L> <steps> <dump.bin> [seed]\n");
+                             "       filter_driver consistency <batch> <L> <steps> <dump.bin> [seed]\n"
+                             "       filter_driver nav <batch> <L> <ticks> <dump.bin> [seed]\n");
         return 2;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "driver failed: %s\n", e.what());

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .config import SlamConfig, default_config, EKF_SLAM, UKF_LOC, UKF_SLAM, F64
+from .config import SlamConfig, NavConfig, default_config, default_nav_config, EKF_SLAM, UKF_LOC, UKF_SLAM, F64
 
 
 def _d(a):
@@ -345,6 +345,84 @@ class BatchedFilter:
         self._need(); b = C.c_double(0); ms = C.c_double(0)
         _lib.check(_lib.lib().slam_last_consistency_work(self.h, C.byref(b), C.byref(ms)))
         return b.value, ms.value
+
+    # -- closed loop: goal_pursuit_node.py:23-50 on the device (slam_nav_*, include/slam_batch.h) --
+    def _nav_config(self, nav):
+        if nav is None:
+            return default_nav_config()
+        if isinstance(nav, NavConfig):
+            return nav
+        c = default_nav_config()
+        for k, v in dict(nav).items():
+            if k not in ("dt", "lookahead_dist_init", "lookahead_dist_max", "method", "control"):
+                raise ValueError(f"unknown controller setting {k!r}")
+            setattr(c, k, v)
+        return c
+
+    def set_path(self, pts, nav=None):
+        """One path (P, 2) of waypoints for every instance; nav: a NavConfig, a dict of its fields, or None for the reference's
+        defaults (pure pursuit, loose control).  Resets the controller state."""
+        self._need()
+        p = np.ascontiguousarray(pts, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise ValueError(f"expected a path of shape (P, 2), got {p.shape}")
+        c = self._nav_config(nav)
+        _lib.check(_lib.lib().slam_nav_set_path(self.h, C.byref(c), _d(p), p.shape[0]))
+
+    def set_paths(self, paths, counts=None, nav=None):
+        """One path per instance: a list of batch (P_b, 2) arrays, or a (batch, P_stride, 2) array with `counts` [batch] waypoints
+        each (default: all P_stride)."""
+        self._need()
+        if isinstance(paths, (list, tuple)):
+            ps = [np.asarray(p, dtype=np.float64) for p in paths]
+            if len(ps) != self.batch or any(p.ndim != 2 or p.shape[1] != 2 or p.shape[0] == 0 for p in ps):
+                raise ValueError(f"expected a list of {self.batch} paths of shape (P_b > 0, 2)")
+            counts = np.array([p.shape[0] for p in ps], dtype=np.int32)
+            arr = np.zeros((self.batch, int(counts.max()), 2))
+            for b, p in enumerate(ps):
+                arr[b, :p.shape[0]] = p
+            paths = arr
+        a = np.ascontiguousarray(paths, dtype=np.float64)
+        if a.ndim != 3 or a.shape[0] != self.batch or a.shape[2] != 2 or a.shape[1] == 0:
+            raise ValueError(f"expected per-instance paths of shape ({self.batch}, P_stride > 0, 2), got {a.shape}")
+        cnt = np.full(self.batch, a.shape[1], np.int32) if counts is None else np.ascontiguousarray(counts, dtype=np.int32)
+        if cnt.shape != (self.batch,):
+            raise ValueError(f"counts: expected {self.batch} waypoint counts")
+        c = self._nav_config(nav)
+        _lib.check(_lib.lib().slam_nav_set_paths(self.h, C.byref(c), _d(a), _i(cnt), a.shape[1]))
+
+    def run_nav(self, T, return_cmds=False):
+        """T ticks of {controller on every instance's own estimate, one simulator timestep}, all on the device.  return_cmds: the
+        (T, batch, 2) float32 commands that were issued."""
+        self._need()
+        T = int(T)
+        cmds = np.zeros((max(T, 0), self.batch, 2), dtype=np.float32) if return_cmds else None
+        _lib.check(_lib.lib().slam_nav_run(self.h, T, None if cmds is None or cmds.size == 0 else _f(cmds)))
+        self.timestep += max(T, 0)
+        return cmds
+
+    def nav_state(self):
+        """Controller state of every instance: dict of [batch] arrays remaining (waypoints still queued), finish_tick (-1 until the
+        queue is empty), integ, err_prev."""
+        self._need()
+        out = dict(remaining=np.zeros(self.batch, dtype=np.int32), finish_tick=np.zeros(self.batch, dtype=np.int32),
+                   integ=np.zeros(self.batch), err_prev=np.zeros(self.batch))
+        _lib.check(_lib.lib().slam_nav_state(self.h, _i(out["remaining"]), _i(out["finish_tick"]), _d(out["integ"]), _d(out["err_prev"])))
+        return out
+
+    def nav_estimates(self):
+        """(batch, 3) float32 x_v, y_v, yaw_v: the state message's wire values, what the next controller tick reads."""
+        self._need(); out = np.zeros((self.batch, 3), dtype=np.float32); _lib.check(_lib.lib().slam_nav_estimates(self.h, _f(out))); return out
+
+    def set_nav_timing(self, per_tick=True):
+        """Time every controller launch of the following run_nav calls with its own event pair (off by default)."""
+        self._need(); _lib.check(_lib.lib().slam_nav_set_timing(self.h, int(bool(per_tick))))
+
+    def last_nav_work(self):
+        """(device ms of the controller kernels, or -1 without set_nav_timing; device ms of everything) of the last run_nav, by HIP events."""
+        self._need(); a = C.c_double(0); b = C.c_double(0)
+        _lib.check(_lib.lib().slam_last_nav_work(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def set_lazy_steps(self, n):
         self._need(); _lib.check(_lib.lib().slam_set_lazy_steps(self.h, int(n)))
