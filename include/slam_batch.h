@@ -197,8 +197,8 @@ int slam_update_dev(slam_handle* h, const float* d_meas, const int32_t* d_meas_c
  * slam_track_instance: the shadow gets the tracked instance's row of every per-instance input.
  * Checkpoints: maps and commands are inputs, not state; slam_save_state / slam_load_state keep their format, and after a load the caller
  *   sets the maps (slam_set_maps) again as for slam_set_map.
- * Not covered: the pose graph (slam_pgs.h: its graphs share one BetweenFactor sequence by construction), slam_multi_*, a per-instance
- *   known map for UKF_LOC, per-instance noise configs. */
+ * The pose graph has the same forms (slam_pgs.h: pgs_init_each, pgs_set_maps, pgs_update_each[_dev], pgs_run_sim_each).
+ * Not covered: slam_multi_*, a per-instance known map for UKF_LOC, per-instance noise configs. */
 /* Filter::init with one start pose per instance: pose0 [batch][3] {x, y, yaw} (float, as slam_init's arguments); truth0 [batch][3] =
  * the simulator's true start pose per instance, NULL = the config's init pose for all.  Resets what slam_init resets. */
 int slam_init_each(slam_handle* h, const float* pose0, const double* truth0);
@@ -316,7 +316,8 @@ int slam_last_consistency_work(slam_handle* h, double* bytes, double* ms);
  * path (no points, more than 1024, a non-finite coordinate, consecutive equal waypoints) or T < 0.
  * Not covered: planning the path (A*, the occupancy map, the local planner, click goals) - the caller brings the waypoints; the zero
  *   "kick-off" command the reference's simulator publishes first (issue slam_step_sim with (0, 0) before slam_nav_run for it); controller
- *   state in slam_save_state files; slam_multi_*; the pose graph. */
+ *   state in slam_save_state files; slam_multi_*; a controller on the pose graph's own estimate (a pose graph FOLLOWS such a run: cmds_out,
+ *   the measurement dump and slam_get_poses of every tick go to pgs_update_each, slam_pgs.h). */
 enum slam_nav_method { SLAM_NAV_PP = 0, SLAM_NAV_DIRECT = 1 };     /* path_planning.nav_method "pp" | "direct" ("simple" = direct) */
 enum slam_nav_control { SLAM_NAV_LOOSE = 0, SLAM_NAV_TIGHT = 1 };  /* the launch file's tight_control (goal_pursuit_node.py:158-161) */
 typedef struct slam_nav_config {

@@ -356,7 +356,8 @@ struct PoseGraphState {
 };
 
 // Batch of B pose graphs behind the reference's PoseGraph interface (filter.h:232-322, pose_graph.cpp, GTSAM path).
-// update(cmd, meas) applies the SAME message to every instance; updateBatch takes per-instance measurements.
+// update(cmd, meas) applies the SAME message to every instance; updateBatch takes per-instance measurements, and with a vector of
+// commands one BetweenFactor measurement per instance (pgs_*_each: init, setMap, updateBatch and runSim overloads as the filters have).
 class BatchedPoseGraph : public Filter {
 public:
     BatchedPoseGraph(int batch, int num_iterations, int L_max, int k_per_pose = 8, int device = 0)
@@ -383,6 +384,24 @@ public:
         check(pgs_init(h_, x_0, y_0, yaw_0));
         isInit = true; solved_pose_graph = false; timestep = 0; have_sec_ = false;
     }
+    // one start pose per instance (pose0 [B][3] {x, y, yaw}), optional true start poses of the simulator (truth0 [B][3], empty = pose0)
+    void init(const std::vector<float>& pose0, const std::vector<double>& truth0 = {}) {
+        need(); checkSize(pose0.size(), 3 * (size_t)batch_, "pose0");
+        if (!truth0.empty()) checkSize(truth0.size(), 3 * (size_t)batch_, "truth0");
+        check(pgs_init_each(h_, pose0.data(), truth0.empty() ? nullptr : truth0.data()));
+        isInit = true; solved_pose_graph = false; timestep = 0; have_sec_ = false;
+    }
+    // the simulator's true map: [L][2] for every instance, or maps [B][L_stride][2] with L [B] landmarks each
+    void setMap(const std::vector<double>& map_xy) { need(); check(pgs_set_map(h_, map_xy.data(), (int)(map_xy.size() / 2))); }
+    void setMap(const std::vector<double>& maps, const std::vector<int32_t>& L, int L_stride) {
+        need(); checkSize(L.size(), (size_t)batch_, "L"); checkSize(maps.size(), 2 * (size_t)L_stride * batch_, "maps");
+        check(pgs_set_maps(h_, maps.data(), L.data(), L_stride));
+    }
+    // the secondary filter's estimate of every instance, poses [B][3] (e.g. slam_get_poses of a filter batch)
+    void updateNaiveVehPoseEstimateBatch(const std::vector<double>& poses) {
+        checkSize(poses.size(), 3 * (size_t)batch_, "poses");
+        sec_ = poses; have_sec_ = true;
+    }
     // pose_graph.cpp:97-119: the same secondary estimate for every instance (e.g. the NaiveFilter)
     void updateNaiveVehPoseEstimate(const std::vector<double>& state_vector, const std::vector<int>&) override {
         sec_.resize((size_t)batch_ * 3);
@@ -405,6 +424,30 @@ public:
         timestep += 1;
         if (solve_graph_every_iteration) { solvePoseGraph(); check(pgs_adopt_result(h_)); }   // :258-264
         publishState();
+    }
+    // one command per instance
+    void updateBatch(const std::vector<Command>& cmds, const float* meas, const int32_t* meas_count, int k_stride) {
+        need();
+        if (solved_pose_graph && !solve_graph_every_iteration) return;
+        if (timestep + 1 >= num_iterations_total) { solvePoseGraph(); publishState(); return; }
+        check(pgs_update_each(h_, packCommands(cmds, batch_).data(), k_stride > 0 ? meas : nullptr, k_stride > 0 ? meas_count : nullptr, k_stride, have_sec_ ? sec_.data() : nullptr));
+        timestep += 1;
+        if (solve_graph_every_iteration) { solvePoseGraph(); check(pgs_adopt_result(h_)); }
+        publishState();
+    }
+    // the device-side simulator with the NaiveFilter as secondary: cmds [T][2] floats for the batch, or [T][B][2] with each = true
+    void runSim(const std::vector<float>& cmds, bool each = false) {
+        need();
+        const size_t row = each ? 2 * (size_t)batch_ : 2;
+        if (cmds.size() % row != 0) checkSize(cmds.size(), row * (cmds.size() / row + 1), each ? "cmds [T][B][2]" : "cmds [T][2]");
+        const int T = (int)(cmds.size() / row);
+        if (solve_graph_every_iteration) {
+            check(each ? pgs_run_sim_every_iteration_each(h_, cmds.data(), T, nullptr) : pgs_run_sim_every_iteration(h_, cmds.data(), T, nullptr));
+            solved_pose_graph = true;
+        } else {
+            check(each ? pgs_run_sim_each(h_, cmds.data(), T) : pgs_run_sim(h_, cmds.data(), T));
+        }
+        timestep += T;
     }
     void solvePoseGraph() { need(); check(pgs_solve(h_)); solved_pose_graph = true; }    // pose_graph.cpp:269-300
     void publishState() override { last_state = stateMsg(0); }

@@ -3,16 +3,21 @@
  * Drop-in boundary for the reference's `PoseGraph : Filter` with `implementation: gtsam`
  * (ekf_ws/src/localization_pkg/src/pose_graph.cpp, class declaration filter.h:232-322): the graph-building calls of
  * every timestep and `solvePoseGraph()` (gtsam::LevenbergMarquardtOptimizer, default parameters), for a batch of B
- * independent graphs — Monte-Carlo instances that share the command sequence (BetweenFactors) and differ in their
- * measurements and in the secondary filter's estimates.  Same conventions as slam_batch.h: plain pointers and sizes,
- * int status codes (slam_status_code), text in slam_last_error(), one caller thread per handle, kernels on one stream.
+ * independent graphs.  By default they are Monte-Carlo instances that share the command sequence (BetweenFactors), the start
+ * pose and the simulator's map and differ in their measurements and in the secondary filter's estimates; the pgs_*_each entry
+ * points give every graph its own start pose, map and commands ("heterogeneous batches" below).  Same conventions as
+ * slam_batch.h: plain pointers and sizes, int status codes (slam_status_code), text in slam_last_error(), one caller thread per
+ * handle, kernels on one stream.
  *
  * Covered beyond the solve: `gtsam::Marginals marginals(graph, result); marginals.marginalCovariance(i)` (pose_graph.cpp:289-294) as
  * pgs_marginals / pgs_get_marginals, for every pose and landmark (the reference's printout of them is not reproduced).
  *
  * Not covered: `implementation: sesync | custom` (the reference itself throws for both, pose_graph.cpp:34-38),
  * unknown landmark ids (the reference throws, pose_graph.cpp:137), `update_landmarks_after_adding` (false in
- * params.yaml:63 and forced false when solving every iteration, pose_graph.cpp:45-48).
+ * params.yaml:63 and forced false when solving every iteration, pose_graph.cpp:45-48), per-instance timestep counts (a handle
+ * is in lockstep: one `timestep` for all of its graphs) and per-instance noise configs, a secondary EKF fused into the device-side
+ * simulator (feed pgs_update_each_dev from a slam_batch.h handle instead), a pgs_nav_* controller (slam_nav_run issues the
+ * commands; its cmds_out go to pgs_update_each), slam_multi_*, checkpoint files.
  */
 #ifndef SLAM_PGS_H
 #define SLAM_PGS_H
@@ -46,7 +51,7 @@ int pgs_destroy(pgs_handle* h);
 int pgs_set_stream(pgs_handle* h, void* hip_stream);
 int pgs_set_instance_offset(pgs_handle* h, int64_t first_global_instance);
 int pgs_set_seed(pgs_handle* h, uint64_t seed);
-int pgs_set_map(pgs_handle* h, const double* map_xy, int L);      /* simulator only (pgs_run_sim) */
+int pgs_set_map(pgs_handle* h, const double* map_xy, int L);      /* simulator only (pgs_run_sim); one map for every instance */
 
 /* PoseGraph::init (pose_graph.cpp:68-95): first pose node + PriorFactor with sigmas (1.3, 1.3, 1.2). */
 int pgs_init(pgs_handle* h, float x_0, float y_0, float yaw_0);
@@ -66,6 +71,35 @@ int pgs_update_dev(pgs_handle* h, const float cmd[2], const float* d_meas, const
  * instance's noise stream, NaiveFilter::update as the secondary filter (filter.h:342-348, params.yaml:60), then the
  * two calls above.  cmds [T][2] float32 host array. */
 int pgs_run_sim(pgs_handle* h, const float* cmds, int T);
+
+/* ---- heterogeneous batches -------------------------------------------------------------------------------------------------
+ * Per-instance forms of the calls above, named and laid out like slam_batch.h's slam_*_each (arrays of `batch` rows, HOST pointers
+ * unless marked _dev), so that one handle can hold several robots, trajectories or maps, and can follow a slam_batch.h handle whose
+ * instances drive their own commands (slam_nav_run).  Every entry point above keeps its behaviour, and per-instance rows that are all
+ * equal give the same bits as the shared call.  pgs_solve, pgs_adopt_result, pgs_marginals*, pgs_get_* and pgs_error_stats work on such
+ * graphs unchanged, in every solve schedule.
+ * Mixing: shared and _each calls may be mixed and take effect in call order.  The handle stays in lockstep (one timestep).  The first
+ *   per-instance command moves the handle's BetweenFactor measurements from one row [N_max][2] to one row per instance ([batch][N_max][2]
+ *   float32: 8 * batch * N_max bytes, 16 MB at batch 2048 with N_max = 1000, kept until pgs_destroy); the ticks the handle already has
+ *   stay in every instance's graph, and a shared call afterwards writes its command into every instance's row.
+ * Errors: SLAM_ERR_STATE before pgs_init / pgs_init_each, and for the simulator calls without a map; SLAM_ERR_ARG for NULL or non-finite
+ *   host inputs, L[b] out of range, T <= 0.  A call that returns an error has changed nothing. */
+/* PoseGraph::init with one start pose per instance: pose0 [batch][3] {x, y, yaw} (float, as pgs_init's arguments) = the first pose
+ * node, cur_veh_pose_estimate and the mean of the PriorFactor; truth0 [batch][3] = the simulator's true start pose per instance, NULL =
+ * the instance's pose0 row widened to double (what pgs_init does with its arguments).  Resets what pgs_init resets. */
+int pgs_init_each(pgs_handle* h, const float* pose0, const double* truth0);
+/* Simulator only: one true map per instance, maps [batch][L_stride][2], L [batch] landmarks (ids 0 .. L[b]-1; 1 <= L[b] <= L_stride <=
+ * 255).  Replaces the shared map; a later pgs_set_map returns to the shared map. */
+int pgs_set_maps(pgs_handle* h, const double* maps, const int32_t* L, int L_stride);
+/* One iterate() with one BetweenFactor measurement per instance, cmds [batch][2] {fwd, ang}; otherwise as pgs_update / pgs_update_dev
+ * (pgs_update_each_dev: d_cmds is a device pointer too, read in the order of the handle's stream - e.g. the controller's commands of a
+ * slam_batch.h handle next to its measurement dump and poses). */
+int pgs_update_each(pgs_handle* h, const float* cmds, const float* meas, const int32_t* meas_count, int k_stride,
+                    const double* sec_pose);
+int pgs_update_each_dev(pgs_handle* h, const float* d_cmds, const float* d_meas, const int32_t* d_meas_count, int k_stride,
+                        const double* d_sec_pose);
+/* T simulator iterations, cmds [T][batch][2] (the layout of slam_run_sim_each): one copy and one transposing launch, no per-tick host work. */
+int pgs_run_sim_each(pgs_handle* h, const float* cmds, int T);
 
 /* PoseGraph::solvePoseGraph (pose_graph.cpp:269-300) for every instance: LM from initial_estimate to `result`.
  * The trials of a batch run in lockstep; once few instances are still active each runs the next lambdas of GTSAM's retry
@@ -103,6 +137,8 @@ int pgs_adopt_result(pgs_handle* h);
  * device: T x { one tick of pgs_run_sim, pgs_solve, pgs_adopt_result }.  counts [batch][2] (may be NULL) = the LM iterations and
  * lambda trials of every instance summed over the T ticks. */
 int pgs_run_sim_every_iteration(pgs_handle* h, const float* cmds, int T, int32_t* counts);
+/* The same with one command per instance and tick, cmds [T][batch][2]. */
+int pgs_run_sim_every_iteration_each(pgs_handle* h, const float* cmds, int T, int32_t* counts);
 /* Phase table of the last such call when SLAM_PGS_ITER_PROF=1 was set (a stream synchronisation after every phase; timing runs leave it
  * unset): out = {host-clock ms in simulator + append, in solve, in adopt, LM trials launched, algorithmic FLOP of the call's consumed
  * trials summed over the batch: Schur-complement SYRK, dense Cholesky + substitutions (n^3/3 + 2 n^2 at n = 2 M)}; the last three are

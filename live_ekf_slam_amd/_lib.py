@@ -99,6 +99,12 @@ SIGNATURES = {
     "pgs_update": (C.c_int, [_H, _fp, _fp, _ip, C.c_int, _dp]),
     "pgs_update_dev": (C.c_int, [_H, _fp, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pgs_run_sim": (C.c_int, [_H, _fp, C.c_int]),
+    "pgs_init_each": (C.c_int, [_H, _fp, _dp]),
+    "pgs_set_maps": (C.c_int, [_H, _dp, _ip, C.c_int]),
+    "pgs_update_each": (C.c_int, [_H, _fp, _fp, _ip, C.c_int, _dp]),
+    "pgs_update_each_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pgs_run_sim_each": (C.c_int, [_H, _fp, C.c_int]),
+    "pgs_run_sim_every_iteration_each": (C.c_int, [_H, _fp, C.c_int, _ip]),
     "pgs_solve": (C.c_int, [_H]),
     "pgs_set_groups": (C.c_int, [_H, C.c_int]),
     "pgs_adopt_result": (C.c_int, [_H]),

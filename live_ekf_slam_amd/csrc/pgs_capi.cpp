@@ -3,6 +3,7 @@
 #include "../../include/slam_pgs.h"
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <sched.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -34,7 +35,14 @@ struct pgs_handle {
     std::vector<Array> arrays;                 // sized by pgs_create
     std::vector<Array> seg_arrays;             // sized for segments of seg_alloc poses (segT joins on first use): replaced as a whole by resize_segments
     DevBuf<double> map;                        // p.map
-    DevBuf<float> dcmds;                       // p.cmds
+    DevBuf<float> dcmds;                       // p.cmds while the handle has seen shared calls only: one row [N_max][2]
+    // Heterogeneous batches (pgs_*_each).  dcmds_each: one row of BetweenFactor measurements per instance, [B][N_max][2] floats = 8 B N_max
+    // bytes (16 MB at batch 2048 with N_max = 1000; 0.1 % of that handle's LM work space), allocated by the first per-instance command and
+    // kept for the handle's lifetime; p.cmds then points at it (ensure_cmds_each).  Not per slot: the lambda lanes read their instance's row.
+    DevBuf<float> dcmds_each;
+    DevBuf<float> dcmd_stage;                  // host commands on their way into the rows ([T][B][2] or [T][2])
+    DevBuf<double> dmaps; DevBuf<int32_t> dLs; // pgs_set_maps: p.map_each [B][map_stride][2], p.L_each [B]
+    DevBuf<float> dpose_each; DevBuf<double> dtruth_each;   // pgs_init_each's staging, [B][3] each
     DevBuf<float> dmeas; DevBuf<int32_t> dcount; DevBuf<double> dsec;   // pgs_update's staging
     DevBuf<double> dout;
     int max_trials = 400;
@@ -222,7 +230,7 @@ int pgs_create(const slam_config* cfg, int batch, int N_max, int L_max, int k_pe
     AC(&p.cnt, N); AC(&p.mlm, K); AC(&p.mnext, K); AC(&p.lm_head, L); AC(&p.lm_last, L); AC(&p.lm_first, L);
     AC(&p.mb, K); AC(&p.mr, K);
     D(h->dcmds, N * 2); p.cmds = h->dcmds;
-    A(&p.cur, B * 3); A(&p.truth, B * 3); A(&p.truth_hist, B * N * 2);
+    A(&p.cur, B * 3); A(&p.truth, B * 3); A(&p.truth_hist, B * N * 2); A(&p.prior, B * 3);
     AC(&p.pw, N * 3); AC(&p.lw, L * 2); A(&p.pn, S * N * 3); A(&p.ln, S * L * 2);
     A(&p.A, S * N * 9); A(&p.C, S * N * 9); A(&p.gp, S * N * 3); A(&p.E, S * K * 6); A(&p.Wl, S * K * 5);
     AC(&p.evt_start, L + 1); AC(&p.evt_pose, K); AC(&p.slot_pos, K); AC(&p.evt_slot, K); A(&p.Elm, S * K * 6);
@@ -301,6 +309,32 @@ int pgs_set_map(pgs_handle* h, const double* map_xy, int L) {
     HIP_TRY(hipMemcpyAsync(h->map, map_xy, sizeof(double) * 2 * (size_t)L, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->p.map = h->map; h->p.L = L;
+    h->p.map_each = nullptr; h->p.L_each = nullptr; h->p.map_stride = 0;   // back from per-instance maps (pgs_set_maps)
+    return SLAM_OK;
+}
+
+int pgs_set_maps(pgs_handle* h, const double* maps, const int32_t* L, int L_stride) {
+    TRY(check(h));
+    if (!maps || !L || L_stride <= 0 || L_stride > 255) return fail(SLAM_ERR_ARG, "bad argument (maps, L, 1 <= L_stride <= 255)");
+    const size_t B = (size_t)h->B;
+    for (size_t b = 0; b < B; ++b) {
+        if (L[b] <= 0 || L[b] > L_stride) return fail(SLAM_ERR_ARG, "instance %zu: %d landmarks, outside [1, L_stride = %d]", b, L[b], L_stride);
+        for (size_t k = 0; k < 2 * (size_t)L[b]; ++k)
+            if (!isfinite(maps[b * L_stride * 2 + k])) return fail(SLAM_ERR_ARG, "instance %zu: landmark %zu is not finite", b, k / 2);
+    }
+    const size_t nm = 2 * (size_t)L_stride * B;
+    if (h->dmaps.cap() < nm || h->dLs.cap() < B) {   // both new blocks first: a failure leaves the handle with the maps it had
+        DevBuf<double> m; DevBuf<int32_t> l;
+        HIP_TRY(m.reserve(nm)); HIP_TRY(l.reserve(B));
+        HIP_TRY(hipStreamSynchronize(h->stream));     // the launches that read the old ones are done
+        h->dmaps = std::move(m); h->dLs = std::move(l);
+    } else {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(h->dmaps, maps, sizeof(double) * nm, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->dLs, L, sizeof(int32_t) * B, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->p.map_each = h->dmaps; h->p.L_each = h->dLs; h->p.map_stride = L_stride;
     return SLAM_OK;
 }
 
@@ -309,8 +343,87 @@ int pgs_init(pgs_handle* h, float x0, float y0, float yaw0) {
     h->mg_valid = false;
     h->timestep = 0; h->p.N = 1;
     h->seg_cur = h->seg_len;
-    h->p.prior[0] = x0; h->p.prior[1] = y0; h->p.prior[2] = yaw0;
     HIP_TRY(slam::pgs_launch_init(h->p, x0, y0, yaw0, h->stream));
+    h->inited = true; h->solved = false;
+    return SLAM_OK;
+}
+
+namespace {
+
+bool all_finite_f(const float* v, size_t n) { for (size_t i = 0; i < n; ++i) if (!isfinite(v[i])) return false; return true; }
+bool all_finite_d(const double* v, size_t n) { for (size_t i = 0; i < n; ++i) if (!isfinite(v[i])) return false; return true; }
+
+// First per-instance command of the handle: its BetweenFactor measurements move from the shared row to one row per instance (dcmds_each,
+// 8 B N_max bytes), and the ticks the handle already has are broadcast into every row - they stay part of every instance's graph.
+int ensure_cmds_each(pgs_handle* h) {
+    if (h->p.cmd_stride) return SLAM_OK;
+    DevBuf<float> rows;
+    HIP_TRY(rows.reserve((size_t)h->B * h->N_max * 2));
+    HIP_TRY(slam::pgs_launch_put_cmds(h->p, rows, 2 * h->N_max, 0, h->timestep, h->dcmds, 2, 0, h->stream));
+    h->dcmds_each = std::move(rows);
+    h->p.cmds = h->dcmds_each; h->p.cmd_stride = 2 * h->N_max;
+    return SLAM_OK;
+}
+
+// The BetweenFactor measurements of the next T ticks (the caller has checked that they fit N_max).  each: src [T][B][2], one per instance
+// (moves the handle to per-instance rows first); else src [T][2], written for every instance.  src_dev: a device pointer read in the order
+// of the handle's stream; else a host array, staged - pageable, so a caller that returns to ITS caller synchronises the stream first.
+int put_commands(pgs_handle* h, const float* src, bool src_dev, int T, bool each) {
+    if (each) TRY(ensure_cmds_each(h));
+    const size_t n = 2 * (size_t)T * (each ? (size_t)h->B : 1);
+    if (!h->p.cmd_stride) {   // the shared row: straight into place
+        HIP_TRY(hipMemcpyAsync(h->dcmds + 2 * (size_t)h->timestep, src, sizeof(float) * n, src_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+        return SLAM_OK;
+    }
+    if (!src_dev) {
+        HIP_TRY(h->dcmd_stage.reserve(n));
+        HIP_TRY(hipMemcpyAsync(h->dcmd_stage, src, sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
+        src = h->dcmd_stage;
+    }
+    // per-instance rows: the [T][B][2] layout is transposed into them on the device; a shared command goes into every row
+    HIP_TRY(slam::pgs_launch_put_cmds(h->p, h->dcmds_each, h->p.cmd_stride, h->timestep, T, src, each ? 2 * h->B : 2, each ? 2 : 0, h->stream));
+    return SLAM_OK;
+}
+
+// updateNaiveVehPoseEstimate + update of one tick on device messages; the tick's commands are in place
+int append_tick(pgs_handle* h, const float* d_meas, const int32_t* d_count, int k_stride, const double* d_sec) {
+    h->p.N = h->timestep + 1;
+    HIP_TRY(slam::pgs_launch_append(h->p, d_meas, d_count, k_stride, d_sec, h->stream));
+    h->timestep += 1;
+    h->p.N = h->timestep + 1;
+    return SLAM_OK;
+}
+
+// host messages of one tick into the handle's staging buffers (pgs_update, pgs_update_each); *ks = the stride the append kernel gets
+int stage_messages(pgs_handle* h, const float* meas, const int32_t* count, int k_stride, const double* sec, int* ks) {
+    *ks = k_stride > 0 ? k_stride : 1;
+    HIP_TRY(h->dmeas.reserve((size_t)3 * *ks * h->B));
+    if (k_stride > 0) {
+        HIP_TRY(hipMemcpyAsync(h->dmeas, meas, sizeof(float) * 3 * (size_t)k_stride * h->B, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->dcount, count, sizeof(int32_t) * (size_t)h->B, hipMemcpyHostToDevice, h->stream));
+    } else {
+        HIP_TRY(hipMemsetAsync(h->dcount, 0, sizeof(int32_t) * (size_t)h->B, h->stream));
+    }
+    if (sec) HIP_TRY(hipMemcpyAsync(h->dsec, sec, sizeof(double) * 3 * (size_t)h->B, hipMemcpyHostToDevice, h->stream));
+    return SLAM_OK;
+}
+
+}  // namespace
+
+int pgs_init_each(pgs_handle* h, const float* pose0, const double* truth0) {
+    TRY(check(h));
+    if (!pose0) return fail(SLAM_ERR_ARG, "pose0 is NULL");
+    const size_t B = (size_t)h->B;
+    if (!all_finite_f(pose0, 3 * B) || (truth0 && !all_finite_d(truth0, 3 * B))) return fail(SLAM_ERR_ARG, "a start pose is not finite");
+    HIP_TRY(h->dpose_each.reserve(3 * B));
+    if (truth0) HIP_TRY(h->dtruth_each.reserve(3 * B));
+    HIP_TRY(hipMemcpyAsync(h->dpose_each, pose0, sizeof(float) * 3 * B, hipMemcpyHostToDevice, h->stream));
+    if (truth0) HIP_TRY(hipMemcpyAsync(h->dtruth_each, truth0, sizeof(double) * 3 * B, hipMemcpyHostToDevice, h->stream));
+    h->mg_valid = false;
+    h->timestep = 0; h->p.N = 1;
+    h->seg_cur = h->seg_len;
+    HIP_TRY(slam::pgs_launch_init_each(h->p, h->dpose_each, truth0 ? h->dtruth_each.get() : nullptr, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // the host arrays are pageable
     h->inited = true; h->solved = false;
     return SLAM_OK;
 }
@@ -321,40 +434,72 @@ int pgs_update_dev(pgs_handle* h, const float cmd[2], const float* d_meas, const
     if (!cmd) return fail(SLAM_ERR_ARG, "cmd is NULL");
     if (h->timestep + 1 >= h->N_max) return fail(SLAM_ERR_STATE, "pose capacity N_max = %d reached", h->N_max);
     h->mg_valid = false;
-    HIP_TRY(hipMemcpyAsync(h->dcmds + 2 * (size_t)h->timestep, cmd, sizeof(float) * 2, hipMemcpyHostToDevice, h->stream));
-    h->p.N = h->timestep + 1;
-    HIP_TRY(slam::pgs_launch_append(h->p, d_meas, d_count, k_stride, d_sec, h->stream));
-    h->timestep += 1;
-    h->p.N = h->timestep + 1;
-    return SLAM_OK;
+    TRY(put_commands(h, cmd, false, 1, false));
+    return append_tick(h, d_meas, d_count, k_stride, d_sec);
 }
 
 int pgs_update(pgs_handle* h, const float cmd[2], const float* meas, const int32_t* count, int k_stride, const double* sec) {
     TRY(check(h));
     if (k_stride < 0 || (k_stride > 0 && (!meas || !count))) return fail(SLAM_ERR_ARG, "bad measurement arguments");
-    const int ks = k_stride > 0 ? k_stride : 1;
-    HIP_TRY(h->dmeas.reserve((size_t)3 * ks * h->B));
-    if (k_stride > 0) {
-        HIP_TRY(hipMemcpyAsync(h->dmeas, meas, sizeof(float) * 3 * (size_t)k_stride * h->B, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->dcount, count, sizeof(int32_t) * (size_t)h->B, hipMemcpyHostToDevice, h->stream));
-    } else {
-        HIP_TRY(hipMemsetAsync(h->dcount, 0, sizeof(int32_t) * (size_t)h->B, h->stream));
-    }
-    if (sec) HIP_TRY(hipMemcpyAsync(h->dsec, sec, sizeof(double) * 3 * (size_t)h->B, hipMemcpyHostToDevice, h->stream));
+    int ks = 1;
+    TRY(stage_messages(h, meas, count, k_stride, sec, &ks));
     const int rc = pgs_update_dev(h, cmd, h->dmeas, h->dcount, ks, sec ? h->dsec : nullptr);
     // the staging buffers are reused by the next call and the host arrays are pageable: finish the copies now
     HIP_TRY(hipStreamSynchronize(h->stream));
     return rc;
 }
 
+int pgs_update_each_dev(pgs_handle* h, const float* d_cmds, const float* d_meas, const int32_t* d_count, int k_stride, const double* d_sec) {
+    TRY(check(h));
+    if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_update_each");
+    if (!d_cmds) return fail(SLAM_ERR_ARG, "cmds is NULL");
+    if (h->timestep + 1 >= h->N_max) return fail(SLAM_ERR_STATE, "pose capacity N_max = %d reached", h->N_max);
+    TRY(put_commands(h, d_cmds, true, 1, true));
+    h->mg_valid = false;
+    return append_tick(h, d_meas, d_count, k_stride, d_sec);
+}
+
+int pgs_update_each(pgs_handle* h, const float* cmds, const float* meas, const int32_t* count, int k_stride, const double* sec) {
+    TRY(check(h));
+    if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_update_each");
+    if (!cmds) return fail(SLAM_ERR_ARG, "cmds is NULL");
+    if (k_stride < 0 || (k_stride > 0 && (!meas || !count))) return fail(SLAM_ERR_ARG, "bad measurement arguments");
+    if (!all_finite_f(cmds, 2 * (size_t)h->B)) return fail(SLAM_ERR_ARG, "a command is not finite");
+    if (h->timestep + 1 >= h->N_max) return fail(SLAM_ERR_STATE, "pose capacity N_max = %d reached", h->N_max);
+    TRY(put_commands(h, cmds, false, 1, true));
+    h->mg_valid = false;
+    int ks = 1;
+    TRY(stage_messages(h, meas, count, k_stride, sec, &ks));
+    const int rc = append_tick(h, h->dmeas, h->dcount, ks, sec ? h->dsec : nullptr);
+    HIP_TRY(hipStreamSynchronize(h->stream));   // as pgs_update: the staging buffers are free for the next call
+    return rc;
+}
+
 int pgs_run_sim(pgs_handle* h, const float* cmds, int T) {
     TRY(check(h));
     if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_run_sim");
-    if (!h->p.map) return fail(SLAM_ERR_STATE, "pgs_set_map must be called before pgs_run_sim");
+    if (!h->p.map && !h->p.map_each) return fail(SLAM_ERR_STATE, "pgs_set_map must be called before pgs_run_sim");
     if (!cmds || T <= 0) return fail(SLAM_ERR_ARG, "bad command sequence");
     if (h->timestep + T >= h->N_max) return fail(SLAM_ERR_STATE, "timestep %d + %d commands exceed the pose capacity N_max = %d", h->timestep, T, h->N_max);
     h->mg_valid = false;
-    HIP_TRY(hipMemcpyAsync(h->dcmds + 2 * (size_t)h->timestep, cmds, sizeof(float) * 2 * (size_t)T, hipMemcpyHostToDevice, h->stream));
+    TRY(put_commands(h, cmds, false, T, false));
+    h->p.N = h->timestep + 1;
+    HIP_TRY(slam::pgs_launch_run_sim(h->p, T, (uint32_t)h->timestep, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // cmds is a pageable host array
+    h->timestep += T;
+    h->p.N = h->timestep + 1;
+    return SLAM_OK;
+}
+
+int pgs_run_sim_each(pgs_handle* h, const float* cmds, int T) {
+    TRY(check(h));
+    if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_run_sim_each");
+    if (!h->p.map && !h->p.map_each) return fail(SLAM_ERR_STATE, "pgs_set_map or pgs_set_maps must be called before pgs_run_sim_each");
+    if (!cmds || T <= 0) return fail(SLAM_ERR_ARG, "bad command sequence");
+    if (!all_finite_f(cmds, 2 * (size_t)T * h->B)) return fail(SLAM_ERR_ARG, "a command is not finite");
+    if (h->timestep + T >= h->N_max) return fail(SLAM_ERR_STATE, "timestep %d + %d commands exceed the pose capacity N_max = %d", h->timestep, T, h->N_max);
+    TRY(put_commands(h, cmds, false, T, true));   // one copy and one transposing launch for the T ticks
+    h->mg_valid = false;
     h->p.N = h->timestep + 1;
     HIP_TRY(slam::pgs_launch_run_sim(h->p, T, (uint32_t)h->timestep, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));   // cmds is a pageable host array
@@ -722,15 +867,41 @@ int pgs_adopt_result(pgs_handle* h) {
 
 // solve_graph_every_iteration with the simulator on the device: T x { get_cmd + NaiveFilter + graph append (one tick of pgs_run_sim),
 // pgs_solve, pgs_adopt_result }.  SLAM_PGS_ITER_PROF=1: the host clock per phase with a stream synchronisation after each (phase table only).
+namespace {
+int run_every_iteration(pgs_handle* h, int T, int32_t* counts);
+}
+
 int pgs_run_sim_every_iteration(pgs_handle* h, const float* cmds, int T, int32_t* counts) {
     TRY(check(h));
     if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_run_sim_every_iteration");
-    if (!h->p.map) return fail(SLAM_ERR_STATE, "pgs_set_map must be called before pgs_run_sim_every_iteration");
+    if (!h->p.map && !h->p.map_each) return fail(SLAM_ERR_STATE, "pgs_set_map must be called before pgs_run_sim_every_iteration");
     if (!cmds || T <= 0) return fail(SLAM_ERR_ARG, "bad command sequence");
     if (h->timestep + T >= h->N_max) return fail(SLAM_ERR_STATE, "timestep %d + %d commands exceed the pose capacity N_max = %d", h->timestep, T, h->N_max);
     h->mg_valid = false;
-    HIP_TRY(hipMemcpyAsync(h->dcmds + 2 * (size_t)h->timestep, cmds, sizeof(float) * 2 * (size_t)T, hipMemcpyHostToDevice, h->stream));
+    TRY(put_commands(h, cmds, false, T, false));
     HIP_TRY(hipStreamSynchronize(h->stream));   // cmds is a pageable host array
+    return run_every_iteration(h, T, counts);
+}
+
+// The same with one command per instance and tick, cmds [T][batch][2]: the commands of all T ticks go to the device at once, the ticks keep
+// their structure.
+int pgs_run_sim_every_iteration_each(pgs_handle* h, const float* cmds, int T, int32_t* counts) {
+    TRY(check(h));
+    if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_run_sim_every_iteration_each");
+    if (!h->p.map && !h->p.map_each) return fail(SLAM_ERR_STATE, "pgs_set_map or pgs_set_maps must be called before pgs_run_sim_every_iteration_each");
+    if (!cmds || T <= 0) return fail(SLAM_ERR_ARG, "bad command sequence");
+    if (!all_finite_f(cmds, 2 * (size_t)T * h->B)) return fail(SLAM_ERR_ARG, "a command is not finite");
+    if (h->timestep + T >= h->N_max) return fail(SLAM_ERR_STATE, "timestep %d + %d commands exceed the pose capacity N_max = %d", h->timestep, T, h->N_max);
+    TRY(put_commands(h, cmds, false, T, true));
+    h->mg_valid = false;
+    HIP_TRY(hipStreamSynchronize(h->stream));   // cmds is a pageable host array
+    return run_every_iteration(h, T, counts);
+}
+
+namespace {
+
+// the T ticks of pgs_run_sim_every_iteration[_each]; their commands are in place
+int run_every_iteration(pgs_handle* h, int T, int32_t* counts) {
     HIP_TRY(h->d_tick.reserve((size_t)h->B * 2));
     HIP_TRY(h->d_tick_flop.reserve((size_t)h->B * 2));
     HIP_TRY(hipMemsetAsync(h->d_tick, 0, sizeof(int32_t) * 2 * (size_t)h->B, h->stream));
@@ -767,6 +938,9 @@ int pgs_run_sim_every_iteration(pgs_handle* h, const float* cmds, int T, int32_t
     if (h->host_prof) fprintf(stderr, "pgs host clock over the run's trials: %.0f ms enqueuing, %.0f ms waiting for the trials' counters\n", h->host_launch_ms, h->host_wait_ms);
     return SLAM_OK;
 }
+
+}  // namespace
+
 // Host-clock phase times of the last pgs_run_sim_every_iteration under SLAM_PGS_ITER_PROF=1: ms in {simulator + append, solve, adopt}, and the
 // LM trials launched over all ticks.
 int pgs_last_iter_phases(pgs_handle* h, double ms[6]) {

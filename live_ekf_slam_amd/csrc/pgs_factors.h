@@ -7,13 +7,13 @@ typedef double dbl4_t __attribute__((ext_vector_type(4)));
 // ------------------------------------------------------------------------------------------------------------
 // factors (whitened residuals / Jacobians); same formulas as the oracle, see there for the GTSAM definitions
 // ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void prior_factor(const PgsParams& p, const double* ps, double e[3]) {
+__device__ __forceinline__ void prior_factor(const PgsParams& p, const double* prior, const double* ps, double e[3]) {
     double s, c;
     det_sincos(ps[2], &s, &c);
-    const double dx = p.prior[0] - ps[0], dy = p.prior[1] - ps[1];
+    const double dx = prior[0] - ps[0], dy = prior[1] - ps[1];
     e[0] = -(c * dx + s * dy) * p.w_prior[0];
     e[1] = -(-s * dx + c * dy) * p.w_prior[1];
-    e[2] = -remainder(p.prior[2] - ps[2], kTwoPi) * p.w_prior[2];
+    e[2] = -remainder(prior[2] - ps[2], kTwoPi) * p.w_prior[2];
 }
 
 template <bool JAC>
@@ -60,12 +60,17 @@ __device__ __forceinline__ void bearing_range_factor(const PgsParams& p, const d
     }
 }
 
-// per-instance views
+// per-instance views of slot b: its own copy of the graph arrays, and the inputs of the instance it belongs to (slot j B + instance)
 struct Inst {
     const int32_t* cnt; const int32_t* mlm; const double* mb; const double* mr;
+    const float* cmds;      // BetweenFactor measurement of pose i at cmds[2 i] (the shared row while cmd_stride = 0)
+    const double* prior;    // mean of the PriorFactor
 };
 __device__ __forceinline__ Inst inst_view(const PgsParams& p, int b) {
     Inst v;
+    const size_t inst = (size_t)((unsigned)b % (unsigned)p.B);
+    v.cmds = p.cmds + inst * p.cmd_stride;
+    v.prior = p.prior + 3 * inst;
     v.cnt = p.cnt + (size_t)b * p.N_max;
     v.mlm = p.mlm + (size_t)b * p.N_max * p.KP;
     v.mb = p.mb + (size_t)b * p.N_max * p.KP;
@@ -92,11 +97,11 @@ __device__ __forceinline__ double block_sum(double v, double* s_buf) {
 __device__ __forceinline__ double pose_cost(const PgsParams& p, const Inst& g, const double* pose, const double* lm, int i, int N) {
     double acc = 0.0, e[3];
     if (i == 0) {
-        prior_factor(p, pose, e);
+        prior_factor(p, g.prior, pose, e);
         acc = acc + 0.5 * ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
     }
     if (i + 1 < N) {
-        between_factor<false>(p, pose + 3 * i, pose + 3 * (i + 1), p.cmds[2 * i], p.cmds[2 * i + 1], e, nullptr);
+        between_factor<false>(p, pose + 3 * i, pose + 3 * (i + 1), g.cmds[2 * i], g.cmds[2 * i + 1], e, nullptr);
         acc = acc + 0.5 * ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
     }
     const int kc = g.cnt[i];

@@ -13,10 +13,39 @@ __global__ void pgs_init_kernel(const PgsParams p, double x0, double y0, double 
     ps[0] = x0; ps[1] = y0; ps[2] = yaw0;
     p.cur[3 * b] = x0; p.cur[3 * b + 1] = y0; p.cur[3 * b + 2] = yaw0;
     p.truth[3 * b] = x0; p.truth[3 * b + 1] = y0; p.truth[3 * b + 2] = yaw0;
+    p.prior[3 * b] = x0; p.prior[3 * b + 1] = y0; p.prior[3 * b + 2] = yaw0;   // PriorFactor(key(0), Pose2(x_0, y_0, yaw_0)) :84
     p.M[b] = 0; p.flags[b] = 0;
     p.cnt[(size_t)b * p.N_max] = 0;
     p.state[b] = 1; p.iters[b] = 0; p.trials[b] = 0;
     p.error[b] = 0.0; p.err_init[b] = 0.0; p.lambda[b] = 0.0;
+}
+
+// PoseGraph::init of every instance with its own arguments (pgs_init_each): pose0 [B][3] float32 as pgs_init's, truth0 [B][3] the
+// simulator's true start pose (NULL: pose0 widened, what pgs_init_kernel does with its arguments)
+__global__ void pgs_init_each_kernel(const PgsParams p, const float* pose0, const double* truth0) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= p.B) return;
+    const double x0 = (double)pose0[3 * b], y0 = (double)pose0[3 * b + 1], yaw0 = (double)pose0[3 * b + 2];
+    double* ps = p.pose0 + (size_t)b * p.N_max * 3;
+    ps[0] = x0; ps[1] = y0; ps[2] = yaw0;
+    p.cur[3 * b] = x0; p.cur[3 * b + 1] = y0; p.cur[3 * b + 2] = yaw0;
+    p.truth[3 * b] = truth0 ? truth0[3 * b] : x0; p.truth[3 * b + 1] = truth0 ? truth0[3 * b + 1] : y0; p.truth[3 * b + 2] = truth0 ? truth0[3 * b + 2] : yaw0;
+    p.prior[3 * b] = x0; p.prior[3 * b + 1] = y0; p.prior[3 * b + 2] = yaw0;
+    p.M[b] = 0; p.flags[b] = 0;
+    p.cnt[(size_t)b * p.N_max] = 0;
+    p.state[b] = 1; p.iters[b] = 0; p.trials[b] = 0;
+    p.error[b] = 0.0; p.err_init[b] = 0.0; p.lambda[b] = 0.0;
+}
+
+// BetweenFactor measurements of the poses [i0, i0 + T) into the rows of dst (pgs_kernel.h: pgs_launch_put_cmds): one thread per
+// (row, tick); rows = B, or 1 for the shared row (dst_stride = 0)
+__global__ void pgs_put_cmds_kernel(float* dst, int dst_stride, int rows, int i0, int T, const float* src, int src_t, int src_b) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= rows * T) return;
+    const int b = idx / T, t = idx - b * T;
+    const float* s = src + (size_t)t * src_t + (size_t)b * src_b;
+    float* d = dst + (size_t)b * dst_stride + 2 * (size_t)(i0 + t);
+    d[0] = s[0]; d[1] = s[1];
 }
 
 // The graph-building half of PoseGraph::update for ONE instance (pose_graph.cpp:216-256): pose node t1 from the
@@ -90,13 +119,16 @@ __global__ __launch_bounds__(64) void pgs_run_sim_kernel(const PgsParams p, int 
     const int b = blockIdx.x, lane = threadIdx.x;
     double tx = p.truth[3 * b], ty = p.truth[3 * b + 1], tth = p.truth[3 * b + 2];
     double lmx = 0.0, lmy = 0.0;
-    if (lane < p.L) { lmx = p.map[2 * lane]; lmy = p.map[2 * lane + 1]; }
+    const double* map = sim_map(p, b);   // the instance's own map (pgs_set_maps) or the shared one
+    const int Lm = sim_map_size(p, b);
+    const float* cmds = p.cmds + (size_t)b * p.cmd_stride;
+    if (lane < Lm) { lmx = map[2 * lane]; lmy = map[2 * lane + 1]; }
 #pragma unroll 1
     for (int t = 0; t < T; ++t) {
         const int i = p.N - 1 + t, t1 = i + 1;
         if (t1 >= p.N_max) { if (lane == 0) p.flags[b] |= PGS_FLAG_POSE_CAP; break; }
-        const float fwd = p.cmds[2 * i], ang = p.cmds[2 * i + 1];
-        int k = sim_wave<KCAP>(p, b, lane, fwd, ang, step0 + (uint32_t)t, p.map, p.L, tx, ty, tth, lmx, lmy, s_meas);
+        const float fwd = cmds[2 * i], ang = cmds[2 * i + 1];
+        int k = sim_wave<KCAP>(p, b, lane, fwd, ang, step0 + (uint32_t)t, map, Lm, tx, ty, tth, lmx, lmy, s_meas);
         if (k > KCAP) { k = KCAP; if (lane == 0) p.flags[b] |= PGS_FLAG_MEAS_CAP; }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         if (lane == 0) {

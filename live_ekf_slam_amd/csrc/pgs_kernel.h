@@ -11,6 +11,8 @@ enum { PGS_FLAG_POSE_CAP = 1, PGS_FLAG_LM_CAP = 2, PGS_FLAG_MEAS_CAP = 4, PGS_FL
 static constexpr int kPgsFirstBit = 1 << 30;   // mlm: this factor is the first detection of its landmark
 
 // One workgroup per instance in every kernel; instance b owns slab b of every array (strides in elements).
+// Per-instance inputs (pgs_*_each, slam_pgs.h "heterogeneous batches"): the BetweenFactor measurements, the PriorFactor mean and the
+// simulator's map are INPUTS of an instance, not LM state - the lambda lanes of instance b (slots j B + b) read row b of them (inst_view).
 struct PgsParams {
     int32_t B, N_max, L_max, KP, LD;   // LD = leading dimension of Y / S = roundup(2*L_max + 1, 64)
     int32_t N;                         // poses in the graph now (timestep + 1), the same for every instance
@@ -28,12 +30,14 @@ struct PgsParams {
     int32_t* lm_last;                  // [B][L_max]      newest factor slot of landmark j
     int32_t* lm_first;                 // [B][L_max]      pose index of the first detection of landmark j
     double* mb; double* mr;            // [B][N_max*KP]   measured bearing / range (float32 wire values widened)
-    const float* cmds;                 // [N_max][2]      BetweenFactor measurements Pose2(fwd, 0, ang), shared
+    const float* cmds;                 // BetweenFactor measurements Pose2(fwd, 0, ang) of pose i of instance b at cmds[b * cmd_stride + 2 i]:
+    int32_t cmd_stride;                //   [N_max][2] shared, cmd_stride = 0 (the handle has seen shared calls only), or [B][N_max][2], cmd_stride = 2 N_max
     double* cur;                       // [B][3]          cur_veh_pose_estimate (secondary filter's pose)
     // ---- simulator (pgs_run_sim) ----
     double* truth;                     // [B][3]
     double* truth_hist;                // [B][N_max][2]   true (x, y) after step t at row t-1
-    const double* map; int32_t L;
+    const double* map; int32_t L;      // the true map, shared ...
+    const double* map_each; const int32_t* L_each; int32_t map_stride;   // ... or one per instance (pgs_set_maps) as in EkfStepParams, NULL = `map` (sim_map)
     double sV00, sV11, sW00, sW11, d_max, th_max, range_max, fov_min, fov_max;
     uint64_t seed; int64_t inst0;
     // ---- LM work space ----
@@ -128,7 +132,7 @@ struct PgsParams {
     double* tick_flop;                 // optional [B][2]: ... and the algorithmic FLOP of its trials: Schur-complement SYRK (inst_flop) | dense Cholesky + substitutions (n^3/3 + 2 n^2, n = 2 M)
     unsigned long long* prof;          // optional [B][8] phase timers of the chol kernel (100 MHz wall clock), debug only
     // ---- factor constants ----
-    double prior[3];
+    double* prior;                     // [B][3] mean of the PriorFactor of instance b (pgs_init_kernel / pgs_init_each_kernel)
     double w_prior[3], w_btw[3], w_meas[2];   // 1 / sigma
 };
 
@@ -140,7 +144,13 @@ __host__ __device__ inline int seg_nb1(int L_max) { return 4 * ((L_max + 63) / 6
                                                                                                // the right-hand-side row, landmark index M <= L_max, has an end too)
 
 hipError_t pgs_launch_init(const PgsParams& p, float x0, float y0, float yaw0, hipStream_t s);
-// append one timestep: BetweenFactor is implied by cmds[t]; meas [B][k_stride][3], count [B] (device); sec_pose [B][3]
+// PoseGraph::init per instance: pose0 [B][3] float32, truth0 [B][3] (the simulator's true start pose) or NULL = pose0 widened; device pointers
+hipError_t pgs_launch_init_each(const PgsParams& p, const float* d_pose0, const double* d_truth0, hipStream_t s);
+// BetweenFactor measurements of the poses [i0, i0 + T) into dst (row stride dst_stride floats, 0 = one shared row written once):
+// dst[b * dst_stride + 2 (i0 + t) + c] = src[t * src_t + b * src_b + c].  src_b = 0 broadcasts a shared sequence (src_t = 2) into every row;
+// src_t = 2 B, src_b = 2 transposes the [T][B][2] layout of the _each calls.  The caller guarantees i0 + T <= N_max.
+hipError_t pgs_launch_put_cmds(const PgsParams& p, float* dst, int dst_stride, int i0, int T, const float* src, int src_t, int src_b, hipStream_t s);
+// append one timestep: BetweenFactor is implied by the instance's cmds[t]; meas [B][k_stride][3], count [B] (device); sec_pose [B][3]
 // (device) or NULL to keep `cur`.  p.N = number of poses BEFORE the call.
 hipError_t pgs_launch_append(const PgsParams& p, const float* d_meas, const int32_t* d_count, int k_stride, const double* d_sec, hipStream_t s);
 // T timesteps of simulator + NaiveFilter secondary + append, on the device (cmds already in p.cmds)

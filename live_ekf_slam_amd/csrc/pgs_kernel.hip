@@ -1,5 +1,5 @@
 // pgs_kernel.hip — batched pose-graph SLAM for gfx950 (MI355X): graph building + Levenberg–Marquardt solve of B
-// independent graphs (Monte-Carlo instances over one map / command sequence), one workgroup per instance.
+// independent graphs (Monte-Carlo instances over one map / command sequence, or each with its own: pgs_*_each), one workgroup per instance.
 //
 // Reference path: PoseGraph::{init, updateNaiveVehPoseEstimate, update, onLandmarkMeasurement, solvePoseGraph}
 // (ekf_ws/src/localization_pkg/src/pose_graph.cpp:68-300) with `implementation: gtsam` (params.yaml:61).  The solve
@@ -46,6 +46,18 @@ namespace {
 
 hipError_t pgs_launch_init(const PgsParams& p, float x0, float y0, float yaw0, hipStream_t s) {
     hipLaunchKernelGGL(pgs_init_kernel, dim3((p.B + 255) / 256), dim3(256), 0, s, p, (double)x0, (double)y0, (double)yaw0);
+    return hipGetLastError();
+}
+
+hipError_t pgs_launch_init_each(const PgsParams& p, const float* d_pose0, const double* d_truth0, hipStream_t s) {
+    hipLaunchKernelGGL(pgs_init_each_kernel, dim3((p.B + 255) / 256), dim3(256), 0, s, p, d_pose0, d_truth0);
+    return hipGetLastError();
+}
+
+hipError_t pgs_launch_put_cmds(const PgsParams& p, float* dst, int dst_stride, int i0, int T, const float* src, int src_t, int src_b, hipStream_t s) {
+    const int rows = dst_stride ? p.B : 1;
+    if (T <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pgs_put_cmds_kernel, dim3((unsigned)(((size_t)rows * T + 255) / 256)), dim3(256), 0, s, dst, dst_stride, rows, i0, T, src, src_t, src_b);
     return hipGetLastError();
 }
 

@@ -209,12 +209,12 @@ __global__ __launch_bounds__(TPB) void pgs_linearize_kernel(const PgsParams p) {
     for (int i = tid; i < N; i += TPB) {
         double A[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, gg[3] = {0, 0, 0}, e[3], J1[9];
         if (i == 0) {
-            prior_factor(p, pose, e);
+            prior_factor(p, g.prior, pose, e);
 #pragma unroll
             for (int k = 0; k < 3; ++k) { A[4 * k] += p.w_prior[k] * p.w_prior[k]; gg[k] += -e[k] * p.w_prior[k]; }
         }
         if (i > 0) {   // between (i-1, i): J2 = diag(w); H[i][i-1] = J2^T J1
-            between_factor<true>(p, pose + 3 * (i - 1), pose + 3 * i, p.cmds[2 * (i - 1)], p.cmds[2 * (i - 1) + 1], e, J1);
+            between_factor<true>(p, pose + 3 * (i - 1), pose + 3 * i, g.cmds[2 * (i - 1)], g.cmds[2 * (i - 1) + 1], e, J1);
 #pragma unroll
             for (int k = 0; k < 3; ++k) { A[4 * k] += p.w_btw[k] * p.w_btw[k]; gg[k] += -e[k] * p.w_btw[k]; }
             double* C = Cb + 9 * (i - 1);
@@ -224,7 +224,7 @@ __global__ __launch_bounds__(TPB) void pgs_linearize_kernel(const PgsParams p) {
                 for (int c = 0; c < 3; ++c) C[3 * a + c] = p.w_btw[a] * J1[3 * a + c];
         }
         if (i + 1 < N) {   // between (i, i+1): J1
-            between_factor<true>(p, pose + 3 * i, pose + 3 * (i + 1), p.cmds[2 * i], p.cmds[2 * i + 1], e, J1);
+            between_factor<true>(p, pose + 3 * i, pose + 3 * (i + 1), g.cmds[2 * i], g.cmds[2 * i + 1], e, J1);
             add_JtJ<3>(A, J1);
 #pragma unroll
             for (int a = 0; a < 3; ++a) gg[a] += -(J1[a] * e[0] + J1[3 + a] * e[1] + J1[6 + a] * e[2]);

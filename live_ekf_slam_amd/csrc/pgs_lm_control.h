@@ -73,12 +73,12 @@ __global__ __launch_bounds__(TPB) void pgs_evaluate_kernel(const PgsParams p) {
         for (int i = tid; i < N; i += TPB) {   // 0.5 |J delta + e|^2 of the UNDAMPED linearisation
             double e[3], J1[9];
             if (i == 0) {
-                prior_factor(p, pose, e);
+                prior_factor(p, g.prior, pose, e);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) { const double v = e[k] + p.w_prior[k] * dp[k]; acc = acc + 0.5 * v * v; }
             }
             if (i + 1 < N) {
-                between_factor<true>(p, pose + 3 * i, pose + 3 * (i + 1), p.cmds[2 * i], p.cmds[2 * i + 1], e, J1);
+                between_factor<true>(p, pose + 3 * i, pose + 3 * (i + 1), g.cmds[2 * i], g.cmds[2 * i + 1], e, J1);
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {
                     const double v = (e[r] + ((J1[3 * r] * dp[3 * i] + J1[3 * r + 1] * dp[3 * i + 1]) + J1[3 * r + 2] * dp[3 * i + 2])) + p.w_btw[r] * dp[3 * (i + 1) + r];
@@ -109,11 +109,11 @@ __global__ __launch_bounds__(TPB) void pgs_evaluate_kernel(const PgsParams p) {
         for (int i = tid; i < N; i += TPB) {
             double e[3], pc = 0.0;   // pose_cost's own accumulator: the pose's terms are summed first, then added to the thread's
             if (i == 0) {
-                prior_factor(p, pose_n, e);
+                prior_factor(p, g.prior, pose_n, e);
                 pc = pc + 0.5 * ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
             }
             if (i + 1 < N) {
-                between_factor<false>(p, pose_n + 3 * i, pose_n + 3 * (i + 1), p.cmds[2 * i], p.cmds[2 * i + 1], e, nullptr);
+                between_factor<false>(p, pose_n + 3 * i, pose_n + 3 * (i + 1), g.cmds[2 * i], g.cmds[2 * i + 1], e, nullptr);
                 pc = pc + 0.5 * ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
             }
             const int kc = g.cnt[i];

@@ -108,11 +108,47 @@ class BatchedPoseGraph:
             raise _lib.SlamError("readParams() must be called before using the filter")
 
     # -- PoseGraph::init (pose_graph.cpp:68-95) --
-    def init(self, x_0=0.0, y_0=0.0, yaw_0=0.0):
+    def init(self, x_0=0.0, y_0=0.0, yaw_0=0.0, truth0=None):
+        """Scalars: one start pose for the batch.  x_0 a (batch, 3) array of (x, y, yaw): one per instance (pgs_init_each; y_0 and
+        yaw_0 are then ignored).  truth0: optional (batch, 3) true start poses of the simulator (default: the start poses)."""
         self._need()
-        _lib.check(_lib.lib().pgs_init(self.h, x_0, y_0, yaw_0))
+        if np.ndim(x_0) == 0 and truth0 is None:
+            _lib.check(_lib.lib().pgs_init(self.h, x_0, y_0, yaw_0))
+        else:
+            pose = (np.asarray(x_0, dtype=np.float32) if np.ndim(x_0) else
+                    np.broadcast_to(np.array([x_0, y_0, yaw_0], dtype=np.float32), (self.batch, 3)))
+            pose = np.ascontiguousarray(self._rows(pose, "x_0", 3), dtype=np.float32)
+            tr = None if truth0 is None else np.ascontiguousarray(self._rows(np.asarray(truth0, dtype=np.float64), "truth0", 3))
+            _lib.check(_lib.lib().pgs_init_each(self.h, _f(pose), None if tr is None else _d(tr)))
         self.isInit, self.solved_pose_graph, self.timestep = True, False, 0
         self._sec = None
+
+    def _rows(self, a, what, width):
+        if a.shape != (self.batch, width):
+            raise ValueError(f"{what}: expected shape ({self.batch}, {width}), got {a.shape}")
+        return a
+
+    def _cmd(self, cmdMsg):
+        """(2,) float32 for one command, (batch, 2) for one per instance."""
+        if isinstance(cmdMsg, Command):
+            return np.array([cmdMsg.fwd, cmdMsg.ang], dtype=np.float32)
+        c = np.ascontiguousarray(cmdMsg, dtype=np.float32)
+        if c.shape == (self.batch, 2):
+            return c
+        if c.size == 2:
+            return c.reshape(2)
+        raise ValueError(f"expected a command of shape (2,) or ({self.batch}, 2), got {c.shape}")
+
+    def _cmds(self, cmds):
+        """(T, 2) float32 for the batch (a flat list of 2 T numbers too), (T, batch, 2) per instance."""
+        c = np.ascontiguousarray(cmds, dtype=np.float32)
+        if c.ndim == 3:
+            if c.shape[0] == 0 or c.shape[1:] != (self.batch, 2):
+                raise ValueError(f"per-instance commands: expected shape (T > 0, {self.batch}, 2), got {c.shape}")
+            return c
+        if c.size == 0 or c.ndim > 2 or (c.ndim == 2 and c.shape[1] != 2) or c.size % 2:
+            raise ValueError(f"expected commands of shape (T, 2) or (T, {self.batch}, 2), got {c.shape}")
+        return c.reshape(-1, 2)
 
     def set_stream(self, ptr):
         self._need(); _lib.check(_lib.lib().pgs_set_stream(self.h, C.c_void_p(ptr)))
@@ -123,10 +159,22 @@ class BatchedPoseGraph:
     def set_instance_offset(self, first):
         self._need(); _lib.check(_lib.lib().pgs_set_instance_offset(self.h, int(first)))
 
-    def set_map(self, map_xy):
+    def set_map(self, map_xy, counts=None):
+        """The simulator's true map [L][2] for every instance, or one per instance (pgs_set_maps): a (batch, L_stride, 2) array with
+        `counts` [batch] landmarks each (default: all L_stride)."""
         self._need()
         m = np.ascontiguousarray(map_xy, dtype=np.float64)
-        _lib.check(_lib.lib().pgs_set_map(self.h, _d(m), m.shape[0]))
+        if m.ndim == 2 and counts is None:
+            if m.shape[1] != 2 or m.shape[0] == 0:
+                raise ValueError(f"expected a map of shape (L > 0, 2), got {m.shape}")
+            _lib.check(_lib.lib().pgs_set_map(self.h, _d(m), m.shape[0]))
+            return
+        if m.ndim != 3 or m.shape[0] != self.batch or m.shape[2] != 2 or not 0 < m.shape[1] <= 255:
+            raise ValueError(f"expected per-instance maps of shape ({self.batch}, 0 < L_stride <= 255, 2), got {m.shape}")
+        cnt = np.full(self.batch, m.shape[1], np.int32) if counts is None else np.ascontiguousarray(counts, dtype=np.int32)
+        if cnt.shape != (self.batch,) or np.any(cnt <= 0) or np.any(cnt > m.shape[1]):
+            raise ValueError(f"counts: expected {self.batch} landmark counts in [1, {m.shape[1]}]")
+        _lib.check(_lib.lib().pgs_set_maps(self.h, _d(m), _i(cnt), m.shape[1]))
 
     # -- PoseGraph::updateNaiveVehPoseEstimate (pose_graph.cpp:97-119) --
     def updateNaiveVehPoseEstimate(self, state_vector, landmark_ids=None):
@@ -138,6 +186,7 @@ class BatchedPoseGraph:
 
     # -- PoseGraph::update (pose_graph.cpp:199-267) --
     def update(self, cmdMsg, lmMeasMsg, meas_count=None):
+        """cmdMsg: Command or (fwd, ang) for the batch, or a (batch, 2) array with one command per instance (pgs_update_each)."""
         self._need()
         if not self.isInit:
             raise _lib.SlamError("init() must be called before update()")
@@ -146,7 +195,7 @@ class BatchedPoseGraph:
         if self.timestep + 1 >= self.num_iterations_total:    # :208-214
             self.solvePoseGraph()
             return
-        cmd = np.array([cmdMsg.fwd, cmdMsg.ang], dtype=np.float32) if isinstance(cmdMsg, Command) else np.ascontiguousarray(cmdMsg, dtype=np.float32).reshape(2)
+        cmd = self._cmd(cmdMsg)
         meas = np.asarray(lmMeasMsg, dtype=np.float32)
         if meas.ndim <= 2 and meas_count is None:             # one message for all instances
             one = meas.reshape(-1, 3)
@@ -155,29 +204,34 @@ class BatchedPoseGraph:
             meas_count = np.full(self.batch, k, dtype=np.int32)
         meas = np.ascontiguousarray(meas.reshape(self.batch, -1, 3), dtype=np.float32)
         cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
+        if cnt.shape != (self.batch,):
+            raise ValueError(f"meas_count: expected shape ({self.batch},), got {cnt.shape}")
         ks = meas.shape[1]
         sec = self._sec
-        _lib.check(_lib.lib().pgs_update(self.h, _f(cmd), _f(meas) if ks else None, _i(cnt) if ks else None, ks,
-                                         _d(sec) if sec is not None else None))
+        step = _lib.lib().pgs_update_each if cmd.ndim == 2 else _lib.lib().pgs_update
+        _lib.check(step(self.h, _f(cmd), _f(meas) if ks else None, _i(cnt) if ks else None, ks, _d(sec) if sec is not None else None))
         self.timestep += 1
         if self.solve_graph_every_iteration:                  # :258-264
             self.solvePoseGraph()
             _lib.check(_lib.lib().pgs_adopt_result(self.h))
 
     def run_sim(self, cmds):
-        """All of `cmds` with the device-side measurement generator and the NaiveFilter as the secondary filter."""
+        """All of `cmds` with the device-side measurement generator and the NaiveFilter as the secondary filter; cmds (T, 2) for the
+        batch, or (T, batch, 2) per instance (pgs_run_sim_each)."""
         self._need()
-        c = np.ascontiguousarray(cmds, dtype=np.float32).reshape(-1, 2)
-        _lib.check(_lib.lib().pgs_run_sim(self.h, _f(c), c.shape[0]))
+        c = self._cmds(cmds)
+        _lib.check((_lib.lib().pgs_run_sim_each if c.ndim == 3 else _lib.lib().pgs_run_sim)(self.h, _f(c), c.shape[0]))
         self.timestep += c.shape[0]
 
     def run_sim_every_iteration(self, cmds):
         """solve_graph_every_iteration (params.yaml:64; pose_graph.cpp:258-264) with the simulator on the device: per command one tick of
-        run_sim, solvePoseGraph, initial_estimate = result.  Returns [batch][2]: LM iterations / lambda trials summed over the ticks."""
+        run_sim, solvePoseGraph, initial_estimate = result.  cmds (T, 2), or (T, batch, 2) per instance.  Returns [batch][2]: LM
+        iterations / lambda trials summed over the ticks."""
         self._need()
-        c = np.ascontiguousarray(cmds, dtype=np.float32).reshape(-1, 2)
+        c = self._cmds(cmds)
         counts = np.zeros((self.batch, 2), dtype=np.int32)
-        _lib.check(_lib.lib().pgs_run_sim_every_iteration(self.h, _f(c), c.shape[0], _i(counts)))
+        run = _lib.lib().pgs_run_sim_every_iteration_each if c.ndim == 3 else _lib.lib().pgs_run_sim_every_iteration
+        _lib.check(run(self.h, _f(c), c.shape[0], _i(counts)))
         self.timestep += c.shape[0]
         self.solved_pose_graph = True
         return counts
