@@ -273,8 +273,8 @@ int slam_status(slam_handle* h, int32_t* per_instance_flags);       /* [batch] s
  * Errors: SLAM_ERR_STATE before slam_init or without a true map, SLAM_ERR_UNSUPPORTED for the UKF kinds.
  * Not covered: the UKF kinds (their state carries (cos yaw, sin yaw), so P is rank-deficient along the unit circle by construction and
  *   indefinite in most steps of the benchmark scenario: a NEES there needs a definition first), slam_multi_* gathers, the pose graph
- *   (slam_pgs.h has pgs_marginals), accumulation of the NEES inside the step kernels, log-determinants or other information measures,
- *   guessing a landmark association for unknown ids. */
+ *   (slam_pgs.h has pgs_marginals), a time series (the run monitor below records the pose part at every tick of a run and calls this
+ *   evaluation at a stride), log-determinants or other information measures, guessing a landmark association for unknown ids. */
 enum slam_consistency_flags {
     SLAM_CONSISTENCY_OK = 0,
     SLAM_CONSISTENCY_FULL_NOT_PD = 1,      /* a Cholesky pivot of S is <= 0 or not finite (exactly that test, no floor): nees_full = NaN, the rest
@@ -289,6 +289,75 @@ int slam_consistency(slam_handle* h, double* nees_full, double* nees_pose, doubl
 /* bytes the model says the last slam_consistency had to read (sum over instances of the factored rows of P, n x ld x element size,
  * plus x, ids, the truth and the map rows) and its device time in ms (HIP events around its launches). */
 int slam_last_consistency_work(slam_handle* h, double* bytes, double* ms);
+
+/* ---- run monitor: the error and the pose NEES of the batch at EVERY tick of a run (the curves of a Monte-Carlo study) -------------------
+ * slam_error_stats is one mean per instance over the whole run and slam_consistency one snapshot that factors the full matrix.  The monitor
+ * evaluates, between the one-step launches of a run and on the handle's stream, for every instance at its current state (fp64 arithmetic,
+ * whatever the storage type; defined once in csrc/monitor_kernel.h, restated in tests/monitor_reference.py):
+ *   err_pos   [batch]  sqrt(wx wx + wy wy), wx = (double)(float)x - x_true, wy likewise: the position error of the estimate in the float32
+ *                      wire format of the state message (EKFState.msg:5-6) - the summand of the handle's error sum (plotting_node.py:209-212),
+ *                      so the mean of an instance's series over a run from slam_init is its slam_error_stats
+ *   err_yaw   [batch]  remainder(yaw - yaw_true, 2 pi); EKF: yaw = x_t(2), UKF kinds: yaw = remainder(atan2(x_t(3), x_t(2)), 2 pi) (ukf.cpp:71)
+ *   nees_pose [batch]  SLAM_EKF_SLAM, both storage types: slam_consistency's nees_pose - e^T S^-1 e with S = (P_t + P_t^T) / 2 of the leading
+ *                      3 x 3 block and e = (x - x_true, y - y_true, err_yaw) in fp64, formed and factored by the same operations in the same
+ *                      order (pivot test: > 0 and finite, no floor).  UKF kinds: NaN
+ *   flags     [batch]  slam_consistency_flags restricted to SLAM_CONSISTENCY_POSE_NOT_PD (nees_pose = NaN) and
+ *                      SLAM_CONSISTENCY_INSTANCE_FAILED (slam_status carries SLAM_INST_NONFINITE or SLAM_INST_WATCHDOG, or a component of
+ *                      e is not finite: all three values NaN, no other bit).  The landmark part of the state is not looked at, so an
+ *                      instance that slam_consistency fails for a non-finite LANDMARK error is a counted instance here
+ * and reduces a tick to a RECORD of 16 doubles (counts are stored as doubles; sums and maxima run over the counted instances, a maximum
+ * over none is 0):
+ *   0 n_ok (not INSTANCE_FAILED)   1 n_failed            2 n_nees (finite nees_pose)   3 n_pose_not_pd
+ *   4 sum err_pos                  5 sum err_pos^2       6 max err_pos                 7 sum err_yaw^2
+ *   8 max |err_yaw|                9 sum nees_pose      10 #{nees_pose < nees_lo}     11 #{nees_pose > nees_hi}
+ *  12 sum M (landmark count clamped to [0, L_max]) over the n_ok instances
+ *  13 n_full  14 sum nees_full  15 sum dof: over the instances whose nees_full is finite, on the ticks with a full evaluation (else 0)
+ * A per-instance value does not depend on the batch the instance sits in.  A record DOES depend on which instances share the batch: its
+ * sums are formed in a fixed order that depends on the batch size alone (256 consecutive instances per workgroup by a fixed tree, then the
+ * workgroups in ascending order; no atomics on values), so a record has the same bits on every run and under every chunking below, but the
+ * record of a batch is not the sum of the records of its shards to the last bit.
+ * Truth and meaning are those of slam_consistency: the simulator's pose, meaningful while the simulator steps the handle.
+ * Errors: SLAM_ERR_ARG: nees_lo / nees_hi not finite or lo > hi, full_every < 0, unknown source, T < 0, cmds NULL for SHARED and EACH (these
+ *   are checked first, before the handle is looked at), NULL handle.  SLAM_ERR_UNSUPPORTED: full_every != 0 on a UKF handle.
+ *   SLAM_ERR_STATE: before slam_init; without a map; slam_monitor_run also: NAV without a path, while slam_track_instance is on, while a
+ *   slam_predict is pending.
+ * Not covered: a pose NEES for the UKF kinds (the reason given at slam_consistency: their P is rank-deficient by construction); per-instance
+ *   nees_full series (call slam_consistency); quantiles or histograms across the batch; monitoring inside multi-step launches (the
+ *   monitored run is a once-per-step run by construction: one launch per timestep, DESIGN.md 4.8 has its price); slam_multi_*; the pose
+ *   graph; monitor state in checkpoint files (there is none: every call stands alone). */
+typedef struct slam_monitor_config {
+    double nees_lo, nees_hi;   /* the band of record entries 10 and 11 */
+    int full_every;            /* N > 0: slam_consistency's evaluation also runs on every N-th tick (entries 13 - 15); 0: never */
+} slam_monitor_config;
+/* nees_lo = 0.21579528262389785, nees_hi = 9.348403604496148 (the chi-square quantiles at 0.025 and 0.975 for 3 degrees of freedom),
+ * full_every = 0 */
+int slam_monitor_config_default(slam_monitor_config* cfg);
+/* One evaluation at the current state: runs the queued timesteps, computes on the handle's stream, returns when the results are on the
+ * host and CHANGES NOTHING, as slam_consistency.  cfg NULL: the defaults.  rec [16]; err_pos, err_yaw, nees_pose, flags [batch]; any
+ * output may be NULL.  full_every != 0: the full evaluation runs too (into the buffers of slam_consistency, chunked by its workspace rule). */
+int slam_monitor_now(slam_handle* h, const slam_monitor_config* cfg, double rec[16], double* err_pos, double* err_yaw, double* nees_pose,
+                     int32_t* flags);
+/* T monitored ticks.  One tick = {NAV only: the controller launch; one SIM timestep, one launch; the monitor}, all on the handle's stream.
+ * source SHARED: cmds [T][2] as slam_run_sim; EACH: cmds [T][batch][2] as slam_run_sim_each; NAV: cmds NULL, the commands come from the
+ * controller of slam_nav_run (a path must be set).  State, truth, error sums, timestep, RNG and (NAV) the controller state advance exactly
+ * as in the unmonitored run of the same commands (slam_run_sim, slam_run_sim_each, slam_nav_run): the same bits.
+ * recs [T][16]; err_pos, err_yaw, nees_pose [T][batch]; any may be NULL.  full_every = N > 0: on the ticks t with (t + 1) % N == 0, t counted
+ * from this call's first tick, slam_consistency's evaluation runs as well and the record gets entries 13 - 15.
+ * Runs the EKF step queue first and is not queued itself.  Long runs are processed in chunks of ticks, each ending synchronised with its
+ * records and series copied out: at most 4096 ticks, and at most as many as keep the per-instance series (and the commands of EACH) of a
+ * chunk on the device within SLAM_MONITOR_LOG_BYTES (environment variable read at the call, default 256 MiB; one tick at least). */
+enum slam_monitor_source { SLAM_MONITOR_SHARED = 0, SLAM_MONITOR_EACH = 1, SLAM_MONITOR_NAV = 2 };
+int slam_monitor_run(slam_handle* h, const slam_monitor_config* cfg, int source, const float* cmds, int T, double* recs, double* err_pos,
+                     double* err_yaw, double* nees_pose);
+/* Device time of the last slam_monitor_run in ms, by HIP events on the handle's stream: everything (one event pair per chunk of ticks), and
+ * what the monitor adds alone (its two launches and, on the ticks of a full evaluation, that one's), which needs an event pair per tick:
+ * the switch is slam_nav_set_timing(h, 1); without it *monitor_ms = -1. */
+int slam_last_monitor_work(slam_handle* h, double* monitor_ms, double* total_ms);
+/* TEST HOOK, not part of the filter interface: the monitor's per-instance function compiled for the HOST (the same source as the kernel, no
+ * device needed).  One instance: x = x_t[0 .. 2] (SLAM_EKF_SLAM) or x_t[0 .. 3] (UKF kinds), P3 = the leading 3 x 3 block of P_t row-major as
+ * stored (not read for the UKF kinds), truth [3], status = slam_instance_flags.  Any output may be NULL. */
+int slam_monitor_instance_host(int filter_kind, const double* x, const double* P3, const double truth[3], int32_t status, double* err_pos,
+                               double* err_yaw, double* nees_pose, int32_t* flags);
 
 /* ---- closed loop: commands from each instance's own estimate (goal_pursuit_node.py:23-50, pure_pursuit.py:17-161) ---------------------
  * The entry points above run open loop: every command is fixed before the run.  The reference's default launch (sim_base.launch,

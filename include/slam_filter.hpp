@@ -59,6 +59,10 @@ inline std::vector<float> packCommands(const std::vector<Command>& cmds, int bat
     for (size_t b = 0; b < cmds.size(); ++b) { c[2 * b] = cmds[b].fwd; c[2 * b + 1] = cmds[b].ang; }
     return c;
 }
+// What monitorNow / monitorRun return: one record and the [B] values of every instance; the [T][16] records of a run and, if asked for,
+// its [T][B] series.
+struct MonitorNow { double rec[16]; std::vector<double> err_pos, err_yaw, nees_pose; std::vector<int32_t> flags; };
+struct MonitorRun { std::vector<double> recs, err_pos, err_yaw, nees_pose; };
 // One start pose per instance (pose0 [B][3] {x, y, yaw}), optional true start poses (truth0 [B][3], empty = the config's init pose);
 // maps [B][L_stride][2] with L [B] landmarks each; commands [B] of one timestep or [T][B][2] floats of a run.
 #define SLAM_FILTER_EACH_METHODS                                                                                                          \
@@ -102,6 +106,26 @@ inline std::vector<float> packCommands(const std::vector<Command>& cmds, int bat
         NavState s; s.remaining.resize(batch_); s.finish_tick.resize(batch_); s.integ.resize(batch_); s.err_prev.resize(batch_);         \
         check(slam_nav_state(h_, s.remaining.data(), s.finish_tick.data(), s.integ.data(), s.err_prev.data()));                         \
         return s;                                                                                                                        \
+    }                                                                                                                                    \
+    /* run monitor (slam_monitor_*, include/slam_batch.h: definitions, the 16 entries of a record, what is not covered)              */  \
+    MonitorNow monitorNow(const slam_monitor_config* cfg = nullptr) {                                                                    \
+        need();                                                                                                                          \
+        MonitorNow m; m.err_pos.resize(batch_); m.err_yaw.resize(batch_); m.nees_pose.resize(batch_); m.flags.resize(batch_);            \
+        check(slam_monitor_now(h_, cfg, m.rec, m.err_pos.data(), m.err_yaw.data(), m.nees_pose.data(), m.flags.data()));                 \
+        return m;                                                                                                                        \
+    }                                                                                                                                    \
+    /* source SLAM_MONITOR_SHARED: cmds [T][2]; EACH: cmds [T][B][2]; NAV: cmds empty, the controller of setPath issues them */          \
+    MonitorRun monitorRun(int source, const std::vector<float>& cmds, int T, bool series = false, const slam_monitor_config* cfg = nullptr) {\
+        need();                                                                                                                          \
+        if (source == SLAM_MONITOR_SHARED) checkSize(cmds.size(), 2 * (size_t)(T > 0 ? T : 0), "cmds [T][2]");                           \
+        if (source == SLAM_MONITOR_EACH) checkSize(cmds.size(), 2 * (size_t)(T > 0 ? T : 0) * batch_, "cmds [T][B][2]");                 \
+        const size_t n = T > 0 ? (size_t)T : 0, per = series ? n * batch_ : 0;                                                           \
+        MonitorRun m; m.recs.resize(16 * n); m.err_pos.resize(per); m.err_yaw.resize(per); m.nees_pose.resize(per);                      \
+        static const float none[2] = {0.f, 0.f};   /* (T = 0 with commands: an empty vector still is "commands given") */                \
+        const float* c = source == SLAM_MONITOR_NAV ? nullptr : (cmds.empty() ? none : cmds.data());                                     \
+        check(slam_monitor_run(h_, cfg, source, c, T, n ? m.recs.data() : nullptr, per ? m.err_pos.data() : nullptr,                     \
+                               per ? m.err_yaw.data() : nullptr, per ? m.nees_pose.data() : nullptr));                                   \
+        return m;                                                                                                                        \
     }
 
 class Filter {  // filter.h:54-77

@@ -2,7 +2,8 @@
 kevin-robb/live_ekf_slam).  Numerics live in the HIP extension libslam_hip.so behind include/slam_batch.h."""
 from .config import SlamConfig, NavConfig, default_config, default_nav_config, EKF_SLAM, UKF_LOC, UKF_SLAM, F64, F32  # noqa: F401
 from .config import NAV_PP, NAV_DIRECT, NAV_LOOSE, NAV_TIGHT  # noqa: F401
+from .config import MonitorConfig, default_monitor_config, MONITOR_SHARED, MONITOR_EACH, MONITOR_NAV  # noqa: F401
 from .navigation import PurePursuitBatch  # noqa: F401
-from .filters import BatchedEKF, BatchedUKF, BatchedUKFLoc, Command  # noqa: F401
+from .filters import BatchedEKF, BatchedUKF, BatchedUKFLoc, Command, MonitorResult, monitor_summary  # noqa: F401
 from .pose_graph import BatchedPoseGraph, NaiveFilter  # noqa: F401
 from ._lib import SlamError  # noqa: F401

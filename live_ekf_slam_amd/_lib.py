@@ -5,7 +5,7 @@ There is no CPU fallback: if the library is missing or a HIP call fails, an exce
 import ctypes as C
 import os
 
-from .config import SlamConfig, NavConfig
+from .config import SlamConfig, NavConfig, MonitorConfig
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # SLAM_HIP_LIB: another build of the same library, for A/B tuning sessions (tools/gpu_ab.sh); the product path is the
@@ -62,6 +62,11 @@ SIGNATURES = {
     "slam_status": (C.c_int, [_H, _ip]),
     "slam_consistency": (C.c_int, [_H, _dp, _dp, _dp, _ip, _ip]),
     "slam_last_consistency_work": (C.c_int, [_H, _dp, _dp]),
+    "slam_monitor_config_default": (C.c_int, [C.POINTER(MonitorConfig)]),
+    "slam_monitor_now": (C.c_int, [_H, C.POINTER(MonitorConfig), _dp, _dp, _dp, _dp, _ip]),
+    "slam_monitor_run": (C.c_int, [_H, C.POINTER(MonitorConfig), C.c_int, _fp, C.c_int, _dp, _dp, _dp, _dp]),
+    "slam_last_monitor_work": (C.c_int, [_H, _dp, _dp]),
+    "slam_monitor_instance_host": (C.c_int, [C.c_int, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp, _ip]),
     "slam_nav_config_default": (C.c_int, [C.POINTER(NavConfig)]),
     "slam_nav_config_load": (C.c_int, [C.POINTER(NavConfig), C.c_char_p]),
     "slam_nav_set_path": (C.c_int, [_H, C.POINTER(NavConfig), _dp, C.c_int]),

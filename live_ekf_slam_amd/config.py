@@ -57,6 +57,19 @@ def default_nav_config() -> NavConfig:
     return NavConfig(0.05, 0.2, 2.0, NAV_PP, NAV_LOOSE)
 
 
+class MonitorConfig(C.Structure):
+    """ctypes mirror of `slam_monitor_config` (include/slam_batch.h): the NEES band of the record and the stride of the full evaluation."""
+    _fields_ = [("nees_lo", C.c_double), ("nees_hi", C.c_double), ("full_every", C.c_int)]
+
+
+MONITOR_SHARED, MONITOR_EACH, MONITOR_NAV = 0, 1, 2
+
+
+def default_monitor_config() -> MonitorConfig:
+    """The chi-square quantiles at 0.025 and 0.975 for 3 degrees of freedom; no full evaluation."""
+    return MonitorConfig(0.21579528262389785, 9.348403604496148, 0)
+
+
 EKF_SLAM, UKF_LOC, UKF_SLAM = 1, 2, 3
 F64, F32 = 0, 1
 INST_NONFINITE, INST_S_SINGULAR, INST_INDEX_OOR, INST_CAPACITY, INST_SQRT_FAILED = 1, 2, 4, 8, 16

@@ -21,6 +21,10 @@
 //       Closed loop through the C++ mirror: setPath (the map's first three landmarks, the reference's controller defaults), runNav with the
 //       commands returned, navState.  The file gets int64 batch, the [ticks][batch][2] float commands, then remaining, finish_tick (int32)
 //       and integ, err_prev (doubles), batch values each.
+//   filter_driver monitor <batch> <L> <ticks> <dump.bin> [seed]
+//       The run monitor through the C++ mirror: monitorRun of the scenario's commands with the series and a full evaluation every 7th tick,
+//       then monitorNow.  The file gets int64 batch, the [ticks][16] records, the [ticks][batch] err_pos, err_yaw, nees_pose (doubles), then
+//       monitorNow's record (16 doubles), err_pos, err_yaw, nees_pose (doubles) and flags (int32), batch values each.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -194,6 +198,32 @@ static int run_nav(int B, int L, int T, const char* dump_path, uint64_t seed) {
     return 0;
 }
 
+static int run_monitor(int B, int L, int T, const char* dump_path, uint64_t seed) {
+    const Scenario sc = make_scenario(seed, L, T);
+    BatchedEKF ekf(B, L);
+    slam_config cfg;
+    check(slam_config_default(&cfg));
+    ekf.readParams(cfg);
+    ekf.init(0.f, 0.f, 0.f);
+    ekf.setMap(sc.map_xy);
+    slam_monitor_config mc;
+    check(slam_monitor_config_default(&mc));
+    mc.full_every = 7;
+    const MonitorRun run = ekf.monitorRun(SLAM_MONITOR_SHARED, sc.cmds, T, true, &mc);
+    const MonitorNow now = ekf.monitorNow();
+    FILE* f = std::fopen(dump_path, "wb");
+    if (!f) throw std::runtime_error(std::string("cannot write ") + dump_path);
+    const int64_t hd = B;
+    std::fwrite(&hd, sizeof(int64_t), 1, f);
+    for (const std::vector<double>* v : {&run.recs, &run.err_pos, &run.err_yaw, &run.nees_pose}) std::fwrite(v->data(), sizeof(double), v->size(), f);
+    std::fwrite(now.rec, sizeof(double), 16, f);
+    for (const std::vector<double>* v : {&now.err_pos, &now.err_yaw, &now.nees_pose}) std::fwrite(v->data(), sizeof(double), v->size(), f);
+    std::fwrite(now.flags.data(), sizeof(int32_t), now.flags.size(), f);
+    std::fclose(f);
+    std::printf("driver ok: monitor batch=%d L=%d ticks=%d n_ok=%g\n", B, L, T, now.rec[0]);
+    return 0;
+}
+
 // the global batch over several GPUs of the node from this one process (SURVEY.md section 8(e) "Host")
 static int run_multi(const std::string& kind, int64_t B, int L, int T, int gpus, uint64_t seed, int gather_mode) {
     const Scenario sc = make_scenario(seed, L, T);
@@ -281,13 +311,16 @@ int main(int argc, char** argv) {
         if (mode == "consistency" && argc >= 6)
             return run_consistency(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), argv[5], argc > 6 ? strtoull(argv[6], nullptr, 10) : 1234ull);
         if (mode == "nav" && argc >= 6) return run_nav(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), argv[5], argc > 6 ? strtoull(argv[6], nullptr, 10) : 1234ull);
+        if (mode == "monitor" && argc >= 6)
+            return run_monitor(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), argv[5], argc > 6 ? strtoull(argv[6], nullptr, 10) : 1234ull);
         if (mode == "pose_graph" && argc >= 5) return run_pose_graph(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), argc > 5 ? argv[5] : nullptr);
         std::fprintf(stderr, "usage: filter_driver stream <ekf|ukf|ukf_loc> <batch> <L_max> <stream.txt> <dump.bin>\n"
                              "       filter_driver run <ekf|ukf> <batch> <L> <steps> [seed]\n"
                              "       filter_driver run_multi <ekf|ukf> <global batch> <L> <steps> <gpus> [seed] [gather 0|1]\n"
                              "       filter_driver pose_graph <batch> <L> <steps> [marginals dump.bin]\n"
                              "       filter_driver consistency <batch> <L> <steps> <dump.bin> [seed]\n"
-                             "       filter_driver nav <batch> <L> <ticks> <dump.bin> [seed]\n");
+                             "       filter_driver nav <batch> <L> <ticks> <dump.bin> [seed]\n"
+                             "       filter_driver monitor <batch> <L> <ticks> <dump.bin> [seed]\n");
         return 2;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "driver failed: %s\n", e.what());

@@ -20,6 +20,7 @@
 #include "consistency_kernel.h"
 #include "host/config_parse.h"
 #include "ekf_kernel.h"
+#include "monitor_kernel.h"
 #include "nav_kernel.h"
 #include "slam_math.h"
 #include "ukf_kernel.h"
@@ -164,6 +165,13 @@ struct slam_handle {
         bool time_ticks = false;   // slam_nav_set_timing: an event pair around every controller launch
         double ctrl_ms = -1.0, total_ms = -1.0;
     } nav;
+    // slam_monitor_*: the per-workgroup partial records of one evaluation, the records and the per-instance series of one chunk of ticks
+    // ([series][ticks][B] doubles, [B] flags of slam_monitor_now), the event pool and the device times of the last slam_monitor_run
+    struct Mon {
+        DevBuf<double> dpart, drec, dlog; DevBuf<int32_t> dflags;
+        std::vector<hipEvent_t> ev;
+        double mon_ms = -1.0, total_ms = -1.0;
+    } mon;
 };
 
 namespace {
@@ -347,6 +355,36 @@ int nav_reset(slam_handle* h) {
     return SLAM_OK;
 }
 
+// The launch parameters of launch_consistency at the handle's current state, with its output buffers and workspace reserved; *chunk_out:
+// instances per launch of the workspace class.
+int consistency_params(slam_handle* h, slam::ConsistencyParams* out, int* chunk_out) {
+    const size_t B = (size_t)h->B;
+    HIP_TRY(h->dcons.reserve(3 * B));
+    HIP_TRY(h->dconsi.reserve(2 * B));
+    // beyond the LDS classes the packed triangles live in a workspace of at most SLAM_CONSISTENCY_WS_BYTES (default 256 MiB; one
+    // instance at least), and the batch is processed in chunks of as many instances as it holds
+    const size_t per = slam::consistency_ws_per_instance(h->L_max);
+    int chunk = h->B;
+    if (per) {
+        const char* env = getenv("SLAM_CONSISTENCY_WS_BYTES");
+        const double budget = env ? atof(env) : 256.0 * 1024 * 1024;
+        const double fit = budget / (8.0 * (double)per);
+        chunk = fit >= (double)h->B ? h->B : (fit >= 1.0 ? (int)fit : 1);
+        HIP_TRY(h->dcons_ws.reserve(per * (size_t)chunk));
+    }
+    slam::ConsistencyParams p;
+    memset(&p, 0, sizeof(p));
+    p.P = h->dP; p.x = h->dx; p.M = h->dM; p.ids = h->dids; p.status = h->dflags; p.truth = h->dtruth;
+    p.map = h->dmap; p.L = h->L;
+    if (h->maps_each) { p.map_each = h->dmaps; p.L_each = h->dLs; p.map_stride = h->map_stride; }
+    p.B = h->B; p.L_max = h->L_max; p.pstride = h->pstride; p.xstride = h->xstride;
+    p.id_known = h->cfg.landmark_id_is_known ? 1 : 0;
+    p.nees_full = h->dcons; p.nees_pose = h->dcons + B; p.map_rms = h->dcons + 2 * B; p.dof = h->dconsi; p.flags = h->dconsi + B;
+    p.ws = h->dcons_ws; p.ws_stride = per;
+    *out = p; *chunk_out = chunk;
+    return SLAM_OK;
+}
+
 }  // namespace
 
 static int run_sim_now(slam_handle* h, const float* cmds, int T, const float* d_cmd_each = nullptr);
@@ -526,6 +564,7 @@ int slam_destroy(slam_handle* h) {
     for (auto& st : h->aux_stream) if (st) { hipStreamSynchronize(st); hipStreamDestroy(st); }
     for (auto& ev : h->aux_ev) if (ev) hipEventDestroy(ev);
     for (auto& ev : h->nav.ev) if (ev) hipEventDestroy(ev);
+    for (auto& ev : h->mon.ev) if (ev) hipEventDestroy(ev);
     if (h->copy_stream) { hipStreamSynchronize(h->copy_stream); hipStreamDestroy(h->copy_stream); }
     if (h->shadow_ev) hipEventDestroy(h->shadow_ev);
     for (auto& f : h->q.host)
@@ -1407,28 +1446,9 @@ int slam_consistency(slam_handle* h, double* nees_full, double* nees_pose, doubl
         return fail(SLAM_ERR_STATE, "no true map to compare the landmarks with: call slam_set_map (or slam_set_maps) first");
     HIP_TRY(hipSetDevice(h->device));
     const size_t B = (size_t)h->B;
-    HIP_TRY(h->dcons.reserve(3 * B));
-    HIP_TRY(h->dconsi.reserve(2 * B));
-    // beyond the LDS classes the packed triangles live in a workspace of at most SLAM_CONSISTENCY_WS_BYTES (default 256 MiB; one
-    // instance at least), and the batch is processed in chunks of as many instances as it holds
-    const size_t per = slam::consistency_ws_per_instance(h->L_max);
-    int chunk = h->B;
-    if (per) {
-        const char* env = getenv("SLAM_CONSISTENCY_WS_BYTES");
-        const double budget = env ? atof(env) : 256.0 * 1024 * 1024;
-        const double fit = budget / (8.0 * (double)per);
-        chunk = fit >= (double)h->B ? h->B : (fit >= 1.0 ? (int)fit : 1);
-        HIP_TRY(h->dcons_ws.reserve(per * (size_t)chunk));
-    }
     slam::ConsistencyParams p;
-    memset(&p, 0, sizeof(p));
-    p.P = h->dP; p.x = h->dx; p.M = h->dM; p.ids = h->dids; p.status = h->dflags; p.truth = h->dtruth;
-    p.map = h->dmap; p.L = h->L;
-    if (h->maps_each) { p.map_each = h->dmaps; p.L_each = h->dLs; p.map_stride = h->map_stride; }
-    p.B = h->B; p.L_max = h->L_max; p.pstride = h->pstride; p.xstride = h->xstride;
-    p.id_known = h->cfg.landmark_id_is_known ? 1 : 0;
-    p.nees_full = h->dcons; p.nees_pose = h->dcons + B; p.map_rms = h->dcons + 2 * B; p.dof = h->dconsi; p.flags = h->dconsi + B;
-    p.ws = h->dcons_ws; p.ws_stride = per;
+    int chunk = 0;
+    TRY(consistency_params(h, &p, &chunk));
     hipEvent_t ev[2] = {nullptr, nullptr};
     HIP_TRY(hipEventCreate(&ev[0]));
     hipError_t e = hipEventCreate(&ev[1]);
@@ -1920,6 +1940,213 @@ int slam_nav_tick_host(const slam_nav_config* cfg, double d_max, double th_max, 
     s.head = *head; s.finish_tick = *finish_tick; s.integ = *integ; s.err_prev = *err_prev;
     slam::nav_tick(nav_consts(*cfg, d_max, th_max), slam::NavPathView{pts}, P, (double)est[0], (double)est[1], (double)est[2], frozen != 0, tick, s, cmd);
     *head = s.head; *finish_tick = s.finish_tick; *integ = s.integ; *err_prev = s.err_prev;
+    return SLAM_OK;
+}
+
+}  // extern "C"
+
+// ---- run monitor: per-tick error and pose-NEES records (monitor_kernel.hip) ----------------------------------------------------------------
+namespace {
+
+// *out = *cfg (NULL: the defaults), checked
+int monitor_config(const slam_monitor_config* cfg, slam_monitor_config* out) {
+    if (cfg) *out = *cfg; else slam_monitor_config_default(out);
+    if (!isfinite(out->nees_lo) || !isfinite(out->nees_hi) || out->nees_lo > out->nees_hi)
+        return fail(SLAM_ERR_ARG, "monitor config: the band nees_lo = %g .. nees_hi = %g must be finite and ordered", out->nees_lo, out->nees_hi);
+    if (out->full_every < 0) return fail(SLAM_ERR_ARG, "monitor config: full_every = %d is negative", out->full_every);
+    return SLAM_OK;
+}
+
+int monitor_full_supported(const slam_handle* h, const slam_monitor_config& c) {
+    if (c.full_every != 0 && h->kind != SLAM_EKF_SLAM)
+        return fail(SLAM_ERR_UNSUPPORTED, "monitor config: full_every = %d needs EKF_SLAM (slam_consistency is not defined for the UKF kinds); full_every = 0 runs", c.full_every);
+    return SLAM_OK;
+}
+
+slam::MonitorParams monitor_params(slam_handle* h, const slam_monitor_config& c) {
+    slam::MonitorParams p;
+    memset(&p, 0, sizeof(p));
+    p.P = h->dP; p.x = h->dx; p.M = h->dM; p.status = h->dflags; p.truth = h->dtruth;
+    p.B = h->B; p.L_max = h->L_max; p.pstride = h->pstride; p.xstride = h->xstride;
+    p.ukf = h->kind != SLAM_EKF_SLAM;
+    p.nees_lo = c.nees_lo; p.nees_hi = c.nees_hi;
+    p.partials = h->mon.dpart;
+    return p;
+}
+
+// one evaluation on the handle's stream; full: launch_consistency first, into the handle's buffers, its results into entries 13 - 15
+int monitor_launch(slam_handle* h, slam::MonitorParams& p, bool full) {
+    p.nees_full = nullptr; p.dof = nullptr;
+    if (full) {
+        slam::ConsistencyParams cp;
+        int chunk = 0;
+        TRY(consistency_params(h, &cp, &chunk));
+        HIP_TRY(slam::launch_consistency(cp, h->esz == 4, chunk, h->stream));
+        p.nees_full = cp.nees_full; p.dof = cp.dof;
+    }
+    p.P = h->dP;   // (the UKF step swaps its two buffers)
+    HIP_TRY(slam::launch_monitor(p, h->esz == 4, h->stream));
+    return SLAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int slam_monitor_config_default(slam_monitor_config* c) {
+    if (!c) return fail(SLAM_ERR_ARG, "cfg is NULL");
+    memset(c, 0, sizeof(*c));
+    c->nees_lo = 0.21579528262389785; c->nees_hi = 9.348403604496148;   // chi-square quantiles at 0.025 and 0.975, 3 degrees of freedom
+    c->full_every = 0;
+    return SLAM_OK;
+}
+
+int slam_monitor_now(slam_handle* h, const slam_monitor_config* cfg, double rec[16], double* err_pos, double* err_yaw, double* nees_pose, int32_t* flags) {
+    slam_monitor_config c;
+    TRY(monitor_config(cfg, &c));
+    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
+    TRY(monitor_full_supported(h, c));
+    TRY(flush_lazy(h));
+    if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
+    if (!has_map(h)) return fail(SLAM_ERR_STATE, "no true map, so no simulated truth to compare with: call slam_set_map (or slam_set_maps) first");
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t B = (size_t)h->B;
+    HIP_TRY(h->mon.dpart.reserve((size_t)slam::monitor_blocks(h->B) * slam::kMonRecLen));
+    HIP_TRY(h->mon.drec.reserve(slam::kMonRecLen));
+    HIP_TRY(h->mon.dlog.reserve(3 * B));
+    HIP_TRY(h->mon.dflags.reserve(B));
+    slam::MonitorParams p = monitor_params(h, c);
+    p.err_pos = h->mon.dlog; p.err_yaw = h->mon.dlog + B; p.nees_pose = h->mon.dlog + 2 * B; p.flags = h->mon.dflags;
+    p.rec = h->mon.drec;
+    TRY(monitor_launch(h, p, c.full_every != 0));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (rec) HIP_TRY(hipMemcpy(rec, h->mon.drec, sizeof(double) * slam::kMonRecLen, hipMemcpyDeviceToHost));
+    if (err_pos) HIP_TRY(hipMemcpy(err_pos, p.err_pos, sizeof(double) * B, hipMemcpyDeviceToHost));
+    if (err_yaw) HIP_TRY(hipMemcpy(err_yaw, p.err_yaw, sizeof(double) * B, hipMemcpyDeviceToHost));
+    if (nees_pose) HIP_TRY(hipMemcpy(nees_pose, p.nees_pose, sizeof(double) * B, hipMemcpyDeviceToHost));
+    if (flags) HIP_TRY(hipMemcpy(flags, h->mon.dflags, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+    return SLAM_OK;
+}
+
+int slam_monitor_run(slam_handle* h, const slam_monitor_config* cfg, int source, const float* cmds, int T, double* recs, double* err_pos,
+                     double* err_yaw, double* nees_pose) {
+    slam_monitor_config c;
+    TRY(monitor_config(cfg, &c));
+    if (source != SLAM_MONITOR_SHARED && source != SLAM_MONITOR_EACH && source != SLAM_MONITOR_NAV) return fail(SLAM_ERR_ARG, "unknown command source %d", source);
+    if (T < 0) return fail(SLAM_ERR_ARG, "T = %d is negative", T);
+    if (source != SLAM_MONITOR_NAV && !cmds) return fail(SLAM_ERR_ARG, "cmds is NULL: the sources SHARED and EACH read the commands from it");
+    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
+    TRY(monitor_full_supported(h, c));
+    if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
+    if (!has_map(h)) return fail(SLAM_ERR_STATE, "slam_set_map has not been called");
+    if (source == SLAM_MONITOR_NAV && !h->nav.set) return fail(SLAM_ERR_STATE, "no path: call slam_nav_set_path or slam_nav_set_paths first");
+    if (h->shadow) return fail(SLAM_ERR_STATE, "slam_track_instance is on: the monitored run steps the batch once per tick and does not drive the shadow filter");
+    if (h->predicted) return fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev before slam_monitor_run");
+    TRY(flush_lazy(h));
+    if (T == 0) return SLAM_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t B = (size_t)h->B, row = 2 * B;
+    double* const series[3] = {err_pos, err_yaw, nees_pose};
+    int ns = 0;
+    for (double* s : series) ns += s != nullptr;
+    // ticks per chunk: the events of a chunk are read, and its records and series copied out, when the chunk is done.  What a tick holds
+    // on the device - its rows of the series and, for EACH, of the commands - stays within SLAM_MONITOR_LOG_BYTES (one tick at least)
+    int chunk = T < 4096 ? T : 4096;
+    const double per_tick = 8.0 * (double)ns * (double)B + (source == SLAM_MONITOR_EACH ? 4.0 * (double)row : 0.0);
+    if (per_tick > 0.0) {
+        const char* env = getenv("SLAM_MONITOR_LOG_BYTES");
+        const double fit = (env ? atof(env) : 256.0 * 1024 * 1024) / per_tick;
+        if (fit < (double)chunk) chunk = fit >= 1.0 ? (int)fit : 1;
+    }
+    HIP_TRY(h->mon.dpart.reserve((size_t)slam::monitor_blocks(h->B) * slam::kMonRecLen));
+    HIP_TRY(h->mon.drec.reserve((size_t)chunk * slam::kMonRecLen));
+    if (ns) HIP_TRY(h->mon.dlog.reserve((size_t)ns * chunk * B));
+    if (source == SLAM_MONITOR_NAV && h->dcmd_each.cap() < row) {
+        if (h->dcmd_each) HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(h->dcmd_each.reserve(row));
+    }
+    const bool timed = h->nav.time_ticks;
+    while (h->mon.ev.size() < 2 + (timed ? 2 * (size_t)chunk : 0)) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreate(&e));
+        h->mon.ev.push_back(e);
+    }
+    slam::NavParams np;
+    memset(&np, 0, sizeof(np));
+    if (source == SLAM_MONITOR_NAV) {
+        np.x = h->dx; np.flags = h->dflags; np.path = h->nav.dpath;
+        np.P_each = h->nav.each ? h->nav.dP.get() : nullptr; np.P = h->nav.P; np.path_stride = h->nav.stride;
+        np.B = h->B; np.xstride = h->xstride; np.ukf = h->kind != SLAM_EKF_SLAM;
+        np.c = nav_consts(h->nav.cfg, h->cfg.d_max, h->cfg.th_max);
+        np.head = h->nav.dhead; np.finish_tick = h->nav.dfinish; np.integ = h->nav.dinteg; np.err_prev = h->nav.derrp;
+        np.cmd_out = h->dcmd_each;
+    }
+    slam::MonitorParams p = monitor_params(h, c);
+    h->mon.mon_ms = timed ? 0.0 : -1.0; h->mon.total_ms = 0.0;
+    hipEvent_t* const ev = h->mon.ev.data();
+    for (int t0 = 0; t0 < T; t0 += chunk) {
+        const int tc = T - t0 < chunk ? T - t0 : chunk;
+        if (source == SLAM_MONITOR_EACH) TRY(upload_cmds_each(h, cmds + (size_t)t0 * row, tc));
+        HIP_TRY(hipEventRecord(ev[0], h->stream));
+        for (int t = 0; t < tc; ++t) {
+            if (source == SLAM_MONITOR_NAV) {
+                np.tick = h->nav.tick;
+                HIP_TRY(slam::launch_nav_tick(np, h->esz == 4, h->stream));
+                h->nav.tick += 1;
+                TRY(launch_step(h, kNoCmd, 1, nullptr, nullptr, 0, h->dcmd_each));
+            } else if (source == SLAM_MONITOR_EACH) {
+                TRY(launch_step(h, kNoCmd, 1, nullptr, nullptr, 0, h->dcmd_each + (size_t)t * row));
+            } else {
+                TRY(launch_step(h, cmds + 2 * (size_t)(t0 + t), 1, nullptr, nullptr, 0));
+            }
+            double* slot = h->mon.dlog;
+            p.err_pos = err_pos ? slot + (size_t)t * B : nullptr; if (err_pos) slot += (size_t)chunk * B;
+            p.err_yaw = err_yaw ? slot + (size_t)t * B : nullptr; if (err_yaw) slot += (size_t)chunk * B;
+            p.nees_pose = nees_pose ? slot + (size_t)t * B : nullptr;
+            p.rec = h->mon.drec + (size_t)t * slam::kMonRecLen;
+            if (timed) HIP_TRY(hipEventRecord(ev[2 + 2 * t], h->stream));
+            TRY(monitor_launch(h, p, c.full_every > 0 && (t0 + t + 1) % c.full_every == 0));
+            if (timed) HIP_TRY(hipEventRecord(ev[3 + 2 * t], h->stream));
+        }
+        HIP_TRY(hipEventRecord(ev[1], h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        h->mon.total_ms += (double)ms;
+        for (int t = 0; timed && t < tc; ++t) {
+            HIP_TRY(hipEventElapsedTime(&ms, ev[2 + 2 * t], ev[3 + 2 * t]));
+            h->mon.mon_ms += (double)ms;
+        }
+        if (recs) HIP_TRY(hipMemcpy(recs + (size_t)t0 * slam::kMonRecLen, h->mon.drec, sizeof(double) * (size_t)tc * slam::kMonRecLen, hipMemcpyDeviceToHost));
+        const double* slot = h->mon.dlog;
+        for (double* s : series)
+            if (s) {
+                HIP_TRY(hipMemcpy(s + (size_t)t0 * B, slot, sizeof(double) * (size_t)tc * B, hipMemcpyDeviceToHost));
+                slot += (size_t)chunk * B;
+            }
+    }
+    return SLAM_OK;
+}
+
+int slam_last_monitor_work(slam_handle* h, double* monitor_ms, double* total_ms) {
+    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
+    if (h->mon.total_ms < 0.0) return fail(SLAM_ERR_STATE, "slam_monitor_run has not run on this handle");
+    if (monitor_ms) *monitor_ms = h->mon.mon_ms;
+    if (total_ms) *total_ms = h->mon.total_ms;
+    return SLAM_OK;
+}
+
+int slam_monitor_instance_host(int filter_kind, const double* x, const double* P3, const double truth[3], int32_t status, double* err_pos,
+                               double* err_yaw, double* nees_pose, int32_t* flags) {
+    if (filter_kind != SLAM_EKF_SLAM && filter_kind != SLAM_UKF_SLAM && filter_kind != SLAM_UKF_LOC) return fail(SLAM_ERR_ARG, "unknown filter kind %d", filter_kind);
+    const bool ukf = filter_kind != SLAM_EKF_SLAM;
+    if (!x || !truth || (!ukf && !P3)) return fail(SLAM_ERR_ARG, "NULL argument");
+    const double zero[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const slam::MonitorValue v = slam::monitor_instance(x, ukf ? zero : P3, truth, status, ukf);
+    if (err_pos) *err_pos = v.err_pos;
+    if (err_yaw) *err_yaw = v.err_yaw;
+    if (nees_pose) *nees_pose = v.nees_pose;
+    if (flags) *flags = v.flags;
     return SLAM_OK;
 }
 

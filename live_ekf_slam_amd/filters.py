@@ -13,6 +13,7 @@ import numpy as np
 
 from . import _lib
 from .config import SlamConfig, NavConfig, default_config, default_nav_config, EKF_SLAM, UKF_LOC, UKF_SLAM, F64
+from .config import MonitorConfig, default_monitor_config, MONITOR_SHARED, MONITOR_EACH, MONITOR_NAV
 
 
 def _d(a):
@@ -33,6 +34,17 @@ class Command:
     def __init__(self, fwd=0.0, ang=0.0):
         self.fwd = float(np.float32(fwd))
         self.ang = float(np.float32(ang))
+
+
+class MonitorResult:
+    """What monitor_run returns: `recs`, the (T, 16) records of the ticks (columns: the REC_* constants; slam_monitor_run in
+    include/slam_batch.h defines them), and - with series=True, else None - `err_pos`, `err_yaw`, `nees_pose`, (T, batch) each."""
+
+    (REC_N_OK, REC_N_FAILED, REC_N_NEES, REC_N_POSE_NOT_PD, REC_SUM_ERR_POS, REC_SUM_ERR_POS2, REC_MAX_ERR_POS, REC_SUM_ERR_YAW2,
+     REC_MAX_ABS_ERR_YAW, REC_SUM_NEES_POSE, REC_N_BELOW, REC_N_ABOVE, REC_SUM_M, REC_N_FULL, REC_SUM_NEES_FULL, REC_SUM_DOF) = range(16)
+
+    def __init__(self, recs, err_pos=None, err_yaw=None, nees_pose=None):
+        self.recs, self.err_pos, self.err_yaw, self.nees_pose = recs, err_pos, err_yaw, nees_pose
 
 
 class BatchedFilter:
@@ -346,6 +358,70 @@ class BatchedFilter:
         _lib.check(_lib.lib().slam_last_consistency_work(self.h, C.byref(b), C.byref(ms)))
         return b.value, ms.value
 
+    # -- no counterpart in the reference: the error and the pose NEES at every tick of a run (slam_monitor_*, include/slam_batch.h) --
+    def _monitor_config(self, cfg):
+        if cfg is None:
+            return default_monitor_config()
+        if isinstance(cfg, MonitorConfig):
+            return cfg
+        c = default_monitor_config()
+        for k, v in dict(cfg).items():
+            if k not in ("nees_lo", "nees_hi", "full_every"):
+                raise ValueError(f"unknown monitor setting {k!r}")
+            setattr(c, k, v)
+        return c
+
+    def monitor_now(self, cfg=None):
+        """One monitor evaluation at the current state, changing nothing: dict of rec (16,), err_pos, err_yaw, nees_pose, flags [batch]
+        (flags: POSE_NOT_PD, INSTANCE_FAILED).  cfg: a MonitorConfig, a dict of its fields, or None for the defaults."""
+        self._need()
+        c = self._monitor_config(cfg)
+        out = dict(rec=np.zeros(16), err_pos=np.zeros(self.batch), err_yaw=np.zeros(self.batch), nees_pose=np.zeros(self.batch),
+                   flags=np.zeros(self.batch, dtype=np.int32))
+        _lib.check(_lib.lib().slam_monitor_now(self.h, C.byref(c), _d(out["rec"]), _d(out["err_pos"]), _d(out["err_yaw"]), _d(out["nees_pose"]),
+                                               _i(out["flags"])))
+        return out
+
+    def monitor_run(self, cmds=None, T=None, source=None, series=False, cfg=None):
+        """A monitored run: per tick one simulator timestep and one monitor evaluation, all on the device; the same bits as the
+        unmonitored run of the same commands.  cmds (T, 2): shared commands; (T, batch, 2): per instance; None with T ticks: the
+        controller of set_path / set_paths issues them (source MONITOR_NAV).  Returns a MonitorResult; series=True also records the
+        per-instance err_pos, err_yaw and nees_pose of every tick."""
+        self._need()
+        if cmds is None:
+            if T is None:
+                raise ValueError("monitor_run needs commands or, for the closed loop, a number of ticks T")
+            source = MONITOR_NAV if source is None else source
+            c32, T = None, int(T)
+        else:
+            c32 = np.ascontiguousarray(cmds, dtype=np.float32)
+            if c32.ndim == 3 and c32.shape[1:] == (self.batch, 2):
+                want = MONITOR_EACH
+            elif c32.ndim == 2 and c32.shape[1] == 2:
+                want = MONITOR_SHARED
+            else:
+                raise ValueError(f"expected commands of shape (T, 2) or (T, {self.batch}, 2), got {c32.shape}")
+            if T is not None and int(T) != c32.shape[0]:
+                raise ValueError(f"T = {T} does not match the {c32.shape[0]} commands")
+            if source is not None and source != want:
+                raise ValueError(f"source {source} does not match commands of shape {c32.shape}")
+            source, T = want, c32.shape[0]
+        n = max(T, 0)
+        res = MonitorResult(np.zeros((n, 16)))
+        if series:
+            res.err_pos, res.err_yaw, res.nees_pose = (np.zeros((n, self.batch)) for _ in range(3))
+        ptr = (lambda a: None if a is None or a.size == 0 else _d(a))
+        _lib.check(_lib.lib().slam_monitor_run(self.h, C.byref(self._monitor_config(cfg)), int(source), None if c32 is None else _f(c32), T,
+                                               ptr(res.recs), ptr(res.err_pos), ptr(res.err_yaw), ptr(res.nees_pose)))
+        self.timestep += n
+        return res
+
+    def last_monitor_work(self):
+        """(device ms of what the monitor added to the last monitor_run, or -1 without set_nav_timing; device ms of the whole run)."""
+        self._need(); a = C.c_double(0); b = C.c_double(0)
+        _lib.check(_lib.lib().slam_last_monitor_work(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     # -- closed loop: goal_pursuit_node.py:23-50 on the device (slam_nav_*, include/slam_batch.h) --
     def _nav_config(self, nav):
         if nav is None:
@@ -505,6 +581,32 @@ def consistency_summary(nees, dof, flags, alpha=0.05):
     lo, hi = chi2_quantile(alpha / 2, total), chi2_quantile(1 - alpha / 2, total)
     return dict(count=int(ok.sum()), left_out=int((~ok).sum()), normalised=float(nees[ok].sum() / total), lower=lo / total,
                 upper=hi / total)
+
+
+def monitor_summary(recs, alpha=0.05):
+    """The curves of a monitored run from its (T, 16) records (one record: shape (16,)), per tick: dict of arrays
+    mean_err_pos, std_err_pos (population standard deviation across the batch), rms_err_yaw, anees (mean nees_pose over the n_nees
+    instances), anees_lower / anees_upper (Bar-Shalom's band for that MEAN: the chi-square quantiles of 3 n_nees degrees of freedom at
+    alpha / 2 and 1 - alpha / 2, divided by n_nees; NaN where 3 n_nees < 30, which chi2_quantile refuses), frac_outside (the fraction of
+    the n_nees instances below nees_lo or above nees_hi of the run's config), n_ok, n_nees.  Ticks without a counted instance give NaN.
+    Pure numpy (no GPU)."""
+    r = np.atleast_2d(np.asarray(recs, dtype=np.float64))
+    if r.ndim != 2 or r.shape[1] != 16:
+        raise ValueError(f"expected records of shape (T, 16), got {np.shape(recs)}")
+    R = MonitorResult
+    with np.errstate(divide="ignore", invalid="ignore"):
+        n_ok, n_nees = r[:, R.REC_N_OK], r[:, R.REC_N_NEES]
+        mean = r[:, R.REC_SUM_ERR_POS] / n_ok
+        var = r[:, R.REC_SUM_ERR_POS2] / n_ok - mean * mean
+        out = dict(mean_err_pos=mean, std_err_pos=np.sqrt(np.maximum(var, 0.0)), rms_err_yaw=np.sqrt(r[:, R.REC_SUM_ERR_YAW2] / n_ok),
+                   anees=r[:, R.REC_SUM_NEES_POSE] / n_nees, frac_outside=(r[:, R.REC_N_BELOW] + r[:, R.REC_N_ABOVE]) / n_nees,
+                   n_ok=n_ok.astype(np.int64), n_nees=n_nees.astype(np.int64))
+    lo, hi = np.full(r.shape[0], np.nan), np.full(r.shape[0], np.nan)
+    for t, n in enumerate(out["n_nees"]):
+        if 3 * n >= 30:
+            lo[t], hi[t] = chi2_quantile(alpha / 2, 3 * int(n)) / n, chi2_quantile(1 - alpha / 2, 3 * int(n)) / n
+    out["anees_lower"], out["anees_upper"] = lo, hi
+    return out
 
 
 class BatchedUKF(BatchedFilter):
