@@ -198,7 +198,8 @@ int slam_update_dev(slam_handle* h, const float* d_meas, const int32_t* d_meas_c
  * Checkpoints: maps and commands are inputs, not state; slam_save_state / slam_load_state keep their format, and after a load the caller
  *   sets the maps (slam_set_maps) again as for slam_set_map.
  * The pose graph has the same forms (slam_pgs.h: pgs_init_each, pgs_set_maps, pgs_update_each[_dev], pgs_run_sim_each).
- * Not covered: slam_multi_*, a per-instance known map for UKF_LOC, per-instance noise configs. */
+ * Per-instance noise parameters: slam_set_noise_each, below.
+ * Not covered: slam_multi_*, a per-instance known map for UKF_LOC. */
 /* Filter::init with one start pose per instance: pose0 [batch][3] {x, y, yaw} (float, as slam_init's arguments); truth0 [batch][3] =
  * the simulator's true start pose per instance, NULL = the config's init pose for all.  Resets what slam_init resets. */
 int slam_init_each(slam_handle* h, const float* pose0, const double* truth0);
@@ -215,6 +216,40 @@ int slam_step_each_dev(slam_handle* h, const float* d_cmds, const float* d_meas,
 int slam_run_sim_each(slam_handle* h, const float* cmds, int T);
 /* UKF only: predictionStage with cmds [batch][2]; the slam_update_dev that follows uses them.  EKF: SLAM_ERR_UNSUPPORTED. */
 int slam_predict_each(slam_handle* h, const float* cmds);
+
+/* ---- per-instance noise parameters: tuning sweeps in one batch ---------------------------------------------------------------------
+ * One row per instance of what slam_config says about noise, for the filter and - independently - for the simulator, so that ONE handle
+ * runs a sweep of settings (one launch per tick instead of one per setting).
+ * Filter fields: v_d .. w_b and V_00 .. W_11 are the YAML keys as the FILTER reads them; the handle's replicate_vw_quirk maps them to
+ *   the effective V / W exactly as for slam_config (quirk 1: V = diag(W_00, W_11), W = I2; V_00, V_11 are then not read).
+ * Simulator fields: sim_V_00 .. sim_W_11 are the half-widths of get_cmd's uniform draws (sim_node.py:216-217,247-248), which slam_config
+ *   takes from the same keys V_00 .. W_11.  EXT mode (slam_step*, slam_predict* / slam_update_dev) reads only the filter fields.
+ * Kinds: EKF_SLAM in both storage types and every size class (the LDS classes, the HBM-streamed class, the long-message pair of
+ *   launches), UKF_SLAM (LDS classes, streamed class, Cholesky square-root mode) and UKF_LOC; SIM and EXT mode; every entry point that
+ *   ends in a step launch: slam_step*, slam_step_sim, slam_run_sim, the _each forms, slam_predict* / slam_update_dev, slam_nav_run,
+ *   slam_monitor_run.  Instance b reads rows[b]; results do not depend on who shares the batch (an instance with row r gives the bits
+ *   of a one-instance handle created from a slam_config with r's values and slam_set_instance_offset(b)).
+ * Call order: the call runs the EKF step queue first, like the _each entry points: timesteps accepted before it keep the old values,
+ *   later ones take the new.  It may be repeated at any time; rows = NULL returns to the handle's slam_config.  A pending UKF prediction
+ *   stage (slam_predict*): SLAM_ERR_STATE.
+ * Rows are inputs, not state, like the maps: slam_save_state / slam_load_state keep their format and the caller sets the rows again
+ *   after a load; slam_init* does not clear them.  slam_track_instance: the shadow gets the tracked instance's row, and again when the
+ *   rows change.
+ * Errors: SLAM_ERR_ARG for a NULL handle and for a non-finite field (slam_last_error names the instance and the field).  No other value
+ *   check: the reference has none.
+ * Not covered: slam_multi_*; the pose graph (slam_pgs.h); per-instance vision limits (slam_set_vision); per-instance d_max / th_max;
+ *   per-instance quirk switches; a device-side reduction of the monitor records per group of instances - a caller groups the series = 1
+ *   output of slam_monitor_run or slam_consistency's per-instance values on the host. */
+typedef struct slam_noise {
+    float  v_d, v_th, w_r, w_b;                      /* filter: noise means, as slam_config */
+    double V_00, V_11, W_00, W_11;                   /* filter: the YAML keys as the filter reads them (see above) */
+    double sim_V_00, sim_V_11, sim_W_00, sim_W_11;   /* simulator: half-widths of get_cmd's uniform draws */
+} slam_noise;
+/* The row that reproduces the shared behaviour: filter and simulator fields both from cfg (rows all equal to it give the bits of a
+ * handle without rows). */
+int slam_noise_from_config(const slam_config* cfg, slam_noise* out);
+/* rows: [batch], host; NULL = back to the handle's slam_config. */
+int slam_set_noise_each(slam_handle* h, const slam_noise* rows);
 
 /* ---- state export: getStateVector / publishState payload (ekf.cpp:181-220, ukf.cpp:47-104) ---------------- */
 /* Sizes: x needs n_max doubles, P needs n_max*n_max doubles, ids needs L_max ints, where

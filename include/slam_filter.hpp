@@ -76,6 +76,12 @@ struct MonitorRun { std::vector<double> recs, err_pos, err_yaw, nees_pose; };
         need(); checkSize(L.size(), (size_t)batch_, "L"); checkSize(maps.size(), 2 * (size_t)L_stride * batch_, "maps");               \
         check(slam_set_maps(h_, maps.data(), L.data(), L_stride));                                                                       \
     }                                                                                                                                    \
+    /* per-instance noise parameters (slam_set_noise_each): rows [B]; an empty vector returns to the config of readParams            */ \
+    void setNoiseEach(const std::vector<slam_noise>& rows) {                                                                             \
+        need();                                                                                                                          \
+        if (!rows.empty()) checkSize(rows.size(), (size_t)batch_, "noise rows");                                                        \
+        check(slam_set_noise_each(h_, rows.empty() ? nullptr : rows.data()));                                                            \
+    }                                                                                                                                    \
     void updateBatch(const std::vector<Command>& cmds, const float* meas, const int32_t* meas_count, int k_stride) {                     \
         need(); check(slam_step_each(h_, packCommands(cmds, batch_).data(), meas, meas_count, k_stride));                                \
     }                                                                                                                                    \

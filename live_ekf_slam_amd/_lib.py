@@ -5,7 +5,7 @@ There is no CPU fallback: if the library is missing or a HIP call fails, an exce
 import ctypes as C
 import os
 
-from .config import SlamConfig, NavConfig, MonitorConfig
+from .config import SlamConfig, NavConfig, MonitorConfig, Noise
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # SLAM_HIP_LIB: another build of the same library, for A/B tuning sessions (tools/gpu_ab.sh); the product path is the
@@ -48,6 +48,8 @@ SIGNATURES = {
     "slam_step_each_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "slam_run_sim_each": (C.c_int, [_H, _fp, C.c_int]),
     "slam_predict_each": (C.c_int, [_H, _fp]),
+    "slam_noise_from_config": (C.c_int, [C.POINTER(SlamConfig), C.POINTER(Noise)]),
+    "slam_set_noise_each": (C.c_int, [_H, C.POINTER(Noise)]),
     "slam_update_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int]),
     "slam_get_state": (C.c_int, [_H, C.c_int, _dp, _dp, _ip, _ip, _ip]),
     "slam_get_sigma_points": (C.c_int, [_H, C.c_int, _dp, _ip, _ip]),

@@ -42,6 +42,42 @@ def default_config() -> SlamConfig:
     return c
 
 
+class Noise(C.Structure):
+    """ctypes mirror of `slam_noise` (include/slam_batch.h): one instance's row of slam_set_noise_each.  Filter fields as the filter
+    reads the YAML keys (the handle's replicate_vw_quirk maps them to the effective V / W), simulator fields = half-widths of the draws."""
+    _fields_ = [("v_d", C.c_float), ("v_th", C.c_float), ("w_r", C.c_float), ("w_b", C.c_float),
+                ("V_00", C.c_double), ("V_11", C.c_double), ("W_00", C.c_double), ("W_11", C.c_double),
+                ("sim_V_00", C.c_double), ("sim_V_11", C.c_double), ("sim_W_00", C.c_double), ("sim_W_11", C.c_double)]
+
+
+NOISE_FIELDS = tuple(name for name, _ in Noise._fields_)
+
+
+def noise_from_config(cfg) -> Noise:
+    """The row that reproduces a handle without rows (slam_noise_from_config): filter and simulator fields both from cfg."""
+    return Noise(cfg.v_d, cfg.v_th, cfg.w_r, cfg.w_b, cfg.V_00, cfg.V_11, cfg.W_00, cfg.W_11, cfg.V_00, cfg.V_11, cfg.W_00, cfg.W_11)
+
+
+def noise_rows(cfg, batch, **columns):
+    """`batch` rows for BatchedFilter.set_noise: every row noise_from_config(cfg), with per-instance values overriding fields -
+    noise_rows(cfg, 8, V_00=np.logspace(-6, -2, 8), sim_W_00=0.02); a column is a scalar or a [batch] array."""
+    rows = (Noise * int(batch))()
+    base = noise_from_config(cfg)
+    for name in columns:
+        if name not in NOISE_FIELDS:
+            raise ValueError(f"unknown noise field {name!r}: expected one of {NOISE_FIELDS}")
+    cols = {}
+    for name, v in columns.items():
+        a = [float(x) for x in (v if hasattr(v, "__len__") else [v] * int(batch))]
+        if len(a) != int(batch):
+            raise ValueError(f"{name}: expected a scalar or {int(batch)} values, got {len(a)}")
+        cols[name] = a
+    for b in range(int(batch)):
+        for name in NOISE_FIELDS:
+            setattr(rows[b], name, cols[name][b] if name in cols else getattr(base, name))
+    return rows
+
+
 class NavConfig(C.Structure):
     """ctypes mirror of `slam_nav_config` (include/slam_batch.h): params.yaml:14,81-84 plus the launch file's tight_control."""
     _fields_ = [("dt", C.c_double), ("lookahead_dist_init", C.c_double), ("lookahead_dist_max", C.c_double),

@@ -64,6 +64,7 @@ __global__ __launch_bounds__(kBigTpb) void ekf_big_step_kernel(const EkfStepPara
     constexpr int ESZ = (int)sizeof(ST);
     extern __shared__ double sm[];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const StepNoise nz = step_noise(p, b);   // the instance's noise values (its row of slam_set_noise_each or the block's scalars), read once
     const int Lcap = p.L_max, nmax = 3 + 2 * Lcap, np = (nmax + 1) & ~1;
     double* const s_xt = sm;
     double* const s_xp = s_xt + np;
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(kBigTpb) void ekf_big_step_kernel(const EkfStepPara
             const int Lm = sim_map_size(p, b);
             const double* const map = sim_map(p, b);
             const double lmx0 = lane < Lm ? map[2 * lane] : 0.0, lmy0 = lane < Lm ? map[2 * lane + 1] : 0.0;
-            const int kr = sim_wave<(1 << 30), false>(p, b, lane, fwd, ang, p.step + (uint32_t)t_off, map, Lm, tx, ty, tth, lmx0, lmy0, s_meas);
+            const int kr = sim_wave<(1 << 30), false>(p, b, lane, fwd, ang, p.step + (uint32_t)t_off, map, Lm, tx, ty, tth, lmx0, lmy0, s_meas, nz.sim);
             if (lane == 0) { s_i[3] = kr; s_sc[24] = tx; s_sc[25] = ty; s_sc[26] = tth; }
         }
     } else {
@@ -132,14 +133,14 @@ __global__ __launch_bounds__(kBigTpb) void ekf_big_step_kernel(const EkfStepPara
         det_sincos(th, &sn, &cs);
         const double fa = (double)(-1 * fwd) * sn;   // F_x(0,2)
         const double fb = (double)fwd * cs;          // F_x(1,2)
-        const float dd = fwd + p.v_d;
-        const double cv = cs * p.V00, sv = sn * p.V00;
+        const float dd = fwd + nz.v_d;
+        const double cv = cs * nz.V00, sv = sn * nz.V00;
         const double q00 = cv * cs, q01 = cv * sn, q10 = sv * cs, q11 = sv * sn;
         __syncthreads();
         if (tid == 0) {
             s_xp[0] = s_xt[0] + (double)dd * cs;
             s_xp[1] = s_xt[1] + (double)dd * sn;
-            s_xp[2] = rem2pi((th + (double)ang) + (double)p.v_th);
+            s_xp[2] = rem2pi((th + (double)ang) + (double)nz.v_th);
         }
         const double p22 = (double)PA[(size_t)2 * ld0 + 2];
         for (int e = tid; e < n0 * n0; e += kBigTpb) {
@@ -153,7 +154,7 @@ __global__ __launch_bounds__(kBigTpb) void ekf_big_step_kernel(const EkfStepPara
                 t = t + a2 * (c == 0 ? fa : fb);
             }
             if (r < 2 && c < 2) t = t + (r == 0 ? (c == 0 ? q00 : q01) : (c == 0 ? q10 : q11));   // + F_v V F_v^T
-            if (r == 2 && c == 2) t = t + p.V11;
+            if (r == 2 && c == 2) t = t + nz.V11;
             PB[(size_t)r * ldw + c] = t;
         }
     }
@@ -207,8 +208,8 @@ __global__ __launch_bounds__(kBigTpb) void ekf_big_step_kernel(const EkfStepPara
                 s_sc[0] = -dx / dd; s_sc[1] = -dy / dd; s_sc[2] = dx / dd; s_sc[3] = dy / dd;           // H0 at columns 0, 1, ii, ii+1
                 s_sc[4] = dy / d2; s_sc[5] = -dx / d2; s_sc[6] = -dy / d2; s_sc[7] = dx / d2;           // H1 at columns 0, 1, ii, ii+1 (H1[2] = -1)
                 const float angf = (float)rem2pi(det_atan2(dy, dx) - s_xp[2]);
-                const float nu0f = r_m - dist - p.w_r;
-                const float nu1f = b_m - angf - p.w_b;
+                const float nu0f = r_m - dist - nz.w_r;
+                const float nu1f = b_m - angf - nz.w_b;
                 s_sc[8] = (double)nu0f; s_sc[9] = (double)nu1f;
             }
             __syncthreads();
@@ -233,8 +234,8 @@ __global__ __launch_bounds__(kBigTpb) void ekf_big_step_kernel(const EkfStepPara
                 S[1] = (((g0[0] * h10 + g0[1] * h11) + g0[2] * h12) + g0[ii] * h13) + g0[ii + 1] * h14;
                 S[2] = ((g1[0] * h00 + g1[1] * h01) + g1[ii] * h03) + g1[ii + 1] * h04;
                 S[3] = (((g1[0] * h10 + g1[1] * h11) + g1[2] * h12) + g1[ii] * h13) + g1[ii + 1] * h14;
-                S[0] = S[0] + p.W00;
-                S[3] = S[3] + p.W11;
+                S[0] = S[0] + nz.W00;
+                S[3] = S[3] + nz.W11;
                 if (!big_inv2x2_lu(S, Si)) s_i[2] |= SLAM_INST_S_SINGULAR;
                 s_sc[10] = Si[0]; s_sc[11] = Si[1]; s_sc[12] = Si[2]; s_sc[13] = Si[3];
             }
@@ -294,8 +295,8 @@ __global__ __launch_bounds__(kBigTpb) void ekf_big_step_kernel(const EkfStepPara
             }
             __syncthreads();
             if (tid == 0) {   // corner: (G_x P_vv) G_x^T + (G_z W) G_z^T
-                const double gw00 = c * p.W00, gw01 = g02 * p.W11;
-                const double gw10 = s * p.W00, gw11 = g12 * p.W11;
+                const double gw00 = c * nz.W00, gw01 = g02 * nz.W11;
+                const double gw10 = s * nz.W00, gw11 = g12 * nz.W11;
                 const double* Ra = PB + (size_t)no * ldw;
                 const double* Rb = PB + (size_t)(no + 1) * ldw;
                 const double v00 = ((Ra[0] + Ra[2] * g02) + gw00 * c) + gw01 * g02;

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "noise_row.h"
+
 namespace slam {
 
 // One launch = one timestep of EKF::update (ekf.cpp:37-179) for every instance of the batch, optionally
@@ -47,6 +49,9 @@ struct EkfStepParams {
     // ---- filter config after readCommonParams (filter.h:105-121), effective V / W ----
     float v_d, v_th, w_r, w_b;
     double V00, V11, W00, W11;
+    // per-instance noise (slam_set_noise_each), NULL = the scalars above and sV00 .. sW11 below, exactly the code path without rows:
+    // [B] rows on the device, instance b reads noise_each[b] once at kernel entry (sim_device.h: step_noise)
+    const NoiseRow* noise_each;
     int32_t id_known;
     float min_sep;
     // Messages longer than the size class holds (ekf_class_message_capacity).  0: none can occur (the LDS kernel alone).  Set by the host when

@@ -226,6 +226,9 @@ __global__ __launch_bounds__(64 * W, (W >= 2 ? 4 : SLAM_W1_WAVES)) void ekf_step
     const int b = blockIdx.x;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
+    // the instance's noise values: its row of slam_set_noise_each or the scalars of the block; read once, before anything is stored, and
+    // held in scalar registers for every timestep of the launch
+    const StepNoise nz = step_noise(p, b);
     if (p.long_mode == 1) {   // (workgroup-uniform) a message this size class cannot hold: the streamed kernel's launch takes the instance (ekf_kernel.h)
         const int kk = p.meas_count_in[b];
         if ((kk < p.k_stride_in ? kk : p.k_stride_in) > p.long_cap) return;

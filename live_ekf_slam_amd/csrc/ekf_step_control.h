@@ -20,8 +20,8 @@
         num = neg ? -num : num;
         const double q = num / (hl < 4 ? dd : d2);
         const float angf = (float)rem2pi(det_atan2(dy, dx) - s_xp[2]);
-        const float nu0f = r_m - dist - p.w_r;     // float arithmetic (ekf.cpp:130-131)
-        const float nu1f = b_m - angf - p.w_b;
+        const float nu0f = r_m - dist - nz.w_r;     // float arithmetic (ekf.cpp:130-131)
+        const float nu1f = b_m - angf - nz.w_b;
         nu0 = (double)nu0f; nu1 = (double)nu1f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) H[j] = rdlane(q, j);
@@ -38,8 +38,8 @@
         S[1] = (((g0x * h10 + g1x * h11) + g2x * h12) + gix * h13) + gjx * h14;
         S[2] = ((g0y * h00 + g1y * h01) + giy * h03) + gjy * h04;
         S[3] = (((g0y * h10 + g1y * h11) + g2y * h12) + giy * h13) + gjy * h14;
-        S[0] = S[0] + p.W00;
-        S[3] = S[3] + p.W11;
+        S[0] = S[0] + nz.W00;
+        S[3] = S[3] + nz.W11;
         return inv2x2_lu(S, Si);
     };
 

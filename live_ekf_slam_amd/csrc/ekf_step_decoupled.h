@@ -179,7 +179,7 @@
                                 tv = tv + a2 * (cc == 0 ? fa : fb);
                             }
                             if (r < 2 && cc < 2) tv = tv + ps[5 + 2 * r + cc];
-                            if (r == 2 && cc == 2) tv = tv + p.V11;
+                            if (r == 2 && cc == 2) tv = tv + nz.V11;
                             return tv;
                         };
                         double n_r0 = 0.0, n_r1 = 0.0, n_c0 = 0.0, n_c1 = 0.0, n_22 = 0.0;

@@ -261,7 +261,7 @@
                     t = t + a2 * (cc == 0 ? fa : fb);
                 }
                 if (r < 2 && cc < 2) t = t + ps[5 + 2 * r + cc];    // + F_v V F_v^T
-                if (r == 2 && cc == 2) t = t + p.V11;
+                if (r == 2 && cc == 2) t = t + nz.V11;
                 return t;
             };
             // only rows 0,1 / cols 0,1 / (2,2) of P change: thin rows 0,1 and thin cols 0,1 entirely ...
@@ -394,8 +394,8 @@
                 __syncthreads();
                 if (tid == 0) {  // corner: (G_x P_vv) G_x^T + (G_z W) G_z^T
                     const double c = s_sc[2], s = s_sc[3];
-                    const double gw00 = c * p.W00, gw01 = g02 * p.W11;   // (G_z W) row 0
-                    const double gw10 = s * p.W00, gw11 = g12 * p.W11;   // (G_z W) row 1
+                    const double gw00 = c * nz.W00, gw01 = g02 * nz.W11;   // (G_z W) row 0
+                    const double gw10 = s * nz.W00, gw11 = g12 * nz.W11;   // (G_z W) row 1
                     const double* Ra = s_R + sa * LDP;
                     const double* Rb = s_R + sb * LDP;
                     const double v00 = ((Ra[0] + Ra[2] * g02) + gw00 * c) + gw01 * g02;

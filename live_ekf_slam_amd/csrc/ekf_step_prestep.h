@@ -65,7 +65,7 @@
         const double* const map = sim_map(p, b);
         const double lmx0 = lane < Lm ? map[2 * lane] : 0.0, lmy0 = lane < Lm ? map[2 * lane + 1] : 0.0;
         const int kr = sim_wave<KCAP, false>(p, b, lane, fwd_n, ang_n, p.step + (uint32_t)tn, map, Lm, tx, ty, tth, lmx0, lmy0,
-                                             s_meas + sq * 3 * KCAP);   // the true pose goes to HBM in finish()
+                                             s_meas + sq * 3 * KCAP, nz.sim);   // the true pose goes to HBM in finish()
         if (lane == 0) {
             s_keep[0] = tx; s_keep[1] = ty; s_keep[2] = tth;
             s_tru[sq * 6 + 3] = tx; s_tru[sq * 6 + 4] = ty; s_tru[sq * 6 + 5] = tth;
@@ -92,13 +92,13 @@
             const double x0 = (double)(ST)xv[0], x1 = (double)(ST)xv[1], th = (double)(ST)xv[2];
             double sn, cs;
             det_sincos(th, &sn, &cs);
-            const float dd = fwd_n + p.v_d;
-            const double cv = cs * p.V00, sv = sn * p.V00;
+            const float dd = fwd_n + nz.v_d;
+            const double cv = cs * nz.V00, sv = sn * nz.V00;
             if (lane == 0) {
                 nx[0] = kraw;
                 ps[0] = x0 + (double)dd * cs;
                 ps[1] = x1 + (double)dd * sn;
-                ps[2] = rem2pi((th + (double)ang_n) + (double)p.v_th);
+                ps[2] = rem2pi((th + (double)ang_n) + (double)nz.v_th);
                 ps[3] = (double)(-1 * fwd_n) * sn;  // F_x(0,2)
                 ps[4] = (double)fwd_n * cs;         // F_x(1,2)
                 ps[5] = cv * cs; ps[6] = cv * sn; ps[7] = sv * cs; ps[8] = sv * sn;

@@ -19,6 +19,7 @@
 #include "capi_internal.h"
 #include "consistency_kernel.h"
 #include "host/config_parse.h"
+#include "host/noise_pack.h"
 #include "ekf_kernel.h"
 #include "monitor_kernel.h"
 #include "nav_kernel.h"
@@ -145,6 +146,9 @@ struct slam_handle {
     DevBuf<double> dmaps; DevBuf<int32_t> dLs; int map_stride = 0; bool maps_each = false;
     std::vector<double> hmaps; std::vector<int32_t> hLs;
     DevBuf<float> dcmd_each;                          // per-instance commands of the launches of one call: [T][B][2]
+    // slam_set_noise_each: [B] packed rows the step kernels read (noise_each: they are set) and the caller's rows for the shadow
+    DevBuf<slam::NoiseRow> dnoise; bool noise_each = false;
+    std::vector<slam_noise> hnoise;
     bool pred_each = false;                           // UKF: slam_predict_each done, the pending update stage reads dcmd_each
     DevBuf<float> dpose_each; DevBuf<double> dstart_each;   // slam_init_each: EKF [B][3] start poses; [B][4] UKF x_t heads + [B][3] true poses
     // slam_consistency: [3][B] nees_full, nees_pose, map_rms and [2][B] dof, flags on the device; the packed triangles of one chunk of
@@ -194,6 +198,7 @@ template <class Params>
 void set_each_inputs(const slam_handle* h, Params& p, const float* d_cmd_each) {
     if (h->maps_each) { p.map_each = h->dmaps; p.L_each = h->dLs; p.map_stride = h->map_stride; }
     p.cmd_each = d_cmd_each;
+    p.noise_each = h->noise_each ? h->dnoise.get() : nullptr;
 }
 
 void fill_ekf_params(slam_handle* h, slam::EkfStepParams& p, const float cmd[2], int sim, int long_cap, const float* meas, const int32_t* count,
@@ -1273,6 +1278,7 @@ int slam_track_instance(slam_handle* h, int inst) {
     if (!h->hmap.empty()) rc = slam_set_map(s, h->hmap.data(), (int)(h->hmap.size() / 2));
     if (!rc && h->maps_each)   // the instance's own map (set after the shared one, which it replaces)
         rc = slam_set_maps(s, h->hmaps.data() + (size_t)inst * h->map_stride * 2, h->hLs.data() + inst, h->map_stride);
+    if (!rc && h->noise_each) rc = slam_set_noise_each(s, h->hnoise.data() + inst);   // the instance's noise row
     if (!rc && h->inited) {
         // the instance's state as it is now: same slab layout (pstride / xstride depend on L_max and dtype only)
         const size_t b = (size_t)inst, e = (size_t)h->esz;
@@ -1608,6 +1614,47 @@ int slam_set_maps(slam_handle* h, const double* maps, const int32_t* L, int L_st
         h->hLs.assign(L, L + B);
     }
     if (h->shadow) return slam_set_maps(h->shadow, maps + (size_t)h->tracked * L_stride * 2, L + h->tracked, L_stride);
+    return SLAM_OK;
+}
+
+int slam_noise_from_config(const slam_config* cfg, slam_noise* out) {
+    if (!cfg || !out) return fail(SLAM_ERR_ARG, "NULL argument");
+    slam_host::noise_from_config(*cfg, out);
+    return SLAM_OK;
+}
+
+int slam_set_noise_each(slam_handle* h, const slam_noise* rows) {
+    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
+    const size_t B = (size_t)h->B;
+    std::vector<slam::NoiseRow> packed(rows ? B : 0);
+    if (rows) {
+        size_t bad = 0; const char* field = nullptr;
+        if (slam_host::noise_pack(rows, B, h->cfg.replicate_vw_quirk, packed.data(), &bad, &field))
+            return fail(SLAM_ERR_ARG, "instance %zu: noise field %s is not finite", bad, field);
+    }
+    TRY(flush_lazy(h));   // the timesteps accepted so far keep the values they were accepted with
+    if (h->predicted) return fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev first");
+    HIP_TRY(hipSetDevice(h->device));
+    // the shadow of slam_track_instance first (its row, or back to its config): if that fails, the batch keeps the rows it had
+    if (h->shadow) TRY(slam_set_noise_each(h->shadow, rows ? rows + h->tracked : nullptr));
+    if (!rows) {
+        h->noise_each = false; h->hnoise.clear();   // (the launches in flight keep reading dnoise: it stays allocated)
+        return SLAM_OK;
+    }
+    if (h->dnoise.cap() < B) {   // the new block first: a failure leaves the handle with the rows it had
+        DevBuf<slam::NoiseRow> d;
+        HIP_TRY(d.reserve(B));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->dnoise = std::move(d);
+    } else {
+        HIP_TRY(hipStreamSynchronize(h->stream));   // the launches that read the old rows are done
+    }
+    for (int i = 0; i < 3; ++i)
+        if (h->aux_stream[i]) HIP_TRY(hipStreamSynchronize(h->aux_stream[i]));
+    HIP_TRY(hipMemcpyAsync(h->dnoise, packed.data(), sizeof(slam::NoiseRow) * B, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->noise_each = true;
+    h->hnoise.assign(rows, rows + B);
     return SLAM_OK;
 }
 

@@ -208,6 +208,7 @@ __global__ __launch_bounds__(kTpb) void ukf_big_sqrt_kernel(const UkfStepParams 
 __global__ __launch_bounds__(kTpb) void ukf_big_step_kernel(const UkfStepParams p) {
     extern __shared__ double sm[];
     const int b = blockIdx.x + p.b_off, tid = threadIdx.x, lane = tid & 63;
+    const StepNoise nz = step_noise(p, b);   // the instance's noise values (its row of slam_set_noise_each or the block's scalars), read once
     const int nmax = 4 + 2 * p.L_max, nsmax = 2 * nmax + 1;
     double* const s_xt = sm;                      // [nmax]
     double* const s_xp = s_xt + nmax;             // [nmax]
@@ -251,7 +252,7 @@ __global__ __launch_bounds__(kTpb) void ukf_big_step_kernel(const UkfStepParams 
             const double* const map = sim_map(p, b);
             const double lmx = lane < Lm ? map[2 * lane] : 0.0, lmy = lane < Lm ? map[2 * lane + 1] : 0.0;
             const float fwd = p.cmd_each ? p.cmd_each[2 * (size_t)b] : p.fwd, ang = p.cmd_each ? p.cmd_each[2 * (size_t)b + 1] : p.ang;
-            const int cnt = sim_wave<(1 << 30)>(p, b, lane, fwd, ang, p.step, map, Lm, tx, ty, tth, lmx, lmy, s_meas);   // stores the new true pose
+            const int cnt = sim_wave<(1 << 30)>(p, b, lane, fwd, ang, p.step, map, Lm, tx, ty, tth, lmx, lmy, s_meas, nz.sim);   // stores the new true pose
             if (lane == 0) { s_i[1] = cnt; s_sc[24] = tx; s_sc[25] = ty; }
         }
     } else {
@@ -271,7 +272,7 @@ __global__ __launch_bounds__(kTpb) void ukf_big_step_kernel(const UkfStepParams 
 
     // ---- sigma points through the motion model (ukf.cpp:214-226,125-135); only rows 0..3 change ----
     const float u_d = p.cmd_each ? p.cmd_each[2 * (size_t)b] : p.fwd, u_th = p.cmd_each ? p.cmd_each[2 * (size_t)b + 1] : p.ang;
-    const float dd = u_d + p.v_d;
+    const float dd = u_d + nz.v_d;
     for (int i = tid; i < ns; i += kTpb) {
         double v[4];
 #pragma unroll
@@ -290,7 +291,7 @@ __global__ __launch_bounds__(kTpb) void ukf_big_step_kernel(const UkfStepParams 
             s_X4[0 * ns + i] = v[0] + (double)dd * cy;
             s_X4[1 * ns + i] = v[1] + (double)dd * sy;
         }
-        const float new_yaw = (float)remainder((double)(yaw + u_th + p.v_th), kTwoPi);   // float adds (ukf.cpp:131)
+        const float new_yaw = (float)remainder((double)(yaw + u_th + nz.v_th), kTwoPi);   // float adds (ukf.cpp:131)
         double sn, cn;
         tsc(new_yaw, p.float_trig, &sn, &cn);
         s_X4[2 * ns + i] = cn;
@@ -327,10 +328,10 @@ __global__ __launch_bounds__(kTpb) void ukf_big_step_kernel(const UkfStepParams 
     if (tid == 0) {
         double sy, cy;
         tsc(yaw_t, p.float_trig, &sy, &cy);
-        Pw[0] = Pw[0] + p.V00 * cy;
-        Pw[(size_t)1 * n + 1] = Pw[(size_t)1 * n + 1] + p.V00 * sy;
-        Pw[(size_t)2 * n + 2] = Pw[(size_t)2 * n + 2] + p.V11 * cy;
-        Pw[(size_t)3 * n + 3] = Pw[(size_t)3 * n + 3] + p.V11 * sy;
+        Pw[0] = Pw[0] + nz.V00 * cy;
+        Pw[(size_t)1 * n + 1] = Pw[(size_t)1 * n + 1] + nz.V00 * sy;
+        Pw[(size_t)2 * n + 2] = Pw[(size_t)2 * n + 2] + nz.V11 * cy;
+        Pw[(size_t)3 * n + 3] = Pw[(size_t)3 * n + 3] + nz.V11 * sy;
     }
     __syncthreads();
 
@@ -360,9 +361,9 @@ __global__ __launch_bounds__(kTpb) void ukf_big_step_kernel(const UkfStepParams 
         const double mx = p.loc ? (double)p.mapf[3 * j + 1] : 0.0, my = p.loc ? (double)p.mapf[3 * j + 2] : 0.0;
         for (int i = tid; i < ns; i += kTpb) {   // sensing model of every sigma point (yaw from x_t)
             const double dx = (p.loc ? mx : xel(li, i)) - xel(0, i), dy = (p.loc ? my : xel(li + 1, i)) - xel(1, i);
-            s_Z0[i] = sqrt(dx * dx + dy * dy) + (double)p.w_r;
+            s_Z0[i] = sqrt(dx * dx + dy * dy) + (double)nz.w_r;
             const double yaw_i = p.yaw_sigma ? (double)yawf(xel(2, i), xel(3, i)) : (double)yaw_t;   // quirk D-9: from x_t
-            s_Z1[i] = remainder((det_atan2(dy, dx) - yaw_i) + (double)p.w_b, kTwoPi);
+            s_Z1[i] = remainder((det_atan2(dy, dx) - yaw_i) + (double)nz.w_b, kTwoPi);
         }
         __syncthreads();
         if (tid == 0) {   // z_est (the bearing component is never accumulated, ukf.cpp:310-314 - quirk D-8 - unless switched) and S
@@ -378,7 +379,7 @@ __global__ __launch_bounds__(kTpb) void ukf_big_step_kernel(const UkfStepParams 
                 const double a0 = ww * d0, a1 = ww * d1;
                 S[0] = S[0] + a0 * d0; S[1] = S[1] + a0 * d1; S[2] = S[2] + a1 * d0; S[3] = S[3] + a1 * d1;
             }
-            S[0] = S[0] + p.W00; S[1] = S[1] + 0.0; S[2] = S[2] + 0.0; S[3] = S[3] + p.W11;
+            S[0] = S[0] + nz.W00; S[1] = S[1] + 0.0; S[2] = S[2] + 0.0; S[3] = S[3] + nz.W11;
             double Si[4];
             if (!inv2(S, Si)) s_i[2] |= SLAM_INST_S_SINGULAR;
             s_sc[0] = z0;
@@ -444,7 +445,7 @@ __global__ __launch_bounds__(kTpb) void ukf_big_step_kernel(const UkfStepParams 
     int bad = 0;
     for (int e = tid; e < n_fin * n_fin; e += kTpb) {
         const int r = e / n_fin, c = e - r * n_fin;
-        const double v = (r < n && c < n) ? Pw[(size_t)r * n + c] : ((r == c) ? (((r - n) & 1) ? p.W11 : p.W00) : 0.0);
+        const double v = (r < n && c < n) ? Pw[(size_t)r * n + c] : ((r == c) ? (((r - n) & 1) ? nz.W11 : nz.W00) : 0.0);
         bad |= !isfinite(v);
         Pout[e] = v;
     }

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "noise_row.h"
+
 namespace slam {
 
 // One timestep of UKF::update (ukf.cpp:161-372) for every instance = two launches:
@@ -37,6 +39,7 @@ struct UkfStepParams {
     // ---- filter config (filter.h:105-121) ----
     float v_d, v_th, w_r, w_b;
     double V00, V11, W00, W11;
+    const NoiseRow* noise_each;   // [B] per-instance noise rows (slam_set_noise_each), indexed by the GLOBAL instance b; NULL = the scalars here and below
     int32_t float_trig;  // unqualified cos/sin(float): float overload (1) or double function (0)
     int32_t acc_zest1, yaw_sigma;   // quirk switches ukf_accumulate_zest1 / ukf_sensing_yaw_from_sigma (include/slam_batch.h), 0 = reference
     // ---- simulator config ----

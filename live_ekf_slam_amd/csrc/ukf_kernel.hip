@@ -969,6 +969,7 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 128 && !PROF) ? SLAM_UKF
     __shared__ int s_misc[8];                 // k, n_upd, n_ins, capacity, singular
 
     const int b = blockIdx.x + p.b_off, tid = threadIdx.x, lane = tid & 63;
+    const StepNoise nz = step_noise(p, b);   // the instance's noise values (its row of slam_set_noise_each or the block's scalars), read once
     if (p.long_mode == 3) {   // (workgroup-uniform) a message this size class cannot hold: the streamed kernel's launch takes the instance (ukf_kernel.h)
         const int kk = p.meas_count_in[b];
         if ((kk < p.k_stride_in ? kk : p.k_stride_in) > p.long_cap) return;
@@ -1008,7 +1009,7 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 128 && !PROF) ? SLAM_UKF
             const int Lm = sim_map_size(p, b);
             const double* const map = sim_map(p, b);
             const float fwd = p.cmd_each ? p.cmd_each[2 * (size_t)b] : p.fwd, ang = p.cmd_each ? p.cmd_each[2 * (size_t)b + 1] : p.ang;
-            const int cnt = sim_wave<KCAP>(p, b, lane, fwd, ang, p.step, map, Lm, tx, ty, tth, lmx, lmy, s_meas);
+            const int cnt = sim_wave<KCAP>(p, b, lane, fwd, ang, p.step, map, Lm, tx, ty, tth, lmx, lmy, s_meas, nz.sim);
             if (lane == 0) s_misc[0] = cnt;
         }
     } else {
@@ -1058,7 +1059,7 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 128 && !PROF) ? SLAM_UKF
 
     // ---- sigma points through the motion model (ukf.cpp:214-226,125-135); only rows 0..3 change ----
     const float u_d = p.cmd_each ? p.cmd_each[2 * (size_t)b] : p.fwd, u_th = p.cmd_each ? p.cmd_each[2 * (size_t)b + 1] : p.ang;
-    const float dd = u_d + p.v_d;
+    const float dd = u_d + nz.v_d;
     for (int i = tid; i < ns; i += TPB) {
         double v[4];
 #pragma unroll
@@ -1077,7 +1078,7 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 128 && !PROF) ? SLAM_UKF
             sX4[0 * ns + i] = v[0] + (double)dd * cy;
             sX4[1 * ns + i] = v[1] + (double)dd * sy;
         }
-        const float new_yaw = (float)remainder((double)(yaw + u_th + p.v_th), kTwoPi);   // float adds (ukf.cpp:131)
+        const float new_yaw = (float)remainder((double)(yaw + u_th + nz.v_th), kTwoPi);   // float adds (ukf.cpp:131)
         double sn, cn;
         tsincos(new_yaw, p.float_trig, &sn, &cn);
         sX4[2 * ns + i] = cn;
@@ -1123,7 +1124,7 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 128 && !PROF) ? SLAM_UKF
         const float yaw = yaw_of(s_xt[2], s_xt[3]);
         double sy, cy;
         tsincos(yaw, p.float_trig, &sy, &cy);
-        s_sc[0] = p.V00 * cy; s_sc[1] = p.V00 * sy; s_sc[2] = p.V11 * cy; s_sc[3] = p.V11 * sy;
+        s_sc[0] = nz.V00 * cy; s_sc[1] = nz.V00 * sy; s_sc[2] = nz.V11 * cy; s_sc[3] = nz.V11 * sy;
         s_sc[4] = (double)yaw;
     }
     __syncthreads();
@@ -1146,10 +1147,10 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 128 && !PROF) ? SLAM_UKF
             const double mx = p.loc ? (double)p.mapf[3 * (packed >> 8) + 1] : 0.0, my = p.loc ? (double)p.mapf[3 * (packed >> 8) + 2] : 0.0;
             for (int i = tid; i < ns; i += TPB) {
                 const double dx = (p.loc ? mx : xpred_elem(li, i)) - xpred_elem(0, i), dy = (p.loc ? my : xpred_elem(li + 1, i)) - xpred_elem(1, i);
-                sZ0[i] = sqrt(dx * dx + dy * dy) + (double)p.w_r;
+                sZ0[i] = sqrt(dx * dx + dy * dy) + (double)nz.w_r;
                 // the sensing model's yaw comes from x_t (quirk D-9, ukf.cpp:139) unless switched to the sigma point's own rows 2, 3
                 const double yaw_i = p.yaw_sigma ? (double)yaw_of(xpred_elem(2, i), xpred_elem(3, i)) : yaw_s;
-                const double z1 = remainder((det_atan2(dy, dx) - yaw_i) + (double)p.w_b, kTwoPi);
+                const double z1 = remainder((det_atan2(dy, dx) - yaw_i) + (double)nz.w_b, kTwoPi);
                 sD1[i] = p.acc_zest1 ? z1 : remainder(z1 - 0.0, kTwoPi);   // z_est(1) stays 0 (quirk D-8, ukf.cpp:310-314); switched off: the leader subtracts it below
             }
             __syncthreads();
@@ -1180,7 +1181,7 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 128 && !PROF) ? SLAM_UKF
                     const double a0 = wi * d0, a1 = wi * d1;
                     S[0] = S[0] + a0 * d0; S[1] = S[1] + a0 * d1; S[2] = S[2] + a1 * d0; S[3] = S[3] + a1 * d1;
                 }
-                S[0] = S[0] + p.W00; S[1] = S[1] + 0.0; S[2] = S[2] + 0.0; S[3] = S[3] + p.W11;
+                S[0] = S[0] + nz.W00; S[1] = S[1] + 0.0; S[2] = S[2] + 0.0; S[3] = S[3] + nz.W11;
                 if (!inv2x2_lu_ukf(S, Si)) s_misc[4] = 1;
                 s_sc[5] = z0;
                 s_sc[6] = S[0]; s_sc[7] = S[1]; s_sc[8] = S[2]; s_sc[9] = S[3];
@@ -1391,7 +1392,7 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 128 && !PROF) ? SLAM_UKF
     }
     for (int e = tid; e < n_fin * n_fin; e += TPB) {   // new rows / cols: zeros, W on the diagonal
         const int r = e / n_fin, c = e - r * n_fin;
-        if (r >= n || c >= n) Pout[e] = (r == c) ? (((r - n) & 1) ? p.W11 : p.W00) : 0.0;
+        if (r >= n || c >= n) Pout[e] = (r == c) ? (((r - n) & 1) ? nz.W11 : nz.W00) : 0.0;
     }
     __syncthreads();
     UKF_STAMP(7);

@@ -14,6 +14,7 @@ import numpy as np
 from . import _lib
 from .config import SlamConfig, NavConfig, default_config, default_nav_config, EKF_SLAM, UKF_LOC, UKF_SLAM, F64
 from .config import MonitorConfig, default_monitor_config, MONITOR_SHARED, MONITOR_EACH, MONITOR_NAV
+from .config import Noise
 
 
 def _d(a):
@@ -161,6 +162,19 @@ class BatchedFilter:
         if cnt.shape != (self.batch,) or np.any(cnt <= 0) or np.any(cnt > m.shape[1]):
             raise ValueError(f"counts: expected {self.batch} landmark counts in [1, {m.shape[1]}]")
         _lib.check(_lib.lib().slam_set_maps(self.h, _d(m), _i(cnt), m.shape[1]))
+
+    def set_noise(self, rows):
+        """Per-instance noise parameters (slam_set_noise_each): `rows` = config.noise_rows(...) (a ctypes array of `batch` Noise rows,
+        or a sequence of them); None returns to the config of readParams.  Inputs, not state: set them again after load_state."""
+        self._need()
+        if rows is None:
+            _lib.check(_lib.lib().slam_set_noise_each(self.h, None))
+            return
+        if not (isinstance(rows, C.Array) and rows._type_ is Noise):
+            rows = (Noise * len(rows))(*rows)
+        if len(rows) != self.batch:
+            raise ValueError(f"expected {self.batch} noise rows, got {len(rows)}")
+        _lib.check(_lib.lib().slam_set_noise_each(self.h, rows))
 
     # -- Filter::update(Command, Float32MultiArray) (filter.h:61) for every instance --
     def update(self, cmdMsg, lmMeasMsg, meas_count=None):
