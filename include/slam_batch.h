@@ -394,6 +394,82 @@ int slam_last_monitor_work(slam_handle* h, double* monitor_ms, double* total_ms)
 int slam_monitor_instance_host(int filter_kind, const double* x, const double* P3, const double truth[3], int32_t status, double* err_pos,
                                double* err_yaw, double* nees_pose, int32_t* flags);
 
+/* ---- innovation (NIS) statistics: judging a filter WITHOUT the truth (csrc/innovation_kernel.h) ------------------------------------------
+ * slam_consistency and the monitor compare the estimate with the simulator's truth, which a handle fed recorded measurements does not
+ * have.  The innovation test needs none: for each landmark update with innovation nu = z - h(x_pred) and innovation covariance
+ * S = H P_pred H^T + W, NIS = nu^T S^-1 nu is chi-square with 2 degrees of freedom if the filter is consistent.  nu and S exist only inside
+ * the step kernel and only for an instant; slam_innovation computes them BEFORE the step, from the pre-step state and the message the step
+ * will be given, on the block of P that EKF::update confines itself to for this message (pose + the message's mapped landmarks, at most
+ * 35 x 35): the same scalar operations on the same operands, so every value is what the step computes, bit for bit.
+ * Per detection slot l, in message order, six doubles: (nis, nu_r, nu_b, S00, S01, S11); slots that are insertions, capacity skips or beyond
+ *   the count hold NaN.  nis = nu_r (Si00 nu_r + Si01 nu_b) + nu_b (Si10 nu_r + Si11 nu_b), Si the PartialPivLU inverse of ekf.cpp:135.
+ *   S01 = (S(0,1) + S(1,0)) / 2: the filter keeps P symmetric only to rounding, the step inverts S as it is, and nu^T S^-1 nu depends on S
+ *   through its symmetric part (to second order in the asymmetry), so the reported values reproduce nis to rounding.  A nu or S that is not
+ *   finite makes the slot's nis NaN without a flag.
+ * Per instance: nis_sum (the finite nis in ascending l; 0 over none), n_upd (update slots), n_new (insertion slots, counting those skipped
+ *   for capacity), post [12] = x_pred[0 .. 2] and the leading 3 x 3 block of P_pred, row-major, after the whole message and before the
+ *   storage rounding: what the step will leave in x_t and P_t (rounded to float for SLAM_F32), flags (slam_innovation_flags).
+ * Record, 16 doubles (counts as doubles): 0 instances evaluated, 1 INSTANCE_FROZEN, 2 TOO_LONG, 3 WOULD_FREEZE, 4 instances with S_SINGULAR,
+ *   5 updates with a finite nis, 6 insertions, 7 sum nis, 8 max nis (0 over none), 9 #{nis < nis_lo}, 10 #{nis > nis_hi}, 11 sum nu_r,
+ *   12 sum nu_b, 13 sum nu_r^2, 14 sum nu_b^2 (11 - 14 over the updates of entry 5), 15 reserved, 0.  Sums run in a fixed order that depends
+ *   on the batch size alone (per instance in message order, 256 consecutive instances per workgroup by a fixed tree, workgroups ascending).
+ * Honours slam_set_noise_each rows, slam_set_maps, the quirk switch ekf_landmark_from_x_pred, both storage types and every capacity class.
+ * Errors: SLAM_ERR_ARG (checked first, before the handle is looked at): a band that is not finite or not ordered, NULL cmds, NULL meas or
+ *   meas_count where they are read, k_stride <= 0, T < 0, an unknown source; NULL handle.  SLAM_ERR_UNSUPPORTED: the UKF kinds (their S
+ *   depends on all sigma points: no block closes), landmark_id_is_known = 0 (that association reads every landmark of x_pred after every
+ *   update).  SLAM_ERR_STATE: before slam_init; slam_innovation_run also: without a map for the simulator sources, NAV without a path, while
+ *   slam_track_instance is on, while a prediction is pending.
+ * Not covered: the UKF kinds; unknown ids; innovation autocorrelation / whiteness; gating or rejecting detections; slam_multi_*; the pose
+ *   graph; evaluation inside multi-step launches (slam_innovation_run steps once per tick). */
+#define SLAM_INNOV_MAX_DET 64   /* detections of one message beyond which the instance is TOO_LONG */
+#define SLAM_INNOV_MAX_LM 16    /* distinct mapped landmarks of one message beyond which the instance is TOO_LONG */
+enum slam_innovation_flags {
+    SLAM_INNOVATION_OK = 0,
+    SLAM_INNOVATION_INSTANCE_FROZEN = 1,   /* slam_status carries SLAM_INST_INDEX_OOR: the step skips the instance.  All values NaN, counts 0 */
+    SLAM_INNOVATION_WOULD_FREEZE = 2,      /* the message repeats an id it inserts: the step raises SLAM_INST_INDEX_OOR and rolls back.  All NaN */
+    SLAM_INNOVATION_S_SINGULAR = 4,        /* the 2 x 2 inverse failed on some slot: its nis is NaN and excluded; the replay goes on as the step does */
+    SLAM_INNOVATION_TOO_LONG = 8           /* more than SLAM_INNOV_MAX_DET detections or SLAM_INNOV_MAX_LM distinct mapped landmarks.  All NaN */
+};
+typedef struct slam_innovation_config {
+    double nis_lo, nis_hi;   /* the band of record entries 9 and 10 */
+} slam_innovation_config;
+/* -2 ln 0.975 and -2 ln 0.025: the 0.025 and 0.975 quantiles of chi-square with 2 degrees of freedom (0.0506356 and 7.3777589) */
+int slam_innovation_config_default(slam_innovation_config* cfg);
+/* What the next slam_step (cmd_each = 0: cmds [2]) or slam_step_each (cmd_each != 0: cmds [batch][2]) with these arguments will compute.
+ * cfg NULL: the defaults.  Host pointers; rec [16], nis_sum / n_upd / n_new / flags [batch], det [batch][SLAM_INNOV_MAX_DET][6],
+ * post [batch][12]; any output may be NULL.  Runs the queued timesteps first, computes on the handle's stream, returns with the results on
+ * the host and CHANGES NOTHING: a checkpoint before and after is byte-identical. */
+int slam_innovation(slam_handle* h, const slam_innovation_config* cfg, const float* cmds, int cmd_each, const float* meas,
+                    const int32_t* meas_count, int k_stride, double rec[16], double* nis_sum, int32_t* n_upd, int32_t* n_new, int32_t* flags,
+                    double* det, double* post);
+/* The same for slam_step_dev / slam_step_each_dev: d_meas, d_count and (cmd_each != 0) cmds are DEVICE pointers, read in stream order. */
+int slam_innovation_dev(slam_handle* h, const slam_innovation_config* cfg, const float* cmds, int cmd_each, const float* d_meas,
+                        const int32_t* d_count, int k_stride, double rec[16], double* nis_sum, int32_t* n_upd, int32_t* n_new, int32_t* flags,
+                        double* det, double* post);
+/* T ticks of {NAV: the controller launch; the innovation launches; the one-step launch}.  Sources SHARED (cmds [T][2]), EACH
+ * (cmds [T][batch][2]) and NAV (cmds not read): the simulator generates the messages, as in slam_monitor_run, and the innovation kernel
+ * regenerates each before the step does (the generator is counter based).  LOG: host-fed, cmds [T][2], meas [T][batch][k_stride][3],
+ * meas_count [T][batch]; meas, meas_count and k_stride are not read by the other sources.  State, truth, error sums, timestep, RNG and
+ * controller state advance bit for bit as in the plain run of the same inputs (slam_run_sim, slam_run_sim_each, slam_nav_run, a slam_step
+ * loop).  recs [T][16], nis_sum / n_upd / flags [T][batch]: tick t describes the step from t to t + 1; any may be NULL.  Long runs are
+ * processed in chunks of ticks exactly as slam_monitor_run does it (at most 4096 ticks, SLAM_MONITOR_LOG_BYTES, the LOG source's message
+ * rows counted in); chunking changes no bit. */
+enum slam_innovation_source { SLAM_INNOVATION_SHARED = 0, SLAM_INNOVATION_EACH = 1, SLAM_INNOVATION_NAV = 2, SLAM_INNOVATION_LOG = 3 };
+int slam_innovation_run(slam_handle* h, const slam_innovation_config* cfg, int source, const float* cmds, const float* meas,
+                        const int32_t* meas_count, int k_stride, int T, double* recs, double* nis_sum, int32_t* n_upd, int32_t* flags);
+/* Device time of the last slam_innovation_run in ms, as slam_last_monitor_work: everything, and the innovation launches alone, which
+ * needs slam_nav_set_timing(h, 1); without it *innovation_ms = -1. */
+int slam_last_innovation_work(slam_handle* h, double* innovation_ms, double* total_ms);
+/* TEST HOOK, not part of the filter interface: the per-instance function compiled for the HOST (the same source as the kernel, no device
+ * needed).  One instance: x [3 + 2 M], P row-major n x n with n = 3 + 2 M, ids [M], 0 <= M <= L_max, status = slam_instance_flags, cmd [2],
+ * meas [k][3] with k >= 0 (NULL for k = 0), noise: the filter fields of one slam_noise row with V_00 .. W_11 taken as the EFFECTIVE values
+ * (no replicate_vw_quirk mapping), lm_from_pred = the quirk switch, f32_storage != 0: x and P are rounded to float before they are read, as
+ * the handle stores them.  Outputs as slam_innovation for one instance (det [SLAM_INNOV_MAX_DET][6], post [12]); any may be NULL. */
+int slam_innovation_instance_host(const double* x, const double* P, const int32_t* ids, int M, int L_max, int32_t status, const float cmd[2],
+                                  const float* meas, int k, const slam_noise* noise, int lm_from_pred, int f32_storage,
+                                  const slam_innovation_config* cfg, double rec[16], double* nis_sum, int32_t* n_upd, int32_t* n_new,
+                                  int32_t* flags, double* det, double* post);
+
 /* ---- closed loop: commands from each instance's own estimate (goal_pursuit_node.py:23-50, pure_pursuit.py:17-161) ---------------------
  * The entry points above run open loop: every command is fixed before the run.  The reference's default launch (sim_base.launch,
  * precompute_trajectory false) closes the loop instead: goal_pursuit_node computes each Command from the state the filter has just published.

@@ -63,6 +63,10 @@ inline std::vector<float> packCommands(const std::vector<Command>& cmds, int bat
 // its [T][B] series.
 struct MonitorNow { double rec[16]; std::vector<double> err_pos, err_yaw, nees_pose; std::vector<int32_t> flags; };
 struct MonitorRun { std::vector<double> recs, err_pos, err_yaw, nees_pose; };
+// What innovation / innovationRun return (slam_innovation_*): one record, the [B] values, post [B][12] and det [B][SLAM_INNOV_MAX_DET][6]
+// of the step that follows; the [T][16] records of a run and, if asked for, its [T][B] series.
+struct Innovation { double rec[16]; std::vector<double> nis_sum, det, post; std::vector<int32_t> n_upd, n_new, flags; };
+struct InnovationRun { std::vector<double> recs, nis_sum; std::vector<int32_t> n_upd, flags; };
 // One start pose per instance (pose0 [B][3] {x, y, yaw}), optional true start poses (truth0 [B][3], empty = the config's init pose);
 // maps [B][L_stride][2] with L [B] landmarks each; commands [B] of one timestep or [T][B][2] floats of a run.
 #define SLAM_FILTER_EACH_METHODS                                                                                                          \
@@ -132,6 +136,38 @@ struct MonitorRun { std::vector<double> recs, err_pos, err_yaw, nees_pose; };
         check(slam_monitor_run(h_, cfg, source, c, T, n ? m.recs.data() : nullptr, per ? m.err_pos.data() : nullptr,                     \
                                per ? m.err_yaw.data() : nullptr, per ? m.nees_pose.data() : nullptr));                                   \
         return m;                                                                                                                        \
+    }                                                                                                                                    \
+    /* innovation statistics (slam_innovation_*, include/slam_batch.h; EKF-SLAM handles): what the next update with these arguments */  \
+    /* will compute, changing nothing.  cmds: one Command for the batch, or [B] of them                                              */  \
+    Innovation innovation(const std::vector<Command>& cmds, const float* meas, const int32_t* meas_count, int k_stride,                  \
+                          bool want_det = true, const slam_innovation_config* cfg = nullptr) {                                           \
+        need();                                                                                                                          \
+        const bool each = cmds.size() != 1;                                                                                              \
+        const std::vector<float> c = packCommands(cmds, each ? batch_ : 1);                                                              \
+        Innovation v; v.nis_sum.resize(batch_); v.post.resize(12 * (size_t)batch_); v.n_upd.resize(batch_); v.n_new.resize(batch_);      \
+        v.flags.resize(batch_); v.det.resize(want_det ? 6 * (size_t)SLAM_INNOV_MAX_DET * batch_ : 0);                                    \
+        check(slam_innovation(h_, cfg, c.data(), each ? 1 : 0, meas, meas_count, k_stride, v.rec, v.nis_sum.data(), v.n_upd.data(),      \
+                              v.n_new.data(), v.flags.data(), want_det ? v.det.data() : nullptr, v.post.data()));                        \
+        return v;                                                                                                                        \
+    }                                                                                                                                    \
+    /* source SLAM_INNOVATION_SHARED: cmds [T][2]; EACH: cmds [T][B][2]; NAV: cmds empty; LOG: cmds [T][2], meas [T][B][k_stride][3], */ \
+    /* meas_count [T][B] (not read by the other sources)                                                                             */  \
+    InnovationRun innovationRun(int source, const std::vector<float>& cmds, int T, bool series = false, const float* meas = nullptr,     \
+                                const int32_t* meas_count = nullptr, int k_stride = 0, const slam_innovation_config* cfg = nullptr) {    \
+        need();                                                                                                                          \
+        if (source == SLAM_INNOVATION_SHARED || source == SLAM_INNOVATION_LOG) checkSize(cmds.size(), 2 * (size_t)(T > 0 ? T : 0), "cmds [T][2]"); \
+        if (source == SLAM_INNOVATION_EACH) checkSize(cmds.size(), 2 * (size_t)(T > 0 ? T : 0) * batch_, "cmds [T][B][2]");              \
+        const size_t n = T > 0 ? (size_t)T : 0, per = series ? n * batch_ : 0;                                                           \
+        InnovationRun m; m.recs.resize(16 * n); m.nis_sum.resize(per); m.n_upd.resize(per); m.flags.resize(per);                         \
+        static const float none[2] = {0.f, 0.f};                                                                                         \
+        const float* c = source == SLAM_INNOVATION_NAV ? nullptr : (cmds.empty() ? none : cmds.data());                                  \
+        check(slam_innovation_run(h_, cfg, source, c, meas, meas_count, k_stride, T, n ? m.recs.data() : nullptr,                        \
+                                  per ? m.nis_sum.data() : nullptr, per ? m.n_upd.data() : nullptr, per ? m.flags.data() : nullptr));    \
+        return m;                                                                                                                        \
+    }                                                                                                                                    \
+    /* device ms of the last innovationRun: {the innovation launches alone (-1 without slam_nav_set_timing), everything}              */  \
+    std::pair<double, double> lastInnovationWork() {                                                                                     \
+        need(); double a = 0, b = 0; check(slam_last_innovation_work(h_, &a, &b)); return {a, b};                                        \
     }
 
 class Filter {  // filter.h:54-77

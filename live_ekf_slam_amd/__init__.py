@@ -3,7 +3,10 @@ kevin-robb/live_ekf_slam).  Numerics live in the HIP extension libslam_hip.so be
 from .config import SlamConfig, NavConfig, default_config, default_nav_config, EKF_SLAM, UKF_LOC, UKF_SLAM, F64, F32  # noqa: F401
 from .config import NAV_PP, NAV_DIRECT, NAV_LOOSE, NAV_TIGHT  # noqa: F401
 from .config import MonitorConfig, default_monitor_config, MONITOR_SHARED, MONITOR_EACH, MONITOR_NAV  # noqa: F401
+from .config import InnovationConfig, default_innovation_config, INNOVATION_SHARED, INNOVATION_EACH, INNOVATION_NAV, INNOVATION_LOG  # noqa: F401
+from .config import INNOV_MAX_DET, INNOV_MAX_LM  # noqa: F401
 from .navigation import PurePursuitBatch  # noqa: F401
 from .filters import BatchedEKF, BatchedUKF, BatchedUKFLoc, Command, MonitorResult, monitor_summary  # noqa: F401
+from .filters import InnovationResult, innovation_summary, innovation_instance_host  # noqa: F401
 from .pose_graph import BatchedPoseGraph, NaiveFilter  # noqa: F401
 from ._lib import SlamError  # noqa: F401

@@ -5,7 +5,7 @@ There is no CPU fallback: if the library is missing or a HIP call fails, an exce
 import ctypes as C
 import os
 
-from .config import SlamConfig, NavConfig, MonitorConfig, Noise
+from .config import SlamConfig, NavConfig, MonitorConfig, InnovationConfig, Noise
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # SLAM_HIP_LIB: another build of the same library, for A/B tuning sessions (tools/gpu_ab.sh); the product path is the
@@ -69,6 +69,14 @@ SIGNATURES = {
     "slam_monitor_run": (C.c_int, [_H, C.POINTER(MonitorConfig), C.c_int, _fp, C.c_int, _dp, _dp, _dp, _dp]),
     "slam_last_monitor_work": (C.c_int, [_H, _dp, _dp]),
     "slam_monitor_instance_host": (C.c_int, [C.c_int, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp, _ip]),
+    "slam_innovation_config_default": (C.c_int, [C.POINTER(InnovationConfig)]),
+    "slam_innovation": (C.c_int, [_H, C.POINTER(InnovationConfig), _fp, C.c_int, _fp, _ip, C.c_int, _dp, _dp, _ip, _ip, _ip, _dp, _dp]),
+    "slam_innovation_dev": (C.c_int, [_H, C.POINTER(InnovationConfig), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, _dp, _dp, _ip, _ip,
+                                      _ip, _dp, _dp]),
+    "slam_innovation_run": (C.c_int, [_H, C.POINTER(InnovationConfig), C.c_int, _fp, _fp, _ip, C.c_int, C.c_int, _dp, _dp, _ip, _ip]),
+    "slam_last_innovation_work": (C.c_int, [_H, _dp, _dp]),
+    "slam_innovation_instance_host": (C.c_int, [_dp, _dp, _ip, C.c_int, C.c_int, C.c_int32, _fp, _fp, C.c_int, C.POINTER(Noise), C.c_int, C.c_int,
+                                                C.POINTER(InnovationConfig), _dp, _dp, _ip, _ip, _ip, _dp, _dp]),
     "slam_nav_config_default": (C.c_int, [C.POINTER(NavConfig)]),
     "slam_nav_config_load": (C.c_int, [C.POINTER(NavConfig), C.c_char_p]),
     "slam_nav_set_path": (C.c_int, [_H, C.POINTER(NavConfig), _dp, C.c_int]),

@@ -101,6 +101,21 @@ class MonitorConfig(C.Structure):
 MONITOR_SHARED, MONITOR_EACH, MONITOR_NAV = 0, 1, 2
 
 
+class InnovationConfig(C.Structure):
+    """ctypes mirror of `slam_innovation_config` (include/slam_batch.h): the NIS band of the record."""
+    _fields_ = [("nis_lo", C.c_double), ("nis_hi", C.c_double)]
+
+
+INNOVATION_SHARED, INNOVATION_EACH, INNOVATION_NAV, INNOVATION_LOG = 0, 1, 2, 3
+INNOV_MAX_DET, INNOV_MAX_LM = 64, 16   # SLAM_INNOV_MAX_DET, SLAM_INNOV_MAX_LM
+
+
+def default_innovation_config() -> InnovationConfig:
+    """The chi-square quantiles at 0.025 and 0.975 for 2 degrees of freedom: -2 ln 0.975 and -2 ln 0.025."""
+    import math
+    return InnovationConfig(-2.0 * math.log(0.975), -2.0 * math.log(0.025))
+
+
 def default_monitor_config() -> MonitorConfig:
     """The chi-square quantiles at 0.025 and 0.975 for 3 degrees of freedom; no full evaluation."""
     return MonitorConfig(0.21579528262389785, 9.348403604496148, 0)

@@ -21,6 +21,8 @@
 //       Closed loop through the C++ mirror: setPath (the map's first three landmarks, the reference's controller defaults), runNav with the
 //       commands returned, navState.  The file gets int64 batch, the [ticks][batch][2] float commands, then remaining, finish_tick (int32)
 //       and integ, err_prev (doubles), batch values each.
+//   filter_driver innovation <batch> <L> <ticks> <dump.bin> [seed]
+//       The innovation statistics through the C++ mirror (run_innovation below says what the file gets).
 //   filter_driver monitor <batch> <L> <ticks> <dump.bin> [seed]
 //       The run monitor through the C++ mirror: monitorRun of the scenario's commands with the series and a full evaluation every 7th tick,
 //       then monitorNow.  The file gets int64 batch, the [ticks][16] records, the [ticks][batch] err_pos, err_yaw, nees_pose (doubles), then
@@ -224,6 +226,43 @@ static int run_monitor(int B, int L, int T, const char* dump_path, uint64_t seed
     return 0;
 }
 
+// The innovation statistics through the C++ mirror: innovationRun of the scenario's commands with the series, then one innovation() of a
+// hand-made message (every instance: its first mapped landmark, if any, at 2 m / 0.1 rad, and the new id 999).  The file gets int64 batch,
+// the [ticks][16] records, the [ticks][batch] nis_sum (doubles), n_upd and flags (int32), then innovation()'s record (16 doubles), nis_sum
+// [batch], post [batch][12], det [batch][SLAM_INNOV_MAX_DET][6] (doubles), n_upd, n_new, flags (int32, [batch] each).
+static int run_innovation(int B, int L, int T, const char* dump_path, uint64_t seed) {
+    const Scenario sc = make_scenario(seed, L, T);
+    BatchedEKF ekf(B, L);
+    slam_config cfg;
+    check(slam_config_default(&cfg));
+    ekf.readParams(cfg);
+    ekf.init(0.f, 0.f, 0.f);
+    ekf.setMap(sc.map_xy);
+    const InnovationRun run = ekf.innovationRun(SLAM_INNOVATION_SHARED, sc.cmds, T, true);
+    std::vector<float> meas((size_t)B * 2 * 3);
+    std::vector<int32_t> count((size_t)B, 2), ids((size_t)L);
+    for (int b = 0; b < B; ++b) {
+        int32_t M = 0;
+        check(slam_get_state(ekf.handle(), b, nullptr, nullptr, &M, ids.data(), nullptr));
+        const float first[3] = {M > 0 ? (float)ids[0] : 998.f, 2.f, 0.1f}, second[3] = {999.f, 1.5f, -0.2f};
+        for (int i = 0; i < 3; ++i) { meas[(size_t)b * 6 + i] = first[i]; meas[(size_t)b * 6 + 3 + i] = second[i]; }
+    }
+    Command c; c.fwd = 0.05f; c.ang = 0.01f;
+    const Innovation now = ekf.innovation({c}, meas.data(), count.data(), 2);
+    FILE* f = std::fopen(dump_path, "wb");
+    if (!f) throw std::runtime_error(std::string("cannot write ") + dump_path);
+    const int64_t hd = B;
+    std::fwrite(&hd, sizeof(int64_t), 1, f);
+    for (const std::vector<double>* v : {&run.recs, &run.nis_sum}) std::fwrite(v->data(), sizeof(double), v->size(), f);
+    for (const std::vector<int32_t>* v : {&run.n_upd, &run.flags}) std::fwrite(v->data(), sizeof(int32_t), v->size(), f);
+    std::fwrite(now.rec, sizeof(double), 16, f);
+    for (const std::vector<double>* v : {&now.nis_sum, &now.post, &now.det}) std::fwrite(v->data(), sizeof(double), v->size(), f);
+    for (const std::vector<int32_t>* v : {&now.n_upd, &now.n_new, &now.flags}) std::fwrite(v->data(), sizeof(int32_t), v->size(), f);
+    std::fclose(f);
+    std::printf("driver ok: innovation batch=%d L=%d ticks=%d evaluated=%g\n", B, L, T, now.rec[0]);
+    return 0;
+}
+
 // the global batch over several GPUs of the node from this one process (SURVEY.md section 8(e) "Host")
 static int run_multi(const std::string& kind, int64_t B, int L, int T, int gpus, uint64_t seed, int gather_mode) {
     const Scenario sc = make_scenario(seed, L, T);
@@ -313,6 +352,8 @@ int main(int argc, char** argv) {
         if (mode == "nav" && argc >= 6) return run_nav(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), argv[5], argc > 6 ? strtoull(argv[6], nullptr, 10) : 1234ull);
         if (mode == "monitor" && argc >= 6)
             return run_monitor(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), argv[5], argc > 6 ? strtoull(argv[6], nullptr, 10) : 1234ull);
+        if (mode == "innovation" && argc >= 6)
+            return run_innovation(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), argv[5], argc > 6 ? strtoull(argv[6], nullptr, 10) : 1234ull);
         if (mode == "pose_graph" && argc >= 5) return run_pose_graph(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), argc > 5 ? argv[5] : nullptr);
         std::fprintf(stderr, "usage: filter_driver stream <ekf|ukf|ukf_loc> <batch> <L_max> <stream.txt> <dump.bin>\n"
                              "       filter_driver run <ekf|ukf> <batch> <L> <steps> [seed]\n"
@@ -320,7 +361,8 @@ int main(int argc, char** argv) {
                              "       filter_driver pose_graph <batch> <L> <steps> [marginals dump.bin]\n"
                              "       filter_driver consistency <batch> <L> <steps> <dump.bin> [seed]\n"
                              "       filter_driver nav <batch> <L> <ticks> <dump.bin> [seed]\n"
-                             "       filter_driver monitor <batch> <L> <ticks> <dump.bin> [seed]\n");
+                             "       filter_driver monitor <batch> <L> <ticks> <dump.bin> [seed]\n"
+                             "       filter_driver innovation <batch> <L> <ticks> <dump.bin> [seed]\n");
         return 2;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "driver failed: %s\n", e.what());

@@ -21,6 +21,7 @@
 #include "host/config_parse.h"
 #include "host/noise_pack.h"
 #include "ekf_kernel.h"
+#include "innovation_kernel.h"
 #include "monitor_kernel.h"
 #include "nav_kernel.h"
 #include "slam_math.h"
@@ -176,6 +177,15 @@ struct slam_handle {
         std::vector<hipEvent_t> ev;
         double mon_ms = -1.0, total_ms = -1.0;
     } mon;
+    // slam_innovation_*: the staged message and per-instance commands of a host-fed evaluation (one chunk of ticks for the LOG source), the
+    // per-instance outputs ([B] nis_sum, [B][12] post, [B][16] contributions, the partial records, the records and the nis_sum series of a
+    // chunk; [B][64][6] detection slots when asked for; [3][ticks][B] n_upd, flags, n_new), the event pool and the device times of the last run
+    struct Inn {
+        DevBuf<float> dmeas, dcmd; DevBuf<int32_t> dcount;
+        DevBuf<double> dval, ddet, dpart, drec, dlog; DevBuf<int32_t> dint;
+        std::vector<hipEvent_t> ev;
+        double inn_ms = -1.0, total_ms = -1.0;
+    } inn;
 };
 
 namespace {
@@ -570,6 +580,7 @@ int slam_destroy(slam_handle* h) {
     for (auto& ev : h->aux_ev) if (ev) hipEventDestroy(ev);
     for (auto& ev : h->nav.ev) if (ev) hipEventDestroy(ev);
     for (auto& ev : h->mon.ev) if (ev) hipEventDestroy(ev);
+    for (auto& ev : h->inn.ev) if (ev) hipEventDestroy(ev);
     if (h->copy_stream) { hipStreamSynchronize(h->copy_stream); hipStreamDestroy(h->copy_stream); }
     if (h->shadow_ev) hipEventDestroy(h->shadow_ev);
     for (auto& f : h->q.host)
@@ -2194,6 +2205,287 @@ int slam_monitor_instance_host(int filter_kind, const double* x, const double* P
     if (err_yaw) *err_yaw = v.err_yaw;
     if (nees_pose) *nees_pose = v.nees_pose;
     if (flags) *flags = v.flags;
+    return SLAM_OK;
+}
+
+}  // extern "C"
+
+// ---- innovation (NIS) statistics of the message the next step will process (innovation_kernel.hip) ----------------------------------------
+namespace {
+
+// *out = *cfg (NULL: the defaults), checked
+int innovation_config(const slam_innovation_config* cfg, slam_innovation_config* out) {
+    if (cfg) *out = *cfg; else slam_innovation_config_default(out);
+    if (!isfinite(out->nis_lo) || !isfinite(out->nis_hi) || out->nis_lo > out->nis_hi)
+        return fail(SLAM_ERR_ARG, "innovation config: the band nis_lo = %g .. nis_hi = %g must be finite and ordered", out->nis_lo, out->nis_hi);
+    return SLAM_OK;
+}
+
+int innovation_supported(const slam_handle* h) {
+    if (h->kind != SLAM_EKF_SLAM)
+        return fail(SLAM_ERR_UNSUPPORTED, "innovation statistics need EKF_SLAM: the innovation covariance of the UKF kinds depends on all sigma points, so no block of P closes");
+    if (!h->cfg.landmark_id_is_known)
+        return fail(SLAM_ERR_UNSUPPORTED, "innovation statistics need landmark_id_is_known = 1: the association of unknown ids reads every landmark of x_pred after every update");
+    return SLAM_OK;
+}
+
+// the per-instance buffers of one evaluation; det: the detection slots are wanted
+int innovation_reserve(slam_handle* h, bool det) {
+    const size_t B = (size_t)h->B;
+    HIP_TRY(h->inn.dval.reserve((1 + 12 + slam::kInnovRecLen) * B));
+    HIP_TRY(h->inn.dpart.reserve((size_t)slam::innovation_blocks(h->B) * slam::kInnovRecLen));
+    if (det) HIP_TRY(h->inn.ddet.reserve(B * slam::kInnovMaxDet * slam::kInnovDetLen));
+    return SLAM_OK;
+}
+
+// the launch parameters of one evaluation of the step launch_step(h, cmd, sim, d_meas, d_count, k_stride, d_cmd_each) would run now
+slam::InnovParams innovation_params(slam_handle* h, const slam_innovation_config& c, const float cmd[2], int sim, const float* d_meas,
+                                    const int32_t* d_count, int k_stride, const float* d_cmd_each) {
+    slam::InnovParams p;
+    memset(&p, 0, sizeof(p));
+    fill_ekf_params(h, p.s, cmd, sim, 0, d_meas, d_count, k_stride, nullptr, 0, d_cmd_each);
+    const size_t B = (size_t)h->B;
+    p.nis_lo = c.nis_lo; p.nis_hi = c.nis_hi;
+    p.inst_rec = h->inn.dval + 13 * B;
+    p.partials = h->inn.dpart;
+    return p;
+}
+
+// slam_innovation / slam_innovation_dev once the message and the commands are on the device
+int innovation_now(slam_handle* h, const slam_innovation_config& c, const float cmd[2], const float* d_cmd_each, const float* d_meas,
+                   const int32_t* d_count, int k_stride, double* rec, double* nis_sum, int32_t* n_upd, int32_t* n_new, int32_t* flags, double* det,
+                   double* post) {
+    const size_t B = (size_t)h->B;
+    TRY(innovation_reserve(h, det != nullptr));
+    HIP_TRY(h->inn.drec.reserve(slam::kInnovRecLen));
+    HIP_TRY(h->inn.dint.reserve(3 * B));
+    slam::InnovParams p = innovation_params(h, c, cmd, 0, d_meas, d_count, k_stride, d_cmd_each);
+    p.nis_sum = h->inn.dval; p.post = h->inn.dval + B;
+    p.n_upd = h->inn.dint; p.flags = h->inn.dint + B; p.n_new = h->inn.dint + 2 * B;
+    p.det = det ? h->inn.ddet.get() : nullptr;
+    p.rec = h->inn.drec;
+    HIP_TRY(slam::launch_innovation(p, h->esz == 4, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (rec) HIP_TRY(hipMemcpy(rec, p.rec, sizeof(double) * slam::kInnovRecLen, hipMemcpyDeviceToHost));
+    if (nis_sum) HIP_TRY(hipMemcpy(nis_sum, p.nis_sum, sizeof(double) * B, hipMemcpyDeviceToHost));
+    if (post) HIP_TRY(hipMemcpy(post, p.post, sizeof(double) * 12 * B, hipMemcpyDeviceToHost));
+    if (det) HIP_TRY(hipMemcpy(det, p.det, sizeof(double) * B * slam::kInnovMaxDet * slam::kInnovDetLen, hipMemcpyDeviceToHost));
+    if (n_upd) HIP_TRY(hipMemcpy(n_upd, p.n_upd, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+    if (flags) HIP_TRY(hipMemcpy(flags, p.flags, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+    if (n_new) HIP_TRY(hipMemcpy(n_new, p.n_new, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+    return SLAM_OK;
+}
+
+// the checks slam_innovation and slam_innovation_dev share; the queued timesteps run first
+int innovation_enter(slam_handle* h, const slam_innovation_config* cfg, const float* cmds, const float* meas, const int32_t* count, int k_stride,
+                     slam_innovation_config* c) {
+    TRY(innovation_config(cfg, c));
+    if (!cmds) return fail(SLAM_ERR_ARG, "cmds is NULL");
+    if (!meas || !count) return fail(SLAM_ERR_ARG, "meas or meas_count is NULL");
+    if (k_stride <= 0) return fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
+    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
+    TRY(innovation_supported(h));
+    if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
+    TRY(flush_lazy(h));
+    HIP_TRY(hipSetDevice(h->device));
+    return SLAM_OK;
+}
+
+// n floats from the host into the handle's staging buffer for per-instance commands, in stream order
+int innovation_upload_cmds(slam_handle* h, const float* cmds, size_t n) {
+    if (h->inn.dcmd.cap() < n) {
+        if (h->inn.dcmd) HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(h->inn.dcmd.reserve(n));
+    }
+    HIP_TRY(hipMemcpyAsync(h->inn.dcmd, cmds, sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
+    return SLAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int slam_innovation_config_default(slam_innovation_config* c) {
+    if (!c) return fail(SLAM_ERR_ARG, "cfg is NULL");
+    memset(c, 0, sizeof(*c));
+    c->nis_lo = -2.0 * log(0.975); c->nis_hi = -2.0 * log(0.025);   // chi-square quantiles at 0.025 and 0.975, 2 degrees of freedom
+    return SLAM_OK;
+}
+
+int slam_innovation(slam_handle* h, const slam_innovation_config* cfg, const float* cmds, int cmd_each, const float* meas, const int32_t* count,
+                    int k_stride, double rec[16], double* nis_sum, int32_t* n_upd, int32_t* n_new, int32_t* flags, double* det, double* post) {
+    slam_innovation_config c;
+    TRY(innovation_enter(h, cfg, cmds, meas, count, k_stride, &c));
+    const size_t B = (size_t)h->B, nm = 3 * (size_t)k_stride * B;
+    if (h->inn.dmeas.cap() < nm || h->inn.dcount.cap() < B) {
+        if (h->inn.dmeas) HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(h->inn.dmeas.reserve(nm)); HIP_TRY(h->inn.dcount.reserve(B));
+    }
+    HIP_TRY(hipMemcpyAsync(h->inn.dmeas, meas, sizeof(float) * nm, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->inn.dcount, count, sizeof(int32_t) * B, hipMemcpyHostToDevice, h->stream));
+    if (cmd_each) TRY(innovation_upload_cmds(h, cmds, 2 * B));
+    return innovation_now(h, c, cmd_each ? kNoCmd : cmds, cmd_each ? h->inn.dcmd.get() : nullptr, h->inn.dmeas, h->inn.dcount, k_stride, rec, nis_sum,
+                          n_upd, n_new, flags, det, post);
+}
+
+int slam_innovation_dev(slam_handle* h, const slam_innovation_config* cfg, const float* cmds, int cmd_each, const float* d_meas,
+                        const int32_t* d_count, int k_stride, double rec[16], double* nis_sum, int32_t* n_upd, int32_t* n_new, int32_t* flags,
+                        double* det, double* post) {
+    slam_innovation_config c;
+    TRY(innovation_enter(h, cfg, cmds, d_meas, d_count, k_stride, &c));
+    return innovation_now(h, c, cmd_each ? kNoCmd : cmds, cmd_each ? cmds : nullptr, d_meas, d_count, k_stride, rec, nis_sum, n_upd, n_new, flags, det,
+                          post);
+}
+
+int slam_innovation_run(slam_handle* h, const slam_innovation_config* cfg, int source, const float* cmds, const float* meas, const int32_t* count,
+                        int k_stride, int T, double* recs, double* nis_sum, int32_t* n_upd, int32_t* flags) {
+    slam_innovation_config c;
+    TRY(innovation_config(cfg, &c));
+    if (source != SLAM_INNOVATION_SHARED && source != SLAM_INNOVATION_EACH && source != SLAM_INNOVATION_NAV && source != SLAM_INNOVATION_LOG)
+        return fail(SLAM_ERR_ARG, "unknown source %d", source);
+    if (T < 0) return fail(SLAM_ERR_ARG, "T = %d is negative", T);
+    if (source != SLAM_INNOVATION_NAV && !cmds) return fail(SLAM_ERR_ARG, "cmds is NULL: the sources SHARED, EACH and LOG read the commands from it");
+    const bool log = source == SLAM_INNOVATION_LOG;
+    if (log && (!meas || !count)) return fail(SLAM_ERR_ARG, "meas or meas_count is NULL: the source LOG reads the messages from them");
+    if (log && k_stride <= 0) return fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
+    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
+    TRY(innovation_supported(h));
+    if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
+    if (!log && !has_map(h)) return fail(SLAM_ERR_STATE, "slam_set_map has not been called: the sources SHARED, EACH and NAV run the simulator");
+    if (source == SLAM_INNOVATION_NAV && !h->nav.set) return fail(SLAM_ERR_STATE, "no path: call slam_nav_set_path or slam_nav_set_paths first");
+    if (h->shadow) return fail(SLAM_ERR_STATE, "slam_track_instance is on: the run steps the batch once per tick and does not drive the shadow filter");
+    if (h->predicted) return fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev before slam_innovation_run");
+    TRY(flush_lazy(h));
+    if (T == 0) return SLAM_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t B = (size_t)h->B, row = 2 * B, mrow = 3 * (size_t)k_stride * B;
+    // ticks per chunk, as slam_monitor_run: what a tick holds on the device - its rows of the series, of the commands (EACH) and of the
+    // messages (LOG) - stays within SLAM_MONITOR_LOG_BYTES (one tick at least)
+    int chunk = T < 4096 ? T : 4096;
+    const double per_tick = 8.0 * (nis_sum ? (double)B : 0.0) + 4.0 * (double)B * ((n_upd ? 1 : 0) + (flags ? 1 : 0)) +
+                            (source == SLAM_INNOVATION_EACH ? 4.0 * (double)row : 0.0) + (log ? 4.0 * (double)mrow + 4.0 * (double)B : 0.0);
+    if (per_tick > 0.0) {
+        const char* env = getenv("SLAM_MONITOR_LOG_BYTES");
+        const double fit = (env ? atof(env) : 256.0 * 1024 * 1024) / per_tick;
+        if (fit < (double)chunk) chunk = fit >= 1.0 ? (int)fit : 1;
+    }
+    TRY(innovation_reserve(h, false));
+    HIP_TRY(h->inn.drec.reserve((size_t)chunk * slam::kInnovRecLen));
+    if (nis_sum) HIP_TRY(h->inn.dlog.reserve((size_t)chunk * B));
+    HIP_TRY(h->inn.dint.reserve(2 * (size_t)chunk * B));
+    if (source == SLAM_INNOVATION_NAV && h->dcmd_each.cap() < row) {
+        if (h->dcmd_each) HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(h->dcmd_each.reserve(row));
+    }
+    if (log && (h->inn.dmeas.cap() < mrow * chunk || h->inn.dcount.cap() < B * chunk)) {
+        if (h->inn.dmeas) HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(h->inn.dmeas.reserve(mrow * chunk)); HIP_TRY(h->inn.dcount.reserve(B * chunk));
+    }
+    const bool timed = h->nav.time_ticks;
+    while (h->inn.ev.size() < 2 + (timed ? 2 * (size_t)chunk : 0)) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreate(&e));
+        h->inn.ev.push_back(e);
+    }
+    slam::NavParams np;
+    memset(&np, 0, sizeof(np));
+    if (source == SLAM_INNOVATION_NAV) {
+        np.x = h->dx; np.flags = h->dflags; np.path = h->nav.dpath;
+        np.P_each = h->nav.each ? h->nav.dP.get() : nullptr; np.P = h->nav.P; np.path_stride = h->nav.stride;
+        np.B = h->B; np.xstride = h->xstride; np.ukf = 0;
+        np.c = nav_consts(h->nav.cfg, h->cfg.d_max, h->cfg.th_max);
+        np.head = h->nav.dhead; np.finish_tick = h->nav.dfinish; np.integ = h->nav.dinteg; np.err_prev = h->nav.derrp;
+        np.cmd_out = h->dcmd_each;
+    }
+    h->inn.inn_ms = timed ? 0.0 : -1.0; h->inn.total_ms = 0.0;
+    hipEvent_t* const ev = h->inn.ev.data();
+    int32_t* const d_upd = h->inn.dint;
+    int32_t* const d_flags = h->inn.dint + (size_t)chunk * B;
+    for (int t0 = 0; t0 < T; t0 += chunk) {
+        const int tc = T - t0 < chunk ? T - t0 : chunk;
+        if (source == SLAM_INNOVATION_EACH) TRY(upload_cmds_each(h, cmds + (size_t)t0 * row, tc));
+        if (log) {
+            HIP_TRY(hipMemcpyAsync(h->inn.dmeas, meas + (size_t)t0 * mrow, sizeof(float) * mrow * tc, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(h->inn.dcount, count + (size_t)t0 * B, sizeof(int32_t) * B * tc, hipMemcpyHostToDevice, h->stream));
+        }
+        HIP_TRY(hipEventRecord(ev[0], h->stream));
+        for (int t = 0; t < tc; ++t) {
+            const float* cmd = kNoCmd;
+            const float* d_each = nullptr;
+            const float* d_meas = nullptr;
+            const int32_t* d_count = nullptr;
+            if (source == SLAM_INNOVATION_NAV) {
+                np.tick = h->nav.tick;
+                HIP_TRY(slam::launch_nav_tick(np, h->esz == 4, h->stream));
+                h->nav.tick += 1;
+                d_each = h->dcmd_each;
+            } else if (source == SLAM_INNOVATION_EACH) {
+                d_each = h->dcmd_each + (size_t)t * row;
+            } else {
+                cmd = cmds + 2 * (size_t)(t0 + t);
+            }
+            if (log) { d_meas = h->inn.dmeas + (size_t)t * mrow; d_count = h->inn.dcount + (size_t)t * B; }
+            slam::InnovParams p = innovation_params(h, c, cmd, log ? 0 : 1, d_meas, d_count, log ? k_stride : 0, d_each);
+            p.nis_sum = nis_sum ? h->inn.dlog + (size_t)t * B : nullptr;
+            p.n_upd = n_upd ? d_upd + (size_t)t * B : nullptr;
+            p.flags = flags ? d_flags + (size_t)t * B : nullptr;
+            p.rec = h->inn.drec + (size_t)t * slam::kInnovRecLen;
+            if (timed) HIP_TRY(hipEventRecord(ev[2 + 2 * t], h->stream));
+            HIP_TRY(slam::launch_innovation(p, h->esz == 4, h->stream));
+            if (timed) HIP_TRY(hipEventRecord(ev[3 + 2 * t], h->stream));
+            TRY(launch_step(h, cmd, log ? 0 : 1, d_meas, d_count, log ? k_stride : 0, d_each));
+        }
+        HIP_TRY(hipEventRecord(ev[1], h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        h->inn.total_ms += (double)ms;
+        for (int t = 0; timed && t < tc; ++t) {
+            HIP_TRY(hipEventElapsedTime(&ms, ev[2 + 2 * t], ev[3 + 2 * t]));
+            h->inn.inn_ms += (double)ms;
+        }
+        if (recs) HIP_TRY(hipMemcpy(recs + (size_t)t0 * slam::kInnovRecLen, h->inn.drec, sizeof(double) * (size_t)tc * slam::kInnovRecLen, hipMemcpyDeviceToHost));
+        if (nis_sum) HIP_TRY(hipMemcpy(nis_sum + (size_t)t0 * B, h->inn.dlog, sizeof(double) * (size_t)tc * B, hipMemcpyDeviceToHost));
+        if (n_upd) HIP_TRY(hipMemcpy(n_upd + (size_t)t0 * B, d_upd, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
+        if (flags) HIP_TRY(hipMemcpy(flags + (size_t)t0 * B, d_flags, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
+    }
+    return SLAM_OK;
+}
+
+int slam_last_innovation_work(slam_handle* h, double* innovation_ms, double* total_ms) {
+    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
+    if (h->inn.total_ms < 0.0) return fail(SLAM_ERR_STATE, "slam_innovation_run has not run on this handle");
+    if (innovation_ms) *innovation_ms = h->inn.inn_ms;
+    if (total_ms) *total_ms = h->inn.total_ms;
+    return SLAM_OK;
+}
+
+int slam_innovation_instance_host(const double* x, const double* P, const int32_t* ids, int M, int L_max, int32_t status, const float cmd[2],
+                                  const float* meas, int k, const slam_noise* noise, int lm_from_pred, int f32_storage,
+                                  const slam_innovation_config* cfg, double rec[16], double* nis_sum, int32_t* n_upd, int32_t* n_new,
+                                  int32_t* flags, double* det, double* post) {
+    slam_innovation_config c;
+    TRY(innovation_config(cfg, &c));
+    if (!x || !P || !cmd || !noise) return fail(SLAM_ERR_ARG, "NULL argument");
+    if (L_max < 0 || M < 0 || M > L_max) return fail(SLAM_ERR_ARG, "M = %d is not in [0, L_max = %d]", M, L_max);
+    if (M > 0 && !ids) return fail(SLAM_ERR_ARG, "ids is NULL");
+    if (k < 0 || (k > 0 && !meas)) return fail(SLAM_ERR_ARG, "k = %d is negative, or meas is NULL", k);
+    if (const char* f = slam_host::noise_bad_field(*noise)) return fail(SLAM_ERR_ARG, "noise: %s is not finite", f);
+    const slam::InnovNoise nz = {noise->v_d, noise->v_th, noise->w_r, noise->w_b, noise->V_00, noise->V_11, noise->W_00, noise->W_11};
+    const int n = 3 + 2 * M;
+    std::vector<slam::InnovWork> ws(1);
+    for (int i = 0; i < 3 * (k < slam::kInnovMaxDet ? k : slam::kInnovMaxDet); ++i) ws[0].meas[i] = meas[i];
+    const bool f32 = f32_storage != 0;
+    const slam::InnovResult v = slam::innovation_instance(
+        slam::InnovSeq(), ws[0], [&](int i) { return f32 ? (double)(float)x[i] : x[i]; },
+        [&](int r, int cc) { const double e = P[(size_t)r * n + cc]; return f32 ? (double)(float)e : e; }, ids, M, L_max, status, cmd[0], cmd[1], k, nz,
+        lm_from_pred != 0, c.nis_lo, c.nis_hi, det);
+    if (rec) slam::innovation_record(v, rec);
+    if (nis_sum) *nis_sum = v.nis_sum;
+    if (n_upd) *n_upd = v.n_upd;
+    if (n_new) *n_new = v.n_new;
+    if (flags) *flags = v.flags;
+    if (post) memcpy(post, v.post, sizeof(v.post));
     return SLAM_OK;
 }
 

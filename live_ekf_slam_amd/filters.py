@@ -15,6 +15,8 @@ from . import _lib
 from .config import SlamConfig, NavConfig, default_config, default_nav_config, EKF_SLAM, UKF_LOC, UKF_SLAM, F64
 from .config import MonitorConfig, default_monitor_config, MONITOR_SHARED, MONITOR_EACH, MONITOR_NAV
 from .config import Noise
+from .config import (InnovationConfig, default_innovation_config, INNOVATION_SHARED, INNOVATION_EACH, INNOVATION_NAV, INNOVATION_LOG,
+                     INNOV_MAX_DET)
 
 
 def _d(a):
@@ -46,6 +48,17 @@ class MonitorResult:
 
     def __init__(self, recs, err_pos=None, err_yaw=None, nees_pose=None):
         self.recs, self.err_pos, self.err_yaw, self.nees_pose = recs, err_pos, err_yaw, nees_pose
+
+
+class InnovationResult:
+    """What innovation_run returns: `recs`, the (T, 16) records of the ticks (columns: the REC_* constants; slam_innovation in
+    include/slam_batch.h defines them), and - with series=True, else None - `nis_sum`, `n_upd`, `flags`, (T, batch) each."""
+
+    (REC_N_EVAL, REC_N_FROZEN, REC_N_TOO_LONG, REC_N_WOULD_FREEZE, REC_N_SINGULAR, REC_N_UPD, REC_N_NEW, REC_SUM_NIS, REC_MAX_NIS,
+     REC_N_BELOW, REC_N_ABOVE, REC_SUM_NU_R, REC_SUM_NU_B, REC_SUM_NU_R2, REC_SUM_NU_B2, REC_RESERVED) = range(16)
+
+    def __init__(self, recs, nis_sum=None, n_upd=None, flags=None):
+        self.recs, self.nis_sum, self.n_upd, self.flags = recs, nis_sum, n_upd, flags
 
 
 class BatchedFilter:
@@ -548,6 +561,133 @@ class BatchedEKF(BatchedFilter):
         lm[0::3] = s["ids"]; lm[1::3] = x[3::2]; lm[2::3] = x[4::2]
         return dict(timestep=s["timestep"], x_v=np.float32(x[0]), y_v=np.float32(x[1]), yaw_v=np.float32(x[2]),
                     M=M, landmarks=lm, P=s["P"].astype(np.float32).ravel())  # P row-major (ekf.cpp:211-217)
+
+    # -- no counterpart in the reference: is the filter believable WITHOUT the truth?  (slam_innovation_*, include/slam_batch.h) --
+    INNOVATION_FROZEN, INNOVATION_WOULD_FREEZE, INNOVATION_S_SINGULAR, INNOVATION_TOO_LONG = 1, 2, 4, 8   # slam_innovation_flags
+
+    def _innovation_config(self, cfg):
+        if cfg is None:
+            return default_innovation_config()
+        if isinstance(cfg, InnovationConfig):
+            return cfg
+        c = default_innovation_config()
+        for k, v in dict(cfg).items():
+            if k not in ("nis_lo", "nis_hi"):
+                raise ValueError(f"unknown innovation setting {k!r}")
+            setattr(c, k, v)
+        return c
+
+    def innovation(self, cmdMsg, meas, meas_count, det=True, cfg=None):
+        """What the next update(cmdMsg, meas, meas_count) will compute, from the state as it is and changing nothing: dict of rec (16,),
+        nis_sum, n_upd, n_new, flags [batch], post (batch, 12) = the pose and its 3 x 3 covariance after the step, and - det=True -
+        det (batch, INNOV_MAX_DET, 6) = (nis, nu_r, nu_b, S00, S01, S11) per detection slot, NaN where the slot is no update.  cmdMsg: one
+        command or (batch, 2); meas (batch, k_stride, 3) float32 [id, range, bearing]; meas_count [batch]."""
+        self._need()
+        cmd = self._cmd(cmdMsg)
+        m = np.ascontiguousarray(meas, dtype=np.float32)
+        cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
+        if m.ndim != 3 or m.shape[0] != self.batch or m.shape[2] != 3 or cnt.shape != (self.batch,):
+            raise ValueError(f"expected meas of shape ({self.batch}, k_stride, 3) and meas_count of shape ({self.batch},)")
+        B = self.batch
+        out = dict(rec=np.zeros(16), nis_sum=np.zeros(B), n_upd=np.zeros(B, dtype=np.int32), n_new=np.zeros(B, dtype=np.int32),
+                   flags=np.zeros(B, dtype=np.int32), post=np.zeros((B, 12)))
+        if det:
+            out["det"] = np.zeros((B, INNOV_MAX_DET, 6))
+        _lib.check(_lib.lib().slam_innovation(self.h, C.byref(self._innovation_config(cfg)), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt),
+                                              m.shape[1], _d(out["rec"]), _d(out["nis_sum"]), _i(out["n_upd"]), _i(out["n_new"]),
+                                              _i(out["flags"]), _d(out["det"]) if det else None, _d(out["post"])))
+        return out
+
+    def innovation_run(self, cmds=None, T=None, meas=None, meas_count=None, series=False, cfg=None):
+        """A run with the innovation statistics of every tick: per tick the innovation launches and then the one-step launch, all on the
+        device; the same bits as the plain run of the same inputs.  cmds (T, 2): shared commands, (T, batch, 2): per instance, None with
+        T ticks: the controller of set_path / set_paths - the simulator generates the messages; cmds (T, 2) with meas
+        (T, batch, k_stride, 3) and meas_count (T, batch): a recorded log (source INNOVATION_LOG).  Returns an InnovationResult;
+        series=True also records nis_sum, n_upd and flags of every instance at every tick."""
+        self._need()
+        m = cnt = None
+        if cmds is None:
+            if T is None:
+                raise ValueError("innovation_run needs commands or, for the closed loop, a number of ticks T")
+            source, c32, T = INNOVATION_NAV, None, int(T)
+        else:
+            c32 = np.ascontiguousarray(cmds, dtype=np.float32)
+            if meas is not None:
+                m = np.ascontiguousarray(meas, dtype=np.float32)
+                cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
+                if c32.ndim != 2 or c32.shape[1] != 2 or m.ndim != 4 or m.shape[:2] != (c32.shape[0], self.batch) or m.shape[3] != 3 \
+                        or cnt.shape != m.shape[:2]:
+                    raise ValueError(f"a log needs cmds (T, 2), meas (T, {self.batch}, k_stride, 3) and meas_count (T, {self.batch})")
+                source = INNOVATION_LOG
+            elif c32.ndim == 3 and c32.shape[1:] == (self.batch, 2):
+                source = INNOVATION_EACH
+            elif c32.ndim == 2 and c32.shape[1] == 2:
+                source = INNOVATION_SHARED
+            else:
+                raise ValueError(f"expected commands of shape (T, 2) or (T, {self.batch}, 2), got {c32.shape}")
+            if T is not None and int(T) != c32.shape[0]:
+                raise ValueError(f"T = {T} does not match the {c32.shape[0]} commands")
+            T = c32.shape[0]
+        n = max(T, 0)
+        res = InnovationResult(np.zeros((n, 16)))
+        if series:
+            res.nis_sum = np.zeros((n, self.batch))
+            res.n_upd, res.flags = np.zeros((n, self.batch), dtype=np.int32), np.zeros((n, self.batch), dtype=np.int32)
+        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
+        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
+        _lib.check(_lib.lib().slam_innovation_run(self.h, C.byref(self._innovation_config(cfg)), int(source), None if c32 is None else _f(c32),
+                                                  None if m is None else _f(m), None if cnt is None else _i(cnt),
+                                                  0 if m is None else m.shape[2], T, pd(res.recs), pd(res.nis_sum), pi(res.n_upd),
+                                                  pi(res.flags)))
+        self.timestep += n
+        return res
+
+    def last_innovation_work(self):
+        """(device ms of the innovation launches of the last innovation_run, or -1 without set_nav_timing; device ms of the whole run)."""
+        self._need(); a = C.c_double(0); b = C.c_double(0)
+        _lib.check(_lib.lib().slam_last_innovation_work(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+
+def innovation_instance_host(x, P, ids, L_max, status, cmd, meas, noise, lm_from_pred=False, f32_storage=False, cfg=None):
+    """TEST HOOK (slam_innovation_instance_host): the per-instance function of the innovation kernel compiled for the host; no GPU.
+    x (3 + 2 M,), P (n, n), ids (M,), meas (k, 3) float32, noise a config.Noise row.  Returns the dict of innovation() for one instance."""
+    x = np.ascontiguousarray(x, dtype=np.float64); P = np.ascontiguousarray(P, dtype=np.float64)
+    ids = np.ascontiguousarray(ids, dtype=np.int32); M = ids.shape[0]
+    m = np.ascontiguousarray(meas, dtype=np.float32).reshape(-1, 3)
+    c = np.ascontiguousarray(cmd, dtype=np.float32).reshape(2)
+    if x.shape != (3 + 2 * M,) or P.shape != (3 + 2 * M, 3 + 2 * M):
+        raise ValueError("x and P do not match the number of ids")
+    out = dict(rec=np.zeros(16), det=np.zeros((INNOV_MAX_DET, 6)), post=np.zeros(12))
+    s = C.c_double(0); nu = C.c_int32(0); nn = C.c_int32(0); fl = C.c_int32(0)
+    c_cfg = default_innovation_config() if cfg is None else cfg
+    _lib.check(_lib.lib().slam_innovation_instance_host(_d(x), _d(P), _i(ids) if M else None, M, int(L_max), int(status), _f(c),
+                                                        _f(m) if m.shape[0] else None, m.shape[0], C.byref(noise), int(bool(lm_from_pred)),
+                                                        int(bool(f32_storage)), C.byref(c_cfg), _d(out["rec"]), C.byref(s), C.byref(nu),
+                                                        C.byref(nn), C.byref(fl), _d(out["det"]), _d(out["post"])))
+    out.update(nis_sum=s.value, n_upd=nu.value, n_new=nn.value, flags=fl.value)
+    return out
+
+
+def innovation_summary(recs, alpha=0.05):
+    """The curves of an innovation run from its (T, 16) records (one record: shape (16,)), per tick: dict of arrays mean_nis (sum nis /
+    updates), nis_lower / nis_upper (the band for that MEAN: the chi-square quantiles of 2 n_upd degrees of freedom at alpha / 2 and
+    1 - alpha / 2 divided by n_upd; NaN where 2 n_upd < 30), frac_outside, mean_nu_r, mean_nu_b, n_upd, n_eval.  Pure numpy (no GPU)."""
+    r = np.atleast_2d(np.asarray(recs, dtype=np.float64))
+    if r.ndim != 2 or r.shape[1] != 16:
+        raise ValueError(f"expected records of shape (T, 16), got {np.shape(recs)}")
+    R = InnovationResult
+    with np.errstate(divide="ignore", invalid="ignore"):
+        n = r[:, R.REC_N_UPD]
+        out = dict(mean_nis=r[:, R.REC_SUM_NIS] / n, frac_outside=(r[:, R.REC_N_BELOW] + r[:, R.REC_N_ABOVE]) / n,
+                   mean_nu_r=r[:, R.REC_SUM_NU_R] / n, mean_nu_b=r[:, R.REC_SUM_NU_B] / n, n_upd=n.astype(np.int64),
+                   n_eval=r[:, R.REC_N_EVAL].astype(np.int64))
+    lo, hi = np.full(r.shape[0], np.nan), np.full(r.shape[0], np.nan)
+    for t, k in enumerate(out["n_upd"]):
+        if 2 * k >= 30:
+            lo[t], hi[t] = chi2_quantile(alpha / 2, 2 * int(k)) / k, chi2_quantile(1 - alpha / 2, 2 * int(k)) / k
+    out["nis_lower"], out["nis_upper"] = lo, hi
+    return out
 
 
 def _normal_quantile(p):
