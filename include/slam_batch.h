@@ -419,8 +419,8 @@ int slam_monitor_instance_host(int filter_kind, const double* x, const double* P
  *   depends on all sigma points: no block closes), landmark_id_is_known = 0 (that association reads every landmark of x_pred after every
  *   update).  SLAM_ERR_STATE: before slam_init; slam_innovation_run also: without a map for the simulator sources, NAV without a path, while
  *   slam_track_instance is on, while a prediction is pending.
- * Not covered: the UKF kinds; unknown ids; innovation autocorrelation / whiteness; gating or rejecting detections; slam_multi_*; the pose
- *   graph; evaluation inside multi-step launches (slam_innovation_run steps once per tick). */
+ * Not covered: the UKF kinds; unknown ids; innovation autocorrelation / whiteness; slam_multi_*; the pose graph; evaluation inside
+ *   multi-step launches (slam_innovation_run steps once per tick).  These calls reject nothing: innovation gating is slam_gate, below. */
 #define SLAM_INNOV_MAX_DET 64   /* detections of one message beyond which the instance is TOO_LONG */
 #define SLAM_INNOV_MAX_LM 16    /* distinct mapped landmarks of one message beyond which the instance is TOO_LONG */
 enum slam_innovation_flags {
@@ -469,6 +469,88 @@ int slam_innovation_instance_host(const double* x, const double* P, const int32_
                                   const float* meas, int k, const slam_noise* noise, int lm_from_pred, int f32_storage,
                                   const slam_innovation_config* cfg, double rec[16], double* nis_sum, int32_t* n_upd, int32_t* n_new,
                                   int32_t* flags, double* det, double* post);
+
+/* ---- innovation gating: the chi-square gate on every detection (csrc/gate_kernel.h) -------------------------------------------------------
+ * slam_innovation tells which detections the filter should not believe; the step still takes every one of them in, and one wrong
+ * association or range spike bends the pose and every correlated landmark.  slam_gate runs the same replay and REJECTS an update slot iff
+ * its nis is finite and nis > gate: the slot's update is not applied in the replay, and the message comes back with the rejected
+ * detections taken out, in message order.  The step kernels are untouched: the unmodified step consumes the filtered message and computes
+ * exactly what the gated replay computed (an update slot is a found id; the insertion, skip and freeze decisions look only at ids that
+ * were not found, so removing an update slot changes no other slot's plan).  A gated step equals, byte for byte, a plain step on the
+ * filtered message.
+ * A slot whose nis is not finite (S_SINGULAR, a non-finite nu or S) is NEVER rejected: it goes through as the step has it.  A slot whose
+ * nis equals the gate is accepted.  Instances flagged INSTANCE_FROZEN, WOULD_FREEZE or TOO_LONG pass their message through unchanged:
+ * n_rej = 0, every verdict 0.
+ * Outputs as slam_innovation, with these differences: a rejected slot still reports its six det values; nis_sum, post and the record's
+ *   entries 5 and 7 - 14 run over the ACCEPTED updates (post is the state after them, which is what the step on the filtered message
+ *   leaves); n_upd counts the update slots of the incoming message, rejected or not; record entry 15 = rejected detections.
+ *   n_rej [batch]; verdict [batch][SLAM_INNOV_MAX_DET] int32 (slam_gate_verdict).
+ *   Output message, with count_in = min(max(count, 0), k_stride): the kept detections in message order, count_out = their number, the
+ *   triplets count_out .. count_in - 1 written as 0.0f, nothing written from count_in up.  A passed-through instance: count_out = count as
+ *   given, and its first count_in triplets copied when the output is not the input.
+ * Honours slam_set_noise_each rows, slam_set_maps, the quirk switch ekf_landmark_from_x_pred, both storage types and every capacity class.
+ * Errors and scope as slam_innovation (argument checks first, before the handle is looked at; SLAM_ERR_UNSUPPORTED for the UKF kinds and
+ *   for landmark_id_is_known = 0); also SLAM_ERR_ARG for a gate that is NaN or <= 0 (+inf is allowed: nothing is rejected) and for outputs
+ *   that overlap the inputs other than in place; slam_step_gated* and slam_gate_run: SLAM_ERR_STATE while slam_track_instance is on or a
+ *   prediction is pending.
+ * Not covered: the simulator sources (their step generates its own message inside the step kernel); slam_multi_*; the pose graph;
+ *   multi-step launches (a gated step is one launch per tick); rejecting on anything but the individual NIS - there is no joint
+ *   compatibility test, and a detection of an unmapped id is inserted ungated. */
+enum slam_gate_verdict {
+    SLAM_GATE_NOT_UPDATE = 0,   /* insertion, capacity skip, beyond the count, or any slot of a passed-through instance */
+    SLAM_GATE_ACCEPTED = 1,
+    SLAM_GATE_REJECTED = 2
+};
+typedef struct slam_gate_config {
+    double gate;             /* reject iff nis is finite and nis > gate; > 0, may be +inf */
+    double nis_lo, nis_hi;   /* the band of record entries 9 and 10, as slam_innovation_config */
+} slam_gate_config;
+/* gate = -2 ln 0.001 = 13.815510557964274, the 0.999 quantile of chi-square with 2 degrees of freedom; the band of
+ * slam_innovation_config_default */
+int slam_gate_config_default(slam_gate_config* cfg);
+/* Gates the message the next slam_step (cmd_each = 0: cmds [2]) or slam_step_each (cmd_each != 0: cmds [batch][2]) would be given and
+ * CHANGES NOTHING in the handle: a checkpoint before and after is byte-identical.  Host pointers; arguments and outputs as slam_innovation,
+ * then meas_out [batch][k_stride][3], count_out [batch], n_rej [batch], verdict [batch][SLAM_INNOV_MAX_DET]; any output may be NULL.
+ * meas_out / count_out may be meas / meas_count themselves, both or neither (one alone is SLAM_ERR_ARG).  The message is staged on the
+ * device, so here meas_out comes back whole: the slots the gate does not write hold the input's values. */
+int slam_gate(slam_handle* h, const slam_gate_config* cfg, const float* cmds, int cmd_each, const float* meas, const int32_t* meas_count,
+              int k_stride, double rec[16], double* nis_sum, int32_t* n_upd, int32_t* n_new, int32_t* flags, double* det, double* post,
+              float* meas_out, int32_t* count_out, int32_t* n_rej, int32_t* verdict);
+/* The same with d_meas, d_count, (cmd_each != 0) cmds, d_meas_out and d_count_out as DEVICE pointers, read and written in stream order;
+ * d_meas_out and d_count_out are required.  In place (d_meas_out == d_meas and d_count_out == d_count) is allowed; any other overlap of an
+ * output with an input or with the other output is SLAM_ERR_ARG.  The other outputs are host pointers and may be NULL. */
+int slam_gate_dev(slam_handle* h, const slam_gate_config* cfg, const float* cmds, int cmd_each, const float* d_meas, const int32_t* d_count,
+                  int k_stride, double rec[16], double* nis_sum, int32_t* n_upd, int32_t* n_new, int32_t* flags, double* det, double* post,
+                  float* d_meas_out, int32_t* d_count_out, int32_t* n_rej, int32_t* verdict);
+/* One gated timestep: the gate launches into a buffer the handle owns, then the ordinary one-step launch on the filtered message, all on
+ * the handle's stream; the caller's message is not written.  Run the EKF step queue first and are not queued themselves.  rec [16] and
+ * n_rej [batch] (host) are optional: with both NULL the call does not synchronise.  slam_step_gated / _each take host messages (and host
+ * cmds [batch][2]), the _dev forms device messages (slam_step_gated_each_dev: device cmds), as the slam_step family. */
+int slam_step_gated(slam_handle* h, const slam_gate_config* cfg, const float cmd[2], const float* meas, const int32_t* meas_count, int k_stride,
+                    double rec[16], int32_t* n_rej);
+int slam_step_gated_dev(slam_handle* h, const slam_gate_config* cfg, const float cmd[2], const float* d_meas, const int32_t* d_count,
+                        int k_stride, double rec[16], int32_t* n_rej);
+int slam_step_gated_each(slam_handle* h, const slam_gate_config* cfg, const float* cmds, const float* meas, const int32_t* meas_count,
+                         int k_stride, double rec[16], int32_t* n_rej);
+int slam_step_gated_each_dev(slam_handle* h, const slam_gate_config* cfg, const float* d_cmds, const float* d_meas, const int32_t* d_count,
+                             int k_stride, double rec[16], int32_t* n_rej);
+/* T host-fed gated ticks of {the gate launches; the one-step launch on the filtered message}, in the layout of slam_innovation_run's LOG
+ * source: cmds [T][2] (cmd_each != 0: [T][batch][2]), meas [T][batch][k_stride][3], meas_count [T][batch].  The state advances bit for bit
+ * as T calls of slam_step_gated (slam_step_gated_each) would leave it.  recs [T][16], nis_sum / n_upd / n_rej / flags [T][batch]; any may
+ * be NULL.  Chunks of ticks by the rule of slam_innovation_run (at most 4096 ticks, SLAM_MONITOR_LOG_BYTES); chunking changes no bit. */
+int slam_gate_run(slam_handle* h, const slam_gate_config* cfg, const float* cmds, int cmd_each, const float* meas, const int32_t* meas_count,
+                  int k_stride, int T, double* recs, double* nis_sum, int32_t* n_upd, int32_t* n_rej, int32_t* flags);
+/* Device time of the last slam_gate_run in ms, as slam_last_innovation_work: everything, and the gate launches alone, which needs
+ * slam_nav_set_timing(h, 1); without it *gate_ms = -1. */
+int slam_last_gate_work(slam_handle* h, double* gate_ms, double* total_ms);
+/* TEST HOOK, not part of the filter interface: the gate's per-instance function compiled for the HOST (the same source as the kernel, no
+ * device needed).  Arguments as slam_innovation_instance_host, except: meas holds min(max(count, 0), k_stride) triplets, count is the
+ * count as given and k_stride > 0 the capacity of the message row.  Extra outputs meas_out [k_stride][3] (may be meas), count_out, n_rej,
+ * verdict [SLAM_INNOV_MAX_DET]; any output may be NULL. */
+int slam_gate_instance_host(const double* x, const double* P, const int32_t* ids, int M, int L_max, int32_t status, const float cmd[2],
+                            const float* meas, int count, int k_stride, const slam_noise* noise, int lm_from_pred, int f32_storage,
+                            const slam_gate_config* cfg, double rec[16], double* nis_sum, int32_t* n_upd, int32_t* n_new, int32_t* flags,
+                            double* det, double* post, float* meas_out, int32_t* count_out, int32_t* n_rej, int32_t* verdict);
 
 /* ---- closed loop: commands from each instance's own estimate (goal_pursuit_node.py:23-50, pure_pursuit.py:17-161) ---------------------
  * The entry points above run open loop: every command is fixed before the run.  The reference's default launch (sim_base.launch,

@@ -67,6 +67,9 @@ struct MonitorRun { std::vector<double> recs, err_pos, err_yaw, nees_pose; };
 // of the step that follows; the [T][16] records of a run and, if asked for, its [T][B] series.
 struct Innovation { double rec[16]; std::vector<double> nis_sum, det, post; std::vector<int32_t> n_upd, n_new, flags; };
 struct InnovationRun { std::vector<double> recs, nis_sum; std::vector<int32_t> n_upd, flags; };
+// What stepGated returns (slam_step_gated*): the gate's record (entry 15 = rejected detections) and the [B] rejected counts.  The other
+// gate entry points (slam_gate, slam_gate_dev, slam_gate_run) are used through the C interface.
+struct GatedStep { double rec[16]; std::vector<int32_t> n_rej; };
 // One start pose per instance (pose0 [B][3] {x, y, yaw}), optional true start poses (truth0 [B][3], empty = the config's init pose);
 // maps [B][L_stride][2] with L [B] landmarks each; commands [B] of one timestep or [T][B][2] floats of a run.
 #define SLAM_FILTER_EACH_METHODS                                                                                                          \
@@ -168,6 +171,17 @@ struct InnovationRun { std::vector<double> recs, nis_sum; std::vector<int32_t> n
     /* device ms of the last innovationRun: {the innovation launches alone (-1 without slam_nav_set_timing), everything}              */  \
     std::pair<double, double> lastInnovationWork() {                                                                                     \
         need(); double a = 0, b = 0; check(slam_last_innovation_work(h_, &a, &b)); return {a, b};                                        \
+    }                                                                                                                                    \
+    /* one GATED timestep (slam_step_gated / slam_step_gated_each; EKF-SLAM handles): the chi-square gate on every detection's NIS,   */  \
+    /* then the ordinary step on the filtered message.  cmds: one Command for the batch, or [B] of them; cfg NULL: gate 13.8155       */  \
+    GatedStep stepGated(const std::vector<Command>& cmds, const float* meas, const int32_t* meas_count, int k_stride,                    \
+                        const slam_gate_config* cfg = nullptr) {                                                                         \
+        need();                                                                                                                          \
+        const bool each = cmds.size() != 1;                                                                                              \
+        const std::vector<float> c = packCommands(cmds, each ? batch_ : 1);                                                              \
+        GatedStep v; v.n_rej.resize(batch_);                                                                                             \
+        check((each ? slam_step_gated_each : slam_step_gated)(h_, cfg, c.data(), meas, meas_count, k_stride, v.rec, v.n_rej.data()));    \
+        return v;                                                                                                                        \
     }
 
 class Filter {  // filter.h:54-77

@@ -8,5 +8,7 @@ from .config import INNOV_MAX_DET, INNOV_MAX_LM  # noqa: F401
 from .navigation import PurePursuitBatch  # noqa: F401
 from .filters import BatchedEKF, BatchedUKF, BatchedUKFLoc, Command, MonitorResult, monitor_summary  # noqa: F401
 from .filters import InnovationResult, innovation_summary, innovation_instance_host  # noqa: F401
+from .config import GateConfig, default_gate_config, GATE_NOT_UPDATE, GATE_ACCEPTED, GATE_REJECTED  # noqa: F401
+from .filters import GateResult, gate_instance_host  # noqa: F401
 from .pose_graph import BatchedPoseGraph, NaiveFilter  # noqa: F401
 from ._lib import SlamError  # noqa: F401

@@ -116,6 +116,20 @@ def default_innovation_config() -> InnovationConfig:
     return InnovationConfig(-2.0 * math.log(0.975), -2.0 * math.log(0.025))
 
 
+class GateConfig(C.Structure):
+    """ctypes mirror of `slam_gate_config` (include/slam_batch.h): the chi-square gate on a detection's NIS and the band of the record."""
+    _fields_ = [("gate", C.c_double), ("nis_lo", C.c_double), ("nis_hi", C.c_double)]
+
+
+GATE_NOT_UPDATE, GATE_ACCEPTED, GATE_REJECTED = 0, 1, 2   # slam_gate_verdict
+
+
+def default_gate_config() -> GateConfig:
+    """gate = -2 ln 0.001, the 0.999 quantile of chi-square with 2 degrees of freedom; the band of default_innovation_config."""
+    import math
+    return GateConfig(-2.0 * math.log(0.001), -2.0 * math.log(0.975), -2.0 * math.log(0.025))
+
+
 def default_monitor_config() -> MonitorConfig:
     """The chi-square quantiles at 0.025 and 0.975 for 3 degrees of freedom; no full evaluation."""
     return MonitorConfig(0.21579528262389785, 9.348403604496148, 0)

@@ -108,6 +108,17 @@ SLAM_HD bool innov_inv2x2_lu(const double S[4], double Si[4]) {
     return ok;
 }
 
+// The gating policy of innovation_instance(): InnovNoGate is the plain evaluation (slam_innovation; every `if constexpr` below drops
+// out and the function is the code it was before there was a gate), InnovGate the chi-square gate of slam_gate (gate_kernel.h).
+struct InnovNoGate { static constexpr bool on = false; };
+struct InnovGate {
+    static constexpr bool on = true;
+    double gate;        // an update slot is REJECTED iff its nis is finite and nis > gate
+    int32_t* verdict;   // [kInnovMaxDet], shared by the lanes like det: 0 not an update slot, 1 accepted, 2 rejected
+    int32_t n_rej;      // out: rejected slots
+};
+constexpr int32_t kGateNone = 0, kGateAccepted = 1, kGateRejected = 2;
+
 // The host's execution policy: one "lane" walks every loop.  The device's (innovation_kernel.hip) spreads the loops over the 64 lanes of
 // a wavefront, finds by ballot and orders the phases by a wavefront fence; the arithmetic of an element does not depend on the lane.
 struct InnovSeq {
@@ -128,11 +139,19 @@ SLAM_HD int innov_full_index(const InnovWork& ws, int s) { return s < 3 ? s : 3 
 // the caller, >= 0).  ids: lm_IDs[0 .. M); M is clamped to [0, L_max].  status: slam_instance_flags.  load_x(i) / load_P(r, c): element i of
 // x_t / element (r, c) of P_t as doubles (fp32 storage converted on load).  lo, hi: the band of the record's entries 9 and 10.
 // det: [kInnovMaxDet][6] or NULL.  Every lane of the policy returns the same result; the lanes share the writes of det.
-template <class W, class LX, class LP>
+// g: the gating policy's state (NULL for InnovNoGate, the plain evaluation).  With InnovGate a rejected slot writes its six det values and is otherwise skipped: no K, no x_pred, no downdate, and
+// it enters none of the sums and counts of the result except n_upd (the update slots of the plan, rejected or not) and g->n_rej; post is
+// the state after the accepted updates.  A slot whose nis is not finite (S_SINGULAR, a non-finite nu or S) is never rejected: it goes
+// through as the step has it.  INSTANCE_FROZEN, WOULD_FREEZE and TOO_LONG pass their message through: n_rej = 0, every verdict 0.
+template <class W, class LX, class LP, class G = InnovNoGate>
 SLAM_HD InnovResult innovation_instance(const W& w, InnovWork& ws, LX load_x, LP load_P, const int32_t* ids, int M, int L_max, int32_t status,
                                         float fwd, float ang, int k, const InnovNoise& nz, bool lm_from_pred, double lo, double hi,
-                                        double* det) {
+                                        double* det, G* g = nullptr) {
     const double nan = __builtin_nan("");
+    if constexpr (G::on) {
+        g->n_rej = 0;
+        for (int e = w.lane(); e < kInnovMaxDet; e += w.width()) g->verdict[e] = kGateNone;
+    }
     InnovResult out;
     out.nis_sum = nan; out.n_upd = 0; out.n_new = 0; out.flags = 0;
     out.n_fin = out.n_below = out.n_above = 0;
@@ -263,7 +282,13 @@ SLAM_HD InnovResult innovation_instance(const W& w, InnovWork& ws, LX load_x, LP
         double nis = nu0 * (Si[0] * nu0 + Si[1] * nu1) + nu1 * (Si[2] * nu0 + Si[3] * nu1);
         if (!ok) { flags |= kInnovSingular; nis = nan; }
         if (!innov_finite(nu0) || !innov_finite(nu1) || !innov_finite(S[0]) || !innov_finite(S[1]) || !innov_finite(S[2]) || !innov_finite(S[3])) nis = nan;
-        if (innov_finite(nis)) {
+        bool rejected = false;
+        if constexpr (G::on) {
+            rejected = innov_finite(nis) && nis > g->gate;
+            if (w.lane() == 0) g->verdict[l] = rejected ? kGateRejected : kGateAccepted;
+            if (rejected) g->n_rej += 1;
+        }
+        if (!rejected && innov_finite(nis)) {
             nis_sum = nis_sum + nis;
             out.n_fin += 1;
             if (nis > out.max_nis) out.max_nis = nis;
@@ -275,6 +300,12 @@ SLAM_HD InnovResult innovation_instance(const W& w, InnovWork& ws, LX load_x, LP
         if (det && w.lane() == 0) {
             double* const dl = det + (size_t)l * kInnovDetLen;
             dl[0] = nis; dl[1] = nu0; dl[2] = nu1; dl[3] = S[0]; dl[4] = 0.5 * (S[1] + S[2]); dl[5] = S[3];
+        }
+        if constexpr (G::on) {
+            if (rejected) {   // x_pred and P stay as they are; the next update's writes of HP come after this slot's reads of it
+                w.sync();
+                continue;
+            }
         }
         for (int r = w.lane(); r < nb; r += w.width()) {        // K = (P H^T) S^-1 (ekf.cpp:135), x_pred += K nu (ekf.cpp:138)
             const double* const pr = ws.P + r * LD;
@@ -315,6 +346,26 @@ SLAM_HD void innovation_record(const InnovResult& v, double r[kInnovRecLen]) {
 }
 
 #if defined(__HIPCC__)
+// the 64 lanes of one wavefront
+struct InnovWave {
+    int ln;
+    __device__ __forceinline__ int lane() const { return ln; }
+    __device__ __forceinline__ int width() const { return 64; }
+    // LDS written by some lanes is read by others of the same wavefront afterwards
+    __device__ __forceinline__ void sync() const {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    template <class F> __device__ __forceinline__ int first(int n, F f) const {   // (called in wave-uniform control flow)
+        for (int i0 = 0; i0 < n; i0 += 64) {
+            const int i = i0 + ln;
+            const unsigned long long m = __ballot(i < n && f(i));
+            if (m != 0ull) return i0 + (__ffsll((long long)m) - 1);
+        }
+        return -1;
+    }
+};
+
 // One evaluation of every instance on `stream`: three launches (the instances, then per-workgroup partial records and their sum in
 // ascending order).  Everything is read only, except the outputs.
 struct InnovParams {
@@ -330,6 +381,8 @@ struct InnovParams {
 };
 inline int innovation_blocks(int B) { return (B + kInnovBlock - 1) / kInnovBlock; }
 hipError_t launch_innovation(const InnovParams& p, int f32_storage, hipStream_t stream);
+// its second and third launch alone: inst_rec [B][kInnovRecLen] -> partials [innovation_blocks(B)][kInnovRecLen] -> rec [kInnovRecLen]
+hipError_t launch_innovation_reduce(const double* inst_rec, int B, double* partials, double* rec, hipStream_t stream);
 #endif
 
 }  // namespace slam

@@ -32,26 +32,6 @@ constexpr int kInnovWaves = 4;                      // instances per workgroup o
 constexpr int kRedWaves = kInnovBlock / 64;
 static_assert(sizeof(InnovWork) * kInnovWaves <= 64 * 1024, "static LDS of a workgroup");
 
-// the 64 lanes of one wavefront
-struct InnovWave {
-    int ln;
-    __device__ __forceinline__ int lane() const { return ln; }
-    __device__ __forceinline__ int width() const { return 64; }
-    // LDS written by some lanes is read by others of the same wavefront afterwards
-    __device__ __forceinline__ void sync() const {
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-    template <class F> __device__ __forceinline__ int first(int n, F f) const {   // (called in wave-uniform control flow)
-        for (int i0 = 0; i0 < n; i0 += 64) {
-            const int i = i0 + ln;
-            const unsigned long long m = __ballot(i < n && f(i));
-            if (m != 0ull) return i0 + (__ffsll((long long)m) - 1);
-        }
-        return -1;
-    }
-};
-
 template <class ST>
 __global__ __launch_bounds__(64 * kInnovWaves) void innovation_instance_kernel(const InnovParams p) {
     __shared__ InnovWork s_ws[kInnovWaves];
@@ -155,16 +135,21 @@ hipError_t launch_innovation(const InnovParams& p, int f32_storage, hipStream_t 
         (long long)s.pstride < (long long)n_max * ekf_ld(n_max, f32_storage ? 4 : 8))
         return hipErrorInvalidValue;
     if (s.sim ? (!s.truth || (!s.map && !s.map_each)) : (!s.meas_in || !s.meas_count_in || s.k_stride_in <= 0)) return hipErrorInvalidValue;
-    const int groups = (s.B + kInnovWaves - 1) / kInnovWaves, blocks = innovation_blocks(s.B);
+    const int groups = (s.B + kInnovWaves - 1) / kInnovWaves;
     (void)hipGetLastError();   // sticky and per thread: only these launches' errors are reported (capi_internal.h)
     if (f32_storage) hipLaunchKernelGGL(innovation_instance_kernel<float>, dim3(groups), dim3(64 * kInnovWaves), 0, stream, p);
     else hipLaunchKernelGGL(innovation_instance_kernel<double>, dim3(groups), dim3(64 * kInnovWaves), 0, stream, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(innovation_reduce_kernel, dim3(blocks), dim3(kInnovBlock), 0, stream, p.inst_rec, s.B, p.partials);
-    e = hipGetLastError();
+    return launch_innovation_reduce(p.inst_rec, s.B, p.partials, p.rec, stream);
+}
+
+hipError_t launch_innovation_reduce(const double* inst_rec, int B, double* partials, double* rec, hipStream_t stream) {
+    const int blocks = innovation_blocks(B);
+    hipLaunchKernelGGL(innovation_reduce_kernel, dim3(blocks), dim3(kInnovBlock), 0, stream, inst_rec, B, partials);
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(innovation_sum_kernel, dim3(1), dim3(64), 0, stream, p.partials, blocks, p.rec);
+    hipLaunchKernelGGL(innovation_sum_kernel, dim3(1), dim3(64), 0, stream, partials, blocks, rec);
     return hipGetLastError();
 }
 

@@ -21,6 +21,7 @@
 #include "host/config_parse.h"
 #include "host/noise_pack.h"
 #include "ekf_kernel.h"
+#include "gate_kernel.h"
 #include "innovation_kernel.h"
 #include "monitor_kernel.h"
 #include "nav_kernel.h"
@@ -186,6 +187,12 @@ struct slam_handle {
         std::vector<hipEvent_t> ev;
         double inn_ms = -1.0, total_ms = -1.0;
     } inn;
+    // slam_gate_*: the filtered message of a gated step or of one tick of slam_gate_run ([B][k_stride][3] and [B] counts), [ticks][B] n_rej
+    // and [B][64] verdicts, the device times of the last slam_gate_run.  Everything else is staged in `inn`, its event pool included.
+    struct Gate {
+        DevBuf<float> dmeas; DevBuf<int32_t> dcount, drej, dverdict;
+        double gate_ms = -1.0, total_ms = -1.0;
+    } gate;
 };
 
 namespace {
@@ -2486,6 +2493,334 @@ int slam_innovation_instance_host(const double* x, const double* P, const int32_
     if (n_new) *n_new = v.n_new;
     if (flags) *flags = v.flags;
     if (post) memcpy(post, v.post, sizeof(v.post));
+    return SLAM_OK;
+}
+
+}  // extern "C"
+
+// ---- innovation gating: the chi-square gate on the message the next step will process (gate_kernel.hip) -----------------------------------
+namespace {
+
+// *out = *cfg (NULL: the defaults), checked
+int gate_config(const slam_gate_config* cfg, slam_gate_config* out) {
+    if (cfg) *out = *cfg; else slam_gate_config_default(out);
+    if (!(out->gate > 0.0)) return fail(SLAM_ERR_ARG, "gate config: gate = %g must be positive (+inf: nothing is rejected)", out->gate);
+    if (!isfinite(out->nis_lo) || !isfinite(out->nis_hi) || out->nis_lo > out->nis_hi)
+        return fail(SLAM_ERR_ARG, "gate config: the band nis_lo = %g .. nis_hi = %g must be finite and ordered", out->nis_lo, out->nis_hi);
+    return SLAM_OK;
+}
+
+// room for n elements in a buffer that launches in flight may still use: they finish before it is replaced
+template <class T>
+int gate_grow(slam_handle* h, DevBuf<T>& buf, size_t n) {
+    if (buf.cap() >= n) return SLAM_OK;
+    if (buf) HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(buf.reserve(n));
+    return SLAM_OK;
+}
+
+bool gate_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const char* const pa = (const char*)a; const char* const pb = (const char*)b;
+    return pa < pb + nb && pb < pa + na;
+}
+
+// the checks every gate entry point shares, in the order of slam_innovation: arguments, then the handle; the queued timesteps run first
+int gate_enter(slam_handle* h, const slam_gate_config* cfg, const float* cmds, const float* meas, const int32_t* count, int k_stride,
+               const float* meas_out, const int32_t* count_out, bool need_out, slam_gate_config* c) {
+    TRY(gate_config(cfg, c));
+    if (!cmds) return fail(SLAM_ERR_ARG, "cmds is NULL");
+    if (!meas || !count) return fail(SLAM_ERR_ARG, "meas or meas_count is NULL");
+    if (k_stride <= 0) return fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
+    if (need_out && (!meas_out || !count_out)) return fail(SLAM_ERR_ARG, "d_meas_out or d_count_out is NULL");
+    if ((meas_out == meas) != (count_out == count))
+        return fail(SLAM_ERR_ARG, "in place means both: meas_out == meas and count_out == meas_count, or neither");
+    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
+    TRY(innovation_supported(h));
+    if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
+    TRY(flush_lazy(h));
+    HIP_TRY(hipSetDevice(h->device));
+    return SLAM_OK;
+}
+
+// the gate launches of one message on the handle's stream; the per-instance outputs may be NULL
+int gate_launch(slam_handle* h, const slam_gate_config& c, const float cmd[2], const float* d_cmd_each, const float* d_meas,
+                const int32_t* d_count, int k_stride, float* d_meas_out, int32_t* d_count_out, double* d_rec, double* d_nis_sum, double* d_post,
+                double* d_det, int32_t* d_n_upd, int32_t* d_flags, int32_t* d_n_new, int32_t* d_n_rej, int32_t* d_verdict) {
+    const slam_innovation_config band = {c.nis_lo, c.nis_hi};
+    slam::GateParams p;
+    memset(&p, 0, sizeof(p));
+    p.in = innovation_params(h, band, cmd, 0, d_meas, d_count, k_stride, d_cmd_each);
+    p.in.nis_sum = d_nis_sum; p.in.post = d_post; p.in.det = d_det; p.in.n_upd = d_n_upd; p.in.flags = d_flags; p.in.n_new = d_n_new;
+    p.in.rec = d_rec;
+    p.gate = c.gate; p.meas_out = d_meas_out; p.count_out = d_count_out; p.n_rej = d_n_rej; p.verdict = d_verdict;
+    HIP_TRY(slam::launch_gate(p, h->esz == 4, h->stream));
+    return SLAM_OK;
+}
+
+// slam_gate / slam_gate_dev once the message and the commands are on the device; d_meas_out / d_count_out: where the filtered message goes
+int gate_now(slam_handle* h, const slam_gate_config& c, const float cmd[2], const float* d_cmd_each, const float* d_meas, const int32_t* d_count,
+             int k_stride, float* d_meas_out, int32_t* d_count_out, double* rec, double* nis_sum, int32_t* n_upd, int32_t* n_new, int32_t* flags,
+             double* det, double* post, int32_t* n_rej, int32_t* verdict) {
+    const size_t B = (size_t)h->B;
+    TRY(innovation_reserve(h, det != nullptr));
+    TRY(gate_grow(h, h->inn.drec, slam::kInnovRecLen));
+    TRY(gate_grow(h, h->inn.dint, 3 * B));
+    TRY(gate_grow(h, h->gate.drej, B));
+    if (verdict) TRY(gate_grow(h, h->gate.dverdict, B * slam::kInnovMaxDet));
+    double* const d_nis = h->inn.dval; double* const d_post = h->inn.dval + B;
+    int32_t* const d_upd = h->inn.dint; int32_t* const d_fl = h->inn.dint + B; int32_t* const d_new = h->inn.dint + 2 * B;
+    TRY(gate_launch(h, c, cmd, d_cmd_each, d_meas, d_count, k_stride, d_meas_out, d_count_out, h->inn.drec, d_nis, d_post,
+                    det ? h->inn.ddet.get() : nullptr, d_upd, d_fl, d_new, h->gate.drej, verdict ? h->gate.dverdict.get() : nullptr));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (rec) HIP_TRY(hipMemcpy(rec, h->inn.drec, sizeof(double) * slam::kInnovRecLen, hipMemcpyDeviceToHost));
+    if (nis_sum) HIP_TRY(hipMemcpy(nis_sum, d_nis, sizeof(double) * B, hipMemcpyDeviceToHost));
+    if (post) HIP_TRY(hipMemcpy(post, d_post, sizeof(double) * 12 * B, hipMemcpyDeviceToHost));
+    if (det) HIP_TRY(hipMemcpy(det, h->inn.ddet, sizeof(double) * B * slam::kInnovMaxDet * slam::kInnovDetLen, hipMemcpyDeviceToHost));
+    if (n_upd) HIP_TRY(hipMemcpy(n_upd, d_upd, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+    if (flags) HIP_TRY(hipMemcpy(flags, d_fl, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+    if (n_new) HIP_TRY(hipMemcpy(n_new, d_new, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+    if (n_rej) HIP_TRY(hipMemcpy(n_rej, h->gate.drej, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+    if (verdict) HIP_TRY(hipMemcpy(verdict, h->gate.dverdict, sizeof(int32_t) * B * slam::kInnovMaxDet, hipMemcpyDeviceToHost));
+    return SLAM_OK;
+}
+
+// the host message of one call into the handle's staging buffers, in stream order
+int gate_upload_message(slam_handle* h, const float* meas, const int32_t* count, int k_stride) {
+    const size_t B = (size_t)h->B, nm = 3 * (size_t)k_stride * B;
+    TRY(gate_grow(h, h->inn.dmeas, nm));
+    TRY(gate_grow(h, h->inn.dcount, B));
+    HIP_TRY(hipMemcpyAsync(h->inn.dmeas, meas, sizeof(float) * nm, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->inn.dcount, count, sizeof(int32_t) * B, hipMemcpyHostToDevice, h->stream));
+    return SLAM_OK;
+}
+
+// the filtered message of one tick, the records of `ticks` ticks and the per-instance contributions
+int gate_reserve_step(slam_handle* h, int k_stride, size_t ticks) {
+    const size_t B = (size_t)h->B;
+    TRY(gate_grow(h, h->gate.dmeas, 3 * (size_t)k_stride * B));
+    TRY(gate_grow(h, h->gate.dcount, B));
+    TRY(gate_grow(h, h->gate.drej, ticks * B));
+    TRY(gate_grow(h, h->inn.dval, (1 + 12 + slam::kInnovRecLen) * B));
+    TRY(gate_grow(h, h->inn.dpart, (size_t)slam::innovation_blocks(h->B) * slam::kInnovRecLen));
+    TRY(gate_grow(h, h->inn.drec, ticks * slam::kInnovRecLen));
+    return SLAM_OK;
+}
+
+int gate_step_state(const slam_handle* h, const char* who) {
+    if (h->shadow) return fail(SLAM_ERR_STATE, "slam_track_instance is on: %s does not drive the shadow filter", who);
+    if (h->predicted) return fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev before %s", who);
+    return SLAM_OK;
+}
+
+// one gated timestep once the message and the commands are on the device
+int step_gated_now(slam_handle* h, const slam_gate_config& c, const float cmd[2], const float* d_cmd_each, const float* d_meas,
+                   const int32_t* d_count, int k_stride, double* rec, int32_t* n_rej) {
+    const size_t B = (size_t)h->B;
+    TRY(gate_reserve_step(h, k_stride, 1));
+    TRY(gate_launch(h, c, cmd, d_cmd_each, d_meas, d_count, k_stride, h->gate.dmeas, h->gate.dcount, h->inn.drec, nullptr, nullptr, nullptr, nullptr,
+                    nullptr, nullptr, h->gate.drej, nullptr));
+    TRY(launch_step(h, cmd, 0, h->gate.dmeas, h->gate.dcount, k_stride, d_cmd_each));
+    if (!rec && !n_rej) return SLAM_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (rec) HIP_TRY(hipMemcpy(rec, h->inn.drec, sizeof(double) * slam::kInnovRecLen, hipMemcpyDeviceToHost));
+    if (n_rej) HIP_TRY(hipMemcpy(n_rej, h->gate.drej, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+    return SLAM_OK;
+}
+
+int step_gated_host(slam_handle* h, const slam_gate_config* cfg, const float* cmds, int cmd_each, const float* meas, const int32_t* count,
+                    int k_stride, double* rec, int32_t* n_rej) {
+    slam_gate_config c;
+    TRY(gate_enter(h, cfg, cmds, meas, count, k_stride, nullptr, nullptr, false, &c));
+    TRY(gate_step_state(h, "a gated step"));
+    TRY(gate_upload_message(h, meas, count, k_stride));
+    if (cmd_each) TRY(innovation_upload_cmds(h, cmds, 2 * (size_t)h->B));
+    return step_gated_now(h, c, cmd_each ? kNoCmd : cmds, cmd_each ? h->inn.dcmd.get() : nullptr, h->inn.dmeas, h->inn.dcount, k_stride, rec, n_rej);
+}
+
+int step_gated_dev(slam_handle* h, const slam_gate_config* cfg, const float* cmds, int cmd_each, const float* d_meas, const int32_t* d_count,
+                   int k_stride, double* rec, int32_t* n_rej) {
+    slam_gate_config c;
+    TRY(gate_enter(h, cfg, cmds, d_meas, d_count, k_stride, nullptr, nullptr, false, &c));
+    TRY(gate_step_state(h, "a gated step"));
+    return step_gated_now(h, c, cmd_each ? kNoCmd : cmds, cmd_each ? cmds : nullptr, d_meas, d_count, k_stride, rec, n_rej);
+}
+
+}  // namespace
+
+extern "C" {
+
+int slam_gate_config_default(slam_gate_config* c) {
+    if (!c) return fail(SLAM_ERR_ARG, "cfg is NULL");
+    memset(c, 0, sizeof(*c));
+    c->gate = -2.0 * log(0.001);   // the 0.999 quantile of chi-square with 2 degrees of freedom
+    c->nis_lo = -2.0 * log(0.975); c->nis_hi = -2.0 * log(0.025);
+    return SLAM_OK;
+}
+
+int slam_gate(slam_handle* h, const slam_gate_config* cfg, const float* cmds, int cmd_each, const float* meas, const int32_t* count, int k_stride,
+              double rec[16], double* nis_sum, int32_t* n_upd, int32_t* n_new, int32_t* flags, double* det, double* post, float* meas_out,
+              int32_t* count_out, int32_t* n_rej, int32_t* verdict) {
+    slam_gate_config c;
+    TRY(gate_enter(h, cfg, cmds, meas, count, k_stride, meas_out, count_out, false, &c));
+    const size_t B = (size_t)h->B, nm = 3 * (size_t)k_stride * B;
+    TRY(gate_upload_message(h, meas, count, k_stride));
+    if (cmd_each) TRY(innovation_upload_cmds(h, cmds, 2 * B));
+    TRY(gate_grow(h, h->gate.dmeas, nm));
+    TRY(gate_grow(h, h->gate.dcount, B));
+    // (slots the kernel does not write keep what the caller gave: the output row starts as the input row)
+    HIP_TRY(hipMemcpyAsync(h->gate.dmeas, h->inn.dmeas, sizeof(float) * nm, hipMemcpyDeviceToDevice, h->stream));
+    TRY(gate_now(h, c, cmd_each ? kNoCmd : cmds, cmd_each ? h->inn.dcmd.get() : nullptr, h->inn.dmeas, h->inn.dcount, k_stride, h->gate.dmeas,
+                 h->gate.dcount, rec, nis_sum, n_upd, n_new, flags, det, post, n_rej, verdict));
+    if (meas_out) HIP_TRY(hipMemcpy(meas_out, h->gate.dmeas, sizeof(float) * nm, hipMemcpyDeviceToHost));
+    if (count_out) HIP_TRY(hipMemcpy(count_out, h->gate.dcount, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+    return SLAM_OK;
+}
+
+int slam_gate_dev(slam_handle* h, const slam_gate_config* cfg, const float* cmds, int cmd_each, const float* d_meas, const int32_t* d_count,
+                  int k_stride, double rec[16], double* nis_sum, int32_t* n_upd, int32_t* n_new, int32_t* flags, double* det, double* post,
+                  float* d_meas_out, int32_t* d_count_out, int32_t* n_rej, int32_t* verdict) {
+    slam_gate_config c;
+    TRY(gate_enter(h, cfg, cmds, d_meas, d_count, k_stride, d_meas_out, d_count_out, true, &c));
+    const size_t B = (size_t)h->B, bm = sizeof(float) * 3 * (size_t)k_stride * B, bc = sizeof(int32_t) * B;
+    if ((d_meas_out != d_meas && gate_overlap(d_meas_out, bm, d_meas, bm)) || (d_count_out != d_count && gate_overlap(d_count_out, bc, d_count, bc)) ||
+        gate_overlap(d_meas_out, bm, d_count, bc) || gate_overlap(d_count_out, bc, d_meas, bm) || gate_overlap(d_meas_out, bm, d_count_out, bc))
+        return fail(SLAM_ERR_ARG, "the output message overlaps the input (only d_meas_out == d_meas with d_count_out == d_count is allowed) or itself");
+    return gate_now(h, c, cmd_each ? kNoCmd : cmds, cmd_each ? cmds : nullptr, d_meas, d_count, k_stride, d_meas_out, d_count_out, rec, nis_sum, n_upd,
+                    n_new, flags, det, post, n_rej, verdict);
+}
+
+int slam_step_gated(slam_handle* h, const slam_gate_config* cfg, const float cmd[2], const float* meas, const int32_t* count, int k_stride,
+                    double rec[16], int32_t* n_rej) {
+    return step_gated_host(h, cfg, cmd, 0, meas, count, k_stride, rec, n_rej);
+}
+
+int slam_step_gated_dev(slam_handle* h, const slam_gate_config* cfg, const float cmd[2], const float* d_meas, const int32_t* d_count, int k_stride,
+                        double rec[16], int32_t* n_rej) {
+    return step_gated_dev(h, cfg, cmd, 0, d_meas, d_count, k_stride, rec, n_rej);
+}
+
+int slam_step_gated_each(slam_handle* h, const slam_gate_config* cfg, const float* cmds, const float* meas, const int32_t* count, int k_stride,
+                         double rec[16], int32_t* n_rej) {
+    return step_gated_host(h, cfg, cmds, 1, meas, count, k_stride, rec, n_rej);
+}
+
+int slam_step_gated_each_dev(slam_handle* h, const slam_gate_config* cfg, const float* d_cmds, const float* d_meas, const int32_t* d_count,
+                             int k_stride, double rec[16], int32_t* n_rej) {
+    return step_gated_dev(h, cfg, d_cmds, 1, d_meas, d_count, k_stride, rec, n_rej);
+}
+
+int slam_gate_run(slam_handle* h, const slam_gate_config* cfg, const float* cmds, int cmd_each, const float* meas, const int32_t* count,
+                  int k_stride, int T, double* recs, double* nis_sum, int32_t* n_upd, int32_t* n_rej, int32_t* flags) {
+    slam_gate_config c;
+    TRY(gate_config(cfg, &c));
+    if (T < 0) return fail(SLAM_ERR_ARG, "T = %d is negative", T);
+    if (!cmds) return fail(SLAM_ERR_ARG, "cmds is NULL");
+    if (!meas || !count) return fail(SLAM_ERR_ARG, "meas or meas_count is NULL");
+    if (k_stride <= 0) return fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
+    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
+    TRY(innovation_supported(h));
+    if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
+    TRY(gate_step_state(h, "slam_gate_run"));
+    TRY(flush_lazy(h));
+    if (T == 0) return SLAM_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t B = (size_t)h->B, row = 2 * B, mrow = 3 * (size_t)k_stride * B;
+    // ticks per chunk, as slam_innovation_run: the rows of the series, of the commands (cmd_each) and of the messages of a chunk stay
+    // within SLAM_MONITOR_LOG_BYTES (one tick at least)
+    int chunk = T < 4096 ? T : 4096;
+    {
+        const double per_tick = 8.0 * (nis_sum ? (double)B : 0.0) + 4.0 * (double)B * ((n_upd ? 1 : 0) + (flags ? 1 : 0) + (n_rej ? 1 : 0)) +
+                                (cmd_each ? 4.0 * (double)row : 0.0) + 4.0 * (double)mrow + 4.0 * (double)B;
+        const char* env = getenv("SLAM_MONITOR_LOG_BYTES");
+        const double fit = (env ? atof(env) : 256.0 * 1024 * 1024) / per_tick;
+        if (fit < (double)chunk) chunk = fit >= 1.0 ? (int)fit : 1;
+    }
+    TRY(gate_reserve_step(h, k_stride, (size_t)chunk));
+    if (nis_sum) TRY(gate_grow(h, h->inn.dlog, (size_t)chunk * B));
+    TRY(gate_grow(h, h->inn.dint, 2 * (size_t)chunk * B));
+    TRY(gate_grow(h, h->inn.dmeas, mrow * chunk));
+    TRY(gate_grow(h, h->inn.dcount, B * chunk));
+    const bool timed = h->nav.time_ticks;
+    while (h->inn.ev.size() < 2 + (timed ? 2 * (size_t)chunk : 0)) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreate(&e));
+        h->inn.ev.push_back(e);
+    }
+    h->gate.gate_ms = timed ? 0.0 : -1.0; h->gate.total_ms = 0.0;
+    hipEvent_t* const ev = h->inn.ev.data();
+    int32_t* const d_upd = h->inn.dint;
+    int32_t* const d_flags = h->inn.dint + (size_t)chunk * B;
+    for (int t0 = 0; t0 < T; t0 += chunk) {
+        const int tc = T - t0 < chunk ? T - t0 : chunk;
+        if (cmd_each) TRY(upload_cmds_each(h, cmds + (size_t)t0 * row, tc));
+        HIP_TRY(hipMemcpyAsync(h->inn.dmeas, meas + (size_t)t0 * mrow, sizeof(float) * mrow * tc, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->inn.dcount, count + (size_t)t0 * B, sizeof(int32_t) * B * tc, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipEventRecord(ev[0], h->stream));
+        for (int t = 0; t < tc; ++t) {
+            const float* const cmd = cmd_each ? kNoCmd : cmds + 2 * (size_t)(t0 + t);
+            const float* const d_each = cmd_each ? h->dcmd_each + (size_t)t * row : nullptr;
+            if (timed) HIP_TRY(hipEventRecord(ev[2 + 2 * t], h->stream));
+            TRY(gate_launch(h, c, cmd, d_each, h->inn.dmeas + (size_t)t * mrow, h->inn.dcount + (size_t)t * B, k_stride, h->gate.dmeas, h->gate.dcount,
+                            h->inn.drec + (size_t)t * slam::kInnovRecLen, nis_sum ? h->inn.dlog + (size_t)t * B : nullptr, nullptr, nullptr,
+                            n_upd ? d_upd + (size_t)t * B : nullptr, flags ? d_flags + (size_t)t * B : nullptr, nullptr,
+                            h->gate.drej + (size_t)t * B, nullptr));
+            if (timed) HIP_TRY(hipEventRecord(ev[3 + 2 * t], h->stream));
+            TRY(launch_step(h, cmd, 0, h->gate.dmeas, h->gate.dcount, k_stride, d_each));
+        }
+        HIP_TRY(hipEventRecord(ev[1], h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        h->gate.total_ms += (double)ms;
+        for (int t = 0; timed && t < tc; ++t) {
+            HIP_TRY(hipEventElapsedTime(&ms, ev[2 + 2 * t], ev[3 + 2 * t]));
+            h->gate.gate_ms += (double)ms;
+        }
+        if (recs) HIP_TRY(hipMemcpy(recs + (size_t)t0 * slam::kInnovRecLen, h->inn.drec, sizeof(double) * (size_t)tc * slam::kInnovRecLen, hipMemcpyDeviceToHost));
+        if (nis_sum) HIP_TRY(hipMemcpy(nis_sum + (size_t)t0 * B, h->inn.dlog, sizeof(double) * (size_t)tc * B, hipMemcpyDeviceToHost));
+        if (n_upd) HIP_TRY(hipMemcpy(n_upd + (size_t)t0 * B, d_upd, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
+        if (flags) HIP_TRY(hipMemcpy(flags + (size_t)t0 * B, d_flags, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
+        if (n_rej) HIP_TRY(hipMemcpy(n_rej + (size_t)t0 * B, h->gate.drej, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
+    }
+    return SLAM_OK;
+}
+
+int slam_last_gate_work(slam_handle* h, double* gate_ms, double* total_ms) {
+    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
+    if (h->gate.total_ms < 0.0) return fail(SLAM_ERR_STATE, "slam_gate_run has not run on this handle");
+    if (gate_ms) *gate_ms = h->gate.gate_ms;
+    if (total_ms) *total_ms = h->gate.total_ms;
+    return SLAM_OK;
+}
+
+int slam_gate_instance_host(const double* x, const double* P, const int32_t* ids, int M, int L_max, int32_t status, const float cmd[2],
+                            const float* meas, int count, int k_stride, const slam_noise* noise, int lm_from_pred, int f32_storage,
+                            const slam_gate_config* cfg, double rec[16], double* nis_sum, int32_t* n_upd, int32_t* n_new, int32_t* flags,
+                            double* det, double* post, float* meas_out, int32_t* count_out, int32_t* n_rej, int32_t* verdict) {
+    slam_gate_config c;
+    TRY(gate_config(cfg, &c));
+    if (!x || !P || !cmd || !noise) return fail(SLAM_ERR_ARG, "NULL argument");
+    if (L_max < 0 || M < 0 || M > L_max) return fail(SLAM_ERR_ARG, "M = %d is not in [0, L_max = %d]", M, L_max);
+    if (M > 0 && !ids) return fail(SLAM_ERR_ARG, "ids is NULL");
+    if (k_stride <= 0) return fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
+    if (count > 0 && !meas) return fail(SLAM_ERR_ARG, "meas is NULL");
+    if (const char* f = slam_host::noise_bad_field(*noise)) return fail(SLAM_ERR_ARG, "noise: %s is not finite", f);
+    const slam::InnovNoise nz = {noise->v_d, noise->v_th, noise->w_r, noise->w_b, noise->V_00, noise->V_11, noise->W_00, noise->W_11};
+    const int n = 3 + 2 * M;
+    std::vector<slam::InnovWork> ws(1);
+    const bool f32 = f32_storage != 0;
+    int32_t rej = 0;
+    const slam::InnovResult v = slam::gate_instance_host(
+        ws[0], [&](int i) { return f32 ? (double)(float)x[i] : x[i]; },
+        [&](int r, int cc) { const double e = P[(size_t)r * n + cc]; return f32 ? (double)(float)e : e; }, ids, M, L_max, status, cmd[0], cmd[1], meas,
+        count, k_stride, nz, lm_from_pred != 0, c.nis_lo, c.nis_hi, c.gate, det, meas_out, count_out, &rej, verdict);
+    if (rec) slam::gate_record(v, rej, rec);
+    if (nis_sum) *nis_sum = v.nis_sum;
+    if (n_upd) *n_upd = v.n_upd;
+    if (n_new) *n_new = v.n_new;
+    if (flags) *flags = v.flags;
+    if (post) memcpy(post, v.post, sizeof(v.post));
+    if (n_rej) *n_rej = rej;
     return SLAM_OK;
 }
 

@@ -17,6 +17,7 @@ from .config import MonitorConfig, default_monitor_config, MONITOR_SHARED, MONIT
 from .config import Noise
 from .config import (InnovationConfig, default_innovation_config, INNOVATION_SHARED, INNOVATION_EACH, INNOVATION_NAV, INNOVATION_LOG,
                      INNOV_MAX_DET)
+from .config import GateConfig, default_gate_config
 
 
 def _d(a):
@@ -59,6 +60,17 @@ class InnovationResult:
 
     def __init__(self, recs, nis_sum=None, n_upd=None, flags=None):
         self.recs, self.nis_sum, self.n_upd, self.flags = recs, nis_sum, n_upd, flags
+
+
+class GateResult(InnovationResult):
+    """What gate_run returns: `recs` (T, 16) as InnovationResult, entries 5 and 7 - 14 over the accepted updates and REC_N_REJ = 15 the
+    rejected detections, and - with series=True, else None - `nis_sum`, `n_upd`, `n_rej`, `flags`, (T, batch) each."""
+
+    REC_N_REJ = 15
+
+    def __init__(self, recs, nis_sum=None, n_upd=None, n_rej=None, flags=None):
+        InnovationResult.__init__(self, recs, nis_sum, n_upd, flags)
+        self.n_rej = n_rej
 
 
 class BatchedFilter:
@@ -648,6 +660,126 @@ class BatchedEKF(BatchedFilter):
         _lib.check(_lib.lib().slam_last_innovation_work(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    # -- the chi-square gate on every detection (slam_gate_*, include/slam_batch.h) --
+    def _gate_config(self, cfg):
+        if cfg is None:
+            return default_gate_config()
+        if isinstance(cfg, GateConfig):
+            return cfg
+        c = default_gate_config()
+        for k, v in dict(cfg).items():
+            if k not in ("gate", "nis_lo", "nis_hi"):
+                raise ValueError(f"unknown gate setting {k!r}")
+            setattr(c, k, v)
+        return c
+
+    def _message(self, meas, meas_count):
+        m = np.ascontiguousarray(meas, dtype=np.float32)
+        cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
+        if m.ndim != 3 or m.shape[0] != self.batch or m.shape[1] == 0 or m.shape[2] != 3 or cnt.shape != (self.batch,):
+            raise ValueError(f"expected meas of shape ({self.batch}, k_stride > 0, 3) and meas_count of shape ({self.batch},)")
+        return m, cnt
+
+    def _gate_outputs(self, det):
+        B = self.batch
+        out = dict(rec=np.zeros(16), nis_sum=np.zeros(B), n_upd=np.zeros(B, dtype=np.int32), n_new=np.zeros(B, dtype=np.int32),
+                   flags=np.zeros(B, dtype=np.int32), post=np.zeros((B, 12)), n_rej=np.zeros(B, dtype=np.int32),
+                   verdict=np.zeros((B, INNOV_MAX_DET), dtype=np.int32))
+        if det:
+            out["det"] = np.zeros((B, INNOV_MAX_DET, 6))
+        return out
+
+    def gate(self, cmdMsg, meas, meas_count, det=True, cfg=None):
+        """The chi-square gate on the message the next update(cmdMsg, meas, meas_count) would be given, changing nothing in the filter:
+        the dict of innovation() - nis_sum, post and the record over the ACCEPTED updates - plus n_rej [batch], verdict
+        (batch, INNOV_MAX_DET) (0 no update slot, 1 accepted, 2 rejected), and the filtered message meas_out (batch, k_stride, 3),
+        count_out [batch]: update(cmdMsg, meas_out, count_out) is the gated step.  cfg: a GateConfig, a dict of its fields, or None."""
+        self._need()
+        cmd = self._cmd(cmdMsg)
+        m, cnt = self._message(meas, meas_count)
+        out = self._gate_outputs(det)
+        out["meas_out"], out["count_out"] = np.zeros_like(m), np.zeros_like(cnt)
+        _lib.check(_lib.lib().slam_gate(self.h, C.byref(self._gate_config(cfg)), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt), m.shape[1],
+                                        _d(out["rec"]), _d(out["nis_sum"]), _i(out["n_upd"]), _i(out["n_new"]), _i(out["flags"]),
+                                        _d(out["det"]) if det else None, _d(out["post"]), _f(out["meas_out"]), _i(out["count_out"]),
+                                        _i(out["n_rej"]), _i(out["verdict"])))
+        return out
+
+    def gate_dev(self, cmdMsg, d_meas_ptr, d_count_ptr, k_stride, d_meas_out_ptr, d_count_out_ptr, det=True, cfg=None):
+        """gate() on DEVICE messages: cmdMsg one command (host) or, as an int, the device pointer of (batch, 2) commands; the filtered
+        message is written to d_meas_out_ptr / d_count_out_ptr, which may be the input pair itself (in place).  Returns the dict of gate()
+        without meas_out and count_out."""
+        self._need()
+        each = isinstance(cmdMsg, int)
+        cmd = None if each else self._cmd(cmdMsg)
+        if cmd is not None and cmd.ndim != 1:
+            raise ValueError("gate_dev takes one command, or the device pointer of per-instance commands")
+        out = self._gate_outputs(det)
+        cp = C.c_void_p(cmdMsg) if each else C.cast(_f(cmd), C.c_void_p)
+        _lib.check(_lib.lib().slam_gate_dev(self.h, C.byref(self._gate_config(cfg)), cp, int(each), C.c_void_p(d_meas_ptr),
+                                            C.c_void_p(d_count_ptr), int(k_stride), _d(out["rec"]), _d(out["nis_sum"]), _i(out["n_upd"]),
+                                            _i(out["n_new"]), _i(out["flags"]), _d(out["det"]) if det else None, _d(out["post"]),
+                                            C.c_void_p(d_meas_out_ptr), C.c_void_p(d_count_out_ptr), _i(out["n_rej"]), _i(out["verdict"])))
+        return out
+
+    def step_gated(self, cmdMsg, meas, meas_count, stats=True, cfg=None):
+        """One gated timestep: the gate, then the ordinary step on the filtered message, on the device.  cmdMsg one command or (batch, 2);
+        host message as gate().  stats=True returns dict(rec (16,), n_rej [batch]) and synchronises; stats=False returns None."""
+        self._need()
+        cmd = self._cmd(cmdMsg)
+        m, cnt = self._message(meas, meas_count)
+        out = dict(rec=np.zeros(16), n_rej=np.zeros(self.batch, dtype=np.int32)) if stats else None
+        fn = _lib.lib().slam_step_gated_each if cmd.ndim == 2 else _lib.lib().slam_step_gated
+        _lib.check(fn(self.h, C.byref(self._gate_config(cfg)), _f(cmd), _f(m), _i(cnt), m.shape[1], _d(out["rec"]) if stats else None,
+                      _i(out["n_rej"]) if stats else None))
+        self.timestep += 1
+        return out
+
+    def step_gated_dev(self, cmdMsg, d_meas_ptr, d_count_ptr, k_stride, stats=True, cfg=None):
+        """step_gated() on DEVICE messages; cmdMsg one command (host) or, as an int, the device pointer of (batch, 2) commands."""
+        self._need()
+        each = isinstance(cmdMsg, int)
+        out = dict(rec=np.zeros(16), n_rej=np.zeros(self.batch, dtype=np.int32)) if stats else None
+        args = (C.c_void_p(d_meas_ptr), C.c_void_p(d_count_ptr), int(k_stride), _d(out["rec"]) if stats else None, _i(out["n_rej"]) if stats else None)
+        if each:
+            _lib.check(_lib.lib().slam_step_gated_each_dev(self.h, C.byref(self._gate_config(cfg)), C.c_void_p(cmdMsg), *args))
+        else:
+            cmd = self._cmd(cmdMsg)
+            if cmd.ndim != 1:
+                raise ValueError("step_gated_dev takes one command, or the device pointer of per-instance commands")
+            _lib.check(_lib.lib().slam_step_gated_dev(self.h, C.byref(self._gate_config(cfg)), _f(cmd), *args))
+        self.timestep += 1
+        return out
+
+    def gate_run(self, cmds, meas, meas_count, series=False, cfg=None):
+        """T gated ticks of a recorded log: cmds (T, 2) or (T, batch, 2), meas (T, batch, k_stride, 3), meas_count (T, batch); the same bits
+        as T step_gated calls.  Returns a GateResult; series=True also records nis_sum, n_upd, n_rej and flags of every instance."""
+        self._need()
+        c32 = np.ascontiguousarray(cmds, dtype=np.float32)
+        m = np.ascontiguousarray(meas, dtype=np.float32)
+        cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
+        each = c32.ndim == 3
+        if c32.shape[1:] != ((self.batch, 2) if each else (2,)) or m.ndim != 4 or m.shape[:2] != (c32.shape[0], self.batch) or m.shape[2] == 0 \
+                or m.shape[3] != 3 or cnt.shape != m.shape[:2]:
+            raise ValueError(f"a log needs cmds (T, 2) or (T, {self.batch}, 2), meas (T, {self.batch}, k_stride > 0, 3) and meas_count (T, {self.batch})")
+        T = c32.shape[0]
+        res = GateResult(np.zeros((T, 16)))
+        if series:
+            res.nis_sum = np.zeros((T, self.batch))
+            res.n_upd, res.n_rej, res.flags = (np.zeros((T, self.batch), dtype=np.int32) for _ in range(3))
+        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
+        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
+        _lib.check(_lib.lib().slam_gate_run(self.h, C.byref(self._gate_config(cfg)), _f(c32), int(each), _f(m), _i(cnt), m.shape[2], T,
+                                            pd(res.recs), pd(res.nis_sum), pi(res.n_upd), pi(res.n_rej), pi(res.flags)))
+        self.timestep += T
+        return res
+
+    def last_gate_work(self):
+        """(device ms of the gate launches of the last gate_run, or -1 without set_nav_timing; device ms of the whole run)."""
+        self._need(); a = C.c_double(0); b = C.c_double(0)
+        _lib.check(_lib.lib().slam_last_gate_work(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
 
 def innovation_instance_host(x, P, ids, L_max, status, cmd, meas, noise, lm_from_pred=False, f32_storage=False, cfg=None):
     """TEST HOOK (slam_innovation_instance_host): the per-instance function of the innovation kernel compiled for the host; no GPU.
@@ -666,6 +798,32 @@ def innovation_instance_host(x, P, ids, L_max, status, cmd, meas, noise, lm_from
                                                         int(bool(f32_storage)), C.byref(c_cfg), _d(out["rec"]), C.byref(s), C.byref(nu),
                                                         C.byref(nn), C.byref(fl), _d(out["det"]), _d(out["post"])))
     out.update(nis_sum=s.value, n_upd=nu.value, n_new=nn.value, flags=fl.value)
+    return out
+
+
+def gate_instance_host(x, P, ids, L_max, status, cmd, meas, noise, lm_from_pred=False, f32_storage=False, cfg=None, count=None, k_stride=None):
+    """TEST HOOK (slam_gate_instance_host): the per-instance function of the gate kernel compiled for the host; no GPU.  Arguments as
+    innovation_instance_host; count (default: the rows of meas) is the count as given and k_stride (default: max(rows, 1)) the capacity
+    of the message row.  Returns the dict of gate() for one instance: meas_out (k_stride, 3) starts as a copy of the input row."""
+    x = np.ascontiguousarray(x, dtype=np.float64); P = np.ascontiguousarray(P, dtype=np.float64)
+    ids = np.ascontiguousarray(ids, dtype=np.int32); M = ids.shape[0]
+    m = np.ascontiguousarray(meas, dtype=np.float32).reshape(-1, 3)
+    c = np.ascontiguousarray(cmd, dtype=np.float32).reshape(2)
+    if x.shape != (3 + 2 * M,) or P.shape != (3 + 2 * M, 3 + 2 * M):
+        raise ValueError("x and P do not match the number of ids")
+    ks = max(m.shape[0], 1) if k_stride is None else int(k_stride)
+    count = m.shape[0] if count is None else int(count)
+    if ks < m.shape[0]:
+        raise ValueError("k_stride is smaller than the message")
+    row = np.zeros((ks, 3), dtype=np.float32); row[:m.shape[0]] = m
+    out = dict(rec=np.zeros(16), det=np.zeros((INNOV_MAX_DET, 6)), post=np.zeros(12), meas_out=row.copy(), verdict=np.zeros(INNOV_MAX_DET, dtype=np.int32))
+    s = C.c_double(0); nu = C.c_int32(0); nn = C.c_int32(0); fl = C.c_int32(0); co = C.c_int32(0); nr = C.c_int32(0)
+    c_cfg = default_gate_config() if cfg is None else cfg
+    _lib.check(_lib.lib().slam_gate_instance_host(_d(x), _d(P), _i(ids) if M else None, M, int(L_max), int(status), _f(c), _f(row), count, ks,
+                                                  C.byref(noise), int(bool(lm_from_pred)), int(bool(f32_storage)), C.byref(c_cfg),
+                                                  _d(out["rec"]), C.byref(s), C.byref(nu), C.byref(nn), C.byref(fl), _d(out["det"]),
+                                                  _d(out["post"]), _f(out["meas_out"]), C.byref(co), C.byref(nr), _i(out["verdict"])))
+    out.update(nis_sum=s.value, n_upd=nu.value, n_new=nn.value, flags=fl.value, count_out=co.value, n_rej=nr.value)
     return out
 
 
