@@ -597,8 +597,10 @@ int slam_nav_set_path(slam_handle* h, const slam_nav_config* cfg, const double* 
 int slam_nav_set_paths(slam_handle* h, const slam_nav_config* cfg, const double* pts, const int32_t* P, int P_stride);
 /* T ticks of {controller, one SIM timestep}.  Runs the EKF step queue first and is not queued itself; advances truth, error sums,
  * timestep and RNG exactly as T calls of slam_run_sim_each(h, cmds, 1) with the same commands would.  cmds_out: host [T][batch][2], the
- * commands issued (NULL: not wanted).  SLAM_ERR_STATE also while a slam_predict is pending.  Returns when the ticks are done (long runs
- * and command logs are processed in chunks of ticks, each ending synchronised). */
+ * commands issued (NULL: not wanted).  SLAM_ERR_STATE also while a slam_predict is pending.  Returns when the ticks are done.  Long runs
+ * are processed in chunks of ticks by the rule of slam_monitor_run, each ending synchronised with its rows of cmds_out copied out: at most
+ * 4096 ticks, and - when cmds_out is given - at most as many as keep the command log of a chunk (8 bytes per instance and tick) within
+ * SLAM_MONITOR_LOG_BYTES (default 256 MiB; one tick at least).  Chunking changes no bit. */
 int slam_nav_run(slam_handle* h, int T, float* cmds_out);
 /* Controller state, [batch] each, any pointer may be NULL: remaining = waypoints still queued. */
 int slam_nav_state(slam_handle* h, int32_t* remaining, int32_t* finish_tick, double* integ, double* err_prev);

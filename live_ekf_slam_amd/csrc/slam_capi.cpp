@@ -20,6 +20,7 @@
 #include "consistency_kernel.h"
 #include "host/config_parse.h"
 #include "host/noise_pack.h"
+#include "host/tick_chunks.h"
 #include "ekf_kernel.h"
 #include "gate_kernel.h"
 #include "innovation_kernel.h"
@@ -77,6 +78,10 @@ struct StepQueue {
     // buffers in stream order, as with an immediate launch); one buffer suffices, since copies and launches share the stream
     DevBuf<float> dmeas; DevBuf<int32_t> dcount;  // [lazy_max][B][ks][3], [lazy_max][B]
 };
+
+// Device times of the last per-tick run of one kind (run_chunked): part_ms is the sum over the launch group each tick marks, -1 while
+// slam_nav_set_timing is off; total_ms is the sum over the chunks, -1 until such a run has run on the handle.
+struct RunTimes { double part_ms = -1.0, total_ms = -1.0; };
 
 }  // namespace
 
@@ -158,7 +163,7 @@ struct slam_handle {
     DevBuf<double> dcons, dcons_ws; DevBuf<int32_t> dconsi;
     double cons_bytes = 0.0, cons_ms = -1.0;
     // slam_nav_*: the path (shared [P][2], or [B][stride][2] with [B] lengths), the controller state of every instance, the command log
-    // of one chunk of ticks, ticks since the state was reset, the event pool and the device times of the last slam_nav_run
+    // of one chunk of ticks, ticks since the state was reset and the device times of the last slam_nav_run
     struct Nav {
         bool set = false, each = false;
         slam_nav_config cfg;
@@ -167,31 +172,31 @@ struct slam_handle {
         DevBuf<int32_t> dhead, dfinish; DevBuf<double> dinteg, derrp;
         DevBuf<float> dlog;
         int tick = 0;
-        std::vector<hipEvent_t> ev;
-        bool time_ticks = false;   // slam_nav_set_timing: an event pair around every controller launch
-        double ctrl_ms = -1.0, total_ms = -1.0;
+        bool time_ticks = false;   // slam_nav_set_timing: every per-tick run brackets one launch group of each tick with an event pair
+        RunTimes times;
     } nav;
+    // the events of a per-tick run (run_chunked): one pair per chunk and, while time_ticks is on, one per tick of a chunk.  One pool serves
+    // every kind of run: a run returns synchronised, so two never overlap on a handle.
+    std::vector<hipEvent_t> run_ev;
     // slam_monitor_*: the per-workgroup partial records of one evaluation, the records and the per-instance series of one chunk of ticks
-    // ([series][ticks][B] doubles, [B] flags of slam_monitor_now), the event pool and the device times of the last slam_monitor_run
+    // ([series][ticks][B] doubles, [B] flags of slam_monitor_now) and the device times of the last slam_monitor_run
     struct Mon {
         DevBuf<double> dpart, drec, dlog; DevBuf<int32_t> dflags;
-        std::vector<hipEvent_t> ev;
-        double mon_ms = -1.0, total_ms = -1.0;
+        RunTimes times;
     } mon;
     // slam_innovation_*: the staged message and per-instance commands of a host-fed evaluation (one chunk of ticks for the LOG source), the
     // per-instance outputs ([B] nis_sum, [B][12] post, [B][16] contributions, the partial records, the records and the nis_sum series of a
-    // chunk; [B][64][6] detection slots when asked for; [3][ticks][B] n_upd, flags, n_new), the event pool and the device times of the last run
+    // chunk; [B][64][6] detection slots when asked for; [3][ticks][B] n_upd, flags, n_new) and the device times of the last run
     struct Inn {
         DevBuf<float> dmeas, dcmd; DevBuf<int32_t> dcount;
         DevBuf<double> dval, ddet, dpart, drec, dlog; DevBuf<int32_t> dint;
-        std::vector<hipEvent_t> ev;
-        double inn_ms = -1.0, total_ms = -1.0;
+        RunTimes times;
     } inn;
     // slam_gate_*: the filtered message of a gated step or of one tick of slam_gate_run ([B][k_stride][3] and [B] counts), [ticks][B] n_rej
-    // and [B][64] verdicts, the device times of the last slam_gate_run.  Everything else is staged in `inn`, its event pool included.
+    // and [B][64] verdicts, the device times of the last slam_gate_run.  Everything else is staged in `inn`.
     struct Gate {
         DevBuf<float> dmeas; DevBuf<int32_t> dcount, drej, dverdict;
-        double gate_ms = -1.0, total_ms = -1.0;
+        RunTimes times;
     } gate;
 };
 
@@ -338,11 +343,13 @@ int ensure_meas_buffers(slam_handle* h, int k_stride) {
     return SLAM_OK;
 }
 
-// the device command buffer of a multi-step launch: room for T timesteps (the launches that read the old one are done first)
-int reserve_cmds(slam_handle* h, int T) {
-    if (h->dcmds.cap() >= 2 * (size_t)T) return SLAM_OK;
-    if (h->dcmds) HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(h->dcmds.reserve(2 * (size_t)T));
+// Room for n elements in a buffer of the handle that launches in flight may still use: they finish before it is replaced.  A buffer that
+// has its size costs a comparison.
+template <class T>
+int grow(slam_handle* h, DevBuf<T>& buf, size_t n) {
+    if (buf.cap() >= n) return SLAM_OK;
+    if (buf) HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(buf.reserve(n));
     return SLAM_OK;
 }
 
@@ -355,10 +362,7 @@ int upload_cmds_each(slam_handle* h, const float* cmds, int T) {
     if (h->predicted) return fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev before the next step");
     const size_t n = 2 * (size_t)T * h->B;
     if (n == 0) return SLAM_OK;
-    if (h->dcmd_each.cap() < n) {
-        if (h->dcmd_each) HIP_TRY(hipStreamSynchronize(h->stream));
-        HIP_TRY(h->dcmd_each.reserve(n));
-    }
+    TRY(grow(h, h->dcmd_each, n));
     HIP_TRY(hipMemcpyAsync(h->dcmd_each, cmds, sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
     return SLAM_OK;
 }
@@ -585,9 +589,7 @@ int slam_destroy(slam_handle* h) {
     if (h->stream) hipStreamSynchronize(h->stream);
     for (auto& st : h->aux_stream) if (st) { hipStreamSynchronize(st); hipStreamDestroy(st); }
     for (auto& ev : h->aux_ev) if (ev) hipEventDestroy(ev);
-    for (auto& ev : h->nav.ev) if (ev) hipEventDestroy(ev);
-    for (auto& ev : h->mon.ev) if (ev) hipEventDestroy(ev);
-    for (auto& ev : h->inn.ev) if (ev) hipEventDestroy(ev);
+    for (auto& ev : h->run_ev) if (ev) hipEventDestroy(ev);
     if (h->copy_stream) { hipStreamSynchronize(h->copy_stream); hipStreamDestroy(h->copy_stream); }
     if (h->shadow_ev) hipEventDestroy(h->shadow_ev);
     for (auto& f : h->q.host)
@@ -924,7 +926,7 @@ static int run_sim_now(slam_handle* h, const float* cmds, int T, const float* d_
     // the true pose and the thin rows/cols of P on chip; only the P stream touches HBM each step.
     HIP_TRY(hipSetDevice(h->device));
     if (!d_cmd_each) {
-        TRY(reserve_cmds(h, T));
+        TRY(grow(h, h->dcmds, 2 * (size_t)T));
         HIP_TRY(hipMemcpyAsync(h->dcmds, cmds, sizeof(float) * 2 * (size_t)T, hipMemcpyHostToDevice, h->stream));
     }
     const int chunk = h->run_chunk > 0 ? h->run_chunk : T;
@@ -964,7 +966,7 @@ static int flush_lazy(slam_handle* h) {
             memcpy(f.hcmds, cmds, sizeof(float) * 2 * (size_t)T);
             cmds = f.hcmds; meas = f.dmeas; count = f.dcount;
         }
-        TRY(reserve_cmds(h, T));
+        TRY(grow(h, h->dcmds, 2 * (size_t)T));
         // device messages: a pageable source, so the copy is staged by the runtime before the call returns and q.cmds may be reused at once
         HIP_TRY(hipMemcpyAsync(h->dcmds, cmds, sizeof(float) * 2 * (size_t)T, hipMemcpyHostToDevice, h->stream));
         if (q.src == StepQueue::kHost) HIP_TRY(hipStreamWaitEvent(h->stream, f.copied, 0));
@@ -1839,6 +1841,118 @@ int nav_install(slam_handle* h, const slam_nav_config* cfg, bool each, int P, in
     return SLAM_OK;
 }
 
+// ---- per-tick runs (slam_nav_run, slam_monitor_run, slam_innovation_run, slam_gate_run): what they share -------------------------------------
+
+// The one place a NavParams is filled from the handle (everything but tick and cmd_log); the commands go to the first row of dcmd_each.
+int nav_params(slam_handle* h, slam::NavParams* out) {
+    TRY(grow(h, h->dcmd_each, 2 * (size_t)h->B));
+    slam::NavParams p;
+    memset(&p, 0, sizeof(p));
+    p.x = h->dx; p.flags = h->dflags; p.path = h->nav.dpath;
+    p.P_each = h->nav.each ? h->nav.dP.get() : nullptr; p.P = h->nav.P; p.path_stride = h->nav.stride;
+    p.B = h->B; p.xstride = h->xstride; p.ukf = h->kind != SLAM_EKF_SLAM;
+    p.c = nav_consts(h->nav.cfg, h->cfg.d_max, h->cfg.th_max);
+    p.head = h->nav.dhead; p.finish_tick = h->nav.dfinish; p.integ = h->nav.dinteg; p.err_prev = h->nav.derrp;
+    p.cmd_out = h->dcmd_each;
+    *out = p;
+    return SLAM_OK;
+}
+
+// the next controller tick on the handle's stream
+int nav_launch(slam_handle* h, slam::NavParams& p) {
+    p.tick = h->nav.tick;
+    HIP_TRY(slam::launch_nav_tick(p, h->esz == 4, h->stream));
+    h->nav.tick += 1;
+    return SLAM_OK;
+}
+
+int innovation_supported(const slam_handle* h);
+
+// What a per-tick run `who` checks once its own arguments are in order: the handle, then its state, then the queued timesteps run.
+// ekf_known_ids: the run evaluates innovations (innovation_supported).
+int run_enter(slam_handle* h, const char* who, bool need_map, bool need_path, bool ekf_known_ids) {
+    if (!h) return fail(SLAM_ERR_ARG, "%s: NULL handle", who);
+    if (ekf_known_ids) TRY(innovation_supported(h));
+    if (!h->inited) return fail(SLAM_ERR_STATE, "%s: slam_init has not been called", who);
+    if (need_map && !has_map(h)) return fail(SLAM_ERR_STATE, "%s runs the simulator: slam_set_map (or slam_set_maps) has not been called", who);
+    if (need_path && !h->nav.set) return fail(SLAM_ERR_STATE, "%s: no path: call slam_nav_set_path or slam_nav_set_paths first", who);
+    if (h->shadow) return fail(SLAM_ERR_STATE, "slam_track_instance is on: %s does not drive the shadow filter", who);
+    // (checked before the first launch: a controller tick would overwrite the commands the pending update stage reads)
+    if (h->predicted) return fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev before %s", who);
+    return flush_lazy(h);
+}
+
+// T ticks in chunks of `chunk`.  Per chunk: before(t0, tc) enqueues the uploads of ticks [t0, t0 + tc); tick(t0, t, mark) enqueues the
+// launches of tick t0 + t and passes the one launch group whose time is wanted through mark(launch); then the stream is synchronised and
+// after(t0, tc) copies the rows of the chunk out.  The device time of every chunk is summed into times.total_ms and, while `timed`, that of
+// every marked group into times.part_ms: an event pair per chunk and per tick of a chunk, from the handle's pool.
+template <class Before, class Tick, class After>
+int run_chunked(slam_handle* h, int T, int chunk, bool timed, RunTimes& times, Before before, Tick tick, After after) {
+    while (h->run_ev.size() < 2 + (timed ? 2 * (size_t)chunk : 0)) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreate(&e));
+        h->run_ev.push_back(e);
+    }
+    hipEvent_t* const ev = h->run_ev.data();
+    times.part_ms = timed ? 0.0 : -1.0; times.total_ms = 0.0;
+    for (int t0 = 0; t0 < T; t0 += chunk) {
+        const int tc = T - t0 < chunk ? T - t0 : chunk;
+        TRY(before(t0, tc));
+        HIP_TRY(hipEventRecord(ev[0], h->stream));
+        for (int t = 0; t < tc; ++t)
+            TRY(tick(t0, t, [&](auto launch) -> int {
+                if (timed) HIP_TRY(hipEventRecord(ev[2 + 2 * t], h->stream));
+                TRY(launch());
+                if (timed) HIP_TRY(hipEventRecord(ev[3 + 2 * t], h->stream));
+                return SLAM_OK;
+            }));
+        HIP_TRY(hipEventRecord(ev[1], h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        times.total_ms += (double)ms;
+        for (int t = 0; timed && t < tc; ++t) {
+            HIP_TRY(hipEventElapsedTime(&ms, ev[2 + 2 * t], ev[3 + 2 * t]));
+            times.part_ms += (double)ms;
+        }
+        TRY(after(t0, tc));
+    }
+    return SLAM_OK;
+}
+
+// slam_last_*_work; t: the times of that kind of run, NULL with a NULL handle
+int last_work(const RunTimes* t, const char* run, double* part_ms, double* total_ms) {
+    if (!t) return fail(SLAM_ERR_ARG, "NULL handle");
+    if (t->total_ms < 0.0) return fail(SLAM_ERR_STATE, "%s has not run on this handle", run);
+    if (part_ms) *part_ms = t->part_ms;
+    if (total_ms) *total_ms = t->total_ms;
+    return SLAM_OK;
+}
+
+// Where the command of a tick comes from: kShared: row t0 + t of the host array cmds [T][2]; kEach: cmds is [T][B][2] on the host, and the
+// rows of a chunk are uploaded to dcmd_each before its ticks; kNav: the controller computes them, one launch per tick.
+struct TickCmds {
+    enum Source { kShared, kEach, kNav } src;
+    const float* cmds;
+    slam::NavParams np;
+
+    int init(slam_handle* h, Source s, const float* host_cmds) {
+        src = s; cmds = host_cmds;
+        memset(&np, 0, sizeof(np));
+        return src == kNav ? nav_params(h, &np) : SLAM_OK;
+    }
+    double bytes_per_tick(const slam_handle* h) const { return src == kEach ? 4.0 * 2.0 * (double)h->B : 0.0; }   // on the device
+    int upload(slam_handle* h, int t0, int tc) const { return src == kEach ? upload_cmds_each(h, cmds + (size_t)t0 * 2 * h->B, tc) : SLAM_OK; }
+    // tick t of the chunk at t0: the shared command and the device row of per-instance commands (NULL: shared) of its step launch
+    int select(slam_handle* h, int t0, int t, const float** cmd, const float** d_each) {
+        *cmd = kNoCmd; *d_each = h->dcmd_each;
+        if (src == kNav) return nav_launch(h, np);
+        if (src == kEach) *d_each = h->dcmd_each + (size_t)t * 2 * h->B;
+        else { *cmd = cmds + 2 * (size_t)(t0 + t); *d_each = nullptr; }
+        return SLAM_OK;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -1876,69 +1990,27 @@ int slam_nav_set_paths(slam_handle* h, const slam_nav_config* cfg, const double*
 }
 
 int slam_nav_run(slam_handle* h, int T, float* cmds_out) {
-    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
     if (T < 0) return fail(SLAM_ERR_ARG, "T = %d is negative", T);
-    if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
-    if (!h->nav.set) return fail(SLAM_ERR_STATE, "no path: call slam_nav_set_path or slam_nav_set_paths first");
-    if (!has_map(h)) return fail(SLAM_ERR_STATE, "slam_set_map has not been called");
-    if (h->shadow) return fail(SLAM_ERR_STATE, "slam_track_instance is on: the shadow filter cannot follow commands computed on the device");
-    // (checked before the first controller launch: it would overwrite the commands the pending update stage reads and advance the controller)
-    if (h->predicted) return fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev before slam_nav_run");
-    TRY(flush_lazy(h));
+    TRY(run_enter(h, "slam_nav_run", true, true, false));
     if (T == 0) return SLAM_OK;
     HIP_TRY(hipSetDevice(h->device));
-    const size_t B = (size_t)h->B, row = 2 * B;
-    // ticks per chunk: the events of a chunk are read, and its command log copied out, when the chunk is done
-    int chunk = T < 4096 ? T : 4096;
-    if (cmds_out) {
-        const size_t fit = ((size_t)256 << 20) / (row * sizeof(float));
-        if ((size_t)chunk > fit) chunk = fit > 0 ? (int)fit : 1;
-        HIP_TRY(h->nav.dlog.reserve((size_t)chunk * row));
-    }
-    if (h->dcmd_each.cap() < row) {
-        if (h->dcmd_each) HIP_TRY(hipStreamSynchronize(h->stream));
-        HIP_TRY(h->dcmd_each.reserve(row));
-    }
-    const bool timed = h->nav.time_ticks;
-    while (h->nav.ev.size() < 2 + (timed ? 2 * (size_t)chunk : 0)) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreate(&e));
-        h->nav.ev.push_back(e);
-    }
+    const size_t row = 2 * (size_t)h->B;
+    // what a tick holds on the device: its row of the command log
+    const int chunk = slam_host::ticks_per_chunk(T, cmds_out ? 4.0 * (double)row : 0.0, slam_host::tick_log_budget());
+    if (cmds_out) TRY(grow(h, h->nav.dlog, (size_t)chunk * row));
     slam::NavParams p;
-    memset(&p, 0, sizeof(p));
-    p.x = h->dx; p.flags = h->dflags; p.path = h->nav.dpath;
-    p.P_each = h->nav.each ? h->nav.dP.get() : nullptr; p.P = h->nav.P; p.path_stride = h->nav.stride;
-    p.B = h->B; p.xstride = h->xstride; p.ukf = h->kind != SLAM_EKF_SLAM;
-    p.c = nav_consts(h->nav.cfg, h->cfg.d_max, h->cfg.th_max);
-    p.head = h->nav.dhead; p.finish_tick = h->nav.dfinish; p.integ = h->nav.dinteg; p.err_prev = h->nav.derrp;
-    p.cmd_out = h->dcmd_each;
-    h->nav.ctrl_ms = timed ? 0.0 : -1.0; h->nav.total_ms = 0.0;
-    hipEvent_t* const ev = h->nav.ev.data();
-    for (int t0 = 0; t0 < T; t0 += chunk) {
-        const int tc = T - t0 < chunk ? T - t0 : chunk;
-        HIP_TRY(hipEventRecord(ev[0], h->stream));
-        for (int t = 0; t < tc; ++t) {
-            p.tick = h->nav.tick;
+    TRY(nav_params(h, &p));
+    return run_chunked(
+        h, T, chunk, h->nav.time_ticks, h->nav.times, [](int, int) { return SLAM_OK; },
+        [&](int, int t, auto mark) -> int {
             p.cmd_log = cmds_out ? h->nav.dlog + (size_t)t * row : nullptr;
-            if (timed) HIP_TRY(hipEventRecord(ev[2 + 2 * t], h->stream));
-            HIP_TRY(slam::launch_nav_tick(p, h->esz == 4, h->stream));
-            if (timed) HIP_TRY(hipEventRecord(ev[3 + 2 * t], h->stream));
-            h->nav.tick += 1;
-            TRY(launch_step(h, kNoCmd, 1, nullptr, nullptr, 0, h->dcmd_each));
-        }
-        HIP_TRY(hipEventRecord(ev[1], h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        h->nav.total_ms += (double)ms;
-        for (int t = 0; timed && t < tc; ++t) {
-            HIP_TRY(hipEventElapsedTime(&ms, ev[2 + 2 * t], ev[3 + 2 * t]));
-            h->nav.ctrl_ms += (double)ms;
-        }
-        if (cmds_out) HIP_TRY(hipMemcpy(cmds_out + (size_t)t0 * row, h->nav.dlog, sizeof(float) * (size_t)tc * row, hipMemcpyDeviceToHost));
-    }
-    return SLAM_OK;
+            TRY(mark([&] { return nav_launch(h, p); }));
+            return launch_step(h, kNoCmd, 1, nullptr, nullptr, 0, h->dcmd_each);
+        },
+        [&](int t0, int tc) -> int {
+            if (cmds_out) HIP_TRY(hipMemcpy(cmds_out + (size_t)t0 * row, h->nav.dlog, sizeof(float) * (size_t)tc * row, hipMemcpyDeviceToHost));
+            return SLAM_OK;
+        });
 }
 
 int slam_nav_state(slam_handle* h, int32_t* remaining, int32_t* finish_tick, double* integ, double* err_prev) {
@@ -1988,11 +2060,7 @@ int slam_nav_set_timing(slam_handle* h, int per_tick) {
 }
 
 int slam_last_nav_work(slam_handle* h, double* controller_ms, double* total_ms) {
-    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
-    if (h->nav.total_ms < 0.0) return fail(SLAM_ERR_STATE, "slam_nav_run has not run on this handle");
-    if (controller_ms) *controller_ms = h->nav.ctrl_ms;
-    if (total_ms) *total_ms = h->nav.total_ms;
-    return SLAM_OK;
+    return last_work(h ? &h->nav.times : nullptr, "slam_nav_run", controller_ms, total_ms);
 }
 
 int slam_nav_tick_host(const slam_nav_config* cfg, double d_max, double th_max, const double* pts, int P, const float est[3], int frozen,
@@ -2076,10 +2144,10 @@ int slam_monitor_now(slam_handle* h, const slam_monitor_config* cfg, double rec[
     if (!has_map(h)) return fail(SLAM_ERR_STATE, "no true map, so no simulated truth to compare with: call slam_set_map (or slam_set_maps) first");
     HIP_TRY(hipSetDevice(h->device));
     const size_t B = (size_t)h->B;
-    HIP_TRY(h->mon.dpart.reserve((size_t)slam::monitor_blocks(h->B) * slam::kMonRecLen));
-    HIP_TRY(h->mon.drec.reserve(slam::kMonRecLen));
-    HIP_TRY(h->mon.dlog.reserve(3 * B));
-    HIP_TRY(h->mon.dflags.reserve(B));
+    TRY(grow(h, h->mon.dpart, (size_t)slam::monitor_blocks(h->B) * slam::kMonRecLen));
+    TRY(grow(h, h->mon.drec, slam::kMonRecLen));
+    TRY(grow(h, h->mon.dlog, 3 * B));
+    TRY(grow(h, h->mon.dflags, B));
     slam::MonitorParams p = monitor_params(h, c);
     p.err_pos = h->mon.dlog; p.err_yaw = h->mon.dlog + B; p.nees_pose = h->mon.dlog + 2 * B; p.flags = h->mon.dflags;
     p.rec = h->mon.drec;
@@ -2100,105 +2168,49 @@ int slam_monitor_run(slam_handle* h, const slam_monitor_config* cfg, int source,
     if (source != SLAM_MONITOR_SHARED && source != SLAM_MONITOR_EACH && source != SLAM_MONITOR_NAV) return fail(SLAM_ERR_ARG, "unknown command source %d", source);
     if (T < 0) return fail(SLAM_ERR_ARG, "T = %d is negative", T);
     if (source != SLAM_MONITOR_NAV && !cmds) return fail(SLAM_ERR_ARG, "cmds is NULL: the sources SHARED and EACH read the commands from it");
-    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
-    TRY(monitor_full_supported(h, c));
-    if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
-    if (!has_map(h)) return fail(SLAM_ERR_STATE, "slam_set_map has not been called");
-    if (source == SLAM_MONITOR_NAV && !h->nav.set) return fail(SLAM_ERR_STATE, "no path: call slam_nav_set_path or slam_nav_set_paths first");
-    if (h->shadow) return fail(SLAM_ERR_STATE, "slam_track_instance is on: the monitored run steps the batch once per tick and does not drive the shadow filter");
-    if (h->predicted) return fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev before slam_monitor_run");
-    TRY(flush_lazy(h));
+    if (h) TRY(monitor_full_supported(h, c));
+    TRY(run_enter(h, "slam_monitor_run", true, source == SLAM_MONITOR_NAV, false));
     if (T == 0) return SLAM_OK;
     HIP_TRY(hipSetDevice(h->device));
-    const size_t B = (size_t)h->B, row = 2 * B;
+    const size_t B = (size_t)h->B;
     double* const series[3] = {err_pos, err_yaw, nees_pose};
     int ns = 0;
     for (double* s : series) ns += s != nullptr;
-    // ticks per chunk: the events of a chunk are read, and its records and series copied out, when the chunk is done.  What a tick holds
-    // on the device - its rows of the series and, for EACH, of the commands - stays within SLAM_MONITOR_LOG_BYTES (one tick at least)
-    int chunk = T < 4096 ? T : 4096;
-    const double per_tick = 8.0 * (double)ns * (double)B + (source == SLAM_MONITOR_EACH ? 4.0 * (double)row : 0.0);
-    if (per_tick > 0.0) {
-        const char* env = getenv("SLAM_MONITOR_LOG_BYTES");
-        const double fit = (env ? atof(env) : 256.0 * 1024 * 1024) / per_tick;
-        if (fit < (double)chunk) chunk = fit >= 1.0 ? (int)fit : 1;
-    }
-    HIP_TRY(h->mon.dpart.reserve((size_t)slam::monitor_blocks(h->B) * slam::kMonRecLen));
-    HIP_TRY(h->mon.drec.reserve((size_t)chunk * slam::kMonRecLen));
-    if (ns) HIP_TRY(h->mon.dlog.reserve((size_t)ns * chunk * B));
-    if (source == SLAM_MONITOR_NAV && h->dcmd_each.cap() < row) {
-        if (h->dcmd_each) HIP_TRY(hipStreamSynchronize(h->stream));
-        HIP_TRY(h->dcmd_each.reserve(row));
-    }
-    const bool timed = h->nav.time_ticks;
-    while (h->mon.ev.size() < 2 + (timed ? 2 * (size_t)chunk : 0)) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreate(&e));
-        h->mon.ev.push_back(e);
-    }
-    slam::NavParams np;
-    memset(&np, 0, sizeof(np));
-    if (source == SLAM_MONITOR_NAV) {
-        np.x = h->dx; np.flags = h->dflags; np.path = h->nav.dpath;
-        np.P_each = h->nav.each ? h->nav.dP.get() : nullptr; np.P = h->nav.P; np.path_stride = h->nav.stride;
-        np.B = h->B; np.xstride = h->xstride; np.ukf = h->kind != SLAM_EKF_SLAM;
-        np.c = nav_consts(h->nav.cfg, h->cfg.d_max, h->cfg.th_max);
-        np.head = h->nav.dhead; np.finish_tick = h->nav.dfinish; np.integ = h->nav.dinteg; np.err_prev = h->nav.derrp;
-        np.cmd_out = h->dcmd_each;
-    }
+    TickCmds tcmd;
+    TRY(tcmd.init(h, source == SLAM_MONITOR_EACH ? TickCmds::kEach : source == SLAM_MONITOR_NAV ? TickCmds::kNav : TickCmds::kShared, cmds));
+    // what a tick holds on the device: its rows of the series and, for EACH, of the commands
+    const int chunk = slam_host::ticks_per_chunk(T, 8.0 * (double)ns * (double)B + tcmd.bytes_per_tick(h), slam_host::tick_log_budget());
+    TRY(grow(h, h->mon.dpart, (size_t)slam::monitor_blocks(h->B) * slam::kMonRecLen));
+    TRY(grow(h, h->mon.drec, (size_t)chunk * slam::kMonRecLen));
+    if (ns) TRY(grow(h, h->mon.dlog, (size_t)ns * chunk * B));
     slam::MonitorParams p = monitor_params(h, c);
-    h->mon.mon_ms = timed ? 0.0 : -1.0; h->mon.total_ms = 0.0;
-    hipEvent_t* const ev = h->mon.ev.data();
-    for (int t0 = 0; t0 < T; t0 += chunk) {
-        const int tc = T - t0 < chunk ? T - t0 : chunk;
-        if (source == SLAM_MONITOR_EACH) TRY(upload_cmds_each(h, cmds + (size_t)t0 * row, tc));
-        HIP_TRY(hipEventRecord(ev[0], h->stream));
-        for (int t = 0; t < tc; ++t) {
-            if (source == SLAM_MONITOR_NAV) {
-                np.tick = h->nav.tick;
-                HIP_TRY(slam::launch_nav_tick(np, h->esz == 4, h->stream));
-                h->nav.tick += 1;
-                TRY(launch_step(h, kNoCmd, 1, nullptr, nullptr, 0, h->dcmd_each));
-            } else if (source == SLAM_MONITOR_EACH) {
-                TRY(launch_step(h, kNoCmd, 1, nullptr, nullptr, 0, h->dcmd_each + (size_t)t * row));
-            } else {
-                TRY(launch_step(h, cmds + 2 * (size_t)(t0 + t), 1, nullptr, nullptr, 0));
-            }
+    return run_chunked(
+        h, T, chunk, h->nav.time_ticks, h->mon.times, [&](int t0, int tc) { return tcmd.upload(h, t0, tc); },
+        [&](int t0, int t, auto mark) -> int {
+            const float *cmd, *d_each;
+            TRY(tcmd.select(h, t0, t, &cmd, &d_each));
+            TRY(launch_step(h, cmd, 1, nullptr, nullptr, 0, d_each));
             double* slot = h->mon.dlog;
             p.err_pos = err_pos ? slot + (size_t)t * B : nullptr; if (err_pos) slot += (size_t)chunk * B;
             p.err_yaw = err_yaw ? slot + (size_t)t * B : nullptr; if (err_yaw) slot += (size_t)chunk * B;
             p.nees_pose = nees_pose ? slot + (size_t)t * B : nullptr;
             p.rec = h->mon.drec + (size_t)t * slam::kMonRecLen;
-            if (timed) HIP_TRY(hipEventRecord(ev[2 + 2 * t], h->stream));
-            TRY(monitor_launch(h, p, c.full_every > 0 && (t0 + t + 1) % c.full_every == 0));
-            if (timed) HIP_TRY(hipEventRecord(ev[3 + 2 * t], h->stream));
-        }
-        HIP_TRY(hipEventRecord(ev[1], h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        h->mon.total_ms += (double)ms;
-        for (int t = 0; timed && t < tc; ++t) {
-            HIP_TRY(hipEventElapsedTime(&ms, ev[2 + 2 * t], ev[3 + 2 * t]));
-            h->mon.mon_ms += (double)ms;
-        }
-        if (recs) HIP_TRY(hipMemcpy(recs + (size_t)t0 * slam::kMonRecLen, h->mon.drec, sizeof(double) * (size_t)tc * slam::kMonRecLen, hipMemcpyDeviceToHost));
-        const double* slot = h->mon.dlog;
-        for (double* s : series)
-            if (s) {
-                HIP_TRY(hipMemcpy(s + (size_t)t0 * B, slot, sizeof(double) * (size_t)tc * B, hipMemcpyDeviceToHost));
-                slot += (size_t)chunk * B;
-            }
-    }
-    return SLAM_OK;
+            return mark([&] { return monitor_launch(h, p, c.full_every > 0 && (t0 + t + 1) % c.full_every == 0); });
+        },
+        [&](int t0, int tc) -> int {
+            if (recs) HIP_TRY(hipMemcpy(recs + (size_t)t0 * slam::kMonRecLen, h->mon.drec, sizeof(double) * (size_t)tc * slam::kMonRecLen, hipMemcpyDeviceToHost));
+            const double* slot = h->mon.dlog;
+            for (double* s : series)
+                if (s) {
+                    HIP_TRY(hipMemcpy(s + (size_t)t0 * B, slot, sizeof(double) * (size_t)tc * B, hipMemcpyDeviceToHost));
+                    slot += (size_t)chunk * B;
+                }
+            return SLAM_OK;
+        });
 }
 
 int slam_last_monitor_work(slam_handle* h, double* monitor_ms, double* total_ms) {
-    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
-    if (h->mon.total_ms < 0.0) return fail(SLAM_ERR_STATE, "slam_monitor_run has not run on this handle");
-    if (monitor_ms) *monitor_ms = h->mon.mon_ms;
-    if (total_ms) *total_ms = h->mon.total_ms;
-    return SLAM_OK;
+    return last_work(h ? &h->mon.times : nullptr, "slam_monitor_run", monitor_ms, total_ms);
 }
 
 int slam_monitor_instance_host(int filter_kind, const double* x, const double* P3, const double truth[3], int32_t status, double* err_pos,
@@ -2239,9 +2251,9 @@ int innovation_supported(const slam_handle* h) {
 // the per-instance buffers of one evaluation; det: the detection slots are wanted
 int innovation_reserve(slam_handle* h, bool det) {
     const size_t B = (size_t)h->B;
-    HIP_TRY(h->inn.dval.reserve((1 + 12 + slam::kInnovRecLen) * B));
-    HIP_TRY(h->inn.dpart.reserve((size_t)slam::innovation_blocks(h->B) * slam::kInnovRecLen));
-    if (det) HIP_TRY(h->inn.ddet.reserve(B * slam::kInnovMaxDet * slam::kInnovDetLen));
+    TRY(grow(h, h->inn.dval, (1 + 12 + slam::kInnovRecLen) * B));
+    TRY(grow(h, h->inn.dpart, (size_t)slam::innovation_blocks(h->B) * slam::kInnovRecLen));
+    if (det) TRY(grow(h, h->inn.ddet, B * slam::kInnovMaxDet * slam::kInnovDetLen));
     return SLAM_OK;
 }
 
@@ -2258,29 +2270,41 @@ slam::InnovParams innovation_params(slam_handle* h, const slam_innovation_config
     return p;
 }
 
+// The outputs of one evaluation (slam_innovation*, slam_gate*): on the device they have fixed places in the handle's buffers.
+struct InnovOut { double *rec, *nis_sum, *post, *det; int32_t *n_upd, *flags, *n_new; };
+
+int innovation_outputs(slam_handle* h, bool det, InnovOut* d) {
+    const size_t B = (size_t)h->B;
+    TRY(innovation_reserve(h, det));
+    TRY(grow(h, h->inn.drec, slam::kInnovRecLen));
+    TRY(grow(h, h->inn.dint, 3 * B));
+    *d = {h->inn.drec, h->inn.dval, h->inn.dval + B, det ? h->inn.ddet.get() : nullptr, h->inn.dint, h->inn.dint + B, h->inn.dint + 2 * B};
+    return SLAM_OK;
+}
+
+// once the stream has run dry: the outputs the caller wants (non-NULL in `to`) from their device places
+int innovation_download(slam_handle* h, const InnovOut& d, const InnovOut& to) {
+    const size_t B = (size_t)h->B;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (to.rec) HIP_TRY(hipMemcpy(to.rec, d.rec, sizeof(double) * slam::kInnovRecLen, hipMemcpyDeviceToHost));
+    if (to.nis_sum) HIP_TRY(hipMemcpy(to.nis_sum, d.nis_sum, sizeof(double) * B, hipMemcpyDeviceToHost));
+    if (to.post) HIP_TRY(hipMemcpy(to.post, d.post, sizeof(double) * 12 * B, hipMemcpyDeviceToHost));
+    if (to.det) HIP_TRY(hipMemcpy(to.det, d.det, sizeof(double) * B * slam::kInnovMaxDet * slam::kInnovDetLen, hipMemcpyDeviceToHost));
+    if (to.n_upd) HIP_TRY(hipMemcpy(to.n_upd, d.n_upd, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+    if (to.flags) HIP_TRY(hipMemcpy(to.flags, d.flags, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+    if (to.n_new) HIP_TRY(hipMemcpy(to.n_new, d.n_new, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+    return SLAM_OK;
+}
+
 // slam_innovation / slam_innovation_dev once the message and the commands are on the device
 int innovation_now(slam_handle* h, const slam_innovation_config& c, const float cmd[2], const float* d_cmd_each, const float* d_meas,
-                   const int32_t* d_count, int k_stride, double* rec, double* nis_sum, int32_t* n_upd, int32_t* n_new, int32_t* flags, double* det,
-                   double* post) {
-    const size_t B = (size_t)h->B;
-    TRY(innovation_reserve(h, det != nullptr));
-    HIP_TRY(h->inn.drec.reserve(slam::kInnovRecLen));
-    HIP_TRY(h->inn.dint.reserve(3 * B));
+                   const int32_t* d_count, int k_stride, const InnovOut& to) {
+    InnovOut d;
+    TRY(innovation_outputs(h, to.det != nullptr, &d));
     slam::InnovParams p = innovation_params(h, c, cmd, 0, d_meas, d_count, k_stride, d_cmd_each);
-    p.nis_sum = h->inn.dval; p.post = h->inn.dval + B;
-    p.n_upd = h->inn.dint; p.flags = h->inn.dint + B; p.n_new = h->inn.dint + 2 * B;
-    p.det = det ? h->inn.ddet.get() : nullptr;
-    p.rec = h->inn.drec;
+    p.nis_sum = d.nis_sum; p.post = d.post; p.n_upd = d.n_upd; p.flags = d.flags; p.n_new = d.n_new; p.det = d.det; p.rec = d.rec;
     HIP_TRY(slam::launch_innovation(p, h->esz == 4, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (rec) HIP_TRY(hipMemcpy(rec, p.rec, sizeof(double) * slam::kInnovRecLen, hipMemcpyDeviceToHost));
-    if (nis_sum) HIP_TRY(hipMemcpy(nis_sum, p.nis_sum, sizeof(double) * B, hipMemcpyDeviceToHost));
-    if (post) HIP_TRY(hipMemcpy(post, p.post, sizeof(double) * 12 * B, hipMemcpyDeviceToHost));
-    if (det) HIP_TRY(hipMemcpy(det, p.det, sizeof(double) * B * slam::kInnovMaxDet * slam::kInnovDetLen, hipMemcpyDeviceToHost));
-    if (n_upd) HIP_TRY(hipMemcpy(n_upd, p.n_upd, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
-    if (flags) HIP_TRY(hipMemcpy(flags, p.flags, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
-    if (n_new) HIP_TRY(hipMemcpy(n_new, p.n_new, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
-    return SLAM_OK;
+    return innovation_download(h, d, to);
 }
 
 // the checks slam_innovation and slam_innovation_dev share; the queued timesteps run first
@@ -2300,11 +2324,18 @@ int innovation_enter(slam_handle* h, const slam_innovation_config* cfg, const fl
 
 // n floats from the host into the handle's staging buffer for per-instance commands, in stream order
 int innovation_upload_cmds(slam_handle* h, const float* cmds, size_t n) {
-    if (h->inn.dcmd.cap() < n) {
-        if (h->inn.dcmd) HIP_TRY(hipStreamSynchronize(h->stream));
-        HIP_TRY(h->inn.dcmd.reserve(n));
-    }
+    TRY(grow(h, h->inn.dcmd, n));
     HIP_TRY(hipMemcpyAsync(h->inn.dcmd, cmds, sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
+    return SLAM_OK;
+}
+
+// the host messages of `ticks` ticks into the handle's staging buffers ([ticks][B][k_stride][3] and [ticks][B]), in stream order
+int upload_messages(slam_handle* h, const float* meas, const int32_t* count, int k_stride, size_t ticks) {
+    const size_t nc = ticks * h->B, nm = 3 * (size_t)k_stride * nc;
+    TRY(grow(h, h->inn.dmeas, nm));
+    TRY(grow(h, h->inn.dcount, nc));
+    HIP_TRY(hipMemcpyAsync(h->inn.dmeas, meas, sizeof(float) * nm, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->inn.dcount, count, sizeof(int32_t) * nc, hipMemcpyHostToDevice, h->stream));
     return SLAM_OK;
 }
 
@@ -2323,16 +2354,10 @@ int slam_innovation(slam_handle* h, const slam_innovation_config* cfg, const flo
                     int k_stride, double rec[16], double* nis_sum, int32_t* n_upd, int32_t* n_new, int32_t* flags, double* det, double* post) {
     slam_innovation_config c;
     TRY(innovation_enter(h, cfg, cmds, meas, count, k_stride, &c));
-    const size_t B = (size_t)h->B, nm = 3 * (size_t)k_stride * B;
-    if (h->inn.dmeas.cap() < nm || h->inn.dcount.cap() < B) {
-        if (h->inn.dmeas) HIP_TRY(hipStreamSynchronize(h->stream));
-        HIP_TRY(h->inn.dmeas.reserve(nm)); HIP_TRY(h->inn.dcount.reserve(B));
-    }
-    HIP_TRY(hipMemcpyAsync(h->inn.dmeas, meas, sizeof(float) * nm, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->inn.dcount, count, sizeof(int32_t) * B, hipMemcpyHostToDevice, h->stream));
-    if (cmd_each) TRY(innovation_upload_cmds(h, cmds, 2 * B));
-    return innovation_now(h, c, cmd_each ? kNoCmd : cmds, cmd_each ? h->inn.dcmd.get() : nullptr, h->inn.dmeas, h->inn.dcount, k_stride, rec, nis_sum,
-                          n_upd, n_new, flags, det, post);
+    TRY(upload_messages(h, meas, count, k_stride, 1));
+    if (cmd_each) TRY(innovation_upload_cmds(h, cmds, 2 * (size_t)h->B));
+    return innovation_now(h, c, cmd_each ? kNoCmd : cmds, cmd_each ? h->inn.dcmd.get() : nullptr, h->inn.dmeas, h->inn.dcount, k_stride,
+                          {rec, nis_sum, post, det, n_upd, flags, n_new});
 }
 
 int slam_innovation_dev(slam_handle* h, const slam_innovation_config* cfg, const float* cmds, int cmd_each, const float* d_meas,
@@ -2340,8 +2365,8 @@ int slam_innovation_dev(slam_handle* h, const slam_innovation_config* cfg, const
                         double* det, double* post) {
     slam_innovation_config c;
     TRY(innovation_enter(h, cfg, cmds, d_meas, d_count, k_stride, &c));
-    return innovation_now(h, c, cmd_each ? kNoCmd : cmds, cmd_each ? cmds : nullptr, d_meas, d_count, k_stride, rec, nis_sum, n_upd, n_new, flags, det,
-                          post);
+    return innovation_now(h, c, cmd_each ? kNoCmd : cmds, cmd_each ? cmds : nullptr, d_meas, d_count, k_stride,
+                          {rec, nis_sum, post, det, n_upd, flags, n_new});
 }
 
 int slam_innovation_run(slam_handle* h, const slam_innovation_config* cfg, int source, const float* cmds, const float* meas, const int32_t* count,
@@ -2355,116 +2380,52 @@ int slam_innovation_run(slam_handle* h, const slam_innovation_config* cfg, int s
     const bool log = source == SLAM_INNOVATION_LOG;
     if (log && (!meas || !count)) return fail(SLAM_ERR_ARG, "meas or meas_count is NULL: the source LOG reads the messages from them");
     if (log && k_stride <= 0) return fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
-    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
-    TRY(innovation_supported(h));
-    if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
-    if (!log && !has_map(h)) return fail(SLAM_ERR_STATE, "slam_set_map has not been called: the sources SHARED, EACH and NAV run the simulator");
-    if (source == SLAM_INNOVATION_NAV && !h->nav.set) return fail(SLAM_ERR_STATE, "no path: call slam_nav_set_path or slam_nav_set_paths first");
-    if (h->shadow) return fail(SLAM_ERR_STATE, "slam_track_instance is on: the run steps the batch once per tick and does not drive the shadow filter");
-    if (h->predicted) return fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev before slam_innovation_run");
-    TRY(flush_lazy(h));
+    TRY(run_enter(h, "slam_innovation_run", !log, source == SLAM_INNOVATION_NAV, true));
     if (T == 0) return SLAM_OK;
     HIP_TRY(hipSetDevice(h->device));
-    const size_t B = (size_t)h->B, row = 2 * B, mrow = 3 * (size_t)k_stride * B;
-    // ticks per chunk, as slam_monitor_run: what a tick holds on the device - its rows of the series, of the commands (EACH) and of the
-    // messages (LOG) - stays within SLAM_MONITOR_LOG_BYTES (one tick at least)
-    int chunk = T < 4096 ? T : 4096;
-    const double per_tick = 8.0 * (nis_sum ? (double)B : 0.0) + 4.0 * (double)B * ((n_upd ? 1 : 0) + (flags ? 1 : 0)) +
-                            (source == SLAM_INNOVATION_EACH ? 4.0 * (double)row : 0.0) + (log ? 4.0 * (double)mrow + 4.0 * (double)B : 0.0);
-    if (per_tick > 0.0) {
-        const char* env = getenv("SLAM_MONITOR_LOG_BYTES");
-        const double fit = (env ? atof(env) : 256.0 * 1024 * 1024) / per_tick;
-        if (fit < (double)chunk) chunk = fit >= 1.0 ? (int)fit : 1;
-    }
+    const size_t B = (size_t)h->B, mrow = 3 * (size_t)k_stride * B;
+    TickCmds tcmd;   // (LOG: the commands are shared ones)
+    TRY(tcmd.init(h, source == SLAM_INNOVATION_EACH ? TickCmds::kEach : source == SLAM_INNOVATION_NAV ? TickCmds::kNav : TickCmds::kShared, cmds));
+    // what a tick holds on the device: its rows of the series, of the commands (EACH) and of the messages (LOG)
+    const double per_tick = 8.0 * (nis_sum ? (double)B : 0.0) + 4.0 * (double)B * ((n_upd ? 1 : 0) + (flags ? 1 : 0)) + tcmd.bytes_per_tick(h) +
+                            (log ? 4.0 * (double)mrow + 4.0 * (double)B : 0.0);
+    const int chunk = slam_host::ticks_per_chunk(T, per_tick, slam_host::tick_log_budget());
     TRY(innovation_reserve(h, false));
-    HIP_TRY(h->inn.drec.reserve((size_t)chunk * slam::kInnovRecLen));
-    if (nis_sum) HIP_TRY(h->inn.dlog.reserve((size_t)chunk * B));
-    HIP_TRY(h->inn.dint.reserve(2 * (size_t)chunk * B));
-    if (source == SLAM_INNOVATION_NAV && h->dcmd_each.cap() < row) {
-        if (h->dcmd_each) HIP_TRY(hipStreamSynchronize(h->stream));
-        HIP_TRY(h->dcmd_each.reserve(row));
-    }
-    if (log && (h->inn.dmeas.cap() < mrow * chunk || h->inn.dcount.cap() < B * chunk)) {
-        if (h->inn.dmeas) HIP_TRY(hipStreamSynchronize(h->stream));
-        HIP_TRY(h->inn.dmeas.reserve(mrow * chunk)); HIP_TRY(h->inn.dcount.reserve(B * chunk));
-    }
-    const bool timed = h->nav.time_ticks;
-    while (h->inn.ev.size() < 2 + (timed ? 2 * (size_t)chunk : 0)) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreate(&e));
-        h->inn.ev.push_back(e);
-    }
-    slam::NavParams np;
-    memset(&np, 0, sizeof(np));
-    if (source == SLAM_INNOVATION_NAV) {
-        np.x = h->dx; np.flags = h->dflags; np.path = h->nav.dpath;
-        np.P_each = h->nav.each ? h->nav.dP.get() : nullptr; np.P = h->nav.P; np.path_stride = h->nav.stride;
-        np.B = h->B; np.xstride = h->xstride; np.ukf = 0;
-        np.c = nav_consts(h->nav.cfg, h->cfg.d_max, h->cfg.th_max);
-        np.head = h->nav.dhead; np.finish_tick = h->nav.dfinish; np.integ = h->nav.dinteg; np.err_prev = h->nav.derrp;
-        np.cmd_out = h->dcmd_each;
-    }
-    h->inn.inn_ms = timed ? 0.0 : -1.0; h->inn.total_ms = 0.0;
-    hipEvent_t* const ev = h->inn.ev.data();
+    TRY(grow(h, h->inn.drec, (size_t)chunk * slam::kInnovRecLen));
+    if (nis_sum) TRY(grow(h, h->inn.dlog, (size_t)chunk * B));
+    TRY(grow(h, h->inn.dint, 2 * (size_t)chunk * B));
     int32_t* const d_upd = h->inn.dint;
     int32_t* const d_flags = h->inn.dint + (size_t)chunk * B;
-    for (int t0 = 0; t0 < T; t0 += chunk) {
-        const int tc = T - t0 < chunk ? T - t0 : chunk;
-        if (source == SLAM_INNOVATION_EACH) TRY(upload_cmds_each(h, cmds + (size_t)t0 * row, tc));
-        if (log) {
-            HIP_TRY(hipMemcpyAsync(h->inn.dmeas, meas + (size_t)t0 * mrow, sizeof(float) * mrow * tc, hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(hipMemcpyAsync(h->inn.dcount, count + (size_t)t0 * B, sizeof(int32_t) * B * tc, hipMemcpyHostToDevice, h->stream));
-        }
-        HIP_TRY(hipEventRecord(ev[0], h->stream));
-        for (int t = 0; t < tc; ++t) {
-            const float* cmd = kNoCmd;
-            const float* d_each = nullptr;
-            const float* d_meas = nullptr;
-            const int32_t* d_count = nullptr;
-            if (source == SLAM_INNOVATION_NAV) {
-                np.tick = h->nav.tick;
-                HIP_TRY(slam::launch_nav_tick(np, h->esz == 4, h->stream));
-                h->nav.tick += 1;
-                d_each = h->dcmd_each;
-            } else if (source == SLAM_INNOVATION_EACH) {
-                d_each = h->dcmd_each + (size_t)t * row;
-            } else {
-                cmd = cmds + 2 * (size_t)(t0 + t);
-            }
-            if (log) { d_meas = h->inn.dmeas + (size_t)t * mrow; d_count = h->inn.dcount + (size_t)t * B; }
+    return run_chunked(
+        h, T, chunk, h->nav.time_ticks, h->inn.times,
+        [&](int t0, int tc) -> int {
+            TRY(tcmd.upload(h, t0, tc));
+            return log ? upload_messages(h, meas + (size_t)t0 * mrow, count + (size_t)t0 * B, k_stride, (size_t)tc) : SLAM_OK;
+        },
+        [&](int t0, int t, auto mark) -> int {
+            const float *cmd, *d_each;
+            TRY(tcmd.select(h, t0, t, &cmd, &d_each));
+            const float* const d_meas = log ? h->inn.dmeas + (size_t)t * mrow : nullptr;
+            const int32_t* const d_count = log ? h->inn.dcount + (size_t)t * B : nullptr;
             slam::InnovParams p = innovation_params(h, c, cmd, log ? 0 : 1, d_meas, d_count, log ? k_stride : 0, d_each);
             p.nis_sum = nis_sum ? h->inn.dlog + (size_t)t * B : nullptr;
             p.n_upd = n_upd ? d_upd + (size_t)t * B : nullptr;
             p.flags = flags ? d_flags + (size_t)t * B : nullptr;
             p.rec = h->inn.drec + (size_t)t * slam::kInnovRecLen;
-            if (timed) HIP_TRY(hipEventRecord(ev[2 + 2 * t], h->stream));
-            HIP_TRY(slam::launch_innovation(p, h->esz == 4, h->stream));
-            if (timed) HIP_TRY(hipEventRecord(ev[3 + 2 * t], h->stream));
-            TRY(launch_step(h, cmd, log ? 0 : 1, d_meas, d_count, log ? k_stride : 0, d_each));
-        }
-        HIP_TRY(hipEventRecord(ev[1], h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        h->inn.total_ms += (double)ms;
-        for (int t = 0; timed && t < tc; ++t) {
-            HIP_TRY(hipEventElapsedTime(&ms, ev[2 + 2 * t], ev[3 + 2 * t]));
-            h->inn.inn_ms += (double)ms;
-        }
-        if (recs) HIP_TRY(hipMemcpy(recs + (size_t)t0 * slam::kInnovRecLen, h->inn.drec, sizeof(double) * (size_t)tc * slam::kInnovRecLen, hipMemcpyDeviceToHost));
-        if (nis_sum) HIP_TRY(hipMemcpy(nis_sum + (size_t)t0 * B, h->inn.dlog, sizeof(double) * (size_t)tc * B, hipMemcpyDeviceToHost));
-        if (n_upd) HIP_TRY(hipMemcpy(n_upd + (size_t)t0 * B, d_upd, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
-        if (flags) HIP_TRY(hipMemcpy(flags + (size_t)t0 * B, d_flags, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
-    }
-    return SLAM_OK;
+            TRY(mark([&]() -> int { HIP_TRY(slam::launch_innovation(p, h->esz == 4, h->stream)); return SLAM_OK; }));
+            return launch_step(h, cmd, log ? 0 : 1, d_meas, d_count, log ? k_stride : 0, d_each);
+        },
+        [&](int t0, int tc) -> int {
+            if (recs) HIP_TRY(hipMemcpy(recs + (size_t)t0 * slam::kInnovRecLen, h->inn.drec, sizeof(double) * (size_t)tc * slam::kInnovRecLen, hipMemcpyDeviceToHost));
+            if (nis_sum) HIP_TRY(hipMemcpy(nis_sum + (size_t)t0 * B, h->inn.dlog, sizeof(double) * (size_t)tc * B, hipMemcpyDeviceToHost));
+            if (n_upd) HIP_TRY(hipMemcpy(n_upd + (size_t)t0 * B, d_upd, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
+            if (flags) HIP_TRY(hipMemcpy(flags + (size_t)t0 * B, d_flags, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
+            return SLAM_OK;
+        });
 }
 
 int slam_last_innovation_work(slam_handle* h, double* innovation_ms, double* total_ms) {
-    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
-    if (h->inn.total_ms < 0.0) return fail(SLAM_ERR_STATE, "slam_innovation_run has not run on this handle");
-    if (innovation_ms) *innovation_ms = h->inn.inn_ms;
-    if (total_ms) *total_ms = h->inn.total_ms;
-    return SLAM_OK;
+    return last_work(h ? &h->inn.times : nullptr, "slam_innovation_run", innovation_ms, total_ms);
 }
 
 int slam_innovation_instance_host(const double* x, const double* P, const int32_t* ids, int M, int L_max, int32_t status, const float cmd[2],
@@ -2510,15 +2471,6 @@ int gate_config(const slam_gate_config* cfg, slam_gate_config* out) {
     return SLAM_OK;
 }
 
-// room for n elements in a buffer that launches in flight may still use: they finish before it is replaced
-template <class T>
-int gate_grow(slam_handle* h, DevBuf<T>& buf, size_t n) {
-    if (buf.cap() >= n) return SLAM_OK;
-    if (buf) HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(buf.reserve(n));
-    return SLAM_OK;
-}
-
 bool gate_overlap(const void* a, size_t na, const void* b, size_t nb) {
     const char* const pa = (const char*)a; const char* const pb = (const char*)b;
     return pa < pb + nb && pb < pa + na;
@@ -2559,50 +2511,28 @@ int gate_launch(slam_handle* h, const slam_gate_config& c, const float cmd[2], c
 
 // slam_gate / slam_gate_dev once the message and the commands are on the device; d_meas_out / d_count_out: where the filtered message goes
 int gate_now(slam_handle* h, const slam_gate_config& c, const float cmd[2], const float* d_cmd_each, const float* d_meas, const int32_t* d_count,
-             int k_stride, float* d_meas_out, int32_t* d_count_out, double* rec, double* nis_sum, int32_t* n_upd, int32_t* n_new, int32_t* flags,
-             double* det, double* post, int32_t* n_rej, int32_t* verdict) {
+             int k_stride, float* d_meas_out, int32_t* d_count_out, const InnovOut& to, int32_t* n_rej, int32_t* verdict) {
     const size_t B = (size_t)h->B;
-    TRY(innovation_reserve(h, det != nullptr));
-    TRY(gate_grow(h, h->inn.drec, slam::kInnovRecLen));
-    TRY(gate_grow(h, h->inn.dint, 3 * B));
-    TRY(gate_grow(h, h->gate.drej, B));
-    if (verdict) TRY(gate_grow(h, h->gate.dverdict, B * slam::kInnovMaxDet));
-    double* const d_nis = h->inn.dval; double* const d_post = h->inn.dval + B;
-    int32_t* const d_upd = h->inn.dint; int32_t* const d_fl = h->inn.dint + B; int32_t* const d_new = h->inn.dint + 2 * B;
-    TRY(gate_launch(h, c, cmd, d_cmd_each, d_meas, d_count, k_stride, d_meas_out, d_count_out, h->inn.drec, d_nis, d_post,
-                    det ? h->inn.ddet.get() : nullptr, d_upd, d_fl, d_new, h->gate.drej, verdict ? h->gate.dverdict.get() : nullptr));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (rec) HIP_TRY(hipMemcpy(rec, h->inn.drec, sizeof(double) * slam::kInnovRecLen, hipMemcpyDeviceToHost));
-    if (nis_sum) HIP_TRY(hipMemcpy(nis_sum, d_nis, sizeof(double) * B, hipMemcpyDeviceToHost));
-    if (post) HIP_TRY(hipMemcpy(post, d_post, sizeof(double) * 12 * B, hipMemcpyDeviceToHost));
-    if (det) HIP_TRY(hipMemcpy(det, h->inn.ddet, sizeof(double) * B * slam::kInnovMaxDet * slam::kInnovDetLen, hipMemcpyDeviceToHost));
-    if (n_upd) HIP_TRY(hipMemcpy(n_upd, d_upd, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
-    if (flags) HIP_TRY(hipMemcpy(flags, d_fl, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
-    if (n_new) HIP_TRY(hipMemcpy(n_new, d_new, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+    InnovOut d;
+    TRY(innovation_outputs(h, to.det != nullptr, &d));
+    TRY(grow(h, h->gate.drej, B));
+    if (verdict) TRY(grow(h, h->gate.dverdict, B * slam::kInnovMaxDet));
+    TRY(gate_launch(h, c, cmd, d_cmd_each, d_meas, d_count, k_stride, d_meas_out, d_count_out, d.rec, d.nis_sum, d.post, d.det, d.n_upd, d.flags,
+                    d.n_new, h->gate.drej, verdict ? h->gate.dverdict.get() : nullptr));
+    TRY(innovation_download(h, d, to));
     if (n_rej) HIP_TRY(hipMemcpy(n_rej, h->gate.drej, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
     if (verdict) HIP_TRY(hipMemcpy(verdict, h->gate.dverdict, sizeof(int32_t) * B * slam::kInnovMaxDet, hipMemcpyDeviceToHost));
-    return SLAM_OK;
-}
-
-// the host message of one call into the handle's staging buffers, in stream order
-int gate_upload_message(slam_handle* h, const float* meas, const int32_t* count, int k_stride) {
-    const size_t B = (size_t)h->B, nm = 3 * (size_t)k_stride * B;
-    TRY(gate_grow(h, h->inn.dmeas, nm));
-    TRY(gate_grow(h, h->inn.dcount, B));
-    HIP_TRY(hipMemcpyAsync(h->inn.dmeas, meas, sizeof(float) * nm, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->inn.dcount, count, sizeof(int32_t) * B, hipMemcpyHostToDevice, h->stream));
     return SLAM_OK;
 }
 
 // the filtered message of one tick, the records of `ticks` ticks and the per-instance contributions
 int gate_reserve_step(slam_handle* h, int k_stride, size_t ticks) {
     const size_t B = (size_t)h->B;
-    TRY(gate_grow(h, h->gate.dmeas, 3 * (size_t)k_stride * B));
-    TRY(gate_grow(h, h->gate.dcount, B));
-    TRY(gate_grow(h, h->gate.drej, ticks * B));
-    TRY(gate_grow(h, h->inn.dval, (1 + 12 + slam::kInnovRecLen) * B));
-    TRY(gate_grow(h, h->inn.dpart, (size_t)slam::innovation_blocks(h->B) * slam::kInnovRecLen));
-    TRY(gate_grow(h, h->inn.drec, ticks * slam::kInnovRecLen));
+    TRY(grow(h, h->gate.dmeas, 3 * (size_t)k_stride * B));
+    TRY(grow(h, h->gate.dcount, B));
+    TRY(grow(h, h->gate.drej, ticks * B));
+    TRY(innovation_reserve(h, false));
+    TRY(grow(h, h->inn.drec, ticks * slam::kInnovRecLen));
     return SLAM_OK;
 }
 
@@ -2632,7 +2562,7 @@ int step_gated_host(slam_handle* h, const slam_gate_config* cfg, const float* cm
     slam_gate_config c;
     TRY(gate_enter(h, cfg, cmds, meas, count, k_stride, nullptr, nullptr, false, &c));
     TRY(gate_step_state(h, "a gated step"));
-    TRY(gate_upload_message(h, meas, count, k_stride));
+    TRY(upload_messages(h, meas, count, k_stride, 1));
     if (cmd_each) TRY(innovation_upload_cmds(h, cmds, 2 * (size_t)h->B));
     return step_gated_now(h, c, cmd_each ? kNoCmd : cmds, cmd_each ? h->inn.dcmd.get() : nullptr, h->inn.dmeas, h->inn.dcount, k_stride, rec, n_rej);
 }
@@ -2663,14 +2593,14 @@ int slam_gate(slam_handle* h, const slam_gate_config* cfg, const float* cmds, in
     slam_gate_config c;
     TRY(gate_enter(h, cfg, cmds, meas, count, k_stride, meas_out, count_out, false, &c));
     const size_t B = (size_t)h->B, nm = 3 * (size_t)k_stride * B;
-    TRY(gate_upload_message(h, meas, count, k_stride));
+    TRY(upload_messages(h, meas, count, k_stride, 1));
     if (cmd_each) TRY(innovation_upload_cmds(h, cmds, 2 * B));
-    TRY(gate_grow(h, h->gate.dmeas, nm));
-    TRY(gate_grow(h, h->gate.dcount, B));
+    TRY(grow(h, h->gate.dmeas, nm));
+    TRY(grow(h, h->gate.dcount, B));
     // (slots the kernel does not write keep what the caller gave: the output row starts as the input row)
     HIP_TRY(hipMemcpyAsync(h->gate.dmeas, h->inn.dmeas, sizeof(float) * nm, hipMemcpyDeviceToDevice, h->stream));
     TRY(gate_now(h, c, cmd_each ? kNoCmd : cmds, cmd_each ? h->inn.dcmd.get() : nullptr, h->inn.dmeas, h->inn.dcount, k_stride, h->gate.dmeas,
-                 h->gate.dcount, rec, nis_sum, n_upd, n_new, flags, det, post, n_rej, verdict));
+                 h->gate.dcount, {rec, nis_sum, post, det, n_upd, flags, n_new}, n_rej, verdict));
     if (meas_out) HIP_TRY(hipMemcpy(meas_out, h->gate.dmeas, sizeof(float) * nm, hipMemcpyDeviceToHost));
     if (count_out) HIP_TRY(hipMemcpy(count_out, h->gate.dcount, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
     return SLAM_OK;
@@ -2685,8 +2615,8 @@ int slam_gate_dev(slam_handle* h, const slam_gate_config* cfg, const float* cmds
     if ((d_meas_out != d_meas && gate_overlap(d_meas_out, bm, d_meas, bm)) || (d_count_out != d_count && gate_overlap(d_count_out, bc, d_count, bc)) ||
         gate_overlap(d_meas_out, bm, d_count, bc) || gate_overlap(d_count_out, bc, d_meas, bm) || gate_overlap(d_meas_out, bm, d_count_out, bc))
         return fail(SLAM_ERR_ARG, "the output message overlaps the input (only d_meas_out == d_meas with d_count_out == d_count is allowed) or itself");
-    return gate_now(h, c, cmd_each ? kNoCmd : cmds, cmd_each ? cmds : nullptr, d_meas, d_count, k_stride, d_meas_out, d_count_out, rec, nis_sum, n_upd,
-                    n_new, flags, det, post, n_rej, verdict);
+    return gate_now(h, c, cmd_each ? kNoCmd : cmds, cmd_each ? cmds : nullptr, d_meas, d_count, k_stride, d_meas_out, d_count_out,
+                    {rec, nis_sum, post, det, n_upd, flags, n_new}, n_rej, verdict);
 }
 
 int slam_step_gated(slam_handle* h, const slam_gate_config* cfg, const float cmd[2], const float* meas, const int32_t* count, int k_stride,
@@ -2717,80 +2647,50 @@ int slam_gate_run(slam_handle* h, const slam_gate_config* cfg, const float* cmds
     if (!cmds) return fail(SLAM_ERR_ARG, "cmds is NULL");
     if (!meas || !count) return fail(SLAM_ERR_ARG, "meas or meas_count is NULL");
     if (k_stride <= 0) return fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
-    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
-    TRY(innovation_supported(h));
-    if (!h->inited) return fail(SLAM_ERR_STATE, "slam_init has not been called");
-    TRY(gate_step_state(h, "slam_gate_run"));
-    TRY(flush_lazy(h));
+    TRY(run_enter(h, "slam_gate_run", false, false, true));
     if (T == 0) return SLAM_OK;
     HIP_TRY(hipSetDevice(h->device));
-    const size_t B = (size_t)h->B, row = 2 * B, mrow = 3 * (size_t)k_stride * B;
-    // ticks per chunk, as slam_innovation_run: the rows of the series, of the commands (cmd_each) and of the messages of a chunk stay
-    // within SLAM_MONITOR_LOG_BYTES (one tick at least)
-    int chunk = T < 4096 ? T : 4096;
-    {
-        const double per_tick = 8.0 * (nis_sum ? (double)B : 0.0) + 4.0 * (double)B * ((n_upd ? 1 : 0) + (flags ? 1 : 0) + (n_rej ? 1 : 0)) +
-                                (cmd_each ? 4.0 * (double)row : 0.0) + 4.0 * (double)mrow + 4.0 * (double)B;
-        const char* env = getenv("SLAM_MONITOR_LOG_BYTES");
-        const double fit = (env ? atof(env) : 256.0 * 1024 * 1024) / per_tick;
-        if (fit < (double)chunk) chunk = fit >= 1.0 ? (int)fit : 1;
-    }
+    const size_t B = (size_t)h->B, mrow = 3 * (size_t)k_stride * B;
+    TickCmds tcmd;
+    TRY(tcmd.init(h, cmd_each ? TickCmds::kEach : TickCmds::kShared, cmds));
+    // what a tick holds on the device: its rows of the series, of the commands (cmd_each) and of the messages
+    const double per_tick = 8.0 * (nis_sum ? (double)B : 0.0) + 4.0 * (double)B * ((n_upd ? 1 : 0) + (flags ? 1 : 0) + (n_rej ? 1 : 0)) +
+                            tcmd.bytes_per_tick(h) + 4.0 * (double)mrow + 4.0 * (double)B;
+    const int chunk = slam_host::ticks_per_chunk(T, per_tick, slam_host::tick_log_budget());
     TRY(gate_reserve_step(h, k_stride, (size_t)chunk));
-    if (nis_sum) TRY(gate_grow(h, h->inn.dlog, (size_t)chunk * B));
-    TRY(gate_grow(h, h->inn.dint, 2 * (size_t)chunk * B));
-    TRY(gate_grow(h, h->inn.dmeas, mrow * chunk));
-    TRY(gate_grow(h, h->inn.dcount, B * chunk));
-    const bool timed = h->nav.time_ticks;
-    while (h->inn.ev.size() < 2 + (timed ? 2 * (size_t)chunk : 0)) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreate(&e));
-        h->inn.ev.push_back(e);
-    }
-    h->gate.gate_ms = timed ? 0.0 : -1.0; h->gate.total_ms = 0.0;
-    hipEvent_t* const ev = h->inn.ev.data();
+    if (nis_sum) TRY(grow(h, h->inn.dlog, (size_t)chunk * B));
+    TRY(grow(h, h->inn.dint, 2 * (size_t)chunk * B));
     int32_t* const d_upd = h->inn.dint;
     int32_t* const d_flags = h->inn.dint + (size_t)chunk * B;
-    for (int t0 = 0; t0 < T; t0 += chunk) {
-        const int tc = T - t0 < chunk ? T - t0 : chunk;
-        if (cmd_each) TRY(upload_cmds_each(h, cmds + (size_t)t0 * row, tc));
-        HIP_TRY(hipMemcpyAsync(h->inn.dmeas, meas + (size_t)t0 * mrow, sizeof(float) * mrow * tc, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->inn.dcount, count + (size_t)t0 * B, sizeof(int32_t) * B * tc, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipEventRecord(ev[0], h->stream));
-        for (int t = 0; t < tc; ++t) {
-            const float* const cmd = cmd_each ? kNoCmd : cmds + 2 * (size_t)(t0 + t);
-            const float* const d_each = cmd_each ? h->dcmd_each + (size_t)t * row : nullptr;
-            if (timed) HIP_TRY(hipEventRecord(ev[2 + 2 * t], h->stream));
-            TRY(gate_launch(h, c, cmd, d_each, h->inn.dmeas + (size_t)t * mrow, h->inn.dcount + (size_t)t * B, k_stride, h->gate.dmeas, h->gate.dcount,
-                            h->inn.drec + (size_t)t * slam::kInnovRecLen, nis_sum ? h->inn.dlog + (size_t)t * B : nullptr, nullptr, nullptr,
-                            n_upd ? d_upd + (size_t)t * B : nullptr, flags ? d_flags + (size_t)t * B : nullptr, nullptr,
-                            h->gate.drej + (size_t)t * B, nullptr));
-            if (timed) HIP_TRY(hipEventRecord(ev[3 + 2 * t], h->stream));
-            TRY(launch_step(h, cmd, 0, h->gate.dmeas, h->gate.dcount, k_stride, d_each));
-        }
-        HIP_TRY(hipEventRecord(ev[1], h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        h->gate.total_ms += (double)ms;
-        for (int t = 0; timed && t < tc; ++t) {
-            HIP_TRY(hipEventElapsedTime(&ms, ev[2 + 2 * t], ev[3 + 2 * t]));
-            h->gate.gate_ms += (double)ms;
-        }
-        if (recs) HIP_TRY(hipMemcpy(recs + (size_t)t0 * slam::kInnovRecLen, h->inn.drec, sizeof(double) * (size_t)tc * slam::kInnovRecLen, hipMemcpyDeviceToHost));
-        if (nis_sum) HIP_TRY(hipMemcpy(nis_sum + (size_t)t0 * B, h->inn.dlog, sizeof(double) * (size_t)tc * B, hipMemcpyDeviceToHost));
-        if (n_upd) HIP_TRY(hipMemcpy(n_upd + (size_t)t0 * B, d_upd, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
-        if (flags) HIP_TRY(hipMemcpy(flags + (size_t)t0 * B, d_flags, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
-        if (n_rej) HIP_TRY(hipMemcpy(n_rej + (size_t)t0 * B, h->gate.drej, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
-    }
-    return SLAM_OK;
+    return run_chunked(
+        h, T, chunk, h->nav.time_ticks, h->gate.times,
+        [&](int t0, int tc) -> int {
+            TRY(tcmd.upload(h, t0, tc));
+            return upload_messages(h, meas + (size_t)t0 * mrow, count + (size_t)t0 * B, k_stride, (size_t)tc);
+        },
+        [&](int t0, int t, auto mark) -> int {
+            const float *cmd, *d_each;
+            TRY(tcmd.select(h, t0, t, &cmd, &d_each));
+            TRY(mark([&] {
+                return gate_launch(h, c, cmd, d_each, h->inn.dmeas + (size_t)t * mrow, h->inn.dcount + (size_t)t * B, k_stride, h->gate.dmeas,
+                                   h->gate.dcount, h->inn.drec + (size_t)t * slam::kInnovRecLen, nis_sum ? h->inn.dlog + (size_t)t * B : nullptr,
+                                   nullptr, nullptr, n_upd ? d_upd + (size_t)t * B : nullptr, flags ? d_flags + (size_t)t * B : nullptr, nullptr,
+                                   h->gate.drej + (size_t)t * B, nullptr);
+            }));
+            return launch_step(h, cmd, 0, h->gate.dmeas, h->gate.dcount, k_stride, d_each);
+        },
+        [&](int t0, int tc) -> int {
+            if (recs) HIP_TRY(hipMemcpy(recs + (size_t)t0 * slam::kInnovRecLen, h->inn.drec, sizeof(double) * (size_t)tc * slam::kInnovRecLen, hipMemcpyDeviceToHost));
+            if (nis_sum) HIP_TRY(hipMemcpy(nis_sum + (size_t)t0 * B, h->inn.dlog, sizeof(double) * (size_t)tc * B, hipMemcpyDeviceToHost));
+            if (n_upd) HIP_TRY(hipMemcpy(n_upd + (size_t)t0 * B, d_upd, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
+            if (flags) HIP_TRY(hipMemcpy(flags + (size_t)t0 * B, d_flags, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
+            if (n_rej) HIP_TRY(hipMemcpy(n_rej + (size_t)t0 * B, h->gate.drej, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
+            return SLAM_OK;
+        });
 }
 
 int slam_last_gate_work(slam_handle* h, double* gate_ms, double* total_ms) {
-    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
-    if (h->gate.total_ms < 0.0) return fail(SLAM_ERR_STATE, "slam_gate_run has not run on this handle");
-    if (gate_ms) *gate_ms = h->gate.gate_ms;
-    if (total_ms) *total_ms = h->gate.total_ms;
-    return SLAM_OK;
+    return last_work(h ? &h->gate.times : nullptr, "slam_gate_run", gate_ms, total_ms);
 }
 
 int slam_gate_instance_host(const double* x, const double* P, const int32_t* ids, int M, int L_max, int32_t status, const float cmd[2],

@@ -421,30 +421,37 @@ class BatchedFilter:
                                                _i(out["flags"])))
         return out
 
+    def _run_cmds(self, name, cmds, T):
+        """The (cmds, T) arguments of monitor_run and innovation_run as (float32 commands or None, source, T).  The sources, numbered
+        alike in slam_monitor_source and slam_innovation_source: (T, 2) SHARED, (T, batch, 2) EACH, no commands but T ticks NAV."""
+        if cmds is None:
+            if T is None:
+                raise ValueError(f"{name} needs commands or, for the closed loop, a number of ticks T")
+            return None, MONITOR_NAV, int(T)
+        c32 = np.ascontiguousarray(cmds, dtype=np.float32)
+        if c32.ndim == 3 and c32.shape[1:] == (self.batch, 2):
+            source = MONITOR_EACH
+        elif c32.ndim == 2 and c32.shape[1] == 2:
+            source = MONITOR_SHARED
+        else:
+            raise ValueError(f"expected commands of shape (T, 2) or (T, {self.batch}, 2), got {c32.shape}")
+        if T is not None and int(T) != c32.shape[0]:
+            raise ValueError(f"T = {T} does not match the {c32.shape[0]} commands")
+        return c32, source, c32.shape[0]
+
     def monitor_run(self, cmds=None, T=None, source=None, series=False, cfg=None):
         """A monitored run: per tick one simulator timestep and one monitor evaluation, all on the device; the same bits as the
         unmonitored run of the same commands.  cmds (T, 2): shared commands; (T, batch, 2): per instance; None with T ticks: the
         controller of set_path / set_paths issues them (source MONITOR_NAV).  Returns a MonitorResult; series=True also records the
         per-instance err_pos, err_yaw and nees_pose of every tick."""
         self._need()
-        if cmds is None:
-            if T is None:
-                raise ValueError("monitor_run needs commands or, for the closed loop, a number of ticks T")
-            source = MONITOR_NAV if source is None else source
-            c32, T = None, int(T)
+        c32, want, T = self._run_cmds("monitor_run", cmds, T)
+        if c32 is None:
+            source = want if source is None else source
+        elif source is not None and source != want:
+            raise ValueError(f"source {source} does not match commands of shape {c32.shape}")
         else:
-            c32 = np.ascontiguousarray(cmds, dtype=np.float32)
-            if c32.ndim == 3 and c32.shape[1:] == (self.batch, 2):
-                want = MONITOR_EACH
-            elif c32.ndim == 2 and c32.shape[1] == 2:
-                want = MONITOR_SHARED
-            else:
-                raise ValueError(f"expected commands of shape (T, 2) or (T, {self.batch}, 2), got {c32.shape}")
-            if T is not None and int(T) != c32.shape[0]:
-                raise ValueError(f"T = {T} does not match the {c32.shape[0]} commands")
-            if source is not None and source != want:
-                raise ValueError(f"source {source} does not match commands of shape {c32.shape}")
-            source, T = want, c32.shape[0]
+            source = want
         n = max(T, 0)
         res = MonitorResult(np.zeros((n, 16)))
         if series:
@@ -618,28 +625,16 @@ class BatchedEKF(BatchedFilter):
         series=True also records nis_sum, n_upd and flags of every instance at every tick."""
         self._need()
         m = cnt = None
-        if cmds is None:
-            if T is None:
-                raise ValueError("innovation_run needs commands or, for the closed loop, a number of ticks T")
-            source, c32, T = INNOVATION_NAV, None, int(T)
-        else:
-            c32 = np.ascontiguousarray(cmds, dtype=np.float32)
-            if meas is not None:
-                m = np.ascontiguousarray(meas, dtype=np.float32)
-                cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
-                if c32.ndim != 2 or c32.shape[1] != 2 or m.ndim != 4 or m.shape[:2] != (c32.shape[0], self.batch) or m.shape[3] != 3 \
-                        or cnt.shape != m.shape[:2]:
-                    raise ValueError(f"a log needs cmds (T, 2), meas (T, {self.batch}, k_stride, 3) and meas_count (T, {self.batch})")
-                source = INNOVATION_LOG
-            elif c32.ndim == 3 and c32.shape[1:] == (self.batch, 2):
-                source = INNOVATION_EACH
-            elif c32.ndim == 2 and c32.shape[1] == 2:
-                source = INNOVATION_SHARED
-            else:
-                raise ValueError(f"expected commands of shape (T, 2) or (T, {self.batch}, 2), got {c32.shape}")
-            if T is not None and int(T) != c32.shape[0]:
-                raise ValueError(f"T = {T} does not match the {c32.shape[0]} commands")
-            T = c32.shape[0]
+        if cmds is not None and meas is not None:   # a log: its shapes are checked as a whole, before T
+            cmds = np.ascontiguousarray(cmds, dtype=np.float32)
+            m = np.ascontiguousarray(meas, dtype=np.float32)
+            cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
+            if cmds.ndim != 2 or cmds.shape[1] != 2 or m.ndim != 4 or m.shape[:2] != (cmds.shape[0], self.batch) or m.shape[3] != 3 \
+                    or cnt.shape != m.shape[:2]:
+                raise ValueError(f"a log needs cmds (T, 2), meas (T, {self.batch}, k_stride, 3) and meas_count (T, {self.batch})")
+        c32, source, T = self._run_cmds("innovation_run", cmds, T)
+        if m is not None:
+            source = INNOVATION_LOG
         n = max(T, 0)
         res = InnovationResult(np.zeros((n, 16)))
         if series:

@@ -348,6 +348,89 @@ def test_gate_run_equals_the_loop_of_gated_steps_whatever_the_chunking(S, tmp_pa
         a.close()
 
 
+def test_runs_of_every_kind_interleaved_on_one_handle(S):
+    """monitor_run, gate_run, innovation_run (LOG), run_nav and monitor_run (NAV) one after the other on ONE handle - they share the
+    driver of the per-tick runs, its event pool and the staging buffers of messages and commands - against a second handle that is given
+    the same inputs through plain calls: run_sim, gate() + update on the filtered message, innovation() + update, and the host route of the
+    closed loop.  Per-tick timing goes on before the third run, so the event pool grows between runs."""
+    from batch_state import describe, differing_instances
+    from test_nav_gpu import _host_controller, _same_nav_state
+    L, Bn = 20, 8
+    lm, cmds = _scenario(L, 9)
+    cmds = np.ascontiguousarray(cmds, dtype=np.float32)
+    cfg = _config(S)
+    path = lm[:3].copy()
+
+    def handle():
+        f = S.BatchedEKF(Bn, L).readParams(cfg)
+        f.set_seed(11); f.set_map(lm); f.init(0.0, 0.0, 0.0)
+        return f
+    src = handle()                                    # the log: the messages the simulator generates at ticks 3 .. 8, one in five spiked
+    src.run_sim(cmds[:3]); src.last_meas(L)
+    log_meas, log_cnt = np.zeros((6, Bn, L, 3), np.float32), np.zeros((6, Bn), np.int32)
+    for t in range(6):
+        src.update_sim(cmds[3 + t]); log_meas[t], log_cnt[t] = src.last_meas(L)
+    src.close()
+    valid = np.arange(L)[None, None, :] < log_cnt[:, :, None]
+    log_meas[~valid] = 0.0
+    log_meas[:, :, :, 1] += np.where(valid & (np.random.default_rng(3).random((6, Bn, L)) < 0.2), np.float32(GR.SPIKE), np.float32(0.0))
+
+    a, b = handle(), handle()
+    a.set_path(path)
+    pp = _host_controller(b, path, dict(method=0, control=0))
+
+    def same(what):
+        d = differing_instances(a, b)
+        assert not d, f"after {what}: {describe(d)}"
+    # 1. a monitored run / run_sim
+    mon = a.monitor_run(cmds[:3])
+    b.run_sim(cmds[:3])
+    assert _same_bits(mon.recs[-1], b.monitor_now()["rec"])
+    same("monitor_run")
+    # 2. a gated run of the log / gate() and update() on the message it returned
+    gr = a.gate_run(cmds[3:6], log_meas[:3], log_cnt[:3], series=True)
+    for t in range(3):
+        g = b.gate(cmds[3 + t], log_meas[t], log_cnt[t], det=False)
+        b.update(cmds[3 + t], g["meas_out"], g["count_out"])
+        assert _same_bits(g["rec"], gr.recs[t]) and _same_bits(g["nis_sum"], gr.nis_sum[t]) and np.array_equal(g["n_rej"], gr.n_rej[t]), t
+    assert gr.n_rej.sum() > 0 and gr.recs[:, 5].sum() > 0
+    same("gate_run")
+    gate_ms, total_ms = a.last_gate_work()
+    assert gate_ms == -1.0 and total_ms > 0.0          # per-tick timing was off
+    # 3. an innovation run of the log / innovation() and update()
+    a.set_nav_timing(True)
+    ir = a.innovation_run(cmds[6:9], meas=log_meas[3:], meas_count=log_cnt[3:], series=True)
+    for t in range(3):
+        r = b.innovation(cmds[6 + t], log_meas[3 + t], log_cnt[3 + t], det=False)
+        b.update(cmds[6 + t], log_meas[3 + t], log_cnt[3 + t])
+        assert _same_bits(r["rec"], ir.recs[t]) and _same_bits(r["nis_sum"], ir.nis_sum[t]) and np.array_equal(r["n_upd"], ir.n_upd[t]), t
+    same("innovation_run")
+    part, total = a.last_innovation_work()
+    assert 0.0 < part < total
+    assert a.last_gate_work() == (gate_ms, total_ms)   # every kind of run keeps its own times
+    # 4. the closed loop / the host route
+    nav_cmds = a.run_nav(3, return_cmds=True)
+    for t in range(3):
+        c = pp.next_cmds(b.nav_estimates(), (b.status() & 4) != 0)
+        assert np.array_equal(c.view(np.uint32), nav_cmds[t].view(np.uint32)), t
+        b.run_sim(c[None])
+    same("run_nav")
+    part, total = a.last_nav_work()
+    assert 0.0 < part < total
+    # 5. the monitored closed loop / the host route
+    mon = a.monitor_run(T=2)
+    for t in range(2):
+        c = pp.next_cmds(b.nav_estimates(), (b.status() & 4) != 0)
+        b.run_sim(c[None])
+        assert _same_bits(mon.recs[t], b.monitor_now()["rec"]), t
+    same("monitor_run, source NAV")
+    part, total = a.last_monitor_work()
+    assert 0.0 < part < total
+    _same_nav_state(a.nav_state(), dict(remaining=pp.remaining, finish_tick=pp.finish_tick, integ=pp.integ, err_prev=pp.err_prev), "device vs host")
+    assert a.timestep == 14 and a.get_state(0)["timestep"] == 14 and nav_cmds.any()
+    a.close(); b.close()
+
+
 # ---- 6. an infinite gate is the plain step ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype32", [False, True], ids=["f64", "f32"])
 def test_an_infinite_gate_is_the_plain_step(S, tmp_path, dtype32):

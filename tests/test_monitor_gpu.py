@@ -385,6 +385,40 @@ def test_chunking_changes_nothing(S, source, monkeypatch):
         f.close()
 
 
+def test_chunking_changes_nothing_source_nav(S, monkeypatch):
+    """The closed loop in chunks: the controller's commands stay on the device, so a tick holds its rows of the series alone."""
+    L, T, B = 20, 7, 8
+    lm, _ = _scenario(L, T)
+    path = np.array([[3.0, 0.5], [5.0, -1.0]])
+    runs = {}
+    for name, budget in (("unchunked", None), ("chunks", 3 * (3 * 8 * B) + 7), ("one_byte", 1)):
+        if budget is None:
+            monkeypatch.delenv("SLAM_MONITOR_LOG_BYTES", raising=False)
+        else:
+            monkeypatch.setenv("SLAM_MONITOR_LOG_BYTES", str(budget))
+        f = _ekf(S, B, L, lm=lm)
+        f.set_path(path)
+        runs[name] = (f, f.monitor_run(T=T, series=True))
+    monkeypatch.delenv("SLAM_MONITOR_LOG_BYTES", raising=False)
+    plain = _ekf(S, B, L, lm=lm)
+    plain.set_path(path)
+    assert plain.run_nav(T, return_cmds=True).any()
+    ref_f, ref = runs["unchunked"]
+    _same(ref_f, plain, "monitored against plain closed loop")
+    for name in ("chunks", "one_byte"):
+        f, got = runs[name]
+        for k in ("recs", "err_pos", "err_yaw", "nees_pose"):
+            _bits_equal(getattr(got, k), getattr(ref, k), f"nav/{name}: {k}")
+        _same(f, ref_f, f"nav/{name}")
+        _same(f, plain, f"nav/{name} against slam_nav_run")
+        sa, sb = f.nav_state(), ref_f.nav_state()
+        for k in sa:
+            assert sa[k].tobytes() == sb[k].tobytes() == plain.nav_state()[k].tobytes(), (name, k)
+    for f, _ in runs.values():
+        f.close()
+    plain.close()
+
+
 # ---- 9. errors that need a device ---------------------------------------------------------------------------------------------------------
 def test_error_codes(S):
     from live_ekf_slam_amd import _lib

@@ -163,6 +163,68 @@ def test_replay_of_the_issued_commands(S, config):
 
 
 @pytest.mark.parametrize("config", ["ekf64_L20", "ukf_slam_L20"])
+def test_chunking_changes_nothing(S, config, monkeypatch):
+    """slam_nav_run cuts its ticks into chunks by the rule of every per-tick run (SLAM_MONITOR_LOG_BYTES over the 8 * batch bytes a tick
+    of the command log holds): the chunk size changes no bit of the commands, of the handle or of the controller state."""
+    Bn, T = 5, 10
+    nav = _nav(*CONTROLS["pp_loose"])
+    paths = _paths(_map(20), Bn, True)
+    st = _starts(paths, Bn)
+
+    def run(budget, timing=False):
+        if budget is None:
+            monkeypatch.delenv("SLAM_MONITOR_LOG_BYTES", raising=False)
+        else:
+            monkeypatch.setenv("SLAM_MONITOR_LOG_BYTES", str(budget))
+        f, _ = _make(S, config, Bn, starts=st)
+        _set(f, paths, True, nav)
+        if timing:
+            f.set_nav_timing(True)
+        return f, f.run_nav(T, return_cmds=True)
+    three = 3 * 8 * Bn + 7                       # three ticks per chunk: four chunks, the last of one tick
+    ref, cmds = run(None)
+    assert cmds.any() and np.isfinite(cmds).all()
+    for budget, timing in ((three, False), (1, False), (three, True)):
+        f, c = run(budget, timing)
+        what = f"{config}, SLAM_MONITOR_LOG_BYTES={budget}, timing {timing}"
+        assert np.array_equal(_bits(c), _bits(cmds)), what
+        _same_handles(f, ref, what)
+        _same_nav_state(f.nav_state(), ref.nav_state(), what)
+        if timing:
+            ctrl, total = f.last_nav_work()
+            assert 0.0 < ctrl < total
+        f.close()
+    monkeypatch.delenv("SLAM_MONITOR_LOG_BYTES", raising=False)
+    fr, _ = _make(S, config, Bn, starts=st)
+    fr.run_sim(cmds)
+    _same_handles(ref, fr, f"replay {config}")
+    ref.close(); fr.close()
+
+
+def test_more_ticks_than_one_chunk_holds(S):
+    """T = 4100 crosses the cap of 4096 ticks per chunk: the commands of both chunks land in their rows (the replay of what was returned
+    ends in the same bits) and the rows of the second chunk are written."""
+    Bn, T = 2, 4100
+    paths = [np.array([[3.0, 0.5], [1.0e5, -1.0]]), np.array([[0.3, 0.0]])]     # instance 0 is under way to the end, instance 1 finishes at once
+    fa, _ = _make(S, "ekf64_L20", Bn)
+    _set(fa, paths, True, _nav(*CONTROLS["pp_loose"]))
+    cmds = fa.run_nav(T, return_cmds=True)
+    assert cmds.shape == (T, Bn, 2) and fa.timestep == T and fa.get_state(0)["timestep"] == T
+    fr, _ = _make(S, "ekf64_L20", Bn)
+    fr.run_sim(cmds)
+    _same_handles(fa, fr, "replay of 4100 ticks")
+    finish = fa.nav_state()["finish_tick"]
+    assert finish[0] == -1 and 0 <= finish[1] < 4096
+    assert np.isfinite(cmds).all()
+    for t in range(T - 4, T):
+        for b in range(Bn):
+            done = 0 <= finish[b] <= t
+            assert cmds[t, b].any() != done, (t, b, cmds[t, b], finish[b])
+    assert cmds[4095, 0].any() and cmds[4096, 0].any()
+    fa.close(); fr.close()
+
+
+@pytest.mark.parametrize("config", ["ekf64_L20", "ukf_slam_L20"])
 def test_batch_independence_and_split_calls(S, config):
     nav = _nav(*CONTROLS["pp_loose"])
     paths = _paths(_map(20), B_TEST, True)
