@@ -29,30 +29,6 @@ namespace {
 
 constexpr int kBigTpb = 1024;
 
-__device__ __forceinline__ bool big_inv2x2_lu(const double S[4], double Si[4]) {   // PartialPivLU inverse (MatrixXd::inverse(), ekf.cpp:135)
-    const bool sw = fabs(S[2]) > fabs(S[0]);
-    const double a00 = sw ? S[2] : S[0], a01 = sw ? S[3] : S[1];
-    const double a10 = sw ? S[0] : S[2], a11 = sw ? S[1] : S[3];
-    const double l = a10 / a00;
-    const double u11 = a11 - l * a01;
-    const bool ok = (a00 != 0.0) && (u11 != 0.0);
-    {
-        const double r0 = sw ? 0.0 : 1.0, r1 = sw ? 1.0 : 0.0;
-        const double y1 = r1 - l * r0;
-        const double x1 = y1 / u11;
-        Si[0] = (r0 - a01 * x1) / a00;
-        Si[2] = x1;
-    }
-    {
-        const double r0 = sw ? 1.0 : 0.0, r1 = sw ? 0.0 : 1.0;
-        const double y1 = r1 - l * r0;
-        const double x1 = y1 / u11;
-        Si[1] = (r0 - a01 * x1) / a00;
-        Si[3] = x1;
-    }
-    return ok;
-}
-
 // LDS layout (dynamic): x_t [np], x_pred [np], K / P H^T [2 np] (interleaved per state index), H P [2 np] (row 0, row 1), scalars [32],
 // ints [16], new ids [L_max], message [3 L] floats (SIM mode)
 // ST = storage type of x_t and P_t.  double: the streamed size class (L_max > 200) and the long messages of the fp64 LDS classes.  float
@@ -236,7 +212,7 @@ __global__ __launch_bounds__(kBigTpb) void ekf_big_step_kernel(const EkfStepPara
                 S[3] = (((g1[0] * h10 + g1[1] * h11) + g1[2] * h12) + g1[ii] * h13) + g1[ii + 1] * h14;
                 S[0] = S[0] + nz.W00;
                 S[3] = S[3] + nz.W11;
-                if (!big_inv2x2_lu(S, Si)) s_i[2] |= SLAM_INST_S_SINGULAR;
+                if (!inv2x2_lu(S, Si)) s_i[2] |= SLAM_INST_S_SINGULAR;
                 s_sc[10] = Si[0]; s_sc[11] = Si[1]; s_sc[12] = Si[2]; s_sc[13] = Si[3];
             }
             __syncthreads();

@@ -65,31 +65,6 @@ constexpr int hp_substride(int ldp) {
     return hs;
 }
 
-// PartialPivLU inverse of a 2x2 (MatrixXd::inverse(), ekf.cpp:135); same sequence as the oracle's inv2x2_lu.
-__device__ __forceinline__ bool inv2x2_lu(const double S[4], double Si[4]) {
-    const bool sw = fabs(S[2]) > fabs(S[0]);
-    const double a00 = sw ? S[2] : S[0], a01 = sw ? S[3] : S[1];
-    const double a10 = sw ? S[0] : S[2], a11 = sw ? S[1] : S[3];
-    const double l = a10 / a00;
-    const double u11 = a11 - l * a01;
-    const bool ok = (a00 != 0.0) && (u11 != 0.0);
-    {   // column 0 of the inverse: rhs = P e_0
-        const double r0 = sw ? 0.0 : 1.0, r1 = sw ? 1.0 : 0.0;
-        const double y1 = r1 - l * r0;
-        const double x1 = y1 / u11;
-        Si[0] = (r0 - a01 * x1) / a00;
-        Si[2] = x1;
-    }
-    {   // column 1
-        const double r0 = sw ? 1.0 : 0.0, r1 = sw ? 0.0 : 1.0;
-        const double y1 = r1 - l * r0;
-        const double x1 = y1 / u11;
-        Si[1] = (r0 - a01 * x1) / a00;
-        Si[3] = x1;
-    }
-    return ok;
-}
-
 // Ablation switches (bit 1: no bulk stream, bit 2: no updates / insertions, bit 16: never skip the stream) produce WRONG
 // filter state; they exist for timing experiments only and are compiled in by -DSLAM_ABLATE (tools/gpu_ablate.py builds
 // its own library).  The release library ignores them; only the timer bits (4, 32) of SLAM_DEBUG_FLAGS stay.

@@ -14,8 +14,8 @@
 //
 // The walk (landmark_id_is_known = 1), per detection l in message order, id = (int)meas[3 l]:
 //   found (first j < M with ids[j] == id)  -> UPDATE of landmark j: dist, d2, angf, nu0, nu1 with the float truncations of ekf.cpp:115,129-131,
-//                                             H0 / H1, H P, P H^T, S in the oracle's association order, Si = inv2x2_lu(S) (PartialPivLU, restated
-//                                             below), K, x_pred += K nu, x_pred(2) = remainder(., 2 pi), the rank-2 downdate on the block
+//                                             H0 / H1, H P, P H^T, S in the oracle's association order, Si = inv2x2_lu(S) (PartialPivLU,
+//                                             slam_math.h), K, x_pred += K nu, x_pred(2) = remainder(., 2 pi), the rank-2 downdate on the block
 //   not found, first occurrence of the id  -> INSERTION while the map has room (M + insertions so far < L_max), else a capacity skip
 //   not found, the id occurred before      -> its first occurrence was inserted by this message: the step raises SLAM_INST_INDEX_OOR and rolls
 //                                             back (WOULD_FREEZE); it was skipped: skipped again
@@ -82,31 +82,6 @@ struct InnovResult {
 };
 
 SLAM_HD bool innov_finite(double v) { return fabs(v) < __builtin_inf(); }
-
-// PartialPivLU inverse of a 2x2 (MatrixXd::inverse(), ekf.cpp:135): the sequence of the step kernels' inv2x2_lu and the oracle's
-SLAM_HD bool innov_inv2x2_lu(const double S[4], double Si[4]) {
-    const bool sw = fabs(S[2]) > fabs(S[0]);
-    const double a00 = sw ? S[2] : S[0], a01 = sw ? S[3] : S[1];
-    const double a10 = sw ? S[0] : S[2], a11 = sw ? S[1] : S[3];
-    const double l = a10 / a00;
-    const double u11 = a11 - l * a01;
-    const bool ok = (a00 != 0.0) && (u11 != 0.0);
-    {   // column 0 of the inverse: rhs = P e_0
-        const double r0 = sw ? 0.0 : 1.0, r1 = sw ? 1.0 : 0.0;
-        const double y1 = r1 - l * r0;
-        const double x1 = y1 / u11;
-        Si[0] = (r0 - a01 * x1) / a00;
-        Si[2] = x1;
-    }
-    {   // column 1
-        const double r0 = sw ? 1.0 : 0.0, r1 = sw ? 0.0 : 1.0;
-        const double y1 = r1 - l * r0;
-        const double x1 = y1 / u11;
-        Si[1] = (r0 - a01 * x1) / a00;
-        Si[3] = x1;
-    }
-    return ok;
-}
 
 // The gating policy of innovation_instance(): InnovNoGate is the plain evaluation (slam_innovation; every `if constexpr` below drops
 // out and the function is the code it was before there was a gate), InnovGate the chi-square gate of slam_gate (gate_kernel.h).
@@ -278,7 +253,7 @@ SLAM_HD InnovResult innovation_instance(const W& w, InnovWork& ws, LX load_x, LP
             S[0] = S[0] + nz.W00;
             S[3] = S[3] + nz.W11;
         }
-        const bool ok = innov_inv2x2_lu(S, Si);
+        const bool ok = inv2x2_lu(S, Si);
         double nis = nu0 * (Si[0] * nu0 + Si[1] * nu1) + nu1 * (Si[2] * nu0 + Si[3] * nu1);
         if (!ok) { flags |= kInnovSingular; nis = nan; }
         if (!innov_finite(nu0) || !innov_finite(nu1) || !innov_finite(S[0]) || !innov_finite(S[1]) || !innov_finite(S[2]) || !innov_finite(S[3])) nis = nan;

@@ -1256,7 +1256,7 @@ int slam_load_state(slam_handle* h, const char* path) {
         if (!rc) rc = column(5, "the timestep", 0, INT32_MAX);
         if (!rc && h->kind != SLAM_EKF_SLAM) rc = column(9, "the size of the stored square root", 0, h->n_max);
         // -1 is the cold-start marker (ukf_init_kernel, and both sqrt kernels after SLAM_INST_SQRT_FAILED); the kernels count the
-        // age up to kWarmMaxAge = 100 and start cold from there, so nothing a run can produce lies outside [-1, 100].
+        // age up to kUkfWarmMaxAge = 100 and start cold from there, so nothing a run can produce lies outside [-1, 100].
         if (!rc && h->kind != SLAM_EKF_SLAM) rc = column(12, "the age of the warm-start eigenvectors", -1, 100);
         if (rc) { fclose(f); return rc; }
         if (fseek(f, (long)sizeof(hd), SEEK_SET) != 0) { fclose(f); return fail(SLAM_ERR_IO, "cannot rewind %s", path); }

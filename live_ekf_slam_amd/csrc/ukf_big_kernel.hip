@@ -23,27 +23,6 @@ namespace slam {
 namespace {
 
 constexpr int kTpb = 1024;
-constexpr float kW0b = 0.2f;   // filter.h:207
-constexpr int kWarmMaxAge = 100;
-
-__device__ __forceinline__ void tsc(float a, int float_trig, double* s, double* c) {   // unqualified cos / sin on a float argument
-    double ss, cc;
-    det_sincos((double)a, &ss, &cc);
-    *s = float_trig ? (double)(float)ss : ss;
-    *c = float_trig ? (double)(float)cc : cc;
-}
-__device__ __forceinline__ float yawf(double c, double s) { return (float)remainder(det_atan2(s, c), kTwoPi); }
-__device__ __forceinline__ bool inv2(const double S[4], double Si[4]) {   // MatrixXd::inverse() of a 2 x 2 (ukf.cpp:339): PartialPivLU
-    const bool sw = fabs(S[2]) > fabs(S[0]);
-    const double a00 = sw ? S[2] : S[0], a01 = sw ? S[3] : S[1];
-    const double a10 = sw ? S[0] : S[2], a11 = sw ? S[1] : S[3];
-    const double l = a10 / a00;
-    const double u11 = a11 - l * a01;
-    const bool ok = (a00 != 0.0) && (u11 != 0.0);
-    { const double r0 = sw ? 0.0 : 1.0, r1 = sw ? 1.0 : 0.0; const double y1 = r1 - l * r0; const double x1 = y1 / u11; Si[0] = (r0 - a01 * x1) / a00; Si[2] = x1; }
-    { const double r0 = sw ? 1.0 : 0.0, r1 = sw ? 0.0 : 1.0; const double y1 = r1 - l * r0; const double x1 = y1 / u11; Si[1] = (r0 - a01 * x1) / a00; Si[3] = x1; }
-    return ok;
-}
 
 // ------------------------------------------------------------------------------------------------------------------
 // nearestSPD + principal square root (ukf.cpp:106-123,208): parallel-order Jacobi on matrices in global memory
@@ -64,10 +43,10 @@ __global__ __launch_bounds__(kTpb) void ukf_big_sqrt_kernel(const UkfStepParams 
     double* Vt = p.Vt_store + (size_t)b * p.pstride;         // V^T: row q = eigenvector q (n x n once this kernel has laid it out)
     double* A = p.big_ws + (size_t)b * 2 * p.pstride;        // the scaled symmetrised matrix, full n x n, kept exactly symmetric
     double* T = A + p.pstride;                               // scratch of the warm start
-    const float scale_f = (float)(2 * M + 4) / (1 - kW0b);   // ukf.cpp:114, evaluated in float
+    const float scale_f = (float)(2 * M + 4) / (1 - kUkfW0);   // ukf.cpp:114, evaluated in float
     const double scale = (double)scale_f;
     const int age = p.v_age[b], n_v = p.n_sq[b];
-    const bool warm = age >= 0 && age < kWarmMaxAge && n_v > 0 && n_v <= n;
+    const bool warm = age >= 0 && age < kUkfWarmMaxAge && n_v > 0 && n_v <= n;
 
     for (int e = tid; e < n * n; e += kTpb) {
         const int r = e / n, c = e - r * n;
@@ -281,9 +260,9 @@ __global__ __launch_bounds__(kTpb) void ukf_big_step_kernel(const UkfStepParams 
             else if (i <= n) v[r] = s_xt[r] + Sq[(size_t)(i - 1) * n + r];
             else v[r] = s_xt[r] - Sq[(size_t)(i - 1 - n) * n + r];
         }
-        const float yaw = yawf(v[2], v[3]);
+        const float yaw = yaw_of(v[2], v[3]);
         double sy, cy;
-        tsc(yaw, p.float_trig, &sy, &cy);
+        tsincos(yaw, p.float_trig, &sy, &cy);
         if (p.float_trig) {
             s_X4[0 * ns + i] = v[0] + (double)(dd * (float)cy);   // float * float (ukf.cpp:129)
             s_X4[1 * ns + i] = v[1] + (double)(dd * (float)sy);
@@ -293,13 +272,13 @@ __global__ __launch_bounds__(kTpb) void ukf_big_step_kernel(const UkfStepParams 
         }
         const float new_yaw = (float)remainder((double)(yaw + u_th + nz.v_th), kTwoPi);   // float adds (ukf.cpp:131)
         double sn, cn;
-        tsc(new_yaw, p.float_trig, &sn, &cn);
+        tsincos(new_yaw, p.float_trig, &sn, &cn);
         s_X4[2 * ns + i] = cn;
         s_X4[3 * ns + i] = sn;
     }
     __syncthreads();
-    const double w0 = (double)kW0b;
-    const double wi = (double)((1 - kW0b) / (2 * n));   // float arithmetic (ukf.cpp:174-175)
+    const double w0 = (double)kUkfW0;
+    const double wi = (double)((1 - kUkfW0) / (2 * n));   // float arithmetic (ukf.cpp:174-175)
     // sigma-point offset i - 1 = ROW i - 1 of sqtP, as ukf_step_kernel reads it: the symmetric eigen root (both halves written from one
     // value, so rows and columns are the same bits) or, in SLAM_UKF_SQRT_CHOLESKY mode on a long-message launch of an LDS class, L^T
     auto xel = [&](int r, int i) -> double {   // X_pred(r, i): rows 0..3 from the motion model, rows >= 4 = the sigma point itself
@@ -324,10 +303,10 @@ __global__ __launch_bounds__(kTpb) void ukf_big_step_kernel(const UkfStepParams 
         Pw[e] = acc;
     }
     __syncthreads();
-    const float yaw_t = yawf(s_xt[2], s_xt[3]);   // yaw of x_t: process noise diagonal (ukf.cpp:182-186) and the sensing model (ukf.cpp:139)
+    const float yaw_t = yaw_of(s_xt[2], s_xt[3]);   // yaw of x_t: process noise diagonal (ukf.cpp:182-186) and the sensing model (ukf.cpp:139)
     if (tid == 0) {
         double sy, cy;
-        tsc(yaw_t, p.float_trig, &sy, &cy);
+        tsincos(yaw_t, p.float_trig, &sy, &cy);
         Pw[0] = Pw[0] + nz.V00 * cy;
         Pw[(size_t)1 * n + 1] = Pw[(size_t)1 * n + 1] + nz.V00 * sy;
         Pw[(size_t)2 * n + 2] = Pw[(size_t)2 * n + 2] + nz.V11 * cy;
@@ -362,7 +341,7 @@ __global__ __launch_bounds__(kTpb) void ukf_big_step_kernel(const UkfStepParams 
         for (int i = tid; i < ns; i += kTpb) {   // sensing model of every sigma point (yaw from x_t)
             const double dx = (p.loc ? mx : xel(li, i)) - xel(0, i), dy = (p.loc ? my : xel(li + 1, i)) - xel(1, i);
             s_Z0[i] = sqrt(dx * dx + dy * dy) + (double)nz.w_r;
-            const double yaw_i = p.yaw_sigma ? (double)yawf(xel(2, i), xel(3, i)) : (double)yaw_t;   // quirk D-9: from x_t
+            const double yaw_i = p.yaw_sigma ? (double)yaw_of(xel(2, i), xel(3, i)) : (double)yaw_t;   // quirk D-9: from x_t
             s_Z1[i] = remainder((det_atan2(dy, dx) - yaw_i) + (double)nz.w_b, kTwoPi);
         }
         __syncthreads();
@@ -381,7 +360,7 @@ __global__ __launch_bounds__(kTpb) void ukf_big_step_kernel(const UkfStepParams 
             }
             S[0] = S[0] + nz.W00; S[1] = S[1] + 0.0; S[2] = S[2] + 0.0; S[3] = S[3] + nz.W11;
             double Si[4];
-            if (!inv2(S, Si)) s_i[2] |= SLAM_INST_S_SINGULAR;
+            if (!inv2x2_lu(S, Si)) s_i[2] |= SLAM_INST_S_SINGULAR;
             s_sc[0] = z0;
             for (int q = 0; q < 4; ++q) { s_sc[4 + q] = S[q]; s_sc[8 + q] = Si[q]; }
             s_sc[12] = (double)r_m - z0;
@@ -423,10 +402,10 @@ __global__ __launch_bounds__(kTpb) void ukf_big_step_kernel(const UkfStepParams 
         if (tid == 0) {
             const float r_m = meas[3 * l + 1], b_m = meas[3 * l + 2];
             const int nn = 4 + 2 * M;
-            const float yaw = yawf(s_xp[2], s_xp[3]);
+            const float yaw = yaw_of(s_xp[2], s_xp[3]);
             const float ang = yaw + b_m;
             double sa, ca;
-            tsc(ang, p.float_trig, &sa, &ca);
+            tsincos(ang, p.float_trig, &sa, &ca);
             if (p.float_trig) {
                 s_xp[nn] = s_xp[0] + (double)(r_m * (float)ca);
                 s_xp[nn + 1] = s_xp[1] + (double)(r_m * (float)sa);

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "noise_row.h"
+#include "slam_math.h"
 
 namespace slam {
 
@@ -86,6 +87,21 @@ static constexpr int kUkfLdsMaxLandmarks = 50;   // n = 4 + 2L <= 104: the fast 
 static constexpr int kUkfMaxLandmarks = 200;     // beyond: ukf_big_kernel.hip, every n x n object in HBM / L2 (slow, bit-identical)
 hipError_t launch_ukf_big_sqrt(const UkfStepParams& p, hipStream_t stream);
 hipError_t launch_ukf_big_step(const UkfStepParams& p, hipStream_t stream);
+
+static constexpr float kUkfW0 = 0.2f;        // weight of the central sigma point (filter.h:207)
+static constexpr int kUkfWarmMaxAge = 100;   // consecutive warm starts of the eigen-decomposition before one starts cold again
+
+// unqualified cos / sin on a float argument (ukf.cpp:39-42,129-133,183-186,358-359)
+__device__ __forceinline__ void tsincos(float a, int float_trig, double* s, double* c) {
+    double ss, cc;
+    det_sincos((double)a, &ss, &cc);
+    *s = float_trig ? (double)(float)ss : ss;
+    *c = float_trig ? (double)(float)cc : cc;
+}
+
+__device__ __forceinline__ float yaw_of(double c, double s) {  // (float) remainder(atan2(x3, x2), 2 pi)
+    return (float)remainder(det_atan2(s, c), kTwoPi);
+}
 
 // SLAM_UKF_SQRT_CHOLESKY: khist[kUkfCholSlot] = Cholesky factors that succeeded, khist[kUkfCholSlot + 1] = eigen fallbacks
 static constexpr int kUkfCholSlot = 14;

@@ -7,7 +7,8 @@
 //                   round (jacobi_schedule.h), every pair-block B' = R_i^T B R_j and every V row-pair an independent work
 //                   item.  The state size, padded to a multiple of four, walks the schedule in PASSES of two rounds that stay inside
 //                   quadruples of indices: the 4 x 4 blocks of A and four rows of V^T in registers across both, one barrier
-//                   per pass.  This O(n^3 * sweeps) fp64 phase dominates the UKF (70 % of its GPU time); it is bound by
+//                   per pass.  Two paths walk the passes: <44, 256> reads a pass's LDS addresses from a table built on the host,
+//                   <104, 1024> generates them from the schedule.  This O(n^3 * sweeps) fp64 phase dominates the UKF (70 % of its GPU time); it is bound by
 //                   VALU issue (82 % utilisation at six workgroups per CU, profiles/r04_ukf/).
 //  ukf_step_kernel  sigma points through the motion model, weighted mean and covariance (sequential in the sigma
 //                   index exactly like the reference's accumulation loops), all landmark updates (the reference never
@@ -18,8 +19,6 @@
 // Arithmetic: plain IEEE fp64 (-ffp-contract=off), same operation order as the CPU oracle
 // (oracle/slam_oracle_ukf.cpp) so results are bit-identical; the reference's float truncations are real fp32 ops.
 #include "ukf_kernel.h"
-
-#include <stdlib.h>
 
 #include <vector>
 
@@ -42,44 +41,6 @@ namespace slam {
 
 namespace {
 
-constexpr float kW0 = 0.2f;  // filter.h:207
-
-__device__ __forceinline__ bool inv2x2_lu_ukf(const double S[4], double Si[4]) {  // MatrixXd::inverse() (ukf.cpp:339)
-    const bool sw = fabs(S[2]) > fabs(S[0]);
-    const double a00 = sw ? S[2] : S[0], a01 = sw ? S[3] : S[1];
-    const double a10 = sw ? S[0] : S[2], a11 = sw ? S[1] : S[3];
-    const double l = a10 / a00;
-    const double u11 = a11 - l * a01;
-    const bool ok = (a00 != 0.0) && (u11 != 0.0);
-    {
-        const double r0 = sw ? 0.0 : 1.0, r1 = sw ? 1.0 : 0.0;
-        const double y1 = r1 - l * r0;
-        const double x1 = y1 / u11;
-        Si[0] = (r0 - a01 * x1) / a00;
-        Si[2] = x1;
-    }
-    {
-        const double r0 = sw ? 1.0 : 0.0, r1 = sw ? 0.0 : 1.0;
-        const double y1 = r1 - l * r0;
-        const double x1 = y1 / u11;
-        Si[1] = (r0 - a01 * x1) / a00;
-        Si[3] = x1;
-    }
-    return ok;
-}
-
-// unqualified cos / sin on a float argument (ukf.cpp:39-42,129-133,183-186,358-359)
-__device__ __forceinline__ void tsincos(float a, int float_trig, double* s, double* c) {
-    double ss, cc;
-    det_sincos((double)a, &ss, &cc);
-    *s = float_trig ? (double)(float)ss : ss;
-    *c = float_trig ? (double)(float)cc : cc;
-}
-
-__device__ __forceinline__ float yaw_of(double c, double s) {  // (float) remainder(atan2(x3, x2), 2 pi)
-    return (float)remainder(det_atan2(s, c), kTwoPi);
-}
-
 // a double from another lane of the same group of four (DPP quad_perm; every lane of the group must be active)
 template <int CTRL>
 __device__ __forceinline__ double dpp_quad(double v) {
@@ -87,19 +48,6 @@ __device__ __forceinline__ double dpp_quad(double v) {
     lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
     hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
     return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double block_max(double v, double* s_red, int tid, int tpb) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const double w = __shfl_down(v, o);
-        v = v > w ? v : w;
-    }
-    __syncthreads();
-    if ((tid & 63) == 0) s_red[tid >> 6] = v;
-    __syncthreads();
-    double r = s_red[0];
-    for (int i = 1; i < tpb / 64; ++i) r = r > s_red[i] ? r : s_red[i];
-    return r;
 }
 
 }  // namespace
@@ -193,6 +141,11 @@ hipError_t launch_ukf_quad_table(uint4* tab, hipStream_t stream) {
 // ------------------------------------------------------------------------------------------------------------------
 // nearestSPD + sqrt
 // ------------------------------------------------------------------------------------------------------------------
+// Two geometries, one path of the Jacobi walk each (both one barrier per pass of two rounds, wavefront 0 forming the next pass's
+// rotation parameters while the others rotate):
+//   <44, 256>    pass table (kTab): the LDS addresses of every operand of a pass come from launch_ukf_quad_table's table
+//   <104, 1024>  generated passes (kQuadGen): block lanes and V items decoded once per launch, addresses from the quadruples' block numbers
+// Either path gives a thread at most two pair-block items per pass; a geometry beyond that does not compile (static_assert below).
 // PROF = true compiles the phase timers in (a separate instantiation, launched only when the debug buffer is attached:
 // as a run-time option they cost the production kernel 20 VGPRs = one wavefront per SIMD of occupancy, -9 % steps/s).
 template <int NMAX, int TPB, bool PROF = false>
@@ -200,13 +153,11 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 256 && !PROF) ? SLAM_UKF
     constexpr int MMAX = NMAX / 2;
     __shared__ double sA[NMAX * (NMAX + 1) / 2];   // packed lower triangle: A(r,c), r >= c, at r(r+1)/2 + c
     __shared__ __attribute__((aligned(16))) double sVt[NMAX * NMAX];   // V transposed: Vt[p*n + k] = V(k, p)
-    __shared__ double s_cs[MMAX], s_sn[MMAX], s_tn[MMAX], s_sd[NMAX];
-    __shared__ int s_pp[MMAX], s_qq[MMAX];
-    constexpr bool kQuadLds = (MMAX * (MMAX + 1) / 2 + TPB - 1) / TPB <= 2;   // the variants that walk the schedule in passes of two rounds (kFast below)
-    __shared__ double2 s_csn[(kQuadLds ? 6 : 2) * MMAX];   // (c, s) of the rotations, one 16-byte read per consumer: [pass parity][round of the pass][pair] (round-by-round variants: [pair])
-    __shared__ int s_qflag[kQuadLds ? 2 * ((MMAX + 1) / 2) : 1];   // passes: [pass parity][quadruple] any rotation of the pass that is not the identity
-    __shared__ int s_xy[kQuadLds ? 2 * ((MMAX + 1) / 2) : 1];      // passes without the table: [pass parity][quadruple] its blocks X | Y << 8
-    __shared__ int s_pass_flag;                                    // passes without the table: wavefront 1 -> wavefront 0, "critical blocks of pass # written"
+    __shared__ double s_sd[NMAX];
+    __shared__ double2 s_csn[6 * MMAX];             // (c, s) of the rotations, one 16-byte read per consumer: [pass parity][round of the pass][pair]
+    __shared__ int s_qflag[2 * ((MMAX + 1) / 2)];   // [pass parity][quadruple] any rotation of the pass that is not the identity
+    __shared__ int s_xy[2 * ((MMAX + 1) / 2)];      // generated passes: [pass parity][quadruple] its blocks X | Y << 8
+    __shared__ int s_pass_flag;                     // generated passes: wavefront 1 -> wavefront 0, "critical blocks of pass # written"
 
     const int b = blockIdx.x + p.b_off, tid = threadIdx.x;
     if (p.chol_ok != nullptr && p.chol_ok[b]) return;   // Cholesky mode: ukf_chol_kernel already wrote this instance's sqtP
@@ -214,20 +165,18 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 256 && !PROF) ? SLAM_UKF
     const int n = 4 + 2 * M, m = n / 2;
     const double* __restrict__ Pb = p.P + (size_t)b * p.pstride;
     double* __restrict__ Sq = p.sqtP + (size_t)b * p.pstride;
-    auto AT = [&](int r, int c) -> double& { return r >= c ? sA[r * (r + 1) / 2 + c] : sA[c * (c + 1) / 2 + r]; };
 
     // phase timers (debug, SLAM_DEBUG_FLAGS & 4): slots 10..15 of the [B][16] buffer whose slots 0..9 the step kernel fills.
     // tid 0 stamps right after a barrier, so a delta is one whole barrier-to-barrier phase as wavefront 0 sees it.
     unsigned long long sacc[PROF ? 6 : 1] = {0}, sprev = 0ull;
     if constexpr (PROF) sprev = wall_clock64();
 #define SQ_STAMP(i) do { if constexpr (PROF) { if (tid == 0) { const unsigned long long now_ = wall_clock64(); sacc[i] += now_ - sprev; sprev = now_; } } } while (0)
-    const float scale_f = (float)(2 * M + 4) / (1 - kW0);   // ukf.cpp:114, evaluated in float
+    const float scale_f = (float)(2 * M + 4) / (1 - kUkfW0);   // ukf.cpp:114, evaluated in float
     const double scale = (double)scale_f;
     // Warm start: the eigenvectors of the previous timestep (extended by the identity for landmarks inserted since)
     // make V0^T A V0 nearly diagonal, so 4 sweeps instead of 8 converge.  Same arithmetic as the oracle's warm path.
-    constexpr int kWarmMaxAge = 100;
     const int age = p.v_age[b], n_v = p.n_sq[b];
-    const bool warm = age >= 0 && age < kWarmMaxAge && n_v > 0 && n_v <= n;
+    const bool warm = age >= 0 && age < kUkfWarmMaxAge && n_v > 0 && n_v <= n;
     double* Vs = p.Vt_store + (size_t)b * p.pstride;   // V0^T on entry; scratch for T once V0 sits in LDS; V^T on exit
     {   // the global loads of four elements are issued before the first value is used (a quarter of the memory round trips
         // of one element at a time: the ISA had vmcnt(0) after each pair of loads).  Four, not all eight: the whole batch
@@ -335,40 +284,16 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 256 && !PROF) ? SLAM_UKF
     }
     SQ_STAMP(0);   // load, symmetrise, warm-start transform
 
-    const int nb = mj * (mj - 1) / 2;       // (the item loop of the variants without passes: pair-blocks, diagonal blocks, V rows of the PADDED size)
-    const int items = nb + mj + mj * n;
-    // The work items a thread owns are the same in every round: decode them once.
-    //   kind 0: pair-block (i, j), i > j      B' = R_i^T B R_j
-    //   kind 1: diagonal block of pair i
-    //   kind 2: row k of V for pair i         V <- V J
-    constexpr int IT = (MMAX * (MMAX - 1) / 2 + MMAX + MMAX * NMAX + TPB - 1) / TPB;
-    int desc[IT];
-#pragma unroll
-    for (int u = 0; u < IT; ++u) {
-        const int it = tid + TPB * u;
-        int d = -1;
-        if (it < nb) {
-            int i = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)it)) * 0.5f);
-            while (i * (i - 1) / 2 > it) --i;
-            while ((i + 1) * i / 2 <= it) ++i;
-            d = (i << 8) | (it - i * (i - 1) / 2);
-        } else if (it < nb + mj) {
-            d = (1 << 16) | ((it - nb) << 8);
-        } else if (it < items) {
-            const int e = it - nb - mj;
-            const int i = e / n;
-            d = (2 << 16) | (i << 8) | (e - i * n);
-        }
-        desc[u] = d;
-    }
-    // The variants with at most two pair-block items per thread walk the schedule in PASSES of two rounds (below); <44, 256> takes the LDS
-    // addresses of a pass from the pass table, the others derive them from the quadruples' block numbers.
+    const int npass = mj - 1;               // passes of two rounds per sweep (block rounds of the schedule over the mj blocks)
+    // The schedule is walked in PASSES of two rounds (below), which takes at most two pair-block items per thread.  <44, 256> reads the LDS
+    // addresses of a pass from the pass table (kTab); the other geometry derives them from the quadruples' block numbers (kQuadGen).
     constexpr int ITB = (MMAX * (MMAX + 1) / 2 + TPB - 1) / TPB;
-    constexpr bool kFast = ITB <= 2;
-    constexpr bool kTab = ITB <= 2 && NMAX == 44 && TPB == kUkfRotThreads;
-    constexpr int VT0 = kFast ? 64 : 0;      // first thread that has V items (wavefront 0 carries the parameter chain)
+    static_assert(ITB <= 2, "more than two pair-block items per thread: neither pass path covers this geometry, it would rotate nothing");
+    constexpr bool kTab = NMAX == 44 && TPB == kUkfRotThreads;
+    constexpr bool kQuadGen = !kTab;
+    constexpr int VT0 = 64;                 // first thread that has V items (wavefront 0 carries the parameter chain)
     bool converged = false;
-    int pass_seq = 1;                       // passes without the table: number of the pass (s_pass_flag)
+    int pass_seq = 1;                       // generated passes: number of the pass (s_pass_flag)
     if (tid == 0) s_pass_flag = 0;          // (the barriers of the prologue come before its first use)
     uint4 te_next = make_uint4(0u, 0u, 0u, 0u);
     const uint4* const qtab = kTab ? p.quad_tab + ((size_t)(nj >> 2) * kUkfQuadPasses * kUkfRotThreads + tid) * 2 : nullptr;   // + 2 * 256 * pass
@@ -442,13 +367,12 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 256 && !PROF) ? SLAM_UKF
     }
     // ---- pieces of the quadruple ("pass") paths (launch_ukf_quad_table; jacobi_schedule.h) ----
     constexpr int MQ = (MMAX + 1) / 2;
-    // convergence scan of the passes without the table: threads 64 .. walk the strictly-lower triangle, scan_tpr of them per row
+    // convergence scan of the generated passes: threads 64 .. walk the strictly-lower triangle, scan_tpr of them per row
     const int scan_tpr = (TPB - 64) / n > 0 ? (TPB - 64) / n : 1, scan_dr = (TPB - 64) / scan_tpr > 0 ? (TPB - 64) / scan_tpr : 1;
     const int scan_r0 = (tid - 64) / scan_tpr, scan_c0 = (tid - 64) - scan_r0 * scan_tpr;
-    // passes without the table: the thread's block lanes (block (I, J) of quadruple positions, I > J: I << 8 | J) and V items (quadruple | pair of
+    // generated passes: the thread's block lanes (block (I, J) of quadruple positions, I > J: I << 8 | J) and V items (quadruple | pair of
     // columns << 8).  As in the table path the "critical" blocks - (1, 0), (k + 1, k - 1), (mq - 1, mq - 2): the ones that hold the next pass's pivots -
     // belong to the first lanes of the workgroup (wavefront 0, and wavefront 1 when there are more than sixteen), the others start at thread QOT0.
-    constexpr bool kQuadGen = ITB <= 2 && !kTab;
     constexpr int QOT0 = 4 * MQ > 64 ? 128 : 64;
     constexpr int QNB = kQuadGen ? 1 + (4 * (MQ * (MQ - 1) / 2) + (TPB - QOT0) - 1) / (TPB - QOT0) : 1, QNV = kQuadGen ? (MQ * MMAX + (TPB - VT0) - 1) / (TPB - VT0) : 1;
     int qb_desc[QNB], qv_desc[QNV];
@@ -564,7 +488,7 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 256 && !PROF) ? SLAM_UKF
         int live = 0;
         if constexpr (kTab) {
             // the thread's (at most four) strictly-lower elements, addresses decoded once per launch: every read of the scan is issued at
-            // once (the two-threads-per-row walk below left two thirds of the workgroup idle and each lane 22 dependent round trips)
+            // once (a two-threads-per-row walk left two thirds of the workgroup idle and each lane 22 dependent round trips)
             const char* const sAc = reinterpret_cast<const char*>(sA);
             double v[NSC], dp[NSC], dq[NSC];
             scan_addresses();   // (once per sweep: kept across the sweep they were eight registers of a kernel that has 80)
@@ -576,14 +500,14 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 256 && !PROF) ? SLAM_UKF
             }
 #pragma unroll
             for (int u = 0; u < NSC; ++u) {
-                if (tid + TPB * u < nlow && v[u] != 0.0 && v[u] == v[u]) {   // (a NaN is not "live": the oracle's max() passes over it, see below)
+                if (tid + TPB * u < nlow && v[u] != 0.0 && v[u] == v[u]) {   // (a NaN is not "live": the oracle's max() passes over it, see the other scan)
                     const double g = 100.0 * fabs(v[u]);
                     const double app = fabs(dp[u]), aqq = fabs(dq[u]);
                     if (!(sweep >= tiny_from && (app + g == app) && (aqq + g == aqq))) live = 1;
                 }
             }
-        } else if constexpr (kFast) {
-            // passes without the table: wavefront 0 forms the parameters of pass 0 (three rounds on the diagonal 4 x 4 blocks: the longest chain of
+        } else {
+            // generated passes: wavefront 0 forms the parameters of pass 0 (three rounds on the diagonal 4 x 4 blocks: the longest chain of
             // a sweep, and nothing else of the workgroup can run beside it but this scan) while the other wavefronts scan.  The two touch the
             // same elements - the pivots the parameter lanes zero or rotate, the diagonal entries they update - and the verdict is still
             // exact: a rotation that is not the identity means an element was live at the start of the sweep and is reported by its lane
@@ -601,25 +525,16 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 256 && !PROF) ? SLAM_UKF
                 for (int r = scan_r0; r < n; r += scan_dr)   // scan_tpr threads per row of the strictly-lower part (divisions: once per launch)
                     for (int c = scan_c0; c < r; c += scan_tpr) {
                         const double v = sA[r * (r + 1) / 2 + c];
-                        if (v != 0.0 && v == v) {   // (NaN: see below)
+                        // (NaN: the oracle's convergence test is max |a_ij| == 0 with std::max, which passes over NaNs - an instance whose P went
+                        // non-finite is flagged SLAM_INST_NONFINITE by the step kernel either way; it must not ALSO end as "no convergence" here only)
+                        if (v != 0.0 && v == v) {
                             const double g = 100.0 * fabs(v);
                             const double app = fabs(sA[c * (c + 1) / 2 + c]), aqq = fabs(sA[r * (r + 1) / 2 + r]);
                             if (!(sweep >= tiny_from && (app + g == app) && (aqq + g == aqq))) live = 1;
                         }
                     }
             }
-        } else
-        for (int r = tid / 2; r < n; r += TPB / 2)          // two threads per row, strictly-lower part
-            for (int c = (tid & 1); c < r; c += 2) {
-                const double v = sA[r * (r + 1) / 2 + c];
-                // (NaN: the oracle's convergence test is max |a_ij| == 0 with std::max, which passes over NaNs - an instance whose P went
-                // non-finite is flagged SLAM_INST_NONFINITE by the step kernel either way; it must not ALSO end as "no convergence" here only)
-                if (v != 0.0 && v == v) {
-                    const double g = 100.0 * fabs(v);
-                    const double app = fabs(sA[c * (c + 1) / 2 + c]), aqq = fabs(sA[r * (r + 1) / 2 + r]);
-                    if (!(sweep >= tiny_from && (app + g == app) && (aqq + g == aqq))) live = 1;
-                }
-            }
+        }
         const int any_live = __syncthreads_or(live);
         SQ_STAMP(1);   // convergence check
         if (!any_live) {
@@ -628,195 +543,134 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 256 && !PROF) ? SLAM_UKF
             break;
         }
         if constexpr (kTab) {
-            {
-                // ======== pass-table path: nj / 2 - 1 passes of two rounds, the in-block round inside pass 0 ========
-                const int mq = nj >> 2;
+            // ======== pass-table path: nj / 2 - 1 passes of two rounds, the in-block round inside pass 0 ========
+            const int mq = nj >> 2;
 #pragma unroll 1
-                for (int T = -1; T < mj - 1; ++T) {   // T = -1: only the parameters of pass 0 (every later pass gets its own a pass ahead)
-                    const uint4 ea = te_next;
-                    const unsigned ez = qnz;
-                    if (T >= 0) {
-                        const int Tn = T + 1 < mj - 1 ? T + 1 : 0;
-                        te_next = qtab[(size_t)Tn * (2 * kUkfRotThreads)]; qnz = qtab[(size_t)Tn * (2 * kUkfRotThreads) + 1].z;
-                        const bool first = T == 0;
-                        const double2* const cs = s_csn + par * 3 * MMAX;
-                        const int* const qf = s_qflag + par * MQ;
-                        if (qrole >= 0) {   // a lane of the 4 x 4 block between quadruples I > J
-                            const int I = (qrole >> 16) & 0xff, J = qrole >> 24, si = qrole & 0xff, sj = (qrole >> 8) & 0xff;
-                            if (qf[I] | qf[J]) {   // (the same for the four lanes of the block)
-                                if (first) {
-                                    const uint2 e0 = *reinterpret_cast<const uint2*>(qtab + 1);   // w4 w5 of pass 0: once per sweep, on demand
-                                    double g00 = ldA(e0.x & 0xffffu), g01 = ldA(e0.x >> 16), g10 = ldA(e0.y & 0xffffu), g11 = ldA(e0.y >> 16);
-                                    rot_block(g00, g01, g10, g11, cs[si], cs[sj]);
-                                    stA(e0.x & 0xffffu, g00); stA(e0.x >> 16, g01); stA(e0.y & 0xffffu, g10); stA(e0.y >> 16, g11);
-                                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the lanes of the block read each other's results below
-                                }
-                                double e00 = ldA(ea.x & 0xffffu), e01 = ldA(ea.x >> 16), e10 = ldA(ea.y & 0xffffu), e11 = ldA(ea.y >> 16);
-                                rot_block(e00, e01, e10, e11, cs[MMAX + si], cs[MMAX + sj]);
-                                // rows (i, i+2) x columns (j, j+2) -> rows (i, 3-i) x columns (j, 3-j): three of the four elements come from the other lanes
-                                e01 = dpp_quad<0xB1>(e01); e10 = dpp_quad<0x4E>(e10); e11 = dpp_quad<0x1B>(e11);
-                                rot_block(e00, e01, e10, e11, cs[2 * MMAX + si], cs[2 * MMAX + sj]);
-                                stA(ea.z & 0xffffu, e00); stA(ea.z >> 16, e01); stA(ea.w & 0xffffu, e10); stA(ea.w >> 16, e11);
-                            }
-                        }
-#pragma unroll 1
-                        for (int u = 0; u < 2; ++u) {   // V <- V J: four rows of V^T, a 16-byte pair of columns (one item at a time: registers)
-                            const int vi = u ? vitem[1] : vitem[0];
-                            if (vi < 0) continue;
-                            const int Q = vi & 0xff, kp = vi >> 8;
-                            if (!qf[Q]) continue;
-                            v_item(Q, kp, (ez >> (16 * u)) & 0xffffu, first, cs);
-                        }
-                    }
-                    // wavefront 0: the next pass's parameters, from what it has just written (its lanes < n / 2 carry their quadruple's blocks in w6)
-                    if (tid < 2 * mq && T + 1 < mj - 1) param_phase(T < 0 ? ez : qnz, T < 0, par ^ 1, sweep);
-                    __syncthreads();
-                    SQ_STAMP(3);   // one pass (one barrier)
-                    if constexpr (PROF) { if (tid == 0 && T >= 0) sacc[5] += 2; }   // rounds
-                    par ^= 1;
-                }
-                continue;
-            }
-        }
-        if constexpr (kFast && !kTab) {
-            {
-                // ======== passes without the table (the other fast variants; L = 50 runs <104, 1024>, one workgroup per CU) ========
-                // One barrier per pass, as in the table path: wavefront 0 (and 1) rotate the critical blocks first, then wavefront 0 goes on to the
-                // parameters of the NEXT pass (two rounds of sqrt / div / sqrt chains on the diagonal 4 x 4 blocks in LDS: ~1 us, the longest thing in
-                // a pass) while the other wavefronts do the rest of the blocks and the V items.  Critical blocks beyond wavefront 0's sixteen are
-                // wavefront 1's: it raises s_pass_flag after writing them and wavefront 0 waits for that before it reads the pivots.
-                const int mq = nj >> 2;
-                const bool crit_in_w1 = 4 * mq > 64;
-                par ^= 1;   // the parameters of pass 0 were formed beside the convergence scan
-#pragma unroll 1
-                for (int T = 0; T < mj - 1; ++T) {
-                    {
-                        const bool first = T == 0;
-                        const double2* const cs = s_csn + par * 3 * MMAX;
-                        const int* const qf = s_qflag + par * MQ;
-#pragma unroll
-                        for (int ub = 0; ub < QNB; ++ub) {
-                            const int bd = qb_desc[ub];   // block (I, J), I > J: I << 8 | J
-                            if (bd < 0) continue;
-                            const int I = bd >> 8, J = bd & 0xff;
-                            if (!(qf[I] | qf[J])) continue;   // (the same for the four lanes of the block)
-                            const int li = (tid >> 1) & 1, lj = tid & 1, si = 2 * I + li, sj = 2 * J + lj;
-                            const unsigned xi = (unsigned)s_xy[par * MQ + I], xj = (unsigned)s_xy[par * MQ + J];
-                            // the blocks (two consecutive indices each) behind the lane's rows and columns; an element (r, c) of the packed lower triangle sits
-                            // at tri(max) + min, and which of r, c is larger is a property of the two BLOCKS (four comparisons for all twelve elements)
-                            const int bX = (int)(xi & 0xffu), bY = (int)(xi >> 8), dX = (int)(xj & 0xffu), dY = (int)(xj >> 8);
-                            auto off = [&](const int r, const int c, const bool r_gt_c) -> unsigned {   // byte offset of A(r, c)
-                                const int hi = r_gt_c ? r : c, lo = r_gt_c ? c : r;
-                                return (unsigned)(4 * hi * (hi + 1) + 8 * lo);
-                            };
-                            const bool gXX = bX > dX, gXY = bX > dY, gYX = bY > dX, gYY = bY > dY;
-                            if (first) {   // the in-block round: rows (2 i, 2 i + 1) x columns (2 j, 2 j + 1) of the block
-                                const int r0 = 2 * (li ? bY : bX), c0 = 2 * (lj ? dY : dX);
-                                const bool g = li ? (lj ? gYY : gYX) : (lj ? gXY : gXX);
-                                const unsigned a00 = off(r0, c0, g), a01 = off(r0, c0 + 1, g), a10 = off(r0 + 1, c0, g), a11 = off(r0 + 1, c0 + 1, g);
-                                double b00 = ldA(a00), b01 = ldA(a01), b10 = ldA(a10), b11 = ldA(a11);
-                                rot_block(b00, b01, b10, b11, cs[si], cs[sj]);
-                                stA(a00, b00); stA(a01, b01); stA(a10, b10); stA(a11, b11);
+            for (int T = -1; T < npass; ++T) {   // T = -1: only the parameters of pass 0 (every later pass gets its own a pass ahead)
+                const uint4 ea = te_next;
+                const unsigned ez = qnz;
+                if (T >= 0) {
+                    const int Tn = T + 1 < npass ? T + 1 : 0;
+                    te_next = qtab[(size_t)Tn * (2 * kUkfRotThreads)]; qnz = qtab[(size_t)Tn * (2 * kUkfRotThreads) + 1].z;
+                    const bool first = T == 0;
+                    const double2* const cs = s_csn + par * 3 * MMAX;
+                    const int* const qf = s_qflag + par * MQ;
+                    if (qrole >= 0) {   // a lane of the 4 x 4 block between quadruples I > J
+                        const int I = (qrole >> 16) & 0xff, J = qrole >> 24, si = qrole & 0xff, sj = (qrole >> 8) & 0xff;
+                        if (qf[I] | qf[J]) {   // (the same for the four lanes of the block)
+                            if (first) {
+                                const uint2 e0 = *reinterpret_cast<const uint2*>(qtab + 1);   // w4 w5 of pass 0: once per sweep, on demand
+                                double g00 = ldA(e0.x & 0xffffu), g01 = ldA(e0.x >> 16), g10 = ldA(e0.y & 0xffffu), g11 = ldA(e0.y >> 16);
+                                rot_block(g00, g01, g10, g11, cs[si], cs[sj]);
+                                stA(e0.x & 0xffffu, g00); stA(e0.x >> 16, g01); stA(e0.y & 0xffffu, g10); stA(e0.y >> 16, g11);
                                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the lanes of the block read each other's results below
                             }
-                            const int rA = 2 * bX + li, rB = 2 * bY + li, cA = 2 * dX + lj, cB = 2 * dY + lj;
-                            double e00 = ldA(off(rA, cA, gXX)), e01 = ldA(off(rA, cB, gXY)), e10 = ldA(off(rB, cA, gYX)), e11 = ldA(off(rB, cB, gYY));
+                            double e00 = ldA(ea.x & 0xffffu), e01 = ldA(ea.x >> 16), e10 = ldA(ea.y & 0xffffu), e11 = ldA(ea.y >> 16);
                             rot_block(e00, e01, e10, e11, cs[MMAX + si], cs[MMAX + sj]);
-                            e01 = dpp_quad<0xB1>(e01); e10 = dpp_quad<0x4E>(e10); e11 = dpp_quad<0x1B>(e11);   // rows (i, i+2) x columns (j, j+2) -> (i, 3-i) x (j, 3-j)
+                            // rows (i, i+2) x columns (j, j+2) -> rows (i, 3-i) x columns (j, 3-j): three of the four elements come from the other lanes
+                            e01 = dpp_quad<0xB1>(e01); e10 = dpp_quad<0x4E>(e10); e11 = dpp_quad<0x1B>(e11);
                             rot_block(e00, e01, e10, e11, cs[2 * MMAX + si], cs[2 * MMAX + sj]);
-                            const int rC = 2 * bY + 1 - li, cC = 2 * dY + 1 - lj;
-                            stA(off(rA, cA, gXX), e00); stA(off(rA, cC, gXY), e01); stA(off(rC, cA, gYX), e10); stA(off(rC, cC, gYY), e11);
-                        }
-                        if (crit_in_w1 && tid >= 64 && tid < 128) {   // wavefront 1: its critical blocks are written (a wavefront's LDS accesses execute in order)
-                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                            if (tid == 64) *reinterpret_cast<volatile int*>(&s_pass_flag) = pass_seq;
-                        }
-                        if (tid >= VT0) {
-#pragma unroll
-                            for (int u = 0; u < QNV; ++u) {
-                                const int vd = qv_desc[u];   // quadruple | pair of columns << 8
-                                if (vd < 0) continue;
-                                const int Q = vd & 0xff;
-                                if (!qf[Q]) continue;
-                                v_item(Q, vd >> 8, (unsigned)s_xy[par * MQ + Q], first, cs);
-                            }
+                            stA(ea.z & 0xffffu, e00); stA(ea.z >> 16, e01); stA(ea.w & 0xffffu, e10); stA(ea.w >> 16, e11);
                         }
                     }
-                    if (tid < 64 && T + 1 < mj - 1) {   // wavefront 0: the next pass's parameters, from what the critical lanes have just written
-                        if (crit_in_w1) {
-                            while (*reinterpret_cast<volatile int*>(&s_pass_flag) != pass_seq) __builtin_amdgcn_s_sleep(1);
-                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                        }
-                        if (tid < 2 * mq) {
-                            int X, Y;
-                            rr_pair(tid >> 1, T + 1, mj, X, Y);
-                            const unsigned xy = (unsigned)X | ((unsigned)Y << 8);
-                            if (!(tid & 1)) s_xy[(par ^ 1) * MQ + (tid >> 1)] = (int)xy;
-                            param_phase(xy, false, par ^ 1, sweep);
-                        }
-                    }
-                    __syncthreads();
-                    SQ_STAMP(3);   // one pass (one barrier)
-                    if constexpr (PROF) { if (tid == 0) sacc[5] += 2; }   // rounds
-                    par ^= 1;
-                    pass_seq += 1;
-                }
-                continue;
-            }
-        }
-        // ======== the variants without passes (more than two pair-block items per thread): round by round, two barriers each ========
-        if constexpr (!kFast) {
 #pragma unroll 1
-        for (int t = 0; t < nj - 1; ++t) {
-            if (tid < mj) {  // rotation parameters of this round's pairs (jacobi_schedule.h)
-                const int k = tid;
-                int pidx, qidx;
-                jacobi_pair(k, t, nj, pidx, qidx);
-                double c, s, tt;
-                jacobi_param(AT(pidx, pidx), AT(qidx, qidx), AT(qidx, pidx), sweep, c, s, tt);
-                s_pp[k] = pidx; s_qq[k] = qidx; s_cs[k] = c; s_sn[k] = s; s_tn[k] = tt;
-                s_csn[par * MMAX + k] = make_double2(c, s);
-            }
-            __syncthreads();
-            SQ_STAMP(2);   // rotation parameters (lanes of wavefront 0) + barrier
-            if constexpr (PROF) { if (tid == 0) sacc[5] += 1; }   // rounds
-#pragma unroll
-            for (int u = 0; u < IT; ++u) {
-                const int d = desc[u];
-                if (d < 0) continue;
-                const int kind = d >> 16, i = (d >> 8) & 0xff, jk = d & 0xff;
-                if (kind == 0) {
-                    const int j = jk;
-                    const double si = s_sn[i], sj = s_sn[j];
-                    if (si == 0.0 && sj == 0.0) continue;   // both rotations are the identity (c = 1 exactly): B' = B bit for bit
-                    const int pi = s_pp[i], qi = s_qq[i], pj = s_pp[j], qj = s_qq[j];
-                    const double ci = s_cs[i], cj = s_cs[j];
-                    double& e00 = AT(pi, pj); double& e01 = AT(pi, qj); double& e10 = AT(qi, pj); double& e11 = AT(qi, qj);
-                    const double b00 = e00, b01 = e01, b10 = e10, b11 = e11;
-                    const double t00 = fma(ci, b00, -(si * b10)), t01 = fma(ci, b01, -(si * b11));
-                    const double t10 = fma(si, b00, ci * b10), t11 = fma(si, b01, ci * b11);
-                    e00 = fma(t00, cj, -(t01 * sj)); e01 = fma(t00, sj, t01 * cj);
-                    e10 = fma(t10, cj, -(t11 * sj)); e11 = fma(t10, sj, t11 * cj);
-                } else if (kind == 1) {
-                    const int pq = s_pp[i], qq = s_qq[i];
-                    const double app = AT(pq, pq), aqq = AT(qq, qq), apq = AT(qq, pq);
-                    AT(pq, pq) = fma(-s_tn[i], apq, app);
-                    AT(qq, qq) = fma(s_tn[i], apq, aqq);
-                    if (apq != 0.0) AT(qq, pq) = 0.0;
-                } else {
-                    const int k = jk;
-                    const double s = s_sn[i];
-                    if (s == 0.0) continue;                 // identity rotation: the V row pair is unchanged
-                    const int pq = s_pp[i], qq = s_qq[i];
-                    const double c = s_cs[i];
-                    const double vp = sVt[pq * n + k], vq = sVt[qq * n + k];
-                    sVt[pq * n + k] = fma(c, vp, -(s * vq));
-                    sVt[qq * n + k] = fma(s, vp, c * vq);
+                    for (int u = 0; u < 2; ++u) {   // V <- V J: four rows of V^T, a 16-byte pair of columns (one item at a time: registers)
+                        const int vi = u ? vitem[1] : vitem[0];
+                        if (vi < 0) continue;
+                        const int Q = vi & 0xff, kp = vi >> 8;
+                        if (!qf[Q]) continue;
+                        v_item(Q, kp, (ez >> (16 * u)) & 0xffffu, first, cs);
+                    }
                 }
+                // wavefront 0: the next pass's parameters, from what it has just written (its lanes < n / 2 carry their quadruple's blocks in w6)
+                if (tid < 2 * mq && T + 1 < npass) param_phase(T < 0 ? ez : qnz, T < 0, par ^ 1, sweep);
+                __syncthreads();
+                SQ_STAMP(3);   // one pass (one barrier)
+                if constexpr (PROF) { if (tid == 0 && T >= 0) sacc[5] += 2; }   // rounds
+                par ^= 1;
             }
-            __syncthreads();
-            SQ_STAMP(3);   // rotation phase + barrier
-        }
+        } else {
+            // ======== generated passes (kQuadGen; L = 50 runs <104, 1024>, one workgroup per CU) ========
+            // One barrier per pass, as in the table path: wavefront 0 (and 1) rotate the critical blocks first, then wavefront 0 goes on to the
+            // parameters of the NEXT pass (two rounds of sqrt / div / sqrt chains on the diagonal 4 x 4 blocks in LDS: ~1 us, the longest thing in
+            // a pass) while the other wavefronts do the rest of the blocks and the V items.  Critical blocks beyond wavefront 0's sixteen are
+            // wavefront 1's: it raises s_pass_flag after writing them and wavefront 0 waits for that before it reads the pivots.
+            const int mq = nj >> 2;
+            const bool crit_in_w1 = 4 * mq > 64;
+            par ^= 1;   // the parameters of pass 0 were formed beside the convergence scan
+#pragma unroll 1
+            for (int T = 0; T < npass; ++T) {
+                {
+                    const bool first = T == 0;
+                    const double2* const cs = s_csn + par * 3 * MMAX;
+                    const int* const qf = s_qflag + par * MQ;
+#pragma unroll
+                    for (int ub = 0; ub < QNB; ++ub) {
+                        const int bd = qb_desc[ub];   // block (I, J), I > J: I << 8 | J
+                        if (bd < 0) continue;
+                        const int I = bd >> 8, J = bd & 0xff;
+                        if (!(qf[I] | qf[J])) continue;   // (the same for the four lanes of the block)
+                        const int li = (tid >> 1) & 1, lj = tid & 1, si = 2 * I + li, sj = 2 * J + lj;
+                        const unsigned xi = (unsigned)s_xy[par * MQ + I], xj = (unsigned)s_xy[par * MQ + J];
+                        // the blocks (two consecutive indices each) behind the lane's rows and columns; an element (r, c) of the packed lower triangle sits
+                        // at tri(max) + min, and which of r, c is larger is a property of the two BLOCKS (four comparisons for all twelve elements)
+                        const int bX = (int)(xi & 0xffu), bY = (int)(xi >> 8), dX = (int)(xj & 0xffu), dY = (int)(xj >> 8);
+                        auto off = [&](const int r, const int c, const bool r_gt_c) -> unsigned {   // byte offset of A(r, c)
+                            const int hi = r_gt_c ? r : c, lo = r_gt_c ? c : r;
+                            return (unsigned)(4 * hi * (hi + 1) + 8 * lo);
+                        };
+                        const bool gXX = bX > dX, gXY = bX > dY, gYX = bY > dX, gYY = bY > dY;
+                        if (first) {   // the in-block round: rows (2 i, 2 i + 1) x columns (2 j, 2 j + 1) of the block
+                            const int r0 = 2 * (li ? bY : bX), c0 = 2 * (lj ? dY : dX);
+                            const bool g = li ? (lj ? gYY : gYX) : (lj ? gXY : gXX);
+                            const unsigned a00 = off(r0, c0, g), a01 = off(r0, c0 + 1, g), a10 = off(r0 + 1, c0, g), a11 = off(r0 + 1, c0 + 1, g);
+                            double b00 = ldA(a00), b01 = ldA(a01), b10 = ldA(a10), b11 = ldA(a11);
+                            rot_block(b00, b01, b10, b11, cs[si], cs[sj]);
+                            stA(a00, b00); stA(a01, b01); stA(a10, b10); stA(a11, b11);
+                            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the lanes of the block read each other's results below
+                        }
+                        const int rA = 2 * bX + li, rB = 2 * bY + li, cA = 2 * dX + lj, cB = 2 * dY + lj;
+                        double e00 = ldA(off(rA, cA, gXX)), e01 = ldA(off(rA, cB, gXY)), e10 = ldA(off(rB, cA, gYX)), e11 = ldA(off(rB, cB, gYY));
+                        rot_block(e00, e01, e10, e11, cs[MMAX + si], cs[MMAX + sj]);
+                        e01 = dpp_quad<0xB1>(e01); e10 = dpp_quad<0x4E>(e10); e11 = dpp_quad<0x1B>(e11);   // rows (i, i+2) x columns (j, j+2) -> (i, 3-i) x (j, 3-j)
+                        rot_block(e00, e01, e10, e11, cs[2 * MMAX + si], cs[2 * MMAX + sj]);
+                        const int rC = 2 * bY + 1 - li, cC = 2 * dY + 1 - lj;
+                        stA(off(rA, cA, gXX), e00); stA(off(rA, cC, gXY), e01); stA(off(rC, cA, gYX), e10); stA(off(rC, cC, gYY), e11);
+                    }
+                    if (crit_in_w1 && tid >= 64 && tid < 128) {   // wavefront 1: its critical blocks are written (a wavefront's LDS accesses execute in order)
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                        if (tid == 64) *reinterpret_cast<volatile int*>(&s_pass_flag) = pass_seq;
+                    }
+                    if (tid >= VT0) {
+#pragma unroll
+                        for (int u = 0; u < QNV; ++u) {
+                            const int vd = qv_desc[u];   // quadruple | pair of columns << 8
+                            if (vd < 0) continue;
+                            const int Q = vd & 0xff;
+                            if (!qf[Q]) continue;
+                            v_item(Q, vd >> 8, (unsigned)s_xy[par * MQ + Q], first, cs);
+                        }
+                    }
+                }
+                if (tid < 64 && T + 1 < npass) {   // wavefront 0: the next pass's parameters, from what the critical lanes have just written
+                    if (crit_in_w1) {
+                        while (*reinterpret_cast<volatile int*>(&s_pass_flag) != pass_seq) __builtin_amdgcn_s_sleep(1);
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                    }
+                    if (tid < 2 * mq) {
+                        int X, Y;
+                        rr_pair(tid >> 1, T + 1, mj, X, Y);
+                        const unsigned xy = (unsigned)X | ((unsigned)Y << 8);
+                        if (!(tid & 1)) s_xy[(par ^ 1) * MQ + (tid >> 1)] = (int)xy;
+                        param_phase(xy, false, par ^ 1, sweep);
+                    }
+                }
+                __syncthreads();
+                SQ_STAMP(3);   // one pass (one barrier)
+                if constexpr (PROF) { if (tid == 0) sacc[5] += 2; }   // rounds
+                par ^= 1;
+                pass_seq += 1;
+            }
         }
     }
     if (!converged) {
@@ -899,7 +753,7 @@ __global__ __launch_bounds__(TPB) void ukf_chol_kernel(const UkfStepParams p) {
     const int M = p.M[b];
     const int n = 4 + 2 * M, nt = n * (n + 1) / 2;
     const double* __restrict__ Pb = p.P + (size_t)b * p.pstride;
-    const double scale = (double)((float)(2 * M + 4) / (1 - kW0));   // ukf.cpp:114, evaluated in float, as ukf_sqrt_kernel
+    const double scale = (double)((float)(2 * M + 4) / (1 - kUkfW0));   // ukf.cpp:114, evaluated in float, as ukf_sqrt_kernel
 #pragma unroll 4
     for (int e = tid; e < nt; e += TPB) {
         int r = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);   // row of packed index e, corrected for rounding
@@ -1088,8 +942,8 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 128 && !PROF) ? SLAM_UKF
     UKF_STAMP(2);
     const int n_upd = s_misc[1], n_insq = s_misc[2];
 
-    const double w0 = (double)kW0;
-    const double wi = (double)((1 - kW0) / (2 * n));   // float arithmetic (ukf.cpp:174-175)
+    const double w0 = (double)kUkfW0;
+    const double wi = (double)((1 - kUkfW0) / (2 * n));   // float arithmetic (ukf.cpp:174-175)
     auto xpred_elem = [&](int r, int i) -> double {    // X_pred(r, i)
         if (r < 4) return sX4[r * ns + i];
         if (i == 0) return s_xt[r];
@@ -1182,7 +1036,7 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 128 && !PROF) ? SLAM_UKF
                     S[0] = S[0] + a0 * d0; S[1] = S[1] + a0 * d1; S[2] = S[2] + a1 * d0; S[3] = S[3] + a1 * d1;
                 }
                 S[0] = S[0] + nz.W00; S[1] = S[1] + 0.0; S[2] = S[2] + 0.0; S[3] = S[3] + nz.W11;
-                if (!inv2x2_lu_ukf(S, Si)) s_misc[4] = 1;
+                if (!inv2x2_lu(S, Si)) s_misc[4] = 1;
                 s_sc[5] = z0;
                 s_sc[6] = S[0]; s_sc[7] = S[1]; s_sc[8] = S[2]; s_sc[9] = S[3];
                 s_sc[10] = Si[0]; s_sc[11] = Si[1]; s_sc[12] = Si[2]; s_sc[13] = Si[3];
@@ -1428,16 +1282,9 @@ __global__ __launch_bounds__(TPB, (NMAX == 44 && TPB == 128 && !PROF) ? SLAM_UKF
 #undef UKF_STAMP
 }
 
-// Tuning: threads per instance.  At BASELINE's batch of 4096 only 16 instances share a CU, so wide workgroups win
-// (measured: n<=44 256 threads, n<=104 1024 threads); env SLAM_UKF_TPB = <sqrt threads>*10000 + <step threads> overrides (tools/gpu_ukf_time.py).
-static int env_tpb(int which, int dflt) {
-    const char* e = getenv("SLAM_UKF_TPB");
-    if (!e) return dflt;
-    const int v = atoi(e);
-    const int t = which == 0 ? v / 10000 : v % 10000;
-    return t > 0 ? t : dflt;
-}
-
+// Threads per instance: at a batch of 4096 only 16 instances share a CU, so wide workgroups win (measured: n <= 44 256 threads for the
+// sqrt kernel and 128 for the step kernel, n <= 104 1024 and 512).  The library holds these geometries only, as for the EKF; trying another
+// thread count is an edit of the launcher (and, for the sqrt kernel, within its two pair-block items per thread).
 hipError_t launch_ukf_sqrt(const UkfStepParams& p, hipStream_t stream) {
     const int nmax = 4 + 2 * p.L_max;
     if (p.chol_ok != nullptr) {   // Cholesky mode: the factor first; the eigen kernel below then only runs the instances it refused
@@ -1448,24 +1295,12 @@ hipError_t launch_ukf_sqrt(const UkfStepParams& p, hipStream_t stream) {
         if (e != hipSuccess) return e;
     }
     if (nmax <= 44) {
-        switch (env_tpb(0, 256)) {
-            case 128: hipLaunchKernelGGL((ukf_sqrt_kernel<44, 128>), dim3(p.b_cnt), dim3(128), 0, stream, p); break;
-            case 64: hipLaunchKernelGGL((ukf_sqrt_kernel<44, 64>), dim3(p.b_cnt), dim3(64), 0, stream, p); break;
-            default:
-                if (p.quad_tab == nullptr) return hipErrorInvalidValue;   // <44, 256> takes its operand addresses from the pass table
-                if (p.prof) hipLaunchKernelGGL((ukf_sqrt_kernel<44, 256, true>), dim3(p.b_cnt), dim3(256), 0, stream, p);
-                else hipLaunchKernelGGL((ukf_sqrt_kernel<44, 256>), dim3(p.b_cnt), dim3(256), 0, stream, p);
-                break;
-        }
+        if (p.quad_tab == nullptr) return hipErrorInvalidValue;   // <44, 256> takes its operand addresses from the pass table
+        if (p.prof) hipLaunchKernelGGL((ukf_sqrt_kernel<44, 256, true>), dim3(p.b_cnt), dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((ukf_sqrt_kernel<44, 256>), dim3(p.b_cnt), dim3(256), 0, stream, p);
     } else if (nmax <= 104) {
-        switch (env_tpb(0, 1024)) {
-            case 512: hipLaunchKernelGGL((ukf_sqrt_kernel<104, 512>), dim3(p.b_cnt), dim3(512), 0, stream, p); break;
-            case 256: hipLaunchKernelGGL((ukf_sqrt_kernel<104, 256>), dim3(p.b_cnt), dim3(256), 0, stream, p); break;
-            default:
-                if (p.prof) hipLaunchKernelGGL((ukf_sqrt_kernel<104, 1024, true>), dim3(p.b_cnt), dim3(1024), 0, stream, p);
-                else hipLaunchKernelGGL((ukf_sqrt_kernel<104, 1024>), dim3(p.b_cnt), dim3(1024), 0, stream, p);
-                break;
-        }
+        if (p.prof) hipLaunchKernelGGL((ukf_sqrt_kernel<104, 1024, true>), dim3(p.b_cnt), dim3(1024), 0, stream, p);
+        else hipLaunchKernelGGL((ukf_sqrt_kernel<104, 1024>), dim3(p.b_cnt), dim3(1024), 0, stream, p);
     } else {
         return launch_ukf_big_sqrt(p, stream);   // every n x n object in HBM / L2 (ukf_big_kernel.hip)
     }
@@ -1485,33 +1320,21 @@ hipError_t launch_ukf_step(const UkfStepParams& p, hipStream_t stream) {
         q.long_mode = 2;                     // ... and the streamed kernel: the others
         return launch_ukf_big_step(q, stream);
     }
-    if (nmax <= 44) {
-        switch (env_tpb(1, 128)) {
-            case 64: hipLaunchKernelGGL((ukf_step_kernel<44, 64, 8>), dim3(p.b_cnt), dim3(64), 0, stream, p); break;
-            case 256: hipLaunchKernelGGL((ukf_step_kernel<44, 256, 8>), dim3(p.b_cnt), dim3(256), 0, stream, p); break;
-            case 192: hipLaunchKernelGGL((ukf_step_kernel<44, 192, 8>), dim3(p.b_cnt), dim3(192), 0, stream, p); break;   // one wavefront per tile row of the covariance
-            default:   // measured best
-                if (p.prof) hipLaunchKernelGGL((ukf_step_kernel<44, 128, 8, true>), dim3(p.b_cnt), dim3(128), 0, stream, p);
-                // KU = 3 updates kept for one pass over P (round 4; it was 8: 33 KB of LDS and 188 VGPRs = four workgroups per CU; 3: 26 KB, 155 =
-                // six; a message with more than three detections of mapped landmarks takes further passes, P back from HBM): 4.69 -> 4.92 M
-                // steps/s at L = 20 (KU = 4: 4.74, KU = 2: 4.74 - the mean is 1.3 - 2 detections per message)
+    if (nmax <= 44) {   // 128 threads: measured best
+        if (p.prof) hipLaunchKernelGGL((ukf_step_kernel<44, 128, 8, true>), dim3(p.b_cnt), dim3(128), 0, stream, p);
+        // KU = 3 updates kept for one pass over P (round 4; it was 8: 33 KB of LDS and 188 VGPRs = four workgroups per CU; 3: 26 KB, 155 =
+        // six; a message with more than three detections of mapped landmarks takes further passes, P back from HBM): 4.69 -> 4.92 M
+        // steps/s at L = 20 (KU = 4: 4.74, KU = 2: 4.74 - the mean is 1.3 - 2 detections per message)
 #ifndef SLAM_UKF_STEP_KU
 #define SLAM_UKF_STEP_KU 3
 #endif
-                else hipLaunchKernelGGL((ukf_step_kernel<44, 128, SLAM_UKF_STEP_KU>), dim3(p.b_cnt), dim3(128), 0, stream, p);
-                break;
-        }
+        else hipLaunchKernelGGL((ukf_step_kernel<44, 128, SLAM_UKF_STEP_KU>), dim3(p.b_cnt), dim3(128), 0, stream, p);
     } else if (nmax <= 104) {
         // 512 threads (220 VGPRs) since round 4: with 1024 the compiler has 128 VGPRs and spills 82 of them; 345 -> 350 k steps/s at L = 50
-        // once the sqrt kernel's passes left the step kernel a quarter of the step (1024 had measured best against the round-3 sqrt kernel)
-        switch (p.prof ? 1024 : env_tpb(1, 512)) {
-            case 256: hipLaunchKernelGGL((ukf_step_kernel<104, 256, 8>), dim3(p.b_cnt), dim3(256), 0, stream, p); break;
-            case 1024:
-                if (p.prof) hipLaunchKernelGGL((ukf_step_kernel<104, 1024, 8, true>), dim3(p.b_cnt), dim3(1024), 0, stream, p);
-                else hipLaunchKernelGGL((ukf_step_kernel<104, 1024, 8>), dim3(p.b_cnt), dim3(1024), 0, stream, p);
-                break;
-            default: hipLaunchKernelGGL((ukf_step_kernel<104, 512, 8>), dim3(p.b_cnt), dim3(512), 0, stream, p); break;
-        }
+        // once the sqrt kernel's passes left the step kernel a quarter of the step (1024 had measured best against the round-3 sqrt kernel).
+        // The profiling build still has 1024 threads, NOT the production geometry: its phase timers describe that build.
+        if (p.prof) hipLaunchKernelGGL((ukf_step_kernel<104, 1024, 8, true>), dim3(p.b_cnt), dim3(1024), 0, stream, p);
+        else hipLaunchKernelGGL((ukf_step_kernel<104, 512, 8>), dim3(p.b_cnt), dim3(512), 0, stream, p);
     } else {
         return launch_ukf_big_step(p, stream);   // every n x n object in HBM / L2 (ukf_big_kernel.hip)
     }

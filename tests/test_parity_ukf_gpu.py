@@ -68,14 +68,11 @@ def test_ukf_sim_step_parity(S, oracle, L, T, B):
     f.close()
 
 
-@pytest.mark.parametrize("code,L", [(0, 20), (1280256, 20), (640064, 20), (0, 50), (5120512, 50), (2560256, 50)])
-def test_ukf_growing_state_walks_padded_sizes_bit_exact(S, oracle, monkeypatch, code, L):
+@pytest.mark.parametrize("L", [20, 50])
+def test_ukf_growing_state_walks_padded_sizes_bit_exact(S, oracle, L):
     """A map discovered landmark by landmark: the state passes through the sizes n = 2 (mod 4), which the sqrt kernels of the LDS classes
-    (and the oracle) pad by two zero rows to walk the quadruple schedule - in every thread-count variant (pass table, passes without the
-    table, round by round).  code 0 = the defaults."""
+    (and the oracle) pad by two zero rows to walk the quadruple schedule - the pass table at L = 20, the generated passes at L = 50."""
     from live_ekf_slam_amd.scenario import make_scenario
-    if code:
-        monkeypatch.setenv("SLAM_UKF_TPB", str(code))
     T, B = 90, 4
     lm, cmds = make_scenario(91, L, T)
     f = S.BatchedUKF(B, L).readParams(); f.set_map(lm); f.set_seed(5); f.set_instance_offset(3); f.init(0, 0, 0)
@@ -92,19 +89,11 @@ def test_ukf_growing_state_walks_padded_sizes_bit_exact(S, oracle, monkeypatch, 
         _eq(f.get_state(b), dict(M=m, ids=r["ids"][b, :m], x=r["x"][b, :n], P=r["P"][b, :n * n].reshape(n, n)))
 
 
-@pytest.mark.parametrize("code,L,T,B", [
-    (1280256, 20, 70, 16),   # sqrt 128 threads (generic rotation path), step 256 threads (2 x 4 covariance tiles)
-    (640064, 20, 70, 12),    # one wavefront per instance in both kernels
-    (5120512, 50, 50, 8),    # n = 104: sqrt 512, step 512 (the step kernel's default since round 4: 220 VGPRs, no spill)
-    (10241024, 50, 50, 8),   # n = 104: sqrt 1024 (the default), step 1024 (128 VGPRs, 82 spilled; the default until round 4)
-    (2560256, 50, 50, 6),    # n = 104: sqrt 256 (256 VGPRs), step 256
-])
-def test_ukf_thread_count_variants_bit_exact(S, oracle, monkeypatch, code, L, T, B):
-    """The tuning variants behind SLAM_UKF_TPB = <sqrt threads> * 10000 + <step threads> are separate instantiations of the
-    same templates (other tile shapes, other item-to-thread maps, other register budgets): every one must give the
-    oracle's bits.  A wide first step maps all L landmarks, so the L = 50 cases run at the full state size n = 104."""
+@pytest.mark.parametrize("L,T,B", [(20, 70, 16), (50, 50, 8)])
+def test_ukf_full_state_size_bit_exact(S, oracle, L, T, B):
+    """A wide first step maps all L landmarks, so every later step runs both kernels of the size class at its full state size: n = 44
+    (sqrt 256 threads with the pass table, step 128) and n = 104 (sqrt 1024 threads with generated passes, step 512)."""
     from live_ekf_slam_amd.scenario import make_scenario
-    monkeypatch.setenv("SLAM_UKF_TPB", str(code))
     lm, cmds = make_scenario(77, L, T)
     vis = np.tile([3.0, -1.57, 1.57], (T, 1)); vis[0] = [1e9, -4.0, 4.0]
     f = S.BatchedUKF(B, L).readParams(); f.set_map(lm); f.set_seed(3); f.set_instance_offset(11); f.init(0, 0, 0)

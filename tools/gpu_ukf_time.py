@@ -15,7 +15,7 @@ for L, B, steps in cfgs:
     f.run_sim(cmds[1:20]); f.sync()
     t0 = time.time(); f.run_sim(cmds[20:20 + steps]); f.sync(); dt = time.time() - t0
     n = 4 + 2 * L
-    print(f"UKF tpb={os.environ.get('SLAM_UKF_TPB','-')} L={L} B={B}: {dt / steps * 1e3:.3f} ms/step  {B * steps / dt / 1e3:.1f} k steps/s  M mean {f.landmark_counts().mean():.1f} flags {np.unique(f.status())} err {f.error_stats().mean():.4f}", flush=True)
+    print(f"UKF L={L} B={B}: {dt / steps * 1e3:.3f} ms/step  {B * steps / dt / 1e3:.1f} k steps/s  M mean {f.landmark_counts().mean():.1f} flags {np.unique(f.status())} err {f.error_stats().mean():.4f}", flush=True)
     f.close()
 if len(sys.argv) > 2: sys.exit(0)
 vis = np.tile([3.0, -1.57, 1.57], (60, 1)); vis[0] = [1e9, -4.0, 4.0]
