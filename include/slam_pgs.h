@@ -117,7 +117,9 @@ int pgs_run_sim_each(pgs_handle* h, const float* cmds, int T);
 int pgs_solve(pgs_handle* h);
 /* The solve splits the batch into `groups` contiguous ranges that run their LM loops on separate HIP streams (the
  * latency-bound phases of one group overlap the bandwidth-bound phases of another); results do not depend on it.
- * 0 = automatic (2 from 512 instances, else 1; 4 groups measured best in a process without other HIP streams). */
+ * 0 = automatic: 2 from 128 instances on, 1 below (SLAM_PGS_GROUPS sets the default).  Whatever is asked for, a solve runs at most 16
+ * groups and at most one per instance, a profiled solve (pgs_set_profiling) one; the ticks of pgs_run_sim_every_iteration[_each] run one
+ * while the setting is 0.  Group g of G owns the instances [g per, min(batch, (g + 1) per)), per = ceil(batch / G). */
 int pgs_set_groups(pgs_handle* h, int groups);
 /* Streaming solve (round 6): the handle holds `batch` graphs but at most `slots` of them are IN FLIGHT (0 = lockstep, all of them from
  * the first trial on; SLAM_PGS_SLOTS sets the default).  The others wait; when a graph converges the device-side decide step hands

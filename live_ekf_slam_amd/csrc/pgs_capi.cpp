@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "capi_internal.h"
+#include "host/pgs_schedule.h"
 #include "pgs_kernel.h"
 
 #define fail slam_internal_fail
@@ -21,7 +22,7 @@
 struct pgs_handle {
     slam_config cfg;
     int B, N_max, L_max, KP, LD, device;
-    int timestep = 0;
+    int timestep = 0;                          // p.N = timestep + 1 at every launch: written by pgs_init[_each] and advance() only, each with p.N
     bool inited = false;
     bool solved = false;                       // a pgs_solve has run since pgs_init: `result` exists
     hipStream_t stream = nullptr;
@@ -45,36 +46,29 @@ struct pgs_handle {
     DevBuf<float> dpose_each; DevBuf<double> dtruth_each;   // pgs_init_each's staging, [B][3] each
     DevBuf<float> dmeas; DevBuf<int32_t> dcount; DevBuf<double> dsec;   // pgs_update's staging
     DevBuf<double> dout;
-    int max_trials = 400;
-    int lanes = 4;                             // slots per instance for speculative lambda lanes (SLAM_PGS_LANES, 1 = off)
-    int lanes_switch_all = 16;                 // ... from which down ALL lanes are used (SLAM_PGS_LANES_SWITCH_ALL)
-    int lanes_switch = 64;                     // active instances (of the whole batch) from which down the lanes are used (SLAM_PGS_LANES_SWITCH)
-    // solve groups: the batch is split into `groups` contiguous ranges whose LM loops run on their own streams, so
-    // the latency-bound phases of one group overlap the bandwidth-bound phases of another (0 = choose from the batch)
-    int groups = 0;
+    // The tuning values (host/pgs_schedule.h), read from the environment by pgs_create.  Of these, `lanes` may shrink there (the lanes multiply
+    // the LM work space), and `groups` / `slots` follow pgs_set_groups / pgs_set_slots.
+    //  * solve groups: the batch is split into contiguous ranges whose LM loops run on their own streams, so the latency-bound phases of one
+    //    group overlap the bandwidth-bound phases of another;
+    //  * streaming (pgs_kernel.h "streaming"): at most `slots` graphs of the batch are in flight (0 = lockstep: all of them), split over the
+    //    solve groups; trials are enqueued `stream_depth` ahead of the host's reading of their counters.
+    slam_host::PgsTuning tune;
     std::vector<hipStream_t> gstreams;
     std::vector<hipEvent_t> gevents;
     PinnedDefaultBuf<int32_t> h_active;        // pinned host: per-group active counts
-    // streaming (round 6, pgs_kernel.h "streaming"): at most `slots` graphs of the batch are in flight (0 = lockstep: all of them), split over
-    // the solve groups; trials are enqueued `stream_depth` ahead of the host's reading of their counters
-    int slots = 0, stream_depth = 3;
-    static constexpr int kRing = 8, kMaxGroups = 16;
-    DevBuf<int32_t> d_cnt;                     // device [kMaxGroups][2][8]: the counter blocks, ping-pong by trial parity
-    DevBuf<int32_t> d_wait;                    // device [kMaxGroups]: the groups' wait cursors
-    PinnedDefaultBuf<int32_t> h_ring;          // pinned host [kMaxGroups][kRing][8]
-    std::vector<hipEvent_t> ring_events;       // [kMaxGroups][kRing]
+    DevBuf<int32_t> d_cnt;                     // device [kPgsMaxGroups][2][8]: the counter blocks, ping-pong by trial parity
+    DevBuf<int32_t> d_wait;                    // device [kPgsMaxGroups]: the groups' wait cursors
+    PinnedDefaultBuf<int32_t> h_ring;          // pinned host [kPgsMaxGroups][kPgsRing][8]
+    std::vector<hipEvent_t> ring_events;       // [kPgsMaxGroups][kPgsRing]
     std::vector<std::vector<int32_t>> timeline;   // per group: slots that ran in every trial of the last solve
     DevBuf<int32_t> d_tick;                    // [B][2] LM iterations / trials summed over the ticks of pgs_run_sim_every_iteration
     DevBuf<double> d_tick_flop;                // [B][2] algorithmic FLOP (SYRK | Cholesky) of the same
     double iter_ms[4] = {0, 0, 0, 0};
-    bool host_prof = false;                    // SLAM_PGS_HOST_PROF: host clock spent enqueuing trials / waiting for their counters (stderr, every-iteration runs)
-    double host_launch_ms = 0.0, host_wait_ms = 0.0;
+    double host_launch_ms = 0.0, host_wait_ms = 0.0;   // tune.host_prof: host clock spent enqueuing trials / waiting for their counters (stderr, every-iteration runs)
     long long iter_trials = 0;
-    bool trace = false;                       // SLAM_PGS_TRACE: print the active-instance count after every trial
     double path_ms[3] = {0.0, 0.0, 0.0};      // profiled solve: ms in the separate SYRK launches / in the fused chain + SYRK launches / in the segmented path's SYRK launches
-    int seg_len = 32;                         // SLAM_PGS_SEG: poses per segment of the segmented elimination (pgs_seg_impl.h), 0 = the sequential chain of rounds 1-4
     bool seg_ok = false;                      // this solve runs the segmented elimination (decided in pgs_solve from the plan)
-    // Round 6: the segment length is chosen PER SOLVE from {seg_len, seg_len / 2, ... >= 8}: the longest whose every segment sees at most
+    // Round 6: the segment length is chosen PER SOLVE from {tune.seg_len, tune.seg_len / 2, ... >= 8}: the longest whose every segment sees at most
     // kPgsSegMaxLm landmarks (a wide sensor on a dense map overflowed 32-pose segments and the whole solve fell back to the sequential chain,
     // 2.3 x slower).  seg_cur: where the next solve's search starts (only goes down while the graph grows; pgs_init resets it); seg_alloc: the
     // length the segment-count-dependent arrays are sized for (re-made on demand, resize_segments); seg_used: the last solve's.
@@ -82,9 +76,6 @@ struct pgs_handle {
     bool fused_ok = false;                    // this solve's graphs fit the fused kernel (decided in pgs_solve from max M)
     bool syrk_inst_ok = false;                // ... and the instance-resident SYRK (its kPgsSyrkInstTiles tiles hold every lower triangle)
     int cus = 256;                            // compute units of the device
-    bool use_list = true;                     // SLAM_PGS_LIST=0: full-size grids, inactive workgroups return (the round-2 launch shape)
-    int fused_mode = -1;                      // SLAM_PGS_FUSED: 0 = chain and SYRK as two launches, -1 (default) = fused when the tiles fit
-    int syrk_inst_switch = 100;               // SLAM_PGS_SYRK_INST_SWITCH: running slots from which the instance-resident SYRK runs (else the tile kernel)
     int last_trials = 0;
     bool profiling = false;                  // per-kernel hipEvent timing of pgs_solve (pgs_set_profiling)
     std::vector<hipEvent_t> events;
@@ -129,8 +120,8 @@ void seg_geometry(const pgs_handle* h, slam::PgsParams& g, int SL) {
 // lanes get copies of it), the segments' outputs and Gram matrices (segT: if with_segT), and Y.  Nothing in them outlives a solve.
 int alloc_seg_arrays(pgs_handle* h, const slam::PgsParams& g, bool with_segT, std::vector<pgs_handle::Array>& set) {
     slam::PgsParams& p = h->p;
-    const size_t S = (size_t)h->B * h->lanes, L = (size_t)h->L_max, G = (size_t)g.nseg_max;
-    if (h->seg_len > 0) {
+    const size_t S = (size_t)h->B * h->tune.lanes, L = (size_t)h->L_max, G = (size_t)g.nseg_max;
+    if (h->tune.seg_len > 0) {
         const size_t NB = (size_t)slam::seg_nb1(h->L_max);
         TRY(add_array(set, &p.seg_ncol, S * G, G)); TRY(add_array(set, &p.seg_lm, S * G * L, G * L)); TRY(add_array(set, &p.seg_inv, S * G * L, G * L));
         TRY(add_array(set, &p.seg_evt, S * G * L, G * L)); TRY(add_array(set, &p.seg_blk, S * G * NB, G * NB)); TRY(add_array(set, &p.sep_evt, S * G * L, G * L));
@@ -144,8 +135,8 @@ int alloc_seg_arrays(pgs_handle* h, const slam::PgsParams& g, bool with_segT, st
 // the segments' Gram matrices: [slots][nseg_max][seg_tld^2] doubles, only when a solve runs the segmented order (128 x 128 per
 // segment whatever L_max, allocated also for handles whose every solve takes the sequential chain)
 int ensure_segT(pgs_handle* h) {
-    if (h->p.segT || h->seg_len <= 0) return SLAM_OK;
-    const size_t S = (size_t)h->B * h->lanes;
+    if (h->p.segT || h->tune.seg_len <= 0) return SLAM_OK;
+    const size_t S = (size_t)h->B * h->tune.lanes;
     TRY(add_array(h->seg_arrays, &h->p.segT, S * (size_t)h->p.nseg_max * (size_t)h->p.seg_tld * h->p.seg_tld));
     bind_arrays(h->seg_arrays);
     return SLAM_OK;
@@ -186,20 +177,8 @@ int pgs_create(const slam_config* cfg, int batch, int N_max, int L_max, int k_pe
     h->cfg = *cfg; h->B = batch; h->N_max = N_max; h->L_max = L_max; h->KP = k_per_pose; h->device = device;
     { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) h->cus = cu; }
     h->LD = round_up(2 * L_max + 1, 64);
-    if (const char* e = getenv("SLAM_PGS_MAX_TRIALS")) h->max_trials = atoi(e) > 0 ? atoi(e) : h->max_trials;
-    if (const char* e = getenv("SLAM_PGS_LANES")) h->lanes = atoi(e) >= 1 && atoi(e) <= 8 ? atoi(e) : h->lanes;
-    if (const char* e = getenv("SLAM_PGS_LANES_SWITCH")) h->lanes_switch = atoi(e);
-    if (const char* e = getenv("SLAM_PGS_LANES_SWITCH_ALL")) h->lanes_switch_all = atoi(e);
-    if (const char* e = getenv("SLAM_PGS_SYRK_INST_SWITCH")) h->syrk_inst_switch = atoi(e);
-    h->trace = getenv("SLAM_PGS_TRACE") != nullptr;
-    h->host_prof = getenv("SLAM_PGS_HOST_PROF") != nullptr;
-    if (const char* e = getenv("SLAM_PGS_FUSED")) h->fused_mode = atoi(e);
-    if (const char* e = getenv("SLAM_PGS_SEG")) { const int v = atoi(e); h->seg_len = v <= 0 ? 0 : (v < 2 ? 2 : (v > slam::kPgsSegMaxLen ? slam::kPgsSegMaxLen : v)); }
-    h->seg_cur = h->seg_alloc = h->seg_len;
-    if (const char* e = getenv("SLAM_PGS_LIST")) h->use_list = atoi(e) != 0;
-    if (const char* e = getenv("SLAM_PGS_GROUPS")) h->groups = atoi(e);
-    if (const char* e = getenv("SLAM_PGS_SLOTS")) h->slots = atoi(e) > 0 ? atoi(e) : 0;
-    if (const char* e = getenv("SLAM_PGS_STREAM_DEPTH")) h->stream_depth = atoi(e) >= 1 && atoi(e) < pgs_handle::kRing ? atoi(e) : h->stream_depth;
+    h->tune = slam_host::PgsTuning::from_env();
+    h->seg_cur = h->seg_alloc = h->tune.seg_len;
     hipError_t e = hipStreamCreate(&h->stream);
     if (e != hipSuccess) { delete h; return fail(SLAM_ERR_HIP, "hipStreamCreate -> %s", hipGetErrorString(e)); }
     h->own_stream = true;
@@ -211,15 +190,15 @@ int pgs_create(const slam_config* cfg, int batch, int N_max, int L_max, int k_pe
     // Every per-instance array has `lanes` slots per instance: slot b is instance b, slot j * B + b its j-th lambda lane (a
     // clone that pgs_solve fills from the instance; PgsParams::lanes_max).  Arrays only the instance itself uses keep B slots.
     {   // the lanes multiply the LM work space (Y alone is 3 N_max x LD doubles per slot): keep them within half of the free memory
-        const double nsegx = h->seg_len > 0 ? (double)((N_max - 2) / h->seg_len + 1) : 0.0;
+        const double nsegx = h->tune.seg_len > 0 ? (double)((N_max - 2) / h->tune.seg_len + 1) : 0.0;
         const double per_slot = 8.0 * (((double)round_up(3 * N_max, 4) + 10.0 * nsegx) * h->LD + (double)h->LD * h->LD + (double)K * 29 + (double)N * 51 + (double)L * 12 + nsegx * (48 + (double)round_up(2 * (L_max < slam::kPgsSegMaxLm ? L_max : slam::kPgsSegMaxLm) + 1, 16) * round_up(2 * (L_max < slam::kPgsSegMaxLm ? L_max : slam::kPgsSegMaxLm) + 1, 16))) +
                                 4.0 * ((double)K * 5 + (double)N + (double)L * 6 + nsegx * (4.0 * L + 16));
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-            while (h->lanes > 1 && per_slot * (double)B * h->lanes > 0.5 * (double)free_b) h->lanes -= 1;
+            while (h->tune.lanes > 1 && per_slot * (double)B * h->tune.lanes > 0.5 * (double)free_b) h->tune.lanes -= 1;
     }
-    const size_t S = B * (size_t)h->lanes;
-    p.lanes_max = h->lanes; p.lanes = 1;
+    const size_t S = B * (size_t)h->tune.lanes;
+    p.lanes_max = h->tune.lanes; p.lanes = 1;
     int rc = SLAM_OK;
     auto A = [&](auto** ptr, size_t count) { if (rc == SLAM_OK) rc = add_array(h->arrays, ptr, count); };
     // AC: S slots, and the clones get the instance's content when a solve begins (per-slot element count given)
@@ -238,11 +217,11 @@ int pgs_create(const slam_config* cfg, int batch, int N_max, int L_max, int k_pe
     A(&p.D, S * L * 3); A(&p.gl, S * L * 2); A(&p.Linv, S * N * 6); A(&p.G, S * N * 9);
     // segmented elimination: the segments' contributions to their separators' right-hand sides and the separators' rows of Y live
     // behind the pose rows of Y (pgs_kernel.h: yr_rc, yr_sep)
-    p.seg_len = h->seg_len; p.seg_on = 0; p.syrk_rows = -1; p.syrk_row0 = 0; p.syrk_first = nullptr;
-    p.seg_back_global = getenv("SLAM_PGS_SEG_BACK_GLOBAL") ? atoi(getenv("SLAM_PGS_SEG_BACK_GLOBAL")) : 0;
+    p.seg_len = h->tune.seg_len; p.seg_on = 0; p.syrk_rows = -1; p.syrk_row0 = 0; p.syrk_first = nullptr;
+    p.seg_back_global = h->tune.seg_back_global;
     p.yr_rc = round_up(3 * N_max, 4);
-    seg_geometry(h, p, h->seg_len);
-    if (h->seg_len > 0) {
+    seg_geometry(h, p, h->tune.seg_len);
+    if (h->tune.seg_len > 0) {
         AC(&p.sep_first, L); A(&p.Gs, S * N * 9);
         // (segT, the segments' Gram matrices - the largest of these arrays - is allocated by the first solve that runs the segmented order: ensure_segT)
         p.seg_tld = round_up(2 * (L_max < slam::kPgsSegMaxLm ? L_max : slam::kPgsSegMaxLm) + 1, 16);
@@ -254,7 +233,7 @@ int pgs_create(const slam_config* cfg, int batch, int N_max, int L_max, int k_pe
     A(&p.iters, B); A(&p.trials, B); A(&p.state, S + 1); AC(&p.solve_ok, 1); A(&p.n_active, 64); A(&p.alist, S); A(&p.inst_flop, B); A(&p.work, 3);
     A(&p.nl, B); A(&p.nlin, S); A(&p.nerr, S); A(&p.nok, S);
     D(h->dcount, B); D(h->dsec, B * 3); D(h->dout, B);
-    D(h->d_cnt, (size_t)pgs_handle::kMaxGroups * 16); D(h->d_wait, (size_t)pgs_handle::kMaxGroups);
+    D(h->d_cnt, (size_t)slam_host::kPgsMaxGroups * 16); D(h->d_wait, (size_t)slam_host::kPgsMaxGroups);
     if (getenv("SLAM_PGS_PROF")) { A(&p.prof, S * 24); }   // [S][8] chol phase timers, then [S][2][8] per-workgroup stamps of the fused chain
     if (rc != SLAM_OK) { pgs_destroy(h); return rc; }
     bind_arrays(h->arrays); bind_arrays(h->seg_arrays);
@@ -342,7 +321,7 @@ int pgs_init(pgs_handle* h, float x0, float y0, float yaw0) {
     TRY(check(h));
     h->mg_valid = false;
     h->timestep = 0; h->p.N = 1;
-    h->seg_cur = h->seg_len;
+    h->seg_cur = h->tune.seg_len;
     HIP_TRY(slam::pgs_launch_init(h->p, x0, y0, yaw0, h->stream));
     h->inited = true; h->solved = false;
     return SLAM_OK;
@@ -385,12 +364,37 @@ int put_commands(pgs_handle* h, const float* src, bool src_dev, int T, bool each
     return SLAM_OK;
 }
 
+bool meas_args_ok(const float* meas, const int32_t* count, int k_stride) { return k_stride == 0 || (k_stride > 0 && meas && count); }
+
+// What a call that adds ticks brings: one command per instance (else one for all), commands in device memory (else a host array), a run of
+// the simulator (else one appended tick of messages); kBadMeasArgs: the caller found its measurement arguments unsound (pgs_update_each).
+enum TickFlags : unsigned { kShared = 0, kEach = 1, kDeviceSource = 2, kSim = 4, kBadMeasArgs = 8 };
+
+// What every call that adds T ticks to the graphs does before its own work, in this order: the handle is initialised; a run of the simulator
+// has a map; the commands are there; the measurement arguments are sound; host commands per instance are finite; the T poses fit.  Then the
+// marginals no longer belong to the values and the commands go into place (put_commands).
+int enter_ticks(pgs_handle* h, const char* who, const float* cmds, int T, unsigned flags) {
+    const bool each = flags & kEach, src_dev = flags & kDeviceSource, sim = flags & kSim;
+    if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before %s", who);
+    if (sim && !h->p.map && !h->p.map_each) return fail(SLAM_ERR_STATE, "pgs_set_map%s must be called before %s", each ? " or pgs_set_maps" : "", who);
+    if (sim && (!cmds || T <= 0)) return fail(SLAM_ERR_ARG, "bad command sequence");
+    if (!cmds) return fail(SLAM_ERR_ARG, each ? "cmds is NULL" : "cmd is NULL");
+    if (flags & kBadMeasArgs) return fail(SLAM_ERR_ARG, "bad measurement arguments");
+    if (each && !src_dev && !all_finite_f(cmds, 2 * (size_t)T * h->B)) return fail(SLAM_ERR_ARG, "a command is not finite");
+    if (h->timestep + T >= h->N_max)
+        return sim ? fail(SLAM_ERR_STATE, "timestep %d + %d commands exceed the pose capacity N_max = %d", h->timestep, T, h->N_max)
+                   : fail(SLAM_ERR_STATE, "pose capacity N_max = %d reached", h->N_max);
+    h->mg_valid = false;
+    return put_commands(h, cmds, src_dev, T, each);
+}
+
+// the graphs have T more poses (p.N = timestep + 1 at every launch)
+void advance(pgs_handle* h, int T) { h->timestep += T; h->p.N = h->timestep + 1; }
+
 // updateNaiveVehPoseEstimate + update of one tick on device messages; the tick's commands are in place
 int append_tick(pgs_handle* h, const float* d_meas, const int32_t* d_count, int k_stride, const double* d_sec) {
-    h->p.N = h->timestep + 1;
     HIP_TRY(slam::pgs_launch_append(h->p, d_meas, d_count, k_stride, d_sec, h->stream));
-    h->timestep += 1;
-    h->p.N = h->timestep + 1;
+    advance(h, 1);
     return SLAM_OK;
 }
 
@@ -421,7 +425,7 @@ int pgs_init_each(pgs_handle* h, const float* pose0, const double* truth0) {
     if (truth0) HIP_TRY(hipMemcpyAsync(h->dtruth_each, truth0, sizeof(double) * 3 * B, hipMemcpyHostToDevice, h->stream));
     h->mg_valid = false;
     h->timestep = 0; h->p.N = 1;
-    h->seg_cur = h->seg_len;
+    h->seg_cur = h->tune.seg_len;
     HIP_TRY(slam::pgs_launch_init_each(h->p, h->dpose_each, truth0 ? h->dtruth_each.get() : nullptr, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));   // the host arrays are pageable
     h->inited = true; h->solved = false;
@@ -430,17 +434,13 @@ int pgs_init_each(pgs_handle* h, const float* pose0, const double* truth0) {
 
 int pgs_update_dev(pgs_handle* h, const float cmd[2], const float* d_meas, const int32_t* d_count, int k_stride, const double* d_sec) {
     TRY(check(h));
-    if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_update");
-    if (!cmd) return fail(SLAM_ERR_ARG, "cmd is NULL");
-    if (h->timestep + 1 >= h->N_max) return fail(SLAM_ERR_STATE, "pose capacity N_max = %d reached", h->N_max);
-    h->mg_valid = false;
-    TRY(put_commands(h, cmd, false, 1, false));
+    TRY(enter_ticks(h, "pgs_update", cmd, 1, kShared));
     return append_tick(h, d_meas, d_count, k_stride, d_sec);
 }
 
 int pgs_update(pgs_handle* h, const float cmd[2], const float* meas, const int32_t* count, int k_stride, const double* sec) {
     TRY(check(h));
-    if (k_stride < 0 || (k_stride > 0 && (!meas || !count))) return fail(SLAM_ERR_ARG, "bad measurement arguments");
+    if (!meas_args_ok(meas, count, k_stride)) return fail(SLAM_ERR_ARG, "bad measurement arguments");
     int ks = 1;
     TRY(stage_messages(h, meas, count, k_stride, sec, &ks));
     const int rc = pgs_update_dev(h, cmd, h->dmeas, h->dcount, ks, sec ? h->dsec : nullptr);
@@ -451,23 +451,13 @@ int pgs_update(pgs_handle* h, const float cmd[2], const float* meas, const int32
 
 int pgs_update_each_dev(pgs_handle* h, const float* d_cmds, const float* d_meas, const int32_t* d_count, int k_stride, const double* d_sec) {
     TRY(check(h));
-    if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_update_each");
-    if (!d_cmds) return fail(SLAM_ERR_ARG, "cmds is NULL");
-    if (h->timestep + 1 >= h->N_max) return fail(SLAM_ERR_STATE, "pose capacity N_max = %d reached", h->N_max);
-    TRY(put_commands(h, d_cmds, true, 1, true));
-    h->mg_valid = false;
+    TRY(enter_ticks(h, "pgs_update_each", d_cmds, 1, kEach | kDeviceSource));
     return append_tick(h, d_meas, d_count, k_stride, d_sec);
 }
 
 int pgs_update_each(pgs_handle* h, const float* cmds, const float* meas, const int32_t* count, int k_stride, const double* sec) {
     TRY(check(h));
-    if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_update_each");
-    if (!cmds) return fail(SLAM_ERR_ARG, "cmds is NULL");
-    if (k_stride < 0 || (k_stride > 0 && (!meas || !count))) return fail(SLAM_ERR_ARG, "bad measurement arguments");
-    if (!all_finite_f(cmds, 2 * (size_t)h->B)) return fail(SLAM_ERR_ARG, "a command is not finite");
-    if (h->timestep + 1 >= h->N_max) return fail(SLAM_ERR_STATE, "pose capacity N_max = %d reached", h->N_max);
-    TRY(put_commands(h, cmds, false, 1, true));
-    h->mg_valid = false;
+    TRY(enter_ticks(h, "pgs_update_each", cmds, 1, kEach | (meas_args_ok(meas, count, k_stride) ? 0u : kBadMeasArgs)));
     int ks = 1;
     TRY(stage_messages(h, meas, count, k_stride, sec, &ks));
     const int rc = append_tick(h, h->dmeas, h->dcount, ks, sec ? h->dsec : nullptr);
@@ -475,38 +465,22 @@ int pgs_update_each(pgs_handle* h, const float* cmds, const float* meas, const i
     return rc;
 }
 
-int pgs_run_sim(pgs_handle* h, const float* cmds, int T) {
+namespace {
+
+// T simulator iterations; each: one command per instance and tick - one copy and one transposing launch for the T ticks
+int run_sim(pgs_handle* h, const char* who, const float* cmds, int T, bool each) {
     TRY(check(h));
-    if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_run_sim");
-    if (!h->p.map && !h->p.map_each) return fail(SLAM_ERR_STATE, "pgs_set_map must be called before pgs_run_sim");
-    if (!cmds || T <= 0) return fail(SLAM_ERR_ARG, "bad command sequence");
-    if (h->timestep + T >= h->N_max) return fail(SLAM_ERR_STATE, "timestep %d + %d commands exceed the pose capacity N_max = %d", h->timestep, T, h->N_max);
-    h->mg_valid = false;
-    TRY(put_commands(h, cmds, false, T, false));
-    h->p.N = h->timestep + 1;
+    TRY(enter_ticks(h, who, cmds, T, kSim | (each ? kEach : kShared)));
     HIP_TRY(slam::pgs_launch_run_sim(h->p, T, (uint32_t)h->timestep, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));   // cmds is a pageable host array
-    h->timestep += T;
-    h->p.N = h->timestep + 1;
+    advance(h, T);
     return SLAM_OK;
 }
 
-int pgs_run_sim_each(pgs_handle* h, const float* cmds, int T) {
-    TRY(check(h));
-    if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_run_sim_each");
-    if (!h->p.map && !h->p.map_each) return fail(SLAM_ERR_STATE, "pgs_set_map or pgs_set_maps must be called before pgs_run_sim_each");
-    if (!cmds || T <= 0) return fail(SLAM_ERR_ARG, "bad command sequence");
-    if (!all_finite_f(cmds, 2 * (size_t)T * h->B)) return fail(SLAM_ERR_ARG, "a command is not finite");
-    if (h->timestep + T >= h->N_max) return fail(SLAM_ERR_STATE, "timestep %d + %d commands exceed the pose capacity N_max = %d", h->timestep, T, h->N_max);
-    TRY(put_commands(h, cmds, false, T, true));   // one copy and one transposing launch for the T ticks
-    h->mg_valid = false;
-    h->p.N = h->timestep + 1;
-    HIP_TRY(slam::pgs_launch_run_sim(h->p, T, (uint32_t)h->timestep, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // cmds is a pageable host array
-    h->timestep += T;
-    h->p.N = h->timestep + 1;
-    return SLAM_OK;
-}
+}  // namespace
+
+int pgs_run_sim(pgs_handle* h, const float* cmds, int T) { return run_sim(h, "pgs_run_sim", cmds, T, false); }
+int pgs_run_sim_each(pgs_handle* h, const float* cmds, int T) { return run_sim(h, "pgs_run_sim_each", cmds, T, true); }
 
 namespace {
 
@@ -514,7 +488,7 @@ namespace {
 // event lists, values and scalars - one contiguous copy per array and lane - and start inactive
 int clone_instances(pgs_handle* h, const slam::PgsParams& p, hipStream_t stream, bool slabs = true) {
     const size_t B = (size_t)h->B, off = (size_t)p.b_off, cnt = (size_t)p.b_cnt;
-    for (int j = 1; j < h->lanes; ++j) {
+    for (int j = 1; j < h->tune.lanes; ++j) {
         if (slabs)
             for (const auto* set : {&h->arrays, &h->seg_arrays})
                 for (const pgs_handle::Array& a : *set)
@@ -537,52 +511,54 @@ int clone_listed(pgs_handle* h, const slam::PgsParams& p, int n_list, hipStream_
         }
     slam::PgsParams q = p;
     q.n_list = n_list;
-    HIP_TRY(slam::pgs_launch_clone(q, t, h->lanes, stream));
+    HIP_TRY(slam::pgs_launch_clone(q, t, h->tune.lanes, stream));
     return SLAM_OK;
 }
 
-// lanes the decide kernel of a trial may hand out, from the number of active instances (of the whole batch) before it
-int lanes_for(const pgs_handle* h, int32_t active_hint) {
-    return active_hint <= h->lanes_switch_all ? h->lanes : (active_hint <= h->lanes_switch ? (h->lanes < 2 ? h->lanes : 2) : 1);
-}
+double now_ms() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
 
-// one tryLambda of the instances [p.b_off, p.b_off + p.b_cnt) on `stream`; `lanes` = the most slots any of them runs in this
-// trial (what the previous trial's pgs_decide_kernel reported; 1 for the first)
+// What the host knows after the last trial it has counted, and the next trial starts from: the group's active instances scaled to the whole
+// batch (x G: the lane and kernel rules go by the batch), the most lanes the decide step handed to any of them, the running slots it listed.
+struct LmState { int32_t active, lanes, slots; };
+
+// One solve group of a solve: a contiguous range of the batch whose LM loop runs on its own stream, driven by its own host thread.
+struct SolveGroup {
+    slam::PgsParams q;                       // the handle's parameter block with the group's range, counters, list and wait cursor
+    hipStream_t stream = nullptr;
+    int index = 0, G = 1;                    // group `index` of G
+    int trials = 0;                          // trials launched so far
+    int rc = SLAM_OK;                        // what its LM loop returned
+    std::vector<int32_t> timeline;           // running slots of every trial (pgs_last_solve_timeline); its storage is the handle's, lent for the solve
+    double launch_ms = 0.0, wait_ms = 0.0;   // tune.host_prof: host clock enqueuing trials / waiting for their counters
+    SolveGroup() {}                          // (q is assigned by setup_groups: no zero-filling of a parameter block per solve)
+    bool idle() const { return q.b_cnt <= 0; }
+};
+
 // The first two operations of a trial - clearing its counters and the linearisation - depend on nothing the host decides
 // (kernel variants, lanes), so they are put on the stream BEFORE the host waits for the previous trial's active count: the
 // linearize kernel covers the round trip of that wait and of the next launches.  Every slot is covered (inactive ones return).
 int prelaunch_trial(pgs_handle* h, slam::PgsParams& p, hipStream_t stream) {
-    p.lanes = h->lanes;
+    p.lanes = h->tune.lanes;
     p.use_list = 0;   // the host does not know the list's length yet
     HIP_TRY(hipMemsetAsync(p.n_active, 0, 4 * sizeof(int32_t), stream));
     HIP_TRY(slam::pgs_launch_trial_kernel(p, 0, stream));
     return SLAM_OK;
 }
 
-int launch_trial(pgs_handle* h, slam::PgsParams& p, int32_t active_hint, int lanes, int32_t nslots, hipStream_t stream, int trial_index,
-                 bool profile, bool prelaunched = false, int force_lanes_next = 0) {
-    p.lanes = lanes < 1 ? 1 : (lanes > h->lanes ? h->lanes : lanes);
-    p.use_list = h->use_list ? 1 : 0; p.n_list = nslots;   // the slots pgs_decide_kernel (or lm_begin) listed for this trial
-    {   // Chain + SYRK fused: NB workgroups per slot, each alone on a CU.  With idle CUs to spare the chain is replicated on up to
-        // four of them so that a workgroup's share of the tiles stays in the shadow of the recursion; between one and two rounds of
-        // NB = 2 the two-launch path (instance-resident SYRK) is faster; a full batch of 2 x 256 workgroups is two clean rounds.
-        const int run = p.use_list ? nslots : p.b_cnt * p.lanes;
-        p.fused = 0;
-        if (h->fused_ok) {
-            if (h->fused_mode >= 2 && h->fused_mode <= 4) p.fused = h->fused_mode;
-            else if (4 * run <= h->cus) p.fused = 4;
-            else if (3 * run <= h->cus) p.fused = 3;
-            else if (2 * run <= h->cus) p.fused = 2;
-            else if (run > (h->cus * 2) / 3 && run <= h->cus) p.fused = 2;
-        }
-    }
-    // Few instances left: the per-trial latency counts and spare slots cost little.  Two lanes from `lanes_switch` active
-    // instances down (the common streak is one failure, then a success at 10 lambda), all of them from `lanes_switch_all` down.
-    p.lanes_next = lanes_for(h, active_hint);
-    if (force_lanes_next > 0) p.lanes_next = force_lanes_next;
-    active_hint *= p.lanes;   // the kernel variants below are chosen by the number of slots that run (an upper bound), not of instances
-    // instance-resident accumulators (code 1) from syrk_inst_switch running slots while its tiles hold every graph of the solve (syrk_inst_ok), else 32x32 wavefront tiles
-    p.syrk_wave_tile = active_hint >= h->syrk_inst_switch && h->syrk_inst_ok ? 1 : 32;
+// kWhole: the trial is enqueued from its first operation on; kPrelaunched: its first two operations are on the stream (prelaunch_trial);
+// kStreaming: whole, and its decide step hands out one lane whatever is left (the streaming loop runs one slot per graph)
+enum class TrialStart { kWhole, kPrelaunched, kStreaming };
+
+// one tryLambda of the instances [p.b_off, p.b_off + p.b_cnt) on `stream`, from the state `s` the previous trial's pgs_decide_kernel reported
+// (the first trial's: lm_begin's): s.lanes = the most slots any instance runs in this trial, s.slots = the slots listed for it
+int launch_trial(pgs_handle* h, slam::PgsParams& p, hipStream_t stream, const LmState& s, int trial_index, TrialStart start) {
+    const slam_host::PgsTuning& tune = h->tune;
+    const bool profile = h->profiling, prelaunched = start == TrialStart::kPrelaunched;
+    p.lanes = s.lanes < 1 ? 1 : (s.lanes > tune.lanes ? tune.lanes : s.lanes);
+    p.use_list = tune.use_list ? 1 : 0; p.n_list = s.slots;
+    p.fused = slam_host::pgs_fused(h->fused_ok, tune.fused_mode, p.use_list ? s.slots : p.b_cnt * p.lanes, h->cus);
+    p.lanes_next = start == TrialStart::kStreaming ? 1 : slam_host::pgs_lanes_next(tune, s.active);
+    p.syrk_wave_tile = slam_host::pgs_syrk_kernel(s.active, p.lanes, tune.syrk_inst_switch, h->syrk_inst_ok);
     if (profile) { if ((int)h->trial_fused.size() <= trial_index) h->trial_fused.resize(trial_index + 1); h->trial_fused[trial_index] = p.fused; }
     if (!prelaunched) HIP_TRY(hipMemsetAsync(p.n_active, 0, 4 * sizeof(int32_t), stream));
     for (int k = prelaunched ? 1 : 0; k < slam::kPgsTrialKernels; ++k) {
@@ -597,253 +573,299 @@ int launch_trial(pgs_handle* h, slam::PgsParams& p, int32_t active_hint, int lan
     return SLAM_OK;
 }
 
+// The plan for segments of SL poses (pgs_seg_plan_kernel; SL = 0: it only counts the factors - the grid of the per-factor kernels):
+// *mx = the most landmarks the interior poses of any segment of any instance see
+int plan_for_length(pgs_handle* h, int SL, int* mx) {
+    h->p.seg_len = SL;
+    HIP_TRY(slam::pgs_launch_seg_plan(h->p, h->stream));
+    std::vector<int32_t> U((size_t)h->B), F((size_t)h->B);
+    if (SL > 0) HIP_TRY(hipMemcpyAsync(U.data(), h->p.seg_umax, sizeof(int32_t) * (size_t)h->B, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(F.data(), h->p.fact_cnt, sizeof(int32_t) * (size_t)h->B, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    int fx = 0;
+    for (int32_t f : F) fx = f > fx ? f : fx;
+    h->p.nfact_max = fx;
+    *mx = 0;
+    for (int32_t u : U) *mx = u > *mx ? u : *mx;
+    return SLAM_OK;
+}
+
+// Segmented elimination of the pose chain (pgs_seg_impl.h): the path runs when no segment of any instance sees more than kPgsSegMaxLm
+// landmarks (its columns fit the segment kernels) and the separators fit the separator kernel's staging.  The segment length of this solve:
+// the longest of seg_cur, seg_cur / 2, ... (slam_host::pgs_seg_step) that does.  None - dense visibility on a big map: the sequential chain.
+int plan_segments(pgs_handle* h) {
+    h->seg_ok = false; h->p.seg_on = 0;
+    int SL = h->tune.seg_len > 0 ? h->seg_cur : 0;
+    for (;;) {
+        int mx = 0;
+        TRY(plan_for_length(h, SL, &mx));
+        if (SL <= 0) break;
+        const slam_host::PgsSegStep step = slam_host::pgs_seg_step(SL, mx, h->p.N);
+        if (step.kind == slam_host::PgsSegStep::kAccept) h->seg_ok = true;
+        if (step.kind != slam_host::PgsSegStep::kTry) break;
+        bool resized = false;
+        TRY(resize_segments(h, step.next, &resized));
+        if (!resized) break;   // (no memory for the shorter segments' arrays: the sequential chain, on the arrays that exist)
+        SL = step.next;
+    }
+    if (h->seg_ok) { h->seg_cur = SL; h->seg_used = SL; TRY(ensure_segT(h)); }
+    else {   // (a graph only grows: what no segment length holds now, none will hold later - the next solves go straight to the sequential chain)
+        h->p.seg_len = h->tune.seg_len > 0 ? h->seg_alloc : 0; h->seg_used = 0; h->seg_cur = 0;
+    }
+    h->p.seg_on = h->seg_ok ? 1 : 0;
+    return SLAM_OK;
+}
+
+// Which chain / SYRK kernels the solve's graphs fit (slam_host::pgs_fit): asked for the sequential chain with a column of Y per lane only
+int decide_paths(pgs_handle* h) {
+    h->fused_ok = false; h->p.fused = 0; h->syrk_inst_ok = false;
+    if (h->seg_ok || h->p.LD > 448) return SLAM_OK;
+    std::vector<int32_t> M((size_t)h->B);
+    HIP_TRY(hipMemcpyAsync(M.data(), h->p.M, sizeof(int32_t) * (size_t)h->B, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    int mx = 0;
+    for (int32_t m : M) mx = m > mx ? m : mx;
+    const slam_host::PgsFit fit = slam_host::pgs_fit(mx, h->p.KP, h->tune.fused_mode);
+    h->fused_ok = fit.fused_ok; h->syrk_inst_ok = fit.syrk_inst_ok;
+    return SLAM_OK;
+}
+
+// The groups' streams must not share a hardware queue: two LM loops whose launches sit in ONE in-order queue wait for each other's
+// queued trials at every host synchronisation (measured inside bench.py's driver command, where the earlier legs' streams shift the
+// runtime's stream -> queue assignment: 3.40 k solves/s with two groups against 5.21 k with one and 5.66 k with two on distinct
+// queues; profiles/r05_pgs/hw_queues.txt).  The runtime keeps separate queues per stream PRIORITY, so the groups alternate between
+// the priority levels the device offers (SLAM_PGS_GROUP_PRIO=0: all at the default priority, the behaviour before).
+int create_group_stream(pgs_handle* h, int g, hipStream_t* st) {
+    int lo = 0, hi = 0;
+    if (h->tune.group_prio && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi) {
+        const int nlev = lo - hi + 1;   // lo = least priority (numerically greatest), hi = greatest
+        HIP_TRY(hipStreamCreateWithPriority(st, hipStreamNonBlocking, hi + (g % nlev)));
+    } else {
+        (void)hipGetLastError();
+        HIP_TRY(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
+    }
+    return SLAM_OK;
+}
+
+// What a solve of G groups needs and the handle keeps: the groups' streams and events, the pinned active counts and, if a group may
+// stream (share > 0), the pinned ring of counter blocks with its events
+int reserve_solve_resources(pgs_handle* h, int G, int share) {
+    while (G > 1 && (int)h->gstreams.size() < G) {
+        hipStream_t st;
+        TRY(create_group_stream(h, (int)h->gstreams.size(), &st));
+        h->gstreams.push_back(st);
+    }
+    while ((int)h->gevents.size() < G + 1) { hipEvent_t e; HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->gevents.push_back(e); }
+    HIP_TRY(h->h_active.reserve(64));
+    if (share > 0) {
+        HIP_TRY(h->h_ring.reserve(8 * slam_host::kPgsRing * slam_host::kPgsMaxGroups));
+        while ((int)h->ring_events.size() < slam_host::kPgsRing * slam_host::kPgsMaxGroups) {
+            hipEvent_t e; HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->ring_events.push_back(e);
+        }
+    }
+    return SLAM_OK;
+}
+
+// The groups' parameter blocks and streams; every group that owns instances starts behind what the handle's stream holds so far, with
+// pgs_lm_begin_kernel and its clones.  A group whose share of the slots covers its graphs runs lockstep (slots_cap = 0).
+int setup_groups(pgs_handle* h, int share, std::vector<SolveGroup>& groups) {
+    const int G = (int)groups.size();
+    if (G > 1) HIP_TRY(hipEventRecord(h->gevents[G], h->stream));   // everything queued on the handle's stream so far comes first
+    h->p.max_trials = h->tune.max_trials;   // the per-graph trial cap, applied by pgs_decide_kernel in every schedule
+    h->timeline.resize((size_t)G);
+    for (int g = 0; g < G; ++g) {
+        SolveGroup& grp = groups[g];
+        grp.timeline.swap(h->timeline[g]); grp.timeline.clear();   // (the last solve's storage: no allocation per solve)
+        const slam_host::PgsRange r = slam_host::pgs_group_range(h->B, G, g);
+        grp.index = g; grp.G = G;
+        grp.stream = G > 1 ? h->gstreams[g] : h->stream;
+        slam::PgsParams& q = grp.q = h->p;
+        q.b_off = r.b_off; q.b_cnt = r.b_cnt;
+        q.n_active = h->p.n_active + 4 * g;
+        q.alist = h->p.alist + (size_t)r.b_off * h->tune.lanes;
+        q.wait_next = h->d_wait + g;
+        q.slots_cap = slam_host::pgs_stream_slots(share, r.b_cnt);
+        q.n_list_dev = nullptr;
+        if (grp.idle()) continue;
+        if (G > 1) HIP_TRY(hipStreamWaitEvent(grp.stream, h->gevents[G], 0));
+        HIP_TRY(slam::pgs_launch_lm_begin(q, grp.stream));
+        TRY(clone_instances(h, q, grp.stream, /*slabs=*/!h->tune.use_list || h->profiling));   // (with the slot list: copied on demand, for the listed instances)
+    }
+    return SLAM_OK;
+}
+
+// the counters of streamed trial `seen` of the group (a blocking wait for its event) into last[8] and its running slots into the timeline
+int read_streamed_trial(pgs_handle* h, SolveGroup& grp, int seen, int32_t last[8]) {
+    constexpr int R = slam_host::kPgsRing;
+    HIP_TRY(hipEventSynchronize(h->ring_events[(size_t)grp.index * R + seen % R]));
+    memcpy(last, h->h_ring + ((size_t)grp.index * R + seen % R) * 8, 8 * sizeof(int32_t));
+    if (h->tune.trace) fprintf(stderr, "pgs group %d trial %d (streaming): active %d, slots %d, next waiting %d of %d\n", grp.index, seen, last[0], last[2], last[4], grp.q.b_off + grp.q.b_cnt);
+    grp.timeline.push_back(last[2]);
+    return SLAM_OK;
+}
+
+// Streaming phase of a group (q.slots_cap > 0): the list of every trial is refilled on the device, its length read on the device, so the host
+// enqueues trials `stream_depth` ahead and only looks at the counters of the trial that far back - to learn that the queue of waiting graphs
+// is empty and few are left (then the lockstep phase takes over, with its lambda lanes), or none at all.  *s: the state the last trial left.
+int stream_phase(pgs_handle* h, SolveGroup& grp, LmState* s) {
+    constexpr int R = slam_host::kPgsRing;
+    slam::PgsParams& q = grp.q;
+    const int cap = q.slots_cap, G = grp.G, D = h->tune.stream_depth, wend = q.b_off + q.b_cnt;
+    int32_t* dcnt = h->d_cnt + (size_t)grp.index * 16;
+    int32_t* ring = h->h_ring + (size_t)grp.index * R * 8;
+    int32_t* const n_active0 = q.n_active;
+    // "the counters trial -1 left": the first `cap` graphs run (pgs_lm_begin_kernel listed them), the cursor stands behind them
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(dcnt + 2), cap, 1, grp.stream));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)q.wait_next, q.b_off + cap, 1, grp.stream));
+    int t = 0, seen = 0;   // trials enqueued / trials whose counters the host has read
+    bool leave = false;    // nothing left, or nothing waiting and few enough running that the lanes pay: the lockstep phase finishes the group
+    int32_t last[8] = {cap * G, 1, cap, 0, q.b_off + cap, 0, 0, 0};
+    grp.timeline.push_back(cap);
+    auto read_next = [&]() -> int {
+        TRY(read_streamed_trial(h, grp, seen++, last));
+        leave = leave || slam_host::pgs_stream_hands_over(last[0], last[4], wend, G, h->tune.lanes_switch);
+        return SLAM_OK;
+    };
+    const long long bound = slam_host::pgs_stream_launch_bound(q.b_cnt, cap, h->tune.max_trials);
+    while (!leave && t < bound) {
+        q.n_list_dev = dcnt + 8 * (t & 1) + 2;
+        q.n_active = dcnt + 8 * ((t + 1) & 1);
+        TRY(launch_trial(h, q, grp.stream, LmState{cap * G, 1, cap}, t, TrialStart::kStreaming));
+        HIP_TRY(hipMemcpyAsync(ring + 8 * (t % R), q.n_active, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, grp.stream));
+        HIP_TRY(hipEventRecord(h->ring_events[(size_t)grp.index * R + t % R], grp.stream));
+        t += 1;
+        while (!leave && t - seen >= D) TRY(read_next());
+    }
+    while (seen < t) TRY(read_next());   // the trials already enqueued are real ones (or return at entry): their counters are the state to go on from
+    grp.timeline.pop_back();             // (the last entry is the list of a trial the lockstep phase launches and records itself)
+    grp.trials = t;
+    q.slots_cap = 0; q.n_list_dev = nullptr; q.n_active = n_active0;
+    *s = LmState{last[0] * G, last[1] > 0 ? last[1] : 1, last[2]};
+    // (graphs still waiting at the trial cap keep state 2: pgs_lm_end_kernel flags them NOT_CONVERGED)
+    return SLAM_OK;
+}
+
+// Lockstep phase of a group, from state s: launch a trial, wait for its active count, choose the next trial's kernel variants and lanes from
+// it.  The first two operations of the next trial are enqueued before that wait (prelaunch_trial) - not in a profiled solve: per-kernel
+// timing wants every kernel of a trial between its own events.
+int lockstep_phase(pgs_handle* h, SolveGroup& grp, LmState s) {
+    slam::PgsParams& q = grp.q;
+    hipStream_t st = grp.stream;
+    const bool profile = h->profiling, host_prof = h->tune.host_prof;
+    int32_t* hact = h->h_active + 4 * grp.index;
+    // a bound that cannot bind first: every launch consumes at least one trial of every graph still running, and pgs_decide_kernel ends
+    // a graph at its own max_trials-th trial
+    const int trials_end = grp.trials + h->tune.max_trials;
+    // the phase's first trial runs over the list it was handed; later ones have their first kernels enqueued ahead
+    TrialStart start = TrialStart::kWhole;
+    bool cloned = !h->tune.use_list || profile || h->tune.lanes <= 1;
+    while (s.active > 0 && grp.trials < trials_end) {
+        // the first trial whose decide step may hand out lanes: the instances it lists (every later list is a subset) get their clones now
+        if (!cloned && slam_host::pgs_lanes_next(h->tune, s.active) > 1) { TRY(clone_listed(h, q, s.slots, st)); cloned = true; }
+        grp.timeline.push_back(s.slots);
+        const double ta = host_prof ? now_ms() : 0.0;
+        TRY(launch_trial(h, q, st, s, grp.trials, start));
+        HIP_TRY(hipMemcpyAsync(hact, q.n_active, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(h->gevents[grp.index], st));
+        if (!profile) { TRY(prelaunch_trial(h, q, st)); start = TrialStart::kPrelaunched; }   // the next trial's linearisation runs while the host waits below
+        const double tb = host_prof ? now_ms() : 0.0;
+        HIP_TRY(hipEventSynchronize(h->gevents[grp.index]));
+        if (host_prof) { grp.launch_ms += tb - ta; grp.wait_ms += now_ms() - tb; }
+        s = LmState{hact[0] * grp.G, hact[1], hact[2]};
+        grp.trials += 1;
+        if (h->tune.trace) {
+            static thread_local double t_prev = 0.0;
+            const double now = now_ms();
+            fprintf(stderr, "pgs group %d trial %d: %.2f ms, lanes %d -> active %d, lanes next %d\n", grp.index, grp.trials - 1, grp.trials > 1 ? now - t_prev : 0.0, (int)q.lanes, (int)hact[0], (int)s.lanes);
+            t_prev = now;
+        }
+    }
+    return SLAM_OK;
+}
+
+// the LM loop of one group, on the calling thread: the streaming phase if the group streams, the lockstep phase from the state it left
+// (or from the start: every instance active, one lane, every slot listed), then the results
+int drive_group(pgs_handle* h, SolveGroup& grp) {
+    HIP_TRY(hipSetDevice(h->device));
+    LmState s{grp.q.b_cnt * grp.G, 1, grp.q.b_cnt};
+    if (grp.q.slots_cap > 0) TRY(stream_phase(h, grp, &s));
+    TRY(lockstep_phase(h, grp, s));
+    HIP_TRY(slam::pgs_launch_lm_end(grp.q, grp.stream));
+    if (grp.G > 1) HIP_TRY(hipEventRecord(h->gevents[grp.index], grp.stream));
+    return SLAM_OK;
+}
+
+// One host thread per group drives its LM loop (group 0: the caller's); the HIP runtime is thread-safe and the groups touch disjoint
+// instance ranges and their own SolveGroup.  Returns when all of them have.
+void run_groups(pgs_handle* h, std::vector<SolveGroup>& groups) {
+    std::vector<std::thread> workers;
+    for (size_t g = 1; g < groups.size(); ++g)
+        if (!groups[g].idle()) workers.emplace_back([h, &grp = groups[g]]() { grp.rc = drive_group(h, grp); });
+    if (!groups[0].idle()) groups[0].rc = drive_group(h, groups[0]);
+    for (std::thread& w : workers) w.join();
+}
+
+// After the groups' threads: their timelines and host-clock sums into the handle, the handle's stream continues after every group
+int join_groups(pgs_handle* h, std::vector<SolveGroup>& groups) {
+    for (SolveGroup& grp : groups) {
+        h->timeline[grp.index].swap(grp.timeline);
+        h->host_launch_ms += grp.launch_ms; h->host_wait_ms += grp.wait_ms;
+    }
+    int most = 0;
+    for (const SolveGroup& grp : groups) {
+        if (grp.rc != SLAM_OK) return grp.rc;
+        if (grp.G > 1 && !grp.idle()) HIP_TRY(hipStreamWaitEvent(h->stream, h->gevents[grp.index], 0));
+        most = grp.trials > most ? grp.trials : most;
+    }
+    h->last_trials = most;
+    return SLAM_OK;
+}
+
+// profiled solve: the HIP event times of every trial's kernels summed per kernel and per path
+int total_profile(pgs_handle* h) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int k = 0; k < slam::kPgsTrialKernels; ++k) h->kernel_ms[k] = 0.0;
+    for (int t = 0; t < h->last_trials; ++t)
+        for (int k = 0; k < slam::kPgsTrialKernels; ++k) {
+            float ms = 0.f;
+            const size_t e0 = (size_t)t * (slam::kPgsTrialKernels + 1) + k;
+            HIP_TRY(hipEventElapsedTime(&ms, h->events[e0], h->events[e0 + 1]));
+            h->kernel_ms[k] += ms;
+            const int tf = t < (int)h->trial_fused.size() ? h->trial_fused[t] : 0;
+            if (k == 1 && tf) h->path_ms[1] += ms;      // chain + SYRK in one launch
+            if (k == 2 && !tf) h->path_ms[h->seg_ok ? 2 : 0] += ms;     // the SYRK launch(es) of the two-launch path / of the segmented path
+            if (h->tune.trace) fprintf(stderr, "%s%.3f%s", k == 0 ? "pgs trial kernels (ms): " : " ", ms, k + 1 == slam::kPgsTrialKernels ? "\n" : "");
+        }
+    return SLAM_OK;
+}
+
 }  // namespace
 
+// The solve as its phases: plan the segments, decide the chain / SYRK paths, reserve what the groups need, set the groups up, drive them
+// (lockstep: two groups on their own streams from batch 128 on - with the segmented elimination a trial's kernels are short enough for two
+// LM loops to fill each other's gaps; profiles/r05_pgs/groups_and_lanes.txt), join, total the profile.  The rules: host/pgs_schedule.h.
 int pgs_solve(pgs_handle* h) {
     TRY(check(h));
     if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_solve");
     h->mg_valid = false; h->solved = true;
     h->p.N = h->timestep + 1;
     h->p.b_off = 0; h->p.b_cnt = h->B;
-    {   // Segmented elimination of the pose chain (pgs_seg_impl.h): the plan kernel lists the landmarks every segment's interior poses
-        // see; the path runs when no segment of any instance sees more than kPgsSegMaxLm of them (its columns fit the segment kernels)
-        // and the separators fit the separator kernel's staging.  Otherwise - dense visibility on a big map - the sequential chain.
-        h->seg_ok = false; h->p.seg_on = 0;
-        int SL = h->seg_len > 0 ? h->seg_cur : 0;
-        for (;;) {
-            // The segment length of this solve: the longest of seg_cur, seg_cur / 2, ... (>= 8 poses) whose every segment sees at most
-            // kPgsSegMaxLm landmarks and whose separators fit the separator kernel's staging.
-            h->p.seg_len = SL;
-            HIP_TRY(slam::pgs_launch_seg_plan(h->p, h->stream));   // (also counts the factors: the grid of the per-factor kernels)
-            std::vector<int32_t> U((size_t)h->B), F((size_t)h->B);
-            if (SL > 0) HIP_TRY(hipMemcpyAsync(U.data(), h->p.seg_umax, sizeof(int32_t) * (size_t)h->B, hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipMemcpyAsync(F.data(), h->p.fact_cnt, sizeof(int32_t) * (size_t)h->B, hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            int mx = 0, fx = 0;
-            for (int32_t f : F) fx = f > fx ? f : fx;
-            h->p.nfact_max = fx;
-            if (SL <= 0) break;
-            for (int32_t u : U) mx = u > mx ? u : mx;
-            if (mx <= slam::kPgsSegMaxLm) { h->seg_ok = true; break; }
-            const int next = SL / 2;
-            // (0x7fffffff: more separators than pgs_sep_kernel stages - shorter segments only add separators)
-            if (mx == 0x7fffffff || next < 8 || (h->p.N - 2) / next > slam::kPgsSegMaxSep) break;
-            bool resized = false;
-            TRY(resize_segments(h, next, &resized));
-            if (!resized) break;   // (no memory for the shorter segments' arrays: the sequential chain, on the arrays that exist)
-            SL = next;
-        }
-        if (h->seg_ok) { h->seg_cur = SL; h->seg_used = SL; TRY(ensure_segT(h)); }
-        else {   // (a graph only grows: what no segment length holds now, none will hold later - the next solves go straight to the sequential chain)
-            h->p.seg_len = h->seg_len > 0 ? h->seg_alloc : 0; h->seg_used = 0; h->seg_cur = 0;
-        }
-        h->p.seg_on = h->seg_ok ? 1 : 0;
-    }
-    {   // chain + SYRK in one launch (Y stays in LDS) is possible while the lower triangle of every instance fits the 72 wavefront
-        // tiles of pgs_chain_syrk_kernel, a column of Y per lane (2M + 1 <= 448) and its event staging (32 factor slots per pose)
-        // The instance-resident SYRK of the two-launch path holds kPgsSyrkInstTiles 32x32 tiles of S_ext (the z column included): 2M + 1
-        // <= 416, M <= 207.  Beyond that its last tile row was never formed (L_max 208 - 223, LD 448); the tile kernel takes those solves.
-        h->fused_ok = false; h->p.fused = 0; h->syrk_inst_ok = false;
-        if (!h->seg_ok && h->p.LD <= 448) {
-            std::vector<int32_t> M((size_t)h->B);
-            HIP_TRY(hipMemcpyAsync(M.data(), h->p.M, sizeof(int32_t) * (size_t)h->B, hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            int mx = 0;
-            for (int32_t m : M) mx = m > mx ? m : mx;
-            const int nt = (2 * mx + 31) / 32, nti = (2 * mx + 1 + 31) / 32;
-            h->fused_ok = h->fused_mode != 0 && h->p.KP <= 32 && nt * (nt + 1) / 2 <= 72;
-            h->syrk_inst_ok = nti * (nti + 1) / 2 <= slam::kPgsSyrkInstTiles;
-        }
-    }
+    TRY(plan_segments(h));
+    TRY(decide_paths(h));
     HIP_TRY(hipMemsetAsync(h->p.work, 0, 3 * sizeof(double), h->stream));
     h->path_ms[0] = h->path_ms[1] = h->path_ms[2] = 0.0;
-    // (round 5: two groups from batch 128 on - with the segmented elimination a trial's kernels are short enough for two LM loops to fill
-    // each other's gaps: 5.20 -> 5.67 k solves/s at batch 256 (three groups 5.47 k, four 3.57 k), 3.49 -> 3.64 k at batch 128, 7.39 k at
-    // 1024 (three: 7.59 k); profiles/r05_pgs/groups_and_lanes.txt)
-    int G = h->groups > 0 ? h->groups : (h->B >= 128 ? 2 : 1);
-    if (G > pgs_handle::kMaxGroups) G = pgs_handle::kMaxGroups;
-    if (G > h->B) G = h->B;
-    if (h->profiling) G = 1;   // per-kernel timing wants the kernels of one stream back to back
-    const bool profile = h->profiling;
-    // The groups' streams must not share a hardware queue: two LM loops whose launches sit in ONE in-order queue wait for each other's
-    // queued trials at every host synchronisation (measured inside bench.py's driver command, where the earlier legs' streams shift the
-    // runtime's stream -> queue assignment: 3.40 k solves/s with two groups against 5.21 k with one and 5.66 k with two on distinct
-    // queues; profiles/r05_pgs/hw_queues.txt).  The runtime keeps separate queues per stream PRIORITY, so the groups alternate between
-    // the priority levels the device offers (SLAM_PGS_GROUP_PRIO=0: all at the default priority, the behaviour before).
-    while (G > 1 && (int)h->gstreams.size() < G) {
-        hipStream_t st;
-        int lo = 0, hi = 0;
-        static const bool use_prio = !(getenv("SLAM_PGS_GROUP_PRIO") && atoi(getenv("SLAM_PGS_GROUP_PRIO")) == 0);
-        if (use_prio && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi) {
-            const int nlev = lo - hi + 1, g = (int)h->gstreams.size();   // lo = least priority (numerically greatest), hi = greatest
-            HIP_TRY(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, hi + (g % nlev)));
-        } else {
-            (void)hipGetLastError();
-            HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        }
-        h->gstreams.push_back(st);
-    }
-    while ((int)h->gevents.size() < G + 1) { hipEvent_t e; HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->gevents.push_back(e); }
-    HIP_TRY(h->h_active.reserve(64));
-    // streaming: `slots` graphs in flight over all groups; a group whose share of the slots covers its graphs runs lockstep as before
-    const int per = (h->B + G - 1) / G;
-    const int cap_g = (h->slots > 0 && !profile) ? (h->slots + G - 1) / G : 0;
-    if (cap_g > 0) {
-        HIP_TRY(h->h_ring.reserve(8 * pgs_handle::kRing * pgs_handle::kMaxGroups));
-        while ((int)h->ring_events.size() < pgs_handle::kRing * pgs_handle::kMaxGroups) {
-            hipEvent_t e; HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->ring_events.push_back(e);
-        }
-    }
-    h->timeline.assign(G, {});
-    if (G > 1) HIP_TRY(hipEventRecord(h->gevents[G], h->stream));   // everything queued on the handle's stream so far comes first
-    h->p.max_trials = h->max_trials;   // the per-graph trial cap, applied by pgs_decide_kernel in every schedule
-    std::vector<slam::PgsParams> gp(G, h->p);
-    std::vector<int> gtrials(G, 0), grc(G, SLAM_OK);
-    std::vector<char> gdone(G, 0);
-    auto gstream = [&](int g) { return G > 1 ? h->gstreams[g] : h->stream; };
-    for (int g = 0; g < G; ++g) {
-        slam::PgsParams& q = gp[g];
-        q.b_off = g * per;
-        q.b_cnt = (h->B - g * per) < per ? (h->B - g * per) : per;
-        q.n_active = h->p.n_active + 4 * g;
-        q.alist = h->p.alist + (size_t)g * per * h->lanes;
-        q.wait_next = h->d_wait + g;
-        q.slots_cap = (cap_g > 0 && cap_g < q.b_cnt) ? cap_g : 0;
-        q.n_list_dev = nullptr;
-        if (q.b_cnt <= 0) { gdone[g] = 1; continue; }
-        if (G > 1) HIP_TRY(hipStreamWaitEvent(gstream(g), h->gevents[G], 0));
-        HIP_TRY(slam::pgs_launch_lm_begin(q, gstream(g)));
-        TRY(clone_instances(h, q, gstream(g), /*slabs=*/!h->use_list || profile));   // (with the slot list: copied on demand, for the listed instances)
-    }
-    // One host thread per group drives its LM loop; the HIP runtime is thread-safe and the groups touch disjoint instance ranges.
-    //  * streaming phase (slots_cap > 0): the list of every trial is refilled on the device, its length read on the device, so the host
-    //    enqueues trials `stream_depth` ahead and only looks at the counters of the trial that far back - to learn that the queue of
-    //    waiting graphs is empty and few are left (then the lockstep loop below takes over, with its lambda lanes), or none at all.
-    //  * lockstep phase: launch a trial, wait for its active count, choose the next trial's kernel variants and lanes from it.  The first
-    //    two operations of a trial (counters, linearisation) are enqueued before that wait (prelaunch_trial).
-    auto drive = [&](int g) -> int {
-        HIP_TRY(hipSetDevice(h->device));
-        slam::PgsParams& q = gp[g];
-        hipStream_t st = gstream(g);
-        std::vector<int32_t>& tl = h->timeline[g];
-        int32_t act[3] = {q.b_cnt * G, 1, q.b_cnt};   // active instances (scaled to the batch), lanes and active slots of the next trial
-        int trials = 0;
-        if (q.slots_cap > 0) {
-            constexpr int R = pgs_handle::kRing;
-            const int cap = q.slots_cap, D = h->stream_depth, wend = q.b_off + q.b_cnt;
-            int32_t* dcnt = h->d_cnt + (size_t)g * 16;
-            int32_t* ring = h->h_ring + (size_t)g * R * 8;
-            hipEvent_t* ev = &h->ring_events[(size_t)g * R];
-            int32_t* const n_active0 = q.n_active;
-            // "the counters trial -1 left": the first `cap` graphs run (pgs_lm_begin_kernel listed them), the cursor stands behind them
-            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(dcnt + 2), cap, 1, st));
-            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)q.wait_next, q.b_off + cap, 1, st));
-            int t = 0, seen = 0;   // trials enqueued / trials whose counters the host has read
-            bool leave = false;
-            int32_t last[8] = {cap * G, 1, cap, 0, q.b_off + cap, 0, 0, 0};
-            tl.push_back(cap);
-            auto read_one = [&]() -> int {
-                HIP_TRY(hipEventSynchronize(ev[seen % R]));
-                memcpy(last, ring + 8 * (seen % R), sizeof(last));
-                seen += 1;
-                if (h->trace) fprintf(stderr, "pgs group %d trial %d (streaming): active %d, slots %d, next waiting %d of %d\n", g, seen - 1, last[0], last[2], last[4], wend);
-                tl.push_back(last[2]);
-                // nothing left, or nothing waiting and few enough running that the lanes pay: the lockstep loop finishes the group
-                if (last[0] == 0 || (last[4] >= wend && last[0] * G <= h->lanes_switch)) leave = true;
-                return SLAM_OK;
-            };
-            // (the trial cap is per graph - pgs_decide_kernel applies it; the launches only need a bound that cannot bind first)
-            const long long launch_cap = ((long long)q.b_cnt / cap + 2) * h->max_trials;
-            while (!leave && t < launch_cap) {
-                q.n_list_dev = dcnt + 8 * (t & 1) + 2;
-                q.n_active = dcnt + 8 * ((t + 1) & 1);
-                TRY(launch_trial(h, q, cap * G, 1, cap, st, t, false, false, 1));
-                HIP_TRY(hipMemcpyAsync(ring + 8 * (t % R), q.n_active, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipEventRecord(ev[t % R], st));
-                t += 1;
-                while (!leave && t - seen >= D) TRY(read_one());
-            }
-            while (seen < t) TRY(read_one());   // the trials already enqueued are real ones (or return at entry): their counters are the state to go on from
-            tl.pop_back();                      // (the last entry is the list of a trial the lockstep loop launches and records itself)
-            trials = t;
-            q.slots_cap = 0; q.n_list_dev = nullptr; q.n_active = n_active0;
-            act[0] = last[0] * G; act[1] = last[1] > 0 ? last[1] : 1; act[2] = last[2];
-            // (graphs still waiting at the trial cap keep state 2: pgs_lm_end_kernel flags them NOT_CONVERGED)
-        }
-        const bool pipe = !profile;   // per-kernel timing wants every kernel of a trial between its own events
-        int32_t* hact = h->h_active + 4 * g;
-        // a bound that cannot bind first: every launch consumes at least one trial of every graph still running, and pgs_decide_kernel ends
-        // a graph at its own max_trials-th trial
-        const int trials_end = trials + h->max_trials;
-        if (act[0] > 0 && trials < trials_end) {
-            bool pre = false;   // the phase's first trial runs over the list it was handed; later ones have their first kernels enqueued ahead
-            bool cloned = !h->use_list || profile || h->lanes <= 1;
-            for (;;) {
-                // the first trial whose decide step may hand out lanes: the instances it lists (every later list is a subset) get their clones now
-                if (!cloned && lanes_for(h, act[0]) > 1) { TRY(clone_listed(h, q, act[2], st)); cloned = true; }
-                tl.push_back(act[2]);
-                timespec ta, tb, tc;
-                if (h->host_prof) clock_gettime(CLOCK_MONOTONIC, &ta);
-                TRY(launch_trial(h, q, act[0], act[1], act[2], st, trials, profile, pre));
-                HIP_TRY(hipMemcpyAsync(hact, q.n_active, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipEventRecord(h->gevents[g], st));
-                if (pipe) { TRY(prelaunch_trial(h, q, st)); pre = true; }   // the next trial's linearisation runs while the host waits below
-                if (h->host_prof) clock_gettime(CLOCK_MONOTONIC, &tb);
-                HIP_TRY(hipEventSynchronize(h->gevents[g]));
-                if (h->host_prof) {
-                    clock_gettime(CLOCK_MONOTONIC, &tc);
-                    h->host_launch_ms += (tb.tv_sec - ta.tv_sec) * 1e3 + (tb.tv_nsec - ta.tv_nsec) * 1e-6;
-                    h->host_wait_ms += (tc.tv_sec - tb.tv_sec) * 1e3 + (tc.tv_nsec - tb.tv_nsec) * 1e-6;
-                }
-                act[0] = hact[0] * G; act[1] = hact[1]; act[2] = hact[2];
-                trials += 1;
-                if (h->trace) {
-                    static thread_local double t_prev = 0.0;
-                    timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts);
-                    const double now = ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-                    fprintf(stderr, "pgs group %d trial %d: %.2f ms, lanes %d -> active %d, lanes next %d\n", g, trials - 1, trials > 1 ? now - t_prev : 0.0, (int)q.lanes, (int)hact[0], (int)act[1]);
-                    t_prev = now;
-                }
-                if (hact[0] == 0 || trials >= trials_end) break;
-            }
-        }
-        gtrials[g] = trials;
-        HIP_TRY(slam::pgs_launch_lm_end(q, st));
-        if (G > 1) HIP_TRY(hipEventRecord(h->gevents[g], st));
-        return SLAM_OK;
-    };
-    std::vector<std::thread> workers;
-    for (int g = 1; g < G; ++g)
-        if (!gdone[g]) workers.emplace_back([&, g]() { grc[g] = drive(g); });
-    if (!gdone[0]) grc[0] = drive(0);
-    for (auto& w : workers) w.join();
-    int max_trials = 0;
-    for (int g = 0; g < G; ++g) {
-        if (grc[g] != SLAM_OK) return grc[g];
-        if (G > 1 && gp[g].b_cnt > 0) HIP_TRY(hipStreamWaitEvent(h->stream, h->gevents[g], 0));   // the handle's stream continues after every group
-        max_trials = gtrials[g] > max_trials ? gtrials[g] : max_trials;
-    }
-    h->last_trials = max_trials;
-    if (profile) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        for (int k = 0; k < slam::kPgsTrialKernels; ++k) h->kernel_ms[k] = 0.0;
-        for (int t = 0; t < max_trials; ++t)
-            for (int k = 0; k < slam::kPgsTrialKernels; ++k) {
-                float ms = 0.f;
-                const size_t e0 = (size_t)t * (slam::kPgsTrialKernels + 1) + k;
-                HIP_TRY(hipEventElapsedTime(&ms, h->events[e0], h->events[e0 + 1]));
-                h->kernel_ms[k] += ms;
-                const int tf = t < (int)h->trial_fused.size() ? h->trial_fused[t] : 0;
-                if (k == 1 && tf) h->path_ms[1] += ms;      // chain + SYRK in one launch
-                if (k == 2 && !tf) h->path_ms[h->seg_ok ? 2 : 0] += ms;     // the SYRK launch(es) of the two-launch path / of the segmented path
-                if (h->trace) fprintf(stderr, "%s%.3f%s", k == 0 ? "pgs trial kernels (ms): " : " ", ms, k + 1 == slam::kPgsTrialKernels ? "\n" : "");
-            }
-    }
-    return SLAM_OK;
+    const int G = slam_host::pgs_groups(h->tune.groups, h->B, h->profiling);
+    const int share = slam_host::pgs_slot_share(h->tune.slots, G, h->profiling);
+    TRY(reserve_solve_resources(h, G, share));
+    std::vector<SolveGroup> groups((size_t)G);
+    TRY(setup_groups(h, share, groups));
+    run_groups(h, groups);
+    TRY(join_groups(h, groups));
+    return h->profiling ? total_profile(h) : SLAM_OK;
 }
 
 // Streaming: at most `slots` graphs of the batch in flight (0 = lockstep, every graph from the first trial on).  Results do not depend on it.
-int pgs_set_slots(pgs_handle* h, int slots) { TRY(check(h)); h->slots = slots < 0 ? 0 : slots; return SLAM_OK; }
+int pgs_set_slots(pgs_handle* h, int slots) { TRY(check(h)); h->tune.slots = slots < 0 ? 0 : slots; return SLAM_OK; }
 // The last solve's running slots per trial of solve group `group`: slots[0 .. *n) (at most cap entries written); *groups = number of groups.
 int pgs_last_solve_timeline(pgs_handle* h, int group, int32_t* slots, int cap, int32_t* n, int32_t* groups) {
     TRY(check(h));
@@ -855,8 +877,8 @@ int pgs_last_solve_timeline(pgs_handle* h, int group, int32_t* slots, int cap, i
     return SLAM_OK;
 }
 
-// number of solve groups (0 = automatic: 2 from 512 instances)
-int pgs_set_groups(pgs_handle* h, int groups) { TRY(check(h)); h->groups = groups < 0 ? 0 : groups; return SLAM_OK; }
+// number of solve groups (0 = automatic: slam_pgs.h)
+int pgs_set_groups(pgs_handle* h, int groups) { TRY(check(h)); h->tune.groups = groups < 0 ? 0 : groups; return SLAM_OK; }
 
 int pgs_adopt_result(pgs_handle* h) {
     TRY(check(h));
@@ -873,12 +895,7 @@ int run_every_iteration(pgs_handle* h, int T, int32_t* counts);
 
 int pgs_run_sim_every_iteration(pgs_handle* h, const float* cmds, int T, int32_t* counts) {
     TRY(check(h));
-    if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_run_sim_every_iteration");
-    if (!h->p.map && !h->p.map_each) return fail(SLAM_ERR_STATE, "pgs_set_map must be called before pgs_run_sim_every_iteration");
-    if (!cmds || T <= 0) return fail(SLAM_ERR_ARG, "bad command sequence");
-    if (h->timestep + T >= h->N_max) return fail(SLAM_ERR_STATE, "timestep %d + %d commands exceed the pose capacity N_max = %d", h->timestep, T, h->N_max);
-    h->mg_valid = false;
-    TRY(put_commands(h, cmds, false, T, false));
+    TRY(enter_ticks(h, "pgs_run_sim_every_iteration", cmds, T, kSim | kShared));
     HIP_TRY(hipStreamSynchronize(h->stream));   // cmds is a pageable host array
     return run_every_iteration(h, T, counts);
 }
@@ -887,13 +904,7 @@ int pgs_run_sim_every_iteration(pgs_handle* h, const float* cmds, int T, int32_t
 // their structure.
 int pgs_run_sim_every_iteration_each(pgs_handle* h, const float* cmds, int T, int32_t* counts) {
     TRY(check(h));
-    if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_run_sim_every_iteration_each");
-    if (!h->p.map && !h->p.map_each) return fail(SLAM_ERR_STATE, "pgs_set_map or pgs_set_maps must be called before pgs_run_sim_every_iteration_each");
-    if (!cmds || T <= 0) return fail(SLAM_ERR_ARG, "bad command sequence");
-    if (!all_finite_f(cmds, 2 * (size_t)T * h->B)) return fail(SLAM_ERR_ARG, "a command is not finite");
-    if (h->timestep + T >= h->N_max) return fail(SLAM_ERR_STATE, "timestep %d + %d commands exceed the pose capacity N_max = %d", h->timestep, T, h->N_max);
-    TRY(put_commands(h, cmds, false, T, true));
-    h->mg_valid = false;
+    TRY(enter_ticks(h, "pgs_run_sim_every_iteration_each", cmds, T, kSim | kEach));
     HIP_TRY(hipStreamSynchronize(h->stream));   // cmds is a pageable host array
     return run_every_iteration(h, T, counts);
 }
@@ -907,20 +918,17 @@ int run_every_iteration(pgs_handle* h, int T, int32_t* counts) {
     HIP_TRY(hipMemsetAsync(h->d_tick, 0, sizeof(int32_t) * 2 * (size_t)h->B, h->stream));
     HIP_TRY(hipMemsetAsync(h->d_tick_flop, 0, sizeof(double) * 2 * (size_t)h->B, h->stream));
     const bool prof = getenv("SLAM_PGS_ITER_PROF") != nullptr;
-    auto now_ms = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     for (int k = 0; k < 4; ++k) h->iter_ms[k] = 0.0;
     h->iter_trials = 0;
     // One solve group per tick unless the caller chose a number: a tick's solve is a handful of latency-bound trials - two groups gain 2 % in
     // a process of their own (15.2 k against 14.9 k graph-ticks/s) and lose 20 % when their streams land on one hardware queue behind other
     // handles' streams (bench.py's secondary leg: 12.3 k; the stream -> queue assignment of the runtime, profiles/r05_pgs/hw_queues.txt).
-    struct GroupsGuard { pgs_handle* h; int saved; ~GroupsGuard() { h->groups = saved; } } guard{h, h->groups};
-    if (h->groups == 0) h->groups = 1;
+    struct GroupsGuard { pgs_handle* h; int saved; ~GroupsGuard() { h->tune.groups = saved; } } guard{h, h->tune.groups};
+    if (h->tune.groups == 0) h->tune.groups = 1;
     for (int t = 0; t < T; ++t) {
         double t0 = prof ? now_ms() : 0.0;
-        h->p.N = h->timestep + 1;
         HIP_TRY(slam::pgs_launch_run_sim(h->p, 1, (uint32_t)h->timestep, h->stream));
-        h->timestep += 1;
-        h->p.N = h->timestep + 1;
+        advance(h, 1);
         if (prof) { HIP_TRY(hipStreamSynchronize(h->stream)); const double t1 = now_ms(); h->iter_ms[0] += t1 - t0; t0 = t1; }
         TRY(pgs_solve(h));
         h->iter_trials += h->last_trials;
@@ -935,7 +943,7 @@ int run_every_iteration(pgs_handle* h, int T, int32_t* counts) {
         HIP_TRY(hipMemcpyAsync(counts, h->d_tick, sizeof(int32_t) * 2 * (size_t)h->B, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
-    if (h->host_prof) fprintf(stderr, "pgs host clock over the run's trials: %.0f ms enqueuing, %.0f ms waiting for the trials' counters\n", h->host_launch_ms, h->host_wait_ms);
+    if (h->tune.host_prof) fprintf(stderr, "pgs host clock over the run's trials: %.0f ms enqueuing, %.0f ms waiting for the trials' counters\n", h->host_launch_ms, h->host_wait_ms);
     return SLAM_OK;
 }
 
@@ -1042,7 +1050,7 @@ int pgs_last_solve_paths_v2(pgs_handle* h, double* out, int n) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     double w[3];
     HIP_TRY(hipMemcpy(w, h->p.work, 3 * sizeof(double), hipMemcpyDeviceToHost));
-    const double v[8] = {w[0], w[1], h->path_ms[0], h->path_ms[1], w[2], h->path_ms[2], h->seg_ok ? 1.0 : 0.0, (double)(h->seg_ok ? h->seg_used : h->seg_len)};
+    const double v[8] = {w[0], w[1], h->path_ms[0], h->path_ms[1], w[2], h->path_ms[2], h->seg_ok ? 1.0 : 0.0, (double)(h->seg_ok ? h->seg_used : h->tune.seg_len)};
     for (int i = 0; i < n; ++i) out[i] = v[i];
     return SLAM_OK;
 }
@@ -1067,7 +1075,7 @@ int pgs_debug_prof2(pgs_handle* h, unsigned long long* out) {
     TRY(check(h));
     if (!h->p.prof) return fail(SLAM_ERR_STATE, "set SLAM_PGS_PROF before pgs_create");
     HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(out, h->p.prof + (size_t)h->B * h->lanes * 8, sizeof(unsigned long long) * 16 * (size_t)h->B, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, h->p.prof + (size_t)h->B * h->tune.lanes * 8, sizeof(unsigned long long) * 16 * (size_t)h->B, hipMemcpyDeviceToHost));
     return SLAM_OK;
 }
 

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "host/pgs_limits.h"
+
 namespace slam {
 
 enum { PGS_FLAG_POSE_CAP = 1, PGS_FLAG_LM_CAP = 2, PGS_FLAG_MEAS_CAP = 4, PGS_FLAG_NOT_CONVERGED = 8, PGS_FLAG_NONFINITE = 16 };
@@ -158,10 +160,7 @@ hipError_t pgs_launch_run_sim(const PgsParams& p, int T, uint32_t step0, hipStre
 hipError_t pgs_launch_lm_begin(const PgsParams& p, hipStream_t s);
 // the segments' column sets of every instance (from the graph alone; before pgs_launch_lm_begin of a solve)
 hipError_t pgs_launch_seg_plan(const PgsParams& p, hipStream_t s);
-static constexpr int kPgsSegMaxLen = 32;      // poses a segment holds at most (seg_len <= this)
-static constexpr int kPgsSegMaxLm = 63;       // landmarks a segment's column set may hold for the segmented path (2 * 63 + 1 = 127 columns)
-static constexpr int kPgsSegMaxSep = 128;     // separators the separator kernel stages in LDS
-static constexpr int kPgsSyrkInstTiles = 96;  // 32x32 tiles of S_ext pgs_syrk_inst_kernel holds per instance (16 wavefronts x SI_NB x SI_NS)
+// (kPgsSegMaxLen, kPgsSegMaxLm, kPgsSegMaxSep, kPgsSyrkInstTiles: host/pgs_limits.h)
 // one tryLambda for every active instance = kernels 0..5 in order: linearize, chain, syrk, chol, backsolve, evaluate (+ decide)
 static constexpr int kPgsTrialKernels = 6;
 hipError_t pgs_launch_trial_kernel(const PgsParams& p, int which, hipStream_t s);
