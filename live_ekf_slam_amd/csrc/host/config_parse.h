@@ -1,6 +1,6 @@
 // config_parse.h — the `key: value` reader behind slam_config_load (include/slam_batch.h): replaces YAML::LoadFile +
 // Filter::readCommonParams (localization_node.cpp:29-30, filter.h:105-121) for a params.yaml-shaped file.  Host-only, no HIP:
-// slam_capi.cpp includes it for the product, oracle/asan_main.cpp compiles it under ASan + UBSan and feeds it malformed files
+// slam_capi.cpp and capi_nav.cpp include it for the product, oracle/asan_main.cpp compiles it under ASan + UBSan and feeds it malformed files
 // (the text is untrusted input).  Unknown keys are ignored, missing keys keep their defaults, over-long lines are skipped
 // whole, values outside the target type's range are rejected instead of converted (float/int casts of out-of-range doubles
 // are undefined behaviour).

@@ -1,5 +1,5 @@
 // noise_pack.h - host side of slam_set_noise_each: validation of the caller's rows and their packing into what the step kernels read.
-// No HIP: included by slam_capi.cpp and by a stand-alone sanitizer driver (tests/test_noise_each_capi.py).
+// No HIP: included by the C ABI units (slam_capi.cpp, capi_innovation.cpp, capi_gate.cpp) and by a stand-alone sanitizer driver (tests/test_noise_each_capi.py).
 #pragma once
 #include <math.h>
 #include <stddef.h>
