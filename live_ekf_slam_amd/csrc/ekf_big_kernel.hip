@@ -5,7 +5,8 @@
 // covariance streamed through HBM / L2 for every phase.  It follows the reference's loop detection by detection (association, update or
 // insertion, in message order) - which also means a message may hold ANY number of detections here (read from the caller's buffer as it is
 // walked; no per-message capacity) - and evaluates every element with the same expressions in the same order as the fused kernel and the
-// oracle's MODE_FAST, so results are bit-identical to both.  It is slow by design (a pass over P per detection instead of one per group of
+// oracle's MODE_FAST (the functions of ekf_model.h, which both kernels call: this file holds the decomposition over 1024 threads, where the
+// operands live, the barriers and the flags), so results are bit-identical to both.  It is slow by design (a pass over P per detection instead of one per group of
 // deferred updates, a barrier per phase); SLAM_ERR_UNSUPPORTED for a legal reference configuration was the alternative.
 //
 // Working matrix: the step works on a copy of P in the handle's second buffer with the FIXED leading dimension ekf_ld(3 + 2 L_max) (no
@@ -19,8 +20,8 @@
 
 #include "../../include/slam_batch.h"
 #include "lds_attr.h"
+#include "ekf_model.h"
 #include "sim_device.h"
-#include "slam_math.h"
 #include "slam_rng.h"
 
 namespace slam {
@@ -104,34 +105,16 @@ __global__ __launch_bounds__(kBigTpb) void ekf_big_step_kernel(const EkfStepPara
 
     // ---- prediction (ekf.cpp:41-61): x_pred of the vehicle, P_pred = F_x P F_x^T + F_v V F_v^T into the working matrix ----
     {
-        const double th = s_xt[2];
-        double sn, cs;
-        det_sincos(th, &sn, &cs);
-        const double fa = (double)(-1 * fwd) * sn;   // F_x(0,2)
-        const double fb = (double)fwd * cs;          // F_x(1,2)
-        const float dd = fwd + nz.v_d;
-        const double cv = cs * nz.V00, sv = sn * nz.V00;
-        const double q00 = cv * cs, q01 = cv * sn, q10 = sv * cs, q11 = sv * sn;
+        const EkfMotion m = ekf_motion(s_xt[0], s_xt[1], s_xt[2], fwd, ang, nz.v_d, nz.v_th, nz.V00);
         __syncthreads();
-        if (tid == 0) {
-            s_xp[0] = s_xt[0] + (double)dd * cs;
-            s_xp[1] = s_xt[1] + (double)dd * sn;
-            s_xp[2] = rem2pi((th + (double)ang) + (double)nz.v_th);
-        }
+        if (tid == 0) { s_xp[0] = m.xp0; s_xp[1] = m.xp1; s_xp[2] = m.xp2; }
         const double p22 = (double)PA[(size_t)2 * ld0 + 2];
         for (int e = tid; e < n0 * n0; e += kBigTpb) {
             const int r = e / n0, c = e - r * n0;
-            double t = (double)PA[(size_t)r * ld0 + c];
-            const double f_r = r == 0 ? fa : fb;
-            if (r < 2) t = t + f_r * (double)PA[(size_t)2 * ld0 + c];   // rows 0, 1 of F_x P
-            if (c < 2) {                                               // cols 0, 1 of (F_x P) F_x^T
-                double a2 = (double)PA[(size_t)r * ld0 + 2];
-                if (r < 2) a2 = a2 + f_r * p22;
-                t = t + a2 * (c == 0 ? fa : fb);
-            }
-            if (r < 2 && c < 2) t = t + (r == 0 ? (c == 0 ? q00 : q01) : (c == 0 ? q10 : q11));   // + F_v V F_v^T
-            if (r == 2 && c == 2) t = t + nz.V11;
-            PB[(size_t)r * ldw + c] = t;
+            const double p2c = r < 2 ? (double)PA[(size_t)2 * ld0 + c] : 0.0;   // rows 0, 1 of F_x P
+            const double pr2 = c < 2 ? (double)PA[(size_t)r * ld0 + 2] : 0.0;   // cols 0, 1 of (F_x P) F_x^T
+            const double q_rc = r == 0 ? (c == 0 ? m.q00 : m.q01) : (c == 0 ? m.q10 : m.q11);   // F_v V F_v^T
+            PB[(size_t)r * ldw + c] = ekf_predicted((double)PA[(size_t)r * ld0 + c], r, c, p2c, pr2, p22, m.fa, m.fb, q_rc, nz.V11);
         }
     }
     __syncthreads();
@@ -178,53 +161,39 @@ __global__ __launch_bounds__(kBigTpb) void ekf_big_step_kernel(const EkfStepPara
             }
             if (tid == 0) {   // the scalar chain: Jacobian entries with the reference's float truncations, innovation
                 const double* const xl = p.lm_from_pred ? s_xp : s_xt;   // quirk D-2
-                const double dx = xl[ii] - s_xp[0], dy = xl[ii + 1] - s_xp[1];
-                const float dist = (float)sqrt(dx * dx + dy * dy);
-                const double dd = (double)dist, d2 = (double)(dist * dist);
-                s_sc[0] = -dx / dd; s_sc[1] = -dy / dd; s_sc[2] = dx / dd; s_sc[3] = dy / dd;           // H0 at columns 0, 1, ii, ii+1
-                s_sc[4] = dy / d2; s_sc[5] = -dx / d2; s_sc[6] = -dy / d2; s_sc[7] = dx / d2;           // H1 at columns 0, 1, ii, ii+1 (H1[2] = -1)
-                const float angf = (float)rem2pi(det_atan2(dy, dx) - s_xp[2]);
-                const float nu0f = r_m - dist - nz.w_r;
-                const float nu1f = b_m - angf - nz.w_b;
-                s_sc[8] = (double)nu0f; s_sc[9] = (double)nu1f;
+                const EkfRange g = ekf_range(xl[ii], xl[ii + 1], s_xp[0], s_xp[1]);
+                const EkfH hj = ekf_jacobian(g.dx, g.dy, g.dd, g.d2);
+                s_sc[0] = hj.h00; s_sc[1] = hj.h01; s_sc[2] = hj.h03; s_sc[3] = hj.h04;   // H0 at columns 0, 1, ii, ii+1
+                s_sc[4] = hj.h10; s_sc[5] = hj.h11; s_sc[6] = hj.h13; s_sc[7] = hj.h14;   // H1 at columns 0, 1, ii, ii+1 (H1[2] = -1)
+                const EkfVec2 nu = ekf_innovation(r_m, b_m, g.dist, g.dx, g.dy, s_xp[2], nz.w_r, nz.w_b);
+                s_sc[8] = nu.x; s_sc[9] = nu.y;
             }
             __syncthreads();
-            const double h00 = s_sc[0], h01 = s_sc[1], h03 = s_sc[2], h04 = s_sc[3];
-            const double h10 = s_sc[4], h11 = s_sc[5], h12 = -1.0, h13 = s_sc[6], h14 = s_sc[7];
+            const EkfH h = {s_sc[0], s_sc[1], s_sc[2], s_sc[3], s_sc[4], s_sc[5], s_sc[6], s_sc[7]};
             for (int c = tid; c < n; c += kBigTpb) {   // H P (rows of P) and P H^T (columns of P)
-                const double p0 = PB[c], p1 = PB[(size_t)ldw + c], p2 = PB[(size_t)2 * ldw + c];
-                const double pi = PB[(size_t)ii * ldw + c], pj = PB[(size_t)(ii + 1) * ldw + c];
-                s_HP[c] = ((h00 * p0 + h01 * p1) + h03 * pi) + h04 * pj;
-                s_HP[np + c] = (((h10 * p0 + h11 * p1) + h12 * p2) + h13 * pi) + h14 * pj;
+                const EkfVec2 g = ekf_hp_col(h, PB[c], PB[(size_t)ldw + c], PB[(size_t)2 * ldw + c], PB[(size_t)ii * ldw + c], PB[(size_t)(ii + 1) * ldw + c]);
+                s_HP[c] = g.x;
+                s_HP[np + c] = g.y;
                 const double* pr = PB + (size_t)c * ldw;
-                const double q0 = pr[0], q1 = pr[1], q2 = pr[2], qi = pr[ii], qj = pr[ii + 1];
-                s_K[2 * c] = ((q0 * h00 + q1 * h01) + qi * h03) + qj * h04;
-                s_K[2 * c + 1] = (((q0 * h10 + q1 * h11) + q2 * h12) + qi * h13) + qj * h14;
+                const EkfVec2 ph = ekf_pht_row(h, pr[0], pr[1], pr[2], pr[ii], pr[ii + 1]);
+                s_K[2 * c] = ph.x;
+                s_K[2 * c + 1] = ph.y;
             }
             __syncthreads();
             if (tid == 0) {   // S = (H P) H^T + W and its inverse (ekf.cpp:133-135)
-                const double* g0 = s_HP;
-                const double* g1 = s_HP + np;
-                double S[4], Si[4];
-                S[0] = ((g0[0] * h00 + g0[1] * h01) + g0[ii] * h03) + g0[ii + 1] * h04;
-                S[1] = (((g0[0] * h10 + g0[1] * h11) + g0[2] * h12) + g0[ii] * h13) + g0[ii + 1] * h14;
-                S[2] = ((g1[0] * h00 + g1[1] * h01) + g1[ii] * h03) + g1[ii + 1] * h04;
-                S[3] = (((g1[0] * h10 + g1[1] * h11) + g1[2] * h12) + g1[ii] * h13) + g1[ii + 1] * h14;
-                S[0] = S[0] + nz.W00;
-                S[3] = S[3] + nz.W11;
-                if (!inv2x2_lu(S, Si)) s_i[2] |= SLAM_INST_S_SINGULAR;
+                auto col = [&](int c) -> EkfVec2 { return EkfVec2{s_HP[c], s_HP[np + c]}; };
+                const EkfS S = ekf_S(h, col(0), col(1), col(2), col(ii), col(ii + 1), nz.W00, nz.W11);
+                double Si[4];
+                if (!inv2x2_lu(S.s, Si)) s_i[2] |= SLAM_INST_S_SINGULAR;
                 s_sc[10] = Si[0]; s_sc[11] = Si[1]; s_sc[12] = Si[2]; s_sc[13] = Si[3];
             }
             __syncthreads();
             {
                 const double si0 = s_sc[10], si1 = s_sc[11], si2 = s_sc[12], si3 = s_sc[13], nu0 = s_sc[8], nu1 = s_sc[9];
                 for (int r = tid; r < n; r += kBigTpb) {   // K = (P H^T) S^-1, x_pred += K nu
-                    const double a = s_K[2 * r], bb = s_K[2 * r + 1];
-                    const double k0 = a * si0 + bb * si2, k1 = a * si1 + bb * si3;
-                    s_K[2 * r] = k0; s_K[2 * r + 1] = k1;
-                    double xv = s_xp[r] + (k0 * nu0 + k1 * nu1);
-                    if (r == 2) xv = rem2pi(xv);
-                    s_xp[r] = xv;
+                    const EkfVec2 kk = ekf_gain(EkfVec2{s_K[2 * r], s_K[2 * r + 1]}, si0, si1, si2, si3);
+                    s_K[2 * r] = kk.x; s_K[2 * r + 1] = kk.y;
+                    s_xp[r] = ekf_state_update(s_xp[r], r, kk.x, kk.y, nu0, nu1);
                 }
             }
             __syncthreads();
@@ -235,8 +204,8 @@ __global__ __launch_bounds__(kBigTpb) void ekf_big_step_kernel(const EkfStepPara
                     const int r = e / nv, j = e - r * nv, c = 2 * j;
                     const double k0 = s_K[2 * r], k1 = s_K[2 * r + 1];
                     dbl2_t v = *reinterpret_cast<dbl2_t*>(PB + (size_t)r * ldw + c);
-                    v.x = v.x - (k0 * s_HP[c] + k1 * s_HP[np + c]);
-                    if (c + 1 < n) v.y = v.y - (k0 * s_HP[c + 1] + k1 * s_HP[np + c + 1]);
+                    v.x = ekf_downdate(v.x, k0, k1, s_HP[c], s_HP[np + c]);
+                    if (c + 1 < n) v.y = ekf_downdate(v.y, k0, k1, s_HP[c + 1], s_HP[np + c + 1]);
                     *reinterpret_cast<dbl2_t*>(PB + (size_t)r * ldw + c) = v;
                 }
             }
@@ -249,38 +218,29 @@ __global__ __launch_bounds__(kBigTpb) void ekf_big_step_kernel(const EkfStepPara
                 continue;
             }
             const int no = n;
-            const double phi = s_xp[2] + (double)b_m;
-            double s, c;
-            det_sincos(phi, &s, &c);
-            const double rd = (double)r_m;
-            const double g02 = -rd * s, g12 = rd * c;
+            const EkfInsert g = ekf_insert_geom(s_xp[0], s_xp[1], s_xp[2], r_m, b_m);
             __syncthreads();
             if (tid == 0) {
-                s_xp[no] = s_xp[0] + rd * c;
-                s_xp[no + 1] = s_xp[1] + rd * s;
+                s_xp[no] = g.lx;
+                s_xp[no + 1] = g.ly;
                 s_newid[M - M0] = p.id_known ? id : M;
             }
             for (int j = tid; j < no; j += kBigTpb) {   // new rows G_x P[0:3, :] and new columns P[:, 0:3] G_x^T
-                const double r0 = PB[j], r1 = PB[(size_t)ldw + j], r2 = PB[(size_t)2 * ldw + j];
-                PB[(size_t)no * ldw + j] = r0 + g02 * r2;
-                PB[(size_t)(no + 1) * ldw + j] = r1 + g12 * r2;
+                const double r2 = PB[(size_t)2 * ldw + j];
+                PB[(size_t)no * ldw + j] = ekf_insert_row(PB[j], g.g02, r2);
+                PB[(size_t)(no + 1) * ldw + j] = ekf_insert_row(PB[(size_t)ldw + j], g.g12, r2);
                 const double* pr = PB + (size_t)j * ldw;
                 const double c0 = pr[0], c1 = pr[1], c2 = pr[2];
-                PB[(size_t)j * ldw + no] = c0 + c2 * g02;
-                PB[(size_t)j * ldw + no + 1] = c1 + c2 * g12;
+                PB[(size_t)j * ldw + no] = ekf_insert_col(c0, c2, g.g02);
+                PB[(size_t)j * ldw + no + 1] = ekf_insert_col(c1, c2, g.g12);
             }
             __syncthreads();
             if (tid == 0) {   // corner: (G_x P_vv) G_x^T + (G_z W) G_z^T
-                const double gw00 = c * nz.W00, gw01 = g02 * nz.W11;
-                const double gw10 = s * nz.W00, gw11 = g12 * nz.W11;
                 const double* Ra = PB + (size_t)no * ldw;
                 const double* Rb = PB + (size_t)(no + 1) * ldw;
-                const double v00 = ((Ra[0] + Ra[2] * g02) + gw00 * c) + gw01 * g02;
-                const double v01 = ((Ra[1] + Ra[2] * g12) + gw00 * s) + gw01 * g12;
-                const double v10 = ((Rb[0] + Rb[2] * g02) + gw10 * c) + gw11 * g02;
-                const double v11 = ((Rb[1] + Rb[2] * g12) + gw10 * s) + gw11 * g12;
-                PB[(size_t)no * ldw + no] = v00; PB[(size_t)no * ldw + no + 1] = v01;
-                PB[(size_t)(no + 1) * ldw + no] = v10; PB[(size_t)(no + 1) * ldw + no + 1] = v11;
+                const EkfCorner v = ekf_insert_corner(Ra[0], Ra[1], Ra[2], Rb[0], Rb[1], Rb[2], g.g02, g.g12, g.c, g.s, nz.W00, nz.W11);
+                PB[(size_t)no * ldw + no] = v.v00; PB[(size_t)no * ldw + no + 1] = v.v01;
+                PB[(size_t)(no + 1) * ldw + no] = v.v10; PB[(size_t)(no + 1) * ldw + no + 1] = v.v11;
             }
             M += 1;
             n += 2;
@@ -317,8 +277,7 @@ __global__ __launch_bounds__(kBigTpb) void ekf_big_step_kernel(const EkfStepPara
         p.flags[b] = flags;
         p.timestep[b] = p.timestep[b] + 1;
         if (p.sim) {   // plotting_node.py:209-212 with the float32 wire format of EKFState.x_v / y_v
-            const double ex = (double)(float)s_xp[0] - s_sc[24], ey = (double)(float)s_xp[1] - s_sc[25];
-            p.err_sum[b] = p.err_sum[b] + sqrt(ex * ex + ey * ey);
+            p.err_sum[b] = p.err_sum[b] + ekf_position_error(s_xp[0], s_xp[1], s_sc[24], s_sc[25]);
             p.truth[3 * (size_t)b] = s_sc[24]; p.truth[3 * (size_t)b + 1] = s_sc[25]; p.truth[3 * (size_t)b + 2] = s_sc[26];
         }
     }

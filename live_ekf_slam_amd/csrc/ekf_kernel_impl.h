@@ -19,7 +19,8 @@
 //    No large register arrays: the kernel runs at high occupancy and has no upper limit on n other than LDS.
 //  More than KG detections in one step are processed in groups (a second pass over P; rare: P(k>4) ~ 0.3 %).
 //
-// Arithmetic: plain IEEE fp64 mul/add/div (-ffp-contract=off), operation order identical to the CPU oracle's
+// Arithmetic: the step's expressions are defined once in ekf_model.h (this kernel calls the ones that leave its code as it is and restates the rest);
+// plain IEEE fp64 mul/add/div (-ffp-contract=off), operation order identical to the CPU oracle's
 // MODE_FAST (oracle/slam_oracle.cpp) so results are bit-identical; float truncations of the reference
 // (ekf.cpp:43-44,57,75-76,115,129-131) are reproduced with real fp32 operations.
 #pragma once
@@ -30,7 +31,7 @@
 #include <type_traits>
 
 #include "../../include/slam_batch.h"
-#include "slam_math.h"
+#include "ekf_model.h"
 #include "slam_rng.h"
 #include "sim_device.h"
 

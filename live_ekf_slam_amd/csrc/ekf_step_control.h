@@ -1,12 +1,14 @@
 // ekf_step_control.h — part of the BODY of ekf_step_kernel (ekf_kernel_impl.h includes it inside the kernel function; round 6: the 1 840-line kernel split into its
 // parts, pure moves - every object file byte-identical).  The dependent scalar chain of one landmark update on one wavefront (`leader_chain`), group formation for known ids (`form_known`), the downdates of the thin rows / columns in LDS (`thin_downdate`, `thin_downdate_ctl`).
 // Lambdas and statements here capture the kernel's locals (p, tid, lane, the LDS arrays ...): not a stand-alone header.  DESIGN.md 4.1.
+//  Element expressions that compile to the parent's code as calls are calls into ekf_model.h (ekf_downdate, ekf_pred_row / ekf_pred_col, ekf_insert_row / ekf_insert_col); the others stay written out and name the model function they restate.
 
     // ---- the scalar chain of one landmark update (ekf.cpp:110-135), evaluated by ONE wavefront without a barrier: the eight
     //      quotients of H on eight lanes at once, atan2 beside them (independent chains in one instruction stream), the five
     //      columns of H P that S needs on five lanes, results passed between lanes as wave-uniform values (v_readlane).
     //      H = {H00, H01, H0i, H0i+1, H10, H11, H1i, H1i+1} (H12 = -1), innovation (nu0, nu1), Si = S^-1.  Every lane of the
     //      wavefront returns the same values.  false: zero pivot in the PartialPivLU of S. ----
+    // (written out: restates ekf_range, ekf_h_entry, ekf_innovation, ekf_hp_col and ekf_S of ekf_model.h)
     auto leader_chain = [&](int ii, int si, float r_m, float b_m, double (&H)[8], double& nu0, double& nu1, double (&Si)[4]) -> bool {
         const double* const xl = p.lm_from_pred ? s_xp : s_xt;   // quirk D-2 (ekf.cpp:115-116): the landmark is read from x_t
         const double dx = xl[ii] - s_xp[0], dy = xl[ii + 1] - s_xp[1];
@@ -124,8 +126,8 @@
                 if ((unsigned)t_s < (unsigned)nd) {   // wave-uniform
                     const double2 kt = Ku[t_s], ht = HPu[hpi(t_s)];
                     const int i = sl * LDP + j;
-                    s_R[i] = s_R[i] - (kt.x * hj.x + kt.y * hj.y);   // P[T_s][j]
-                    s_C[i] = s_C[i] - (kj.x * ht.x + kj.y * ht.y);   // P[j][T_s]
+                    s_R[i] = ekf_downdate(s_R[i], kt.x, kt.y, hj.x, hj.y);   // P[T_s][j]
+                    s_C[i] = ekf_downdate(s_C[i], kj.x, kj.y, ht.x, ht.y);   // P[j][T_s]
                 }
             }
         }
@@ -173,8 +175,8 @@
                     const int j = lane + 64 * u;
                     if (j < nd) {
                         const int i = sl * LDP + j;
-                        s_R[i] = rv[g][u] - (kt[g].x * hj[u].x + kt[g].y * hj[u].y);   // P[T_s][j]
-                        s_C[i] = cv[g][u] - (kj[u].x * ht[g].x + kj[u].y * ht[g].y);   // P[j][T_s]
+                        s_R[i] = ekf_downdate(rv[g][u], kt[g].x, kt[g].y, hj[u].x, hj[u].y);   // P[T_s][j]
+                        s_C[i] = ekf_downdate(cv[g][u], kj[u].x, kj[u].y, ht[g].x, ht[g].y);   // P[j][T_s]
                     }
                 }
             }

@@ -1,6 +1,7 @@
 // ekf_step_decoupled.h — part of the BODY of ekf_step_kernel (ekf_kernel_impl.h includes it inside the kernel function; round 6: the 1 840-line kernel split into its
 // parts, pure moves - every object file byte-identical).  The DECOUPLED steady-state loop: wavefront 0 runs the thin phases of consecutive timesteps and publishes updates in the ring, the other wavefronts stream them into P.
 // Lambdas and statements here capture the kernel's locals (p, tid, lane, the LDS arrays ...): not a stand-alone header.  DESIGN.md 4.1.
+//  Element expressions that compile to the parent's code as calls are calls into ekf_model.h (ekf_downdate, ekf_pred_row / ekf_pred_col, ekf_insert_row / ekf_insert_col); the others stay written out and name the model function they restate.
 
     // =====================================================================================================================
     // DECOUPLED STEADY-STATE LOOP.  As long as the steps ahead neither insert landmarks nor freeze, overflow or exceed KG
@@ -136,8 +137,8 @@
 #pragma unroll
                                     for (int g = 0; g < GB; ++g) {
                                         const double2 kt = Ku[ts[g]], ht = HPu[hpi(ts[g])];
-                                        rv[g] = rv[g] - (kt.x * hj.x + kt.y * hj.y);
-                                        cv[g] = cv[g] - (kj.x * ht.x + kj.y * ht.y);
+                                        rv[g] = ekf_downdate(rv[g], kt.x, kt.y, hj.x, hj.y);
+                                        cv[g] = ekf_downdate(cv[g], kj.x, kj.y, ht.x, ht.y);
                                         if constexpr (!kWide) {
                                             if (we) { rv[g] = (double)(ST)rv[g]; cv[g] = (double)(ST)cv[g]; }   // end of a timestep: storage rounding
                                         }
@@ -170,7 +171,7 @@
                         const double* const c2o = s_C + 2 * LDP;
                         const double fa = ps[3], fb = ps[4];
                         const double p22 = r2o[2];
-                        auto predicted = [&](double tv, int r, int cc) -> double {
+                        auto predicted = [&](double tv, int r, int cc) -> double {   // written out: restates ekf_predicted (ekf_model.h)
                             const double f_r = r == 0 ? fa : fb;
                             if (r < 2) tv = tv + f_r * r2o[cc];
                             if (cc < 2) {
@@ -199,10 +200,10 @@
                             const int j = lane + 64 * u;
                             if (j >= 2 && j < n) {
                                 const double r2 = r2o[j], c2 = c2o[j];
-                                s_R[j] = s_R[j] + fa * r2;
-                                s_R[LDP + j] = s_R[LDP + j] + fb * r2;
-                                s_C[j] = s_C[j] + c2 * fa;
-                                s_C[LDP + j] = s_C[LDP + j] + c2 * fb;
+                                s_R[j] = ekf_pred_row(s_R[j], fa, r2);
+                                s_R[LDP + j] = ekf_pred_row(s_R[LDP + j], fb, r2);
+                                s_C[j] = ekf_pred_col(s_C[j], c2, fa);
+                                s_C[LDP + j] = ekf_pred_col(s_C[LDP + j], c2, fb);
                             }
                         }
                         if (lane < 2) {   // the 2 x 2 corner (all terms)
@@ -238,6 +239,7 @@
                         double2 kreg[NU], hreg[NU];   // this lane's K[j], (H P)[j], j = lane + 64 u: the thin downdate takes them from here
 #pragma unroll
                         for (int u = 0; u < NU; ++u) { kreg[u] = make_double2(0.0, 0.0); hreg[u] = make_double2(0.0, 0.0); }
+                        // (written out: restates ekf_hp_col, ekf_pht_row, ekf_gain and ekf_state_update of ekf_model.h)
                         if (!SLAM_DBG(p.dbg & 512)) {   // (ablation 512: timing without H P / K / x)
                             const double h00 = H[0], h01 = H[1], h03 = H[2], h04 = H[3], h10 = H[4], h11 = H[5], h12 = -1.0, h13 = H[6], h14 = H[7];
                             const double* Ri = s_R + si * LDP;
@@ -284,7 +286,7 @@
                     if (ld_i(&s_ring[2])) break;   // watchdog fired: the instance is frozen below
                     SLAM_STAMP(23);  // thin downdates (+ loop)
                     // ---- end of the step: error statistic, x_t = x_pred (ekf.cpp:176), storage rounding ----
-                    if (p.sim && lane == 0) {   // plotting_node.py:209-212 with the float32 wire format of EKFState.x_v / y_v
+                    if (p.sim && lane == 0) {   // plotting_node.py:209-212 with the float32 wire format of EKFState.x_v / y_v (restates ekf_position_error)
                         const double* tru = s_tru + (tt % SD) * 6 + 3;   // true pose after this timestep
                         const double ex = (double)(float)s_xp[0] - tru[0], ey = (double)(float)s_xp[1] - tru[1];
                         s_keep[3] = s_keep[3] + sqrt(ex * ex + ey * ey);

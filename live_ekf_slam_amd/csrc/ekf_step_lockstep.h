@@ -1,6 +1,7 @@
 // ekf_step_lockstep.h — part of the BODY of ekf_step_kernel (ekf_kernel_impl.h includes it inside the kernel function; round 6: the 1 840-line kernel split into its
 // parts, pure moves - every object file byte-identical).  The barrier-synchronised timestep: insertions, unknown ids, freezes, more detections than the ring holds, single-step launches.
 // Lambdas and statements here capture the kernel's locals (p, tid, lane, the LDS arrays ...): not a stand-alone header.  DESIGN.md 4.1.
+//  Element expressions that compile to the parent's code as calls are calls into ekf_model.h (ekf_downdate, ekf_pred_row / ekf_pred_col, ekf_insert_row / ekf_insert_col); the others stay written out and name the model function they restate.
 
     int nf = n_old + 2 * n_ins;           // leading dimension of the matrix written this step
     nf = nf < NMAX ? nf : NMAX;
@@ -252,7 +253,7 @@
             const double* const c2o = s_C + 2 * LDP;   // P_t[.][2]
             const double fa = ps[3], fb = ps[4];
             const double p22 = r2o[2];
-            auto predicted = [&](double t, int r, int cc) -> double {
+            auto predicted = [&](double t, int r, int cc) -> double {   // written out: restates ekf_predicted (ekf_model.h)
                 const double f_r = r == 0 ? fa : fb;
                 if (r < 2) t = t + f_r * r2o[cc];                  // rows 0,1 of F_x * P
                 if (cc < 2) {                                      // cols 0,1 of (F_x P) F_x^T
@@ -333,6 +334,7 @@
                 double2* __restrict__ HPu = s_HP + nu * HPW;   // entry c at hpi(c)
                 double2* __restrict__ Ku = s_K + nu * LDP;
                 {   // every state index: its column of H P, its row of P H^T, K = P H^T S^-1, x_pred += K nu
+                    // (written out: restates ekf_hp_col, ekf_pht_row, ekf_gain and ekf_state_update of ekf_model.h)
                     const double h00 = s_sc[0], h01 = s_sc[1], h03 = s_sc[2], h04 = s_sc[3];
                     const double h10 = s_sc[4], h11 = s_sc[5], h12 = -1.0, h13 = s_sc[6], h14 = s_sc[7];
                     const double si0 = s_sc[10], si1 = s_sc[11], si2 = s_sc[12], si3 = s_sc[13];
@@ -373,7 +375,7 @@
                 // ---------------- landmark insertion, ekf.cpp:141-173 ----------------
                 const int sa = s_slot[ii], sb = sa + 1;
                 const int no = na;
-                if (tid == 0) {  // leader: G_x, G_z entries and the new landmark position
+                if (tid == 0) {  // leader: G_x, G_z entries and the new landmark position (written out: restates ekf_insert_geom)
                     const double phi = s_xp[2] + (double)b_m;
                     double s, c;
                     det_sincos(phi, &s, &c);
@@ -386,13 +388,13 @@
                 // new rows G_x P[0:3,:] and new cols P[:,0:3] G_x^T
 #pragma unroll 1
                 for (int j = td; j < no; j += TPB) {
-                    s_R[sa * LDP + j] = s_R[j] + g02 * s_R[2 * LDP + j];
-                    s_R[sb * LDP + j] = s_R[LDP + j] + g12 * s_R[2 * LDP + j];
-                    s_C[sa * LDP + j] = s_C[j] + s_C[2 * LDP + j] * g02;
-                    s_C[sb * LDP + j] = s_C[LDP + j] + s_C[2 * LDP + j] * g12;
+                    s_R[sa * LDP + j] = ekf_insert_row(s_R[j], g02, s_R[2 * LDP + j]);
+                    s_R[sb * LDP + j] = ekf_insert_row(s_R[LDP + j], g12, s_R[2 * LDP + j]);
+                    s_C[sa * LDP + j] = ekf_insert_col(s_C[j], s_C[2 * LDP + j], g02);
+                    s_C[sb * LDP + j] = ekf_insert_col(s_C[LDP + j], s_C[2 * LDP + j], g12);
                 }
                 __syncthreads();
-                if (tid == 0) {  // corner: (G_x P_vv) G_x^T + (G_z W) G_z^T
+                if (tid == 0) {  // corner: (G_x P_vv) G_x^T + (G_z W) G_z^T (written out: restates ekf_insert_corner)
                     const double c = s_sc[2], s = s_sc[3];
                     const double gw00 = c * nz.W00, gw01 = g02 * nz.W11;   // (G_z W) row 0
                     const double gw10 = s * nz.W00, gw11 = g12 * nz.W11;   // (G_z W) row 1
@@ -432,7 +434,7 @@
         // ---- the last wavefront first closes the books of this step and prepares the next one; it joins the stream
         //      when it is done (chunks are handed out dynamically, so the others simply take more of them) ----
         if (l1 >= k && (tid >> 6) == W - 1) {
-            if (p.sim && lane == 0) {  // plotting_node.py:209-212 with the float32 wire format of EKFState.x_v / y_v
+            if (p.sim && lane == 0) {  // plotting_node.py:209-212 with the float32 wire format of EKFState.x_v / y_v (restates ekf_position_error)
                 const double* tru = s_tru + (t % SD) * 6 + 3;   // true pose after this timestep
                 const double ex = (double)(float)s_xp[0] - tru[0], ey = (double)(float)s_xp[1] - tru[1];
                 s_keep[3] = s_keep[3] + sqrt(ex * ex + ey * ey);

@@ -88,7 +88,7 @@
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         const int kraw = s_kraw[tn % SD];
-        {   // x_pred of the vehicle (ekf.cpp:56-59) and the scalars of F_x, F_v V F_v^T (ekf.cpp:41-55)
+        {   // x_pred of the vehicle (ekf.cpp:56-59) and the scalars of F_x, F_v V F_v^T (ekf.cpp:41-55); written out: restates ekf_motion (ekf_model.h)
             const double x0 = (double)(ST)xv[0], x1 = (double)(ST)xv[1], th = (double)(ST)xv[2];
             double sn, cs;
             det_sincos(th, &sn, &cs);

@@ -1,6 +1,6 @@
 // ekf_step_stream.h — part of the BODY of ekf_step_kernel (ekf_kernel_impl.h includes it inside the kernel function; round 6: the 1 840-line kernel split into its
 // parts, pure moves - every object file byte-identical).  The passes over P in HBM: the in-place bulk stream with the deferred rank-2 updates (`stream_pass`), layout changes through the second buffer (`mid_pass`), vehicle rows / columns (`write_vehicle`), gathers of newly visible landmarks' rows (`pregather`).
-// Lambdas and statements here capture the kernel's locals (p, tid, lane, the LDS arrays ...): not a stand-alone header.  DESIGN.md 4.1.
+// Lambdas and statements here capture the kernel's locals (p, tid, lane, the LDS arrays ...): not a stand-alone header.  The downdate of an element is ekf_downdate (ekf_model.h).  DESIGN.md 4.1.
 
     struct PassArgs {
         const ST* src; ST* dst; double* mid;
@@ -100,7 +100,7 @@
                 for (int i = 0; i < R; ++i) {
                     const double2 kk = s_K[sw * LDP + rr[i]];
 #pragma unroll
-                    for (int e = 0; e < VEC; ++e) val[i][e] = val[i][e] - (kk.x * hp[e].x + kk.y * hp[e].y);
+                    for (int e = 0; e < VEC; ++e) val[i][e] = ekf_downdate(val[i][e], kk.x, kk.y, hp[e].x, hp[e].y);
                 }
                 if constexpr (!kWide) {
                     // fp32 storage rounds P at the end of every timestep; a group that spans several timesteps rounds
@@ -223,7 +223,7 @@
                     if (r < nsrc && c < nsrc) v = src_mid ? Pmid[(size_t)r * lds + c] : (double)Pin[(size_t)r * lds + c];
                     for (int w = 0; w < nu; ++w) {
                         const double2 kk = s_K[w * LDP + r], hh = s_HP[w * HPW + hpi(c)];
-                        v = v - (kk.x * hh.x + kk.y * hh.y);
+                        v = ekf_downdate(v, kk.x, kk.y, hh.x, hh.y);
                     }
                     const int scl = s_slot[c];
                     if (scl >= 0) v = s_C[scl * LDP + r];

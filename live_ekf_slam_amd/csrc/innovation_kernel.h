@@ -2,7 +2,8 @@
 // PRE-step state without touching the step kernel (slam_innovation, slam_innovation_run; gfx950).
 //
 // innovation_instance() below is THE definition: the device kernel (innovation_kernel.hip) and the host test hook
-// (slam_innovation_instance_host) compile this one function, with -ffp-contract=off on both sides, so the two give the same bits.
+// (slam_innovation_instance_host) compile this one function, with -ffp-contract=off on both sides, so the two give the same bits.  Its
+// arithmetic is the functions of ekf_model.h, the ones the step kernels call; what is written here is the plan, the walk and the statistics.
 //
 // Why a side kernel can do it.  Let J = {0, 1, 2} U {ii, ii + 1 : landmark slot of a detection of this message that is already mapped}.
 // In EKF::update (ekf.cpp:37-179, oracle/slam_oracle.cpp update_t / predict_fast / landmark_update_apply_fast) the prediction of rows and
@@ -34,7 +35,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "slam_math.h"
+#include "ekf_model.h"
 #if defined(__HIPCC__)
 #include "ekf_kernel.h"
 #endif
@@ -186,33 +187,25 @@ SLAM_HD InnovResult innovation_instance(const W& w, InnovWork& ws, LX load_x, LP
 
     // ---- predict (ekf.cpp:41-61, predict_fast) ----
     {
-        const double th = ws.x[2];
-        double s, c;
-        det_sincos(th, &s, &c);
-        const double a = (double)(-1 * fwd) * s;   // F_x(0,2)
-        const double b = (double)fwd * c;          // F_x(1,2)
-        const float dd = fwd + nz.v_d;             // float add, ekf.cpp:57
-        const double xp0 = ws.x[0] + (double)dd * c, xp1 = ws.x[1] + (double)dd * s;
-        const double xp2 = rem2pi((th + (double)ang) + (double)nz.v_th);
+        const EkfMotion m = ekf_motion(ws.x[0], ws.x[1], ws.x[2], fwd, ang, nz.v_d, nz.v_th, nz.V00);
         for (int cc = w.lane(); cc < nb; cc += w.width()) {   // rows 0, 1 of F_x P
             const double p2 = ws.P[2 * LD + cc];
-            ws.P[cc] = ws.P[cc] + a * p2;
-            ws.P[LD + cc] = ws.P[LD + cc] + b * p2;
-            ws.xp[cc] = cc == 0 ? xp0 : (cc == 1 ? xp1 : (cc == 2 ? xp2 : ws.x[cc]));
+            ws.P[cc] = ekf_pred_row(ws.P[cc], m.fa, p2);
+            ws.P[LD + cc] = ekf_pred_row(ws.P[LD + cc], m.fb, p2);
+            ws.xp[cc] = cc == 0 ? m.xp0 : (cc == 1 ? m.xp1 : (cc == 2 ? m.xp2 : ws.x[cc]));
         }
         w.sync();
         for (int r = w.lane(); r < nb; r += w.width()) {      // columns 0, 1 of (F_x P) F_x^T
             const double a2 = ws.P[r * LD + 2];
-            ws.P[r * LD + 0] = ws.P[r * LD + 0] + a2 * a;
-            ws.P[r * LD + 1] = ws.P[r * LD + 1] + a2 * b;
+            ws.P[r * LD + 0] = ekf_pred_col(ws.P[r * LD + 0], a2, m.fa);
+            ws.P[r * LD + 1] = ekf_pred_col(ws.P[r * LD + 1], a2, m.fb);
         }
         w.sync();
         if (w.lane() == 0) {                                   // + F_v V F_v^T
-            const double cv = c * nz.V00, sv = s * nz.V00;
-            ws.P[0] = ws.P[0] + cv * c;
-            ws.P[1] = ws.P[1] + cv * s;
-            ws.P[LD] = ws.P[LD] + sv * c;
-            ws.P[LD + 1] = ws.P[LD + 1] + sv * s;
+            ws.P[0] = ws.P[0] + m.q00;
+            ws.P[1] = ws.P[1] + m.q01;
+            ws.P[LD] = ws.P[LD] + m.q10;
+            ws.P[LD + 1] = ws.P[LD + 1] + m.q11;
             ws.P[2 * LD + 2] = ws.P[2 * LD + 2] + nz.V11;
         }
         w.sync();
@@ -227,32 +220,20 @@ SLAM_HD InnovResult innovation_instance(const W& w, InnovWork& ws, LX load_x, LP
         const int ii = 3 + 2 * q;
         const float r_m = ws.meas[3 * l + 1], b_m = ws.meas[3 * l + 2];
         const double* const xl = lm_from_pred ? ws.xp : ws.x;   // quirk D-2 (ekf.cpp:115-116): the landmark is read from x_t
-        const double dx = xl[ii] - ws.xp[0], dy = xl[ii + 1] - ws.xp[1];
-        const float dist = (float)sqrt(dx * dx + dy * dy);      // ekf.cpp:115 (float)
-        const double dd = (double)dist, d2 = (double)(dist * dist);
-        const double H0[5] = {-dx / dd, -dy / dd, 0.0, dx / dd, dy / dd};
-        const double H1[5] = {dy / d2, -dx / d2, -1.0, -dy / d2, dx / d2};
-        const float angf = (float)rem2pi(det_atan2(dy, dx) - ws.xp[2]);   // ekf.cpp:129
-        const float nu0f = r_m - dist - nz.w_r;                 // float arithmetic, ekf.cpp:130-131
-        const float nu1f = b_m - angf - nz.w_b;
-        const double nu0 = (double)nu0f, nu1 = (double)nu1f;
+        const EkfRange rg = ekf_range(xl[ii], xl[ii + 1], ws.xp[0], ws.xp[1]);   // ekf.cpp:115 (float)
+        const EkfH h = ekf_jacobian(rg.dx, rg.dy, rg.dd, rg.d2);
+        const EkfVec2 nu = ekf_innovation(r_m, b_m, rg.dist, rg.dx, rg.dy, ws.xp[2], nz.w_r, nz.w_b);   // ekf.cpp:129-131
+        const double nu0 = nu.x, nu1 = nu.y;
         for (int c = w.lane(); c < nb; c += w.width()) {        // H P (H0[2] == 0 is skipped)
-            const double p0 = ws.P[c], p1 = ws.P[LD + c], p2 = ws.P[2 * LD + c], pi = ws.P[ii * LD + c], pj = ws.P[(ii + 1) * LD + c];
-            ws.HP[c] = ((H0[0] * p0 + H0[1] * p1) + H0[3] * pi) + H0[4] * pj;
-            ws.HP[kInnovNb + c] = (((H1[0] * p0 + H1[1] * p1) + H1[2] * p2) + H1[3] * pi) + H1[4] * pj;
+            const EkfVec2 hp = ekf_hp_col(h, ws.P[c], ws.P[LD + c], ws.P[2 * LD + c], ws.P[ii * LD + c], ws.P[(ii + 1) * LD + c]);
+            ws.HP[c] = hp.x;
+            ws.HP[kInnovNb + c] = hp.y;
         }
         w.sync();
-        double S[4], Si[4];
-        {   // S = (H P) H^T + W (ekf.cpp:133)
-            const double* const h0 = ws.HP;
-            const double* const h1 = ws.HP + kInnovNb;
-            S[0] = ((h0[0] * H0[0] + h0[1] * H0[1]) + h0[ii] * H0[3]) + h0[ii + 1] * H0[4];
-            S[1] = (((h0[0] * H1[0] + h0[1] * H1[1]) + h0[2] * H1[2]) + h0[ii] * H1[3]) + h0[ii + 1] * H1[4];
-            S[2] = ((h1[0] * H0[0] + h1[1] * H0[1]) + h1[ii] * H0[3]) + h1[ii + 1] * H0[4];
-            S[3] = (((h1[0] * H1[0] + h1[1] * H1[1]) + h1[2] * H1[2]) + h1[ii] * H1[3]) + h1[ii + 1] * H1[4];
-            S[0] = S[0] + nz.W00;
-            S[3] = S[3] + nz.W11;
-        }
+        auto hp_col = [&](int c) -> EkfVec2 { return EkfVec2{ws.HP[c], ws.HP[kInnovNb + c]}; };
+        const EkfS Sm = ekf_S(h, hp_col(0), hp_col(1), hp_col(2), hp_col(ii), hp_col(ii + 1), nz.W00, nz.W11);   // S = (H P) H^T + W (ekf.cpp:133)
+        const double (&S)[4] = Sm.s;
+        double Si[4];
         const bool ok = inv2x2_lu(S, Si);
         double nis = nu0 * (Si[0] * nu0 + Si[1] * nu1) + nu1 * (Si[2] * nu0 + Si[3] * nu1);
         if (!ok) { flags |= kInnovSingular; nis = nan; }
@@ -284,17 +265,14 @@ SLAM_HD InnovResult innovation_instance(const W& w, InnovWork& ws, LX load_x, LP
         }
         for (int r = w.lane(); r < nb; r += w.width()) {        // K = (P H^T) S^-1 (ekf.cpp:135), x_pred += K nu (ekf.cpp:138)
             const double* const pr = ws.P + r * LD;
-            const double pa = ((pr[0] * H0[0] + pr[1] * H0[1]) + pr[ii] * H0[3]) + pr[ii + 1] * H0[4];
-            const double pb = (((pr[0] * H1[0] + pr[1] * H1[1]) + pr[2] * H1[2]) + pr[ii] * H1[3]) + pr[ii + 1] * H1[4];
-            const double k0 = pa * Si[0] + pb * Si[2], k1 = pa * Si[1] + pb * Si[3];
-            ws.K[2 * r] = k0; ws.K[2 * r + 1] = k1;
-            const double xn = ws.xp[r] + (k0 * nu0 + k1 * nu1);
-            ws.xp[r] = r == 2 ? rem2pi(xn) : xn;                // ekf.cpp:139
+            const EkfVec2 kk = ekf_gain(ekf_pht_row(h, pr[0], pr[1], pr[2], pr[ii], pr[ii + 1]), Si[0], Si[1], Si[2], Si[3]);
+            ws.K[2 * r] = kk.x; ws.K[2 * r + 1] = kk.y;
+            ws.xp[r] = ekf_state_update(ws.xp[r], r, kk.x, kk.y, nu0, nu1);   // ekf.cpp:139
         }
         w.sync();
         for (int e = w.lane(); e < nb * nb; e += w.width()) {   // P_pred -= K (H P) (ekf.cpp:140, the rank-2 form)
             const int r = e / nb, c = e - r * nb;
-            ws.P[r * LD + c] = ws.P[r * LD + c] - (ws.K[2 * r] * ws.HP[c] + ws.K[2 * r + 1] * ws.HP[kInnovNb + c]);
+            ws.P[r * LD + c] = ekf_downdate(ws.P[r * LD + c], ws.K[2 * r], ws.K[2 * r + 1], ws.HP[c], ws.HP[kInnovNb + c]);
         }
         w.sync();
     }
