@@ -9,6 +9,9 @@ namespace slam {
 
 // One launch = one timestep of EKF::update (ekf.cpp:37-179) for every instance of the batch, optionally
 // preceded (SIM mode) by the measurement generator get_cmd (sim_node.py:209-250) for the same instance.
+// ekf_step_kernel takes the block by value as its ONLY argument and reads the fields its steady-state loops do not need (write-back
+// pointers, simulator configuration, map, external measurements, dump, unknown-id switches, scratch) straight from the kernarg segment
+// where they are used (ekf_cold_params, ekf_kernel_impl.h): the block must stay the first thing in that segment.
 struct EkfStepParams {
     // ---- filter state in HBM ----
     // P and x are stored as fp64 (SLAM_F64) or fp32 (SLAM_F32); strides are in ELEMENTS of that type

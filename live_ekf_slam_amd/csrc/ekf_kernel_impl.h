@@ -144,6 +144,37 @@ __device__ __forceinline__ int opaque(int v) {
     return v;
 }
 
+// The parameter block where the launch put it: the by-value argument is the first thing in the kernarg segment.  A field read as
+// `p.field` is loaded at the kernel's entry and then lives in a scalar register - or a spill lane - until its last use, and the timestep
+// loop makes "until its last use" the whole launch.  The COLD fields (write-back pointers of `finish`, the simulator's configuration,
+// the map, external measurements, the unknown-id switches, the fp32 scratch buffer) are read through this pointer WHERE THEY ARE USED
+// instead: scalar loads from the constant address space, a few per use, none of them in the control wavefront's steady-state loop.
+// The empty asm keeps the optimiser from moving those loads back to the entry.  Same bytes, so the same values as `p.field`.
+typedef const __attribute__((address_space(4))) EkfStepParams* EkfColdParams;
+__device__ __forceinline__ EkfColdParams ekf_cold_params() {
+    EkfColdParams k = (EkfColdParams)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return k;
+}
+// what the measurement generator reads of a parameter block (sim_wave, sim_map / sim_map_size, sim_noise of sim_device.h take any block
+// with these members): `simgen` fills it from the cold fields when it runs
+struct EkfSimCold {   // sim_wave
+    uint64_t seed;
+    int64_t inst0;
+    double d_max, th_max, range_max, fov_min, fov_max;
+};
+struct EkfMapCold {   // sim_map, sim_map_size
+    const double* map;
+    const double* map_each;
+    const int32_t* L_each;
+    int32_t map_stride, L;
+};
+struct EkfSimNoiseCold {   // sim_noise
+    double sV00, sV11, sW00, sW11;
+    const NoiseRow* noise_each;
+    int32_t sim;
+};
+
 // value of `v` in lane `l` as a wave-uniform double (two v_readlane_b32)
 __device__ __forceinline__ double rdlane(double v, int l) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
@@ -157,6 +188,7 @@ __device__ __forceinline__ unsigned hi_abs(double v) {
 
 // MULTI = false: one timestep per launch (slam_step / slam_step_dev / slam_step_sim); MULTI = true: p.T timesteps per
 // launch with the per-instance state resident on chip (slam_run_sim).  Same code, the loop is compiled out for T = 1.
+// `p` must stay the kernel's FIRST argument and stay by value: ekf_cold_params() reads the cold fields at offset 0 of the kernarg segment.
 template <int NMAX, int W, int KG_, int UNR_, class ST, int PIPE, bool MULTI, int KP_ = 0>
 __global__ __launch_bounds__(64 * W, (W >= 2 ? 4 : SLAM_W1_WAVES)) void ekf_step_kernel(const EkfStepParams p) {
     using G = EkfGeom<NMAX, W, KG_, UNR_, KP_>;
@@ -203,13 +235,15 @@ __global__ __launch_bounds__(64 * W, (W >= 2 ? 4 : SLAM_W1_WAVES)) void ekf_step
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     // the instance's noise values: its row of slam_set_noise_each or the scalars of the block; read once, before anything is stored, and
-    // held in scalar registers for every timestep of the launch
-    const StepNoise nz = step_noise(p, b);
+    // held in scalar registers for every timestep of the launch (the filter's values; the simulator's half-widths are cold: `simgen`
+    // reads them from the same places when it runs)
+    const FilterNoise nz = filter_noise(p, b);
     if (p.long_mode == 1) {   // (workgroup-uniform) a message this size class cannot hold: the streamed kernel's launch takes the instance (ekf_kernel.h)
         const int kk = p.meas_count_in[b];
         if ((kk < p.k_stride_in ? kk : p.k_stride_in) > p.long_cap) return;
     }
 
+    const bool dump_meas = p.meas_out != nullptr;   // the dump's pointers themselves are cold (read where the dump is written)
     const bool prof_on = (p.dbg & 4) && p.prof != nullptr;
     unsigned long long tprev = prof_on ? __builtin_readcyclecounter() : 0ull;
     if (prof_on && tid < 64) p.prof[(size_t)blockIdx.x * kEkfProfSlots + tid] = 0ull;
@@ -309,10 +343,12 @@ __global__ __launch_bounds__(64 * W, (W >= 2 ? 4 : SLAM_W1_WAVES)) void ekf_step
     if (kraw > KCAP) flags |= SLAM_INST_CAPACITY;   // more detections in one message than the landmark capacity (only possible with repeated ids)
     const int k = kraw < KCAP ? kraw : KCAP;
     if (tid == 0) s_kh[k < 7 ? k : 7] += 1;
-    if (p.sim && p.meas_out != nullptr && t == T - 1) {
-        for (int i = tid; i < 3 * k && i < 3 * p.k_stride_out; i += TPB)
-            p.meas_out[(size_t)b * p.k_stride_out * 3 + i] = meas_t[i];
-        if (tid == 0) p.meas_count_out[b] = k;
+    if (p.sim && dump_meas && t == T - 1) {   // (cold fields: read here, once per launch)
+        const EkfColdParams pc = ekf_cold_params();
+        const int kso = pc->k_stride_out;
+        float* const mo = pc->meas_out + (size_t)b * kso * 3;
+        for (int i = tid; i < 3 * k && i < 3 * kso; i += TPB) mo[i] = meas_t[i];
+        if (tid == 0) pc->meas_count_out[b] = k;
     }
     // insertions this step; unknown ids: an upper bound - every detection could be a new landmark - but never more than the
     // capacity has room for (the matrix of this step is laid out for n_old + 2 n_ins: without the clamp a wide message at a full

@@ -25,7 +25,7 @@
             constexpr int kStepMax = sizeof(ST) == 8 ? KLOOP : (KLOOP < KG ? KLOOP : KG);
             return nx[0] <= kStepMax && nx[1] == 0 && nx[2] == 0 && nx[3] == 0;
         };
-        const bool fast_ok = p.id_known && p.meas_out == nullptr && fastable(t) &&
+        const bool fast_ok = p.id_known && !dump_meas && fastable(t) &&
                              !SLAM_DBG(p.dbg & (2 | 16 | 64));
         if (fast_ok) {
             const int n = na, ldn = ekf_ld(n, ESZ);

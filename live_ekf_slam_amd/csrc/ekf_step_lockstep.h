@@ -6,7 +6,7 @@
     int nf = n_old + 2 * n_ins;           // leading dimension of the matrix written this step
     nf = nf < NMAX ? nf : NMAX;
     ST* const Pout = (nf != n_old) ? (Pcur == PA ? PB : PA) : Pcur;   // in place unless the layout changes
-    double* const Pmid = kWide ? reinterpret_cast<double*>(Pout) : (p.scratch + (size_t)b * p.pstride);
+    double* const Pmid = kWide ? reinterpret_cast<double*>(Pout) : (ekf_cold_params()->scratch + (size_t)b * ekf_cold_params()->pstride);
 
     // x_pred of the vehicle (ekf.cpp:56-59) was computed by the pre-step; it is needed before the first group because
     // unknown-id association (ekf.cpp:82-98) projects detections with the PREDICTED pose.  The covariance part of the
@@ -87,11 +87,13 @@
                     const float x_det = (float)(s_xp[0] + (double)r_m * c);
                     const float y_det = (float)(s_xp[1] + (double)r_m * s);
                     idx = -2;
+                    const int abs_is_int = ekf_cold_params()->abs_is_int;   // (cold fields: only this path reads them)
+                    const float min_sep = ekf_cold_params()->min_sep;
 #pragma unroll 1
                     for (int j = 0; j < M_g; ++j) {
-                        const float xd = assoc_abs((double)x_det - s_xp[3 + 2 * j], p.abs_is_int);       // ekf.cpp:91-92: which `abs`
-                        const float yd = assoc_abs((double)y_det - s_xp[3 + 2 * j + 1], p.abs_is_int);
-                        if (xd < p.min_sep && yd < p.min_sep) { idx = j; break; }
+                        const float xd = assoc_abs((double)x_det - s_xp[3 + 2 * j], abs_is_int);       // ekf.cpp:91-92: which `abs`
+                        const float yd = assoc_abs((double)y_det - s_xp[3 + 2 * j + 1], abs_is_int);
+                        if (xd < min_sep && yd < min_sep) { idx = j; break; }
                     }
                     if (idx == -2) idx = (M_g < p.L_max && M_g < LMAX && na_g + 2 <= nf) ? M_g : -1;
                     if (idx == -1) s_misc[3] = 1;

@@ -5,27 +5,33 @@
     // state -> HBM at the end of the launch (or when the instance freezes): x_t lives in s_xt
     // `pre`: the instance freezes in its PRE-step state (x, P, timestep, error sum and the true pose alike)
     auto finish = [&](int steps_done, int Mf, int fl, bool pre) {
+        const EkfColdParams pc = ekf_cold_params();   // the write-back pointers are read here, not carried through the launch
         const int nfin = 3 + 2 * Mf;
         for (int i = tid; i < nfin; i += TPB) xb[i] = (ST)s_xt[i];
         if (Mf != M_init) {
-            for (int i = tid; i < Mf; i += TPB) p.ids[(size_t)b * p.L_max + i] = s_ids[i];
+            int32_t* const ids_b = pc->ids + (size_t)b * pc->L_max;
+            for (int i = tid; i < Mf; i += TPB) ids_b[i] = s_ids[i];
         }
+        // (pc->sim, not p.sim: the hot copy's live range then ends with the timestep loop instead of reaching the epilogue: read as p.sim here, the fp64
+        // L = 50 instantiation had more SGPR spills and its one-step kernel a 20-byte stack frame that nothing accesses)
+        const bool simf = pc->sim != 0;
         if (tid == 0) {
-            p.M[b] = Mf;
-            p.flags[b] = fl;
-            p.timestep[b] = ts0 + steps_done;
-            if (p.sim) p.err_sum[b] = s_keep[3];
+            pc->M[b] = Mf;
+            pc->flags[b] = fl;
+            pc->timestep[b] = ts0 + steps_done;
+            if (simf) pc->err_sum[b] = s_keep[3];
         }
         // true pose: before the frozen step, or after the last step of the launch (the generator never runs past it)
-        if (p.sim && tid < 3) {
+        if (simf && tid < 3) {
             const int tq = pre ? steps_done : steps_done - 1;
-            p.truth[3 * (size_t)b + tid] = steps_done == 0 && !pre ? s_keep[tid] : s_tru[(tq % SD) * 6 + (pre ? 0 : 3) + tid];
+            pc->truth[3 * (size_t)b + tid] = steps_done == 0 && !pre ? s_keep[tid] : s_tru[(tq % SD) * 6 + (pre ? 0 : 3) + tid];
         }
-        if (p.khist != nullptr && tid < 8 && s_kh[tid] != 0) atomicAdd(&p.khist[tid], (unsigned long long)s_kh[tid]);
-        if (p.khist != nullptr && tid >= 8 && tid < 12) {   // slam_traffic_counters: bytes of the P stream, other bytes, passes, updates
+        unsigned long long* const kh = pc->khist;
+        if (kh != nullptr && tid < 8 && s_kh[tid] != 0) atomicAdd(&kh[tid], (unsigned long long)s_kh[tid]);
+        if (kh != nullptr && tid >= 8 && tid < 12) {   // slam_traffic_counters: bytes of the P stream, other bytes, passes, updates
             const unsigned long long v = s_cnt[tid - 8] + (tid == 9 ? (unsigned long long)((nfin + 8) * ESZ / 8) : 0ull);
             const unsigned long long unit = tid == 8 ? 16ull : (tid == 9 ? 8ull : 1ull);
-            if (v != 0ull) atomicAdd(&p.khist[kEkfTrafficSlot + tid - 8], v * unit);
+            if (v != 0ull) atomicAdd(&kh[kEkfTrafficSlot + tid - 8], v * unit);
         }
     };
 
@@ -42,14 +48,17 @@
     // simgen(tn): the measurement generator for timestep tn (ONE wavefront) into ring slot tn % SD; advances the true pose.
     auto simgen = [&](int tn) {
         const int sq = tn % SD;
+        const EkfColdParams pc = ekf_cold_params();   // the generator's inputs are read here, not carried through the launch
         if (!p.sim) {
             // EXT mode: the message of timestep tn comes from the caller's queue in device memory,
             // meas_in[tn][b][k_stride][3] / meas_count_in[tn][b] (one timestep per launch: tn = 0)
-            int kk = p.meas_count_in[(size_t)tn * p.B + b];
-            kk = kk < p.k_stride_in ? kk : p.k_stride_in;
+            const int ksi = pc->k_stride_in;
+            const size_t row = (size_t)tn * pc->B + b;
+            int kk = pc->meas_count_in[row];
+            kk = kk < ksi ? kk : ksi;
             kk = kk < 0 ? 0 : kk;
             const int kc = kk < KCAP ? kk : KCAP;
-            const float* src = p.meas_in + ((size_t)tn * p.B + b) * p.k_stride_in * 3;
+            const float* src = pc->meas_in + row * ksi * 3;
             for (int i = lane; i < 3 * kc; i += 64) s_meas[sq * 3 * KCAP + i] = src[i];
             if (lane == 0) s_kraw[sq] = kk;
             return;
@@ -61,11 +70,15 @@
         const float ang_n = (MULTI || cp) ? cp[1] : p.ang;
         double tx = s_keep[0], ty = s_keep[1], tth = s_keep[2];
         if (lane == 0) { s_tru[sq * 6 + 0] = tx; s_tru[sq * 6 + 1] = ty; s_tru[sq * 6 + 2] = tth; }
-        const int Lm = sim_map_size(p, b);
-        const double* const map = sim_map(p, b);
+        // the simulator's configuration, the map and the half-widths from the cold fields, through the helpers every kernel uses
+        const EkfSimCold sc = {pc->seed, pc->inst0, pc->d_max, pc->th_max, pc->range_max, pc->fov_min, pc->fov_max};
+        const EkfMapCold mc = {pc->map, pc->map_each, pc->L_each, pc->map_stride, pc->L};
+        const EkfSimNoiseCold nc = {pc->sV00, pc->sV11, pc->sW00, pc->sW11, pc->noise_each, 1};
+        const int Lm = sim_map_size(mc, b);
+        const double* const map = sim_map(mc, b);
         const double lmx0 = lane < Lm ? map[2 * lane] : 0.0, lmy0 = lane < Lm ? map[2 * lane + 1] : 0.0;
-        const int kr = sim_wave<KCAP, false>(p, b, lane, fwd_n, ang_n, p.step + (uint32_t)tn, map, Lm, tx, ty, tth, lmx0, lmy0,
-                                             s_meas + sq * 3 * KCAP, nz.sim);   // the true pose goes to HBM in finish()
+        const int kr = sim_wave<KCAP, false>(sc, b, lane, fwd_n, ang_n, pc->step + (uint32_t)tn, map, Lm, tx, ty, tth, lmx0, lmy0,
+                                             s_meas + sq * 3 * KCAP, sim_noise(nc, b));   // the true pose goes to HBM in finish()
         if (lane == 0) {
             s_keep[0] = tx; s_keep[1] = ty; s_keep[2] = tth;
             s_tru[sq * 6 + 3] = tx; s_tru[sq * 6 + 4] = ty; s_tru[sq * 6 + 5] = tth;

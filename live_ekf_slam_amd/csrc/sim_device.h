@@ -99,10 +99,12 @@ __device__ __forceinline__ int sim_wave(const P& p, int b, int lane, float fwd, 
         }
         count += __popcll(mask);
     }
-    if (STORE_TRUTH && lane == 0) {
-        p.truth[3 * (size_t)b] = tx;
-        p.truth[3 * (size_t)b + 1] = ty;
-        p.truth[3 * (size_t)b + 2] = tth;
+    if constexpr (STORE_TRUTH) {   // (a block without `truth` may call the other form)
+        if (lane == 0) {
+            p.truth[3 * (size_t)b] = tx;
+            p.truth[3 * (size_t)b + 1] = ty;
+            p.truth[3 * (size_t)b + 2] = tth;
+        }
     }
     return count;   // the caller caps at KCAP and flags the overflow
 }
@@ -112,6 +114,20 @@ template <int KCAP, bool STORE_TRUTH = true, class P>
 __device__ __forceinline__ int sim_wave(const P& p, int b, int lane, float fwd, float ang, uint32_t step, const double* map, int L,
                                         double& tx, double& ty, double& tth, double lmx, double lmy, float* s_meas) {
     return sim_wave<KCAP, STORE_TRUTH>(p, b, lane, fwd, ang, step, map, L, tx, ty, tth, lmx, lmy, s_meas, sim_noise(p, b));
+}
+
+// ... and the filter's values alone, for a kernel whose generator reads the simulator's half-widths itself when it runs (the EKF step
+// kernel: sim_noise on its cold fields).  Same places and the same branch as the filter part of step_noise.
+struct FilterNoise { float v_d, v_th, w_r, w_b; double V00, V11, W00, W11; };
+template <class P>
+__device__ __forceinline__ FilterNoise filter_noise(const P& p, int b) {
+    FilterNoise s = {p.v_d, p.v_th, p.w_r, p.w_b, p.V00, p.V11, p.W00, p.W11};
+    if (p.noise_each) {
+        const NoiseRow* const r = p.noise_each + (size_t)b;
+        s.v_d = r->v_d; s.v_th = r->v_th; s.w_r = r->w_r; s.w_b = r->w_b;
+        s.V00 = r->V00; s.V11 = r->V11; s.W00 = r->W00; s.W11 = r->W11;
+    }
+    return s;
 }
 
 // The true map of instance b and its landmark count: its own (slam_set_maps) or the shared one.  The branch is on a pointer of the
