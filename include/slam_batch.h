@@ -495,7 +495,7 @@ int slam_innovation_instance_host(const double* x, const double* P, const int32_
  *   prediction is pending.
  * Not covered: the simulator sources (their step generates its own message inside the step kernel); slam_multi_*; the pose graph;
  *   multi-step launches (a gated step is one launch per tick); rejecting on anything but the individual NIS - there is no joint
- *   compatibility test, and a detection of an unmapped id is inserted ungated. */
+ *   compatibility test, and a detection of an unmapped id is inserted ungated (detections without ids: slam_associate, below). */
 enum slam_gate_verdict {
     SLAM_GATE_NOT_UPDATE = 0,   /* insertion, capacity skip, beyond the count, or any slot of a passed-through instance */
     SLAM_GATE_ACCEPTED = 1,
@@ -551,6 +551,95 @@ int slam_gate_instance_host(const double* x, const double* P, const int32_t* ids
                             const float* meas, int count, int k_stride, const slam_noise* noise, int lm_from_pred, int f32_storage,
                             const slam_gate_config* cfg, double rec[16], double* nis_sum, int32_t* n_upd, int32_t* n_new, int32_t* flags,
                             double* det, double* post, float* meas_out, int32_t* count_out, int32_t* n_rej, int32_t* verdict);
+
+/* ---- association of detections WITHOUT ids: nearest neighbour in Mahalanobis distance (csrc/assoc_kernel.h) ------------------------------
+ * slam_innovation, slam_gate and the known-id step assume every detection carries a landmark id.  A range-bearing sensor without fiducials
+ * gives (r, b) and nothing else; for it landmark_id_is_known = 0 offers the reference's rule (ekf.cpp:82-98), a box test on positions that
+ * ignores the covariance and runs inside the step's slow path.  slam_associate labels the message instead, from the PRE-step state, on a
+ * handle with landmark_id_is_known = 1: the unmodified known-id step then consumes the labelled message on its fast path, and
+ * slam_innovation or slam_gate can be put in between.  The id column of the incoming message is NOT READ.
+ * Cost: for detection l and mapped slot j < M, d2[l][j] is, bit for bit, the nis slam_innovation reports in slot 0 for the one-detection
+ *   message [(ids[j], r_l, b_l)] at the same state, command and noise row; NaN where the 2 x 2 inverse failed or nu or S is not finite.  The
+ *   quirk switch ekf_landmark_from_x_pred cannot matter: no update precedes a cost.
+ * Decisions per instance, count_in = min(max(count, 0), k_stride): per detection the best finite cost (ties: lowest j) and the second best.
+ *   INVALID: M > 0 and no finite cost.  NEW candidate: M == 0 or best > gate_new.  MATCH candidate: best <= gate_match.  AMBIGUOUS: the rest.
+ *   A landmark is seen at most once per message: among the MATCH candidates of one slot the smallest (d2, l) wins, the others are CONFLICT
+ *   and dropped.  NEW candidates in message order get rank 0, 1, ... and the id base + rank, base = 0 for M == 0, else 1 + max(ids[0 .. M));
+ *   a candidate is NO_ROOM when M + rank >= L_max or when its id is not below 2^24 (a message carries ids as floats).
+ * Output message: the MATCHED and NEW detections in message order as ((float)id, r, b), r and b copied bit for bit; count_out = their
+ *   number; the triplets count_out .. count_in - 1 written as 0.0f; nothing written from count_in up.  In place is allowed under the
+ *   gate's overlap rules.  Instances that cannot be associated emit an EMPTY message (count_out = 0, every verdict 0, the first count_in
+ *   triplets zeroed), so that an unlabelled id never reaches the step: status SLAM_INST_INDEX_OOR (flag SLAM_INNOVATION_INSTANCE_FROZEN)
+ *   and more than SLAM_INNOV_MAX_DET detections (flag SLAM_INNOVATION_TOO_LONG).  There is no limit on distinct landmarks.
+ * Outputs, any may be NULL: verdict [batch][SLAM_INNOV_MAX_DET] int32 (slam_assoc_verdict); slot [batch][SLAM_INNOV_MAX_DET] int32, the
+ *   best j or -1; det [batch][SLAM_INNOV_MAX_DET][4] doubles (d2_best, d2_second, nu_r, nu_b of the best), NaN where undefined; n_match,
+ *   n_new, n_drop (ambiguous + conflict + no room + invalid), flags [batch]; meas_out, count_out as the gate's.
+ * Record, 16 doubles: 0 instances evaluated, 1 FROZEN, 2 TOO_LONG, 3 detections in, 4 matched, 5 new, 6 ambiguous, 7 sum of d2_best over the
+ *   matched, 8 max of d2_best over the matched (0 over none), 9 conflict, 10 no room, 11 invalid, 12 - 15 reserved, 0; summed in the fixed
+ *   order of the innovation record.
+ * Honours slam_set_noise_each rows, both storage types and every capacity class (L_max <= 1000).
+ * Errors: SLAM_ERR_ARG (checked first, before the handle is looked at): gate_match or gate_new NaN, gate_match <= 0, gate_match > gate_new
+ *   (gate_new = +inf is allowed: localisation against the map that exists, only M == 0 inserts); NULL cmds, meas or meas_count,
+ *   k_stride <= 0, T < 0, outputs that overlap the inputs other than in place; NULL handle.  SLAM_ERR_UNSUPPORTED: the UKF kinds, and
+ *   handles with landmark_id_is_known = 0 (those associate inside their step).  SLAM_ERR_STATE: before slam_init; slam_step_associated*
+ *   and slam_associate_run also while slam_track_instance is on or a prediction is pending.
+ * Not covered: joint compatibility (JCBB); reassigning conflict losers; the ln det S term of the full likelihood; the simulator sources;
+ *   slam_multi_*; the pose graph; a fused associate-plus-gate call - chain slam_associate_dev and slam_step_gated_dev on device buffers. */
+enum slam_assoc_verdict {
+    SLAM_ASSOC_NONE = 0,        /* beyond the count, or any slot of an instance that emits an empty message */
+    SLAM_ASSOC_MATCHED = 1,
+    SLAM_ASSOC_NEW = 2,
+    SLAM_ASSOC_AMBIGUOUS = 3,   /* gate_match < best <= gate_new: dropped */
+    SLAM_ASSOC_CONFLICT = 4,    /* lost its landmark to a detection with a smaller (d2, l): dropped */
+    SLAM_ASSOC_NO_ROOM = 5,     /* a new landmark the map or the id range has no room for: dropped */
+    SLAM_ASSOC_INVALID = 6      /* no finite cost: dropped */
+};
+typedef struct slam_assoc_config {
+    double gate_match;   /* a detection matches its nearest landmark iff d2_best <= gate_match; > 0 */
+    double gate_new;     /* it is a new landmark iff d2_best > gate_new; >= gate_match, may be +inf */
+} slam_assoc_config;
+/* gate_match = -2 ln 0.01 = 9.210340371976182 and gate_new = -2 ln 1e-6 = 27.631021115928547: the 0.99 and 1 - 1e-6 quantiles of chi-square
+ * with 2 degrees of freedom */
+int slam_assoc_config_default(slam_assoc_config* cfg);
+/* Associates the message the next slam_step (cmd_each = 0: cmds [2]) or slam_step_each (cmd_each != 0: cmds [batch][2]) would be given
+ * and CHANGES NOTHING in the handle: a checkpoint before and after is byte-identical.  Host pointers; cfg NULL: the defaults.  meas_out /
+ * count_out may be meas / meas_count themselves, both or neither.  The message is staged on the device, so meas_out comes back whole:
+ * the slots the kernel does not write hold the input's values. */
+int slam_associate(slam_handle* h, const slam_assoc_config* cfg, const float* cmds, int cmd_each, const float* meas, const int32_t* meas_count,
+                   int k_stride, double rec[16], int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* flags, int32_t* verdict,
+                   int32_t* slot, double* det, float* meas_out, int32_t* count_out);
+/* The same with d_meas, d_count, (cmd_each != 0) cmds, d_meas_out and d_count_out as DEVICE pointers, read and written in stream order;
+ * d_meas_out and d_count_out are required.  In place is allowed; any other overlap is SLAM_ERR_ARG.  The other outputs are host pointers. */
+int slam_associate_dev(slam_handle* h, const slam_assoc_config* cfg, const float* cmds, int cmd_each, const float* d_meas,
+                       const int32_t* d_count, int k_stride, double rec[16], int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* flags,
+                       int32_t* verdict, int32_t* slot, double* det, float* d_meas_out, int32_t* d_count_out);
+/* One associated timestep: the association launches into a buffer the handle owns, then the ordinary one-step launch on the labelled
+ * message, all on the handle's stream; the caller's message is not written.  cmd_each as above (slam_step_associated_dev with
+ * cmd_each != 0: cmds is a device pointer).  rec [16] and n_drop [batch] (host) are optional: with both NULL the call does not synchronise. */
+int slam_step_associated(slam_handle* h, const slam_assoc_config* cfg, const float* cmds, int cmd_each, const float* meas,
+                         const int32_t* meas_count, int k_stride, double rec[16], int32_t* n_drop);
+int slam_step_associated_dev(slam_handle* h, const slam_assoc_config* cfg, const float* cmds, int cmd_each, const float* d_meas,
+                             const int32_t* d_count, int k_stride, double rec[16], int32_t* n_drop);
+/* T host-fed associated ticks in the layout of slam_gate_run: cmds [T][2] (cmd_each != 0: [T][batch][2]), meas [T][batch][k_stride][3],
+ * meas_count [T][batch].  The state advances bit for bit as T calls of slam_step_associated would leave it.  recs [T][16], n_match / n_new /
+ * n_drop / flags [T][batch]; any may be NULL.  Chunks of ticks by the rule of slam_innovation_run; chunking changes no bit. */
+int slam_associate_run(slam_handle* h, const slam_assoc_config* cfg, const float* cmds, int cmd_each, const float* meas,
+                       const int32_t* meas_count, int k_stride, int T, double* recs, int32_t* n_match, int32_t* n_new, int32_t* n_drop,
+                       int32_t* flags);
+/* What the association launches of the last slam_associate, slam_associate_dev or slam_associate_run had to move, and the device time of
+ * the last slam_associate_run.  bytes [2]: the model in bytes - per instance (3 n + 10 M) elements of P (rows 0 - 2 whole, per landmark
+ * P[ii .. ii + 1][0 .. 2] and the 2 x 2 diagonal block), x, ids and the message in and out - and the same with the reads of P counted in
+ * 128-byte lines (the strided column reads touch one line per row).  assoc_ms: the association launches alone, which needs
+ * slam_nav_set_timing(h, 1), else -1; total_ms: the whole run; both -1 before any slam_associate_run.  Any output may be NULL. */
+int slam_last_associate_work(slam_handle* h, double* bytes, double* assoc_ms, double* total_ms);
+/* TEST HOOK, not part of the filter interface: associate_instance() compiled for the HOST (the same source as the kernel, no device
+ * needed).  Arguments as slam_gate_instance_host (lm_from_pred is accepted and cannot matter).  Outputs, any may be NULL: rec [16], n_match,
+ * n_new, n_drop, flags, cost [count_in][M] the full matrix, verdict and slot [SLAM_INNOV_MAX_DET], det [SLAM_INNOV_MAX_DET][4],
+ * meas_out [k_stride][3] (may be meas), count_out. */
+int slam_associate_instance_host(const double* x, const double* P, const int32_t* ids, int M, int L_max, int32_t status, const float cmd[2],
+                                 const float* meas, int count, int k_stride, const slam_noise* noise, int lm_from_pred, int f32_storage,
+                                 const slam_assoc_config* cfg, double rec[16], int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* flags,
+                                 double* cost, int32_t* verdict, int32_t* slot, double* det, float* meas_out, int32_t* count_out);
 
 /* ---- closed loop: commands from each instance's own estimate (goal_pursuit_node.py:23-50, pure_pursuit.py:17-161) ---------------------
  * The entry points above run open loop: every command is fixed before the run.  The reference's default launch (sim_base.launch,

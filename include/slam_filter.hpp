@@ -70,6 +70,9 @@ struct InnovationRun { std::vector<double> recs, nis_sum; std::vector<int32_t> n
 // What stepGated returns (slam_step_gated*): the gate's record (entry 15 = rejected detections) and the [B] rejected counts.  The other
 // gate entry points (slam_gate, slam_gate_dev, slam_gate_run) are used through the C interface.
 struct GatedStep { double rec[16]; std::vector<int32_t> n_rej; };
+// What stepAssociated returns (slam_step_associated): the association's record (slam_associate in slam_batch.h) and the [B] dropped
+// detections.  The other association entry points (slam_associate, slam_associate_dev, slam_associate_run) are used through the C interface.
+struct AssociatedStep { double rec[16]; std::vector<int32_t> n_drop; };
 // One start pose per instance (pose0 [B][3] {x, y, yaw}), optional true start poses (truth0 [B][3], empty = the config's init pose);
 // maps [B][L_stride][2] with L [B] landmarks each; commands [B] of one timestep or [T][B][2] floats of a run.
 #define SLAM_FILTER_EACH_METHODS                                                                                                          \
@@ -181,6 +184,18 @@ struct GatedStep { double rec[16]; std::vector<int32_t> n_rej; };
         const std::vector<float> c = packCommands(cmds, each ? batch_ : 1);                                                              \
         GatedStep v; v.n_rej.resize(batch_);                                                                                             \
         check((each ? slam_step_gated_each : slam_step_gated)(h_, cfg, c.data(), meas, meas_count, k_stride, v.rec, v.n_rej.data()));    \
+        return v;                                                                                                                        \
+    }                                                                                                                                    \
+    /* one ASSOCIATED timestep (slam_step_associated; EKF-SLAM handles with known ids): detections WITHOUT ids are labelled by    */     \
+    /* nearest neighbour in Mahalanobis distance, then the ordinary step on the labelled message; the id column of meas is not read. */  \
+    /* cmds: one Command for the batch, or [B] of them; cfg NULL: gate_match 9.2103, gate_new 27.6310                               */   \
+    AssociatedStep stepAssociated(const std::vector<Command>& cmds, const float* meas, const int32_t* meas_count, int k_stride,          \
+                                  const slam_assoc_config* cfg = nullptr) {                                                              \
+        need();                                                                                                                          \
+        const bool each = cmds.size() != 1;                                                                                              \
+        const std::vector<float> c = packCommands(cmds, each ? batch_ : 1);                                                              \
+        AssociatedStep v; v.n_drop.resize(batch_);                                                                                       \
+        check(slam_step_associated(h_, cfg, c.data(), each ? 1 : 0, meas, meas_count, k_stride, v.rec, v.n_drop.data()));                \
         return v;                                                                                                                        \
     }
 

@@ -10,5 +10,8 @@ from .filters import BatchedEKF, BatchedUKF, BatchedUKFLoc, Command, MonitorResu
 from .filters import InnovationResult, innovation_summary, innovation_instance_host  # noqa: F401
 from .config import GateConfig, default_gate_config, GATE_NOT_UPDATE, GATE_ACCEPTED, GATE_REJECTED  # noqa: F401
 from .filters import GateResult, gate_instance_host  # noqa: F401
+from .config import AssocConfig, default_assoc_config  # noqa: F401
+from .config import ASSOC_NONE, ASSOC_MATCHED, ASSOC_NEW, ASSOC_AMBIGUOUS, ASSOC_CONFLICT, ASSOC_NO_ROOM, ASSOC_INVALID  # noqa: F401
+from .filters import AssocResult, associate_instance_host  # noqa: F401
 from .pose_graph import BatchedPoseGraph, NaiveFilter  # noqa: F401
 from ._lib import SlamError  # noqa: F401

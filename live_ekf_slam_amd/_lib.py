@@ -5,7 +5,7 @@ There is no CPU fallback: if the library is missing or a HIP call fails, an exce
 import ctypes as C
 import os
 
-from .config import SlamConfig, NavConfig, MonitorConfig, InnovationConfig, GateConfig, Noise
+from .config import SlamConfig, NavConfig, MonitorConfig, InnovationConfig, GateConfig, AssocConfig, Noise
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # SLAM_HIP_LIB: another build of the same library, for A/B tuning sessions (tools/gpu_ab.sh); the product path is the
@@ -89,6 +89,16 @@ SIGNATURES = {
     "slam_last_gate_work": (C.c_int, [_H, _dp, _dp]),
     "slam_gate_instance_host": (C.c_int, [_dp, _dp, _ip, C.c_int, C.c_int, C.c_int32, _fp, _fp, C.c_int, C.c_int, C.POINTER(Noise), C.c_int, C.c_int,
                                           C.POINTER(GateConfig), _dp, _dp, _ip, _ip, _ip, _dp, _dp, _fp, _ip, _ip, _ip]),
+    "slam_assoc_config_default": (C.c_int, [C.POINTER(AssocConfig)]),
+    "slam_associate": (C.c_int, [_H, C.POINTER(AssocConfig), _fp, C.c_int, _fp, _ip, C.c_int, _dp, _ip, _ip, _ip, _ip, _ip, _ip, _dp, _fp, _ip]),
+    "slam_associate_dev": (C.c_int, [_H, C.POINTER(AssocConfig), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, _dp, _ip, _ip, _ip, _ip, _ip,
+                                     _ip, _dp, C.c_void_p, C.c_void_p]),
+    "slam_step_associated": (C.c_int, [_H, C.POINTER(AssocConfig), _fp, C.c_int, _fp, _ip, C.c_int, _dp, _ip]),
+    "slam_step_associated_dev": (C.c_int, [_H, C.POINTER(AssocConfig), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, _dp, _ip]),
+    "slam_associate_run": (C.c_int, [_H, C.POINTER(AssocConfig), _fp, C.c_int, _fp, _ip, C.c_int, C.c_int, _dp, _ip, _ip, _ip, _ip]),
+    "slam_last_associate_work": (C.c_int, [_H, _dp, _dp, _dp]),
+    "slam_associate_instance_host": (C.c_int, [_dp, _dp, _ip, C.c_int, C.c_int, C.c_int32, _fp, _fp, C.c_int, C.c_int, C.POINTER(Noise), C.c_int,
+                                               C.c_int, C.POINTER(AssocConfig), _dp, _ip, _ip, _ip, _ip, _dp, _ip, _ip, _dp, _fp, _ip]),
     "slam_nav_config_default": (C.c_int, [C.POINTER(NavConfig)]),
     "slam_nav_config_load": (C.c_int, [C.POINTER(NavConfig), C.c_char_p]),
     "slam_nav_set_path": (C.c_int, [_H, C.POINTER(NavConfig), _dp, C.c_int]),

@@ -130,6 +130,20 @@ def default_gate_config() -> GateConfig:
     return GateConfig(-2.0 * math.log(0.001), -2.0 * math.log(0.975), -2.0 * math.log(0.025))
 
 
+class AssocConfig(C.Structure):
+    """ctypes mirror of `slam_assoc_config` (include/slam_batch.h): the match gate and the new-landmark gate on a detection's best cost."""
+    _fields_ = [("gate_match", C.c_double), ("gate_new", C.c_double)]
+
+
+ASSOC_NONE, ASSOC_MATCHED, ASSOC_NEW, ASSOC_AMBIGUOUS, ASSOC_CONFLICT, ASSOC_NO_ROOM, ASSOC_INVALID = range(7)   # slam_assoc_verdict
+
+
+def default_assoc_config() -> AssocConfig:
+    """gate_match = -2 ln 0.01 and gate_new = -2 ln 1e-6: the 0.99 and 1 - 1e-6 quantiles of chi-square with 2 degrees of freedom."""
+    import math
+    return AssocConfig(-2.0 * math.log(0.01), -2.0 * math.log(1e-6))
+
+
 def default_monitor_config() -> MonitorConfig:
     """The chi-square quantiles at 0.025 and 0.975 for 3 degrees of freedom; no full evaluation."""
     return MonitorConfig(0.21579528262389785, 9.348403604496148, 0)

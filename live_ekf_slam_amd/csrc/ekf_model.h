@@ -70,12 +70,17 @@ SLAM_HD EkfH ekf_jacobian(double dx, double dy, double dd, double d2) {
                 ekf_h_entry(4, dx, dy, dd, d2), ekf_h_entry(5, dx, dy, dd, d2), ekf_h_entry(6, dx, dy, dd, d2), ekf_h_entry(7, dx, dy, dd, d2)};
 }
 
-// Innovation (ekf.cpp:129-131): the bearing wrapped and truncated to float, both differences in float arithmetic.
-SLAM_HD EkfVec2 ekf_innovation(float r_m, float b_m, float dist, double dx, double dy, double xp2, float w_r, float w_b) {
-    const float angf = (float)rem2pi(det_atan2(dy, dx) - xp2);
+// Innovation (ekf.cpp:129-131): the bearing wrapped and truncated to float, both differences in float arithmetic.  In two halves: the
+// predicted bearing depends on the landmark and the pose alone, the differences on the detection (the association forms the first once
+// per landmark, assoc_kernel.h).
+SLAM_HD float ekf_predicted_bearing(double dx, double dy, double xp2) { return (float)rem2pi(det_atan2(dy, dx) - xp2); }
+SLAM_HD EkfVec2 ekf_innovation_from(float r_m, float b_m, float dist, float angf, float w_r, float w_b) {
     const float nu0f = r_m - dist - w_r;
     const float nu1f = b_m - angf - w_b;
     return EkfVec2{(double)nu0f, (double)nu1f};
+}
+SLAM_HD EkfVec2 ekf_innovation(float r_m, float b_m, float dist, double dx, double dy, double xp2, float w_r, float w_b) {
+    return ekf_innovation_from(r_m, b_m, dist, ekf_predicted_bearing(dx, dy, xp2), w_r, w_b);
 }
 
 // Column c of H P from P[0][c], P[1][c], P[2][c], P[i][c], P[i+1][c] (ekf.cpp:133; H02 == 0 is skipped, H12 = -1)

@@ -1,6 +1,6 @@
 // slam_handle.h — the handle of the filter ABI (include/slam_batch.h) and the host helpers that more than one of its translation units
 // uses (slam_capi.cpp: create / configure / init; capi_step.cpp: the steps and their queue; capi_state.cpp: reading the state back;
-// capi_consistency.cpp, capi_nav.cpp, capi_monitor.cpp, capi_innovation.cpp, capi_gate.cpp: one feature each).  Not installed, not part
+// capi_consistency.cpp, capi_nav.cpp, capi_monitor.cpp, capi_innovation.cpp, capi_gate.cpp, capi_assoc.cpp: one feature each).  Not installed, not part
 // of the ABI: the standing of capi_internal.h.
 #pragma once
 #include "../../include/slam_batch.h"
@@ -163,6 +163,15 @@ struct slam_handle {
         DevBuf<float> dmeas; DevBuf<int32_t> dcount, drej, dverdict;
         slam_capi::RunTimes times;
     } gate;
+    // slam_associate_*: the labelled message of an associated step or of one tick of slam_associate_run ([B][k_stride][3] and [B] counts),
+    // [5][ticks][B] n_match, n_new, n_drop, flags and landmarks compared with, [B][64] verdicts and slots, [B][64][4] detection slots, the three sums of the traffic
+    // model, what the last synchronising call read and the device times of the last slam_associate_run.  The incoming message, the
+    // per-instance contributions and the records are staged in `inn`.
+    struct Assoc {
+        DevBuf<float> dmeas; DevBuf<int32_t> dcount, dint, dverdict, dslot; DevBuf<double> ddet; DevBuf<unsigned long long> dwork;
+        double bytes = -1.0, lines = -1.0;
+        slam_capi::RunTimes times;
+    } assoc;
 };
 
 #pragma GCC visibility push(hidden)

@@ -18,6 +18,7 @@ from .config import Noise
 from .config import (InnovationConfig, default_innovation_config, INNOVATION_SHARED, INNOVATION_EACH, INNOVATION_NAV, INNOVATION_LOG,
                      INNOV_MAX_DET)
 from .config import GateConfig, default_gate_config
+from .config import AssocConfig, default_assoc_config
 
 
 def _d(a):
@@ -71,6 +72,17 @@ class GateResult(InnovationResult):
     def __init__(self, recs, nis_sum=None, n_upd=None, n_rej=None, flags=None):
         InnovationResult.__init__(self, recs, nis_sum, n_upd, flags)
         self.n_rej = n_rej
+
+
+class AssocResult:
+    """What associate_run returns: `recs`, the (T, 16) records of the ticks (columns: the REC_* constants; slam_associate in
+    include/slam_batch.h defines them), and - with series=True, else None - `n_match`, `n_new`, `n_drop`, `flags`, (T, batch) each."""
+
+    (REC_N_EVAL, REC_N_FROZEN, REC_N_TOO_LONG, REC_N_DET, REC_N_MATCHED, REC_N_NEW, REC_N_AMBIGUOUS, REC_SUM_D2, REC_MAX_D2, REC_N_CONFLICT,
+     REC_N_NO_ROOM, REC_N_INVALID) = range(12)
+
+    def __init__(self, recs, n_match=None, n_new=None, n_drop=None, flags=None):
+        self.recs, self.n_match, self.n_new, self.n_drop, self.flags = recs, n_match, n_new, n_drop, flags
 
 
 class BatchedFilter:
@@ -775,6 +787,120 @@ class BatchedEKF(BatchedFilter):
         _lib.check(_lib.lib().slam_last_gate_work(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    # -- detections without ids: nearest neighbour in Mahalanobis distance (slam_associate_*, include/slam_batch.h) --
+    def _assoc_config(self, cfg):
+        if cfg is None:
+            return default_assoc_config()
+        if isinstance(cfg, AssocConfig):
+            return cfg
+        c = default_assoc_config()
+        for k, v in dict(cfg).items():
+            if k not in ("gate_match", "gate_new"):
+                raise ValueError(f"unknown association setting {k!r}")
+            setattr(c, k, v)
+        return c
+
+    def _assoc_outputs(self, det):
+        B = self.batch
+        out = dict(rec=np.zeros(16), n_match=np.zeros(B, dtype=np.int32), n_new=np.zeros(B, dtype=np.int32), n_drop=np.zeros(B, dtype=np.int32),
+                   flags=np.zeros(B, dtype=np.int32), verdict=np.zeros((B, INNOV_MAX_DET), dtype=np.int32),
+                   slot=np.zeros((B, INNOV_MAX_DET), dtype=np.int32))
+        if det:
+            out["det"] = np.zeros((B, INNOV_MAX_DET, 4))
+        return out
+
+    def associate(self, cmdMsg, meas, meas_count, det=True, cfg=None):
+        """Labels a message whose id column is not read with landmark ids, from the state as it is and changing nothing: dict of rec (16,),
+        n_match, n_new, n_drop, flags [batch], verdict and slot (batch, INNOV_MAX_DET) (ASSOC_* verdicts; the best landmark slot or -1),
+        - det=True - det (batch, INNOV_MAX_DET, 4) = (d2_best, d2_second, nu_r, nu_b of the best), and the labelled message meas_out
+        (batch, k_stride, 3), count_out [batch]: update(cmdMsg, meas_out, count_out) is the associated step.  cfg: an AssocConfig, a dict of
+        its fields, or None."""
+        self._need()
+        cmd = self._cmd(cmdMsg)
+        m, cnt = self._message(meas, meas_count)
+        out = self._assoc_outputs(det)
+        out["meas_out"], out["count_out"] = np.zeros_like(m), np.zeros_like(cnt)
+        _lib.check(_lib.lib().slam_associate(self.h, C.byref(self._assoc_config(cfg)), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt), m.shape[1],
+                                             _d(out["rec"]), _i(out["n_match"]), _i(out["n_new"]), _i(out["n_drop"]), _i(out["flags"]),
+                                             _i(out["verdict"]), _i(out["slot"]), _d(out["det"]) if det else None, _f(out["meas_out"]),
+                                             _i(out["count_out"])))
+        return out
+
+    def associate_dev(self, cmdMsg, d_meas_ptr, d_count_ptr, k_stride, d_meas_out_ptr, d_count_out_ptr, det=True, cfg=None):
+        """associate() on DEVICE messages: cmdMsg one command (host) or, as an int, the device pointer of (batch, 2) commands; the labelled
+        message is written to d_meas_out_ptr / d_count_out_ptr, which may be the input pair itself (in place).  Returns the dict of
+        associate() without meas_out and count_out."""
+        self._need()
+        each = isinstance(cmdMsg, int)
+        cmd = None if each else self._cmd(cmdMsg)
+        if cmd is not None and cmd.ndim != 1:
+            raise ValueError("associate_dev takes one command, or the device pointer of per-instance commands")
+        out = self._assoc_outputs(det)
+        cp = C.c_void_p(cmdMsg) if each else C.cast(_f(cmd), C.c_void_p)
+        _lib.check(_lib.lib().slam_associate_dev(self.h, C.byref(self._assoc_config(cfg)), cp, int(each), C.c_void_p(d_meas_ptr),
+                                                 C.c_void_p(d_count_ptr), int(k_stride), _d(out["rec"]), _i(out["n_match"]), _i(out["n_new"]),
+                                                 _i(out["n_drop"]), _i(out["flags"]), _i(out["verdict"]), _i(out["slot"]),
+                                                 _d(out["det"]) if det else None, C.c_void_p(d_meas_out_ptr), C.c_void_p(d_count_out_ptr)))
+        return out
+
+    def step_associated(self, cmdMsg, meas, meas_count, stats=True, cfg=None):
+        """One associated timestep: the association, then the ordinary step on the labelled message, on the device.  cmdMsg one command or
+        (batch, 2); host message as associate().  stats=True returns dict(rec (16,), n_drop [batch]) and synchronises; stats=False None."""
+        self._need()
+        cmd = self._cmd(cmdMsg)
+        m, cnt = self._message(meas, meas_count)
+        out = dict(rec=np.zeros(16), n_drop=np.zeros(self.batch, dtype=np.int32)) if stats else None
+        _lib.check(_lib.lib().slam_step_associated(self.h, C.byref(self._assoc_config(cfg)), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt),
+                                                   m.shape[1], _d(out["rec"]) if stats else None, _i(out["n_drop"]) if stats else None))
+        self.timestep += 1
+        return out
+
+    def step_associated_dev(self, cmdMsg, d_meas_ptr, d_count_ptr, k_stride, stats=True, cfg=None):
+        """step_associated() on DEVICE messages; cmdMsg one command (host) or, as an int, the device pointer of (batch, 2) commands."""
+        self._need()
+        each = isinstance(cmdMsg, int)
+        cmd = None if each else self._cmd(cmdMsg)
+        if cmd is not None and cmd.ndim != 1:
+            raise ValueError("step_associated_dev takes one command, or the device pointer of per-instance commands")
+        out = dict(rec=np.zeros(16), n_drop=np.zeros(self.batch, dtype=np.int32)) if stats else None
+        cp = C.c_void_p(cmdMsg) if each else C.cast(_f(cmd), C.c_void_p)
+        _lib.check(_lib.lib().slam_step_associated_dev(self.h, C.byref(self._assoc_config(cfg)), cp, int(each), C.c_void_p(d_meas_ptr),
+                                                       C.c_void_p(d_count_ptr), int(k_stride), _d(out["rec"]) if stats else None,
+                                                       _i(out["n_drop"]) if stats else None))
+        self.timestep += 1
+        return out
+
+    def associate_run(self, cmds, meas, meas_count, series=False, cfg=None):
+        """T associated ticks of a recorded log without ids: cmds (T, 2) or (T, batch, 2), meas (T, batch, k_stride, 3), meas_count
+        (T, batch); the same bits as T step_associated calls.  Returns an AssocResult; series=True also records n_match, n_new, n_drop and
+        flags of every instance."""
+        self._need()
+        c32 = np.ascontiguousarray(cmds, dtype=np.float32)
+        m = np.ascontiguousarray(meas, dtype=np.float32)
+        cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
+        each = c32.ndim == 3
+        if c32.shape[1:] != ((self.batch, 2) if each else (2,)) or m.ndim != 4 or m.shape[:2] != (c32.shape[0], self.batch) or m.shape[2] == 0 \
+                or m.shape[3] != 3 or cnt.shape != m.shape[:2]:
+            raise ValueError(f"a log needs cmds (T, 2) or (T, {self.batch}, 2), meas (T, {self.batch}, k_stride > 0, 3) and meas_count (T, {self.batch})")
+        T = c32.shape[0]
+        res = AssocResult(np.zeros((T, 16)))
+        if series:
+            res.n_match, res.n_new, res.n_drop, res.flags = (np.zeros((T, self.batch), dtype=np.int32) for _ in range(4))
+        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
+        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
+        _lib.check(_lib.lib().slam_associate_run(self.h, C.byref(self._assoc_config(cfg)), _f(c32), int(each), _f(m), _i(cnt), m.shape[2], T,
+                                                 pd(res.recs), pi(res.n_match), pi(res.n_new), pi(res.n_drop), pi(res.flags)))
+        self.timestep += T
+        return res
+
+    def last_associate_work(self):
+        """(model bytes of the association launches of the last associate / associate_dev / associate_run, the same with the reads of P in
+        128-byte lines, device ms of the association launches of the last associate_run or -1 without set_nav_timing, device ms of that
+        whole run or -1)."""
+        self._need(); by = (C.c_double * 2)(); a = C.c_double(0); b = C.c_double(0)
+        _lib.check(_lib.lib().slam_last_associate_work(self.h, by, C.byref(a), C.byref(b)))
+        return by[0], by[1], a.value, b.value
+
 
 def innovation_instance_host(x, P, ids, L_max, status, cmd, meas, noise, lm_from_pred=False, f32_storage=False, cfg=None):
     """TEST HOOK (slam_innovation_instance_host): the per-instance function of the innovation kernel compiled for the host; no GPU.
@@ -819,6 +945,35 @@ def gate_instance_host(x, P, ids, L_max, status, cmd, meas, noise, lm_from_pred=
                                                   _d(out["rec"]), C.byref(s), C.byref(nu), C.byref(nn), C.byref(fl), _d(out["det"]),
                                                   _d(out["post"]), _f(out["meas_out"]), C.byref(co), C.byref(nr), _i(out["verdict"])))
     out.update(nis_sum=s.value, n_upd=nu.value, n_new=nn.value, flags=fl.value, count_out=co.value, n_rej=nr.value)
+    return out
+
+
+def associate_instance_host(x, P, ids, L_max, status, cmd, meas, noise, lm_from_pred=False, f32_storage=False, cfg=None, count=None, k_stride=None):
+    """TEST HOOK (slam_associate_instance_host): the per-instance function of the association kernel compiled for the host; no GPU.
+    Arguments as gate_instance_host (the id column of meas is not read).  Returns the dict of associate() for one instance, plus cost
+    (count_in, M), the full matrix; meas_out (k_stride, 3) starts as a copy of the input row."""
+    x = np.ascontiguousarray(x, dtype=np.float64); P = np.ascontiguousarray(P, dtype=np.float64)
+    ids = np.ascontiguousarray(ids, dtype=np.int32); M = ids.shape[0]
+    m = np.ascontiguousarray(meas, dtype=np.float32).reshape(-1, 3)
+    c = np.ascontiguousarray(cmd, dtype=np.float32).reshape(2)
+    if x.shape != (3 + 2 * M,) or P.shape != (3 + 2 * M, 3 + 2 * M):
+        raise ValueError("x and P do not match the number of ids")
+    ks = max(m.shape[0], 1) if k_stride is None else int(k_stride)
+    count = m.shape[0] if count is None else int(count)
+    if ks < m.shape[0]:
+        raise ValueError("k_stride is smaller than the message")
+    row = np.zeros((ks, 3), dtype=np.float32); row[:m.shape[0]] = m
+    k_in = min(max(count, 0), ks)
+    out = dict(rec=np.zeros(16), cost=np.full((k_in if k_in <= INNOV_MAX_DET else 0, M), np.nan), verdict=np.zeros(INNOV_MAX_DET, dtype=np.int32),
+               slot=np.zeros(INNOV_MAX_DET, dtype=np.int32), det=np.zeros((INNOV_MAX_DET, 4)), meas_out=row.copy())
+    nm = C.c_int32(0); nn = C.c_int32(0); nd = C.c_int32(0); fl = C.c_int32(0); co = C.c_int32(0)
+    c_cfg = default_assoc_config() if cfg is None else cfg
+    _lib.check(_lib.lib().slam_associate_instance_host(_d(x), _d(P), _i(ids) if M else None, M, int(L_max), int(status), _f(c), _f(row), count, ks,
+                                                       C.byref(noise), int(bool(lm_from_pred)), int(bool(f32_storage)), C.byref(c_cfg),
+                                                       _d(out["rec"]), C.byref(nm), C.byref(nn), C.byref(nd), C.byref(fl),
+                                                       _d(out["cost"]) if out["cost"].size else None, _i(out["verdict"]), _i(out["slot"]),
+                                                       _d(out["det"]), _f(out["meas_out"]), C.byref(co)))
+    out.update(n_match=nm.value, n_new=nn.value, n_drop=nd.value, flags=fl.value, count_out=co.value)
     return out
 
 
