@@ -42,8 +42,13 @@ enum slam_status_code {
  * reference where the corresponding condition throws and kills the node (filter.h:5 eigen_assert -> exception). */
 enum slam_instance_flags {
     SLAM_INST_OK = 0,
-    SLAM_INST_NONFINITE = 1,     /* x or P became non-finite                                                    */
-    SLAM_INST_S_SINGULAR = 2,    /* zero pivot while inverting the 2x2 innovation covariance (ekf.cpp:135)      */
+    SLAM_INST_NONFINITE = 1,     /* x or P became non-finite.  Checked after EVERY step of an instance that is not frozen, a step with an
+                                    empty message included: the bit is set iff some stored entry of x or P (after the rounding of fp32
+                                    storage) is not finite.  Sticky: no later step clears it.  The state is undefined from then on - its
+                                    values need not equal the CPU checker's - but the instance keeps stepping: M, ids and the timestep
+                                    follow the messages as for any other instance (a frozen instance, SLAM_INST_INDEX_OOR, does not step) */
+    SLAM_INST_S_SINGULAR = 2,    /* zero pivot while inverting the 2x2 innovation covariance (ekf.cpp:135).  Sticky as well; the step
+                                    goes on with the non-finite S^-1 (as the reference does), which SLAM_INST_NONFINITE then reports     */
     SLAM_INST_INDEX_OOR = 4,     /* landmark index outside x_t (ekf.cpp:115 under the duplicate/unknown-id quirk): a message repeats a
                                     NEW id that it has itself just inserted (a repeat of an id that found no room is skipped again, a
                                     repeat of a mapped id is a second update - as the reference's loop does, detection by detection) */

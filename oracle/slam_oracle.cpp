@@ -58,6 +58,16 @@ struct Ekf {
 
     int n() const { return 3 + 2 * M; }
 
+    // SLAM_INST_NONFINITE (slam_batch.h): after every step of a non-frozen instance, the empty message included, the flag is set iff some
+    // stored entry of x or P is not finite; it is never cleared.
+    int check_finite() {
+        bool fin = true;
+        for (double v : x_t) fin = fin && std::isfinite(v);
+        for (double v : P_t) fin = fin && std::isfinite(v);
+        if (!fin) flags |= SLAM_INST_NONFINITE;
+        return flags;
+    }
+
     bool storage_f32 = false;   // SLAM_F32: x_t and P_t are rounded to float whenever they are stored
     Ekf(const slam_config& c, int Lm, int mth, int md) : cfg(c), nz(effective_noise(c)), L_max(Lm), math(mth), mode(md & 1) {
         storage_f32 = (md & 2) != 0;
@@ -281,7 +291,7 @@ int Ekf::update_t(float fwd, float ang, const float* meas, int k) {
     if (k < 1) {                                     // ekf.cpp:67-71
         x_t = x_pred; P_t = P_pred;
         round_storage();
-        return flags;
+        return check_finite();
     }
     for (int l = 0; l < k; ++l) {                    // ekf.cpp:73
         const float r = meas[3 * l + 1], b = meas[3 * l + 2];
@@ -337,11 +347,7 @@ int Ekf::update_t(float fwd, float ang, const float* meas, int k) {
     }
     x_t = x_pred; P_t = P_pred;                      // ekf.cpp:176-177
     round_storage();
-    bool fin = true;
-    for (double v : x_t) fin = fin && std::isfinite(v);
-    for (double v : P_t) fin = fin && std::isfinite(v);
-    if (!fin) flags |= SLAM_INST_NONFINITE;
-    return flags;
+    return check_finite();
 }
 
 }  // namespace

@@ -105,7 +105,9 @@ def _check_record(rec, r, cfg_band, what):
 
 
 def _post_against_the_step(S, f, r, cmds, meas, cnt, what):
-    """after slam_innovation, the same handle is stepped with the same arguments: post rounded to storage = the pose and its block"""
+    """after slam_innovation, the same handle is stepped with the same arguments: post rounded to storage = the pose and its block; the
+    step raises SLAM_INST_S_SINGULAR for exactly the instances whose replay reported a singular S"""
+    before = f.status()
     f.update(cmds, meas, cnt)
     status = f.status()
     f32 = f.dtype == S.F32
@@ -117,6 +119,7 @@ def _post_against_the_step(S, f, r, cmds, meas, cnt, what):
         if fl & (IR.WOULD_FREEZE | IR.FROZEN | IR.TOO_LONG):
             continue
         assert not status[b] & IR.INST_INDEX_OOR, (what, b)
+        assert bool(status[b] & IR.INST_S_SINGULAR) == bool(fl & IR.S_SINGULAR or before[b] & IR.INST_S_SINGULAR), (what, b, int(status[b]), fl)
         st = f.get_state(b)
         _bits_equal(IR.post_as_stored(r["post"][b], f32), IR.oracle_post(st), f"{what}: post of instance {b} against the step")
         n += 1
