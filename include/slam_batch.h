@@ -646,6 +646,91 @@ int slam_associate_instance_host(const double* x, const double* P, const int32_t
                                  const slam_assoc_config* cfg, double rec[16], int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* flags,
                                  double* cost, int32_t* verdict, int32_t* slot, double* det, float* meas_out, int32_t* count_out);
 
+/* ---- map management: landmarks leave the map again (csrc/map_kernel.h) ------------------------------------------------------------------
+ * With slam_associate every detection farther than gate_new from the map becomes a landmark, and without the calls below nothing ever
+ * leaves the map: with clutter (a false return, a moving object seen twice) the state grows until slam_associate answers
+ * SLAM_ASSOC_NO_ROOM and SLAM_INST_CAPACITY sticks.  EKF handles only.
+ * Removal: slam_remove_landmarks takes remove [batch][L_max] int32, nonzero = drop this slot; entries at or above M[b] are ignored.  In
+ *   covariance form this is exact marginalisation: with the kept slots k0 < k1 < ... in their old order, x', ids' and P' are the
+ *   sub-vector and sub-matrix on the state indices {0, 1, 2} u {3 + 2 k, 4 + 2 k}, bit for bit (NaNs included), stored at the leading
+ *   dimension of the smaller state with zero pad columns; M' = M - removed; ids[M' .. L_max) and the track counters of those slots are
+ *   zeroed.  Status flags, timestep, truth and err_sum are not touched, and the status is not consulted: frozen or non-finite instances
+ *   move their bits like any other.  An instance with nothing to remove is not written at all.  The step kernels are unchanged: what is
+ *   left is an ordinary state of fewer landmarks.  A removed id that shows up again in a known-id message is inserted as NEW by the step,
+ *   and slam_associate's base = 1 + max id may hand a removed top id out again: an id names a landmark only while it is in the map.
+ * Record, 16 doubles: 0 instances touched, 1 landmarks removed, 2 elements of P moved (n'^2 per touched instance), 3 - 15 reserved, 0;
+ *   summed in the fixed order of the innovation record.
+ * Track evidence: seen and expected, [batch][L_max] int32 each, per-handle state OUTSIDE the checkpoint format, allocated by the first
+ *   call that needs them and zero after slam_init*, slam_load_state and slam_map_track_reset.  slam_map_tally, called after the step that
+ *   consumed the labelled message, adds for every slot j < M of the post-step state
+ *     seen_now = some triplet l < count has (int32)id == ids[j]          (an id that is NaN or outside int32 matches nothing)
+ *     in_view  = !(r > range_max * range_shrink) && beta > fov_min + fov_margin && beta < fov_max - fov_margin
+ *     seen[j] += seen_now;  expected[j] += seen_now || in_view
+ *   with r and beta of the estimated landmark from the estimated pose (the stored x, widened for fp32 storage), computed as the simulator
+ *   computes them for the true ones; range_max and fov_* are the handle's vision parameters (slam_set_vision).  An instance is skipped
+ *   whole when it is frozen (SLAM_INST_INDEX_OOR), failed (SLAM_INST_NONFINITE, SLAM_INST_WATCHDOG) or its assoc_flags entry is not 0.
+ * Prune rule: slam_map_prune removes slot j iff expected[j] >= min_expected && (double)seen[j] < min_ratio * (double)expected[j], decided
+ *   and compacted on the device in one launch; the counters of the kept slots move with them.
+ * Honours both storage types and every capacity class (L_max <= 1000).
+ * Errors: SLAM_ERR_ARG (checked first, before the handle is looked at): a NULL mask, message or count, k_stride <= 0, T < 0, a map config
+ *   with a NaN, range_shrink outside (0, 1], fov_margin < 0, min_expected < 1, min_ratio outside [0, 1] or prune_every < 1, the errors of
+ *   the association's arguments; NULL handle.  SLAM_ERR_UNSUPPORTED: the UKF kinds (their sqtP, Vt and ages would have to follow), and
+ *   for slam_step_managed* and slam_manage_run what slam_step_associated refuses.  SLAM_ERR_STATE: before slam_init, while
+ *   slam_track_instance is on, while a prediction is pending.  Every call runs the queued timesteps first.
+ * Not covered: merging duplicate landmarks; the UKF; slam_multi_*; the simulator sources; the pose graph; counters in checkpoints. */
+typedef struct slam_map_config {
+    double range_shrink;    /* a landmark is expected within range_max * range_shrink; in (0, 1] */
+    double fov_margin;      /* ... and at least this far inside the field of view, rad; >= 0 */
+    int32_t min_expected;   /* a slot is judged once it was expected this often; >= 1 */
+    double min_ratio;       /* ... and goes when seen / expected is below this; in [0, 1] */
+    int32_t prune_every;    /* slam_manage_run prunes after every prune_every-th tick; >= 1 */
+} slam_map_config;
+/* range_shrink 0.9, fov_margin 0.1, min_expected 10, min_ratio 0.3, prune_every 10 */
+int slam_map_config_default(slam_map_config* cfg);
+/* remove: host pointer.  n_removed [batch] and rec [16] (host) are optional: with both NULL the call does not synchronise. */
+int slam_remove_landmarks(slam_handle* h, const int32_t* remove, int32_t* n_removed, double rec[16]);
+/* The same with the mask as a DEVICE pointer, read in stream order; n_removed and rec are host pointers. */
+int slam_remove_landmarks_dev(slam_handle* h, const int32_t* d_remove, int32_t* n_removed, double rec[16]);
+/* The tally of one labelled message (host pointers; cfg NULL: the defaults); assoc_flags [batch] may be NULL.  Does not synchronise. */
+int slam_map_tally(slam_handle* h, const slam_map_config* cfg, const float* meas, const int32_t* meas_count, int k_stride,
+                   const int32_t* assoc_flags);
+/* The same with d_meas, d_count and d_assoc_flags as DEVICE pointers, read in stream order. */
+int slam_map_tally_dev(slam_handle* h, const slam_map_config* cfg, const float* d_meas, const int32_t* d_count, int k_stride,
+                       const int32_t* d_assoc_flags);
+/* The prune rule on the counters as they are, then the removal, without a host round trip.  rec [16], n_removed [batch]: as above. */
+int slam_map_prune(slam_handle* h, const slam_map_config* cfg, double rec[16], int32_t* n_removed);
+/* The counters, [batch][L_max] each (zeros before the first tally); either may be NULL. */
+int slam_map_get_track(slam_handle* h, int32_t* seen, int32_t* expected);
+int slam_map_track_reset(slam_handle* h);
+/* One managed timestep: the launches of slam_step_associated*, then the tally on the labelled message the handle owns, with the
+ * association's flags, all on the handle's stream.  Arguments as slam_step_associated*; with rec and n_drop NULL nothing synchronises. */
+int slam_step_managed(slam_handle* h, const slam_assoc_config* assoc_cfg, const slam_map_config* map_cfg, const float* cmds, int cmd_each,
+                      const float* meas, const int32_t* meas_count, int k_stride, double rec[16], int32_t* n_drop);
+int slam_step_managed_dev(slam_handle* h, const slam_assoc_config* assoc_cfg, const slam_map_config* map_cfg, const float* cmds, int cmd_each,
+                          const float* d_meas, const int32_t* d_count, int k_stride, double rec[16], int32_t* n_drop);
+/* T host-fed managed ticks in the layout of slam_associate_run; a prune follows tick t when (t + 1) % prune_every == 0, t counted within
+ * the run.  The state and the counters advance bit for bit as the loop of slam_step_managed and slam_map_prune would leave them.  recs
+ * [T][16], n_match / n_new / n_drop / flags [T][batch] as slam_associate_run; n_removed [T][batch], 0 on the ticks without a prune; any may
+ * be NULL.  Chunks of ticks by the rule of slam_innovation_run; chunking changes no bit. */
+int slam_manage_run(slam_handle* h, const slam_assoc_config* assoc_cfg, const slam_map_config* map_cfg, const float* cmds, int cmd_each,
+                    const float* meas, const int32_t* meas_count, int k_stride, int T, double* recs, int32_t* n_match, int32_t* n_new,
+                    int32_t* n_drop, int32_t* n_removed, int32_t* flags);
+/* What the removals of the last slam_remove_landmarks*, slam_map_prune or slam_manage_run (all its prunes) had to move, and the device
+ * times of the last slam_manage_run.  bytes: the model - per touched instance n'^2 elements of P read and written and its pads written,
+ * x, ids and the counters; per instance M, its mask row below M (a prune: its two counter rows) and n_removed: an instance with nothing
+ * to remove adds those few words and no P.  prune_ms: the prune launches alone, which needs slam_nav_set_timing(h, 1), else -1;
+ * total_ms: the whole run; both -1 before any slam_manage_run.  Synchronises.  Any output may be NULL. */
+int slam_last_map_work(slam_handle* h, double* bytes, double* prune_ms, double* total_ms);
+/* TEST HOOK, not part of the filter interface: the tally, the decision and the compaction of ONE instance compiled for the HOST from
+ * csrc/map_kernel.h (the source the kernels compile, no device needed), in this order: the tally of (meas, count, k_stride) when meas is
+ * not NULL (skipped by status and assoc_flag as on the device); then the removal of the slots of `remove` [M] (nonzero = drop) or, with
+ * remove NULL and prune != 0, of the slots the prune rule picks.  x [3 + 2 M], P [n][n] packed, ids [L_max], seen / expected [L_max]
+ * (may both be NULL without a tally or prune) are updated IN PLACE: P' is packed [n'][n'] at the front of P.  f32_storage: x and P are
+ * rounded to float first, as the handle stores them.  mask_out [L_max] (the decision, may be NULL), M_out. */
+int slam_map_instance_host(double* x, double* P, int32_t* ids, int M, int L_max, int32_t status, const float* meas, int count, int k_stride,
+                           int32_t assoc_flag, double range_max, double fov_min, double fov_max, int f32_storage, const slam_map_config* cfg,
+                           int32_t* seen, int32_t* expected, const int32_t* remove, int prune, int32_t* mask_out, int32_t* M_out);
+
 /* ---- closed loop: commands from each instance's own estimate (goal_pursuit_node.py:23-50, pure_pursuit.py:17-161) ---------------------
  * The entry points above run open loop: every command is fixed before the run.  The reference's default launch (sim_base.launch,
  * precompute_trajectory false) closes the loop instead: goal_pursuit_node computes each Command from the state the filter has just published.

@@ -13,5 +13,7 @@ from .filters import GateResult, gate_instance_host  # noqa: F401
 from .config import AssocConfig, default_assoc_config  # noqa: F401
 from .config import ASSOC_NONE, ASSOC_MATCHED, ASSOC_NEW, ASSOC_AMBIGUOUS, ASSOC_CONFLICT, ASSOC_NO_ROOM, ASSOC_INVALID  # noqa: F401
 from .filters import AssocResult, associate_instance_host  # noqa: F401
+from .config import MapConfig, default_map_config  # noqa: F401
+from .filters import MapResult, map_instance_host  # noqa: F401
 from .pose_graph import BatchedPoseGraph, NaiveFilter  # noqa: F401
 from ._lib import SlamError  # noqa: F401

@@ -144,6 +144,21 @@ def default_assoc_config() -> AssocConfig:
     return AssocConfig(-2.0 * math.log(0.01), -2.0 * math.log(1e-6))
 
 
+class MapConfig(C.Structure):
+    """ctypes mirror of `slam_map_config` (include/slam_batch.h): the shrunk view a landmark is expected in, the prune rule on its track
+    counters and the stride of the prunes of manage_run."""
+    _fields_ = [("range_shrink", C.c_double), ("fov_margin", C.c_double), ("min_expected", C.c_int32), ("min_ratio", C.c_double),
+                ("prune_every", C.c_int32)]
+
+
+MAP_CONFIG_FIELDS = tuple(name for name, _ in MapConfig._fields_)
+
+
+def default_map_config() -> MapConfig:
+    """range_shrink 0.9, fov_margin 0.1 rad, judged after 10 expectations, removed below a seen / expected ratio of 0.3, every 10 ticks."""
+    return MapConfig(0.9, 0.1, 10, 0.3, 10)
+
+
 def default_monitor_config() -> MonitorConfig:
     """The chi-square quantiles at 0.025 and 0.975 for 3 degrees of freedom; no full evaluation."""
     return MonitorConfig(0.21579528262389785, 9.348403604496148, 0)

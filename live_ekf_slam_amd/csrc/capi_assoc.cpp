@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "assoc_kernel.h"
+#include "capi_assoc.h"
 #include "capi_innovation.h"
 #include "capi_run.h"
 #include "ekf_kernel.h"
@@ -13,7 +14,7 @@
 
 using namespace slam_capi;
 
-namespace {
+namespace slam_capi {
 
 // *out = *cfg (NULL: the defaults), checked
 int assoc_config(const slam_assoc_config* cfg, slam_assoc_config* out) {
@@ -24,7 +25,7 @@ int assoc_config(const slam_assoc_config* cfg, slam_assoc_config* out) {
     return SLAM_OK;
 }
 
-bool assoc_overlap(const void* a, size_t na, const void* b, size_t nb) {
+static bool assoc_overlap(const void* a, size_t na, const void* b, size_t nb) {
     const char* const pa = (const char*)a; const char* const pb = (const char*)b;
     return pa < pb + nb && pb < pa + na;
 }
@@ -66,9 +67,6 @@ int assoc_step_state(const slam_handle* h, const char* who) {
     return SLAM_OK;
 }
 
-// the per-instance outputs of one association on the device ([5][ticks][B] counts, flags and landmarks; the detection slots when asked for)
-struct AssocDev { int32_t *n_match, *n_new, *n_drop, *flags, *n_lm, *verdict, *slot; double* det; };
-
 // the association launches of one message on the handle's stream
 int assoc_launch(slam_handle* h, const slam_assoc_config& c, const float cmd[2], const float* d_cmd_each, const float* d_meas, const int32_t* d_count,
                  int k_stride, float* d_meas_out, int32_t* d_count_out, double* d_rec, const AssocDev& d) {
@@ -97,6 +95,10 @@ int assoc_reserve(slam_handle* h, int k_stride, size_t ticks) {
     HIP_TRY(hipMemsetAsync(h->assoc.dwork, 0, 3 * sizeof(unsigned long long), h->stream));
     return SLAM_OK;
 }
+
+}  // namespace slam_capi
+
+namespace {
 
 // the traffic model of `ticks` associations whose counts are in dint ([5][stride] rows, the first ticks * B of each), summed on the stream
 int assoc_sum_work(slam_handle* h, size_t ticks, size_t stride) {

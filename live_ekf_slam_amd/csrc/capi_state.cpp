@@ -249,6 +249,7 @@ int slam_load_state(slam_handle* h, const char* path) {
     fclose(f);
     h->step = hd.step; h->inited = hd.inited != 0; h->seed = hd.seed; h->inst0 = hd.inst0;
     h->ukf.predicted = false;
+    TRY(map_track_reset(h));   // (the counters are no part of a checkpoint)
     if (h->shadow) {   // the tracked instance restarts from the loaded state
         const int tr = h->tracked;
         const int rc = slam_track_instance(h, tr);

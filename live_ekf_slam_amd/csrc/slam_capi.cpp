@@ -241,6 +241,7 @@ int slam_init(slam_handle* h, float x0, float y0, float yaw0) {
     h->step = 0;
     h->inited = true;
     TRY(nav_reset(h));
+    TRY(map_track_reset(h));
     if (h->shadow) return slam_init(h->shadow, x0, y0, yaw0);
     return SLAM_OK;
 }
@@ -309,6 +310,7 @@ int slam_init_each(slam_handle* h, const float* pose0, const double* truth0) {
     h->step = 0;
     h->inited = true;
     TRY(nav_reset(h));
+    TRY(map_track_reset(h));
     if (h->shadow) return slam_init_each(h->shadow, pose0 + 3 * (size_t)h->tracked, truth0 ? truth0 + 3 * (size_t)h->tracked : nullptr);
     return SLAM_OK;
 }

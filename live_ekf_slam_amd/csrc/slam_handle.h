@@ -1,6 +1,6 @@
 // slam_handle.h — the handle of the filter ABI (include/slam_batch.h) and the host helpers that more than one of its translation units
 // uses (slam_capi.cpp: create / configure / init; capi_step.cpp: the steps and their queue; capi_state.cpp: reading the state back;
-// capi_consistency.cpp, capi_nav.cpp, capi_monitor.cpp, capi_innovation.cpp, capi_gate.cpp, capi_assoc.cpp: one feature each).  Not installed, not part
+// capi_consistency.cpp, capi_nav.cpp, capi_monitor.cpp, capi_innovation.cpp, capi_gate.cpp, capi_assoc.cpp, capi_map.cpp: one feature each).  Not installed, not part
 // of the ABI: the standing of capi_internal.h.
 #pragma once
 #include "../../include/slam_batch.h"
@@ -172,6 +172,15 @@ struct slam_handle {
         double bytes = -1.0, lines = -1.0;
         slam_capi::RunTimes times;
     } assoc;
+    // slam_remove_landmarks / slam_map_*: the track counters seen and expected ([B][L_max] each, allocated on first use and outside the
+    // checkpoint format; tracked: they exist), the staged mask of a host-pointer removal ([B][L_max]), [2][ticks][B] n_removed and the M
+    // before, the record, the three sums of the traffic model (work_set: a removal has filled them) and the device times of the last
+    // slam_manage_run
+    struct Map {
+        DevBuf<int32_t> dseen, dexpected, dmask, dint; DevBuf<double> drec; DevBuf<unsigned long long> dwork;
+        bool tracked = false, work_set = false;
+        slam_capi::RunTimes times;
+    } map;
 };
 
 #pragma GCC visibility push(hidden)
@@ -215,6 +224,10 @@ int flush_lazy(slam_handle* h);
 // The launch parameters of launch_consistency at the handle's current state, with its output buffers and workspace reserved; *chunk_out:
 // instances per launch of the workspace class.
 int consistency_params(slam_handle* h, slam::ConsistencyParams* out, int* chunk_out);
+
+// ---- capi_map.cpp
+// slam_init / slam_init_each / slam_load_state: the track counters, where they exist, are zero again, in stream order
+int map_track_reset(slam_handle* h);
 
 // ---- capi_nav.cpp
 // slam_init / slam_init_each / setting a path: head = 0, integ = err_prev = 0, finish_tick = -1 for every instance, in stream order

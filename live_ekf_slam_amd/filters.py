@@ -19,6 +19,7 @@ from .config import (InnovationConfig, default_innovation_config, INNOVATION_SHA
                      INNOV_MAX_DET)
 from .config import GateConfig, default_gate_config
 from .config import AssocConfig, default_assoc_config
+from .config import MapConfig, default_map_config, MAP_CONFIG_FIELDS
 
 
 def _d(a):
@@ -83,6 +84,18 @@ class AssocResult:
 
     def __init__(self, recs, n_match=None, n_new=None, n_drop=None, flags=None):
         self.recs, self.n_match, self.n_new, self.n_drop, self.flags = recs, n_match, n_new, n_drop, flags
+
+
+class MapResult(AssocResult):
+    """What manage_run returns: `recs` (T, 16) and - with series=True, else None - `n_match`, `n_new`, `n_drop`, `flags` as AssocResult, and
+    `n_removed` (T, batch), the landmarks each prune took (0 on the ticks without one).  The REC_MAP_* constants index the (16,) record of
+    remove_landmarks and map_prune."""
+
+    REC_MAP_TOUCHED, REC_MAP_REMOVED, REC_MAP_MOVED = range(3)
+
+    def __init__(self, recs, n_match=None, n_new=None, n_drop=None, flags=None, n_removed=None):
+        AssocResult.__init__(self, recs, n_match, n_new, n_drop, flags)
+        self.n_removed = n_removed
 
 
 class BatchedFilter:
@@ -900,6 +913,164 @@ class BatchedEKF(BatchedFilter):
         self._need(); by = (C.c_double * 2)(); a = C.c_double(0); b = C.c_double(0)
         _lib.check(_lib.lib().slam_last_associate_work(self.h, by, C.byref(a), C.byref(b)))
         return by[0], by[1], a.value, b.value
+
+
+    # -- map management: landmarks leave the map again (slam_remove_landmarks, slam_map_*, include/slam_batch.h) --
+    def _map_config(self, cfg):
+        if cfg is None:
+            return default_map_config()
+        if isinstance(cfg, MapConfig):
+            return cfg
+        c = default_map_config()
+        for k, v in dict(cfg).items():
+            if k not in MAP_CONFIG_FIELDS:
+                raise ValueError(f"unknown map setting {k!r}")
+            setattr(c, k, v)
+        return c
+
+    def remove_landmarks(self, remove, stats=True):
+        """Drops the slots whose entry of remove (batch, L_max) is nonzero (entries at or above an instance's landmark count are ignored):
+        exact marginalisation, x, P and ids compacted on the device bit for bit.  remove as an int: the DEVICE pointer of the mask.
+        stats=True returns dict(rec (16,), n_removed [batch]) and synchronises; stats=False None."""
+        self._need()
+        out = dict(rec=np.zeros(16), n_removed=np.zeros(self.batch, dtype=np.int32)) if stats else None
+        nr, rec = (_i(out["n_removed"]), _d(out["rec"])) if stats else (None, None)
+        if isinstance(remove, int):
+            _lib.check(_lib.lib().slam_remove_landmarks_dev(self.h, C.c_void_p(remove), nr, rec))
+        else:
+            m = np.ascontiguousarray(remove, dtype=np.int32)
+            if m.shape != (self.batch, self.L_max):
+                raise ValueError(f"remove: expected shape ({self.batch}, {self.L_max}), got {m.shape}")
+            _lib.check(_lib.lib().slam_remove_landmarks(self.h, _i(m), nr, rec))
+        return out
+
+    def map_tally(self, meas, meas_count, assoc_flags=None, cfg=None):
+        """Adds the evidence of one labelled message to the track counters, after the step that consumed it: host message as associate();
+        assoc_flags [batch] or None.  meas as an int: DEVICE pointers (meas, meas_count = (pointer, k_stride), assoc_flags or None)."""
+        self._need()
+        c = self._map_config(cfg)
+        if isinstance(meas, int):
+            d_count, k_stride = meas_count
+            _lib.check(_lib.lib().slam_map_tally_dev(self.h, C.byref(c), C.c_void_p(meas), C.c_void_p(d_count), int(k_stride),
+                                                     None if assoc_flags is None else C.c_void_p(assoc_flags)))
+            return
+        m, cnt = self._message(meas, meas_count)
+        fl = None if assoc_flags is None else np.ascontiguousarray(assoc_flags, dtype=np.int32)
+        if fl is not None and fl.shape != (self.batch,):
+            raise ValueError(f"assoc_flags: expected shape ({self.batch},), got {fl.shape}")
+        _lib.check(_lib.lib().slam_map_tally(self.h, C.byref(c), _f(m), _i(cnt), m.shape[1], None if fl is None else _i(fl)))
+
+    def map_prune(self, stats=True, cfg=None):
+        """Removes the slots the prune rule picks from the track counters, decided and compacted on the device.  Returns as remove_landmarks."""
+        self._need()
+        out = dict(rec=np.zeros(16), n_removed=np.zeros(self.batch, dtype=np.int32)) if stats else None
+        _lib.check(_lib.lib().slam_map_prune(self.h, C.byref(self._map_config(cfg)), _d(out["rec"]) if stats else None,
+                                             _i(out["n_removed"]) if stats else None))
+        return out
+
+    def map_track(self):
+        """(seen, expected), (batch, L_max) int32 each: the track counters."""
+        self._need()
+        seen = np.zeros((self.batch, self.L_max), dtype=np.int32); expected = np.zeros_like(seen)
+        _lib.check(_lib.lib().slam_map_get_track(self.h, _i(seen), _i(expected)))
+        return seen, expected
+
+    def map_track_reset(self):
+        self._need()
+        _lib.check(_lib.lib().slam_map_track_reset(self.h))
+
+    def step_managed(self, cmdMsg, meas, meas_count, stats=True, cfg=None, map_cfg=None):
+        """step_associated(), then the tally of the labelled message with the association's flags, on the device.  meas as an int: DEVICE
+        pointers as step_associated_dev (meas_count = (pointer, k_stride); cmdMsg one command or, as an int, a device pointer)."""
+        self._need()
+        ac, mc = self._assoc_config(cfg), self._map_config(map_cfg)
+        out = dict(rec=np.zeros(16), n_drop=np.zeros(self.batch, dtype=np.int32)) if stats else None
+        rec, nd = (_d(out["rec"]), _i(out["n_drop"])) if stats else (None, None)
+        if isinstance(meas, int):
+            d_count, k_stride = meas_count
+            each = isinstance(cmdMsg, int)
+            cmd = None if each else self._cmd(cmdMsg)
+            if cmd is not None and cmd.ndim != 1:
+                raise ValueError("a managed step on device messages takes one command, or the device pointer of per-instance commands")
+            cp = C.c_void_p(cmdMsg) if each else C.cast(_f(cmd), C.c_void_p)
+            _lib.check(_lib.lib().slam_step_managed_dev(self.h, C.byref(ac), C.byref(mc), cp, int(each), C.c_void_p(meas), C.c_void_p(d_count),
+                                                        int(k_stride), rec, nd))
+        else:
+            cmd = self._cmd(cmdMsg)
+            m, cnt = self._message(meas, meas_count)
+            _lib.check(_lib.lib().slam_step_managed(self.h, C.byref(ac), C.byref(mc), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt), m.shape[1], rec, nd))
+        self.timestep += 1
+        return out
+
+    def manage_run(self, cmds, meas, meas_count, series=False, cfg=None, map_cfg=None):
+        """T managed ticks of a recorded log without ids, layout as associate_run: every tick a step_managed, and a map_prune after every
+        prune_every-th tick; the same bits as that loop.  Returns a MapResult; series=True also records n_match, n_new, n_drop, flags and
+        n_removed of every instance."""
+        self._need()
+        c32 = np.ascontiguousarray(cmds, dtype=np.float32)
+        m = np.ascontiguousarray(meas, dtype=np.float32)
+        cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
+        each = c32.ndim == 3
+        if c32.shape[1:] != ((self.batch, 2) if each else (2,)) or m.ndim != 4 or m.shape[:2] != (c32.shape[0], self.batch) or m.shape[2] == 0 \
+                or m.shape[3] != 3 or cnt.shape != m.shape[:2]:
+            raise ValueError(f"a log needs cmds (T, 2) or (T, {self.batch}, 2), meas (T, {self.batch}, k_stride > 0, 3) and meas_count (T, {self.batch})")
+        T = c32.shape[0]
+        res = MapResult(np.zeros((T, 16)))
+        if series:
+            res.n_match, res.n_new, res.n_drop, res.flags, res.n_removed = (np.zeros((T, self.batch), dtype=np.int32) for _ in range(5))
+        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
+        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
+        _lib.check(_lib.lib().slam_manage_run(self.h, C.byref(self._assoc_config(cfg)), C.byref(self._map_config(map_cfg)), _f(c32), int(each),
+                                              _f(m), _i(cnt), m.shape[2], T, pd(res.recs), pi(res.n_match), pi(res.n_new), pi(res.n_drop),
+                                              pi(res.n_removed), pi(res.flags)))
+        self.timestep += T
+        return res
+
+    def last_map_work(self):
+        """(model bytes the removals of the last remove_landmarks / map_prune / manage_run had to move, device ms of the prunes of the last
+        manage_run or -1 without set_nav_timing, device ms of that whole run or -1)."""
+        self._need(); by = C.c_double(0); a = C.c_double(0); b = C.c_double(0)
+        _lib.check(_lib.lib().slam_last_map_work(self.h, C.byref(by), C.byref(a), C.byref(b)))
+        return by.value, a.value, b.value
+
+
+def map_instance_host(x, P, ids, L_max, status=0, meas=None, count=None, k_stride=None, assoc_flag=0, vision=(3.0, -1.57, 1.57), f32_storage=False,
+                      cfg=None, seen=None, expected=None, remove=None, prune=False):
+    """TEST HOOK (slam_map_instance_host): the tally, the prune decision and the compaction of one instance compiled for the host; no GPU.
+    x (3 + 2 M,), P (n, n), ids (M,); meas (k, 3) float32 or None (no tally); vision = (range_max, fov_min, fov_max); seen / expected
+    (L_max,) or None (zeros); remove (M,) mask or None; prune: decide by the rule.  Returns dict(x, P, ids (the compacted state), M, mask
+    (L_max,), seen, expected (L_max,))."""
+    x = np.array(x, dtype=np.float64); P = np.array(P, dtype=np.float64)
+    ids_in = np.ascontiguousarray(ids, dtype=np.int32); M = ids_in.shape[0]
+    if x.shape != (3 + 2 * M,) or P.shape != (3 + 2 * M, 3 + 2 * M):
+        raise ValueError("x and P do not match the number of ids")
+    L_max = int(L_max)
+    row = np.zeros(max(L_max, M), dtype=np.int32); row[:M] = ids_in
+    se = np.zeros(max(L_max, 1), dtype=np.int32) if seen is None else np.array(seen, dtype=np.int32)
+    ex = np.zeros(max(L_max, 1), dtype=np.int32) if expected is None else np.array(expected, dtype=np.int32)
+    mp, cnt, ks = None, 0, 1
+    if meas is not None:
+        m = np.ascontiguousarray(meas, dtype=np.float32).reshape(-1, 3)
+        ks = max(m.shape[0], 1) if k_stride is None else int(k_stride)
+        cnt = m.shape[0] if count is None else int(count)
+        if ks < m.shape[0]:
+            raise ValueError("k_stride is smaller than the message")
+        mrow = np.zeros((ks, 3), dtype=np.float32); mrow[:m.shape[0]] = m
+        mp = _f(mrow)
+    rm = None if remove is None else np.ascontiguousarray(remove, dtype=np.int32)
+    if rm is not None and rm.shape != (M,):
+        raise ValueError("remove does not match the number of ids")
+    if rm is not None and M == 0:
+        rm = np.zeros(1, dtype=np.int32)
+    mask = np.zeros(max(L_max, 1), dtype=np.int32); Mo = C.c_int32(0)
+    c_cfg = default_map_config() if cfg is None else cfg
+    Pf = np.ascontiguousarray(P).reshape(-1).copy()
+    _lib.check(_lib.lib().slam_map_instance_host(_d(x), _d(Pf), _i(row), M, L_max, int(status), mp, cnt, ks, int(assoc_flag), float(vision[0]),
+                                                 float(vision[1]), float(vision[2]), int(bool(f32_storage)), C.byref(c_cfg), _i(se), _i(ex),
+                                                 None if rm is None else _i(rm), int(bool(prune)), _i(mask), C.byref(Mo)))
+    Mk = Mo.value; n2 = 3 + 2 * Mk
+    return dict(x=x[:n2].copy(), P=Pf[:n2 * n2].reshape(n2, n2).copy(), ids=row[:Mk].copy(), M=Mk, mask=mask[:L_max].copy(), seen=se[:L_max].copy(),
+                expected=ex[:L_max].copy(), ids_row=row[:L_max].copy())
 
 
 def innovation_instance_host(x, P, ids, L_max, status, cmd, meas, noise, lm_from_pred=False, f32_storage=False, cfg=None):
