@@ -677,7 +677,8 @@ int slam_associate_instance_host(const double* x, const double* P, const int32_t
  *   the association's arguments; NULL handle.  SLAM_ERR_UNSUPPORTED: the UKF kinds (their sqtP, Vt and ages would have to follow), and
  *   for slam_step_managed* and slam_manage_run what slam_step_associated refuses.  SLAM_ERR_STATE: before slam_init, while
  *   slam_track_instance is on, while a prediction is pending.  Every call runs the queued timesteps first.
- * Not covered: merging duplicate landmarks; the UKF; slam_multi_*; the simulator sources; the pose graph; counters in checkpoints. */
+ * Not covered: merging duplicate landmarks (these calls do not merge: see "landmark merging" below, slam_map_merge); the UKF;
+ *   slam_multi_*; the simulator sources; the pose graph; counters in checkpoints. */
 typedef struct slam_map_config {
     double range_shrink;    /* a landmark is expected within range_max * range_shrink; in (0, 1] */
     double fov_margin;      /* ... and at least this far inside the field of view, rad; >= 0 */
@@ -730,6 +731,80 @@ int slam_last_map_work(slam_handle* h, double* bytes, double* prune_ms, double* 
 int slam_map_instance_host(double* x, double* P, int32_t* ids, int M, int L_max, int32_t status, const float* meas, int count, int k_stride,
                            int32_t assoc_flag, double range_max, double fov_min, double fov_max, int f32_storage, const slam_map_config* cfg,
                            int32_t* seen, int32_t* expected, const int32_t* remove, int prune, int32_t* mask_out, int32_t* M_out);
+
+/* ---- landmark merging: duplicate landmarks are found and fused (csrc/merge_kernel.h) -----------------------------------------------------
+ * A detection farther than gate_new from every mapped landmark is inserted as a new one.  After the pose has drifted, or on one outlier
+ * return, a landmark that is already mapped is inserted a second time; from then on the two copies split the detections, each looks
+ * rarely seen to the prune rule, the state is larger than it should be and both copies keep their own error.  The prune rule can only
+ * delete a copy.  The calls below fuse the two: an EKF update with the pseudo-measurement l_i - l_j = 0 (noise sigma^2 I), then the
+ * exact marginalisation of slot j by the compaction of slam_remove_landmarks.  EKF handles only, both storage types, L_max <= 1000.
+ * With ii = 3 + 2 i, jj = 3 + 2 j, i < j, from the stored state (widened to double for fp32 storage):
+ * Cost:     delta = (x[ii] - x[jj], x[ii+1] - x[jj+1]);
+ *           S[a][b] = (P[ii+a][ii+b] - P[ii+a][jj+b]) - (P[jj+a][ii+b] - P[jj+a][jj+b]) + [a == b] sigma^2 (both off-diagonal blocks of
+ *           P are read: P is symmetric only to rounding); Si = the 2 x 2 LU inverse the step uses;
+ *           d2 = delta0 (Si00 delta0 + Si01 delta1) + delta1 (Si10 delta0 + Si11 delta1), unfused; NaN where Si failed or delta or S is
+ *           not finite.  The cost belongs to the unordered pair.
+ * Decision: nn(j) = the slot with the smallest finite d2 <= gate_merge against j, ties to the lowest slot, -1 if none.  (i, j) is a
+ *           duplicate iff nn(i) == j && nn(j) == i: a slot is in at most one pair, and no traversal order matters.  Instances that are
+ *           non-finite, frozen or stopped by the watchdog, or with M < 2, have no pairs.
+ * Fusion:   the pairs of an instance in ascending i, each on the state the previous one left: with c_r = (P[r][ii] - P[r][jj],
+ *           P[r][ii+1] - P[r][jj+1]) and g_c = (P[ii][c] - P[jj][c], P[ii+1][c] - P[jj+1][c]), S and Si as above from the current state
+ *           (Si failed or S not finite: the pair is skipped and counted SINGULAR), K_r = c_r Si, x[r] += K_r (-delta) (yaw wrapped as
+ *           in the step), P[r][c] -= K_r g_c, stored rounded to the storage type.  Then slot j of every fused pair is removed: the kept
+ *           slot is i, the kept id ids[i]; with track counters expected' = max(expected[i], expected[j]),
+ *           seen[i] = min(seen[i] + seen[j], expected'), expected[i] = expected'.  Flags, timestep, truth and err_sum are untouched; an
+ *           instance without a fused pair is not written.  Exact copies (S = 0 with sigma = 0) are SINGULAR; sigma > 0 fuses them.
+ * Record, 16 doubles, entry 8 a maximum and every other a sum, in the fixed order of the innovation record: 0 instances touched,
+ *   1 pairs fused, 2 slots with a candidate (nn >= 0) that was not mutual - for slam_merge_landmarks: entries that were ignored -,
+ *   3 pairs skipped SINGULAR, 4 elements of P updated (n^2 per fused pair), 7 the sum and 8 the largest d2 of the fused pairs, each taken
+ *   from the state the pair was fused on (0 without one); the rest reserved, 0.
+ * Errors: SLAM_ERR_ARG (checked first, with a text, before the handle is looked at): a NULL partner array, T < 0, a merge config with
+ *   gate_merge not finite or <= 0, sigma not finite or < 0, merge_every < 1, the errors of slam_manage_run's arguments; NULL handle.
+ *   SLAM_ERR_UNSUPPORTED and SLAM_ERR_STATE: as slam_map_prune; slam_manage_merge_run: as slam_manage_run.
+ * Not covered: the UKF; slam_multi_*; joint (multi-pair) updates; merging inside multi-step launches; counters in checkpoints. */
+typedef struct slam_merge_config {
+    double gate_merge;      /* a pair is a candidate when its d2 is at most this; finite and > 0 */
+    double sigma;           /* standard deviation of the pseudo-measurement l_i - l_j = 0, m; finite and >= 0 */
+    int32_t merge_every;    /* slam_manage_merge_run merges after every merge_every-th tick; >= 1 */
+} slam_merge_config;
+/* gate_merge = -2 ln 0.05, the 0.95 quantile of chi-square with 2 degrees of freedom; sigma 0: the copies are the same point; merge_every 10 */
+int slam_merge_config_default(slam_merge_config* cfg);
+/* The decision alone, no state change.  partner [batch][L_max] int32 (host): the slot's mutual partner, -1 if none (and at or above M);
+ * d2 [batch][L_max] (host, may be NULL): the d2 of the slot's best candidate, mutual or not, NaN if it has none.  Synchronises. */
+int slam_map_duplicates(slam_handle* h, const slam_merge_config* cfg, int32_t* partner, double* d2);
+/* The same with DEVICE pointers, written in stream order (d_d2 may be NULL); does not synchronise. */
+int slam_map_duplicates_dev(slam_handle* h, const slam_merge_config* cfg, int32_t* d_partner, double* d_d2);
+/* Fuses the pairs the caller gives: partner [batch][L_max] (host).  The entry of slot s is honoured iff s < M, 0 <= partner[s] < M,
+ * partner[s] != s and partner[partner[s]] == s; every other entry that is not -1 is ignored and counted (record entry 2), and an instance
+ * that is non-finite, frozen or stopped by the watchdog honours none.  gate_merge is not consulted.  n_merged [batch] and rec [16] (host)
+ * are optional: with both NULL the call does not synchronise. */
+int slam_merge_landmarks(slam_handle* h, const slam_merge_config* cfg, const int32_t* partner, int32_t* n_merged, double rec[16]);
+/* The same with the partner array as a DEVICE pointer, read in stream order. */
+int slam_merge_landmarks_dev(slam_handle* h, const slam_merge_config* cfg, const int32_t* d_partner, int32_t* n_merged, double rec[16]);
+/* Find, fuse and compact in one call, without a host round trip.  rec, n_merged: as above. */
+int slam_map_merge(slam_handle* h, const slam_merge_config* cfg, double rec[16], int32_t* n_merged);
+/* slam_manage_run's ticks, and after tick t with (t + 1) % merge_every == 0 a slam_map_merge, before that tick's prune.  The state and the
+ * counters advance bit for bit as the loop of slam_step_managed, slam_map_merge and slam_map_prune would leave them.  Outputs as
+ * slam_manage_run, and n_merged [T][batch], 0 on the ticks without a merge; any may be NULL.  Chunks of ticks by the rule of
+ * slam_innovation_run; chunking changes no bit. */
+int slam_manage_merge_run(slam_handle* h, const slam_assoc_config* assoc_cfg, const slam_map_config* map_cfg, const slam_merge_config* merge_cfg,
+                          const float* cmds, int cmd_each, const float* meas, const int32_t* meas_count, int k_stride, int T, double* recs,
+                          int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* n_removed, int32_t* n_merged, int32_t* flags);
+/* What the last slam_map_duplicates*, slam_merge_landmarks*, slam_map_merge or slam_manage_merge_run (all its merges) had to move, and
+ * the device times of the last slam_manage_merge_run.  bytes: the model, summed in integers on the device outside the timed part - per
+ * eligible instance of a find P and x read once; per attempted pair the gathers (8 n elements); per fused pair P and x read and written
+ * once; the partner row; the compaction as slam_last_map_work counts it.  merge_ms: the merge launches alone, which needs
+ * slam_nav_set_timing(h, 1), else -1; total_ms: the whole run; both -1 before any slam_manage_merge_run.  Synchronises. */
+int slam_last_merge_work(slam_handle* h, double* bytes, double* merge_ms, double* total_ms);
+/* TEST HOOK, not part of the filter interface: the find, the fusion and the compaction of ONE instance compiled for the HOST from
+ * csrc/merge_kernel.h (the source the kernels compile, no device needed).  x [3 + 2 M], P [n][n] packed, ids [L_max], seen / expected
+ * [L_max] (both or neither) are updated IN PLACE: P' is packed [n'][n'] at the front of P.  f32_storage: x and P are rounded to float
+ * first, as the handle stores them.  The find always runs: partner_out [L_max] and d2_out [L_max] (may be NULL).  fuse != 0: the pairs
+ * of partner_in [L_max] - or, with partner_in NULL, the pairs found - are fused and their slots removed.  rec [16] (may be NULL): the
+ * instance's contribution to the record; M_out. */
+int slam_merge_instance_host(double* x, double* P, int32_t* ids, int M, int L_max, int32_t status, int f32_storage, const slam_merge_config* cfg,
+                             int32_t* seen, int32_t* expected, const int32_t* partner_in, int fuse, int32_t* partner_out, double* d2_out,
+                             double rec[16], int32_t* M_out);
 
 /* ---- closed loop: commands from each instance's own estimate (goal_pursuit_node.py:23-50, pure_pursuit.py:17-161) ---------------------
  * The entry points above run open loop: every command is fixed before the run.  The reference's default launch (sim_base.launch,

@@ -15,5 +15,7 @@ from .config import ASSOC_NONE, ASSOC_MATCHED, ASSOC_NEW, ASSOC_AMBIGUOUS, ASSOC
 from .filters import AssocResult, associate_instance_host  # noqa: F401
 from .config import MapConfig, default_map_config  # noqa: F401
 from .filters import MapResult, map_instance_host  # noqa: F401
+from .config import MergeConfig, default_merge_config  # noqa: F401
+from .filters import MergeResult, merge_instance_host  # noqa: F401
 from .pose_graph import BatchedPoseGraph, NaiveFilter  # noqa: F401
 from ._lib import SlamError  # noqa: F401

@@ -5,7 +5,7 @@ There is no CPU fallback: if the library is missing or a HIP call fails, an exce
 import ctypes as C
 import os
 
-from .config import SlamConfig, NavConfig, MonitorConfig, InnovationConfig, GateConfig, AssocConfig, MapConfig, Noise
+from .config import SlamConfig, NavConfig, MonitorConfig, InnovationConfig, GateConfig, AssocConfig, MapConfig, MergeConfig, Noise
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # SLAM_HIP_LIB: another build of the same library, for A/B tuning sessions (tools/gpu_ab.sh); the product path is the
@@ -115,6 +115,17 @@ SIGNATURES = {
     "slam_last_map_work": (C.c_int, [_H, _dp, _dp, _dp]),
     "slam_map_instance_host": (C.c_int, [_dp, _dp, _ip, C.c_int, C.c_int, C.c_int32, _fp, C.c_int, C.c_int, C.c_int32, C.c_double, C.c_double,
                                          C.c_double, C.c_int, C.POINTER(MapConfig), _ip, _ip, _ip, C.c_int, _ip, _ip]),
+    "slam_merge_config_default": (C.c_int, [C.POINTER(MergeConfig)]),
+    "slam_map_duplicates": (C.c_int, [_H, C.POINTER(MergeConfig), _ip, _dp]),
+    "slam_map_duplicates_dev": (C.c_int, [_H, C.POINTER(MergeConfig), C.c_void_p, C.c_void_p]),
+    "slam_merge_landmarks": (C.c_int, [_H, C.POINTER(MergeConfig), _ip, _ip, _dp]),
+    "slam_merge_landmarks_dev": (C.c_int, [_H, C.POINTER(MergeConfig), C.c_void_p, _ip, _dp]),
+    "slam_map_merge": (C.c_int, [_H, C.POINTER(MergeConfig), _dp, _ip]),
+    "slam_manage_merge_run": (C.c_int, [_H, C.POINTER(AssocConfig), C.POINTER(MapConfig), C.POINTER(MergeConfig), _fp, C.c_int, _fp, _ip, C.c_int,
+                                        C.c_int, _dp, _ip, _ip, _ip, _ip, _ip, _ip]),
+    "slam_last_merge_work": (C.c_int, [_H, _dp, _dp, _dp]),
+    "slam_merge_instance_host": (C.c_int, [_dp, _dp, _ip, C.c_int, C.c_int, C.c_int32, C.c_int, C.POINTER(MergeConfig), _ip, _ip, _ip, C.c_int, _ip,
+                                           _dp, _dp, _ip]),
     "slam_nav_config_default": (C.c_int, [C.POINTER(NavConfig)]),
     "slam_nav_config_load": (C.c_int, [C.POINTER(NavConfig), C.c_char_p]),
     "slam_nav_set_path": (C.c_int, [_H, C.POINTER(NavConfig), _dp, C.c_int]),

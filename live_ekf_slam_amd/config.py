@@ -159,6 +159,21 @@ def default_map_config() -> MapConfig:
     return MapConfig(0.9, 0.1, 10, 0.3, 10)
 
 
+class MergeConfig(C.Structure):
+    """ctypes mirror of `slam_merge_config` (include/slam_batch.h): the gate on a pair's d2, the standard deviation of the pseudo-measurement
+    l_i - l_j = 0 and the stride of the merges of manage_merge_run."""
+    _fields_ = [("gate_merge", C.c_double), ("sigma", C.c_double), ("merge_every", C.c_int32)]
+
+
+MERGE_CONFIG_FIELDS = tuple(name for name, _ in MergeConfig._fields_)
+
+
+def default_merge_config() -> MergeConfig:
+    """gate_merge = -2 ln 0.05, the 0.95 quantile of chi-square with 2 degrees of freedom; sigma 0: the copies are the same point; every 10 ticks."""
+    import math
+    return MergeConfig(-2.0 * math.log(0.05), 0.0, 10)
+
+
 def default_monitor_config() -> MonitorConfig:
     """The chi-square quantiles at 0.025 and 0.975 for 3 degrees of freedom; no full evaluation."""
     return MonitorConfig(0.21579528262389785, 9.348403604496148, 0)

@@ -9,6 +9,7 @@
 #include "assoc_kernel.h"
 #include "capi_assoc.h"
 #include "capi_innovation.h"
+#include "capi_map.h"
 #include "capi_run.h"
 #include "ekf_kernel.h"
 #include "host/tick_chunks.h"
@@ -16,7 +17,7 @@
 
 using namespace slam_capi;
 
-namespace {
+namespace slam_capi {
 
 // *out = *cfg (NULL: the defaults), checked
 int map_config(const slam_map_config* cfg, slam_map_config* out) {
@@ -93,7 +94,7 @@ int map_sum_work(slam_handle* h, const int32_t* d_n_removed, const int32_t* d_m_
 }
 
 // slam_remove_landmarks* and slam_map_prune once the mask (or nothing) is on the device
-int remove_now(slam_handle* h, const int32_t* d_remove, const slam_map_config& c, int32_t* n_removed, double* rec) {
+static int remove_now(slam_handle* h, const int32_t* d_remove, const slam_map_config& c, int32_t* n_removed, double* rec) {
     const size_t B = (size_t)h->B;
     TRY(map_reserve(h, 1));
     TRY(map_zero_work(h));
@@ -121,7 +122,7 @@ int tally_now(slam_handle* h, const slam_map_config& c, const float* d_meas, con
     return SLAM_OK;
 }
 
-int tally_args(const slam_map_config* cfg, const float* meas, const int32_t* count, int k_stride, slam_map_config* c) {
+static int tally_args(const slam_map_config* cfg, const float* meas, const int32_t* count, int k_stride, slam_map_config* c) {
     TRY(map_config(cfg, c));
     if (!meas || !count) return slam_internal_fail(SLAM_ERR_ARG, "meas or meas_count is NULL");
     if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
@@ -129,7 +130,7 @@ int tally_args(const slam_map_config* cfg, const float* meas, const int32_t* cou
 }
 
 // one managed timestep once the message and the commands are on the device
-int step_managed_now(slam_handle* h, const slam_assoc_config& ac, const slam_map_config& mc, const float cmd[2], const float* d_cmd_each,
+static int step_managed_now(slam_handle* h, const slam_assoc_config& ac, const slam_map_config& mc, const float cmd[2], const float* d_cmd_each,
                      const float* d_meas, const int32_t* d_count, int k_stride, double* rec, int32_t* n_drop) {
     const size_t B = (size_t)h->B;
     TRY(assoc_reserve(h, k_stride, 1));
@@ -149,10 +150,6 @@ int managed_enter(slam_handle* h, const char* who) {
     TRY(assoc_enter(h));
     return assoc_step_state(h, who);
 }
-
-}  // namespace
-
-namespace slam_capi {
 
 int map_track_reset(slam_handle* h) {
     if (!h->map.tracked) return SLAM_OK;

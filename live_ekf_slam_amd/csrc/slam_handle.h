@@ -1,6 +1,6 @@
 // slam_handle.h — the handle of the filter ABI (include/slam_batch.h) and the host helpers that more than one of its translation units
 // uses (slam_capi.cpp: create / configure / init; capi_step.cpp: the steps and their queue; capi_state.cpp: reading the state back;
-// capi_consistency.cpp, capi_nav.cpp, capi_monitor.cpp, capi_innovation.cpp, capi_gate.cpp, capi_assoc.cpp, capi_map.cpp: one feature each).  Not installed, not part
+// capi_consistency.cpp, capi_nav.cpp, capi_monitor.cpp, capi_innovation.cpp, capi_gate.cpp, capi_assoc.cpp, capi_map.cpp, capi_merge.cpp: one feature each).  Not installed, not part
 // of the ABI: the standing of capi_internal.h.
 #pragma once
 #include "../../include/slam_batch.h"
@@ -181,6 +181,15 @@ struct slam_handle {
         bool tracked = false, work_set = false;
         slam_capi::RunTimes times;
     } map;
+    // slam_map_duplicates / slam_merge_landmarks / slam_map_merge: the partner row of every slot ([B][L_max]; a staged host array or what the
+    // find wrote), the d2 of the slots' best candidates ([B][L_max], when asked for), the mask the fusion writes for the compaction
+    // ([B][L_max]), [6][ticks][B] candidates that were not mutual, eligible, pairs fused, pairs attempted, slots removed and the M before,
+    // the record, the five sums of the traffic model (work_set: a merge has filled them) and the device times of the last slam_manage_merge_run
+    struct Merge {
+        DevBuf<int32_t> dpartner, dmask, dint; DevBuf<double> dd2, drec; DevBuf<unsigned long long> dwork;
+        bool work_set = false;
+        slam_capi::RunTimes times;
+    } merge;
 };
 
 #pragma GCC visibility push(hidden)

@@ -20,6 +20,7 @@ from .config import (InnovationConfig, default_innovation_config, INNOVATION_SHA
 from .config import GateConfig, default_gate_config
 from .config import AssocConfig, default_assoc_config
 from .config import MapConfig, default_map_config, MAP_CONFIG_FIELDS
+from .config import MergeConfig, default_merge_config, MERGE_CONFIG_FIELDS
 
 
 def _d(a):
@@ -96,6 +97,18 @@ class MapResult(AssocResult):
     def __init__(self, recs, n_match=None, n_new=None, n_drop=None, flags=None, n_removed=None):
         AssocResult.__init__(self, recs, n_match, n_new, n_drop, flags)
         self.n_removed = n_removed
+
+
+class MergeResult(MapResult):
+    """What manage_merge_run returns: MapResult and - with series=True, else None - `n_merged` (T, batch), the landmarks each merge fused
+    away (0 on the ticks without one).  The REC_MERGE_* constants index the (16,) record of merge_landmarks and map_merge."""
+
+    REC_MERGE_TOUCHED, REC_MERGE_FUSED, REC_MERGE_NOT_MUTUAL, REC_MERGE_SINGULAR, REC_MERGE_UPDATED = range(5)
+    REC_MERGE_SUM_D2, REC_MERGE_MAX_D2 = 7, 8
+
+    def __init__(self, recs, n_match=None, n_new=None, n_drop=None, flags=None, n_removed=None, n_merged=None):
+        MapResult.__init__(self, recs, n_match, n_new, n_drop, flags, n_removed)
+        self.n_merged = n_merged
 
 
 class BatchedFilter:
@@ -1032,6 +1045,119 @@ class BatchedEKF(BatchedFilter):
         self._need(); by = C.c_double(0); a = C.c_double(0); b = C.c_double(0)
         _lib.check(_lib.lib().slam_last_map_work(self.h, C.byref(by), C.byref(a), C.byref(b)))
         return by.value, a.value, b.value
+
+
+    # -- landmark merging: duplicate landmarks are found and fused (slam_map_duplicates, slam_merge_landmarks, slam_map_merge) --
+    def _merge_config(self, cfg):
+        if cfg is None:
+            return default_merge_config()
+        if isinstance(cfg, MergeConfig):
+            return cfg
+        c = default_merge_config()
+        for k, v in dict(cfg).items():
+            if k not in MERGE_CONFIG_FIELDS:
+                raise ValueError(f"unknown merge setting {k!r}")
+            setattr(c, k, v)
+        return c
+
+    def map_duplicates(self, d2=True, cfg=None, dev=None):
+        """The duplicate decision, no state change: (partner, d2), (batch, L_max) each: the slot's mutual nearest neighbour within gate_merge
+        (-1: none) and - d2=True, else None - the d2 of its best candidate (NaN: none).  dev = (d_partner, d_d2 or None): DEVICE pointers,
+        written in stream order; returns None."""
+        self._need()
+        c = self._merge_config(cfg)
+        if dev is not None:
+            _lib.check(_lib.lib().slam_map_duplicates_dev(self.h, C.byref(c), C.c_void_p(dev[0]), None if dev[1] is None else C.c_void_p(dev[1])))
+            return None
+        partner = np.zeros((self.batch, self.L_max), dtype=np.int32)
+        dd = np.zeros((self.batch, self.L_max)) if d2 else None
+        _lib.check(_lib.lib().slam_map_duplicates(self.h, C.byref(c), _i(partner), _d(dd) if d2 else None))
+        return partner, dd
+
+    def merge_landmarks(self, partner, stats=True, cfg=None):
+        """Fuses the pairs of partner (batch, L_max): an entry is honoured where it is mutual and both slots are mapped; the others are
+        ignored and counted.  partner as an int: the DEVICE pointer of the array.  stats=True returns dict(rec (16,), n_merged [batch]) and
+        synchronises; stats=False None."""
+        self._need()
+        c = self._merge_config(cfg)
+        out = dict(rec=np.zeros(16), n_merged=np.zeros(self.batch, dtype=np.int32)) if stats else None
+        nm, rec = (_i(out["n_merged"]), _d(out["rec"])) if stats else (None, None)
+        if isinstance(partner, int):
+            _lib.check(_lib.lib().slam_merge_landmarks_dev(self.h, C.byref(c), C.c_void_p(partner), nm, rec))
+        else:
+            m = np.ascontiguousarray(partner, dtype=np.int32)
+            if m.shape != (self.batch, self.L_max):
+                raise ValueError(f"partner: expected shape ({self.batch}, {self.L_max}), got {m.shape}")
+            _lib.check(_lib.lib().slam_merge_landmarks(self.h, C.byref(c), _i(m), nm, rec))
+        return out
+
+    def map_merge(self, stats=True, cfg=None):
+        """Finds the duplicate pairs, fuses them and compacts the maps, all on the device.  Returns as merge_landmarks."""
+        self._need()
+        out = dict(rec=np.zeros(16), n_merged=np.zeros(self.batch, dtype=np.int32)) if stats else None
+        _lib.check(_lib.lib().slam_map_merge(self.h, C.byref(self._merge_config(cfg)), _d(out["rec"]) if stats else None,
+                                             _i(out["n_merged"]) if stats else None))
+        return out
+
+    def manage_merge_run(self, cmds, meas, meas_count, series=False, cfg=None, map_cfg=None, merge_cfg=None):
+        """manage_run with a map_merge after every merge_every-th tick, before that tick's prune; the same bits as that loop.  Returns a
+        MergeResult; series=True also records n_match, n_new, n_drop, flags, n_removed and n_merged of every instance."""
+        self._need()
+        c32 = np.ascontiguousarray(cmds, dtype=np.float32)
+        m = np.ascontiguousarray(meas, dtype=np.float32)
+        cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
+        each = c32.ndim == 3
+        if c32.shape[1:] != ((self.batch, 2) if each else (2,)) or m.ndim != 4 or m.shape[:2] != (c32.shape[0], self.batch) or m.shape[2] == 0 \
+                or m.shape[3] != 3 or cnt.shape != m.shape[:2]:
+            raise ValueError(f"a log needs cmds (T, 2) or (T, {self.batch}, 2), meas (T, {self.batch}, k_stride > 0, 3) and meas_count (T, {self.batch})")
+        T = c32.shape[0]
+        res = MergeResult(np.zeros((T, 16)))
+        if series:
+            res.n_match, res.n_new, res.n_drop, res.flags, res.n_removed, res.n_merged = (np.zeros((T, self.batch), dtype=np.int32) for _ in range(6))
+        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
+        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
+        _lib.check(_lib.lib().slam_manage_merge_run(self.h, C.byref(self._assoc_config(cfg)), C.byref(self._map_config(map_cfg)),
+                                                    C.byref(self._merge_config(merge_cfg)), _f(c32), int(each), _f(m), _i(cnt), m.shape[2], T,
+                                                    pd(res.recs), pi(res.n_match), pi(res.n_new), pi(res.n_drop), pi(res.n_removed), pi(res.n_merged),
+                                                    pi(res.flags)))
+        self.timestep += T
+        return res
+
+    def last_merge_work(self):
+        """(model bytes the last map_duplicates / merge_landmarks / map_merge / manage_merge_run had to move, device ms of the merges of the
+        last manage_merge_run or -1 without set_nav_timing, device ms of that whole run or -1)."""
+        self._need(); by = C.c_double(0); a = C.c_double(0); b = C.c_double(0)
+        _lib.check(_lib.lib().slam_last_merge_work(self.h, C.byref(by), C.byref(a), C.byref(b)))
+        return by.value, a.value, b.value
+
+
+def merge_instance_host(x, P, ids, L_max, status=0, f32_storage=False, cfg=None, seen=None, expected=None, partner=None, fuse=True):
+    """TEST HOOK (slam_merge_instance_host): the find, the fusion and the compaction of one instance compiled for the host; no GPU.
+    x (3 + 2 M,), P (n, n), ids (M,); seen / expected (L_max,) or None (no counters); partner (L_max,) caller pairs or None (the pairs
+    found); fuse=False: the decision alone.  Returns dict(x, P, ids (the merged state), M, partner, d2 (L_max,: the find on the state
+    given), rec (16,), seen, expected (L_max,) or None)."""
+    x = np.array(x, dtype=np.float64); P = np.array(P, dtype=np.float64)
+    ids_in = np.ascontiguousarray(ids, dtype=np.int32); M = ids_in.shape[0]
+    if x.shape != (3 + 2 * M,) or P.shape != (3 + 2 * M, 3 + 2 * M):
+        raise ValueError("x and P do not match the number of ids")
+    L_max = int(L_max)
+    row = np.zeros(max(L_max, M, 1), dtype=np.int32); row[:M] = ids_in
+    if (seen is None) != (expected is None):
+        raise ValueError("seen and expected come together")
+    se = None if seen is None else np.array(seen, dtype=np.int32)
+    ex = None if expected is None else np.array(expected, dtype=np.int32)
+    pin = None if partner is None else np.ascontiguousarray(partner, dtype=np.int32)
+    if pin is not None and pin.shape != (L_max,):
+        raise ValueError("partner does not have L_max entries")
+    pout = np.zeros(max(L_max, 1), dtype=np.int32); dout = np.zeros(max(L_max, 1)); rec = np.zeros(16); Mo = C.c_int32(0)
+    c_cfg = default_merge_config() if cfg is None else cfg
+    Pf = np.ascontiguousarray(P).reshape(-1).copy()
+    _lib.check(_lib.lib().slam_merge_instance_host(_d(x), _d(Pf), _i(row), M, L_max, int(status), int(bool(f32_storage)), C.byref(c_cfg),
+                                                   None if se is None else _i(se), None if ex is None else _i(ex),
+                                                   None if pin is None else _i(pin), int(bool(fuse)), _i(pout), _d(dout), _d(rec), C.byref(Mo)))
+    Mk = Mo.value; n2 = 3 + 2 * Mk
+    return dict(x=x[:n2].copy(), P=Pf[:n2 * n2].reshape(n2, n2).copy(), ids=row[:Mk].copy(), M=Mk, partner=pout[:L_max].copy(), d2=dout[:L_max].copy(),
+                rec=rec, seen=None if se is None else se[:L_max].copy(), expected=None if ex is None else ex[:L_max].copy(), ids_row=row[:L_max].copy())
 
 
 def map_instance_host(x, P, ids, L_max, status=0, meas=None, count=None, k_stride=None, assoc_flag=0, vision=(3.0, -1.57, 1.57), f32_storage=False,
