@@ -946,7 +946,12 @@ int slam_reset_counters_async(slam_handle* h);
 int slam_kernel_info(slam_handle* h, int multi_step, char* name, int name_cap, int32_t out[5]);
 /* Diagnostics: flag 32 = every workgroup of the EKF multi-step kernel stamps the wall clock and its detection count per
  * timestep (read back by the profiling tools / bench.py's per-k table), flag 4 = per-phase cycle counters; 0 = off (default;
- * the environment variable SLAM_DEBUG_FLAGS sets the initial value). */
+ * the environment variable SLAM_DEBUG_FLAGS sets the initial value).
+ * TEST-ONLY flags, accepted here and never from the environment variable: 128 = the pass leader of the EKF multi-step kernel loses
+ * its `applied` update, so the control wavefront starves and the watchdog must flag the instance (SLAM_INST_WATCHDOG); 1024 = the
+ * control wavefront's look at its ring slot always answers "full", so every update of the decoupled loop finishes its thin work
+ * before it waits for the slot and is published (the order an update takes when the ring is full) - whether the ring is full
+ * depends on timing, and a test must not.  Results are the same bits with and without 1024. */
 int slam_set_debug_flags(slam_handle* h, int flags);
 /* Build introspection: 1 if the library holds the EKF step-kernel tuning variant `variant` (code PIPE*1000 + W*100 + KG*10 +
  * UNR, selected per handle by the environment variable SLAM_WAVES_PER_FILTER) for landmark capacity L_max and storage

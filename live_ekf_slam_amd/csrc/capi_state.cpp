@@ -324,7 +324,8 @@ int slam_set_debug_flags(slam_handle* h, int flags) {
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
 #ifndef SLAM_ABLATE
-    flags &= (4 | 32 | 128);   // 128: tests only, provokes the watchdog of the EKF step kernel
+    flags &= (4 | 32 | 128 | 1024);   // 128: tests only, provokes the watchdog of the EKF step kernel; 1024: tests only, every update of the
+                                      // decoupled loop takes the deferred order (thin work before its ring slot), same results
 #endif
     if ((flags & (4 | 32)) && !h->dprof) {
         HIP_TRY(h->dprof.reserve(slam::kEkfProfSlots * (size_t)h->B));

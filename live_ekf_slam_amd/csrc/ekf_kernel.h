@@ -75,7 +75,8 @@ struct EkfStepParams {
                                // launches (one atomicAdd per bin and workgroup at the end of a launch); may be NULL
     unsigned long long* prof;  // optional [B][PROF_SLOTS] per-block stamps of the last launch (dbg & 4 | 32), NULL otherwise
     int32_t dbg;  // SLAM_DEBUG_FLAGS: 4 = phase cycle counters, 32 = wall-clock stamp + detection count per timestep of a
-                  // multi-step launch; 1 / 2 / 16 (ablations, WRONG results) only in a -DSLAM_ABLATE build
+                  // multi-step launch; 1 / 2 / 16 (ablations, WRONG results) only in a -DSLAM_ABLATE build; 128 / 1024: tests only
+                  // (slam_set_debug_flags: lose an `applied` update / every update of the decoupled loop in the deferred order)
 };
 
 // Leading dimension (in elements) of the row-major covariance of an instance with state size n: every row starts on a

@@ -202,7 +202,11 @@ __global__ __launch_bounds__(64 * W, (W >= 2 ? 4 : SLAM_W1_WAVES)) void ekf_step
     constexpr int VEC = Vec16<ST>::VEC;   // elements of the storage type per 16-byte vector
     constexpr int HS = hp_substride<VEC>(LDP), HPW = (VEC - 1) * HS + (LDP + VEC - 1) / VEC;   // (the last sub-array is not padded)
     __shared__ double2 s_HP[KG * HPW];    // per update of the group: (H P)[0..1][c] at hpi(c) (de-interleaved by c % VEC)
-    __shared__ double s_sc[16];           // scalars computed by the leader lane (H entries, nu, S^-1, G_x ...)
+    // The synchronised path's scalars are dead inside the decoupled loop (between its entry and exit barriers); there the same bytes are
+    // the control wavefront's STAGING ARRAY: K[T_s] and (H P)[T_s] of the update in hand per thin slot s, TS double2 each, which the thin
+    // downdate reads as its broadcast operands - so an update can finish its thin work before it has a ring slot (ekf_step_decoupled.h).
+    constexpr int kScN = (MULTI && W >= 2 && 4 * TS > 16) ? 4 * TS : 16;
+    __shared__ __attribute__((aligned(16))) double s_sc[kScN];   // scalars computed by the leader lane (H entries, nu, S^-1, G_x ...)
     // The measurement generator does not depend on the filter, so it may run AHEAD of it: a ring of SD timesteps, slot = t % SD.
     constexpr int SD = SLAM_SD;   // (three, to stay within 40 KB of LDS = 4 workgroups per CU; fp64 had four until the ring got its fifth slot)
     __shared__ float s_meas[SD * 3 * KCAP];  // [t % SD][detection][id, range, bearing]

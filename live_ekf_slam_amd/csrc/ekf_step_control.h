@@ -136,16 +136,18 @@
     // ---- the same downdate for the CONTROL wavefront of the decoupled loop (round 4), written for memory-level parallelism: the loop
     //      above makes two DEPENDENT LDS round trips per slot and state index (slot table -> operands -> element), 18 of them per
     //      update at n = 103, and that latency was 15 % of the control wavefront's timeline.  Here the slot table is read once (one
-    //      batch), a lane's own K[j] / (H P)[j] arrive in registers from the phase that computed them, and the slots are walked in
+    //      load and a ballot: which slots are in use), a lane's own K[j] / (H P)[j] arrive in registers from the phase that computed them, and the slots are walked in
     //      groups of SG: the group's operands K[T_s], (H P)[T_s] and its elements of R and C are requested together, then updated and
-    //      stored.  Same expression per element, so not a bit changes; it wants registers (W = 3 variants: 168 VGPRs). ----
+    //      stored.  Same expression per element, so not a bit changes; it wants registers (W = 3 variants: 168 VGPRs).
+    //      The broadcast operands come from the staging array (Kt[s] = K[T_s], Ht[s] = (H P)[T_s], written per thin slot by the lanes that
+    //      own those state indices when they computed them), not from the update's ring slot: the update may not have a slot yet. ----
     constexpr int NU = (LDP + 63) / 64;   // state indices per lane of ONE wavefront
-    auto thin_downdate_ctl = [&](int nTd, int nd, const double2* __restrict__ Ku, const double2* __restrict__ HPu, const double2 (&kj)[NU],
+    auto thin_downdate_ctl = [&](int nTd, int nd, const double2* __restrict__ Kt, const double2* __restrict__ Ht, const double2 (&kj)[NU],
                                  const double2 (&hj)[NU]) {
         constexpr int SG = SLAM_CTRL_SG;
-        int tsv[TS];
-#pragma unroll
-        for (int sl = 0; sl < TS; ++sl) tsv[sl] = s_T[sl];
+        // the slots in use, one bit each (lane s <-> slot s): with the operands staged by slot the state indices themselves are not needed
+        const int t_l = lane < nTd ? s_T[lane] : -1;   // (nTd <= TS)
+        const unsigned okm = (unsigned)__ballot((unsigned)t_l < (unsigned)nd);
 #pragma unroll
         for (int s0 = 0; s0 < TS; s0 += SG) {
             if (s0 >= nTd) break;   // wave-uniform
@@ -155,10 +157,8 @@
 #pragma unroll
             for (int g = 0; g < SG; ++g) {
                 const int sl = s0 + g < TS ? s0 + g : TS - 1;
-                const int t_s = tsv[sl];
-                ok[g] = s0 + g < nTd && (unsigned)t_s < (unsigned)nd;   // wave-uniform
-                const int tc = ok[g] ? t_s : 0;
-                kt[g] = Ku[tc]; ht[g] = HPu[hpi(tc)];
+                ok[g] = ((okm >> (s0 + g)) & 1u) != 0u;   // wave-uniform (slots s0 + g >= TS or >= nTd have no bit)
+                kt[g] = Kt[sl]; ht[g] = Ht[sl];   // (a slot that is not ok holds stale values: never used)
 #pragma unroll
                 for (int u = 0; u < NU; ++u) {
                     const int j = lane + 64 * u;

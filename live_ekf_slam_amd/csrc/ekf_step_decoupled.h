@@ -230,13 +230,21 @@
                         double H[8], Si[4], nu0, nu1;
                         if (!leader_chain(ii, si, r_m, b_m, H, nu0, nu1, Si)) fl_or |= SLAM_INST_S_SINGULAR;
                         SLAM_STAMP(20);  // scalar chain of the update
+                        // ORDER OF AN UPDATE.  H P / K / x and the thin downdate need nothing from the streamers: they read the thin copies, s_xp and
+                        // this lane's own registers, so neither needs the update's ring slot.  The slot is looked at ONCE, without waiting, after
+                        // H P / K / x: if it is free the update is stored and published there and then, before its thin work (the streamers get it
+                        // as early as they can); if the ring is full - a pass frees its slots together, at its end - the thin downdate runs first
+                        // and the wait, the store and the publication follow it, so the time the ring is full is spent on work that was due anyway.
+                        // At most one update is ever unpublished, and it is published before the next update, group or step begins.
+#if !SLAM_CTRL_ILP
+                        // (thin_downdate reads its operands from the slot: the slot comes first, whatever the wait)
                         for (int sp = 0; pub - ld_i(&s_ring[1]) >= KG && !spin_over(sp);) __builtin_amdgcn_s_sleep(SLAM_SLEEP_RING);   // a free slot in the ring
                         if (ld_i(&s_ring[2])) break;   // watchdog
                         SLAM_STAMP(21);  // waiting for a ring slot
-                        const int slot = pub % KG;
-                        double2* __restrict__ HPu = s_HP + slot * HPW;
-                        double2* __restrict__ Ku = s_K + slot * LDP;
-                        double2 kreg[NU], hreg[NU];   // this lane's K[j], (H P)[j], j = lane + 64 u: the thin downdate takes them from here
+#endif
+                        double2* const s_kt = reinterpret_cast<double2*>(s_sc);   // staging: K[T_s], (H P)[T_s] by thin slot s (s_sc is dead in here)
+                        double2* const s_ht = s_kt + TS;
+                        double2 kreg[NU], hreg[NU];   // this lane's K[j], (H P)[j], j = lane + 64 u: the thin downdate and the slot take them from here
 #pragma unroll
                         for (int u = 0; u < NU; ++u) { kreg[u] = make_double2(0.0, 0.0); hreg[u] = make_double2(0.0, 0.0); }
                         // (written out: restates ekf_hp_col, ekf_pht_row, ekf_gain and ekf_state_update of ekf_model.h)
@@ -263,22 +271,60 @@
                                     if (c == 2) xv = rem2pi(xv);
                                     s_xp[c] = xv;
                                 }
-                                if (c < LDP) { HPu[hpi(c)] = hp; Ku[c] = kk; }
                                 kreg[u] = kk; hreg[u] = hp;
                             }
+                            // the lanes whose state index has a thin row / column stage their K / H P: the thin downdate's broadcast operands
+#pragma unroll
+                            for (int u = 0; u < NU; ++u) {
+                                const int c = lane + 64 * u;
+                                const int sc = c < n ? (int)s_slot[c] : -1;
+                                if (sc >= 0) { s_kt[sc] = kreg[u]; s_ht[sc] = hreg[u]; }
+                            }
                         }
-                        if (!kWide && lane == 0) s_wend[slot] = (l == lastu) ? 1 : 0;
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // K / H P of the slot are in LDS before it is published
-                        pub += 1;
-                        if (lane == 0) st_i(&s_ring[0], pub);
+                        // the update goes into ring slot pub % KG and is published: registers to LDS (pad entries c >= n are zeros), s_wend, fence
+                        auto publish = [&]() {
+                            const int slot = pub % KG;
+                            double2* __restrict__ HPu = s_HP + slot * HPW;
+                            double2* __restrict__ Ku = s_K + slot * LDP;
+#pragma unroll
+                            for (int u = 0; u < NU; ++u) {
+                                const int c = lane + 64 * u;
+                                if (c < LDP) { HPu[hpi(c)] = hreg[u]; Ku[c] = kreg[u]; }
+                            }
+                            if (!kWide && lane == 0) s_wend[slot] = (l == lastu) ? 1 : 0;
+                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // K / H P of the slot are in LDS before it is published
+                            pub += 1;
+                            if (lane == 0) st_i(&s_ring[0], pub);
+                        };
+#if SLAM_CTRL_ILP
+                        // p.dbg & 1024 (tests only): the answer is always "full", so every update takes the deferred order whatever the timing
+                        // (readfirstlane: every lane loads the same word; the branches on the answer are then scalar ones)
+                        const bool slot_free = __builtin_amdgcn_readfirstlane(pub - ld_i(&s_ring[1])) < KG && !(p.dbg & 1024);
+#else
+                        constexpr bool slot_free = true;   // waited for above
+#endif
+                        if (slot_free) publish();
                         SLAM_STAMP(22);  // H P, K, x_pred
                         // thin copies follow the same downdate  P -= K (H P)
                         if (!SLAM_DBG(p.dbg & 256)) {   // (ablation 256: timing without the thin downdates)
 #if SLAM_CTRL_ILP
-                            thin_downdate_ctl(nTq, n, Ku, HPu, kreg, hreg);
+                            thin_downdate_ctl(nTq, n, s_kt, s_ht, kreg, hreg);
 #else
-                            thin_downdate(lane, 64, 0, 1, nTq, n, Ku, HPu);
+                            thin_downdate(lane, 64, 0, 1, nTq, n, s_K + ((pub - 1) % KG) * LDP, s_HP + ((pub - 1) % KG) * HPW);
 #endif
+                        }
+                        if (!slot_free) {
+                            // The ring was full when the update was computed.  The shared-word protocol is what it was: the control wavefront
+                            // writes a slot only after it has seen pub - applied < KG, and publishes right after
+                            // (tests/test_ring_protocol_model.py still describes it).  fp32 storage too: a waiting control wavefront implies
+                            // pub - app == KG, so a prefix that ends on a step boundary exists (a step has at most KG updates and s_wend of
+                            // every published slot is set) - the pass leader can always cut a pass, and it frees this update's slot.
+                            SLAM_STAMP(23);  // thin downdates
+                            for (int sp = 0; pub - ld_i(&s_ring[1]) >= KG && !spin_over(sp);) __builtin_amdgcn_s_sleep(SLAM_SLEEP_RING);   // a free slot in the ring
+                            if (ld_i(&s_ring[2])) break;   // watchdog
+                            SLAM_STAMP(21);  // waiting for a ring slot
+                            publish();
+                            SLAM_STAMP(22);  // (the store and the publication)
                         }
                     }
                     l0q = l1q;

@@ -107,11 +107,16 @@
             det_sincos(th, &sn, &cs);
             const float dd = fwd_n + nz.v_d;
             const double cv = cs * nz.V00, sv = sn * nz.V00;
+            // v_th is converted to fp64 HERE: hoisted to the kernel's entry, the converted value holds a register pair for the whole launch
+            // and is the one the allocator sends to scratch - a scratch load in every pre-step of the control wavefront
+            int v_th_bits = __float_as_int(nz.v_th);
+            if constexpr (MULTI) asm volatile("" : "+s"(v_th_bits));   // (the one-step kernels have no loop to hoist it out of)
+            const float v_th = __int_as_float(v_th_bits);
             if (lane == 0) {
                 nx[0] = kraw;
                 ps[0] = x0 + (double)dd * cs;
                 ps[1] = x1 + (double)dd * sn;
-                ps[2] = rem2pi((th + (double)ang_n) + (double)nz.v_th);
+                ps[2] = rem2pi((th + (double)ang_n) + (double)v_th);
                 ps[3] = (double)(-1 * fwd_n) * sn;  // F_x(0,2)
                 ps[4] = (double)fwd_n * cs;         // F_x(1,2)
                 ps[5] = cv * cs; ps[6] = cv * sn; ps[7] = sv * cs; ps[8] = sv * sn;

@@ -98,7 +98,8 @@ int slam_create(const slam_config* cfg, int kind, int batch, int L_max, int dtyp
     env = getenv("SLAM_DEBUG_FLAGS");   // 4 / 32: phase and per-step timers.  The ablation bits (1, 2, 16: WRONG results) are
     if (env) h->dbg = atoi(env);        // compiled out of the release kernels (-DSLAM_ABLATE builds only)
 #ifndef SLAM_ABLATE
-    h->dbg &= (4 | 32);   // (the fault-injection bit 128 is reachable through slam_set_debug_flags only: no environment variable can plant it)
+    h->dbg &= (4 | 32);   // (the fault-injection bit 128 and the order-forcing bit 1024 are reachable through slam_set_debug_flags only: no
+                          // environment variable can plant them)
 #endif
     env = getenv("SLAM_UKF_SPLIT_MIN");   // batch size from which UKF run_sim splits the batch over two streams
     if (env) h->ukf.split_min = atoi(env);
