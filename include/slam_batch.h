@@ -962,6 +962,23 @@ int slam_variant_available(int L_max, int dtype, int variant);
  * {sin a, cos a, atan2(a,b), remainder(a,2pi), sqrt|a|, a/b, (double)(float)a, u53 noise} per element.
  * Used by the parity tests to prove the device math is bit-identical to the host's. */
 int slam_math_probe(const double* a, const double* b, double* out, int n, int device);
+/* Diagnostics: ONE of the functions the kernels share with the CPU oracle (slam_math.h, slam_rng.h) or the UKF kernels' own
+ * wrappers, evaluated on the device for every item of the host arrays a..d[n]; results in out[n][out_per_item] (out_per_item >= the
+ * op's result count; further entries of an item keep their values).  Arrays an op does not read may be NULL.
+ *   op  reads                          writes per item
+ *   0   a                              sin, cos                      (det_sincos)
+ *   1   a = y, b = x                   det_atan2(y, x)
+ *   2   a                              rem2pi(a), wrap2pi(a)         (the short-cut, the device library's remainder(a, 2 pi))
+ *   3   a, b                           sqrt(a), a / b, (double)(float)a
+ *   4   a, b, c, d = S row-major       Si[0..3], ok (1 / 0)          (inv2x2_lu)
+ *   5   a, b = as_int (0 / not 0)      assoc_abs(a, as_int)
+ *   6   a, b = float_trig (0 / not 0)  sin, cos of tsincos((float)a, float_trig)   (the UKF kernels' unqualified sin / cos)
+ *   7   a = cos, b = sin               yaw_of(cos, sin)              (the UKF kernels' (float) remainder(atan2(sin, cos), 2 pi))
+ *   8   a..d = counters, packed        u0, u1 of noise_pair(seed, inst, t, p)
+ * Packing of op 8, every value an integer below 2^48 and so exact in a double: a = seed mod 2^48, b = inst mod 2^48,
+ * c = (seed >> 48) + 65536 * t, d = (inst >> 48) + 65536 * p.
+ * Used by tests/test_math_edges_gpu.py, which compares every result with the host's bit for bit. */
+int slam_math_probe2(int op, const double* a, const double* b, const double* c, const double* d, double* out, int out_per_item, int n, int device);
 const char* slam_last_error(void);
 const char* slam_version(void);
 

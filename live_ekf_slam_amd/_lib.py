@@ -152,6 +152,7 @@ SIGNATURES = {
     "slam_reset_counters_async": (C.c_int, [_H]),
     "slam_kernel_info": (C.c_int, [_H, C.c_int, C.c_char_p, C.c_int, _ip]),
     "slam_math_probe": (C.c_int, [_dp, _dp, _dp, C.c_int, C.c_int]),
+    "slam_math_probe2": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int]),
     # include/slam_pgs.h
     "pgs_create": (C.c_int, [C.POINTER(SlamConfig), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
     "pgs_destroy": (C.c_int, [_H]),

@@ -477,4 +477,29 @@ int slam_math_probe(const double* a, const double* b, double* out, int n, int de
     return SLAM_OK;
 }
 
+// one shared function per call on HOST arrays (slam_batch.h); the kernel is in ukf_kernel.hip
+int slam_math_probe2(int op, const double* a, const double* b, const double* c, const double* d, double* out, int out_per_item, int n, int device) {
+    if (op < 0 || op >= slam::kProbeOps) return slam_internal_fail(SLAM_ERR_ARG, "unknown probe op");
+    const int nin = slam::kProbeIn[op];
+    const double* const in[4] = {a, b, c, d};
+    for (int k = 0; k < nin; ++k)
+        if (!in[k]) return slam_internal_fail(SLAM_ERR_ARG, "the op reads an input array that is NULL");
+    if (!out || n <= 0 || out_per_item < slam::kProbeOut[op]) return slam_internal_fail(SLAM_ERR_ARG, "bad argument");
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<double> din[4], dout;   // (released on every return)
+    const double* dp[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < nin; ++k) {
+        HIP_TRY(din[k].reserve(n));
+        HIP_TRY(hipMemcpy(din[k], in[k], sizeof(double) * n, hipMemcpyHostToDevice));
+        dp[k] = din[k];
+    }
+    const size_t nout = (size_t)out_per_item * (size_t)n;
+    HIP_TRY(dout.reserve(nout));
+    HIP_TRY(hipMemcpy(dout, out, sizeof(double) * nout, hipMemcpyHostToDevice));   // items beyond the op's outputs keep the caller's values
+    HIP_TRY(slam::launch_math_probe2(op, dp[0], dp[1], dp[2], dp[3], dout, out_per_item, n, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, dout, sizeof(double) * nout, hipMemcpyDeviceToHost));
+    return SLAM_OK;
+}
+
 }  // extern "C"

@@ -11,8 +11,18 @@
 //
 // The algorithms are the classical ones (Cody–Waite π/2 reduction; minimax odd/even polynomials on
 // [-π/4, π/4] for sin/cos; 4-interval argument reduction + degree-11 odd polynomial for atan), with the
-// published fdlibm/msun coefficient sets; error < 1 ulp.  The oracle can also be built against libm
+// published fdlibm/msun coefficient sets.  The oracle can also be built against libm
 // (LibmMath policy in oracle/slam_oracle.cpp) to show how little the choice matters (tests/test_oracle_math.py).
+//
+// Accuracy against the exact value (mpmath at 300 bits, tests/test_math_edges_cpu.py, on the edge sets of tests/math_edges.py; the unit
+// is the ulp of the exact value):
+//   det_sincos  < 1 ulp for |x| <= 2^20 * pi/2; measured maximum 0.757 ulp (cos 41.62610266006476), arguments one and two ulp either
+//               side of k * pi/2 up to k = 1048575 included.  See det_sincos for what happens beyond.
+//   det_atan2   NOT below 1 ulp: measured maximum 1.163 ulp at (y, x) = (-8.964202309202546, -3.353288908687162); the test's bound is
+//               1.25 ulp.  With x > 0 (det_atan of the rounded quotient |y / x|) 1.133 ulp; x < 0 adds the two roundings of
+//               (z - pi_lo) - pi.
+//   rem2pi      exact (the IEEE remainder, ties included); inv2x2_lu: left residual |Si S - I| <= 1.7 u kappa_inf(S) measured on SPD S.
+// What is the same on host and device is the BITS, which tests/test_math_edges_gpu.py checks on every element of the same sets.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -64,8 +74,16 @@ SLAM_HD double k_cos(double x, double y) {
     return w + (((1.0 - w) - hz) + (z * r - x * y));
 }
 
-// sin and cos of x together.  Valid for |x| < ~1e6 (Cody–Waite reduction); the filters only ever pass wrapped
-// headings plus a bearing, and the simulator's unwrapped true yaw stays within a few hundred radians.
+// sin and cos of x together.  The filters only ever pass wrapped headings plus a bearing, and the simulator's unwrapped true yaw stays
+// within a few hundred radians.
+// DOMAIN: |x| <= 2^20 * pi/2 (1 647 099.3), i.e. fn = rint(x * 2/pi) <= 2^20 in the Cody–Waite reduction below; nothing enforces it.
+//   Beyond it no accuracy is claimed.  Measured (tests/test_math_edges_cpu.py): the constants carry fewer bits than the 33 the proof
+//   allows for (pio2_1 31, pio2_2 32), so the result is in fact still below 1 ulp at 1.65e6, 3.3e6 and 6.6e6.  Arguments next to a
+//   multiple of pi/2 go first, where fn * pio2_2 rounds (odd fn from ~4.02e6, |x| > 6.31e6): 7e7 ulp.  From fn >= 2^22 (|x| >= 6.59e6)
+//   fn * pio2_1 can round too (6.6e6 still escapes), and at 1.32e7 and every doubling above it the result is 1e9 ulp off.
+//   Up to |x| <= 1e18 the result is still finite garbage that host and device compute alike, bit for bit.  Beyond 2^62 * pi/2 (5.8e18)
+//   the conversion (long long)fn is undefined behaviour in C++ (x86 gives LLONG_MIN, quadrant 0; the GPU saturates, quadrant 3): there,
+//   and only there, host and device are NOT claimed equal.  +-inf and NaN give NaN on both.
 SLAM_HD void det_sincos(double x, double* s, double* c) {
     const double invpio2 = 6.36619772367581382433e-01;
     const double pio2_1 = 1.57079632673412561417e+00;   // first 33 bits of pi/2
@@ -79,7 +97,7 @@ SLAM_HD void det_sincos(double x, double* s, double* c) {
     }
     double fn = rint(x * invpio2);
     // two compensated subtraction rounds: 33 + 33 + 53 bits of pi/2 (abs. error ~ fn * 2^-119)
-    double t = x - fn * pio2_1;  // exact: fn < 2^20 and pio2_1 has 33 significant bits
+    double t = x - fn * pio2_1;  // exact: fn <= 2^20 and pio2_1 has at most 33 significant bits
     double w = fn * pio2_2;
     double r = t - w;
     w = fn * pio2_2t - ((t - r) - w);

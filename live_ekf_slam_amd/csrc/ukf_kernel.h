@@ -120,4 +120,25 @@ struct UkfInitParams {
 };
 hipError_t launch_ukf_init(const UkfInitParams& p, hipStream_t stream);
 
+// slam_math_probe2 (include/slam_batch.h): one shared function per launch, selected by `op`, on device arrays a..d[n] -> out[n][out_per_item].
+// The kernel lives in ukf_kernel.hip so that a second translation unit (other code generation options than ekf_kernel.hip, which holds
+// slam_math_probe's kernel) compiles slam_math.h / slam_rng.h for a probe, and so that tsincos / yaw_of above are within its reach.
+enum MathProbeOp {
+    kProbeSincos = 0,     // a                  -> det_sincos: sin, cos
+    kProbeAtan2 = 1,      // a = y, b = x       -> det_atan2
+    kProbeRem2pi = 2,     // a                  -> rem2pi, wrap2pi (the library remainder)
+    kProbeArith = 3,      // a, b               -> sqrt(a), a / b, (double)(float)a
+    kProbeInv2x2 = 4,     // a..d = S[0..3]     -> Si[0..3], ok
+    kProbeAssocAbs = 5,   // a, b = as_int      -> assoc_abs
+    kProbeTsincos = 6,    // (float)a, b = float_trig -> tsincos: sin, cos
+    kProbeYawOf = 7,      // a = c, b = s       -> yaw_of
+    kProbeNoisePair = 8,  // a..d = packed (seed, inst, t, p), see slam_batch.h -> u0, u1
+    kProbeOps = 9
+};
+// inputs read / outputs written per item by each op (the host allocates and checks by these)
+static constexpr int kProbeIn[kProbeOps] = {1, 2, 1, 2, 4, 2, 2, 2, 4};
+static constexpr int kProbeOut[kProbeOps] = {2, 1, 2, 3, 5, 1, 2, 1, 2};
+hipError_t launch_math_probe2(int op, const double* a, const double* b, const double* c, const double* d, double* out, int out_per_item, int n,
+                              hipStream_t stream);
+
 }  // namespace slam

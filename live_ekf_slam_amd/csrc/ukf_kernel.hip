@@ -1360,4 +1360,53 @@ hipError_t launch_ukf_init(const UkfInitParams& p, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// One shared function per launch (MathProbeOp, ukf_kernel.h) on item i; o = out + i * out_per_item holds kProbeOut[op] results.  Only the
+// first kProbeIn[op] of a..d are read (the others may be NULL).
+__global__ void math_probe2_kernel(int op, const double* a, const double* b, const double* c, const double* d, double* out, int out_per_item,
+                                   int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double* const o = out + (size_t)i * out_per_item;
+    switch (op) {
+    case kProbeSincos: {
+        double s, co;
+        det_sincos(a[i], &s, &co);
+        o[0] = s; o[1] = co;
+        break;
+    }
+    case kProbeAtan2: o[0] = det_atan2(a[i], b[i]); break;
+    case kProbeRem2pi: o[0] = rem2pi(a[i]); o[1] = wrap2pi(a[i]); break;
+    case kProbeArith: o[0] = sqrt(a[i]); o[1] = a[i] / b[i]; o[2] = (double)(float)a[i]; break;
+    case kProbeInv2x2: {
+        const double S[4] = {a[i], b[i], c[i], d[i]};
+        double Si[4];
+        const bool ok = inv2x2_lu(S, Si);
+        o[0] = Si[0]; o[1] = Si[1]; o[2] = Si[2]; o[3] = Si[3]; o[4] = ok ? 1.0 : 0.0;
+        break;
+    }
+    case kProbeAssocAbs: o[0] = (double)assoc_abs(a[i], b[i] != 0.0 ? 1 : 0); break;
+    case kProbeTsincos: {
+        double s, co;
+        tsincos((float)a[i], b[i] != 0.0 ? 1 : 0, &s, &co);
+        o[0] = s; o[1] = co;
+        break;
+    }
+    case kProbeYawOf: o[0] = (double)yaw_of(a[i], b[i]); break;
+    case kProbeNoisePair: {   // a = seed & (2^48 - 1), b = inst & (2^48 - 1), c = (seed >> 48) + 65536 t, d = (inst >> 48) + 65536 p: all exact
+        const uint64_t ua = (uint64_t)a[i], ub = (uint64_t)b[i], uc = (uint64_t)c[i], ud = (uint64_t)d[i];
+        const uint64_t seed = ua | ((uc & 0xFFFFull) << 48), inst = ub | ((ud & 0xFFFFull) << 48);
+        double u0, u1;
+        noise_pair(seed, inst, (uint32_t)(uc >> 16), (uint32_t)(ud >> 16), &u0, &u1);
+        o[0] = u0; o[1] = u1;
+        break;
+    }
+    default: break;
+    }
+}
+hipError_t launch_math_probe2(int op, const double* a, const double* b, const double* c, const double* d, double* out, int out_per_item, int n,
+                              hipStream_t stream) {
+    hipLaunchKernelGGL(math_probe2_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, op, a, b, c, d, out, out_per_item, n);
+    return hipGetLastError();
+}
+
 }  // namespace slam

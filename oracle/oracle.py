@@ -93,6 +93,15 @@ def lib():
         for name in ("orc_det_atan2", "orc_libm_atan2"):
             getattr(L, name).argtypes = [_dp, _dp, _dp, C.c_int]
         L.orc_libm_remainder2pi.argtypes = [_dp, _dp, C.c_int]
+        L.orc_rem2pi.argtypes = [_dp, _dp, C.c_int]
+        for name in ("orc_inv2x2_shared", "orc_inv2x2_own"):
+            getattr(L, name).argtypes = [_dp, _dp, _ip, C.c_int]
+        L.orc_assoc_abs.argtypes = [_dp, _ip, _fp, C.c_int]
+        L.orc_noise_pairs.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _dp, C.c_int]
+        L.orc_double_to_float.argtypes = [_dp, _fp, C.c_int]
+        for name in ("orc_det_sincos", "orc_libm_sincos", "orc_det_atan2", "orc_libm_atan2", "orc_libm_remainder2pi", "orc_rem2pi", "orc_inv2x2_shared",
+                     "orc_inv2x2_own", "orc_assoc_abs", "orc_noise_pairs", "orc_double_to_float"):
+            getattr(L, name).restype = None
         _lib = L
     return _lib
 

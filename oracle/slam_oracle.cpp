@@ -370,6 +370,16 @@ void orc_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
     for (int i = 0; i < 4; ++i) out[i] = r.v[i];
 }
 void orc_noise_pair(uint64_t seed, uint64_t inst, uint32_t t, uint32_t p, double out[2]) { slam::noise_pair(seed, inst, t, p, &out[0], &out[1]); }
+// array forms for the edge-set tests (tests/test_math_edges_*.py)
+void orc_rem2pi(const double* x, double* out, int n) { for (int i = 0; i < n; ++i) out[i] = slam::rem2pi(x[i]); }
+// S: [n][4] row-major; Si: [n][4]; ok: [n].  _shared: the text the kernels compile; _own: the oracle's independently written one
+void orc_inv2x2_shared(const double* S, double* Si, int* ok, int n) { for (int i = 0; i < n; ++i) ok[i] = slam::inv2x2_lu(S + 4 * i, Si + 4 * i) ? 1 : 0; }
+void orc_inv2x2_own(const double* S, double* Si, int* ok, int n) { for (int i = 0; i < n; ++i) ok[i] = orc::inv2x2_lu(S + 4 * i, Si + 4 * i) ? 1 : 0; }
+void orc_assoc_abs(const double* d, const int* as_int, float* out, int n) { for (int i = 0; i < n; ++i) out[i] = slam::assoc_abs(d[i], as_int[i]); }
+void orc_noise_pairs(const uint64_t* seed, const uint64_t* inst, const uint32_t* t, const uint32_t* p, double* out, int n) {   // out: [n][2]
+    for (int i = 0; i < n; ++i) slam::noise_pair(seed[i], inst[i], t[i], p[i], &out[2 * i], &out[2 * i + 1]);
+}
+void orc_double_to_float(const double* x, float* out, int n) { for (int i = 0; i < n; ++i) out[i] = (float)x[i]; }
 
 // ---- EKF ------------------------------------------------------------------------------------------------------
 void* orc_ekf_create(const slam_config* cfg, int L_max, int math, int mode) { return new Ekf(*cfg, L_max, math, mode); }
