@@ -154,7 +154,8 @@ int pgs_get_graph(pgs_handle* h, int instance, int which, double* poses, double*
 /* msg_measurement_connections (pose_graph.cpp:176-177): pairs (timestep, landmark index; -1 for a first detection).
  * conn [cap][2]; *n = number of pairs (may exceed cap). */
 int pgs_get_connections(pgs_handle* h, int instance, int32_t* conn, int cap, int32_t* n);
-/* Per instance [batch]: LM iterations, lambda trials, status bits; initial / final objective 0.5*sum|e|^2, final lambda. */
+/* Per instance [batch]: LM iterations, lambda trials, status bits; initial / final objective, final lambda.  The objective is sum rho:
+ * 0.5 |e|^2 of every prior and between factor, and of every landmark factor rho(|e|) of the loss set (pgs_set_robust; 0.5 |e|^2 without). */
 int pgs_get_stats(pgs_handle* h, int32_t* iterations, int32_t* trials, int32_t* flags, double* err_init,
                   double* err_final, double* lambda);
 /* compute_average_error as the pose-graph plot calls it (plotting_node.py:203-213,432-434) against the simulator's
@@ -201,6 +202,39 @@ int pgs_marginals_dev(pgs_handle* h, const double** d_pose_cov, const double** d
  * n = 2 M: 3N n^2 (triangular product, counted dense) + 12 * 3N n (chain recurrence + Gram) + 2 n^3 / 3 (R^-1 and its Gram)
  * + 3N n^2 + n^3 / 3 (the lambda = 0 factorisation: Schur complement and Cholesky). */
 int pgs_last_marginals_work(pgs_handle* h, double* flop, double* ms);
+
+/* ---- robust loss on the landmark factors ------------------------------------------------------------------------------------
+ * The graph's defence against bad detections (a wrong id, a range spike): GTSAM's noiseModel::Robust on every BearingRangeFactor, solved
+ * by iteratively reweighted least squares inside the same Levenberg-Marquardt loop.  With e the whitened residual of a factor and
+ * r = |e|:
+ *   PGS_LOSS_NONE (default)      rho = 0.5 r^2                                   w = 1
+ *   PGS_LOSS_HUBER, k            rho = 0.5 r^2 (r <= k), k (r - 0.5 k) (r > k)   w = 1 (r <= k), k / r (r > k)
+ *   PGS_LOSS_GEMAN_MCCLURE, k    rho = 0.5 k^2 r^2 / (k^2 + r^2)                 w = (k^2 / (k^2 + r^2))^2
+ * A factor is linearised as sqrt(w) e, sqrt(w) J with w at the linearisation point (frozen over the lambda trials that share the
+ * linearisation); its nonlinear cost is rho(r).  Prior and between factors stay Gaussian.  pgs_get_stats' objective is sum rho; the LM
+ * accept test compares it with the weighted linearised cost.  With PGS_LOSS_NONE every result is bit for bit what it is without these calls.
+ * kind unknown, or k NaN, <= 0 or +inf for a loss: SLAM_ERR_ARG (checked before the handle).  The setting may change between solves and
+ * takes effect at the next pgs_solve, pgs_marginals or pgs_factor_weights, in every solve schedule and in
+ * pgs_run_sim_every_iteration[_each]; pgs_marginals then linearises the weighted graph (weights at the values it is called for).  Changing
+ * it invalidates the marginals and the factor weights.  One setting per handle; a loss costs 8 bytes of device memory per factor slot
+ * and lambda lane, allocated by the first call that solves with it. */
+enum pgs_loss_kind { PGS_LOSS_NONE = 0, PGS_LOSS_HUBER = 1, PGS_LOSS_GEMAN_MCCLURE = 2 };
+int pgs_set_robust(pgs_handle* h, int kind, double k);
+int pgs_get_robust(const pgs_handle* h, int* kind, double* k);
+/* The weight w of every stored BearingRangeFactor at the values `which` (0 = initial_estimate, 1 = result; 1 needs a pgs_solve): which
+ * detections the solve did not believe.  Device array [batch][N_max][k_per_pose] in slot order (detection s stored at pose t: [t][s], the
+ * order of pgs_get_connections); slots at or beyond a pose's count hold NaN; with PGS_LOSS_NONE every stored factor gets 1.0.
+ * Synchronous; changes nothing else (results and statistics are bit for bit what they are without the call); invalidated by the calls
+ * that invalidate the marginals.  Its output buffer is allocated by the first call. */
+int pgs_factor_weights(pgs_handle* h, int which);
+/* One instance's weights: w [min(cap, *n)] of *n = (timestep + 1) * k_per_pose entries.  SLAM_ERR_STATE before a valid pgs_factor_weights. */
+int pgs_get_factor_weights(pgs_handle* h, int instance, double* w, int cap, int32_t* n);
+/* The device buffer for a consumer on the GPU; valid until the next pgs_factor_weights. */
+int pgs_factor_weights_dev(pgs_handle* h, const double** d_w);
+/* TEST HOOK, not part of the solver interface: the loss function compiled for the HOST (the same source as the kernels, no device
+ * needed): rho, w and sqrt(w) at residual norm r.  Argument errors as pgs_set_robust. */
+int pgs_robust_loss_host(int kind, double k, double r, double* rho, double* w, double* sw);
+
 int pgs_sync(pgs_handle* h);
 int pgs_timestep(const pgs_handle* h);
 

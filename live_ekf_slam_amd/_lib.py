@@ -190,6 +190,12 @@ SIGNATURES = {
     "pgs_get_marginals": (C.c_int, [_H, C.c_int, _dp, _dp, _ip]),
     "pgs_marginals_dev": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "pgs_last_marginals_work": (C.c_int, [_H, _dp, _dp]),
+    "pgs_set_robust": (C.c_int, [_H, C.c_int, C.c_double]),
+    "pgs_get_robust": (C.c_int, [_H, C.POINTER(C.c_int), _dp]),
+    "pgs_factor_weights": (C.c_int, [_H, C.c_int]),
+    "pgs_get_factor_weights": (C.c_int, [_H, C.c_int, _dp, C.c_int, _ip]),
+    "pgs_factor_weights_dev": (C.c_int, [_H, C.POINTER(C.c_void_p)]),
+    "pgs_robust_loss_host": (C.c_int, [C.c_int, C.c_double, C.c_double, _dp, _dp, _dp]),
     "pgs_sync": (C.c_int, [_H]),
     "pgs_timestep": (C.c_int, [_H]),
     # include/slam_multi.h

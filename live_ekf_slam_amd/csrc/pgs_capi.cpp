@@ -19,6 +19,9 @@
 
 #define fail slam_internal_fail
 
+static_assert(PGS_LOSS_NONE == slam::kPgsLossNone && PGS_LOSS_HUBER == slam::kPgsLossHuber && PGS_LOSS_GEMAN_MCCLURE == slam::kPgsLossGemanMcClure,
+              "pgs_loss_kind (slam_pgs.h) and pgs_robust.h number the losses alike");
+
 struct pgs_handle {
     slam_config cfg;
     int B, N_max, L_max, KP, LD, device;
@@ -88,6 +91,13 @@ struct pgs_handle {
     hipEvent_t mg_ev[2] = {nullptr, nullptr};
     bool mg_valid = false;
     double mg_ms = 0.0;
+    // robust loss of the bearing-range factors (pgs_set_robust): the setting as the caller left it; apply_robust copies it into p - with lin0
+    // behind it - when the next solve / marginals / factor weights begin.  fw: the factor weights' own output, [B][N_max][KP], first use.
+    int loss_kind = slam::kPgsLossNone;
+    double loss_k = 0.0;
+    DevBuf<double> rb_lin0;                    // p.lin0, [slots][N_max * KP]: allocated by the first such call with a loss set
+    DevBuf<double> fw;
+    bool fw_valid = false;
 };
 
 namespace {
@@ -107,6 +117,25 @@ int check(pgs_handle* h) {
     if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
     HIP_TRY(hipSetDevice(h->device));
     return SLAM_OK;
+}
+
+// The handle's loss setting into the parameter block the kernels get.  A loss needs lin0 (8 bytes per factor slot and lambda lane): allocated
+// here once; if that fails the call returns the error and the handle - parameter block included - is what it was.
+int apply_robust(pgs_handle* h) {
+    if (h->loss_kind != slam::kPgsLossNone && !h->rb_lin0) {
+        DevBuf<double> a;
+        if (a.reserve((size_t)h->B * h->tune.lanes * h->N_max * h->KP) != hipSuccess)
+            return fail(SLAM_ERR_HIP, "out of device memory for the robust loss' per-factor terms (%zu bytes)", sizeof(double) * (size_t)h->B * h->tune.lanes * h->N_max * h->KP);
+        h->rb_lin0 = std::move(a);
+        h->p.lin0 = h->rb_lin0;
+    }
+    h->p.loss_kind = h->loss_kind; h->p.loss_k = h->loss_k;
+    return SLAM_OK;
+}
+
+bool robust_args_ok(int kind, double k) {
+    if (kind == slam::kPgsLossNone) return true;
+    return (kind == slam::kPgsLossHuber || kind == slam::kPgsLossGemanMcClure) && k > 0.0 && k < (double)INFINITY;   // (NaN fails both)
 }
 
 // the layout of Y for segments of SL poses (0: the sequential chain): the separators' rows live behind the pose rows (pgs_kernel.h: yr_rc, yr_sep)
@@ -231,7 +260,7 @@ int pgs_create(const slam_config* cfg, int batch, int N_max, int L_max, int k_pe
     A(&p.dl, S * L * 2); A(&p.dp, S * N * 3);
     A(&p.lambda, S); A(&p.error, B); A(&p.cur_error, B); A(&p.err_init, B);
     A(&p.iters, B); A(&p.trials, B); A(&p.state, S + 1); AC(&p.solve_ok, 1); A(&p.n_active, 64); A(&p.alist, S); A(&p.inst_flop, B); A(&p.work, 3);
-    A(&p.nl, B); A(&p.nlin, S); A(&p.nerr, S); A(&p.nok, S);
+    A(&p.nl, B); A(&p.nlin, S); A(&p.nerr, S); A(&p.nok, S); A(&p.oldlin, S);
     D(h->dcount, B); D(h->dsec, B * 3); D(h->dout, B);
     D(h->d_cnt, (size_t)slam_host::kPgsMaxGroups * 16); D(h->d_wait, (size_t)slam_host::kPgsMaxGroups);
     if (getenv("SLAM_PGS_PROF")) { A(&p.prof, S * 24); }   // [S][8] chol phase timers, then [S][2][8] per-workgroup stamps of the fused chain
@@ -319,7 +348,7 @@ int pgs_set_maps(pgs_handle* h, const double* maps, const int32_t* L, int L_stri
 
 int pgs_init(pgs_handle* h, float x0, float y0, float yaw0) {
     TRY(check(h));
-    h->mg_valid = false;
+    h->mg_valid = false; h->fw_valid = false;
     h->timestep = 0; h->p.N = 1;
     h->seg_cur = h->tune.seg_len;
     HIP_TRY(slam::pgs_launch_init(h->p, x0, y0, yaw0, h->stream));
@@ -384,7 +413,7 @@ int enter_ticks(pgs_handle* h, const char* who, const float* cmds, int T, unsign
     if (h->timestep + T >= h->N_max)
         return sim ? fail(SLAM_ERR_STATE, "timestep %d + %d commands exceed the pose capacity N_max = %d", h->timestep, T, h->N_max)
                    : fail(SLAM_ERR_STATE, "pose capacity N_max = %d reached", h->N_max);
-    h->mg_valid = false;
+    h->mg_valid = false; h->fw_valid = false;
     return put_commands(h, cmds, src_dev, T, each);
 }
 
@@ -423,7 +452,7 @@ int pgs_init_each(pgs_handle* h, const float* pose0, const double* truth0) {
     if (truth0) HIP_TRY(h->dtruth_each.reserve(3 * B));
     HIP_TRY(hipMemcpyAsync(h->dpose_each, pose0, sizeof(float) * 3 * B, hipMemcpyHostToDevice, h->stream));
     if (truth0) HIP_TRY(hipMemcpyAsync(h->dtruth_each, truth0, sizeof(double) * 3 * B, hipMemcpyHostToDevice, h->stream));
-    h->mg_valid = false;
+    h->mg_valid = false; h->fw_valid = false;
     h->timestep = 0; h->p.N = 1;
     h->seg_cur = h->tune.seg_len;
     HIP_TRY(slam::pgs_launch_init_each(h->p, h->dpose_each, truth0 ? h->dtruth_each.get() : nullptr, h->stream));
@@ -847,7 +876,8 @@ int total_profile(pgs_handle* h) {
 int pgs_solve(pgs_handle* h) {
     TRY(check(h));
     if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_solve");
-    h->mg_valid = false; h->solved = true;
+    TRY(apply_robust(h));
+    h->mg_valid = false; h->fw_valid = false; h->solved = true;
     h->p.N = h->timestep + 1;
     h->p.b_off = 0; h->p.b_cnt = h->B;
     TRY(plan_segments(h));
@@ -882,7 +912,7 @@ int pgs_set_groups(pgs_handle* h, int groups) { TRY(check(h)); h->tune.groups = 
 
 int pgs_adopt_result(pgs_handle* h) {
     TRY(check(h));
-    h->mg_valid = false;
+    h->mg_valid = false; h->fw_valid = false;
     HIP_TRY(slam::pgs_launch_adopt(h->p, h->stream));
     return SLAM_OK;
 }
@@ -1088,6 +1118,7 @@ int pgs_marginals(pgs_handle* h, int which) {
     if (which != 0 && which != 1) return fail(SLAM_ERR_ARG, "which = %d (0: initial_estimate, 1: result)", which);
     if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_marginals");
     if (which == 1 && !h->solved) return fail(SLAM_ERR_STATE, "pgs_marginals(which = 1): no result yet (pgs_solve has not run since pgs_init)");
+    TRY(apply_robust(h));
     h->mg_valid = false;
     const size_t B = (size_t)h->B;
     if (!h->mg_pose) {   // first call: everything or nothing (each owner is filled only once all allocations succeeded)
@@ -1164,6 +1195,66 @@ int pgs_last_marginals_work(pgs_handle* h, double* flop, double* ms) {
         *flop = tot;
     }
     if (ms) *ms = h->mg_ms;
+    return SLAM_OK;
+}
+
+// ---- robust loss on the bearing-range factors (pgs_robust.h) ----
+int pgs_set_robust(pgs_handle* h, int kind, double k) {
+    if (!robust_args_ok(kind, k)) return fail(SLAM_ERR_ARG, "pgs_set_robust: kind %d, k %g (kind 0 | 1 | 2; k finite and > 0 for a loss)", kind, k);
+    TRY(check(h));
+    h->loss_kind = kind; h->loss_k = kind == slam::kPgsLossNone ? 0.0 : k;
+    h->mg_valid = false; h->fw_valid = false;   // what was computed belongs to the setting it was computed with
+    return SLAM_OK;
+}
+
+int pgs_get_robust(const pgs_handle* h, int* kind, double* k) {
+    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
+    if (kind) *kind = h->loss_kind;
+    if (k) *k = h->loss_k;
+    return SLAM_OK;
+}
+
+int pgs_robust_loss_host(int kind, double k, double r, double* rho, double* w, double* sw) {
+    if (!robust_args_ok(kind, k) || !rho || !w || !sw) return fail(SLAM_ERR_ARG, "pgs_robust_loss_host: kind %d, k %g, or a NULL output", kind, k);
+    slam::pgs_robust_loss(kind, k, r * r, r, rho, w, sw);
+    return SLAM_OK;
+}
+
+int pgs_factor_weights(pgs_handle* h, int which) {
+    TRY(check(h));
+    if (which != 0 && which != 1) return fail(SLAM_ERR_ARG, "which = %d (0: initial_estimate, 1: result)", which);
+    if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_factor_weights");
+    if (which == 1 && !h->solved) return fail(SLAM_ERR_STATE, "pgs_factor_weights(which = 1): no result yet (pgs_solve has not run since pgs_init)");
+    h->fw_valid = false;
+    if (!h->fw) {   // one allocation: there or not
+        DevBuf<double> a;
+        if (a.reserve((size_t)h->B * h->N_max * h->KP) != hipSuccess)
+            return fail(SLAM_ERR_HIP, "pgs_factor_weights: out of device memory for the output (%zu bytes)", sizeof(double) * (size_t)h->B * h->N_max * h->KP);
+        h->fw = std::move(a);
+    }
+    slam::PgsParams q = h->p;   // the setting of now; it needs none of the solve's work space (lin0 included)
+    q.N = h->timestep + 1; q.loss_kind = h->loss_kind; q.loss_k = h->loss_k;
+    HIP_TRY(slam::pgs_launch_factor_weights(q, which, h->fw, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->fw_valid = true;
+    return SLAM_OK;
+}
+
+int pgs_get_factor_weights(pgs_handle* h, int inst, double* w, int cap, int32_t* n) {
+    TRY(check(h));
+    if (inst < 0 || inst >= h->B) return fail(SLAM_ERR_ARG, "instance %d out of range", inst);
+    if (cap < 0 || (cap > 0 && !w)) return fail(SLAM_ERR_ARG, "bad output (w, cap = %d)", cap);
+    if (!h->fw_valid) return fail(SLAM_ERR_STATE, "no factor weights for the current values: call pgs_factor_weights after the last update / solve");
+    const size_t have = (size_t)(h->timestep + 1) * h->KP, take = have < (size_t)cap ? have : (size_t)cap;
+    if (take) HIP_TRY(hipMemcpy(w, h->fw + (size_t)inst * h->N_max * h->KP, sizeof(double) * take, hipMemcpyDeviceToHost));
+    if (n) *n = (int32_t)have;
+    return SLAM_OK;
+}
+
+int pgs_factor_weights_dev(pgs_handle* h, const double** d_w) {
+    TRY(check(h));
+    if (!h->fw_valid) return fail(SLAM_ERR_STATE, "no factor weights for the current values: call pgs_factor_weights after the last update / solve");
+    if (d_w) *d_w = h->fw;
     return SLAM_OK;
 }
 

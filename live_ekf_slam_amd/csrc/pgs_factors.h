@@ -93,7 +93,18 @@ __device__ __forceinline__ double block_sum(double v, double* s_buf) {
     return s_buf[0];
 }
 
-// 0.5 * sum |whitened e|^2 of the factors owned by pose i: prior (i = 0), between (i, i+1), bearing-range at i
+// cost of one bearing-range factor with whitened residual e: 0.5 |e|^2, or (RB) rho(|e|) of the handle's robust loss (pgs_robust.h)
+template <bool RB>
+__device__ __forceinline__ double factor_cost(const PgsParams& p, const double e[2]) {
+    const double ss = e[0] * e[0] + e[1] * e[1];
+    if (!RB) return 0.5 * ss;
+    double rho, w, sw;
+    pgs_robust_loss(p.loss_kind, p.loss_k, ss, sqrt(ss), &rho, &w, &sw);
+    return rho;
+}
+
+// sum of the costs of the factors owned by pose i: 0.5 |whitened e|^2 of the prior (i = 0) and the between (i, i+1), factor_cost of the bearing-range at i
+template <bool RB>
 __device__ __forceinline__ double pose_cost(const PgsParams& p, const Inst& g, const double* pose, const double* lm, int i, int N) {
     double acc = 0.0, e[3];
     if (i == 0) {
@@ -109,15 +120,15 @@ __device__ __forceinline__ double pose_cost(const PgsParams& p, const Inst& g, c
         const size_t k = (size_t)i * p.KP + s;
         const int j = g.mlm[k] & (kPgsFirstBit - 1);
         bearing_range_factor<false>(p, pose + 3 * i, lm + 2 * j, g.mb[k], g.mr[k], e, nullptr, nullptr);
-        acc = acc + 0.5 * (e[0] * e[0] + e[1] * e[1]);
+        acc = acc + factor_cost<RB>(p, e);
     }
     return acc;
 }
 
-template <int TPB>
+template <int TPB, bool RB>
 __device__ __forceinline__ double block_cost(const PgsParams& p, int b, int N, const double* pose, const double* lm, double* s_buf) {
     const Inst g = inst_view(p, b);
     double acc = 0.0;
-    for (int i = threadIdx.x; i < N; i += TPB) acc = acc + pose_cost(p, g, pose, lm, i, N);
+    for (int i = threadIdx.x; i < N; i += TPB) acc = acc + pose_cost<RB>(p, g, pose, lm, i, N);
     return block_sum<TPB>(acc, s_buf);
 }

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "host/pgs_limits.h"
+#include "pgs_robust.h"
 
 namespace slam {
 
@@ -136,6 +137,15 @@ struct PgsParams {
     // ---- factor constants ----
     double* prior;                     // [B][3] mean of the PriorFactor of instance b (pgs_init_kernel / pgs_init_each_kernel)
     double w_prior[3], w_btw[3], w_meas[2];   // 1 / sigma
+    // ---- robust loss of the bearing-range factors (pgs_robust.h; pgs_set_robust) ----
+    // loss_kind = kPgsLossNone: the kernels instantiated without the loss run (the code of before, lin0 and oldlin untouched).  Otherwise every
+    // bearing-range factor is linearised as sw e, sw J with its weight at the linearisation point, its cost is rho(r), and pgs_decide_kernel takes
+    // oldLin - the linearised cost at delta = 0, which is `error` only for Gaussian factors - from oldlin.
+    int32_t loss_kind; double loss_k;
+    double* lin0;                      // [S][N_max*KP]   per factor slot: 0.5 w r^2 at the linearisation point (pgs_lin_factor_kernel ->
+                                       //                 pgs_linearize_kernel); allocated by the first solve / marginals with a loss set
+    double* oldlin;                    // [S]             the slot's linearised cost at delta = 0: the Gaussian terms + sum 0.5 w r^2, slot order
+                                       //                 within a pose, then the block tree (pgs_linearize_kernel, once per linearisation)
 };
 
 // geometry of the segmented elimination: separators at the poses k SL, k = 1 .. seg_ns; segment ps holds the poses [seg_lo, seg_hi)
@@ -178,5 +188,9 @@ hipError_t pgs_launch_avg_error(const PgsParams& p, int which, double* out, hipS
 // arrays of the CALLER ([B] each; the solve's own are not touched), p.nfact_max at an upper bound of the factors of an instance.
 // pose_cov [B][N_max][9], lm_cov [B][L_max][4], status [B] (0 ok, 1 singular: its blocks are NaN), flop [B] (the model, pgs_marginals.h).
 hipError_t pgs_launch_marginals(const PgsParams& p, int which, double* pose_cov, double* lm_cov, int32_t* status, double* flop, hipStream_t s);
+// IRLS weight of every stored bearing-range factor at initial_estimate (which = 0) / result (1): out [B][N_max][KP] in slot order (the indexing
+// of mb / mr), NaN in the slots at or beyond a pose's count and at poses the graph does not have; 1.0 everywhere stored with kPgsLossNone.
+// One thread per factor slot; reads the graph and the values only.
+hipError_t pgs_launch_factor_weights(const PgsParams& p, int which, double* out, hipStream_t s);
 
 }  // namespace slam

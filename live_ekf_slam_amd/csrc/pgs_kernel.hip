@@ -77,7 +77,8 @@ hipError_t pgs_launch_seg_plan(const PgsParams& p, hipStream_t s) {
 }
 
 hipError_t pgs_launch_lm_begin(const PgsParams& p, hipStream_t s) {
-    hipLaunchKernelGGL(pgs_lm_begin_kernel, dim3(p.b_cnt), dim3(TPB), 0, s, p);
+    if (p.loss_kind != kPgsLossNone) hipLaunchKernelGGL(pgs_lm_begin_kernel<true>, dim3(p.b_cnt), dim3(TPB), 0, s, p);
+    else hipLaunchKernelGGL(pgs_lm_begin_kernel<false>, dim3(p.b_cnt), dim3(TPB), 0, s, p);
     return hipGetLastError();
 }
 
@@ -86,8 +87,14 @@ hipError_t pgs_launch_trial_kernel(const PgsParams& p, int which, hipStream_t s)
     if (nslot <= 0) return hipSuccess;
     switch (which) {
     case 0:
-        if (p.nfact_max > 0) hipLaunchKernelGGL(pgs_lin_factor_kernel, dim3(nslot * ((p.nfact_max + LF_TPB - 1) / LF_TPB)), dim3(LF_TPB), 0, s, p);
-        hipLaunchKernelGGL(pgs_linearize_kernel, dim3(nslot), dim3(TPB), 0, s, p);
+        if (p.loss_kind != kPgsLossNone) {   // the weighted factors and oldlin (pgs_robust.h); the same launches
+            if (!p.lin0 || !p.oldlin) return hipErrorInvalidValue;
+            if (p.nfact_max > 0) hipLaunchKernelGGL(pgs_lin_factor_kernel<true>, dim3(nslot * ((p.nfact_max + LF_TPB - 1) / LF_TPB)), dim3(LF_TPB), 0, s, p);
+            hipLaunchKernelGGL(pgs_linearize_kernel<true>, dim3(nslot), dim3(TPB), 0, s, p);
+            break;
+        }
+        if (p.nfact_max > 0) hipLaunchKernelGGL(pgs_lin_factor_kernel<false>, dim3(nslot * ((p.nfact_max + LF_TPB - 1) / LF_TPB)), dim3(LF_TPB), 0, s, p);
+        hipLaunchKernelGGL(pgs_linearize_kernel<false>, dim3(nslot), dim3(TPB), 0, s, p);
         break;
     case 1: {
         if (p.seg_on) {   // segmented elimination: the interiors of all segments side by side, then the separator chain
@@ -151,9 +158,14 @@ hipError_t pgs_launch_trial_kernel(const PgsParams& p, int which, hipStream_t s)
         else hipLaunchKernelGGL(pgs_backsolve_kernel, dim3(nslot), dim3(BTPB), 0, s, p);
         break;
     default:   // the candidates of every slot, then GTSAM's accept / lambda / convergence logic per instance
-        if (p.nfact_max > 0) hipLaunchKernelGGL(pgs_eval_factor_kernel, dim3(nslot * ((p.nfact_max + LF_TPB - 1) / LF_TPB)), dim3(LF_TPB), 0, s, p);
+        if (p.nfact_max > 0) {
+            const dim3 grid(nslot * ((p.nfact_max + LF_TPB - 1) / LF_TPB));
+            if (p.loss_kind != kPgsLossNone) hipLaunchKernelGGL(pgs_eval_factor_kernel<true>, grid, dim3(LF_TPB), 0, s, p);
+            else hipLaunchKernelGGL(pgs_eval_factor_kernel<false>, grid, dim3(LF_TPB), 0, s, p);
+        }
         hipLaunchKernelGGL(pgs_evaluate_kernel, dim3(nslot), dim3(TPB), 0, s, p);
-        hipLaunchKernelGGL(pgs_decide_kernel, dim3(p.b_cnt), dim3(TPB), 0, s, p);
+        if (p.loss_kind != kPgsLossNone) hipLaunchKernelGGL(pgs_decide_kernel<true>, dim3(p.b_cnt), dim3(TPB), 0, s, p);
+        else hipLaunchKernelGGL(pgs_decide_kernel<false>, dim3(p.b_cnt), dim3(TPB), 0, s, p);
         break;
     }
     return hipGetLastError();
@@ -192,6 +204,12 @@ hipError_t pgs_launch_marginals(const PgsParams& p, int which, double* pose_cov,
     hipLaunchKernelGGL(pgs_marg_back_kernel, dim3(q.b_cnt), dim3(64 + q.LD), 0, s, q, pose_cov);
     const int ntile = (q.N + 15) / 16;
     hipLaunchKernelGGL(pgs_marg_gram_kernel, dim3(q.b_cnt * ntile), dim3(MG_TPB), 0, s, q, pose_cov, ntile);
+    return hipGetLastError();
+}
+
+hipError_t pgs_launch_factor_weights(const PgsParams& p, int which, double* out, hipStream_t s) {
+    const int nfb = (p.N_max * p.KP + LF_TPB - 1) / LF_TPB;
+    hipLaunchKernelGGL(pgs_factor_weights_kernel, dim3(p.B * nfb), dim3(LF_TPB), 0, s, p, which, out);
     return hipGetLastError();
 }
 

@@ -19,6 +19,7 @@ __device__ __forceinline__ int pgs_slot(const PgsParams& p, int bl) {
 // slots a trial-kernel launch covers
 __host__ __device__ __forceinline__ int pgs_nslot(const PgsParams& p) { return p.use_list ? p.n_list : p.b_cnt * (p.lanes > 0 ? p.lanes : 1); }
 
+template <bool RB>   // RB: a robust loss is set - the initial cost is sum rho (pgs_robust.h)
 __global__ __launch_bounds__(TPB) void pgs_lm_begin_kernel(const PgsParams p) {
     __shared__ double s_buf[TPB];
     const int b = blockIdx.x + p.b_off, tid = threadIdx.x;
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(TPB) void pgs_lm_begin_kernel(const PgsParams p) {
         f = block_sum<TPB>(f, s_buf);
         if (tid == 0) p.inst_flop[b] = f + extra;
     }
-    const double err = block_cost<TPB>(p, b, N, pw, lw, s_buf);
+    const double err = block_cost<TPB, RB>(p, b, N, pw, lw, s_buf);
     if (tid == 0) {
         p.error[b] = err; p.err_init[b] = err; p.cur_error[b] = err;
         p.lambda[b] = 1e-5;                    // LevenbergMarquardtParams::lambdaInitial
@@ -148,7 +149,10 @@ __device__ __forceinline__ void add_JtJ(double A[9], const double* J) {
 // at BASELINE configs[4]); a thread per pose walked its factors one after the other, each behind two dependent loads.  Every factor
 // leaves its blocks E (slot order and event order), the landmark terms Wl, and its SHARE of the pose block in PF; part 2 adds the shares
 // in slot order, so every sum has the terms and the order it always had (bit-identical to the one-kernel version).
+// RB (robust loss set, pgs_robust.h): the factor is linearised as sw e, sw J with its weight at these values, and leaves 0.5 w r^2 - its term of
+// the linearised cost at delta = 0 - in lin0 (8 bytes per factor; part 2 sums them into oldlin).  RB = false is the code of before.
 constexpr int LF_TPB = 256;
+template <bool RB>
 __global__ __launch_bounds__(LF_TPB) void pgs_lin_factor_kernel(const PgsParams p) {
     const int nfb = (p.nfact_max + LF_TPB - 1) / LF_TPB;
     const int bl = blockIdx.x / nfb, fb = blockIdx.x - bl * nfb;
@@ -165,6 +169,17 @@ __global__ __launch_bounds__(LF_TPB) void pgs_lin_factor_kernel(const PgsParams 
     const int j = g.mlm[k] & (kPgsFirstBit - 1);
     double e2[2], Jp[6], Jl[4];
     bearing_range_factor<true>(p, pose + 3 * i, lm + 2 * j, g.mb[k], g.mr[k], e2, Jp, Jl);
+    if (RB) {
+        const double ss = e2[0] * e2[0] + e2[1] * e2[1];
+        double rho, w, sw;
+        pgs_robust_loss(p.loss_kind, p.loss_k, ss, sqrt(ss), &rho, &w, &sw);
+        p.lin0[(size_t)b * p.N_max * KP + k] = 0.5 * (w * ss);
+        e2[0] *= sw; e2[1] *= sw;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) Jp[a] *= sw;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) Jl[a] *= sw;
+    }
     double* PF = p.PF + ((size_t)b * p.N_max * KP + k) * 12;
 #pragma unroll
     for (int a = 0; a < 3; ++a)
@@ -192,8 +207,11 @@ __global__ __launch_bounds__(LF_TPB) void pgs_lin_factor_kernel(const PgsParams 
 }
 
 // Linearisation, part 2: per pose the prior / between factors and the sum of its factors' shares (slot order); per landmark the sum of
-// its factors' terms (chronological order).
+// its factors' terms (chronological order).  RB: also oldlin, the linearised cost at delta = 0 - per pose the Gaussian terms and its factors'
+// lin0 in pose_cost's order, per thread and over the block in block_cost's; with every weight 1 these are the bits of block_cost.
+template <bool RB>
 __global__ __launch_bounds__(TPB) void pgs_linearize_kernel(const PgsParams p) {
+    __shared__ double s_buf[RB ? TPB : 1];
     const int b = pgs_slot(p, blockIdx.x), tid = threadIdx.x;
     if (p.state[b]) return;
     const int N = p.N, KP = p.KP, M = p.M[b];
@@ -206,10 +224,13 @@ __global__ __launch_bounds__(TPB) void pgs_linearize_kernel(const PgsParams p) {
     double* gpb = p.gp + (size_t)b * p.N_max * 3;
     const double* PFb = p.PF + (size_t)b * p.N_max * KP * 12;
     double* Wlb = p.Wl + (size_t)b * p.N_max * KP * 5;
+    double cacc = 0.0;
     for (int i = tid; i < N; i += TPB) {
         double A[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, gg[3] = {0, 0, 0}, e[3], J1[9];
+        double pc = 0.0;
         if (i == 0) {
             prior_factor(p, g.prior, pose, e);
+            if (RB) pc = pc + 0.5 * ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
 #pragma unroll
             for (int k = 0; k < 3; ++k) { A[4 * k] += p.w_prior[k] * p.w_prior[k]; gg[k] += -e[k] * p.w_prior[k]; }
         }
@@ -225,6 +246,7 @@ __global__ __launch_bounds__(TPB) void pgs_linearize_kernel(const PgsParams p) {
         }
         if (i + 1 < N) {   // between (i, i+1): J1
             between_factor<true>(p, pose + 3 * i, pose + 3 * (i + 1), g.cmds[2 * i], g.cmds[2 * i + 1], e, J1);
+            if (RB) pc = pc + 0.5 * ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
             add_JtJ<3>(A, J1);
 #pragma unroll
             for (int a = 0; a < 3; ++a) gg[a] += -(J1[a] * e[0] + J1[3 + a] * e[1] + J1[6 + a] * e[2]);
@@ -253,6 +275,11 @@ __global__ __launch_bounds__(TPB) void pgs_linearize_kernel(const PgsParams p) {
             for (int c = 0; c < 9; ++c) A[c] += PF[12 * (size_t)s + c];
 #pragma unroll
             for (int c = 0; c < 3; ++c) gg[c] += PF[12 * (size_t)s + 9 + c];
+        }
+        if (RB) {
+            const double* l0 = p.lin0 + ((size_t)b * p.N_max + i) * KP;
+            for (int q = 0; q < kc; ++q) pc = pc + l0[q];
+            cacc = cacc + pc;
         }
 #pragma unroll
         for (int k = 0; k < 9; ++k) Ab[9 * i + k] = A[k];
@@ -285,6 +312,10 @@ __global__ __launch_bounds__(TPB) void pgs_linearize_kernel(const PgsParams p) {
         }
         Db[3 * j] = d0; Db[3 * j + 1] = d1; Db[3 * j + 2] = d2;
         glb[2 * j] = g0; glb[2 * j + 1] = g1;
+    }
+    if (RB) {
+        const double ol = block_sum<TPB>(cacc, s_buf);
+        if (tid == 0) p.oldlin[b] = ol;
     }
     if (tid == 0) p.lin_ok[b] = 1;
 }

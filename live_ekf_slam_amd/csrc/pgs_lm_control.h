@@ -14,7 +14,10 @@ __device__ __forceinline__ void retract_pose(const double* ps, const double* d, 
 // Evaluation, part 1: one thread per FACTOR (see pgs_lin_factor_kernel) - its two terms of the linearised cost 0.5 |J delta + e|^2 at the
 // current values and its term of the true cost at the candidate (the factor forms the candidate pose / landmark itself, with the
 // expressions part 2 stores them with).  PF[3 slot ..] = {0.5 v_0^2, 0.5 v_1^2, 0.5 |e(candidate)|^2}; part 2 adds them where the one-kernel
-// version added them (bit-identical sums).
+// version added them (bit-identical sums).  RB (robust loss set): the linearised terms are those of the weighted factor sw e, sw J - the weight
+// recomputed from the residual at the current values, which are the linearisation point, so it is the bits pgs_lin_factor_kernel used and is
+// frozen over the trials and lanes of that linearisation - and the true cost is rho.  Same three doubles per factor slot.
+template <bool RB>
 __global__ __launch_bounds__(LF_TPB) void pgs_eval_factor_kernel(const PgsParams p) {
     const int nfb = (p.nfact_max + LF_TPB - 1) / LF_TPB;
     const int bl = blockIdx.x / nfb, fb = blockIdx.x - bl * nfb;
@@ -34,6 +37,16 @@ __global__ __launch_bounds__(LF_TPB) void pgs_eval_factor_kernel(const PgsParams
     const double bb = g.mb[k], rr = g.mr[k];
     double e2[2], Jp[6], Jl[4];
     bearing_range_factor<true>(p, pose, lm, bb, rr, e2, Jp, Jl);
+    if (RB) {
+        const double ss = e2[0] * e2[0] + e2[1] * e2[1];
+        double rho, w, sw;
+        pgs_robust_loss(p.loss_kind, p.loss_k, ss, sqrt(ss), &rho, &w, &sw);
+        e2[0] *= sw; e2[1] *= sw;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) Jp[a] *= sw;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) Jl[a] *= sw;
+    }
     // The three terms go COMPACT into the head of the slot's PF block, 24 bytes per factor slot (round 6; the linearisation's 96-byte records there are
     // dead once pgs_linearize_kernel has run): pgs_evaluate_kernel then reads a pose's terms as one contiguous run instead of three doubles out of every
     // 96-byte record - 27 -> 11 GB fetched per solve of 2048 graphs, that kernel 16.8 -> 10.5 ms (profiles/r06_pgs/summary.txt).  The writes here stay
@@ -48,7 +61,7 @@ __global__ __launch_bounds__(LF_TPB) void pgs_eval_factor_kernel(const PgsParams
     retract_pose(pose, dp, pn);
     ln[0] = lm[0] + dl[0]; ln[1] = lm[1] + dl[1];
     bearing_range_factor<false>(p, pn, ln, bb, rr, en, nullptr, nullptr);
-    PF[2] = 0.5 * (en[0] * en[0] + en[1] * en[1]);
+    PF[2] = factor_cost<RB>(p, en);
 }
 
 // linearised cost of the step, retraction, true cost of the candidate (part 2: the prior / between factors and the sums); GTSAM's
@@ -139,6 +152,7 @@ __global__ __launch_bounds__(TPB) void pgs_evaluate_kernel(const PgsParams p) {
     }
 }
 
+template <bool RB>   // RB: oldLin, the linearised cost at delta = 0, is the slot's oldlin (a robust loss is set); else it is the cost itself
 __global__ __launch_bounds__(TPB) void pgs_decide_kernel(const PgsParams p) {
     __shared__ int s_win, s_next;
     const int b = blockIdx.x + p.b_off, tid = threadIdx.x;
@@ -160,7 +174,7 @@ __global__ __launch_bounds__(TPB) void pgs_decide_kernel(const PgsParams p) {
             const double newLin = p.nlin[sl], newError = p.nerr[sl];
             bool success = false, stop = false;
             if (ok) {
-                const double oldLin = error;
+                const double oldLin = RB ? p.oldlin[sl] : error;   // (Gaussian factors: the linearised cost at delta = 0 IS the cost)
                 const double linChange = oldLin - newLin;
                 if (linChange >= 0.0) {
                     const double costChange = error - newError;
@@ -303,6 +317,29 @@ __global__ __launch_bounds__(TPB) void pgs_adopt_kernel(const PgsParams p) {
         p.tick_flop[2 * b] += tr * p.inst_flop[b];
         p.tick_flop[2 * b + 1] += tr * (n * n * n / 3.0 + 2.0 * n * n);
     }
+}
+
+// IRLS weight of every stored bearing-range factor at initial_estimate (which = 0) / result (1) - what the solve believed of each detection,
+// the graph's analogue of the gate's verdict.  One thread per factor SLOT (pose idx / KP, slot idx % KP), LF_TPB-thread workgroups per instance
+// like pgs_lin_factor_kernel; out [B][N_max][KP] in slot order, NaN where no factor is stored.  Reads the graph and the values, writes out only.
+__global__ __launch_bounds__(LF_TPB) void pgs_factor_weights_kernel(const PgsParams p, int which, double* out) {
+    const int KP = p.KP, nslots = p.N_max * KP;
+    const int nfb = (nslots + LF_TPB - 1) / LF_TPB;
+    const int b = blockIdx.x / nfb, idx = (blockIdx.x - b * nfb) * LF_TPB + threadIdx.x;
+    if (b >= p.B || idx >= nslots) return;
+    const Inst g = inst_view(p, b);
+    const int i = idx / KP, s = idx - i * KP;
+    double w = __builtin_nan("");
+    if (i < p.N && s < g.cnt[i]) {
+        const double* pose = (which ? p.pose1 : p.pose0) + (size_t)b * p.N_max * 3 + 3 * i;
+        const int j = g.mlm[idx] & (kPgsFirstBit - 1);
+        const double* lm = (which ? p.lm1 : p.lm0) + (size_t)b * p.L_max * 2 + 2 * j;
+        double e[2], rho, sw;
+        bearing_range_factor<false>(p, pose, lm, g.mb[idx], g.mr[idx], e, nullptr, nullptr);
+        const double ss = e[0] * e[0] + e[1] * e[1];
+        pgs_robust_loss(p.loss_kind, p.loss_k, ss, sqrt(ss), &rho, &w, &sw);
+    }
+    out[(size_t)b * nslots + idx] = w;
 }
 
 // compute_average_error as the pose-graph plot calls it (plotting_node.py:203-213,432-434): pose i of the message

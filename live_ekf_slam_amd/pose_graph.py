@@ -17,6 +17,17 @@ from .config import SlamConfig, default_config
 from .filters import Command, _d, _f, _i
 
 
+LOSS_NONE, LOSS_HUBER, LOSS_GEMAN_MCCLURE = 0, 1, 2      # pgs_loss_kind (slam_pgs.h)
+LOSS_KINDS = {"none": LOSS_NONE, "huber": LOSS_HUBER, "geman_mcclure": LOSS_GEMAN_MCCLURE}
+
+
+def robust_loss_host(kind, k, r):
+    """TEST HOOK (pgs_robust_loss_host): (rho, w, sqrt(w)) of the loss at residual norm r, the kernels' source compiled for the host; no GPU."""
+    rho, w, sw = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+    _lib.check(_lib.lib().pgs_robust_loss_host(int(kind), float(k), float(r), C.byref(rho), C.byref(w), C.byref(sw)))
+    return rho.value, w.value, sw.value
+
+
 class NaiveFilter:
     """NaiveFilter (filter.h:325-369): propagate the commands, ignore the measurements.  Identical for every
     instance of a batch (it never sees instance-specific data), so one copy serves the whole batch."""
@@ -338,6 +349,35 @@ class BatchedPoseGraph:
         self._need(); f = C.c_double(0); ms = C.c_double(0)
         _lib.check(_lib.lib().pgs_last_marginals_work(self.h, C.byref(f), C.byref(ms)))
         return f.value, ms.value
+
+    # -- robust loss on the landmark factors (noiseModel::Robust; slam_pgs.h) --
+    def set_robust(self, kind, k=0.0):
+        """Loss of every bearing-range factor from the next solve / marginals / factor_weights on: kind LOSS_NONE | LOSS_HUBER |
+        LOSS_GEMAN_MCCLURE (or "none" | "huber" | "geman_mcclure"), parameter k in whitened units (Huber: 1.345 is the usual choice)."""
+        self._need()
+        kind = LOSS_KINDS[kind] if isinstance(kind, str) else int(kind)
+        _lib.check(_lib.lib().pgs_set_robust(self.h, kind, float(k)))
+
+    @property
+    def robust(self):
+        """(kind, k) as set."""
+        self._need(); kind = C.c_int(0); k = C.c_double(0.0)
+        _lib.check(_lib.lib().pgs_get_robust(self.h, C.byref(kind), C.byref(k)))
+        return kind.value, k.value
+
+    def factor_weights(self, which=None):
+        """IRLS weight of every stored bearing-range factor at initial_estimate (which = 0) / result (1; default as get_graph):
+        [batch][timestep + 1][k_per_pose] in slot order (the order of connections()), NaN where a pose stores no factor; all 1.0
+        without a loss.  Which detections the solve did not believe."""
+        self._need()
+        which = int(self.solved_pose_graph) if which is None else int(which)
+        _lib.check(_lib.lib().pgs_factor_weights(self.h, which))
+        N = self.timestep + 1
+        out = np.zeros((self.batch, N, self.k_per_pose))
+        n = C.c_int32(0)
+        for b in range(self.batch):
+            _lib.check(_lib.lib().pgs_get_factor_weights(self.h, b, _d(out[b]), N * self.k_per_pose, C.byref(n)))
+        return out
 
     def error_stats(self, which=1):
         self._need(); out = np.zeros(self.batch); _lib.check(_lib.lib().pgs_error_stats(self.h, int(which), _d(out))); return out
