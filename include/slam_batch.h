@@ -500,7 +500,8 @@ int slam_innovation_instance_host(const double* x, const double* P, const int32_
  *   prediction is pending.
  * Not covered: the simulator sources (their step generates its own message inside the step kernel); slam_multi_*; the pose graph;
  *   multi-step launches (a gated step is one launch per tick); rejecting on anything but the individual NIS - there is no joint
- *   compatibility test, and a detection of an unmapped id is inserted ungated (detections without ids: slam_associate, below). */
+ *   compatibility test here (id-less detections get one in slam_associate_joint, below), and a detection of an unmapped id is inserted
+ *   ungated (detections without ids: slam_associate, below). */
 enum slam_gate_verdict {
     SLAM_GATE_NOT_UPDATE = 0,   /* insertion, capacity skip, beyond the count, or any slot of a passed-through instance */
     SLAM_GATE_ACCEPTED = 1,
@@ -588,7 +589,7 @@ int slam_gate_instance_host(const double* x, const double* P, const int32_t* ids
  *   k_stride <= 0, T < 0, outputs that overlap the inputs other than in place; NULL handle.  SLAM_ERR_UNSUPPORTED: the UKF kinds, and
  *   handles with landmark_id_is_known = 0 (those associate inside their step).  SLAM_ERR_STATE: before slam_init; slam_step_associated*
  *   and slam_associate_run also while slam_track_instance is on or a prediction is pending.
- * Not covered: joint compatibility (JCBB); reassigning conflict losers; the ln det S term of the full likelihood; the simulator sources;
+ * Not covered: joint compatibility (JCBB) - that is slam_associate_joint, below; reassigning conflict losers; the ln det S term of the full likelihood; the simulator sources;
  *   slam_multi_*; the pose graph; a fused associate-plus-gate call - chain slam_associate_dev and slam_step_gated_dev on device buffers. */
 enum slam_assoc_verdict {
     SLAM_ASSOC_NONE = 0,        /* beyond the count, or any slot of an instance that emits an empty message */
@@ -597,7 +598,8 @@ enum slam_assoc_verdict {
     SLAM_ASSOC_AMBIGUOUS = 3,   /* gate_match < best <= gate_new: dropped */
     SLAM_ASSOC_CONFLICT = 4,    /* lost its landmark to a detection with a smaller (d2, l): dropped */
     SLAM_ASSOC_NO_ROOM = 5,     /* a new landmark the map or the id range has no room for: dropped */
-    SLAM_ASSOC_INVALID = 6      /* no finite cost: dropped */
+    SLAM_ASSOC_INVALID = 6,     /* no finite cost: dropped */
+    SLAM_ASSOC_JOINT_UNPAIRED = 7   /* slam_associate_joint only: had candidates, left out by the best hypothesis: dropped */
 };
 typedef struct slam_assoc_config {
     double gate_match;   /* a detection matches its nearest landmark iff d2_best <= gate_match; > 0 */
@@ -645,6 +647,95 @@ int slam_associate_instance_host(const double* x, const double* P, const int32_t
                                  const float* meas, int count, int k_stride, const slam_noise* noise, int lm_from_pred, int f32_storage,
                                  const slam_assoc_config* cfg, double rec[16], int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* flags,
                                  double* cost, int32_t* verdict, int32_t* slot, double* det, float* meas_out, int32_t* count_out);
+
+/* ---- joint-compatibility association of detections WITHOUT ids: JCBB (csrc/joint_kernel.h) ------------------------------------------------
+ * slam_associate judges every detection alone.  When the pose is uncertain relative to the landmark spacing (a stretch without detections,
+ * then a cluster of landmarks) every detection sits inside the individual gate of several landmarks, and nearest neighbour drops them as
+ * AMBIGUOUS or CONFLICT or matches a consistently shifted set: it cannot see that the errors of all detections are tied together through
+ * the pose.  slam_associate_joint judges the hypothesis as a whole (Neira and Tardos, joint compatibility branch and bound): among the
+ * hypotheses whose STACKED innovation passes a chi-square test with 2 m degrees of freedom, it takes the one that pairs the most
+ * detections.  Same pattern and same rules as slam_associate: a side kernel labels the message from the PRE-step state, the unmodified
+ * known-id step consumes it, slam_innovation, slam_gate and the map calls chain behind it unchanged; message in and out, in place and
+ * overlap rules, cmd_each, the empty message of frozen and TOO_LONG instances, NEW ranks and ids, NO_ROOM: all as there.
+ * Costs: d2[l][j], nu and the per-landmark S of slam_associate, bit for bit.
+ * Candidates of detection l: the slots with finite d2 <= gate_match, ascending by (d2, j); the first SLAM_JOINT_MAX_CAND are kept.  A
+ *   detection without a candidate is INVALID (M > 0 and no finite cost), NEW (M == 0 or best > gate_new) or AMBIGUOUS, as there.
+ * Hypotheses: every detection with candidates is paired with one of them or left unpaired; a landmark is used at most once; at most
+ *   SLAM_JOINT_MAX_PAIR = SLAM_INNOV_MAX_LM pairings, so a jointly labelled message is never TOO_LONG for slam_innovation / slam_gate
+ *   because of its matches.
+ * Joint distance of m pairings: nu stacked; S (2 m x 2 m) with the cost phase's S_j on the diagonal and H_a P_pred[block a, block b] H_b^T
+ *   off it, from the predicted state before any update (P as the handle stores it); a Cholesky factor grown by two rows per pairing (pivot
+ *   test: > 0 and finite; a failed pivot makes the pairing incompatible, flag SLAM_JOINT_S_SINGULAR); d2_m = d2_{m-1} + (y^2 + y^2) with
+ *   y = L^-1 nu, so the distance never decreases along a branch.  Compatible iff d2_m <= gate_joint[m - 1].  The evaluation order is fixed in
+ *   csrc/joint_kernel.h.
+ * Search: depth first over the detections with candidates in message order, candidates in ascending (d2, j), then the unpaired branch.
+ *   Best: most pairings, then smallest joint distance, then first found.  A branch is cut when pairs + min(remaining, 16 - pairs) is
+ *   below the best's pairings, or equals them while its distance is >= the best's.  A node is one attempted pairing; after max_nodes
+ *   nodes the search stops with the best so far - the branch at hand, its remaining detections unpaired, competes - and the flag
+ *   SLAM_JOINT_BUDGET.  The first dive is sequential-compatibility nearest neighbour.
+ * Verdicts: slam_assoc_verdict, and SLAM_ASSOC_JOINT_UNPAIRED: the detection had candidates, the best hypothesis leaves it out, it is
+ *   dropped and never inserted as new.
+ * Outputs as slam_associate (slot: the paired slot when MATCHED, else the individual best; det: d2 and nu of the paired slot when MATCHED),
+ *   then d2_joint [batch] (the best hypothesis' distance, 0 without pairings), nodes [batch], ncand [batch][SLAM_INNOV_MAX_DET] candidates
+ *   kept; n_drop = ambiguous + unpaired + no room + invalid; flags: SLAM_INNOVATION_INSTANCE_FROZEN, SLAM_INNOVATION_TOO_LONG and
+ *   slam_joint_flags.
+ * Record, 16 doubles: 0 instances evaluated, 1 FROZEN, 2 TOO_LONG, 3 detections in, 4 matched, 5 new, 6 ambiguous, 7 sum of d2_joint, 8 max
+ *   of d2_joint, 9 unpaired, 10 no room, 11 invalid, 12 sum of nodes, 13 instances with SLAM_JOINT_BUDGET, 14 instances with
+ *   SLAM_JOINT_S_SINGULAR, 15 matched detections whose slot is not their individual best; summed in the fixed order of the innovation record.
+ * Errors: as slam_associate (SLAM_ERR_ARG is checked first, before the handle is looked at; SLAM_ERR_UNSUPPORTED for the UKF kinds and for
+ *   landmark_id_is_known = 0; SLAM_ERR_STATE before slam_init, and for the steps and the run while slam_track_instance is on or a
+ *   prediction is pending); also SLAM_ERR_ARG for a gate_joint entry that is NaN, <= 0 or below its predecessor (+inf is allowed) and for
+ *   max_nodes outside 1 .. 65536.
+ * Not covered: the UKF kinds; the simulator sources; slam_multi_*; the pose graph; joint association inside slam_manage_run /
+ *   slam_manage_merge_run; the ln det S term of the full likelihood; more than 16 pairings per message. */
+#define SLAM_JOINT_MAX_CAND 4    /* candidates kept per detection */
+#define SLAM_JOINT_MAX_PAIR 16   /* pairings of one hypothesis */
+enum slam_joint_flags {
+    SLAM_JOINT_BUDGET = 16,       /* the search stopped at max_nodes */
+    SLAM_JOINT_S_SINGULAR = 32,   /* a pivot of the joint Cholesky factor failed on some node: that pairing was incompatible */
+    SLAM_JOINT_LM_TABLE = 64      /* more than 64 distinct candidate landmarks: the candidates beyond them were never paired */
+};
+typedef struct slam_joint_config {
+    double gate_match;       /* the individual match gate, as slam_assoc_config */
+    double gate_new;         /* the new-landmark gate, as slam_assoc_config */
+    double gate_joint[16];   /* the joint gates, entry m - 1 for m pairings: > 0, non-decreasing, may be +inf */
+    int32_t max_nodes;       /* the node budget of the search, 1 .. 65536 */
+} slam_joint_config;
+/* gate_match and gate_new of slam_assoc_config_default; gate_joint[m - 1] = the 0.99 quantile of chi-square with 2 m degrees of freedom
+ * (entry 0 = gate_match); max_nodes = 2048 */
+int slam_joint_config_default(slam_joint_config* cfg);
+/* As slam_associate: CHANGES NOTHING in the handle.  d2_joint, nodes [batch] and ncand [batch][SLAM_INNOV_MAX_DET] may be NULL. */
+int slam_associate_joint(slam_handle* h, const slam_joint_config* cfg, const float* cmds, int cmd_each, const float* meas,
+                         const int32_t* meas_count, int k_stride, double rec[16], int32_t* n_match, int32_t* n_new, int32_t* n_drop,
+                         int32_t* flags, int32_t* verdict, int32_t* slot, double* det, float* meas_out, int32_t* count_out, double* d2_joint,
+                         int32_t* nodes, int32_t* ncand);
+/* As slam_associate_dev: d_meas, d_count, (cmd_each != 0) cmds, d_meas_out and d_count_out are DEVICE pointers. */
+int slam_associate_joint_dev(slam_handle* h, const slam_joint_config* cfg, const float* cmds, int cmd_each, const float* d_meas,
+                             const int32_t* d_count, int k_stride, double rec[16], int32_t* n_match, int32_t* n_new, int32_t* n_drop,
+                             int32_t* flags, int32_t* verdict, int32_t* slot, double* det, float* d_meas_out, int32_t* d_count_out,
+                             double* d2_joint, int32_t* nodes, int32_t* ncand);
+/* One jointly associated timestep, as slam_step_associated*: with rec and n_drop NULL the call does not synchronise. */
+int slam_step_associated_joint(slam_handle* h, const slam_joint_config* cfg, const float* cmds, int cmd_each, const float* meas,
+                               const int32_t* meas_count, int k_stride, double rec[16], int32_t* n_drop);
+int slam_step_associated_joint_dev(slam_handle* h, const slam_joint_config* cfg, const float* cmds, int cmd_each, const float* d_meas,
+                                   const int32_t* d_count, int k_stride, double rec[16], int32_t* n_drop);
+/* T host-fed jointly associated ticks in the layout of slam_associate_run; the state advances bit for bit as T calls of
+ * slam_step_associated_joint would leave it.  recs [T][16], n_match / n_new / n_drop / flags / nodes [T][batch], d2_joint [T][batch]; any may
+ * be NULL.  Chunking changes no bit. */
+int slam_associate_joint_run(slam_handle* h, const slam_joint_config* cfg, const float* cmds, int cmd_each, const float* meas,
+                             const int32_t* meas_count, int k_stride, int T, double* recs, int32_t* n_match, int32_t* n_new, int32_t* n_drop,
+                             int32_t* flags, double* d2_joint, int32_t* nodes);
+/* As slam_last_associate_work, for the last slam_associate_joint, slam_associate_joint_dev or slam_associate_joint_run: the association's
+ * model plus, per node, the 2 x 2 landmark - landmark blocks of P read on demand (one per pairing already on the branch: 4 elements, one
+ * 128-byte line each).  joint_ms: the joint launches alone, which needs slam_nav_set_timing(h, 1), else -1. */
+int slam_last_joint_work(slam_handle* h, double* bytes, double* joint_ms, double* total_ms);
+/* TEST HOOK, not part of the filter interface: joint_instance() compiled for the HOST.  Arguments and outputs as
+ * slam_associate_instance_host, then d2_joint, nodes, ncand [SLAM_INNOV_MAX_DET]; any output may be NULL. */
+int slam_associate_joint_instance_host(const double* x, const double* P, const int32_t* ids, int M, int L_max, int32_t status, const float cmd[2],
+                                       const float* meas, int count, int k_stride, const slam_noise* noise, int lm_from_pred, int f32_storage,
+                                       const slam_joint_config* cfg, double rec[16], int32_t* n_match, int32_t* n_new, int32_t* n_drop,
+                                       int32_t* flags, double* cost, int32_t* verdict, int32_t* slot, double* det, float* meas_out,
+                                       int32_t* count_out, double* d2_joint, int32_t* nodes, int32_t* ncand);
 
 /* ---- map management: landmarks leave the map again (csrc/map_kernel.h) ------------------------------------------------------------------
  * With slam_associate every detection farther than gate_new from the map becomes a landmark, and without the calls below nothing ever

@@ -197,6 +197,17 @@ struct AssociatedStep { double rec[16]; std::vector<int32_t> n_drop; };
         AssociatedStep v; v.n_drop.resize(batch_);                                                                                       \
         check(slam_step_associated(h_, cfg, c.data(), each ? 1 : 0, meas, meas_count, k_stride, v.rec, v.n_drop.data()));                \
         return v;                                                                                                                        \
+    }                                                                                                                                    \
+    /* the same with JOINT compatibility (slam_step_associated_joint): the hypothesis that pairs the most detections among those whose */ \
+    /* stacked innovation passes the chi-square test; rec: the joint record (slam_associate_joint in slam_batch.h); cfg NULL: defaults  */ \
+    AssociatedStep stepAssociatedJoint(const std::vector<Command>& cmds, const float* meas, const int32_t* meas_count, int k_stride,     \
+                                       const slam_joint_config* cfg = nullptr) {                                                         \
+        need();                                                                                                                          \
+        const bool each = cmds.size() != 1;                                                                                              \
+        const std::vector<float> c = packCommands(cmds, each ? batch_ : 1);                                                              \
+        AssociatedStep v; v.n_drop.resize(batch_);                                                                                       \
+        check(slam_step_associated_joint(h_, cfg, c.data(), each ? 1 : 0, meas, meas_count, k_stride, v.rec, v.n_drop.data()));          \
+        return v;                                                                                                                        \
     }
 
 class Filter {  // filter.h:54-77

@@ -13,6 +13,8 @@ from .filters import GateResult, gate_instance_host  # noqa: F401
 from .config import AssocConfig, default_assoc_config  # noqa: F401
 from .config import ASSOC_NONE, ASSOC_MATCHED, ASSOC_NEW, ASSOC_AMBIGUOUS, ASSOC_CONFLICT, ASSOC_NO_ROOM, ASSOC_INVALID  # noqa: F401
 from .filters import AssocResult, associate_instance_host  # noqa: F401
+from .config import JointConfig, default_joint_config, ASSOC_JOINT_UNPAIRED, JOINT_BUDGET, JOINT_S_SINGULAR, JOINT_LM_TABLE  # noqa: F401
+from .filters import JointResult, associate_joint_instance_host  # noqa: F401
 from .config import MapConfig, default_map_config  # noqa: F401
 from .filters import MapResult, map_instance_host  # noqa: F401
 from .config import MergeConfig, default_merge_config  # noqa: F401

@@ -5,7 +5,7 @@ There is no CPU fallback: if the library is missing or a HIP call fails, an exce
 import ctypes as C
 import os
 
-from .config import SlamConfig, NavConfig, MonitorConfig, InnovationConfig, GateConfig, AssocConfig, MapConfig, MergeConfig, Noise
+from .config import SlamConfig, NavConfig, MonitorConfig, InnovationConfig, GateConfig, AssocConfig, JointConfig, MapConfig, MergeConfig, Noise
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # SLAM_HIP_LIB: another build of the same library, for A/B tuning sessions (tools/gpu_ab.sh); the product path is the
@@ -99,6 +99,18 @@ SIGNATURES = {
     "slam_last_associate_work": (C.c_int, [_H, _dp, _dp, _dp]),
     "slam_associate_instance_host": (C.c_int, [_dp, _dp, _ip, C.c_int, C.c_int, C.c_int32, _fp, _fp, C.c_int, C.c_int, C.POINTER(Noise), C.c_int,
                                                C.c_int, C.POINTER(AssocConfig), _dp, _ip, _ip, _ip, _ip, _dp, _ip, _ip, _dp, _fp, _ip]),
+    "slam_joint_config_default": (C.c_int, [C.POINTER(JointConfig)]),
+    "slam_associate_joint": (C.c_int, [_H, C.POINTER(JointConfig), _fp, C.c_int, _fp, _ip, C.c_int, _dp, _ip, _ip, _ip, _ip, _ip, _ip, _dp, _fp, _ip,
+                                       _dp, _ip, _ip]),
+    "slam_associate_joint_dev": (C.c_int, [_H, C.POINTER(JointConfig), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, _dp, _ip, _ip, _ip, _ip,
+                                           _ip, _ip, _dp, C.c_void_p, C.c_void_p, _dp, _ip, _ip]),
+    "slam_step_associated_joint": (C.c_int, [_H, C.POINTER(JointConfig), _fp, C.c_int, _fp, _ip, C.c_int, _dp, _ip]),
+    "slam_step_associated_joint_dev": (C.c_int, [_H, C.POINTER(JointConfig), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, _dp, _ip]),
+    "slam_associate_joint_run": (C.c_int, [_H, C.POINTER(JointConfig), _fp, C.c_int, _fp, _ip, C.c_int, C.c_int, _dp, _ip, _ip, _ip, _ip, _dp, _ip]),
+    "slam_last_joint_work": (C.c_int, [_H, _dp, _dp, _dp]),
+    "slam_associate_joint_instance_host": (C.c_int, [_dp, _dp, _ip, C.c_int, C.c_int, C.c_int32, _fp, _fp, C.c_int, C.c_int, C.POINTER(Noise), C.c_int,
+                                                     C.c_int, C.POINTER(JointConfig), _dp, _ip, _ip, _ip, _ip, _dp, _ip, _ip, _dp, _fp, _ip, _dp, _ip,
+                                                     _ip]),
     "slam_map_config_default": (C.c_int, [C.POINTER(MapConfig)]),
     "slam_remove_landmarks": (C.c_int, [_H, _ip, _ip, _dp]),
     "slam_remove_landmarks_dev": (C.c_int, [_H, C.c_void_p, _ip, _dp]),

@@ -144,6 +144,30 @@ def default_assoc_config() -> AssocConfig:
     return AssocConfig(-2.0 * math.log(0.01), -2.0 * math.log(1e-6))
 
 
+class JointConfig(C.Structure):
+    """ctypes mirror of `slam_joint_config` (include/slam_batch.h): the individual gates of AssocConfig, the joint gates by pairing count
+    and the node budget of the search."""
+    _fields_ = [("gate_match", C.c_double), ("gate_new", C.c_double), ("gate_joint", C.c_double * 16), ("max_nodes", C.c_int32)]
+
+
+ASSOC_JOINT_UNPAIRED = 7                                    # slam_assoc_verdict, slam_associate_joint only
+JOINT_BUDGET, JOINT_S_SINGULAR, JOINT_LM_TABLE = 16, 32, 64   # slam_joint_flags
+JOINT_MAX_CAND, JOINT_MAX_PAIR = 4, 16                      # SLAM_JOINT_MAX_CAND, SLAM_JOINT_MAX_PAIR
+# the 0.99 quantiles of chi-square with 2, 4, ..., 32 degrees of freedom (mpmath, 50 digits, rounded to nearest)
+JOINT_GATES_99 = (9.210340371976184, 13.276704135987625, 16.81189382977093, 20.090235029663233, 23.20925115895436, 26.21696730553585,
+                  29.141237740672796, 31.99992690881518, 34.80530573470507, 37.56623478662505, 40.289360437593864, 42.97982013935164,
+                  45.64168266628315, 48.2782357703155, 50.89218131151709, 53.485771836235365)
+
+
+def default_joint_config() -> JointConfig:
+    """The gates of default_assoc_config, gate_joint[m - 1] = the 0.99 quantile of chi-square with 2 m degrees of freedom (entry 0 is
+    gate_match), max_nodes = 2048."""
+    a = default_assoc_config()
+    c = JointConfig(a.gate_match, a.gate_new, (C.c_double * 16)(*JOINT_GATES_99), 2048)
+    c.gate_joint[0] = a.gate_match
+    return c
+
+
 class MapConfig(C.Structure):
     """ctypes mirror of `slam_map_config` (include/slam_batch.h): the shrunk view a landmark is expected in, the prune rule on its track
     counters and the stride of the prunes of manage_run."""

@@ -89,39 +89,55 @@ SLAM_HD double assoc_second(double a0, double a1, double b0, double b1) {
     return hi < lo ? hi : lo;
 }
 
-// One instance.  ws.meas holds the message's first min(k, kInnovMaxDet) triplets already; k = count_in.  ids: lm_IDs[0 .. M); M is clamped
-// to [0, L_max].  load_x(i) / load_P(r, c) as innovation_instance.  cost: [k][M] or NULL (the host hook's full matrix).  verdict, slot:
-// [kInnovMaxDet], det: [kInnovMaxDet][kAssocDetLen], or NULL.  meas_out: the output row ([k_stride][3], may be the input row) or NULL.
-// Every lane of the policy returns the same result; the lanes share the writes.
-template <class W, class LX, class LP>
-SLAM_HD AssocResult associate_instance(const W& w, AssocWork& ws, LX load_x, LP load_P, const int32_t* ids, int M, int L_max, int32_t status,
-                                       float fwd, float ang, int k, const InnovNoise& nz, double gate_match, double gate_new, double* cost,
-                                       int32_t* verdict, int32_t* slot, double* det, float* meas_out) {
-    const double nan = __builtin_nan(""), inf = __builtin_inf();
-    AssocResult out;
-    out.n_match = out.n_new = out.n_drop = out.flags = 0;
-    out.n_in = out.n_amb = out.n_conf = out.n_room = out.n_inv = out.count_out = 0;
-    out.sum_d2 = out.max_d2 = 0.0;
-    if (status & kInnovStatusFrozen) out.flags = kInnovFrozen;
-    else if (k > kInnovMaxDet) out.flags = kInnovTooLong;
-    if (out.flags) {   // an empty message
-        for (int l = w.lane(); l < kInnovMaxDet; l += w.width()) {
-            if (verdict) verdict[l] = kAssocNone;
-            if (slot) slot[l] = -1;
-            if (det)
-                for (int i = 0; i < kAssocDetLen; ++i) det[l * kAssocDetLen + i] = nan;
-        }
-        if (meas_out)
-            for (int i = w.lane(); i < 3 * k; i += w.width()) meas_out[i] = 0.0f;
-        return out;
+// What the cost phase forms once per landmark slot jj, from the pre-step state: the offset and range, H, S of the predicted 5 x 5 block
+// {0, 1, 2, ii, ii + 1} (ii = 3 + 2 jj), Si = inv2x2_lu(S) with `ok` (the inverse succeeded and S is finite) and the predicted bearing.
+// The joint association (joint_kernel.h) calls it again for its candidate landmarks: the same function on the same operands, the same bits.
+struct AssocLandmark { EkfRange rg; EkfH h; EkfS Sm; double Si[4]; bool ok; float angf; };
+template <class LX, class LP>
+SLAM_HD AssocLandmark assoc_landmark(LX load_x, LP load_P, const EkfMotion& m, const InnovNoise& nz, int jj) {
+    AssocLandmark o;
+    const int ii = 3 + 2 * jj;
+    const int idx[5] = {0, 1, 2, ii, ii + 1};
+    o.rg = ekf_range(load_x(ii), load_x(ii + 1), m.xp0, m.xp1);   // ekf.cpp:115 (no update precedes: x_pred[ii] = x_t[ii])
+    o.h = ekf_jacobian(o.rg.dx, o.rg.dy, o.rg.dd, o.rg.d2);
+    const double q[2][2] = {{m.q00, m.q01}, {m.q10, m.q11}};
+    // P_pred on the block (ekf.cpp:61; block rows 3, 4 are rows >= 3 of the state) and H P, a column at a time: a column of the
+    // prediction takes its own column of P and column 2
+    double a2[5];
+#pragma unroll
+    for (int r = 0; r < 5; ++r) a2[r] = load_P(idx[r], 2);
+    EkfVec2 hp[5];
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+        double a[5], pc[5];
+#pragma unroll
+        for (int r = 0; r < 5; ++r) a[r] = c == 2 ? a2[r] : load_P(idx[r], idx[c]);
+#pragma unroll
+        for (int r = 0; r < 5; ++r) pc[r] = ekf_predicted(a[r], r, c, a[2], a2[r], a2[2], m.fa, m.fb, (r < 2 && c < 2) ? q[r][c] : 0.0, nz.V11);
+        hp[c] = ekf_hp_col(o.h, pc[0], pc[1], pc[2], pc[3], pc[4]);
     }
-    M = M < 0 ? 0 : (M > L_max ? L_max : M);
+    o.Sm = ekf_S(o.h, hp[0], hp[1], hp[2], hp[3], hp[4], nz.W00, nz.W11);   // ekf.cpp:133
+    o.ok = inv2x2_lu(o.Sm.s, o.Si) && innov_finite(o.Sm.s[0]) && innov_finite(o.Sm.s[1]) && innov_finite(o.Sm.s[2]) && innov_finite(o.Sm.s[3]);
+    o.angf = ekf_predicted_bearing(o.rg.dx, o.rg.dy, m.xp2);
+    return o;
+}
+
+// what the cost phase hands every pair (l, j) to, in wave-uniform control flow: nothing for slam_associate, the candidate lists of the
+// joint association (joint_kernel.h)
+struct AssocNoSink {
+    template <class W> SLAM_HD void pair(const W&, int, int, bool, double, const EkfVec2&) const {}
+};
+
+// The cost phase: lanes over landmarks, width() of them at a time; per detection a butterfly arg-min with the (value, j) tie-break into
+// ws.best / second / slot / nu0 / nu1 (initialised here).  Returns the largest id of the map (INT_MIN for M == 0) in every lane.
+template <class W, class LX, class LP, class SINK>
+SLAM_HD int assoc_cost_phase(const W& w, AssocWork& ws, LX load_x, LP load_P, const int32_t* ids, int M, float fwd, float ang, int k,
+                             const InnovNoise& nz, double* cost, SINK& sink) {
+    const double nan = __builtin_nan(""), inf = __builtin_inf();
     for (int l = w.lane(); l < kInnovMaxDet; l += w.width()) {
         ws.best[l] = inf; ws.second[l] = inf; ws.nu0[l] = nan; ws.nu1[l] = nan; ws.slot[l] = -1;
     }
     w.sync();
-
-    // ---- costs: lanes over landmarks, width() of them at a time; per detection a butterfly arg-min with the (value, j) tie-break ----
     const double x0 = load_x(0), x1 = load_x(1), x2 = load_x(2);
     const EkfMotion m = ekf_motion(x0, x1, x2, fwd, ang, nz.v_d, nz.v_th, nz.V00);   // ekf.cpp:41-59
     int idmax = -2147483647 - 1;
@@ -129,33 +145,12 @@ SLAM_HD AssocResult associate_instance(const W& w, AssocWork& ws, LX load_x, LP 
         const int j = j0 + w.lane();
         const bool mine = j < M;
         const int jj = mine ? j : 0;              // (a lane past the map computes on landmark 0 and discards: no index leaves the state)
-        const int ii = 3 + 2 * jj;
         if (mine && ids[j] > idmax) idmax = ids[j];
-        const int idx[5] = {0, 1, 2, ii, ii + 1};
-        const EkfRange rg = ekf_range(load_x(ii), load_x(ii + 1), m.xp0, m.xp1);   // ekf.cpp:115 (no update precedes: x_pred[ii] = x_t[ii])
-        const EkfH h = ekf_jacobian(rg.dx, rg.dy, rg.dd, rg.d2);
-        const double q[2][2] = {{m.q00, m.q01}, {m.q10, m.q11}};
-        // P_pred on the block (ekf.cpp:61; block rows 3, 4 are rows >= 3 of the state) and H P, a column at a time: a column of the
-        // prediction takes its own column of P and column 2
-        double a2[5];
-#pragma unroll
-        for (int r = 0; r < 5; ++r) a2[r] = load_P(idx[r], 2);
-        EkfVec2 hp[5];
-#pragma unroll
-        for (int c = 0; c < 5; ++c) {
-            double a[5], pc[5];
-#pragma unroll
-            for (int r = 0; r < 5; ++r) a[r] = c == 2 ? a2[r] : load_P(idx[r], idx[c]);
-#pragma unroll
-            for (int r = 0; r < 5; ++r) pc[r] = ekf_predicted(a[r], r, c, a[2], a2[r], a2[2], m.fa, m.fb, (r < 2 && c < 2) ? q[r][c] : 0.0, nz.V11);
-            hp[c] = ekf_hp_col(h, pc[0], pc[1], pc[2], pc[3], pc[4]);
-        }
-        const EkfS Sm = ekf_S(h, hp[0], hp[1], hp[2], hp[3], hp[4], nz.W00, nz.W11);   // ekf.cpp:133
-        double Si[4];
-        const bool ok = inv2x2_lu(Sm.s, Si) && innov_finite(Sm.s[0]) && innov_finite(Sm.s[1]) && innov_finite(Sm.s[2]) && innov_finite(Sm.s[3]);
-        const float angf = ekf_predicted_bearing(rg.dx, rg.dy, m.xp2);
+        const AssocLandmark lm = assoc_landmark(load_x, load_P, m, nz, jj);
+        const double (&Si)[4] = lm.Si;
+        const bool ok = lm.ok;
         for (int l = 0; l < k; ++l) {
-            const EkfVec2 nu = ekf_innovation_from(ws.meas[3 * l + 1], ws.meas[3 * l + 2], rg.dist, angf, nz.w_r, nz.w_b);   // ekf.cpp:129-131
+            const EkfVec2 nu = ekf_innovation_from(ws.meas[3 * l + 1], ws.meas[3 * l + 2], lm.rg.dist, lm.angf, nz.w_r, nz.w_b);   // ekf.cpp:129-131
             double d2 = nu.x * (Si[0] * nu.x + Si[1] * nu.y) + nu.y * (Si[2] * nu.x + Si[3] * nu.y);
             if (!ok || !innov_finite(nu.x) || !innov_finite(nu.y)) d2 = nan;
             if (cost && mine) cost[(size_t)l * M + j] = d2;
@@ -177,6 +172,7 @@ SLAM_HD AssocResult associate_instance(const W& w, AssocWork& ws, LX load_x, LP 
                 if (better) { ws.best[l] = b0; ws.slot[l] = bj; }
             }
             if (better && fin && j == bj) { ws.nu0[l] = nu.x; ws.nu1[l] = nu.y; }
+            sink.pair(w, l, j, fin, d2, nu);
         }
         w.sync();
     }
@@ -184,6 +180,66 @@ SLAM_HD AssocResult associate_instance(const W& w, AssocWork& ws, LX load_x, LP 
         const int o = w.xor_get(idmax, s);
         idmax = o > idmax ? o : idmax;
     }
+    return idmax;
+}
+
+// An instance that cannot be associated (step 6): every verdict 0, every slot -1, det NaN, the first k triplets of the row zeroed
+template <class W>
+SLAM_HD void assoc_empty_message(const W& w, int k, int32_t* verdict, int32_t* slot, double* det, float* meas_out) {
+    const double nan = __builtin_nan("");
+    for (int l = w.lane(); l < kInnovMaxDet; l += w.width()) {
+        if (verdict) verdict[l] = kAssocNone;
+        if (slot) slot[l] = -1;
+        if (det)
+            for (int i = 0; i < kAssocDetLen; ++i) det[l * kAssocDetLen + i] = nan;
+    }
+    if (meas_out)
+        for (int i = w.lane(); i < 3 * k; i += w.width()) meas_out[i] = 0.0f;
+}
+
+// The labelled message (step 5) from ws.verdict / ws.id / ws.meas, in message order; returns count_out
+template <class W>
+SLAM_HD int assoc_emit_message(const W& w, const AssocWork& ws, int k, float* meas_out) {
+    int count_out = 0;
+    auto kept_at = [&](int i) { return ws.verdict[i] == kAssocMatched || ws.verdict[i] == kAssocNew; };
+    for (int l = w.lane(); l < kInnovMaxDet; l += w.width()) {
+        const int pos = w.below(l, kept_at);
+        const int kept = w.total(kept_at);
+        count_out = kept;
+        if (!meas_out || l >= k) continue;        // every output index below is < 3 k <= 3 k_stride
+        if (kept_at(l)) {
+            meas_out[3 * pos] = (float)ws.id[l]; meas_out[3 * pos + 1] = ws.meas[3 * l + 1]; meas_out[3 * pos + 2] = ws.meas[3 * l + 2];
+        } else {                                  // the dropped detections zero the tail kept .. k - 1, one triplet each
+            const int t = kept + (l - pos);       // l - pos = dropped detections below l
+            meas_out[3 * t] = 0.0f; meas_out[3 * t + 1] = 0.0f; meas_out[3 * t + 2] = 0.0f;
+        }
+    }
+    return count_out;
+}
+
+// One instance.  ws.meas holds the message's first min(k, kInnovMaxDet) triplets already; k = count_in.  ids: lm_IDs[0 .. M); M is clamped
+// to [0, L_max].  load_x(i) / load_P(r, c) as innovation_instance.  cost: [k][M] or NULL (the host hook's full matrix).  verdict, slot:
+// [kInnovMaxDet], det: [kInnovMaxDet][kAssocDetLen], or NULL.  meas_out: the output row ([k_stride][3], may be the input row) or NULL.
+// Every lane of the policy returns the same result; the lanes share the writes.
+template <class W, class LX, class LP>
+SLAM_HD AssocResult associate_instance(const W& w, AssocWork& ws, LX load_x, LP load_P, const int32_t* ids, int M, int L_max, int32_t status,
+                                       float fwd, float ang, int k, const InnovNoise& nz, double gate_match, double gate_new, double* cost,
+                                       int32_t* verdict, int32_t* slot, double* det, float* meas_out) {
+    const double nan = __builtin_nan(""), inf = __builtin_inf();
+    AssocResult out;
+    out.n_match = out.n_new = out.n_drop = out.flags = 0;
+    out.n_in = out.n_amb = out.n_conf = out.n_room = out.n_inv = out.count_out = 0;
+    out.sum_d2 = out.max_d2 = 0.0;
+    if (status & kInnovStatusFrozen) out.flags = kInnovFrozen;
+    else if (k > kInnovMaxDet) out.flags = kInnovTooLong;
+    if (out.flags) {   // an empty message
+        assoc_empty_message(w, k, verdict, slot, det, meas_out);
+        return out;
+    }
+    M = M < 0 ? 0 : (M > L_max ? L_max : M);
+    // ---- costs (assoc_cost_phase) ----
+    AssocNoSink sink;
+    const int idmax = assoc_cost_phase(w, ws, load_x, load_P, ids, M, fwd, ang, k, nz, cost, sink);
     const long long base = M == 0 ? 0ll : 1ll + (long long)idmax;
     const int room = L_max - M;
 
@@ -230,19 +286,7 @@ SLAM_HD AssocResult associate_instance(const W& w, AssocWork& ws, LX load_x, LP 
     w.sync();
 
     // ---- the labelled message, in message order ----
-    auto kept_at = [&](int i) { return ws.verdict[i] == kAssocMatched || ws.verdict[i] == kAssocNew; };
-    for (int l = w.lane(); l < kInnovMaxDet; l += w.width()) {
-        const int pos = w.below(l, kept_at);
-        const int kept = w.total(kept_at);
-        out.count_out = kept;
-        if (!meas_out || l >= k) continue;        // every output index below is < 3 k <= 3 k_stride
-        if (kept_at(l)) {
-            meas_out[3 * pos] = (float)ws.id[l]; meas_out[3 * pos + 1] = ws.meas[3 * l + 1]; meas_out[3 * pos + 2] = ws.meas[3 * l + 2];
-        } else {                                  // the dropped detections zero the tail kept .. k - 1, one triplet each
-            const int t = kept + (l - pos);       // l - pos = dropped detections below l
-            meas_out[3 * t] = 0.0f; meas_out[3 * t + 1] = 0.0f; meas_out[3 * t + 2] = 0.0f;
-        }
-    }
+    out.count_out = assoc_emit_message(w, ws, k, meas_out);
 
     // ---- counts and sums, ascending l (every lane walks all of them: LDS broadcasts) ----
     out.n_in = k;

@@ -25,7 +25,7 @@ int assoc_config(const slam_assoc_config* cfg, slam_assoc_config* out) {
     return SLAM_OK;
 }
 
-static bool assoc_overlap(const void* a, size_t na, const void* b, size_t nb) {
+bool assoc_overlap(const void* a, size_t na, const void* b, size_t nb) {
     const char* const pa = (const char*)a; const char* const pb = (const char*)b;
     return pa < pb + nb && pb < pa + na;
 }

@@ -11,6 +11,8 @@ int assoc_config(const slam_assoc_config* cfg, slam_assoc_config* out);
 // the arguments every entry point of one message shares, checked before the handle is looked at
 int assoc_args(const slam_assoc_config* cfg, const float* cmds, const float* meas, const int32_t* count, int k_stride, const float* meas_out,
                const int32_t* count_out, bool need_out, slam_assoc_config* c);
+// the byte ranges [a, a + na) and [b, b + nb) meet
+bool assoc_overlap(const void* a, size_t na, const void* b, size_t nb);
 int assoc_supported(const slam_handle* h);
 // the handle, once the arguments are in order; the queued timesteps run first
 int assoc_enter(slam_handle* h);

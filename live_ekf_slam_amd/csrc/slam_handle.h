@@ -1,6 +1,6 @@
 // slam_handle.h — the handle of the filter ABI (include/slam_batch.h) and the host helpers that more than one of its translation units
 // uses (slam_capi.cpp: create / configure / init; capi_step.cpp: the steps and their queue; capi_state.cpp: reading the state back;
-// capi_consistency.cpp, capi_nav.cpp, capi_monitor.cpp, capi_innovation.cpp, capi_gate.cpp, capi_assoc.cpp, capi_map.cpp, capi_merge.cpp: one feature each).  Not installed, not part
+// capi_consistency.cpp, capi_nav.cpp, capi_monitor.cpp, capi_innovation.cpp, capi_gate.cpp, capi_assoc.cpp, capi_joint.cpp, capi_map.cpp, capi_merge.cpp: one feature each).  Not installed, not part
 // of the ABI: the standing of capi_internal.h.
 #pragma once
 #include "../../include/slam_batch.h"
@@ -172,6 +172,13 @@ struct slam_handle {
         double bytes = -1.0, lines = -1.0;
         slam_capi::RunTimes times;
     } assoc;
+    // slam_associate_joint_*: as `assoc`, with [7][ticks][B] n_match, n_new, n_drop, flags, landmarks compared with, nodes and on-demand
+    // blocks, [ticks][B] d2_joint and [B][64] candidate counts
+    struct Joint {
+        DevBuf<float> dmeas; DevBuf<int32_t> dcount, dint, dverdict, dslot, dncand; DevBuf<double> ddet, dd2; DevBuf<unsigned long long> dwork;
+        double bytes = -1.0, lines = -1.0;
+        slam_capi::RunTimes times;
+    } joint;
     // slam_remove_landmarks / slam_map_*: the track counters seen and expected ([B][L_max] each, allocated on first use and outside the
     // checkpoint format; tracked: they exist), the staged mask of a host-pointer removal ([B][L_max]), [2][ticks][B] n_removed and the M
     // before, the record, the three sums of the traffic model (work_set: a removal has filled them) and the device times of the last

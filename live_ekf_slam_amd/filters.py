@@ -19,6 +19,7 @@ from .config import (InnovationConfig, default_innovation_config, INNOVATION_SHA
                      INNOV_MAX_DET)
 from .config import GateConfig, default_gate_config
 from .config import AssocConfig, default_assoc_config
+from .config import JointConfig, default_joint_config
 from .config import MapConfig, default_map_config, MAP_CONFIG_FIELDS
 from .config import MergeConfig, default_merge_config, MERGE_CONFIG_FIELDS
 
@@ -85,6 +86,34 @@ class AssocResult:
 
     def __init__(self, recs, n_match=None, n_new=None, n_drop=None, flags=None):
         self.recs, self.n_match, self.n_new, self.n_drop, self.flags = recs, n_match, n_new, n_drop, flags
+
+
+class JointResult:
+    """What associate_joint_run returns: `recs`, the (T, 16) records of the ticks (columns: the REC_* constants; slam_associate_joint in
+    include/slam_batch.h defines them), and - with series=True, else None - `n_match`, `n_new`, `n_drop`, `flags`, `nodes` and `d2_joint`,
+    (T, batch) each."""
+
+    (REC_N_EVAL, REC_N_FROZEN, REC_N_TOO_LONG, REC_N_DET, REC_N_MATCHED, REC_N_NEW, REC_N_AMBIGUOUS, REC_SUM_D2, REC_MAX_D2, REC_N_UNPAIRED,
+     REC_N_NO_ROOM, REC_N_INVALID, REC_SUM_NODES, REC_N_BUDGET, REC_N_S_SINGULAR, REC_N_DIFFER) = range(16)
+
+    def __init__(self, recs, n_match=None, n_new=None, n_drop=None, flags=None, nodes=None, d2_joint=None):
+        self.recs, self.n_match, self.n_new, self.n_drop, self.flags, self.nodes, self.d2_joint = recs, n_match, n_new, n_drop, flags, nodes, d2_joint
+
+
+def _joint_config(cfg):
+    """A JointConfig from None (the defaults), a JointConfig or a dict of its fields (gate_joint: 16 values)."""
+    if cfg is None:
+        return default_joint_config()
+    if isinstance(cfg, JointConfig):
+        return cfg
+    c = default_joint_config()
+    for k, v in dict(cfg).items():
+        if k not in ("gate_match", "gate_new", "gate_joint", "max_nodes"):
+            raise ValueError(f"unknown joint association setting {k!r}")
+        if k == "gate_joint":
+            v = (C.c_double * 16)(*[float(g) for g in v])
+        setattr(c, k, v)
+    return c
 
 
 class MapResult(AssocResult):
@@ -927,6 +956,96 @@ class BatchedEKF(BatchedFilter):
         _lib.check(_lib.lib().slam_last_associate_work(self.h, by, C.byref(a), C.byref(b)))
         return by[0], by[1], a.value, b.value
 
+    # -- detections without ids, judged jointly: JCBB (slam_associate_joint_*, include/slam_batch.h) --
+    def _joint_config(self, cfg):
+        return _joint_config(cfg)
+
+    def _joint_outputs(self, det):
+        out = self._assoc_outputs(det)
+        out.update(d2_joint=np.zeros(self.batch), nodes=np.zeros(self.batch, dtype=np.int32),
+                   ncand=np.zeros((self.batch, INNOV_MAX_DET), dtype=np.int32))
+        return out
+
+    def associate_joint(self, cmdMsg, meas, meas_count, det=True, cfg=None, dev_out=None):
+        """associate() with joint compatibility (JCBB): the dict of associate() - verdict may hold ASSOC_JOINT_UNPAIRED, slot and det are
+        those of the paired slot where MATCHED - plus d2_joint [batch], nodes [batch] and ncand (batch, INNOV_MAX_DET).  cfg: a
+        JointConfig, a dict of its fields, or None.  meas as an int: DEVICE pointers (meas_count = (pointer, k_stride), cmdMsg one command
+        or a device pointer, dev_out = (d_meas_out, d_count_out), which may be the input pair); then no meas_out / count_out are returned."""
+        self._need()
+        out = self._joint_outputs(det)
+        c = self._joint_config(cfg)
+        tail = (_d(out["d2_joint"]), _i(out["nodes"]), _i(out["ncand"]))
+        if isinstance(meas, int):
+            each = isinstance(cmdMsg, int)
+            cmd = None if each else self._cmd(cmdMsg)
+            if cmd is not None and cmd.ndim != 1:
+                raise ValueError("device messages take one command, or the device pointer of per-instance commands")
+            cp = C.c_void_p(cmdMsg) if each else C.cast(_f(cmd), C.c_void_p)
+            _lib.check(_lib.lib().slam_associate_joint_dev(self.h, C.byref(c), cp, int(each), C.c_void_p(meas), C.c_void_p(meas_count[0]),
+                                                           int(meas_count[1]), _d(out["rec"]), _i(out["n_match"]), _i(out["n_new"]),
+                                                           _i(out["n_drop"]), _i(out["flags"]), _i(out["verdict"]), _i(out["slot"]),
+                                                           _d(out["det"]) if det else None, C.c_void_p(dev_out[0]), C.c_void_p(dev_out[1]), *tail))
+            return out
+        cmd = self._cmd(cmdMsg)
+        m, cnt = self._message(meas, meas_count)
+        out["meas_out"], out["count_out"] = np.zeros_like(m), np.zeros_like(cnt)
+        _lib.check(_lib.lib().slam_associate_joint(self.h, C.byref(c), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt), m.shape[1], _d(out["rec"]),
+                                                   _i(out["n_match"]), _i(out["n_new"]), _i(out["n_drop"]), _i(out["flags"]), _i(out["verdict"]),
+                                                   _i(out["slot"]), _d(out["det"]) if det else None, _f(out["meas_out"]), _i(out["count_out"]),
+                                                   *tail))
+        return out
+
+    def step_associated_joint(self, cmdMsg, meas, meas_count, stats=True, cfg=None):
+        """One jointly associated timestep, as step_associated().  meas as an int: DEVICE pointers as associate_joint()."""
+        self._need()
+        out = dict(rec=np.zeros(16), n_drop=np.zeros(self.batch, dtype=np.int32)) if stats else None
+        c = self._joint_config(cfg)
+        rp, dp = (_d(out["rec"]) if stats else None), (_i(out["n_drop"]) if stats else None)
+        if isinstance(meas, int):
+            each = isinstance(cmdMsg, int)
+            cmd = None if each else self._cmd(cmdMsg)
+            if cmd is not None and cmd.ndim != 1:
+                raise ValueError("device messages take one command, or the device pointer of per-instance commands")
+            cp = C.c_void_p(cmdMsg) if each else C.cast(_f(cmd), C.c_void_p)
+            _lib.check(_lib.lib().slam_step_associated_joint_dev(self.h, C.byref(c), cp, int(each), C.c_void_p(meas), C.c_void_p(meas_count[0]),
+                                                                 int(meas_count[1]), rp, dp))
+        else:
+            cmd = self._cmd(cmdMsg)
+            m, cnt = self._message(meas, meas_count)
+            _lib.check(_lib.lib().slam_step_associated_joint(self.h, C.byref(c), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt), m.shape[1], rp, dp))
+        self.timestep += 1
+        return out
+
+    def associate_joint_run(self, cmds, meas, meas_count, series=False, cfg=None):
+        """T jointly associated ticks of a recorded log without ids, layout and result as associate_run (the records' columns: JointResult's
+        REC_* constants); series=True also records n_match, n_new, n_drop, flags, nodes and d2_joint of every instance."""
+        self._need()
+        c32 = np.ascontiguousarray(cmds, dtype=np.float32)
+        m = np.ascontiguousarray(meas, dtype=np.float32)
+        cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
+        each = c32.ndim == 3
+        if c32.shape[1:] != ((self.batch, 2) if each else (2,)) or m.ndim != 4 or m.shape[:2] != (c32.shape[0], self.batch) or m.shape[2] == 0 \
+                or m.shape[3] != 3 or cnt.shape != m.shape[:2]:
+            raise ValueError(f"a log needs cmds (T, 2) or (T, {self.batch}, 2), meas (T, {self.batch}, k_stride > 0, 3) and meas_count (T, {self.batch})")
+        T = c32.shape[0]
+        res = JointResult(np.zeros((T, 16)))
+        if series:
+            res.n_match, res.n_new, res.n_drop, res.flags, res.nodes = (np.zeros((T, self.batch), dtype=np.int32) for _ in range(5))
+            res.d2_joint = np.zeros((T, self.batch))
+        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
+        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
+        _lib.check(_lib.lib().slam_associate_joint_run(self.h, C.byref(self._joint_config(cfg)), _f(c32), int(each), _f(m), _i(cnt), m.shape[2], T,
+                                                       pd(res.recs), pi(res.n_match), pi(res.n_new), pi(res.n_drop), pi(res.flags),
+                                                       pd(res.d2_joint), pi(res.nodes)))
+        self.timestep += T
+        return res
+
+    def last_joint_work(self):
+        """last_associate_work() for the joint association: (model bytes, the same with the reads of P in 128-byte lines, device ms of the
+        joint launches of the last associate_joint_run or -1 without set_nav_timing, device ms of that whole run or -1)."""
+        self._need(); by = (C.c_double * 2)(); a = C.c_double(0); b = C.c_double(0)
+        _lib.check(_lib.lib().slam_last_joint_work(self.h, by, C.byref(a), C.byref(b)))
+        return by[0], by[1], a.value, b.value
 
     # -- map management: landmarks leave the map again (slam_remove_landmarks, slam_map_*, include/slam_batch.h) --
     def _map_config(self, cfg):
@@ -1271,6 +1390,37 @@ def associate_instance_host(x, P, ids, L_max, status, cmd, meas, noise, lm_from_
                                                        _d(out["cost"]) if out["cost"].size else None, _i(out["verdict"]), _i(out["slot"]),
                                                        _d(out["det"]), _f(out["meas_out"]), C.byref(co)))
     out.update(n_match=nm.value, n_new=nn.value, n_drop=nd.value, flags=fl.value, count_out=co.value)
+    return out
+
+
+def associate_joint_instance_host(x, P, ids, L_max, status, cmd, meas, noise, lm_from_pred=False, f32_storage=False, cfg=None, count=None,
+                                  k_stride=None):
+    """TEST HOOK (slam_associate_joint_instance_host): the per-instance function of the joint association kernel compiled for the host; no
+    GPU.  Arguments as associate_instance_host (cfg: a JointConfig, a dict of its fields, or None).  Returns its dict plus d2_joint, nodes
+    and ncand (INNOV_MAX_DET,)."""
+    x = np.ascontiguousarray(x, dtype=np.float64); P = np.ascontiguousarray(P, dtype=np.float64)
+    ids = np.ascontiguousarray(ids, dtype=np.int32); M = ids.shape[0]
+    m = np.ascontiguousarray(meas, dtype=np.float32).reshape(-1, 3)
+    c = np.ascontiguousarray(cmd, dtype=np.float32).reshape(2)
+    if x.shape != (3 + 2 * M,) or P.shape != (3 + 2 * M, 3 + 2 * M):
+        raise ValueError("x and P do not match the number of ids")
+    ks = max(m.shape[0], 1) if k_stride is None else int(k_stride)
+    count = m.shape[0] if count is None else int(count)
+    if ks < m.shape[0]:
+        raise ValueError("k_stride is smaller than the message")
+    row = np.zeros((ks, 3), dtype=np.float32); row[:m.shape[0]] = m
+    k_in = min(max(count, 0), ks)
+    out = dict(rec=np.zeros(16), cost=np.full((k_in if k_in <= INNOV_MAX_DET else 0, M), np.nan), verdict=np.zeros(INNOV_MAX_DET, dtype=np.int32),
+               slot=np.zeros(INNOV_MAX_DET, dtype=np.int32), det=np.zeros((INNOV_MAX_DET, 4)), meas_out=row.copy(),
+               ncand=np.zeros(INNOV_MAX_DET, dtype=np.int32))
+    nm = C.c_int32(0); nn = C.c_int32(0); nd = C.c_int32(0); fl = C.c_int32(0); co = C.c_int32(0); d2 = C.c_double(0); no = C.c_int32(0)
+    _lib.check(_lib.lib().slam_associate_joint_instance_host(_d(x), _d(P), _i(ids) if M else None, M, int(L_max), int(status), _f(c), _f(row), count,
+                                                             ks, C.byref(noise), int(bool(lm_from_pred)), int(bool(f32_storage)),
+                                                             C.byref(_joint_config(cfg)), _d(out["rec"]), C.byref(nm), C.byref(nn), C.byref(nd),
+                                                             C.byref(fl), _d(out["cost"]) if out["cost"].size else None, _i(out["verdict"]),
+                                                             _i(out["slot"]), _d(out["det"]), _f(out["meas_out"]), C.byref(co), C.byref(d2),
+                                                             C.byref(no), _i(out["ncand"])))
+    out.update(n_match=nm.value, n_new=nn.value, n_drop=nd.value, flags=fl.value, count_out=co.value, d2_joint=d2.value, nodes=no.value)
     return out
 
 
