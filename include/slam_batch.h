@@ -498,7 +498,8 @@ int slam_innovation_instance_host(const double* x, const double* P, const int32_
  *   for landmark_id_is_known = 0); also SLAM_ERR_ARG for a gate that is NaN or <= 0 (+inf is allowed: nothing is rejected) and for outputs
  *   that overlap the inputs other than in place; slam_step_gated* and slam_gate_run: SLAM_ERR_STATE while slam_track_instance is on or a
  *   prediction is pending.
- * Not covered: the simulator sources (their step generates its own message inside the step kernel); slam_multi_*; the pose graph;
+ * Not covered: the simulator sources (their step generates its own message inside the step kernel; slam_gate_run_sim, "simulator source
+ *   with a sensor fault model" below, puts the simulator in front of the gated step instead); slam_multi_*; the pose graph;
  *   multi-step launches (a gated step is one launch per tick); rejecting on anything but the individual NIS - there is no joint
  *   compatibility test here (id-less detections get one in slam_associate_joint, below), and a detection of an unmapped id is inserted
  *   ungated (detections without ids: slam_associate, below). */
@@ -589,7 +590,7 @@ int slam_gate_instance_host(const double* x, const double* P, const int32_t* ids
  *   k_stride <= 0, T < 0, outputs that overlap the inputs other than in place; NULL handle.  SLAM_ERR_UNSUPPORTED: the UKF kinds, and
  *   handles with landmark_id_is_known = 0 (those associate inside their step).  SLAM_ERR_STATE: before slam_init; slam_step_associated*
  *   and slam_associate_run also while slam_track_instance is on or a prediction is pending.
- * Not covered: joint compatibility (JCBB) - that is slam_associate_joint, below; reassigning conflict losers; the ln det S term of the full likelihood; the simulator sources;
+ * Not covered: joint compatibility (JCBB) - that is slam_associate_joint, below; reassigning conflict losers; the ln det S term of the full likelihood; the simulator sources (slam_associate_run_sim, below, puts the simulator in front instead);
  *   slam_multi_*; the pose graph; a fused associate-plus-gate call - chain slam_associate_dev and slam_step_gated_dev on device buffers. */
 enum slam_assoc_verdict {
     SLAM_ASSOC_NONE = 0,        /* beyond the count, or any slot of an instance that emits an empty message */
@@ -686,7 +687,8 @@ int slam_associate_instance_host(const double* x, const double* P, const int32_t
  *   landmark_id_is_known = 0; SLAM_ERR_STATE before slam_init, and for the steps and the run while slam_track_instance is on or a
  *   prediction is pending); also SLAM_ERR_ARG for a gate_joint entry that is NaN, <= 0 or below its predecessor (+inf is allowed) and for
  *   max_nodes outside 1 .. 65536.
- * Not covered: the UKF kinds; the simulator sources; slam_multi_*; the pose graph; joint association inside slam_manage_run /
+ * Not covered: the UKF kinds; the simulator sources (slam_associate_joint_run_sim, below, puts the simulator in front instead);
+ *   slam_multi_*; the pose graph; joint association inside slam_manage_run /
  *   slam_manage_merge_run; the ln det S term of the full likelihood; more than 16 pairings per message. */
 #define SLAM_JOINT_MAX_CAND 4    /* candidates kept per detection */
 #define SLAM_JOINT_MAX_PAIR 16   /* pairings of one hypothesis */
@@ -769,7 +771,8 @@ int slam_associate_joint_instance_host(const double* x, const double* P, const i
  *   for slam_step_managed* and slam_manage_run what slam_step_associated refuses.  SLAM_ERR_STATE: before slam_init, while
  *   slam_track_instance is on, while a prediction is pending.  Every call runs the queued timesteps first.
  * Not covered: merging duplicate landmarks (these calls do not merge: see "landmark merging" below, slam_map_merge); the UKF;
- *   slam_multi_*; the simulator sources; the pose graph; counters in checkpoints. */
+ *   slam_multi_*; the simulator sources (slam_manage_run_sim and slam_manage_merge_run_sim, below, put the simulator in front instead);
+ *   the pose graph; counters in checkpoints. */
 typedef struct slam_map_config {
     double range_shrink;    /* a landmark is expected within range_max * range_shrink; in (0, 1] */
     double fov_margin;      /* ... and at least this far inside the field of view, rad; >= 0 */
@@ -896,6 +899,125 @@ int slam_last_merge_work(slam_handle* h, double* bytes, double* merge_ms, double
 int slam_merge_instance_host(double* x, double* P, int32_t* ids, int M, int L_max, int32_t status, int f32_storage, const slam_merge_config* cfg,
                              int32_t* seen, int32_t* expected, const int32_t* partner_in, int fuse, int32_t* partner_out, double* d2_out,
                              double rec[16], int32_t* M_out);
+
+/* ---- simulator source with a sensor fault model for the robust runs (csrc/sense_kernel.h) -------------------------------------------------
+ * slam_gate_run, slam_associate_run, slam_associate_joint_run, slam_manage_run and slam_manage_merge_run are host-fed: their messages come
+ * from a log, the handle's truth does not move, and a recorded log fixes the trajectory.  The calls below put the simulator in front of
+ * them on the device: a side kernel writes the message the unmodified known-id step (or a gate, an association, a managed step in front of
+ * it) is then given, with dropouts, range spikes, clutter, a shuffled order and erased ids drawn per instance from the handle's counter
+ * based generator; a second side kernel commits the simulator's bookkeeping after the step, so slam_get_truth, slam_error_stats,
+ * slam_monitor_now and the pose part of slam_consistency see such a run.  The step kernels are untouched.  EKF_SLAM with
+ * landmark_id_is_known = 1, both storage types; honours slam_set_maps, slam_set_noise_each, per-instance commands.
+ * Model, instance b (global id g = instance offset + b) at RNG step s, the step slam_step_sim would use:
+ *   0. clean message: exactly slam_step_sim's - pair 0 for the motion, pair 1 + v for the v-th visible landmark in ascending id - from the
+ *      instance's simulator noise, map and the vision limits.  The true pose advances into a STAGED row.  c_vis visible, the first
+ *      c = min(c_vis, SLAM_SENSE_MAX_DET) are kept; more sets SLAM_SENSE_TOO_LONG.  An instance whose status carries SLAM_INST_INDEX_OOR
+ *      is skipped: count 0, nothing staged, SLAM_SENSE_INSTANCE_FROZEN.
+ *   1. fault draws, pair indices the clean generator never uses, F = 0x40000000: (a_v, b_v) = pair F + v, (m_v, k_v) = pair F + 64 + v for
+ *      v < c; (ur_j, ub_j) = pair F + 128 + j, (e_j, kc_j) = pair F + 136 + j for clutter slot j < n_clutter.
+ *   2. dropout: detection v is missed iff a_v < p_miss.
+ *   3. range spike: a detection that was not missed is spiked iff b_v < p_spike; then
+ *      r_out = (float)((double)r_f32 + (spike_lo + (spike_hi - spike_lo) * m_v)), r_f32 the clean float of the message.
+ *   4. clutter: slot j is present iff e_j < p_clutter; r = (float)(clutter_r_min + (range_max - clutter_r_min) * ur_j),
+ *      beta = (float)(fov_min + (fov_max - fov_min) * ub_j), id = (float)(L_b + j) with L_b the instance's map size: never an id of the
+ *      true map - a known-id pipeline inserts it as a phantom, an id-less one never reads it.
+ *   5. order: shuffle = 0: survivors in ascending v, then present clutter in ascending j; shuffle = 1: all of them ascending by
+ *      (key, position in the shuffle = 0 order), keys k_v / kc_j.
+ *   6. erase_ids = 1: the id column is the quiet NaN 0x7FC00000.
+ *   7. output: n_out detections; the first min(n_out, k_stride) are written, the rest of the row up to k_stride as 0.0f; count = n_out
+ *      (the consumers clamp as they always do).  origin [batch][k_stride] int32: the true map row, -1 for clutter and beyond the message;
+ *      fault [batch][k_stride] int32: 1 spiked, else 0.
+ *   Every expression is evaluated as parenthesised, in fp64, unfused.  The default row (all zero) gives slam_step_sim's message bit for bit.
+ * Record, 16 doubles, every entry a sum in the fixed order of the innovation record: 0 instances sensed, 1 FROZEN, 2 TOO_LONG, 3 clean
+ *   detections kept, 4 missed, 5 spiked, 6 clutter present, 7 sum of n_out, 8 sum of max(n_out - k_stride, 0), 9 sum of the spike amounts (per
+ *   instance in ascending v), 10 instances committed, 11 sum of the position errors added at the commit, 12 - 15 reserved, 0.  Entries 10 and
+ *   11 are the commit's: 0 in the record of slam_sense.
+ * Commit, per instance, after the step: if timestep == (the timestep at the sense) + 1 the staged true pose becomes the truth and
+ *   ekf_position_error of the STORED estimate (widened) against it is added to the error sum - the value the simulator step adds, in both
+ *   storage types.  Otherwise nothing: an instance that froze in this step keeps its pre-step truth and error sum, as in slam_step_sim.
+ * Protocol: slam_sense[_dev]; the caller's step - slam_step[_each]_dev, slam_step_gated*_dev, slam_step_associated*_dev,
+ *   slam_step_managed_dev - on the message; slam_sense_commit, before any slam_map_prune or slam_map_merge of the tick (a merge can move
+ *   the pose; the simulator's error is taken after the step).  The commit leaves the handle's RNG step at s + 1 however many step calls
+ *   ran in between; an instance that advanced by more or less than one timestep is not committed.  While a sense is pending,
+ *   SLAM_ERR_STATE for a second sense, slam_step_sim, slam_run_sim*, slam_nav_run, slam_monitor_run, slam_innovation_run with a simulator
+ *   source, the *_run_sim calls and slam_save_state; slam_init* and slam_load_state clear it.
+ * Rows are inputs, not state, like the noise rows: checkpoints keep their format, slam_init* does not clear them.
+ * Errors: SLAM_ERR_ARG (checked first, before the handle is looked at): NULL cmds or outputs, k_stride <= 0, T < 0, an unknown source or
+ *   SLAM_INNOVATION_LOG, the errors of the LOG sibling's configs; NULL handle; a sensor row with a probability outside [0, 1] or not
+ *   finite, spike_lo > spike_hi or not finite, n_clutter outside 0 .. SLAM_SENSE_MAX_CLUTTER, clutter_r_min negative, not finite or above
+ *   the handle's range_max (slam_last_error names the instance and the field).  SLAM_ERR_UNSUPPORTED: the UKF kinds and
+ *   landmark_id_is_known = 0, state untouched.  SLAM_ERR_STATE: before slam_init, without a map, for NAV without a path, while
+ *   slam_track_instance is on, while a prediction or a sense is pending; slam_sense_commit with nothing pending.
+ * Not covered: the UKF kinds; the pose graph; slam_multi_*; a simulator source inside multi-step launches; wrong-id (swapped fiducial)
+ *   faults; bursty or correlated faults; more than SLAM_SENSE_MAX_DET clean detections per message; the landmark part of slam_consistency
+ *   on id-less runs (its truth lookup goes by the filter's own ids). */
+#define SLAM_SENSE_MAX_DET 64      /* clean detections of one message (= SLAM_INNOV_MAX_DET) */
+#define SLAM_SENSE_MAX_CLUTTER 8   /* clutter slots of one message */
+enum slam_sense_flags {
+    SLAM_SENSE_INSTANCE_FROZEN = 1,   /* status SLAM_INST_INDEX_OOR: nothing sensed, nothing staged */
+    SLAM_SENSE_TOO_LONG = 2           /* more than SLAM_SENSE_MAX_DET landmarks in view: the surplus (highest ids) is not in the message */
+};
+typedef struct slam_sensor {
+    double p_miss;          /* a clean detection is dropped with this probability */
+    double p_spike;         /* a surviving detection gets a range spike with this probability */
+    double spike_lo, spike_hi;   /* the spike is uniform in [spike_lo, spike_hi), m, added to the range */
+    double p_clutter;       /* each of the n_clutter slots holds a false detection with this probability */
+    double clutter_r_min;   /* clutter ranges are uniform in [clutter_r_min, range_max); 0 <= clutter_r_min <= range_max */
+    int32_t n_clutter;      /* 0 .. SLAM_SENSE_MAX_CLUTTER */
+    int32_t shuffle;        /* nonzero: the message order is random instead of ascending id */
+    int32_t erase_ids;      /* nonzero: the id column is NaN */
+} slam_sensor;
+/* the all-off row: every field 0 */
+int slam_sensor_default(slam_sensor* row);
+/* rows: [batch], host; NULL = the all-off row for every instance.  Runs the step queue first, like slam_set_noise_each. */
+int slam_set_sensor_each(slam_handle* h, const slam_sensor* rows);
+/* One tick of the model for the command the step will be given (cmd_each = 0: cmds [2]; else cmds [batch][2]), into the caller's HOST
+ * buffers: meas [batch][k_stride][3], meas_count [batch]; optional origin, fault [batch][k_stride], truth_next [batch][3] (the staged true
+ * pose; a frozen instance: its pose as it is) and rec [16].  The truth is staged and a sense is pending.  Synchronises. */
+int slam_sense(slam_handle* h, const float* cmds, int cmd_each, float* meas, int32_t* meas_count, int k_stride, int32_t* origin, int32_t* fault,
+               double* truth_next, double rec[16]);
+/* The same into DEVICE buffers, written in the order of the handle's stream (cmd_each != 0: cmds is a device pointer too); d_origin and
+ * d_fault may be NULL.  Does not synchronise. */
+int slam_sense_dev(slam_handle* h, const float* cmds, int cmd_each, float* d_meas, int32_t* d_count, int k_stride, int32_t* d_origin,
+                   int32_t* d_fault);
+/* After the caller's step: the commit of every instance, and the tick's record with entries 10 and 11 (rec may be NULL: the call does not
+ * synchronise then). */
+int slam_sense_commit(slam_handle* h, double rec[16]);
+/* Optional HOST arrays of a *_run_sim call, any may be NULL: meas [T][batch][k_stride][3] and count [T][batch], the message as emitted,
+ * before the run's own filtering; origin, fault [T][batch][k_stride]; truth [T][batch][3] after the tick's commit; err_pos [T][batch], the
+ * value the commit added, NaN where not committed; cmds [T][batch][2], what the step was given (which matters for NAV);
+ * recs [T][16], the sense records. */
+typedef struct slam_sense_log {
+    float* meas; int32_t* count; int32_t* origin; int32_t* fault; double* truth; double* err_pos; float* cmds; double* recs;
+} slam_sense_log;
+/* The five host-fed runs with the simulator as their source: the configs and outputs of the LOG sibling, source = SLAM_INNOVATION_SHARED
+ * (cmds [T][2]), _EACH (cmds [T][batch][2]) or _NAV (cmds not read; slam_nav_set_path* first); SLAM_INNOVATION_LOG is SLAM_ERR_ARG.  A tick
+ * is {NAV: the controller launch; the sense launch; the sibling's own launches and its one-step launch on that message; the commit
+ * launch; the sibling's prune or merge}.  The filter state, the records and every series are, bit for bit, what the LOG sibling gives on
+ * log->meas, log->count and log->cmds.  The rows of the log count in the chunk budget of slam_innovation_run; chunking changes no bit. */
+int slam_gate_run_sim(slam_handle* h, const slam_gate_config* cfg, int source, const float* cmds, int k_stride, int T, double* recs,
+                      double* nis_sum, int32_t* n_upd, int32_t* n_rej, int32_t* flags, const slam_sense_log* log);
+int slam_associate_run_sim(slam_handle* h, const slam_assoc_config* cfg, int source, const float* cmds, int k_stride, int T, double* recs,
+                           int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* flags, const slam_sense_log* log);
+int slam_associate_joint_run_sim(slam_handle* h, const slam_joint_config* cfg, int source, const float* cmds, int k_stride, int T, double* recs,
+                                 int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* flags, double* d2_joint, int32_t* nodes,
+                                 const slam_sense_log* log);
+int slam_manage_run_sim(slam_handle* h, const slam_assoc_config* assoc_cfg, const slam_map_config* map_cfg, int source, const float* cmds,
+                        int k_stride, int T, double* recs, int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* n_removed, int32_t* flags,
+                        const slam_sense_log* log);
+int slam_manage_merge_run_sim(slam_handle* h, const slam_assoc_config* assoc_cfg, const slam_map_config* map_cfg,
+                              const slam_merge_config* merge_cfg, int source, const float* cmds, int k_stride, int T, double* recs,
+                              int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* n_removed, int32_t* n_merged, int32_t* flags,
+                              const slam_sense_log* log);
+/* TEST HOOK, not part of the filter interface: the model of ONE instance compiled for the HOST from csrc/sense_kernel.h (the source the
+ * kernel compiles, no device needed).  instance: the global id; truth [3]: the true pose before the tick; status: slam_instance_flags;
+ * map_xy [L][2]; d_max, th_max: the config's command limits; sim_noise [4]: the half-widths sim_V_00, sim_V_11, sim_W_00, sim_W_11;
+ * row NULL: the all-off row.  Outputs, any but meas and count may be NULL: meas [k_stride][3], count, origin and fault [k_stride],
+ * truth_next [3], flags (slam_sense_flags), rec [16]. */
+int slam_sense_instance_host(uint64_t seed, int64_t instance, uint32_t step, const double truth[3], const float cmd[2], int32_t status,
+                             const double* map_xy, int L, double d_max, double th_max, double range_max, double fov_min, double fov_max,
+                             const double sim_noise[4], const slam_sensor* row, int k_stride, float* meas, int32_t* count, int32_t* origin,
+                             int32_t* fault, double truth_next[3], int32_t* flags, double rec[16]);
 
 /* ---- closed loop: commands from each instance's own estimate (goal_pursuit_node.py:23-50, pure_pursuit.py:17-161) ---------------------
  * The entry points above run open loop: every command is fixed before the run.  The reference's default launch (sim_base.launch,

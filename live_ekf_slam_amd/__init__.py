@@ -19,5 +19,7 @@ from .config import MapConfig, default_map_config  # noqa: F401
 from .filters import MapResult, map_instance_host  # noqa: F401
 from .config import MergeConfig, default_merge_config  # noqa: F401
 from .filters import MergeResult, merge_instance_host  # noqa: F401
+from .config import SensorConfig, default_sensor_config, SENSE_MAX_DET, SENSE_MAX_CLUTTER, SENSE_INSTANCE_FROZEN, SENSE_TOO_LONG  # noqa: F401
+from .filters import SenseLogResult, sense_instance_host  # noqa: F401
 from .pose_graph import BatchedPoseGraph, NaiveFilter  # noqa: F401
 from ._lib import SlamError  # noqa: F401

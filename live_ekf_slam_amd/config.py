@@ -198,6 +198,35 @@ def default_merge_config() -> MergeConfig:
     return MergeConfig(-2.0 * math.log(0.05), 0.0, 10)
 
 
+class SensorConfig(C.Structure):
+    """ctypes mirror of `slam_sensor` (include/slam_batch.h): one row of the sensor fault model of sense() and the *_run_sim calls -
+    dropout, range spikes, clutter, shuffled order, erased ids."""
+    _fields_ = [("p_miss", C.c_double), ("p_spike", C.c_double), ("spike_lo", C.c_double), ("spike_hi", C.c_double), ("p_clutter", C.c_double),
+                ("clutter_r_min", C.c_double), ("n_clutter", C.c_int32), ("shuffle", C.c_int32), ("erase_ids", C.c_int32)]
+
+
+SENSOR_FIELDS = tuple(name for name, _ in SensorConfig._fields_)
+SENSE_MAX_DET, SENSE_MAX_CLUTTER = 64, 8
+SENSE_INSTANCE_FROZEN, SENSE_TOO_LONG = 1, 2
+
+
+def default_sensor_config(**fields) -> SensorConfig:
+    """The all-off row (every field 0): the message of the plain simulator step.  Keyword arguments set fields."""
+    row = SensorConfig()
+    for k, v in fields.items():
+        if k not in SENSOR_FIELDS:
+            raise ValueError(f"unknown sensor setting {k!r}")
+        setattr(row, k, v)
+    return row
+
+
+class SenseLog(C.Structure):
+    """ctypes mirror of `slam_sense_log`: the optional host arrays of a *_run_sim call."""
+    _fields_ = [("meas", C.POINTER(C.c_float)), ("count", C.POINTER(C.c_int32)), ("origin", C.POINTER(C.c_int32)), ("fault", C.POINTER(C.c_int32)),
+                ("truth", C.POINTER(C.c_double)), ("err_pos", C.POINTER(C.c_double)), ("cmds", C.POINTER(C.c_float)),
+                ("recs", C.POINTER(C.c_double))]
+
+
 def default_monitor_config() -> MonitorConfig:
     """The chi-square quantiles at 0.025 and 0.975 for 3 degrees of freedom; no full evaluation."""
     return MonitorConfig(0.21579528262389785, 9.348403604496148, 0)

@@ -225,45 +225,50 @@ int slam_step_associated_dev(slam_handle* h, const slam_assoc_config* cfg, const
     return step_associated_now(h, c, cmd_each ? kNoCmd : cmds, cmd_each ? cmds : nullptr, d_meas, d_count, k_stride, rec, n_drop);
 }
 
-int slam_associate_run(slam_handle* h, const slam_assoc_config* cfg, const float* cmds, int cmd_each, const float* meas, const int32_t* count,
-                       int k_stride, int T, double* recs, int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* flags) {
-    slam_assoc_config c;
-    TRY(assoc_config(cfg, &c));
-    if (T < 0) return slam_internal_fail(SLAM_ERR_ARG, "T = %d is negative", T);
-    if (!cmds) return slam_internal_fail(SLAM_ERR_ARG, "cmds is NULL");
-    if (!meas || !count) return slam_internal_fail(SLAM_ERR_ARG, "meas or meas_count is NULL");
-    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
-    TRY(run_enter(h, "slam_associate_run", false, false, true));
+}  // extern "C"
+
+namespace {
+
+// slam_associate_run and slam_associate_run_sim once their arguments are in order: T associated ticks with the commands of `csrc` on the messages of `msgs`
+int associate_run(slam_handle* h, const char* who, const slam_assoc_config& c, TickCmds::Source csrc, const float* cmds, TickMsgs& msgs, int T,
+                  double* recs, int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* flags) {
+    const int k_stride = msgs.k_stride;
+    TRY(run_enter(h, who, msgs.sim(), csrc == TickCmds::kNav, true));
     if (T == 0) return SLAM_OK;
     HIP_TRY(hipSetDevice(h->device));
-    const size_t B = (size_t)h->B, mrow = 3 * (size_t)k_stride * B;
+    const size_t B = (size_t)h->B;
     TickCmds tcmd;
-    TRY(tcmd.init(h, cmd_each ? TickCmds::kEach : TickCmds::kShared, cmds));
+    TRY(tcmd.init(h, csrc, cmds));
     // what a tick holds on the device: its rows of the counts, of the commands (cmd_each) and of the messages
-    const double per_tick = 5.0 * 4.0 * (double)B + tcmd.bytes_per_tick(h) + 4.0 * (double)mrow + 4.0 * (double)B;
+    const double per_tick = 5.0 * 4.0 * (double)B + tcmd.bytes_per_tick(h) + msgs.bytes_per_tick(h, tcmd);
     const int chunk = slam_host::ticks_per_chunk(T, per_tick, slam_host::tick_log_budget());
     TRY(assoc_reserve(h, k_stride, (size_t)chunk));
+    TRY(msgs.reserve(h, tcmd, chunk));
     const size_t cb = (size_t)chunk * B;
     int32_t* const di = h->assoc.dint;
     const int rc = run_chunked(
         h, T, chunk, h->nav.time_ticks, h->assoc.times,
         [&](int t0, int tc) -> int {
             TRY(tcmd.upload(h, t0, tc));
-            return upload_messages(h, meas + (size_t)t0 * mrow, count + (size_t)t0 * B, k_stride, (size_t)tc);
+            return msgs.upload(h, t0, tc);
         },
         [&](int t0, int t, auto mark) -> int {
-            const float *cmd, *d_each;
+            const float *cmd, *d_each, *dm;
+            const int32_t* dc;
             TRY(tcmd.select(h, t0, t, &cmd, &d_each));
+            TRY(msgs.produce(h, tcmd, t, cmd, d_each, &dm, &dc));
             const size_t o = (size_t)t * B;
             TRY(mark([&] {
-                return assoc_launch(h, c, cmd, d_each, h->inn.dmeas + (size_t)t * mrow, h->inn.dcount + o, k_stride, h->assoc.dmeas, h->assoc.dcount,
+                return assoc_launch(h, c, cmd, d_each, dm, dc, k_stride, h->assoc.dmeas, h->assoc.dcount,
                                     h->inn.drec + (size_t)t * slam::kInnovRecLen,
                                     {di + o, di + cb + o, di + 2 * cb + o, di + 3 * cb + o, di + 4 * cb + o, nullptr, nullptr, nullptr});
             }));
-            return launch_step(h, cmd, 0, h->assoc.dmeas, h->assoc.dcount, k_stride, d_each);
+            TRY(launch_step(h, cmd, 0, h->assoc.dmeas, h->assoc.dcount, k_stride, d_each));
+            return msgs.commit(h, t);
         },
         [&](int t0, int tc) -> int {
             const size_t nb = sizeof(int32_t) * (size_t)tc * B, o = (size_t)t0 * B;
+            TRY(msgs.download(h, tcmd, t0, tc));
             TRY(assoc_sum_work(h, (size_t)tc, cb));   // (after the chunk's events: it is no part of the run's times)
             if (recs) HIP_TRY(hipMemcpy(recs + (size_t)t0 * slam::kInnovRecLen, h->inn.drec, sizeof(double) * (size_t)tc * slam::kInnovRecLen, hipMemcpyDeviceToHost));
             if (n_match) HIP_TRY(hipMemcpy(n_match + o, di, nb, hipMemcpyDeviceToHost));
@@ -275,6 +280,36 @@ int slam_associate_run(slam_handle* h, const slam_assoc_config* cfg, const float
     TRY(rc);
     HIP_TRY(hipStreamSynchronize(h->stream));
     return assoc_read_work(h);
+}
+
+}  // namespace
+
+extern "C" {
+
+int slam_associate_run(slam_handle* h, const slam_assoc_config* cfg, const float* cmds, int cmd_each, const float* meas, const int32_t* count,
+                       int k_stride, int T, double* recs, int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* flags) {
+    slam_assoc_config c;
+    TRY(assoc_config(cfg, &c));
+    if (T < 0) return slam_internal_fail(SLAM_ERR_ARG, "T = %d is negative", T);
+    if (!cmds) return slam_internal_fail(SLAM_ERR_ARG, "cmds is NULL");
+    if (!meas || !count) return slam_internal_fail(SLAM_ERR_ARG, "meas or meas_count is NULL");
+    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
+    TickMsgs msgs;
+    msgs.init_log(meas, count, k_stride);
+    return associate_run(h, "slam_associate_run", c, cmd_each ? TickCmds::kEach : TickCmds::kShared, cmds, msgs, T, recs, n_match, n_new, n_drop, flags);
+}
+
+int slam_associate_run_sim(slam_handle* h, const slam_assoc_config* cfg, int source, const float* cmds, int k_stride, int T, double* recs,
+                           int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* flags, const slam_sense_log* log) {
+    slam_assoc_config c;
+    TickCmds::Source csrc;
+    TRY(assoc_config(cfg, &c));
+    TRY(sim_run_source(source, cmds, &csrc));
+    if (T < 0) return slam_internal_fail(SLAM_ERR_ARG, "T = %d is negative", T);
+    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
+    TickMsgs msgs;
+    msgs.init_sim(log, k_stride);
+    return associate_run(h, "slam_associate_run_sim", c, csrc, cmds, msgs, T, recs, n_match, n_new, n_drop, flags);
 }
 
 int slam_last_associate_work(slam_handle* h, double* bytes, double* assoc_ms, double* total_ms) {

@@ -191,25 +191,26 @@ int slam_step_gated_each_dev(slam_handle* h, const slam_gate_config* cfg, const 
     return step_gated_dev(h, cfg, d_cmds, 1, d_meas, d_count, k_stride, rec, n_rej);
 }
 
-int slam_gate_run(slam_handle* h, const slam_gate_config* cfg, const float* cmds, int cmd_each, const float* meas, const int32_t* count,
-                  int k_stride, int T, double* recs, double* nis_sum, int32_t* n_upd, int32_t* n_rej, int32_t* flags) {
-    slam_gate_config c;
-    TRY(gate_config(cfg, &c));
-    if (T < 0) return slam_internal_fail(SLAM_ERR_ARG, "T = %d is negative", T);
-    if (!cmds) return slam_internal_fail(SLAM_ERR_ARG, "cmds is NULL");
-    if (!meas || !count) return slam_internal_fail(SLAM_ERR_ARG, "meas or meas_count is NULL");
-    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
-    TRY(run_enter(h, "slam_gate_run", false, false, true));
+}  // extern "C"
+
+namespace {
+
+// slam_gate_run and slam_gate_run_sim once their arguments are in order: T gated ticks with the commands of `csrc` on the messages of `msgs`
+int gate_run(slam_handle* h, const char* who, const slam_gate_config& c, TickCmds::Source csrc, const float* cmds, TickMsgs& msgs, int T,
+             double* recs, double* nis_sum, int32_t* n_upd, int32_t* n_rej, int32_t* flags) {
+    const int k_stride = msgs.k_stride;
+    TRY(run_enter(h, who, msgs.sim(), csrc == TickCmds::kNav, true));
     if (T == 0) return SLAM_OK;
     HIP_TRY(hipSetDevice(h->device));
-    const size_t B = (size_t)h->B, mrow = 3 * (size_t)k_stride * B;
+    const size_t B = (size_t)h->B;
     TickCmds tcmd;
-    TRY(tcmd.init(h, cmd_each ? TickCmds::kEach : TickCmds::kShared, cmds));
+    TRY(tcmd.init(h, csrc, cmds));
     // what a tick holds on the device: its rows of the series, of the commands (cmd_each) and of the messages
     const double per_tick = 8.0 * (nis_sum ? (double)B : 0.0) + 4.0 * (double)B * ((n_upd ? 1 : 0) + (flags ? 1 : 0) + (n_rej ? 1 : 0)) +
-                            tcmd.bytes_per_tick(h) + 4.0 * (double)mrow + 4.0 * (double)B;
+                            tcmd.bytes_per_tick(h) + msgs.bytes_per_tick(h, tcmd);
     const int chunk = slam_host::ticks_per_chunk(T, per_tick, slam_host::tick_log_budget());
     TRY(gate_reserve_step(h, k_stride, (size_t)chunk));
+    TRY(msgs.reserve(h, tcmd, chunk));
     if (nis_sum) TRY(grow(h, h->inn.dlog, (size_t)chunk * B));
     TRY(grow(h, h->inn.dint, 2 * (size_t)chunk * B));
     int32_t* const d_upd = h->inn.dint;
@@ -218,20 +219,24 @@ int slam_gate_run(slam_handle* h, const slam_gate_config* cfg, const float* cmds
         h, T, chunk, h->nav.time_ticks, h->gate.times,
         [&](int t0, int tc) -> int {
             TRY(tcmd.upload(h, t0, tc));
-            return upload_messages(h, meas + (size_t)t0 * mrow, count + (size_t)t0 * B, k_stride, (size_t)tc);
+            return msgs.upload(h, t0, tc);
         },
         [&](int t0, int t, auto mark) -> int {
-            const float *cmd, *d_each;
+            const float *cmd, *d_each, *dm;
+            const int32_t* dc;
             TRY(tcmd.select(h, t0, t, &cmd, &d_each));
+            TRY(msgs.produce(h, tcmd, t, cmd, d_each, &dm, &dc));
             TRY(mark([&] {
-                return gate_launch(h, c, cmd, d_each, h->inn.dmeas + (size_t)t * mrow, h->inn.dcount + (size_t)t * B, k_stride, h->gate.dmeas,
+                return gate_launch(h, c, cmd, d_each, dm, dc, k_stride, h->gate.dmeas,
                                    h->gate.dcount, h->inn.drec + (size_t)t * slam::kInnovRecLen, nis_sum ? h->inn.dlog + (size_t)t * B : nullptr,
                                    nullptr, nullptr, n_upd ? d_upd + (size_t)t * B : nullptr, flags ? d_flags + (size_t)t * B : nullptr, nullptr,
                                    h->gate.drej + (size_t)t * B, nullptr);
             }));
-            return launch_step(h, cmd, 0, h->gate.dmeas, h->gate.dcount, k_stride, d_each);
+            TRY(launch_step(h, cmd, 0, h->gate.dmeas, h->gate.dcount, k_stride, d_each));
+            return msgs.commit(h, t);
         },
         [&](int t0, int tc) -> int {
+            TRY(msgs.download(h, tcmd, t0, tc));
             if (recs) HIP_TRY(hipMemcpy(recs + (size_t)t0 * slam::kInnovRecLen, h->inn.drec, sizeof(double) * (size_t)tc * slam::kInnovRecLen, hipMemcpyDeviceToHost));
             if (nis_sum) HIP_TRY(hipMemcpy(nis_sum + (size_t)t0 * B, h->inn.dlog, sizeof(double) * (size_t)tc * B, hipMemcpyDeviceToHost));
             if (n_upd) HIP_TRY(hipMemcpy(n_upd + (size_t)t0 * B, d_upd, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
@@ -239,6 +244,36 @@ int slam_gate_run(slam_handle* h, const slam_gate_config* cfg, const float* cmds
             if (n_rej) HIP_TRY(hipMemcpy(n_rej + (size_t)t0 * B, h->gate.drej, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
             return SLAM_OK;
         });
+}
+
+}  // namespace
+
+extern "C" {
+
+int slam_gate_run(slam_handle* h, const slam_gate_config* cfg, const float* cmds, int cmd_each, const float* meas, const int32_t* count,
+                  int k_stride, int T, double* recs, double* nis_sum, int32_t* n_upd, int32_t* n_rej, int32_t* flags) {
+    slam_gate_config c;
+    TRY(gate_config(cfg, &c));
+    if (T < 0) return slam_internal_fail(SLAM_ERR_ARG, "T = %d is negative", T);
+    if (!cmds) return slam_internal_fail(SLAM_ERR_ARG, "cmds is NULL");
+    if (!meas || !count) return slam_internal_fail(SLAM_ERR_ARG, "meas or meas_count is NULL");
+    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
+    TickMsgs msgs;
+    msgs.init_log(meas, count, k_stride);
+    return gate_run(h, "slam_gate_run", c, cmd_each ? TickCmds::kEach : TickCmds::kShared, cmds, msgs, T, recs, nis_sum, n_upd, n_rej, flags);
+}
+
+int slam_gate_run_sim(slam_handle* h, const slam_gate_config* cfg, int source, const float* cmds, int k_stride, int T, double* recs,
+                      double* nis_sum, int32_t* n_upd, int32_t* n_rej, int32_t* flags, const slam_sense_log* log) {
+    slam_gate_config c;
+    TickCmds::Source csrc;
+    TRY(gate_config(cfg, &c));
+    TRY(sim_run_source(source, cmds, &csrc));
+    if (T < 0) return slam_internal_fail(SLAM_ERR_ARG, "T = %d is negative", T);
+    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
+    TickMsgs msgs;
+    msgs.init_sim(log, k_stride);
+    return gate_run(h, "slam_gate_run_sim", c, csrc, cmds, msgs, T, recs, nis_sum, n_upd, n_rej, flags);
 }
 
 int slam_last_gate_work(slam_handle* h, double* gate_ms, double* total_ms) {

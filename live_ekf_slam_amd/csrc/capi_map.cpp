@@ -258,27 +258,26 @@ int slam_step_managed_dev(slam_handle* h, const slam_assoc_config* assoc_cfg, co
     return step_managed_now(h, ac, mc, cmd_each ? kNoCmd : cmds, cmd_each ? cmds : nullptr, d_meas, d_count, k_stride, rec, n_drop);
 }
 
-int slam_manage_run(slam_handle* h, const slam_assoc_config* assoc_cfg, const slam_map_config* map_cfg, const float* cmds, int cmd_each,
-                    const float* meas, const int32_t* count, int k_stride, int T, double* recs, int32_t* n_match, int32_t* n_new, int32_t* n_drop,
-                    int32_t* n_removed, int32_t* flags) {
-    slam_assoc_config ac; slam_map_config mc;
-    TRY(assoc_config(assoc_cfg, &ac));
-    TRY(map_config(map_cfg, &mc));
-    if (T < 0) return slam_internal_fail(SLAM_ERR_ARG, "T = %d is negative", T);
-    if (!cmds) return slam_internal_fail(SLAM_ERR_ARG, "cmds is NULL");
-    if (!meas || !count) return slam_internal_fail(SLAM_ERR_ARG, "meas or meas_count is NULL");
-    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
-    TRY(run_enter(h, "slam_manage_run", false, false, true));
+}  // extern "C"
+
+namespace {
+
+// slam_manage_run and slam_manage_run_sim once their arguments are in order: T managed ticks with the commands of `csrc` on the messages of `msgs`
+int manage_run(slam_handle* h, const char* who, const slam_assoc_config& ac, const slam_map_config& mc, TickCmds::Source csrc, const float* cmds,
+               TickMsgs& msgs, int T, double* recs, int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* n_removed, int32_t* flags) {
+    const int k_stride = msgs.k_stride;
+    TRY(run_enter(h, who, msgs.sim(), csrc == TickCmds::kNav, true));
     if (T == 0) return SLAM_OK;
     HIP_TRY(hipSetDevice(h->device));
-    const size_t B = (size_t)h->B, mrow = 3 * (size_t)k_stride * B;
+    const size_t B = (size_t)h->B;
     TickCmds tcmd;
-    TRY(tcmd.init(h, cmd_each ? TickCmds::kEach : TickCmds::kShared, cmds));
+    TRY(tcmd.init(h, csrc, cmds));
     // what a tick holds on the device: its rows of the counts (the association's five, the removal's two), of the commands (cmd_each)
     // and of the messages
-    const double per_tick = 7.0 * 4.0 * (double)B + tcmd.bytes_per_tick(h) + 4.0 * (double)mrow + 4.0 * (double)B;
+    const double per_tick = 7.0 * 4.0 * (double)B + tcmd.bytes_per_tick(h) + msgs.bytes_per_tick(h, tcmd);
     const int chunk = slam_host::ticks_per_chunk(T, per_tick, slam_host::tick_log_budget());
     TRY(assoc_reserve(h, k_stride, (size_t)chunk));
+    TRY(msgs.reserve(h, tcmd, chunk));
     TRY(map_reserve(h, (size_t)chunk));
     TRY(map_track(h));
     TRY(map_zero_work(h));
@@ -291,22 +290,26 @@ int slam_manage_run(slam_handle* h, const slam_assoc_config* assoc_cfg, const sl
         [&](int t0, int tc) -> int {
             TRY(tcmd.upload(h, t0, tc));
             HIP_TRY(hipMemsetAsync(mi, 0, sizeof(int32_t) * 2 * cb, h->stream));   // (n_removed of the ticks without a prune)
-            return upload_messages(h, meas + (size_t)t0 * mrow, count + (size_t)t0 * B, k_stride, (size_t)tc);
+            return msgs.upload(h, t0, tc);
         },
         [&](int t0, int t, auto mark) -> int {
-            const float *cmd, *d_each;
+            const float *cmd, *d_each, *dm;
+            const int32_t* dc;
             TRY(tcmd.select(h, t0, t, &cmd, &d_each));
+            TRY(msgs.produce(h, tcmd, t, cmd, d_each, &dm, &dc));
             const size_t o = (size_t)t * B;
-            TRY(assoc_launch(h, ac, cmd, d_each, h->inn.dmeas + (size_t)t * mrow, h->inn.dcount + o, k_stride, h->assoc.dmeas, h->assoc.dcount,
+            TRY(assoc_launch(h, ac, cmd, d_each, dm, dc, k_stride, h->assoc.dmeas, h->assoc.dcount,
                              h->inn.drec + (size_t)t * slam::kInnovRecLen,
                              {di + o, di + cb + o, di + 2 * cb + o, di + 3 * cb + o, di + 4 * cb + o, nullptr, nullptr, nullptr}));
             TRY(launch_step(h, cmd, 0, h->assoc.dmeas, h->assoc.dcount, k_stride, d_each));
+            TRY(msgs.commit(h, t));   // (before the prune: the simulator's error is taken after the step)
             TRY(tally_now(h, mc, h->assoc.dmeas, h->assoc.dcount, k_stride, di + 3 * cb + o));
             // (the marked group of a tick without a prune is empty: its event pair brackets nothing)
             return mark([&]() -> int { return prunes_after(t0 + t) ? map_compact_launch(h, nullptr, mc, mi + o, mi + cb + o, false) : SLAM_OK; });
         },
         [&](int t0, int tc) -> int {
             const size_t nb = sizeof(int32_t) * (size_t)tc * B, o = (size_t)t0 * B;
+            TRY(msgs.download(h, tcmd, t0, tc));
             for (int t = 0; t < tc; ++t)               // (after the chunk's events: the model is no part of the run's times)
                 if (prunes_after(t0 + t)) TRY(map_sum_work(h, mi + (size_t)t * B, mi + cb + (size_t)t * B, true));
             if (recs) HIP_TRY(hipMemcpy(recs + (size_t)t0 * slam::kInnovRecLen, h->inn.drec, sizeof(double) * (size_t)tc * slam::kInnovRecLen, hipMemcpyDeviceToHost));
@@ -320,6 +323,41 @@ int slam_manage_run(slam_handle* h, const slam_assoc_config* assoc_cfg, const sl
     TRY(rc);
     HIP_TRY(hipStreamSynchronize(h->stream));
     return SLAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int slam_manage_run(slam_handle* h, const slam_assoc_config* assoc_cfg, const slam_map_config* map_cfg, const float* cmds, int cmd_each,
+                    const float* meas, const int32_t* count, int k_stride, int T, double* recs, int32_t* n_match, int32_t* n_new, int32_t* n_drop,
+                    int32_t* n_removed, int32_t* flags) {
+    slam_assoc_config ac; slam_map_config mc;
+    TRY(assoc_config(assoc_cfg, &ac));
+    TRY(map_config(map_cfg, &mc));
+    if (T < 0) return slam_internal_fail(SLAM_ERR_ARG, "T = %d is negative", T);
+    if (!cmds) return slam_internal_fail(SLAM_ERR_ARG, "cmds is NULL");
+    if (!meas || !count) return slam_internal_fail(SLAM_ERR_ARG, "meas or meas_count is NULL");
+    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
+    TickMsgs msgs;
+    msgs.init_log(meas, count, k_stride);
+    return manage_run(h, "slam_manage_run", ac, mc, cmd_each ? TickCmds::kEach : TickCmds::kShared, cmds, msgs, T, recs, n_match, n_new, n_drop, n_removed,
+                      flags);
+}
+
+int slam_manage_run_sim(slam_handle* h, const slam_assoc_config* assoc_cfg, const slam_map_config* map_cfg, int source, const float* cmds,
+                        int k_stride, int T, double* recs, int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* n_removed, int32_t* flags,
+                        const slam_sense_log* log) {
+    slam_assoc_config ac; slam_map_config mc;
+    TickCmds::Source csrc;
+    TRY(assoc_config(assoc_cfg, &ac));
+    TRY(map_config(map_cfg, &mc));
+    TRY(sim_run_source(source, cmds, &csrc));
+    if (T < 0) return slam_internal_fail(SLAM_ERR_ARG, "T = %d is negative", T);
+    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
+    TickMsgs msgs;
+    msgs.init_sim(log, k_stride);
+    return manage_run(h, "slam_manage_run_sim", ac, mc, csrc, cmds, msgs, T, recs, n_match, n_new, n_drop, n_removed, flags);
 }
 
 int slam_last_map_work(slam_handle* h, double* bytes, double* prune_ms, double* total_ms) {

@@ -188,27 +188,26 @@ int slam_map_merge(slam_handle* h, const slam_merge_config* cfg, double rec[16],
     return merge_now(h, c, nullptr, n_merged, rec);
 }
 
-int slam_manage_merge_run(slam_handle* h, const slam_assoc_config* assoc_cfg, const slam_map_config* map_cfg, const slam_merge_config* merge_cfg,
-                          const float* cmds, int cmd_each, const float* meas, const int32_t* count, int k_stride, int T, double* recs,
-                          int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* n_removed, int32_t* n_merged, int32_t* flags) {
-    slam_assoc_config ac; slam_map_config mc; slam_merge_config gc;
-    TRY(assoc_config(assoc_cfg, &ac));
-    TRY(map_config(map_cfg, &mc));
-    TRY(merge_config(merge_cfg, &gc));
-    if (T < 0) return slam_internal_fail(SLAM_ERR_ARG, "T = %d is negative", T);
-    if (!cmds) return slam_internal_fail(SLAM_ERR_ARG, "cmds is NULL");
-    if (!meas || !count) return slam_internal_fail(SLAM_ERR_ARG, "meas or meas_count is NULL");
-    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
-    TRY(run_enter(h, "slam_manage_merge_run", false, false, true));
+}  // extern "C"
+
+namespace {
+
+// slam_manage_merge_run and its _sim form once their arguments are in order: T ticks with the commands of `csrc` on the messages of `msgs`
+int manage_merge_run(slam_handle* h, const char* who, const slam_assoc_config& ac, const slam_map_config& mc, const slam_merge_config& gc,
+                     TickCmds::Source csrc, const float* cmds, TickMsgs& msgs, int T, double* recs, int32_t* n_match, int32_t* n_new, int32_t* n_drop,
+                     int32_t* n_removed, int32_t* n_merged, int32_t* flags) {
+    const int k_stride = msgs.k_stride;
+    TRY(run_enter(h, who, msgs.sim(), csrc == TickCmds::kNav, true));
     if (T == 0) return SLAM_OK;
     HIP_TRY(hipSetDevice(h->device));
-    const size_t B = (size_t)h->B, mrow = 3 * (size_t)k_stride * B;
+    const size_t B = (size_t)h->B;
     TickCmds tcmd;
-    TRY(tcmd.init(h, cmd_each ? TickCmds::kEach : TickCmds::kShared, cmds));
+    TRY(tcmd.init(h, csrc, cmds));
     // what a tick holds on the device: slam_manage_run's rows and the six of a merge
-    const double per_tick = (7.0 + kRows) * 4.0 * (double)B + tcmd.bytes_per_tick(h) + 4.0 * (double)mrow + 4.0 * (double)B;
+    const double per_tick = (7.0 + kRows) * 4.0 * (double)B + tcmd.bytes_per_tick(h) + msgs.bytes_per_tick(h, tcmd);
     const int chunk = slam_host::ticks_per_chunk(T, per_tick, slam_host::tick_log_budget());
     TRY(assoc_reserve(h, k_stride, (size_t)chunk));
+    TRY(msgs.reserve(h, tcmd, chunk));
     TRY(map_reserve(h, (size_t)chunk));
     TRY(merge_reserve(h, (size_t)chunk, false));
     TRY(map_track(h));
@@ -226,16 +225,19 @@ int slam_manage_merge_run(slam_handle* h, const slam_assoc_config* assoc_cfg, co
             TRY(tcmd.upload(h, t0, tc));
             HIP_TRY(hipMemsetAsync(mi, 0, sizeof(int32_t) * 2 * cb, h->stream));       // (n_removed of the ticks without a prune)
             HIP_TRY(hipMemsetAsync(gi, 0, sizeof(int32_t) * kRows * cb, h->stream));   // (and the rows of the ticks without a merge)
-            return upload_messages(h, meas + (size_t)t0 * mrow, count + (size_t)t0 * B, k_stride, (size_t)tc);
+            return msgs.upload(h, t0, tc);
         },
         [&](int t0, int t, auto mark) -> int {
-            const float *cmd, *d_each;
+            const float *cmd, *d_each, *dm;
+            const int32_t* dc;
             TRY(tcmd.select(h, t0, t, &cmd, &d_each));
+            TRY(msgs.produce(h, tcmd, t, cmd, d_each, &dm, &dc));
             const size_t o = (size_t)t * B;
-            TRY(assoc_launch(h, ac, cmd, d_each, h->inn.dmeas + (size_t)t * mrow, h->inn.dcount + o, k_stride, h->assoc.dmeas, h->assoc.dcount,
+            TRY(assoc_launch(h, ac, cmd, d_each, dm, dc, k_stride, h->assoc.dmeas, h->assoc.dcount,
                              h->inn.drec + (size_t)t * slam::kInnovRecLen,
                              {di + o, di + cb + o, di + 2 * cb + o, di + 3 * cb + o, di + 4 * cb + o, nullptr, nullptr, nullptr}));
             TRY(launch_step(h, cmd, 0, h->assoc.dmeas, h->assoc.dcount, k_stride, d_each));
+            TRY(msgs.commit(h, t));   // (before the merge, which can move the pose: the simulator's error is taken after the step)
             TRY(tally_now(h, mc, h->assoc.dmeas, h->assoc.dcount, k_stride, di + 3 * cb + o));
             // (the marked group of a tick without a merge is empty: its event pair brackets nothing)
             TRY(mark([&]() -> int { return merges_after(t0 + t) ? merge_launches(h, gc, nullptr, gi + o, cb, false) : SLAM_OK; }));
@@ -243,6 +245,7 @@ int slam_manage_merge_run(slam_handle* h, const slam_assoc_config* assoc_cfg, co
         },
         [&](int t0, int tc) -> int {
             const size_t nb = sizeof(int32_t) * (size_t)tc * B, o = (size_t)t0 * B;
+            TRY(msgs.download(h, tcmd, t0, tc));
             for (int t = 0; t < tc; ++t) {             // (after the chunk's events: the models are no part of the run's times)
                 const size_t ot = (size_t)t * B;
                 if (merges_after(t0 + t)) TRY(merge_sum_work(h, gi + kMBefore * cb + ot, gi + ot, cb, true));
@@ -260,6 +263,44 @@ int slam_manage_merge_run(slam_handle* h, const slam_assoc_config* assoc_cfg, co
     TRY(rc);
     HIP_TRY(hipStreamSynchronize(h->stream));
     return SLAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int slam_manage_merge_run(slam_handle* h, const slam_assoc_config* assoc_cfg, const slam_map_config* map_cfg, const slam_merge_config* merge_cfg,
+                          const float* cmds, int cmd_each, const float* meas, const int32_t* count, int k_stride, int T, double* recs,
+                          int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* n_removed, int32_t* n_merged, int32_t* flags) {
+    slam_assoc_config ac; slam_map_config mc; slam_merge_config gc;
+    TRY(assoc_config(assoc_cfg, &ac));
+    TRY(map_config(map_cfg, &mc));
+    TRY(merge_config(merge_cfg, &gc));
+    if (T < 0) return slam_internal_fail(SLAM_ERR_ARG, "T = %d is negative", T);
+    if (!cmds) return slam_internal_fail(SLAM_ERR_ARG, "cmds is NULL");
+    if (!meas || !count) return slam_internal_fail(SLAM_ERR_ARG, "meas or meas_count is NULL");
+    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
+    TickMsgs msgs;
+    msgs.init_log(meas, count, k_stride);
+    return manage_merge_run(h, "slam_manage_merge_run", ac, mc, gc, cmd_each ? TickCmds::kEach : TickCmds::kShared, cmds, msgs, T, recs, n_match, n_new,
+                            n_drop, n_removed, n_merged, flags);
+}
+
+int slam_manage_merge_run_sim(slam_handle* h, const slam_assoc_config* assoc_cfg, const slam_map_config* map_cfg,
+                              const slam_merge_config* merge_cfg, int source, const float* cmds, int k_stride, int T, double* recs,
+                              int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* n_removed, int32_t* n_merged, int32_t* flags,
+                              const slam_sense_log* log) {
+    slam_assoc_config ac; slam_map_config mc; slam_merge_config gc;
+    TickCmds::Source csrc;
+    TRY(assoc_config(assoc_cfg, &ac));
+    TRY(map_config(map_cfg, &mc));
+    TRY(merge_config(merge_cfg, &gc));
+    TRY(sim_run_source(source, cmds, &csrc));
+    if (T < 0) return slam_internal_fail(SLAM_ERR_ARG, "T = %d is negative", T);
+    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
+    TickMsgs msgs;
+    msgs.init_sim(log, k_stride);
+    return manage_merge_run(h, "slam_manage_merge_run_sim", ac, mc, gc, csrc, cmds, msgs, T, recs, n_match, n_new, n_drop, n_removed, n_merged, flags);
 }
 
 int slam_last_merge_work(slam_handle* h, double* bytes, double* merge_ms, double* total_ms) {

@@ -93,15 +93,16 @@ int nav_launch(slam_handle* h, slam::NavParams& p) {
     return SLAM_OK;
 }
 
-int run_enter(slam_handle* h, const char* who, bool need_map, bool need_path, bool ekf_known_ids) {
+int run_enter(slam_handle* h, const char* who, bool runs_simulator, bool need_path, bool ekf_known_ids) {
     if (!h) return slam_internal_fail(SLAM_ERR_ARG, "%s: NULL handle", who);
     if (ekf_known_ids) TRY(innovation_supported(h));
     if (!h->inited) return slam_internal_fail(SLAM_ERR_STATE, "%s: slam_init has not been called", who);
-    if (need_map && !has_map(h)) return slam_internal_fail(SLAM_ERR_STATE, "%s runs the simulator: slam_set_map (or slam_set_maps) has not been called", who);
+    if (runs_simulator && !has_map(h)) return slam_internal_fail(SLAM_ERR_STATE, "%s runs the simulator: slam_set_map (or slam_set_maps) has not been called", who);
     if (need_path && !h->nav.set) return slam_internal_fail(SLAM_ERR_STATE, "%s: no path: call slam_nav_set_path or slam_nav_set_paths first", who);
     if (h->shadow) return slam_internal_fail(SLAM_ERR_STATE, "slam_track_instance is on: %s does not drive the shadow filter", who);
     // (checked before the first launch: a controller tick would overwrite the commands the pending update stage reads)
     if (h->ukf.predicted) return slam_internal_fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev before %s", who);
+    if (runs_simulator) TRY(sense_idle(h, who));   // (the truth it would advance is staged)
     return flush_lazy(h);
 }
 

@@ -1,6 +1,6 @@
 // capi_run.h — what the per-tick runs (slam_nav_run, slam_monitor_run, slam_innovation_run, slam_gate_run) share: the checks at entry, the
-// chunked driver, the source of a tick's command and the slam_last_*_work readers.  Defined in capi_nav.cpp, except the template and TickCmds (here)
-// and innovation_supported (capi_innovation.cpp).  Internal, like slam_handle.h.
+// chunked driver, the source of a tick's command, the source of a tick's message and the slam_last_*_work readers.  Defined in capi_nav.cpp,
+// except the template and TickCmds (here), innovation_supported (capi_innovation.cpp) and TickMsgs (capi_sense.cpp).  Internal, like slam_handle.h.
 #pragma once
 #include <string.h>
 
@@ -19,8 +19,10 @@ int nav_launch(slam_handle* h, slam::NavParams& p);
 int innovation_supported(const slam_handle* h);
 
 // What a per-tick run `who` checks once its own arguments are in order: the handle, then its state, then the queued timesteps run.
-// ekf_known_ids: the run evaluates innovations (innovation_supported).
-int run_enter(slam_handle* h, const char* who, bool need_map, bool need_path, bool ekf_known_ids);
+// runs_simulator: the run advances the simulator's truth (its step generates the message, or the sensor model does): it needs a true map
+// and no sense waiting for its commit.  need_path: the controller issues the commands.  ekf_known_ids: the run evaluates innovations
+// (innovation_supported).
+int run_enter(slam_handle* h, const char* who, bool runs_simulator, bool need_path, bool ekf_known_ids);
 
 // T ticks in chunks of `chunk`.  Per chunk: before(t0, tc) enqueues the uploads of ticks [t0, t0 + tc); tick(t0, t, mark) enqueues the
 // launches of tick t0 + t and passes the one launch group whose time is wanted through mark(launch); then the stream is synchronised and
@@ -86,6 +88,40 @@ struct TickCmds {
         return SLAM_OK;
     }
 };
+
+// Where the message of a tick comes from, for the runs that step on host-fed messages (slam_gate_run, slam_associate_run,
+// slam_associate_joint_run, slam_manage_run, slam_manage_merge_run and their _sim forms).  kLog: the host arrays meas [T][B][k_stride][3] and
+// count [T][B], the rows of a chunk uploaded before its ticks.  kSim: the sensor model (sense_kernel.h) writes the tick's message on the
+// device from the tick's command, the commit follows the tick's step launch, and the rows the caller's slam_sense_log asks for are held
+// per chunk and copied out after it.  Defined in capi_sense.cpp.
+struct TickMsgs {
+    enum Source { kLog, kSim } src;
+    const float* meas; const int32_t* count;   // kLog
+    slam_sense_log log;                        // kSim: what is wanted (all NULL: nothing)
+    int k_stride; int chunk;
+
+    void init_log(const float* host_meas, const int32_t* host_count, int ks) {
+        src = kLog; meas = host_meas; count = host_count; k_stride = ks; chunk = 0;
+        memset(&log, 0, sizeof(log));
+    }
+    void init_sim(const slam_sense_log* want, int ks) {
+        src = kSim; meas = nullptr; count = nullptr; k_stride = ks; chunk = 0;
+        memset(&log, 0, sizeof(log));
+        if (want) log = *want;
+    }
+    bool sim() const { return src == kSim; }
+    double bytes_per_tick(const slam_handle* h, const TickCmds& tcmd) const;   // on the device
+    int reserve(slam_handle* h, const TickCmds& tcmd, int ticks);  // once the chunk length is known
+    int upload(slam_handle* h, int t0, int tc) const;              // before(): kLog uploads the chunk's messages
+    // tick t of the chunk, after TickCmds::select: the device message the tick's launches read (kSim: the sense launch comes first)
+    int produce(slam_handle* h, const TickCmds& tcmd, int t, const float cmd[2], const float* d_each, const float** d_meas,
+                const int32_t** d_count);
+    int commit(slam_handle* h, int t);                             // right after the tick's step launch (kLog: nothing)
+    int download(slam_handle* h, const TickCmds& tcmd, int t0, int tc) const;   // after(): the logged rows of the chunk
+};
+
+// the `source` argument of a *_run_sim call as a TickCmds source; LOG and unknown values are SLAM_ERR_ARG
+int sim_run_source(int source, const float* cmds, TickCmds::Source* out);
 
 }  // namespace slam_capi
 #pragma GCC visibility pop

@@ -180,6 +180,7 @@ int slam_save_state(slam_handle* h, const char* path) {
     if (!h || !path) return slam_internal_fail(SLAM_ERR_ARG, "bad argument");
     TRY(flush_lazy(h));
     if (h->ukf.predicted) return slam_internal_fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev first");
+    TRY(sense_idle(h, "slam_save_state"));
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(h->kind == SLAM_EKF_SLAM ? hipStreamSynchronize(h->stream) : hipDeviceSynchronize());
     FILE* f = fopen(path, "wb");
@@ -249,6 +250,7 @@ int slam_load_state(slam_handle* h, const char* path) {
     fclose(f);
     h->step = hd.step; h->inited = hd.inited != 0; h->seed = hd.seed; h->inst0 = hd.inst0;
     h->ukf.predicted = false;
+    h->sense.pending = false;
     TRY(map_track_reset(h));   // (the counters are no part of a checkpoint)
     if (h->shadow) {   // the tracked instance restarts from the loaded state
         const int tr = h->tracked;

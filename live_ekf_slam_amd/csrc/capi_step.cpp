@@ -474,6 +474,7 @@ int slam_step_sim(slam_handle* h, const float cmd[2]) {
     if (!h || !cmd) return slam_internal_fail(SLAM_ERR_ARG, "bad argument");
     if (!h->inited) return slam_internal_fail(SLAM_ERR_STATE, "slam_init has not been called");
     if (!has_map(h)) return slam_internal_fail(SLAM_ERR_STATE, "slam_set_map has not been called");
+    TRY(sense_idle(h, "slam_step_sim"));
     if (h->shadow) { const int rs = slam_step_sim(h->shadow, cmd); if (rs) return rs; }
     if (h->kind == SLAM_EKF_SLAM && h->lazy_max > 1 && !h->dump_meas && h->run_chunk != 1) {
         StepQueue& q = h->q;
@@ -504,6 +505,7 @@ int slam_run_sim(slam_handle* h, const float* cmds, int T) {
     if (!h || !cmds || T < 0) return slam_internal_fail(SLAM_ERR_ARG, "bad argument");
     if (!h->inited) return slam_internal_fail(SLAM_ERR_STATE, "slam_init has not been called");
     if (!has_map(h)) return slam_internal_fail(SLAM_ERR_STATE, "slam_set_map has not been called");
+    TRY(sense_idle(h, "slam_run_sim"));
     if (h->shadow) { const int rs = slam_run_sim(h->shadow, cmds, T); if (rs) return rs; }
     TRY(flush_lazy(h));
     return run_sim_now(h, cmds, T);
@@ -604,6 +606,7 @@ int slam_run_sim_each(slam_handle* h, const float* cmds, int T) {
     if (!h || !cmds || T < 0) return slam_internal_fail(SLAM_ERR_ARG, "bad argument");
     if (!h->inited) return slam_internal_fail(SLAM_ERR_STATE, "slam_init has not been called");
     if (!has_map(h)) return slam_internal_fail(SLAM_ERR_STATE, "slam_set_map has not been called");
+    TRY(sense_idle(h, "slam_run_sim_each"));
     if (h->shadow && T > 0) {   // the tracked instance's column of the commands
         std::vector<float> mine(2 * (size_t)T);
         for (size_t t = 0; t < (size_t)T; ++t) {

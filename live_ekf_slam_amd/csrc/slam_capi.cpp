@@ -241,6 +241,7 @@ int slam_init(slam_handle* h, float x0, float y0, float yaw0) {
     }
     h->step = 0;
     h->inited = true;
+    h->sense.pending = false;
     TRY(nav_reset(h));
     TRY(map_track_reset(h));
     if (h->shadow) return slam_init(h->shadow, x0, y0, yaw0);
@@ -310,6 +311,7 @@ int slam_init_each(slam_handle* h, const float* pose0, const double* truth0) {
     HIP_TRY(hipStreamSynchronize(h->stream));   // (the host vector of the UKF is staged; the buffers are free for the next call)
     h->step = 0;
     h->inited = true;
+    h->sense.pending = false;
     TRY(nav_reset(h));
     TRY(map_track_reset(h));
     if (h->shadow) return slam_init_each(h->shadow, pose0 + 3 * (size_t)h->tracked, truth0 ? truth0 + 3 * (size_t)h->tracked : nullptr);

@@ -1,6 +1,6 @@
 // slam_handle.h — the handle of the filter ABI (include/slam_batch.h) and the host helpers that more than one of its translation units
 // uses (slam_capi.cpp: create / configure / init; capi_step.cpp: the steps and their queue; capi_state.cpp: reading the state back;
-// capi_consistency.cpp, capi_nav.cpp, capi_monitor.cpp, capi_innovation.cpp, capi_gate.cpp, capi_assoc.cpp, capi_joint.cpp, capi_map.cpp, capi_merge.cpp: one feature each).  Not installed, not part
+// capi_consistency.cpp, capi_nav.cpp, capi_monitor.cpp, capi_innovation.cpp, capi_gate.cpp, capi_assoc.cpp, capi_joint.cpp, capi_map.cpp, capi_merge.cpp, capi_sense.cpp: one feature each).  Not installed, not part
 // of the ABI: the standing of capi_internal.h.
 #pragma once
 #include "../../include/slam_batch.h"
@@ -197,6 +197,16 @@ struct slam_handle {
         bool work_set = false;
         slam_capi::RunTimes times;
     } merge;
+    // slam_sense_* and the *_run_sim calls: the [B] sensor rows (rows_set: the kernels read them), the staged true poses [B][3] and the
+    // timesteps they were staged at [B], the per-instance records [B][16] with their partial records and the record; pending: a sense
+    // waits for its commit, made at RNG step pending_step.  The staged message and labels of slam_sense, and of one chunk of ticks of a
+    // run: meas, count, origin, fault, the logged truth, position errors, commands and records.
+    struct Sense {
+        DevBuf<slam_sensor> drows; bool rows_set = false;
+        DevBuf<double> dnext, dinst, dpart, drec; DevBuf<int32_t> dstaged;
+        bool pending = false; uint32_t pending_step = 0;
+        DevBuf<float> dmeas, dcmd; DevBuf<int32_t> dcount, dorigin, dfault; DevBuf<double> dtruth, derrpos, drecs;
+    } sense;
 };
 
 #pragma GCC visibility push(hidden)
@@ -218,6 +228,12 @@ constexpr float kNoCmd[2] = {0.f, 0.f};   // the shared command of a launch whos
 
 // slam_set_map or slam_set_maps has given the simulator a true map (inline: every per-tick call asks)
 inline bool has_map(const slam_handle* h) { return h->dmap || h->each.maps_each; }
+
+// no slam_sense waits for its slam_sense_commit (checked where a pending prediction stage is): the simulator's truth is staged, so nothing
+// else may run the simulator or write a checkpoint
+inline int sense_idle(const slam_handle* h, const char* who) {
+    return h->sense.pending ? slam_internal_fail(SLAM_ERR_STATE, "a sense is pending: call slam_sense_commit before %s", who) : SLAM_OK;
+}
 
 // ---- capi_step.cpp (the functions without a comment here carry it at their definition)
 // Every EKF step launch: T = 0 is one timestep with `cmd`; T > 0 is a multi-step launch over the device commands d_cmds, whose first

@@ -22,6 +22,7 @@ from .config import AssocConfig, default_assoc_config
 from .config import JointConfig, default_joint_config
 from .config import MapConfig, default_map_config, MAP_CONFIG_FIELDS
 from .config import MergeConfig, default_merge_config, MERGE_CONFIG_FIELDS
+from .config import SensorConfig, SenseLog, default_sensor_config
 
 
 def _d(a):
@@ -1248,6 +1249,208 @@ class BatchedEKF(BatchedFilter):
         self._need(); by = C.c_double(0); a = C.c_double(0); b = C.c_double(0)
         _lib.check(_lib.lib().slam_last_merge_work(self.h, C.byref(by), C.byref(a), C.byref(b)))
         return by.value, a.value, b.value
+
+    # -- the simulator source with a sensor fault model (slam_sense_*, the *_run_sim calls; include/slam_batch.h) --
+    def set_sensor(self, rows):
+        """The sensor fault model of sense() and the *_run_sim calls (slam_set_sensor_each): one SensorConfig (or a dict of its fields),
+        replicated over the batch, or `batch` of them (a sequence or a ctypes array); None returns to the all-off row.  Inputs, not state:
+        set them again after load_state."""
+        self._need()
+        if rows is None:
+            _lib.check(_lib.lib().slam_set_sensor_each(self.h, None))
+            return
+        if isinstance(rows, dict):
+            rows = default_sensor_config(**rows)
+        if isinstance(rows, SensorConfig):
+            rows = [rows] * self.batch
+        if not (isinstance(rows, C.Array) and rows._type_ is SensorConfig):
+            rows = (SensorConfig * len(rows))(*rows)
+        if len(rows) != self.batch:
+            raise ValueError(f"expected {self.batch} sensor rows, got {len(rows)}")
+        _lib.check(_lib.lib().slam_set_sensor_each(self.h, rows))
+
+    def sense(self, cmdMsg, k_stride, labels=True, stats=True):
+        """One tick of the sensor model for the command the step will be given (one command or (batch, 2)): dict(meas (batch, k_stride, 3),
+        count [batch], truth_next (batch, 3), and with labels origin and fault (batch, k_stride), with stats rec (16,)).  The truth is
+        staged: step on the message (update_dev, step_gated_dev, ... or update) and then call sense_commit()."""
+        self._need()
+        cmd = self._cmd(cmdMsg)
+        B, ks = self.batch, int(k_stride)
+        out = dict(meas=np.zeros((B, max(ks, 0), 3), dtype=np.float32), count=np.zeros(B, dtype=np.int32), truth_next=np.zeros((B, 3)))
+        if labels:
+            out["origin"], out["fault"] = np.zeros((B, max(ks, 0)), dtype=np.int32), np.zeros((B, max(ks, 0)), dtype=np.int32)
+        if stats:
+            out["rec"] = np.zeros(16)
+        _lib.check(_lib.lib().slam_sense(self.h, _f(cmd), int(cmd.ndim == 2), _f(out["meas"]), _i(out["count"]), ks,
+                                         _i(out["origin"]) if labels else None, _i(out["fault"]) if labels else None, _d(out["truth_next"]),
+                                         _d(out["rec"]) if stats else None))
+        return out
+
+    def sense_dev(self, cmdMsg, d_meas_ptr, d_count_ptr, k_stride, d_origin_ptr=None, d_fault_ptr=None):
+        """sense() into DEVICE buffers, in the order of the handle's stream; cmdMsg one command (host) or, as an int, the device pointer
+        of (batch, 2) commands.  Does not synchronise."""
+        self._need()
+        each = isinstance(cmdMsg, int)
+        cmd = None if each else self._cmd(cmdMsg)
+        if cmd is not None and cmd.ndim != 1:
+            raise ValueError("sense_dev takes one command, or the device pointer of per-instance commands")
+        cp = C.c_void_p(cmdMsg) if each else C.cast(_f(cmd), C.c_void_p)
+        _lib.check(_lib.lib().slam_sense_dev(self.h, cp, int(each), C.c_void_p(d_meas_ptr), C.c_void_p(d_count_ptr), int(k_stride),
+                                             C.c_void_p(d_origin_ptr) if d_origin_ptr else None, C.c_void_p(d_fault_ptr) if d_fault_ptr else None))
+
+    def sense_commit(self, stats=True):
+        """After the step on the sensed message: the staged truth becomes the truth of every instance that advanced by one timestep, and
+        its position error is added.  stats=True returns the tick's record (16,) and synchronises; stats=False returns None."""
+        self._need()
+        rec = np.zeros(16) if stats else None
+        _lib.check(_lib.lib().slam_sense_commit(self.h, _d(rec) if stats else None))
+        return rec
+
+    def _sim_run(self, name, cmds, T, source, k_stride, log):
+        """The shared arguments of the *_run_sim calls: (float32 commands or None, source, T, k_stride, SenseLogResult or None, its struct)."""
+        self._need()
+        c32, want, T = self._run_cmds(name, cmds, T)
+        if c32 is None:
+            source = want if source is None else source
+        elif source is not None and source != want:
+            raise ValueError(f"source {source} does not match commands of shape {c32.shape}")
+        else:
+            source = want
+        ks, n = int(k_stride), max(T, 0)
+        sense = SenseLogResult(n, self.batch, max(ks, 1), log) if log else None
+        return c32, int(source), T, ks, sense, (C.byref(sense.struct()) if log and n > 0 else None)
+
+    def gate_run_sim(self, cmds=None, T=None, source=None, series=False, log=False, k_stride=16, cfg=None):
+        """gate_run with the simulator and the sensor model of set_sensor as its source: cmds (T, 2) shared, (T, batch, 2) per instance,
+        None with T ticks the controller of set_path (source INNOVATION_NAV).  Returns a GateResult whose `.sense` is None or, with
+        log=True, a SenseLogResult (meas, count, origin, fault, truth, err_pos, cmds, recs of every tick); log may also name the wanted
+        arrays, e.g. ("origin", "err_pos"): the others are not held on the device or copied."""
+        c32, source, T, ks, sense, lp = self._sim_run("gate_run_sim", cmds, T, source, k_stride, log)
+        n = max(T, 0)
+        res = GateResult(np.zeros((n, 16)))
+        if series:
+            res.nis_sum = np.zeros((n, self.batch))
+            res.n_upd, res.n_rej, res.flags = (np.zeros((n, self.batch), dtype=np.int32) for _ in range(3))
+        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
+        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
+        _lib.check(_lib.lib().slam_gate_run_sim(self.h, C.byref(self._gate_config(cfg)), source, None if c32 is None else _f(c32), ks, T,
+                                                pd(res.recs), pd(res.nis_sum), pi(res.n_upd), pi(res.n_rej), pi(res.flags), lp))
+        self.timestep += n
+        res.sense = sense
+        return res
+
+    def associate_run_sim(self, cmds=None, T=None, source=None, series=False, log=False, k_stride=16, cfg=None):
+        """associate_run with the simulator and the sensor model as its source (arguments and `.sense` as gate_run_sim)."""
+        c32, source, T, ks, sense, lp = self._sim_run("associate_run_sim", cmds, T, source, k_stride, log)
+        n = max(T, 0)
+        res = AssocResult(np.zeros((n, 16)))
+        if series:
+            res.n_match, res.n_new, res.n_drop, res.flags = (np.zeros((n, self.batch), dtype=np.int32) for _ in range(4))
+        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
+        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
+        _lib.check(_lib.lib().slam_associate_run_sim(self.h, C.byref(self._assoc_config(cfg)), source, None if c32 is None else _f(c32), ks, T,
+                                                     pd(res.recs), pi(res.n_match), pi(res.n_new), pi(res.n_drop), pi(res.flags), lp))
+        self.timestep += n
+        res.sense = sense
+        return res
+
+    def associate_joint_run_sim(self, cmds=None, T=None, source=None, series=False, log=False, k_stride=16, cfg=None):
+        """associate_joint_run with the simulator and the sensor model as its source (arguments and `.sense` as gate_run_sim)."""
+        c32, source, T, ks, sense, lp = self._sim_run("associate_joint_run_sim", cmds, T, source, k_stride, log)
+        n = max(T, 0)
+        res = JointResult(np.zeros((n, 16)))
+        if series:
+            res.n_match, res.n_new, res.n_drop, res.flags, res.nodes = (np.zeros((n, self.batch), dtype=np.int32) for _ in range(5))
+            res.d2_joint = np.zeros((n, self.batch))
+        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
+        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
+        _lib.check(_lib.lib().slam_associate_joint_run_sim(self.h, C.byref(self._joint_config(cfg)), source, None if c32 is None else _f(c32), ks, T,
+                                                           pd(res.recs), pi(res.n_match), pi(res.n_new), pi(res.n_drop), pi(res.flags),
+                                                           pd(res.d2_joint), pi(res.nodes), lp))
+        self.timestep += n
+        res.sense = sense
+        return res
+
+    def manage_run_sim(self, cmds=None, T=None, source=None, series=False, log=False, k_stride=16, cfg=None, map_cfg=None):
+        """manage_run with the simulator and the sensor model as its source (arguments and `.sense` as gate_run_sim)."""
+        c32, source, T, ks, sense, lp = self._sim_run("manage_run_sim", cmds, T, source, k_stride, log)
+        n = max(T, 0)
+        res = MapResult(np.zeros((n, 16)))
+        if series:
+            res.n_match, res.n_new, res.n_drop, res.flags, res.n_removed = (np.zeros((n, self.batch), dtype=np.int32) for _ in range(5))
+        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
+        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
+        _lib.check(_lib.lib().slam_manage_run_sim(self.h, C.byref(self._assoc_config(cfg)), C.byref(self._map_config(map_cfg)), source,
+                                                  None if c32 is None else _f(c32), ks, T, pd(res.recs), pi(res.n_match), pi(res.n_new),
+                                                  pi(res.n_drop), pi(res.n_removed), pi(res.flags), lp))
+        self.timestep += n
+        res.sense = sense
+        return res
+
+    def manage_merge_run_sim(self, cmds=None, T=None, source=None, series=False, log=False, k_stride=16, cfg=None, map_cfg=None, merge_cfg=None):
+        """manage_merge_run with the simulator and the sensor model as its source (arguments and `.sense` as gate_run_sim)."""
+        c32, source, T, ks, sense, lp = self._sim_run("manage_merge_run_sim", cmds, T, source, k_stride, log)
+        n = max(T, 0)
+        res = MergeResult(np.zeros((n, 16)))
+        if series:
+            res.n_match, res.n_new, res.n_drop, res.flags, res.n_removed, res.n_merged = (np.zeros((n, self.batch), dtype=np.int32) for _ in range(6))
+        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
+        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
+        _lib.check(_lib.lib().slam_manage_merge_run_sim(self.h, C.byref(self._assoc_config(cfg)), C.byref(self._map_config(map_cfg)),
+                                                        C.byref(self._merge_config(merge_cfg)), source, None if c32 is None else _f(c32), ks, T,
+                                                        pd(res.recs), pi(res.n_match), pi(res.n_new), pi(res.n_drop), pi(res.n_removed),
+                                                        pi(res.n_merged), pi(res.flags), lp))
+        self.timestep += n
+        res.sense = sense
+        return res
+
+
+class SenseLogResult:
+    """The `.sense` of a *_run_sim result with log=True: meas (T, batch, k_stride, 3) and count (T, batch), the messages as emitted, before
+    the run's own filtering; origin and fault (T, batch, k_stride), the true map row (-1: clutter or no detection) and 1 where spiked; truth
+    (T, batch, 3) after each tick's commit; err_pos (T, batch), the position error the commit added (NaN where not committed); cmds
+    (T, batch, 2), what the step was given; recs (T, 16), the sense records (columns: the REC_* constants)."""
+
+    (REC_N_SENSED, REC_N_FROZEN, REC_N_TOO_LONG, REC_N_CLEAN, REC_N_MISSED, REC_N_SPIKED, REC_N_CLUTTER, REC_SUM_OUT, REC_SUM_OVERFLOW,
+     REC_SUM_SPIKE, REC_N_COMMITTED, REC_SUM_ERR_POS) = range(12)
+
+    NAMES = ("meas", "count", "origin", "fault", "truth", "err_pos", "cmds", "recs")
+
+    def __init__(self, T, batch, k_stride, names=True):
+        """names: True for every array, or the names of the wanted ones (the others stay None and cost nothing)."""
+        shapes = dict(meas=((T, batch, k_stride, 3), np.float32), count=((T, batch), np.int32), origin=((T, batch, k_stride), np.int32),
+                      fault=((T, batch, k_stride), np.int32), truth=((T, batch, 3), np.float64), err_pos=((T, batch), np.float64),
+                      cmds=((T, batch, 2), np.float32), recs=((T, 16), np.float64))
+        want = self.NAMES if names is True else tuple(names)
+        for n in want:
+            if n not in shapes:
+                raise ValueError(f"unknown log array {n!r}: expected some of {self.NAMES}")
+        for n, (shape, dt) in shapes.items():
+            setattr(self, n, np.zeros(shape, dtype=dt) if n in want else None)
+
+    def struct(self):
+        cast = dict(meas=_f, cmds=_f, count=_i, origin=_i, fault=_i, truth=_d, err_pos=_d, recs=_d)
+        return SenseLog(*[None if getattr(self, n) is None else cast[n](getattr(self, n)) for n in self.NAMES])
+
+
+def sense_instance_host(seed, instance, step, truth, cmd, map_xy, cfg, vision=(3.0, -1.57, 1.57), sim_noise=None, row=None, k_stride=16, status=0):
+    """TEST HOOK (slam_sense_instance_host): the sensor model of one instance compiled for the host; no GPU.  cfg: the SlamConfig (d_max,
+    th_max and, without sim_noise, the simulator's half-widths V_00, V_11, W_00, W_11); vision: (range_max, fov_min, fov_max).  Returns
+    dict(meas (k_stride, 3), count, origin, fault (k_stride,), truth_next (3,), flags, rec (16,))."""
+    truth = np.ascontiguousarray(truth, dtype=np.float64)
+    c = np.ascontiguousarray(cmd, dtype=np.float32)
+    m = np.ascontiguousarray(map_xy, dtype=np.float64).reshape(-1, 2)
+    sn = np.ascontiguousarray((cfg.V_00, cfg.V_11, cfg.W_00, cfg.W_11) if sim_noise is None else sim_noise, dtype=np.float64)
+    ks = int(k_stride)
+    out = dict(meas=np.zeros((max(ks, 0), 3), dtype=np.float32), origin=np.zeros(max(ks, 0), dtype=np.int32), fault=np.zeros(max(ks, 0), dtype=np.int32),
+               truth_next=np.zeros(3), rec=np.zeros(16))
+    count, flags = C.c_int32(0), C.c_int32(0)
+    _lib.check(_lib.lib().slam_sense_instance_host(int(seed), int(instance), int(step), _d(truth), _f(c), int(status), _d(m), m.shape[0],
+                                                   float(cfg.d_max), float(cfg.th_max), float(vision[0]), float(vision[1]), float(vision[2]), _d(sn),
+                                                   None if row is None else C.byref(row), ks, _f(out["meas"]), C.byref(count), _i(out["origin"]),
+                                                   _i(out["fault"]), _d(out["truth_next"]), C.byref(flags), _d(out["rec"])))
+    out["count"], out["flags"] = count.value, flags.value
+    return out
 
 
 def merge_instance_host(x, P, ids, L_max, status=0, f32_storage=False, cfg=None, seen=None, expected=None, partner=None, fuse=True):
