@@ -1,14 +1,13 @@
-// capi_innovation.cpp — C ABI: innovation (NIS) statistics of the message the next step will process (innovation_kernel.hip)
+// capi_innovation.cpp — C ABI: innovation (NIS) statistics of the message the next step will process (innovation_kernel.hip), and the
+// bodies of capi_filter.h
 #include <math.h>
 #include <string.h>
 
 #include <vector>
 
-#include "capi_innovation.h"
-#include "capi_run.h"
+#include "capi_filter.h"
 #include "ekf_kernel.h"
 #include "host/noise_pack.h"
-#include "host/tick_chunks.h"
 
 using namespace slam_capi;
 
@@ -66,14 +65,9 @@ int innovation_outputs(slam_handle* h, bool det, InnovOut* d) {
 int innovation_download(slam_handle* h, const InnovOut& d, const InnovOut& to) {
     const size_t B = (size_t)h->B;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (to.rec) HIP_TRY(hipMemcpy(to.rec, d.rec, sizeof(double) * slam::kInnovRecLen, hipMemcpyDeviceToHost));
-    if (to.nis_sum) HIP_TRY(hipMemcpy(to.nis_sum, d.nis_sum, sizeof(double) * B, hipMemcpyDeviceToHost));
-    if (to.post) HIP_TRY(hipMemcpy(to.post, d.post, sizeof(double) * 12 * B, hipMemcpyDeviceToHost));
-    if (to.det) HIP_TRY(hipMemcpy(to.det, d.det, sizeof(double) * B * slam::kInnovMaxDet * slam::kInnovDetLen, hipMemcpyDeviceToHost));
-    if (to.n_upd) HIP_TRY(hipMemcpy(to.n_upd, d.n_upd, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
-    if (to.flags) HIP_TRY(hipMemcpy(to.flags, d.flags, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
-    if (to.n_new) HIP_TRY(hipMemcpy(to.n_new, d.n_new, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
-    return SLAM_OK;
+    return copy_rows({{d.rec, to.rec, slam::kInnovRecLen}, {d.nis_sum, to.nis_sum, B}, {d.post, to.post, 12 * B},
+                      {d.det, to.det, B * slam::kInnovMaxDet * slam::kInnovDetLen}, {d.n_upd, to.n_upd, B}, {d.flags, to.flags, B},
+                      {d.n_new, to.n_new, B}}, 0, 1);
 }
 
 int innovation_upload_cmds(slam_handle* h, const float* cmds, size_t n) {
@@ -88,6 +82,105 @@ int upload_messages(slam_handle* h, const float* meas, const int32_t* count, int
     TRY(grow(h, h->inn.dcount, nc));
     HIP_TRY(hipMemcpyAsync(h->inn.dmeas, meas, sizeof(float) * nm, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->inn.dcount, count, sizeof(int32_t) * nc, hipMemcpyHostToDevice, h->stream));
+    return SLAM_OK;
+}
+
+// ---- capi_filter.h --------------------------------------------------------------------------------------------------------------------------
+int copy_rows(const std::vector<TickRow>& rows, int t0, int tc) {
+    for (const TickRow& r : rows) {
+        const size_t tick = r.per_tick * r.elem_bytes;
+        if (r.host) HIP_TRY(hipMemcpy((char*)r.host + (size_t)t0 * tick, r.dev, (size_t)tc * tick, hipMemcpyDeviceToHost));
+    }
+    return SLAM_OK;
+}
+
+int message_args(const float* cmds, const void* meas, const void* count, int k_stride, const void* meas_out, const void* count_out, bool need_out) {
+    if (!cmds) return slam_internal_fail(SLAM_ERR_ARG, "cmds is NULL");
+    if (!meas || !count) return slam_internal_fail(SLAM_ERR_ARG, "meas or meas_count is NULL");
+    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
+    if (need_out && (!meas_out || !count_out)) return slam_internal_fail(SLAM_ERR_ARG, "d_meas_out or d_count_out is NULL");
+    if ((meas_out == meas) != (count_out == count))
+        return slam_internal_fail(SLAM_ERR_ARG, "in place means both: meas_out == meas and count_out == meas_count, or neither");
+    return SLAM_OK;
+}
+
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const char* const pa = (const char*)a; const char* const pb = (const char*)b;
+    return pa < pb + nb && pb < pa + na;
+}
+
+int out_message_overlaps(const slam_handle* h, const float* d_meas, const int32_t* d_count, int k_stride, DevMsg out) {
+    const size_t bm = sizeof(float) * 3 * (size_t)k_stride * h->B, bc = sizeof(int32_t) * (size_t)h->B;
+    if ((out.meas != d_meas && ranges_overlap(out.meas, bm, d_meas, bm)) || (out.count != d_count && ranges_overlap(out.count, bc, d_count, bc)) ||
+        ranges_overlap(out.meas, bm, d_count, bc) || ranges_overlap(out.count, bc, d_meas, bm) || ranges_overlap(out.meas, bm, out.count, bc))
+        return slam_internal_fail(SLAM_ERR_ARG, "the output message overlaps the input (only d_meas_out == d_meas with d_count_out == d_count is allowed) or itself");
+    return SLAM_OK;
+}
+
+int filter_enter(slam_handle* h, int (*supported)(const slam_handle*)) {
+    if (!h) return slam_internal_fail(SLAM_ERR_ARG, "NULL handle");
+    TRY(supported(h));
+    if (!h->inited) return slam_internal_fail(SLAM_ERR_STATE, "slam_init has not been called");
+    TRY(flush_lazy(h));
+    HIP_TRY(hipSetDevice(h->device));
+    return SLAM_OK;
+}
+
+int step_state(const slam_handle* h, const char* who) {
+    if (h->shadow) return slam_internal_fail(SLAM_ERR_STATE, "slam_track_instance is on: %s does not drive the shadow filter", who);
+    if (h->ukf.predicted) return slam_internal_fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev before %s", who);
+    return SLAM_OK;
+}
+
+int stage_message(slam_handle* h, bool host, const float* cmds, int cmd_each, const float** meas, const int32_t** count, int k_stride,
+                  const float** cmd, const float** d_each) {
+    *cmd = cmd_each ? kNoCmd : cmds; *d_each = cmd_each ? cmds : nullptr;
+    if (!host) return SLAM_OK;
+    TRY(upload_messages(h, *meas, *count, k_stride, 1));
+    if (cmd_each) TRY(innovation_upload_cmds(h, cmds, 2 * (size_t)h->B));
+    *meas = h->inn.dmeas; *count = h->inn.dcount;
+    if (cmd_each) *d_each = h->inn.dcmd;
+    return SLAM_OK;
+}
+
+int seed_out_message(slam_handle* h, float* d_meas_out, int k_stride) {
+    HIP_TRY(hipMemcpyAsync(d_meas_out, h->inn.dmeas, sizeof(float) * 3 * (size_t)k_stride * h->B, hipMemcpyDeviceToDevice, h->stream));
+    return SLAM_OK;
+}
+
+int step_outputs(slam_handle* h, double* rec, const int32_t* d_n, int32_t* n) {
+    if (!rec && !n) return SLAM_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return copy_rows({{h->inn.drec, rec, slam::kInnovRecLen}, {d_n, n, (size_t)h->B}}, 0, 1);
+}
+
+int run_args_log(const float* cmds, const float* meas, const int32_t* count, int k_stride, int T, TickMsgs* msgs) {
+    if (T < 0) return slam_internal_fail(SLAM_ERR_ARG, "T = %d is negative", T);
+    TRY(message_args(cmds, meas, count, k_stride));
+    msgs->init_log(meas, count, k_stride);
+    return SLAM_OK;
+}
+
+int run_args_sim(int source, const float* cmds, int k_stride, int T, const slam_sense_log* log, TickCmds::Source* csrc, TickMsgs* msgs) {
+    TRY(sim_run_source(source, cmds, csrc));
+    if (T < 0) return slam_internal_fail(SLAM_ERR_ARG, "T = %d is negative", T);
+    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
+    msgs->init_sim(log, k_stride);
+    return SLAM_OK;
+}
+
+int InstanceHostArgs::init(const double* x, const double* P, const int32_t* ids, int M, int L_max, const float cmd[2], const float* meas, int count,
+                           int k_stride, bool strided, const slam_noise* noise, int f32_storage) {
+    if (!x || !P || !cmd || !noise) return slam_internal_fail(SLAM_ERR_ARG, "NULL argument");
+    if (L_max < 0 || M < 0 || M > L_max) return slam_internal_fail(SLAM_ERR_ARG, "M = %d is not in [0, L_max = %d]", M, L_max);
+    if (M > 0 && !ids) return slam_internal_fail(SLAM_ERR_ARG, "ids is NULL");
+    if (strided && k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
+    if (strided && count > 0 && !meas) return slam_internal_fail(SLAM_ERR_ARG, "meas is NULL");
+    if (!strided && (count < 0 || (count > 0 && !meas))) return slam_internal_fail(SLAM_ERR_ARG, "k = %d is negative, or meas is NULL", count);
+    if (const char* f = slam_host::noise_bad_field(*noise)) return slam_internal_fail(SLAM_ERR_ARG, "noise: %s is not finite", f);
+    nz = {noise->v_d, noise->v_th, noise->w_r, noise->w_b, noise->V_00, noise->V_11, noise->W_00, noise->W_11};
+    load_x = {x, f32_storage != 0};
+    load_P = {P, 3 + 2 * M, f32_storage != 0};
     return SLAM_OK;
 }
 
@@ -106,19 +199,16 @@ int innovation_now(slam_handle* h, const slam_innovation_config& c, const float 
     return innovation_download(h, d, to);
 }
 
-// the checks slam_innovation and slam_innovation_dev share; the queued timesteps run first
-int innovation_enter(slam_handle* h, const slam_innovation_config* cfg, const float* cmds, const float* meas, const int32_t* count, int k_stride,
-                     slam_innovation_config* c) {
-    TRY(innovation_config(cfg, c));
-    if (!cmds) return slam_internal_fail(SLAM_ERR_ARG, "cmds is NULL");
-    if (!meas || !count) return slam_internal_fail(SLAM_ERR_ARG, "meas or meas_count is NULL");
-    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
-    if (!h) return slam_internal_fail(SLAM_ERR_ARG, "NULL handle");
-    TRY(innovation_supported(h));
-    if (!h->inited) return slam_internal_fail(SLAM_ERR_STATE, "slam_init has not been called");
-    TRY(flush_lazy(h));
-    HIP_TRY(hipSetDevice(h->device));
-    return SLAM_OK;
+// slam_innovation (host: the message and per-instance commands are host arrays) and slam_innovation_dev
+int innovation(slam_handle* h, bool host, const slam_innovation_config* cfg, const float* cmds, int cmd_each, const float* meas,
+               const int32_t* count, int k_stride, const InnovOut& to) {
+    slam_innovation_config c;
+    const float *cmd, *d_each;
+    TRY(innovation_config(cfg, &c));
+    TRY(message_args(cmds, meas, count, k_stride));
+    TRY(filter_enter(h, innovation_supported));
+    TRY(stage_message(h, host, cmds, cmd_each, &meas, &count, k_stride, &cmd, &d_each));
+    return innovation_now(h, c, cmd, d_each, meas, count, k_stride, to);
 }
 
 }  // namespace
@@ -134,21 +224,13 @@ int slam_innovation_config_default(slam_innovation_config* c) {
 
 int slam_innovation(slam_handle* h, const slam_innovation_config* cfg, const float* cmds, int cmd_each, const float* meas, const int32_t* count,
                     int k_stride, double rec[16], double* nis_sum, int32_t* n_upd, int32_t* n_new, int32_t* flags, double* det, double* post) {
-    slam_innovation_config c;
-    TRY(innovation_enter(h, cfg, cmds, meas, count, k_stride, &c));
-    TRY(upload_messages(h, meas, count, k_stride, 1));
-    if (cmd_each) TRY(innovation_upload_cmds(h, cmds, 2 * (size_t)h->B));
-    return innovation_now(h, c, cmd_each ? kNoCmd : cmds, cmd_each ? h->inn.dcmd.get() : nullptr, h->inn.dmeas, h->inn.dcount, k_stride,
-                          {rec, nis_sum, post, det, n_upd, flags, n_new});
+    return innovation(h, true, cfg, cmds, cmd_each, meas, count, k_stride, {rec, nis_sum, post, det, n_upd, flags, n_new});
 }
 
 int slam_innovation_dev(slam_handle* h, const slam_innovation_config* cfg, const float* cmds, int cmd_each, const float* d_meas,
                         const int32_t* d_count, int k_stride, double rec[16], double* nis_sum, int32_t* n_upd, int32_t* n_new, int32_t* flags,
                         double* det, double* post) {
-    slam_innovation_config c;
-    TRY(innovation_enter(h, cfg, cmds, d_meas, d_count, k_stride, &c));
-    return innovation_now(h, c, cmd_each ? kNoCmd : cmds, cmd_each ? cmds : nullptr, d_meas, d_count, k_stride,
-                          {rec, nis_sum, post, det, n_upd, flags, n_new});
+    return innovation(h, false, cfg, cmds, cmd_each, d_meas, d_count, k_stride, {rec, nis_sum, post, det, n_upd, flags, n_new});
 }
 
 int slam_innovation_run(slam_handle* h, const slam_innovation_config* cfg, int source, const float* cmds, const float* meas, const int32_t* count,
@@ -198,11 +280,7 @@ int slam_innovation_run(slam_handle* h, const slam_innovation_config* cfg, int s
             return launch_step(h, cmd, log ? 0 : 1, d_meas, d_count, log ? k_stride : 0, d_each);
         },
         [&](int t0, int tc) -> int {
-            if (recs) HIP_TRY(hipMemcpy(recs + (size_t)t0 * slam::kInnovRecLen, h->inn.drec, sizeof(double) * (size_t)tc * slam::kInnovRecLen, hipMemcpyDeviceToHost));
-            if (nis_sum) HIP_TRY(hipMemcpy(nis_sum + (size_t)t0 * B, h->inn.dlog, sizeof(double) * (size_t)tc * B, hipMemcpyDeviceToHost));
-            if (n_upd) HIP_TRY(hipMemcpy(n_upd + (size_t)t0 * B, d_upd, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
-            if (flags) HIP_TRY(hipMemcpy(flags + (size_t)t0 * B, d_flags, sizeof(int32_t) * (size_t)tc * B, hipMemcpyDeviceToHost));
-            return SLAM_OK;
+            return copy_rows({{h->inn.drec, recs, slam::kInnovRecLen}, {h->inn.dlog, nis_sum, B}, {d_upd, n_upd, B}, {d_flags, flags, B}}, t0, tc);
         });
 }
 
@@ -216,20 +294,12 @@ int slam_innovation_instance_host(const double* x, const double* P, const int32_
                                   int32_t* flags, double* det, double* post) {
     slam_innovation_config c;
     TRY(innovation_config(cfg, &c));
-    if (!x || !P || !cmd || !noise) return slam_internal_fail(SLAM_ERR_ARG, "NULL argument");
-    if (L_max < 0 || M < 0 || M > L_max) return slam_internal_fail(SLAM_ERR_ARG, "M = %d is not in [0, L_max = %d]", M, L_max);
-    if (M > 0 && !ids) return slam_internal_fail(SLAM_ERR_ARG, "ids is NULL");
-    if (k < 0 || (k > 0 && !meas)) return slam_internal_fail(SLAM_ERR_ARG, "k = %d is negative, or meas is NULL", k);
-    if (const char* f = slam_host::noise_bad_field(*noise)) return slam_internal_fail(SLAM_ERR_ARG, "noise: %s is not finite", f);
-    const slam::InnovNoise nz = {noise->v_d, noise->v_th, noise->w_r, noise->w_b, noise->V_00, noise->V_11, noise->W_00, noise->W_11};
-    const int n = 3 + 2 * M;
+    InstanceHostArgs a;
+    TRY(a.init(x, P, ids, M, L_max, cmd, meas, k, 0, false, noise, f32_storage));
     std::vector<slam::InnovWork> ws(1);
     for (int i = 0; i < 3 * (k < slam::kInnovMaxDet ? k : slam::kInnovMaxDet); ++i) ws[0].meas[i] = meas[i];
-    const bool f32 = f32_storage != 0;
-    const slam::InnovResult v = slam::innovation_instance(
-        slam::InnovSeq(), ws[0], [&](int i) { return f32 ? (double)(float)x[i] : x[i]; },
-        [&](int r, int cc) { const double e = P[(size_t)r * n + cc]; return f32 ? (double)(float)e : e; }, ids, M, L_max, status, cmd[0], cmd[1], k, nz,
-        lm_from_pred != 0, c.nis_lo, c.nis_hi, det);
+    const slam::InnovResult v = slam::innovation_instance(slam::InnovSeq(), ws[0], a.load_x, a.load_P, ids, M, L_max, status, cmd[0], cmd[1], k, a.nz,
+                                                          lm_from_pred != 0, c.nis_lo, c.nis_hi, det);
     if (rec) slam::innovation_record(v, rec);
     if (nis_sum) *nis_sum = v.nis_sum;
     if (n_upd) *n_upd = v.n_upd;

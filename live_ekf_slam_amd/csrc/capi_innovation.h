@@ -1,4 +1,5 @@
-// capi_innovation.h — the pieces of capi_innovation.cpp that the gate (capi_gate.cpp) evaluates and stages its messages with.  Internal.
+// capi_innovation.h — the pieces of capi_innovation.cpp that the gate (capi_gate.cpp) evaluates with, and the staging buffers every unit
+// over capi_filter.h uploads its messages and commands to.  Internal.
 #pragma once
 #include "innovation_kernel.h"
 #include "slam_handle.h"

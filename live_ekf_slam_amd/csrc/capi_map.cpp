@@ -7,12 +7,8 @@
 #include <vector>
 
 #include "assoc_kernel.h"
-#include "capi_assoc.h"
-#include "capi_innovation.h"
 #include "capi_map.h"
-#include "capi_run.h"
 #include "ekf_kernel.h"
-#include "host/tick_chunks.h"
 #include "map_kernel.h"
 
 using namespace slam_capi;
@@ -41,8 +37,7 @@ int map_enter(slam_handle* h, const char* who) {
     if (h->kind != SLAM_EKF_SLAM)
         return slam_internal_fail(SLAM_ERR_UNSUPPORTED, "%s needs EKF_SLAM: the UKF's stored square root, eigenvectors and ages would have to follow a removal", who);
     if (!h->inited) return slam_internal_fail(SLAM_ERR_STATE, "slam_init has not been called");
-    if (h->shadow) return slam_internal_fail(SLAM_ERR_STATE, "slam_track_instance is on: %s does not drive the shadow filter", who);
-    if (h->ukf.predicted) return slam_internal_fail(SLAM_ERR_STATE, "a prediction stage is pending: call slam_update_dev before %s", who);
+    TRY(step_state(h, who));
     TRY(flush_lazy(h));
     HIP_TRY(hipSetDevice(h->device));
     return SLAM_OK;
@@ -58,9 +53,9 @@ int map_track(slam_handle* h) {
     return map_track_reset(h);
 }
 
-// n_removed and the M before of `ticks` removals ([2][ticks][B]), the record, the sums of the traffic model, the per-instance contributions
+// the rows of `ticks` removals, the record, the sums of the traffic model, the per-instance contributions
 int map_reserve(slam_handle* h, size_t ticks) {
-    TRY(grow(h, h->map.dint, 2 * ticks * (size_t)h->B));
+    TRY(grow(h, h->map.dint, kMapRows * ticks * (size_t)h->B));
     TRY(grow(h, h->map.drec, slam::kMapRecLen));
     TRY(grow(h, h->map.dwork, 3));
     return innovation_reserve(h, false);
@@ -99,13 +94,11 @@ static int remove_now(slam_handle* h, const int32_t* d_remove, const slam_map_co
     TRY(map_reserve(h, 1));
     TRY(map_zero_work(h));
     int32_t* const di = h->map.dint;
-    TRY(map_compact_launch(h, d_remove, c, di, di + B, rec != nullptr));
-    TRY(map_sum_work(h, di, di + B, d_remove == nullptr));
+    TRY(map_compact_launch(h, d_remove, c, row(di, kMapRemoved, B), row(di, kMapMBefore, B), rec != nullptr));
+    TRY(map_sum_work(h, row(di, kMapRemoved, B), row(di, kMapMBefore, B), d_remove == nullptr));
     if (!n_removed && !rec) return SLAM_OK;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (n_removed) HIP_TRY(hipMemcpy(n_removed, di, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
-    if (rec) HIP_TRY(hipMemcpy(rec, h->map.drec, sizeof(double) * slam::kMapRecLen, hipMemcpyDeviceToHost));
-    return SLAM_OK;
+    return copy_rows({{row(di, kMapRemoved, B), n_removed, B}, {h->map.drec, rec, slam::kMapRecLen}}, 0, 1);
 }
 
 // the tally of one message that is on the device, on the handle's stream
@@ -129,26 +122,26 @@ static int tally_args(const slam_map_config* cfg, const float* meas, const int32
     return SLAM_OK;
 }
 
-// one managed timestep once the message and the commands are on the device
-static int step_managed_now(slam_handle* h, const slam_assoc_config& ac, const slam_map_config& mc, const float cmd[2], const float* d_cmd_each,
-                     const float* d_meas, const int32_t* d_count, int k_stride, double* rec, int32_t* n_drop) {
-    const size_t B = (size_t)h->B;
+// slam_step_managed (host: the message and per-instance commands are host arrays) and slam_step_managed_dev: one managed timestep
+static int step_managed(slam_handle* h, bool host, const slam_assoc_config* assoc_cfg, const slam_map_config* map_cfg, const float* cmds, int cmd_each,
+                        const float* meas, const int32_t* count, int k_stride, double* rec, int32_t* n_drop) {
+    slam_assoc_config ac; slam_map_config mc;
+    const float *cmd, *d_each;
+    TRY(assoc_config(assoc_cfg, &ac));
+    TRY(message_args(cmds, meas, count, k_stride));
+    TRY(map_config(map_cfg, &mc));
+    TRY(filter_enter(h, assoc_supported));
+    TRY(step_state(h, "a managed step"));
+    TRY(stage_message(h, host, cmds, cmd_each, &meas, &count, k_stride, &cmd, &d_each));
     TRY(assoc_reserve(h, k_stride, 1));
-    int32_t* const di = h->assoc.dint;
-    TRY(assoc_launch(h, ac, cmd, d_cmd_each, d_meas, d_count, k_stride, h->assoc.dmeas, h->assoc.dcount, h->inn.drec,
-                     {nullptr, nullptr, di + 2 * B, di + 3 * B, nullptr, nullptr, nullptr, nullptr}));
-    TRY(launch_step(h, cmd, 0, h->assoc.dmeas, h->assoc.dcount, k_stride, d_cmd_each));
-    TRY(tally_now(h, mc, h->assoc.dmeas, h->assoc.dcount, k_stride, di + 3 * B));
-    if (!rec && !n_drop) return SLAM_OK;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (rec) HIP_TRY(hipMemcpy(rec, h->inn.drec, sizeof(double) * slam::kInnovRecLen, hipMemcpyDeviceToHost));
-    if (n_drop) HIP_TRY(hipMemcpy(n_drop, di + 2 * B, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
-    return SLAM_OK;
-}
-
-int managed_enter(slam_handle* h, const char* who) {
-    TRY(assoc_enter(h));
-    return assoc_step_state(h, who);
+    const size_t B = (size_t)h->B;
+    int32_t* const d_drop = row(h->assoc.dint, kAssocDrop, B);
+    int32_t* const d_flags = row(h->assoc.dint, kAssocFlags, B);
+    TRY(assoc_launch(h, ac, cmd, d_each, meas, count, k_stride, h->assoc.dmeas, h->assoc.dcount, h->inn.drec,
+                     {nullptr, nullptr, d_drop, d_flags, nullptr, nullptr, nullptr, nullptr}));
+    TRY(launch_step(h, cmd, 0, h->assoc.dmeas, h->assoc.dcount, k_stride, d_each));
+    TRY(tally_now(h, mc, h->assoc.dmeas, h->assoc.dcount, k_stride, d_flags));
+    return step_outputs(h, rec, d_drop, n_drop);
 }
 
 int map_track_reset(slam_handle* h) {
@@ -239,110 +232,24 @@ int slam_map_track_reset(slam_handle* h) {
 
 int slam_step_managed(slam_handle* h, const slam_assoc_config* assoc_cfg, const slam_map_config* map_cfg, const float* cmds, int cmd_each,
                       const float* meas, const int32_t* count, int k_stride, double rec[16], int32_t* n_drop) {
-    slam_assoc_config ac; slam_map_config mc;
-    TRY(assoc_args(assoc_cfg, cmds, meas, count, k_stride, nullptr, nullptr, false, &ac));
-    TRY(map_config(map_cfg, &mc));
-    TRY(managed_enter(h, "a managed step"));
-    TRY(upload_messages(h, meas, count, k_stride, 1));
-    if (cmd_each) TRY(innovation_upload_cmds(h, cmds, 2 * (size_t)h->B));
-    return step_managed_now(h, ac, mc, cmd_each ? kNoCmd : cmds, cmd_each ? h->inn.dcmd.get() : nullptr, h->inn.dmeas, h->inn.dcount, k_stride, rec,
-                            n_drop);
+    return step_managed(h, true, assoc_cfg, map_cfg, cmds, cmd_each, meas, count, k_stride, rec, n_drop);
 }
 
 int slam_step_managed_dev(slam_handle* h, const slam_assoc_config* assoc_cfg, const slam_map_config* map_cfg, const float* cmds, int cmd_each,
                           const float* d_meas, const int32_t* d_count, int k_stride, double rec[16], int32_t* n_drop) {
-    slam_assoc_config ac; slam_map_config mc;
-    TRY(assoc_args(assoc_cfg, cmds, d_meas, d_count, k_stride, nullptr, nullptr, false, &ac));
-    TRY(map_config(map_cfg, &mc));
-    TRY(managed_enter(h, "a managed step"));
-    return step_managed_now(h, ac, mc, cmd_each ? kNoCmd : cmds, cmd_each ? cmds : nullptr, d_meas, d_count, k_stride, rec, n_drop);
+    return step_managed(h, false, assoc_cfg, map_cfg, cmds, cmd_each, d_meas, d_count, k_stride, rec, n_drop);
 }
-
-}  // extern "C"
-
-namespace {
-
-// slam_manage_run and slam_manage_run_sim once their arguments are in order: T managed ticks with the commands of `csrc` on the messages of `msgs`
-int manage_run(slam_handle* h, const char* who, const slam_assoc_config& ac, const slam_map_config& mc, TickCmds::Source csrc, const float* cmds,
-               TickMsgs& msgs, int T, double* recs, int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* n_removed, int32_t* flags) {
-    const int k_stride = msgs.k_stride;
-    TRY(run_enter(h, who, msgs.sim(), csrc == TickCmds::kNav, true));
-    if (T == 0) return SLAM_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t B = (size_t)h->B;
-    TickCmds tcmd;
-    TRY(tcmd.init(h, csrc, cmds));
-    // what a tick holds on the device: its rows of the counts (the association's five, the removal's two), of the commands (cmd_each)
-    // and of the messages
-    const double per_tick = 7.0 * 4.0 * (double)B + tcmd.bytes_per_tick(h) + msgs.bytes_per_tick(h, tcmd);
-    const int chunk = slam_host::ticks_per_chunk(T, per_tick, slam_host::tick_log_budget());
-    TRY(assoc_reserve(h, k_stride, (size_t)chunk));
-    TRY(msgs.reserve(h, tcmd, chunk));
-    TRY(map_reserve(h, (size_t)chunk));
-    TRY(map_track(h));
-    TRY(map_zero_work(h));
-    const size_t cb = (size_t)chunk * B;
-    int32_t* const di = h->assoc.dint;
-    int32_t* const mi = h->map.dint;
-    auto prunes_after = [&](int t_run) { return (t_run + 1) % mc.prune_every == 0; };
-    const int rc = run_chunked(
-        h, T, chunk, h->nav.time_ticks, h->map.times,
-        [&](int t0, int tc) -> int {
-            TRY(tcmd.upload(h, t0, tc));
-            HIP_TRY(hipMemsetAsync(mi, 0, sizeof(int32_t) * 2 * cb, h->stream));   // (n_removed of the ticks without a prune)
-            return msgs.upload(h, t0, tc);
-        },
-        [&](int t0, int t, auto mark) -> int {
-            const float *cmd, *d_each, *dm;
-            const int32_t* dc;
-            TRY(tcmd.select(h, t0, t, &cmd, &d_each));
-            TRY(msgs.produce(h, tcmd, t, cmd, d_each, &dm, &dc));
-            const size_t o = (size_t)t * B;
-            TRY(assoc_launch(h, ac, cmd, d_each, dm, dc, k_stride, h->assoc.dmeas, h->assoc.dcount,
-                             h->inn.drec + (size_t)t * slam::kInnovRecLen,
-                             {di + o, di + cb + o, di + 2 * cb + o, di + 3 * cb + o, di + 4 * cb + o, nullptr, nullptr, nullptr}));
-            TRY(launch_step(h, cmd, 0, h->assoc.dmeas, h->assoc.dcount, k_stride, d_each));
-            TRY(msgs.commit(h, t));   // (before the prune: the simulator's error is taken after the step)
-            TRY(tally_now(h, mc, h->assoc.dmeas, h->assoc.dcount, k_stride, di + 3 * cb + o));
-            // (the marked group of a tick without a prune is empty: its event pair brackets nothing)
-            return mark([&]() -> int { return prunes_after(t0 + t) ? map_compact_launch(h, nullptr, mc, mi + o, mi + cb + o, false) : SLAM_OK; });
-        },
-        [&](int t0, int tc) -> int {
-            const size_t nb = sizeof(int32_t) * (size_t)tc * B, o = (size_t)t0 * B;
-            TRY(msgs.download(h, tcmd, t0, tc));
-            for (int t = 0; t < tc; ++t)               // (after the chunk's events: the model is no part of the run's times)
-                if (prunes_after(t0 + t)) TRY(map_sum_work(h, mi + (size_t)t * B, mi + cb + (size_t)t * B, true));
-            if (recs) HIP_TRY(hipMemcpy(recs + (size_t)t0 * slam::kInnovRecLen, h->inn.drec, sizeof(double) * (size_t)tc * slam::kInnovRecLen, hipMemcpyDeviceToHost));
-            if (n_match) HIP_TRY(hipMemcpy(n_match + o, di, nb, hipMemcpyDeviceToHost));
-            if (n_new) HIP_TRY(hipMemcpy(n_new + o, di + cb, nb, hipMemcpyDeviceToHost));
-            if (n_drop) HIP_TRY(hipMemcpy(n_drop + o, di + 2 * cb, nb, hipMemcpyDeviceToHost));
-            if (flags) HIP_TRY(hipMemcpy(flags + o, di + 3 * cb, nb, hipMemcpyDeviceToHost));
-            if (n_removed) HIP_TRY(hipMemcpy(n_removed + o, mi, nb, hipMemcpyDeviceToHost));
-            return SLAM_OK;
-        });
-    TRY(rc);
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return SLAM_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int slam_manage_run(slam_handle* h, const slam_assoc_config* assoc_cfg, const slam_map_config* map_cfg, const float* cmds, int cmd_each,
                     const float* meas, const int32_t* count, int k_stride, int T, double* recs, int32_t* n_match, int32_t* n_new, int32_t* n_drop,
                     int32_t* n_removed, int32_t* flags) {
     slam_assoc_config ac; slam_map_config mc;
+    TickMsgs msgs;
     TRY(assoc_config(assoc_cfg, &ac));
     TRY(map_config(map_cfg, &mc));
-    if (T < 0) return slam_internal_fail(SLAM_ERR_ARG, "T = %d is negative", T);
-    if (!cmds) return slam_internal_fail(SLAM_ERR_ARG, "cmds is NULL");
-    if (!meas || !count) return slam_internal_fail(SLAM_ERR_ARG, "meas or meas_count is NULL");
-    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
-    TickMsgs msgs;
-    msgs.init_log(meas, count, k_stride);
-    return manage_run(h, "slam_manage_run", ac, mc, cmd_each ? TickCmds::kEach : TickCmds::kShared, cmds, msgs, T, recs, n_match, n_new, n_drop, n_removed,
-                      flags);
+    TRY(run_args_log(cmds, meas, count, k_stride, T, &msgs));
+    return run_filtered(h, "slam_manage_run", cmd_each ? TickCmds::kEach : TickCmds::kShared, cmds, msgs, T,
+                        ManageTicks{{h, ac, recs, n_match, n_new, n_drop, flags}, mc, n_removed});
 }
 
 int slam_manage_run_sim(slam_handle* h, const slam_assoc_config* assoc_cfg, const slam_map_config* map_cfg, int source, const float* cmds,
@@ -350,14 +257,11 @@ int slam_manage_run_sim(slam_handle* h, const slam_assoc_config* assoc_cfg, cons
                         const slam_sense_log* log) {
     slam_assoc_config ac; slam_map_config mc;
     TickCmds::Source csrc;
+    TickMsgs msgs;
     TRY(assoc_config(assoc_cfg, &ac));
     TRY(map_config(map_cfg, &mc));
-    TRY(sim_run_source(source, cmds, &csrc));
-    if (T < 0) return slam_internal_fail(SLAM_ERR_ARG, "T = %d is negative", T);
-    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
-    TickMsgs msgs;
-    msgs.init_sim(log, k_stride);
-    return manage_run(h, "slam_manage_run_sim", ac, mc, csrc, cmds, msgs, T, recs, n_match, n_new, n_drop, n_removed, flags);
+    TRY(run_args_sim(source, cmds, k_stride, T, log, &csrc, &msgs));
+    return run_filtered(h, "slam_manage_run_sim", csrc, cmds, msgs, T, ManageTicks{{h, ac, recs, n_match, n_new, n_drop, flags}, mc, n_removed});
 }
 
 int slam_last_map_work(slam_handle* h, double* bytes, double* prune_ms, double* total_ms) {

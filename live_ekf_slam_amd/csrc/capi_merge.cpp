@@ -7,12 +7,8 @@
 #include <vector>
 
 #include "assoc_kernel.h"
-#include "capi_assoc.h"
-#include "capi_innovation.h"
 #include "capi_map.h"
-#include "capi_run.h"
 #include "ekf_kernel.h"
-#include "host/tick_chunks.h"
 #include "map_kernel.h"
 #include "merge_kernel.h"
 
@@ -62,7 +58,7 @@ int find_launch(slam_handle* h, const slam_merge_config& c, int32_t* d_partner, 
     memset(&p, 0, sizeof(p));
     p.P = h->dP; p.x = h->dx; p.M = h->dM; p.status = h->dflags;
     p.gate = c.gate_merge; p.sigma2 = c.sigma * c.sigma;
-    p.partner = d_partner; p.d2 = d_d2; p.n_notmutual = rows + kNotMutual * cb; p.find_on = rows + kFindOn * cb;
+    p.partner = d_partner; p.d2 = d_d2; p.n_notmutual = row(rows, kNotMutual, cb); p.find_on = row(rows, kFindOn, cb);
     p.B = h->B; p.L_max = h->L_max; p.pstride = h->pstride; p.xstride = h->xstride;
     HIP_TRY(slam::launch_merge_find(p, h->esz == 4, h->stream));
     return SLAM_OK;
@@ -73,16 +69,16 @@ int fuse_launch(slam_handle* h, const slam_merge_config& c, const int32_t* d_par
     slam::MergeFuseParams p;
     memset(&p, 0, sizeof(p));
     p.P = h->dP; p.x = h->dx; p.M = h->dM; p.status = h->dflags;
-    p.partner = d_partner; p.n_notmutual = found ? rows + kNotMutual * cb : nullptr; p.sigma2 = c.sigma * c.sigma;
+    p.partner = d_partner; p.n_notmutual = found ? row(rows, kNotMutual, cb) : nullptr; p.sigma2 = c.sigma * c.sigma;
     p.seen = h->map.tracked ? h->map.dseen.get() : nullptr; p.expected = h->map.tracked ? h->map.dexpected.get() : nullptr;
-    p.remove = h->merge.dmask; p.n_fused = rows + kFused * cb; p.n_attempted = rows + kAttempted * cb;
+    p.remove = h->merge.dmask; p.n_fused = row(rows, kFused, cb); p.n_attempted = row(rows, kAttempted, cb);
     p.inst_rec = h->inn.dval + 13 * (size_t)h->B;   // (the places innovation_reserve gives the contributions and the partial records)
     p.partials = h->inn.dpart; p.rec = with_rec ? h->merge.drec.get() : nullptr;
     p.B = h->B; p.L_max = h->L_max; p.pstride = h->pstride; p.xstride = h->xstride;
     HIP_TRY(slam::launch_merge_fuse(p, h->esz == 4, h->stream));
     slam_map_config mc;
     slam_map_config_default(&mc);
-    return map_compact_launch(h, h->merge.dmask, mc, rows + kRemoved * cb, rows + kMBefore * cb, false);
+    return map_compact_launch(h, h->merge.dmask, mc, row(rows, kRemoved, cb), row(rows, kMBefore, cb), false);
 }
 
 // find (d_partner NULL), fuse and compact on the handle's stream
@@ -93,10 +89,10 @@ int merge_launches(slam_handle* h, const slam_merge_config& c, const int32_t* d_
 
 // the traffic model of one merge whose rows are filled; m: the M the find and the fusion saw
 int merge_sum_work(slam_handle* h, const int32_t* m, const int32_t* rows, size_t cb, bool compacted) {
-    HIP_TRY(slam::launch_merge_work(m, rows + kFindOn * cb, rows + kAttempted * cb, rows + kFused * cb, (size_t)h->B, h->L_max, h->map.tracked,
+    HIP_TRY(slam::launch_merge_work(m, row(rows, kFindOn, cb), row(rows, kAttempted, cb), row(rows, kFused, cb), (size_t)h->B, h->L_max, h->map.tracked,
                                     h->merge.dwork, h->stream));
     if (compacted)
-        HIP_TRY(slam::launch_map_work(rows + kMBefore * cb, rows + kRemoved * cb, (size_t)h->B, h->L_max, h->esz, 0, h->map.tracked,
+        HIP_TRY(slam::launch_map_work(row(rows, kMBefore, cb), row(rows, kRemoved, cb), (size_t)h->B, h->L_max, h->esz, 0, h->map.tracked,
                                       h->merge.dwork + 2, h->stream));
     return SLAM_OK;
 }
@@ -109,12 +105,10 @@ int merge_now(slam_handle* h, const slam_merge_config& c, const int32_t* d_partn
     int32_t* const rows = h->merge.dint;
     HIP_TRY(hipMemsetAsync(rows, 0, sizeof(int32_t) * kRows * B, h->stream));
     TRY(merge_launches(h, c, d_partner, rows, B, rec != nullptr));
-    TRY(merge_sum_work(h, rows + kMBefore * B, rows, B, true));
+    TRY(merge_sum_work(h, row(rows, kMBefore, B), rows, B, true));
     if (!n_merged && !rec) return SLAM_OK;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (n_merged) HIP_TRY(hipMemcpy(n_merged, rows + kRemoved * B, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
-    if (rec) HIP_TRY(hipMemcpy(rec, h->merge.drec, sizeof(double) * slam::kMergeRecLen, hipMemcpyDeviceToHost));
-    return SLAM_OK;
+    return copy_rows({{row(rows, kRemoved, B), n_merged, B}, {h->merge.drec, rec, slam::kMergeRecLen}}, 0, 1);
 }
 
 // slam_map_duplicates* once the outputs' device places are known
@@ -192,78 +186,51 @@ int slam_map_merge(slam_handle* h, const slam_merge_config* cfg, double rec[16],
 
 namespace {
 
-// slam_manage_merge_run and its _sim form once their arguments are in order: T ticks with the commands of `csrc` on the messages of `msgs`
-int manage_merge_run(slam_handle* h, const char* who, const slam_assoc_config& ac, const slam_map_config& mc, const slam_merge_config& gc,
-                     TickCmds::Source csrc, const float* cmds, TickMsgs& msgs, int T, double* recs, int32_t* n_match, int32_t* n_new, int32_t* n_drop,
-                     int32_t* n_removed, int32_t* n_merged, int32_t* flags) {
-    const int k_stride = msgs.k_stride;
-    TRY(run_enter(h, who, msgs.sim(), csrc == TickCmds::kNav, true));
-    if (T == 0) return SLAM_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t B = (size_t)h->B;
-    TickCmds tcmd;
-    TRY(tcmd.init(h, csrc, cmds));
-    // what a tick holds on the device: slam_manage_run's rows and the six of a merge
-    const double per_tick = (7.0 + kRows) * 4.0 * (double)B + tcmd.bytes_per_tick(h) + msgs.bytes_per_tick(h, tcmd);
-    const int chunk = slam_host::ticks_per_chunk(T, per_tick, slam_host::tick_log_budget());
-    TRY(assoc_reserve(h, k_stride, (size_t)chunk));
-    TRY(msgs.reserve(h, tcmd, chunk));
-    TRY(map_reserve(h, (size_t)chunk));
-    TRY(merge_reserve(h, (size_t)chunk, false));
-    TRY(map_track(h));
-    TRY(map_zero_work(h));
-    TRY(merge_zero_work(h));
-    const size_t cb = (size_t)chunk * B;
-    int32_t* const di = h->assoc.dint;
-    int32_t* const mi = h->map.dint;
-    int32_t* const gi = h->merge.dint;
-    auto prunes_after = [&](int t_run) { return (t_run + 1) % mc.prune_every == 0; };
-    auto merges_after = [&](int t_run) { return (t_run + 1) % gc.merge_every == 0; };
-    const int rc = run_chunked(
-        h, T, chunk, h->nav.time_ticks, h->merge.times,
-        [&](int t0, int tc) -> int {
-            TRY(tcmd.upload(h, t0, tc));
-            HIP_TRY(hipMemsetAsync(mi, 0, sizeof(int32_t) * 2 * cb, h->stream));       // (n_removed of the ticks without a prune)
-            HIP_TRY(hipMemsetAsync(gi, 0, sizeof(int32_t) * kRows * cb, h->stream));   // (and the rows of the ticks without a merge)
-            return msgs.upload(h, t0, tc);
-        },
-        [&](int t0, int t, auto mark) -> int {
-            const float *cmd, *d_each, *dm;
-            const int32_t* dc;
-            TRY(tcmd.select(h, t0, t, &cmd, &d_each));
-            TRY(msgs.produce(h, tcmd, t, cmd, d_each, &dm, &dc));
-            const size_t o = (size_t)t * B;
-            TRY(assoc_launch(h, ac, cmd, d_each, dm, dc, k_stride, h->assoc.dmeas, h->assoc.dcount,
-                             h->inn.drec + (size_t)t * slam::kInnovRecLen,
-                             {di + o, di + cb + o, di + 2 * cb + o, di + 3 * cb + o, di + 4 * cb + o, nullptr, nullptr, nullptr}));
-            TRY(launch_step(h, cmd, 0, h->assoc.dmeas, h->assoc.dcount, k_stride, d_each));
-            TRY(msgs.commit(h, t));   // (before the merge, which can move the pose: the simulator's error is taken after the step)
-            TRY(tally_now(h, mc, h->assoc.dmeas, h->assoc.dcount, k_stride, di + 3 * cb + o));
-            // (the marked group of a tick without a merge is empty: its event pair brackets nothing)
-            TRY(mark([&]() -> int { return merges_after(t0 + t) ? merge_launches(h, gc, nullptr, gi + o, cb, false) : SLAM_OK; }));
-            return prunes_after(t0 + t) ? map_compact_launch(h, nullptr, mc, mi + o, mi + cb + o, false) : SLAM_OK;
-        },
-        [&](int t0, int tc) -> int {
-            const size_t nb = sizeof(int32_t) * (size_t)tc * B, o = (size_t)t0 * B;
-            TRY(msgs.download(h, tcmd, t0, tc));
-            for (int t = 0; t < tc; ++t) {             // (after the chunk's events: the models are no part of the run's times)
-                const size_t ot = (size_t)t * B;
-                if (merges_after(t0 + t)) TRY(merge_sum_work(h, gi + kMBefore * cb + ot, gi + ot, cb, true));
-                if (prunes_after(t0 + t)) TRY(map_sum_work(h, mi + ot, mi + cb + ot, true));
-            }
-            if (recs) HIP_TRY(hipMemcpy(recs + (size_t)t0 * slam::kInnovRecLen, h->inn.drec, sizeof(double) * (size_t)tc * slam::kInnovRecLen, hipMemcpyDeviceToHost));
-            if (n_match) HIP_TRY(hipMemcpy(n_match + o, di, nb, hipMemcpyDeviceToHost));
-            if (n_new) HIP_TRY(hipMemcpy(n_new + o, di + cb, nb, hipMemcpyDeviceToHost));
-            if (n_drop) HIP_TRY(hipMemcpy(n_drop + o, di + 2 * cb, nb, hipMemcpyDeviceToHost));
-            if (flags) HIP_TRY(hipMemcpy(flags + o, di + 3 * cb, nb, hipMemcpyDeviceToHost));
-            if (n_removed) HIP_TRY(hipMemcpy(n_removed + o, mi, nb, hipMemcpyDeviceToHost));
-            if (n_merged) HIP_TRY(hipMemcpy(n_merged + o, gi + kRemoved * cb, nb, hipMemcpyDeviceToHost));
-            return SLAM_OK;
-        });
-    TRY(rc);
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return SLAM_OK;
-}
+// slam_manage_merge_run as run_filtered's feature: the managed tick with a merge, every merge_every ticks, between its tally and its
+// prune; the merge is the marked group
+struct MergeTicks {
+    ManageTicks m; const slam_merge_config& gc; int32_t* n_merged;
+
+    RunTimes& times() const { return m.a.h->merge.times; }
+    double bytes_per_tick() const { return m.bytes_per_tick() + kRows * 4.0 * (double)m.a.h->B; }
+    int reserve(int k_stride, int chunk) {
+        TRY(m.reserve(k_stride, chunk));
+        TRY(merge_reserve(m.a.h, (size_t)chunk, false));
+        return merge_zero_work(m.a.h);
+    }
+    int chunk_begin() {   // (and the rows of the ticks without a merge)
+        TRY(m.chunk_begin());
+        HIP_TRY(hipMemsetAsync(m.a.h->merge.dint, 0, sizeof(int32_t) * kRows * m.a.cb, m.a.h->stream));
+        return SLAM_OK;
+    }
+    DevMsg out() const { return m.out(); }
+    template <class Mark>
+    int filter(int t, const float* cmd, const float* d_each, const float* dm, const int32_t* dc, int k_stride, Mark mark) {
+        return m.filter(t, cmd, d_each, dm, dc, k_stride, mark);
+    }
+    int32_t* at(int t) const { return m.a.h->merge.dint + (size_t)t * m.a.B; }   // the rows of tick t, at stride cb
+    bool merges_after(int t_run) const { return (t_run + 1) % gc.merge_every == 0; }
+    template <class Mark>
+    int after_step(int t_run, int t, Mark mark) {
+        TRY(m.tally(t));
+        // (the marked group of a tick without a merge is empty: its event pair brackets nothing; the merge can move the pose)
+        TRY(mark([&]() -> int { return merges_after(t_run) ? merge_launches(m.a.h, gc, nullptr, at(t), m.a.cb, false) : SLAM_OK; }));
+        return m.prune(t_run, t);
+    }
+    int chunk_done(int t0, int tc) {
+        for (int t = 0; t < tc; ++t) {
+            if (merges_after(t0 + t)) TRY(merge_sum_work(m.a.h, row(at(t), kMBefore, m.a.cb), at(t), m.a.cb, true));
+            TRY(m.sum_work(t0 + t, t));
+        }
+        return SLAM_OK;
+    }
+    std::vector<TickRow> rows() const {
+        std::vector<TickRow> r = m.rows();
+        r.push_back({row(at(0), kRemoved, m.a.cb), n_merged, m.a.B});
+        return r;
+    }
+    int finish() { return m.finish(); }
+};
 
 }  // namespace
 
@@ -273,17 +240,13 @@ int slam_manage_merge_run(slam_handle* h, const slam_assoc_config* assoc_cfg, co
                           const float* cmds, int cmd_each, const float* meas, const int32_t* count, int k_stride, int T, double* recs,
                           int32_t* n_match, int32_t* n_new, int32_t* n_drop, int32_t* n_removed, int32_t* n_merged, int32_t* flags) {
     slam_assoc_config ac; slam_map_config mc; slam_merge_config gc;
+    TickMsgs msgs;
     TRY(assoc_config(assoc_cfg, &ac));
     TRY(map_config(map_cfg, &mc));
     TRY(merge_config(merge_cfg, &gc));
-    if (T < 0) return slam_internal_fail(SLAM_ERR_ARG, "T = %d is negative", T);
-    if (!cmds) return slam_internal_fail(SLAM_ERR_ARG, "cmds is NULL");
-    if (!meas || !count) return slam_internal_fail(SLAM_ERR_ARG, "meas or meas_count is NULL");
-    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
-    TickMsgs msgs;
-    msgs.init_log(meas, count, k_stride);
-    return manage_merge_run(h, "slam_manage_merge_run", ac, mc, gc, cmd_each ? TickCmds::kEach : TickCmds::kShared, cmds, msgs, T, recs, n_match, n_new,
-                            n_drop, n_removed, n_merged, flags);
+    TRY(run_args_log(cmds, meas, count, k_stride, T, &msgs));
+    return run_filtered(h, "slam_manage_merge_run", cmd_each ? TickCmds::kEach : TickCmds::kShared, cmds, msgs, T,
+                        MergeTicks{{{h, ac, recs, n_match, n_new, n_drop, flags}, mc, n_removed}, gc, n_merged});
 }
 
 int slam_manage_merge_run_sim(slam_handle* h, const slam_assoc_config* assoc_cfg, const slam_map_config* map_cfg,
@@ -292,15 +255,13 @@ int slam_manage_merge_run_sim(slam_handle* h, const slam_assoc_config* assoc_cfg
                               const slam_sense_log* log) {
     slam_assoc_config ac; slam_map_config mc; slam_merge_config gc;
     TickCmds::Source csrc;
+    TickMsgs msgs;
     TRY(assoc_config(assoc_cfg, &ac));
     TRY(map_config(map_cfg, &mc));
     TRY(merge_config(merge_cfg, &gc));
-    TRY(sim_run_source(source, cmds, &csrc));
-    if (T < 0) return slam_internal_fail(SLAM_ERR_ARG, "T = %d is negative", T);
-    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
-    TickMsgs msgs;
-    msgs.init_sim(log, k_stride);
-    return manage_merge_run(h, "slam_manage_merge_run_sim", ac, mc, gc, csrc, cmds, msgs, T, recs, n_match, n_new, n_drop, n_removed, n_merged, flags);
+    TRY(run_args_sim(source, cmds, k_stride, T, log, &csrc, &msgs));
+    return run_filtered(h, "slam_manage_merge_run_sim", csrc, cmds, msgs, T,
+                        MergeTicks{{{h, ac, recs, n_match, n_new, n_drop, flags}, mc, n_removed}, gc, n_merged});
 }
 
 int slam_last_merge_work(slam_handle* h, double* bytes, double* merge_ms, double* total_ms) {

@@ -1,6 +1,8 @@
-// capi_run.h — what the per-tick runs (slam_nav_run, slam_monitor_run, slam_innovation_run, slam_gate_run) share: the checks at entry, the
-// chunked driver, the source of a tick's command, the source of a tick's message and the slam_last_*_work readers.  Defined in capi_nav.cpp,
-// except the template and TickCmds (here), innovation_supported (capi_innovation.cpp) and TickMsgs (capi_sense.cpp).  Internal, like slam_handle.h.
+// capi_run.h — what the per-tick runs share (slam_nav_run, slam_monitor_run, slam_innovation_run and, through run_filtered of capi_filter.h,
+// slam_gate_run, slam_associate_run, slam_associate_joint_run, slam_manage_run, slam_manage_merge_run and their _sim forms): the checks at
+// entry, the chunked driver, the source of a tick's command, the source of a tick's message and the slam_last_*_work readers.  Defined in
+// capi_nav.cpp, except the template and TickCmds (here), innovation_supported (capi_innovation.cpp) and TickMsgs (capi_sense.cpp).
+// Internal, like slam_handle.h.
 #pragma once
 #include <string.h>
 

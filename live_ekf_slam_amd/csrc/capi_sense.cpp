@@ -5,8 +5,7 @@
 
 #include <vector>
 
-#include "capi_innovation.h"
-#include "capi_run.h"
+#include "capi_filter.h"
 #include "capi_sense.h"
 #include "ekf_kernel.h"
 #include "sense_kernel.h"
@@ -17,9 +16,7 @@ namespace {
 
 // the checks slam_sense and slam_sense_dev share, arguments first; the queued timesteps run first
 int sense_enter(slam_handle* h, const float* cmds, const void* meas, const void* count, int k_stride, const char* who) {
-    if (!cmds) return slam_internal_fail(SLAM_ERR_ARG, "cmds is NULL");
-    if (!meas || !count) return slam_internal_fail(SLAM_ERR_ARG, "meas or meas_count is NULL");
-    if (k_stride <= 0) return slam_internal_fail(SLAM_ERR_ARG, "k_stride = %d is not positive", k_stride);
+    TRY(message_args(cmds, meas, count, k_stride));
     return run_enter(h, who, true, false, true);
 }
 
@@ -131,13 +128,9 @@ int TickMsgs::commit(slam_handle* h, int t) {
 int TickMsgs::download(slam_handle* h, const TickCmds& tcmd, int t0, int tc) const {
     if (src == kLog) return SLAM_OK;
     const size_t B = (size_t)h->B, n = (size_t)tc, o = (size_t)t0, mrow = msg_row(h, k_stride), lrow = (size_t)k_stride * B;
-    if (log.meas) HIP_TRY(hipMemcpy(log.meas + o * mrow, h->sense.dmeas, sizeof(float) * n * mrow, hipMemcpyDeviceToHost));
-    if (log.count) HIP_TRY(hipMemcpy(log.count + o * B, h->sense.dcount, sizeof(int32_t) * n * B, hipMemcpyDeviceToHost));
-    if (log.origin) HIP_TRY(hipMemcpy(log.origin + o * lrow, h->sense.dorigin, sizeof(int32_t) * n * lrow, hipMemcpyDeviceToHost));
-    if (log.fault) HIP_TRY(hipMemcpy(log.fault + o * lrow, h->sense.dfault, sizeof(int32_t) * n * lrow, hipMemcpyDeviceToHost));
-    if (log.truth) HIP_TRY(hipMemcpy(log.truth + o * 3 * B, h->sense.dtruth, sizeof(double) * n * 3 * B, hipMemcpyDeviceToHost));
-    if (log.err_pos) HIP_TRY(hipMemcpy(log.err_pos + o * B, h->sense.derrpos, sizeof(double) * n * B, hipMemcpyDeviceToHost));
-    if (log.recs) HIP_TRY(hipMemcpy(log.recs + o * slam::kSenseRecLen, h->sense.drecs, sizeof(double) * n * slam::kSenseRecLen, hipMemcpyDeviceToHost));
+    TRY(copy_rows({{h->sense.dmeas, log.meas, mrow}, {h->sense.dcount, log.count, B}, {h->sense.dorigin, log.origin, lrow},
+                   {h->sense.dfault, log.fault, lrow}, {h->sense.dtruth, log.truth, 3 * B}, {h->sense.derrpos, log.err_pos, B},
+                   {h->sense.drecs, log.recs, slam::kSenseRecLen}}, t0, tc));
     if (log.cmds) {
         float* const dst = log.cmds + o * 2 * B;
         if (tcmd.src == TickCmds::kNav) HIP_TRY(hipMemcpy(dst, h->sense.dcmd, sizeof(float) * n * 2 * B, hipMemcpyDeviceToHost));

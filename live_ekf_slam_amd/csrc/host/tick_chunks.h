@@ -1,4 +1,5 @@
-// tick_chunks.h — how many ticks of a per-tick run (slam_nav_run, slam_monitor_run, slam_innovation_run, slam_gate_run) go into one chunk.
+// tick_chunks.h — how many ticks of a per-tick run (every caller of run_chunked, capi_run.h: slam_nav_run, slam_monitor_run,
+// slam_innovation_run and the filtered runs of capi_filter.h) go into one chunk.
 // A chunk is what such a run enqueues before it synchronises, reads its events and copies the rows of its ticks out; the rows of one chunk
 // live on the device.  Plain C++: needs no HIP runtime (tests/test_tick_chunks_cpu.py).
 #pragma once

@@ -1,7 +1,8 @@
 // slam_handle.h — the handle of the filter ABI (include/slam_batch.h) and the host helpers that more than one of its translation units
 // uses (slam_capi.cpp: create / configure / init; capi_step.cpp: the steps and their queue; capi_state.cpp: reading the state back;
-// capi_consistency.cpp, capi_nav.cpp, capi_monitor.cpp, capi_innovation.cpp, capi_gate.cpp, capi_assoc.cpp, capi_joint.cpp, capi_map.cpp, capi_merge.cpp, capi_sense.cpp: one feature each).  Not installed, not part
-// of the ABI: the standing of capi_internal.h.
+// capi_consistency.cpp, capi_nav.cpp, capi_monitor.cpp, capi_innovation.cpp, capi_gate.cpp, capi_assoc.cpp, capi_joint.cpp, capi_map.cpp,
+// capi_merge.cpp, capi_sense.cpp: one feature each; capi_run.h: what the per-tick runs share; capi_filter.h: what the features that filter a
+// message before the step share).  Not installed, not part of the ABI: the standing of capi_internal.h.
 #pragma once
 #include "../../include/slam_batch.h"
 
@@ -20,7 +21,16 @@ namespace slam { struct EkfStepParams; struct UkfStepParams; struct ConsistencyP
 
 // Device times of the last per-tick run of one kind (run_chunked): part_ms is the sum over the launch group each tick marks, -1 while
 // slam_nav_set_timing is off; total_ms is the sum over the chunks, -1 until such a run has run on the handle.
-namespace slam_capi { struct RunTimes { double part_ms = -1.0, total_ms = -1.0; }; }
+namespace slam_capi {
+struct RunTimes { double part_ms = -1.0, total_ms = -1.0; };
+// The traffic model of an association (slam_associate*, slam_associate_joint*): its three sums on the device, what the last synchronising
+// call read from them and the device times of the last run.
+struct Traffic {
+    DevBuf<unsigned long long> dwork;
+    double bytes = -1.0, lines = -1.0;
+    RunTimes times;
+};
+}
 
 struct slam_handle {
     slam_config cfg;
@@ -167,17 +177,13 @@ struct slam_handle {
     // [5][ticks][B] n_match, n_new, n_drop, flags and landmarks compared with, [B][64] verdicts and slots, [B][64][4] detection slots, the three sums of the traffic
     // model, what the last synchronising call read and the device times of the last slam_associate_run.  The incoming message, the
     // per-instance contributions and the records are staged in `inn`.
-    struct Assoc {
-        DevBuf<float> dmeas; DevBuf<int32_t> dcount, dint, dverdict, dslot; DevBuf<double> ddet; DevBuf<unsigned long long> dwork;
-        double bytes = -1.0, lines = -1.0;
-        slam_capi::RunTimes times;
+    struct Assoc : slam_capi::Traffic {
+        DevBuf<float> dmeas; DevBuf<int32_t> dcount, dint, dverdict, dslot; DevBuf<double> ddet;
     } assoc;
     // slam_associate_joint_*: as `assoc`, with [7][ticks][B] n_match, n_new, n_drop, flags, landmarks compared with, nodes and on-demand
     // blocks, [ticks][B] d2_joint and [B][64] candidate counts
-    struct Joint {
-        DevBuf<float> dmeas; DevBuf<int32_t> dcount, dint, dverdict, dslot, dncand; DevBuf<double> ddet, dd2; DevBuf<unsigned long long> dwork;
-        double bytes = -1.0, lines = -1.0;
-        slam_capi::RunTimes times;
+    struct Joint : slam_capi::Traffic {
+        DevBuf<float> dmeas; DevBuf<int32_t> dcount, dint, dverdict, dslot, dncand; DevBuf<double> ddet, dd2;
     } joint;
     // slam_remove_landmarks / slam_map_*: the track counters seen and expected ([B][L_max] each, allocated on first use and outside the
     // checkpoint format; tracked: they exist), the staged mask of a host-pointer removal ([B][L_max]), [2][ticks][B] n_removed and the M
