@@ -1019,6 +1019,112 @@ int slam_sense_instance_host(uint64_t seed, int64_t instance, uint32_t step, con
                              const double sim_noise[4], const slam_sensor* row, int k_stride, float* meas, int32_t* count, int32_t* origin,
                              int32_t* fault, double truth_next[3], int32_t* flags, double rec[16]);
 
+/* ---- absolute position and heading fixes: GPS, compass, motion capture (csrc/fix_kernel.h) ---------------------------------------------------
+ * Every other measurement of the batch is a range-bearing detection of a landmark; a stretch with no landmark in view is dead reckoning
+ * whose error grows without bound.  A fix is a direct measurement of the pose: of (x, y), of the yaw, or of both.  EKF_SLAM, both storage
+ * types, every size class; no step, gate, association, map, merge or sense kernel changes.
+ * A fix of instance b is one row fix [batch][5] of doubles {z_x, z_y, z_yaw, sigma_pos, sigma_yaw} and one int32 kinds [batch]: bit 0
+ * (SLAM_FIX_POS) the position part is present, bit 1 (SLAM_FIX_YAW) the heading part; other bits are ignored.  The parts are applied
+ * sequentially, position first, then heading, each on the state the previous one left (stored values, widened for fp32 storage):
+ *   position: nu = (z_x - x[0], z_y - x[1]); S = P[0:2][0:2] + sigma_pos^2 I; Si = the PartialPivLU inverse the step uses;
+ *             nis = nu^T Si nu; accepted: K = P[:, 0:2] Si, x += K nu (yaw wrapped as in the step), P -= K P[0:2, :]
+ *   heading:  nu = the wrapped z_yaw - x[2]; S = P[2][2] + sigma_yaw^2; nis = nu^2 / S; accepted: k = P[:, 2] / S, x += k nu (yaw
+ *             wrapped), P -= k P[2, :]
+ *   (the exact operation order is csrc/fix_kernel.h's; results are stored rounded to the storage type).
+ * Verdict of a part (slam_fix_verdict), in this order: 0 absent; INVALID: a z or the sigma of the part is not finite, or sigma < 0;
+ *   SINGULAR: the inverse failed or S is not finite (heading: S not finite or <= 0), or nis is not finite; REJECTED: nis > the part's
+ *   gate (a nis equal to the gate is accepted); APPLIED.  Only APPLIED writes.  verdict [batch] int32 = position | heading << 4;
+ *   nis [batch][2]: the part's nis where it is APPLIED or REJECTED, NaN otherwise.
+ * An instance whose status carries SLAM_INST_NONFINITE, SLAM_INST_INDEX_OOR or SLAM_INST_WATCHDOG is not written and reports verdict 0; an
+ *   instance without an APPLIED part is not written at all.  M, ids, flags, timestep, truth, the error sum and the track counters are
+ *   never touched.  An instance with both parts applied has its P read and written ONCE (csrc/fix_kernel.h has the argument why that
+ *   equals the two sequential updates in bits).
+ * Record, 16 doubles, every entry a sum in the fixed order of the sense record: 0 instances written; 1 - 5 position parts present /
+ *   applied / rejected / singular / invalid; 6 - 10 the same for heading; 11, 12 the sums of the nis of the applied position and heading
+ *   parts; 13 instances skipped by their status (they add to no other entry); 14, 15 reserved, 0.
+ * Sense protocol: a fix belongs after slam_sense_commit, as a merge does (it moves the pose; the simulator's error is taken after the
+ *   step).  While a sense waits for its commit every call of this section is SLAM_ERR_STATE.
+ * Errors: SLAM_ERR_ARG (checked first, with a text, before the handle is looked at): a NULL fix or kinds array, a config with a gate that
+ *   is NaN or <= 0 (+inf is allowed: nothing is rejected) or fix_every < 1, T < 0, an unknown source or SLAM_INNOVATION_LOG, NULL cmds for
+ *   SHARED and EACH, NULL outputs of slam_fix_sense*; NULL handle; a sensor row with a negative or non-finite half-width or sigma, a
+ *   probability outside [0, 1], jump_lo > jump_hi or not finite, kinds outside 0 .. 3 (slam_last_error names the instance and the field).
+ *   SLAM_ERR_UNSUPPORTED: the UKF kinds (their P is rank-deficient in the (cos, sin) yaw pair), state untouched.  SLAM_ERR_STATE: before
+ *   slam_init, while slam_track_instance is on, while a prediction or a sense is pending; slam_fix_sense* and slam_fix_run without a true
+ *   map; SLAM_INNOVATION_NAV without a path.  The step queue is run first.
+ * Not covered: the UKF kinds; the pose graph (a unary pose factor is the counterpart); slam_multi_*; fixes inside the five *_run_sim
+ *   runs and inside multi-step launches (a caller composes them from the _dev calls); full 2 x 2 position covariances; lever arms;
+ *   checkpoints of the sensor rows (inputs, like noise rows). */
+enum slam_fix_kinds { SLAM_FIX_POS = 1, SLAM_FIX_YAW = 2 };
+enum slam_fix_verdict { SLAM_FIX_ABSENT = 0, SLAM_FIX_APPLIED = 1, SLAM_FIX_REJECTED = 2, SLAM_FIX_SINGULAR = 3, SLAM_FIX_INVALID = 4 };
+typedef struct slam_fix_config {
+    double gate_pos;        /* a position part is rejected when its nis exceeds this; > 0, +inf: never */
+    double gate_yaw;        /* the same for a heading part */
+    int32_t fix_every;      /* slam_fix_run fixes after every fix_every-th tick; >= 1 */
+} slam_fix_config;
+/* gate_pos = -2 ln 0.001 and gate_yaw = 10.827566170662733, the 0.999 quantiles of chi-square with 2 and 1 degrees of freedom; fix_every 10 */
+int slam_fix_config_default(slam_fix_config* cfg);
+/* One fix of every instance from HOST arrays fix [batch][5], kinds [batch].  verdict [batch], nis [batch][2], rec [16] (host) may each be
+ * NULL; the call synchronises only when one of them is wanted.  cfg NULL: the defaults. */
+int slam_fix(slam_handle* h, const slam_fix_config* cfg, const double* fix, const int32_t* kinds, int32_t* verdict, double* nis, double rec[16]);
+/* The same from DEVICE arrays, read in the order of the handle's stream; d_verdict [batch], d_nis [batch][2] and d_rec [16] are device
+ * pointers and may each be NULL.  Never synchronises. */
+int slam_fix_dev(slam_handle* h, const slam_fix_config* cfg, const double* d_fix, const int32_t* d_kinds, int32_t* d_verdict, double* d_nis,
+                 double* d_rec);
+/* A simulated source of fixes of the handle's TRUE pose, for runs and tools.  Draws of instance g at RNG step s - the step the next
+ * simulator step would use - from the handle's counter based generator, at pair indices neither the clean generator nor the fault model
+ * (F = 0x40000000) uses, G = 0x50000000:
+ *   (u0, u1) = pair G      z_x = (t_x + (2 a) u0) - a, z_y = (t_y + (2 a) u1) - a, a = pos_halfwidth
+ *   (v0, v1) = pair G + 1  z_yaw = the wrapped (t_yaw + (2 h) v0) - h, h = yaw_halfwidth; the position part is missed iff v1 < p_miss_pos
+ *   (j0, j1) = pair G + 2  a position part that was not missed jumps iff j0 < p_jump, by m = jump_lo + (jump_hi - jump_lo) * j1
+ *   (d0, d1) = pair G + 3  in the direction phi = (2 pi d0) - pi: z_x += m cos phi, z_y += m sin phi; the heading part is missed iff
+ *                          d1 < p_miss_yaw
+ * kinds_out = kinds & 3 without the missed parts; the z of a part that is not emitted is 0; sigma_pos and sigma_yaw are copied.  fp64, as
+ * parenthesised.  The all-zero row emits nothing.  The status is not consulted; the truth and the RNG step are read, never advanced. */
+typedef struct slam_fix_sensor {
+    double pos_halfwidth;   /* position noise, uniform in [-a, a) per axis, m */
+    double yaw_halfwidth;   /* heading noise, uniform, rad */
+    double sigma_pos;       /* what the emitted row claims, copied */
+    double sigma_yaw;
+    double p_miss_pos;      /* the position part is missing with this probability */
+    double p_miss_yaw;
+    double p_jump;          /* an emitted position jumps (multipath) with this probability */
+    double jump_lo, jump_hi;   /* the jump is uniform in [jump_lo, jump_hi), m, in a uniform direction */
+    int32_t kinds;          /* the parts the source emits: slam_fix_kinds, 0 .. 3 */
+} slam_fix_sensor;
+/* the all-zero row */
+int slam_fix_sensor_default(slam_fix_sensor* row);
+/* rows: [batch], host; NULL = the all-zero row for every instance.  Runs the step queue first, like slam_set_sensor_each. */
+int slam_set_fix_sensor_each(slam_handle* h, const slam_fix_sensor* rows);
+/* One emission into HOST arrays fix [batch][5], kinds [batch] and (may be NULL) jumped [batch].  Synchronises. */
+int slam_fix_sense(slam_handle* h, double* fix, int32_t* kinds, int32_t* jumped);
+/* The same into DEVICE arrays in the order of the handle's stream; d_jumped may be NULL.  Does not synchronise. */
+int slam_fix_sense_dev(slam_handle* h, double* d_fix, int32_t* d_kinds, int32_t* d_jumped);
+/* T ticks.  A tick is {the command by source - SLAM_INNOVATION_SHARED (cmds [T][2]), _EACH (cmds [T][batch][2]) or _NAV (cmds not read,
+ * the controller launch) -; one simulator timestep, as slam_nav_run launches it}; after tick t with (t + 1) % fix_every == 0 also {the
+ * slam_fix_sense_dev launch, the slam_fix_dev launch}.  The state advances bit for bit as the loop of the single calls would leave it.
+ * Optional HOST series: recs [T][16], verdict [T][batch], nis [T][batch][2], and through fix_log (may be NULL, as may its members) the
+ * emitted rows fix [T][batch][5] and kinds [T][batch]; ticks without a fix give zeros, and NaN for nis.  Chunks of ticks by the rule of
+ * slam_monitor_run; chunking changes no bit. */
+typedef struct slam_fix_log {
+    double* fix; int32_t* kinds;
+} slam_fix_log;
+int slam_fix_run(slam_handle* h, const slam_fix_config* cfg, int source, const float* cmds, int T, double* recs, int32_t* verdict, double* nis,
+                 const slam_fix_log* fix_log);
+/* What the last slam_fix*, or all the fixes of the last slam_fix_run, had to move, and the device times of the last slam_fix_run.  bytes:
+ * the model, summed in integers on the device outside the timed part - per evaluated part the gather of 4 n + 2 (position) or 2 n + 1
+ * (heading) elements; per instance WRITTEN, whatever its parts, P and x read and written once; the fix row, kinds, M, status, verdict and
+ * nis.  fix_ms: the fix-sense and fix launches alone, which needs slam_nav_set_timing(h, 1), else -1; total_ms: the whole run; both -1
+ * before any slam_fix_run.  Synchronises. */
+int slam_last_fix_work(slam_handle* h, double* bytes, double* fix_ms, double* total_ms);
+/* TEST HOOK, not part of the filter interface: the fix of ONE instance compiled for the HOST from csrc/fix_kernel.h (the source the
+ * kernel compiles, no device needed), as two sequential passes.  x [3 + 2 M], P [n][n] packed, both in place; row [5]; outputs verdict,
+ * nis [2], rec [16] may be NULL. */
+int slam_fix_instance_host(double* x, double* P, int M, int L_max, int32_t status, int f32_storage, const slam_fix_config* cfg, const double row[5],
+                           int32_t kinds, int32_t* verdict, double nis[2], double rec[16]);
+/* TEST HOOK: the simulated source of ONE instance on the host.  instance: the global id; truth [3]; row NULL: the all-zero row. */
+int slam_fix_sense_instance_host(uint64_t seed, int64_t instance, uint32_t step, const double truth[3], const slam_fix_sensor* row, double fix[5],
+                                 int32_t* kinds, int32_t* jumped);
+
 /* ---- closed loop: commands from each instance's own estimate (goal_pursuit_node.py:23-50, pure_pursuit.py:17-161) ---------------------
  * The entry points above run open loop: every command is fixed before the run.  The reference's default launch (sim_base.launch,
  * precompute_trajectory false) closes the loop instead: goal_pursuit_node computes each Command from the state the filter has just published.

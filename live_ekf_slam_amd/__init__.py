@@ -21,5 +21,8 @@ from .config import MergeConfig, default_merge_config  # noqa: F401
 from .filters import MergeResult, merge_instance_host  # noqa: F401
 from .config import SensorConfig, default_sensor_config, SENSE_MAX_DET, SENSE_MAX_CLUTTER, SENSE_INSTANCE_FROZEN, SENSE_TOO_LONG  # noqa: F401
 from .filters import SenseLogResult, sense_instance_host  # noqa: F401
+from .config import FixConfig, FixSensorConfig, default_fix_config, default_fix_sensor_config, FIX_POS, FIX_YAW  # noqa: F401
+from .config import FIX_ABSENT, FIX_APPLIED, FIX_REJECTED, FIX_SINGULAR, FIX_INVALID  # noqa: F401
+from .filters import FixResult, fix_instance_host, fix_sense_instance_host  # noqa: F401
 from .pose_graph import BatchedPoseGraph, NaiveFilter  # noqa: F401
 from ._lib import SlamError  # noqa: F401

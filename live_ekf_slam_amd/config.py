@@ -227,6 +227,49 @@ class SenseLog(C.Structure):
                 ("recs", C.POINTER(C.c_double))]
 
 
+class FixConfig(C.Structure):
+    """ctypes mirror of `slam_fix_config` (include/slam_batch.h): the nis gates of the position and the heading part of a fix and the stride
+    of the fixes of fix_run."""
+    _fields_ = [("gate_pos", C.c_double), ("gate_yaw", C.c_double), ("fix_every", C.c_int32)]
+
+
+FIX_CONFIG_FIELDS = tuple(name for name, _ in FixConfig._fields_)
+FIX_POS, FIX_YAW = 1, 2
+FIX_ABSENT, FIX_APPLIED, FIX_REJECTED, FIX_SINGULAR, FIX_INVALID = 0, 1, 2, 3, 4
+
+
+def default_fix_config() -> FixConfig:
+    """The 0.999 quantiles of chi-square with 2 and with 1 degrees of freedom; a fix every 10 ticks."""
+    import math
+    return FixConfig(-2.0 * math.log(0.001), 10.827566170662733, 10)
+
+
+class FixSensorConfig(C.Structure):
+    """ctypes mirror of `slam_fix_sensor` (include/slam_batch.h): one row of the simulated source of fixes - uniform noise, the sigmas the
+    rows claim, misses and position jumps."""
+    _fields_ = [("pos_halfwidth", C.c_double), ("yaw_halfwidth", C.c_double), ("sigma_pos", C.c_double), ("sigma_yaw", C.c_double),
+                ("p_miss_pos", C.c_double), ("p_miss_yaw", C.c_double), ("p_jump", C.c_double), ("jump_lo", C.c_double), ("jump_hi", C.c_double),
+                ("kinds", C.c_int32)]
+
+
+FIX_SENSOR_FIELDS = tuple(name for name, _ in FixSensorConfig._fields_)
+
+
+def default_fix_sensor_config(**fields) -> FixSensorConfig:
+    """The all-zero row, which emits nothing.  Keyword arguments set fields."""
+    row = FixSensorConfig()
+    for k, v in fields.items():
+        if k not in FIX_SENSOR_FIELDS:
+            raise ValueError(f"unknown fix sensor setting {k!r}")
+        setattr(row, k, v)
+    return row
+
+
+class FixLog(C.Structure):
+    """ctypes mirror of `slam_fix_log`: the emitted rows and kinds of a fix_run."""
+    _fields_ = [("fix", C.POINTER(C.c_double)), ("kinds", C.POINTER(C.c_int32))]
+
+
 def default_monitor_config() -> MonitorConfig:
     """The chi-square quantiles at 0.025 and 0.975 for 3 degrees of freedom; no full evaluation."""
     return MonitorConfig(0.21579528262389785, 9.348403604496148, 0)

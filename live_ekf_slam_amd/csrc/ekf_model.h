@@ -111,6 +111,16 @@ SLAM_HD double ekf_state_update(double x, int r, double k0, double k1, double nu
 // One element of P_pred -= K (H P) (ekf.cpp:140, the rank-2 form): P[r][c] with K[r][0 .. 1] and (H P)[0 .. 1][c]
 SLAM_HD double ekf_downdate(double p, double k0, double k1, double h0, double h1) { return p - (k0 * h0 + k1 * h1); }
 
+// ---- the same update for a scalar measurement of one state entry (fix_kernel.h: a heading fix; H is a unit row, so P H^T is a column
+// of P and H P a row; si = 1 / S) ----
+SLAM_HD double ekf_gain1(double ph, double si) { return ph * si; }
+SLAM_HD double ekf_state_update1(double x, int r, double k, double nu) {
+    double xv = x + k * nu;
+    if (r == 2) xv = rem2pi(xv);
+    return xv;
+}
+SLAM_HD double ekf_downdate1(double p, double k, double h) { return p - k * h; }
+
 // ---- landmark insertion, ekf.cpp:141-173 ---------------------------------------------------------------------------------------------
 // G_x(0,2) = G_z(0,1), G_x(1,2) = G_z(1,1), cos and sin of the bearing in the world frame (G_z's first column), the new landmark's position
 struct EkfInsert { double g02, g12, c, s, lx, ly; };

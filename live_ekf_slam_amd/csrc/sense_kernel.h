@@ -274,6 +274,10 @@ struct SenseCommitParams {
     double* inst_rec; double* partials; double* rec;
 };
 hipError_t launch_sense_commit(const SenseCommitParams& p, hipStream_t stream);
+
+// The two reduction launches of the above alone, for another record of kSenseRecLen doubles whose every entry is a sum (fix_kernel.hip):
+// inst_rec [B][kSenseRecLen] -> partials [innovation_blocks(B)][kSenseRecLen] -> rec [kSenseRecLen], in the same fixed order.
+hipError_t launch_record_sum(const double* inst_rec, int B, double* partials, double* rec, hipStream_t stream);
 #endif
 
 }  // namespace slam

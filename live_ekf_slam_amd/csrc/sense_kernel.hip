@@ -128,6 +128,12 @@ hipError_t sense_reduce(const double* inst_rec, int B, double* partials, double*
 
 }  // namespace
 
+hipError_t launch_record_sum(const double* inst_rec, int B, double* partials, double* rec, hipStream_t stream) {
+    if (B <= 0 || !inst_rec || !partials || !rec) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    return sense_reduce(inst_rec, B, partials, rec, stream);
+}
+
 hipError_t launch_sense(const SenseParams& p, hipStream_t stream) {
     const EkfStepParams& s = p.s;
     if (s.B <= 0 || p.k_stride <= 0 || !p.meas_out || !p.count_out || !p.truth_next || !p.staged_ts || !p.inst_rec || !s.truth || !s.flags ||

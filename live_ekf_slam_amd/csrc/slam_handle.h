@@ -1,7 +1,7 @@
 // slam_handle.h — the handle of the filter ABI (include/slam_batch.h) and the host helpers that more than one of its translation units
 // uses (slam_capi.cpp: create / configure / init; capi_step.cpp: the steps and their queue; capi_state.cpp: reading the state back;
 // capi_consistency.cpp, capi_nav.cpp, capi_monitor.cpp, capi_innovation.cpp, capi_gate.cpp, capi_assoc.cpp, capi_joint.cpp, capi_map.cpp,
-// capi_merge.cpp, capi_sense.cpp: one feature each; capi_run.h: what the per-tick runs share; capi_filter.h: what the features that filter a
+// capi_merge.cpp, capi_sense.cpp, capi_fix.cpp: one feature each; capi_run.h: what the per-tick runs share; capi_filter.h: what the features that filter a
 // message before the step share).  Not installed, not part of the ABI: the standing of capi_internal.h.
 #pragma once
 #include "../../include/slam_batch.h"
@@ -213,6 +213,16 @@ struct slam_handle {
         bool pending = false; uint32_t pending_step = 0;
         DevBuf<float> dmeas, dcmd; DevBuf<int32_t> dcount, dorigin, dfault; DevBuf<double> dtruth, derrpos, drecs;
     } sense;
+    // slam_fix*: the [B] rows of the simulated source (rows_set: the kernel reads them); the staged rows, kinds, verdicts, nis and jumped
+    // flags of a host-pointer call, and of one chunk of ticks of slam_fix_run ([ticks][B] each, the records [ticks][16]); the record; the two
+    // sums of the traffic model (work_set: a fix has filled them) and the device times of the last slam_fix_run.  The per-instance
+    // contributions and the partial records are staged in `inn`.
+    struct Fix {
+        DevBuf<slam_fix_sensor> drows; bool rows_set = false;
+        DevBuf<double> dfix, dnis, drec, drecs; DevBuf<int32_t> dkinds, dverdict, djumped; DevBuf<unsigned long long> dwork;
+        bool work_set = false;
+        slam_capi::RunTimes times;
+    } fix;
 };
 
 #pragma GCC visibility push(hidden)

@@ -23,6 +23,7 @@ from .config import JointConfig, default_joint_config
 from .config import MapConfig, default_map_config, MAP_CONFIG_FIELDS
 from .config import MergeConfig, default_merge_config, MERGE_CONFIG_FIELDS
 from .config import SensorConfig, SenseLog, default_sensor_config
+from .config import FixConfig, FixSensorConfig, FixLog, default_fix_config, default_fix_sensor_config, FIX_CONFIG_FIELDS
 
 
 def _d(a):
@@ -139,6 +140,18 @@ class MergeResult(MapResult):
     def __init__(self, recs, n_match=None, n_new=None, n_drop=None, flags=None, n_removed=None, n_merged=None):
         MapResult.__init__(self, recs, n_match, n_new, n_drop, flags, n_removed)
         self.n_merged = n_merged
+
+
+class FixResult:
+    """The outcome of a fix_run: recs (T, 16), one record per tick (zeros on the ticks without a fix), indexed by the REC_FIX_* constants,
+    and - series=True, else None - verdict (T, batch) int32 (position | heading << 4), nis (T, batch, 2), the emitted rows fix (T, batch, 5)
+    and kinds (T, batch)."""
+    REC_FIX_WRITTEN, REC_FIX_POS_PRESENT, REC_FIX_POS_APPLIED, REC_FIX_POS_REJECTED, REC_FIX_POS_SINGULAR, REC_FIX_POS_INVALID = 0, 1, 2, 3, 4, 5
+    REC_FIX_YAW_PRESENT, REC_FIX_YAW_APPLIED, REC_FIX_YAW_REJECTED, REC_FIX_YAW_SINGULAR, REC_FIX_YAW_INVALID = 6, 7, 8, 9, 10
+    REC_FIX_SUM_NIS_POS, REC_FIX_SUM_NIS_YAW, REC_FIX_SKIPPED = 11, 12, 13
+
+    def __init__(self, recs, verdict=None, nis=None, fix=None, kinds=None):
+        self.recs, self.verdict, self.nis, self.fix, self.kinds = recs, verdict, nis, fix, kinds
 
 
 class BatchedFilter:
@@ -1250,6 +1263,101 @@ class BatchedEKF(BatchedFilter):
         _lib.check(_lib.lib().slam_last_merge_work(self.h, C.byref(by), C.byref(a), C.byref(b)))
         return by.value, a.value, b.value
 
+    # -- absolute position and heading fixes (slam_fix_*; include/slam_batch.h) --
+    def _fix_config(self, cfg):
+        if cfg is None:
+            return default_fix_config()
+        if isinstance(cfg, FixConfig):
+            return cfg
+        c = default_fix_config()
+        for k, v in dict(cfg).items():
+            if k not in FIX_CONFIG_FIELDS:
+                raise ValueError(f"unknown fix setting {k!r}")
+            setattr(c, k, v)
+        return c
+
+    def fix(self, fix, kinds, stats=True, cfg=None):
+        """One fix of every instance: fix (batch, 5) rows {z_x, z_y, z_yaw, sigma_pos, sigma_yaw}, kinds [batch] (FIX_POS | FIX_YAW).  Both as
+        ints: the DEVICE pointers of the arrays, read in stream order (nothing is returned and nothing synchronises).  stats=True returns
+        dict(verdict [batch] (position | heading << 4), nis (batch, 2), rec (16,)) and synchronises; stats=False None."""
+        self._need()
+        c = self._fix_config(cfg)
+        if isinstance(fix, int) or isinstance(kinds, int):
+            if not (isinstance(fix, int) and isinstance(kinds, int)):
+                raise ValueError("fix and kinds are both device pointers or both arrays")
+            _lib.check(_lib.lib().slam_fix_dev(self.h, C.byref(c), C.c_void_p(fix), C.c_void_p(kinds), None, None, None))
+            return None
+        f = np.ascontiguousarray(fix, dtype=np.float64)
+        k = np.ascontiguousarray(kinds, dtype=np.int32)
+        if f.shape != (self.batch, 5) or k.shape != (self.batch,):
+            raise ValueError(f"expected fix ({self.batch}, 5) and kinds ({self.batch},), got {f.shape} and {k.shape}")
+        out = dict(verdict=np.zeros(self.batch, dtype=np.int32), nis=np.zeros((self.batch, 2)), rec=np.zeros(16)) if stats else None
+        _lib.check(_lib.lib().slam_fix(self.h, C.byref(c), _d(f), _i(k), _i(out["verdict"]) if stats else None, _d(out["nis"]) if stats else None,
+                                       _d(out["rec"]) if stats else None))
+        return out
+
+    def set_fix_sensor(self, rows):
+        """The simulated source of fix_sense() and fix_run (slam_set_fix_sensor_each): one FixSensorConfig (or a dict of its fields),
+        replicated over the batch, or `batch` of them; None returns to the all-zero row, which emits nothing.  Inputs, not state."""
+        self._need()
+        if rows is None:
+            _lib.check(_lib.lib().slam_set_fix_sensor_each(self.h, None))
+            return
+        if isinstance(rows, dict):
+            rows = default_fix_sensor_config(**rows)
+        if isinstance(rows, FixSensorConfig):
+            rows = [rows] * self.batch
+        if not (isinstance(rows, C.Array) and rows._type_ is FixSensorConfig):
+            rows = (FixSensorConfig * len(rows))(*rows)
+        if len(rows) != self.batch:
+            raise ValueError(f"expected {self.batch} fix sensor rows, got {len(rows)}")
+        _lib.check(_lib.lib().slam_set_fix_sensor_each(self.h, rows))
+
+    def fix_sense(self, dev=None):
+        """One emission of the simulated source from the true poses: dict(fix (batch, 5), kinds [batch], jumped [batch]).  dev = (d_fix,
+        d_kinds, d_jumped or None): DEVICE pointers, written in stream order; returns None."""
+        self._need()
+        if dev is not None:
+            _lib.check(_lib.lib().slam_fix_sense_dev(self.h, C.c_void_p(dev[0]), C.c_void_p(dev[1]), C.c_void_p(dev[2]) if dev[2] else None))
+            return None
+        out = dict(fix=np.zeros((self.batch, 5)), kinds=np.zeros(self.batch, dtype=np.int32), jumped=np.zeros(self.batch, dtype=np.int32))
+        _lib.check(_lib.lib().slam_fix_sense(self.h, _d(out["fix"]), _i(out["kinds"]), _i(out["jumped"])))
+        return out
+
+    def fix_run(self, cmds=None, T=None, source=None, series=False, cfg=None):
+        """Per tick one simulator timestep and, after every fix_every-th tick, one emission of the simulated source and its fix, all on the
+        device; the same bits as that loop of single calls.  cmds (T, 2): shared commands; (T, batch, 2): per instance; None with T ticks:
+        the controller of set_path / set_paths.  Returns a FixResult; series=True also records verdict, nis, fix and kinds of every tick."""
+        self._need()
+        c32, want, T = self._run_cmds("fix_run", cmds, T)
+        if c32 is None:
+            source = want if source is None else source
+        elif source is not None and source != want:
+            raise ValueError(f"source {source} does not match commands of shape {c32.shape}")
+        else:
+            source = want
+        n = max(T, 0)
+        res = FixResult(np.zeros((n, 16)))
+        log = None
+        if series:
+            res.verdict, res.kinds = np.zeros((n, self.batch), dtype=np.int32), np.zeros((n, self.batch), dtype=np.int32)
+            res.nis, res.fix = np.zeros((n, self.batch, 2)), np.zeros((n, self.batch, 5))
+            if n > 0:
+                log = FixLog(_d(res.fix), _i(res.kinds))
+        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
+        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
+        _lib.check(_lib.lib().slam_fix_run(self.h, C.byref(self._fix_config(cfg)), int(source), None if c32 is None else _f(c32), T, pd(res.recs),
+                                           pi(res.verdict), pd(res.nis), None if log is None else C.byref(log)))
+        self.timestep += n
+        return res
+
+    def last_fix_work(self):
+        """(model bytes the last fix, or all the fixes of the last fix_run, had to move; device ms of the fix launches of the last fix_run
+        or -1 without set_nav_timing; device ms of that whole run or -1)."""
+        self._need(); by = C.c_double(0); a = C.c_double(0); b = C.c_double(0)
+        _lib.check(_lib.lib().slam_last_fix_work(self.h, C.byref(by), C.byref(a), C.byref(b)))
+        return by.value, a.value, b.value
+
     # -- the simulator source with a sensor fault model (slam_sense_*, the *_run_sim calls; include/slam_batch.h) --
     def set_sensor(self, rows):
         """The sensor fault model of sense() and the *_run_sim calls (slam_set_sensor_each): one SensorConfig (or a dict of its fields),
@@ -1451,6 +1559,35 @@ def sense_instance_host(seed, instance, step, truth, cmd, map_xy, cfg, vision=(3
                                                    _i(out["fault"]), _d(out["truth_next"]), C.byref(flags), _d(out["rec"])))
     out["count"], out["flags"] = count.value, flags.value
     return out
+
+
+def fix_instance_host(x, P, L_max, row, kinds, status=0, f32_storage=False, cfg=None):
+    """TEST HOOK (slam_fix_instance_host): the fix of one instance compiled for the host, as two sequential passes; no GPU.  x (3 + 2 M,),
+    P (n, n), row (5,), kinds.  Returns dict(x, P (the state after the fix; the input's bytes where no part applied), verdict, nis (2,),
+    rec (16,))."""
+    x = np.array(x, dtype=np.float64); P = np.array(P, dtype=np.float64)
+    n = x.shape[0]; M = (n - 3) // 2
+    if n < 3 or n != 3 + 2 * M or P.shape != (n, n):
+        raise ValueError("x and P do not describe a state of 3 + 2 M entries")
+    r = np.ascontiguousarray(row, dtype=np.float64)
+    if r.shape != (5,):
+        raise ValueError("a fix row has 5 entries")
+    c_cfg = default_fix_config() if cfg is None else cfg
+    Pf = np.ascontiguousarray(P).reshape(-1).copy()
+    verdict = C.c_int32(0); nis = np.zeros(2); rec = np.zeros(16)
+    _lib.check(_lib.lib().slam_fix_instance_host(_d(x), _d(Pf), M, int(L_max), int(status), int(bool(f32_storage)), C.byref(c_cfg), _d(r), int(kinds),
+                                                 C.byref(verdict), _d(nis), _d(rec)))
+    return dict(x=x, P=Pf.reshape(n, n), verdict=verdict.value, nis=nis, rec=rec)
+
+
+def fix_sense_instance_host(seed, instance, step, truth, row=None):
+    """TEST HOOK (slam_fix_sense_instance_host): the simulated source of fixes of one instance on the host; no GPU.  Returns dict(fix (5,),
+    kinds, jumped)."""
+    t = np.ascontiguousarray(truth, dtype=np.float64)
+    fix = np.zeros(5); kinds = C.c_int32(0); jumped = C.c_int32(0)
+    _lib.check(_lib.lib().slam_fix_sense_instance_host(int(seed), int(instance), int(step), _d(t), None if row is None else C.byref(row), _d(fix),
+                                                       C.byref(kinds), C.byref(jumped)))
+    return dict(fix=fix, kinds=kinds.value, jumped=jumped.value)
 
 
 def merge_instance_host(x, P, ids, L_max, status=0, f32_storage=False, cfg=None, seen=None, expected=None, partner=None, fuse=True):
