@@ -1051,7 +1051,7 @@ int slam_sense_instance_host(uint64_t seed, int64_t instance, uint32_t step, con
  *   SLAM_ERR_UNSUPPORTED: the UKF kinds (their P is rank-deficient in the (cos, sin) yaw pair), state untouched.  SLAM_ERR_STATE: before
  *   slam_init, while slam_track_instance is on, while a prediction or a sense is pending; slam_fix_sense* and slam_fix_run without a true
  *   map; SLAM_INNOVATION_NAV without a path.  The step queue is run first.
- * Not covered: the UKF kinds; the pose graph (a unary pose factor is the counterpart); slam_multi_*; fixes inside the five *_run_sim
+ * Not covered: the UKF kinds; the pose graph, whose counterpart is a unary pose factor (slam_pgs.h: pgs_fix, fed by slam_fix_sense_dev's rows unchanged); slam_multi_*; fixes inside the five *_run_sim
  *   runs and inside multi-step launches (a caller composes them from the _dev calls); full 2 x 2 position covariances; lever arms;
  *   checkpoints of the sensor rows (inputs, like noise rows). */
 enum slam_fix_kinds { SLAM_FIX_POS = 1, SLAM_FIX_YAW = 2 };

@@ -11,6 +11,8 @@
  *
  * Covered beyond the solve: `gtsam::Marginals marginals(graph, result); marginals.marginalCovariance(i)` (pose_graph.cpp:289-294) as
  * pgs_marginals / pgs_get_marginals, for every pose and landmark (the reference's printout of them is not reproduced).
+ * Beyond the reference: a robust loss on the landmark factors (pgs_set_robust) and absolute position / heading fixes as unary pose factors
+ * (pgs_fix, "absolute fixes" below).
  *
  * Not covered: `implementation: sesync | custom` (the reference itself throws for both, pose_graph.cpp:34-38),
  * unknown landmark ids (the reference throws, pose_graph.cpp:137), `update_landmarks_after_adding` (false in
@@ -234,6 +236,63 @@ int pgs_factor_weights_dev(pgs_handle* h, const double** d_w);
 /* TEST HOOK, not part of the solver interface: the loss function compiled for the HOST (the same source as the kernels, no device
  * needed): rho, w and sqrt(w) at residual norm r.  Argument errors as pgs_set_robust. */
 int pgs_robust_loss_host(int kind, double k, double r, double* rho, double* w, double* sw);
+
+/* ---- absolute fixes: unary pose factors ---------------------------------------------------------------------------------------
+ * A GPS position, a compass heading, a pose from motion capture: the graph-side counterpart of slam_fix (slam_batch.h).  A stretch
+ * with no landmark in view is odometry integrated open loop; a fix is the factor that pulls it back.  A fix of instance b is the EKF's
+ * row {z_x, z_y, z_yaw, sigma_pos, sigma_yaw} (5 doubles) plus kinds (SLAM_FIX_POS | SLAM_FIX_YAW); the rows slam_fix_sense* emits go in
+ * unchanged.  It attaches to the graph's NEWEST pose (pose `timestep`) as two independent factors, in the tangent coordinates of the
+ * solver's Pose2 chart; with wp = 1 / sigma_pos, wy = 1 / sigma_yaw and (s, c) = sin, cos of the pose's yaw:
+ *   position   e = ((x - z_x) wp, (y - z_y) wp)          J = wp [[c, -s, 0], [s, c, 0]]
+ *   heading    e = remainder(yaw - z_yaw, 2 pi) wy        J = [0, 0, wy]
+ * Validation per part: PGS_FIX_ABSENT its kinds bit is clear; PGS_FIX_INVALID a z of the part or its sigma is not finite, or the sigma is
+ * <= 0 (unlike the EKF, sigma = 0 is invalid here: it would be an infinite weight); PGS_FIX_STORED otherwise.
+ * verdict [batch] = position | heading << 4.  A part a call carries STORED replaces that part at that pose; a part it does not carry stays.
+ * Every solve schedule, pgs_marginals, pgs_run_sim_every_iteration[_each] (fixes already in the graph) and the objective of pgs_get_stats
+ * honour the fixes.  Cost: 40 + 4 bytes per instance and pose capacity, allocated by the first call that attaches a fix; a handle that never
+ * sees one allocates nothing and runs the kernels built without fixes, bit for bit the results of before.  pgs_init[_each] removes every fix.
+ * Fix loss: each part may carry a robust loss of its own (the kinds and the function of pgs_set_robust; position: r = |e|, heading: r = |e|),
+ * the graph's answer to a GPS jump that the EKF answers with a gate.  One setting per handle.  pgs_set_fix_robust and attaching a fix
+ * invalidate the marginals, the factor weights and the fix weights.
+ * Errors: SLAM_ERR_ARG first (NULL arrays, an unknown loss kind or a k that is NaN, <= 0 or +inf for a loss, a bad sensor row, fix_every < 1,
+ * T <= 0); SLAM_ERR_STATE before pgs_init*, for the sense / run calls without a map, and when the handle's last update was dropped for pose
+ * capacity (nothing is stored then).  A call that returns an error has changed nothing.
+ * Not covered: full 2x2 position covariances and lever arms, per-instance loss parameters, fixes as a SOURCE inside
+ * pgs_run_sim_every_iteration* (fixes already attached are honoured there), a chi-square gate (a graph has no sequential innovation; the loss
+ * is its defence), slam_multi_*, checkpoint files, the UKF. */
+enum pgs_fix_verdict { PGS_FIX_ABSENT = 0, PGS_FIX_STORED = 1, PGS_FIX_INVALID = 4 };
+/* fix [batch][5], kinds [batch], verdict [batch] (may be NULL): HOST pointers; synchronous. */
+int pgs_fix(pgs_handle* h, const double* fix, const int32_t* kinds, int32_t* verdict);
+/* DEVICE pointers, read in the order of the handle's stream (e.g. slam_fix_sense_dev's outputs next to pgs_update_each_dev); never synchronises. */
+int pgs_fix_dev(pgs_handle* h, const double* d_fix, const int32_t* d_kinds, int32_t* d_verdict);
+int pgs_set_fix_robust(pgs_handle* h, int kind, double k);
+int pgs_get_fix_robust(const pgs_handle* h, int* kind, double* k);
+/* One instance's stored fixes: fix [min(cap, *n)][5], kinds [min(cap, *n)] of *n = timestep + 1 poses (kinds 0: none at that pose, its row
+ * is zero; of a pose with one part the other part's entries are zero).  Any pointer may be NULL. */
+int pgs_get_fixes(pgs_handle* h, int instance, double* fix, int32_t* kinds, int cap, int32_t* n);
+/* The weight w of both parts of every fix at the values `which` (0 = initial_estimate, 1 = result; 1 needs a pgs_solve): which fixes the
+ * solve did not believe.  Device array [batch][N_max][2] (position, heading); NaN where the part is not stored; 1.0 without a fix loss.
+ * Synchronous; changes nothing else; invalidated by the calls that invalidate the marginals.  Its buffer is allocated by the first call. */
+int pgs_fix_weights(pgs_handle* h, int which);
+/* One instance's weights: w [min(cap, *n)][2] of *n = timestep + 1 poses.  SLAM_ERR_STATE before a valid pgs_fix_weights. */
+int pgs_get_fix_weights(pgs_handle* h, int instance, double* w, int cap, int32_t* n);
+int pgs_fix_weights_dev(pgs_handle* h, const double** d_w);
+/* The simulated source, for the runs and the tools: slam_fix_sense's (slam_batch.h: the row format slam_fix_sensor, the draws and their
+ * RNG pair indices) on the pose graph's simulator - a fix of the TRUE pose pgs_run_sim left, with the handle's seed, the global instance id
+ * and the RNG step the next pgs_run_sim tick would use.  rows [batch], NULL: all-zero rows (nothing is emitted).  The truth and the RNG step
+ * are read, never advanced: a following pgs_run_sim gives the bytes it gives without the call.  jumped [batch] may be NULL. */
+int pgs_set_fix_sensor_each(pgs_handle* h, const slam_fix_sensor* rows);
+int pgs_fix_sense(pgs_handle* h, double* fix, int32_t* kinds, int32_t* jumped);
+int pgs_fix_sense_dev(pgs_handle* h, double* d_fix, int32_t* d_kinds, int32_t* d_jumped);
+/* T simulator iterations with a fix of the source after every tick t (0-based within the call) with (t + 1) % fix_every == 0: the loop of
+ * pgs_run_sim[_each] over the ticks in between, pgs_fix_sense and pgs_fix, byte for byte, without the rows' trip to the host.
+ * each = 0: cmds [T][2]; 1: cmds [T][batch][2]. */
+int pgs_run_sim_fix(pgs_handle* h, const float* cmds, int T, int each, int fix_every);
+/* TEST HOOK, not part of the solver interface: one fix factor compiled for the HOST from the kernels' source (csrc/pgs_fix.h; no device
+ * needed).  e [3] and J [3][3] row-major (rows 0, 1: position, row 2: heading; rows of a part that is not STORED are zero) WITHOUT the loss;
+ * rho [2], w [2] of the two parts under the loss (NaN where the part is not STORED); *verdict as pgs_fix's. */
+int pgs_fix_factor_host(const double pose[3], const double row[5], int32_t kinds, int loss_kind, double loss_k, double e[3], double J[9],
+                        double rho[2], double w[2], int32_t* verdict);
 
 int pgs_sync(pgs_handle* h);
 int pgs_timestep(const pgs_handle* h);

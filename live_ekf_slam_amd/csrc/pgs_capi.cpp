@@ -13,92 +13,16 @@
 #include <thread>
 #include <vector>
 
-#include "capi_internal.h"
-#include "host/pgs_schedule.h"
-#include "pgs_kernel.h"
+#include "pgs_handle.h"
 
 #define fail slam_internal_fail
 
+using pgs_capi::apply_robust;
+using pgs_capi::check;
+using pgs_capi::robust_args_ok;
+
 static_assert(PGS_LOSS_NONE == slam::kPgsLossNone && PGS_LOSS_HUBER == slam::kPgsLossHuber && PGS_LOSS_GEMAN_MCCLURE == slam::kPgsLossGemanMcClure,
               "pgs_loss_kind (slam_pgs.h) and pgs_robust.h number the losses alike");
-
-struct pgs_handle {
-    slam_config cfg;
-    int B, N_max, L_max, KP, LD, device;
-    int timestep = 0;                          // p.N = timestep + 1 at every launch: written by pgs_init[_each] and advance() only, each with p.N
-    bool inited = false;
-    bool solved = false;                       // a pgs_solve has run since pgs_init: `result` exists
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    uint64_t seed = 2025;
-    int64_t inst0 = 0;
-    slam::PgsParams p;
-    // The device arrays behind p's pointer fields, each with the address of the field it backs (bind_arrays writes it).  slot_bytes > 0:
-    // a per-slot array the clones (lambda lanes) get a copy of when a solve begins (clone_instances / clone_listed), bytes per slot.
-    struct Array { DevBuf<char> buf; void** field; size_t slot_bytes; };
-    std::vector<Array> arrays;                 // sized by pgs_create
-    std::vector<Array> seg_arrays;             // sized for segments of seg_alloc poses (segT joins on first use): replaced as a whole by resize_segments
-    DevBuf<double> map;                        // p.map
-    DevBuf<float> dcmds;                       // p.cmds while the handle has seen shared calls only: one row [N_max][2]
-    // Heterogeneous batches (pgs_*_each).  dcmds_each: one row of BetweenFactor measurements per instance, [B][N_max][2] floats = 8 B N_max
-    // bytes (16 MB at batch 2048 with N_max = 1000; 0.1 % of that handle's LM work space), allocated by the first per-instance command and
-    // kept for the handle's lifetime; p.cmds then points at it (ensure_cmds_each).  Not per slot: the lambda lanes read their instance's row.
-    DevBuf<float> dcmds_each;
-    DevBuf<float> dcmd_stage;                  // host commands on their way into the rows ([T][B][2] or [T][2])
-    DevBuf<double> dmaps; DevBuf<int32_t> dLs; // pgs_set_maps: p.map_each [B][map_stride][2], p.L_each [B]
-    DevBuf<float> dpose_each; DevBuf<double> dtruth_each;   // pgs_init_each's staging, [B][3] each
-    DevBuf<float> dmeas; DevBuf<int32_t> dcount; DevBuf<double> dsec;   // pgs_update's staging
-    DevBuf<double> dout;
-    // The tuning values (host/pgs_schedule.h), read from the environment by pgs_create.  Of these, `lanes` may shrink there (the lanes multiply
-    // the LM work space), and `groups` / `slots` follow pgs_set_groups / pgs_set_slots.
-    //  * solve groups: the batch is split into contiguous ranges whose LM loops run on their own streams, so the latency-bound phases of one
-    //    group overlap the bandwidth-bound phases of another;
-    //  * streaming (pgs_kernel.h "streaming"): at most `slots` graphs of the batch are in flight (0 = lockstep: all of them), split over the
-    //    solve groups; trials are enqueued `stream_depth` ahead of the host's reading of their counters.
-    slam_host::PgsTuning tune;
-    std::vector<hipStream_t> gstreams;
-    std::vector<hipEvent_t> gevents;
-    PinnedDefaultBuf<int32_t> h_active;        // pinned host: per-group active counts
-    DevBuf<int32_t> d_cnt;                     // device [kPgsMaxGroups][2][8]: the counter blocks, ping-pong by trial parity
-    DevBuf<int32_t> d_wait;                    // device [kPgsMaxGroups]: the groups' wait cursors
-    PinnedDefaultBuf<int32_t> h_ring;          // pinned host [kPgsMaxGroups][kPgsRing][8]
-    std::vector<hipEvent_t> ring_events;       // [kPgsMaxGroups][kPgsRing]
-    std::vector<std::vector<int32_t>> timeline;   // per group: slots that ran in every trial of the last solve
-    DevBuf<int32_t> d_tick;                    // [B][2] LM iterations / trials summed over the ticks of pgs_run_sim_every_iteration
-    DevBuf<double> d_tick_flop;                // [B][2] algorithmic FLOP (SYRK | Cholesky) of the same
-    double iter_ms[4] = {0, 0, 0, 0};
-    double host_launch_ms = 0.0, host_wait_ms = 0.0;   // tune.host_prof: host clock spent enqueuing trials / waiting for their counters (stderr, every-iteration runs)
-    long long iter_trials = 0;
-    double path_ms[3] = {0.0, 0.0, 0.0};      // profiled solve: ms in the separate SYRK launches / in the fused chain + SYRK launches / in the segmented path's SYRK launches
-    bool seg_ok = false;                      // this solve runs the segmented elimination (decided in pgs_solve from the plan)
-    // Round 6: the segment length is chosen PER SOLVE from {tune.seg_len, tune.seg_len / 2, ... >= 8}: the longest whose every segment sees at most
-    // kPgsSegMaxLm landmarks (a wide sensor on a dense map overflowed 32-pose segments and the whole solve fell back to the sequential chain,
-    // 2.3 x slower).  seg_cur: where the next solve's search starts (only goes down while the graph grows; pgs_init resets it); seg_alloc: the
-    // length the segment-count-dependent arrays are sized for (re-made on demand, resize_segments); seg_used: the last solve's.
-    int seg_cur = 32, seg_alloc = 32, seg_used = 0;
-    bool fused_ok = false;                    // this solve's graphs fit the fused kernel (decided in pgs_solve from max M)
-    bool syrk_inst_ok = false;                // ... and the instance-resident SYRK (its kPgsSyrkInstTiles tiles hold every lower triangle)
-    int cus = 256;                            // compute units of the device
-    int last_trials = 0;
-    bool profiling = false;                  // per-kernel hipEvent timing of pgs_solve (pgs_set_profiling)
-    std::vector<hipEvent_t> events;
-    std::vector<int> trial_fused;             // profiled solve: the fused choice (0 | 2 | 3 | 4) of every trial
-    double kernel_ms[slam::kPgsTrialKernels] = {0, 0, 0, 0, 0, 0};
-    // marginal covariances (pgs_marginals): the outputs, and the per-instance flags / lambda = 0 the trial kernels read in place of the
-    // solve's own (nothing pgs_get_stats returns is touched).  Allocated by the first call.  mg_valid: they belong to the current values.
-    DevBuf<double> mg_pose, mg_lm, mg_flop, mg_lambda;   // [B][N_max][9], [B][L_max][4], [B], [B]
-    DevBuf<int32_t> mg_status, mg_state;                 // [B], [3][B]: state | lin_ok | solve_ok
-    hipEvent_t mg_ev[2] = {nullptr, nullptr};
-    bool mg_valid = false;
-    double mg_ms = 0.0;
-    // robust loss of the bearing-range factors (pgs_set_robust): the setting as the caller left it; apply_robust copies it into p - with lin0
-    // behind it - when the next solve / marginals / factor weights begin.  fw: the factor weights' own output, [B][N_max][KP], first use.
-    int loss_kind = slam::kPgsLossNone;
-    double loss_k = 0.0;
-    DevBuf<double> rb_lin0;                    // p.lin0, [slots][N_max * KP]: allocated by the first such call with a loss set
-    DevBuf<double> fw;
-    bool fw_valid = false;
-};
 
 namespace {
 
@@ -113,16 +37,14 @@ int add_array(std::vector<pgs_handle::Array>& set, T** field, size_t count, size
 
 void bind_arrays(std::vector<pgs_handle::Array>& set) { for (pgs_handle::Array& a : set) *a.field = a.buf.get(); }
 
-int check(pgs_handle* h) {
-    if (!h) return fail(SLAM_ERR_ARG, "NULL handle");
-    HIP_TRY(hipSetDevice(h->device));
-    return SLAM_OK;
-}
+}  // namespace
 
-// The handle's loss setting into the parameter block the kernels get.  A loss needs lin0 (8 bytes per factor slot and lambda lane): allocated
-// here once; if that fails the call returns the error and the handle - parameter block included - is what it was.
-int apply_robust(pgs_handle* h) {
-    if (h->loss_kind != slam::kPgsLossNone && !h->rb_lin0) {
+// The handle's loss settings into the parameter block the kernels get.  A loss - on the landmark factors, or on the fixes of a handle that has
+// fixes - needs lin0 (8 bytes per factor slot and lambda lane): allocated here once; if that fails the call returns the error and the handle
+// - parameter block included - is what it was.
+int pgs_capi::apply_robust(pgs_handle* h) {
+    const bool loss = h->loss_kind != slam::kPgsLossNone || (h->fix_kind && h->fix_loss_kind != slam::kPgsLossNone);
+    if (loss && !h->rb_lin0) {
         DevBuf<double> a;
         if (a.reserve((size_t)h->B * h->tune.lanes * h->N_max * h->KP) != hipSuccess)
             return fail(SLAM_ERR_HIP, "out of device memory for the robust loss' per-factor terms (%zu bytes)", sizeof(double) * (size_t)h->B * h->tune.lanes * h->N_max * h->KP);
@@ -130,13 +52,16 @@ int apply_robust(pgs_handle* h) {
         h->p.lin0 = h->rb_lin0;
     }
     h->p.loss_kind = h->loss_kind; h->p.loss_k = h->loss_k;
+    h->p.fix_loss_kind = h->fix_loss_kind; h->p.fix_loss_k = h->fix_loss_k;
     return SLAM_OK;
 }
 
-bool robust_args_ok(int kind, double k) {
+bool pgs_capi::robust_args_ok(int kind, double k) {
     if (kind == slam::kPgsLossNone) return true;
     return (kind == slam::kPgsLossHuber || kind == slam::kPgsLossGemanMcClure) && k > 0.0 && k < (double)INFINITY;   // (NaN fails both)
 }
+
+namespace {
 
 // the layout of Y for segments of SL poses (0: the sequential chain): the separators' rows live behind the pose rows (pgs_kernel.h: yr_rc, yr_sep)
 void seg_geometry(const pgs_handle* h, slam::PgsParams& g, int SL) {
@@ -186,6 +111,15 @@ int resize_segments(pgs_handle* h, int SL, bool* resized) {
     bind_arrays(h->seg_arrays);
     h->p.nseg_max = g.nseg_max; h->p.yr_sep = g.yr_sep; h->p.y_stride = g.y_stride;
     h->seg_alloc = SL;
+    return SLAM_OK;
+}
+
+// pgs_init[_each]: the graph is empty again and no pose carries a fix (the fix arrays, once allocated, stay)
+int clear_fixes(pgs_handle* h) {
+    h->tick_dropped = false;
+    if (!h->fix_kind) return SLAM_OK;
+    HIP_TRY(hipMemsetAsync(h->fix_row, 0, sizeof(double) * slam::kPgsFixRowLen * (size_t)h->B * h->N_max, h->stream));
+    HIP_TRY(hipMemsetAsync(h->fix_kind, 0, sizeof(int32_t) * (size_t)h->B * h->N_max, h->stream));
     return SLAM_OK;
 }
 
@@ -348,9 +282,10 @@ int pgs_set_maps(pgs_handle* h, const double* maps, const int32_t* L, int L_stri
 
 int pgs_init(pgs_handle* h, float x0, float y0, float yaw0) {
     TRY(check(h));
-    h->mg_valid = false; h->fw_valid = false;
+    h->invalidate_derived();
     h->timestep = 0; h->p.N = 1;
     h->seg_cur = h->tune.seg_len;
+    TRY(clear_fixes(h));
     HIP_TRY(slam::pgs_launch_init(h->p, x0, y0, yaw0, h->stream));
     h->inited = true; h->solved = false;
     return SLAM_OK;
@@ -410,10 +345,13 @@ int enter_ticks(pgs_handle* h, const char* who, const float* cmds, int T, unsign
     if (!cmds) return fail(SLAM_ERR_ARG, each ? "cmds is NULL" : "cmd is NULL");
     if (flags & kBadMeasArgs) return fail(SLAM_ERR_ARG, "bad measurement arguments");
     if (each && !src_dev && !all_finite_f(cmds, 2 * (size_t)T * h->B)) return fail(SLAM_ERR_ARG, "a command is not finite");
-    if (h->timestep + T >= h->N_max)
+    if (h->timestep + T >= h->N_max) {
+        h->tick_dropped = true;   // (pgs_fix: the graph's newest pose is not the one this update was for)
         return sim ? fail(SLAM_ERR_STATE, "timestep %d + %d commands exceed the pose capacity N_max = %d", h->timestep, T, h->N_max)
                    : fail(SLAM_ERR_STATE, "pose capacity N_max = %d reached", h->N_max);
-    h->mg_valid = false; h->fw_valid = false;
+    }
+    h->tick_dropped = false;
+    h->invalidate_derived();
     return put_commands(h, cmds, src_dev, T, each);
 }
 
@@ -452,9 +390,10 @@ int pgs_init_each(pgs_handle* h, const float* pose0, const double* truth0) {
     if (truth0) HIP_TRY(h->dtruth_each.reserve(3 * B));
     HIP_TRY(hipMemcpyAsync(h->dpose_each, pose0, sizeof(float) * 3 * B, hipMemcpyHostToDevice, h->stream));
     if (truth0) HIP_TRY(hipMemcpyAsync(h->dtruth_each, truth0, sizeof(double) * 3 * B, hipMemcpyHostToDevice, h->stream));
-    h->mg_valid = false; h->fw_valid = false;
+    h->invalidate_derived();
     h->timestep = 0; h->p.N = 1;
     h->seg_cur = h->tune.seg_len;
+    TRY(clear_fixes(h));
     HIP_TRY(slam::pgs_launch_init_each(h->p, h->dpose_each, truth0 ? h->dtruth_each.get() : nullptr, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));   // the host arrays are pageable
     h->inited = true; h->solved = false;
@@ -877,7 +816,7 @@ int pgs_solve(pgs_handle* h) {
     TRY(check(h));
     if (!h->inited) return fail(SLAM_ERR_STATE, "pgs_init must be called before pgs_solve");
     TRY(apply_robust(h));
-    h->mg_valid = false; h->fw_valid = false; h->solved = true;
+    h->invalidate_derived(); h->solved = true;
     h->p.N = h->timestep + 1;
     h->p.b_off = 0; h->p.b_cnt = h->B;
     TRY(plan_segments(h));
@@ -912,7 +851,7 @@ int pgs_set_groups(pgs_handle* h, int groups) { TRY(check(h)); h->tune.groups = 
 
 int pgs_adopt_result(pgs_handle* h) {
     TRY(check(h));
-    h->mg_valid = false; h->fw_valid = false;
+    h->invalidate_derived();
     HIP_TRY(slam::pgs_launch_adopt(h->p, h->stream));
     return SLAM_OK;
 }
@@ -1203,7 +1142,7 @@ int pgs_set_robust(pgs_handle* h, int kind, double k) {
     if (!robust_args_ok(kind, k)) return fail(SLAM_ERR_ARG, "pgs_set_robust: kind %d, k %g (kind 0 | 1 | 2; k finite and > 0 for a loss)", kind, k);
     TRY(check(h));
     h->loss_kind = kind; h->loss_k = kind == slam::kPgsLossNone ? 0.0 : k;
-    h->mg_valid = false; h->fw_valid = false;   // what was computed belongs to the setting it was computed with
+    h->invalidate_derived();   // what was computed belongs to the setting it was computed with
     return SLAM_OK;
 }
 

@@ -103,9 +103,44 @@ __device__ __forceinline__ double factor_cost(const PgsParams& p, const double e
     return rho;
 }
 
-// sum of the costs of the factors owned by pose i: 0.5 |whitened e|^2 of the prior (i = 0) and the between (i, i+1), factor_cost of the bearing-range at i
+// The absolute fixes of slot b (pgs_fix.h): inputs of the instance it belongs to, like cmds and prior.  Only the kernels built with FX ask.
+struct FixView { const double* row; const int32_t* kind; };
+__device__ __forceinline__ FixView fix_view(const PgsParams& p, int b) {
+    const size_t inst = (size_t)((unsigned)b % (unsigned)p.B);
+    return FixView{p.fix_row + inst * p.N_max * kPgsFixRowLen, p.fix_kind + inst * p.N_max};
+}
+
+// cost of one fix part with squared whitened residual norm ss: 0.5 ss, or (RB) rho of the fix loss
 template <bool RB>
-__device__ __forceinline__ double pose_cost(const PgsParams& p, const Inst& g, const double* pose, const double* lm, int i, int N) {
+__device__ __forceinline__ double fix_part_cost(const PgsParams& p, double ss) {
+    if (!RB) return 0.5 * ss;
+    double rho, w, sw;
+    pgs_robust_loss(p.fix_loss_kind, p.fix_loss_k, ss, sqrt(ss), &rho, &w, &sw);
+    return rho;
+}
+
+// acc plus the costs of the fix parts stored at pose i with value ps: position, then heading (the order of sums within a pose, everywhere)
+template <bool RB>
+__device__ __forceinline__ double add_fix_cost(const PgsParams& p, const FixView& f, const double* ps, int i, double acc) {
+    const int fk = f.kind[i];
+    const double* row = f.row + (size_t)kPgsFixRowLen * i;
+    if (fk & kPgsFixPos) {
+        double e[2];
+        pgs_fix_pos<false>(ps, row, e, nullptr);
+        acc = acc + fix_part_cost<RB>(p, e[0] * e[0] + e[1] * e[1]);
+    }
+    if (fk & kPgsFixYaw) {
+        double wy;
+        const double e = pgs_fix_yaw(ps, row, &wy);
+        acc = acc + fix_part_cost<RB>(p, e * e);
+    }
+    return acc;
+}
+
+// sum of the costs of the factors owned by pose i: 0.5 |whitened e|^2 of the prior (i = 0) and the between (i, i+1), (FX) the fix parts at i,
+// factor_cost of the bearing-range at i
+template <bool RB, bool FX>
+__device__ __forceinline__ double pose_cost(const PgsParams& p, const Inst& g, const double* pose, const double* lm, int i, int N, int b) {
     double acc = 0.0, e[3];
     if (i == 0) {
         prior_factor(p, g.prior, pose, e);
@@ -115,6 +150,7 @@ __device__ __forceinline__ double pose_cost(const PgsParams& p, const Inst& g, c
         between_factor<false>(p, pose + 3 * i, pose + 3 * (i + 1), g.cmds[2 * i], g.cmds[2 * i + 1], e, nullptr);
         acc = acc + 0.5 * ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
     }
+    if (FX) acc = add_fix_cost<RB>(p, fix_view(p, b), pose + 3 * i, i, acc);
     const int kc = g.cnt[i];
     for (int s = 0; s < kc; ++s) {
         const size_t k = (size_t)i * p.KP + s;
@@ -125,10 +161,10 @@ __device__ __forceinline__ double pose_cost(const PgsParams& p, const Inst& g, c
     return acc;
 }
 
-template <int TPB, bool RB>
+template <int TPB, bool RB, bool FX>
 __device__ __forceinline__ double block_cost(const PgsParams& p, int b, int N, const double* pose, const double* lm, double* s_buf) {
     const Inst g = inst_view(p, b);
     double acc = 0.0;
-    for (int i = threadIdx.x; i < N; i += TPB) acc = acc + pose_cost<RB>(p, g, pose, lm, i, N);
+    for (int i = threadIdx.x; i < N; i += TPB) acc = acc + pose_cost<RB, FX>(p, g, pose, lm, i, N, b);
     return block_sum<TPB>(acc, s_buf);
 }

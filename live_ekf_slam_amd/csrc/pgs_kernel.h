@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "host/pgs_limits.h"
+#include "pgs_fix.h"
 #include "pgs_robust.h"
 
 namespace slam {
@@ -146,7 +147,19 @@ struct PgsParams {
                                        //                 pgs_linearize_kernel); allocated by the first solve / marginals with a loss set
     double* oldlin;                    // [S]             the slot's linearised cost at delta = 0: the Gaussian terms + sum 0.5 w r^2, slot order
                                        //                 within a pose, then the block tree (pgs_linearize_kernel, once per linearisation)
+    // ---- absolute position / heading fixes: unary factors of a pose (pgs_fix.h; pgs_fix) ----
+    // INPUTS of an instance like cmds and prior: the lambda lanes of instance b read row b (fix_view), nothing is cloned.  NULL: the handle
+    // has never attached a fix and the kernels instantiated without them run (FX = false: the code of before, no additional byte moved).
+    const double* fix_row;             // [B][N_max][5]  {z_x, z_y, z_yaw, sigma_pos, sigma_yaw} of the fix at pose i
+    const int32_t* fix_kind;           // [B][N_max]     bit 0: a position part is stored at pose i, bit 1: a heading part; 0: none
+    int32_t fix_loss_kind; double fix_loss_k;   // the loss of the fix parts (the kinds of pgs_robust.h), each part with its own weight
 };
+
+// the kernels built with the fixes' terms run (FX)
+inline bool pgs_has_fixes(const PgsParams& p) { return p.fix_kind != nullptr; }
+// The kernels built with a loss run (RB): oldLin differs from the cost as soon as ANY factor carries a loss - a landmark factor, or a fix part
+// of a handle that has fixes (pgs_robust_loss gives the landmark factors weight 1 while their own kind is NONE).
+inline bool pgs_has_loss(const PgsParams& p) { return p.loss_kind != kPgsLossNone || (pgs_has_fixes(p) && p.fix_loss_kind != kPgsLossNone); }
 
 // geometry of the segmented elimination: separators at the poses k SL, k = 1 .. seg_ns; segment ps holds the poses [seg_lo, seg_hi)
 __host__ __device__ inline int seg_ns(int N, int SL) { return N >= 2 ? (N - 2) / SL : 0; }
@@ -192,5 +205,16 @@ hipError_t pgs_launch_marginals(const PgsParams& p, int which, double* pose_cov,
 // of mb / mr), NaN in the slots at or beyond a pose's count and at poses the graph does not have; 1.0 everywhere stored with kPgsLossNone.
 // One thread per factor slot; reads the graph and the values only.
 hipError_t pgs_launch_factor_weights(const PgsParams& p, int which, double* out, hipStream_t s);
+// Absolute fixes (pgs_fix.h).  Attach: one lane per instance validates row b of d_fix [B][5] / d_kinds [B], stores the STORED parts at pose
+// p.N - 1 of fix_row / fix_kind (a part the call carries replaces that part there, one it does not carry stays) and writes
+// d_verdict [B] (may be NULL).  The caller guarantees 1 <= p.N <= N_max and that fix_row / fix_kind exist.
+hipError_t pgs_launch_fix_attach(const PgsParams& p, double* fix_row, int32_t* fix_kind, const double* d_fix, const int32_t* d_kinds, int32_t* d_verdict, hipStream_t s);
+// The simulated source (fix_kernel.h: fix_sense_instance, its pair indices) on p.truth with the handle's seed, the global instance id and the RNG
+// step `step` (the one the next pgs_run_sim tick would use): fix [B][5], kinds [B], jumped [B] or NULL; rows [B] or NULL = all-zero rows.
+// Reads state, advances none.  d_rows: const slam_fix_sensor* (slam_batch.h).
+hipError_t pgs_launch_fix_sense(const PgsParams& p, const void* d_rows, uint32_t step, double* d_fix, int32_t* d_kinds, int32_t* d_jumped, hipStream_t s);
+// w of both parts of every fix at initial_estimate (which = 0) / result (1): out [B][N_max][2] (position, heading), NaN where no part is stored
+// and at poses the graph does not have, 1.0 without a fix loss.  Reads the graph and the values only.
+hipError_t pgs_launch_fix_weights(const PgsParams& p, int which, double* out, hipStream_t s);
 
 }  // namespace slam

@@ -27,6 +27,8 @@
 #include "slam_math.h"
 #include "slam_rng.h"
 #include "sim_device.h"
+#include "pgs_fix.h"
+#include "fix_kernel.h"
 
 namespace slam {
 namespace {
@@ -41,6 +43,7 @@ namespace {
 #include "pgs_lm_control.h"
 #include "pgs_seg_impl.h"
 #include "pgs_marginals.h"
+#include "pgs_fix_phase.h"
 
 }  // namespace
 
@@ -77,24 +80,32 @@ hipError_t pgs_launch_seg_plan(const PgsParams& p, hipStream_t s) {
 }
 
 hipError_t pgs_launch_lm_begin(const PgsParams& p, hipStream_t s) {
-    if (p.loss_kind != kPgsLossNone) hipLaunchKernelGGL(pgs_lm_begin_kernel<true>, dim3(p.b_cnt), dim3(TPB), 0, s, p);
-    else hipLaunchKernelGGL(pgs_lm_begin_kernel<false>, dim3(p.b_cnt), dim3(TPB), 0, s, p);
+    const bool rb = pgs_has_loss(p);
+    if (pgs_has_fixes(p)) {   // the handle has fixes: their terms join the cost (pgs_fix.h)
+        if (rb) hipLaunchKernelGGL((pgs_lm_begin_kernel<true, true>), dim3(p.b_cnt), dim3(TPB), 0, s, p);
+        else hipLaunchKernelGGL((pgs_lm_begin_kernel<false, true>), dim3(p.b_cnt), dim3(TPB), 0, s, p);
+    } else if (rb) hipLaunchKernelGGL((pgs_lm_begin_kernel<true, false>), dim3(p.b_cnt), dim3(TPB), 0, s, p);
+    else hipLaunchKernelGGL((pgs_lm_begin_kernel<false, false>), dim3(p.b_cnt), dim3(TPB), 0, s, p);
     return hipGetLastError();
 }
 
 hipError_t pgs_launch_trial_kernel(const PgsParams& p, int which, hipStream_t s) {
     const int nslot = pgs_nslot(p);   // slots covered: the instances of the group and their active lambda lanes, or the compacted list
     if (nslot <= 0) return hipSuccess;
+    // RB: a loss is set on the landmark factors or on the fixes; FX: the handle has fixes.  Without fixes these are the launches of before.
+    const bool rb = pgs_has_loss(p), fx = pgs_has_fixes(p);
     switch (which) {
     case 0:
-        if (p.loss_kind != kPgsLossNone) {   // the weighted factors and oldlin (pgs_robust.h); the same launches
+        if (rb) {   // the weighted factors and oldlin (pgs_robust.h); the same launches
             if (!p.lin0 || !p.oldlin) return hipErrorInvalidValue;
             if (p.nfact_max > 0) hipLaunchKernelGGL(pgs_lin_factor_kernel<true>, dim3(nslot * ((p.nfact_max + LF_TPB - 1) / LF_TPB)), dim3(LF_TPB), 0, s, p);
-            hipLaunchKernelGGL(pgs_linearize_kernel<true>, dim3(nslot), dim3(TPB), 0, s, p);
+            if (fx) hipLaunchKernelGGL((pgs_linearize_kernel<true, true>), dim3(nslot), dim3(TPB), 0, s, p);
+            else hipLaunchKernelGGL((pgs_linearize_kernel<true, false>), dim3(nslot), dim3(TPB), 0, s, p);
             break;
         }
         if (p.nfact_max > 0) hipLaunchKernelGGL(pgs_lin_factor_kernel<false>, dim3(nslot * ((p.nfact_max + LF_TPB - 1) / LF_TPB)), dim3(LF_TPB), 0, s, p);
-        hipLaunchKernelGGL(pgs_linearize_kernel<false>, dim3(nslot), dim3(TPB), 0, s, p);
+        if (fx) hipLaunchKernelGGL((pgs_linearize_kernel<false, true>), dim3(nslot), dim3(TPB), 0, s, p);
+        else hipLaunchKernelGGL((pgs_linearize_kernel<false, false>), dim3(nslot), dim3(TPB), 0, s, p);
         break;
     case 1: {
         if (p.seg_on) {   // segmented elimination: the interiors of all segments side by side, then the separator chain
@@ -160,11 +171,13 @@ hipError_t pgs_launch_trial_kernel(const PgsParams& p, int which, hipStream_t s)
     default:   // the candidates of every slot, then GTSAM's accept / lambda / convergence logic per instance
         if (p.nfact_max > 0) {
             const dim3 grid(nslot * ((p.nfact_max + LF_TPB - 1) / LF_TPB));
-            if (p.loss_kind != kPgsLossNone) hipLaunchKernelGGL(pgs_eval_factor_kernel<true>, grid, dim3(LF_TPB), 0, s, p);
+            if (rb) hipLaunchKernelGGL(pgs_eval_factor_kernel<true>, grid, dim3(LF_TPB), 0, s, p);
             else hipLaunchKernelGGL(pgs_eval_factor_kernel<false>, grid, dim3(LF_TPB), 0, s, p);
         }
-        hipLaunchKernelGGL(pgs_evaluate_kernel, dim3(nslot), dim3(TPB), 0, s, p);
-        if (p.loss_kind != kPgsLossNone) hipLaunchKernelGGL(pgs_decide_kernel<true>, dim3(p.b_cnt), dim3(TPB), 0, s, p);
+        if (!fx) hipLaunchKernelGGL((pgs_evaluate_kernel<false, false>), dim3(nslot), dim3(TPB), 0, s, p);
+        else if (rb) hipLaunchKernelGGL((pgs_evaluate_kernel<true, true>), dim3(nslot), dim3(TPB), 0, s, p);
+        else hipLaunchKernelGGL((pgs_evaluate_kernel<false, true>), dim3(nslot), dim3(TPB), 0, s, p);
+        if (rb) hipLaunchKernelGGL(pgs_decide_kernel<true>, dim3(p.b_cnt), dim3(TPB), 0, s, p);
         else hipLaunchKernelGGL(pgs_decide_kernel<false>, dim3(p.b_cnt), dim3(TPB), 0, s, p);
         break;
     }
@@ -210,6 +223,24 @@ hipError_t pgs_launch_marginals(const PgsParams& p, int which, double* pose_cov,
 hipError_t pgs_launch_factor_weights(const PgsParams& p, int which, double* out, hipStream_t s) {
     const int nfb = (p.N_max * p.KP + LF_TPB - 1) / LF_TPB;
     hipLaunchKernelGGL(pgs_factor_weights_kernel, dim3(p.B * nfb), dim3(LF_TPB), 0, s, p, which, out);
+    return hipGetLastError();
+}
+
+hipError_t pgs_launch_fix_attach(const PgsParams& p, double* fix_row, int32_t* fix_kind, const double* d_fix, const int32_t* d_kinds, int32_t* d_verdict, hipStream_t s) {
+    if (!fix_row || !fix_kind || !d_fix || !d_kinds || p.N < 1 || p.N > p.N_max) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pgs_fix_attach_kernel, dim3((p.B + 255) / 256), dim3(256), 0, s, p, fix_row, fix_kind, d_fix, d_kinds, d_verdict);
+    return hipGetLastError();
+}
+
+hipError_t pgs_launch_fix_sense(const PgsParams& p, const void* d_rows, uint32_t step, double* d_fix, int32_t* d_kinds, int32_t* d_jumped, hipStream_t s) {
+    if (!d_fix || !d_kinds || !p.truth) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pgs_fix_sense_kernel, dim3((p.B + 255) / 256), dim3(256), 0, s, p, (const slam_fix_sensor*)d_rows, step, d_fix, d_kinds, d_jumped);
+    return hipGetLastError();
+}
+
+hipError_t pgs_launch_fix_weights(const PgsParams& p, int which, double* out, hipStream_t s) {
+    if (!out || !p.fix_row || !p.fix_kind) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pgs_fix_weights_kernel, dim3(p.B * ((p.N_max + 255) / 256)), dim3(256), 0, s, p, which, out);
     return hipGetLastError();
 }
 

@@ -19,7 +19,7 @@ __device__ __forceinline__ int pgs_slot(const PgsParams& p, int bl) {
 // slots a trial-kernel launch covers
 __host__ __device__ __forceinline__ int pgs_nslot(const PgsParams& p) { return p.use_list ? p.n_list : p.b_cnt * (p.lanes > 0 ? p.lanes : 1); }
 
-template <bool RB>   // RB: a robust loss is set - the initial cost is sum rho (pgs_robust.h)
+template <bool RB, bool FX>   // RB: a robust loss is set - the initial cost is sum rho (pgs_robust.h); FX: the handle has fixes (pgs_fix.h)
 __global__ __launch_bounds__(TPB) void pgs_lm_begin_kernel(const PgsParams p) {
     __shared__ double s_buf[TPB];
     const int b = blockIdx.x + p.b_off, tid = threadIdx.x;
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(TPB) void pgs_lm_begin_kernel(const PgsParams p) {
         f = block_sum<TPB>(f, s_buf);
         if (tid == 0) p.inst_flop[b] = f + extra;
     }
-    const double err = block_cost<TPB, RB>(p, b, N, pw, lw, s_buf);
+    const double err = block_cost<TPB, RB, FX>(p, b, N, pw, lw, s_buf);
     if (tid == 0) {
         p.error[b] = err; p.err_init[b] = err; p.cur_error[b] = err;
         p.lambda[b] = 1e-5;                    // LevenbergMarquardtParams::lambdaInitial
@@ -209,7 +209,9 @@ __global__ __launch_bounds__(LF_TPB) void pgs_lin_factor_kernel(const PgsParams 
 // Linearisation, part 2: per pose the prior / between factors and the sum of its factors' shares (slot order); per landmark the sum of
 // its factors' terms (chronological order).  RB: also oldlin, the linearised cost at delta = 0 - per pose the Gaussian terms and its factors'
 // lin0 in pose_cost's order, per thread and over the block in block_cost's; with every weight 1 these are the bits of block_cost.
-template <bool RB>
+// FX (the handle has fixes, pgs_fix.h): the parts stored at a pose add J^T J to A, -J^T e to the gradient - after the between shares, before the
+// factors' - and (RB) 0.5 w ss to pc, position then heading; a part is linearised as sw e, sw J with the weight of the fix loss at these values.
+template <bool RB, bool FX>
 __global__ __launch_bounds__(TPB) void pgs_linearize_kernel(const PgsParams p) {
     __shared__ double s_buf[RB ? TPB : 1];
     const int b = pgs_slot(p, blockIdx.x), tid = threadIdx.x;
@@ -250,6 +252,41 @@ __global__ __launch_bounds__(TPB) void pgs_linearize_kernel(const PgsParams p) {
             add_JtJ<3>(A, J1);
 #pragma unroll
             for (int a = 0; a < 3; ++a) gg[a] += -(J1[a] * e[0] + J1[3 + a] * e[1] + J1[6 + a] * e[2]);
+        }
+        if (FX) {
+            const FixView f = fix_view(p, b);
+            const int fk = f.kind[i];
+            const double* row = f.row + (size_t)kPgsFixRowLen * i;
+            if (fk & kPgsFixPos) {
+                double e2[2], Jf[6];
+                pgs_fix_pos<true>(pose + 3 * i, row, e2, Jf);
+                if (RB) {
+                    const double ss = e2[0] * e2[0] + e2[1] * e2[1];
+                    double rho, w, sw;
+                    pgs_robust_loss(p.fix_loss_kind, p.fix_loss_k, ss, sqrt(ss), &rho, &w, &sw);
+                    pc = pc + 0.5 * (w * ss);
+                    e2[0] *= sw; e2[1] *= sw;
+#pragma unroll
+                    for (int a = 0; a < 6; ++a) Jf[a] *= sw;
+                }
+                add_JtJ<2>(A, Jf);
+#pragma unroll
+                for (int a = 0; a < 3; ++a) gg[a] += -(Jf[a] * e2[0] + Jf[3 + a] * e2[1]);
+            }
+            if (fk & kPgsFixYaw) {
+                double Jf[3] = {0.0, 0.0, 0.0};
+                double e1 = pgs_fix_yaw(pose + 3 * i, row, &Jf[2]);
+                if (RB) {
+                    const double ss = e1 * e1;
+                    double rho, w, sw;
+                    pgs_robust_loss(p.fix_loss_kind, p.fix_loss_k, ss, sqrt(ss), &rho, &w, &sw);
+                    pc = pc + 0.5 * (w * ss);
+                    e1 *= sw; Jf[2] *= sw;
+                }
+                add_JtJ<1>(A, Jf);
+#pragma unroll
+                for (int a = 0; a < 3; ++a) gg[a] += -(Jf[a] * e1);
+            }
         }
         const int kc = g.cnt[i];
         const double* PF = PFb + (size_t)i * KP * 12;

@@ -66,6 +66,11 @@ __global__ __launch_bounds__(LF_TPB) void pgs_eval_factor_kernel(const PgsParams
 
 // linearised cost of the step, retraction, true cost of the candidate (part 2: the prior / between factors and the sums); GTSAM's
 // tryLambda / iterate / defaultOptimize decisions follow in pgs_decide_kernel (LevenbergMarquardtOptimizer.cpp, NonlinearOptimizer.cpp).
+// FX (the handle has fixes, pgs_fix.h): the fix parts stored at a pose join both sums after the between factor and before the bearing-range terms,
+// position then heading - linearised as pgs_linearize_kernel linearised them (RB: sw e, sw J with the weight of the fix loss at the current
+// values, which are the linearisation point), costed at the candidate with 0.5 ss or (RB) rho.  <false, false> is the kernel of before; RB
+// matters only to the fix parts here (the landmark factors' terms come from pgs_eval_factor_kernel).
+template <bool RB, bool FX>
 __global__ __launch_bounds__(TPB) void pgs_evaluate_kernel(const PgsParams p) {
     __shared__ double s_buf[TPB];
     const int b = pgs_slot(p, blockIdx.x), tid = threadIdx.x;
@@ -95,6 +100,40 @@ __global__ __launch_bounds__(TPB) void pgs_evaluate_kernel(const PgsParams p) {
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {
                     const double v = (e[r] + ((J1[3 * r] * dp[3 * i] + J1[3 * r + 1] * dp[3 * i + 1]) + J1[3 * r + 2] * dp[3 * i + 2])) + p.w_btw[r] * dp[3 * (i + 1) + r];
+                    acc = acc + 0.5 * v * v;
+                }
+            }
+            if (FX) {
+                const FixView f = fix_view(p, b);
+                const int fk = f.kind[i];
+                const double* row = f.row + (size_t)kPgsFixRowLen * i;
+                if (fk & kPgsFixPos) {
+                    double e2[2], Jf[6];
+                    pgs_fix_pos<true>(pose + 3 * i, row, e2, Jf);
+                    if (RB) {
+                        const double ss = e2[0] * e2[0] + e2[1] * e2[1];
+                        double rho, w, sw;
+                        pgs_robust_loss(p.fix_loss_kind, p.fix_loss_k, ss, sqrt(ss), &rho, &w, &sw);
+                        e2[0] *= sw; e2[1] *= sw;
+#pragma unroll
+                        for (int a = 0; a < 6; ++a) Jf[a] *= sw;
+                    }
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) {
+                        const double v = e2[r] + ((Jf[3 * r] * dp[3 * i] + Jf[3 * r + 1] * dp[3 * i + 1]) + Jf[3 * r + 2] * dp[3 * i + 2]);
+                        acc = acc + 0.5 * v * v;
+                    }
+                }
+                if (fk & kPgsFixYaw) {
+                    double wy;
+                    double e1 = pgs_fix_yaw(pose + 3 * i, row, &wy);
+                    if (RB) {
+                        const double ss = e1 * e1;
+                        double rho, w, sw;
+                        pgs_robust_loss(p.fix_loss_kind, p.fix_loss_k, ss, sqrt(ss), &rho, &w, &sw);
+                        e1 *= sw; wy *= sw;
+                    }
+                    const double v = e1 + wy * dp[3 * i + 2];
                     acc = acc + 0.5 * v * v;
                 }
             }
@@ -129,6 +168,7 @@ __global__ __launch_bounds__(TPB) void pgs_evaluate_kernel(const PgsParams p) {
                 between_factor<false>(p, pose_n + 3 * i, pose_n + 3 * (i + 1), g.cmds[2 * i], g.cmds[2 * i + 1], e, nullptr);
                 pc = pc + 0.5 * ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
             }
+            if (FX) pc = add_fix_cost<RB>(p, fix_view(p, b), pose_n + 3 * i, i, pc);
             const int kc = g.cnt[i];
             const double* PF = PFb + (size_t)i * KP * 3 + 2;
             constexpr int UB = 8;

@@ -13,8 +13,21 @@ import math
 import numpy as np
 
 from . import _lib
-from .config import SlamConfig, default_config
+from .config import SlamConfig, default_config, FixSensorConfig, default_fix_sensor_config, FIX_POS, FIX_YAW   # noqa: F401
 from .filters import Command, _d, _f, _i
+
+FIX_ABSENT, FIX_STORED, FIX_INVALID = 0, 1, 4            # pgs_fix_verdict (slam_pgs.h)
+
+
+def fix_factor_host(pose, row, kinds, loss_kind=0, loss_k=0.0):
+    """TEST HOOK (pgs_fix_factor_host): one fix factor at `pose` (x, y, yaw), the kernels' source compiled for the host; no GPU.  Returns
+    dict(e (3,), J (3, 3) - rows 0, 1 position, row 2 heading, without the loss -, rho (2,), w (2,), verdict)."""
+    p = np.ascontiguousarray(pose, dtype=np.float64); r = np.ascontiguousarray(row, dtype=np.float64)
+    if p.shape != (3,) or r.shape != (5,):
+        raise ValueError("pose (3,) and row (5,) expected")
+    e = np.zeros(3); J = np.zeros((3, 3)); rho = np.zeros(2); w = np.zeros(2); v = C.c_int32(0)
+    _lib.check(_lib.lib().pgs_fix_factor_host(_d(p), _d(r), int(kinds), int(loss_kind), float(loss_k), _d(e), _d(J), _d(rho), _d(w), C.byref(v)))
+    return dict(e=e, J=J, rho=rho, w=w, verdict=v.value)
 
 
 LOSS_NONE, LOSS_HUBER, LOSS_GEMAN_MCCLURE = 0, 1, 2      # pgs_loss_kind (slam_pgs.h)
@@ -378,6 +391,92 @@ class BatchedPoseGraph:
         for b in range(self.batch):
             _lib.check(_lib.lib().pgs_get_factor_weights(self.h, b, _d(out[b]), N * self.k_per_pose, C.byref(n)))
         return out
+
+    # -- absolute fixes: unary pose factors (slam_pgs.h "absolute fixes") --
+    def fix(self, fix, kinds, dev=False):
+        """One fix per instance at the graph's newest pose: fix (batch, 5) rows {z_x, z_y, z_yaw, sigma_pos, sigma_yaw}, kinds [batch]
+        (FIX_POS | FIX_YAW).  Returns the verdicts [batch] (position | heading << 4; 0 absent, 1 stored, 4 invalid).  dev=True: fix and
+        kinds are DEVICE pointers read in stream order (pgs_fix_dev); returns None."""
+        self._need()
+        if dev:
+            _lib.check(_lib.lib().pgs_fix_dev(self.h, C.c_void_p(fix), C.c_void_p(kinds), None))
+            return None
+        f = np.ascontiguousarray(self._rows(np.asarray(fix, dtype=np.float64), "fix", 5))
+        k = np.ascontiguousarray(kinds, dtype=np.int32)
+        if k.shape != (self.batch,):
+            raise ValueError(f"kinds: expected shape ({self.batch},), got {k.shape}")
+        verdict = np.zeros(self.batch, dtype=np.int32)
+        _lib.check(_lib.lib().pgs_fix(self.h, _d(f), _i(k), _i(verdict)))
+        return verdict
+
+    def set_fix_robust(self, kind, k=0.0):
+        """Loss of every fix part from the next solve / marginals / fix_weights on (kinds and parameter as set_robust)."""
+        self._need()
+        kind = LOSS_KINDS[kind] if isinstance(kind, str) else int(kind)
+        _lib.check(_lib.lib().pgs_set_fix_robust(self.h, kind, float(k)))
+
+    @property
+    def fix_robust(self):
+        """(kind, k) of the fix loss as set."""
+        self._need(); kind = C.c_int(0); k = C.c_double(0.0)
+        _lib.check(_lib.lib().pgs_get_fix_robust(self.h, C.byref(kind), C.byref(k)))
+        return kind.value, k.value
+
+    def fixes(self, instance=0):
+        """The stored fixes of one instance: dict(fix (timestep + 1, 5), kinds [timestep + 1]); kinds 0 where a pose has none."""
+        self._need()
+        N = self.timestep + 1
+        f = np.zeros((N, 5)); k = np.zeros(N, dtype=np.int32); n = C.c_int32(0)
+        _lib.check(_lib.lib().pgs_get_fixes(self.h, int(instance), _d(f), _i(k), N, C.byref(n)))
+        return dict(fix=f, kinds=k)
+
+    def fix_weights(self, which=None):
+        """IRLS weight of both parts of every fix at initial_estimate (which = 0) / result (1; default as get_graph):
+        [batch][timestep + 1][2] (position, heading), NaN where a part is not stored; 1.0 without a fix loss."""
+        self._need()
+        which = int(self.solved_pose_graph) if which is None else int(which)
+        _lib.check(_lib.lib().pgs_fix_weights(self.h, which))
+        N = self.timestep + 1
+        out = np.zeros((self.batch, N, 2))
+        n = C.c_int32(0)
+        for b in range(self.batch):
+            _lib.check(_lib.lib().pgs_get_fix_weights(self.h, b, _d(out[b]), N, C.byref(n)))
+        return out
+
+    def set_fix_sensor(self, rows):
+        """The simulated source of fix_sense() and run_sim_fix (pgs_set_fix_sensor_each): one FixSensorConfig (or a dict of its fields),
+        replicated over the batch, or `batch` of them; None returns to the all-zero row, which emits nothing."""
+        self._need()
+        if rows is None:
+            _lib.check(_lib.lib().pgs_set_fix_sensor_each(self.h, None))
+            return
+        if isinstance(rows, dict):
+            rows = default_fix_sensor_config(**rows)
+        if isinstance(rows, FixSensorConfig):
+            rows = [rows] * self.batch
+        if not (isinstance(rows, C.Array) and rows._type_ is FixSensorConfig):
+            rows = (FixSensorConfig * len(rows))(*rows)
+        if len(rows) != self.batch:
+            raise ValueError(f"expected {self.batch} fix sensor rows, got {len(rows)}")
+        _lib.check(_lib.lib().pgs_set_fix_sensor_each(self.h, rows))
+
+    def fix_sense(self, dev=None):
+        """One emission of the simulated source from the simulator's true poses: dict(fix (batch, 5), kinds [batch], jumped [batch]).
+        dev = (d_fix, d_kinds, d_jumped or None): DEVICE pointers, written in stream order; returns None."""
+        self._need()
+        if dev is not None:
+            _lib.check(_lib.lib().pgs_fix_sense_dev(self.h, C.c_void_p(dev[0]), C.c_void_p(dev[1]), C.c_void_p(dev[2]) if dev[2] else None))
+            return None
+        out = dict(fix=np.zeros((self.batch, 5)), kinds=np.zeros(self.batch, dtype=np.int32), jumped=np.zeros(self.batch, dtype=np.int32))
+        _lib.check(_lib.lib().pgs_fix_sense(self.h, _d(out["fix"]), _i(out["kinds"]), _i(out["jumped"])))
+        return out
+
+    def run_sim_fix(self, cmds, fix_every):
+        """run_sim with a fix of the simulated source attached after every fix_every-th tick of the call, all on the device."""
+        self._need()
+        c = self._cmds(cmds)
+        _lib.check(_lib.lib().pgs_run_sim_fix(self.h, _f(c), c.shape[0], int(c.ndim == 3), int(fix_every)))
+        self.timestep += c.shape[0]
 
     def error_stats(self, which=1):
         self._need(); out = np.zeros(self.batch); _lib.check(_lib.lib().pgs_error_stats(self.h, int(which), _d(out))); return out
