@@ -6,6 +6,17 @@ path reads (Filter::readCommonParams, filter.h:105-121; get_cmd, sim_node.py:209
 import ctypes as C
 
 
+def set_fields(c, fields, noun):
+    """Sets fields of the ctypes struct c from a dict; a name c does not have is refused as an unknown `noun` setting.  An array field
+    (JointConfig.gate_joint) takes a sequence of numbers."""
+    types = dict(c._fields_)
+    for k, v in dict(fields).items():
+        if k not in types:
+            raise ValueError(f"unknown {noun} setting {k!r}")
+        setattr(c, k, types[k](*[float(g) for g in v]) if issubclass(types[k], C.Array) else v)
+    return c
+
+
 class SlamConfig(C.Structure):
     _fields_ = [
         ("v_d", C.c_float), ("v_th", C.c_float),
@@ -212,12 +223,7 @@ SENSE_INSTANCE_FROZEN, SENSE_TOO_LONG = 1, 2
 
 def default_sensor_config(**fields) -> SensorConfig:
     """The all-off row (every field 0): the message of the plain simulator step.  Keyword arguments set fields."""
-    row = SensorConfig()
-    for k, v in fields.items():
-        if k not in SENSOR_FIELDS:
-            raise ValueError(f"unknown sensor setting {k!r}")
-        setattr(row, k, v)
-    return row
+    return set_fields(SensorConfig(), fields, "sensor")
 
 
 class SenseLog(C.Structure):
@@ -257,12 +263,7 @@ FIX_SENSOR_FIELDS = tuple(name for name, _ in FixSensorConfig._fields_)
 
 def default_fix_sensor_config(**fields) -> FixSensorConfig:
     """The all-zero row, which emits nothing.  Keyword arguments set fields."""
-    row = FixSensorConfig()
-    for k, v in fields.items():
-        if k not in FIX_SENSOR_FIELDS:
-            raise ValueError(f"unknown fix sensor setting {k!r}")
-        setattr(row, k, v)
-    return row
+    return set_fields(FixSensorConfig(), fields, "fix sensor")
 
 
 class FixLog(C.Structure):

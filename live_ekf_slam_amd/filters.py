@@ -6,44 +6,29 @@ The reference drives ONE filter object through
 90-106,108-140).  `BatchedEKF` keeps those names, argument meanings and the exception-on-error convention, for a
 batch of B instances that share map + commands (Monte-Carlo seeds) or get their own start pose, map and commands (several robots or
 scenarios: the per-instance forms of init / set_map / update / run_sim); everything numeric happens in libslam_hip.so.
-The C++ twin of this class (for a C++/ROS host) is include/slam_filter.hpp.
+The C++ twin of this class (for a C++/ROS host) is include/slam_filter.hpp.  How arguments become pointers, structs and rows is in
+_marshal.py; the *_instance_host test hooks are in _hooks.py and re-exported here.
 """
 import ctypes as C
 import numpy as np
 
 from . import _lib
-from .config import SlamConfig, NavConfig, default_config, default_nav_config, EKF_SLAM, UKF_LOC, UKF_SLAM, F64
-from .config import MonitorConfig, default_monitor_config, MONITOR_SHARED, MONITOR_EACH, MONITOR_NAV
+from ._marshal import Handle, Command, _d, _f, _i, ptr, opt, config_from   # noqa: F401
+from ._marshal import MONITOR, NAV, INNOVATION, GATE, ASSOC, JOINT, MAP, MERGE, FIX
+from ._hooks import (sense_instance_host, fix_instance_host, fix_sense_instance_host, merge_instance_host, map_instance_host,   # noqa: F401
+                     innovation_instance_host, gate_instance_host, associate_instance_host, associate_joint_instance_host)
+from .config import SlamConfig, NavConfig, default_config, default_nav_config, EKF_SLAM, UKF_LOC, UKF_SLAM, F64   # noqa: F401
+from .config import MonitorConfig, default_monitor_config, MONITOR_SHARED, MONITOR_EACH, MONITOR_NAV   # noqa: F401
 from .config import Noise
-from .config import (InnovationConfig, default_innovation_config, INNOVATION_SHARED, INNOVATION_EACH, INNOVATION_NAV, INNOVATION_LOG,
+from .config import (InnovationConfig, default_innovation_config, INNOVATION_SHARED, INNOVATION_EACH, INNOVATION_NAV, INNOVATION_LOG,   # noqa: F401
                      INNOV_MAX_DET)
-from .config import GateConfig, default_gate_config
-from .config import AssocConfig, default_assoc_config
-from .config import JointConfig, default_joint_config
-from .config import MapConfig, default_map_config, MAP_CONFIG_FIELDS
-from .config import MergeConfig, default_merge_config, MERGE_CONFIG_FIELDS
+from .config import GateConfig, default_gate_config   # noqa: F401
+from .config import AssocConfig, default_assoc_config   # noqa: F401
+from .config import JointConfig, default_joint_config   # noqa: F401
+from .config import MapConfig, default_map_config, MAP_CONFIG_FIELDS   # noqa: F401
+from .config import MergeConfig, default_merge_config, MERGE_CONFIG_FIELDS   # noqa: F401
 from .config import SensorConfig, SenseLog, default_sensor_config
-from .config import FixConfig, FixSensorConfig, FixLog, default_fix_config, default_fix_sensor_config, FIX_CONFIG_FIELDS
-
-
-def _d(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _f(a):
-    return a.ctypes.data_as(C.POINTER(C.c_float))
-
-
-def _i(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int32))
-
-
-class Command:
-    """base_pkg/Command (Command.msg:3-5): float32 fwd, ang."""
-
-    def __init__(self, fwd=0.0, ang=0.0):
-        self.fwd = float(np.float32(fwd))
-        self.ang = float(np.float32(ang))
+from .config import FixConfig, FixSensorConfig, FixLog, default_fix_config, default_fix_sensor_config, FIX_CONFIG_FIELDS   # noqa: F401
 
 
 class MonitorResult:
@@ -104,18 +89,7 @@ class JointResult:
 
 def _joint_config(cfg):
     """A JointConfig from None (the defaults), a JointConfig or a dict of its fields (gate_joint: 16 values)."""
-    if cfg is None:
-        return default_joint_config()
-    if isinstance(cfg, JointConfig):
-        return cfg
-    c = default_joint_config()
-    for k, v in dict(cfg).items():
-        if k not in ("gate_match", "gate_new", "gate_joint", "max_nodes"):
-            raise ValueError(f"unknown joint association setting {k!r}")
-        if k == "gate_joint":
-            v = (C.c_double * 16)(*[float(g) for g in v])
-        setattr(c, k, v)
-    return c
+    return config_from(cfg, *JOINT)
 
 
 class MapResult(AssocResult):
@@ -154,10 +128,11 @@ class FixResult:
         self.recs, self.verdict, self.nis, self.fix, self.kinds = recs, verdict, nis, fix, kinds
 
 
-class BatchedFilter:
+class BatchedFilter(Handle):
     """Common part of the batched filters (reference: class Filter, filter.h:54-145)."""
 
     kind = None
+    _INIT, _INIT_EACH, _DESTROY = "slam_init", "slam_init_each", "slam_destroy"
 
     def __init__(self, batch, L_max, device=0, dtype=F64):
         self.batch, self.L_max, self.device, self.dtype = int(batch), int(L_max), int(device), dtype
@@ -202,30 +177,11 @@ class BatchedFilter:
         self.n_max = L.slam_state_dim_max(self.h)
         return self
 
-    def _need(self):
-        if self.h is None:
-            raise _lib.SlamError("readParams() must be called before using the filter")
-
     # -- Filter::init(float x_0, float y_0, float yaw_0) (filter.h:60) --
     def init(self, x_0=0.0, y_0=0.0, yaw_0=0.0, truth0=None):
         """Scalars: one start pose for the batch.  x_0 a (batch, 3) array of (x, y, yaw): one per instance (slam_init_each; y_0 and
         yaw_0 are then ignored).  truth0: optional (batch, 3) true start poses of the simulator (default: the config's init pose)."""
-        self._need()
-        if np.ndim(x_0) == 0 and truth0 is None:
-            _lib.check(_lib.lib().slam_init(self.h, x_0, y_0, yaw_0))
-        else:
-            pose = (np.asarray(x_0, dtype=np.float32) if np.ndim(x_0) else
-                    np.broadcast_to(np.array([x_0, y_0, yaw_0], dtype=np.float32), (self.batch, 3)))
-            pose = np.ascontiguousarray(self._rows(pose, "x_0", 3), dtype=np.float32)
-            tr = None if truth0 is None else np.ascontiguousarray(self._rows(np.asarray(truth0, dtype=np.float64), "truth0", 3))
-            _lib.check(_lib.lib().slam_init_each(self.h, _f(pose), None if tr is None else _d(tr)))
-        self.isInit = True
-        self.timestep = 0
-
-    def _rows(self, a, what, width):
-        if a.shape != (self.batch, width):
-            raise ValueError(f"{what}: expected shape ({self.batch}, {width}), got {a.shape}")
-        return a
+        self._init(x_0, y_0, yaw_0, truth0)
 
     # -- batch plumbing that has no counterpart in the single-instance reference --
     def set_stream(self, hip_stream_ptr):
@@ -272,15 +228,7 @@ class BatchedFilter:
     def set_noise(self, rows):
         """Per-instance noise parameters (slam_set_noise_each): `rows` = config.noise_rows(...) (a ctypes array of `batch` Noise rows,
         or a sequence of them); None returns to the config of readParams.  Inputs, not state: set them again after load_state."""
-        self._need()
-        if rows is None:
-            _lib.check(_lib.lib().slam_set_noise_each(self.h, None))
-            return
-        if not (isinstance(rows, C.Array) and rows._type_ is Noise):
-            rows = (Noise * len(rows))(*rows)
-        if len(rows) != self.batch:
-            raise ValueError(f"expected {self.batch} noise rows, got {len(rows)}")
-        _lib.check(_lib.lib().slam_set_noise_each(self.h, rows))
+        self._set_rows("slam_set_noise_each", rows, Noise, "noise")
 
     # -- Filter::update(Command, Float32MultiArray) (filter.h:61) for every instance --
     def update(self, cmdMsg, lmMeasMsg, meas_count=None):
@@ -347,17 +295,6 @@ class BatchedFilter:
                 raise ValueError(f"expected commands of shape (T, 2) or (T, {self.batch}, 2), got {c.shape}")
             _lib.check(_lib.lib().slam_run_sim(self.h, _f(c), c.shape[0]))
         self.timestep += c.shape[0]
-
-    def _cmd(self, cmdMsg):
-        """(2,) float32 for one command, (batch, 2) for one per instance."""
-        if isinstance(cmdMsg, Command):
-            return np.array([cmdMsg.fwd, cmdMsg.ang], dtype=np.float32)
-        c = np.ascontiguousarray(cmdMsg, dtype=np.float32)
-        if c.shape == (self.batch, 2):
-            return c
-        if c.size == 2:
-            return c.reshape(2)
-        raise ValueError(f"expected a command of shape (2,) or ({self.batch}, 2), got {c.shape}")
 
     # -- Filter::getStateVector() (filter.h:76; ekf.cpp:181-184) --
     def getStateVector(self, instance=0):
@@ -474,51 +411,40 @@ class BatchedFilter:
 
     def last_consistency_work(self):
         """(bytes the model says the last consistency() had to read, its device time in ms)."""
-        self._need(); b = C.c_double(0); ms = C.c_double(0)
-        _lib.check(_lib.lib().slam_last_consistency_work(self.h, C.byref(b), C.byref(ms)))
-        return b.value, ms.value
+        return self._last_work("slam_last_consistency_work", 2)
 
     # -- no counterpart in the reference: the error and the pose NEES at every tick of a run (slam_monitor_*, include/slam_batch.h) --
-    def _monitor_config(self, cfg):
-        if cfg is None:
-            return default_monitor_config()
-        if isinstance(cfg, MonitorConfig):
-            return cfg
-        c = default_monitor_config()
-        for k, v in dict(cfg).items():
-            if k not in ("nees_lo", "nees_hi", "full_every"):
-                raise ValueError(f"unknown monitor setting {k!r}")
-            setattr(c, k, v)
-        return c
-
     def monitor_now(self, cfg=None):
         """One monitor evaluation at the current state, changing nothing: dict of rec (16,), err_pos, err_yaw, nees_pose, flags [batch]
         (flags: POSE_NOT_PD, INSTANCE_FAILED).  cfg: a MonitorConfig, a dict of its fields, or None for the defaults."""
         self._need()
-        c = self._monitor_config(cfg)
+        c = config_from(cfg, *MONITOR)
         out = dict(rec=np.zeros(16), err_pos=np.zeros(self.batch), err_yaw=np.zeros(self.batch), nees_pose=np.zeros(self.batch),
                    flags=np.zeros(self.batch, dtype=np.int32))
         _lib.check(_lib.lib().slam_monitor_now(self.h, C.byref(c), _d(out["rec"]), _d(out["err_pos"]), _d(out["err_yaw"]), _d(out["nees_pose"]),
                                                _i(out["flags"])))
         return out
 
-    def _run_cmds(self, name, cmds, T):
-        """The (cmds, T) arguments of monitor_run and innovation_run as (float32 commands or None, source, T).  The sources, numbered
-        alike in slam_monitor_source and slam_innovation_source: (T, 2) SHARED, (T, batch, 2) EACH, no commands but T ticks NAV."""
+    def _run_cmds(self, name, cmds, T, source=None):
+        """The (cmds, T, source) arguments of a run the simulator feeds as (float32 commands or None, source, T).  The sources, numbered
+        alike in slam_monitor_source and slam_innovation_source: (T, 2) SHARED, (T, batch, 2) EACH, no commands but T ticks NAV unless
+        `source` says otherwise; with commands, a `source` must be the one their shape implies."""
         if cmds is None:
             if T is None:
                 raise ValueError(f"{name} needs commands or, for the closed loop, a number of ticks T")
-            return None, MONITOR_NAV, int(T)
+            return None, int(MONITOR_NAV if source is None else source), int(T)
         c32 = np.ascontiguousarray(cmds, dtype=np.float32)
         if c32.ndim == 3 and c32.shape[1:] == (self.batch, 2):
-            source = MONITOR_EACH
+            want = MONITOR_EACH
         elif c32.ndim == 2 and c32.shape[1] == 2:
-            source = MONITOR_SHARED
+            want = MONITOR_SHARED
         else:
             raise ValueError(f"expected commands of shape (T, 2) or (T, {self.batch}, 2), got {c32.shape}")
         if T is not None and int(T) != c32.shape[0]:
             raise ValueError(f"T = {T} does not match the {c32.shape[0]} commands")
-        return c32, source, c32.shape[0]
+        if source is not None and source != want:
+            raise ValueError(f"source {source} does not match commands of shape {c32.shape}")
+        return c32, want, c32.shape[0]
 
     def monitor_run(self, cmds=None, T=None, source=None, series=False, cfg=None):
         """A monitored run: per tick one simulator timestep and one monitor evaluation, all on the device; the same bits as the
@@ -526,42 +452,22 @@ class BatchedFilter:
         controller of set_path / set_paths issues them (source MONITOR_NAV).  Returns a MonitorResult; series=True also records the
         per-instance err_pos, err_yaw and nees_pose of every tick."""
         self._need()
-        c32, want, T = self._run_cmds("monitor_run", cmds, T)
-        if c32 is None:
-            source = want if source is None else source
-        elif source is not None and source != want:
-            raise ValueError(f"source {source} does not match commands of shape {c32.shape}")
-        else:
-            source = want
+        c32, source, T = self._run_cmds("monitor_run", cmds, T, source)
         n = max(T, 0)
         res = MonitorResult(np.zeros((n, 16)))
         if series:
             res.err_pos, res.err_yaw, res.nees_pose = (np.zeros((n, self.batch)) for _ in range(3))
-        ptr = (lambda a: None if a is None or a.size == 0 else _d(a))
-        _lib.check(_lib.lib().slam_monitor_run(self.h, C.byref(self._monitor_config(cfg)), int(source), None if c32 is None else _f(c32), T,
-                                               ptr(res.recs), ptr(res.err_pos), ptr(res.err_yaw), ptr(res.nees_pose)))
+        c = config_from(cfg, *MONITOR)
+        _lib.check(_lib.lib().slam_monitor_run(self.h, C.byref(c), source, ptr(c32), T,
+                                               opt(res.recs), opt(res.err_pos), opt(res.err_yaw), opt(res.nees_pose)))
         self.timestep += n
         return res
 
     def last_monitor_work(self):
         """(device ms of what the monitor added to the last monitor_run, or -1 without set_nav_timing; device ms of the whole run)."""
-        self._need(); a = C.c_double(0); b = C.c_double(0)
-        _lib.check(_lib.lib().slam_last_monitor_work(self.h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return self._last_work("slam_last_monitor_work", 2)
 
     # -- closed loop: goal_pursuit_node.py:23-50 on the device (slam_nav_*, include/slam_batch.h) --
-    def _nav_config(self, nav):
-        if nav is None:
-            return default_nav_config()
-        if isinstance(nav, NavConfig):
-            return nav
-        c = default_nav_config()
-        for k, v in dict(nav).items():
-            if k not in ("dt", "lookahead_dist_init", "lookahead_dist_max", "method", "control"):
-                raise ValueError(f"unknown controller setting {k!r}")
-            setattr(c, k, v)
-        return c
-
     def set_path(self, pts, nav=None):
         """One path (P, 2) of waypoints for every instance; nav: a NavConfig, a dict of its fields, or None for the reference's
         defaults (pure pursuit, loose control).  Resets the controller state."""
@@ -569,7 +475,7 @@ class BatchedFilter:
         p = np.ascontiguousarray(pts, dtype=np.float64)
         if p.ndim != 2 or p.shape[1] != 2:
             raise ValueError(f"expected a path of shape (P, 2), got {p.shape}")
-        c = self._nav_config(nav)
+        c = config_from(nav, *NAV)
         _lib.check(_lib.lib().slam_nav_set_path(self.h, C.byref(c), _d(p), p.shape[0]))
 
     def set_paths(self, paths, counts=None, nav=None):
@@ -591,7 +497,7 @@ class BatchedFilter:
         cnt = np.full(self.batch, a.shape[1], np.int32) if counts is None else np.ascontiguousarray(counts, dtype=np.int32)
         if cnt.shape != (self.batch,):
             raise ValueError(f"counts: expected {self.batch} waypoint counts")
-        c = self._nav_config(nav)
+        c = config_from(nav, *NAV)
         _lib.check(_lib.lib().slam_nav_set_paths(self.h, C.byref(c), _d(a), _i(cnt), a.shape[1]))
 
     def run_nav(self, T, return_cmds=False):
@@ -600,7 +506,7 @@ class BatchedFilter:
         self._need()
         T = int(T)
         cmds = np.zeros((max(T, 0), self.batch, 2), dtype=np.float32) if return_cmds else None
-        _lib.check(_lib.lib().slam_nav_run(self.h, T, None if cmds is None or cmds.size == 0 else _f(cmds)))
+        _lib.check(_lib.lib().slam_nav_run(self.h, T, opt(cmds)))
         self.timestep += max(T, 0)
         return cmds
 
@@ -623,26 +529,13 @@ class BatchedFilter:
 
     def last_nav_work(self):
         """(device ms of the controller kernels, or -1 without set_nav_timing; device ms of everything) of the last run_nav, by HIP events."""
-        self._need(); a = C.c_double(0); b = C.c_double(0)
-        _lib.check(_lib.lib().slam_last_nav_work(self.h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return self._last_work("slam_last_nav_work", 2)
 
     def set_lazy_steps(self, n):
         self._need(); _lib.check(_lib.lib().slam_set_lazy_steps(self.h, int(n)))
 
     def sync(self):
         self._need(); _lib.check(_lib.lib().slam_sync(self.h))
-
-    def close(self):
-        if self.h is not None:
-            _lib.lib().slam_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class BatchedEKF(BatchedFilter):
@@ -665,18 +558,6 @@ class BatchedEKF(BatchedFilter):
     # -- no counterpart in the reference: is the filter believable WITHOUT the truth?  (slam_innovation_*, include/slam_batch.h) --
     INNOVATION_FROZEN, INNOVATION_WOULD_FREEZE, INNOVATION_S_SINGULAR, INNOVATION_TOO_LONG = 1, 2, 4, 8   # slam_innovation_flags
 
-    def _innovation_config(self, cfg):
-        if cfg is None:
-            return default_innovation_config()
-        if isinstance(cfg, InnovationConfig):
-            return cfg
-        c = default_innovation_config()
-        for k, v in dict(cfg).items():
-            if k not in ("nis_lo", "nis_hi"):
-                raise ValueError(f"unknown innovation setting {k!r}")
-            setattr(c, k, v)
-        return c
-
     def innovation(self, cmdMsg, meas, meas_count, det=True, cfg=None):
         """What the next update(cmdMsg, meas, meas_count) will compute, from the state as it is and changing nothing: dict of rec (16,),
         nis_sum, n_upd, n_new, flags [batch], post (batch, 12) = the pose and its 3 x 3 covariance after the step, and - det=True -
@@ -693,9 +574,10 @@ class BatchedEKF(BatchedFilter):
                    flags=np.zeros(B, dtype=np.int32), post=np.zeros((B, 12)))
         if det:
             out["det"] = np.zeros((B, INNOV_MAX_DET, 6))
-        _lib.check(_lib.lib().slam_innovation(self.h, C.byref(self._innovation_config(cfg)), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt),
-                                              m.shape[1], _d(out["rec"]), _d(out["nis_sum"]), _i(out["n_upd"]), _i(out["n_new"]),
-                                              _i(out["flags"]), _d(out["det"]) if det else None, _d(out["post"])))
+        c = config_from(cfg, *INNOVATION)
+        _lib.check(_lib.lib().slam_innovation(self.h, C.byref(c), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt), m.shape[1], _d(out["rec"]),
+                                              _d(out["nis_sum"]), _i(out["n_upd"]), _i(out["n_new"]), _i(out["flags"]), opt(out.get("det")),
+                                              _d(out["post"])))
         return out
 
     def innovation_run(self, cmds=None, T=None, meas=None, meas_count=None, series=False, cfg=None):
@@ -721,34 +603,19 @@ class BatchedEKF(BatchedFilter):
         if series:
             res.nis_sum = np.zeros((n, self.batch))
             res.n_upd, res.flags = np.zeros((n, self.batch), dtype=np.int32), np.zeros((n, self.batch), dtype=np.int32)
-        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
-        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
-        _lib.check(_lib.lib().slam_innovation_run(self.h, C.byref(self._innovation_config(cfg)), int(source), None if c32 is None else _f(c32),
-                                                  None if m is None else _f(m), None if cnt is None else _i(cnt),
-                                                  0 if m is None else m.shape[2], T, pd(res.recs), pd(res.nis_sum), pi(res.n_upd),
-                                                  pi(res.flags)))
+        c = config_from(cfg, *INNOVATION)
+        _lib.check(_lib.lib().slam_innovation_run(self.h, C.byref(c), source, ptr(c32),
+                                                  ptr(m), ptr(cnt),
+                                                  0 if m is None else m.shape[2], T, opt(res.recs), opt(res.nis_sum), opt(res.n_upd),
+                                                  opt(res.flags)))
         self.timestep += n
         return res
 
     def last_innovation_work(self):
         """(device ms of the innovation launches of the last innovation_run, or -1 without set_nav_timing; device ms of the whole run)."""
-        self._need(); a = C.c_double(0); b = C.c_double(0)
-        _lib.check(_lib.lib().slam_last_innovation_work(self.h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return self._last_work("slam_last_innovation_work", 2)
 
-    # -- the chi-square gate on every detection (slam_gate_*, include/slam_batch.h) --
-    def _gate_config(self, cfg):
-        if cfg is None:
-            return default_gate_config()
-        if isinstance(cfg, GateConfig):
-            return cfg
-        c = default_gate_config()
-        for k, v in dict(cfg).items():
-            if k not in ("gate", "nis_lo", "nis_hi"):
-                raise ValueError(f"unknown gate setting {k!r}")
-            setattr(c, k, v)
-        return c
-
+    # -- what the gate, the association and the map calls share --
     def _message(self, meas, meas_count):
         m = np.ascontiguousarray(meas, dtype=np.float32)
         cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
@@ -756,6 +623,52 @@ class BatchedEKF(BatchedFilter):
             raise ValueError(f"expected meas of shape ({self.batch}, k_stride > 0, 3) and meas_count of shape ({self.batch},)")
         return m, cnt
 
+    def _log(self, cmds, meas, meas_count):
+        """A recorded log as (commands, each, meas, meas_count), float32 / int32 and their shapes checked against each other."""
+        c32 = np.ascontiguousarray(cmds, dtype=np.float32)
+        m = np.ascontiguousarray(meas, dtype=np.float32)
+        cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
+        each = c32.ndim == 3
+        if c32.shape[1:] != ((self.batch, 2) if each else (2,)) or m.ndim != 4 or m.shape[:2] != (c32.shape[0], self.batch) or m.shape[2] == 0 \
+                or m.shape[3] != 3 or cnt.shape != m.shape[:2]:
+            raise ValueError(f"a log needs cmds (T, 2) or (T, {self.batch}, 2), meas (T, {self.batch}, k_stride > 0, 3) and meas_count (T, {self.batch})")
+        return c32, each, m, cnt
+
+    def _stats(self, stats, key):
+        """The outputs of a step or a map edit: (dict(rec (16,), `key` [batch] int32), their two pointers), all None without stats."""
+        if not stats:
+            return None, None, None
+        out = {"rec": np.zeros(16), key: np.zeros(self.batch, dtype=np.int32)}
+        return out, _d(out["rec"]), _i(out[key])
+
+    def _filtered_run(self, run, cfgs, series, log=None, sim=None):
+        """One of the ten runs that filter a message before the step, described by _RUNS[run].  log = (cmds, meas, meas_count): the
+        recorded-log form; sim = (the caller's name, cmds, T, source, k_stride, log): the *_run_sim form, whose result gets `.sense`."""
+        Result, symbol, symbol_sim, kinds, outs = _RUNS[run]
+        self._need()
+        if sim is None:
+            c32, each, m, cnt = self._log(*log)
+            T = c32.shape[0]
+            head, tail = (_f(c32), int(each), _f(m), _i(cnt), m.shape[2], T), ()
+        else:
+            name, cmds, T, source, k_stride, want = sim
+            c32, source, T = self._run_cmds(name, cmds, T, source)
+            ks, symbol = int(k_stride), symbol_sim
+            sense = SenseLogResult(max(T, 0), self.batch, max(ks, 1), want) if want else None
+            head, tail = (source, ptr(c32), ks, T), (C.byref(sense.struct()) if want and T > 0 else None,)
+        n = max(T, 0)
+        res = Result(np.zeros((n, 16)))
+        if series:
+            for key, dtype in outs:
+                setattr(res, key, np.zeros((n, self.batch), dtype=dtype))
+        structs = [C.byref(config_from(cfg, *kind)) for cfg, kind in zip(cfgs, kinds)]
+        _lib.check(getattr(_lib.lib(), symbol)(self.h, *structs, *head, opt(res.recs), *[opt(getattr(res, key)) for key, _ in outs], *tail))
+        self.timestep += n
+        if sim is not None:
+            res.sense = sense
+        return res
+
+    # -- the chi-square gate on every detection (slam_gate_*, include/slam_batch.h) --
     def _gate_outputs(self, det):
         B = self.batch
         out = dict(rec=np.zeros(16), nis_sum=np.zeros(B), n_upd=np.zeros(B, dtype=np.int32), n_new=np.zeros(B, dtype=np.int32),
@@ -775,9 +688,10 @@ class BatchedEKF(BatchedFilter):
         m, cnt = self._message(meas, meas_count)
         out = self._gate_outputs(det)
         out["meas_out"], out["count_out"] = np.zeros_like(m), np.zeros_like(cnt)
-        _lib.check(_lib.lib().slam_gate(self.h, C.byref(self._gate_config(cfg)), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt), m.shape[1],
+        c = config_from(cfg, *GATE)
+        _lib.check(_lib.lib().slam_gate(self.h, C.byref(c), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt), m.shape[1],
                                         _d(out["rec"]), _d(out["nis_sum"]), _i(out["n_upd"]), _i(out["n_new"]), _i(out["flags"]),
-                                        _d(out["det"]) if det else None, _d(out["post"]), _f(out["meas_out"]), _i(out["count_out"]),
+                                        opt(out.get("det")), _d(out["post"]), _f(out["meas_out"]), _i(out["count_out"]),
                                         _i(out["n_rej"]), _i(out["verdict"])))
         return out
 
@@ -786,15 +700,12 @@ class BatchedEKF(BatchedFilter):
         message is written to d_meas_out_ptr / d_count_out_ptr, which may be the input pair itself (in place).  Returns the dict of gate()
         without meas_out and count_out."""
         self._need()
-        each = isinstance(cmdMsg, int)
-        cmd = None if each else self._cmd(cmdMsg)
-        if cmd is not None and cmd.ndim != 1:
-            raise ValueError("gate_dev takes one command, or the device pointer of per-instance commands")
+        cp, each = self._cmd_dev(cmdMsg, "gate_dev takes")
         out = self._gate_outputs(det)
-        cp = C.c_void_p(cmdMsg) if each else C.cast(_f(cmd), C.c_void_p)
-        _lib.check(_lib.lib().slam_gate_dev(self.h, C.byref(self._gate_config(cfg)), cp, int(each), C.c_void_p(d_meas_ptr),
+        c = config_from(cfg, *GATE)
+        _lib.check(_lib.lib().slam_gate_dev(self.h, C.byref(c), cp, each, C.c_void_p(d_meas_ptr),
                                             C.c_void_p(d_count_ptr), int(k_stride), _d(out["rec"]), _d(out["nis_sum"]), _i(out["n_upd"]),
-                                            _i(out["n_new"]), _i(out["flags"]), _d(out["det"]) if det else None, _d(out["post"]),
+                                            _i(out["n_new"]), _i(out["flags"]), opt(out.get("det")), _d(out["post"]),
                                             C.c_void_p(d_meas_out_ptr), C.c_void_p(d_count_out_ptr), _i(out["n_rej"]), _i(out["verdict"])))
         return out
 
@@ -804,71 +715,37 @@ class BatchedEKF(BatchedFilter):
         self._need()
         cmd = self._cmd(cmdMsg)
         m, cnt = self._message(meas, meas_count)
-        out = dict(rec=np.zeros(16), n_rej=np.zeros(self.batch, dtype=np.int32)) if stats else None
+        out, rec, nr = self._stats(stats, "n_rej")
+        c = config_from(cfg, *GATE)
         fn = _lib.lib().slam_step_gated_each if cmd.ndim == 2 else _lib.lib().slam_step_gated
-        _lib.check(fn(self.h, C.byref(self._gate_config(cfg)), _f(cmd), _f(m), _i(cnt), m.shape[1], _d(out["rec"]) if stats else None,
-                      _i(out["n_rej"]) if stats else None))
+        _lib.check(fn(self.h, C.byref(c), _f(cmd), _f(m), _i(cnt), m.shape[1], rec, nr))
         self.timestep += 1
         return out
 
     def step_gated_dev(self, cmdMsg, d_meas_ptr, d_count_ptr, k_stride, stats=True, cfg=None):
         """step_gated() on DEVICE messages; cmdMsg one command (host) or, as an int, the device pointer of (batch, 2) commands."""
         self._need()
-        each = isinstance(cmdMsg, int)
-        out = dict(rec=np.zeros(16), n_rej=np.zeros(self.batch, dtype=np.int32)) if stats else None
-        args = (C.c_void_p(d_meas_ptr), C.c_void_p(d_count_ptr), int(k_stride), _d(out["rec"]) if stats else None, _i(out["n_rej"]) if stats else None)
+        cp, each = self._cmd_dev(cmdMsg, "step_gated_dev takes")
+        out, rec, nr = self._stats(stats, "n_rej")
+        c = config_from(cfg, *GATE)
         if each:
-            _lib.check(_lib.lib().slam_step_gated_each_dev(self.h, C.byref(self._gate_config(cfg)), C.c_void_p(cmdMsg), *args))
+            fn = _lib.lib().slam_step_gated_each_dev
         else:
-            cmd = self._cmd(cmdMsg)
-            if cmd.ndim != 1:
-                raise ValueError("step_gated_dev takes one command, or the device pointer of per-instance commands")
-            _lib.check(_lib.lib().slam_step_gated_dev(self.h, C.byref(self._gate_config(cfg)), _f(cmd), *args))
+            fn, cp = _lib.lib().slam_step_gated_dev, C.cast(cp, C.POINTER(C.c_float))   # this one symbol declares the host command as float *
+        _lib.check(fn(self.h, C.byref(c), cp, C.c_void_p(d_meas_ptr), C.c_void_p(d_count_ptr), int(k_stride), rec, nr))
         self.timestep += 1
         return out
 
     def gate_run(self, cmds, meas, meas_count, series=False, cfg=None):
         """T gated ticks of a recorded log: cmds (T, 2) or (T, batch, 2), meas (T, batch, k_stride, 3), meas_count (T, batch); the same bits
         as T step_gated calls.  Returns a GateResult; series=True also records nis_sum, n_upd, n_rej and flags of every instance."""
-        self._need()
-        c32 = np.ascontiguousarray(cmds, dtype=np.float32)
-        m = np.ascontiguousarray(meas, dtype=np.float32)
-        cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
-        each = c32.ndim == 3
-        if c32.shape[1:] != ((self.batch, 2) if each else (2,)) or m.ndim != 4 or m.shape[:2] != (c32.shape[0], self.batch) or m.shape[2] == 0 \
-                or m.shape[3] != 3 or cnt.shape != m.shape[:2]:
-            raise ValueError(f"a log needs cmds (T, 2) or (T, {self.batch}, 2), meas (T, {self.batch}, k_stride > 0, 3) and meas_count (T, {self.batch})")
-        T = c32.shape[0]
-        res = GateResult(np.zeros((T, 16)))
-        if series:
-            res.nis_sum = np.zeros((T, self.batch))
-            res.n_upd, res.n_rej, res.flags = (np.zeros((T, self.batch), dtype=np.int32) for _ in range(3))
-        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
-        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
-        _lib.check(_lib.lib().slam_gate_run(self.h, C.byref(self._gate_config(cfg)), _f(c32), int(each), _f(m), _i(cnt), m.shape[2], T,
-                                            pd(res.recs), pd(res.nis_sum), pi(res.n_upd), pi(res.n_rej), pi(res.flags)))
-        self.timestep += T
-        return res
+        return self._filtered_run("gate", (cfg,), series, log=(cmds, meas, meas_count))
 
     def last_gate_work(self):
         """(device ms of the gate launches of the last gate_run, or -1 without set_nav_timing; device ms of the whole run)."""
-        self._need(); a = C.c_double(0); b = C.c_double(0)
-        _lib.check(_lib.lib().slam_last_gate_work(self.h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return self._last_work("slam_last_gate_work", 2)
 
     # -- detections without ids: nearest neighbour in Mahalanobis distance (slam_associate_*, include/slam_batch.h) --
-    def _assoc_config(self, cfg):
-        if cfg is None:
-            return default_assoc_config()
-        if isinstance(cfg, AssocConfig):
-            return cfg
-        c = default_assoc_config()
-        for k, v in dict(cfg).items():
-            if k not in ("gate_match", "gate_new"):
-                raise ValueError(f"unknown association setting {k!r}")
-            setattr(c, k, v)
-        return c
-
     def _assoc_outputs(self, det):
         B = self.batch
         out = dict(rec=np.zeros(16), n_match=np.zeros(B, dtype=np.int32), n_new=np.zeros(B, dtype=np.int32), n_drop=np.zeros(B, dtype=np.int32),
@@ -877,6 +754,12 @@ class BatchedEKF(BatchedFilter):
         if det:
             out["det"] = np.zeros((B, INNOV_MAX_DET, 4))
         return out
+
+    @staticmethod
+    def _assoc_pointers(out):
+        """The outputs slam_associate* and slam_associate_joint* share, in C order up to det."""
+        return (_d(out["rec"]), _i(out["n_match"]), _i(out["n_new"]), _i(out["n_drop"]), _i(out["flags"]), _i(out["verdict"]), _i(out["slot"]),
+                opt(out.get("det")))
 
     def associate(self, cmdMsg, meas, meas_count, det=True, cfg=None):
         """Labels a message whose id column is not read with landmark ids, from the state as it is and changing nothing: dict of rec (16,),
@@ -889,10 +772,9 @@ class BatchedEKF(BatchedFilter):
         m, cnt = self._message(meas, meas_count)
         out = self._assoc_outputs(det)
         out["meas_out"], out["count_out"] = np.zeros_like(m), np.zeros_like(cnt)
-        _lib.check(_lib.lib().slam_associate(self.h, C.byref(self._assoc_config(cfg)), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt), m.shape[1],
-                                             _d(out["rec"]), _i(out["n_match"]), _i(out["n_new"]), _i(out["n_drop"]), _i(out["flags"]),
-                                             _i(out["verdict"]), _i(out["slot"]), _d(out["det"]) if det else None, _f(out["meas_out"]),
-                                             _i(out["count_out"])))
+        c = config_from(cfg, *ASSOC)
+        _lib.check(_lib.lib().slam_associate(self.h, C.byref(c), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt), m.shape[1],
+                                             *self._assoc_pointers(out), _f(out["meas_out"]), _i(out["count_out"])))
         return out
 
     def associate_dev(self, cmdMsg, d_meas_ptr, d_count_ptr, k_stride, d_meas_out_ptr, d_count_out_ptr, det=True, cfg=None):
@@ -900,16 +782,11 @@ class BatchedEKF(BatchedFilter):
         message is written to d_meas_out_ptr / d_count_out_ptr, which may be the input pair itself (in place).  Returns the dict of
         associate() without meas_out and count_out."""
         self._need()
-        each = isinstance(cmdMsg, int)
-        cmd = None if each else self._cmd(cmdMsg)
-        if cmd is not None and cmd.ndim != 1:
-            raise ValueError("associate_dev takes one command, or the device pointer of per-instance commands")
+        cp, each = self._cmd_dev(cmdMsg, "associate_dev takes")
         out = self._assoc_outputs(det)
-        cp = C.c_void_p(cmdMsg) if each else C.cast(_f(cmd), C.c_void_p)
-        _lib.check(_lib.lib().slam_associate_dev(self.h, C.byref(self._assoc_config(cfg)), cp, int(each), C.c_void_p(d_meas_ptr),
-                                                 C.c_void_p(d_count_ptr), int(k_stride), _d(out["rec"]), _i(out["n_match"]), _i(out["n_new"]),
-                                                 _i(out["n_drop"]), _i(out["flags"]), _i(out["verdict"]), _i(out["slot"]),
-                                                 _d(out["det"]) if det else None, C.c_void_p(d_meas_out_ptr), C.c_void_p(d_count_out_ptr)))
+        c = config_from(cfg, *ASSOC)
+        _lib.check(_lib.lib().slam_associate_dev(self.h, C.byref(c), cp, each, C.c_void_p(d_meas_ptr), C.c_void_p(d_count_ptr), int(k_stride),
+                                                 *self._assoc_pointers(out), C.c_void_p(d_meas_out_ptr), C.c_void_p(d_count_out_ptr)))
         return out
 
     def step_associated(self, cmdMsg, meas, meas_count, stats=True, cfg=None):
@@ -918,24 +795,20 @@ class BatchedEKF(BatchedFilter):
         self._need()
         cmd = self._cmd(cmdMsg)
         m, cnt = self._message(meas, meas_count)
-        out = dict(rec=np.zeros(16), n_drop=np.zeros(self.batch, dtype=np.int32)) if stats else None
-        _lib.check(_lib.lib().slam_step_associated(self.h, C.byref(self._assoc_config(cfg)), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt),
-                                                   m.shape[1], _d(out["rec"]) if stats else None, _i(out["n_drop"]) if stats else None))
+        out, rec, nd = self._stats(stats, "n_drop")
+        c = config_from(cfg, *ASSOC)
+        _lib.check(_lib.lib().slam_step_associated(self.h, C.byref(c), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt), m.shape[1], rec, nd))
         self.timestep += 1
         return out
 
     def step_associated_dev(self, cmdMsg, d_meas_ptr, d_count_ptr, k_stride, stats=True, cfg=None):
         """step_associated() on DEVICE messages; cmdMsg one command (host) or, as an int, the device pointer of (batch, 2) commands."""
         self._need()
-        each = isinstance(cmdMsg, int)
-        cmd = None if each else self._cmd(cmdMsg)
-        if cmd is not None and cmd.ndim != 1:
-            raise ValueError("step_associated_dev takes one command, or the device pointer of per-instance commands")
-        out = dict(rec=np.zeros(16), n_drop=np.zeros(self.batch, dtype=np.int32)) if stats else None
-        cp = C.c_void_p(cmdMsg) if each else C.cast(_f(cmd), C.c_void_p)
-        _lib.check(_lib.lib().slam_step_associated_dev(self.h, C.byref(self._assoc_config(cfg)), cp, int(each), C.c_void_p(d_meas_ptr),
-                                                       C.c_void_p(d_count_ptr), int(k_stride), _d(out["rec"]) if stats else None,
-                                                       _i(out["n_drop"]) if stats else None))
+        cp, each = self._cmd_dev(cmdMsg, "step_associated_dev takes")
+        out, rec, nd = self._stats(stats, "n_drop")
+        c = config_from(cfg, *ASSOC)
+        _lib.check(_lib.lib().slam_step_associated_dev(self.h, C.byref(c), cp, each, C.c_void_p(d_meas_ptr), C.c_void_p(d_count_ptr),
+                                                       int(k_stride), rec, nd))
         self.timestep += 1
         return out
 
@@ -943,32 +816,13 @@ class BatchedEKF(BatchedFilter):
         """T associated ticks of a recorded log without ids: cmds (T, 2) or (T, batch, 2), meas (T, batch, k_stride, 3), meas_count
         (T, batch); the same bits as T step_associated calls.  Returns an AssocResult; series=True also records n_match, n_new, n_drop and
         flags of every instance."""
-        self._need()
-        c32 = np.ascontiguousarray(cmds, dtype=np.float32)
-        m = np.ascontiguousarray(meas, dtype=np.float32)
-        cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
-        each = c32.ndim == 3
-        if c32.shape[1:] != ((self.batch, 2) if each else (2,)) or m.ndim != 4 or m.shape[:2] != (c32.shape[0], self.batch) or m.shape[2] == 0 \
-                or m.shape[3] != 3 or cnt.shape != m.shape[:2]:
-            raise ValueError(f"a log needs cmds (T, 2) or (T, {self.batch}, 2), meas (T, {self.batch}, k_stride > 0, 3) and meas_count (T, {self.batch})")
-        T = c32.shape[0]
-        res = AssocResult(np.zeros((T, 16)))
-        if series:
-            res.n_match, res.n_new, res.n_drop, res.flags = (np.zeros((T, self.batch), dtype=np.int32) for _ in range(4))
-        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
-        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
-        _lib.check(_lib.lib().slam_associate_run(self.h, C.byref(self._assoc_config(cfg)), _f(c32), int(each), _f(m), _i(cnt), m.shape[2], T,
-                                                 pd(res.recs), pi(res.n_match), pi(res.n_new), pi(res.n_drop), pi(res.flags)))
-        self.timestep += T
-        return res
+        return self._filtered_run("associate", (cfg,), series, log=(cmds, meas, meas_count))
 
     def last_associate_work(self):
         """(model bytes of the association launches of the last associate / associate_dev / associate_run, the same with the reads of P in
         128-byte lines, device ms of the association launches of the last associate_run or -1 without set_nav_timing, device ms of that
         whole run or -1)."""
-        self._need(); by = (C.c_double * 2)(); a = C.c_double(0); b = C.c_double(0)
-        _lib.check(_lib.lib().slam_last_associate_work(self.h, by, C.byref(a), C.byref(b)))
-        return by[0], by[1], a.value, b.value
+        return self._last_work("slam_last_associate_work", 2, pair=True)
 
     # -- detections without ids, judged jointly: JCBB (slam_associate_joint_*, include/slam_batch.h) --
     def _joint_config(self, cfg):
@@ -990,103 +844,61 @@ class BatchedEKF(BatchedFilter):
         c = self._joint_config(cfg)
         tail = (_d(out["d2_joint"]), _i(out["nodes"]), _i(out["ncand"]))
         if isinstance(meas, int):
-            each = isinstance(cmdMsg, int)
-            cmd = None if each else self._cmd(cmdMsg)
-            if cmd is not None and cmd.ndim != 1:
-                raise ValueError("device messages take one command, or the device pointer of per-instance commands")
-            cp = C.c_void_p(cmdMsg) if each else C.cast(_f(cmd), C.c_void_p)
-            _lib.check(_lib.lib().slam_associate_joint_dev(self.h, C.byref(c), cp, int(each), C.c_void_p(meas), C.c_void_p(meas_count[0]),
-                                                           int(meas_count[1]), _d(out["rec"]), _i(out["n_match"]), _i(out["n_new"]),
-                                                           _i(out["n_drop"]), _i(out["flags"]), _i(out["verdict"]), _i(out["slot"]),
-                                                           _d(out["det"]) if det else None, C.c_void_p(dev_out[0]), C.c_void_p(dev_out[1]), *tail))
+            cp, each = self._cmd_dev(cmdMsg, "device messages take")
+            _lib.check(_lib.lib().slam_associate_joint_dev(self.h, C.byref(c), cp, each, C.c_void_p(meas), C.c_void_p(meas_count[0]),
+                                                           int(meas_count[1]), *self._assoc_pointers(out), C.c_void_p(dev_out[0]),
+                                                           C.c_void_p(dev_out[1]), *tail))
             return out
         cmd = self._cmd(cmdMsg)
         m, cnt = self._message(meas, meas_count)
         out["meas_out"], out["count_out"] = np.zeros_like(m), np.zeros_like(cnt)
-        _lib.check(_lib.lib().slam_associate_joint(self.h, C.byref(c), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt), m.shape[1], _d(out["rec"]),
-                                                   _i(out["n_match"]), _i(out["n_new"]), _i(out["n_drop"]), _i(out["flags"]), _i(out["verdict"]),
-                                                   _i(out["slot"]), _d(out["det"]) if det else None, _f(out["meas_out"]), _i(out["count_out"]),
-                                                   *tail))
+        _lib.check(_lib.lib().slam_associate_joint(self.h, C.byref(c), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt), m.shape[1],
+                                                   *self._assoc_pointers(out), _f(out["meas_out"]), _i(out["count_out"]), *tail))
         return out
 
     def step_associated_joint(self, cmdMsg, meas, meas_count, stats=True, cfg=None):
         """One jointly associated timestep, as step_associated().  meas as an int: DEVICE pointers as associate_joint()."""
         self._need()
-        out = dict(rec=np.zeros(16), n_drop=np.zeros(self.batch, dtype=np.int32)) if stats else None
+        out, rec, nd = self._stats(stats, "n_drop")
         c = self._joint_config(cfg)
-        rp, dp = (_d(out["rec"]) if stats else None), (_i(out["n_drop"]) if stats else None)
         if isinstance(meas, int):
-            each = isinstance(cmdMsg, int)
-            cmd = None if each else self._cmd(cmdMsg)
-            if cmd is not None and cmd.ndim != 1:
-                raise ValueError("device messages take one command, or the device pointer of per-instance commands")
-            cp = C.c_void_p(cmdMsg) if each else C.cast(_f(cmd), C.c_void_p)
-            _lib.check(_lib.lib().slam_step_associated_joint_dev(self.h, C.byref(c), cp, int(each), C.c_void_p(meas), C.c_void_p(meas_count[0]),
-                                                                 int(meas_count[1]), rp, dp))
+            cp, each = self._cmd_dev(cmdMsg, "device messages take")
+            _lib.check(_lib.lib().slam_step_associated_joint_dev(self.h, C.byref(c), cp, each, C.c_void_p(meas), C.c_void_p(meas_count[0]),
+                                                                 int(meas_count[1]), rec, nd))
         else:
             cmd = self._cmd(cmdMsg)
             m, cnt = self._message(meas, meas_count)
-            _lib.check(_lib.lib().slam_step_associated_joint(self.h, C.byref(c), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt), m.shape[1], rp, dp))
+            _lib.check(_lib.lib().slam_step_associated_joint(self.h, C.byref(c), _f(cmd), int(cmd.ndim == 2), _f(m), _i(cnt), m.shape[1], rec, nd))
         self.timestep += 1
         return out
 
     def associate_joint_run(self, cmds, meas, meas_count, series=False, cfg=None):
         """T jointly associated ticks of a recorded log without ids, layout and result as associate_run (the records' columns: JointResult's
         REC_* constants); series=True also records n_match, n_new, n_drop, flags, nodes and d2_joint of every instance."""
-        self._need()
-        c32 = np.ascontiguousarray(cmds, dtype=np.float32)
-        m = np.ascontiguousarray(meas, dtype=np.float32)
-        cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
-        each = c32.ndim == 3
-        if c32.shape[1:] != ((self.batch, 2) if each else (2,)) or m.ndim != 4 or m.shape[:2] != (c32.shape[0], self.batch) or m.shape[2] == 0 \
-                or m.shape[3] != 3 or cnt.shape != m.shape[:2]:
-            raise ValueError(f"a log needs cmds (T, 2) or (T, {self.batch}, 2), meas (T, {self.batch}, k_stride > 0, 3) and meas_count (T, {self.batch})")
-        T = c32.shape[0]
-        res = JointResult(np.zeros((T, 16)))
-        if series:
-            res.n_match, res.n_new, res.n_drop, res.flags, res.nodes = (np.zeros((T, self.batch), dtype=np.int32) for _ in range(5))
-            res.d2_joint = np.zeros((T, self.batch))
-        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
-        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
-        _lib.check(_lib.lib().slam_associate_joint_run(self.h, C.byref(self._joint_config(cfg)), _f(c32), int(each), _f(m), _i(cnt), m.shape[2], T,
-                                                       pd(res.recs), pi(res.n_match), pi(res.n_new), pi(res.n_drop), pi(res.flags),
-                                                       pd(res.d2_joint), pi(res.nodes)))
-        self.timestep += T
-        return res
+        return self._filtered_run("associate_joint", (cfg,), series, log=(cmds, meas, meas_count))
 
     def last_joint_work(self):
         """last_associate_work() for the joint association: (model bytes, the same with the reads of P in 128-byte lines, device ms of the
         joint launches of the last associate_joint_run or -1 without set_nav_timing, device ms of that whole run or -1)."""
-        self._need(); by = (C.c_double * 2)(); a = C.c_double(0); b = C.c_double(0)
-        _lib.check(_lib.lib().slam_last_joint_work(self.h, by, C.byref(a), C.byref(b)))
-        return by[0], by[1], a.value, b.value
+        return self._last_work("slam_last_joint_work", 2, pair=True)
 
     # -- map management: landmarks leave the map again (slam_remove_landmarks, slam_map_*, include/slam_batch.h) --
-    def _map_config(self, cfg):
-        if cfg is None:
-            return default_map_config()
-        if isinstance(cfg, MapConfig):
-            return cfg
-        c = default_map_config()
-        for k, v in dict(cfg).items():
-            if k not in MAP_CONFIG_FIELDS:
-                raise ValueError(f"unknown map setting {k!r}")
-            setattr(c, k, v)
-        return c
+    def _mask(self, a, what):
+        m = np.ascontiguousarray(a, dtype=np.int32)
+        if m.shape != (self.batch, self.L_max):
+            raise ValueError(f"{what}: expected shape ({self.batch}, {self.L_max}), got {m.shape}")
+        return m
 
     def remove_landmarks(self, remove, stats=True):
         """Drops the slots whose entry of remove (batch, L_max) is nonzero (entries at or above an instance's landmark count are ignored):
         exact marginalisation, x, P and ids compacted on the device bit for bit.  remove as an int: the DEVICE pointer of the mask.
         stats=True returns dict(rec (16,), n_removed [batch]) and synchronises; stats=False None."""
         self._need()
-        out = dict(rec=np.zeros(16), n_removed=np.zeros(self.batch, dtype=np.int32)) if stats else None
-        nr, rec = (_i(out["n_removed"]), _d(out["rec"])) if stats else (None, None)
+        out, rec, nr = self._stats(stats, "n_removed")
         if isinstance(remove, int):
             _lib.check(_lib.lib().slam_remove_landmarks_dev(self.h, C.c_void_p(remove), nr, rec))
         else:
-            m = np.ascontiguousarray(remove, dtype=np.int32)
-            if m.shape != (self.batch, self.L_max):
-                raise ValueError(f"remove: expected shape ({self.batch}, {self.L_max}), got {m.shape}")
+            m = self._mask(remove, "remove")
             _lib.check(_lib.lib().slam_remove_landmarks(self.h, _i(m), nr, rec))
         return out
 
@@ -1094,7 +906,7 @@ class BatchedEKF(BatchedFilter):
         """Adds the evidence of one labelled message to the track counters, after the step that consumed it: host message as associate();
         assoc_flags [batch] or None.  meas as an int: DEVICE pointers (meas, meas_count = (pointer, k_stride), assoc_flags or None)."""
         self._need()
-        c = self._map_config(cfg)
+        c = config_from(cfg, *MAP)
         if isinstance(meas, int):
             d_count, k_stride = meas_count
             _lib.check(_lib.lib().slam_map_tally_dev(self.h, C.byref(c), C.c_void_p(meas), C.c_void_p(d_count), int(k_stride),
@@ -1104,14 +916,14 @@ class BatchedEKF(BatchedFilter):
         fl = None if assoc_flags is None else np.ascontiguousarray(assoc_flags, dtype=np.int32)
         if fl is not None and fl.shape != (self.batch,):
             raise ValueError(f"assoc_flags: expected shape ({self.batch},), got {fl.shape}")
-        _lib.check(_lib.lib().slam_map_tally(self.h, C.byref(c), _f(m), _i(cnt), m.shape[1], None if fl is None else _i(fl)))
+        _lib.check(_lib.lib().slam_map_tally(self.h, C.byref(c), _f(m), _i(cnt), m.shape[1], ptr(fl)))
 
     def map_prune(self, stats=True, cfg=None):
         """Removes the slots the prune rule picks from the track counters, decided and compacted on the device.  Returns as remove_landmarks."""
         self._need()
-        out = dict(rec=np.zeros(16), n_removed=np.zeros(self.batch, dtype=np.int32)) if stats else None
-        _lib.check(_lib.lib().slam_map_prune(self.h, C.byref(self._map_config(cfg)), _d(out["rec"]) if stats else None,
-                                             _i(out["n_removed"]) if stats else None))
+        out, rec, nr = self._stats(stats, "n_removed")
+        c = config_from(cfg, *MAP)
+        _lib.check(_lib.lib().slam_map_prune(self.h, C.byref(c), rec, nr))
         return out
 
     def map_track(self):
@@ -1129,17 +941,12 @@ class BatchedEKF(BatchedFilter):
         """step_associated(), then the tally of the labelled message with the association's flags, on the device.  meas as an int: DEVICE
         pointers as step_associated_dev (meas_count = (pointer, k_stride); cmdMsg one command or, as an int, a device pointer)."""
         self._need()
-        ac, mc = self._assoc_config(cfg), self._map_config(map_cfg)
-        out = dict(rec=np.zeros(16), n_drop=np.zeros(self.batch, dtype=np.int32)) if stats else None
-        rec, nd = (_d(out["rec"]), _i(out["n_drop"])) if stats else (None, None)
+        ac, mc = config_from(cfg, *ASSOC), config_from(map_cfg, *MAP)
+        out, rec, nd = self._stats(stats, "n_drop")
         if isinstance(meas, int):
             d_count, k_stride = meas_count
-            each = isinstance(cmdMsg, int)
-            cmd = None if each else self._cmd(cmdMsg)
-            if cmd is not None and cmd.ndim != 1:
-                raise ValueError("a managed step on device messages takes one command, or the device pointer of per-instance commands")
-            cp = C.c_void_p(cmdMsg) if each else C.cast(_f(cmd), C.c_void_p)
-            _lib.check(_lib.lib().slam_step_managed_dev(self.h, C.byref(ac), C.byref(mc), cp, int(each), C.c_void_p(meas), C.c_void_p(d_count),
+            cp, each = self._cmd_dev(cmdMsg, "a managed step on device messages takes")
+            _lib.check(_lib.lib().slam_step_managed_dev(self.h, C.byref(ac), C.byref(mc), cp, each, C.c_void_p(meas), C.c_void_p(d_count),
                                                         int(k_stride), rec, nd))
         else:
             cmd = self._cmd(cmdMsg)
@@ -1152,59 +959,26 @@ class BatchedEKF(BatchedFilter):
         """T managed ticks of a recorded log without ids, layout as associate_run: every tick a step_managed, and a map_prune after every
         prune_every-th tick; the same bits as that loop.  Returns a MapResult; series=True also records n_match, n_new, n_drop, flags and
         n_removed of every instance."""
-        self._need()
-        c32 = np.ascontiguousarray(cmds, dtype=np.float32)
-        m = np.ascontiguousarray(meas, dtype=np.float32)
-        cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
-        each = c32.ndim == 3
-        if c32.shape[1:] != ((self.batch, 2) if each else (2,)) or m.ndim != 4 or m.shape[:2] != (c32.shape[0], self.batch) or m.shape[2] == 0 \
-                or m.shape[3] != 3 or cnt.shape != m.shape[:2]:
-            raise ValueError(f"a log needs cmds (T, 2) or (T, {self.batch}, 2), meas (T, {self.batch}, k_stride > 0, 3) and meas_count (T, {self.batch})")
-        T = c32.shape[0]
-        res = MapResult(np.zeros((T, 16)))
-        if series:
-            res.n_match, res.n_new, res.n_drop, res.flags, res.n_removed = (np.zeros((T, self.batch), dtype=np.int32) for _ in range(5))
-        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
-        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
-        _lib.check(_lib.lib().slam_manage_run(self.h, C.byref(self._assoc_config(cfg)), C.byref(self._map_config(map_cfg)), _f(c32), int(each),
-                                              _f(m), _i(cnt), m.shape[2], T, pd(res.recs), pi(res.n_match), pi(res.n_new), pi(res.n_drop),
-                                              pi(res.n_removed), pi(res.flags)))
-        self.timestep += T
-        return res
+        return self._filtered_run("manage", (cfg, map_cfg), series, log=(cmds, meas, meas_count))
 
     def last_map_work(self):
         """(model bytes the removals of the last remove_landmarks / map_prune / manage_run had to move, device ms of the prunes of the last
         manage_run or -1 without set_nav_timing, device ms of that whole run or -1)."""
-        self._need(); by = C.c_double(0); a = C.c_double(0); b = C.c_double(0)
-        _lib.check(_lib.lib().slam_last_map_work(self.h, C.byref(by), C.byref(a), C.byref(b)))
-        return by.value, a.value, b.value
-
+        return self._last_work("slam_last_map_work", 3)
 
     # -- landmark merging: duplicate landmarks are found and fused (slam_map_duplicates, slam_merge_landmarks, slam_map_merge) --
-    def _merge_config(self, cfg):
-        if cfg is None:
-            return default_merge_config()
-        if isinstance(cfg, MergeConfig):
-            return cfg
-        c = default_merge_config()
-        for k, v in dict(cfg).items():
-            if k not in MERGE_CONFIG_FIELDS:
-                raise ValueError(f"unknown merge setting {k!r}")
-            setattr(c, k, v)
-        return c
-
     def map_duplicates(self, d2=True, cfg=None, dev=None):
         """The duplicate decision, no state change: (partner, d2), (batch, L_max) each: the slot's mutual nearest neighbour within gate_merge
         (-1: none) and - d2=True, else None - the d2 of its best candidate (NaN: none).  dev = (d_partner, d_d2 or None): DEVICE pointers,
         written in stream order; returns None."""
         self._need()
-        c = self._merge_config(cfg)
+        c = config_from(cfg, *MERGE)
         if dev is not None:
             _lib.check(_lib.lib().slam_map_duplicates_dev(self.h, C.byref(c), C.c_void_p(dev[0]), None if dev[1] is None else C.c_void_p(dev[1])))
             return None
         partner = np.zeros((self.batch, self.L_max), dtype=np.int32)
         dd = np.zeros((self.batch, self.L_max)) if d2 else None
-        _lib.check(_lib.lib().slam_map_duplicates(self.h, C.byref(c), _i(partner), _d(dd) if d2 else None))
+        _lib.check(_lib.lib().slam_map_duplicates(self.h, C.byref(c), _i(partner), opt(dd)))
         return partner, dd
 
     def merge_landmarks(self, partner, stats=True, cfg=None):
@@ -1212,76 +986,40 @@ class BatchedEKF(BatchedFilter):
         ignored and counted.  partner as an int: the DEVICE pointer of the array.  stats=True returns dict(rec (16,), n_merged [batch]) and
         synchronises; stats=False None."""
         self._need()
-        c = self._merge_config(cfg)
-        out = dict(rec=np.zeros(16), n_merged=np.zeros(self.batch, dtype=np.int32)) if stats else None
-        nm, rec = (_i(out["n_merged"]), _d(out["rec"])) if stats else (None, None)
+        c = config_from(cfg, *MERGE)
+        out, rec, nm = self._stats(stats, "n_merged")
         if isinstance(partner, int):
             _lib.check(_lib.lib().slam_merge_landmarks_dev(self.h, C.byref(c), C.c_void_p(partner), nm, rec))
         else:
-            m = np.ascontiguousarray(partner, dtype=np.int32)
-            if m.shape != (self.batch, self.L_max):
-                raise ValueError(f"partner: expected shape ({self.batch}, {self.L_max}), got {m.shape}")
+            m = self._mask(partner, "partner")
             _lib.check(_lib.lib().slam_merge_landmarks(self.h, C.byref(c), _i(m), nm, rec))
         return out
 
     def map_merge(self, stats=True, cfg=None):
         """Finds the duplicate pairs, fuses them and compacts the maps, all on the device.  Returns as merge_landmarks."""
         self._need()
-        out = dict(rec=np.zeros(16), n_merged=np.zeros(self.batch, dtype=np.int32)) if stats else None
-        _lib.check(_lib.lib().slam_map_merge(self.h, C.byref(self._merge_config(cfg)), _d(out["rec"]) if stats else None,
-                                             _i(out["n_merged"]) if stats else None))
+        out, rec, nm = self._stats(stats, "n_merged")
+        c = config_from(cfg, *MERGE)
+        _lib.check(_lib.lib().slam_map_merge(self.h, C.byref(c), rec, nm))
         return out
 
     def manage_merge_run(self, cmds, meas, meas_count, series=False, cfg=None, map_cfg=None, merge_cfg=None):
         """manage_run with a map_merge after every merge_every-th tick, before that tick's prune; the same bits as that loop.  Returns a
         MergeResult; series=True also records n_match, n_new, n_drop, flags, n_removed and n_merged of every instance."""
-        self._need()
-        c32 = np.ascontiguousarray(cmds, dtype=np.float32)
-        m = np.ascontiguousarray(meas, dtype=np.float32)
-        cnt = np.ascontiguousarray(meas_count, dtype=np.int32)
-        each = c32.ndim == 3
-        if c32.shape[1:] != ((self.batch, 2) if each else (2,)) or m.ndim != 4 or m.shape[:2] != (c32.shape[0], self.batch) or m.shape[2] == 0 \
-                or m.shape[3] != 3 or cnt.shape != m.shape[:2]:
-            raise ValueError(f"a log needs cmds (T, 2) or (T, {self.batch}, 2), meas (T, {self.batch}, k_stride > 0, 3) and meas_count (T, {self.batch})")
-        T = c32.shape[0]
-        res = MergeResult(np.zeros((T, 16)))
-        if series:
-            res.n_match, res.n_new, res.n_drop, res.flags, res.n_removed, res.n_merged = (np.zeros((T, self.batch), dtype=np.int32) for _ in range(6))
-        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
-        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
-        _lib.check(_lib.lib().slam_manage_merge_run(self.h, C.byref(self._assoc_config(cfg)), C.byref(self._map_config(map_cfg)),
-                                                    C.byref(self._merge_config(merge_cfg)), _f(c32), int(each), _f(m), _i(cnt), m.shape[2], T,
-                                                    pd(res.recs), pi(res.n_match), pi(res.n_new), pi(res.n_drop), pi(res.n_removed), pi(res.n_merged),
-                                                    pi(res.flags)))
-        self.timestep += T
-        return res
+        return self._filtered_run("manage_merge", (cfg, map_cfg, merge_cfg), series, log=(cmds, meas, meas_count))
 
     def last_merge_work(self):
         """(model bytes the last map_duplicates / merge_landmarks / map_merge / manage_merge_run had to move, device ms of the merges of the
         last manage_merge_run or -1 without set_nav_timing, device ms of that whole run or -1)."""
-        self._need(); by = C.c_double(0); a = C.c_double(0); b = C.c_double(0)
-        _lib.check(_lib.lib().slam_last_merge_work(self.h, C.byref(by), C.byref(a), C.byref(b)))
-        return by.value, a.value, b.value
+        return self._last_work("slam_last_merge_work", 3)
 
     # -- absolute position and heading fixes (slam_fix_*; include/slam_batch.h) --
-    def _fix_config(self, cfg):
-        if cfg is None:
-            return default_fix_config()
-        if isinstance(cfg, FixConfig):
-            return cfg
-        c = default_fix_config()
-        for k, v in dict(cfg).items():
-            if k not in FIX_CONFIG_FIELDS:
-                raise ValueError(f"unknown fix setting {k!r}")
-            setattr(c, k, v)
-        return c
-
     def fix(self, fix, kinds, stats=True, cfg=None):
         """One fix of every instance: fix (batch, 5) rows {z_x, z_y, z_yaw, sigma_pos, sigma_yaw}, kinds [batch] (FIX_POS | FIX_YAW).  Both as
         ints: the DEVICE pointers of the arrays, read in stream order (nothing is returned and nothing synchronises).  stats=True returns
         dict(verdict [batch] (position | heading << 4), nis (batch, 2), rec (16,)) and synchronises; stats=False None."""
         self._need()
-        c = self._fix_config(cfg)
+        c = config_from(cfg, *FIX)
         if isinstance(fix, int) or isinstance(kinds, int):
             if not (isinstance(fix, int) and isinstance(kinds, int)):
                 raise ValueError("fix and kinds are both device pointers or both arrays")
@@ -1291,27 +1029,14 @@ class BatchedEKF(BatchedFilter):
         k = np.ascontiguousarray(kinds, dtype=np.int32)
         if f.shape != (self.batch, 5) or k.shape != (self.batch,):
             raise ValueError(f"expected fix ({self.batch}, 5) and kinds ({self.batch},), got {f.shape} and {k.shape}")
-        out = dict(verdict=np.zeros(self.batch, dtype=np.int32), nis=np.zeros((self.batch, 2)), rec=np.zeros(16)) if stats else None
-        _lib.check(_lib.lib().slam_fix(self.h, C.byref(c), _d(f), _i(k), _i(out["verdict"]) if stats else None, _d(out["nis"]) if stats else None,
-                                       _d(out["rec"]) if stats else None))
-        return out
+        out = dict(verdict=np.zeros(self.batch, dtype=np.int32), nis=np.zeros((self.batch, 2)), rec=np.zeros(16)) if stats else {}
+        _lib.check(_lib.lib().slam_fix(self.h, C.byref(c), _d(f), _i(k), opt(out.get("verdict")), opt(out.get("nis")), opt(out.get("rec"))))
+        return out or None
 
     def set_fix_sensor(self, rows):
         """The simulated source of fix_sense() and fix_run (slam_set_fix_sensor_each): one FixSensorConfig (or a dict of its fields),
         replicated over the batch, or `batch` of them; None returns to the all-zero row, which emits nothing.  Inputs, not state."""
-        self._need()
-        if rows is None:
-            _lib.check(_lib.lib().slam_set_fix_sensor_each(self.h, None))
-            return
-        if isinstance(rows, dict):
-            rows = default_fix_sensor_config(**rows)
-        if isinstance(rows, FixSensorConfig):
-            rows = [rows] * self.batch
-        if not (isinstance(rows, C.Array) and rows._type_ is FixSensorConfig):
-            rows = (FixSensorConfig * len(rows))(*rows)
-        if len(rows) != self.batch:
-            raise ValueError(f"expected {self.batch} fix sensor rows, got {len(rows)}")
-        _lib.check(_lib.lib().slam_set_fix_sensor_each(self.h, rows))
+        self._set_rows("slam_set_fix_sensor_each", rows, FixSensorConfig, "fix sensor", one=default_fix_sensor_config)
 
     def fix_sense(self, dev=None):
         """One emission of the simulated source from the true poses: dict(fix (batch, 5), kinds [batch], jumped [batch]).  dev = (d_fix,
@@ -1329,13 +1054,7 @@ class BatchedEKF(BatchedFilter):
         device; the same bits as that loop of single calls.  cmds (T, 2): shared commands; (T, batch, 2): per instance; None with T ticks:
         the controller of set_path / set_paths.  Returns a FixResult; series=True also records verdict, nis, fix and kinds of every tick."""
         self._need()
-        c32, want, T = self._run_cmds("fix_run", cmds, T)
-        if c32 is None:
-            source = want if source is None else source
-        elif source is not None and source != want:
-            raise ValueError(f"source {source} does not match commands of shape {c32.shape}")
-        else:
-            source = want
+        c32, source, T = self._run_cmds("fix_run", cmds, T, source)
         n = max(T, 0)
         res = FixResult(np.zeros((n, 16)))
         log = None
@@ -1344,38 +1063,23 @@ class BatchedEKF(BatchedFilter):
             res.nis, res.fix = np.zeros((n, self.batch, 2)), np.zeros((n, self.batch, 5))
             if n > 0:
                 log = FixLog(_d(res.fix), _i(res.kinds))
-        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
-        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
-        _lib.check(_lib.lib().slam_fix_run(self.h, C.byref(self._fix_config(cfg)), int(source), None if c32 is None else _f(c32), T, pd(res.recs),
-                                           pi(res.verdict), pd(res.nis), None if log is None else C.byref(log)))
+        c = config_from(cfg, *FIX)
+        _lib.check(_lib.lib().slam_fix_run(self.h, C.byref(c), source, ptr(c32), T, opt(res.recs),
+                                           opt(res.verdict), opt(res.nis), None if log is None else C.byref(log)))
         self.timestep += n
         return res
 
     def last_fix_work(self):
         """(model bytes the last fix, or all the fixes of the last fix_run, had to move; device ms of the fix launches of the last fix_run
         or -1 without set_nav_timing; device ms of that whole run or -1)."""
-        self._need(); by = C.c_double(0); a = C.c_double(0); b = C.c_double(0)
-        _lib.check(_lib.lib().slam_last_fix_work(self.h, C.byref(by), C.byref(a), C.byref(b)))
-        return by.value, a.value, b.value
+        return self._last_work("slam_last_fix_work", 3)
 
     # -- the simulator source with a sensor fault model (slam_sense_*, the *_run_sim calls; include/slam_batch.h) --
     def set_sensor(self, rows):
         """The sensor fault model of sense() and the *_run_sim calls (slam_set_sensor_each): one SensorConfig (or a dict of its fields),
         replicated over the batch, or `batch` of them (a sequence or a ctypes array); None returns to the all-off row.  Inputs, not state:
         set them again after load_state."""
-        self._need()
-        if rows is None:
-            _lib.check(_lib.lib().slam_set_sensor_each(self.h, None))
-            return
-        if isinstance(rows, dict):
-            rows = default_sensor_config(**rows)
-        if isinstance(rows, SensorConfig):
-            rows = [rows] * self.batch
-        if not (isinstance(rows, C.Array) and rows._type_ is SensorConfig):
-            rows = (SensorConfig * len(rows))(*rows)
-        if len(rows) != self.batch:
-            raise ValueError(f"expected {self.batch} sensor rows, got {len(rows)}")
-        _lib.check(_lib.lib().slam_set_sensor_each(self.h, rows))
+        self._set_rows("slam_set_sensor_each", rows, SensorConfig, "sensor", one=default_sensor_config)
 
     def sense(self, cmdMsg, k_stride, labels=True, stats=True):
         """One tick of the sensor model for the command the step will be given (one command or (batch, 2)): dict(meas (batch, k_stride, 3),
@@ -1391,19 +1095,15 @@ class BatchedEKF(BatchedFilter):
             out["rec"] = np.zeros(16)
         _lib.check(_lib.lib().slam_sense(self.h, _f(cmd), int(cmd.ndim == 2), _f(out["meas"]), _i(out["count"]), ks,
                                          _i(out["origin"]) if labels else None, _i(out["fault"]) if labels else None, _d(out["truth_next"]),
-                                         _d(out["rec"]) if stats else None))
+                                         opt(out.get("rec"))))
         return out
 
     def sense_dev(self, cmdMsg, d_meas_ptr, d_count_ptr, k_stride, d_origin_ptr=None, d_fault_ptr=None):
         """sense() into DEVICE buffers, in the order of the handle's stream; cmdMsg one command (host) or, as an int, the device pointer
         of (batch, 2) commands.  Does not synchronise."""
         self._need()
-        each = isinstance(cmdMsg, int)
-        cmd = None if each else self._cmd(cmdMsg)
-        if cmd is not None and cmd.ndim != 1:
-            raise ValueError("sense_dev takes one command, or the device pointer of per-instance commands")
-        cp = C.c_void_p(cmdMsg) if each else C.cast(_f(cmd), C.c_void_p)
-        _lib.check(_lib.lib().slam_sense_dev(self.h, cp, int(each), C.c_void_p(d_meas_ptr), C.c_void_p(d_count_ptr), int(k_stride),
+        cp, each = self._cmd_dev(cmdMsg, "sense_dev takes")
+        _lib.check(_lib.lib().slam_sense_dev(self.h, cp, each, C.c_void_p(d_meas_ptr), C.c_void_p(d_count_ptr), int(k_stride),
                                              C.c_void_p(d_origin_ptr) if d_origin_ptr else None, C.c_void_p(d_fault_ptr) if d_fault_ptr else None))
 
     def sense_commit(self, stats=True):
@@ -1411,106 +1111,47 @@ class BatchedEKF(BatchedFilter):
         its position error is added.  stats=True returns the tick's record (16,) and synchronises; stats=False returns None."""
         self._need()
         rec = np.zeros(16) if stats else None
-        _lib.check(_lib.lib().slam_sense_commit(self.h, _d(rec) if stats else None))
+        _lib.check(_lib.lib().slam_sense_commit(self.h, opt(rec)))
         return rec
-
-    def _sim_run(self, name, cmds, T, source, k_stride, log):
-        """The shared arguments of the *_run_sim calls: (float32 commands or None, source, T, k_stride, SenseLogResult or None, its struct)."""
-        self._need()
-        c32, want, T = self._run_cmds(name, cmds, T)
-        if c32 is None:
-            source = want if source is None else source
-        elif source is not None and source != want:
-            raise ValueError(f"source {source} does not match commands of shape {c32.shape}")
-        else:
-            source = want
-        ks, n = int(k_stride), max(T, 0)
-        sense = SenseLogResult(n, self.batch, max(ks, 1), log) if log else None
-        return c32, int(source), T, ks, sense, (C.byref(sense.struct()) if log and n > 0 else None)
 
     def gate_run_sim(self, cmds=None, T=None, source=None, series=False, log=False, k_stride=16, cfg=None):
         """gate_run with the simulator and the sensor model of set_sensor as its source: cmds (T, 2) shared, (T, batch, 2) per instance,
         None with T ticks the controller of set_path (source INNOVATION_NAV).  Returns a GateResult whose `.sense` is None or, with
         log=True, a SenseLogResult (meas, count, origin, fault, truth, err_pos, cmds, recs of every tick); log may also name the wanted
         arrays, e.g. ("origin", "err_pos"): the others are not held on the device or copied."""
-        c32, source, T, ks, sense, lp = self._sim_run("gate_run_sim", cmds, T, source, k_stride, log)
-        n = max(T, 0)
-        res = GateResult(np.zeros((n, 16)))
-        if series:
-            res.nis_sum = np.zeros((n, self.batch))
-            res.n_upd, res.n_rej, res.flags = (np.zeros((n, self.batch), dtype=np.int32) for _ in range(3))
-        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
-        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
-        _lib.check(_lib.lib().slam_gate_run_sim(self.h, C.byref(self._gate_config(cfg)), source, None if c32 is None else _f(c32), ks, T,
-                                                pd(res.recs), pd(res.nis_sum), pi(res.n_upd), pi(res.n_rej), pi(res.flags), lp))
-        self.timestep += n
-        res.sense = sense
-        return res
+        return self._filtered_run("gate", (cfg,), series, sim=("gate_run_sim", cmds, T, source, k_stride, log))
 
     def associate_run_sim(self, cmds=None, T=None, source=None, series=False, log=False, k_stride=16, cfg=None):
         """associate_run with the simulator and the sensor model as its source (arguments and `.sense` as gate_run_sim)."""
-        c32, source, T, ks, sense, lp = self._sim_run("associate_run_sim", cmds, T, source, k_stride, log)
-        n = max(T, 0)
-        res = AssocResult(np.zeros((n, 16)))
-        if series:
-            res.n_match, res.n_new, res.n_drop, res.flags = (np.zeros((n, self.batch), dtype=np.int32) for _ in range(4))
-        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
-        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
-        _lib.check(_lib.lib().slam_associate_run_sim(self.h, C.byref(self._assoc_config(cfg)), source, None if c32 is None else _f(c32), ks, T,
-                                                     pd(res.recs), pi(res.n_match), pi(res.n_new), pi(res.n_drop), pi(res.flags), lp))
-        self.timestep += n
-        res.sense = sense
-        return res
+        return self._filtered_run("associate", (cfg,), series, sim=("associate_run_sim", cmds, T, source, k_stride, log))
 
     def associate_joint_run_sim(self, cmds=None, T=None, source=None, series=False, log=False, k_stride=16, cfg=None):
         """associate_joint_run with the simulator and the sensor model as its source (arguments and `.sense` as gate_run_sim)."""
-        c32, source, T, ks, sense, lp = self._sim_run("associate_joint_run_sim", cmds, T, source, k_stride, log)
-        n = max(T, 0)
-        res = JointResult(np.zeros((n, 16)))
-        if series:
-            res.n_match, res.n_new, res.n_drop, res.flags, res.nodes = (np.zeros((n, self.batch), dtype=np.int32) for _ in range(5))
-            res.d2_joint = np.zeros((n, self.batch))
-        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
-        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
-        _lib.check(_lib.lib().slam_associate_joint_run_sim(self.h, C.byref(self._joint_config(cfg)), source, None if c32 is None else _f(c32), ks, T,
-                                                           pd(res.recs), pi(res.n_match), pi(res.n_new), pi(res.n_drop), pi(res.flags),
-                                                           pd(res.d2_joint), pi(res.nodes), lp))
-        self.timestep += n
-        res.sense = sense
-        return res
+        return self._filtered_run("associate_joint", (cfg,), series, sim=("associate_joint_run_sim", cmds, T, source, k_stride, log))
 
     def manage_run_sim(self, cmds=None, T=None, source=None, series=False, log=False, k_stride=16, cfg=None, map_cfg=None):
         """manage_run with the simulator and the sensor model as its source (arguments and `.sense` as gate_run_sim)."""
-        c32, source, T, ks, sense, lp = self._sim_run("manage_run_sim", cmds, T, source, k_stride, log)
-        n = max(T, 0)
-        res = MapResult(np.zeros((n, 16)))
-        if series:
-            res.n_match, res.n_new, res.n_drop, res.flags, res.n_removed = (np.zeros((n, self.batch), dtype=np.int32) for _ in range(5))
-        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
-        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
-        _lib.check(_lib.lib().slam_manage_run_sim(self.h, C.byref(self._assoc_config(cfg)), C.byref(self._map_config(map_cfg)), source,
-                                                  None if c32 is None else _f(c32), ks, T, pd(res.recs), pi(res.n_match), pi(res.n_new),
-                                                  pi(res.n_drop), pi(res.n_removed), pi(res.flags), lp))
-        self.timestep += n
-        res.sense = sense
-        return res
+        return self._filtered_run("manage", (cfg, map_cfg), series, sim=("manage_run_sim", cmds, T, source, k_stride, log))
 
     def manage_merge_run_sim(self, cmds=None, T=None, source=None, series=False, log=False, k_stride=16, cfg=None, map_cfg=None, merge_cfg=None):
         """manage_merge_run with the simulator and the sensor model as its source (arguments and `.sense` as gate_run_sim)."""
-        c32, source, T, ks, sense, lp = self._sim_run("manage_merge_run_sim", cmds, T, source, k_stride, log)
-        n = max(T, 0)
-        res = MergeResult(np.zeros((n, 16)))
-        if series:
-            res.n_match, res.n_new, res.n_drop, res.flags, res.n_removed, res.n_merged = (np.zeros((n, self.batch), dtype=np.int32) for _ in range(6))
-        pd = (lambda a: None if a is None or a.size == 0 else _d(a))
-        pi = (lambda a: None if a is None or a.size == 0 else _i(a))
-        _lib.check(_lib.lib().slam_manage_merge_run_sim(self.h, C.byref(self._assoc_config(cfg)), C.byref(self._map_config(map_cfg)),
-                                                        C.byref(self._merge_config(merge_cfg)), source, None if c32 is None else _f(c32), ks, T,
-                                                        pd(res.recs), pi(res.n_match), pi(res.n_new), pi(res.n_drop), pi(res.n_removed),
-                                                        pi(res.n_merged), pi(res.flags), lp))
-        self.timestep += n
-        res.sense = sense
-        return res
+        return self._filtered_run("manage_merge", (cfg, map_cfg, merge_cfg), series,
+                                  sim=("manage_merge_run_sim", cmds, T, source, k_stride, log))
+
+
+_I32, _F64 = np.int32, np.float64
+_ASSOC_SERIES = (("n_match", _I32), ("n_new", _I32), ("n_drop", _I32))
+# the ten runs that filter a message before the step: the result class, the symbols of the recorded-log form and of the simulator
+# form, the settings in C order, and - after recs - the (T, batch) series in C order (flags closes the manage runs; d2_joint and nodes
+# follow it in the joint runs)
+_RUNS = dict(
+    gate=(GateResult, "slam_gate_run", "slam_gate_run_sim", (GATE,), (("nis_sum", _F64), ("n_upd", _I32), ("n_rej", _I32), ("flags", _I32))),
+    associate=(AssocResult, "slam_associate_run", "slam_associate_run_sim", (ASSOC,), _ASSOC_SERIES + (("flags", _I32),)),
+    associate_joint=(JointResult, "slam_associate_joint_run", "slam_associate_joint_run_sim", (JOINT,),
+                     _ASSOC_SERIES + (("flags", _I32), ("d2_joint", _F64), ("nodes", _I32))),
+    manage=(MapResult, "slam_manage_run", "slam_manage_run_sim", (ASSOC, MAP), _ASSOC_SERIES + (("n_removed", _I32), ("flags", _I32))),
+    manage_merge=(MergeResult, "slam_manage_merge_run", "slam_manage_merge_run_sim", (ASSOC, MAP, MERGE),
+                  _ASSOC_SERIES + (("n_removed", _I32), ("n_merged", _I32), ("flags", _I32))))
 
 
 class SenseLogResult:
@@ -1537,231 +1178,7 @@ class SenseLogResult:
             setattr(self, n, np.zeros(shape, dtype=dt) if n in want else None)
 
     def struct(self):
-        cast = dict(meas=_f, cmds=_f, count=_i, origin=_i, fault=_i, truth=_d, err_pos=_d, recs=_d)
-        return SenseLog(*[None if getattr(self, n) is None else cast[n](getattr(self, n)) for n in self.NAMES])
-
-
-def sense_instance_host(seed, instance, step, truth, cmd, map_xy, cfg, vision=(3.0, -1.57, 1.57), sim_noise=None, row=None, k_stride=16, status=0):
-    """TEST HOOK (slam_sense_instance_host): the sensor model of one instance compiled for the host; no GPU.  cfg: the SlamConfig (d_max,
-    th_max and, without sim_noise, the simulator's half-widths V_00, V_11, W_00, W_11); vision: (range_max, fov_min, fov_max).  Returns
-    dict(meas (k_stride, 3), count, origin, fault (k_stride,), truth_next (3,), flags, rec (16,))."""
-    truth = np.ascontiguousarray(truth, dtype=np.float64)
-    c = np.ascontiguousarray(cmd, dtype=np.float32)
-    m = np.ascontiguousarray(map_xy, dtype=np.float64).reshape(-1, 2)
-    sn = np.ascontiguousarray((cfg.V_00, cfg.V_11, cfg.W_00, cfg.W_11) if sim_noise is None else sim_noise, dtype=np.float64)
-    ks = int(k_stride)
-    out = dict(meas=np.zeros((max(ks, 0), 3), dtype=np.float32), origin=np.zeros(max(ks, 0), dtype=np.int32), fault=np.zeros(max(ks, 0), dtype=np.int32),
-               truth_next=np.zeros(3), rec=np.zeros(16))
-    count, flags = C.c_int32(0), C.c_int32(0)
-    _lib.check(_lib.lib().slam_sense_instance_host(int(seed), int(instance), int(step), _d(truth), _f(c), int(status), _d(m), m.shape[0],
-                                                   float(cfg.d_max), float(cfg.th_max), float(vision[0]), float(vision[1]), float(vision[2]), _d(sn),
-                                                   None if row is None else C.byref(row), ks, _f(out["meas"]), C.byref(count), _i(out["origin"]),
-                                                   _i(out["fault"]), _d(out["truth_next"]), C.byref(flags), _d(out["rec"])))
-    out["count"], out["flags"] = count.value, flags.value
-    return out
-
-
-def fix_instance_host(x, P, L_max, row, kinds, status=0, f32_storage=False, cfg=None):
-    """TEST HOOK (slam_fix_instance_host): the fix of one instance compiled for the host, as two sequential passes; no GPU.  x (3 + 2 M,),
-    P (n, n), row (5,), kinds.  Returns dict(x, P (the state after the fix; the input's bytes where no part applied), verdict, nis (2,),
-    rec (16,))."""
-    x = np.array(x, dtype=np.float64); P = np.array(P, dtype=np.float64)
-    n = x.shape[0]; M = (n - 3) // 2
-    if n < 3 or n != 3 + 2 * M or P.shape != (n, n):
-        raise ValueError("x and P do not describe a state of 3 + 2 M entries")
-    r = np.ascontiguousarray(row, dtype=np.float64)
-    if r.shape != (5,):
-        raise ValueError("a fix row has 5 entries")
-    c_cfg = default_fix_config() if cfg is None else cfg
-    Pf = np.ascontiguousarray(P).reshape(-1).copy()
-    verdict = C.c_int32(0); nis = np.zeros(2); rec = np.zeros(16)
-    _lib.check(_lib.lib().slam_fix_instance_host(_d(x), _d(Pf), M, int(L_max), int(status), int(bool(f32_storage)), C.byref(c_cfg), _d(r), int(kinds),
-                                                 C.byref(verdict), _d(nis), _d(rec)))
-    return dict(x=x, P=Pf.reshape(n, n), verdict=verdict.value, nis=nis, rec=rec)
-
-
-def fix_sense_instance_host(seed, instance, step, truth, row=None):
-    """TEST HOOK (slam_fix_sense_instance_host): the simulated source of fixes of one instance on the host; no GPU.  Returns dict(fix (5,),
-    kinds, jumped)."""
-    t = np.ascontiguousarray(truth, dtype=np.float64)
-    fix = np.zeros(5); kinds = C.c_int32(0); jumped = C.c_int32(0)
-    _lib.check(_lib.lib().slam_fix_sense_instance_host(int(seed), int(instance), int(step), _d(t), None if row is None else C.byref(row), _d(fix),
-                                                       C.byref(kinds), C.byref(jumped)))
-    return dict(fix=fix, kinds=kinds.value, jumped=jumped.value)
-
-
-def merge_instance_host(x, P, ids, L_max, status=0, f32_storage=False, cfg=None, seen=None, expected=None, partner=None, fuse=True):
-    """TEST HOOK (slam_merge_instance_host): the find, the fusion and the compaction of one instance compiled for the host; no GPU.
-    x (3 + 2 M,), P (n, n), ids (M,); seen / expected (L_max,) or None (no counters); partner (L_max,) caller pairs or None (the pairs
-    found); fuse=False: the decision alone.  Returns dict(x, P, ids (the merged state), M, partner, d2 (L_max,: the find on the state
-    given), rec (16,), seen, expected (L_max,) or None)."""
-    x = np.array(x, dtype=np.float64); P = np.array(P, dtype=np.float64)
-    ids_in = np.ascontiguousarray(ids, dtype=np.int32); M = ids_in.shape[0]
-    if x.shape != (3 + 2 * M,) or P.shape != (3 + 2 * M, 3 + 2 * M):
-        raise ValueError("x and P do not match the number of ids")
-    L_max = int(L_max)
-    row = np.zeros(max(L_max, M, 1), dtype=np.int32); row[:M] = ids_in
-    if (seen is None) != (expected is None):
-        raise ValueError("seen and expected come together")
-    se = None if seen is None else np.array(seen, dtype=np.int32)
-    ex = None if expected is None else np.array(expected, dtype=np.int32)
-    pin = None if partner is None else np.ascontiguousarray(partner, dtype=np.int32)
-    if pin is not None and pin.shape != (L_max,):
-        raise ValueError("partner does not have L_max entries")
-    pout = np.zeros(max(L_max, 1), dtype=np.int32); dout = np.zeros(max(L_max, 1)); rec = np.zeros(16); Mo = C.c_int32(0)
-    c_cfg = default_merge_config() if cfg is None else cfg
-    Pf = np.ascontiguousarray(P).reshape(-1).copy()
-    _lib.check(_lib.lib().slam_merge_instance_host(_d(x), _d(Pf), _i(row), M, L_max, int(status), int(bool(f32_storage)), C.byref(c_cfg),
-                                                   None if se is None else _i(se), None if ex is None else _i(ex),
-                                                   None if pin is None else _i(pin), int(bool(fuse)), _i(pout), _d(dout), _d(rec), C.byref(Mo)))
-    Mk = Mo.value; n2 = 3 + 2 * Mk
-    return dict(x=x[:n2].copy(), P=Pf[:n2 * n2].reshape(n2, n2).copy(), ids=row[:Mk].copy(), M=Mk, partner=pout[:L_max].copy(), d2=dout[:L_max].copy(),
-                rec=rec, seen=None if se is None else se[:L_max].copy(), expected=None if ex is None else ex[:L_max].copy(), ids_row=row[:L_max].copy())
-
-
-def map_instance_host(x, P, ids, L_max, status=0, meas=None, count=None, k_stride=None, assoc_flag=0, vision=(3.0, -1.57, 1.57), f32_storage=False,
-                      cfg=None, seen=None, expected=None, remove=None, prune=False):
-    """TEST HOOK (slam_map_instance_host): the tally, the prune decision and the compaction of one instance compiled for the host; no GPU.
-    x (3 + 2 M,), P (n, n), ids (M,); meas (k, 3) float32 or None (no tally); vision = (range_max, fov_min, fov_max); seen / expected
-    (L_max,) or None (zeros); remove (M,) mask or None; prune: decide by the rule.  Returns dict(x, P, ids (the compacted state), M, mask
-    (L_max,), seen, expected (L_max,))."""
-    x = np.array(x, dtype=np.float64); P = np.array(P, dtype=np.float64)
-    ids_in = np.ascontiguousarray(ids, dtype=np.int32); M = ids_in.shape[0]
-    if x.shape != (3 + 2 * M,) or P.shape != (3 + 2 * M, 3 + 2 * M):
-        raise ValueError("x and P do not match the number of ids")
-    L_max = int(L_max)
-    row = np.zeros(max(L_max, M), dtype=np.int32); row[:M] = ids_in
-    se = np.zeros(max(L_max, 1), dtype=np.int32) if seen is None else np.array(seen, dtype=np.int32)
-    ex = np.zeros(max(L_max, 1), dtype=np.int32) if expected is None else np.array(expected, dtype=np.int32)
-    mp, cnt, ks = None, 0, 1
-    if meas is not None:
-        m = np.ascontiguousarray(meas, dtype=np.float32).reshape(-1, 3)
-        ks = max(m.shape[0], 1) if k_stride is None else int(k_stride)
-        cnt = m.shape[0] if count is None else int(count)
-        if ks < m.shape[0]:
-            raise ValueError("k_stride is smaller than the message")
-        mrow = np.zeros((ks, 3), dtype=np.float32); mrow[:m.shape[0]] = m
-        mp = _f(mrow)
-    rm = None if remove is None else np.ascontiguousarray(remove, dtype=np.int32)
-    if rm is not None and rm.shape != (M,):
-        raise ValueError("remove does not match the number of ids")
-    if rm is not None and M == 0:
-        rm = np.zeros(1, dtype=np.int32)
-    mask = np.zeros(max(L_max, 1), dtype=np.int32); Mo = C.c_int32(0)
-    c_cfg = default_map_config() if cfg is None else cfg
-    Pf = np.ascontiguousarray(P).reshape(-1).copy()
-    _lib.check(_lib.lib().slam_map_instance_host(_d(x), _d(Pf), _i(row), M, L_max, int(status), mp, cnt, ks, int(assoc_flag), float(vision[0]),
-                                                 float(vision[1]), float(vision[2]), int(bool(f32_storage)), C.byref(c_cfg), _i(se), _i(ex),
-                                                 None if rm is None else _i(rm), int(bool(prune)), _i(mask), C.byref(Mo)))
-    Mk = Mo.value; n2 = 3 + 2 * Mk
-    return dict(x=x[:n2].copy(), P=Pf[:n2 * n2].reshape(n2, n2).copy(), ids=row[:Mk].copy(), M=Mk, mask=mask[:L_max].copy(), seen=se[:L_max].copy(),
-                expected=ex[:L_max].copy(), ids_row=row[:L_max].copy())
-
-
-def innovation_instance_host(x, P, ids, L_max, status, cmd, meas, noise, lm_from_pred=False, f32_storage=False, cfg=None):
-    """TEST HOOK (slam_innovation_instance_host): the per-instance function of the innovation kernel compiled for the host; no GPU.
-    x (3 + 2 M,), P (n, n), ids (M,), meas (k, 3) float32, noise a config.Noise row.  Returns the dict of innovation() for one instance."""
-    x = np.ascontiguousarray(x, dtype=np.float64); P = np.ascontiguousarray(P, dtype=np.float64)
-    ids = np.ascontiguousarray(ids, dtype=np.int32); M = ids.shape[0]
-    m = np.ascontiguousarray(meas, dtype=np.float32).reshape(-1, 3)
-    c = np.ascontiguousarray(cmd, dtype=np.float32).reshape(2)
-    if x.shape != (3 + 2 * M,) or P.shape != (3 + 2 * M, 3 + 2 * M):
-        raise ValueError("x and P do not match the number of ids")
-    out = dict(rec=np.zeros(16), det=np.zeros((INNOV_MAX_DET, 6)), post=np.zeros(12))
-    s = C.c_double(0); nu = C.c_int32(0); nn = C.c_int32(0); fl = C.c_int32(0)
-    c_cfg = default_innovation_config() if cfg is None else cfg
-    _lib.check(_lib.lib().slam_innovation_instance_host(_d(x), _d(P), _i(ids) if M else None, M, int(L_max), int(status), _f(c),
-                                                        _f(m) if m.shape[0] else None, m.shape[0], C.byref(noise), int(bool(lm_from_pred)),
-                                                        int(bool(f32_storage)), C.byref(c_cfg), _d(out["rec"]), C.byref(s), C.byref(nu),
-                                                        C.byref(nn), C.byref(fl), _d(out["det"]), _d(out["post"])))
-    out.update(nis_sum=s.value, n_upd=nu.value, n_new=nn.value, flags=fl.value)
-    return out
-
-
-def gate_instance_host(x, P, ids, L_max, status, cmd, meas, noise, lm_from_pred=False, f32_storage=False, cfg=None, count=None, k_stride=None):
-    """TEST HOOK (slam_gate_instance_host): the per-instance function of the gate kernel compiled for the host; no GPU.  Arguments as
-    innovation_instance_host; count (default: the rows of meas) is the count as given and k_stride (default: max(rows, 1)) the capacity
-    of the message row.  Returns the dict of gate() for one instance: meas_out (k_stride, 3) starts as a copy of the input row."""
-    x = np.ascontiguousarray(x, dtype=np.float64); P = np.ascontiguousarray(P, dtype=np.float64)
-    ids = np.ascontiguousarray(ids, dtype=np.int32); M = ids.shape[0]
-    m = np.ascontiguousarray(meas, dtype=np.float32).reshape(-1, 3)
-    c = np.ascontiguousarray(cmd, dtype=np.float32).reshape(2)
-    if x.shape != (3 + 2 * M,) or P.shape != (3 + 2 * M, 3 + 2 * M):
-        raise ValueError("x and P do not match the number of ids")
-    ks = max(m.shape[0], 1) if k_stride is None else int(k_stride)
-    count = m.shape[0] if count is None else int(count)
-    if ks < m.shape[0]:
-        raise ValueError("k_stride is smaller than the message")
-    row = np.zeros((ks, 3), dtype=np.float32); row[:m.shape[0]] = m
-    out = dict(rec=np.zeros(16), det=np.zeros((INNOV_MAX_DET, 6)), post=np.zeros(12), meas_out=row.copy(), verdict=np.zeros(INNOV_MAX_DET, dtype=np.int32))
-    s = C.c_double(0); nu = C.c_int32(0); nn = C.c_int32(0); fl = C.c_int32(0); co = C.c_int32(0); nr = C.c_int32(0)
-    c_cfg = default_gate_config() if cfg is None else cfg
-    _lib.check(_lib.lib().slam_gate_instance_host(_d(x), _d(P), _i(ids) if M else None, M, int(L_max), int(status), _f(c), _f(row), count, ks,
-                                                  C.byref(noise), int(bool(lm_from_pred)), int(bool(f32_storage)), C.byref(c_cfg),
-                                                  _d(out["rec"]), C.byref(s), C.byref(nu), C.byref(nn), C.byref(fl), _d(out["det"]),
-                                                  _d(out["post"]), _f(out["meas_out"]), C.byref(co), C.byref(nr), _i(out["verdict"])))
-    out.update(nis_sum=s.value, n_upd=nu.value, n_new=nn.value, flags=fl.value, count_out=co.value, n_rej=nr.value)
-    return out
-
-
-def associate_instance_host(x, P, ids, L_max, status, cmd, meas, noise, lm_from_pred=False, f32_storage=False, cfg=None, count=None, k_stride=None):
-    """TEST HOOK (slam_associate_instance_host): the per-instance function of the association kernel compiled for the host; no GPU.
-    Arguments as gate_instance_host (the id column of meas is not read).  Returns the dict of associate() for one instance, plus cost
-    (count_in, M), the full matrix; meas_out (k_stride, 3) starts as a copy of the input row."""
-    x = np.ascontiguousarray(x, dtype=np.float64); P = np.ascontiguousarray(P, dtype=np.float64)
-    ids = np.ascontiguousarray(ids, dtype=np.int32); M = ids.shape[0]
-    m = np.ascontiguousarray(meas, dtype=np.float32).reshape(-1, 3)
-    c = np.ascontiguousarray(cmd, dtype=np.float32).reshape(2)
-    if x.shape != (3 + 2 * M,) or P.shape != (3 + 2 * M, 3 + 2 * M):
-        raise ValueError("x and P do not match the number of ids")
-    ks = max(m.shape[0], 1) if k_stride is None else int(k_stride)
-    count = m.shape[0] if count is None else int(count)
-    if ks < m.shape[0]:
-        raise ValueError("k_stride is smaller than the message")
-    row = np.zeros((ks, 3), dtype=np.float32); row[:m.shape[0]] = m
-    k_in = min(max(count, 0), ks)
-    out = dict(rec=np.zeros(16), cost=np.full((k_in if k_in <= INNOV_MAX_DET else 0, M), np.nan), verdict=np.zeros(INNOV_MAX_DET, dtype=np.int32),
-               slot=np.zeros(INNOV_MAX_DET, dtype=np.int32), det=np.zeros((INNOV_MAX_DET, 4)), meas_out=row.copy())
-    nm = C.c_int32(0); nn = C.c_int32(0); nd = C.c_int32(0); fl = C.c_int32(0); co = C.c_int32(0)
-    c_cfg = default_assoc_config() if cfg is None else cfg
-    _lib.check(_lib.lib().slam_associate_instance_host(_d(x), _d(P), _i(ids) if M else None, M, int(L_max), int(status), _f(c), _f(row), count, ks,
-                                                       C.byref(noise), int(bool(lm_from_pred)), int(bool(f32_storage)), C.byref(c_cfg),
-                                                       _d(out["rec"]), C.byref(nm), C.byref(nn), C.byref(nd), C.byref(fl),
-                                                       _d(out["cost"]) if out["cost"].size else None, _i(out["verdict"]), _i(out["slot"]),
-                                                       _d(out["det"]), _f(out["meas_out"]), C.byref(co)))
-    out.update(n_match=nm.value, n_new=nn.value, n_drop=nd.value, flags=fl.value, count_out=co.value)
-    return out
-
-
-def associate_joint_instance_host(x, P, ids, L_max, status, cmd, meas, noise, lm_from_pred=False, f32_storage=False, cfg=None, count=None,
-                                  k_stride=None):
-    """TEST HOOK (slam_associate_joint_instance_host): the per-instance function of the joint association kernel compiled for the host; no
-    GPU.  Arguments as associate_instance_host (cfg: a JointConfig, a dict of its fields, or None).  Returns its dict plus d2_joint, nodes
-    and ncand (INNOV_MAX_DET,)."""
-    x = np.ascontiguousarray(x, dtype=np.float64); P = np.ascontiguousarray(P, dtype=np.float64)
-    ids = np.ascontiguousarray(ids, dtype=np.int32); M = ids.shape[0]
-    m = np.ascontiguousarray(meas, dtype=np.float32).reshape(-1, 3)
-    c = np.ascontiguousarray(cmd, dtype=np.float32).reshape(2)
-    if x.shape != (3 + 2 * M,) or P.shape != (3 + 2 * M, 3 + 2 * M):
-        raise ValueError("x and P do not match the number of ids")
-    ks = max(m.shape[0], 1) if k_stride is None else int(k_stride)
-    count = m.shape[0] if count is None else int(count)
-    if ks < m.shape[0]:
-        raise ValueError("k_stride is smaller than the message")
-    row = np.zeros((ks, 3), dtype=np.float32); row[:m.shape[0]] = m
-    k_in = min(max(count, 0), ks)
-    out = dict(rec=np.zeros(16), cost=np.full((k_in if k_in <= INNOV_MAX_DET else 0, M), np.nan), verdict=np.zeros(INNOV_MAX_DET, dtype=np.int32),
-               slot=np.zeros(INNOV_MAX_DET, dtype=np.int32), det=np.zeros((INNOV_MAX_DET, 4)), meas_out=row.copy(),
-               ncand=np.zeros(INNOV_MAX_DET, dtype=np.int32))
-    nm = C.c_int32(0); nn = C.c_int32(0); nd = C.c_int32(0); fl = C.c_int32(0); co = C.c_int32(0); d2 = C.c_double(0); no = C.c_int32(0)
-    _lib.check(_lib.lib().slam_associate_joint_instance_host(_d(x), _d(P), _i(ids) if M else None, M, int(L_max), int(status), _f(c), _f(row), count,
-                                                             ks, C.byref(noise), int(bool(lm_from_pred)), int(bool(f32_storage)),
-                                                             C.byref(_joint_config(cfg)), _d(out["rec"]), C.byref(nm), C.byref(nn), C.byref(nd),
-                                                             C.byref(fl), _d(out["cost"]) if out["cost"].size else None, _i(out["verdict"]),
-                                                             _i(out["slot"]), _d(out["det"]), _f(out["meas_out"]), C.byref(co), C.byref(d2),
-                                                             C.byref(no), _i(out["ncand"])))
-    out.update(n_match=nm.value, n_new=nn.value, n_drop=nd.value, flags=fl.value, count_out=co.value, d2_joint=d2.value, nodes=no.value)
-    return out
+        return SenseLog(*[opt(getattr(self, n)) for n in self.NAMES])
 
 
 def innovation_summary(recs, alpha=0.05):

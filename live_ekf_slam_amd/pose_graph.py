@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from .config import SlamConfig, default_config, FixSensorConfig, default_fix_sensor_config, FIX_POS, FIX_YAW   # noqa: F401
-from .filters import Command, _d, _f, _i
+from ._marshal import Handle, Command, _d, _f, _i, opt
 
 FIX_ABSENT, FIX_STORED, FIX_INVALID = 0, 1, 4            # pgs_fix_verdict (slam_pgs.h)
 
@@ -70,8 +70,10 @@ class NaiveFilter:
         return self.x_t.copy()
 
 
-class BatchedPoseGraph:
+class BatchedPoseGraph(Handle):
     """Pose-graph SLAM (reference: class PoseGraph, filter.h:232-322, pose_graph.cpp) for `batch` instances."""
+
+    _INIT, _INIT_EACH, _DESTROY = "pgs_init", "pgs_init_each", "pgs_destroy"
 
     def __init__(self, batch, num_iterations=1000, L_max=20, k_per_pose=8, device=0):
         self.batch, self.L_max, self.k_per_pose, self.device = int(batch), int(L_max), int(k_per_pose), int(device)
@@ -127,41 +129,12 @@ class BatchedPoseGraph:
         self.h = h
         return self
 
-    def _need(self):
-        if self.h is None:
-            raise _lib.SlamError("readParams() must be called before using the filter")
-
     # -- PoseGraph::init (pose_graph.cpp:68-95) --
     def init(self, x_0=0.0, y_0=0.0, yaw_0=0.0, truth0=None):
         """Scalars: one start pose for the batch.  x_0 a (batch, 3) array of (x, y, yaw): one per instance (pgs_init_each; y_0 and
         yaw_0 are then ignored).  truth0: optional (batch, 3) true start poses of the simulator (default: the start poses)."""
-        self._need()
-        if np.ndim(x_0) == 0 and truth0 is None:
-            _lib.check(_lib.lib().pgs_init(self.h, x_0, y_0, yaw_0))
-        else:
-            pose = (np.asarray(x_0, dtype=np.float32) if np.ndim(x_0) else
-                    np.broadcast_to(np.array([x_0, y_0, yaw_0], dtype=np.float32), (self.batch, 3)))
-            pose = np.ascontiguousarray(self._rows(pose, "x_0", 3), dtype=np.float32)
-            tr = None if truth0 is None else np.ascontiguousarray(self._rows(np.asarray(truth0, dtype=np.float64), "truth0", 3))
-            _lib.check(_lib.lib().pgs_init_each(self.h, _f(pose), None if tr is None else _d(tr)))
-        self.isInit, self.solved_pose_graph, self.timestep = True, False, 0
-        self._sec = None
-
-    def _rows(self, a, what, width):
-        if a.shape != (self.batch, width):
-            raise ValueError(f"{what}: expected shape ({self.batch}, {width}), got {a.shape}")
-        return a
-
-    def _cmd(self, cmdMsg):
-        """(2,) float32 for one command, (batch, 2) for one per instance."""
-        if isinstance(cmdMsg, Command):
-            return np.array([cmdMsg.fwd, cmdMsg.ang], dtype=np.float32)
-        c = np.ascontiguousarray(cmdMsg, dtype=np.float32)
-        if c.shape == (self.batch, 2):
-            return c
-        if c.size == 2:
-            return c.reshape(2)
-        raise ValueError(f"expected a command of shape (2,) or ({self.batch}, 2), got {c.shape}")
+        self._init(x_0, y_0, yaw_0, truth0)
+        self.solved_pose_graph, self._sec = False, None
 
     def _cmds(self, cmds):
         """(T, 2) float32 for the batch (a flat list of 2 T numbers too), (T, batch, 2) per instance."""
@@ -231,9 +204,8 @@ class BatchedPoseGraph:
         if cnt.shape != (self.batch,):
             raise ValueError(f"meas_count: expected shape ({self.batch},), got {cnt.shape}")
         ks = meas.shape[1]
-        sec = self._sec
         step = _lib.lib().pgs_update_each if cmd.ndim == 2 else _lib.lib().pgs_update
-        _lib.check(step(self.h, _f(cmd), _f(meas) if ks else None, _i(cnt) if ks else None, ks, _d(sec) if sec is not None else None))
+        _lib.check(step(self.h, _f(cmd), opt(meas), _i(cnt) if ks else None, ks, opt(self._sec)))
         self.timestep += 1
         if self.solve_graph_every_iteration:                  # :258-264
             self.solvePoseGraph()
@@ -359,9 +331,7 @@ class BatchedPoseGraph:
 
     def last_marginals_work(self):
         """(algorithmic FLOP of the last marginals() summed over the batch, its HIP-event milliseconds)."""
-        self._need(); f = C.c_double(0); ms = C.c_double(0)
-        _lib.check(_lib.lib().pgs_last_marginals_work(self.h, C.byref(f), C.byref(ms)))
-        return f.value, ms.value
+        return self._last_work("pgs_last_marginals_work", 2)
 
     # -- robust loss on the landmark factors (noiseModel::Robust; slam_pgs.h) --
     def set_robust(self, kind, k=0.0):
@@ -446,19 +416,7 @@ class BatchedPoseGraph:
     def set_fix_sensor(self, rows):
         """The simulated source of fix_sense() and run_sim_fix (pgs_set_fix_sensor_each): one FixSensorConfig (or a dict of its fields),
         replicated over the batch, or `batch` of them; None returns to the all-zero row, which emits nothing."""
-        self._need()
-        if rows is None:
-            _lib.check(_lib.lib().pgs_set_fix_sensor_each(self.h, None))
-            return
-        if isinstance(rows, dict):
-            rows = default_fix_sensor_config(**rows)
-        if isinstance(rows, FixSensorConfig):
-            rows = [rows] * self.batch
-        if not (isinstance(rows, C.Array) and rows._type_ is FixSensorConfig):
-            rows = (FixSensorConfig * len(rows))(*rows)
-        if len(rows) != self.batch:
-            raise ValueError(f"expected {self.batch} fix sensor rows, got {len(rows)}")
-        _lib.check(_lib.lib().pgs_set_fix_sensor_each(self.h, rows))
+        self._set_rows("pgs_set_fix_sensor_each", rows, FixSensorConfig, "fix sensor", one=default_fix_sensor_config)
 
     def fix_sense(self, dev=None):
         """One emission of the simulated source from the simulator's true poses: dict(fix (batch, 5), kinds [batch], jumped [batch]).
@@ -502,14 +460,3 @@ class BatchedPoseGraph:
 
     def sync(self):
         self._need(); _lib.check(_lib.lib().pgs_sync(self.h))
-
-    def close(self):
-        if self.h is not None:
-            _lib.lib().pgs_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
