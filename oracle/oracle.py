@@ -56,7 +56,7 @@ def lib():
         L.orc_ukf_init.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float]
         L.orc_ukf_update.argtypes = [C.c_void_p, C.c_float, C.c_float, _fp, C.c_int]
         L.orc_ukf_get.argtypes = [C.c_void_p, _dp, _dp, _ip, _ip, _ip, _ip]
-        L.orc_ukf_sqrt_probe.argtypes = [_dp, C.c_int, C.c_double, _dp]
+        L.orc_ukf_sqrt_probe.argtypes = [_dp, C.c_int, C.c_double, _dp, C.c_int]
         L.orc_ukf_jacobi_pair.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.orc_ukf_jacobi_pair.restype = None
         L.orc_ukf_set_loc_map.argtypes = [C.c_void_p, _dp, C.c_int]
@@ -243,10 +243,12 @@ def ukf_jacobi_pair(k, t, n):
     return p.value, q.value
 
 
-def ukf_sqrt_probe(P, scale):
+def ukf_sqrt_probe(P, scale, pad=None):
+    """pad: None = the rule of a handle just large enough for n (sizes n = 2 mod 4 are padded to n + 2 up to n = 104, the LDS classes);
+    False = the unpadded circle schedule the HBM-streamed class (L_max > 50) runs at every n it holds; True = padded."""
     P = np.ascontiguousarray(P, dtype=np.float64); n = P.shape[0]
     out = np.zeros((n, n))
-    sweeps = lib().orc_ukf_sqrt_probe(_d(P), n, float(scale), _d(out))
+    sweeps = lib().orc_ukf_sqrt_probe(_d(P), n, float(scale), _d(out), -1 if pad is None else int(bool(pad)))
     return out, sweeps
 
 

@@ -482,11 +482,13 @@ void orc_ukf_get(void* h, double* x, double* P, int* M, int* ids, int* timestep,
 // the Jacobi schedule (tests: every pair once per sweep, disjoint rounds, the same pairs as the kernels' jacobi_schedule.h)
 void orc_ukf_jacobi_pair(int k, int t, int n, int* p, int* q) { jacobi_pair(k, t, n, *p, *q); }
 
-int orc_ukf_sqrt_probe(const double* P, int n, double scale, double* out) {
+// pad: 1 / 0 = pad a size n = 2 (mod 4) to n + 2 (the LDS classes) or run the circle method over the n indices (the HBM-streamed class, which a
+// handle of L_max > 50 runs at EVERY n it holds); negative = by size, n <= 104, what a handle whose L_max is just large enough for n does
+int orc_ukf_sqrt_probe(const double* P, int n, double scale, double* out, int pad) {
     std::vector<double> Y((size_t)n * n), V((size_t)n * n);
     for (int r = 0; r < n; ++r)
         for (int c = 0; c < n; ++c) Y[(size_t)r * n + c] = (0.5 * (P[(size_t)r * n + c] + P[(size_t)c * n + r])) * scale;
-    const int sweeps = jacobi_parallel(Y.data(), V.data(), n, 60, false, false, n <= 104);
+    const int sweeps = jacobi_parallel(Y.data(), V.data(), n, 60, false, false, pad < 0 ? n <= 104 : pad != 0);
     if (sweeps < 0) return -1;
     for (int r = 0; r < n; ++r)
         for (int c = 0; c <= r; ++c) {

@@ -12,7 +12,7 @@ def sweep_pairs(O, n):
     return [[O.ukf_jacobi_pair(k, t, n) for k in range(n // 2)] for t in range(n - 1)]
 
 
-@pytest.mark.parametrize("n", [4, 6, 8, 10, 12, 22, 42, 44, 102, 104, 204])
+@pytest.mark.parametrize("n", [4, 6, 8, 10, 12, 22, 42, 44, 102, 104, 106, 202, 204, 402, 404])
 def test_a_sweep_visits_every_pair_once_in_disjoint_rounds(oracle, n):
     seen = set()
     for rnd in sweep_pairs(oracle, n):
@@ -42,7 +42,7 @@ def test_two_rounds_of_a_pass_stay_inside_quadruples(oracle, n):
                 assert rounds[0][2 * kb] == (a, b) and rounds[0][2 * kb + 1] == (c, d)
 
 
-@pytest.mark.parametrize("n", [6, 10, 42])
+@pytest.mark.parametrize("n", [6, 10, 42, 106, 402])
 def test_other_sizes_use_the_circle_method_over_the_indices(oracle, n):
     """(What the HBM-streamed class runs at n = 2 mod 4; the LDS classes pad such a size to n + 2 and walk the quadruples -
     test_padded_sizes_give_the_square_root below.)"""
@@ -58,14 +58,17 @@ def test_device_header_lists_the_same_pairs(oracle, tmp_path):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not found")
+    # every size up to n = 204, then sizes up to the streamed class's capacity (L = 200, n = 404) of both residues mod 4
+    sizes = list(range(4, 206, 2)) + [206, 208, 302, 402, 404]
     src = tmp_path / "sched.cpp"
-    src.write_text('#include <cstdio>\n#include "jacobi_schedule.h"\nint main() { for (int n = 4; n <= 204; n += 2) for (int t = 0; t < n - 1; ++t) '
-                   'for (int k = 0; k < n / 2; ++k) { int p, q; slam::jacobi_pair(k, t, n, p, q); std::printf("%d %d\\n", p, q); } return 0; }\n')
+    src.write_text('#include <cstdio>\n#include "jacobi_schedule.h"\nint main() { const int ns[] = {%s}; for (int n : ns) for (int t = 0; t < n - 1; ++t) '
+                   'for (int k = 0; k < n / 2; ++k) { int p, q; slam::jacobi_pair(k, t, n, p, q); std::printf("%%d %%d\\n", p, q); } return 0; }\n'
+                   % ", ".join(map(str, sizes)))
     exe = tmp_path / "sched"
     subprocess.check_call([hipcc, "-O1", "-std=c++17", "-x", "hip", "--offload-arch=gfx950", "-I", os.path.join(REPO, "live_ekf_slam_amd", "csrc"),
                            str(src), "-o", str(exe)])
     out = np.array(subprocess.check_output([str(exe)]).split(), dtype=np.int64).reshape(-1, 2)
-    ref = [oracle.ukf_jacobi_pair(k, t, n) for n in range(4, 206, 2) for t in range(n - 1) for k in range(n // 2)]
+    ref = [oracle.ukf_jacobi_pair(k, t, n) for n in sizes for t in range(n - 1) for k in range(n // 2)]
     assert np.array_equal(out, np.array(ref, dtype=np.int64))
 
 

@@ -164,6 +164,58 @@ def test_jacobi_sqrt_against_lapack(oracle):
     np.testing.assert_allclose(np.diag(out), [1.0, 1e-4, math.sqrt(2.0), 1e-4], rtol=1e-12)
 
 
+def _spd_case(n):
+    """The matrix of test_padded_sizes_give_the_square_root (test_jacobi_schedule.py) with the filter's slight asymmetry, the filter's scale
+    (2 M + 4) / (1 - W_0) in float, and the LAPACK root of the clamped symmetric part."""
+    rng = np.random.default_rng(n)
+    A = rng.normal(size=(n, n)); P = A @ A.T / n + np.diag(rng.uniform(1e-6, 1.0, n))
+    P[0, 1] += 1e-13
+    scale = float(np.float32(n) / np.float32(0.8))
+    Y = 0.5 * (P + P.T) * scale
+    D, Q = np.linalg.eigh(Y)
+    return P, scale, Y, (Q * np.sqrt(np.maximum(D, 1e-8))) @ Q.T
+
+
+def _assert_is_the_root(out, sweeps, Y, ref):
+    assert 0 < sweeps < 20
+    assert np.abs(out - ref).max() < 1e-12 * max(1.0, np.abs(ref).max())
+    assert np.array_equal(out, out.T)
+    assert np.abs(out @ out - Y).max() < 1e-11 * np.abs(Y).max()
+
+
+@pytest.mark.parametrize("n, pad", [(106, None), (108, None), (202, None), (204, None), (402, None), (404, None),
+                                    (6, False), (10, False), (46, False), (102, False)])
+def test_jacobi_sqrt_of_the_streamed_class_against_lapack(oracle, n, pad):
+    """The path the HBM-streamed class (handles of 51 to 200 landmarks, n up to 404) shares with the oracle: the circle method over the
+    indices themselves at n = 2 (mod 4), no padding.  By size it starts above n = 104; a streamed handle that holds FEW landmarks runs it at
+    small n too (the oracle pads by L_max, not by n), which the probe reaches with pad=False.  Same bars as test_jacobi_sqrt_against_lapack."""
+    P, scale, Y, ref = _spd_case(n)
+    out, sweeps = oracle.ukf_sqrt_probe(P, scale, pad=pad)
+    _assert_is_the_root(out, sweeps, Y, ref)
+
+
+@pytest.mark.parametrize("n", [6, 10, 46])
+def test_padded_and_unpadded_roots_are_the_same_matrix_by_different_paths(oracle, n):
+    """An L_max = 200 handle at n = 46 runs unpadded where an L_max = 50 handle pads to 48: one matrix to 1e-12, but two schedules (rr_pair
+    over 46 indices against quadruples over 48), so not the same bits - were they equal, pad=False would not be probing another path.  The
+    probe's default is the padded rule at these sizes, and pad=True states it."""
+    P, scale, Y, ref = _spd_case(n)
+    padded, sp = oracle.ukf_sqrt_probe(P, scale, pad=True)
+    plain, su = oracle.ukf_sqrt_probe(P, scale, pad=False)
+    dflt, sd = oracle.ukf_sqrt_probe(P, scale)
+    assert sd == sp and np.array_equal(dflt, padded)
+    _assert_is_the_root(padded, sp, Y, ref); _assert_is_the_root(plain, su, Y, ref)
+    assert np.abs(padded - plain).max() < 1e-12 * max(1.0, np.abs(ref).max())
+    assert not np.array_equal(padded, plain)
+
+
+def test_the_probe_pads_only_sizes_that_need_it(oracle):
+    """n = 0 (mod 4) walks the quadruples whatever `pad` says: the argument changes nothing there."""
+    P, scale, _, _ = _spd_case(44)
+    a, sa = oracle.ukf_sqrt_probe(P, scale, pad=True); b, sb = oracle.ukf_sqrt_probe(P, scale, pad=False)
+    assert sa == sb and np.array_equal(a, b)
+
+
 def test_ukf_trajectory_invariants(oracle):
     g = load_golden("sim_seed0_L20_T1000.npz")
     u = oracle.OracleUKF(L_max=20); u.init(0, 0, 0)

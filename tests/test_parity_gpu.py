@@ -667,6 +667,59 @@ def test_state_of_400_landmarks(S, oracle):
     f.close()
 
 
+def _capacity_script(B, L=1000):
+    """Per-instance messages that fill a handle of L landmarks to the brim: ids 0 .. L - 3; 40 known ids and L - 2; 20 known ids and
+    L - 1, L, L + 1 (the last two do not fit: SLAM_INST_CAPACITY at M = L); 30 known ids.  (msgs[b][t] [k][3] float32, cmds [4][2].)"""
+    msgs = []
+    for b in range(B):
+        rng = np.random.default_rng(1000 + b)
+        def msg(ids):
+            m = np.zeros((len(ids), 3), dtype=np.float32)
+            m[:, 0] = ids; m[:, 1] = rng.uniform(0.5, 6.0, len(ids)); m[:, 2] = rng.uniform(-3.1, 3.1, len(ids))
+            return m
+        msgs.append([msg(np.arange(L - 2)),
+                     msg(np.append(rng.choice(L - 2, 40, replace=False), L - 2)),
+                     msg(np.append(rng.choice(L - 1, 20, replace=False), [L - 1, L, L + 1])),
+                     msg(rng.choice(L, 30, replace=False))])
+    rng = np.random.default_rng(10)
+    cmds = np.stack([rng.uniform(0.0, 0.1, 4), rng.uniform(-0.05, 0.05, 4)], axis=1).astype(np.float32)
+    return msgs, cmds
+
+
+def test_state_at_the_capacity_of_1000_landmarks(S, oracle):
+    """n = 2003: the capacity of the HBM-streamed class (slam_create answers SLAM_ERR_UNSUPPORTED above 1000 landmarks), against the oracle
+    and not only against another run on the GPU.  External messages, one oracle per instance: 998 insertions in one message, growth to 999
+    and to 1000, two ids that no longer fit, updates at the full size."""
+    L, B = 1000, 2
+    msgs, cmds = _capacity_script(B, L)
+    f = S.BatchedEKF(B, L).readParams(); f.init(0.0, 0.0, 0.0)
+    assert f.kernel_info()["name"] == "ekf_big_step_kernel"
+    es = [oracle.OracleEKF(L_max=L) for _ in range(B)]
+    for e in es: e.init(0, 0, 0)
+    def walk(b):
+        fl = []
+        for t in range(len(cmds)):
+            fl.append(es[b].update(cmds[t][0], cmds[t][1], msgs[b][t]))
+        return fl
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=B) as pool:
+        flags = pool.map(walk, range(B))                       # (ctypes releases the GIL: the oracles run beside the device)
+        counts = []
+        for t in range(len(cmds)):
+            ks = np.array([len(msgs[b][t]) for b in range(B)], dtype=np.int32)
+            meas = np.zeros((B, int(ks.max()), 3), dtype=np.float32)
+            for b in range(B): meas[b, :ks[b]] = msgs[b][t]
+            f.update(cmds[t], meas, ks)
+            counts.append(f.landmark_counts().tolist())
+        flags = list(flags)
+    print(f"[capacity 1000] counts after every message {counts}, oracle flags {flags}, device flags {f.status().tolist()}")
+    assert counts == [[L - 2] * B, [L - 1] * B, [L] * B, [L] * B]
+    assert flags == [[0, 0, 8, 8]] * B and f.status().tolist() == [8] * B       # SLAM_INST_CAPACITY, from the third message on
+    for b in range(B):
+        _assert_state_equal(f.get_state(b), es[b].state())
+    f.close()
+
+
 @pytest.mark.parametrize("idknown", [1, 0])
 def test_streamed_class_walks_messages_of_any_length(S, oracle, idknown):
     """The HBM-streamed class follows the reference's loop detection by detection (ekf.cpp:73): per-instance external messages with
