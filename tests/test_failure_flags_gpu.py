@@ -6,7 +6,8 @@ failure_flags_reference.py (checked on the oracle alone by test_failure_flags_re
         203, .., false> (the barrier-synchronised step of ekf_step_lockstep.h; bulk stream, write_vehicle and the x copy of ekf_kernel_impl.h);
         L_max 201 fp64 and 60 fp32: ekf_big_step_kernel (ekf_big_kernel.hip checks every entry it stores).  Case H (P alone overflows, empty
         message) hangs on write_vehicle, case L (nine detections) on the last pass of a step of several groups (mid_pass)
-  EKF, eight queued steps per launch (slam_set_lazy_steps(8) + slam_step)  ekf_step_kernel<.., true>: a step of 0 .. 2 updates runs in the
+  EKF, eight queued steps per launch (slam_set_lazy_steps(8) + slam_step)  L_max 20, 50 (both storage types), 100 and 200:
+        ekf_step_kernel<43 | 103 | 203 | 403, .., true>: a step of 0 .. 2 updates runs in the
         decoupled control / streamer loop (ekf_step_decoupled.h; `fastable` takes EMPTY messages too, so case C's step stays in that loop -
         its vehicle rows and columns are checked when the loop ends, write_vehicle), an insertion (case E) goes through the lockstep step
   UKF (slam_step_each)  L_max 20, 50: ukf_step_kernel in its LDS classes; 100: ukf_big_step_kernel; ukf_loc with a map of 20
@@ -145,7 +146,8 @@ QUEUES = {"messages": dict(cases=("A", "B", "E", "F", "A", "H", "B")), "fwd_inf"
 
 
 @pytest.mark.parametrize("queue", list(QUEUES))
-@pytest.mark.parametrize("L_max,f32", [(20, False), (20, True), (50, False), (50, True)], ids=["L20_f64", "L20_f32", "L50_f64", "L50_f32"])
+@pytest.mark.parametrize("L_max,f32", [(20, False), (20, True), (50, False), (50, True), (100, False), (200, False)],
+                         ids=["L20_f64", "L20_f32", "L50_f64", "L50_f32", "L100_f64", "L200_f64"])
 def test_ekf_multi_step_launch(S, oracle, tmp_path, monkeypatch, L_max, f32, queue):
     """eight slam_step calls queued into ONE launch, the failing step the fourth; the same calls with the queue off (one launch each, checked
     after every one); the two handles agree in status everywhere and in state where bit 1 is not set"""
