@@ -35,6 +35,22 @@ CLASS_IDS = ["L20_f64", "L20_f32", "L50_f64", "L50_f32"]
 HOWS = ("near", "far_pos", "far_yaw", "nan_sigma", "neg_sigma", "inf_z", "near")
 
 
+def _fix_row(rng, x, how):
+    """The fix row of one verdict scenario of HOWS, built from the estimate x (three draws of rng)."""
+    row = np.array([x[0] + rng.normal(0, 0.01), x[1] + rng.normal(0, 0.01), x[2] + rng.normal(0, 0.005), 0.03, 0.01])
+    if how == "far_pos":
+        row[0] += 20.0
+    elif how == "far_yaw":
+        row[2] += 2.0
+    elif how == "nan_sigma":
+        row[3] = math.nan; row[4] = math.inf
+    elif how == "neg_sigma":
+        row[3] = -0.03; row[4] = -0.01
+    elif how == "inf_z":
+        row[1] = -math.inf; row[2] = math.nan
+    return row
+
+
 def _fix_rows(states, seed):
     """kinds b % 4 (every combination; some with bits that are ignored) and a verdict scenario (b // 4) % 7 per instance, built from
     the instance's own estimate."""
@@ -43,19 +59,7 @@ def _fix_rows(states, seed):
     fix = np.zeros((n, 5)); kinds = np.zeros(n, np.int32)
     for b, st in enumerate(states):
         x = st["x"] if np.isfinite(st["x"][:3]).all() else np.zeros(3)
-        how = HOWS[(b // 4) % len(HOWS)]
-        row = np.array([x[0] + rng.normal(0, 0.01), x[1] + rng.normal(0, 0.01), x[2] + rng.normal(0, 0.005), 0.03, 0.01])
-        if how == "far_pos":
-            row[0] += 20.0
-        elif how == "far_yaw":
-            row[2] += 2.0
-        elif how == "nan_sigma":
-            row[3] = math.nan; row[4] = math.inf
-        elif how == "neg_sigma":
-            row[3] = -0.03; row[4] = -0.01
-        elif how == "inf_z":
-            row[1] = -math.inf; row[2] = math.nan
-        fix[b] = row
+        fix[b] = _fix_row(rng, x, HOWS[(b // 4) % len(HOWS)])
         kinds[b] = (b % 4) | (16 if b % 5 == 0 else 0)
     return fix, kinds
 
