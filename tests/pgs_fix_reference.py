@@ -220,9 +220,15 @@ def case(name):
 def placement(N, path):
     """The poses of the placement test's fixes in a graph of N poses: pose 0 (with the prior), separators of the path's segmentation,
     segment-interior poses, the last pose.  (Separators are the multiples of the segment length: 5, 10 under seg5, 2, 4 under seg2, 32, 64
-    by default; the sequential chain has none and gets seg5's poses.)"""
-    sl = {"seg5": 5, "seg2": 2, "default": 32}.get(path, 5)
+    by default; the sequential chain has none and gets seg5's poses.)  A graph of more than 64 separators also gets them at the separators
+    64 and 65 (the segments beside them run in the first lanes of the segment chain kernel's second wavefront), at the last separator
+    NS = (N - 2) / sl (the last row of what the separator kernel stages) and at the one before."""
+    lengths = {"seg5": 5, "seg2": 2, "default": 32}
+    sl = lengths.get(path, 5)
     want = [0, 3, sl, 2 * sl, 2 * sl + 1, sl + 2, N - 1]
+    NS = (N - 2) // sl
+    if path in lengths and NS > 64:
+        want += [64 * sl, 65 * sl, (NS - 1) * sl, NS * sl]
     return sorted({i for i in want if 0 <= i < N})
 
 

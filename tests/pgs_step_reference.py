@@ -177,8 +177,19 @@ def recover_step(p0, l0, p1, l1):
 # ----------------------------------------------------------------------------------------------------------------------------
 # host measurement streams
 # ----------------------------------------------------------------------------------------------------------------------------
+def sep_last_landmark(M, at_last, sep_only):
+    """Index of the landmark make_streams(sep_last=True) places at the last separator in an instance of M landmarks (None: the instance
+    has no landmark left for it: at_last and sep_only took them, or M is too small)."""
+    free = M - at_last
+    if free <= sep_only:
+        return None
+    taken = {(q * 7 + 3) % free for q in range(sep_only)}
+    j = (sep_only * 7 + 3) % free
+    return None if j in taken else j
+
+
 def make_streams(N, Ms, per_pose, seed, *, window=24, new_last=False, at_last=0, sep_only=0, SL=32, quiet=(), far_once=0,
-                 empty_every=0, radius=3.0):
+                 empty_every=0, radius=3.0, sep_last=False):
     """Host streams of a batch of len(Ms) graphs of N poses (N - 1 updates after init(0, 0, 0)) in which instance b creates exactly
     Ms[b] landmarks.  The truth drives a circle of `radius` round (0, radius) with the shared commands (0.1 m, 0.1 / radius rad); the maps
     lie near it, so |x| stays small against |delta|.  Landmark j of an instance is in view on the poses [s_j, s_j + window) (s_j spread
@@ -191,6 +202,9 @@ def make_streams(N, Ms, per_pose, seed, *, window=24, new_last=False, at_last=0,
       quiet:       (lo, hi) pose ranges without detections
       far_once:    that many landmarks are seen exactly once, 9 - 10 m away
       empty_every: poses t with t % empty_every == 0 have no detections
+      sep_last:    one more landmark (sep_last_landmark) is seen only from the LAST three separators, (NS - 2) SL, (NS - 1) SL and NS SL with
+                   NS = (N - 2) / SL: pose NS SL and row NS - 1 of whatever is staged per separator carry a landmark no interior pose sees.
+                   (Off, it draws nothing: every stream built without it keeps its bits.)
     Returns dict(cmds [N-1][2] f32, meas [B][N-1][K][3] f32, cnt [B][N-1] i32, sec [B][N-1][3], truth [N][3])."""
     rng = np.random.default_rng(seed)
     B, T = len(Ms), N - 1
@@ -224,7 +238,10 @@ def make_streams(N, Ms, per_pose, seed, *, window=24, new_last=False, at_last=0,
             j = (q * 7 + 3) % max(M - at_last, 1)
             s0 = seps[q % len(seps)]
             start[j], wlen[j], only_sep[j] = s0, 2 * SL + 1, True
-        for q in range(min(far_once, M)):                       # seen once, near the far end of the range
+        j = sep_last_landmark(M, at_last, sep_only) if sep_last else None
+        if j is not None and (N - 2) // SL >= 3:                # seen only from the last three separators
+            start[j], wlen[j], only_sep[j] = ((N - 2) // SL - 2) * SL, 2 * SL + 1, True
+        for q in range(min(far_once, M)):                      # seen once, near the far end of the range
             j = (q * 5 + 1) % M
             if only_sep[j] or start[j] == T:
                 continue

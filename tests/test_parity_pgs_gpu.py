@@ -469,14 +469,17 @@ def test_segmented_elimination_agrees_with_the_oracle(monkeypatch, oracle, L, T,
     elimination order.  (i) Against the oracle's SEQUENTIAL order: the usual bar, identical LM iteration / trial counts and 1e-7 m.
     (ii) Against the oracle restating the SAME order (LIN_SEG): 1e-9 m - what is left is the MFMA's fused accumulation and the
     reciprocal-square-root pivots.  Segment lengths 32 (default), 16 and 7, with and without the slot list; the pose counts around 33 / 34 /
-    66 put the last separator next to the end of the chain; the last size is BASELINE configs[4]."""
+    66 put the last separator next to the end of the chain; the last size is BASELINE configs[4], where 7 poses per segment are over the
+    separator capacity: that solve reports the sequential chain and is held to (i) alone."""
     import live_ekf_slam_amd as S
     lm, cmds = make_scenario(155 + L, L, T)
     cfg = default_config()
     r = oracle.run_pgs_batch(lm, cmds, B, L, KP=KP, seed=8, cfg=cfg, nthreads=8)
     for sl, lst in ((32, "1"), (16, "1"), (7, "0")):
-        if L == 200 and sl == 7:
-            continue   # 142 separators: beyond the separator kernel's staging (the host would fall back to the sequential chain)
+        # (L = 200 at 7 poses per segment: 142 separators, beyond the 128 the separator kernel stages - the plan kernel says so and the
+        # host takes the sequential chain, which must still be the oracle's solve)
+        over = (T + 1 - 2) // sl > 128
+        assert over == (L == 200 and sl == 7)
         monkeypatch.setenv("SLAM_PGS_SEG", str(sl))
         monkeypatch.setenv("SLAM_PGS_LIST", lst)
         monkeypatch.setenv("SLAM_PGS_SEG_BACK_GLOBAL", "1" if sl == 16 else "0")   # the pose step's chains from global memory / out of LDS
@@ -484,15 +487,95 @@ def test_segmented_elimination_agrees_with_the_oracle(monkeypatch, oracle, L, T,
         pg.set_map(lm); pg.set_seed(8); pg.init(0.0, 0.0, 0.0)
         pg.run_sim(cmds); pg.solvePoseGraph()
         paths = pg.last_solve_paths()
-        assert paths["segmented"] and paths["segment_length"] == sl, paths   # the path under test really ran
+        if over:
+            assert not paths["segmented"], paths
+        else:
+            assert paths["segmented"] and paths["segment_length"] == sl, paths   # the path under test really ran
         _compare(pg, r, B)
-        rs = oracle.run_pgs_batch(lm, cmds, B, L, KP=KP, seed=8, cfg=cfg, nthreads=8, lin_mode=oracle.LIN_SEG | (sl << 8))
+        if not over:   # (over the capacity the segmented order did not run: nothing to compare LIN_SEG with)
+            rs = oracle.run_pgs_batch(lm, cmds, B, L, KP=KP, seed=8, cfg=cfg, nthreads=8, lin_mode=oracle.LIN_SEG | (sl << 8))
+            assert np.array_equal(rs["iterations"], r["iterations"]) and np.array_equal(rs["trials"], r["trials"])
+            for b in range(B):
+                g1 = pg.get_graph(b, 1); M = r["M"][b]
+                assert np.abs(g1["poses"] - rs["pose_res"][b]).max() < 1e-9
+                assert np.abs(g1["landmarks"] - rs["lm_res"][b, :M]).max() < 1e-9
+        pg.close()
+
+
+@pytest.mark.parametrize("T,expect_sl", [(257, 2), (258, 2), (259, 0)])
+def test_whole_solves_at_and_over_the_separator_capacity(monkeypatch, oracle, T, expect_sl):
+    """Segments of 2 poses: N = 258 and 259 poses give 128 separators, the most the separator kernel stages (129 segments: the last lane of
+    pgs_seg_chain_kernel, alone in its wavefront; a last segment of one pose and of two), N = 260 gives 129 and the solve must take the
+    sequential chain and say so.  Either way the oracle's LM path to the usual bar; at the capacity also the oracle restating the same order
+    (LIN_SEG with 2-pose segments) to 1e-9 m."""
+    import live_ekf_slam_amd as S
+    L, KP, B = 8, 8, 3
+    assert (T + 1 - 2) // 2 == (128 if expect_sl else 129)
+    lm, cmds = make_scenario(155 + L, L, T)
+    cfg = default_config()
+    r = oracle.run_pgs_batch(lm, cmds, B, L, KP=KP, seed=8, cfg=cfg, nthreads=8)
+    monkeypatch.setenv("SLAM_PGS_SEG", "2")
+    pg = S.BatchedPoseGraph(B, num_iterations=T + 1, L_max=L, k_per_pose=KP).readParams(cfg)
+    pg.set_map(lm); pg.set_seed(8); pg.init(0.0, 0.0, 0.0)
+    pg.run_sim(cmds); pg.solvePoseGraph()
+    paths = pg.last_solve_paths()
+    assert paths["segmented"] == (expect_sl > 0) and (not expect_sl or paths["segment_length"] == expect_sl), paths
+    _compare(pg, r, B)
+    if expect_sl:
+        rs = oracle.run_pgs_batch(lm, cmds, B, L, KP=KP, seed=8, cfg=cfg, nthreads=8, lin_mode=oracle.LIN_SEG | (expect_sl << 8))
         assert np.array_equal(rs["iterations"], r["iterations"]) and np.array_equal(rs["trials"], r["trials"])
         for b in range(B):
             g1 = pg.get_graph(b, 1); M = r["M"][b]
             assert np.abs(g1["poses"] - rs["pose_res"][b]).max() < 1e-9
             assert np.abs(g1["landmarks"] - rs["lm_res"][b, :M]).max() < 1e-9
-        pg.close()
+    pg.close()
+
+
+def test_a_handle_that_grows_past_the_separator_capacity(monkeypatch, oracle):
+    """One handle of 262 poses' capacity with 2-pose segments, solved at N = 258, 259, 260 and 261 as its graphs grow (one simulator tick
+    between the solves): 128, 128, 129, 129 separators, so the solves run segmented, segmented, then the sequential chain twice - the plan
+    gives the segmented order up on a live handle, whose arrays are sized for 131 segments while at most 129 run.  Every solve against the
+    oracle's graph fed the same streams and solved at the same N, to the usual bar."""
+    import live_ekf_slam_amd as S
+    L, KP, B, N_max = 8, 8, 3, 262
+    T = N_max - 2
+    lm, cmds = make_scenario(155 + L, L, T)
+    cfg = default_config()
+    st = oracle.run_pgs_batch(lm, cmds, B, L, KP=KP, seed=8, cfg=cfg, nthreads=8, want_streams=True)     # the simulator's streams
+    assert st["cnt"].max() <= KP
+    gs = []
+    for b in range(B):
+        g = oracle.OraclePoseGraph(cfg, N_max=N_max, L_max=L, KP=KP); g.init(0.0, 0.0, 0.0); gs.append(g)
+    monkeypatch.setenv("SLAM_PGS_SEG", "2")
+    pg = S.BatchedPoseGraph(B, num_iterations=N_max, L_max=L, k_per_pose=KP).readParams(cfg)
+    pg.set_map(lm); pg.set_seed(8); pg.init(0.0, 0.0, 0.0)
+    ran = []
+    for t in range(T):
+        for b, g in enumerate(gs):
+            g.updateNaiveVehPoseEstimate(st["pose_init"][b, t + 1])
+            g.update(cmds[t, 0], cmds[t, 1], st["meas"][b, t, :st["cnt"][b, t]])
+        N = t + 2
+        if N < 258:
+            continue
+        pg.run_sim(cmds[pg.timestep:t + 1])
+        assert pg.timestep == N - 1
+        pg.solvePoseGraph()
+        paths = pg.last_solve_paths()
+        ran.append((N, paths["segment_length"] if paths["segmented"] else 0))
+        so = [g.solve() for g in gs]
+        v0, v1 = [g.values(0) for g in gs], [g.values(1) for g in gs]
+        r = {k: np.array([s[k] for s in so]) for k in ("iterations", "trials", "flags", "err_init", "err_final", "lam")}
+        r["M"] = np.array([v["M"] for v in v0])
+        r["ids"] = np.zeros((B, L), dtype=np.int32)
+        r["lm_res"] = np.zeros((B, L, 2))
+        for b in range(B):
+            r["ids"][b, :v0[b]["M"]] = v0[b]["ids"]
+            r["lm_res"][b, :v1[b]["M"]] = v1[b]["landmarks"]
+        r["pose_init"], r["pose_res"] = [v["poses"] for v in v0], [v["poses"] for v in v1]
+        assert all(v["poses"].shape[0] == N for v in v1)
+        _compare(pg, r, B)
+    pg.close()
+    assert ran == [(258, 2), (259, 2), (260, 0), (261, 0)], ran
 
 
 def test_segmented_elimination_falls_back_when_a_segment_sees_too_many_landmarks(monkeypatch, oracle):

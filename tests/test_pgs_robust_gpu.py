@@ -25,6 +25,9 @@ SMALL = ("n2", "n9", "n33", "n34")
 # launches - `fusable`, the step test's scenario for that kernel, is added so that the fused kernel does read weighted blocks)
 STEP_CASES = [(n, p) for n in SMALL for p in ("default", "seg5", "seg2", "chain")] + [("ragged", "default"), ("ragged", "chain_fused3_list1"),
                                                                                       ("fusable", "chain_fused3_list1")]
+# 128 separators, the most the separator kernel stages (the step test's sep258): the reweighted blocks - and, through test_pgs_fix_gpu.py, the
+# appended rows of fixes at separators, the last among them - in every row of what it reads from A
+STEP_CASES += [("sep258", "seg2")]
 SOLVE_CASES = [(n, p) for n in ("n33", "n34") for p in ("default", "seg5", "chain")]
 
 

@@ -11,7 +11,9 @@ its first trial (asserted), so its result is x0 (+) delta_dev, and per instance 
 
 eps_rec bounds the rounding of the retraction and of its inverse (pgs_step_reference.recover_step), eta_rec the same pushed through the
 norm of eta; the constant 8 is calibrated in test_pgs_step_reference.py.  The same solve twice gives bit-identical results.  The
-largest eta of each path, its bound and the largest kappa_1 are printed (pytest -s).  Every case asserts that the path it names really ran:
+largest eta of each case and of each path, its bound, the largest kappa_1 and the plan taken are printed (pytest -s).  The `sep{N}`
+scenarios put the segmented elimination at its separator-count edges (63 .. 129 separators, capacity 128), `lds1365` | `long` at the pose
+count up to which the pose step keeps its chains in LDS; their premises are asserted without a GPU in test_pgs_step_reference.py.  Every case asserts that the path it names really ran:
 the segment length the solve took (predicted from the factors with the plan kernel's rule, pgs_step_reference.predict_plan), and for the
 sequential chain whether the fused chain + SYRK launch or the separate SYRK launches formed the Schur complement."""
 import functools
@@ -44,8 +46,28 @@ SCENARIOS = {
 for _N, _kp in ((2, 8), (7, 8), (8, 8), (9, 8), (31, 1), (32, 8), (33, 33), (34, 32)):
     SCENARIOS[f"n{_N}"] = (_N, [0, 1, 7, 8, 17], max(8, -(-17 // max(_N - 1, 1))), _kp, 17, dict(window=6, at_last=1, sep_only=1, SL=5))
 
+# The separator-count edges of the segmented elimination (pgs_seg_impl.h; capacity kPgsSegMaxSep = 128 separators, NS = (N - 2) / SL):
+# NS = 63, 64, 65 put the last segment (nseg = NS + 1 of them, one lane each in pgs_seg_chain_kernel) in the last lane of wavefront 0 and the
+# first of wavefront 1, with NS % 4 = 3, 0, 1 for the separator kernel's batches of four; NS = 127, 128 reach the last rows of every array
+# staged per separator and lane 128, alone in wavefront 2, with a last segment of one pose (N = 258, 642) and of more; NS = 129 is over
+# the capacity: the solve must take the sequential chain.  Segments of 2 poses (an interior of one pose), of 5 (real chains in every lane)
+# and of 8 (the shortest the host's own search tries).  A landmark seen from the last three separators only (sep_last) wherever NS is 127 or
+# 128.  The instance without landmarks keeps the gradient-only column of the separator kernel in every case.
+SEP_EDGES = {}     # name -> (path, NS)
+for _N, _sl, _Ms in ([(n, 2, [0, 1, 17, 40]) for n in (128, 130, 132, 256, 258, 259, 260)] + [(n, 5, [0, 17, 64]) for n in (637, 642, 646, 647)]
+                     + [(1026, 8, [0, 17, 64]), (1034, 8, [17])]):
+    _ns = (_N - 2) // _sl
+    # (a landmark stays in view for 12 poses, for 24 / 32 in the longer chains, whose landmarks start 10 / 16 poses apart: the segments 64, 127
+    # and 128 of the largest instance must hold factors - test_pgs_step_reference.py asserts it)
+    SCENARIOS[f"sep{_N}"] = (_N, _Ms, 8, 8, max(_Ms), dict(window={2: 12, 5: 24, 8: 32}[_sl], at_last=1, sep_only=2, SL=_sl, sep_last=_ns in (127, 128)))
+    SEP_EDGES[f"sep{_N}"] = (f"seg{_sl}", _ns)
+FALLBACK = {n for n, (_, ns) in SEP_EDGES.items() if ns > 128}   # more separators than the capacity: the plan is the sequential chain
+# `long` with one pose fewer: N = 1365 = kSegBackLdsPoses, the most poses whose chains the LDS pose step holds (12 N doubles of dynamic LDS)
+SCENARIOS["lds1365"] = (1365, [0, 17, 64], 8, 8, 64, dict(window=60, at_last=1))
+
 SEG = {"default": {}, "seg16": {"SLAM_PGS_SEG": "16"}, "seg8": {"SLAM_PGS_SEG": "8"}, "seg5": {"SLAM_PGS_SEG": "5"},
-       "seg2": {"SLAM_PGS_SEG": "2"}, "back_global": {"SLAM_PGS_SEG_BACK_GLOBAL": "1"}, "chain": {"SLAM_PGS_SEG": "0"}}
+       "seg2": {"SLAM_PGS_SEG": "2"}, "back_global": {"SLAM_PGS_SEG_BACK_GLOBAL": "1"}, "chain": {"SLAM_PGS_SEG": "0"},
+       "seg5_back_global": {"SLAM_PGS_SEG": "5", "SLAM_PGS_SEG_BACK_GLOBAL": "1"}}
 for _f in ("0", "2", "3", "4"):
     for _l in ("0", "1"):
         SEG[f"chain_fused{_f}_list{_l}"] = {"SLAM_PGS_SEG": "0", "SLAM_PGS_FUSED": _f, "SLAM_PGS_LIST": _l}
@@ -60,6 +82,9 @@ CASES += [("ld512", "default"), ("ld512", "chain"), ("configs4", "default"), ("c
           ("ill", "default"), ("ill", "chain"), ("wide16", "default"), ("wide8", "default"), ("widechain", "default"),
           ("soak", "default"), ("soak", "chain_fused3_list1")]
 CASES += [(f"n{n}", p) for n in (2, 7, 8, 9, 31, 32, 33, 34) for p in ("default", "seg5", "seg2", "chain")]
+# 128 separators with the pose step's chains read from global memory (s_ds[129] of pgs_seg_backsolve_kernel), and the LDS pose step at its
+# largest N against the global one
+CASES += [(n, p) for n, (p, _) in SEP_EDGES.items()] + [("sep642", "seg5_back_global"), ("lds1365", "default"), ("lds1365", "back_global")]
 # the plan each wide-sensor graph makes the default solve take: segment length (0 = the sequential chain)
 EXPECT_SL = {"wide16": 16, "wide8": 8, "widechain": 0}
 # graphs whose largest M the instance-resident SYRK holds (M <= 207): SYRK_INST_SWITCH=0 runs that kernel on them; on `ragged` (M up to 223)
@@ -67,6 +92,7 @@ EXPECT_SL = {"wide16": 16, "wide8": 8, "widechain": 0}
 INST_SYRK_OK = {"fusable", "ragged207"}
 
 REPORT = {}
+BITS = {}      # (scenario, path) -> the bytes of every instance's result (test_the_pose_count_boundary_of_the_lds_pose_step)
 
 
 @functools.lru_cache(maxsize=None)
@@ -92,7 +118,7 @@ def scenario(name):
         S = R.system_of(g, v["poses"], v["landmarks"], LAM0)
         d_ref, kappa, _ = R.reference_step(S)
         refs.append((v, S, d_ref, kappa, R.factor_pairs(g, v["poses"], v["landmarks"])))
-    return dict(st=st, N=N, KP=KP, L_max=L_max, cfg=cfg, refs=refs)
+    return dict(st=st, N=N, KP=KP, L_max=L_max, cfg=cfg, refs=refs, graphs=gs)
 
 
 def expected_plan(sc, name, path):
@@ -136,6 +162,7 @@ def test_one_lm_step_against_the_extended_precision_reference(monkeypatch, name,
     plan = pg.last_solve_paths()
     pg.close()
     (res, st), (res2, st2) = runs
+    BITS[(name, path)] = b"".join(res[b][key].tobytes() for b in range(B) for key in ("poses", "landmarks"))
     for b in range(B):   # determinism: the same solve twice, bit for bit
         assert np.array_equal(res[b]["poses"], res2[b]["poses"]) and np.array_equal(res[b]["landmarks"], res2[b]["landmarks"]), (path, name, b)
     assert np.array_equal(st["trials"], st2["trials"]) and np.array_equal(st["iterations"], st2["iterations"])
@@ -148,12 +175,15 @@ def test_one_lm_step_against_the_extended_precision_reference(monkeypatch, name,
     # the path the case names really ran: the segment length (a forced length that re-planned would duplicate another case), the chain's
     # launch shape (the solve's SYRK FLOP by path: separate SYRK launches / fused chain + SYRK)
     want = EXPECT_SL[name] if name in EXPECT_SL else expected_plan(sc, name, path)
-    if name not in EXPECT_SL and "SLAM_PGS_SEG" in SEG[path] and SEG[path]["SLAM_PGS_SEG"] != "0":
+    if name in FALLBACK:   # over the separator capacity: the plan kernel says so and the host takes the sequential chain
+        assert want == 0 and not plan["segmented"], (path, name, plan, want)
+    elif name not in EXPECT_SL and "SLAM_PGS_SEG" in SEG[path] and SEG[path]["SLAM_PGS_SEG"] != "0":
         assert want == int(SEG[path]["SLAM_PGS_SEG"]), f"{name}: SLAM_PGS_SEG={SEG[path]['SLAM_PGS_SEG']} would re-plan to {want}"
     if name not in EXPECT_SL and path in ("default", "back_global"):
         assert want == 32, f"{name}: the default solve would re-plan to {want}"
     got = plan["segment_length"] if plan["segmented"] else 0
     assert got == want, (path, name, plan, want)
+    asked = int(SEG[path].get("SLAM_PGS_SEG", "32"))   # the length the search for the plan starts from (0: the chain was asked for)
     fused = SEG[path].get("SLAM_PGS_FUSED")
     if fused in ("2", "3", "4"):
         assert plan["flop_fused"] > 0 and plan["flop_separate"] == 0, (path, name, plan)
@@ -162,7 +192,7 @@ def test_one_lm_step_against_the_extended_precision_reference(monkeypatch, name,
     if path.startswith("chain_syrk_switch"):
         assert (name in INST_SYRK_OK) == (max(r[0]["M"] for r in sc["refs"]) <= 207), name
     worst = REPORT.setdefault(path, [0.0, 0.0, 0.0, ""])
-    fails = []
+    fails, case_eta = [], (0.0, 0.0)
     for b, (v, S, d_ref, kappa, _) in enumerate(sc["refs"]):
         delta, eps = R.recover_step(v["poses"], v["landmarks"], res[b]["poses"], res[b]["landmarks"])
         eta = S.eta(delta)
@@ -171,15 +201,47 @@ def test_one_lm_step_against_the_extended_precision_reference(monkeypatch, name,
         fwd = float(np.abs(delta - dref).max(initial=0.0))
         fbound = R.BOUND_C * S.n * R.U * kappa * float(np.abs(dref).max(initial=0.0)) + float(eps.max(initial=0.0))
         N, M = v["poses"].shape[0], v["M"]
+        if eta >= case_eta[0]:
+            case_eta = (eta, bound)
         if eta > worst[0]:
             worst[0], worst[1], worst[3] = eta, bound, f"{name} instance {b}"
         worst[2] = max(worst[2], kappa)
         if not (eta <= bound and fwd <= fbound):
             fails.append(f"path {path} / {name}: instance {b} (N {N}, M {M}, n {S.n}): eta {eta:.3g} vs bound {bound:.3g}; "
                          f"|d_dev - d_ref| {fwd:.3g} vs {fbound:.3g}; kappa_1 {kappa:.3g}")
-    print(f"\n{path:28s} {name:10s} largest eta so far {worst[0]:.3g} (bound {worst[1]:.3g}, {worst[3]}), largest kappa_1 {worst[2]:.3g}, "
-          f"plan {'seg ' + str(plan['segment_length']) if plan['segmented'] else 'chain'}")
+    print(f"\n{path:28s} {name:10s} largest eta {case_eta[0]:.3g} (bound {case_eta[1]:.3g}); on this path so far {worst[0]:.3g} (bound {worst[1]:.3g}, {worst[3]}), largest kappa_1 {worst[2]:.3g}, "
+          f"plan {'seg ' + str(plan['segment_length']) if plan['segmented'] else 'chain'}"
+          + (f", NS {(sc['N'] - 2) // asked} at {asked} poses per segment" if asked else ""))
     assert not fails, f"{len(fails)} instance(s) off the reference: " + "; ".join(fails[:8])
+
+
+def _result_bits(monkeypatch, name, path):
+    """The bytes of every instance's result of one solve of `path` on scenario `name` (from the case above when it ran in this process)."""
+    if (name, path) not in BITS:
+        sc = scenario(name)
+        monkeypatch.setenv("SLAM_PGS_MAX_TRIALS", "1")
+        for k, v in SEG[path].items():
+            monkeypatch.setenv(k, v)
+        pg = _device(sc)
+        pg.solvePoseGraph()
+        BITS[(name, path)] = b"".join(pg.get_graph(b, 1)[key].tobytes() for b in range(len(sc["refs"])) for key in ("poses", "landmarks"))
+        pg.close()
+        for k in SEG[path]:
+            monkeypatch.delenv(k)
+    return BITS[(name, path)]
+
+
+@pytest.mark.gpu
+def test_the_pose_count_boundary_of_the_lds_pose_step(monkeypatch):
+    """The pose step of the segmented elimination keeps its chains in LDS up to N = 1365 poses (kSegBackLdsPoses) unless
+    SLAM_PGS_SEG_BACK_GLOBAL = 1 asks for the kernel that reads them from global memory.  At N = 1366 (`long`) both settings run that same
+    kernel: their results are equal byte for byte.  At N = 1365 (`lds1365`) the two kernels run, each held to the bounds by the cases above;
+    the LDS kernel associates differently by design, so whether their bits differ is printed, not asserted."""
+    assert SCENARIOS["long"][0] == 1366 and SCENARIOS["lds1365"][0] == 1365
+    assert _result_bits(monkeypatch, "long", "default") == _result_bits(monkeypatch, "long", "back_global"), \
+        "N = 1366: SLAM_PGS_SEG_BACK_GLOBAL changed a result (the LDS pose step ran beyond its pose count?)"
+    same = _result_bits(monkeypatch, "lds1365", "default") == _result_bits(monkeypatch, "lds1365", "back_global")
+    print(f"\nN = 1365: the LDS pose step and the global one give {'the same' if same else 'different'} bits")
 
 
 def test_the_ill_conditioned_scenario_is_ill_conditioned():

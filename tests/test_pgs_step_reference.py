@@ -162,6 +162,71 @@ def test_recovering_the_step_from_the_retraction(oracle, medium):
         assert np.all(np.abs(delta - R.pack(dp, dl)) <= eps), (b, np.max(np.abs(delta - R.pack(dp, dl)) - eps))
 
 
+# The separator and pose-count edges of tests/test_pgs_step_gpu.py, written out: scenario -> (solve paths, N, segment length the search starts
+# from, NS = (N - 2) / SL, the plan the solve must take: that length, or 0 = the sequential chain beyond 128 separators)
+EDGE_TABLE = {"sep128": (("seg2",), 128, 2, 63, 2), "sep130": (("seg2",), 130, 2, 64, 2), "sep132": (("seg2",), 132, 2, 65, 2),
+              "sep256": (("seg2",), 256, 2, 127, 2), "sep258": (("seg2",), 258, 2, 128, 2), "sep259": (("seg2",), 259, 2, 128, 2),
+              "sep260": (("seg2",), 260, 2, 129, 0),
+              "sep637": (("seg5",), 637, 5, 127, 5), "sep642": (("seg5", "seg5_back_global"), 642, 5, 128, 5), "sep646": (("seg5",), 646, 5, 128, 5),
+              "sep647": (("seg5",), 647, 5, 129, 0),
+              "sep1026": (("seg8",), 1026, 8, 128, 8), "sep1034": (("seg8",), 1034, 8, 129, 0),
+              "lds1365": (("default", "back_global"), 1365, 32, 42, 32)}
+
+
+def test_the_edge_table_is_the_gpu_tests_table():
+    import test_pgs_step_gpu as T
+    assert set(T.SEP_EDGES) | {"lds1365"} == set(EDGE_TABLE)
+    want = {(n, p) for n, row in EDGE_TABLE.items() for p in row[0]}
+    assert want <= set(T.CASES) and not {c for c in T.CASES if c[0] in EDGE_TABLE} - want
+    assert T.FALLBACK == {n for n, row in EDGE_TABLE.items() if row[4] == 0}
+    for name, (paths, N, SL, NS, _) in EDGE_TABLE.items():
+        assert T.SCENARIOS[name][0] == N and (N - 2) // SL == NS, name
+        for p in paths:
+            assert int(T.SEG[p].get("SLAM_PGS_SEG", "32")) == SL, (name, p)
+        if name in T.SEP_EDGES:
+            assert T.SEP_EDGES[name] == (paths[0], NS) and T.SCENARIOS[name][5]["SL"] == SL, name
+            assert T.SCENARIOS[name][5]["sep_last"] == (NS in (127, 128)), name
+    # every count the edges are about: the lanes 63 | 64 of pgs_seg_chain_kernel (nseg = NS + 1), lane 128, the capacity and one beyond
+    assert {row[3] for row in EDGE_TABLE.values()} >= {63, 64, 65, 127, 128, 129}
+    assert {row[3] % 4 for n, row in EDGE_TABLE.items() if row[3] in (63, 64, 65)} == {3, 0, 1}
+
+
+@pytest.mark.parametrize("name", list(EDGE_TABLE))
+def test_premises_of_the_separator_and_pose_count_edges(oracle, name):
+    """What test_pgs_step_gpu.py's cases at the separator capacity rest on, without a GPU: the plan (the forced length, the chain beyond 128
+    separators), the landmark counts, a first trial the dense reference LM accepts, the landmark at the last separator, and factors in the
+    segments whose lanes the cases are about."""
+    import pgs_robust_reference as RR
+    import test_pgs_step_gpu as T
+    paths, N, SL, NS, plan = EDGE_TABLE[name]
+    nseg = NS + 1
+    sc = T.scenario(name)
+    Ms = T.SCENARIOS[name][1]
+    assert sc["N"] == N and len(sc["refs"]) == len(Ms)
+    for p in paths:
+        assert T.expected_plan(sc, name, p) == plan, (name, p)
+    opt = T.SCENARIOS[name][5]
+    with_last = 0
+    for b, (g, (v, _, _, _, (pose, lm))) in enumerate(zip(sc["graphs"], sc["refs"])):
+        assert v["M"] == Ms[b] and v["poses"].shape[0] == N, (name, b)
+        first = RR.lm_solve(g, RR.NONE, 0.0, max_trials=1)
+        assert (first["iterations"], first["trials"]) == (1, 1), (name, b, first["margin"])
+        seg = np.minimum(np.where(pose == 0, 0, (pose - 1) // SL), NS)          # the segment of an interior pose (predict_plan's rule)
+        interior = (pose % SL != 0) | (pose == 0) | (pose > NS * SL)
+        assert seg.max(initial=0) < nseg
+        j = R.sep_last_landmark(Ms[b], opt.get("at_last", 0), opt.get("sep_only", 0)) if opt.get("sep_last") else None
+        if j is not None:     # the landmark of the last separator: factors at the last three separators and nowhere else
+            k = int(np.flatnonzero(v["ids"] == 100 + j)[0])
+            assert sorted(pose[lm == k].tolist()) == [(NS - 2) * SL, (NS - 1) * SL, NS * SL], (name, b, pose[lm == k])
+            assert not interior[lm == k].any()
+            with_last += 1
+        if NS == 128 and Ms[b] == max(Ms):   # its segments 64 (first lane of wavefront 1), 127 and 128 (alone in wavefront 2) hold factors
+            held = set(np.unique(seg[interior]).tolist())
+            assert {64, 127, 128} <= held, (name, b, sorted({64, 127, 128} - held))
+    if opt.get("sep_last"):
+        assert NS in (127, 128) and with_last >= 2, (name, with_last)
+
+
 def test_streams_hold_what_they_promise(oracle, medium):
     """M exactly as asked, messages longer than the 8 factor slots, poses without detections, and - from the detections those messages
     drop while their landmarks are still created - landmarks whose first FACTOR comes after that of a landmark numbered after them (the
