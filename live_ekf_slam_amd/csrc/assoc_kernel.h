@@ -34,7 +34,7 @@
 // Per detection slot: verdict, slot (best j or -1), det[4] = (d2_best, d2_second, nu_r, nu_b of the best), NaN where undefined.
 // Record (kInnovRecLen doubles): 0 evaluated, 1 FROZEN, 2 TOO_LONG, 3 detections in, 4 matched, 5 new, 6 ambiguous, 7 sum of d2_best over
 // the matched (ascending l), 8 max of d2_best over the matched (0 over none), 9 conflict, 10 no room, 11 invalid, 12 - 15 reserved, 0.
-// Entry 8 is a maximum and every other a sum: what rec_join of launch_innovation_reduce does, so the record goes through it unchanged.
+// Entry 8 is a maximum and every other a sum (kAssocRecMax).
 #pragma once
 #include "innovation_kernel.h"
 
@@ -49,7 +49,7 @@ enum AssocRec {
     kAscEval = 0, kAscFrozen = 1, kAscTooLong = 2, kAscDetIn = 3, kAscMatched = 4, kAscNew = 5, kAscAmbiguous = 6, kAscSumD2 = 7,
     kAscMaxD2 = 8, kAscConflict = 9, kAscNoRoom = 10, kAscInvalid = 11
 };
-static_assert((int)kAscMaxD2 == (int)kInnMaxNis, "the entry launch_innovation_reduce joins by max");
+constexpr unsigned kAssocRecMax = 1u << kAscMaxD2;   // the entries joined by a maximum (record_kernel.h)
 
 // what one instance holds between its phases: LDS on the device (one per wavefront), plain memory on the host.  The per-detection
 // arrays are separate (not a struct per detection): lane l reads element l, consecutive banks.
@@ -356,7 +356,7 @@ struct AssocParams {
     double* det;                // [B][kInnovMaxDet][kAssocDetLen] or NULL
     int32_t* n_lm;              // [B] landmarks the instance compared with (-1: it emitted an empty message), or NULL
     double* inst_rec;           // [B][kInnovRecLen]
-    double* partials;           // [innovation_blocks(B)][kInnovRecLen]
+    double* partials;           // [record_blocks(B)][kInnovRecLen]
     double* rec;                // [kInnovRecLen]
 };
 hipError_t launch_associate(const AssocParams& p, int f32_storage, hipStream_t stream);

@@ -277,7 +277,7 @@ int slam_fix_instance_host(double* x, double* P, int M, int L_max, int32_t statu
     // the instance's slab as the handle holds it: rows at the padded leading dimension, elements of the storage type
     auto run = [&](auto zero) {
         using ST = decltype(zero);
-        const int ld = slam::map_ld(n, (int)sizeof(ST));
+        const int ld = slam::ekf_ld(n, (int)sizeof(ST));
         std::vector<ST> Ps((size_t)n * ld, (ST)0), xs((size_t)n);
         for (int r = 0; r < n; ++r)
             for (int cc = 0; cc < n; ++cc) Ps[(size_t)r * ld + cc] = (ST)P[(size_t)r * n + cc];

@@ -36,7 +36,7 @@ int innovation_supported(const slam_handle* h) {
 int innovation_reserve(slam_handle* h, bool det) {
     const size_t B = (size_t)h->B;
     TRY(grow(h, h->inn.dval, (1 + 12 + slam::kInnovRecLen) * B));
-    TRY(grow(h, h->inn.dpart, (size_t)slam::innovation_blocks(h->B) * slam::kInnovRecLen));
+    TRY(grow(h, h->inn.dpart, (size_t)slam::record_blocks(h->B) * slam::kInnovRecLen));
     if (det) TRY(grow(h, h->inn.ddet, B * slam::kInnovMaxDet * slam::kInnovDetLen));
     return SLAM_OK;
 }

@@ -314,7 +314,7 @@ int slam_map_instance_host(double* x, double* P, int32_t* ids, int M, int L_max,
     auto run = [&](auto zero) {
         using T = decltype(zero);
         using F = typename std::conditional<sizeof(T) == 4, float, double>::type;
-        const int ld = slam::map_ld(n, (int)sizeof(T));
+        const int ld = slam::ekf_ld(n, (int)sizeof(T));
         std::vector<T> Ps((size_t)n * ld, 0), xs((size_t)n);
         auto bits = [](double v) { const F f = (F)v; T t; memcpy(&t, &f, sizeof(T)); return t; };
         auto value = [](T t) { F f; memcpy(&f, &t, sizeof(T)); return (double)f; };
@@ -323,7 +323,7 @@ int slam_map_instance_host(double* x, double* P, int32_t* ids, int M, int L_max,
         for (int i = 0; i < n; ++i) xs[i] = bits(x[i]);
         Mk = slam::map_remove_instance_host(Ps.data(), xs.data(), ids, seen, expected, mask.data(), M, L_max, kept.data());
         if (Mk == M) return;
-        const int n2 = 3 + 2 * Mk, ld2 = slam::map_ld(n2, (int)sizeof(T));
+        const int n2 = 3 + 2 * Mk, ld2 = slam::ekf_ld(n2, (int)sizeof(T));
         for (int r = 0; r < n2; ++r)
             for (int cc = 0; cc < n2; ++cc) P[(size_t)r * n2 + cc] = value(Ps[(size_t)r * ld2 + cc]);
         for (int i = 0; i < n2; ++i) x[i] = value(xs[i]);

@@ -302,7 +302,7 @@ int slam_merge_instance_host(double* x, double* P, int32_t* ids, int M, int L_ma
     auto run = [&](auto zero) {
         using ST = decltype(zero);
         using T = typename std::conditional<sizeof(ST) == 4, uint32_t, uint64_t>::type;
-        const int ld = slam::map_ld(n, (int)sizeof(ST));
+        const int ld = slam::ekf_ld(n, (int)sizeof(ST));
         std::vector<ST> Ps((size_t)n * ld, (ST)0), xs((size_t)n);
         for (int r = 0; r < n; ++r)
             for (int cc = 0; cc < n; ++cc) Ps[(size_t)r * ld + cc] = (ST)P[(size_t)r * n + cc];
@@ -333,7 +333,7 @@ int slam_merge_instance_host(double* x, double* P, int32_t* ids, int M, int L_ma
         memcpy(Pi.data(), Ps.data(), sizeof(T) * Ps.size()); memcpy(xi.data(), xs.data(), sizeof(T) * xs.size());
         Mk = slam::map_remove_instance_host(Pi.data(), xi.data(), ids, seen, expected, mask.data(), M, L_max, kept.data());
         memcpy(Ps.data(), Pi.data(), sizeof(T) * Ps.size()); memcpy(xs.data(), xi.data(), sizeof(T) * xs.size());
-        const int n2 = 3 + 2 * Mk, ld2 = slam::map_ld(n2, (int)sizeof(ST));
+        const int n2 = 3 + 2 * Mk, ld2 = slam::ekf_ld(n2, (int)sizeof(ST));
         for (int r = 0; r < n2; ++r)
             for (int cc = 0; cc < n2; ++cc) P[(size_t)r * n2 + cc] = (double)Ps[(size_t)r * ld2 + cc];
         for (int i = 0; i < n2; ++i) x[i] = (double)xs[i];

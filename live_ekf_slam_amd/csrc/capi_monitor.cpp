@@ -74,7 +74,7 @@ int slam_monitor_now(slam_handle* h, const slam_monitor_config* cfg, double rec[
     if (!has_map(h)) return slam_internal_fail(SLAM_ERR_STATE, "no true map, so no simulated truth to compare with: call slam_set_map (or slam_set_maps) first");
     HIP_TRY(hipSetDevice(h->device));
     const size_t B = (size_t)h->B;
-    TRY(grow(h, h->mon.dpart, (size_t)slam::monitor_blocks(h->B) * slam::kMonRecLen));
+    TRY(grow(h, h->mon.dpart, (size_t)slam::record_blocks(h->B) * slam::kMonRecLen));
     TRY(grow(h, h->mon.drec, slam::kMonRecLen));
     TRY(grow(h, h->mon.dlog, 3 * B));
     TRY(grow(h, h->mon.dflags, B));
@@ -110,7 +110,7 @@ int slam_monitor_run(slam_handle* h, const slam_monitor_config* cfg, int source,
     TRY(tcmd.init(h, source == SLAM_MONITOR_EACH ? TickCmds::kEach : source == SLAM_MONITOR_NAV ? TickCmds::kNav : TickCmds::kShared, cmds));
     // what a tick holds on the device: its rows of the series and, for EACH, of the commands
     const int chunk = slam_host::ticks_per_chunk(T, 8.0 * (double)ns * (double)B + tcmd.bytes_per_tick(h), slam_host::tick_log_budget());
-    TRY(grow(h, h->mon.dpart, (size_t)slam::monitor_blocks(h->B) * slam::kMonRecLen));
+    TRY(grow(h, h->mon.dpart, (size_t)slam::record_blocks(h->B) * slam::kMonRecLen));
     TRY(grow(h, h->mon.drec, (size_t)chunk * slam::kMonRecLen));
     if (ns) TRY(grow(h, h->mon.dlog, (size_t)ns * chunk * B));
     slam::MonitorParams p = monitor_params(h, c);

@@ -31,7 +31,7 @@ int sense_reserve(slam_handle* h) {
     TRY(grow(h, h->sense.dnext, 3 * B));
     TRY(grow(h, h->sense.dstaged, B));
     TRY(grow(h, h->sense.dinst, B * slam::kSenseRecLen));
-    TRY(grow(h, h->sense.dpart, (size_t)slam::innovation_blocks(h->B) * slam::kSenseRecLen));
+    TRY(grow(h, h->sense.dpart, (size_t)slam::record_blocks(h->B) * slam::kSenseRecLen));
     TRY(grow(h, h->sense.drec, slam::kSenseRecLen));
     return SLAM_OK;
 }

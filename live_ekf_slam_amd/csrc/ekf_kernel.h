@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "noise_row.h"
+#include "slam_math.h"   // ekf_ld
 
 namespace slam {
 
@@ -78,14 +79,6 @@ struct EkfStepParams {
                   // multi-step launch; 1 / 2 / 16 (ablations, WRONG results) only in a -DSLAM_ABLATE build; 128 / 1024: tests only
                   // (slam_set_debug_flags: lose an `applied` update / every update of the decoupled loop in the deferred order)
 };
-
-// Leading dimension (in elements) of the row-major covariance of an instance with state size n: every row starts on a
-// 16-byte boundary (2 doubles / 4 floats), so one lane's 16-byte vector never straddles two rows and the bulk stream
-// can hand a lane the same column group in several consecutive rows (its (H P) operands are then read once per strip
-// instead of once per element).  The pad elements (columns n .. ld-1) are kept at zero.
-__host__ __device__ constexpr int ekf_ld(int n, int elem_bytes) {
-    return elem_bytes == 8 ? ((n + 1) & ~1) : ((n + 3) & ~3);
-}
 
 static constexpr int kEkfProfSlots = 128;   // per-block slots of EkfStepParams::prof
 static constexpr int kEkfTrafficSlot = 10;  // khist[10..13]: bytes moved by the P-stream passes (read + write), other global bytes

@@ -75,6 +75,7 @@ enum FixRec {
     kFixYawPresent = 6, kFixYawApplied = 7, kFixYawRejected = 8, kFixYawSingular = 9, kFixYawInvalid = 10, kFixSumNisPos = 11,
     kFixSumNisYaw = 12, kFixSkipped = 13
 };
+constexpr unsigned kFixRecMax = 0u;                 // no entry is joined by a maximum (record_kernel.h): every one is a sum
 enum FixVerdict { kFixAbsent = 0, kFixApplied = 1, kFixRejected = 2, kFixSingular = 3, kFixInvalid = 4 };
 constexpr int kFixRowLen = 5;                       // doubles of one fix row
 constexpr uint32_t kFixPair = 0x50000000u;          // G: the first pair index of the source's draws
@@ -125,14 +126,14 @@ struct FixResult { int32_t verdict; double nis[2]; int written; };
 
 SLAM_HD double fix_nis_out(int verdict, double nis) { return (verdict == kFixApplied || verdict == kFixRejected) ? nis : __builtin_nan(""); }
 
-// One instance that is not skipped, in place.  ST: float or double, P at the leading dimension map_ld(n), x [n]; row [5], gates [2]
+// One instance that is not skipped, in place.  ST: float or double, P at the leading dimension ekf_ld(n), x [n]; row [5], gates [2]
 // (position, heading); ws: fix_ws_len(n) doubles (LDS on the device).  W: an execution policy of map_kernel.h (MapSeq on the host, the
 // workgroup on the device).  ONE_PASS: every element of P and x is visited once, whatever the parts (the device); otherwise the two parts
 // are two passes, each on the state the previous one left (the host hook: the definition).  The two give the same bits; the argument and
 // the barriers are at the top of this file.  Every lane of the policy calls it with the same arguments and gets the same result.
 template <bool ONE_PASS, class W, class ST>
 SLAM_HD FixResult fix_instance(const W& w, ST* P, ST* x, int M, const double* row, int kinds, const double* gates, double* ws) {
-    const int n = 3 + 2 * M, ld = map_ld(n, (int)sizeof(ST));
+    const int n = 3 + 2 * M, ld = ekf_ld(n, (int)sizeof(ST));
     const int total = n * ld;                        // (<= 2003 * 2004: int)
     double* const cr = ws;                           // c_r of the position part, pairs
     double* const gc = ws + 2 * n;                   // g_c of the position part, pairs
@@ -372,7 +373,7 @@ struct FixParams {
     int32_t* verdict;                 // [B]
     double* nis;                      // [B][2]
     double* inst_rec;                 // [B][kFixRecLen]
-    double* partials;                 // [innovation_blocks(B)][kFixRecLen]
+    double* partials;                 // [record_blocks(B)][kFixRecLen]
     double* rec;                      // [kFixRecLen], or NULL: no record, and inst_rec / partials are not used
     int32_t B, L_max, pstride, xstride;
 };

@@ -10,23 +10,22 @@
 //   An instance without an applied part leaves after the barrier without a store; one whose parts are absent or invalid by the fix row
 //   alone, or whose status skips it, never reads P.  Index arithmetic inside an instance is int; b * pstride is formed in size_t.
 // fix_sense_kernel: one lane per instance, fix_sense_instance.
-// fix_work_kernel: the traffic model summed in integers, outside any timed part (merge_work_kernel's shape).
+// FixWorkTerms: the traffic model, summed in integers by launch_work_sum outside any timed part.
+// Record: launch_record_reduce (record_kernel.h) with the join mask kFixRecMax, every entry a sum.
 #include <hip/hip_runtime.h>
 
 #include "../../include/slam_batch.h"
-#include "ekf_kernel.h"
+#include "aux_device.h"
 #include "fix_kernel.h"
 #include "lds_attr.h"
-#include "sense_kernel.h"
 
 namespace slam {
 namespace {
 
-static_assert(kFixRecLen == kSenseRecLen, "the record goes through launch_record_sum");
+static_assert(kFixRecLen == kRecLen, "the record launch_record_reduce takes");
 static_assert((int)kFixApplied == (int)SLAM_FIX_APPLIED && (int)kFixRejected == (int)SLAM_FIX_REJECTED &&
               (int)kFixSingular == (int)SLAM_FIX_SINGULAR && (int)kFixInvalid == (int)SLAM_FIX_INVALID, "the verdicts are slam_fix_verdict");
 static_assert(sizeof(slam_fix_sensor) == 80, "nine doubles, one int32 and its padding");
-static_assert(map_ld(103, 8) == ekf_ld(103, 8) && map_ld(103, 4) == ekf_ld(103, 4) && map_ld(2003, 4) == ekf_ld(2003, 4), "one leading dimension");
 
 constexpr int kFixThreads = 256;                    // one instance's workgroup
 
@@ -41,15 +40,12 @@ __global__ __launch_bounds__(kFixThreads) void fix_instance_kernel(const FixPara
     extern __shared__ double s_ws[];                 // fix_ws_len(3 + 2 L_max) doubles
     const int b = blockIdx.x;                        // (the grid is exactly B workgroups)
     const int tid = threadIdx.x;
-    int M = p.M[b];
-    M = M < 0 ? 0 : (M > p.L_max ? p.L_max : M);
+    const int M = aux_clamp_m(p.M[b], p.L_max);
     const bool skip = (p.status[b] & kMapStatusSkip) != 0;   // (the whole workgroup: no barrier is passed by a part of it)
     const double gates[2] = {p.gate_pos, p.gate_yaw};
     FixResult o = {0, {__builtin_nan(""), __builtin_nan("")}, 0};
     if (!skip) {
-        ST* const Pb = static_cast<ST*>(p.P) + (size_t)b * p.pstride;
-        ST* const xb = static_cast<ST*>(p.x) + (size_t)b * p.xstride;
-        o = fix_instance<true>(FixGroup(), Pb, xb, M, p.fix + (size_t)b * kFixRowLen, p.kinds[b], gates, s_ws);
+        o = fix_instance<true>(FixGroup(), aux_row<ST>(p.P, b, p.pstride), aux_row<ST>(p.x, b, p.xstride), M, p.fix + (size_t)b * kFixRowLen, p.kinds[b], gates, s_ws);
     }
     if (tid == 0) {
         p.verdict[b] = o.verdict;
@@ -75,26 +71,21 @@ __global__ __launch_bounds__(256) void fix_sense_kernel(const FixSenseParams p) 
     if (p.jumped) p.jumped[b] = o.jumped;
 }
 
-__global__ __launch_bounds__(256) void fix_work_kernel(const int32_t* __restrict__ M, const int32_t* __restrict__ verdict, size_t n, int L_max,
-                                                       unsigned long long* __restrict__ work) {
-    unsigned long long a0 = 0, a1 = 0;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        int m = M[i];
-        m = m < 0 ? 0 : (m > L_max ? L_max : m);
-        const FixTraffic t = fix_traffic(m, verdict[i]);
-        a0 += t.elems; a1 += t.other_bytes;
+// element i of the traffic model's sum: one instance of one call
+struct FixWorkTerms {
+    const int32_t *M, *verdict;
+    int L_max;
+    __device__ void operator()(size_t i, unsigned long long (&t)[2]) const {
+        const FixTraffic w = fix_traffic(aux_clamp_m(M[i], L_max), verdict[i]);
+        t[0] = w.elems; t[1] = w.other_bytes;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { a0 += __shfl_down(a0, off, 64); a1 += __shfl_down(a1, off, 64); }
-    if (threadIdx.x % 64 == 0) { atomicAdd(work, a0); atomicAdd(work + 1, a1); }
-}
+};
 
 }  // namespace
 
 hipError_t launch_fix(const FixParams& p, int f32_storage, hipStream_t stream) {
     const int n_max = 3 + 2 * p.L_max;
-    if (p.B <= 0 || p.L_max <= 0 || p.L_max > kMapMaxLandmarks || p.xstride < n_max ||
-        (long long)p.pstride < (long long)n_max * ekf_ld(n_max, f32_storage ? 4 : 8) || !p.P || !p.x || !p.M || !p.status || !p.fix || !p.kinds ||
+    if (!aux_shape_ok(p.B, p.L_max, p.xstride, p.pstride, f32_storage) || p.L_max <= 0 || p.L_max > kMapMaxLandmarks || !p.P || !p.x || !p.M || !p.status || !p.fix || !p.kinds ||
         !p.verdict || !p.nis || (p.rec && (!p.inst_rec || !p.partials)) ||
         reinterpret_cast<uintptr_t>(p.P) % 16 != 0 || ((size_t)p.pstride * (f32_storage ? 4 : 8)) % 16 != 0)   // (the 16-byte accesses of a row)
         return hipErrorInvalidValue;
@@ -104,12 +95,9 @@ hipError_t launch_fix(const FixParams& p, int f32_storage, hipStream_t stream) {
         const hipError_t e = slam_allow_full_lds(fn);
         if (e != hipSuccess) return e;
     }
-    (void)hipGetLastError();   // sticky and per thread: only these launches' errors are reported (capi_internal.h)
-    if (f32_storage) hipLaunchKernelGGL(fix_instance_kernel<float>, dim3(p.B), dim3(kFixThreads), lds, stream, p);
-    else hipLaunchKernelGGL(fix_instance_kernel<double>, dim3(p.B), dim3(kFixThreads), lds, stream, p);
-    const hipError_t e = hipGetLastError();
+    const hipError_t e = aux_launch(f32_storage, fix_instance_kernel<float>, fix_instance_kernel<double>, dim3(p.B), dim3(kFixThreads), lds, stream, p);
     if (e != hipSuccess || !p.rec) return e;
-    return launch_record_sum(p.inst_rec, p.B, p.partials, p.rec, stream);
+    return launch_record_reduce<kFixRecMax>(p.inst_rec, p.B, p.partials, p.rec, stream);
 }
 
 hipError_t launch_fix_sense(const FixSenseParams& p, hipStream_t stream) {
@@ -120,11 +108,8 @@ hipError_t launch_fix_sense(const FixSenseParams& p, hipStream_t stream) {
 }
 
 hipError_t launch_fix_work(const int32_t* M, const int32_t* verdict, size_t n, int L_max, unsigned long long* work, hipStream_t stream) {
-    if (!M || !verdict || !work || n == 0) return hipErrorInvalidValue;
-    const size_t want = (n + 255) / 256;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(fix_work_kernel, dim3((unsigned)(want < 256 ? want : 256)), dim3(256), 0, stream, M, verdict, n, L_max, work);
-    return hipGetLastError();
+    if (!M || !verdict) return hipErrorInvalidValue;
+    return launch_work_sum<2>(FixWorkTerms{M, verdict, L_max}, n, work, stream);
 }
 
 }  // namespace slam

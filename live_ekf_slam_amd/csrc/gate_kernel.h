@@ -66,7 +66,7 @@ InnovResult gate_instance_host(InnovWork& ws, LX load_x, LP load_P, const int32_
 
 #if defined(__HIPCC__)
 // One gating of every instance on `stream`: three launches (the instances with their filtered messages, then the record as
-// launch_innovation reduces it).  in.s is what the step that follows is launched with, message source meas_in / meas_count_in /
+// launch_innovation reduces it, join mask kInnovRecMax).  in.s is what the step that follows is launched with, message source meas_in / meas_count_in /
 // k_stride_in (never the simulator).  meas_out / count_out may be the input pair itself (in place: the message is in LDS before anything is
 // written) and must not overlap it otherwise.
 struct GateParams {

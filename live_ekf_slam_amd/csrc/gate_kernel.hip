@@ -8,14 +8,14 @@
 // verdict != 2, a kept detection's position the popcount of the mask below its lane, so message order is preserved without a scan loop.
 // The whole message is in LDS before the first write, so the output row may be the input row.  Instances that pass through (frozen, would
 // freeze, too long) copy their row from global memory when the output is another buffer.
-// Record: the per-instance contributions (entry 15 = rejected detections) go through innovation_reduce_kernel and innovation_sum_kernel
-// (launch_innovation_reduce): a fixed order that depends on the batch size alone, no atomics on values.  All arithmetic is fp64, unfused.
+// Record: the per-instance contributions (an innovation record with entry 15 = rejected detections, join mask kInnovRecMax) go through
+// launch_record_reduce (record_kernel.h): a fixed order that depends on the batch size alone, no atomics on values.  All arithmetic is
+// fp64, unfused.
 #include <hip/hip_runtime.h>
 
 #include "../../include/slam_batch.h"
-#include "ekf_kernel.h"
+#include "aux_device.h"
 #include "gate_kernel.h"
-#include "sim_device.h"
 
 namespace slam {
 namespace {
@@ -36,30 +36,18 @@ __global__ __launch_bounds__(64 * kGateWaves) void gate_instance_kernel(const Ga
     if (b >= s.B) return;                            // (the whole wavefront; there is no workgroup barrier below)
     InnovWork& ws = s_ws[wave];
     const InnovWave w = {lane};
-    const StepNoise sn = step_noise(s, b);
-    const InnovNoise nz = {sn.v_d, sn.v_th, sn.w_r, sn.w_b, sn.V00, sn.V11, sn.W00, sn.W11};
-    const int32_t status = s.flags[b];
-    const float* const cp = s.cmd_each ? s.cmd_each + 2 * (size_t)b : nullptr;
-    const float fwd = cp ? cp[0] : s.fwd, ang = cp ? cp[1] : s.ang;
-    const int count = s.meas_count_in[b];
-    int k = count < s.k_stride_in ? count : s.k_stride_in;
-    k = k < 0 ? 0 : k;
-    const float* const src = s.meas_in + (size_t)b * s.k_stride_in * 3;
+    const AuxInstance<ST> inst(s, b);
+    const AuxMessage msg(s, b);
+    const int count = msg.count, k = msg.k;
+    const float* const src = msg.src;
     float* const dst = p.meas_out + (size_t)b * s.k_stride_in * 3;
-    if (k <= kInnovMaxDet)
-        for (int i = lane; i < 3 * k; i += 64) ws.meas[i] = src[i];
+    msg.stage(lane, ws.meas);
     w.sync();
-    int M = s.M[b];
-    M = M < 0 ? 0 : (M > s.L_max ? s.L_max : M);
-    const int ld = ekf_ld(3 + 2 * M, (int)sizeof(ST));
-    const ST* __restrict__ const xb = static_cast<const ST*>(s.x) + (size_t)b * s.xstride;
-    const ST* __restrict__ const Pb = static_cast<const ST*>(s.P) + (size_t)b * s.pstride;
     double* const det = p.in.det ? p.in.det + (size_t)b * kInnovMaxDet * kInnovDetLen : nullptr;
     InnovGate g = {p.gate, s_verdict[wave], 0};
     // (every index the loaders see is below 3 + 2 M: the block's landmarks come from ids[0 .. M))
-    const InnovResult v = innovation_instance(
-        w, ws, [&](int i) { return (double)xb[i]; }, [&](int r, int c) { return (double)Pb[(size_t)r * ld + c]; },
-        s.ids + (size_t)b * s.L_max, M, s.L_max, status, fwd, ang, k, nz, s.lm_from_pred != 0, p.in.nis_lo, p.in.nis_hi, det, &g);
+    const InnovResult v = innovation_instance(w, ws, inst.load_x(), inst.load_P(), inst.ids, inst.M, s.L_max, inst.status, inst.fwd, inst.ang, k,
+                                              inst.nz, s.lm_from_pred != 0, p.in.nis_lo, p.in.nis_hi, det, &g);
     w.sync();                                        // the verdicts lane 0 wrote
     const int32_t vd = s_verdict[wave][lane];
     if (p.verdict) p.verdict[(size_t)b * kInnovMaxDet + lane] = vd;
@@ -101,18 +89,13 @@ __global__ __launch_bounds__(64 * kGateWaves) void gate_instance_kernel(const Ga
 
 hipError_t launch_gate(const GateParams& p, int f32_storage, hipStream_t stream) {
     const EkfStepParams& s = p.in.s;
-    const int n_max = 3 + 2 * s.L_max;
-    if (s.B <= 0 || s.L_max < 0 || !p.in.inst_rec || !p.in.partials || !p.in.rec || s.xstride < n_max ||
-        (long long)s.pstride < (long long)n_max * ekf_ld(n_max, f32_storage ? 4 : 8))
-        return hipErrorInvalidValue;
+    if (!aux_shape_ok(s.B, s.L_max, s.xstride, s.pstride, f32_storage) || !p.in.inst_rec || !p.in.partials || !p.in.rec) return hipErrorInvalidValue;
     if (s.sim || !s.meas_in || !s.meas_count_in || s.k_stride_in <= 0 || !p.meas_out || !p.count_out || !(p.gate > 0.0)) return hipErrorInvalidValue;
     const int groups = (s.B + kGateWaves - 1) / kGateWaves;
-    (void)hipGetLastError();   // sticky and per thread: only these launches' errors are reported (capi_internal.h)
-    if (f32_storage) hipLaunchKernelGGL(gate_instance_kernel<float>, dim3(groups), dim3(64 * kGateWaves), 0, stream, p);
-    else hipLaunchKernelGGL(gate_instance_kernel<double>, dim3(groups), dim3(64 * kGateWaves), 0, stream, p);
-    const hipError_t e = hipGetLastError();
+    const hipError_t e = aux_launch(f32_storage, gate_instance_kernel<float>, gate_instance_kernel<double>, dim3(groups), dim3(64 * kGateWaves), 0,
+                                    stream, p);
     if (e != hipSuccess) return e;
-    return launch_innovation_reduce(p.in.inst_rec, s.B, p.in.partials, p.in.rec, stream);
+    return launch_record_reduce<kInnovRecMax>(p.in.inst_rec, s.B, p.in.partials, p.in.rec, stream);
 }
 
 }  // namespace slam

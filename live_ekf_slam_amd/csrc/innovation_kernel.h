@@ -38,6 +38,7 @@
 #include "ekf_model.h"
 #if defined(__HIPCC__)
 #include "ekf_kernel.h"
+#include "record_kernel.h"
 #endif
 
 namespace slam {
@@ -48,7 +49,6 @@ constexpr int kInnovNb = 3 + 2 * kInnovMaxLm;       // rows of the largest block
                                                     // doubles hit 32 different bank pairs)
 constexpr int kInnovDetLen = 6;                     // doubles per detection slot
 constexpr int kInnovRecLen = 16;                    // doubles of one record
-constexpr int kInnovBlock = 256;                    // instances one workgroup of the reduction takes
 
 constexpr int32_t kInnovFrozen = 1, kInnovWouldFreeze = 2, kInnovSingular = 4, kInnovTooLong = 8;   // slam_innovation_flags
 constexpr int32_t kInnovStatusFrozen = 4;           // SLAM_INST_INDEX_OOR: the step kernel returns at once
@@ -58,6 +58,7 @@ enum InnovRec {
     kInnEval = 0, kInnFrozen = 1, kInnTooLong = 2, kInnWouldFreeze = 3, kInnSingular = 4, kInnUpd = 5, kInnNew = 6, kInnSumNis = 7,
     kInnMaxNis = 8, kInnBelow = 9, kInnAbove = 10, kInnSumNuR = 11, kInnSumNuB = 12, kInnSumNuR2 = 13, kInnSumNuB2 = 14, kInnReserved = 15
 };
+constexpr unsigned kInnovRecMax = 1u << kInnMaxNis;    // the entries joined by a maximum (record_kernel.h); every other is a sum
 
 struct InnovNoise { float v_d, v_th, w_r, w_b; double V00, V11, W00, W11; };   // the instance's filter noise (effective V / W)
 
@@ -329,13 +330,10 @@ struct InnovParams {
     double* det;                // [B][kInnovMaxDet][kInnovDetLen] or NULL
     double* post;               // [B][12] or NULL
     double* inst_rec;           // [B][kInnovRecLen]
-    double* partials;           // [innovation_blocks(B)][kInnovRecLen]
+    double* partials;           // [record_blocks(B)][kInnovRecLen]
     double* rec;                // [kInnovRecLen]
 };
-inline int innovation_blocks(int B) { return (B + kInnovBlock - 1) / kInnovBlock; }
 hipError_t launch_innovation(const InnovParams& p, int f32_storage, hipStream_t stream);
-// its second and third launch alone: inst_rec [B][kInnovRecLen] -> partials [innovation_blocks(B)][kInnovRecLen] -> rec [kInnovRecLen]
-hipError_t launch_innovation_reduce(const double* inst_rec, int B, double* partials, double* rec, hipStream_t stream);
 #endif
 
 }  // namespace slam

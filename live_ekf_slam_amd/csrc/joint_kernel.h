@@ -49,7 +49,7 @@
 // as slam_associate, d2 and nu being those of the paired slot when MATCHED, and the number of candidates kept.
 // Record (kInnovRecLen doubles): 0 evaluated, 1 FROZEN, 2 TOO_LONG, 3 detections in, 4 matched, 5 new, 6 ambiguous, 7 sum of d2_joint,
 // 8 max of d2_joint, 9 unpaired, 10 no room, 11 invalid, 12 sum of nodes, 13 instances with kJointBudget, 14 instances with
-// kJointSingular, 15 matched detections whose slot is not their individual best.  Entry 8 is a maximum, the rest sums (rec_join).
+// kJointSingular, 15 matched detections whose slot is not their individual best.  Entry 8 is a maximum, the rest sums (kJointRecMax).
 // Out of scope: the UKF kinds, the simulator sources, slam_multi_*, the pose graph, joint association inside slam_manage_run /
 // slam_manage_merge_run, the ln det S term, more than 16 pairings per message.
 #pragma once
@@ -71,7 +71,7 @@ enum JointRec {
     kJntEval = 0, kJntFrozen = 1, kJntTooLong = 2, kJntDetIn = 3, kJntMatched = 4, kJntNew = 5, kJntAmbiguous = 6, kJntSumD2 = 7,
     kJntMaxD2 = 8, kJntUnpaired = 9, kJntNoRoom = 10, kJntInvalid = 11, kJntNodes = 12, kJntBudget = 13, kJntSingular = 14, kJntDiffer = 15
 };
-static_assert((int)kJntMaxD2 == (int)kInnMaxNis, "the entry launch_innovation_reduce joins by max");
+constexpr unsigned kJointRecMax = 1u << kJntMaxD2;   // the entries joined by a maximum (record_kernel.h)
 
 // what one instance holds between its phases: LDS on the device (one per wavefront), plain memory on the host.  Arrays over detections
 // and table entries are indexed [..][l]: lane l reads element l, consecutive banks.
@@ -467,7 +467,7 @@ struct JointParams {
     double* det;                // [B][kInnovMaxDet][kAssocDetLen] or NULL
     int32_t *n_lm, *n_blk;      // [B]: landmarks compared with (-1: an empty message) and 2 x 2 blocks read on demand, or NULL
     double* inst_rec;           // [B][kInnovRecLen]
-    double* partials;           // [innovation_blocks(B)][kInnovRecLen]
+    double* partials;           // [record_blocks(B)][kInnovRecLen]
     double* rec;                // [kInnovRecLen]
 };
 hipError_t launch_associate_joint(const JointParams& p, int f32_storage, hipStream_t stream);

@@ -15,13 +15,12 @@
 //              right-looking: lane (row, column) holds one element and subtracts in ascending column order, what the sequential policy
 //              does too; the corner, y and the distance are summed by every lane alike from LDS broadcasts
 //   the search its control state (level, pairs, used set, best) is computed alike in every lane and kept scalar by readfirstlane
-// Record and traffic model: as assoc_kernel.hip.  All arithmetic is fp64, unfused.
+// Record (join mask kJointRecMax) and traffic model: as assoc_kernel.hip.  All arithmetic is fp64, unfused.
 #include <hip/hip_runtime.h>
 
 #include "../../include/slam_batch.h"
-#include "ekf_kernel.h"
+#include "aux_device.h"
 #include "joint_kernel.h"
-#include "sim_device.h"
 
 namespace slam {
 namespace {
@@ -29,6 +28,8 @@ namespace {
 static_assert(kAssocJointUnpaired == SLAM_ASSOC_JOINT_UNPAIRED && kJointMaxCand == SLAM_JOINT_MAX_CAND && kJointMaxPair == SLAM_JOINT_MAX_PAIR &&
               kJointBudget == SLAM_JOINT_BUDGET && kJointSingular == SLAM_JOINT_S_SINGULAR && kJointLmTable == SLAM_JOINT_LM_TABLE,
               "the constants of slam_batch.h");
+
+static_assert(kInnovRecLen == kRecLen, "the record launch_record_reduce takes");
 
 constexpr int kJointWaves = 2;                      // instances per workgroup
 static_assert(sizeof(JointWork) * kJointWaves <= 64 * 1024, "static LDS of a workgroup");
@@ -43,17 +44,9 @@ __global__ __launch_bounds__(64 * kJointWaves) void joint_instance_kernel(const 
     JointWork& ws = s_ws[wave];
     JointWave w;
     w.ln = lane;
-    const StepNoise sn = step_noise(s, b);
-    const InnovNoise nz = {sn.v_d, sn.v_th, sn.w_r, sn.w_b, sn.V00, sn.V11, sn.W00, sn.W11};
-    const int32_t status = s.flags[b];
-    const float* const cp = s.cmd_each ? s.cmd_each + 2 * (size_t)b : nullptr;
-    const float fwd = cp ? cp[0] : s.fwd, ang = cp ? cp[1] : s.ang;
-    const int count = s.meas_count_in[b];
-    int k = count < s.k_stride_in ? count : s.k_stride_in;
-    k = k < 0 ? 0 : k;
-    const float* const src = s.meas_in + (size_t)b * s.k_stride_in * 3;
-    if (k <= kInnovMaxDet)
-        for (int i = lane; i < 3 * k; i += 64) ws.a.meas[i] = src[i];
+    const AuxInstance<ST> inst(s, b);
+    const AuxMessage msg(s, b);
+    msg.stage(lane, ws.a.meas);
     {   // gate_joint into LDS (constant indices: the kernel arguments stay in scalar registers)
         double g = 0.0;
 #pragma unroll
@@ -61,19 +54,14 @@ __global__ __launch_bounds__(64 * kJointWaves) void joint_instance_kernel(const 
         if (lane < kJointMaxPair) ws.gj[lane] = g;
     }
     w.sync();
-    int M = s.M[b];
-    M = M < 0 ? 0 : (M > s.L_max ? s.L_max : M);
-    const int ld = ekf_ld(3 + 2 * M, (int)sizeof(ST));
-    const ST* __restrict__ const xb = static_cast<const ST*>(s.x) + (size_t)b * s.xstride;
-    const ST* __restrict__ const Pb = static_cast<const ST*>(s.P) + (size_t)b * s.pstride;
+    const int M = inst.M;
     const size_t bd = (size_t)b * kInnovMaxDet;
     // (every index the loaders see is below 3 + 2 M: a landmark of the cost phase is j < M or landmark 0 while M > 0, and the table
     // and the pairings hold slots the cost phase found, j < M)
     const JointResult v = joint_instance(
-        w, ws, [&](int i) { return (double)xb[i]; }, [&](int r, int c) { return (double)Pb[(size_t)r * ld + c]; }, s.ids + (size_t)b * s.L_max, M,
-        s.L_max, status, fwd, ang, k, nz, p.gate_match, p.gate_new, ws.gj, p.max_nodes, nullptr, p.verdict ? p.verdict + bd : nullptr,
-        p.slot ? p.slot + bd : nullptr, p.det ? p.det + bd * kAssocDetLen : nullptr, p.ncand ? p.ncand + bd : nullptr,
-        p.meas_out + (size_t)b * s.k_stride_in * 3);
+        w, ws, inst.load_x(), inst.load_P(), inst.ids, M, s.L_max, inst.status, inst.fwd, inst.ang, msg.k, inst.nz, p.gate_match, p.gate_new,
+        ws.gj, p.max_nodes, nullptr, p.verdict ? p.verdict + bd : nullptr, p.slot ? p.slot + bd : nullptr,
+        p.det ? p.det + bd * kAssocDetLen : nullptr, p.ncand ? p.ncand + bd : nullptr, p.meas_out + (size_t)b * s.k_stride_in * 3);
     if (lane == 0) {
         p.count_out[b] = v.count_out;
         if (p.n_match) p.n_match[b] = v.n_match;
@@ -91,57 +79,37 @@ __global__ __launch_bounds__(64 * kJointWaves) void joint_instance_kernel(const 
     }
 }
 
-// The traffic model summed over n instance-ticks, in integers: assoc_work_kernel's sums plus, per on-demand 2 x 2 block of P, four
-// elements and one 128-byte line
-__global__ __launch_bounds__(256) void joint_work_kernel(const int32_t* __restrict__ n_lm, const int32_t* __restrict__ n_match,
-                                                         const int32_t* __restrict__ n_new, const int32_t* __restrict__ n_drop,
-                                                         const int32_t* __restrict__ n_blk, size_t n, int esz, unsigned long long* __restrict__ work) {
-    unsigned long long a0 = 0, a1 = 0, a2 = 0;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int M = n_lm[i];
-        AssocTraffic t;
-        if (M >= 0) {
-            t = assoc_traffic(M, n_match[i] + n_new[i] + n_drop[i], esz);
-            t.p_elems += 4ull * (unsigned long long)n_blk[i]; t.p_lines += (unsigned long long)n_blk[i];
-        } else {
-            t = AssocTraffic{0ull, 8ull, 0ull};    // an instance that emits an empty message: the counts
-        }
-        a0 += t.p_elems; a1 += t.other_bytes; a2 += t.p_lines;
+// element i of the traffic model's sum: assoc_kernel.hip's terms plus, per on-demand 2 x 2 block of P, four elements and one 128-byte line
+struct JointWorkTerms {
+    const int32_t *n_lm, *n_match, *n_new, *n_drop, *n_blk;
+    int esz;
+    __device__ void operator()(size_t i, unsigned long long (&t)[3]) const {
+        const bool some = n_lm[i] >= 0;              // (else: an instance that emits an empty message: the counts)
+        const AssocTraffic w = some ? assoc_traffic(n_lm[i], n_match[i] + n_new[i] + n_drop[i], esz) : AssocTraffic{0ull, 8ull, 0ull};
+        const unsigned long long blk = some ? (unsigned long long)n_blk[i] : 0ull;
+        t[0] = w.p_elems + 4ull * blk; t[1] = w.other_bytes; t[2] = w.p_lines + blk;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        a0 += __shfl_down(a0, off, 64); a1 += __shfl_down(a1, off, 64); a2 += __shfl_down(a2, off, 64);
-    }
-    if (threadIdx.x % 64 == 0) { atomicAdd(work, a0); atomicAdd(work + 1, a1); atomicAdd(work + 2, a2); }
-}
+};
 
 }  // namespace
 
 hipError_t launch_associate_joint_work(const int32_t* n_lm, const int32_t* n_match, const int32_t* n_new, const int32_t* n_drop, const int32_t* n_blk,
                                        size_t n, int esz, unsigned long long* work, hipStream_t stream) {
-    if (!n_lm || !n_match || !n_new || !n_drop || !n_blk || !work || n == 0) return hipErrorInvalidValue;
-    const size_t want = (n + 255) / 256;
-    hipLaunchKernelGGL(joint_work_kernel, dim3((unsigned)(want < 256 ? want : 256)), dim3(256), 0, stream, n_lm, n_match, n_new, n_drop, n_blk, n, esz,
-                       work);
-    return hipGetLastError();
+    if (!n_lm || !n_match || !n_new || !n_drop || !n_blk) return hipErrorInvalidValue;
+    return launch_work_sum<3>(JointWorkTerms{n_lm, n_match, n_new, n_drop, n_blk, esz}, n, work, stream);
 }
 
 hipError_t launch_associate_joint(const JointParams& p, int f32_storage, hipStream_t stream) {
     const EkfStepParams& s = p.s;
-    const int n_max = 3 + 2 * s.L_max;
-    if (s.B <= 0 || s.L_max < 0 || !p.inst_rec || !p.partials || !p.rec || s.xstride < n_max ||
-        (long long)s.pstride < (long long)n_max * ekf_ld(n_max, f32_storage ? 4 : 8))
-        return hipErrorInvalidValue;
+    if (!aux_shape_ok(s.B, s.L_max, s.xstride, s.pstride, f32_storage) || !p.inst_rec || !p.partials || !p.rec) return hipErrorInvalidValue;
     if (s.sim || !s.meas_in || !s.meas_count_in || s.k_stride_in <= 0 || !p.meas_out || !p.count_out || !(p.gate_match > 0.0) ||
         !(p.gate_match <= p.gate_new) || p.max_nodes < 1 || p.max_nodes > kJointMaxNodes)
         return hipErrorInvalidValue;
     const int groups = (s.B + kJointWaves - 1) / kJointWaves;
-    (void)hipGetLastError();   // sticky and per thread: only these launches' errors are reported (capi_internal.h)
-    if (f32_storage) hipLaunchKernelGGL(joint_instance_kernel<float>, dim3(groups), dim3(64 * kJointWaves), 0, stream, p);
-    else hipLaunchKernelGGL(joint_instance_kernel<double>, dim3(groups), dim3(64 * kJointWaves), 0, stream, p);
-    const hipError_t e = hipGetLastError();
+    const hipError_t e = aux_launch(f32_storage, joint_instance_kernel<float>, joint_instance_kernel<double>, dim3(groups), dim3(64 * kJointWaves), 0,
+                                    stream, p);
     if (e != hipSuccess) return e;
-    return launch_innovation_reduce(p.inst_rec, s.B, p.partials, p.rec, stream);
+    return launch_record_reduce<kJointRecMax>(p.inst_rec, s.B, p.partials, p.rec, stream);
 }
 
 }  // namespace slam

@@ -8,7 +8,7 @@
 // Removal (map_compact_instance).  In covariance form, dropping a landmark is exact marginalisation: its two entries of x and its two
 // rows and columns of P disappear and nothing else changes.  With the kept slots k0 < k1 < ... in their old order, x', ids' and P' are
 // the sub-vector and sub-matrix on the state indices {0, 1, 2} u {3 + 2 k, 4 + 2 k}, P' stored at the leading dimension
-// map_ld(3 + 2 M') = ekf_ld of the smaller state, its pad columns zero (the invariant of ekf_kernel.h), M' = M - removed,
+// ekf_ld(3 + 2 M') of the smaller state, its pad columns zero (the invariant of ekf_kernel.h), M' = M - removed,
 // ids[M' .. L_max) and the track counters of those slots zero.  Pure data movement: elements are moved as integers of their size, so
 // NaNs keep their payloads.  Status flags, timestep, truth and err_sum are not touched and the status is not consulted; the slab beyond
 // n' * ld' elements keeps whatever it held.
@@ -36,16 +36,17 @@
 
 namespace slam {
 
-constexpr int kMapRecLen = 16;                      // doubles of one record (kInnovRecLen: it goes through launch_innovation_reduce)
+constexpr int kMapRecLen = 16;                      // doubles of one record
 enum MapRec { kMapTouched = 0, kMapRemoved = 1, kMapMoved = 2 };   // instances touched, landmarks removed, elements of P moved; the rest 0
+constexpr unsigned kMapRecMax = 1u << 8;             // the entries joined by a maximum (record_kernel.h): entry 8, unused and 0, as it always was
 constexpr int32_t kMapStatusSkip = 1 | 4 | 32;      // SLAM_INST_NONFINITE | SLAM_INST_INDEX_OOR | SLAM_INST_WATCHDOG: no tally
 constexpr int kMapMaxLandmarks = 1000;              // kEkfMaxLandmarks: what the index table of a workgroup holds
 constexpr int kMapChunk = 8;                        // elements a lane holds between the loads and the stores of a chunk (16 floats
                                                     // measured slower than 8: 1.53 against 1.41 ms at L = 50 x 65 536)
 constexpr int kMapIdBlock = 64;                     // ids of the message held at once by the tally
 
-// ekf_ld (ekf_kernel.h), repeated for the host build that has no HIP headers; map_kernel.hip asserts that the two agree
-constexpr int map_ld(int n, int elem_bytes) { return elem_bytes == 8 ? ((n + 1) & ~1) : ((n + 3) & ~3); }
+// ekf_ld (slam_math.h) under the name the stand-alone host programs of the map, merge and fix tests call it by
+SLAM_HD constexpr int map_ld(int n, int elem_bytes) { return ekf_ld(n, elem_bytes); }
 
 // the view test of one estimated landmark from the estimated pose: sim_device.h:84-87 on estimates, with shrunk limits
 SLAM_HD bool map_in_view(double px, double py, double pth, double lx, double ly, double r_lim, double b_lo, double b_hi) {
@@ -133,7 +134,7 @@ template <class W, class T>
 SLAM_HD void map_compact_instance(const W& w, T* P, T* x, int32_t* ids, int32_t* seen, int32_t* expected, const uint16_t* kept, int M, int Mk,
                                   int L_max) {
     const int n = 3 + 2 * M, n2 = 3 + 2 * Mk;
-    const int ld = map_ld(n, (int)sizeof(T)), ld2 = map_ld(n2, (int)sizeof(T));
+    const int ld = ekf_ld(n, (int)sizeof(T)), ld2 = ekf_ld(n2, (int)sizeof(T));
     auto old_index = [&](int k) { return k < 3 ? k : 3 + 2 * (int)kept[(k - 3) >> 1] + ((k - 3) & 1); };   // R
     map_gather_chunks(w, P, P, n2 * ld2, [&](int i) -> int {
         const int r = i / ld2, c = i - r * ld2;
@@ -156,7 +157,7 @@ SLAM_HD MapTraffic map_traffic(int M, int removed, int L_max, int esz, bool from
     MapTraffic t = {0ull, 0ull, 4ull + (from_counters ? 8ull : 4ull) * m + 4ull};   // M, the decision's inputs, n_removed
     if (removed <= 0) return t;
     const unsigned long long mk = m - (unsigned long long)removed, n2 = 3ull + 2ull * mk;
-    const unsigned long long ld2 = (unsigned long long)map_ld((int)n2, esz);
+    const unsigned long long ld2 = (unsigned long long)ekf_ld((int)n2, esz);
     t.moved = n2 * n2;
     t.pads = n2 * (ld2 - n2);
     t.other_bytes += 2ull * n2 * e + (counters ? 3ull : 1ull) * 4ull * (mk + (unsigned long long)L_max) + 4ull;
@@ -177,7 +178,7 @@ int map_remove_instance_host(T* P, T* x, int32_t* ids, int32_t* seen, int32_t* e
 
 #if defined(__HIPCC__)
 // One removal of every instance on `stream`: the compaction launch, then - when rec is wanted - the record as
-// launch_innovation_reduce sums it (two more launches).
+// launch_record_reduce sums it (two more launches).
 struct MapCompactParams {
     void* P; void* x;                 // [B][pstride], [B][xstride] in elements of the storage type; compacted in place
     int32_t *M, *ids;                 // [B], [B][L_max]
@@ -186,7 +187,7 @@ struct MapCompactParams {
     int32_t min_expected; double min_ratio;
     int32_t *n_removed, *m_before;    // [B] each: what the instance dropped and the M it had (the traffic model reads both)
     double* inst_rec;                 // [B][kMapRecLen]
-    double* partials;                 // [innovation_blocks(B)][kMapRecLen]
+    double* partials;                 // [record_blocks(B)][kMapRecLen]
     double* rec;                      // [kMapRecLen], or NULL: no record, and inst_rec / partials are not used
     int32_t B, L_max, pstride, xstride;
 };

@@ -16,23 +16,20 @@
 //              or of two rows at a row end, so every line is fetched once; kMapChunk = 8 loads per lane are in flight before the barrier.
 // map_tally_kernel: a wavefront per instance, four per workgroup, lanes over slots, the message's ids in the wavefront's slice of LDS,
 //   phases ordered by wavefront fences (assoc_kernel.hip's mapping).
-// map_work_kernel: the traffic model summed in integers from the per-instance counts, outside any timed part (assoc_work_kernel's shape).
+// MapWorkTerms: the traffic model, summed in integers from the per-instance counts by launch_work_sum, outside any timed part.
+// Record: launch_record_reduce (record_kernel.h) with the join mask kMapRecMax.
 #include <hip/hip_runtime.h>
 
 #include "../../include/slam_batch.h"
-#include "ekf_kernel.h"
-#include "innovation_kernel.h"
+#include "aux_device.h"
 #include "map_kernel.h"
 
 namespace slam {
 namespace {
 
-static_assert(kMapRecLen == kInnovRecLen, "the record goes through launch_innovation_reduce");
+static_assert(kMapRecLen == kRecLen, "the record launch_record_reduce takes");
 static_assert(kMapStatusSkip == (SLAM_INST_NONFINITE | SLAM_INST_INDEX_OOR | SLAM_INST_WATCHDOG), "the instances the tally skips");
 static_assert(kMapMaxLandmarks == kEkfMaxLandmarks, "the kept table holds every slot");
-static_assert(map_ld(3, 8) == ekf_ld(3, 8) && map_ld(43, 8) == ekf_ld(43, 8) && map_ld(2003, 8) == ekf_ld(2003, 8) &&
-              map_ld(3, 4) == ekf_ld(3, 4) && map_ld(5, 4) == ekf_ld(5, 4) && map_ld(43, 4) == ekf_ld(43, 4) && map_ld(2003, 4) == ekf_ld(2003, 4),
-              "map_ld is ekf_ld");
 
 constexpr int kMapThreads = 256;                    // one instance's workgroup of the compaction
 constexpr int kMapTallyWaves = 4;                   // instances per workgroup of the tally
@@ -61,8 +58,7 @@ __global__ __launch_bounds__(kMapThreads) void map_compact_kernel(const MapCompa
     __shared__ int s_Mk;
     const int b = blockIdx.x;                        // (the grid is exactly B workgroups)
     const int tid = threadIdx.x;
-    int M = p.M[b];
-    M = M < 0 ? 0 : (M > p.L_max ? p.L_max : M);
+    const int M = aux_clamp_m(p.M[b], p.L_max);
     const size_t row = (size_t)b * p.L_max;
     const int32_t* const remove = p.remove ? p.remove + row : nullptr;
     int32_t* const seen = p.seen ? p.seen + row : nullptr;
@@ -91,9 +87,7 @@ __global__ __launch_bounds__(kMapThreads) void map_compact_kernel(const MapCompa
     }
     __syncthreads();
     const int Mk = s_Mk;
-    T* const Pb = static_cast<T*>(p.P) + (size_t)b * p.pstride;
-    T* const xb = static_cast<T*>(p.x) + (size_t)b * p.xstride;
-    map_compact_instance(MapGroup(), Pb, xb, p.ids + row, seen, expected, s_kept, M, Mk, p.L_max);
+    map_compact_instance(MapGroup(), aux_row<T>(p.P, b, p.pstride), aux_row<T>(p.x, b, p.xstride), p.ids + row, seen, expected, s_kept, M, Mk, p.L_max);
     if (tid == 0) {
         const int n2 = 3 + 2 * Mk;
         p.M[b] = Mk;
@@ -116,49 +110,37 @@ __global__ __launch_bounds__(64 * kMapTallyWaves) void map_tally_kernel(const Ma
     if (b >= p.B) return;                            // (the whole wavefront; there is no workgroup barrier below)
     if (p.status[b] & kMapStatusSkip) return;
     if (p.assoc_flags && p.assoc_flags[b] != 0) return;
-    int M = p.M[b];
-    M = M < 0 ? 0 : (M > p.L_max ? p.L_max : M);
+    const int M = aux_clamp_m(p.M[b], p.L_max);
     const int count = p.count[b];
     int k = count < p.k_stride ? count : p.k_stride;
     k = k < 0 ? 0 : k;
-    const ST* __restrict__ const xb = static_cast<const ST*>(p.x) + (size_t)b * p.xstride;
+    const ST* __restrict__ const xb = aux_row<ST>(p.x, b, p.xstride);
     const size_t row = (size_t)b * p.L_max;
     // (every index load_x sees is below 3 + 2 M: only the lanes with j < M read a landmark)
     map_tally_instance(MapWave{lane}, [&](int i) { return (double)xb[i]; }, p.ids + row, M, p.meas + (size_t)b * p.k_stride * 3, k, s_id[wave],
                        s_ok[wave], p.r_lim, p.b_lo, p.b_hi, p.seen + row, p.expected + row);
 }
 
-// map_traffic summed over n instances, in integers (the order of the additions does not matter): a grid-stride sum per lane, a shuffle
-// tree per wavefront, one atomic add per wavefront and sum
-__global__ __launch_bounds__(256) void map_work_kernel(const int32_t* __restrict__ m_before, const int32_t* __restrict__ n_removed, size_t n,
-                                                       int L_max, int esz, int from_counters, int counters,
-                                                       unsigned long long* __restrict__ work) {
-    unsigned long long a0 = 0, a1 = 0, a2 = 0;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const MapTraffic t = map_traffic(m_before[i], n_removed[i], L_max, esz, from_counters != 0, counters != 0);
-        a0 += t.moved; a1 += t.pads; a2 += t.other_bytes;
+// element i of the traffic model's sum: one instance of one call
+struct MapWorkTerms {
+    const int32_t *m_before, *n_removed;
+    int L_max, esz, from_counters, counters;
+    __device__ void operator()(size_t i, unsigned long long (&t)[3]) const {
+        const MapTraffic w = map_traffic(m_before[i], n_removed[i], L_max, esz, from_counters != 0, counters != 0);
+        t[0] = w.moved; t[1] = w.pads; t[2] = w.other_bytes;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        a0 += __shfl_down(a0, off, 64); a1 += __shfl_down(a1, off, 64); a2 += __shfl_down(a2, off, 64);
-    }
-    if (threadIdx.x % 64 == 0) { atomicAdd(work, a0); atomicAdd(work + 1, a1); atomicAdd(work + 2, a2); }
-}
+};
 
 }  // namespace
 
 hipError_t launch_map_compact(const MapCompactParams& p, int f32_storage, hipStream_t stream) {
-    const int n_max = 3 + 2 * p.L_max;
-    if (p.B <= 0 || p.L_max <= 0 || p.L_max > kMapMaxLandmarks || !p.P || !p.x || !p.M || !p.ids || !p.n_removed || !p.m_before ||
-        (p.rec && (!p.inst_rec || !p.partials)) || p.xstride < n_max || (long long)p.pstride < (long long)n_max * ekf_ld(n_max, f32_storage ? 4 : 8))
+    if (!aux_shape_ok(p.B, p.L_max, p.xstride, p.pstride, f32_storage) || p.L_max <= 0 || p.L_max > kMapMaxLandmarks || !p.P || !p.x || !p.M ||
+        !p.ids || !p.n_removed || !p.m_before || (p.rec && (!p.inst_rec || !p.partials)))
         return hipErrorInvalidValue;
     if ((p.seen == nullptr) != (p.expected == nullptr) || (!p.remove && !p.seen)) return hipErrorInvalidValue;
-    (void)hipGetLastError();   // sticky and per thread: only these launches' errors are reported (capi_internal.h)
-    if (f32_storage) hipLaunchKernelGGL(map_compact_kernel<uint32_t>, dim3(p.B), dim3(kMapThreads), 0, stream, p);
-    else hipLaunchKernelGGL(map_compact_kernel<uint64_t>, dim3(p.B), dim3(kMapThreads), 0, stream, p);
-    const hipError_t e = hipGetLastError();
+    const hipError_t e = aux_launch(f32_storage, map_compact_kernel<uint32_t>, map_compact_kernel<uint64_t>, dim3(p.B), dim3(kMapThreads), 0, stream, p);
     if (e != hipSuccess || !p.rec) return e;
-    return launch_innovation_reduce(p.inst_rec, p.B, p.partials, p.rec, stream);
+    return launch_record_reduce<kMapRecMax>(p.inst_rec, p.B, p.partials, p.rec, stream);
 }
 
 hipError_t launch_map_tally(const MapTallyParams& p, int f32_storage, hipStream_t stream) {
@@ -166,19 +148,13 @@ hipError_t launch_map_tally(const MapTallyParams& p, int f32_storage, hipStream_
         p.xstride < 3 + 2 * p.L_max)
         return hipErrorInvalidValue;
     const int groups = (p.B + kMapTallyWaves - 1) / kMapTallyWaves;
-    (void)hipGetLastError();
-    if (f32_storage) hipLaunchKernelGGL(map_tally_kernel<float>, dim3(groups), dim3(64 * kMapTallyWaves), 0, stream, p);
-    else hipLaunchKernelGGL(map_tally_kernel<double>, dim3(groups), dim3(64 * kMapTallyWaves), 0, stream, p);
-    return hipGetLastError();
+    return aux_launch(f32_storage, map_tally_kernel<float>, map_tally_kernel<double>, dim3(groups), dim3(64 * kMapTallyWaves), 0, stream, p);
 }
 
 hipError_t launch_map_work(const int32_t* m_before, const int32_t* n_removed, size_t n, int L_max, int esz, int from_counters, int counters,
                            unsigned long long* work, hipStream_t stream) {
-    if (!m_before || !n_removed || !work || n == 0) return hipErrorInvalidValue;
-    const size_t want = (n + 255) / 256;
-    hipLaunchKernelGGL(map_work_kernel, dim3((unsigned)(want < 256 ? want : 256)), dim3(256), 0, stream, m_before, n_removed, n, L_max, esz,
-                       from_counters, counters, work);
-    return hipGetLastError();
+    if (!m_before || !n_removed) return hipErrorInvalidValue;
+    return launch_work_sum<3>(MapWorkTerms{m_before, n_removed, L_max, esz, from_counters, counters}, n, work, stream);
 }
 
 }  // namespace slam

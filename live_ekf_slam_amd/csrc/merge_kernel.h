@@ -46,10 +46,11 @@
 
 namespace slam {
 
-constexpr int kMergeRecLen = 16;                    // doubles of one record (it goes through launch_innovation_reduce: entry 8 a maximum)
+constexpr int kMergeRecLen = 16;                    // doubles of one record
 // instances touched, pairs fused, entries / candidates that were not mutual, pairs skipped SINGULAR, elements of P updated (n^2 per fused
 // pair), the sum and the largest d2 of the fused pairs (0 without one); the rest 0
 enum MergeRec { kMrgTouched = 0, kMrgFused = 1, kMrgNotMutual = 2, kMrgSingular = 3, kMrgUpdated = 4, kMrgSumD2 = 7, kMrgMaxD2 = 8 };
+constexpr unsigned kMergeRecMax = 1u << kMrgMaxD2;   // the entries joined by a maximum (record_kernel.h); every other is a sum
 
 SLAM_HD bool merge_finite(double v) { return fabs(v) < __builtin_inf(); }
 
@@ -114,13 +115,13 @@ void merge_find_instance_host(LX load_x, LP load_P, int M, double gate, double s
 struct MergeCounts { int fused, singular; double sum_d2, max_d2; };
 
 // The fusion of one instance's pairs (pi[k] < pj[k], ascending pi; LDS on the device), in place.  ST: float or double, P at the leading
-// dimension ld = map_ld(n), x [n].  ws: 4 n + 2 doubles (c_r at 2 r, g_c at 2 n + 2 c, delta at 4 n).  remove [>= M] receives 1 at the
+// dimension ld = ekf_ld(n), x [n].  ws: 4 n + 2 doubles (c_r at 2 r, g_c at 2 n + 2 c, delta at 4 n).  remove [>= M] receives 1 at the
 // slot j of every fused pair (the caller zeroed it); seen / expected may be NULL.  Every lane of the policy calls it with the same
 // arguments and gets the same counts.  The barriers: see the top of this file.
 template <class W, class ST>
 SLAM_HD MergeCounts merge_fuse_instance(const W& w, ST* P, ST* x, int M, const uint16_t* pi, const uint16_t* pj, int n_pairs, double sigma2,
                                         double* ws, int32_t* remove, int32_t* seen, int32_t* expected) {
-    const int n = 3 + 2 * M, ld = map_ld(n, (int)sizeof(ST));
+    const int n = 3 + 2 * M, ld = ekf_ld(n, (int)sizeof(ST));
     MergeCounts cnt = {0, 0, 0.0, 0.0};
     double* const cr = ws;
     double* const gc = ws + 2 * n;

@@ -25,20 +25,19 @@
 //   lanes, the workspace (4 n + 2 doubles, 64 KB at n = 2003) in dynamic LDS.  The gather of c_r is a column read (two lines per row and
 //   pair, n rows) beside the n * ld elements the update streams through along rows; the two barriers per pair are argued in merge_kernel.h.
 //   Index arithmetic inside an instance is int; b * pstride is formed in size_t.
-// merge_work_kernel: the traffic model summed in integers, outside any timed part (map_work_kernel's shape).
+// MergeWorkTerms: the traffic model, summed in integers by launch_work_sum outside any timed part.
+// Record of the fusion: launch_record_reduce (record_kernel.h) with the join mask kMergeRecMax (entry kMrgMaxD2 is a maximum).
 #include <hip/hip_runtime.h>
 
 #include "../../include/slam_batch.h"
-#include "ekf_kernel.h"
-#include "innovation_kernel.h"
+#include "aux_device.h"
 #include "lds_attr.h"
 #include "merge_kernel.h"
 
 namespace slam {
 namespace {
 
-static_assert(kMergeRecLen == kInnovRecLen, "the record goes through launch_innovation_reduce");
-static_assert((int)kMrgMaxD2 == (int)kInnMaxNis, "the entry launch_innovation_reduce joins by max");
+static_assert(kMergeRecLen == kRecLen, "the record launch_record_reduce takes");
 
 constexpr int kMergeThreads = 256;                  // one instance's workgroup
 constexpr int kMergeOwn = 4;                        // slots a lane of the find owns at most
@@ -83,12 +82,11 @@ __global__ __launch_bounds__(kMergeThreads) void merge_find_kernel(const MergeFi
     static_assert(!SPLIT || OWN == 1, "a split find owns one slot per lane");
     const int b = blockIdx.x;                        // (the grid is exactly B workgroups)
     const int tid = threadIdx.x, nth = blockDim.x;
-    int M = p.M[b];
-    M = M < 0 ? 0 : (M > p.L_max ? p.L_max : M);
+    const int M = aux_clamp_m(p.M[b], p.L_max);
     if ((p.status[b] & kMapStatusSkip) || M < 2) return;   // (the whole workgroup, before any barrier: no pairs, nothing written)
     const int n = 3 + 2 * M, ld = ekf_ld(n, (int)sizeof(ST));
-    const ST* __restrict__ const Pb = static_cast<const ST*>(p.P) + (size_t)b * p.pstride;
-    const ST* __restrict__ const xb = static_cast<const ST*>(p.x) + (size_t)b * p.xstride;
+    const ST* __restrict__ const Pb = aux_row<ST>(p.P, b, p.pstride);
+    const ST* __restrict__ const xb = aux_row<ST>(p.x, b, p.xstride);
     double* const s_ct = s_dyn;
     double* const s_rw = s_dyn + 2 * TP * npad;
     const int wv = SPLIT ? tid / 64 : 0, own0 = SPLIT ? tid % 64 : tid;
@@ -175,8 +173,7 @@ __global__ __launch_bounds__(kMergeThreads) void merge_fuse_kernel(const MergeFu
     __shared__ int s_np, s_ig;
     const int b = blockIdx.x;
     const int tid = threadIdx.x;
-    int M = p.M[b];
-    M = M < 0 ? 0 : (M > p.L_max ? p.L_max : M);
+    const int M = aux_clamp_m(p.M[b], p.L_max);
     const bool skip = (p.status[b] & kMapStatusSkip) != 0;
     const size_t row = (size_t)b * p.L_max;
     const int32_t* const partner = p.partner + row;
@@ -202,9 +199,7 @@ __global__ __launch_bounds__(kMergeThreads) void merge_fuse_kernel(const MergeFu
     const int np = s_np;
     MergeCounts cnt = {0, 0, 0.0, 0.0};
     if (np > 0) {
-        ST* const Pb = static_cast<ST*>(p.P) + (size_t)b * p.pstride;
-        ST* const xb = static_cast<ST*>(p.x) + (size_t)b * p.xstride;
-        cnt = merge_fuse_instance(MergeGroup(), Pb, xb, M, s_pi, s_pj, np, p.sigma2, s_ws, p.remove + row, p.seen ? p.seen + row : nullptr,
+        cnt = merge_fuse_instance(MergeGroup(), aux_row<ST>(p.P, b, p.pstride), aux_row<ST>(p.x, b, p.xstride), M, s_pi, s_pj, np, p.sigma2, s_ws, p.remove + row, p.seen ? p.seen + row : nullptr,
                                   p.expected ? p.expected + row : nullptr);
     }
     if (tid == 0) {
@@ -223,30 +218,25 @@ __global__ __launch_bounds__(kMergeThreads) void merge_fuse_kernel(const MergeFu
     }
 }
 
-__global__ __launch_bounds__(256) void merge_work_kernel(const int32_t* __restrict__ M, const int32_t* __restrict__ find_on,
-                                                         const int32_t* __restrict__ n_attempted, const int32_t* __restrict__ n_fused, size_t n,
-                                                         int L_max, int counters, unsigned long long* __restrict__ work) {
-    unsigned long long a0 = 0, a1 = 0;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        int m = M[i];
-        m = m < 0 ? 0 : (m > L_max ? L_max : m);
-        const MergeTraffic t = merge_traffic(m, find_on ? find_on[i] : 0, n_attempted[i], n_fused[i], L_max, counters != 0);
-        a0 += t.elems; a1 += t.other_bytes;
+// element i of the traffic model's sum: one instance of one call
+struct MergeWorkTerms {
+    const int32_t *M, *find_on, *n_attempted, *n_fused;
+    int L_max, counters;
+    __device__ void operator()(size_t i, unsigned long long (&t)[2]) const {
+        const MergeTraffic w = merge_traffic(aux_clamp_m(M[i], L_max), find_on ? find_on[i] : 0, n_attempted[i], n_fused[i], L_max, counters != 0);
+        t[0] = w.elems; t[1] = w.other_bytes;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { a0 += __shfl_down(a0, off, 64); a1 += __shfl_down(a1, off, 64); }
-    if (threadIdx.x % 64 == 0) { atomicAdd(work, a0); atomicAdd(work + 1, a1); }
-}
+};
 
-bool merge_shape_ok(int B, int L_max, int pstride, int xstride, int esz) {
-    const int n_max = 3 + 2 * L_max;
-    return B > 0 && L_max > 0 && L_max <= kMapMaxLandmarks && xstride >= n_max && (long long)pstride >= (long long)n_max * ekf_ld(n_max, esz);
+// the shape of a handle the find and the fusion take
+bool merge_shape_ok(int B, int L_max, int pstride, int xstride, int f32_storage) {
+    return aux_shape_ok(B, L_max, xstride, pstride, f32_storage) && L_max > 0 && L_max <= kMapMaxLandmarks;
 }
 
 }  // namespace
 
 hipError_t launch_merge_find(const MergeFindParams& p, int f32_storage, hipStream_t stream) {
-    if (!merge_shape_ok(p.B, p.L_max, p.pstride, p.xstride, f32_storage ? 4 : 8) || !p.P || !p.x || !p.M || !p.status || !p.partner || !p.n_notmutual)
+    if (!merge_shape_ok(p.B, p.L_max, p.pstride, p.xstride, f32_storage) || !p.P || !p.x || !p.M || !p.status || !p.partner || !p.n_notmutual)
         return hipErrorInvalidValue;
     const int npad = (3 + 2 * p.L_max) | 1;          // odd: the transposing stores of a row segment spread over the banks
     int TP = kMergePanelBytes / (32 * npad);
@@ -277,7 +267,7 @@ hipError_t launch_merge_find(const MergeFindParams& p, int f32_storage, hipStrea
 }
 
 hipError_t launch_merge_fuse(const MergeFuseParams& p, int f32_storage, hipStream_t stream) {
-    if (!merge_shape_ok(p.B, p.L_max, p.pstride, p.xstride, f32_storage ? 4 : 8) || !p.P || !p.x || !p.M || !p.status || !p.partner || !p.remove ||
+    if (!merge_shape_ok(p.B, p.L_max, p.pstride, p.xstride, f32_storage) || !p.P || !p.x || !p.M || !p.status || !p.partner || !p.remove ||
         !p.n_fused || !p.n_attempted || (p.rec && (!p.inst_rec || !p.partials)) || (p.seen == nullptr) != (p.expected == nullptr))
         return hipErrorInvalidValue;
     const size_t lds = sizeof(double) * (4 * (size_t)(3 + 2 * p.L_max) + 2);
@@ -286,21 +276,15 @@ hipError_t launch_merge_fuse(const MergeFuseParams& p, int f32_storage, hipStrea
         const hipError_t e = slam_allow_full_lds(fn);
         if (e != hipSuccess) return e;
     }
-    (void)hipGetLastError();
-    if (f32_storage) hipLaunchKernelGGL(merge_fuse_kernel<float>, dim3(p.B), dim3(kMergeThreads), lds, stream, p);
-    else hipLaunchKernelGGL(merge_fuse_kernel<double>, dim3(p.B), dim3(kMergeThreads), lds, stream, p);
-    const hipError_t e = hipGetLastError();
+    const hipError_t e = aux_launch(f32_storage, merge_fuse_kernel<float>, merge_fuse_kernel<double>, dim3(p.B), dim3(kMergeThreads), lds, stream, p);
     if (e != hipSuccess || !p.rec) return e;
-    return launch_innovation_reduce(p.inst_rec, p.B, p.partials, p.rec, stream);
+    return launch_record_reduce<kMergeRecMax>(p.inst_rec, p.B, p.partials, p.rec, stream);
 }
 
 hipError_t launch_merge_work(const int32_t* M, const int32_t* find_on, const int32_t* n_attempted, const int32_t* n_fused, size_t n, int L_max,
                              int counters, unsigned long long* work, hipStream_t stream) {
-    if (!M || !n_attempted || !n_fused || !work || n == 0) return hipErrorInvalidValue;
-    const size_t want = (n + 255) / 256;
-    hipLaunchKernelGGL(merge_work_kernel, dim3((unsigned)(want < 256 ? want : 256)), dim3(256), 0, stream, M, find_on, n_attempted, n_fused, n,
-                       L_max, counters, work);
-    return hipGetLastError();
+    if (!M || !n_attempted || !n_fused) return hipErrorInvalidValue;
+    return launch_work_sum<2>(MergeWorkTerms{M, find_on, n_attempted, n_fused, L_max, counters}, n, work, stream);
 }
 
 }  // namespace slam

@@ -22,17 +22,20 @@
 #include <stdint.h>
 
 #include "slam_math.h"
+#if defined(__HIPCC__)
+#include "record_kernel.h"
+#endif
 
 namespace slam {
 
 constexpr int kMonRecLen = 16;     // doubles of one record
-constexpr int kMonBlock = 256;     // instances one workgroup reduces
 
 // indices of a record (counts are stored as doubles); sums and maxima run over the counted instances, a maximum over none is 0
 enum MonitorRec {
     kMonOk = 0, kMonFailed = 1, kMonNees = 2, kMonPoseNotPd = 3, kMonSumPos = 4, kMonSumPos2 = 5, kMonMaxPos = 6, kMonSumYaw2 = 7,
     kMonMaxYaw = 8, kMonSumNees = 9, kMonBelow = 10, kMonAbove = 11, kMonSumM = 12, kMonFull = 13, kMonSumFull = 14, kMonSumDof = 15
 };
+constexpr unsigned kMonRecMax = (1u << kMonMaxPos) | (1u << kMonMaxYaw);   // the entries joined by a maximum (record_kernel.h)
 
 constexpr int32_t kMonFlagPoseNotPd = 2, kMonFlagFailed = 8;   // SLAM_CONSISTENCY_POSE_NOT_PD, SLAM_CONSISTENCY_INSTANCE_FAILED
 constexpr int32_t kMonStatusDead = 1 | 32;                     // SLAM_INST_NONFINITE | SLAM_INST_WATCHDOG: the state is undefined
@@ -104,10 +107,9 @@ struct MonitorParams {
     const double* nees_full;  // [B] of a launch_consistency that ran before on the stream, with dof [B]; NULL: entries 13 - 15 are 0
     const int32_t* dof;
     double* err_pos; double* err_yaw; double* nees_pose; int32_t* flags;   // [B] each, any may be NULL
-    double* partials;         // [monitor_blocks(B)][kMonRecLen]
+    double* partials;         // [record_blocks(B)][kMonRecLen]
     double* rec;              // [kMonRecLen]
 };
-inline int monitor_blocks(int B) { return (B + kMonBlock - 1) / kMonBlock; }
 hipError_t launch_monitor(const MonitorParams& p, int f32_storage, hipStream_t stream);
 #endif
 

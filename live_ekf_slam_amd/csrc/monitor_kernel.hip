@@ -5,13 +5,13 @@
 // 171 KB its timestep moves at L = 50, followed by some fifty dependent fp64 operations with three square roots and six divisions.  There is
 // nothing for the lanes of a wavefront to share and nothing to stage, so the kernel is bound by the latency of its loads, and the batch's
 // 256 workgroups (B = 65 536) fill the device once.
-// Reduction: every workgroup reduces the sixteen entries of the record over its 256 consecutive instances by a fixed tree (shuffles within a
-// wavefront, then the four wavefronts in order) and writes one partial record; a second launch of one workgroup adds the partials in
-// ascending order.  No atomics on values: the order of every sum depends on B alone.
+// Reduction: every workgroup ends in record_block_tree (record_kernel.h) over its 256 consecutive instances and writes one partial record,
+// fused with the evaluation; launch_record_total then joins the partials in ascending order.  The join mask is kMonRecMax (entries
+// kMonMaxPos and kMonMaxYaw are maxima).  No atomics on values: the order of every sum depends on B alone.
 #include <hip/hip_runtime.h>
 
 #include "../../include/slam_batch.h"
-#include "ekf_kernel.h"
+#include "aux_device.h"
 #include "monitor_kernel.h"
 
 namespace slam {
@@ -19,24 +19,18 @@ namespace {
 
 static_assert(kMonFlagPoseNotPd == SLAM_CONSISTENCY_POSE_NOT_PD && kMonFlagFailed == SLAM_CONSISTENCY_INSTANCE_FAILED, "monitor flags are slam_consistency_flags");
 static_assert(kMonStatusDead == (SLAM_INST_NONFINITE | SLAM_INST_WATCHDOG), "the status bits that leave an undefined state");
-static_assert(kMonBlock % 64 == 0, "whole wavefronts");
-
-constexpr int kMonWaves = kMonBlock / 64;
-
-__device__ __forceinline__ bool rec_is_max(int i) { return i == kMonMaxPos || i == kMonMaxYaw; }
-__device__ __forceinline__ double rec_join(int i, double a, double b) { return rec_is_max(i) ? (b > a ? b : a) : a + b; }
+static_assert(kMonRecLen == kRecLen, "the record record_block_tree takes");
 
 template <class ST>
-__global__ __launch_bounds__(kMonBlock) void monitor_tick_kernel(const MonitorParams p) {
-    __shared__ double s_part[kMonWaves][kMonRecLen];
-    const int b = blockIdx.x * kMonBlock + threadIdx.x;
+__global__ __launch_bounds__(kRecBlock) void monitor_tick_kernel(const MonitorParams p) {
+    __shared__ double s_part[kRecBlock / 64][kRecLen];
+    const int b = blockIdx.x * kRecBlock + threadIdx.x;
     double r[kMonRecLen];
 #pragma unroll
     for (int i = 0; i < kMonRecLen; ++i) r[i] = 0.0;
     if (b < p.B) {
-        int m = p.M[b];
-        m = m < 0 ? 0 : (m > p.L_max ? p.L_max : m);
-        const ST* __restrict__ xb = static_cast<const ST*>(p.x) + (size_t)b * p.xstride;
+        const int m = aux_clamp_m(p.M[b], p.L_max);
+        const ST* __restrict__ xb = aux_row<ST>(p.x, b, p.xstride);
         double x[4], P3[9], truth[3];
         x[0] = (double)xb[0]; x[1] = (double)xb[1]; x[2] = (double)xb[2];
         x[3] = p.ukf ? (double)xb[3] : 0.0;                                 // (xstride >= 4 for every kind)
@@ -44,7 +38,7 @@ __global__ __launch_bounds__(kMonBlock) void monitor_tick_kernel(const MonitorPa
         for (int i = 0; i < 9; ++i) P3[i] = 0.0;
         if (!p.ukf) {                                                       // rows 0 .. 2 of P_t: 3 <= ld, 3 ld <= pstride
             const int ld = ekf_ld(3 + 2 * m, (int)sizeof(ST));
-            const ST* __restrict__ Pb = static_cast<const ST*>(p.P) + (size_t)b * p.pstride;
+            const ST* __restrict__ Pb = aux_row<ST>(p.P, b, p.pstride);
 #pragma unroll
             for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -76,32 +70,8 @@ __global__ __launch_bounds__(kMonBlock) void monitor_tick_kernel(const MonitorPa
             if (mon_finite(nf)) { r[kMonFull] = 1.0; r[kMonSumFull] = nf; r[kMonSumDof] = (double)p.dof[b]; }
         }
     }
-    // lane 0 of every wavefront ends with the tree over its 64 lanes (a lane past the batch contributes zeros, which change no sum of
-    // non-negative terms and no maximum)
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-        for (int i = 0; i < kMonRecLen; ++i) r[i] = rec_join(i, r[i], __shfl_down(r[i], off, 64));
-    const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-    if (lane == 0)
-#pragma unroll
-        for (int i = 0; i < kMonRecLen; ++i) s_part[wave][i] = r[i];
-    __syncthreads();
-    if (threadIdx.x < kMonRecLen) {
-        const int i = threadIdx.x;
-        double a = s_part[0][i];
-        for (int w = 1; w < kMonWaves; ++w) a = rec_join(i, a, s_part[w][i]);
-        p.partials[(size_t)blockIdx.x * kMonRecLen + i] = a;
-    }
-}
-
-// the partial records in ascending order of their workgroups: one lane per entry
-__global__ __launch_bounds__(64) void monitor_sum_kernel(const double* __restrict__ partials, int blocks, double* __restrict__ rec) {
-    const int i = threadIdx.x;
-    if (i >= kMonRecLen) return;
-    double a = partials[i];
-    for (int k = 1; k < blocks; ++k) a = rec_join(i, a, partials[(size_t)k * kMonRecLen + i]);
-    rec[i] = a;
+    // (a lane past the batch contributes zeros, which change no sum of non-negative terms and no maximum)
+    record_block_tree(r, kMonRecMax, s_part, p.partials + (size_t)blockIdx.x * kRecLen);
 }
 
 }  // namespace
@@ -109,14 +79,10 @@ __global__ __launch_bounds__(64) void monitor_sum_kernel(const double* __restric
 hipError_t launch_monitor(const MonitorParams& p, int f32_storage, hipStream_t stream) {
     if (p.B <= 0 || !p.partials || !p.rec || p.xstride < 4 || (!p.ukf && p.pstride < 3 * ekf_ld(3 + 2 * p.L_max, f32_storage ? 4 : 8)))
         return hipErrorInvalidValue;
-    const int blocks = monitor_blocks(p.B);
-    (void)hipGetLastError();   // sticky and per thread: only these launches' errors are reported (capi_internal.h)
-    if (f32_storage) hipLaunchKernelGGL(monitor_tick_kernel<float>, dim3(blocks), dim3(kMonBlock), 0, stream, p);
-    else hipLaunchKernelGGL(monitor_tick_kernel<double>, dim3(blocks), dim3(kMonBlock), 0, stream, p);
-    hipError_t e = hipGetLastError();
+    const int blocks = record_blocks(p.B);
+    const hipError_t e = aux_launch(f32_storage, monitor_tick_kernel<float>, monitor_tick_kernel<double>, dim3(blocks), dim3(kRecBlock), 0, stream, p);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(monitor_sum_kernel, dim3(1), dim3(64), 0, stream, p.partials, blocks, p.rec);
-    return hipGetLastError();
+    return launch_record_total<kMonRecMax>(p.partials, blocks, p.rec, stream);
 }
 
 }  // namespace slam

@@ -41,13 +41,14 @@ constexpr int kSenseRecLen = 16;
 constexpr uint32_t kSenseFaultPair = 0x40000000u;                 // F: the first pair index of the fault draws
 constexpr uint32_t kSenseNanBits = 0x7FC00000u;                   // the erased id
 constexpr int32_t kSenseFrozen = 1, kSenseTooLong = 2;            // slam_sense_flags
-static_assert(kSenseMaxDet == kInnovMaxDet && kSenseRecLen == kInnovRecLen, "one message limit and one record length");
+static_assert(kSenseMaxDet == kInnovMaxDet, "one message limit");
 
 // indices of a record (counts are stored as doubles)
 enum SenseRec {
     kSenSensed = 0, kSenFrozen = 1, kSenTooLong = 2, kSenClean = 3, kSenMissed = 4, kSenSpiked = 5, kSenClutter = 6, kSenOut = 7,
     kSenOverflow = 8, kSenSpikeSum = 9, kSenCommitted = 10, kSenErrSum = 11
 };
+constexpr unsigned kSenseRecMax = 0u;                               // no entry is joined by a maximum (record_kernel.h): every one is a sum
 
 // the simulator's configuration of one instance: what sim_wave reads from its parameter block and the instance's half-widths
 struct SenseSim { uint64_t seed; uint64_t g; double d_max, th_max, range_max, fov_min, fov_max, sV00, sV11, sW00, sW11; };
@@ -257,7 +258,7 @@ struct SenseParams {
     double* truth_next;          // [B][3] staged true pose (a frozen instance: its pose as it is)
     int32_t* staged_ts;          // [B] the timestep the message was made at (a frozen instance: -2, which no step reaches)
     double* inst_rec;            // [B][kSenseRecLen]
-    double* partials;            // [innovation_blocks(B)][kSenseRecLen]
+    double* partials;            // [record_blocks(B)][kSenseRecLen]
     double* rec;                 // [kSenseRecLen] or NULL: no reduction
 };
 hipError_t launch_sense(const SenseParams& p, hipStream_t stream);
@@ -274,10 +275,6 @@ struct SenseCommitParams {
     double* inst_rec; double* partials; double* rec;
 };
 hipError_t launch_sense_commit(const SenseCommitParams& p, hipStream_t stream);
-
-// The two reduction launches of the above alone, for another record of kSenseRecLen doubles whose every entry is a sum (fix_kernel.hip):
-// inst_rec [B][kSenseRecLen] -> partials [innovation_blocks(B)][kSenseRecLen] -> rec [kSenseRecLen], in the same fixed order.
-hipError_t launch_record_sum(const double* inst_rec, int B, double* partials, double* rec, hipStream_t stream);
 #endif
 
 }  // namespace slam

@@ -6,12 +6,12 @@
 // takes the candidates i and i + 64 of the fault model.  Phases are ordered by wavefront fences: the wavefronts of a workgroup share
 // nothing, there is no workgroup barrier.  An instance reads its map (16 L bytes), its pose, its noise and sensor rows and writes
 // 12 k_stride bytes of message (8 k_stride more with both label rows), its staged pose and a record of 128 bytes.
-// Commit: one thread per instance.  Record: 256 consecutive instances per workgroup by a fixed tree, the workgroups in ascending order:
+// Commit: one thread per instance.  Record: launch_record_reduce (record_kernel.h) with the join mask kSenseRecMax, every entry a sum:
 // no atomics, the order of every sum depends on the batch size alone.
 #include <hip/hip_runtime.h>
 
+#include "aux_device.h"
 #include "sense_kernel.h"
-#include "sim_device.h"
 
 namespace slam {
 namespace {
@@ -21,7 +21,7 @@ static_assert(kSenseMaxDet == SLAM_SENSE_MAX_DET && kSenseMaxClutter == SLAM_SEN
 static_assert(kInnovStatusFrozen == SLAM_INST_INDEX_OOR, "the status bit the step kernel returns on");
 
 constexpr int kSenseWaves = 4;                      // instances per workgroup of the instance kernel
-constexpr int kRedWaves = kInnovBlock / 64;
+static_assert(kSenseRecLen == kRecLen, "the record launch_record_reduce takes");
 static_assert(sizeof(SenseWork) * kSenseWaves <= 64 * 1024, "static LDS of a workgroup");
 
 __global__ __launch_bounds__(64 * kSenseWaves) void sense_instance_kernel(const SenseParams p) {
@@ -42,12 +42,11 @@ __global__ __launch_bounds__(64 * kSenseWaves) void sense_instance_kernel(const 
     if (s.flags[b] & kInnovStatusFrozen) {
         v = sense_frozen(w, ks, mo, org, flt);
     } else {
-        const float* const cp = s.cmd_each ? s.cmd_each + 2 * (size_t)b : nullptr;
-        const float fwd = cp ? cp[0] : s.fwd, ang = cp ? cp[1] : s.ang;
+        const AuxCommand c = aux_command(s, b);
         const int Lm = sim_map_size(s, b);
         const double* const map = sim_map(s, b);
         const double lmx0 = lane < Lm ? map[2 * lane] : 0.0, lmy0 = lane < Lm ? map[2 * lane + 1] : 0.0;
-        const int c_vis = sim_wave<kSenseMaxDet, false>(s, b, lane, fwd, ang, s.step, map, Lm, tx, ty, tth, lmx0, lmy0, ws.meas, sim_noise(s, b));
+        const int c_vis = sim_wave<kSenseMaxDet, false>(s, b, lane, c.fwd, c.ang, s.step, map, Lm, tx, ty, tth, lmx0, lmy0, ws.meas, sim_noise(s, b));
         w.sync();
         const slam_sensor row = p.rows ? p.rows[b] : sense_default_row();
         v = sense_instance(w, ws, row, s.seed, (uint64_t)(s.inst0 + b), s.step, c_vis, Lm, s.range_max, s.fov_min, s.fov_max, ks, mo, org, flt);
@@ -73,7 +72,7 @@ __global__ __launch_bounds__(256) void sense_commit_kernel(const SenseCommitPara
     const double tx = src[0], ty = src[1], tth = src[2];
     double e = 0.0;
     if (commit) {
-        const ST* const xb = static_cast<const ST*>(p.x) + (size_t)b * p.xstride;
+        const ST* const xb = aux_row<ST>(p.x, b, p.xstride);
         p.truth[3 * (size_t)b] = tx; p.truth[3 * (size_t)b + 1] = ty; p.truth[3 * (size_t)b + 2] = tth;
         e = ekf_position_error((double)xb[0], (double)xb[1], tx, ty);
         p.err_sum[b] = p.err_sum[b] + e;
@@ -84,55 +83,7 @@ __global__ __launch_bounds__(256) void sense_commit_kernel(const SenseCommitPara
     p.inst_rec[(size_t)b * kSenseRecLen + kSenErrSum] = e;
 }
 
-// one lane per instance: the records of 256 consecutive instances by a fixed tree into one partial record (every entry is a sum)
-__global__ __launch_bounds__(kInnovBlock) void sense_reduce_kernel(const double* __restrict__ inst_rec, int B, double* __restrict__ partials) {
-    __shared__ double s_part[kRedWaves][kSenseRecLen];
-    const int b = blockIdx.x * kInnovBlock + threadIdx.x;
-    double r[kSenseRecLen];
-#pragma unroll
-    for (int i = 0; i < kSenseRecLen; ++i) r[i] = b < B ? inst_rec[(size_t)b * kSenseRecLen + i] : 0.0;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-        for (int i = 0; i < kSenseRecLen; ++i) r[i] = r[i] + __shfl_down(r[i], off, 64);
-    const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-    if (lane == 0)
-#pragma unroll
-        for (int i = 0; i < kSenseRecLen; ++i) s_part[wave][i] = r[i];
-    __syncthreads();
-    if (threadIdx.x < kSenseRecLen) {
-        const int i = threadIdx.x;
-        double a = s_part[0][i];
-        for (int wv = 1; wv < kRedWaves; ++wv) a = a + s_part[wv][i];
-        partials[(size_t)blockIdx.x * kSenseRecLen + i] = a;
-    }
-}
-
-// the partial records in ascending order of their workgroups: one lane per entry
-__global__ __launch_bounds__(64) void sense_sum_kernel(const double* __restrict__ partials, int blocks, double* __restrict__ rec) {
-    const int i = threadIdx.x;
-    if (i >= kSenseRecLen) return;
-    double a = partials[i];
-    for (int k = 1; k < blocks; ++k) a = a + partials[(size_t)k * kSenseRecLen + i];
-    rec[i] = a;
-}
-
-hipError_t sense_reduce(const double* inst_rec, int B, double* partials, double* rec, hipStream_t stream) {
-    const int blocks = innovation_blocks(B);
-    hipLaunchKernelGGL(sense_reduce_kernel, dim3(blocks), dim3(kInnovBlock), 0, stream, inst_rec, B, partials);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(sense_sum_kernel, dim3(1), dim3(64), 0, stream, partials, blocks, rec);
-    return hipGetLastError();
-}
-
 }  // namespace
-
-hipError_t launch_record_sum(const double* inst_rec, int B, double* partials, double* rec, hipStream_t stream) {
-    if (B <= 0 || !inst_rec || !partials || !rec) return hipErrorInvalidValue;
-    (void)hipGetLastError();
-    return sense_reduce(inst_rec, B, partials, rec, stream);
-}
 
 hipError_t launch_sense(const SenseParams& p, hipStream_t stream) {
     const EkfStepParams& s = p.s;
@@ -144,20 +95,17 @@ hipError_t launch_sense(const SenseParams& p, hipStream_t stream) {
     hipLaunchKernelGGL(sense_instance_kernel, dim3(groups), dim3(64 * kSenseWaves), 0, stream, p);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || !p.rec) return e;
-    return sense_reduce(p.inst_rec, s.B, p.partials, p.rec, stream);
+    return launch_record_reduce<kSenseRecMax>(p.inst_rec, s.B, p.partials, p.rec, stream);
 }
 
 hipError_t launch_sense_commit(const SenseCommitParams& p, hipStream_t stream) {
     if (p.B <= 0 || !p.x || p.xstride < 3 || !p.timestep || !p.staged_ts || !p.truth || !p.truth_next || !p.err_sum || !p.inst_rec ||
         (p.rec && !p.partials))
         return hipErrorInvalidValue;
-    (void)hipGetLastError();
-    const dim3 grid((p.B + 255) / 256);
-    if (p.f32_storage) hipLaunchKernelGGL(sense_commit_kernel<float>, grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(sense_commit_kernel<double>, grid, dim3(256), 0, stream, p);
-    const hipError_t e = hipGetLastError();
+    const hipError_t e = aux_launch(p.f32_storage, sense_commit_kernel<float>, sense_commit_kernel<double>, dim3((p.B + 255) / 256), dim3(256), 0,
+                                    stream, p);
     if (e != hipSuccess || !p.rec) return e;
-    return sense_reduce(p.inst_rec, p.B, p.partials, p.rec, stream);
+    return launch_record_reduce<kSenseRecMax>(p.inst_rec, p.B, p.partials, p.rec, stream);
 }
 
 }  // namespace slam

@@ -35,6 +35,13 @@
 #endif
 
 namespace slam {
+// Leading dimension (in elements) of the row-major covariance of an EKF instance with state size n: every row starts on a
+// 16-byte boundary (2 doubles / 4 floats), so one lane's 16-byte vector never straddles two rows and the bulk stream
+// can hand a lane the same column group in several consecutive rows (its (H P) operands are then read once per strip
+// instead of once per element).  The pad elements (columns n .. ld-1) are kept at zero.  Here, not in ekf_kernel.h, because the
+// per-instance definitions that are also built for the host without HIP headers (map, merge, fix) need it too.
+SLAM_HD constexpr int ekf_ld(int n, int elem_bytes) { return elem_bytes == 8 ? ((n + 1) & ~1) : ((n + 3) & ~3); }
+
 // |d| as the unknown-id association of ekf.cpp:91-92 sees it: the double overload of abs (as_int = 0), or - if the unqualified `abs`
 // resolves to ::abs(int) - the value truncated to an int first (out-of-range values saturate, here and in the oracle alike).
 #if defined(__HIPCC__)

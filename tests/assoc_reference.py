@@ -146,6 +146,22 @@ def reference_associate(case, cost, nu, cfg=None):
                 n_drop=cnt[AMBIGUOUS] + cnt[CONFLICT] + cnt[NO_ROOM] + cnt[INVALID], flags=0, rec=rec)
 
 
+def model_work(M, k, flags, esz):
+    """slam_last_associate_work's model restated in Python integers (assoc_traffic of csrc/assoc_kernel.h summed over the instances): per
+    instance M landmarks, k = n_match + n_new + n_drop detections and its flags.  Returns (bytes, the same with the reads of P in
+    128-byte lines).  An instance that emits an empty message (any flag) contributes (0, 8, 0): its counts."""
+    p_elems = other = p_lines = 0
+    for m, kk, fl in zip(M, k, flags):
+        if int(fl):
+            other += 8
+            continue
+        m, n = int(m), 3 + 2 * int(m)
+        p_elems += 3 * n + 10 * m                                 # rows 0 - 2 whole; per landmark P[ii .. ii + 1][0 .. 2] and the 2 x 2 diagonal block
+        other += n * esz + 4 * m + 24 * int(kk) + 8               # x, ids, the message in and out, the count in and out
+        p_lines += 3 * ((n * esz + 127) // 128) + 4 * m
+    return p_elems * esz + other, 128 * p_lines + other
+
+
 def same_bits(a, b):
     a, b = np.ravel(np.asarray(a, dtype=np.float64)), np.ravel(np.asarray(b, dtype=np.float64))
     return a.shape == b.shape and not ((a.view(np.uint64) != b.view(np.uint64)) & ~(np.isnan(a) & np.isnan(b))).any()

@@ -15,7 +15,8 @@ import pytest
 
 import assoc_reference as AR
 import innovation_reference as IR
-from test_gate_gpu import _Dev, _fixed_order_record, _same_bits
+from record_tree import MAX_ENTRY_8, fixed_order_record
+from test_gate_gpu import _Dev, _same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -157,7 +158,7 @@ def _check_against_hooks(r, hooks, meas_out, count_out, meas, cnt, what):
         if not same:
             wrong.append((b, int(r["flags"][b]), h["flags"], int(r["n_match"][b]), h["n_match"], int(count_out[b]), h["count_out"]))
     assert not wrong, f"{what}: {len(wrong)} instance(s) differ from the host hook (b, flags dev/host, n_match dev/host, count_out dev/host): {wrong[:10]}"
-    rec = _fixed_order_record(np.stack([h["rec"] for h in hooks]))
+    rec = fixed_order_record(np.stack([h["rec"] for h in hooks]), MAX_ENTRY_8)
     assert _same_bits(rec, r["rec"]), (what, "the record against the fixed-order join of the hook's records", rec, r["rec"])
 
 
@@ -206,7 +207,9 @@ def test_associate_against_the_hook_and_the_associated_step_against_the_plain_st
     assert set(np.unique(r["verdict"]).tolist()) == set(range(7)), np.unique(r["verdict"])
     assert r["rec"][4] == r["n_match"].sum() > B and r["rec"][5] == r["n_new"].sum() > 0 and r["rec"][3] > 2 * B
     by, lines, _, _ = a.last_associate_work()
-    assert 0 < by and 0 < lines
+    model = AR.model_work([a.get_state(b)["M"] for b in range(B)], r["n_match"] + r["n_new"] + r["n_drop"], r["flags"], 4 if dtype32 else 8)
+    print(f"{what}: slam_last_associate_work (bytes, lines) = {(by, lines)}, the model in Python integers = {model}")
+    assert 0 < by and 0 < lines and (by, lines) == model, (what, "the traffic model summed on the device against its restatement", by, lines, model)
     # the host form gives the same, and changes nothing either
     rh = a.associate(cmds, meas, cnt)
     a.save_state(after)

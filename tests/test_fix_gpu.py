@@ -20,10 +20,11 @@ import pytest
 import assoc_reference as AR
 import fix_reference as FR
 import innovation_reference as IR
+from record_tree import ALL_SUMS, fixed_order_record
 from test_assoc_gpu import B, _config
 from test_gate_gpu import _Dev, _same_bits
 from test_map_gpu import S, hip, _each, _grown, _items, _raw, _same_state  # noqa: F401
-from test_sense_gpu import PATH, W, _saved, _sum_record  # noqa: F401
+from test_sense_gpu import PATH, W, _saved  # noqa: F401
 from test_sense_gpu import _handle as _sim_handle
 
 pytestmark = pytest.mark.gpu
@@ -76,7 +77,7 @@ def _check_fix(S, f, r, before, status, hooks, after, f32, what):
     assert _same_bits(r["nis"], np.stack([h["nis"] for h in hooks])), what
     wrong = [b for b in range(n) if not _same_state(after[b], dict(x=hooks[b]["x"], P=hooks[b]["P"], M=before[b]["M"], ids=before[b]["ids"]))]
     assert not wrong, f"{what}: {len(wrong)} instance(s) differ from the hook's state: {wrong[:10]}"
-    assert _same_bits(_sum_record(np.stack([h["rec"] for h in hooks])), r["rec"]), (what, r["rec"])
+    assert _same_bits(fixed_order_record(np.stack([h["rec"] for h in hooks]), ALL_SUMS), r["rec"]), (what, r["rec"])
     by, fix_ms, total_ms = f.last_fix_work()
     assert by == FR.model_bytes([st["M"] for st in before], hv, 4 if f32 else 8) and fix_ms == -1.0 and total_ms == -1.0, (what, by)
     return hv
@@ -185,6 +186,43 @@ def test_a_map_of_more_than_256_landmarks(S, f32):
     hooks = _hooks(S, before, status, L_max, f32, fix, kinds)
     hv = _check_fix(S, f, r, before, status, hooks, after, f32, "L300")
     assert hv.tolist() == [0x01, 0x10, 0x11]
+    f.close()
+
+
+def test_a_batch_one_past_the_work_sums_launch(S):
+    """B = 65 537, L_max = 1 with its landmark mapped, a position fix on every instance: the work sum (csrc/aux_device.h) launches
+    256 x 256 lanes, so this is the smallest batch at which a lane - lane 0 - takes a second element of its grid-stride loop, and the
+    record tree (csrc/record_kernel.h) joins 257 partial records.  Every instance is stepped alike into the same state, so the hook is
+    evaluated once per kind of fix row (applied, rejected, invalid: b % 3; the last instance is a rejected one, whose traffic differs from
+    its neighbours'); the bytes of slam_last_fix_work equal the model exactly and the record equals the restated tree in bits."""
+    nb, L_max = 65537, 1
+    f = S.BatchedEKF(nb, L_max).readParams(_config(S))
+    f.set_seed(11); f.init(0.3, -0.2, 0.4)
+    m = np.tile(np.array([[[100.0, 2.0, 0.1]]], np.float32), (nb, 1, 1))
+    for _ in range(2):                                               # the insertion, then an update
+        f.update((0.02, 0.01), m, np.ones(nb, np.int32))
+    probe = (0, 1, 2, 255, 256, 65535, 65536)
+    before = {b: f.get_state(b) for b in probe}
+    st = before[0]
+    assert not f.status().any() and all(s["M"] == 1 and _same_state(s, st) for s in before.values())
+    rng = np.random.default_rng(5)
+    rows3 = np.stack([_fix_row(rng, st["x"], how) for how in ("near", "far_pos", "nan_sigma")])
+    which = np.arange(nb) % 3
+    kinds = np.ones(nb, np.int32)
+    r = f.fix(rows3[which], kinds)
+    hooks3 = _hooks(S, [st] * 3, np.zeros(3, np.int32), L_max, False, rows3, kinds[:3])
+    hv3 = np.array([h["verdict"] for h in hooks3], np.int32)
+    assert hv3.tolist() == [0x01, 0x02, 0x04], hv3                      # applied, rejected, invalid
+    assert np.array_equal(r["verdict"], hv3[which]) and _same_bits(r["nis"], np.stack([h["nis"] for h in hooks3])[which])
+    want = fixed_order_record(np.stack([h["rec"] for h in hooks3])[which], ALL_SUMS)
+    by = f.last_fix_work()[0]
+    model = FR.model_bytes(np.ones(nb, np.int64), hv3[which], 8)
+    print(f"B = {nb}: slam_last_fix_work bytes {by}, the model {model}; record {r['rec']}")
+    assert by == model, (by, model)
+    assert _same_bits(want, r["rec"]) and r["rec"][2] == (which == 0).sum() and r["rec"][3] == (which == 1).sum(), (want, r["rec"])
+    for b in probe:
+        h = hooks3[b % 3]
+        assert _same_state(f.get_state(b), dict(x=h["x"], P=h["P"], M=1, ids=st["ids"])), b
     f.close()
 
 

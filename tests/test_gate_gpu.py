@@ -12,6 +12,7 @@ import pytest
 
 import gate_reference as GR
 import innovation_reference as IR
+from record_tree import MAX_ENTRY_8, fixed_order_record
 
 pytestmark = pytest.mark.gpu
 
@@ -160,32 +161,6 @@ def _same_bits(a, b):
     return not ((a.view(np.uint64) != b.view(np.uint64)) & ~(np.isnan(a) & np.isnan(b))).any()
 
 
-def _join(a, b):
-    r = a + b
-    r[..., 8] = np.maximum(a[..., 8], b[..., 8])
-    return r
-
-
-def _fixed_order_record(inst):
-    """The reduction of innovation_reduce_kernel and innovation_sum_kernel restated: per 256 instances the shuffle tree of each wavefront
-    of 64 lanes (lane i joins lane i + off for off = 32 .. 1; a lane without a partner joins itself), the four wavefronts in order, then
-    the blocks in ascending order.  Instances past the batch contribute zeros."""
-    n = inst.shape[0]
-    blocks = (n + 255) // 256
-    pad = np.zeros((blocks * 256, 16)); pad[:n] = inst
-    rec = None
-    for blk in range(blocks):
-        part = None
-        for wv in range(4):
-            r = pad[blk * 256 + wv * 64: blk * 256 + (wv + 1) * 64].copy()
-            for off in (32, 16, 8, 4, 2, 1):
-                partner = np.concatenate([r[off:], r[64 - off:]])
-                r = _join(r, partner)
-            part = r[0] if part is None else _join(part, r[0])
-        rec = part if rec is None else _join(rec, part)
-    return rec
-
-
 def _check_against_hooks(r, hooks, meas_out, count_out, meas, cnt, what):
     wrong = []
     for b, h in enumerate(hooks):
@@ -198,7 +173,7 @@ def _check_against_hooks(r, hooks, meas_out, count_out, meas, cnt, what):
         if not same:
             wrong.append((b, int(r["flags"][b]), h["flags"], int(r["n_rej"][b]), h["n_rej"], int(count_out[b]), h["count_out"]))
     assert not wrong, f"{what}: {len(wrong)} instance(s) differ from the host hook (b, flags dev/host, n_rej dev/host, count_out dev/host): {wrong[:10]}"
-    rec = _fixed_order_record(np.stack([h["rec"] for h in hooks]))
+    rec = fixed_order_record(np.stack([h["rec"] for h in hooks]), MAX_ENTRY_8)
     assert _same_bits(rec, r["rec"]), (what, "the record against the fixed-order sum of the hook's records", rec, r["rec"])
 
 

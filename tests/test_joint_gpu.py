@@ -24,11 +24,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import assoc_reference as AR
 import innovation_reference as IR
 import joint_reference as JR
 import test_assoc_gpu as TA
 from test_assoc_gpu import S, hip  # noqa: F401  (fixtures)
-from test_gate_gpu import _Dev, _fixed_order_record, _same_bits
+from record_tree import MAX_ENTRY_8, fixed_order_record
+from test_gate_gpu import _Dev, _same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -119,7 +121,7 @@ def _check_against_hooks(r, hooks, meas_out, count_out, meas, cnt, what):
                           float(r["d2_joint"][b]), h["d2_joint"]))
     assert not wrong, (f"{what}: {len(wrong)} instance(s) differ from the host hook (b, flags dev/host, n_match dev/host, nodes dev/host, "
                        f"d2_joint dev/host): {wrong[:8]}")
-    rec = _fixed_order_record(np.stack([h["rec"] for h in hooks]))
+    rec = fixed_order_record(np.stack([h["rec"] for h in hooks]), MAX_ENTRY_8)
     assert _same_bits(rec, r["rec"]), (what, "the record against the fixed-order join of the hook's records", rec, r["rec"])
 
 
@@ -164,8 +166,16 @@ def test_joint_against_the_hook_and_the_joint_step_against_the_plain_step(S, hip
         assert all((meas_out[b, cin[b]:] == SENTINEL).all() for b in range(B)), "something was written from count_in up"
         assert r["rec"][4] == r["n_match"].sum() > B and r["rec"][12] == r["nodes"].sum() and r["n_match"].max() <= 16
         seen_verdicts |= set(np.unique(r["verdict"]).tolist()); seen_flags |= set(int(v) for v in r["flags"])
+        # the traffic model: the association's, plus four elements of P and one 128-byte line per on-demand block; the block count is
+        # not exposed, so both sums must leave the association's model by one and the same whole number of blocks
         by, lines, _, _ = a.last_joint_work()
-        assert 0 < by and 0 < lines
+        esz = 4 if dtype32 else 8
+        m_by, m_lines = AR.model_work([a.get_state(b)["M"] for b in range(B)], r["n_match"] + r["n_new"] + r["n_drop"],
+                                      r["flags"] & (IR.FROZEN | IR.TOO_LONG), esz)
+        print(f"{what}, {name}: slam_last_joint_work (bytes, lines) = {(by, lines)}, the association's model = {(m_by, m_lines)}")
+        n_blk = (int(by) - m_by) // (4 * esz)
+        assert 0 < by and 0 < lines and by == int(by) and lines == int(lines) and n_blk >= 0, (what, name, by, lines, m_by, m_lines)
+        assert int(by) - m_by == 4 * esz * n_blk and int(lines) - m_lines == 128 * n_blk, (what, name, by, lines, m_by, m_lines, n_blk)
         if name == "default":                       # the crafted cases on the device
             v, sl, fl = r["verdict"], r["slot"], r["flags"]
             with_cand = (r["ncand"] > 0).sum(axis=1)

@@ -50,7 +50,8 @@ from test_consistency_gpu import _write
 from test_fix_gpu import _check_fix, _fix_row
 from test_fix_gpu import _hooks as _fix_hooks
 from test_fix_reference import _state as _fix_state
-from test_gate_gpu import _fixed_order_record, _same_bits
+from record_tree import MAX_ENTRY_8, fixed_order_record
+from test_gate_gpu import _same_bits
 from test_map_gpu import S, _model_bytes, _same_state  # noqa: F401
 from test_merge_gpu import _hooks as _merge_hooks
 from test_merge_gpu import _merge_model_bytes
@@ -366,7 +367,7 @@ def test_duplicates_and_the_merge_at_every_kind_panel_depth_and_lds_branch(S, or
     assert not wrong, f"L_max {L_max}: instance(s) {wrong} differ from the hook's merged state"
     merged = np.array([before[b]["M"] - hooks[b]["M"] for b in range(nb)], dtype=np.int32)
     assert np.array_equal(r["n_merged"], merged) and merged.tolist() == [len(c[1]) + 1 for c in crafted] + [0]
-    assert _same_bits(_fixed_order_record(np.stack([h["rec"] for h in hooks])), r["rec"]), r["rec"]
+    assert _same_bits(fixed_order_record(np.stack([h["rec"] for h in hooks]), MAX_ENTRY_8), r["rec"]), r["rec"]
     assert r["rec"][0] == 3 and r["rec"][1] == merged.sum() and r["rec"][2] == ignored and r["rec"][3] == 0
     assert f.last_merge_work()[0] == _merge_model_bytes(before, status, hooks, L_max, esz, False, not by_pairs)
     _unmoved(raw0, raw1, ("flags", "timestep", "truth", "err"), range(nb), "slam_map_merge")
@@ -452,7 +453,7 @@ def test_tally_removal_and_prune_at_the_trip_edges_and_with_thousands_of_chunks(
     assert np.array_equal(r["n_removed"], removed) and removed.tolist() == [int(mask[b, :M].sum()) for b in range(nb)]
     n2 = 3 + 2 * np.array([h["M"] for h in hooks])
     inst = np.zeros((nb, 16)); inst[:, 0] = removed > 0; inst[:, 1] = removed; inst[:, 2] = np.where(removed > 0, n2.astype(np.float64) ** 2, 0.0)
-    assert _same_bits(_fixed_order_record(inst), r["rec"]), r["rec"]
+    assert _same_bits(fixed_order_record(inst, MAX_ENTRY_8), r["rec"]), r["rec"]
     assert f.last_map_work()[0] == _model_bytes([M] * nb, removed, L_max, esz, False, True)
     ds, de = f.map_track()
     seen = np.stack([h["seen"] for h in hooks]); expected = np.stack([h["expected"] for h in hooks])

@@ -21,7 +21,8 @@ import assoc_reference as AR
 import innovation_reference as IR
 import map_reference as MR
 from test_assoc_gpu import B, KS, SENTINEL, _config, _grid, _handle
-from test_gate_gpu import _Dev, _fixed_order_record, _same_bits
+from record_tree import MAX_ENTRY_8, fixed_order_record
+from test_gate_gpu import _Dev, _same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -158,7 +159,7 @@ def test_removal_is_np_delete_in_bits_and_the_steps_after_it_follow_the_oracle(S
     n2 = 3 + 2 * np.array([w["M"] for w in want])
     assert r["rec"][0] == (removed > 0).sum() and r["rec"][1] == removed.sum() and r["rec"][2] == (n2[removed > 0] ** 2).sum() and not r["rec"][3:].any()
     inst = np.zeros((B, 16)); inst[:, 0] = removed > 0; inst[:, 1] = removed; inst[:, 2] = np.where(removed > 0, n2.astype(np.float64) ** 2, 0.0)
-    assert _same_bits(_fixed_order_record(inst), r["rec"])
+    assert _same_bits(fixed_order_record(inst, MAX_ENTRY_8), r["rec"])
     by, prune_ms, total_ms = f.last_map_work()
     assert by == _model_bytes([st["M"] for st in before], removed, L_max, 4 if f32 else 8, False, False) and prune_ms == -1.0 and total_ms == -1.0
     seen, expected = f.map_track()

@@ -16,7 +16,8 @@ import pytest
 import assoc_reference as AR
 import innovation_reference as IR
 from test_assoc_gpu import B, KS, SENTINEL, _config, _grid, _handle
-from test_gate_gpu import _Dev, _fixed_order_record, _same_bits
+from record_tree import MAX_ENTRY_8, fixed_order_record
+from test_gate_gpu import _Dev, _same_bits
 from test_map_gpu import CLASSES, CLASS_IDS, S, hip, _clutter_log, _each, _grown, _items, _model_bytes, _raw, _same_state  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -119,7 +120,7 @@ def test_duplicates_and_the_merge_equal_the_host_hook_and_the_steps_after_follow
             for i in np.nonzero(partner[b] > np.arange(L_max))[0]:
                 assert int(before[b]["ids"][i]) in kept and int(before[b]["ids"][partner[b, i]]) not in kept, (what, b, "the kept id is ids[i]")
     inst = np.stack([h["rec"] for h in hooks])
-    assert _same_bits(_fixed_order_record(inst), r["rec"]), (what, r["rec"])
+    assert _same_bits(fixed_order_record(inst, MAX_ENTRY_8), r["rec"]), (what, r["rec"])
     assert r["rec"][0] == (merged > 0).sum() and r["rec"][1] == merged.sum() and r["rec"][3] == 0 and 0 < r["rec"][8] <= S.default_merge_config().gate_merge
     by, _, _ = f.last_merge_work()
     assert by == _merge_model_bytes(before, status, hooks, L_max, esz, False, True)
@@ -200,7 +201,7 @@ def test_a_map_of_more_than_256_landmarks(S, f32):
     r = f.map_merge()
     hooks = _hooks(S, before, status, L_max, f32)
     assert all(_same_state(f.get_state(b), hooks[b]) for b in range(nb)) and np.array_equal(r["n_merged"], (partner >= 0).sum(axis=1) // 2)
-    assert _same_bits(_fixed_order_record(np.stack([h["rec"] for h in hooks])), r["rec"])
+    assert _same_bits(fixed_order_record(np.stack([h["rec"] for h in hooks]), MAX_ENTRY_8), r["rec"])
     f.close()
 
 
@@ -241,7 +242,7 @@ def test_caller_pairs_with_entries_that_are_not_mutual_or_out_of_range(S, tmp_pa
     wrong = [b for b in range(B) if not _same_state(after[b], hooks[b])]
     assert not wrong, f"{len(wrong)} instance(s) differ from the hook's merged state: {wrong[:10]}"
     assert np.array_equal(r["n_merged"], [st["M"] - h["M"] for st, h in zip(before, hooks)])
-    assert _same_bits(_fixed_order_record(np.stack([h["rec"] for h in hooks])), r["rec"]) and r["rec"][2] > B // 2 and r["rec"][1] > B
+    assert _same_bits(fixed_order_record(np.stack([h["rec"] for h in hooks]), MAX_ENTRY_8), r["rec"]) and r["rec"][2] > B // 2 and r["rec"][1] > B
     seen, expected = f.map_track()
     assert all(np.array_equal(seen[b], hooks[b]["seen"]) and np.array_equal(expected[b], hooks[b]["expected"]) for b in range(B))
     raw1 = _items(_raw(f, tmp_path))

@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from record_tree import ALL_SUMS, fixed_order_record
 from test_gate_gpu import _Dev, _same_bits
 
 pytestmark = pytest.mark.gpu
@@ -109,24 +110,6 @@ def _sensor_rows(S, idless):
     return [groups[b % 16] for b in range(B)]
 
 
-def _sum_record(inst):
-    """The reduction of sense_reduce_kernel and sense_sum_kernel restated (every entry a sum): per 256 instances the shuffle tree of each
-    wavefront of 64 lanes, the four wavefronts in order, then the blocks in ascending order.  Instances past the batch contribute zeros."""
-    n = inst.shape[0]
-    blocks = (n + 255) // 256
-    pad = np.zeros((blocks * 256, 16)); pad[:n] = inst
-    rec = None
-    for blk in range(blocks):
-        part = None
-        for wv in range(4):
-            r = pad[blk * 256 + wv * 64: blk * 256 + (wv + 1) * 64].copy()
-            for off in (32, 16, 8, 4, 2, 1):
-                r = r + np.concatenate([r[off:], r[64 - off:]])
-            part = r[0] if part is None else part + r[0]
-        rec = part if rec is None else rec + part
-    return rec
-
-
 # ---- 5. the default row against slam_run_sim_each ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("L_max,f32", CLASSES, ids=CLASS_IDS)
 def test_default_row_is_the_simulator_run(S, W, hip, tmp_path, L_max, f32):
@@ -190,7 +173,7 @@ def test_faults_against_the_host_hook(S, W, L_max, f32):
             inst[b] = h["rec"]
             seen["short"] += h["count"] > ks
         assert not wrong, f"tick {tick}: {len(wrong)} instance(s) differ from the host hook (b, count dev/host): {wrong[:10]}"
-        want = _sum_record(inst)
+        want = fixed_order_record(inst, ALL_SUMS)
         assert _same_bits(want, out["rec"]), (tick, want, out["rec"])
         assert want[1] == len(PRE_FROZEN) and want[0] == B - len(PRE_FROZEN) and want[10] == 0 and want[11] == 0
         seen["spiked"] += want[5]; seen["clutter"] += want[6]; seen["missed"] += want[4]
@@ -430,7 +413,7 @@ def test_too_long_on_the_device_against_the_host_hook(S, W):
             assert SR.same(got, h), (ks, b, got["count"], h["count"])
             assert h["flags"] == (SR.TOO_LONG if counts[b] > 64 else 0) and h["rec"][3] == min(counts[b], 64), (b, h["flags"], h["rec"][3])
             inst[b] = h["rec"]
-        assert _same_bits(_sum_record(inst), out["rec"]) and out["rec"][2] == 4
+        assert _same_bits(fixed_order_record(inst, ALL_SUMS), out["rec"]) and out["rec"][2] == 4
         assert f.sense_commit()[10] == 0
     f.close()
 
