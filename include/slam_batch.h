@@ -1125,6 +1125,79 @@ int slam_fix_instance_host(double* x, double* P, int M, int L_max, int32_t statu
 int slam_fix_sense_instance_host(uint64_t seed, int64_t instance, uint32_t step, const double truth[3], const slam_fix_sensor* row, double fix[5],
                                  int32_t* kinds, int32_t* jumped);
 
+/* ---- map score: the estimated map against the true map WITHOUT ids (csrc/score_kernel.h) ---------------------------------------------------
+ * slam_consistency and the monitor's full evaluation look the landmark truth up through ids[j]; with landmark_id_is_known = 0 they report
+ * NO_TRUTH.  This call matches every estimated landmark of every instance of an SLAM_EKF_SLAM handle to the true map by position instead
+ * and reports what every SLAM paper reports: matched, duplicate and spurious landmarks, the map error, and the per-landmark and joint NEES
+ * under that matching.  Known or unknown ids, both storage types, every capacity up to 1000 landmarks, the shared map or the maps of
+ * slam_set_maps.  Computed on the GPU in fp64 arithmetic (unfused), whatever the storage type.
+ * Definitions, per instance; M is clamped to [0, L_max], Lb is the size of the instance's true map:
+ *   d2(j, r)   for slot j < M and true row r < Lb: dx = x[3+2j] - map[2r], dy = x[4+2j] - map[2r+1], d2 = dx dx + dy dy
+ *   row[j]     the r of least d2, ties to the lowest r; a d2 that is not finite never wins.  If no d2 is finite or the least exceeds
+ *              match_radius^2 (formed once on the host; d2 equal to it is inside): row[j] = -1 and the slot is SPURIOUS
+ *   role[j]    slam_score_role: among the slots that claim one true row the one of least d2 is MATCHED (ties to the lowest j), the others
+ *              are DUPLICATE; slots >= M are NONE with row = -1 and NaN values
+ *   lm_err[j]  sqrt(d2) of a MATCHED or DUPLICATE slot, NaN otherwise
+ *   lm_nees[j] of a MATCHED or DUPLICATE slot: the factorisation of slam_consistency on the slot's symmetrised 2 x 2 block with e = (dx, dy)
+ *              appended - a = P[i][i], b = (P[i+1][i] + P[i][i+1]) / 2, c = P[i+1][i+1], i = 3 + 2 j; s0 = sqrt(a), y0 = dx / s0, l = b / s0,
+ *              d = c - l l, y1 = (dy - y0 l) / sqrt(d), lm_nees = y0 y0 + y1 y1.  The pivot test is slam_consistency's (a and d > 0 and
+ *              finite, no floor); a failed test gives NaN and LM_NOT_PD.  NaN otherwise
+ *   n_matched, n_duplicate, n_spurious   the counts of the roles (their sum is M)
+ *   map_rms    sqrt((sum of d2 over the MATCHED slots, ascending j, one addition per slot) / n_matched), 0 over none
+ *   max_err    the largest lm_err over the MATCHED slots, 0 over none
+ *   nees_matched, dof_matched   with full = 1: e^T S^-1 e and 3 + 2 n_matched, e = (x - x_true, y - y_true, remainder(yaw - yaw_true, 2 pi),
+ *              then (dx, dy) of the MATCHED slots in ascending j) and S the principal submatrix of (P + P^T) / 2 on those rows: DUPLICATE
+ *              and SPURIOUS slots are marginalised out by dropping their rows.  The factorisation, its pivot test, its size classes, its
+ *              workspace and SLAM_CONSISTENCY_WS_BYTES are slam_consistency's; a failed pivot gives NaN and MATCHED_NOT_PD.  With known ids
+ *              and every slot MATCHED to the row of its id, nees_matched, map_rms and dof_matched have the bits of slam_consistency's
+ *              nees_full, map_rms and dof.  With full = 0: NaN and dof_matched = 0
+ *   flags      slam_score_flags
+ * A landmark coordinate that is not finite does not fail the instance: its slot is SPURIOUS.
+ * rec [16] (counts as doubles; a fixed summation order that depends on the batch size alone): 0 instances scored (not INSTANCE_FAILED),
+ *   1 failed, then over the scored ones 2 sum of M, 3 MATCHED, 4 DUPLICATE, 5 SPURIOUS slots, 6 sum of d2 over MATCHED, 7 largest lm_err over
+ *   MATCHED, 8 the finite lm_nees of MATCHED slots, 9 their sum, 10 how many are < lm_lo, 11 how many are > lm_hi, 12 the finite
+ *   nees_matched, 13 their sum, 14 the sum of dof_matched over those, 15 instances with at least one DUPLICATE or SPURIOUS slot.
+ * Any output pointer may be NULL; the per-instance outputs are [batch], the per-slot ones [batch][L_max].  Like slam_consistency the call
+ * runs the queued timesteps first, computes on the handle's stream, returns when the results are on the host, and CHANGES NOTHING: a
+ * checkpoint written before and after is byte-identical.  The values of an instance do not depend on the batch it sits in, on a second
+ * call or on the chunking of the workspace class.  Meaningful for the pose part only while the simulator steps the handle.
+ * Errors: SLAM_ERR_ARG (checked first, before the handle is looked at): match_radius NaN or <= 0 (+inf is allowed: nothing is SPURIOUS
+ *   for its distance), a band that is not finite or not ordered; NULL handle.  SLAM_ERR_UNSUPPORTED: the UKF kinds.  SLAM_ERR_STATE: before
+ *   slam_init; without a true map.
+ * Not covered: optimal (Hungarian) assignment or Mahalanobis matching (the matching is greedy per true row, in Euclidean distance); which
+ *   true rows were ever in view (the caller holds the origin logs of the simulator source; Lb - n_matched is what the call can say); the
+ *   UKF kinds, slam_multi_* and the pose graph; a *_run form or a stride inside the monitor (the call changes nothing, so a caller scores
+ *   between the chunks of any run); checkpoint state (there is none). */
+typedef struct slam_score_config {
+    double match_radius;   /* > 0, may be +inf (default): a slot farther than this from every true row is SPURIOUS */
+    double lm_lo, lm_hi;   /* band of record entries 10 / 11; default: the chi-square(2) quantiles slam_innovation_config_default uses */
+    int full;              /* 0: matching and per-landmark values only (default); 1: also nees_matched (a factorisation per instance) */
+} slam_score_config;
+enum slam_score_role { SLAM_SCORE_NONE = 0, SLAM_SCORE_MATCHED = 1, SLAM_SCORE_DUPLICATE = 2, SLAM_SCORE_SPURIOUS = 3 };
+enum slam_score_flags {
+    SLAM_SCORE_OK = 0,
+    SLAM_SCORE_MATCHED_NOT_PD = 1,     /* full = 1: a Cholesky pivot of the selected submatrix is <= 0 or not finite: nees_matched = NaN, the rest
+                                          is still reported */
+    SLAM_SCORE_LM_NOT_PD = 4,          /* the same for the 2 x 2 block of a MATCHED or DUPLICATE slot: that slot's lm_nees = NaN */
+    SLAM_SCORE_INSTANCE_FAILED = 8     /* as SLAM_CONSISTENCY_INSTANCE_FAILED: slam_status carries SLAM_INST_NONFINITE or SLAM_INST_WATCHDOG, or a
+                                          component of the pose error is not finite: every value NaN, counts and dof_matched 0, row = -1,
+                                          role NONE, no other bit */
+};
+int slam_score_config_default(slam_score_config* cfg);
+int slam_map_score(slam_handle* h, const slam_score_config* cfg /* NULL: defaults */, double rec[16], int32_t* n_matched, int32_t* n_duplicate,
+                   int32_t* n_spurious, double* map_rms, double* max_err, double* nees_matched, int32_t* dof_matched, int32_t* flags, int32_t* row,
+                   int32_t* role, double* lm_err, double* lm_nees);
+/* bytes the model says the last slam_map_score had to move (summed in integers on the device, outside the timed part: x, the 2 x 2 diagonal
+ * blocks of the slots with a row, the map once, M, status and truth, the outputs; with full = 1 also the selected elements of P and the
+ * list they are selected by - nothing else of P is read with full = 0) and its device time in ms (HIP events around its launches). */
+int slam_last_score_work(slam_handle* h, double* bytes, double* ms);
+/* TEST HOOK, not part of the filter interface: the scoring of ONE instance compiled for the HOST from csrc/score_kernel.h (the source the
+ * kernel compiles, no device needed).  x [3 + 2 M], P [n][n] row-major, 0 <= M <= L_max, truth [3], map [L][2], L >= 1; the outputs are the
+ * per-instance ones except nees_matched / dof_matched (single values) and the per-slot ones ([L_max] each); any may be NULL. */
+int slam_map_score_instance_host(const double* x, const double* P, int M, int L_max, int32_t status, const double truth[3], const double* map, int L,
+                                 int f32_storage, const slam_score_config* cfg, int32_t* n_matched, int32_t* n_duplicate, int32_t* n_spurious,
+                                 double* map_rms, double* max_err, int32_t* flags, int32_t* row, int32_t* role, double* lm_err, double* lm_nees);
+
 /* ---- closed loop: commands from each instance's own estimate (goal_pursuit_node.py:23-50, pure_pursuit.py:17-161) ---------------------
  * The entry points above run open loop: every command is fixed before the run.  The reference's default launch (sim_base.launch,
  * precompute_trajectory false) closes the loop instead: goal_pursuit_node computes each Command from the state the filter has just published.

@@ -327,6 +327,26 @@ public:
         check(slam_consistency(h_, c.nees_full.data(), c.nees_pose.data(), c.map_rms.data(), c.dof.data(), c.flags.data()));
         return c;
     }
+    // The estimated map of every instance matched to the true map by position, with or without ids, computed on the GPU (slam_map_score,
+    // include/slam_batch.h: definitions, slam_score_role, slam_score_flags, the record, what it does not cover).  Changes nothing.
+    // The per-slot vectors are [batch][L_max].
+    struct MapScore {
+        double rec[16];
+        std::vector<int32_t> n_matched, n_duplicate, n_spurious, dof_matched, flags, row, role;
+        std::vector<double> map_rms, max_err, nees_matched, lm_err, lm_nees;
+    };
+    MapScore mapScore(const slam_score_config* cfg = nullptr) {
+        need();
+        MapScore s;
+        const size_t B = (size_t)batch_, n = B * (size_t)L_max_;
+        s.n_matched.resize(B); s.n_duplicate.resize(B); s.n_spurious.resize(B); s.dof_matched.resize(B); s.flags.resize(B);
+        s.map_rms.resize(B); s.max_err.resize(B); s.nees_matched.resize(B);
+        s.row.resize(n); s.role.resize(n); s.lm_err.resize(n); s.lm_nees.resize(n);
+        check(slam_map_score(h_, cfg, s.rec, s.n_matched.data(), s.n_duplicate.data(), s.n_spurious.data(), s.map_rms.data(), s.max_err.data(),
+                             s.nees_matched.data(), s.dof_matched.data(), s.flags.data(), s.row.data(), s.role.data(), s.lm_err.data(),
+                             s.lm_nees.data()));
+        return s;
+    }
     slam_handle* handle() { return h_; }
     EKFState last_state;
 

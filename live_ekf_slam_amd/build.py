@@ -11,10 +11,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libslam_hip.so")
-SOURCES = ["ekf_kernel.hip", "ekf_big_kernel.hip", "ukf_kernel.hip", "ukf_big_kernel.hip", "consistency_kernel.hip", "monitor_kernel.hip", "record_kernel.hip", "innovation_kernel.hip", "gate_kernel.hip", "assoc_kernel.hip", "joint_kernel.hip", "map_kernel.hip", "merge_kernel.hip", "sense_kernel.hip", "fix_kernel.hip", "nav_kernel.hip", "pgs_kernel.hip", "pgs_capi.cpp", "pgs_capi_fix.cpp", "slam_capi.cpp", "capi_step.cpp", "capi_state.cpp", "capi_consistency.cpp", "capi_nav.cpp", "capi_monitor.cpp",
-           "capi_innovation.cpp", "capi_gate.cpp", "capi_assoc.cpp", "capi_joint.cpp", "capi_map.cpp", "capi_merge.cpp", "capi_sense.cpp", "capi_fix.cpp", "scenario_capi.cpp", "multi_capi.cpp"]
+SOURCES = ["ekf_kernel.hip", "ekf_big_kernel.hip", "ukf_kernel.hip", "ukf_big_kernel.hip", "consistency_kernel.hip", "monitor_kernel.hip", "record_kernel.hip", "innovation_kernel.hip", "gate_kernel.hip", "assoc_kernel.hip", "joint_kernel.hip", "map_kernel.hip", "merge_kernel.hip", "score_kernel.hip", "sense_kernel.hip", "fix_kernel.hip", "nav_kernel.hip", "pgs_kernel.hip", "pgs_capi.cpp", "pgs_capi_fix.cpp", "slam_capi.cpp", "capi_step.cpp", "capi_state.cpp", "capi_consistency.cpp", "capi_nav.cpp", "capi_monitor.cpp",
+           "capi_innovation.cpp", "capi_gate.cpp", "capi_assoc.cpp", "capi_joint.cpp", "capi_map.cpp", "capi_merge.cpp", "capi_score.cpp", "capi_sense.cpp", "capi_fix.cpp", "scenario_capi.cpp", "multi_capi.cpp"]
 HEADERS = ["ukf_kernel.h", "ekf_kernel.h", "ekf_kernel_impl.h", "ekf_model.h", "ekf_step_prestep.h", "ekf_step_control.h", "ekf_step_stream.h", "ekf_step_decoupled.h", "ekf_step_lockstep.h", "ekf_inst.hip", "sim_device.h", "noise_row.h", "slam_math.h", "slam_rng.h", "pgs_kernel.h", "pgs_seg_impl.h", "pgs_factors.h", "pgs_robust.h", "pgs_fix.h", "pgs_fix_phase.h", "pgs_handle.h", "pgs_graph.h", "pgs_linearize.h", "pgs_chain.h", "pgs_syrk.h", "pgs_chol.h",
-           "pgs_backsolve.h", "pgs_lm_control.h", "pgs_marginals.h", "consistency_kernel.h", "monitor_kernel.h", "record_kernel.h", "aux_device.h", "innovation_kernel.h", "gate_kernel.h", "assoc_kernel.h", "joint_kernel.h", "map_kernel.h", "merge_kernel.h", "sense_kernel.h", "fix_kernel.h", "nav_kernel.h",
+           "pgs_backsolve.h", "pgs_lm_control.h", "pgs_marginals.h", "consistency_kernel.h", "monitor_kernel.h", "record_kernel.h", "aux_device.h", "innovation_kernel.h", "gate_kernel.h", "assoc_kernel.h", "joint_kernel.h", "map_kernel.h", "merge_kernel.h", "score_kernel.h", "sense_kernel.h", "fix_kernel.h", "nav_kernel.h",
            "capi_internal.h", "slam_handle.h", "capi_run.h", "capi_filter.h", "capi_innovation.h", "capi_assoc.h", "capi_map.h", "capi_sense.h", "jacobi_schedule.h", "lds_attr.h", "../../include/slam_batch.h", "../../include/slam_pgs.h", "../../include/slam_scenario.hpp",
            "../../include/slam_filter.hpp", "../../include/slam_multi.h", "host/filter_driver.cpp", "host/config_parse.h", "host/stream_parse.h", "host/owned_buf.h", "host/noise_pack.h", "host/tick_chunks.h", "host/pgs_schedule.h",
            "host/pgs_limits.h"]

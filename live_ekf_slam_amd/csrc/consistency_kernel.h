@@ -26,11 +26,19 @@ struct ConsistencyParams {
     // the class beyond the LDS: packed triangles of the instances of one chunk, ws_stride doubles apart
     double* ws; size_t ws_stride;
     int32_t b0, count;      // the instances [b0, b0 + count) of this launch (set by launch_consistency)
+    // launch_consistency_selected only: the slots whose rows of S are factored, ascending, and the true row of each ([B][L_max] each, n_sel
+    // [B] entries in use); nees_full and dof are then nees_matched and dof_matched, flags is read (INSTANCE_FAILED as the list's writer
+    // decided it) and written, nees_pose and map_rms are not written, entries 12 - 14 of inst_rec [B][16] are
+    const int32_t* sel; const int32_t* sel_row; const int32_t* n_sel;
+    double* inst_rec;
 };
 
 // doubles of workspace ONE instance needs (0: the LDS classes, L_max <= 50)
 size_t consistency_ws_per_instance(int L_max);
 // All instances, in chunks of `chunk` (the workspace class; ws holds chunk * consistency_ws_per_instance doubles) on `stream`.
 hipError_t launch_consistency(ConsistencyParams p, int f32_storage, int chunk, hipStream_t stream);
+// The same factorisation on the principal submatrix of S that the pose and the listed slots select (slam_map_score: score_kernel.h
+// writes the list), with the landmark truth through the list; the classes, the workspace and the chunks are those of launch_consistency.
+hipError_t launch_consistency_selected(ConsistencyParams p, int f32_storage, int chunk, hipStream_t stream);
 
 }  // namespace slam

@@ -11,6 +11,10 @@
 // All arithmetic is fp64, whatever the storage type of P and x; sums run in a fixed order (no atomics on values), so an instance's
 // result does not depend on the batch, the chunk or the call.  Nothing the kernel indexes with is trusted: M is clamped to
 // [0, L_max], an id is compared with the instance's map size before the map is read.
+// The SEL variant (launch_consistency_selected, slam_map_score with full = 1) is the same factorisation on a principal submatrix: row i
+// of S is row src(i) of P, src = (0, 1, 2, then 3 + 2 s, 4 + 2 s for the slots s of the instance's list sel [n_sel], ascending), and the
+// landmark truth of list entry k is map[sel_row[k]]; score_kernel.hip wrote the list, decided INSTANCE_FAILED and summed map_rms.  It
+// is a compile-time variant (if constexpr): the instantiations behind slam_consistency contain none of it.
 #include "consistency_kernel.h"
 
 #include "../../include/slam_batch.h"
@@ -25,7 +29,7 @@ __device__ inline bool finite_d(double v) { return fabs(v) < __builtin_inf(); }
 
 // NMAX: largest n of the class; TPI threads per instance, IPW instances per workgroup; G lanes share one row of the trailing update
 // (TPI / G rows in flight); WS: the triangle lives in the workspace, else in LDS; ST: storage type of P and x.
-template <int NMAX, int TPI, int IPW, int G, bool WS, class ST>
+template <int NMAX, int TPI, int IPW, int G, bool WS, class ST, bool SEL = false>
 __global__ __launch_bounds__(TPI * IPW) void consistency_kernel(const ConsistencyParams p) {
     constexpr int TRI = (NMAX + 1) * (NMAX + 2) / 2;
     constexpr int NG = TPI / G;
@@ -42,20 +46,39 @@ __global__ __launch_bounds__(TPI * IPW) void consistency_kernel(const Consistenc
 
     int m = live ? p.M[b] : 0;
     m = m < 0 ? 0 : (m > p.L_max ? p.L_max : m);
+    int ld_n = 3 + 2 * m;                            // the n the instance's P is stored at
+    if constexpr (SEL) {                             // the selected slots: n_sel of the m (never more: the list has m places)
+        const int k = live ? p.n_sel[b] : 0;
+        m = k < 0 ? 0 : (k > m ? m : k);
+    }
     const int n = 3 + 2 * m;
-    const bool failed = live && (p.status[b] & (SLAM_INST_NONFINITE | SLAM_INST_WATCHDOG)) != 0;
+    const bool failed = live && (SEL ? (p.flags[b] & SLAM_CONSISTENCY_INSTANCE_FAILED) != 0
+                                     : (p.status[b] & (SLAM_INST_NONFINITE | SLAM_INST_WATCHDOG)) != 0);
     const ST* x = static_cast<const ST*>(p.x) + (size_t)b * p.xstride;
     const ST* P = static_cast<const ST*>(p.P) + (size_t)b * p.pstride;
-    const int ld = ekf_ld(n, (int)sizeof(ST));
+    const int ld = ekf_ld(SEL ? ld_n : n, (int)sizeof(ST));
+    const int32_t* const sel = SEL ? p.sel + (size_t)b * p.L_max : nullptr;
+    const int32_t* const sel_row = SEL ? p.sel_row + (size_t)b * p.L_max : nullptr;
+    // row i of S in the stored state (SEL: through the list; every entry is clamped into the instance's slots before it indexes)
+    auto src = [&](int i) -> int {
+        if constexpr (SEL) {
+            if (i < 3) return i;
+            int s = sel[(i - 3) >> 1];
+            s = s < 0 ? 0 : (s > (ld_n - 3) / 2 - 1 ? (ld_n - 3) / 2 - 1 : s);
+            return 3 + 2 * s + ((i - 3) & 1);
+        } else {
+            return i;
+        }
+    };
     const double* map = p.map_each ? p.map_each + (size_t)b * p.map_stride * 2 : p.map;
     int Lb = p.map_each ? p.L_each[b] : p.L;
     if (p.map_each && Lb > p.map_stride) Lb = p.map_stride;
     const int32_t* ids = p.ids + (size_t)b * p.L_max;
 
     // ---- which landmarks have a truth ----
-    if (t == 0) s_flag[inst] = (!p.id_known && m > 0) ? SLAM_CONSISTENCY_NO_TRUTH : 0;
+    if (t == 0) s_flag[inst] = (!SEL && !p.id_known && m > 0) ? SLAM_CONSISTENCY_NO_TRUTH : 0;
     __syncthreads();
-    if (live && !failed && p.id_known)
+    if (!SEL && live && !failed && p.id_known)
         for (int j = t; j < m; j += TPI)
             if (ids[j] < 0 || ids[j] >= Lb) atomicOr(&s_flag[inst], SLAM_CONSISTENCY_NO_TRUTH);
     __syncthreads();
@@ -71,6 +94,9 @@ __global__ __launch_bounds__(TPI * IPW) void consistency_kernel(const Consistenc
         if (i < 3) {
             e = (double)x[i] - p.truth[(size_t)b * 3 + i];
             if (i == 2) e = wrap2pi(e);
+        } else if constexpr (SEL) {                  // (a row outside the instance's map reads row 0: the list's writer never gives one)
+            const int r = sel_row[(i - 3) >> 1];
+            e = (double)x[src(i)] - map[2 * (r < 0 || r >= Lb ? 0 : r) + ((i - 3) & 1)];
         } else {
             e = (double)x[i] - map[2 * ids[(i - 3) >> 1] + ((i - 3) & 1)];
         }
@@ -78,18 +104,18 @@ __global__ __launch_bounds__(TPI * IPW) void consistency_kernel(const Consistenc
         E[i] = e;
     }
     for (int i = g; i < nf; i += NG)
-        for (int j = l; j <= i; j += G) A[i * (i + 1) / 2 + j] = (double)P[(size_t)i * ld + j];
+        for (int j = l; j <= i; j += G) A[i * (i + 1) / 2 + j] = (double)P[(size_t)src(i) * ld + src(j)];
     __syncthreads();
     // the upper triangle, read along its rows like the lower one: S_ji = (P_ji + P_ij) / 2, each element owned by one thread
     for (int i = g; i < nf; i += NG)
         for (int j = i + 1 + l; j < nf; j += G) {
             double* a = A + j * (j + 1) / 2 + i;
-            *a = 0.5 * (*a + (double)P[(size_t)i * ld + j]);
+            *a = 0.5 * (*a + (double)P[(size_t)src(i) * ld + src(j)]);
         }
     __syncthreads();
     // the landmark part of e, before the factorisation updates row nf in place: slot order, one thread
     double rms = 0.0;
-    if (t == 0 && nf > 3) {
+    if (!SEL && t == 0 && nf > 3) {
         for (int j = 3; j < nf; j += 2) rms += E[j] * E[j] + E[j + 1] * E[j + 1];
         rms = sqrt(rms / (double)m);
     }
@@ -138,6 +164,18 @@ __global__ __launch_bounds__(TPI * IPW) void consistency_kernel(const Consistenc
     }
 
     if (!live || t != 0) return;
+    if constexpr (SEL) {                             // nees_matched, dof_matched, MATCHED_NOT_PD and the record entries 12 - 14
+        int fl = p.flags[b];
+        const bool dead = failed || (s_flag[inst] & SLAM_CONSISTENCY_INSTANCE_FAILED) != 0;
+        const bool fin = !dead && !bad_full && finite_d(acc);
+        if (!dead && bad_full) fl |= SLAM_CONSISTENCY_FULL_NOT_PD;
+        p.nees_full[b] = (dead || bad_full) ? __builtin_nan("") : acc;
+        p.dof[b] = dead ? 0 : n;
+        p.flags[b] = fl;
+        double* const r = p.inst_rec + (size_t)b * 16;
+        r[12] = fin ? 1.0 : 0.0; r[13] = fin ? acc : 0.0; r[14] = fin ? (double)n : 0.0;
+        return;
+    }
     int fl = s_flag[inst];
     if (failed) fl = SLAM_CONSISTENCY_INSTANCE_FAILED;
     const double nan = __builtin_nan("");
@@ -157,12 +195,27 @@ __global__ __launch_bounds__(TPI * IPW) void consistency_kernel(const Consistenc
     p.nees_full[b] = out_full; p.nees_pose[b] = out_pose; p.map_rms[b] = rms; p.dof[b] = n; p.flags[b] = fl;
 }
 
-template <int NMAX, int TPI, int IPW, int G, bool WS>
+template <int NMAX, int TPI, int IPW, int G, bool WS, bool SEL = false>
 hipError_t launch_class(const ConsistencyParams& p, int f32, hipStream_t stream) {
     const dim3 grid((p.count + IPW - 1) / IPW), block(TPI * IPW);
-    if (f32) hipLaunchKernelGGL((consistency_kernel<NMAX, TPI, IPW, G, WS, float>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((consistency_kernel<NMAX, TPI, IPW, G, WS, double>), grid, block, 0, stream, p);
+    if (f32) hipLaunchKernelGGL((consistency_kernel<NMAX, TPI, IPW, G, WS, float, SEL>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((consistency_kernel<NMAX, TPI, IPW, G, WS, double, SEL>), grid, block, 0, stream, p);
     return hipGetLastError();
+}
+
+// the classes of launch_consistency, for either variant
+template <bool SEL>
+hipError_t launch_classes(ConsistencyParams p, int f32, int chunk, hipStream_t stream) {
+    if (p.L_max > kEkfMaxLandmarks || p.B <= 0) return hipErrorInvalidValue;
+    if (p.L_max <= 20) { p.b0 = 0; p.count = p.B; return launch_class<43, 64, 4, 16, false, SEL>(p, f32, stream); }
+    if (p.L_max <= 50) { p.b0 = 0; p.count = p.B; return launch_class<103, 256, 1, 64, false, SEL>(p, f32, stream); }
+    if (!p.ws || chunk <= 0 || p.ws_stride < consistency_ws_per_instance(p.L_max)) return hipErrorInvalidValue;
+    for (int b0 = 0; b0 < p.B; b0 += chunk) {   // (launches on one stream: the next chunk reuses the workspace after the last one is done)
+        p.b0 = b0; p.count = p.B - b0 < chunk ? p.B - b0 : chunk;
+        const hipError_t e = launch_class<3 + 2 * kEkfMaxLandmarks, 1024, 1, 64, true, SEL>(p, f32, stream);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 }  // namespace
@@ -173,17 +226,11 @@ size_t consistency_ws_per_instance(int L_max) {
     return (n + 1) * (n + 2) / 2;
 }
 
-hipError_t launch_consistency(ConsistencyParams p, int f32, int chunk, hipStream_t stream) {
-    if (p.L_max > kEkfMaxLandmarks || p.B <= 0) return hipErrorInvalidValue;
-    if (p.L_max <= 20) { p.b0 = 0; p.count = p.B; return launch_class<43, 64, 4, 16, false>(p, f32, stream); }
-    if (p.L_max <= 50) { p.b0 = 0; p.count = p.B; return launch_class<103, 256, 1, 64, false>(p, f32, stream); }
-    if (!p.ws || chunk <= 0 || p.ws_stride < consistency_ws_per_instance(p.L_max)) return hipErrorInvalidValue;
-    for (int b0 = 0; b0 < p.B; b0 += chunk) {   // (launches on one stream: the next chunk reuses the workspace after the last one is done)
-        p.b0 = b0; p.count = p.B - b0 < chunk ? p.B - b0 : chunk;
-        const hipError_t e = launch_class<3 + 2 * kEkfMaxLandmarks, 1024, 1, 64, true>(p, f32, stream);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+hipError_t launch_consistency(ConsistencyParams p, int f32, int chunk, hipStream_t stream) { return launch_classes<false>(p, f32, chunk, stream); }
+
+hipError_t launch_consistency_selected(ConsistencyParams p, int f32, int chunk, hipStream_t stream) {
+    if (!p.sel || !p.sel_row || !p.n_sel || !p.inst_rec || !p.flags || !p.nees_full || !p.dof) return hipErrorInvalidValue;
+    return launch_classes<true>(p, f32, chunk, stream);
 }
 
 }  // namespace slam

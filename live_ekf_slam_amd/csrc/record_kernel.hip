@@ -48,9 +48,10 @@ hipError_t launch_record_total(const double* partials, int blocks, double* rec, 
 }
 
 // the masks in use: entry 8 a maximum (innovation, gate, association, joint association, map, merge); every entry a sum (sense, fix);
-// entries 6 and 8 maxima (the monitor, whose kernel runs the tree itself)
+// entry 7 a maximum (score); entries 6 and 8 maxima (the monitor, whose kernel runs the tree itself)
 template hipError_t launch_record_reduce<1u << 8>(const double*, int, double*, double*, hipStream_t);
 template hipError_t launch_record_reduce<0u>(const double*, int, double*, double*, hipStream_t);
+template hipError_t launch_record_reduce<1u << 7>(const double*, int, double*, double*, hipStream_t);
 template hipError_t launch_record_total<(1u << 6) | (1u << 8)>(const double*, int, double*, hipStream_t);
 
 }  // namespace slam

@@ -1,7 +1,7 @@
 // slam_handle.h — the handle of the filter ABI (include/slam_batch.h) and the host helpers that more than one of its translation units
 // uses (slam_capi.cpp: create / configure / init; capi_step.cpp: the steps and their queue; capi_state.cpp: reading the state back;
 // capi_consistency.cpp, capi_nav.cpp, capi_monitor.cpp, capi_innovation.cpp, capi_gate.cpp, capi_assoc.cpp, capi_joint.cpp, capi_map.cpp,
-// capi_merge.cpp, capi_sense.cpp, capi_fix.cpp: one feature each; capi_run.h: what the per-tick runs share; capi_filter.h: what the features that filter a
+// capi_merge.cpp, capi_score.cpp, capi_sense.cpp, capi_fix.cpp: one feature each; capi_run.h: what the per-tick runs share; capi_filter.h: what the features that filter a
 // message before the step share).  Not installed, not part of the ABI: the standing of capi_internal.h.
 #pragma once
 #include "../../include/slam_batch.h"
@@ -137,6 +137,14 @@ struct slam_handle {
         DevBuf<double> dcons, dcons_ws; DevBuf<int32_t> dconsi;
         double cons_bytes = 0.0, cons_ms = -1.0;
     } cons;
+    // slam_map_score: [3][B] map_rms, max_err, nees_matched and [6][B] n_matched, n_duplicate, n_spurious, dof_matched, flags, slots with a
+    // row on the device; [2][B][L_max] lm_err, lm_nees and [4][B][L_max] row, role, the list of MATCHED slots and their true rows; the
+    // per-instance records [B][16], their partial records and the record; the two sums of the traffic model, what the last call read from
+    // them and its device time.  The factorisation of full = 1 uses the workspace of `cons`.
+    struct SLAM_HANDLE_BLOCK Score {
+        DevBuf<double> dval, dslot, dinst, dpart, drec; DevBuf<int32_t> dint, dsloti; DevBuf<unsigned long long> dwork;
+        double bytes = 0.0, ms = -1.0;
+    } score;
     // slam_nav_*: the path (shared [P][2], or [B][stride][2] with [B] lengths), the controller state of every instance, the command log
     // of one chunk of ticks, ticks since the state was reset and the device times of the last slam_nav_run
     struct Nav {
